@@ -1,15 +1,21 @@
 #!/usr/bin/env python
 """bench.py -- ICP iterations/s, 100k-point scan vs 1M-point map (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--chain p2p|p2plane|docs_knn6] [--no-extras] [--no-cpu]
+    python bench.py --gpus N --steps K --warmup W [--chain p2p|p2plane|docs_knn6] [--dump-outputs DIR]
+                    [--full [--no-extras] [--no-cpu]]
 
 One "step" is one registration of the hot path in throughput mode: a fixed 20 ICP iterations
 (Counter checker only) of one synthetic 100k-point scan against the 1M-point map,
 with the scan already resident in HBM.  value = ICP iterations executed by all ranks / wall time
 (max over ranks, barrier + device sync on both sides).  Ranks hold a replica of the map and their own
 scan (independent seeds): the path shards across scans with no data-path collective => weak scaling.
+Exactly K steps are timed (--min-seconds > 0 repeats the K-step block instead and reports the median).
 
-Extra objects on the JSON line (rank 0):
+A plain run sets up, warms up, times the K steps and prints the headline line.  --dump-outputs DIR
+also writes what the last timed step returned (the 4x4 corrections, float32 .npy; every input is
+seeded, so two builds can be compared output for output).
+
+With --full, extra objects on the JSON line (rank 0):
   roofline     -- the NN kernel of the headline workload: algorithmic bytes per launch (N*16 query read +
                   M*16 map read + N*8 result write) / mean launch duration measured with HIP
                   events on the library's stream (profile mode), against the 8 TB/s HBM peak.
@@ -23,6 +29,7 @@ Extra objects on the JSON line (rank 0):
                   bounded sample of the same workload.
   libpointmatcher -- "present" when oracle/_ref/liboracle_pm.so (the real PM::ICPSequence, `make -C oracle oracle_pm`)
                   exists and was used for pose_err_vs_libpointmatcher; "absent" otherwise.
+  merge_epoch  -- (N > 1) one map-growth epoch through the library's RCCL communicator, after the timed region.
 """
 import argparse
 import json
@@ -259,14 +266,15 @@ def circle_scans(pkg, n_scans, n_points, scale, rank, radius=20.0):
     return out
 
 
-def config5_stream(np, torch, pkg, dev, d_map, d_nrm, d_scans, chain, min_dist, comm, barrier, normals_knn=0, cell_size=20.0):
+def config5_stream(np, torch, pkg, dev, d_map, d_nrm, d_scans, chain, min_dist, comm, barrier, normals_knn=0, cell_size=20.0, outputs=None):
     """One rank's part of BASELINE config 5: every scan is registered against the shared map (Counter 40 + Differential: what
     Mapper::processInput runs) and followed by ONE map-growth epoch (icpmi_staged_merge_allgather: PointDistance accept against the
     resident map, all-gather of the accepted points, rank-ordered merge, append, incremental index insert on every replica; r6: the merged
     set binned into the mapper's 20 m cells on the device and appended to the replica's cell log, icpmi_staged_bin_cells -- Map.cpp:206-229 /
     RAMCellManager.cpp:13-16) -- registration AND epoch inside the timed region.  normals_knn > 0 (a point-to-plane replica): the epoch also
     recomputes the map's normals, SurfaceNormalDataPointsFilter over the grown map as Map.cpp:524 applies it on every update.
-    comm: None (single rank), ("rccl", id, world, rank) or ("loopback", R, shift)."""
+    comm: None (single rank), ("rccl", id, world, rank) or ("loopback", R, shift).  outputs: a dict that receives what the last scan's
+    registration and epoch returned (--dump-outputs)."""
     import os as _os
     icp = pkg.ICPSequence(device=dev, max_iterations=40, use_differential=1, **chain)
     assert icp.setMapDev(d_map.data_ptr(), d_map.shape[0], d_nrm.data_ptr() if d_nrm is not None else None)
@@ -300,6 +308,8 @@ def config5_stream(np, torch, pkg, dev, d_map, d_nrm, d_scans, chain, min_dist, 
         cells_binned.append(int(ijk.shape[0]))
     barrier()
     elapsed = time.perf_counter() - t0
+    if outputs is not None:
+        outputs.update(correction=corr, epoch_counts=np.array([mine, app, new_m]), cells_ijk=ijk, cells_offset=_off, cells_count=_cnt)
     cr, cme, ckind = icp.commInfo()
     dbg = icp.debugCounters()
     fast_ep, slow_ep = int(dbg[14]), int(dbg[15])
@@ -320,6 +330,16 @@ def config5_stream(np, torch, pkg, dev, d_map, d_nrm, d_scans, chain, min_dist, 
         icp.commDestroy()
     del icp
     return res
+
+
+def dump_outputs(np, out_dir, arrays, rank):
+    """--dump-outputs: one DIR/<name>.npy per array (float32 stays float32, everything else float64); ranks other than 0 of a
+    multi-GPU run add _rank<r> to the name."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        a = a.astype(np.float32 if a.dtype == np.float32 else np.float64)
+        np.save(os.path.join(out_dir, (name if rank == 0 else f"{name}_rank{rank}") + ".npy"), a)
 
 
 def dry_launch(args):
@@ -350,7 +370,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)  # 0.2 s of timed region at ~1 ms per registration: long enough for an outside sampler to see
-    ap.add_argument("--min-seconds", type=float, default=1.0, help="repeat the timed --steps block until this much wall time has passed (median block reported)")
+    ap.add_argument("--min-seconds", type=float, default=0.0, help="repeat the timed --steps block until this much wall time has passed (median block reported)")
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--chain", default="p2p", choices=list(CHAINS))
     ap.add_argument("--map-points", type=int, default=M_MAP)
@@ -361,8 +381,12 @@ def main():
                     help="map normals of the point-to-plane chains: the scene's analytic ones, or SurfaceNormalDataPointsFilter{knn: 10} "
                          "run on the map through icpmi_surface_normals (BASELINE config 3)")
     ap.add_argument("--batch", type=int, default=0, help="headline through icpmi_register_batch_dev with this many readings (0: single registration)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
-    ap.add_argument("--no-extras", action="store_true", help="skip the `chains` object (configs 3 / 5 and the batch of 8)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also measure and check everything else: roofline, pose errors, the other configurations "
+                         "(`chains`), cpu_baseline and, for N > 1, the merge epoch")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step returned as DIR/<name>.npy")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the cpu_baseline leg")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip the `chains` object (configs 3 / 5 and the batch of 8)")
     ap.add_argument("--cpu-iters", type=int, default=10, help="iterations of the single-threaded cpu_baseline leg")
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="CPU work of the multi-threaded cpu_baseline leg")
     ap.add_argument("--workload", default="registration", choices=["registration", "config5"],
@@ -441,7 +465,10 @@ def main():
             box = [pkg.ICPSequence.commUniqueId() if rank == 0 else None]
             dist.broadcast_object_list(box, src=0)
             comm = ("rccl", box[0], world, rank)
-        res = config5_stream(np, torch, pkg, dev, d_map, d_nrm, d_scans, chain, 0.15, comm, barrier, normals_knn=args.epoch_normals_knn)
+        last = {}
+        res = config5_stream(np, torch, pkg, dev, d_map, d_nrm, d_scans, chain, 0.15, comm, barrier, normals_knn=args.epoch_normals_knn, outputs=last)
+        if args.dump_outputs:
+            dump_outputs(np, args.dump_outputs, last, rank)
         el = torch.tensor([res["elapsed_s"], float(res["iterations"])], dtype=torch.float64, device="cuda")
         each = [torch.zeros_like(el) for _ in range(world)]
         if use_pg:
@@ -489,31 +516,33 @@ def main():
     assert icp.setMapDev(d_map.data_ptr(), d_map.shape[0], d_nrm.data_ptr())
     set_map_ms = (time.perf_counter() - t0) * 1e3          # first call on this handle: includes every allocation
     warm = []
-    for _ in range(5):                                      # what Map::updateLocalPointCloud pays from the second update on
+    for _ in range(5 if args.full else 0):                  # what Map::updateLocalPointCloud pays from the second update on
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         assert icp.setMapDev(d_map.data_ptr(), d_map.shape[0], d_nrm.data_ptr())
         warm.append((time.perf_counter() - t0) * 1e3)
-    set_map_warm_ms = statistics.median(warm)
 
     batch_scans = None
     if args.batch > 1:
         batch_scans = [d_scan] + [torch.from_numpy(pkg.synth.make_scene(m=8, n=args.scan_points, seed_scan=43 + 1000 * rank + 7 * b, scale=args.scale)["scan"]).cuda()
                                   for b in range(1, args.batch)]
 
+    last_batch = []
+
     def step():
         if batch_scans is not None:
             Ts, _, status = icp.registerBatchDev([d.data_ptr() for d in batch_scans], [d.shape[0] for d in batch_scans], fixed_iterations=ITERS_PER_STEP)
             assert not any(status), status
+            last_batch[:] = Ts
             return Ts[0]
         return icp.registerDev(d_scan.data_ptr(), d_scan.shape[0], fixed_iterations=ITERS_PER_STEP)
 
     for _ in range(args.warmup):
         step()
 
-    # The contract's timed region: EXACTLY --steps steps between two barriers.  20 steps are 17 ms here -- too short for the driver's own
-    # clock and GPU-busy sampler to see -- so the block is REPEATED until a second of wall time has gone by (every
-    # block bracketed the same way), and the line reports the MEDIAN block; `blocks` says how many, `block_ms` their spread.
+    # The contract's timed region: EXACTLY --steps steps between two barriers, once.  --min-seconds S > 0 REPEATS the block until S seconds
+    # of wall time have gone by (every block bracketed the same way; for an outside sampler that needs a longer window),
+    # and the line reports the MEDIAN block; `blocks` says how many, `block_ms` their spread.
     def timed_block():
         barrier()
         t0 = time.perf_counter()
@@ -554,13 +583,15 @@ def main():
     readings = max(args.batch, 1)
     iters_total = world * args.steps * ITERS_PER_STEP * readings
     value = iters_total / elapsed
+    if args.dump_outputs:   # the last step of the last block: with --min-seconds 0 the one timed block
+        dump_outputs(np, args.dump_outputs, {"correction": np.stack(last_batch) if batch_scans is not None else blocks[-1]["T"]}, rank)
 
     # ---- the one exchange of the multi-GPU path, outside the timed region: a map-growth epoch through the library's own RCCL
     # communicator (icpmi_staged_merge_allgather: accepted points compacted, all-gathered on the handle's stream, merged in rank
     # order and appended on the device).  Every rank must take the same decisions, or the collective would hang: agree first.
     merge = None
     merge_hung = False
-    if use_pg:
+    if use_pg and args.full:
         # On a watchdog: a collective that never completes (a rank lost, an RCCL transport problem between two GPUs) must not
         # take the headline measured above with it -- after MERGE_TIMEOUT_S the line is printed without the epoch and every
         # rank leaves through os._exit.
@@ -634,21 +665,24 @@ def main():
     }
 
     if rank == 0:
-        gi = icp.gridInfo()
         out["per_rank_value"] = per_rank_value
-        if merge is not None:
-            out["merge_epoch"] = merge
         out["step_ms"] = step_stats(per_step)
         out["blocks"] = len(blocks)
         out["block_ms"] = step_stats([b["elapsed"] * 1e3 for b in blocks])
         out["timed_wall_s"] = sum(b["elapsed"] for b in blocks)
         out["build"] = pkg._capi.load().icpmi_build_info().decode()
-        out["device_loop_ms_per_step"] = loop_ms / args.steps
-        out["set_map_ms"] = set_map_ms
-        out["set_map_warm_ms"] = set_map_warm_ms
         if normals_ms is not None:
             out["surface_normals_ms"] = normals_ms
             out["config"]["map_normals"] = "SurfaceNormalDataPointsFilter knn 10 (icpmi_surface_normals, host pointers)"
+
+    # ---- --full: everything beyond the headline ----
+    if rank == 0 and args.full:
+        gi = icp.gridInfo()
+        if merge is not None:
+            out["merge_epoch"] = merge
+        out["device_loop_ms_per_step"] = loop_ms / args.steps
+        out["set_map_ms"] = set_map_ms
+        out["set_map_warm_ms"] = statistics.median(warm)
         out["grid"] = gi
         gt_t, gt_r = pkg.synth.pose_error(T, sc["T_gt"])
         out["pose_err_vs_ground_truth"] = {"m": gt_t, "rad": gt_r,
@@ -959,6 +993,7 @@ def main():
                     out["pose_err_vs_libpointmatcher"] = {"m": pt, "rad": pr}
                 except Exception as e:
                     out["pose_err_vs_libpointmatcher"] = {"error": repr(e)}
+    if rank == 0:
         sys.stdout.flush()
         os.write(real_stdout, (json.dumps(out) + "\n").encode())
     if use_pg:

@@ -1,12 +1,13 @@
 #!/bin/bash
 # round-2 counter collection on HEAD: FETCH / WRITE / TCC / SQ for the NN kernel on every benchmark chain, the 10 M map and the batch
 cd "$GRAFT_REPO_ROOT"; R=$GRAFT_REPO_ROOT/gpurun_out/r2pmc; rm -rf $R; mkdir -p $R
+ROOT=$PWD
 cd /tmp && export TMPDIR=/tmp
 pmc() { # name, counters..., -- command
   local name=$1; shift; local ctr=(); while [ "$1" != "--" ]; do ctr+=("$1"); shift; done; shift
   timeout 600 rocprofv3 --pmc "${ctr[@]}" --output-format csv -d $R/$name -- "$@" > /dev/null 2>$R/$(echo $name | tr / _).err
 }
-B="python $GRAFT_REPO_ROOT/bench.py --no-cpu --no-extras --steps 3 --warmup 1"
+B="python $ROOT/bench.py --full --no-cpu --no-extras --steps 3 --warmup 1"
 pmc calib/fetch FETCH_SIZE -- $GRAFT_REPO_ROOT/scripts/pmc_calib.bin
 pmc calib/write WRITE_SIZE -- $GRAFT_REPO_ROOT/scripts/pmc_calib.bin
 for wl in "p2p:--chain p2p" "p2plane:--chain p2plane" "knn6:--chain docs_knn6" "map10M:--chain p2p --map-points 10000000 --scale 3.16" "batch8:--chain p2p --batch 8"; do

@@ -1,8 +1,9 @@
 #!/bin/bash
 # usage: pmc_nn.sh <tag> [ENV=val ...] -- SQ counters of the NN kernel of a short p2p bench run (separate --pmc passes, no trace domains)
 cd "$GRAFT_REPO_ROOT"; R=$GRAFT_REPO_ROOT/gpurun_out/r3/pmc_$1; rm -rf $R; mkdir -p $R; tag=$1; shift
+ROOT=$PWD
 cd /tmp && export TMPDIR=/tmp
-B="python $GRAFT_REPO_ROOT/bench.py --no-cpu --no-extras --steps 3 --warmup 1 --chain ${CHAIN:-p2p}"
+B="python $ROOT/bench.py --full --no-cpu --no-extras --steps 3 --warmup 1 --chain ${CHAIN:-p2p}"
 i=0
 for set in "SQ_WAVES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_BUSY_CYCLES" "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_SMEM SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA" "SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS SQ_ACTIVE_INST_VMEM SQ_INSTS_BRANCH" "FETCH_SIZE WRITE_SIZE TCC_HIT_sum TCC_MISS_sum" "TCP_TOTAL_CACHE_ACCESSES_sum TCP_TCC_READ_REQ_sum TCP_TOTAL_ACCESSES_sum"; do
   i=$((i+1))

@@ -2,10 +2,11 @@
 # Round-3 counter collection: FETCH / WRITE / TCC / SQ for the NN kernel on every benchmark chain, the 10 M map and the batch; every
 # --pmc set in its own rocprofv3 run, no trace domains.  Writes gpurun_out/r3pmc/summary.json and gpurun_out/r3pmc/nn_traffic.json.
 cd "$GRAFT_REPO_ROOT"; R=$GRAFT_REPO_ROOT/gpurun_out/r3pmc; rm -rf $R; mkdir -p $R
+ROOT=$PWD
 cd /tmp && export TMPDIR=/tmp
 pmc() { local name=$1; shift; local ctr=(); while [ "$1" != "--" ]; do ctr+=("$1"); shift; done; shift
   timeout 600 rocprofv3 --pmc "${ctr[@]}" --output-format csv -d $R/$name -- "$@" > /dev/null 2>$R/$(echo $name | tr / _).err; }
-B="python $GRAFT_REPO_ROOT/bench.py --no-cpu --no-extras --steps 3 --warmup 1"
+B="python $ROOT/bench.py --full --no-cpu --no-extras --steps 3 --warmup 1"
 pmc calib/fetch FETCH_SIZE -- $GRAFT_REPO_ROOT/scripts/pmc_calib.bin
 pmc calib/write WRITE_SIZE -- $GRAFT_REPO_ROOT/scripts/pmc_calib.bin
 for wl in "p2p:--chain p2p" "p2plane:--chain p2plane" "knn6:--chain docs_knn6" "map10M:--chain p2p --map-points 10000000 --scale 3.16" "batch8:--chain p2p --batch 8"; do
@@ -23,7 +24,7 @@ cd $GRAFT_REPO_ROOT && python scripts/pmc_collect.py gpurun_out/r3pmc > gpurun_o
 python - <<'PY'
 import json
 d = json.load(open("gpurun_out/r3pmc/summary.json"))
-out = {"source": "profiles/r3_pmc_summary.json (scripts/r3_pmc.sh: rocprofv3 --pmc FETCH_SIZE, --pmc WRITE_SIZE, TCC, TCP and SQ sets, each in its own pass, no trace domains; `python bench.py --no-cpu --no-extras --steps 3 --warmup 1` per workload)",
+out = {"source": "profiles/r3_pmc_summary.json (scripts/r3_pmc.sh: rocprofv3 --pmc FETCH_SIZE, --pmc WRITE_SIZE, TCC, TCP and SQ sets, each in its own pass, no trace domains; `python bench.py --full --no-cpu --no-extras --steps 3 --warmup 1` per workload)",
        "calibration": d.get("factors_used"),
        "per_launch": "average over the 20 NN launches of a registration (nn1_wg_kernel for k = 1; knn 6: nnk_wg_kernel, 18 of the 20 launches -- the two nnk_ml_kernel launches of iterations 0 and 1 are NOT in this figure); the bench's roofline.avg_launch_us is the same average",
        "l2_hit_rate": {}, "wave": {}}

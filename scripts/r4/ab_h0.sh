@@ -6,8 +6,8 @@ cd /tmp && export TMPDIR=/tmp
 for h0 in 1 0; do
   for chain in p2p p2plane; do
     export ICPMI_NN_FUSE_HIST0=$h0
-    python $R/bench.py --no-cpu --no-extras --chain $chain 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('fuse_h0=$h0 $chain', d['value'], d['ms_per_step'], d['roofline']['avg_launch_us'])"
-    timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/prof_${chain}_$h0 -o t -- python $R/bench.py --no-cpu --no-extras --chain $chain > /dev/null 2>&1
+    python $R/bench.py --full --no-cpu --no-extras --chain $chain 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('fuse_h0=$h0 $chain', d['value'], d['ms_per_step'], d['roofline']['avg_launch_us'])"
+    timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/prof_${chain}_$h0 -o t -- python $R/bench.py --full --no-cpu --no-extras --chain $chain > /dev/null 2>&1
     f=$(find $R/$O/prof_${chain}_$h0 -name "*kernel_stats.csv" | head -1); python $R/scripts/kstats.py $f 2>/dev/null | head -7
   done
 done

@@ -3,7 +3,7 @@
 cd "$GRAFT_REPO_ROOT"; O=gpurun_out/abenv; mkdir -p $O
 one() { # label, env...
   local lab=$1; shift
-  local v=$(env "$@" python bench.py --no-cpu --no-extras 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(round(d['value'],1), round(d['roofline']['avg_launch_us'],2))")
+  local v=$(env "$@" python bench.py --full --no-cpu --no-extras 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(round(d['value'],1), round(d['roofline']['avg_launch_us'],2))")
   local c=$(env "$@" python scripts/r3/checked_loop_bench.py 2>/dev/null | grep "p2plane" | sed 's/.*p2plane: \([0-9.]*\) ms.*/\1/')
   echo "$lab : headline it/s, NN us = $v ; checked p2plane ms = $c" | tee -a $O/ab.txt
 }

@@ -1,7 +1,7 @@
 #!/bin/bash
 # the speculative level 0 of the k > 1 loop (ICPMI_SEL_WIN) and the pair sums' skipped gathers (ICPMI_ACC_SKIP: built for this A/B, no gain, removed afterwards -- the switch is a no-op in the tree), one call
 cd "$GRAFT_REPO_ROOT"
-one() { env "$@" python bench.py --no-cpu --no-extras --chain "$CH" 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('   $CH', round(d['value']), 'it/s  ms_per_step', round(d['ms_per_step'],4))"; }
+one() { env "$@" python bench.py --full --no-cpu --no-extras --chain "$CH" 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('   $CH', round(d['value']), 'it/s  ms_per_step', round(d['ms_per_step'],4))"; }
 run() { echo "== $1"; shift; for CH in docs_knn6 p2plane; do one "$@"; done; }
 for rep in 1 2 3; do
   run "both off (rep $rep)" ICPMI_SEL_WIN=0 ICPMI_ACC_SKIP=0
@@ -10,7 +10,7 @@ for rep in 1 2 3; do
   run "default: both (rep $rep)" A=1
 done
 echo "== headline (k = 1 point-to-point: neither applies)"
-python bench.py --no-cpu --no-extras 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('   headline', round(d['value']), 'it/s')"
+python bench.py --full --no-cpu --no-extras 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('   headline', round(d['value']), 'it/s')"
 python - <<'P'
 import numpy as np, norlab_icp_mapper_amd as pkg
 sc = pkg.synth.make_scene(m=1_000_000, n=100_000)

@@ -3,8 +3,9 @@
 # normal and with every NN launch issued twice back to back (ICPMI_NN_TWICE=1).  Output: gpurun_out/r5l2/
 cd "$GRAFT_REPO_ROOT"; O=$GRAFT_REPO_ROOT/gpurun_out/r5l2; rm -rf $O; mkdir -p $O
 timeout 120 scripts/r5/l2_survive.bin > $O/l2_survive.txt 2>&1; cat $O/l2_survive.txt
+ROOT=$PWD
 cd /tmp && export TMPDIR=/tmp
-B="python $GRAFT_REPO_ROOT/bench.py --no-cpu --no-extras --steps 2 --warmup 1 --chain p2p"
+B="python $ROOT/bench.py --full --no-cpu --no-extras --steps 2 --warmup 1 --chain p2p"
 for mode in normal twice; do
   if [ $mode = twice ]; then export ICPMI_NN_TWICE=1; else unset ICPMI_NN_TWICE; fi
   timeout 300 rocprofv3 --pmc FETCH_SIZE WRITE_SIZE --output-format csv -d $O/$mode/fetch -- $B > /dev/null 2>$O/${mode}_fetch.err

@@ -5,7 +5,7 @@ chain=$1; shift
 for tag in "$@"; do
   if [ "$tag" = prod ]; then cp /tmp/prod.so norlab_icp_mapper_amd/libicpmi.so; else cp scripts/r6/libicpmi_$tag.bin norlab_icp_mapper_amd/libicpmi.so; fi
   for n in 65536 98304 100000 114688 131072; do
-    echo "$tag | $chain | $n | $(python bench.py --no-extras --no-cpu --chain $chain --scan-points $n 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(round(d['value']), 'it/s nn', round(d['roofline']['avg_launch_us'],2), 'us')")"
+    echo "$tag | $chain | $n | $(python bench.py --full --no-extras --no-cpu --chain $chain --scan-points $n 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(round(d['value']), 'it/s nn', round(d['roofline']['avg_launch_us'],2), 'us')")"
   done
 done
 cp /tmp/prod.so norlab_icp_mapper_amd/libicpmi.so

@@ -3,7 +3,7 @@
 cd $GRAFT_REPO_ROOT; O=gpurun_out/r6_eps; mkdir -p $O
 timeout 900 python -m pytest tests/test_gpu_epsilon.py -m gpu -x -q 2>&1 | tail -25 | tee $O/tests.txt
 timeout 1500 python -m pytest tests/test_gpu_parity.py tests/test_gpu_knn_wg.py tests/test_gpu_sel_window.py tests/test_pins.py -m gpu -x -q 2>&1 | tail -8 | tee -a $O/tests.txt
-timeout 900 python bench.py --no-cpu > $O/bench.json 2> $O/bench.err
+timeout 900 python bench.py --full --no-cpu > $O/bench.json 2> $O/bench.err
 python - <<'PY' | tee $O/summary.txt
 import json
 d = json.load(open("gpurun_out/r6_eps/bench.json"))
