@@ -216,10 +216,7 @@ void icpmi_destroy(icpmi_handle c)
     selfgrid_destroy(c);
     comm_destroy(c);
     if (c->stream) hipStreamSynchronize(c->stream);
-    if (c->graph_exec) hipGraphExecDestroy(c->graph_exec);
-    if (c->bgraph_exec) hipGraphExecDestroy(c->bgraph_exec);
-    for (int g = 0; g < 2; ++g) if (c->seg_exec[g]) hipGraphExecDestroy(c->seg_exec[g]);
-    for (auto& hd : c->seg_heads) if (hd.exec) hipGraphExecDestroy(hd.exec);
+    c->graphs.reset();
     // ONE device-wide wait for all of the handle's blocks (one per block, each under the exclusive capture gate, stalled every
     // other thread's registration on this GPU ~80 times in a row)
     (void)dev_sync_for_free();

@@ -266,6 +266,24 @@ struct CaptureGate {
     CaptureGate& operator=(const CaptureGate&) = delete;
 };
 
+// One cached loop graph (loop.hip: capture_loop_graph): valid for the registrations whose signature is `sig`.  `sorted` is the loop state
+// order it leaves (nn_out_sorted at capture); a head graph of a checked loop also keeps its length and an LRU stamp.
+struct LoopGraph {
+    hipGraphExec_t exec = nullptr; uint64_t sig = 0; int uses = 0; bool sorted = false;
+    int len = 0; unsigned long used = 0;
+    bool holds(uint64_t s) const { return exec && sig == s; }
+    void reset() { if (exec) hipGraphExecDestroy(exec); *this = LoopGraph(); }
+};
+// every graph of a handle's loops: one fixed-count registration, one batched registration, a checked loop's SEGMENT graphs ([0] = head + the
+// first S iterations, [1] = S further iterations, replayed while the progress word says the loop is still running) and (r5) head graphs of
+// OTHER lengths (head + L iterations, L = the iteration count of the handle's previous checked registration: a mapper's registrations stop
+// after about the same number of iterations scan after scan, and a head graph of exactly that length has no dead iterations)
+struct LoopGraphs {
+    LoopGraph fixed, batch, seg[2], heads[4];
+    unsigned long clock = 0;
+    void reset() { fixed.reset(); batch.reset(); for (LoopGraph& g : seg) g.reset(); for (LoopGraph& g : heads) g.reset(); }
+};
+
 struct DevBlockCache {
     struct Live { size_t bytes; int dev; };
     std::mutex mu;
@@ -475,7 +493,6 @@ struct icpmi_ctx {
     float4* d_read_normals = nullptr; size_t cap_read_normals = 0;
     float*  d_read_noise = nullptr; size_t cap_read_noise = 0; int64_t read_noise_n = 0; // simpleSensorNoise of the NEXT reading (one shot)
     float*  d_read_scalar = nullptr; size_t cap_read_scalar = 0; int64_t read_scalar_n = 0; // GenericDescriptor{source: reading} row of the NEXT reading
-    bool graph_sorted = false;        // loop state order of the cached graph
     float4* d_qsorted = nullptr; size_t cap_qsorted = 0;       // centred reading sorted by tile (NN locality)
     int*    d_qindex = nullptr; size_t cap_qindex = 0;         // sorted position -> original index
     unsigned* d_qkeys = nullptr; size_t cap_qkeys = 0;
@@ -549,18 +566,9 @@ struct icpmi_ctx {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     std::vector<hipEvent_t> nn_events;
 
-    // cached graph of one full fixed-count loop
-    hipGraphExec_t graph_exec = nullptr;
-    int64_t graph_n = -1; int graph_iters = -1; uint64_t graph_sig = 0;
-    hipGraphExec_t bgraph_exec = nullptr; uint64_t bgraph_sig = 0; // ... and of one batched registration
-    // checked loops (Counter + Differential / Bound: what Mapper::processInput runs) as SEGMENT graphs: [0] = head + the first
-    // seg_len iterations, [1] = seg_len further iterations, replayed while the progress word says the loop is still running
-    hipGraphExec_t seg_exec[2] = {nullptr, nullptr}; uint64_t seg_sig = 0; int64_t seg_n = -1; int seg_len = 0; bool seg_sorted = false;
-    int seg_uses = 0, seg_wasted = 0, graph_uses = 0, graph_wasted = 0; uint64_t eager_sig = 0, map_epoch = 0; int64_t eager_n = -1;   // see drop_loop_graphs (map_epoch: one tick per invalidation)
-    // r5: head graphs of OTHER lengths (head + L iterations, L = the iteration count of the handle's previous checked registration): a mapper's
-    // registrations stop after about the same number of iterations scan after scan, and a head graph of exactly that length has no dead iterations
-    struct SegHead { int len = 0; hipGraphExec_t exec = nullptr; unsigned long used = 0; } seg_heads[4];
-    int seg_prev_iters = 0, seg_last_iters = 0; unsigned long seg_clock = 0;
+    LoopGraphs graphs;                // the cached loop graphs (checked loops: Counter + Differential / Bound, what Mapper::processInput runs)
+    int seg_wasted = 0, graph_wasted = 0; uint64_t eager_sig = 0, map_epoch = 0;   // see drop_loop_graphs (map_epoch: one tick per invalidation)
+    int seg_prev_iters = 0, seg_last_iters = 0;
 
     // buffers of the map-growth epoch (ops.hip: ops_staged_merge_allgather): this rank's accepted points, all ranks' blocks, the merged set
     float4* d_merge_send = nullptr; size_t cap_merge_send = 0;
@@ -615,9 +623,9 @@ static inline icpmi_status ensure_cap(icpmi_ctx* c, T** p, size_t* cap, size_t n
     return ICPMI_OK;
 }
 
-// Every cached loop graph (fixed-count, batched, the two segment graphs of a checked loop) holds pointers, grid parameters, the map's mean
-// and its normals flag as they were at capture time: a rebuilt index or a changed stream invalidates all of them (only graph_exec
-// was dropped, and the signature of the segment graphs does not cover mean / m / has_normals / d_map_pn / the level arrays).
+// Every cached loop graph (fixed-count, batched, the segment and head graphs of a checked loop) holds pointers, grid parameters, the map's
+// mean and its normals flag as they were at capture time: a rebuilt index or a changed stream invalidates all of them (only the
+// fixed-count graph was dropped, and the signatures do not cover mean / m / has_normals / d_map_pn / the level arrays).
 // The loop state and the selection histograms of a new handle are cleared at its FIRST call, on the stream it then has: a private handle adopts its
 // owner's stream right after its creation and never touches its own -- clearing there at creation (r5, after the synchronous hipMemset on the
 // legacy stream had to go: it breaks another thread's capture) made the runtime build a hardware queue for every such stream, milliseconds
@@ -633,17 +641,12 @@ static inline icpmi_status zero_state_if_pending(icpmi_ctx* c)
 
 static inline void drop_loop_graphs(icpmi_ctx* c)
 {
-    if (c->graph_exec) { if (c->graph_uses <= 1) ++c->graph_wasted; else c->graph_wasted = 0; hipGraphExecDestroy(c->graph_exec); c->graph_exec = nullptr; }
-    c->graph_n = -1; c->graph_sig = 0; c->graph_uses = 0;
-    if (c->bgraph_exec) { hipGraphExecDestroy(c->bgraph_exec); c->bgraph_exec = nullptr; }
-    c->bgraph_sig = 0;
-    // (r5) segment graphs that served a single registration before the map under them changed were not worth their capture: two such
-    // sets in a row and loop_run goes eager until a signature repeats (a mapper rebuilds its map behind every scan)
-    if (c->seg_exec[0]) { if (c->seg_uses <= 1) ++c->seg_wasted; else c->seg_wasted = 0; }
-    c->seg_uses = 0; ++c->map_epoch;
-    for (int g = 0; g < 2; ++g) if (c->seg_exec[g]) { hipGraphExecDestroy(c->seg_exec[g]); c->seg_exec[g] = nullptr; }
-    for (auto& hd : c->seg_heads) { if (hd.exec) hipGraphExecDestroy(hd.exec); hd.exec = nullptr; hd.len = 0; }
-    c->seg_sig = 0; c->seg_n = -1;
+    // (r5) graphs that served a single registration before the map under them changed were not worth their capture: two such sets in a
+    // row and loop_run goes eager until a signature repeats (a mapper rebuilds its map behind every scan)
+    if (c->graphs.fixed.exec) c->graph_wasted = c->graphs.fixed.uses <= 1 ? c->graph_wasted + 1 : 0;
+    if (c->graphs.seg[0].exec) c->seg_wasted = c->graphs.seg[0].uses <= 1 ? c->seg_wasted + 1 : 0;
+    ++c->map_epoch;
+    c->graphs.reset();
 }
 
 // scratch device allocation of one call: freed on every exit path (hipFree waits for work still using it)
@@ -667,6 +670,25 @@ struct DevBuf {
 #define ICPMI_PROGRESS_OCT_WORD 48  // ... and 8 words for the octree's root cube (octree.hip)
 #define ICPMI_PROGRESS_SELF_WORD 56 // ... two words: sum over the A-cells of (points in the cell)^2 of the handle's last self search (selfgrid.hip: the next build tunes its edge with it)
 #define ICPMI_PROGRESS_SCAN_WORD 40 // word of the host-mapped progress page (api.hip: h_progress, 64 words) that device_scan_flags_count reports into
+
+// Host wait on `count` words of host-mapped memory that the stream's kernels write: spins on them (v = a fresh snapshot) until ready(v),
+// and asks the stream every `cadence` spins (a power of two) whether anything is still to run.  A stream in an error state ends the wait
+// with its error (nothing will ever write the words); an idle stream means the words are final: v is read once more and *idle set.
+template <class T, class Ready>
+static inline hipError_t spin_on_host(hipStream_t stream, unsigned cadence, const T* src, int count, T* v, Ready ready, bool* idle = nullptr)
+{
+    auto load = [&] { for (int i = 0; i < count; ++i) v[i] = __atomic_load_n(src + i, __ATOMIC_ACQUIRE); };
+    if (idle) *idle = false;
+    for (unsigned spins = 1;; ++spins) {
+        load();
+        if (ready((const T*)v)) return hipSuccess;
+        if ((spins & (cadence - 1)) != 0) continue;
+        const hipError_t qe = hipStreamQuery(stream);
+        if (qe == hipErrorNotReady) continue;
+        if (qe == hipSuccess) { load(); if (idle) *idle = true; }
+        return qe;
+    }
+}
 static inline icpmi_status read_back2(icpmi_ctx* c, void* dst0, const void* src0, size_t b0, void* dst1, const void* src1, size_t b1)
 {
     if (!c->h_pin || b0 + b1 > ICPMI_PIN_BYTES) {

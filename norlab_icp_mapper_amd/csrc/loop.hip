@@ -1072,16 +1072,14 @@ icpmi_status loop_sensor_noise_overlap(icpmi_ctx* c, int64_t n, const LoopCfg& l
     return ICPMI_OK;
 }
 
-// centring, loop-state initialisation and the clearing of the selection histograms ride in the kernels of the query sort (SortHead) -- the
-// head of a registration is 3 graph nodes instead of 8
-static bool fuse_head() { return true; }
-
-// head_done: the caller wants the loop state initialised too (enqueue_registration_head); set when the sort's kernels did it
+// head_done: the caller wants the loop state initialised too (enqueue_registration_head); set when the sort's kernels did it.  Centring,
+// loop-state initialisation and the clearing of the selection histograms ride in the kernels of the query sort (SortHead) -- the head of a
+// registration is 3 graph nodes instead of 8
 icpmi_status loop_prepare_reading(icpmi_ctx* c, const float4* d_scan, int64_t n, const float* d_normals3, bool* head_done)
 {
     if (ensure_cap(c, &c->d_reading, &c->cap_reading, (size_t)n + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
     const int blocks = (int)((n + 255) / 256);
-    const bool fused = head_done && fuse_head() && c->cfg.knn <= 8 && n > 0;
+    const bool fused = head_done && c->cfg.knn <= 8 && n > 0;
     if (head_done) *head_done = fused;
     if (blocks && !fused) {
         BatchSrc src; memset(&src, 0, sizeof src); src.p[0] = d_scan;
@@ -1096,8 +1094,7 @@ icpmi_status loop_prepare_reading(icpmi_ctx* c, const float4* d_scan, int64_t n,
     if (fused) {
         SortHead h; memset(&h.raw, 0, sizeof h.raw);
         h.raw.p[0] = d_scan; h.mean[0] = c->mean[0]; h.mean[1] = c->mean[1]; h.mean[2] = c->mean[2];
-        h.st = c->d_state; h.seq = c->reg_seq; h.progress = c->d_progress;
-        h.seq_src = c->d_progress ? (const unsigned*)(c->d_progress + 32) : (const unsigned*)nullptr;
+        h.st = c->d_state; h.seq = c->reg_seq; h.progress = c->d_progress; h.seq_src = c->d_progress + 32;
         h.selhist = c->d_selhist;
         return sort_queries_batch(c, c->d_reading, batch_of_one(n), &h);
     }
@@ -1258,7 +1255,6 @@ static void enqueue_selection(icpmi_ctx* c, const LoopCfg& lc, int64_t count, bo
 
 template <int MIN, bool FUSED, bool EXT>
 static void launch_accumulate_ext(icpmi_ctx* c, int64_t n, const LoopCfg& lc, int nb, int slot);
-static bool pn_enabled() { return true; }
 
 template <int MIN, bool FUSED>
 static void launch_accumulate(icpmi_ctx* c, int64_t n, const LoopCfg& lc, int nb, int slot)
@@ -1280,14 +1276,14 @@ static void launch_accumulate_ext(icpmi_ctx* c, int64_t n, const LoopCfg& lc, in
         hipLaunchKernelGGL((accumulate_kernel<MIN, FUSED, EXT, 1024>), dim3(nb, ba.nscan), dim3(1024), 0, c->stream, sorted ? c->d_qsorted : c->d_reading, ba, acc_cap(), lc, c->d_state,
                            c->d_map_sorted, c->has_normals ? c->d_normals_sorted : (const float4*)nullptr, rn, c->d_sidx, c->d_d2, c->d_selhist, slot, is_med, factor,
                            (const float4*)nullptr, sorted ? c->d_qindex : (const int*)nullptr, (EXT && c->raw_has_scalar) ? c->d_raw_s : (const float*)nullptr,
-                           (MIN == ICPMI_MIN_POINT_TO_PLANE && c->has_normals && c->d_map_pn && pn_enabled()) ? c->d_map_pn : (const float4*)nullptr);
+                           (MIN == ICPMI_MIN_POINT_TO_PLANE && c->has_normals && c->d_map_pn) ? c->d_map_pn : (const float4*)nullptr);
         return;
     }
     hipLaunchKernelGGL((accumulate_kernel<MIN, FUSED, EXT>), dim3(nb, ba.nscan), dim3(256), 0, c->stream, sorted ? c->d_qsorted : c->d_reading, ba, acc_cap(), lc, c->d_state,
                        c->d_map_sorted, c->has_normals ? c->d_normals_sorted : (const float4*)nullptr, rn, c->d_sidx, c->d_d2, c->d_selhist, slot, is_med, factor,
                        (sorted && lc.k == 1) ? c->d_match_pt : (const float4*)nullptr, sorted ? c->d_qindex : (const int*)nullptr,
                        (EXT && c->raw_has_scalar) ? c->d_raw_s : (const float*)nullptr,
-                       (lc.k > 1 && MIN == ICPMI_MIN_POINT_TO_PLANE && c->has_normals && c->d_map_pn && pn_enabled()) ? c->d_map_pn : (const float4*)nullptr);
+                       (lc.k > 1 && MIN == ICPMI_MIN_POINT_TO_PLANE && c->has_normals && c->d_map_pn) ? c->d_map_pn : (const float4*)nullptr);
 }
 
 static void enqueue_accumulate_solve(icpmi_ctx* c, int64_t n, const LoopCfg& lc, float* d_Tstep, double* d_sums)
@@ -1314,42 +1310,14 @@ static void enqueue_accumulate_solve(icpmi_ctx* c, int64_t n, const LoopCfg& lc,
                        c->d_progress, ba.nscan == 1 ? c->d_state_mirror : (IcpState*)nullptr);
 }
 
-// diagnostic (r5, scripts/r5/l2_real2.sh): 64 MB of other lines through every XCD's L2 in front of an NN launch -- whatever the L2 still held
-// of the map from the previous iteration is gone; the launch's events (profile mode) do not include this kernel
-__global__ __launch_bounds__(256) void l2_thrash_kernel(const uint4* __restrict__ buf, size_t n_u4, unsigned* __restrict__ sink)
-{
-    unsigned acc = 0;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n_u4; i += (size_t)gridDim.x * 256) { const uint4 v = buf[i]; acc ^= v.x ^ v.y ^ v.z ^ v.w; }
-    if (acc == 0x12345u) sink[0] = 1;
-}
-
-// (allocated by the first loop_run, outside any stream capture; nullptr unless ICPMI_NN_FLUSH_L2 is set)
-static uint4* g_l2_thrash = nullptr;
-static const uint4* l2_thrash_buffer() { return g_l2_thrash; }
-static void l2_thrash_prepare()
-{
-    static int thrash = -1;
-    if (thrash >= 0) return;
-    thrash = 0; // (r5 diagnostic, DESIGN_history.md 13.1: 64 MB pushed through every L2 in front of every NN launch; compile with -DICPMI_NN_FLUSH_L2 to get it back)
-#ifdef ICPMI_NN_FLUSH_L2
-    thrash = 1;
-#endif
-    if (!thrash) return;
-    const size_t bytes = (64u << 20) + 64;
-    if (hipMalloc((void**)&g_l2_thrash, bytes) != hipSuccess || hipMemset(g_l2_thrash, 0, bytes) != hipSuccess || hipDeviceSynchronize() != hipSuccess) g_l2_thrash = nullptr;
-}
-
 static icpmi_status enqueue_iteration(icpmi_ctx* c, int64_t n, const LoopCfg& lc, hipEvent_t nn0, hipEvent_t nn1)
 {
-    if (const uint4* buf = l2_thrash_buffer())
-        hipLaunchKernelGGL(l2_thrash_kernel, dim3(2048), dim3(256), 0, c->stream, buf, (size_t)(64u << 20) / 16, reinterpret_cast<unsigned*>(const_cast<uint4*>(buf) + (size_t)(64u << 20) / 16));
     if (nn0) HIP_TRY(c, hipEventRecord(nn0, c->stream));
     c->nn_hist0 = fused_filter_slot(lc) >= 0 ? c->d_selhist : nullptr;
     c->nn_builds_hist0 = false;
     c->nn_builds_win = false;
-    constexpr int keep_pts = 1;
-    c->nn_match_pt = (lc.k == 1 && keep_pts) ? c->d_match_pt : nullptr;
-    c->nn_sorted_k = lc.k > 1 && keep_pts;
+    c->nn_match_pt = lc.k == 1 ? c->d_match_pt : nullptr;
+    c->nn_sorted_k = lc.k > 1;
     c->nn_out_sorted = false;
     icpmi_status s = nn_launch_k(c, c->d_reading, n, c->d_state->T_iter, lc, 1, c->d_sidx, c->d_d2, c->d_state);
     c->nn_sorted_k = false; // (only this launch: stage calls on the same handle answer in the caller's order)
@@ -1361,10 +1329,10 @@ static icpmi_status enqueue_iteration(icpmi_ctx* c, int64_t n, const LoopCfg& lc
     return ICPMI_OK;
 }
 
-static void fill_stats(icpmi_ctx* c, const LoopCfg& lc, int64_t n, icpmi_stats* stats)
+// with_dbg = false (the batch path): reserved[] stays as the caller cleared it
+static void fill_stats(const IcpState* hs, const LoopCfg& lc, int64_t n, icpmi_stats* stats, bool with_dbg = true)
 {
     if (!stats) return;
-    const IcpState* hs = c->h_state;
     stats->iterations = hs->iter;
     stats->stop_reason = hs->stop_reason;
     stats->pairs = hs->pairs;
@@ -1376,7 +1344,7 @@ static void fill_stats(icpmi_ctx* c, const LoopCfg& lc, int64_t n, icpmi_stats* 
         if (lc.out_type[f] == ICPMI_OUT_TRIMMEDDIST || lc.out_type[f] == ICPMI_OUT_MEDIANDIST || lc.out_type[f] == ICPMI_OUT_VARTRIMMEDDIST) stats->trimmed_limit = hs->limits[f];
     stats->hard_queries = (int64_t)hs->hard_total;
     stats->sensor_noise_overlap = -1.f; // "not computed" unless loop_run's sensor-noise pass overwrites it
-    for (int i = 0; i < 2; ++i) { stats->reserved[2 * i] = (int32_t)(hs->dbg[i] & 0xffffffffu); stats->reserved[2 * i + 1] = (int32_t)(hs->dbg[i] >> 32); }
+    for (int i = 0; i < 2 && with_dbg; ++i) { stats->reserved[2 * i] = (int32_t)(hs->dbg[i] & 0xffffffffu); stats->reserved[2 * i + 1] = (int32_t)(hs->dbg[i] >> 32); }
 }
 
 static void host_mat4_mul(const float* A, const float* B, float* C)
@@ -1391,6 +1359,16 @@ static void host_mat4_mul(const float* A, const float* B, float* C)
     memcpy(C, R, sizeof R);
 }
 
+// the registration's result in the caller's frame: T_refIn_refMean * T_iter * T_refMean_dataIn
+static void pose_out(const icpmi_ctx* c, const float* T_iter, float* T_out)
+{
+    float Tm[16], Tmi[16], tmp[16];
+    for (int i = 0; i < 16; ++i) Tm[i] = Tmi[i] = (i % 5 == 0) ? 1.f : 0.f;
+    for (int r = 0; r < 3; ++r) { Tm[12 + r] = c->mean[r]; Tmi[12 + r] = -c->mean[r]; }
+    host_mat4_mul(T_iter, Tmi, tmp);
+    host_mat4_mul(Tm, tmp, T_out);
+}
+
 // everything a registration enqueues before its first iteration: centring + tile sort of the reading,
 // loop state, selection histograms
 static icpmi_status enqueue_registration_head(icpmi_ctx* c, const float4* d_scan, const float* d_normals3, int64_t n)
@@ -1401,16 +1379,61 @@ static icpmi_status enqueue_registration_head(icpmi_ctx* c, const float4* d_scan
     if (head_done) return ICPMI_OK;
     // (the registration's sequence number: loop_run stores it in h_progress[32] before it launches anything)
     hipLaunchKernelGGL(init_state_kernel, dim3(1), dim3(64), 0, c->stream, c->d_state, (const float*)nullptr, c->reg_seq, c->d_progress,
-                       c->d_progress ? (const unsigned*)(c->d_progress + 32) : (const unsigned*)nullptr);
+                       (const unsigned*)(c->d_progress + 32));
     HIP_TRY(c, hipMemsetAsync(c->d_selhist, 0, ICPMI_SELHIST_WORDS * sizeof(unsigned), c->stream));
     HIP_TRY(c, hipGetLastError());
     return ICPMI_OK;
 }
 
+// Capture what enqueue() puts on the handle's stream (a head and the iterations behind it) into g, replacing what g held; g then serves the
+// registrations of signature `sig`
+template <class Enqueue>
+static icpmi_status capture_loop_graph(icpmi_ctx* c, LoopGraph& g, uint64_t sig, Enqueue enqueue)
+{
+    g.reset();
+    hipGraph_t gr = nullptr;
+    CaptureGate capture_scope; // (common.h: no device-wide synchronisation of another thread while this one captures)
+    HIP_TRY(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
+    const icpmi_status s = enqueue();
+    const hipError_t ce = hipStreamEndCapture(c->stream, &gr);
+    if (s != ICPMI_OK) { if (gr) hipGraphDestroy(gr); return s; }
+    HIP_TRY(c, ce);
+    const hipError_t ie = hipGraphInstantiate(&g.exec, gr, nullptr, nullptr, 0);
+    hipGraphDestroy(gr);
+    HIP_TRY(c, ie);
+    g.sig = sig; g.uses = 1; g.sorted = c->nn_out_sorted;
+    return ICPMI_OK;
+}
+
+// what a graph of loop_run is valid for: the chain (its iteration count, hence the segment length, included), the reading's size, every
+// buffer its launches take a pointer to, the grid and the map epoch
+static uint64_t loop_sig(const icpmi_ctx* c, const LoopCfg& lc, const float4* d_scan, const float* d_normals3, int64_t n)
+{
+    uint64_t sig = fnv(&lc, sizeof lc, 1469598103934665603ull);
+    const void* ptrs[] = {d_scan, d_normals3, c->d_qkeys, c->d_qtile, c->d_reading, c->d_read_normals, c->d_sidx, c->d_d2, c->d_hard, c->d_state, c->d_match_pt,
+                          c->d_qsorted, c->d_qindex, c->d_map_sorted, c->d_normals_sorted, c->d_cell_start, c->d_selhist,
+                          c->scratch[0], c->scratch[1], c->scratch[2], c->scratch[3], c->scratch[4]}; // (VarTrimmedDist passes)
+    sig = fnv(ptrs, sizeof ptrs, sig);
+    sig = fnv(&c->grid, sizeof c->grid, sig);
+    sig = fnv(&c->map_epoch, sizeof c->map_epoch, sig);
+    return fnv(&n, sizeof n, sig);
+}
+
+// r5: a mapper rebuilds its map behind every scan (Map::updateLocalPointCloud -> icp.setMap), and every rebuild drops the graphs: capture +
+// instantiate + destroy per scan cost more than they saved (chain bench: register 0.58 -> 0.455 ms, update 1.53 -> 1.45 ms with no graph at
+// all).  After two sets of a kind in a row that served one registration each (`wasted`, counted by drop_loop_graphs) the handle runs that
+// kind eagerly, until the same signature comes back twice (localisation against a fixed map, the benchmark's repeats): then a graph pays again.
+static bool go_eager(icpmi_ctx* c, int* wasted, bool cached, uint64_t sig)
+{
+    if (cached || *wasted < 2) return false;
+    if (c->eager_sig == sig) { *wasted = 0; return false; }
+    c->eager_sig = sig;
+    return true;
+}
+
 icpmi_status loop_run(icpmi_ctx* c, const float4* d_scan, const float* d_normals3, int64_t n, const LoopCfg& lc_in, bool fixed,
                       float T_out[16], icpmi_stats* stats)
 {
-    l2_thrash_prepare();
     LoopCfg lc = lc_in;
     // all allocations up front: none may happen while the stream is capturing
     if (ensure_loop_buffers(c, n, lc.k) != ICPMI_OK) return ICPMI_ERR_HIP;
@@ -1423,162 +1446,89 @@ icpmi_status loop_run(icpmi_ctx* c, const float4* d_scan, const float* d_normals
     bool graph = c->cfg.use_graph != 0 && fixed && !profile;
     float nn_ms_sum = 0.f; int nn_cnt = 0;
     c->reg_seq = (c->reg_seq + 1) & 0x7ffffu;
-    if (c->h_progress) __atomic_store_n(c->h_progress + 32, c->reg_seq, __ATOMIC_RELEASE);
+    __atomic_store_n(c->h_progress + 32, c->reg_seq, __ATOMIC_RELEASE);
     // r5 (fast finish, see the end of this function): the finished state reaches the host by itself and carries the device clocks of its
     // start and stop -- no event pair, no copy, no drain
-    const bool fast_ok = !profile && c->d_state_mirror && c->h_progress && lc.max_iter < 0xfff;
+    const bool fast_ok = !profile && c->d_state_mirror && lc.max_iter < 0xfff;
     if (!fast_ok) HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
     // A checked loop (Counter + Differential / Bound: what Mapper::processInput runs) as SEGMENT graphs (r3):
     // head + the first S iterations are one graph, S further iterations another; a segment is launched when the progress word
     // says the loop is still running and within S / 2 iterations of the end of what is enqueued.  Iterations past the stop are
     // early-exit kernels (every kernel of the loop returns on st->done): at most S - 1 of them, against eager launches -- and
     // their wider kernel-to-kernel gaps -- for every real iteration.
-    constexpr int seg_cfg = 4;
-    bool segmented = !graph && !profile && c->cfg.use_graph != 0 && seg_cfg > 0 && (lc.use_diff || lc.use_bound) && c->h_progress &&
-                     lc.max_iter < 0xfff && lc.max_iter > 1;
-    const int S = seg_cfg > 0 && seg_cfg < lc.max_iter ? seg_cfg : lc.max_iter;
-    uint64_t sig = 1469598103934665603ull;
-    if (segmented) {
-        sig = fnv(&lc, sizeof lc, sig);
-        const void* ptrs[] = {d_scan, d_normals3, c->d_qkeys, c->d_qtile,c->d_reading, c->d_read_normals, c->d_sidx, c->d_d2, c->d_hard, c->d_state, c->d_match_pt,
-                              c->d_qsorted, c->d_qindex, c->d_map_sorted, c->d_normals_sorted, c->d_cell_start, c->d_selhist,
-                              c->scratch[0], c->scratch[1], c->scratch[2], c->scratch[3], c->scratch[4]};
-        sig = fnv(ptrs, sizeof ptrs, sig);
-        sig = fnv(&c->grid, sizeof c->grid, sig);
-        sig = fnv(&c->map_epoch, sizeof c->map_epoch, sig);
-        // r5: a mapper rebuilds its map behind every scan (Map::updateLocalPointCloud -> icp.setMap), and every rebuild drops the graphs:
-        // capture + instantiate + destroy per scan cost more than they saved (chain bench: register 0.58 -> 0.455 ms, update 1.53 -> 1.45 ms
-        // with no graph at all).  After two sets in a row that served one registration each the handle runs its checked loops eagerly,
-        // until the same map and scan size come back twice (localisation against a fixed map, the benchmark's repeats): then a graph pays again.
-        constexpr int adapt = 1;
-        const bool cached = c->seg_exec[0] && c->seg_exec[1] && c->seg_n == n && c->seg_len == S && c->seg_sig == sig;
-        if (adapt && !cached && c->seg_wasted >= 2) {
-            if (c->eager_sig == sig && c->eager_n == n) c->seg_wasted = 0;
-            else { c->eager_sig = sig; c->eager_n = n; segmented = false; }
-        }
-    }
-    uint64_t fsig = 1469598103934665603ull;
-    if (graph) {
-        fsig = fnv(&lc, sizeof lc, fsig);
-        const void* ptrs[] = {d_scan, d_normals3, c->d_qkeys, c->d_qtile,c->d_reading, c->d_read_normals, c->d_sidx, c->d_d2, c->d_hard, c->d_state, c->d_match_pt,
-                              c->d_qsorted, c->d_qindex,
-                              c->d_map_sorted, c->d_normals_sorted, c->d_cell_start, c->d_selhist,
-                              c->scratch[0], c->scratch[1], c->scratch[2], c->scratch[3], c->scratch[4]}; // (VarTrimmedDist passes)
-        fsig = fnv(ptrs, sizeof ptrs, fsig);
-        fsig = fnv(&c->grid, sizeof c->grid, fsig);
-        fsig = fnv(&c->map_epoch, sizeof c->map_epoch, fsig);
-        // the same rule for the one-graph registration of a Counter-only chain (the shipped configuration: examples/config.yaml:54-57)
-        constexpr int adapt = 1;
-        const bool cached = c->graph_exec && c->graph_n == n && c->graph_iters == lc.max_iter && c->graph_sig == fsig;
-        if (adapt && !cached && c->graph_wasted >= 2) {
-            if (c->eager_sig == fsig && c->eager_n == n) c->graph_wasted = 0;
-            else { c->eager_sig = fsig; c->eager_n = n; graph = false; }
-        }
-    }
+    bool segmented = !graph && !profile && c->cfg.use_graph != 0 && (lc.use_diff || lc.use_bound) && lc.max_iter < 0xfff && lc.max_iter > 1;
+    const int S = std::min(4, lc.max_iter);
+    LoopGraphs& gs = c->graphs;
+    const uint64_t sig = (graph || segmented) ? loop_sig(c, lc, d_scan, d_normals3, n) : 0;
+    const bool cached = segmented ? gs.seg[0].holds(sig) && gs.seg[1].holds(sig) : gs.fixed.holds(sig);
+    if (segmented && go_eager(c, &c->seg_wasted, cached, sig)) segmented = false;
+    // (the same rule for the one-graph registration of a Counter-only chain: the shipped configuration, examples/config.yaml:54-57)
+    if (graph && go_eager(c, &c->graph_wasted, cached, sig)) graph = false;
+    // head (when asked) + `count` iterations from iteration `first` on, in the order every path enqueues them
+    auto enqueue_loop = [&](bool with_head, int first, int count) {
+        icpmi_status s = with_head ? enqueue_registration_head(c, d_scan, d_normals3, n) : ICPMI_OK;
+        for (int it = 0; it < count && s == ICPMI_OK; ++it) { c->nn_iter_hint = first + it; s = enqueue_iteration(c, n, lc, nullptr, nullptr); }
+        return s;
+    };
     if (!graph && !segmented) {
         icpmi_status s = enqueue_registration_head(c, d_scan, d_normals3, n);
         if (s != ICPMI_OK) return s;
     }
     if (segmented) {
-        ++c->seg_uses;
-        if (!c->seg_exec[0] || !c->seg_exec[1] || c->seg_n != n || c->seg_len != S || c->seg_sig != sig) {
-            for (int g = 0; g < 2; ++g) if (c->seg_exec[g]) { hipGraphExecDestroy(c->seg_exec[g]); c->seg_exec[g] = nullptr; }
-            for (auto& hd : c->seg_heads) { if (hd.exec) hipGraphExecDestroy(hd.exec); hd.exec = nullptr; hd.len = 0; } // (captured the same pointers)
+        ++gs.seg[0].uses;
+        if (!cached) {
+            for (LoopGraph& hd : gs.heads) hd.reset(); // (captured the same pointers)
+            // (later segments: every iteration is seeded and past the wide first launches -- one graph serves them all)
             for (int g = 0; g < 2; ++g) {
-                hipGraph_t gr = nullptr;
-                CaptureGate capture_scope; // (common.h: no device-wide synchronisation of another thread while this one captures)
-                HIP_TRY(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-                icpmi_status s = g == 0 ? enqueue_registration_head(c, d_scan, d_normals3, n) : ICPMI_OK;
-                // (later segments: every iteration is seeded and past the wide first launches -- one graph serves them all)
-                for (int it = 0; it < S && s == ICPMI_OK; ++it) { c->nn_iter_hint = g == 0 ? it : S + it; s = enqueue_iteration(c, n, lc, nullptr, nullptr); }
-                hipError_t ce = hipStreamEndCapture(c->stream, &gr);
-                if (s != ICPMI_OK) { if (gr) hipGraphDestroy(gr); return s; }
-                HIP_TRY(c, ce);
-                hipError_t ie = hipGraphInstantiate(&c->seg_exec[g], gr, nullptr, nullptr, 0);
-                hipGraphDestroy(gr);
-                HIP_TRY(c, ie);
+                const icpmi_status s = capture_loop_graph(c, gs.seg[g], sig, [&] { return enqueue_loop(g == 0, g == 0 ? 0 : S, S); });
+                if (s != ICPMI_OK) return s;
             }
-            c->seg_n = n; c->seg_len = S; c->seg_sig = sig; c->seg_sorted = c->nn_out_sorted; c->seg_uses = 1;
         }
         // r5: the head graph's length follows the handle's previous checked registration.  A mapper registers scan after scan against almost
         // the same map from almost the same prior: the loop stops after the same few iterations every time (6 in the benchmark scene), and
         // head + 4 followed by a segment of 4 ran two dead iterations (eight early-exit launches, ~24 us of a 0.37 ms registration) behind the
         // stop.  With a head of exactly the previous count the host waits for that head to finish (no look-ahead: the prediction says the loop
         // is over) and goes on with ordinary segments only if it is not.
-        constexpr int adapt_cfg = 1;
-        hipGraphExec_t head_exec = c->seg_exec[0];
-        int head_len = S;
-        if (adapt_cfg && c->seg_prev_iters >= 2 && c->seg_prev_iters != S && c->seg_prev_iters <= 24 && c->seg_prev_iters < lc.max_iter) {
-            const int L = c->seg_prev_iters;
-            icpmi_ctx::SegHead* slot = nullptr;
-            for (auto& hd : c->seg_heads) if (hd.exec && hd.len == L) slot = &hd;
-            if (!slot) {
-                slot = &c->seg_heads[0];
-                for (auto& hd : c->seg_heads) if (!hd.exec) { slot = &hd; break; } else if (hd.used < slot->used) slot = &hd;
-                if (slot->exec) { hipGraphExecDestroy(slot->exec); slot->exec = nullptr; slot->len = 0; }
-                hipGraph_t gr = nullptr;
-                CaptureGate capture_scope; // (common.h: no device-wide synchronisation of another thread while this one captures)
-                HIP_TRY(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-                icpmi_status hs = enqueue_registration_head(c, d_scan, d_normals3, n);
-                for (int it = 0; it < L && hs == ICPMI_OK; ++it) { c->nn_iter_hint = it; hs = enqueue_iteration(c, n, lc, nullptr, nullptr); }
-                hipError_t ce = hipStreamEndCapture(c->stream, &gr);
-                if (hs != ICPMI_OK) { if (gr) hipGraphDestroy(gr); return hs; }
-                HIP_TRY(c, ce);
-                hipError_t ie = hipGraphInstantiate(&slot->exec, gr, nullptr, nullptr, 0);
-                hipGraphDestroy(gr);
-                HIP_TRY(c, ie);
-                slot->len = L;
+        LoopGraph* head = &gs.seg[0];
+        const int L = c->seg_prev_iters;
+        if (L >= 2 && L != S && L <= 24 && L < lc.max_iter) {
+            head = nullptr;
+            for (LoopGraph& hd : gs.heads) if (hd.exec && hd.len == L) head = &hd;
+            if (!head) {
+                head = &gs.heads[0];
+                for (LoopGraph& hd : gs.heads) if (!hd.exec) { head = &hd; break; } else if (hd.used < head->used) head = &hd;
+                const icpmi_status s = capture_loop_graph(c, *head, sig, [&] { return enqueue_loop(true, 0, L); });
+                if (s != ICPMI_OK) return s;
+                head->len = L;
             }
-            slot->used = ++c->seg_clock;
-            head_exec = slot->exec; head_len = L;
+            head->used = ++gs.clock;
         }
-        HIP_TRY(c, hipGraphLaunch(head_exec, c->stream));
+        const int head_len = head == &gs.seg[0] ? S : L;
+        HIP_TRY(c, hipGraphLaunch(head->exec, c->stream));
         if (c->cfg.knn <= 8) { c->qsorted_n = n; c->qsorted_src = c->d_reading; } // what the replayed head leaves in d_qsorted
         int launched = head_len;
-        bool stopped = false;
-        while (launched < lc.max_iter && !stopped) {
+        while (launched < lc.max_iter) {
             // (behind a predicted head: no look-ahead -- the next segment goes out only once the head has run and the loop is still going)
             const int lead = (launched == head_len && head_len != S) ? 0 : (S > 1 ? S / 2 : 1);
-            for (unsigned spins = 1;; ++spins) {
-                const unsigned v = __atomic_load_n(c->h_progress, __ATOMIC_ACQUIRE);
-                if (((v >> 12) & 0x7ffffu) == c->reg_seq) {
-                    if (v >> 31) { stopped = true; break; }
-                    if ((int)(v & 0xfffu) + lead >= launched) break;
-                }
-                if ((spins & 255u) != 0) continue;
-                const hipError_t qe = hipStreamQuery(c->stream);
-                if (qe != hipSuccess && qe != hipErrorNotReady) HIP_TRY(c, qe);
-                if (qe == hipSuccess) { // everything enqueued has run: the word is final
-                    const unsigned w = __atomic_load_n(c->h_progress, __ATOMIC_ACQUIRE);
-                    stopped = ((w >> 12) & 0x7ffffu) != c->reg_seq || (w >> 31) != 0 || (int)(w & 0xfffu) < launched;
-                    break;
-                }
-            }
-            if (stopped) break;
-            HIP_TRY(c, hipGraphLaunch(c->seg_exec[1], c->stream));
+            unsigned v = 0; bool idle = false;
+            HIP_TRY(c, spin_on_host(c->stream, 256, c->h_progress, 1, &v, [&](const unsigned* w) {
+                const ProgressWord p = decode_progress(*w, c->reg_seq);
+                return p.mine && (p.done || p.iter + lead >= launched);
+            }, &idle));
+            const ProgressWord p = decode_progress(v, c->reg_seq);
+            if (idle ? !p.mine || p.done || p.iter < launched : p.done) break; // (idle: everything enqueued has run, the word is final)
+            HIP_TRY(c, hipGraphLaunch(gs.seg[1].exec, c->stream));
             launched += S;
         }
     } else if (graph) {
         // the whole registration -- head and all iterations -- is one graph, replayed while the scan
         // buffer, the map and the chain stay the same
-        const uint64_t sig = fsig;
-        ++c->graph_uses;
-        if (!c->graph_exec || c->graph_n != n || c->graph_iters != lc.max_iter || c->graph_sig != sig) {
-            if (c->graph_exec) { hipGraphExecDestroy(c->graph_exec); c->graph_exec = nullptr; }
-            hipGraph_t g = nullptr;
-            CaptureGate capture_scope; // (common.h: no device-wide synchronisation of another thread while this one captures)
-                HIP_TRY(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-            icpmi_status s = enqueue_registration_head(c, d_scan, d_normals3, n);
-            for (int it = 0; it < lc.max_iter && s == ICPMI_OK; ++it) { c->nn_iter_hint = it; s = enqueue_iteration(c, n, lc, nullptr, nullptr); }
-            hipError_t ce = hipStreamEndCapture(c->stream, &g);
-            if (s != ICPMI_OK) { if (g) hipGraphDestroy(g); return s; }
-            HIP_TRY(c, ce);
-            hipError_t ie = hipGraphInstantiate(&c->graph_exec, g, nullptr, nullptr, 0);
-            hipGraphDestroy(g);
-            HIP_TRY(c, ie);
-            c->graph_n = n; c->graph_iters = lc.max_iter; c->graph_sig = sig; c->graph_sorted = c->nn_out_sorted; c->graph_uses = 1;
+        ++gs.fixed.uses;
+        if (!cached) {
+            const icpmi_status s = capture_loop_graph(c, gs.fixed, sig, [&] { return enqueue_loop(true, 0, lc.max_iter); });
+            if (s != ICPMI_OK) return s;
         }
-        HIP_TRY(c, hipGraphLaunch(c->graph_exec, c->stream));
+        HIP_TRY(c, hipGraphLaunch(gs.fixed.exec, c->stream));
         if (c->cfg.knn <= 8) { c->qsorted_n = n; c->qsorted_src = c->d_reading; } // what the replayed head leaves in d_qsorted
     } else {
         const int check_every = (lc.use_diff || lc.use_bound) ? 4 : lc.max_iter;
@@ -1592,7 +1542,7 @@ icpmi_status loop_run(icpmi_ctx* c, const float4* d_scan, const float* d_normals
         // a hipMemcpy + hipStreamSynchronize every 4 iterations, ~25 us of idle GPU each), and at most `ahead` iterations
         // run as early-exit kernels after the loop has stopped.
         constexpr int ahead = 2;
-        const bool poll = ahead > 0 && !profile && (lc.use_diff || lc.use_bound) && c->h_progress && lc.max_iter < 0xfff;
+        const bool poll = !profile && (lc.use_diff || lc.use_bound) && lc.max_iter < 0xfff;
         int launched = 0;
         bool stopped = false;
         for (int it = 0; it < lc.max_iter && !stopped; ++it) {
@@ -1603,24 +1553,15 @@ icpmi_status loop_run(icpmi_ctx* c, const float4* d_scan, const float* d_normals
             ++launched;
             if (it + 1 >= lc.max_iter) break;
             if (poll) {
-                // go on as soon as the GPU has finished all but `ahead` of the iterations enqueued so far
-                for (unsigned spins = 1;; ++spins) {
-                    const unsigned v = __atomic_load_n(c->h_progress, __ATOMIC_ACQUIRE);
-                    if (((v >> 12) & 0x7ffffu) == c->reg_seq) {
-                        if (v >> 31) { stopped = true; break; }
-                        if ((int)(v & 0xfffu) + ahead > it) break;
-                    }
-                    if ((spins & 255u) != 0) continue;
-                    const hipError_t qe = hipStreamQuery(c->stream);
-                    if (qe != hipSuccess && qe != hipErrorNotReady) HIP_TRY(c, qe); // stream in an error state: nothing will ever advance the word
-                    if (qe == hipSuccess) {
-                        // everything enqueued has run: the word is final (a kernel that stops the loop without passing
-                        // through the solve kernel cannot leave the host waiting)
-                        const unsigned w = __atomic_load_n(c->h_progress, __ATOMIC_ACQUIRE);
-                        stopped = ((w >> 12) & 0x7ffffu) != c->reg_seq || (w >> 31) != 0 || (int)(w & 0xfffu) <= it;
-                        break;
-                    }
-                }
+                // go on as soon as the GPU has finished all but `ahead` of the iterations enqueued so far; an idle stream leaves the word
+                // final (a kernel that stops the loop without passing through the solve kernel cannot leave the host waiting)
+                unsigned v = 0; bool idle = false;
+                HIP_TRY(c, spin_on_host(c->stream, 256, c->h_progress, 1, &v, [&](const unsigned* w) {
+                    const ProgressWord p = decode_progress(*w, c->reg_seq);
+                    return p.mine && (p.done || p.iter + ahead > it);
+                }, &idle));
+                const ProgressWord p = decode_progress(v, c->reg_seq);
+                stopped = idle ? !p.mine || p.done || p.iter <= it : p.done;
             } else if ((it + 1) % check_every == 0) {
                 const IcpState* sd = c->d_state;
                 HIP_TRY(c, hipMemcpyAsync(&c->h_state->done, &sd->done, sizeof(int), hipMemcpyDeviceToHost, c->stream));
@@ -1658,18 +1599,10 @@ icpmi_status loop_run(icpmi_ctx* c, const float4* d_scan, const float* d_normals
     // bound reached, a stream in an error state), for the profiling loop and for ICPMI_FAST_FINISH=0.
     bool have_state = false;
     if (fast_ok) {
-        for (unsigned spins = 1;; ++spins) {
-            const unsigned v = __atomic_load_n(c->h_progress, __ATOMIC_ACQUIRE);
-            if (((v >> 12) & 0x7ffffu) == (c->reg_seq & 0x7ffffu) && (v >> 31)) { have_state = true; break; }
-            if ((spins & 255u) != 0) continue;
-            const hipError_t qe = hipStreamQuery(c->stream);
-            if (qe != hipSuccess && qe != hipErrorNotReady) HIP_TRY(c, qe);
-            if (qe == hipSuccess) { // everything has run: the word is final
-                const unsigned w = __atomic_load_n(c->h_progress, __ATOMIC_ACQUIRE);
-                have_state = ((w >> 12) & 0x7ffffu) == (c->reg_seq & 0x7ffffu) && (w >> 31);
-                break;
-            }
-        }
+        auto finished = [&](const unsigned* w) { const ProgressWord p = decode_progress(*w, c->reg_seq); return p.mine && p.done; };
+        unsigned v = 0;
+        HIP_TRY(c, spin_on_host(c->stream, 256, c->h_progress, 1, &v, finished)); // (an idle stream: the word is final)
+        have_state = finished(&v);
         if (have_state) {
             __atomic_thread_fence(__ATOMIC_ACQUIRE);
             const volatile IcpState* hv = c->h_state;
@@ -1681,7 +1614,7 @@ icpmi_status loop_run(icpmi_ctx* c, const float4* d_scan, const float* d_normals
         HIP_TRY(c, hipStreamSynchronize(c->stream));
     }
 
-    fill_stats(c, lc, n, stats);
+    fill_stats(c->h_state, lc, n, stats);
     if (segmented) { // what the next checked registration's head graph is cut to (the larger of the last two counts: one dead iteration costs
                      // less than a head that ends one iteration early and a segment behind it)
         const int it_now = c->h_state->error ? 0 : c->h_state->iter;
@@ -1704,7 +1637,7 @@ icpmi_status loop_run(icpmi_ctx* c, const float4* d_scan, const float* d_normals
     }
     if (lc.sensor_noise && stats && !c->h_state->error && c->h_state->iter > 0) {
         // ErrorMinimizer::getOverlap() with sensor noise: one pass over the last iteration's pairs, still in the loop's buffers
-        const bool sorted_state = graph ? c->graph_sorted : (segmented ? c->seg_sorted : c->nn_out_sorted);
+        const bool sorted_state = graph ? c->graphs.fixed.sorted : (segmented ? c->graphs.seg[1].sorted : c->nn_out_sorted);
         const icpmi_status os = loop_sensor_noise_overlap(c, n, lc, sorted_state, &stats->sensor_noise_overlap);
         if (os != ICPMI_OK) return os;
     }
@@ -1719,12 +1652,7 @@ icpmi_status loop_run(icpmi_ctx* c, const float4* d_scan, const float* d_normals
         }
         return (icpmi_status)hs->error;
     }
-    // T_refIn_refMean * T_iter * T_refMean_dataIn
-    float Tm[16], Tmi[16], tmp[16];
-    for (int i = 0; i < 16; ++i) Tm[i] = Tmi[i] = (i % 5 == 0) ? 1.f : 0.f;
-    for (int r = 0; r < 3; ++r) { Tm[12 + r] = c->mean[r]; Tmi[12 + r] = -c->mean[r]; }
-    host_mat4_mul(hs->T_iter, Tmi, tmp);
-    host_mat4_mul(Tm, tmp, T_out);
+    pose_out(c, hs->T_iter, T_out);
     return ICPMI_OK;
 }
 
@@ -1738,27 +1666,10 @@ icpmi_status loop_run(icpmi_ctx* c, const float4* d_scan, const float* d_normals
 // ---------------------------------------------------------------------------------------------
 static void batch_result(icpmi_ctx* c, const LoopCfg& lc, const IcpState* hs, int64_t n, float* T_out, icpmi_stats* stats, icpmi_status* status)
 {
-    if (stats) {
-        stats->iterations = hs->iter;
-        stats->stop_reason = hs->stop_reason;
-        stats->pairs = hs->pairs;
-        const double denom = (double)lc.k * (double)n;
-        stats->point_used_ratio = denom > 0 ? (float)hs->pairs / (float)denom : 0.f;
-        stats->weighted_point_used_ratio = denom > 0 ? (float)(hs->wsum / denom) : 0.f;
-        stats->trimmed_limit = -1.f;
-        for (int f = 0; f < lc.n_out; ++f)
-            if (lc.out_type[f] == ICPMI_OUT_TRIMMEDDIST || lc.out_type[f] == ICPMI_OUT_MEDIANDIST) stats->trimmed_limit = hs->limits[f];
-        stats->hard_queries = (int64_t)hs->hard_total;
-        stats->sensor_noise_overlap = -1.f; // the batch path never runs the sensor-noise pass
-    }
-    for (int i = 0; i < 16; ++i) T_out[i] = (i % 5 == 0) ? 1.f : 0.f;
+    fill_stats(hs, lc, n, stats, false); // (the batch path never runs the sensor-noise pass)
     if (status) *status = (icpmi_status)hs->error;
-    if (hs->error) return;
-    float Tm[16], Tmi[16], tmp[16];
-    for (int i = 0; i < 16; ++i) Tm[i] = Tmi[i] = (i % 5 == 0) ? 1.f : 0.f;
-    for (int r = 0; r < 3; ++r) { Tm[12 + r] = c->mean[r]; Tmi[12 + r] = -c->mean[r]; }
-    host_mat4_mul(hs->T_iter, Tmi, tmp);
-    host_mat4_mul(Tm, tmp, T_out);
+    if (hs->error) for (int i = 0; i < 16; ++i) T_out[i] = (i % 5 == 0) ? 1.f : 0.f;
+    else pose_out(c, hs->T_iter, T_out);
 }
 
 icpmi_status loop_run_batch(icpmi_ctx* c, int B, const float* const* d_scans4, const int64_t* nn, const LoopCfg& lc, bool fixed, float* T_out,
@@ -1780,7 +1691,7 @@ icpmi_status loop_run_batch(icpmi_ctx* c, int B, const float* const* d_scans4, c
 
     auto head = [&]() -> icpmi_status {
         const int blocks = (int)((nmax + 255) / 256);
-        if (fuse_head() && nmax > 0) {
+        if (nmax > 0) {
             c->reg_seq = (c->reg_seq + 1) & 0x7ffffu;
             SortHead h; h.raw = src; h.mean[0] = c->mean[0]; h.mean[1] = c->mean[1]; h.mean[2] = c->mean[2];
             h.st = c->d_state; h.seq = c->reg_seq; h.progress = c->d_progress; h.seq_src = nullptr; h.selhist = c->d_selhist;
@@ -1807,57 +1718,43 @@ icpmi_status loop_run_batch(icpmi_ctx* c, int B, const float* const* d_scans4, c
                               c->d_qsorted, c->d_qindex, c->d_map_sorted, c->d_normals_sorted, c->d_cell_start, c->d_selhist};
         sig = fnv(ptrs, sizeof ptrs, sig);
         sig = fnv(&c->grid, sizeof c->grid, sig);
-        if (!c->bgraph_exec || c->bgraph_sig != sig) {
-            if (c->bgraph_exec) { hipGraphExecDestroy(c->bgraph_exec); c->bgraph_exec = nullptr; }
-            hipGraph_t g = nullptr;
-            CaptureGate capture_scope; // (common.h: no device-wide synchronisation of another thread while this one captures)
-                HIP_TRY(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-            icpmi_status s = head();
-            for (int it = 0; it < lc.max_iter && s == ICPMI_OK; ++it) { c->nn_iter_hint = it; s = enqueue_iteration(c, nmax, lc, nullptr, nullptr); }
-            hipError_t ce = hipStreamEndCapture(c->stream, &g);
-            if (s != ICPMI_OK) { if (g) hipGraphDestroy(g); return s; }
-            HIP_TRY(c, ce);
-            hipError_t ie = hipGraphInstantiate(&c->bgraph_exec, g, nullptr, nullptr, 0);
-            hipGraphDestroy(g);
-            HIP_TRY(c, ie);
-            c->bgraph_sig = sig;
+        if (!c->graphs.batch.holds(sig)) {
+            const icpmi_status s = capture_loop_graph(c, c->graphs.batch, sig, [&] {
+                icpmi_status s = head();
+                for (int it = 0; it < lc.max_iter && s == ICPMI_OK; ++it) { c->nn_iter_hint = it; s = enqueue_iteration(c, nmax, lc, nullptr, nullptr); }
+                return s;
+            });
+            if (s != ICPMI_OK) return s;
         }
-        HIP_TRY(c, hipGraphLaunch(c->bgraph_exec, c->stream));
+        HIP_TRY(c, hipGraphLaunch(c->graphs.batch.exec, c->stream));
     } else {
         icpmi_status s = head();
         if (s != ICPMI_OK) return s;
         constexpr int ahead = 2;
-        const bool poll = (lc.use_diff || lc.use_bound) && c->h_progress && lc.max_iter < 0xfff;
+        const bool poll = (lc.use_diff || lc.use_bound) && lc.max_iter < 0xfff;
         bool stopped = false;
         for (int it = 0; it < lc.max_iter && !stopped; ++it) {
             c->nn_iter_hint = it;
             s = enqueue_iteration(c, nmax, lc, nullptr, nullptr);
             if (s != ICPMI_OK) return s;
             if (it + 1 >= lc.max_iter || !poll) continue;
-            // as loop_run: stay `ahead` iterations in front of the slowest reading still running; stop when all have stopped
-            for (unsigned spins = 1;; ++spins) {
-                bool all_done = true, may_go = true;
+            // as loop_run: stay `ahead` iterations in front of the slowest reading still running; stop when all have stopped, or when the
+            // stream is idle (everything enqueued has run) and no reading still iterates
+            unsigned v[ICPMI_MAX_BATCH]; bool idle = false, all_done = true;
+            HIP_TRY(c, spin_on_host(c->stream, 256, c->h_progress, B, v, [&](const unsigned* w) {
+                bool may_go = true;
+                all_done = true;
                 for (int b = 0; b < B; ++b) {
-                    const unsigned v = __atomic_load_n(c->h_progress + b, __ATOMIC_ACQUIRE);
-                    const bool mine = ((v >> 12) & 0x7ffffu) == c->reg_seq;
-                    const bool done = mine && (v >> 31);
-                    all_done &= done;
-                    if (!done && !(mine && (int)(v & 0xfffu) + ahead > it)) may_go = false;
+                    const ProgressWord p = decode_progress(w[b], c->reg_seq);
+                    all_done &= p.mine && p.done;
+                    may_go &= p.mine && (p.done || p.iter + ahead > it);
                 }
-                if (all_done) { stopped = true; break; }
-                if (may_go) break;
-                if ((spins & 255u) != 0) continue;
-                const hipError_t qe = hipStreamQuery(c->stream);
-                if (qe != hipSuccess && qe != hipErrorNotReady) HIP_TRY(c, qe); // stream in an error state: terminal
-                if (qe == hipSuccess) {
-                    bool progress = false; // everything enqueued has run: go on only if some reading still iterates
-                    for (int b = 0; b < B; ++b) {
-                        const unsigned w = __atomic_load_n(c->h_progress + b, __ATOMIC_ACQUIRE);
-                        progress |= ((w >> 12) & 0x7ffffu) == c->reg_seq && (w >> 31) == 0 && (int)(w & 0xfffu) > it;
-                    }
-                    stopped = !progress;
-                    break;
-                }
+                return all_done || may_go;
+            }, &idle));
+            stopped = all_done || idle;
+            for (int b = 0; b < B && idle; ++b) {
+                const ProgressWord p = decode_progress(v[b], c->reg_seq);
+                if (p.mine && !p.done && p.iter > it) stopped = false;
             }
         }
     }
@@ -1914,7 +1811,7 @@ icpmi_status loop_single_step(icpmi_ctx* c, int64_t n, const LoopCfg& lc, const 
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (s != ICPMI_OK) return s;
     HIP_TRY(c, e);
-    fill_stats(c, l1, n, stats);
+    fill_stats(c->h_state, l1, n, stats);
     if (c->h_state->error) { c->last_error = "minimize_step: device-side convergence error"; return (icpmi_status)c->h_state->error; }
     if (T_step) memcpy(T_step, hT, sizeof hT);
     if (sums) memcpy(sums, hS, sizeof hS);

@@ -696,11 +696,6 @@ static int run_atomics_cfg()
 // in-place exclusive scan of data[0..n) (counts -> starts); data[n] = total
 icpmi_status device_exclusive_scan(icpmi_ctx* c, unsigned* data, int n, unsigned total) { return device_exclusive_scan_io(c, data, data, n, total); }
 
-static int scan2_enabled()
-{
-    return 1; // (the two-kernel scan, r5; tables beyond SCAN2_MAX_NB chunks take the three-kernel one)
-}
-
 // The count table of a grid build -> the cell starts, in the layout a CURSOR scatter wants (r5): counts[0..n) (+ the occupancy word at
 // counts[n + 1]) -> starts[0] = 0, starts[i + 1] = start of cell i, starts[n + 1] = total.  A scatter then takes its slots with
 // atomicAdd(&starts[key + 1], len): when every point is placed, starts[i + 1] has grown to the start of cell i + 1 -- the array IS the plain
@@ -710,7 +705,7 @@ icpmi_status device_exclusive_scan_cursor(icpmi_ctx* c, unsigned* counts, unsign
 {
     const int nb = (n + SCAN_CHUNK - 1) / SCAN_CHUNK;
     if (ensure_cap(c, &c->d_blocksums, &c->cap_blocksums, (size_t)nb + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
-    if (scan2_enabled() && nb <= SCAN2_MAX_NB) {
+    if (nb <= SCAN2_MAX_NB) { // (the two-kernel scan, r5; tables beyond SCAN2_MAX_NB chunks take the three-kernel one)
         hipLaunchKernelGGL(scan2_sums_kernel, dim3(nb > 0 ? nb : 1), dim3(SCAN_T), 0, c->stream, (const unsigned*)counts, n, c->d_blocksums);
         hipLaunchKernelGGL(scan2_final_kernel, dim3(nb > 0 ? nb : 1), dim3(SCAN_T), 0, c->stream, (const unsigned*)counts, starts, n, (const unsigned*)c->d_blocksums, total, 1,
                            zero_counts ? counts : (unsigned*)nullptr, (unsigned*)nullptr, tail_out);
@@ -727,7 +722,7 @@ icpmi_status device_exclusive_scan_cursor(icpmi_ctx* c, unsigned* counts, unsign
     return ICPMI_OK;
 }
 
-bool device_scan_side_ok(int n) { return scan2_enabled() && (n + SCAN_CHUNK - 1) / SCAN_CHUNK <= SCAN2_MAX_NB; }
+bool device_scan_side_ok(int n) { return (n + SCAN_CHUNK - 1) / SCAN_CHUNK <= SCAN2_MAX_NB; }
 size_t device_scan_side_words(int n) { return (size_t)(n + SCAN_CHUNK - 1) / SCAN_CHUNK + 1; }
 icpmi_status device_exclusive_scan_cursor_side(icpmi_ctx* c, hipStream_t stream, unsigned* sums, unsigned* counts, unsigned* starts, int n, unsigned total)
 {
@@ -765,10 +760,9 @@ icpmi_status device_scan_flags_count(icpmi_ctx* c, const unsigned* flag, unsigne
     *count = 0;
     if (n <= 0) return ICPMI_OK;
     const int nb = (n + SCAN_CHUNK - 1) / SCAN_CHUNK;
-    if (c->d_progress && c->h_progress && scan2_enabled() && nb <= SCAN2_MAX_NB) {
+    if (nb <= SCAN2_MAX_NB) {
         if (ensure_cap(c, &c->d_blocksums, &c->cap_blocksums, (size_t)nb + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
         unsigned* d_word = c->d_progress + ICPMI_PROGRESS_SCAN_WORD;
-        volatile unsigned* h_word = c->h_progress + ICPMI_PROGRESS_SCAN_WORD;
         // r5: the count arrives TAGGED (words 40 / 41 as one 64-bit slot: call number << 32 | count, system-scope release) and the host spins on
         // the tag instead of draining the stream: a drained stream costs the completion signal and the restart of an empty queue (~20 us,
         // DESIGN 13.6e) -- five to seven times per map update --, the word is here ~2 us after the kernel's last workgroup wrote it, and what the
@@ -778,22 +772,11 @@ icpmi_status device_scan_flags_count(icpmi_ctx* c, const unsigned* flag, unsigne
         hipLaunchKernelGGL(scan2_final_kernel, dim3(nb), dim3(SCAN_T), 0, c->stream, flag, pos, n, (const unsigned*)c->d_blocksums, 0u, 0, (unsigned*)nullptr, d_word,
                            (unsigned*)nullptr, tag);
         HIP_TRY(c, hipGetLastError());
-        if (tag) {
-            const volatile unsigned long long* h64 = reinterpret_cast<const volatile unsigned long long*>(c->h_progress + ICPMI_PROGRESS_SCAN_WORD);
-            for (unsigned spins = 1;; ++spins) {
-                const unsigned long long v = __atomic_load_n(h64, __ATOMIC_ACQUIRE);
-                if ((unsigned)(v >> 32) == tag) { *count = (int64_t)(unsigned)(v & 0xffffffffull); return ICPMI_OK; }
-                if ((spins & 1023u) != 0) continue;
-                const hipError_t qe = hipStreamQuery(c->stream);
-                if (qe == hipErrorNotReady) continue;
-                HIP_TRY(c, qe); // (a stream in an error state: nothing will ever write the word)
-                const unsigned long long w = __atomic_load_n(h64, __ATOMIC_ACQUIRE);
-                if ((unsigned)(w >> 32) == tag) { *count = (int64_t)(unsigned)(w & 0xffffffffull); return ICPMI_OK; }
-                c->last_error = "device_scan_flags_count: the count never arrived"; return ICPMI_ERR_HIP;
-            }
-        }
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        *count = (int64_t)*h_word;
+        const unsigned long long* h64 = reinterpret_cast<const unsigned long long*>(c->h_progress + ICPMI_PROGRESS_SCAN_WORD);
+        unsigned long long v = 0;
+        HIP_TRY(c, spin_on_host(c->stream, 1024, h64, 1, &v, [&](const unsigned long long* w) { return (unsigned)(*w >> 32) == tag; }));
+        if ((unsigned)(v >> 32) != tag) { c->last_error = "device_scan_flags_count: the count never arrived"; return ICPMI_ERR_HIP; }
+        *count = (int64_t)(unsigned)(v & 0xffffffffull);
         return ICPMI_OK;
     }
     const icpmi_status s = device_exclusive_scan_io(c, flag, pos, n, 0u);
@@ -813,7 +796,7 @@ __global__ void scan_tail_sum_kernel(const unsigned* __restrict__ pos, const uns
 icpmi_status device_exclusive_scan_sum(icpmi_ctx* c, const unsigned* flag, unsigned* pos, int n, unsigned* d_sum)
 {
     const int nb = (n + SCAN_CHUNK - 1) / SCAN_CHUNK;
-    if (n > 0 && scan2_enabled() && nb <= SCAN2_MAX_NB) {
+    if (n > 0 && nb <= SCAN2_MAX_NB) {
         if (ensure_cap(c, &c->d_blocksums, &c->cap_blocksums, (size_t)nb + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
         hipLaunchKernelGGL(scan2_sums_kernel, dim3(nb), dim3(SCAN_T), 0, c->stream, flag, n, c->d_blocksums);
         hipLaunchKernelGGL(scan2_final_kernel, dim3(nb), dim3(SCAN_T), 0, c->stream, flag, pos, n, (const unsigned*)c->d_blocksums, 0u, 0, (unsigned*)nullptr, d_sum);
@@ -831,7 +814,7 @@ icpmi_status device_exclusive_scan_io(icpmi_ctx* c, const unsigned* in, unsigned
 {
     const int nb = (n + SCAN_CHUNK - 1) / SCAN_CHUNK;
     if (ensure_cap(c, &c->d_blocksums, &c->cap_blocksums, (size_t)nb + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
-    if (scan2_enabled() && nb <= SCAN2_MAX_NB) {
+    if (nb <= SCAN2_MAX_NB) {
         hipLaunchKernelGGL(scan2_sums_kernel, dim3(nb > 0 ? nb : 1), dim3(SCAN_T), 0, c->stream, in, n, c->d_blocksums);
         hipLaunchKernelGGL(scan2_final_kernel, dim3(nb > 0 ? nb : 1), dim3(SCAN_T), 0, c->stream, in, data, n, (const unsigned*)c->d_blocksums, total, 0, (unsigned*)nullptr);
         HIP_TRY(c, hipGetLastError());

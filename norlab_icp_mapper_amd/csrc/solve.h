@@ -614,6 +614,9 @@ __device__ __forceinline__ void publish_progress(const IcpState* st, unsigned* p
     const unsigned v = ((unsigned)(st->done != 0) << 31) | ((st->seq & 0x7ffffu) << 12) | ((unsigned)st->iter & 0xfffu);
     __hip_atomic_store(progress, v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
+// ... as the host reads it: mine = written by registration `seq`
+struct ProgressWord { bool mine, done; int iter; };
+static inline ProgressWord decode_progress(unsigned v, unsigned seq) { return {((v >> 12) & 0x7ffffu) == seq, (v >> 31) != 0, (int)(v & 0xfffu)}; }
 
 
 } // namespace
