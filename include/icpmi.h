@@ -508,6 +508,13 @@ icpmi_status icpmi_trim_cache(void);
 /* Diagnostics of the last registration (engine internals, not part of the reference surface).  Slots 12 / 13 (r5): iterations of a k > 1 loop whose
    quantile selection took its level 0 from the NN kernel's window / from the full histogram behind a window that missed. */
 icpmi_status icpmi_debug_counters(icpmi_handle h, uint64_t out[24]);
+/* Test seam: the matches of the last COUNTED iteration of the last single registration (icpmi_register*) on this handle, in the caller's point
+ * order: row i holds the k matches of reading point i as ORIGINAL map indices, ascending by (d2, index), unfilled slots -1 / +inf; d2 as the
+ * matcher computed it, against the centred map.  T_used (column-major) is the centred-frame pose that iteration's NN launch moved the centred
+ * reading by, i.e. the query of point i was T_used * (p_i - mean).  n / k must be the registration's.  ICPMI_ERR_UNSUPPORTED when there is
+ * nothing to read: no registration yet, one that failed, a batch (icpmi_register_batch_dev), or any other call that reused the matcher's
+ * buffers or changed the map after it. */
+icpmi_status icpmi_debug_last_matches(icpmi_handle h, int64_t n, int32_t k, int32_t* ids, float* d2, float T_used[16]);
 /* Test seam: the n-th value (n >= 1) of the std::minstd_rand stream as the DEVICE computes it by skip-ahead (csrc/ssn.hip, behind
  * SamplingSurfaceNormalDataPointsFilter -- PM::ICPSequence::setDefault(), Mapper.cpp:74-78).  [rand.predef]: seed 1, n = 10 000 -> 399268537. */
 icpmi_status icpmi_debug_minstd_nth(icpmi_handle h, uint32_t seed, uint32_t n, uint32_t* out);

@@ -309,6 +309,39 @@ icpmi_status icpmi_debug_counters(icpmi_handle h, uint64_t out[24])
     return ICPMI_OK;
 }
 
+icpmi_status icpmi_debug_last_matches(icpmi_handle h, int64_t n, int32_t k, int32_t* ids, float* d2, float T_used[16])
+{
+    CHECK_H(h);
+    if (n < 1 || k < 1 || !ids || !d2 || !T_used) { h->last_error = "debug_last_matches: bad arguments"; return ICPMI_ERR_INVALID_ARG; }
+    if (h->last_match_n == 0) {
+        h->last_error = "debug_last_matches: no single registration's matches on this handle (none ran, it failed, or a batch / another call came after it)";
+        return ICPMI_ERR_UNSUPPORTED;
+    }
+    if (n != h->last_match_n || k != h->last_match_k) { h->last_error = "debug_last_matches: n / k differ from the last registration's"; return ICPMI_ERR_INVALID_ARG; }
+    // the layout overlap_kernel reads (loop.hip): element e = slot * k + j, slot = the caller's index or -- sorted -- qindex[slot]
+    const size_t cnt = (size_t)n * k;
+    DevBuf<int> d_ids;
+    HIP_TRY(h, d_ids.alloc(cnt));
+    icpmi_status s = nn_ids_to_original(h, h->d_sidx, (int64_t)cnt, d_ids);
+    if (s != ICPMI_OK) return s;
+    std::vector<int> hid(cnt), hq(h->last_match_sorted ? (size_t)n : 0);
+    std::vector<float> hd(cnt);
+    HIP_TRY(h, hipMemcpyAsync(hid.data(), d_ids, cnt * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(hd.data(), h->d_d2, cnt * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    if (h->last_match_sorted) HIP_TRY(h, hipMemcpyAsync(hq.data(), h->d_qindex, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(T_used, h->d_state->T_prev, 16 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    for (int64_t slot = 0; slot < n; ++slot) {
+        const int64_t oi = h->last_match_sorted ? hq[slot] : slot;
+        if (oi < 0 || oi >= n) { h->last_error = "debug_last_matches: query index out of range"; return ICPMI_ERR_HIP; }
+        for (int j = 0; j < k; ++j) {
+            ids[oi * k + j] = hid[slot * k + j];
+            d2[oi * k + j] = hd[slot * k + j];
+        }
+    }
+    return ICPMI_OK;
+}
+
 icpmi_status icpmi_debug_minstd_nth(icpmi_handle h, uint32_t seed, uint32_t n, uint32_t* out)
 {
     CHECK_H(h);

@@ -220,7 +220,7 @@ struct IcpState {
     unsigned long long hard_total;
     unsigned seq;                // registration sequence number (tag of the progress word, see icpmi_ctx::h_progress)
     unsigned long long dbg[24];  // diagnostics: NN phase cycles with -DICPMI_NN_TIMING (scripts/nn_phase.py), [20]/[21] serial solve cycles / calls
-    float T_prev[16];            // T_iter BEFORE the last minimisation (kept when LoopCfg::sensor_noise: getOverlap() looks at that step's pairs)
+    float T_prev[16];            // T_iter BEFORE the last minimisation: the pose the last counted iteration's pairs were formed under
     // result
     float T_out[16];
     // r5: device clocks (wall_clock64, 100 MHz) of the first kernel of the registration's head and of the solve that stopped the loop:
@@ -546,6 +546,9 @@ struct icpmi_ctx {
     float4* nn_match_pt = nullptr;    // set by the loop: keep the loop state (sidx, d2, matched point) in query order
     bool nn_out_sorted = false;       // set by the NN launcher: true if the launched kernel did so
     bool nn_sorted_k = false;         // set by the loop for k > 1: keep the k matches of a query at its slot of the tile-sorted order
+    // what icpmi_debug_last_matches reads: n and k of the last single registration whose matches are still in d_sidx / d_d2 (0 = none), and
+    // whether they are in the tile-sorted query order (d_qindex).  Cleared by everything else that writes those buffers or moves the map.
+    int64_t last_match_n = 0; int last_match_k = 0; bool last_match_sorted = false;
     IcpState* d_state = nullptr;                               // ICPMI_MAX_BATCH states (a single registration uses the first)
     IcpState* h_state = nullptr;                               // pinned mirror (ICPMI_MAX_BATCH)
     bool zero_pending = false;                                 // d_state / d_selhist still to be cleared: on the stream the handle really uses, at its first call (zero_state_if_pending)
@@ -647,6 +650,7 @@ static inline void drop_loop_graphs(icpmi_ctx* c)
     if (c->graphs.seg[0].exec) c->seg_wasted = c->graphs.seg[0].uses <= 1 ? c->seg_wasted + 1 : 0;
     ++c->map_epoch;
     c->graphs.reset();
+    c->last_match_n = 0;
 }
 
 // scratch device allocation of one call: freed on every exit path (hipFree waits for work still using it)

@@ -1435,6 +1435,7 @@ icpmi_status loop_run(icpmi_ctx* c, const float4* d_scan, const float* d_normals
                       float T_out[16], icpmi_stats* stats)
 {
     LoopCfg lc = lc_in;
+    c->last_match_n = 0;
     // all allocations up front: none may happen while the stream is capturing
     if (ensure_loop_buffers(c, n, lc.k) != ICPMI_OK) return ICPMI_ERR_HIP;
     if (chain_has_vartrimmed(lc)) { VtBuffers vb; if (vt_buffers(c, n * lc.k, &vb) != ICPMI_OK) return ICPMI_ERR_HIP; }
@@ -1635,9 +1636,11 @@ icpmi_status loop_run(icpmi_ctx* c, const float4* d_scan, const float* d_normals
         }
         stats->sensor_noise_overlap = -1.f;
     }
+    // the last counted iteration's matches stay in the loop's buffers (dead iterations behind the stop early-exit before they write)
+    const bool sorted_state = graph ? c->graphs.fixed.sorted : (segmented ? c->graphs.seg[1].sorted : c->nn_out_sorted);
+    if (!c->h_state->error && c->h_state->iter > 0) { c->last_match_n = n; c->last_match_k = lc.k; c->last_match_sorted = sorted_state; }
     if (lc.sensor_noise && stats && !c->h_state->error && c->h_state->iter > 0) {
         // ErrorMinimizer::getOverlap() with sensor noise: one pass over the last iteration's pairs, still in the loop's buffers
-        const bool sorted_state = graph ? c->graphs.fixed.sorted : (segmented ? c->graphs.seg[1].sorted : c->nn_out_sorted);
         const icpmi_status os = loop_sensor_noise_overlap(c, n, lc, sorted_state, &stats->sensor_noise_overlap);
         if (os != ICPMI_OK) return os;
     }
@@ -1675,6 +1678,7 @@ static void batch_result(icpmi_ctx* c, const LoopCfg& lc, const IcpState* hs, in
 icpmi_status loop_run_batch(icpmi_ctx* c, int B, const float* const* d_scans4, const int64_t* nn, const LoopCfg& lc, bool fixed, float* T_out,
                             icpmi_stats* stats, icpmi_status* status)
 {
+    c->last_match_n = 0; // (icpmi_debug_last_matches serves single registrations only)
     int64_t nmax = 0;
     for (int b = 0; b < B; ++b) nmax = nn[b] > nmax ? nn[b] : nmax;
     const int64_t NS = (nmax + 63) / 64 * 64; // slice stride of the per-query arrays
@@ -1821,6 +1825,7 @@ icpmi_status loop_single_step(icpmi_ctx* c, int64_t n, const LoopCfg& lc, const 
 icpmi_status loop_outlier_weights(icpmi_ctx* c, const LoopCfg& lc, const float* d2, const int32_t* ids, int k, int64_t n,
                                   const float* read_normals3, float* weights, float* limit_out)
 {
+    c->last_match_n = 0; // (d2 / ids of the caller go through the loop's buffers)
     // matches arrive with ORIGINAL ids; the device's normals table is in sorted order.  SurfaceNormalOutlierFilter (r4) reads the map's
     // normals from the resident copy instead, which IS in the caller's order (d_raw_n3, padded to float4 for the kernel).
     bool needs_sn = false;

@@ -1634,6 +1634,7 @@ static icpmi_status nnk_launch_t(icpmi_ctx* c, const float4* d_reading, int64_t 
 icpmi_status nn_launch_k(icpmi_ctx* c, const float4* d_reading, int64_t n, const float* d_T, const LoopCfg& lc, int allow_self,
                          int* d_sidx, float* d_d2, IcpState* d_state)
 {
+    c->last_match_n = 0; // (loop_run sets it again once its last iteration is in)
     if (lc.k == 1) return nn_launch_k1(c, d_reading, n, d_T, lc, allow_self, d_sidx, d_d2, d_state);
     if (lc.k <= 4) return nnk_launch_t<4>(c, d_reading, n, d_T, lc, allow_self, d_sidx, d_d2, d_state);
     if (lc.k <= 6) return nnk_launch_t<6>(c, d_reading, n, d_T, lc, allow_self, d_sidx, d_d2, d_state); // knn 6: the documented chain

@@ -537,7 +537,7 @@ __device__ void solve_serial(IcpState* st, const double* tot, const LoopCfg& lc,
 
     float Ti[16];
     mat4_mul_dev(Ts, st->T_iter, Ti);
-    if (lc.sensor_noise) for (int i = 0; i < 16; ++i) st->T_prev[i] = st->T_iter[i]; // the pose this step's pairs were formed under
+    for (int i = 0; i < 16; ++i) st->T_prev[i] = st->T_iter[i]; // the pose this step's pairs were formed under (sensor-noise overlap, icpmi_debug_last_matches)
     for (int i = 0; i < 16; ++i) st->T_iter[i] = Ti[i];
     st->iter += 1;
 

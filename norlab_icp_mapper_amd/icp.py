@@ -247,6 +247,7 @@ class ICPSequence:
         self._h = h
         self.stats = _capi.Stats()
         self.errorMinimizer = _ErrorMinimizerView(self)
+        self._last_n = 0
 
     @classmethod
     def loadFromYaml(cls, chain, **engine):
@@ -307,6 +308,7 @@ class ICPSequence:
             scan_normals = _f32c(scan_normals, 3)
             nptr = scan_normals.ctypes.data
         T = (C.c_float * 16)()
+        self._last_n = scan.shape[0]
         st = self._lib.icpmi_register(self._h, scan.ctypes.data, scan.shape[0], nptr, T, C.byref(self.stats))
         self._check(st)
         return _T_from_c(T[:])
@@ -323,6 +325,7 @@ class ICPSequence:
 
     def registerDev(self, d_scan_ptr, n, fixed_iterations=0, d_normals_ptr=None):
         T = (C.c_float * 16)()
+        self._last_n = int(n)
         if fixed_iterations > 0:
             st = self._lib.icpmi_register_fixed_dev(self._h, d_scan_ptr, n, d_normals_ptr, fixed_iterations, T, C.byref(self.stats))
         else:
@@ -617,7 +620,7 @@ class ICPSequence:
         P = _T_to_c(prior)
         T = (C.c_float * 16)()
         self._check(self._lib.icpmi_register_prior(self._h, sc.ctypes.data, sc.shape[0], P.ctypes.data, T, C.byref(self.stats)))
-        self._staged_n = sc.shape[0]
+        self._staged_n = self._last_n = sc.shape[0]
         return _T_from_c(T[:])
 
     def registerWithPriorDev(self, d_scan_ptr, n, prior):
@@ -625,7 +628,7 @@ class ICPSequence:
         P = _T_to_c(prior)
         T = (C.c_float * 16)()
         self._check(self._lib.icpmi_register_prior_dev(self._h, d_scan_ptr, n, P.ctypes.data, T, C.byref(self.stats)))
-        self._staged_n = n
+        self._staged_n = self._last_n = n
         return _T_from_c(T[:])
 
     def mapUpdateStaged(self, correction, min_dist, normals_knn=0, return_keep=False):
@@ -755,6 +758,18 @@ class ICPSequence:
 
     def setStream(self, hip_stream_ptr):
         self._check(self._lib.icpmi_set_stream(self._h, hip_stream_ptr))
+
+    def lastMatches(self, n=None):
+        """icpmi_debug_last_matches: (ids (n, k) int32, d2 (n, k) float32, T_used 4x4) of the last counted iteration of the last single
+        registration, rows in the reading's order; T_used is the centred-frame pose its queries were moved by.  n defaults to the size of
+        the last reading registered through this object."""
+        n = self._last_n if n is None else int(n)
+        k = int(self.cfg.knn)
+        ids = np.empty((n, k), dtype=np.int32)
+        d2 = np.empty((n, k), dtype=np.float32)
+        T = (C.c_float * 16)()
+        self._check(self._lib.icpmi_debug_last_matches(self._h, n, k, ids.ctypes.data, d2.ctypes.data, T))
+        return ids, d2, _T_from_c(T[:])
 
     def debugCounters(self):
         out = (C.c_uint64 * 24)()
