@@ -374,6 +374,27 @@ icpmi_status icpmi_sampling_surface_normal_ex(icpmi_handle h, const float* in4, 
 icpmi_status icpmi_octree_sample(icpmi_handle h, const float* in4, int64_t n, float max_size, int32_t max_points, int32_t method,
                                  int32_t* order_out, int32_t* leaf_of_out, int64_t* n_out);
 
+/* `VoxelGridDataPointsFilter{vSizeX, vSizeY, vSizeZ, useCentroid: 1, averageExistingDescriptors}` (libpointmatcher
+ * DataPointsFilters/VoxelGrid, AS RECALLED: upstream's source is not on hand; every quantity is float32, every division
+ * correctly rounded, no contraction):
+ *   minV / maxV = per-axis minimum / maximum of the coordinates; minB = minV / vsize, maxB = maxV / vsize;
+ *   numDiv[a] = (unsigned)((1 + maxB[a]) - minB[a]) (left to right in float, then truncated);
+ *   point p: i = (unsigned)floor(x_p / vsize[0] - minB[0]), j and k the same on y and z;
+ *   idx = i + j numDiv[0] + k numDiv[0] numDiv[1] in unsigned 32-bit arithmetic.
+ * The points of one idx form a voxel; its first point is the member with the smallest index.  Output: one point per voxel, in
+ * ascending order of first-point index.  x, y, z = the centroid: the first point's value, plus every other member in ascending
+ * index order (one float add at a time), divided by (float)count; the homogeneous row is the first point's.  Descriptors
+ * (desc: point-major, n x desc_rows; NULL when desc_rows == 0): average_descriptors = 1 averages every row the same way
+ * (normals are not renormalised), 0 keeps the first point's rows (upstream's doc says "drop"; its compaction as recalled
+ * copies the columns).  A planar cloud (z = 0) gives numDiv[2] = 1, k = 0: upstream's 2-D formula.
+ * order_out (the first-point index of every output point, may be NULL), out4 (4 per point) and desc_out (desc_rows per point)
+ * have capacity n; *n_out = the number of voxels.  ICPMI_ERR_INVALID_ARG (last_error says why): a vsize that is not finite
+ * and > 0, non-finite coordinates, numDiv[a] >= 2^24 on some axis, numDiv[0] numDiv[1] numDiv[2] > 2^32 - 1 (computed in
+ * 64 bits).  n > 2^31 - 1: ICPMI_ERR_UNSUPPORTED; n == 0: nothing to do.  Entirely on the device, no float atomics: two calls
+ * give the same bits (csrc/voxelgrid.hip). */
+icpmi_status icpmi_voxel_grid(icpmi_handle h, const float* in4, int64_t n, const float vsize[3], int32_t average_descriptors, const float* desc,
+                              int32_t desc_rows, int32_t* order_out, float* out4, float* desc_out, int64_t* n_out);
+
 /* `Map::updateLocalPointCloud` (Map.cpp:502-534) for a whole module chain on the RESIDENT map: the mapper modules
  * (`mapperModuleVec`, Map.cpp:506-521) and then the post filters (Map.cpp:523-525) run as one program on the device copy
  * of the map; only the scan crosses PCIe.  The device tracks the features, the `normals` and ONE scalar descriptor of

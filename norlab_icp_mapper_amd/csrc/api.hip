@@ -918,6 +918,21 @@ icpmi_status icpmi_octree_sample(icpmi_handle h, const float* in4, int64_t n, fl
     return ops_octree_sample(h, in4, n, max_size, max_points, method, order_out, leaf_of_out, n_out);
 }
 
+icpmi_status icpmi_voxel_grid(icpmi_handle h, const float* in4, int64_t n, const float vsize[3], int32_t average_descriptors, const float* desc,
+                              int32_t desc_rows, int32_t* order_out, float* out4, float* desc_out, int64_t* n_out)
+{
+    CHECK_H(h);
+    if (n_out) *n_out = 0;
+    if (n < 0 || !n_out || (n > 0 && (!in4 || !out4)) || !vsize || desc_rows < 0 || (desc_rows > 0 && n > 0 && (!desc || !desc_out)) ||
+        (average_descriptors != 0 && average_descriptors != 1)) {
+        h->last_error = "voxel_grid: bad arguments"; return ICPMI_ERR_INVALID_ARG;
+    }
+    for (int r = 0; r < 3; ++r)
+        if (!(vsize[r] > 0.f) || !std::isfinite(vsize[r])) { h->last_error = "voxel_grid: vSizeX / vSizeY / vSizeZ must be finite and > 0"; return ICPMI_ERR_INVALID_ARG; }
+    if (n > 0x7fffffffll) { h->last_error = "voxel_grid: more than 2^31 - 1 points"; return ICPMI_ERR_UNSUPPORTED; }
+    return ops_voxel_grid(h, in4, n, vsize, average_descriptors, desc_rows > 0 ? desc : nullptr, desc_rows, order_out, out4, desc_out, n_out);
+}
+
 icpmi_status icpmi_voxel_keep_first(icpmi_handle h, const float* in4, int64_t n, float edge, uint8_t* keep)
 {
     return icpmi_voxel_keep(h, in4, n, edge, 0, keep);

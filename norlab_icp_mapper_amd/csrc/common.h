@@ -970,3 +970,5 @@ icpmi_status octree_sample_dev(icpmi_ctx* c, const float4* d_in, int64_t n, floa
                                int64_t* n_out);
 icpmi_status ops_octree_sample(icpmi_ctx* c, const float* in4, int64_t n, float max_size, int max_pts, int method, int32_t* order_out,
                                int32_t* leaf_of_out, int64_t* n_out);
+icpmi_status ops_voxel_grid(icpmi_ctx* c, const float* in4, int64_t n, const float vsize[3], int average, const float* desc, int rows,
+                            int32_t* order_out, float* out4, float* desc_out, int64_t* n_out);

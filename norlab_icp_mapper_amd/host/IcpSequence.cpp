@@ -267,7 +267,10 @@ bool GpuICPSequence::setMap(const DataPoints& mapIn)
     if (referenceDataPointsFilters && referenceDataPointsFilters->size()) {
         // upstream filters the CENTRED copy of the map (mean subtracted first): filters that look at coordinates
         // (BoundingBox, DistanceLimit) mean them relative to the centroid.  The original coordinates ride along as a descriptor
-        // and are put back afterwards, so that the core centres the very points the caller handed in.
+        // and are put back afterwards, so that the core centres the very points the caller handed in -- unless a filter moves points
+        // (VoxelGrid): its output is centred centroids, which get the mean added back (the `else` below).
+        bool moves = false;
+        for (const auto& f : referenceDataPointsFilters->filters) moves |= f->movesFeatures();
         filtered = mapIn;
         const size_t n = filtered.getNbPoints();
         double mean[3] = {0, 0, 0};
@@ -275,7 +278,7 @@ bool GpuICPSequence::setMap(const DataPoints& mapIn)
         std::vector<float> orig(3 * n);
         for (size_t i = 0; i < n; ++i)
             for (int r = 0; r < 3; ++r) { orig[3 * i + r] = filtered.col(i)[r]; filtered.col(i)[r] = (float)(filtered.col(i)[r] - mean[r] / (double)n); }
-        filtered.addDescriptor("__icpmi_original_xyz", 3, std::move(orig));
+        if (!moves) filtered.addDescriptor("__icpmi_original_xyz", 3, std::move(orig));
         referenceDataPointsFilters->apply(filtered);
         const size_t m = filtered.getNbPoints();
         if (filtered.descriptorExists("__icpmi_original_xyz")) {
@@ -877,6 +880,50 @@ struct OctreeGridFilter : DataPointsFilter {
     }
 };
 
+// VoxelGridDataPointsFilter{vSizeX, vSizeY, vSizeZ, useCentroid, averageExistingDescriptors} (libpointmatcher, as recalled;
+// the formulation is icpmi_voxel_grid's in include/icpmi.h): one point per occupied voxel of upstream's bounding-box lattice, the
+// centroid of its members, in ascending order of the voxel's first point.  The grid, the sort and the sums live on the device; here
+// every descriptor row is packed point-major for it, and the cloud is rebuilt with the names, spans and order of the input.  `times`
+// keep the first point's values.  useCentroid: 0 is refused at creation.
+struct VoxelGridFilter : DataPointsFilter {
+    float vsize[3] = {1.f, 1.f, 1.f}; bool averageDescriptors = true;
+    icpmi_handle h = nullptr;
+    bool movesFeatures() const override { return true; }
+    void inPlaceFilter(DataPoints& c) const override {
+        const size_t n = c.getNbPoints();
+        if (n == 0) return;
+        if (!h) throw std::logic_error("VoxelGridDataPointsFilter needs a GPU context");
+        int rows = 0;
+        for (const auto& d : c.descriptors) rows += d.span;
+        std::vector<float> desc((size_t)rows * n), descOut((size_t)rows * n), out4(4 * n);
+        for (size_t i = 0, r0 = 0; i < c.descriptors.size(); r0 += (size_t)c.descriptors[i].span, ++i) {
+            const Descriptor& d = c.descriptors[i];
+            for (size_t p = 0; p < n; ++p)
+                for (int r = 0; r < d.span; ++r) desc[(size_t)rows * p + r0 + r] = d.data[(size_t)d.span * p + r];
+        }
+        std::vector<int32_t> order(n);
+        int64_t m = 0;
+        GpuICPSequence::check(h, icpmi_voxel_grid(h, c.features.data(), (int64_t)n, vsize, averageDescriptors ? 1 : 0, rows ? desc.data() : nullptr, rows,
+                                                  order.data(), out4.data(), rows ? descOut.data() : nullptr, &m));
+        DataPoints out = c.createSimilarEmpty((size_t)m);
+        out.features.assign(out4.begin(), out4.begin() + 4 * m);
+        for (size_t i = 0, r0 = 0; i < out.descriptors.size(); r0 += (size_t)out.descriptors[i].span, ++i) {
+            Descriptor& d = out.descriptors[i];
+            d.data.resize((size_t)d.span * m);
+            for (size_t p = 0; p < (size_t)m; ++p)
+                for (int r = 0; r < d.span; ++r) d.data[(size_t)d.span * p + r] = descOut[(size_t)rows * p + r0 + r];
+        }
+        for (size_t k = 0; k < out.times.size(); ++k) {
+            const TimeField& s = c.times[k];
+            TimeField& t = out.times[k];
+            t.data.resize((size_t)t.span * m);
+            for (size_t p = 0; p < (size_t)m; ++p)
+                std::copy(s.data.begin() + (size_t)s.span * order[p], s.data.begin() + (size_t)s.span * (order[p] + 1), t.data.begin() + (size_t)t.span * p);
+        }
+        c = std::move(out);
+    }
+};
+
 float getf(const yaml::Node& p, const char* k, float def) { return p[k] ? p[k].as<float>() : def; }
 int geti(const yaml::Node& p, const char* k, int def) { return p[k] ? p[k].as<int>() : def; }
 
@@ -989,6 +1036,19 @@ std::shared_ptr<DataPointsFilter> createDataPointsFilter(const std::string& name
         f->maxSize = getf(p, "maxSizeByNode", 0.f); f->method = geti(p, "samplingMethod", 0);
         f->maxPointByNode = geti(p, "maxPointByNode", 1);
         if (f->maxSize < 0.f || f->maxPointByNode < 1 || f->method < 0 || f->method > 3) throw InvalidParameter(name + ": parameter out of range");
+        f->h = ctx;
+        return f;
+    }
+    if (name == "VoxelGridDataPointsFilter") {
+        requireKnown(p, {"vSizeX", "vSizeY", "vSizeZ", "useCentroid", "averageExistingDescriptors"}, name);
+        if (geti(p, "useCentroid", 1) == 0)
+            throw InvalidParameter(name + ": useCentroid: 0 (voxel centres) is not supported: upstream's centre branch, as recalled, "
+                                          "writes the centre without the grid origin and cannot be checked");
+        auto f = std::make_shared<VoxelGridFilter>();
+        f->vsize[0] = getf(p, "vSizeX", 1.f); f->vsize[1] = getf(p, "vSizeY", 1.f); f->vsize[2] = getf(p, "vSizeZ", 1.f);
+        for (float v : f->vsize)
+            if (!(v > 0.f) || !std::isfinite(v)) throw InvalidParameter(name + ": vSizeX / vSizeY / vSizeZ must be finite and > 0");
+        f->averageDescriptors = geti(p, "averageExistingDescriptors", 1) != 0;
         f->h = ctx;
         return f;
     }

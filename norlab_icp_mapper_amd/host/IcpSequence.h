@@ -118,6 +118,8 @@ public:
     // false when two calls on the same cloud may differ (RandomSampling seeded from std::random_device): such a filter cannot
     // serve as a readingStepDataPointsFilter, which the accelerated loop applies once instead of once per iteration
     virtual bool repeatable() const { return true; }
+    // true when the kept points get new coordinates (VoxelGrid's centroids): setMap then cannot put the caller's coordinates back
+    virtual bool movesFeatures() const { return false; }
 };
 
 class DataPointsFilters {

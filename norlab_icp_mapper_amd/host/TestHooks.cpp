@@ -39,4 +39,51 @@ int nim_test_filter_chain(icpmi_handle h, const char* yaml_seq, const float* in4
     }
 }
 
+// the same with one float descriptor AND one int64 `times` row group (`time_name`, time_span x n, may be NULL): out_times
+// (time_span x n) receives it after filtering.  Descriptors and times are (span x n) column-major, like the DataPoints.
+int nim_test_filter_chain_times(icpmi_handle h, const char* yaml_seq, const float* in4, int64_t n, const char* desc_name, int desc_span,
+                                const float* desc, const char* time_name, int time_span, const int64_t* times, float* out4, float* out_desc,
+                                int64_t* out_times, int64_t* n_out, char* err, int err_cap)
+{
+    try {
+        nim::DataPoints c((size_t)n);
+        std::memcpy(c.features.data(), in4, sizeof(float) * 4 * (size_t)n);
+        if (desc_name && desc) c.addDescriptor(desc_name, desc_span, std::vector<float>(desc, desc + (size_t)desc_span * n));
+        if (time_name && times) c.addTime(time_name, time_span, std::vector<int64_t>(times, times + (size_t)time_span * n));
+        nim::DataPointsFilters chain(nim::yaml::Load(yaml_seq), h);
+        chain.apply(c);
+        const size_t m = c.getNbPoints();
+        std::memcpy(out4, c.features.data(), sizeof(float) * 4 * m);
+        if (desc_name && out_desc && c.descriptorExists(desc_name)) std::memcpy(out_desc, c.getDescriptorByName(desc_name).data.data(), sizeof(float) * (size_t)desc_span * m);
+        if (time_name && out_times && c.timeExists(time_name)) std::memcpy(out_times, c.getTimeByName(time_name).data.data(), sizeof(int64_t) * (size_t)time_span * m);
+        *n_out = (int64_t)m;
+        return 0;
+    } catch (const std::exception& e) {
+        if (err && err_cap > 0) { std::strncpy(err, e.what(), (size_t)err_cap - 1); err[err_cap - 1] = 0; }
+        return 1;
+    }
+}
+
+// GpuICPSequence on device 0: loadFromYamlNode(yaml_icp) (the `icp:` sub-tree), setMap(in4), then the resident map as the core holds it
+// (downloadMap): what the referenceDataPointsFilters chain made of the cloud.  out4: capacity 4 n.  Returns 0, or 1 with the text in err.
+int nim_test_icp_set_map(const char* yaml_icp, const float* in4, int64_t n, float* out4, int64_t* n_out, char* err, int err_cap)
+{
+    try {
+        nim::DataPoints c((size_t)n);
+        std::memcpy(c.features.data(), in4, sizeof(float) * 4 * (size_t)n);
+        nim::GpuICPSequence icp(0);
+        icp.loadFromYamlNode(nim::yaml::Load(yaml_icp));
+        *n_out = 0;
+        if (!icp.setMap(c)) return 0;
+        const nim::DataPoints m = icp.downloadMap();
+        if (m.getNbPoints() > (size_t)n) throw std::runtime_error("the resident map is larger than the input");
+        std::memcpy(out4, m.features.data(), sizeof(float) * 4 * m.getNbPoints());
+        *n_out = (int64_t)m.getNbPoints();
+        return 0;
+    } catch (const std::exception& e) {
+        if (err && err_cap > 0) { std::strncpy(err, e.what(), (size_t)err_cap - 1); err[err_cap - 1] = 0; }
+        return 1;
+    }
+}
+
 } // extern "C"

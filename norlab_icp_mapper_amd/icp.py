@@ -493,6 +493,32 @@ class ICPSequence:
                                                   None if leaf is None else leaf.ctypes.data, C.byref(m)))
         return (order[:m.value].copy(), leaf) if with_leaves else order[:m.value].copy()
 
+    def voxelGrid(self, cloud, vsize, average_descriptors=True, descriptors=None):
+        """VoxelGridDataPointsFilter (useCentroid: 1; the formulation of icpmi_voxel_grid, as recalled): vsize = one edge or
+        (vSizeX, vSizeY, vSizeZ); descriptors = (N, rows) or (N,) point-major, or None.  Returns (order, out4, desc_out):
+        the first-point index of every voxel in ascending order, the centroids (N', 4) and the descriptor rows (N', rows)
+        -- averaged, or the first point's when average_descriptors is False -- or None without descriptors."""
+        c = _f32c(cloud, 4)
+        n = c.shape[0]
+        vs = np.broadcast_to(np.asarray(vsize, dtype=np.float32), (3,)).copy()
+        d = None
+        rows = 0
+        if descriptors is not None:
+            d = np.ascontiguousarray(descriptors, dtype=np.float32)
+            d = d.reshape(n, 1) if d.ndim == 1 else d
+            if d.ndim != 2 or d.shape[0] != n:
+                raise InvalidParameter(f"descriptors must be ({n}, rows), got {d.shape}")
+            rows = d.shape[1]
+        order = np.empty(n, dtype=np.int32)
+        out4 = np.empty((n, 4), dtype=np.float32)
+        dout = np.empty((n, rows), dtype=np.float32) if d is not None else None
+        m = C.c_int64(0)
+        self._check(self._lib.icpmi_voxel_grid(self._h, c.ctypes.data, n, vs.ctypes.data, 1 if average_descriptors else 0,
+                                               None if d is None else d.ctypes.data, rows, order.ctypes.data, out4.ctypes.data,
+                                               None if dout is None else dout.ctypes.data, C.byref(m)))
+        k = m.value
+        return order[:k].copy(), out4[:k].copy(), (None if dout is None else dout[:k].copy())
+
     def voxelKeep(self, cloud, edge, method=0):
         """Same lattice, representative by `samplingMethod`: 0 first point, 1 pseudo-random point (smallest fmix32 of the index)."""
         c = _f32c(cloud, 4)
