@@ -148,7 +148,10 @@ typedef struct {
                                /* (1 + epsilon) x the exact j-th distance (tests/test_gpu_epsilon.py); WHICH valid answer comes back differs from     */
                                /* libnabo's (its pick depends on the kd-tree's traversal order).  0 (default): the exact search.  k <= 16; filters'   */
                                /* own searches (PointDistance, SurfaceNormal) stay exact.                                                              */
-    int32_t reserved[4];
+    int32_t covariance;        /* PointToPlaneWithCovErrorMinimizer: 1 = every single registration leaves the 6 x 6 pose covariance for       */
+                               /* icpmi_get_covariance (two launches after the loop); point-to-plane on 3-D clouds only.  Default 0.          */
+    float   sensor_std_dev;    /* PointToPlaneWithCovErrorMinimizer.sensorStdDev: sigma of the range noise, finite and >= 0, default 0.01    */
+    int32_t reserved[2];
 } icpmi_config;
 
 /* What PM::ICPSequence exposes after a call: errorMinimizer->getOverlap() (Mapper.cpp:219) is
@@ -536,6 +539,28 @@ icpmi_status icpmi_debug_counters(icpmi_handle h, uint64_t out[24]);
  * nothing to read: no registration yet, one that failed, a batch (icpmi_register_batch_dev), or any other call that reused the matcher's
  * buffers or changed the map after it. */
 icpmi_status icpmi_debug_last_matches(icpmi_handle h, int64_t n, int32_t k, int32_t* ids, float* d2, float T_used[16]);
+
+/* `errorMinimizer->getCovariance()` of PointToPlaneWithCovErrorMinimizer (upstream's formulation as recalled; Censi's closed form).
+ * Needs icpmi_config::covariance = 1 (point-to-plane, 3-D clouds; force2D / force4DOF do not change the formula).  The pairs are those
+ * of the LAST COUNTED iteration of the last single registration: error elements e = (query i, slot j) with weight w_e > 0 -- the weight
+ * only decides whether a pair is in, its value is not used.  Everything is in the centred frame (the map minus its mean mu), as upstream's:
+ *   p = T_prev (p_i - mu)   the query exactly as that iteration's NN launch formed it (T_prev = icpmi_debug_last_matches' T_used)
+ *   q = m_s - mu, n = the map normal of s as stored
+ *   r = |p|, d = p / r, rho = |q|, u = q / rho          (ranges measured from the map centroid, as upstream does)
+ *   T_s = T_iter T_prev^-1 (the last step; T_prev^-1 = [R^T | -R^T t]), beta = -asin(T_s[2,0]), alpha = atan2(T_s[2,1], T_s[2,2]),
+ *     gamma = atan2(T_s[1,0] / cos beta, T_s[0,0] / cos beta), t = T_s[0:3, 3]
+ *   c = d x n, L = [[1, -gamma, beta], [gamma, 1, -alpha], [-beta, alpha, 1]]
+ *   E = n . (L p + t - q),  N_r = n . (L d),  N_q = -n . u
+ *   h = (n, r c),  a = (n N_r, c (E + r N_r)),  b = (n N_q, r c N_q)
+ *   H = sum h h^T,  S = sum (a a^T + b b^T),  Cov = sigma^2 H^-1 S H^-1   (sigma = sensor_std_dev)
+ * a / b are the derivatives of the gradient of the linearised cost sum E^2 by the reading range r and the reference range rho (the
+ * factors 2 cancel).  Parameter order (tx, ty, tz, alpha, beta, gamma); `cov` is float, 6 x 6, column-major (PM::Matrix), exactly
+ * symmetric.  The sums run in double on the device, per workgroup and then in a fixed order: no float atomics, two identical calls
+ * give the same bits.  H not positive definite (a double Cholesky meets a pivot <= 0): Cov = FLT_MAX I, upstream's "cannot estimate".
+ * A pair at zero range gives NaN, as upstream.  ICPMI_ERR_UNSUPPORTED when there is nothing to read: covariance not asked for, no
+ * registration yet, one that failed, a batch (icpmi_register_batch_dev), or any other call that reused the matcher's buffers or changed
+ * the map after it -- the same rule as icpmi_debug_last_matches. */
+icpmi_status icpmi_get_covariance(icpmi_handle h, float cov[36]);
 /* Test seam: the n-th value (n >= 1) of the std::minstd_rand stream as the DEVICE computes it by skip-ahead (csrc/ssn.hip, behind
  * SamplingSurfaceNormalDataPointsFilter -- PM::ICPSequence::setDefault(), Mapper.cpp:74-78).  [rand.predef]: seed 1, n = 10 000 -> 399268537. */
 icpmi_status icpmi_debug_minstd_nth(icpmi_handle h, uint32_t seed, uint32_t n, uint32_t* out);

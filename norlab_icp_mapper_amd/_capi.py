@@ -55,7 +55,9 @@ class Config(C.Structure):
         ("knn_wg_from", C.c_int32),
         ("sel_window_off", C.c_int32),
         ("epsilon_approx", C.c_int32),
-        ("reserved", C.c_int32 * 4),
+        ("covariance", C.c_int32),
+        ("sensor_std_dev", C.c_float),
+        ("reserved", C.c_int32 * 2),
     ]
 
 
@@ -154,6 +156,7 @@ SYMBOLS = [
     ("icpmi_set_stream", C.c_int, [_P, _P]),
     ("icpmi_debug_counters", C.c_int, [_P, C.POINTER(C.c_uint64)]),
     ("icpmi_debug_last_matches", C.c_int, [_P, C.c_int64, C.c_int32, _P, _P, _F]),
+    ("icpmi_get_covariance", C.c_int, [_P, _F]),
     ("icpmi_debug_minstd_nth", C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]),
     ("icpmi_get_grid_info", C.c_int, [_P, _F, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
 ]

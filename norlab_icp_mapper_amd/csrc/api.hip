@@ -84,6 +84,8 @@ void icpmi_config_default(icpmi_config* cfg)
     cfg->grid_cell = 0.f;
     cfg->use_graph = 1;
     cfg->profile = 0;
+    cfg->covariance = 0;
+    cfg->sensor_std_dev = 0.01f; // PointToPlaneWithCovErrorMinimizer.sensorStdDev
 }
 
 static icpmi_status validate_config(const icpmi_config* cfg, std::string& err)
@@ -122,6 +124,12 @@ static icpmi_status validate_config(const icpmi_config* cfg, std::string& err)
     if (cfg->max_iterations < 1) { err = "InvalidParameter: maxIterationCount must be >= 1"; return ICPMI_ERR_INVALID_ARG; }
     if (cfg->use_differential && (cfg->smooth_length < 1 || cfg->smooth_length > ICPMI_MAX_SMOOTH)) { err = "InvalidParameter: smoothLength must be in [1, 16]"; return ICPMI_ERR_INVALID_ARG; }
     if (cfg->grid_cell < 0.f) { err = "InvalidParameter: grid_cell must be >= 0"; return ICPMI_ERR_INVALID_ARG; }
+    if (cfg->covariance != 0 && cfg->covariance != 1) { err = "InvalidParameter: covariance must be 0 or 1"; return ICPMI_ERR_INVALID_ARG; }
+    if (cfg->covariance) {
+        if (cfg->minimizer != ICPMI_MIN_POINT_TO_PLANE) { err = "InvalidParameter: PointToPlaneWithCovErrorMinimizer: the covariance needs the point-to-plane minimizer"; return ICPMI_ERR_INVALID_ARG; }
+        if (cfg->is_2d) { err = "InvalidParameter: PointToPlaneWithCovErrorMinimizer: no covariance of planar (2-D) clouds"; return ICPMI_ERR_INVALID_ARG; }
+        if (!std::isfinite(cfg->sensor_std_dev) || cfg->sensor_std_dev < 0.f) { err = "InvalidParameter: PointToPlaneWithCovErrorMinimizer: sensorStdDev must be finite and >= 0"; return ICPMI_ERR_INVALID_ARG; }
+    }
     return ICPMI_OK;
 }
 
@@ -233,7 +241,7 @@ void icpmi_destroy(icpmi_handle c)
     dev_free(c->d_match_pt); dev_free(c->d_lvl_tab); dev_free(c->d_raw); dev_free(c->d_raw_n3); dev_free(c->d_raw_s); dev_free(c->d_src); dev_free(c->d_alt_raw); dev_free(c->d_alt_n3);
     dev_free(c->d_alt_s); dev_free(c->d_alt_src); dev_free(c->d_stage_s); dev_free(c->d_merge_send); dev_free(c->d_merge_recv); dev_free(c->d_merged); dev_free(c->d_cell_log); if (c->h_cells) (void)hipHostFree(c->h_cells); dev_free(c->d_raw_dk); dev_free(c->d_comm_cnt); dev_free(c->d_read_noise); dev_free(c->d_read_scalar); dev_free(c->d_map_pn);
     for (int k = 0; k < ICPMI_SCRATCH_SLOTS; ++k) dev_free(c->scratch[k]); dev_free(c->d_scan_map); dev_free(c->d_T16);
-    dev_free(c->d_sidx); dev_free(c->d_d2); dev_free(c->d_hard); dev_free(c->d_selhist);
+    dev_free(c->d_sidx); dev_free(c->d_d2); dev_free(c->d_hard); dev_free(c->d_selhist); dev_free(c->d_cov);
     dev_free(c->d_state);
 #undef dev_free
     if (c->h_state) hipHostFree(c->h_state);
@@ -340,6 +348,18 @@ icpmi_status icpmi_debug_last_matches(icpmi_handle h, int64_t n, int32_t k, int3
         }
     }
     return ICPMI_OK;
+}
+
+icpmi_status icpmi_get_covariance(icpmi_handle h, float cov[36])
+{
+    CHECK_H(h);
+    if (!cov) { h->last_error = "get_covariance: cov is null"; return ICPMI_ERR_INVALID_ARG; }
+    if (!h->cfg.covariance) { h->last_error = "get_covariance: the chain does not ask for a covariance (icpmi_config::covariance)"; return ICPMI_ERR_UNSUPPORTED; }
+    if (!h->cov_ready || h->last_match_n == 0) {
+        h->last_error = "get_covariance: no covariance of a single registration on this handle (none ran, it failed, or a batch / another call came after it)";
+        return ICPMI_ERR_UNSUPPORTED;
+    }
+    return read_back(h, cov, loop_covariance_out(h), 36 * sizeof(float));
 }
 
 icpmi_status icpmi_debug_minstd_nth(icpmi_handle h, uint32_t seed, uint32_t n, uint32_t* out)
@@ -450,6 +470,7 @@ static icpmi_status register_impl(icpmi_handle h, const float* d_scan4, int64_t 
     // any early return, so that a registration that bails out cannot leave a stale row armed for the next one
     const int64_t have_scalar_n = h->read_scalar_n, have_noise_n = h->read_noise_n;
     h->read_scalar_n = 0; h->read_noise_n = 0;
+    h->cov_ready = false; // (loop_run sets it again once the covariance of THIS registration is enqueued)
     if (!T_out) { h->last_error = "register: T_out is null"; return ICPMI_ERR_INVALID_ARG; }
     if (stats) { memset(stats, 0, sizeof *stats); stats->sensor_noise_overlap = -1.f; } // -1 = "not computed" on EVERY path
     identity16(T_out);
@@ -569,10 +590,12 @@ icpmi_status icpmi_register_batch_dev(icpmi_handle h, int32_t batch, const float
             if (status) status[b] = sb;
             if (sb != ICPMI_OK && first == ICPMI_OK) first = sb;
         }
+        h->cov_ready = false; // (no covariance per reading of a batch)
         return status ? ICPMI_OK : first;
     }
     if (stats) { memset(stats, 0, sizeof(icpmi_stats) * batch); for (int b = 0; b < batch; ++b) stats[b].sensor_noise_overlap = -1.f; }
     LoopCfg lc = make_loop_cfg(h, fixed_iterations);
+    h->cov_ready = false;
     return loop_run_batch(h, batch, d_scans4, n, lc, fixed_iterations > 0, T_out, stats, status);
 }
 

@@ -549,6 +549,9 @@ struct icpmi_ctx {
     // what icpmi_debug_last_matches reads: n and k of the last single registration whose matches are still in d_sidx / d_d2 (0 = none), and
     // whether they are in the tile-sorted query order (d_qindex).  Cleared by everything else that writes those buffers or moves the map.
     int64_t last_match_n = 0; int last_match_k = 0; bool last_match_sorted = false;
+    // icpmi_get_covariance (loop.hip: loop_covariance): per-workgroup partials of H / S, then the 36 floats of Cov; cov_ready = computed
+    // for the last single registration (read only while last_match_n says its pairs are still the ones in the buffers)
+    double* d_cov = nullptr; size_t cap_cov = 0; bool cov_ready = false;
     IcpState* d_state = nullptr;                               // ICPMI_MAX_BATCH states (a single registration uses the first)
     IcpState* h_state = nullptr;                               // pinned mirror (ICPMI_MAX_BATCH)
     bool zero_pending = false;                                 // d_state / d_selhist still to be cleared: on the stream the handle really uses, at its first call (zero_state_if_pending)
@@ -907,6 +910,8 @@ icpmi_status create_handle(const icpmi_config* cfg, icpmi_handle* out); // icpmi
 icpmi_status loop_run(icpmi_ctx* c, const float4* d_scan, const float* d_normals3, int64_t n, const LoopCfg& lc, bool fixed, float T_out[16],
                       icpmi_stats* stats);
 icpmi_status loop_sensor_noise_overlap(icpmi_ctx* c, int64_t n, const LoopCfg& lc, bool sorted, float* overlap);
+icpmi_status loop_covariance(icpmi_ctx* c, int64_t n, const LoopCfg& lc, bool sorted);
+const float* loop_covariance_out(const icpmi_ctx* c); // device address of the 36 floats loop_covariance leaves
 icpmi_status loop_prepare_reading(icpmi_ctx* c, const float4* d_scan, int64_t n, const float* d_normals3, bool* head_done = nullptr);
 icpmi_status loop_run_batch(icpmi_ctx* c, int batch, const float* const* d_scans4, const int64_t* n, const LoopCfg& lc, bool fixed,
                             float* T_out, icpmi_stats* stats, icpmi_status* status);

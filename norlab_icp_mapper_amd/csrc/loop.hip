@@ -1072,6 +1072,224 @@ icpmi_status loop_sensor_noise_overlap(icpmi_ctx* c, int64_t n, const LoopCfg& l
     return ICPMI_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// PointToPlaneWithCovErrorMinimizer::getCovariance() (include/icpmi.h: icpmi_get_covariance has the formula).  Two launches behind the
+// loop, outside any graph, over the same pairs as the overlap pass: the last counted iteration's error elements with w > 0, the reading
+// under T_prev.  Pass 1: every workgroup sums h h^T and a a^T + b b^T (21 + 21 upper-triangle values) in double and writes its partials;
+// pass 2 (one workgroup) adds the partials in a fixed order, factors H and writes Cov.  No atomics: the same bits on every call.
+// ---------------------------------------------------------------------------------------------
+#define ICPMI_COV_NB 256   // pass-1 workgroups, one per CU (fixed: the summation order must not depend on anything but the pair count)
+#define ICPMI_COV_NV 42    // [0..20] H, [21..41] S, upper triangles row-major
+
+// (tx, ty, tz, alpha, beta, gamma) of the last step T_s = T_iter T_prev^-1 (T_prev^-1 = [R^T | -R^T t]), in double
+__device__ inline void cov_step_params(const IcpState* st, double* x)
+{
+    const float* A = st->T_iter;
+    const float* P = st->T_prev;
+    double R[3][3];
+    for (int r = 0; r < 3; ++r)
+        for (int cc = 0; cc < 3; ++cc) R[r][cc] = (double)A[r] * P[cc] + (double)A[4 + r] * P[4 + cc] + (double)A[8 + r] * P[8 + cc];
+    for (int r = 0; r < 3; ++r) x[r] = (double)A[12 + r] - (R[r][0] * P[12] + R[r][1] * P[13] + R[r][2] * P[14]);
+    const double beta = -asin(R[2][0]);
+    const double cb = cos(beta);
+    x[3] = atan2(R[2][1], R[2][2]);
+    x[4] = beta;
+    x[5] = atan2(R[1][0] / cb, R[0][0] / cb);
+}
+
+__global__ __launch_bounds__(256) void cov_pairs_kernel(const float4* __restrict__ reading, const int* __restrict__ qindex, int n, LoopCfg lc,
+                                                        const IcpState* __restrict__ st, const float4* __restrict__ map,
+                                                        const float4* __restrict__ ref_normals, const float4* __restrict__ read_normals,
+                                                        const float* __restrict__ ref_scalar, const int* __restrict__ sidx,
+                                                        const float* __restrict__ d2a, const float4* __restrict__ match_pt,
+                                                        double* __restrict__ partial)
+{
+    __shared__ double xs[6];
+    __shared__ double sh[4][ICPMI_COV_NV];
+    if (threadIdx.x == 0) cov_step_params(st, xs);
+    __syncthreads();
+    const double tx = xs[0], ty = xs[1], tz = xs[2], al = xs[3], be = xs[4], ga = xs[5];
+    const float* T = st->T_prev;
+    const int64_t total = (int64_t)n * lc.k;
+    double acc[ICPMI_COV_NV];
+#pragma unroll
+    for (int i = 0; i < ICPMI_COV_NV; ++i) acc[i] = 0.0;
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
+        const float d2 = d2a[e];
+        if (d2 == INFINITY) continue;
+        const int qi = (int)(e / lc.k);
+        const int oi = qindex ? qindex[qi] : qi;
+        const int s = sidx[e];
+        const float4 r4 = reading[qi];
+        const float3 p = xf_point(T, r4.x, r4.y, r4.z, r4.w);
+        const float4 q = match_pt ? match_pt[e] : map[s];
+        const float4 nm = ref_normals[s];
+        float w;
+        if (lc.ext) { // the filters that read the pair itself, as the pair-sum kernel evaluates them
+            const float dx = p.x - q.x, dy = p.y - q.y, dz = p.z - q.z;
+            const float dot = dx * nm.x + dy * nm.y + dz * nm.z;
+            w = match_weight<true>(lc, st, d2, T, read_normals, oi, ref_normals, s, -1, 0.f, ref_scalar, __float_as_int(q.w), dot * dot);
+        } else w = match_weight(lc, st, d2, T, read_normals, oi, ref_normals, s);
+        if (!(w > 0.f)) continue;
+        const double px = p.x, py = p.y, pz = p.z, qx = q.x, qy = q.y, qz = q.z, nx = nm.x, ny = nm.y, nz = nm.z;
+        const double r = sqrt(px * px + py * py + pz * pz), rho = sqrt(qx * qx + qy * qy + qz * qz);
+        const double ir = 1.0 / r, irho = 1.0 / rho; // (two double divisions per pair instead of six)
+        const double dx = px * ir, dy = py * ir, dz = pz * ir, ux = qx * irho, uy = qy * irho, uz = qz * irho;
+        const double cx = dy * nz - dz * ny, cy = dz * nx - dx * nz, cz = dx * ny - dy * nx;
+        // L v = v + (alpha, beta, gamma) x v
+        const double lpx = px - ga * py + be * pz, lpy = ga * px + py - al * pz, lpz = -be * px + al * py + pz;
+        const double ldx = dx - ga * dy + be * dz, ldy = ga * dx + dy - al * dz, ldz = -be * dx + al * dy + dz;
+        const double E = nx * (lpx + tx - qx) + ny * (lpy + ty - qy) + nz * (lpz + tz - qz);
+        const double Nr = nx * ldx + ny * ldy + nz * ldz;
+        const double Nq = -(nx * ux + ny * uy + nz * uz);
+        const double ea = E + r * Nr;
+        const double h[6] = {nx, ny, nz, r * cx, r * cy, r * cz};
+        const double a[6] = {nx * Nr, ny * Nr, nz * Nr, cx * ea, cy * ea, cz * ea};
+        const double b[6] = {nx * Nq, ny * Nq, nz * Nq, r * cx * Nq, r * cy * Nq, r * cz * Nq};
+        int idx = 0;
+#pragma unroll
+        for (int i = 0; i < 6; ++i)
+#pragma unroll
+            for (int j = i; j < 6; ++j, ++idx) {
+                acc[idx] += h[i] * h[j];
+                acc[21 + idx] += a[i] * a[j] + b[i] * b[j];
+            }
+    }
+    // wave butterfly, then the four waves in order: a fixed pattern, the same sums on every call
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+    for (int i = 0; i < ICPMI_COV_NV; ++i) {
+        double v = acc[i];
+#pragma unroll
+        for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m, 64);
+        if (lane == 0) sh[wv][i] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < ICPMI_COV_NV) {
+        const int i = threadIdx.x;
+        partial[(size_t)blockIdx.x * ICPMI_COV_NV + i] = ((sh[0][i] + sh[1][i]) + sh[2][i]) + sh[3][i];
+    }
+}
+
+#define ICPMI_COV_CH 6     // pass 2: six threads per value, each over every sixth workgroup partial
+__global__ __launch_bounds__(256) void cov_solve_kernel(const double* __restrict__ partial, int nb, float sigma, float* __restrict__ cov)
+{
+    __shared__ double part[ICPMI_COV_NV][ICPMI_COV_CH];
+    __shared__ double tot[ICPMI_COV_NV];
+    if (threadIdx.x < ICPMI_COV_NV * ICPMI_COV_CH) {
+        // every load issued before the first add (a loop of dependent loads and adds was 35 us at 128 partials)
+        constexpr int PER = (ICPMI_COV_NB + ICPMI_COV_CH - 1) / ICPMI_COV_CH;
+        const int v = threadIdx.x / ICPMI_COV_CH, ch = threadIdx.x % ICPMI_COV_CH;
+        double x[PER];
+#pragma unroll
+        for (int i = 0; i < PER; ++i) {
+            const int b = ch + ICPMI_COV_CH * i;
+            x[i] = b < nb ? partial[(size_t)b * ICPMI_COV_NV + v] : 0.0;
+        }
+        double acc = 0.0;
+#pragma unroll
+        for (int i = 0; i < PER; ++i) acc += x[i];
+        part[v][ch] = acc;
+    }
+    __syncthreads();
+    if (threadIdx.x < ICPMI_COV_NV) {
+        double acc = 0.0;
+#pragma unroll
+        for (int ch = 0; ch < ICPMI_COV_CH; ++ch) acc += part[threadIdx.x][ch];
+        tot[threadIdx.x] = acc;
+    }
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    double H[6][6], S[6][6], L[6][6], Hi[6][6], M[6][6];
+    int idx = 0;
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+#pragma unroll
+        for (int j = i; j < 6; ++j, ++idx) { H[i][j] = H[j][i] = tot[idx]; S[i][j] = S[j][i] = tot[21 + idx]; }
+    // H = L L^T; a pivot <= 0 (not NaN: a zero range propagates) means no estimate
+    bool ok = true;
+    double id[6]; // 1 / L[j][j]
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+        double dgn = H[j][j];
+#pragma unroll
+        for (int k = 0; k < j; ++k) dgn -= L[j][k] * L[j][k];
+        if (dgn <= 0.0) ok = false;
+        L[j][j] = sqrt(dgn);
+        id[j] = 1.0 / L[j][j];
+#pragma unroll
+        for (int i = j + 1; i < 6; ++i) {
+            double v = H[i][j];
+#pragma unroll
+            for (int k = 0; k < j; ++k) v -= L[i][k] * L[j][k];
+            L[i][j] = v * id[j];
+        }
+    }
+    if (!ok) {
+#pragma unroll
+        for (int i = 0; i < 36; ++i) cov[i] = (i % 7 == 0) ? 3.402823466e38f : 0.f;
+        return;
+    }
+    // H^-1, column by column: L y = e_c, L^T x = y
+#pragma unroll
+    for (int cc = 0; cc < 6; ++cc) {
+        double y[6];
+#pragma unroll
+        for (int i = 0; i < 6; ++i) {
+            double v = (i == cc) ? 1.0 : 0.0;
+#pragma unroll
+            for (int k = 0; k < i; ++k) v -= L[i][k] * y[k];
+            y[i] = v * id[i];
+        }
+#pragma unroll
+        for (int i = 5; i >= 0; --i) {
+            double v = y[i];
+#pragma unroll
+            for (int k = i + 1; k < 6; ++k) v -= L[k][i] * Hi[k][cc];
+            Hi[i][cc] = v * id[i];
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+#pragma unroll
+        for (int j = 0; j < 6; ++j) {
+            double v = 0.0;
+#pragma unroll
+            for (int k = 0; k < 6; ++k) v += Hi[i][k] * S[k][j];
+            M[i][j] = v;
+        }
+    const double s2 = (double)sigma * (double)sigma;
+    // the upper triangle, mirrored: Cov is symmetric to the bit
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+#pragma unroll
+        for (int j = i; j < 6; ++j) {
+            double v = 0.0;
+#pragma unroll
+            for (int k = 0; k < 6; ++k) v += M[i][k] * Hi[k][j];
+            const float f = (float)(s2 * v);
+            cov[6 * j + i] = f; cov[6 * i + j] = f;
+        }
+}
+
+const float* loop_covariance_out(const icpmi_ctx* c) { return reinterpret_cast<const float*>(c->d_cov + ICPMI_COV_NB * ICPMI_COV_NV); }
+
+icpmi_status loop_covariance(icpmi_ctx* c, int64_t n, const LoopCfg& lc, bool sorted)
+{
+    if (ensure_cap(c, &c->d_cov, &c->cap_cov, (size_t)ICPMI_COV_NB * ICPMI_COV_NV + 18) != ICPMI_OK) return ICPMI_ERR_HIP; // (+ 36 floats)
+    const float4* rd = sorted ? c->d_qsorted : c->d_reading;
+    const int* qi = sorted ? c->d_qindex : nullptr;
+    const float4* mp = (sorted && lc.k == 1) ? c->d_match_pt : nullptr;
+    const float4* rn = lc.has_read_normals ? c->d_read_normals : nullptr;
+    const float* rs = (lc.ext && c->raw_has_scalar) ? c->d_raw_s : nullptr;
+    hipLaunchKernelGGL(cov_pairs_kernel, dim3(ICPMI_COV_NB), dim3(256), 0, c->stream, rd, qi, (int)n, lc, c->d_state, c->d_map_sorted,
+                       c->d_normals_sorted, rn, rs, c->d_sidx, c->d_d2, mp, c->d_cov);
+    hipLaunchKernelGGL(cov_solve_kernel, dim3(1), dim3(256), 0, c->stream, c->d_cov, ICPMI_COV_NB, c->cfg.sensor_std_dev,
+                       const_cast<float*>(loop_covariance_out(c)));
+    HIP_TRY(c, hipGetLastError());
+    return ICPMI_OK;
+}
+
 // head_done: the caller wants the loop state initialised too (enqueue_registration_head); set when the sort's kernels did it.  Centring,
 // loop-state initialisation and the clearing of the selection histograms ride in the kernels of the query sort (SortHead) -- the head of a
 // registration is 3 graph nodes instead of 8
@@ -1435,7 +1653,7 @@ icpmi_status loop_run(icpmi_ctx* c, const float4* d_scan, const float* d_normals
                       float T_out[16], icpmi_stats* stats)
 {
     LoopCfg lc = lc_in;
-    c->last_match_n = 0;
+    c->last_match_n = 0; c->cov_ready = false;
     // all allocations up front: none may happen while the stream is capturing
     if (ensure_loop_buffers(c, n, lc.k) != ICPMI_OK) return ICPMI_ERR_HIP;
     if (chain_has_vartrimmed(lc)) { VtBuffers vb; if (vt_buffers(c, n * lc.k, &vb) != ICPMI_OK) return ICPMI_ERR_HIP; }
@@ -1643,6 +1861,12 @@ icpmi_status loop_run(icpmi_ctx* c, const float4* d_scan, const float* d_normals
         // ErrorMinimizer::getOverlap() with sensor noise: one pass over the last iteration's pairs, still in the loop's buffers
         const icpmi_status os = loop_sensor_noise_overlap(c, n, lc, sorted_state, &stats->sensor_noise_overlap);
         if (os != ICPMI_OK) return os;
+    }
+    if (c->cfg.covariance && !c->h_state->error && c->h_state->iter > 0) {
+        // PointToPlaneWithCovErrorMinimizer: two launches over the same pairs; icpmi_get_covariance reads the result
+        const icpmi_status cs = loop_covariance(c, n, lc, sorted_state);
+        if (cs != ICPMI_OK) return cs;
+        c->cov_ready = true;
     }
     const IcpState* hs = c->h_state;
     if (hs->error) {

@@ -27,6 +27,20 @@ void GpuICPSequence::check(icpmi_handle h, icpmi_status s)
     }
 }
 
+// the covariance of the registration that just ran, read before anything else (a map update) reuses the matcher's buffers
+void GpuICPSequence::keepCovariance()
+{
+    haveCovariance = cfg.covariance != 0 && icpmi_get_covariance(h, covariance.data()) == ICPMI_OK;
+}
+
+std::array<float, 36> GpuICPSequence::ErrorMinimizerView::getCovariance() const
+{
+    if (owner->haveCovariance) return owner->covariance;
+    std::array<float, 36> c{};
+    check(owner->h, icpmi_get_covariance(owner->h, c.data())); // (throws: nothing to read)
+    return c;
+}
+
 GpuICPSequence::GpuICPSequence(int device)
 {
     icpmi_config_default(&cfg);
@@ -202,8 +216,13 @@ void GpuICPSequence::loadFromYamlNode(const yaml::Node& icp)
         auto e = singleEntry(icp["errorMinimizer"], "errorMinimizer");
         if (e.first == "IdentityErrorMinimizer") cfg.minimizer = ICPMI_MIN_IDENTITY;
         else if (e.first == "PointToPointErrorMinimizer") cfg.minimizer = ICPMI_MIN_POINT_TO_POINT;
-        else if (e.first == "PointToPlaneErrorMinimizer") {
+        else if (e.first == "PointToPlaneErrorMinimizer" || e.first == "PointToPlaneWithCovErrorMinimizer") {
             cfg.minimizer = ICPMI_MIN_POINT_TO_PLANE;
+            if (e.first == "PointToPlaneWithCovErrorMinimizer") { // the same registration, plus getCovariance() (icpmi_get_covariance)
+                requireKnown(e.second, {"sensorStdDev", "force2D", "force4DOF"}, e.first);
+                cfg.covariance = 1;
+                if (e.second["sensorStdDev"]) cfg.sensor_std_dev = e.second["sensorStdDev"].as<float>();
+            }
             cfg.force_4dof = (e.second["force4DOF"] && e.second["force4DOF"].as<int>() != 0) ? 1 : 0;
             cfg.force_2d = (e.second["force2D"] && e.second["force2D"].as<int>() != 0) ? 1 : 0;
             if (cfg.force_4dof && cfg.force_2d) throw InvalidParameter("PointToPlaneErrorMinimizer: force2D and force4DOF exclude each other");
@@ -324,7 +343,9 @@ Mat4 GpuICPSequence::registerWithPrior(const DataPoints& scan, const Mat4& prior
 {
     Mat4 T = Mat4::identity();
     stagedPoints = scan.getNbPoints();
+    haveCovariance = false;
     check(h, icpmi_register_prior(h, scan.features.data(), (int64_t)scan.getNbPoints(), prior.data(), T.data(), &lastStats));
+    keepCovariance();
     return T;
 }
 
@@ -424,7 +445,9 @@ Mat4 GpuICPSequence::operator()(const DataPoints& readingIn)
     if ((normals || cfg.minimizer == ICPMI_MIN_POINT_TO_POINT) && reading.descriptorExists("simpleSensorNoise") &&
         reading.getDescriptorByName("simpleSensorNoise").span == 1)
         check(h, icpmi_set_reading_sensor_noise(h, reading.getDescriptorByName("simpleSensorNoise").data.data(), (int64_t)reading.getNbPoints()));
+    haveCovariance = false;
     check(h, icpmi_register(h, reading.features.data(), (int64_t)reading.getNbPoints(), normals, T.data(), &lastStats));
+    keepCovariance();
     return T;
 }
 

@@ -7,6 +7,7 @@
 // plus the registrar-created helpers the mapper uses next to it: RigidTransformation (Mapper.cpp:22,
 // Map.cpp:14) and the DataPointsFilters of the shipped configuration (Mapper.cpp:27-31,82,92).
 #pragma once
+#include <array>
 #include <memory>
 #include <string>
 #include <vector>
@@ -25,6 +26,9 @@ public:
         const GpuICPSequence* owner;
         float getOverlap() const { return owner->lastStats.sensor_noise_overlap >= 0.f ? owner->lastStats.sensor_noise_overlap : owner->lastStats.weighted_point_used_ratio; }
         float getPointUsedRatio() const { return owner->lastStats.point_used_ratio; }
+        // PointToPlaneWithCovErrorMinimizer::getCovariance(): 6 x 6 column-major, (tx, ty, tz, alpha, beta, gamma), centred frame, of the
+        // last registration (include/icpmi.h: icpmi_get_covariance); throws through check() when there is none
+        std::array<float, 36> getCovariance() const;
     };
 
     explicit GpuICPSequence(int device = 0);
@@ -91,6 +95,9 @@ private:
   private:
     bool planar = false;                               // 2-D mapping (is3D == false): icpmi_config::is_2d
     ErrorMinimizerView minimizerView{this};
+    void keepCovariance();
+    std::array<float, 36> covariance{};                // of the last registration, when the chain asks for it
+    bool haveCovariance = false;
 };
 
 // PM::Transformation created with "RigidTransformation": features' = T * features, descriptors named

@@ -69,6 +69,7 @@ public:
     void loadYamlConfig(const std::string& configFilePath);
     void loadYamlConfigFromString(const std::string& text);
     const icpmi_stats& lastIcpStats() const { return icp.stats(); }
+    const GpuICPSequence& icpSequence() const { return icp; } // (errorMinimizer->getCovariance() of the last registration)
     // the last processInput: version of the registration map it ran against (Map::icpMapVersion, read under the ICP lock) and
     // whether it started a map update -- what a replay needs to reproduce a free-running online run scan by scan
     long lastRegistrationMapVersion() const { return lastSeenMapVersion; }

@@ -4,6 +4,7 @@
 #include <cstring>
 
 #include "IcpSequence.h"
+#include "Mapper.h"
 
 namespace nim { uint32_t minstdNth(uint32_t seed, uint32_t n); } // IcpSequence.cpp: the generator RandomSampling / MaxDensity / SamplingSurfaceNormal draw from
 
@@ -79,6 +80,35 @@ int nim_test_icp_set_map(const char* yaml_icp, const float* in4, int64_t n, floa
         if (m.getNbPoints() > (size_t)n) throw std::runtime_error("the resident map is larger than the input");
         std::memcpy(out4, m.features.data(), sizeof(float) * 4 * m.getNbPoints());
         *n_out = (int64_t)m.getNbPoints();
+        return 0;
+    } catch (const std::exception& e) {
+        if (err && err_cap > 0) { std::strncpy(err, e.what(), (size_t)err_cap - 1); err[err_cap - 1] = 0; }
+        return 1;
+    }
+}
+
+// The offline replay of build_map_from_scans_and_trajectory (Mapper on device 0, 3-D, mapping) over the scan files `paths` with the given
+// poses (column-major 4 x 4 each) and stamps; after every processInput the mapper's pose goes to poses_out16 and, when the ICP chain has
+// PointToPlaneWithCovErrorMinimizer and that scan was registered, errorMinimizer->getCovariance() to cov36 (cov_ok[i] = 1; else 0).
+int nim_test_mapper_replay(const char* config, int n_scans, const char* const* paths, const float* poses16, const int64_t* stamps_ns,
+                           float* poses_out16, float* cov36, int32_t* cov_ok, char* err, int err_cap)
+{
+    try {
+        nim::Mapper mapper(config, true, false, true, false);
+        for (int i = 0; i < n_scans; ++i) {
+            nim::DataPoints cloud = nim::DataPoints::load(paths[i]);
+            mapper.applyInputFilters(cloud);
+            nim::Mat4 pose;
+            std::memcpy(pose.data(), poses16 + 16 * i, sizeof(float) * 16);
+            mapper.processInput(cloud, pose, nim::TimePoint{std::chrono::nanoseconds(stamps_ns[i])});
+            std::memcpy(poses_out16 + 16 * i, mapper.getPose().data(), sizeof(float) * 16);
+            cov_ok[i] = 0;
+            try {
+                const std::array<float, 36> c = mapper.icpSequence().errorMinimizer->getCovariance();
+                std::memcpy(cov36 + 36 * i, c.data(), sizeof c);
+                cov_ok[i] = 1;
+            } catch (const std::exception&) {}
+        }
         return 0;
     } catch (const std::exception& e) {
         if (err && err_cap > 0) { std::strncpy(err, e.what(), (size_t)err_cap - 1); err[err_cap - 1] = 0; }

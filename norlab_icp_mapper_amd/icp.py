@@ -186,6 +186,14 @@ def config_from_yaml_chain(chain, **engine):
     kw["outliers"] = outs
 
     name, p = single(chain.get("errorMinimizer", "PointToPlaneErrorMinimizer"), "errorMinimizer")
+    if name == "PointToPlaneWithCovErrorMinimizer":
+        # registers as PointToPlaneErrorMinimizer and leaves the pose covariance (errorMinimizer.getCovariance())
+        for key in p:
+            if key not in ("sensorStdDev", "force2D", "force4DOF"):
+                raise InvalidParameter(f"{name}: unknown parameter {key}")
+        kw["covariance"] = 1
+        kw["sensor_std_dev"] = float(p.get("sensorStdDev", 0.01))
+        name = "PointToPlaneErrorMinimizer"
     if name not in _MINIMIZERS:
         raise InvalidParameter(f"unknown error minimizer {name}")
     kw["minimizer"] = _MINIMIZERS[name]
@@ -231,6 +239,13 @@ class _ErrorMinimizerView:
 
     def getWeightedPointUsedRatio(self):
         return float(self._o.stats.weighted_point_used_ratio)
+
+    def getCovariance(self):
+        """PointToPlaneWithCovErrorMinimizer: the (6, 6) float32 covariance of the last single registration's pose, parameters
+        (tx, ty, tz, alpha, beta, gamma), centred frame (include/icpmi.h: icpmi_get_covariance); NotImplementedError when there is none"""
+        out = (C.c_float * 36)()
+        self._o._check(self._o._lib.icpmi_get_covariance(self._o._h, out))
+        return np.array(out[:], dtype=np.float32).reshape(6, 6).T.copy()
 
 
 class ICPSequence:
