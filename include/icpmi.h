@@ -398,6 +398,36 @@ icpmi_status icpmi_octree_sample(icpmi_handle h, const float* in4, int64_t n, fl
 icpmi_status icpmi_voxel_grid(icpmi_handle h, const float* in4, int64_t n, const float vsize[3], int32_t average_descriptors, const float* desc,
                               int32_t desc_rows, int32_t* order_out, float* out4, float* desc_out, int64_t* n_out);
 
+/* What icpmi_covariance_sampling worked with: the centre c, the torque normalisation L, the eigenvalues of C in ascending order and
+ * the eigenvectors, column-major: basis[6 k + j] = component j of x_k (the eigenvector of eigval[k]; its sign is the solver's). */
+typedef struct {
+    double center[3];
+    double lnorm;
+    double eigval[6];
+    double basis[36];
+} icpmi_covsamp_info;
+
+/* `CovarianceSamplingDataPointsFilter{nbSample, torqueNorm}` (libpointmatcher DataPointsFilters/CovarianceSampling, Gelfand et al.
+ * 2003, AS RECALLED: upstream's source is not on hand).  Every quantity is double, computed from the float inputs, no contraction:
+ *   1. nb_sample >= n: the cloud is returned unchanged (order_out = 0 .. n - 1, *n_out = n, info_out untouched), normals or not.
+ *      Otherwise normals3 (3 per point, point-major) is required: NULL gives ICPMI_ERR_MISSING_NORMALS.
+ *   2. c = the mean of x, y, z.
+ *   3. L: torque_norm 0 (L1) 1; 1 (Lavg) the mean of |p_i - c|; 2 (Lmax) half the largest bounding-box extent over x, y, z.
+ *      L == 0 (every point equal) uses L = 1.
+ *   4. v_i = [ s tau_i ; n_i ], s = 1.0 / L, tau_i = (p_i - c) x n_i with tau_x = (a_y b_z) - (a_z b_y) and so on.
+ *   5. C = sum_i v_i v_i^T; x_0 .. x_5 its eigenvectors in ASCENDING eigenvalue order.
+ *   6. m_ik = v_i . x_k summed left to right over j = 0 .. 5; list k = every point sorted by the key (float)|m_ik| descending,
+ *      stable (ties in ascending index order).
+ *   7. t[0 .. 5] = 0; nb_sample times: k = the first index of the minimum of t; the first point of list k not yet selected is
+ *      selected; t_j += m_sel,j^2 for j = 0 .. 5 in that order.
+ * order_out (capacity min(n, nb_sample)) = the selected indices in selection order, *n_out = min(n, nb_sample); nb_sample == 0 gives
+ * an empty cloud.  info_out (may be NULL) = the device's c, L and eigenbasis, from which the selection replays bit for bit.
+ * ICPMI_ERR_INVALID_ARG (last_error says why): nb_sample < 0, torque_norm outside 0 .. 2, a planar handle (icpmi_config::is_2d:
+ * upstream takes 3-D clouds only), non-finite coordinates or normals.  n > 2^31 - 1: ICPMI_ERR_UNSUPPORTED.  Entirely on the
+ * device, no float atomics: two calls give the same bits (csrc/covsampling.hip). */
+icpmi_status icpmi_covariance_sampling(icpmi_handle h, const float* in4, int64_t n, const float* normals3, int64_t nb_sample, int32_t torque_norm,
+                                       int32_t* order_out, int64_t* n_out, icpmi_covsamp_info* info_out);
+
 /* `Map::updateLocalPointCloud` (Map.cpp:502-534) for a whole module chain on the RESIDENT map: the mapper modules
  * (`mapperModuleVec`, Map.cpp:506-521) and then the post filters (Map.cpp:523-525) run as one program on the device copy
  * of the map; only the scan crosses PCIe.  The device tracks the features, the `normals` and ONE scalar descriptor of

@@ -89,6 +89,11 @@ class PointFilter(C.Structure):
     _fields_ = [("type", C.c_int32), ("i", C.c_int32), ("f", C.c_float * 6)]
 
 
+class CovSampInfo(C.Structure):
+    """icpmi_covsamp_info: centre, torque normalisation, ascending eigenvalues and eigenbasis (basis[6 k + j] = x_k[j])."""
+    _fields_ = [("center", C.c_double * 3), ("lnorm", C.c_double), ("eigval", C.c_double * 6), ("basis", C.c_double * 36)]
+
+
 MOP_POINT_DISTANCE, MOP_DYNAMIC_POINTS, MOP_VOXEL, MOP_SURFACE_NORMALS, MOP_CUT_SCALAR, MOP_OCTREE = range(6)
 
 
@@ -129,6 +134,7 @@ SYMBOLS = [
     ("icpmi_sampling_surface_normal_ex", C.c_int, [_P, _P, C.c_int64, C.c_float, C.c_int32, C.c_float, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P]),
     ("icpmi_octree_sample", C.c_int, [_P, _P, C.c_int64, C.c_float, C.c_int32, C.c_int32, _P, _P, _P]),
     ("icpmi_voxel_grid", C.c_int, [_P, _P, C.c_int64, _P, C.c_int32, _P, C.c_int32, _P, _P, _P, _P]),
+    ("icpmi_covariance_sampling", C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, C.c_int32, _P, _P, _P]),
     ("icpmi_map_update_chain", C.c_int, [_P, _P, C.c_int64, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, _P, C.c_int64, _P, _P]),
     ("icpmi_map_update_chain_staged", C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, _P, C.c_int64, _P, _P]),
     ("icpmi_set_map_scalar", C.c_int, [_P, _P, C.c_int64]),

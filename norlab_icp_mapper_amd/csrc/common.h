@@ -977,3 +977,5 @@ icpmi_status ops_octree_sample(icpmi_ctx* c, const float* in4, int64_t n, float 
                                int32_t* leaf_of_out, int64_t* n_out);
 icpmi_status ops_voxel_grid(icpmi_ctx* c, const float* in4, int64_t n, const float vsize[3], int average, const float* desc, int rows,
                             int32_t* order_out, float* out4, float* desc_out, int64_t* n_out);
+icpmi_status ops_covariance_sampling(icpmi_ctx* c, const float* in4, int64_t n, const float* normals3, int64_t nb, int torque_norm, int32_t* order_out,
+                                     icpmi_covsamp_info* info_out);

@@ -947,6 +947,35 @@ struct VoxelGridFilter : DataPointsFilter {
     }
 };
 
+// CovarianceSamplingDataPointsFilter{nbSample, torqueNorm} (libpointmatcher, Gelfand et al. 2003, as recalled; the formulation is
+// icpmi_covariance_sampling's in include/icpmi.h): keeps nbSample points chosen greedily to constrain the six pose directions evenly,
+// in selection order.  The whole selection runs on the device; here features, every descriptor and `times` follow the order.
+struct CovarianceSamplingFilter : DataPointsFilter {
+    int64_t nbSample = 5000; int torqueNorm = 1;
+    icpmi_handle h = nullptr;
+    void inPlaceFilter(DataPoints& c) const override {
+        const size_t n = c.getNbPoints();
+        if ((size_t)nbSample >= n) return;
+        const Descriptor& nrm = c.getDescriptorByName("normals"); // (InvalidField without normals, as upstream)
+        if (nrm.span != 3) throw InvalidField("descriptor normals must have 3 rows");
+        if (!h) throw std::logic_error("CovarianceSamplingDataPointsFilter needs a GPU context");
+        std::vector<int32_t> order((size_t)nbSample);
+        int64_t m = 0;
+        GpuICPSequence::check(h, icpmi_covariance_sampling(h, c.features.data(), (int64_t)n, nrm.data.data(), nbSample, torqueNorm, order.data(), &m,
+                                                           nullptr));
+        order.resize((size_t)m);
+        DataPoints out = OctreeGridFilter::gather(c, order);
+        for (size_t k = 0; k < out.times.size(); ++k) {
+            const TimeField& s = c.times[k];
+            TimeField& t = out.times[k];
+            t.data.resize((size_t)t.span * order.size());
+            for (size_t p = 0; p < order.size(); ++p)
+                std::copy(s.data.begin() + (size_t)s.span * order[p], s.data.begin() + (size_t)s.span * (order[p] + 1), t.data.begin() + (size_t)t.span * p);
+        }
+        c = std::move(out);
+    }
+};
+
 float getf(const yaml::Node& p, const char* k, float def) { return p[k] ? p[k].as<float>() : def; }
 int geti(const yaml::Node& p, const char* k, int def) { return p[k] ? p[k].as<int>() : def; }
 
@@ -1072,6 +1101,16 @@ std::shared_ptr<DataPointsFilter> createDataPointsFilter(const std::string& name
         for (float v : f->vsize)
             if (!(v > 0.f) || !std::isfinite(v)) throw InvalidParameter(name + ": vSizeX / vSizeY / vSizeZ must be finite and > 0");
         f->averageDescriptors = geti(p, "averageExistingDescriptors", 1) != 0;
+        f->h = ctx;
+        return f;
+    }
+    if (name == "CovarianceSamplingDataPointsFilter") {
+        requireKnown(p, {"nbSample", "torqueNorm"}, name);
+        auto f = std::make_shared<CovarianceSamplingFilter>();
+        f->nbSample = geti(p, "nbSample", 5000);
+        f->torqueNorm = geti(p, "torqueNorm", 1);
+        if (f->nbSample < 0) throw InvalidParameter(name + ": nbSample must be >= 0");
+        if (f->torqueNorm < 0 || f->torqueNorm > 2) throw InvalidParameter(name + ": torqueNorm must be 0 (L1), 1 (Lavg) or 2 (Lmax)");
         f->h = ctx;
         return f;
     }

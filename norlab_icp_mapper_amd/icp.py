@@ -534,6 +534,31 @@ class ICPSequence:
         k = m.value
         return order[:k].copy(), out4[:k].copy(), (None if dout is None else dout[:k].copy())
 
+    def covarianceSampling(self, cloud, normals, nb_sample=5000, torque_norm=1, with_info=False):
+        """CovarianceSamplingDataPointsFilter{nbSample, torqueNorm} (the formulation of icpmi_covariance_sampling, as recalled):
+        cloud (N, 4), normals (N, 3) or None.  Returns the selected indices in selection order (int32), or (order, info) with info
+        = {center (3,), lnorm, eigval (6,) ascending, basis (6, 6), column k = x_k} -- None when nb_sample >= N (nothing sampled)."""
+        c = _f32c(cloud, 4)
+        n = c.shape[0]
+        nptr = None
+        if normals is not None:
+            normals = _f32c(normals, 3)
+            if normals.shape[0] != n:
+                raise InvalidParameter("normals / cloud size mismatch")
+            nptr = normals.ctypes.data
+        order = np.empty(max(0, min(n, int(nb_sample))), dtype=np.int32)
+        info = _capi.CovSampInfo()
+        m = C.c_int64(0)
+        self._check(self._lib.icpmi_covariance_sampling(self._h, c.ctypes.data, n, nptr, int(nb_sample), int(torque_norm), order.ctypes.data,
+                                                        C.byref(m), C.byref(info)))
+        order = order[:m.value].copy()
+        if not with_info:
+            return order
+        if nb_sample >= n:
+            return order, None
+        return order, {"center": np.array(info.center[:]), "lnorm": float(info.lnorm), "eigval": np.array(info.eigval[:]),
+                       "basis": np.array(info.basis[:]).reshape(6, 6).T.copy()}
+
     def voxelKeep(self, cloud, edge, method=0):
         """Same lattice, representative by `samplingMethod`: 0 first point, 1 pseudo-random point (smallest fmix32 of the index)."""
         c = _f32c(cloud, 4)
