@@ -8,8 +8,10 @@
 // Map.cpp:14) and the DataPointsFilters of the shipped configuration (Mapper.cpp:27-31,82,92).
 #pragma once
 #include <array>
+#include <initializer_list>
 #include <memory>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/icpmi.h"
@@ -19,6 +21,11 @@
 namespace nim {
 
 class DataPointsFilters;
+
+// YAML helpers of the chain loaders (IcpSequence.cpp; also the filter factory's): InvalidParameter on a key outside `known`;
+// a `Name` / `Name: {params}` entry split into its name and parameters
+void requireKnown(const yaml::Node& params, std::initializer_list<const char*> known, const std::string& who);
+std::pair<std::string, yaml::Node> singleEntry(const yaml::Node& n, const std::string& what);
 
 class GpuICPSequence {
 public:

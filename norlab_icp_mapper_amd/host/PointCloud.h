@@ -6,6 +6,7 @@
 // consecutive (x, y, z, 1) quadruples; each descriptor is span x N column-major.  Value semantics
 // throughout (copies are deep), like PM::DataPoints.
 #pragma once
+#include <algorithm>
 #include <array>
 #include <cmath>
 #include <cstdint>
@@ -200,12 +201,29 @@ public:
         for (auto& t : times) t.data.resize((size_t)t.span * w);
     }
 
+    // columns order[0], order[1], ... of *this, in that order (indices may repeat): features, every descriptor and every time row group
+    DataPoints select(const int32_t* order, size_t count) const {
+        DataPoints r;
+        r.features = selectCols(features, 4, order, count);
+        for (const auto& d : descriptors) r.descriptors.push_back(Descriptor{d.name, d.span, selectCols(d.data, d.span, order, count)});
+        for (const auto& t : times) r.times.push_back(TimeField{t.name, t.span, selectCols(t.data, t.span, order, count)});
+        return r;
+    }
+
     // ASCII VTK POLYDATA in libpointmatcher's dialect: POINTS / VERTICES / POINT_DATA
     // with SCALARS, VECTORS and NORMALS blocks mapped to descriptors by name; a time row group `t` travels as the two
     // unsigned_int scalars `t_splitTime_high32` / `t_splitTime_low32` (upstream's IO.cpp convention, as recalled: VTK legacy
     // has no portable 64-bit integer type) and comes back as `times`
     static DataPoints load(const std::string& path);
     void save(const std::string& path, bool binary = false) const; // VTK legacy, ASCII (default, as the reference's examples) or BINARY
+
+private:
+    template <typename T>
+    static std::vector<T> selectCols(const std::vector<T>& src, int span, const int32_t* order, size_t count) {
+        std::vector<T> out((size_t)span * count);
+        for (size_t j = 0; j < count; ++j) std::copy(src.begin() + (size_t)span * order[j], src.begin() + (size_t)span * (order[j] + 1), out.begin() + (size_t)span * j);
+        return out;
+    }
 };
 
 } // namespace nim

@@ -6,7 +6,38 @@
 #include "IcpSequence.h"
 #include "Mapper.h"
 
-namespace nim { uint32_t minstdNth(uint32_t seed, uint32_t n); } // IcpSequence.cpp: the generator RandomSampling / MaxDensity / SamplingSurfaceNormal draw from
+namespace nim { uint32_t minstdNth(uint32_t seed, uint32_t n); } // DataPointsFilters.cpp: the generator RandomSampling / MaxDensity / SamplingSurfaceNormal draw from
+
+// the one body of nim_test_filter_chain and nim_test_filter_chain_times: every input and output beyond in4 / out4 / n_out may be NULL
+static int filterChain(icpmi_handle h, const char* yaml_seq, const float* in4, int64_t n, const char* desc_name, int desc_span, const float* desc,
+                       const char* time_name, int time_span, const int64_t* times, float* out4, float* out_normals3, float* out_desc,
+                       int64_t* out_times, int64_t* n_out, int* has_normals, char* err, int err_cap)
+{
+    try {
+        nim::DataPoints c((size_t)n);
+        std::memcpy(c.features.data(), in4, sizeof(float) * 4 * (size_t)n);
+        if (desc_name && desc) c.addDescriptor(desc_name, desc_span, std::vector<float>(desc, desc + (size_t)desc_span * n));
+        if (time_name && times) c.addTime(time_name, time_span, std::vector<int64_t>(times, times + (size_t)time_span * n));
+        nim::DataPointsFilters chain(nim::yaml::Load(yaml_seq), h);
+        chain.apply(c);
+        const size_t m = c.getNbPoints();
+        std::memcpy(out4, c.features.data(), sizeof(float) * 4 * m);
+        const bool hn = c.descriptorExists("normals");
+        if (has_normals) *has_normals = hn ? 1 : 0;
+        if (hn && out_normals3) std::memcpy(out_normals3, c.getDescriptorByName("normals").data.data(), sizeof(float) * 3 * m);
+        if (desc_name && out_desc && c.descriptorExists(desc_name)) std::memcpy(out_desc, c.getDescriptorByName(desc_name).data.data(), sizeof(float) * (size_t)desc_span * m);
+        if (time_name && out_times && c.timeExists(time_name)) {
+            const std::vector<int64_t>& t = c.getTimeByName(time_name).data;
+            if (t.size() != (size_t)time_span * m) throw std::logic_error("the filter chain left `times` out of step with the points");
+            std::memcpy(out_times, t.data(), sizeof(int64_t) * t.size());
+        }
+        *n_out = (int64_t)m;
+        return 0;
+    } catch (const std::exception& e) {
+        if (err && err_cap > 0) { std::strncpy(err, e.what(), (size_t)err_cap - 1); err[err_cap - 1] = 0; }
+        return 1;
+    }
+}
 
 extern "C" {
 
@@ -20,24 +51,7 @@ int nim_test_filter_chain(icpmi_handle h, const char* yaml_seq, const float* in4
                           const float* desc, float* out4, float* out_normals3, float* out_desc, int64_t* n_out, int* has_normals,
                           char* err, int err_cap)
 {
-    try {
-        nim::DataPoints c((size_t)n);
-        std::memcpy(c.features.data(), in4, sizeof(float) * 4 * (size_t)n);
-        if (desc_name && desc) c.addDescriptor(desc_name, desc_span, std::vector<float>(desc, desc + (size_t)desc_span * n));
-        nim::DataPointsFilters chain(nim::yaml::Load(yaml_seq), h);
-        chain.apply(c);
-        const size_t m = c.getNbPoints();
-        std::memcpy(out4, c.features.data(), sizeof(float) * 4 * m);
-        const bool hn = c.descriptorExists("normals");
-        if (has_normals) *has_normals = hn ? 1 : 0;
-        if (hn && out_normals3) std::memcpy(out_normals3, c.getDescriptorByName("normals").data.data(), sizeof(float) * 3 * m);
-        if (desc_name && out_desc && c.descriptorExists(desc_name)) std::memcpy(out_desc, c.getDescriptorByName(desc_name).data.data(), sizeof(float) * (size_t)desc_span * m);
-        *n_out = (int64_t)m;
-        return 0;
-    } catch (const std::exception& e) {
-        if (err && err_cap > 0) { std::strncpy(err, e.what(), (size_t)err_cap - 1); err[err_cap - 1] = 0; }
-        return 1;
-    }
+    return filterChain(h, yaml_seq, in4, n, desc_name, desc_span, desc, nullptr, 0, nullptr, out4, out_normals3, out_desc, nullptr, n_out, has_normals, err, err_cap);
 }
 
 // the same with one float descriptor AND one int64 `times` row group (`time_name`, time_span x n, may be NULL): out_times
@@ -46,23 +60,7 @@ int nim_test_filter_chain_times(icpmi_handle h, const char* yaml_seq, const floa
                                 const float* desc, const char* time_name, int time_span, const int64_t* times, float* out4, float* out_desc,
                                 int64_t* out_times, int64_t* n_out, char* err, int err_cap)
 {
-    try {
-        nim::DataPoints c((size_t)n);
-        std::memcpy(c.features.data(), in4, sizeof(float) * 4 * (size_t)n);
-        if (desc_name && desc) c.addDescriptor(desc_name, desc_span, std::vector<float>(desc, desc + (size_t)desc_span * n));
-        if (time_name && times) c.addTime(time_name, time_span, std::vector<int64_t>(times, times + (size_t)time_span * n));
-        nim::DataPointsFilters chain(nim::yaml::Load(yaml_seq), h);
-        chain.apply(c);
-        const size_t m = c.getNbPoints();
-        std::memcpy(out4, c.features.data(), sizeof(float) * 4 * m);
-        if (desc_name && out_desc && c.descriptorExists(desc_name)) std::memcpy(out_desc, c.getDescriptorByName(desc_name).data.data(), sizeof(float) * (size_t)desc_span * m);
-        if (time_name && out_times && c.timeExists(time_name)) std::memcpy(out_times, c.getTimeByName(time_name).data.data(), sizeof(int64_t) * (size_t)time_span * m);
-        *n_out = (int64_t)m;
-        return 0;
-    } catch (const std::exception& e) {
-        if (err && err_cap > 0) { std::strncpy(err, e.what(), (size_t)err_cap - 1); err[err_cap - 1] = 0; }
-        return 1;
-    }
+    return filterChain(h, yaml_seq, in4, n, desc_name, desc_span, desc, time_name, time_span, times, out4, nullptr, out_desc, out_times, n_out, nullptr, err, err_cap);
 }
 
 // GpuICPSequence on device 0: loadFromYamlNode(yaml_icp) (the `icp:` sub-tree), setMap(in4), then the resident map as the core holds it

@@ -120,6 +120,33 @@ static DataPoints makeCloud(size_t n)
     return c;
 }
 
+// DataPoints::select: repeated and out-of-order indices, two descriptors of different span, a two-row `times` group, the empty list
+static void testSelect()
+{
+    DataPoints c = makeCloud(6); // `intensity` (1 row) and `normals` (3 rows)
+    std::vector<std::int64_t> t(2 * 6);
+    for (size_t i = 0; i < 6; ++i) { t[2 * i] = (1ll << 60) + 2 * (std::int64_t)i; t[2 * i + 1] = (1ll << 60) + 2 * (std::int64_t)i + 1; }
+    c.addTime("stamps", 2, t);
+    for (size_t i = 0; i < 6; ++i) c.getDescriptorByName("normals").data[3 * i] = 10.f + (float)i;
+    const int32_t order[] = {4, 0, 4, 5, 1, 0, 0};
+    const DataPoints s = c.select(order, 7);
+    CHECK(s.getNbPoints() == 7 && s.descriptors.size() == 2 && s.times.size() == 1);
+    CHECK(s.descriptors[0].name == "intensity" && s.descriptors[0].span == 1 && s.descriptors[0].data.size() == 7);
+    CHECK(s.descriptors[1].name == "normals" && s.descriptors[1].span == 3 && s.descriptors[1].data.size() == 21);
+    CHECK(s.times[0].name == "stamps" && s.times[0].span == 2 && s.times[0].data.size() == 14);
+    for (size_t j = 0; j < s.getNbPoints() && j < 7; ++j) {
+        const size_t i = (size_t)order[j];
+        CHECK(std::memcmp(s.col(j), c.col(i), 4 * sizeof(float)) == 0);
+        CHECK(s.descriptors[0].data[j] == (float)i);
+        CHECK(s.descriptors[1].data[3 * j] == 10.f + (float)i && s.descriptors[1].data[3 * j + 1] == 0.f && s.descriptors[1].data[3 * j + 2] == 1.f);
+        CHECK(s.times[0].data[2 * j] == t[2 * i] && s.times[0].data[2 * j + 1] == t[2 * i + 1]);
+    }
+    const DataPoints e = c.select(order, 0);
+    CHECK(e.getNbPoints() == 0 && e.descriptors.size() == 2 && e.descriptors[1].span == 3 && e.descriptors[1].data.empty());
+    CHECK(e.times.size() == 1 && e.times[0].name == "stamps" && e.times[0].span == 2 && e.times[0].data.empty());
+    CHECK(e.select(nullptr, 0).getNbPoints() == 0);
+}
+
 static void testCloud()
 {
     DataPoints a = makeCloud(10), b = makeCloud(4);
@@ -294,6 +321,7 @@ int main()
     testYaml();
     testTrajectoryTimes();
     testCloud();
+    testSelect();
     testFilters();
     testGridAndCells();
     testMat4();

@@ -99,6 +99,60 @@ def test_octree_chain_equals_oracle_composition(amd, oracle):
     assert np.abs(both[src, :3] - got[:, :3]).max() < 5e-5
 
 
+_T0 = (1 << 60) + 1            # above 2^53: a detour of `times` through double would lose the index
+
+
+@pytest.mark.parametrize("name,params", [("OctreeGridDataPointsFilter", "maxPointByNode: 3, samplingMethod: 0"),
+                                         ("OctreeGridDataPointsFilter", "maxPointByNode: 3, samplingMethod: 1"),
+                                         ("OctreeGridDataPointsFilter", "maxPointByNode: 3, samplingMethod: 2"),
+                                         ("OctreeGridDataPointsFilter", "maxPointByNode: 3, samplingMethod: 3"),
+                                         ("SamplingSurfaceNormalDataPointsFilter", "knn: 7, samplingMethod: 0"),
+                                         ("SamplingSurfaceNormalDataPointsFilter", "knn: 7, samplingMethod: 1"),
+                                         ("RandomSamplingDataPointsFilter", "prob: 0.5, seed: 3")])
+def test_host_sampling_filters_carry_times(amd, name, params):
+    """Every host filter that reorders or subsamples a cloud hands back `times` with one column per kept point, and the column is the kept
+    point's own: the index encoded in the two int64 rows equals the index encoded in a float descriptor, column by column.  Where the
+    filter averages the descriptors, `times` are the representative's: the point samplingMethod 0 keeps in that leaf (Octree centroid), the
+    smallest member index of the box (SamplingSurfaceNormal samplingMethod 1)."""
+    import ctypes as C
+    import host_bindings as hb
+    from test_host_cpp import _build_host
+    _build_host()
+    fn = hb.load().nim_test_filter_chain_times
+    fn.restype = C.c_int
+    icp = amd.ICPSequence()
+    n = 4000
+    cloud = np.ones((n, 4), np.float32)
+    cloud[:, :3] = np.random.default_rng(21).uniform(-1, 1, (n, 3)) * [10.0, 6.0, 2.0]
+    idx = np.arange(n, dtype=np.int64)
+    d = idx.astype(np.float32)                                               # (n,) == 1 x n; exact below 2^24
+    t = np.stack([_T0 + 3 * idx, _T0 + 3 * idx + 1], 1)                      # (n, 2) == 2 x n column-major
+    sentinel = np.int64(-7)
+    out = np.empty_like(cloud); dout = np.full_like(d, -1.0); tout = np.full_like(t, sentinel); m = C.c_int64(0); err = C.create_string_buffer(512)
+    y = "[{%s: {%s}}]" % (name, params)
+    h = icp._h.value if hasattr(icp._h, "value") else icp._h
+    rc = fn(C.c_void_p(h), y.encode(), C.c_void_p(cloud.ctypes.data), C.c_int64(n), b"index", C.c_int(1), C.c_void_p(d.ctypes.data),
+            b"stamps", C.c_int(2), C.c_void_p(t.ctypes.data), C.c_void_p(out.ctypes.data), C.c_void_p(dout.ctypes.data),
+            C.c_void_p(tout.ctypes.data), C.byref(m), err, 512)
+    assert rc == 0, err.value
+    k = m.value
+    assert 0 < k < n
+    assert not (tout[:k] == sentinel).any() and (tout[k:] == sentinel).all()  # n_out columns of `times` came back, no more
+    rel = tout[:k] - _T0
+    assert np.array_equal(rel % 3, np.tile(np.array([0, 1], np.int64), (k, 1)))   # both rows intact, each in its place
+    from_times = rel // 3
+    assert np.array_equal(from_times[:, 0], from_times[:, 1])
+    if "samplingMethod: 2" in params:
+        want = icp.octreeSample(cloud, 0.0, 3, 0)
+    elif "samplingMethod: 1" in params and name.startswith("SamplingSurfaceNormal"):
+        want, _, _, ms, mc, mem = icp.samplingSurfaceNormalBoxes(cloud, knn=7)
+        assert np.array_equal(want, [mem[ms[j]:ms[j] + mc[j]].min() for j in range(want.shape[0])])
+    else:
+        want = dout[:k].astype(np.int64)                                     # the filter kept input points unchanged
+        assert np.array_equal(out[:k], cloud[want])
+    assert np.array_equal(from_times[:, 0], want)
+
+
 @pytest.mark.parametrize("n,knn,ratio,seed,max_box", [(6000, 7, 0.5, 1, np.inf), (3001, 12, 0.9, 5, np.inf), (50, 7, 1.0, 2, np.inf), (5, 7, 0.5, 1, np.inf),
                                                       (40000, 7, 0.5, 1, np.inf), (20000, 9, 0.7, 3, 1.5), (9, 3, 0.5, 1, np.inf)])
 def test_sampling_surface_normal_on_device_equals_oracle(amd, oracle, n, knn, ratio, seed, max_box):
