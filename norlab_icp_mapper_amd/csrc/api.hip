@@ -165,10 +165,9 @@ icpmi_status create_handle(const icpmi_config* cfg, icpmi_handle* out)
     CR(hipSetDevice(c->device));
     CR(stream_acquire(&c->stream));
     c->own_stream = true;
-    CR(dev_malloc((void**)&c->d_state, sizeof(IcpState) * ICPMI_MAX_BATCH));
+    CR(c->d_state.alloc(ICPMI_MAX_BATCH));
     c->zero_pending = true; // (common.h: zero_state_if_pending -- neither the legacy stream, which breaks another thread's capture, nor a stream this handle may never use)
-    CR(dev_malloc((void**)&c->d_selhist, ICPMI_SELHIST_WORDS * sizeof(unsigned)));
-    c->cap_selhist = ICPMI_SELHIST_WORDS;
+    CR(c->d_selhist.alloc(ICPMI_SELHIST_WORDS));
     CR(hipHostMalloc((void**)&c->h_state, sizeof(IcpState) * ICPMI_MAX_BATCH, hipHostMallocMapped));
     memset(c->h_state, 0, sizeof(IcpState) * ICPMI_MAX_BATCH);
     if (hipHostGetDevicePointer((void**)&c->d_state_mirror, c->h_state, 0) != hipSuccess) { c->d_state_mirror = nullptr; (void)hipGetLastError(); } // (then loop_run copies)
@@ -225,29 +224,13 @@ void icpmi_destroy(icpmi_handle c)
     comm_destroy(c);
     if (c->stream) hipStreamSynchronize(c->stream);
     c->graphs.reset();
-    // ONE device-wide wait for all of the handle's blocks (one per block, each under the exclusive capture gate, stalled every
-    // other thread's registration on this GPU ~80 times in a row)
-    (void)dev_sync_for_free();
-#define dev_free(p) dev_free((p), true)
-    dev_free(c->d_map_sorted); dev_free(c->d_normals_sorted); dev_free(c->d_cell_start);
-    for (int l = 0; l < ICPMI_MAXLEV; ++l) { dev_free(c->d_lvl_pts[l]); dev_free(c->d_lvl_cs[l]); dev_free(c->d_lvl_pos0[l]); }
-    dev_free(c->d_inv);
-    for (int l = 0; l < ICPMI_MAXLEV; ++l) { dev_free(c->d_lvl_key[l]); dev_free(c->d_alt_pts[l]); dev_free(c->d_alt_cs[l]); dev_free(c->d_alt_pos0[l]); dev_free(c->d_alt_key[l]); }
-    dev_free(c->d_raw0); dev_free(c->d_alt_raw0); dev_free(c->d_ins_dstart0);
-    dev_free(c->d_alt_nsorted); dev_free(c->d_alt_pn); dev_free(c->d_ins_key); dev_free(c->d_ins_rank);
-    dev_free(c->d_keys); dev_free(c->d_fill); dev_free(c->d_blocksums); dev_free(c->d_red);
-    dev_free(c->d_qsorted); dev_free(c->d_qindex); dev_free(c->d_qkeys); dev_free(c->d_qtile);
-    dev_free(c->d_reading); dev_free(c->d_read_normals); dev_free(c->d_stage_in); dev_free(c->d_stage_n3);
-    dev_free(c->d_match_pt); dev_free(c->d_lvl_tab); dev_free(c->d_raw); dev_free(c->d_raw_n3); dev_free(c->d_raw_s); dev_free(c->d_src); dev_free(c->d_alt_raw); dev_free(c->d_alt_n3);
-    dev_free(c->d_alt_s); dev_free(c->d_alt_src); dev_free(c->d_stage_s); dev_free(c->d_merge_send); dev_free(c->d_merge_recv); dev_free(c->d_merged); dev_free(c->d_cell_log); if (c->h_cells) (void)hipHostFree(c->h_cells); dev_free(c->d_raw_dk); dev_free(c->d_comm_cnt); dev_free(c->d_read_noise); dev_free(c->d_read_scalar); dev_free(c->d_map_pn);
-    for (int k = 0; k < ICPMI_SCRATCH_SLOTS; ++k) dev_free(c->scratch[k]); dev_free(c->d_scan_map); dev_free(c->d_T16);
-    dev_free(c->d_sidx); dev_free(c->d_d2); dev_free(c->d_hard); dev_free(c->d_selhist); dev_free(c->d_cov);
-    dev_free(c->d_state);
-#undef dev_free
+    // ONE device-wide wait for all of the handle's blocks, which free themselves when the handle is deleted below (common.h: DevFreeSynced)
+    DevFreeSynced synced;
     if (c->h_state) hipHostFree(c->h_state);
     if (c->h_pin) hipHostFree(c->h_pin);
     if (c->h_nocc) hipHostFree(c->h_nocc);
     if (c->h_progress) hipHostFree(c->h_progress);
+    if (c->h_cells) (void)hipHostFree(c->h_cells);
     if (c->ev0) hipEventDestroy(c->ev0);
     if (c->ev1) hipEventDestroy(c->ev1);
     for (hipEvent_t e : c->nn_events) hipEventDestroy(e);
@@ -405,13 +388,13 @@ icpmi_status icpmi_set_map(icpmi_handle h, const float* map4, int64_t m, const f
     if (accepted) *accepted = 0;
     if (m < 0 || (m > 0 && !map4)) { h->last_error = "set_map: bad arguments"; return ICPMI_ERR_INVALID_ARG; }
     if (m == 0) return ICPMI_OK;
-    if (ensure_cap(h, &h->d_stage_in, &h->cap_stage_in, (size_t)m) != ICPMI_OK) return ICPMI_ERR_HIP;
+    if (h->d_stage_in.ensure(h, (size_t)m) != ICPMI_OK) return ICPMI_ERR_HIP;
     HIP_TRY(h, hipMemcpyAsync(h->d_stage_in, map4, (size_t)m * sizeof(float4), hipMemcpyHostToDevice, h->stream));
     if (normals3) {
-        if (ensure_cap(h, &h->d_stage_n3, &h->cap_stage_n3, (size_t)m * 3) != ICPMI_OK) return ICPMI_ERR_HIP;
+        if (h->d_stage_n3.ensure(h, (size_t)m * 3) != ICPMI_OK) return ICPMI_ERR_HIP;
         HIP_TRY(h, hipMemcpyAsync(h->d_stage_n3, normals3, (size_t)m * 3 * sizeof(float), hipMemcpyHostToDevice, h->stream));
     }
-    return icpmi_set_map_dev(h, (const float*)h->d_stage_in, m, normals3 ? h->d_stage_n3 : nullptr, accepted);
+    return icpmi_set_map_dev(h, (const float*)h->d_stage_in.get(), m, normals3 ? h->d_stage_n3 : nullptr, accepted);
 }
 
 static void identity16(float* T) { for (int i = 0; i < 16; ++i) T[i] = (i % 5 == 0) ? 1.f : 0.f; }
@@ -524,7 +507,7 @@ icpmi_status icpmi_set_reading_sensor_noise(icpmi_handle h, const float* noise, 
     CHECK_H(h);
     h->read_noise_n = 0;
     if (!noise || n <= 0) return ICPMI_OK;
-    if (ensure_cap(h, &h->d_read_noise, &h->cap_read_noise, (size_t)n + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
+    if (h->d_read_noise.ensure(h, (size_t)n + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
     HIP_TRY(h, hipMemcpyAsync(h->d_read_noise, noise, (size_t)n * sizeof(float), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream)); // the caller's buffer is free on return
     h->read_noise_n = n;
@@ -536,7 +519,7 @@ icpmi_status icpmi_set_reading_scalar(icpmi_handle h, const float* scalar, int64
     CHECK_H(h);
     h->read_scalar_n = 0;
     if (!scalar || n <= 0) return ICPMI_OK;
-    if (ensure_cap(h, &h->d_read_scalar, &h->cap_read_scalar, (size_t)n + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
+    if (h->d_read_scalar.ensure(h, (size_t)n + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
     HIP_TRY(h, hipMemcpyAsync(h->d_read_scalar, scalar, (size_t)n * sizeof(float), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream)); // the caller's buffer is free on return
     h->read_scalar_n = n;
@@ -607,11 +590,11 @@ icpmi_status icpmi_register(icpmi_handle h, const float* scan4, int64_t n, const
     const float* d_scan = nullptr;
     const float* d_n3 = nullptr;
     if (n > 0 && h->m > 0) {
-        if (ensure_cap(h, &h->d_stage_in, &h->cap_stage_in, (size_t)n) != ICPMI_OK) return ICPMI_ERR_HIP;
+        if (h->d_stage_in.ensure(h, (size_t)n) != ICPMI_OK) return ICPMI_ERR_HIP;
         HIP_TRY(h, hipMemcpyAsync(h->d_stage_in, scan4, (size_t)n * sizeof(float4), hipMemcpyHostToDevice, h->stream));
-        d_scan = (const float*)h->d_stage_in;
+        d_scan = (const float*)h->d_stage_in.get();
         if (scan_normals3) {
-            if (ensure_cap(h, &h->d_stage_n3, &h->cap_stage_n3, (size_t)n * 3) != ICPMI_OK) return ICPMI_ERR_HIP;
+            if (h->d_stage_n3.ensure(h, (size_t)n * 3) != ICPMI_OK) return ICPMI_ERR_HIP;
             HIP_TRY(h, hipMemcpyAsync(h->d_stage_n3, scan_normals3, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, h->stream));
             d_n3 = h->d_stage_n3;
         }
@@ -642,8 +625,8 @@ icpmi_status icpmi_knn(icpmi_handle h, const float* q4, int64_t n, int32_t k, fl
         return ICPMI_OK;
     }
     const size_t cnt = (size_t)n * k + 1;
-    if (ensure_cap(h, &h->d_reading, &h->cap_reading, (size_t)n + 1) != ICPMI_OK || ensure_cap(h, &h->d_sidx, &h->cap_sidx, cnt) != ICPMI_OK ||
-        ensure_cap(h, &h->d_d2, &h->cap_d2, cnt) != ICPMI_OK || ensure_cap(h, &h->d_hard, &h->cap_hard, (size_t)n + 1) != ICPMI_OK)
+    if (h->d_reading.ensure(h, (size_t)n + 1) != ICPMI_OK || h->d_sidx.ensure(h, cnt) != ICPMI_OK ||
+        h->d_d2.ensure(h, cnt) != ICPMI_OK || h->d_hard.ensure(h, (size_t)n + 1) != ICPMI_OK)
         return ICPMI_ERR_HIP;
     HIP_TRY(h, hipMemcpyAsync(h->d_reading, q4, (size_t)n * sizeof(float4), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipMemsetAsync(h->d_state, 0, sizeof(IcpState), h->stream));
@@ -703,7 +686,7 @@ icpmi_status icpmi_minimize_step(icpmi_handle h, const float* reading4, int64_t 
         return ICPMI_ERR_MISSING_NORMALS;
     }
     if (stats) { memset(stats, 0, sizeof *stats); stats->sensor_noise_overlap = -1.f; }
-    if (ensure_cap(h, &h->d_reading, &h->cap_reading, (size_t)n + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
+    if (h->d_reading.ensure(h, (size_t)n + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
     HIP_TRY(h, hipMemcpyAsync(h->d_reading, reading4, (size_t)n * sizeof(float4), hipMemcpyHostToDevice, h->stream));
     // d_reading has new contents: a tile-sorted copy of what was there before (an icpmi_knn with the same n) must not be searched in
     // its place (r3: tests/test_gpu_golden.py found the step computed on the previous call's queries)
@@ -766,14 +749,14 @@ icpmi_status icpmi_register_prior(icpmi_handle h, const float* scan4, int64_t n,
     if (n < 0 || (n > 0 && !scan4) || !prior) { h->last_error = "register_prior: bad arguments"; return ICPMI_ERR_INVALID_ARG; }
     h->scan_map_n = 0;
     if (n > 0) {
-        if (ensure_cap(h, &h->d_stage_in, &h->cap_stage_in, (size_t)n + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
-        if (ensure_cap(h, &h->d_scan_map, &h->cap_scan_map, (size_t)n + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
+        if (h->d_stage_in.ensure(h, (size_t)n + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
+        if (h->d_scan_map.ensure(h, (size_t)n + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
         HIP_TRY(h, hipMemcpyAsync(h->d_stage_in, scan4, (size_t)n * sizeof(float4), hipMemcpyHostToDevice, h->stream));
         icpmi_status s = ops_transform_dev(h, prior, h->d_stage_in, n, h->d_scan_map); // Mapper.cpp:197
         if (s != ICPMI_OK) return s;
         h->scan_map_n = n;
     }
-    return register_impl(h, (const float*)h->d_scan_map, n, nullptr, 0, T_out, stats);
+    return register_impl(h, (const float*)h->d_scan_map.get(), n, nullptr, 0, T_out, stats);
 }
 
 // ... with the scan already in HBM (sensor frame): what a scan stream that lives on the device -- or a benchmark that must not time
@@ -784,12 +767,12 @@ icpmi_status icpmi_register_prior_dev(icpmi_handle h, const float* d_scan4, int6
     if (n < 0 || (n > 0 && !d_scan4) || !prior) { h->last_error = "register_prior_dev: bad arguments"; return ICPMI_ERR_INVALID_ARG; }
     h->scan_map_n = 0;
     if (n > 0) {
-        if (ensure_cap(h, &h->d_scan_map, &h->cap_scan_map, (size_t)n + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
+        if (h->d_scan_map.ensure(h, (size_t)n + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
         icpmi_status s = ops_transform_dev(h, prior, (const float4*)d_scan4, n, h->d_scan_map); // Mapper.cpp:197
         if (s != ICPMI_OK) return s;
         h->scan_map_n = n;
     }
-    return register_impl(h, (const float*)h->d_scan_map, n, nullptr, 0, T_out, stats);
+    return register_impl(h, (const float*)h->d_scan_map.get(), n, nullptr, 0, T_out, stats);
 }
 
 icpmi_status icpmi_map_update_staged(icpmi_handle h, const float correction[16], float min_dist, int32_t normals_knn, uint8_t* keep_out,
@@ -799,7 +782,7 @@ icpmi_status icpmi_map_update_staged(icpmi_handle h, const float correction[16],
     if (!correction || !(min_dist >= 0.f)) { h->last_error = "map_update_staged: bad arguments"; return ICPMI_ERR_INVALID_ARG; }
     if (h->scan_map_n <= 0) { h->last_error = "map_update_staged: no scan staged by icpmi_register_prior"; return ICPMI_ERR_INVALID_ARG; }
     const int64_t n = h->scan_map_n;
-    if (ensure_cap(h, &h->d_stage_in, &h->cap_stage_in, (size_t)n + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
+    if (h->d_stage_in.ensure(h, (size_t)n + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
     icpmi_status s = ops_transform_dev(h, correction, h->d_scan_map, n, h->d_stage_in); // Mapper.cpp:221
     if (s != ICPMI_OK) return s;
     return ops_map_update_dev(h, h->d_stage_in, n, nullptr, min_dist, normals_knn, keep_out, appended, new_m);
@@ -985,7 +968,7 @@ icpmi_status icpmi_voxel_keep_first(icpmi_handle h, const float* in4, int64_t n,
 static icpmi_status stage_chain_scalar(icpmi_handle h, const float* scan_scalar, int64_t n)
 {
     if (!scan_scalar || n == 0) return ICPMI_OK;
-    if (ensure_cap(h, &h->d_stage_s, &h->cap_stage_s, (size_t)n + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
+    if (h->d_stage_s.ensure(h, (size_t)n + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
     HIP_TRY(h, hipMemcpyAsync(h->d_stage_s, scan_scalar, (size_t)n * sizeof(float), hipMemcpyHostToDevice, h->stream));
     return ICPMI_OK;
 }
@@ -1003,10 +986,10 @@ icpmi_status icpmi_map_update_chain(icpmi_handle h, const float* scan4, int64_t 
     CHECK_H(h);
     if (n < 0 || (n > 0 && !scan4) || (chain_needs_pose(ops, n_ops) && !to_sensor) || (from_sensor && !to_sensor)) { h->last_error = "map_update_chain: bad arguments"; return ICPMI_ERR_INVALID_ARG; }
     if (n > 0) {
-        if (ensure_cap(h, &h->d_stage_in, &h->cap_stage_in, (size_t)n + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
+        if (h->d_stage_in.ensure(h, (size_t)n + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
         HIP_TRY(h, hipMemcpyAsync(h->d_stage_in, scan4, (size_t)n * sizeof(float4), hipMemcpyHostToDevice, h->stream));
         if (scan_normals3) {
-            if (ensure_cap(h, &h->d_stage_n3, &h->cap_stage_n3, (size_t)n * 3) != ICPMI_OK) return ICPMI_ERR_HIP;
+            if (h->d_stage_n3.ensure(h, (size_t)n * 3) != ICPMI_OK) return ICPMI_ERR_HIP;
             HIP_TRY(h, hipMemcpyAsync(h->d_stage_n3, scan_normals3, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, h->stream));
         }
         icpmi_status s = stage_chain_scalar(h, scan_scalar, n);
@@ -1024,7 +1007,7 @@ icpmi_status icpmi_map_update_chain_staged(icpmi_handle h, const float correctio
     if (!correction || (chain_needs_pose(ops, n_ops) && !to_sensor) || (from_sensor && !to_sensor)) { h->last_error = "map_update_chain_staged: bad arguments"; return ICPMI_ERR_INVALID_ARG; }
     if (h->scan_map_n <= 0) { h->last_error = "map_update_chain_staged: no scan staged by icpmi_register_prior"; return ICPMI_ERR_INVALID_ARG; }
     const int64_t n = h->scan_map_n;
-    if (ensure_cap(h, &h->d_stage_in, &h->cap_stage_in, (size_t)n + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
+    if (h->d_stage_in.ensure(h, (size_t)n + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
     icpmi_status s = ops_transform_dev(h, correction, h->d_scan_map, n, h->d_stage_in); // Mapper.cpp:221
     if (s == ICPMI_OK) s = stage_chain_scalar(h, scan_scalar, n);
     if (s != ICPMI_OK) return s;

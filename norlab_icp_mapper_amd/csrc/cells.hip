@@ -160,7 +160,7 @@ static icpmi_status cells_enqueue(icpmi_ctx* c, float cell_size, int bits)
     CbCell* cells = reinterpret_cast<CbCell*>(hdr + 1);
     unsigned* rank_of = reinterpret_cast<unsigned*>(cells + CB_MAXCELLS);
     const int64_t base = c->cell_log_n;
-    icpmi_status s = ensure_cap_keep(c, &c->d_cell_log, &c->cap_cell_log, (size_t)(base + n) + 1, (size_t)base);
+    icpmi_status s = c->d_cell_log.ensure_keep(c, (size_t)(base + n) + 1, (size_t)base);
     if (s != ICPMI_OK) return s;
     // one fill: key = ~0 (empty), first = ~0 (atomicMin), count = ~0 -- the adds wrap it to (points - 1), the rank kernel reads count + 1
     HIP_TRY(c, hipMemsetAsync(tab, 0xff, sizeof(CbSlot) * CB_SLOTS, c->stream));

@@ -143,9 +143,9 @@ icpmi_status merge_blocks_reserve(icpmi_ctx* c, int n_ranks)
     if (n_ranks > 256) return ICPMI_OK; // (the R block headers arrive in 256 words of the host-mapped page, common.h: ICPMI_PROGRESS_HDR_WORD -- larger jobs keep the three-collective epoch)
     const size_t b4 = (size_t)block_cfg + 1;
     if (b4 * (size_t)n_ranks >= (1ull << 31)) return ICPMI_OK; // (the merge indexes the gathered span with 31 bits: such a job keeps the old epoch)
-    if (ensure_cap(c, &c->d_merge_send, &c->cap_merge_send, b4 + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
-    if (ensure_cap(c, &c->d_merge_recv, &c->cap_merge_recv, b4 * (size_t)n_ranks + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
-    if (ensure_cap(c, &c->d_merged, &c->cap_merged, (size_t)block_cfg * (size_t)n_ranks + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
+    if (c->d_merge_send.ensure(c, b4 + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
+    if (c->d_merge_recv.ensure(c, b4 * (size_t)n_ranks + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
+    if (c->d_merged.ensure(c, (size_t)block_cfg * (size_t)n_ranks + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
     c->merge_block = block_cfg;
     return ICPMI_OK;
 }
@@ -166,7 +166,7 @@ icpmi_status comm_init(icpmi_ctx* c, const icpmi_comm_id* id, int n_ranks, int r
             c->comm = nullptr; c->comm_ranks = R; c->comm_rank = 0; c->comm_loop_shift = sh ? (float)atof(sh) : 0.f;
             c->comm_loop_ragged = rg && atoi(rg) != 0;
             fprintf(stderr, "[icpmi] loopback communicator active: %d simulated ranks on one GPU, no RCCL (ICPMI_COMM_LOOPBACK)\n", R);
-            if (ensure_cap(c, &c->d_comm_cnt, &c->cap_comm_cnt, (size_t)2 * R + 16) != ICPMI_OK) return ICPMI_ERR_HIP;
+            if (c->d_comm_cnt.ensure(c, (size_t)2 * R + 16) != ICPMI_OK) return ICPMI_ERR_HIP;
             return merge_blocks_reserve(c, R);
         }
     }
@@ -174,7 +174,7 @@ icpmi_status comm_init(icpmi_ctx* c, const icpmi_comm_id* id, int n_ranks, int r
     if (!r.lib) { c->last_error = r.error; return ICPMI_ERR_HIP; }
     if (c->comm) { RCCL_TRY(c, r.CommDestroy((ncclComm_t)c->comm)); c->comm = nullptr; }
     // the words of the epoch's count / ready exchanges: allocated here so that no allocation can fail between two collectives
-    if (ensure_cap(c, &c->d_comm_cnt, &c->cap_comm_cnt, (size_t)2 * n_ranks + 16) != ICPMI_OK) return ICPMI_ERR_HIP;
+    if (c->d_comm_cnt.ensure(c, (size_t)2 * n_ranks + 16) != ICPMI_OK) return ICPMI_ERR_HIP;
     if (merge_blocks_reserve(c, n_ranks) != ICPMI_OK) return ICPMI_ERR_HIP; // (a failure here is reported before any collective exists)
     ncclUniqueId u;
     memcpy(&u, id, sizeof u);

@@ -301,7 +301,8 @@ struct DevBlockCache {
 };
 inline DevBlockCache& dev_block_cache() { static DevBlockCache* c = new DevBlockCache; return *c; } // (never destroyed: the runtime may be gone first)
 
-// every cached block of every device back to the runtime (icpmi_trim_cache; the out-of-memory path; the last handle's destruction).
+// every cached block of every device back to the runtime (icpmi_trim_cache; the out-of-memory path -- and nothing else: a destroyed handle,
+// the last one included, leaves its blocks cached, api.hip: icpmi_destroy).
 // Caller holds bc.mu.  hipFree synchronises the device it runs on; the blocks are idle, so any device will do.
 inline void dev_cache_release_locked(DevBlockCache& bc)
 {
@@ -345,9 +346,18 @@ inline hipError_t dev_malloc(void** p, size_t bytes)
     return hipSuccess;
 }
 
-// synced == true: the caller has just synchronised the block's device itself (icpmi_destroy: ONE device-wide wait for its ~80 blocks instead of
-// one per block, each under the exclusive capture gate -- ADVICE r5)
-inline hipError_t dev_free(void* p, bool synced = false)
+// A destroy returns ~80 blocks: ONE device-wide wait under the exclusive capture gate when this scope opens, and every dev_free of the thread
+// inside it skips its own (one wait per block stalled every other thread's registration on this GPU ~80 times in a row).  The
+// scope covers blocks of the device that is current when it opens (icpmi_destroy: the handle's).
+struct DevFreeSynced {
+    static int& depth() { static thread_local int d = 0; return d; }
+    DevFreeSynced() { std::unique_lock<std::shared_mutex> gate(capture_gate()); (void)hipDeviceSynchronize(); ++depth(); }
+    ~DevFreeSynced() { --depth(); }
+    DevFreeSynced(const DevFreeSynced&) = delete;
+    DevFreeSynced& operator=(const DevFreeSynced&) = delete;
+};
+
+inline hipError_t dev_free(void* p)
 {
     if (!p) return hipSuccess;
     DevBlockCache& bc = dev_block_cache();
@@ -360,7 +370,7 @@ inline hipError_t dev_free(void* p, bool synced = false)
         lv = it->second; bc.live.erase(it);
     }
     hipError_t e = hipSuccess;
-    if (!synced) {
+    if (!DevFreeSynced::depth()) {
         // what hipFree would have waited for -- on the device the block lives on; not while another thread captures
         std::unique_lock<std::shared_mutex> gate(capture_gate());
         int cur = 0;
@@ -380,12 +390,60 @@ inline hipError_t dev_free(void* p, bool synced = false)
     }
     return e;
 }
-inline hipError_t dev_sync_for_free() // one device-wide wait under the capture gate, for a run of dev_free(p, true)
-{
-    std::unique_lock<std::shared_mutex> gate(capture_gate());
-    return hipDeviceSynchronize();
-}
 
+// ------------------------------------------------------------------------------------------------
+// DevArr<T>: a device array that OWNS its block -- pointer and capacity (in entries) as one unit.  Every device array a handle keeps
+// (icpmi_ctx, SelfGridCtx) and every per-call block (DevBuf) is one: it frees itself through dev_free when it dies, a ping-pong exchange
+// is one swap(a, b), and it reads as a T* wherever a pointer is expected.  It cannot be copied (`auto p = c->d_x;` does not compile) and
+// its address cannot be taken (`(void**)&c->d_x` would write a pointer past its capacity).
+// Everything that is a plain pointer BORROWS: GridLevels::pts / cs / pos0, nn_hist0, nn_match_pt, qsorted_src, d_state_mirror, d_progress,
+// d_nocc_host, kernel arguments -- views of blocks some DevArr (or pinned host memory) owns, never freed through them.
+// The growth rule is part of the type: how much more than asked for a reallocation takes decides which requests the block cache can serve
+// and how much HBM a long run holds.
+// ------------------------------------------------------------------------------------------------
+struct icpmi_ctx;
+// doubling: a map that grows by a scan's worth of points per update would otherwise reallocate a few of its ~20 arrays on every
+// update, and a hipFree is a device-wide synchronisation (~0.2 ms each, r3 HIP trace: 1 ms per map update); HBM is not the constraint
+struct GrowDouble { static size_t want(size_t need) { return 2 * need + 64; } static constexpr bool drains_stream = false; };
+// the self grid's tables follow the cloud closely (a quarter of headroom); the handle's stream is drained before a block is given back
+struct GrowQuarter { static size_t want(size_t need) { return need + need / 4 + 64; } static constexpr bool drains_stream = true; };
+// operator scratch, in bytes
+struct GrowScratch { static size_t want(size_t need) { return 2 * need + 256; } static constexpr bool drains_stream = true; };
+
+template <typename T, class Grow = GrowDouble>
+class DevArr {
+    T* p = nullptr;
+    size_t cap = 0;
+public:
+    DevArr() = default;
+    DevArr(const DevArr&) = delete;
+    DevArr& operator=(const DevArr&) = delete;
+    DevArr(DevArr&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    DevArr& operator=(DevArr&& o) noexcept { swap(*this, o); return *this; }
+    ~DevArr() { (void)reset(); }
+    DevArr* operator&() = delete;
+    friend void swap(DevArr& a, DevArr& b) noexcept { std::swap(a.p, b.p); std::swap(a.cap, b.cap); }
+    operator T*() const { return p; }
+    T* operator->() const { return p; }
+    T* get() const { return p; }
+    size_t capacity() const { return cap; }
+    hipError_t reset() { const hipError_t e = dev_free(p); p = nullptr; cap = 0; return e; }
+    // a block of exactly n entries (an empty array only: what is allocated once, or per call)
+    hipError_t alloc(size_t n)
+    {
+        if (p) return hipErrorInvalidValue;
+        if (!n) n = 1;
+        const hipError_t e = dev_malloc((void**)&p, n * sizeof(T));
+        if (e == hipSuccess) cap = n; else p = nullptr;
+        return e;
+    }
+    // at least `need` entries, contents undefined; *fresh = true when the block is a new one.  Errors: last_error, ICPMI_ERR_HIP.
+    icpmi_status ensure(icpmi_ctx* c, size_t need, bool* fresh = nullptr);
+    // ... the first `used` entries survive a reallocation
+    icpmi_status ensure_keep(icpmi_ctx* c, size_t need, size_t used);
+};
+// scratch device allocation of one call: freed on every exit path (dev_free waits for work still using it)
+template <typename T> using DevBuf = DevArr<T>;
 
 // Streams through a process-wide pool (r5): hipStreamCreateWithFlags takes 1.7 - 23 ms on this runtime and hipStreamDestroy 2 - 3.5 ms
 // (rocprofv3 --hip-runtime-trace on the BASELINE config 4 replay: 10 creations = 50 ms of a run whose 42 scans take 130 ms) -- a mapper
@@ -438,38 +496,37 @@ struct icpmi_ctx {
     float mean[3] = {0, 0, 0};
     GridParams grid{};
     int64_t n_occupied = 0;
-    float4* d_map_sorted = nullptr;     // xyz centred, w = bits of the original index
-    float4* d_normals_sorted = nullptr; // xyz normal, w unused; nullptr if the map has no normals
+    DevArr<float4> d_map_sorted;        // xyz centred, w = bits of the original index
+    DevArr<float4> d_normals_sorted;    // xyz normal, w unused; unused if the map has no normals
     // point and normal of level-0 position s side by side (pn[2 s], pn[2 s + 1]: one 64-byte sector): what the pair sums of a k > 1
     // chain gather at random -- two separate 16-byte gathers fetch two sectors (r3: 76.5 MB per launch for 33.6 MB of payload)
-    float4* d_map_pn = nullptr; size_t cap_map_pn = 0;
-    unsigned* d_cell_start = nullptr;   // ncells + 1
-    size_t cap_map = 0, cap_cells = 0, cap_normals = 0;
+    DevArr<float4> d_map_pn;
+    DevArr<unsigned> d_cell_start;      // ncells + 1
     bool has_normals = false;
     // coarser pyramid levels (level 0 aliases d_map_sorted / d_cell_start)
     GridLevels levels{};
-    uint4* d_lvl_tab = nullptr;       // device copy of `levels` as 4 x uint4 per level (nn.hip reads it into LDS)
-    float4* d_lvl_pts[ICPMI_MAXLEV] = {};   size_t cap_lvl_pts[ICPMI_MAXLEV] = {};
-    unsigned* d_lvl_cs[ICPMI_MAXLEV] = {};  size_t cap_lvl_cs[ICPMI_MAXLEV] = {};
-    unsigned* d_lvl_pos0[ICPMI_MAXLEV] = {}; size_t cap_lvl_pos0[ICPMI_MAXLEV] = {};
-    unsigned* d_inv = nullptr; size_t cap_inv = 0; // original index -> level-0 position (kept for the incremental insert, map_build.hip: map_insert)
+    DevArr<uint4> d_lvl_tab;            // device copy of `levels` as 4 x uint4 per level (nn.hip reads it into LDS)
+    DevArr<float4> d_lvl_pts[ICPMI_MAXLEV];
+    DevArr<unsigned> d_lvl_cs[ICPMI_MAXLEV];
+    DevArr<unsigned> d_lvl_pos0[ICPMI_MAXLEV];
+    DevArr<unsigned> d_inv;             // original index -> level-0 position (kept for the incremental insert, map_build.hip: map_insert)
     // r4: incremental index insert.  A map that grew by an APPEND (Map::updateLocalPointCloud with PointDistanceMapperModule, the merge epoch
     // of the scan-sharded mapper) keeps its grid; its new index is the old one with the delta merged into the cell-sorted arrays of every
     // level -- one streaming pass per level instead of keys + histogram + scan + atomic scatter over all points.  The result is what a
     // full build on the same grid produces up to the order inside a cell (which nothing downstream sees): centred coordinates are
     // recomputed from the raw points with the NEW centroid, bit for bit what map_build writes.
-    unsigned* d_lvl_key[ICPMI_MAXLEV] = {}; size_t cap_lvl_key[ICPMI_MAXLEV] = {};   // cell of every sorted position, per level
-    float4* d_alt_pts[ICPMI_MAXLEV] = {};   size_t cap_alt_pts[ICPMI_MAXLEV] = {};   // ping-pong set the merge writes into
-    unsigned* d_alt_cs[ICPMI_MAXLEV] = {};  size_t cap_alt_cs[ICPMI_MAXLEV] = {};
-    unsigned* d_alt_pos0[ICPMI_MAXLEV] = {}; size_t cap_alt_pos0[ICPMI_MAXLEV] = {};
-    unsigned* d_alt_key[ICPMI_MAXLEV] = {}; size_t cap_alt_key[ICPMI_MAXLEV] = {};
-    float4* d_raw0 = nullptr; size_t cap_raw0 = 0;           // level-0 twin: the RAW points (w = original index) in level-0 sorted order (centred handles)
-    float4* d_alt_raw0 = nullptr; size_t cap_alt_raw0 = 0;
-    unsigned* d_ins_dstart0 = nullptr; size_t cap_ins_dstart0 = 0; // level 0's delta prefix, kept while the upper levels are merged
-    float4* d_alt_nsorted = nullptr; size_t cap_alt_nsorted = 0;
-    float4* d_alt_pn = nullptr; size_t cap_alt_pn = 0;
-    unsigned* d_ins_key = nullptr; size_t cap_ins_key = 0;   // delta: cell key and rank inside the cell, per level
-    unsigned* d_ins_rank = nullptr; size_t cap_ins_rank = 0;
+    DevArr<unsigned> d_lvl_key[ICPMI_MAXLEV];// cell of every sorted position, per level
+    DevArr<float4> d_alt_pts[ICPMI_MAXLEV];// ping-pong set the merge writes into
+    DevArr<unsigned> d_alt_cs[ICPMI_MAXLEV];
+    DevArr<unsigned> d_alt_pos0[ICPMI_MAXLEV];
+    DevArr<unsigned> d_alt_key[ICPMI_MAXLEV];
+    DevArr<float4> d_raw0;              // level-0 twin: the RAW points (w = original index) in level-0 sorted order (centred handles)
+    DevArr<float4> d_alt_raw0;
+    DevArr<unsigned> d_ins_dstart0;     // level 0's delta prefix, kept while the upper levels are merged
+    DevArr<float4> d_alt_nsorted;
+    DevArr<float4> d_alt_pn;
+    DevArr<unsigned> d_ins_key;         // delta: cell key and rank inside the cell, per level
+    DevArr<unsigned> d_ins_rank;
     bool ins_ready = false;            // the current index carries the key / twin arrays the insert needs
     bool ins_normals_changed = false;  // set by a caller that recomputed the normals of the WHOLE cloud before an append-build (ops.hip)
     double sum_raw[3] = {0, 0, 0};     // sum of the raw coordinates of the indexed cloud (the centroid of the grown cloud without a pass over it)
@@ -482,47 +539,45 @@ struct icpmi_ctx {
     int64_t ins_count = 0, full_count = 0; // builds served by the insert / by the full path (diagnostics)
 
     // scratch for set_map
-    unsigned* d_keys = nullptr; size_t cap_keys = 0;
+    DevArr<unsigned> d_keys;
     int oct_depth_hint = 0, oct_tag = 0; long oct_respeculated = 0; // octree.hip: tree depth of the previous call on this handle (the sort runs ahead of the depth's arrival), wrong guesses
-    unsigned* d_fill = nullptr; size_t cap_fill = 0; bool fill_clean = false; // the count table of the grid builds: zero between builds while fill_clean (map_build.hip: counts_begin)
-    unsigned* d_blocksums = nullptr; size_t cap_blocksums = 0;
-    double* d_red = nullptr; size_t cap_red = 0;
+    DevArr<unsigned> d_fill; bool fill_clean = false; // the count table of the grid builds: zero between builds while fill_clean (map_build.hip: counts_begin)
+    DevArr<unsigned> d_blocksums;
+    DevArr<double> d_red;
 
     // reading-side buffers (capacity in entries)
-    float4* d_reading = nullptr; size_t cap_reading = 0;       // centred reading
-    float4* d_read_normals = nullptr; size_t cap_read_normals = 0;
-    float*  d_read_noise = nullptr; size_t cap_read_noise = 0; int64_t read_noise_n = 0; // simpleSensorNoise of the NEXT reading (one shot)
-    float*  d_read_scalar = nullptr; size_t cap_read_scalar = 0; int64_t read_scalar_n = 0; // GenericDescriptor{source: reading} row of the NEXT reading
-    float4* d_qsorted = nullptr; size_t cap_qsorted = 0;       // centred reading sorted by tile (NN locality)
-    int*    d_qindex = nullptr; size_t cap_qindex = 0;         // sorted position -> original index
-    unsigned* d_qkeys = nullptr; size_t cap_qkeys = 0;
-    unsigned* d_qtile = nullptr; size_t cap_qtile = 0;
+    DevArr<float4> d_reading;           // centred reading
+    DevArr<float4> d_read_normals;
+    DevArr<float> d_read_noise; int64_t read_noise_n = 0; // simpleSensorNoise of the NEXT reading (one shot)
+    DevArr<float> d_read_scalar; int64_t read_scalar_n = 0; // GenericDescriptor{source: reading} row of the NEXT reading
+    DevArr<float4> d_qsorted;           // centred reading sorted by tile (NN locality)
+    DevArr<int> d_qindex;               // sorted position -> original index
+    DevArr<unsigned> d_qkeys;
+    DevArr<unsigned> d_qtile;
     int64_t qsorted_n = -1; const float4* qsorted_src = nullptr; // which reading d_qsorted was built from
-    float4* d_stage_in = nullptr; size_t cap_stage_in = 0;     // host->device staging
-    float*  d_stage_n3 = nullptr; size_t cap_stage_n3 = 0;
+    DevArr<float4> d_stage_in;          // host->device staging
+    DevArr<float> d_stage_n3;
     // resident copy of the map as it was handed to set_map (original frame, caller's order): what the
     // device-side map update appends to and rebuilds from
-    float4* d_raw = nullptr; size_t cap_raw = 0;
-    float*  d_raw_n3 = nullptr; size_t cap_raw_n3 = 0;
+    DevArr<float4> d_raw;
+    DevArr<float> d_raw_n3;
     int64_t m_raw = 0; bool raw_has_normals = false;
     // one tracked scalar descriptor of the resident map (`probabilityDynamic` for the shipped chain) and the ping-pong
     // set the map-update chain compacts into (ops.hip: ops_map_update_chain)
-    float*  d_raw_s = nullptr; size_t cap_raw_s = 0; bool raw_has_scalar = false;
-    int*    d_src = nullptr; size_t cap_src = 0;               // provenance of every point of the map being updated
-    float4* d_alt_raw = nullptr; size_t cap_alt_raw = 0;
-    float*  d_alt_n3 = nullptr; size_t cap_alt_n3 = 0;
-    float*  d_alt_s = nullptr; size_t cap_alt_s = 0;
-    int*    d_alt_src = nullptr; size_t cap_alt_src = 0;
-    float*  d_stage_s = nullptr; size_t cap_stage_s = 0;
+    DevArr<float> d_raw_s; bool raw_has_scalar = false;
+    DevArr<int> d_src;                  // provenance of every point of the map being updated
+    DevArr<float4> d_alt_raw;
+    DevArr<float> d_alt_n3;
+    DevArr<float> d_alt_s;
+    DevArr<int> d_alt_src;
+    DevArr<float> d_stage_s;
     // scratch of the map-side operators (hash tables, beam buckets, flags): kept between calls -- a hipMalloc / hipFree
     // pair costs more than most of the kernels that use them
-    void* scratch[ICPMI_SCRATCH_SLOTS] = {};                  // slots 0..9: operators on the handle's stream; 10..19: the DynamicPoints module (may run on `side`)
-    size_t scratch_bytes[ICPMI_SCRATCH_SLOTS] = {};
+    DevArr<unsigned char, GrowScratch> scratch[ICPMI_SCRATCH_SLOTS];// slots 0..9: operators on the handle's stream; 10..19: the DynamicPoints module (may run on `side`)
     hipStream_t side = nullptr;                              // map-update chain: DynamicPoints next to the decimation that follows it (ops.hip)
     hipEvent_t side_fork = nullptr, side_join = nullptr;
     // the scan of the last icpmi_register_prior, in the map frame by its prior (what Mapper::processInput calls `input`)
-    float4* d_scan_map = nullptr; size_t cap_scan_map = 0; int64_t scan_map_n = 0;
-    float* d_T16 = nullptr;           // a 4x4 for device-side transforms
+    DevArr<float4> d_scan_map; int64_t scan_map_n = 0;
     icpmi_ctx* temp = nullptr;        // private handle of the map-side operators (indexes arbitrary clouds), created on first use
     // PointDistanceMapperModule builds its kd-tree on the map AS IT IS (PointDistanceMapperModule.cpp:32-36), the ICP matcher on the
     // map minus its centroid: squared distances in the two frames differ by rounding, and a keep decision at d2 ~ minDist^2 with
@@ -534,15 +589,15 @@ struct icpmi_ctx {
     bool keep_raw = true;             // temp handles index clouds they do not own: no resident copy of the input
     bool no_centre = false;           // temp handles of the map-side operators: index raw coordinates (mean = 0)
     bool is_raw_index = false;        // the private raw-frame index of a resident map (ops.hip: raw_index): grows by appends with its owner
-    int*    d_sidx = nullptr; size_t cap_sidx = 0;             // k x n sorted-map index (-1 none)
-    float*  d_d2 = nullptr; size_t cap_d2 = 0;                 // k x n
-    unsigned* d_hard = nullptr; size_t cap_hard = 0;           // hard query list
-    unsigned* d_selhist = nullptr; size_t cap_selhist = 0;     // ICPMI_SELHIST_WORDS per reading of a batch
+    DevArr<int> d_sidx;                 // k x n sorted-map index (-1 none)
+    DevArr<float> d_d2;                 // k x n
+    DevArr<unsigned> d_hard;            // hard query list
+    DevArr<unsigned> d_selhist;         // ICPMI_SELHIST_WORDS per reading of a batch
     unsigned* nn_hist0 = nullptr;     // set by the loop when the NN kernel should build the level-0 histogram
     bool nn_builds_hist0 = false;     // set by the NN launcher: true if the launched variant did build it
     bool nn_builds_win = false;       // ... true if it counted the speculative window (ICPMI_S2_WIN: nnk_wg_kernel in a fused-selection loop)
     int nn_iter_hint = 0;             // iteration index of the launch being enqueued (> 0: seeded by the previous match)
-    float4* d_match_pt = nullptr; size_t cap_match_pt = 0;     // k = 1 loop: matched map point (xyz, original index bits) per query slot
+    DevArr<float4> d_match_pt;          // k = 1 loop: matched map point (xyz, original index bits) per query slot
     float4* nn_match_pt = nullptr;    // set by the loop: keep the loop state (sidx, d2, matched point) in query order
     bool nn_out_sorted = false;       // set by the NN launcher: true if the launched kernel did so
     bool nn_sorted_k = false;         // set by the loop for k > 1: keep the k matches of a query at its slot of the tile-sorted order
@@ -551,8 +606,8 @@ struct icpmi_ctx {
     int64_t last_match_n = 0; int last_match_k = 0; bool last_match_sorted = false;
     // icpmi_get_covariance (loop.hip: loop_covariance): per-workgroup partials of H / S, then the 36 floats of Cov; cov_ready = computed
     // for the last single registration (read only while last_match_n says its pairs are still the ones in the buffers)
-    double* d_cov = nullptr; size_t cap_cov = 0; bool cov_ready = false;
-    IcpState* d_state = nullptr;                               // ICPMI_MAX_BATCH states (a single registration uses the first)
+    DevArr<double> d_cov; bool cov_ready = false;
+    DevArr<IcpState> d_state;           // ICPMI_MAX_BATCH states (a single registration uses the first)
     IcpState* h_state = nullptr;                               // pinned mirror (ICPMI_MAX_BATCH)
     bool zero_pending = false;                                 // d_state / d_selhist still to be cleared: on the stream the handle really uses, at its first call (zero_state_if_pending)
     unsigned scan_tag = 0;                                     // call number of device_scan_flags_count: the tag its count comes back with (map_build.hip)
@@ -577,14 +632,14 @@ struct icpmi_ctx {
     int seg_prev_iters = 0, seg_last_iters = 0;
 
     // buffers of the map-growth epoch (ops.hip: ops_staged_merge_allgather): this rank's accepted points, all ranks' blocks, the merged set
-    float4* d_merge_send = nullptr; size_t cap_merge_send = 0;
-    float4* d_merge_recv = nullptr; size_t cap_merge_recv = 0;
-    float4* d_merged = nullptr; size_t cap_merged = 0;
+    DevArr<float4> d_merge_send;
+    DevArr<float4> d_merge_recv;
+    DevArr<float4> d_merged;
     // RCCL communicator of the scan-sharded mapping mode (comm.hip); null = a single rank
     void* comm = nullptr; int comm_ranks = 1, comm_rank = 0;
     float comm_loop_shift = 0.f;      // loopback communicator (comm.hip): rank r's block = this rank's, moved r * shift along x
     bool comm_loop_ragged = false;    // ... and cut to unequal sizes (comm.hip: loop_counts_kernel)
-    long long* d_comm_cnt = nullptr; size_t cap_comm_cnt = 0; // words of the epoch's count / ready exchanges (allocated by comm_init)
+    DevArr<long long> d_comm_cnt;       // words of the epoch's count / ready exchanges (allocated by comm_init)
     // r5: the ONE-collective epoch (ops.hip: ops_staged_merge_allgather).  Every rank hands in a block of merge_block + 1 float4: a header
     // {bits(count) | -1, magic} and up to merge_block accepted points; the blocks are sized when the communicator is created (no allocation,
     // hence no `ready` exchange, between the local accept and the collective).  0: the three-collective epoch of r4.
@@ -592,11 +647,11 @@ struct icpmi_ctx {
     long merge_fast_epochs = 0, merge_slow_epochs = 0; // epochs served by the one-collective path / by the count + ready + points path
     int64_t merged_last_n = 0;        // points of the last epoch's merged set, still in d_merged (icpmi_staged_merged_points)
     // r6 (cells.hip): every merged set binned by icpmi_staged_bin_cells, cell after cell; the host keeps {offset, count} runs per cell id
-    float4* d_cell_log = nullptr; size_t cap_cell_log = 0; int64_t cell_log_n = 0;
+    DevArr<float4> d_cell_log; int64_t cell_log_n = 0;
     // r6 (ops.hip: surface_normals_dev): d^2 of the k-th neighbour of every resident point as the last SurfaceNormal pass over the resident map found it
     // (original order) -- an append recomputes only the normals an appended point can have changed.  Valid for the first dk_m points while
     // dk_epoch == raw_epoch (nobody rewrote the resident copy) and the filter's knn is dk_knn.
-    float* d_raw_dk = nullptr; size_t cap_raw_dk = 0; int64_t dk_m = 0; int dk_knn = 0; uint64_t dk_epoch = ~0ull;
+    DevArr<float> d_raw_dk; int64_t dk_m = 0; int dk_knn = 0; uint64_t dk_epoch = ~0ull;
     long normals_incremental = 0, normals_full = 0; int64_t normals_last_searched = 0;   // diagnostics (icpmi_debug_counters 20 / 21 / 22)
     bool merged_binned = false;       // the merged set of the last epoch is in the log already
     int cell_bits_hint = 0;           // key bits the previous epoch's cell count needed (the sort is enqueued before the count is known)
@@ -616,16 +671,30 @@ struct icpmi_ctx {
         }                                                                                      \
     } while (0)
 
-template <typename T>
-static inline icpmi_status ensure_cap(icpmi_ctx* c, T** p, size_t* cap, size_t need)
+template <typename T, class Grow>
+icpmi_status DevArr<T, Grow>::ensure(icpmi_ctx* c, size_t need, bool* fresh)
 {
-    if (need <= *cap && *p) return ICPMI_OK;
-    if (*p) { HIP_TRY(c, dev_free(*p)); *p = nullptr; *cap = 0; }
-    // doubling: a map that grows by a scan's worth of points per update would otherwise reallocate a few of its ~20 arrays on every
-    // update, and a hipFree is a device-wide synchronisation (~0.2 ms each, r3 HIP trace: 1 ms per map update); HBM is not the constraint
-    size_t want = 2 * need + 64;
-    HIP_TRY(c, dev_malloc((void**)p, want * sizeof(T)));
-    *cap = want;
+    if (need <= cap && p) return ICPMI_OK;
+    if (p) {
+        if (Grow::drains_stream) HIP_TRY(c, hipStreamSynchronize(c->stream));
+        HIP_TRY(c, reset());
+    }
+    const size_t want = Grow::want(need);
+    HIP_TRY(c, dev_malloc((void**)&p, want * sizeof(T)));
+    cap = want;
+    if (fresh) *fresh = true;
+    return ICPMI_OK;
+}
+template <typename T, class Grow>
+icpmi_status DevArr<T, Grow>::ensure_keep(icpmi_ctx* c, size_t need, size_t used)
+{
+    if (need <= cap && p) return ICPMI_OK;
+    const size_t want = Grow::want(need);
+    T* q = nullptr;
+    HIP_TRY(c, dev_malloc((void**)&q, want * sizeof(T)));
+    if (p && used) HIP_TRY(c, hipMemcpyAsync(q, p, used * sizeof(T), hipMemcpyDeviceToDevice, c->stream));
+    if (p) { HIP_TRY(c, hipStreamSynchronize(c->stream)); HIP_TRY(c, reset()); }
+    p = q; cap = want;
     return ICPMI_OK;
 }
 
@@ -655,18 +724,6 @@ static inline void drop_loop_graphs(icpmi_ctx* c)
     c->graphs.reset();
     c->last_match_n = 0;
 }
-
-// scratch device allocation of one call: freed on every exit path (hipFree waits for work still using it)
-template <typename T>
-struct DevBuf {
-    T* p = nullptr;
-    DevBuf() = default;
-    DevBuf(const DevBuf&) = delete;
-    DevBuf& operator=(const DevBuf&) = delete;
-    ~DevBuf() { if (p) dev_free(p); }
-    hipError_t alloc(size_t n) { return dev_malloc((void**)&p, (n ? n : 1) * sizeof(T)); }
-    operator T*() const { return p; }
-};
 
 // Small device -> host read through the pinned page: a copy into pageable memory is staged and blocks for tens of
 // microseconds, and a map update makes a dozen of them (counts after every compaction, grid statistics).
@@ -735,28 +792,8 @@ static inline icpmi_status upload_small(icpmi_ctx* c, void* d_dst, const void* h
 template <typename T>
 static inline T* scratch_get(icpmi_ctx* c, int k, size_t count)
 {
-    const size_t need = (count ? count : 1) * sizeof(T);
-    if (need > c->scratch_bytes[k] || !c->scratch[k]) {
-        if (c->scratch[k]) { (void)hipStreamSynchronize(c->stream); (void)dev_free(c->scratch[k]); c->scratch[k] = nullptr; c->scratch_bytes[k] = 0; }
-        const size_t want = 2 * need + 256;
-        if (dev_malloc(&c->scratch[k], want) != hipSuccess) { c->scratch[k] = nullptr; c->last_error = "out of device memory (operator scratch)"; return nullptr; }
-        c->scratch_bytes[k] = want;
-    }
-    return (T*)c->scratch[k];
-}
-
-// like ensure_cap, but the first `used` entries survive a reallocation
-template <typename T>
-static inline icpmi_status ensure_cap_keep(icpmi_ctx* c, T** p, size_t* cap, size_t need, size_t used)
-{
-    if (need <= *cap && *p) return ICPMI_OK;
-    const size_t want = 2 * need + 64;
-    T* q = nullptr;
-    HIP_TRY(c, dev_malloc((void**)&q, want * sizeof(T)));
-    if (*p && used) HIP_TRY(c, hipMemcpyAsync(q, *p, used * sizeof(T), hipMemcpyDeviceToDevice, c->stream));
-    if (*p) { HIP_TRY(c, hipStreamSynchronize(c->stream)); HIP_TRY(c, dev_free(*p)); }
-    *p = q; *cap = want;
-    return ICPMI_OK;
+    if (c->scratch[k].ensure(c, (count ? count : 1) * sizeof(T)) != ICPMI_OK) { c->last_error = "out of device memory (operator scratch)"; return nullptr; }
+    return (T*)c->scratch[k].get();
 }
 
 // ---- device helpers -------------------------------------------------------------------------

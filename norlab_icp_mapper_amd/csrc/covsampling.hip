@@ -419,7 +419,7 @@ icpmi_status ops_covariance_sampling(icpmi_ctx* c, const float* in4, int64_t n, 
         // radix_sort_pairs' halves are [0, m) and [m, 2 m) of the arrays
         const unsigned* sorted = d_vals + (half ? m : 0);
         if (g == 6) lists = sorted;
-        else HIP_TRY(c, hipMemcpyAsync(d_lists.p + (size_t)k0 * n, sorted, (size_t)m * sizeof(unsigned), hipMemcpyDeviceToDevice, c->stream));
+        else HIP_TRY(c, hipMemcpyAsync(d_lists.get() + (size_t)k0 * n, sorted, (size_t)m * sizeof(unsigned), hipMemcpyDeviceToDevice, c->stream));
     }
     if (g < 6) lists = d_lists;
     if (nb > 0) {

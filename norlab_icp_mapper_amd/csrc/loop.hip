@@ -1276,7 +1276,7 @@ const float* loop_covariance_out(const icpmi_ctx* c) { return reinterpret_cast<c
 
 icpmi_status loop_covariance(icpmi_ctx* c, int64_t n, const LoopCfg& lc, bool sorted)
 {
-    if (ensure_cap(c, &c->d_cov, &c->cap_cov, (size_t)ICPMI_COV_NB * ICPMI_COV_NV + 18) != ICPMI_OK) return ICPMI_ERR_HIP; // (+ 36 floats)
+    if (c->d_cov.ensure(c, (size_t)ICPMI_COV_NB * ICPMI_COV_NV + 18) != ICPMI_OK) return ICPMI_ERR_HIP; // (+ 36 floats)
     const float4* rd = sorted ? c->d_qsorted : c->d_reading;
     const int* qi = sorted ? c->d_qindex : nullptr;
     const float4* mp = (sorted && lc.k == 1) ? c->d_match_pt : nullptr;
@@ -1295,7 +1295,7 @@ icpmi_status loop_covariance(icpmi_ctx* c, int64_t n, const LoopCfg& lc, bool so
 // registration is 3 graph nodes instead of 8
 icpmi_status loop_prepare_reading(icpmi_ctx* c, const float4* d_scan, int64_t n, const float* d_normals3, bool* head_done)
 {
-    if (ensure_cap(c, &c->d_reading, &c->cap_reading, (size_t)n + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
+    if (c->d_reading.ensure(c, (size_t)n + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
     const int blocks = (int)((n + 255) / 256);
     const bool fused = head_done && c->cfg.knn <= 8 && n > 0;
     if (head_done) *head_done = fused;
@@ -1304,7 +1304,7 @@ icpmi_status loop_prepare_reading(icpmi_ctx* c, const float4* d_scan, int64_t n,
         hipLaunchKernelGGL(centre_kernel, dim3(blocks), dim3(256), 0, c->stream, src, batch_of_one(n), c->mean[0], c->mean[1], c->mean[2], c->d_reading);
     }
     if (d_normals3) {
-        if (ensure_cap(c, &c->d_read_normals, &c->cap_read_normals, (size_t)n + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
+        if (c->d_read_normals.ensure(c, (size_t)n + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
         if (blocks) hipLaunchKernelGGL(pad_normals_kernel, dim3(blocks), dim3(256), 0, c->stream, d_normals3, n, c->d_read_normals);
     }
     HIP_TRY(c, hipGetLastError());
@@ -1345,11 +1345,11 @@ static BatchArgs cur_batch(const icpmi_ctx* c, int64_t n) { return c->batch_cur 
 static icpmi_status ensure_loop_buffers(icpmi_ctx* c, int64_t n, int k, int nscan = 1)
 {
     const size_t cnt = (size_t)n * k * nscan + 1;
-    if (ensure_cap(c, &c->d_sidx, &c->cap_sidx, cnt) != ICPMI_OK) return ICPMI_ERR_HIP;
-    if (ensure_cap(c, &c->d_d2, &c->cap_d2, cnt) != ICPMI_OK) return ICPMI_ERR_HIP;
-    if (ensure_cap(c, &c->d_hard, &c->cap_hard, (size_t)n * nscan + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
-    if (k == 1 && ensure_cap(c, &c->d_match_pt, &c->cap_match_pt, (size_t)n * nscan + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
-    if (ensure_cap(c, &c->d_selhist, &c->cap_selhist, (size_t)ICPMI_SELHIST_WORDS * nscan) != ICPMI_OK) return ICPMI_ERR_HIP;
+    if (c->d_sidx.ensure(c, cnt) != ICPMI_OK) return ICPMI_ERR_HIP;
+    if (c->d_d2.ensure(c, cnt) != ICPMI_OK) return ICPMI_ERR_HIP;
+    if (c->d_hard.ensure(c, (size_t)n * nscan + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
+    if (k == 1 && c->d_match_pt.ensure(c, (size_t)n * nscan + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
+    if (c->d_selhist.ensure(c, (size_t)ICPMI_SELHIST_WORDS * nscan) != ICPMI_OK) return ICPMI_ERR_HIP;
     return ICPMI_OK;
 }
 
@@ -1657,8 +1657,8 @@ icpmi_status loop_run(icpmi_ctx* c, const float4* d_scan, const float* d_normals
     // all allocations up front: none may happen while the stream is capturing
     if (ensure_loop_buffers(c, n, lc.k) != ICPMI_OK) return ICPMI_ERR_HIP;
     if (chain_has_vartrimmed(lc)) { VtBuffers vb; if (vt_buffers(c, n * lc.k, &vb) != ICPMI_OK) return ICPMI_ERR_HIP; }
-    if (ensure_cap(c, &c->d_reading, &c->cap_reading, (size_t)n + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
-    if (d_normals3 && ensure_cap(c, &c->d_read_normals, &c->cap_read_normals, (size_t)n + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
+    if (c->d_reading.ensure(c, (size_t)n + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
+    if (d_normals3 && c->d_read_normals.ensure(c, (size_t)n + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
     if (c->cfg.knn <= 8 && sort_queries_reserve(c, n) != ICPMI_OK) return ICPMI_ERR_HIP;
 
     const bool profile = c->cfg.profile != 0;
@@ -1912,7 +1912,7 @@ icpmi_status loop_run_batch(icpmi_ctx* c, int B, const float* const* d_scans4, c
     for (int b = 0; b < B; ++b) { ba.n[b] = (int)nn[b]; src.p[b] = (const float4*)d_scans4[b]; }
     // all allocations up front: none may happen while the stream is capturing
     if (ensure_loop_buffers(c, NS, lc.k, B) != ICPMI_OK) return ICPMI_ERR_HIP;
-    if (ensure_cap(c, &c->d_reading, &c->cap_reading, (size_t)NS * B + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
+    if (c->d_reading.ensure(c, (size_t)NS * B + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
     if (sort_queries_reserve(c, NS, B) != ICPMI_OK) return ICPMI_ERR_HIP;
     struct Scope { icpmi_ctx* c; ~Scope() { c->batch_cur = 1; c->qsorted_n = -1; c->qsorted_src = nullptr; } } scope{c};
     c->batch_cur = B; c->batch_args = ba;
@@ -2011,7 +2011,7 @@ icpmi_status loop_single_step(icpmi_ctx* c, int64_t n, const LoopCfg& lc, const 
     DevBuf<double> d_sums;
     HIP_TRY(c, d_Tstep.alloc(32));
     HIP_TRY(c, d_sums.alloc(ICPMI_NV));
-    float* d_T0 = d_Tstep.p + 16;
+    float* d_T0 = d_Tstep.get() + 16;
     if (T_iter_host) HIP_TRY(c, hipMemcpyAsync(d_T0, T_iter_host, 16 * sizeof(float), hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(init_state_kernel, dim3(1), dim3(64), 0, c->stream, c->d_state, T_iter_host ? (const float*)d_T0 : (const float*)nullptr, 0u,
                        (unsigned*)nullptr);
@@ -2066,7 +2066,7 @@ icpmi_status loop_outlier_weights(icpmi_ctx* c, const LoopCfg& lc, const float* 
         d_ref_n4 = scratch_get<float4>(c, 8, (size_t)c->m_raw + 1);
         d_rn3 = scratch_get<float>(c, 9, (size_t)3 * n + 3);
         if (!d_ref_n4 || !d_rn3) return ICPMI_ERR_HIP;
-        if (ensure_cap(c, &c->d_read_normals, &c->cap_read_normals, (size_t)n + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
+        if (c->d_read_normals.ensure(c, (size_t)n + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
         HIP_TRY(c, hipMemcpyAsync(d_rn3, read_normals3, (size_t)3 * n * sizeof(float), hipMemcpyHostToDevice, c->stream));
         hipLaunchKernelGGL(pad_normals_kernel, dim3((int)((n + 255) / 256)), dim3(256), 0, c->stream, (const float*)d_rn3, n, c->d_read_normals);
         hipLaunchKernelGGL(pad_normals_kernel, dim3((int)((c->m_raw + 255) / 256)), dim3(256), 0, c->stream, (const float*)c->d_raw_n3, c->m_raw, d_ref_n4);

@@ -632,10 +632,10 @@ icpmi_status sort_queries_reserve(icpmi_ctx* c, int64_t n, int nscan)
     int tx, ty, passes, nwg; size_t tab;
     sort_dims(c, n, tx, ty, passes, nwg, tab);
     const size_t tot = (size_t)n * nscan;
-    if (ensure_cap(c, &c->d_qsorted, &c->cap_qsorted, tot + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
-    if (ensure_cap(c, &c->d_qindex, &c->cap_qindex, tot + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
-    if (ensure_cap(c, &c->d_qkeys, &c->cap_qkeys, (size_t)4 * tot + 4) != ICPMI_OK) return ICPMI_ERR_HIP; // keys / values, ping-pong
-    if (ensure_cap(c, &c->d_qtile, &c->cap_qtile, tab * passes * nscan) != ICPMI_OK) return ICPMI_ERR_HIP;
+    if (c->d_qsorted.ensure(c, tot + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
+    if (c->d_qindex.ensure(c, tot + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
+    if (c->d_qkeys.ensure(c, (size_t)4 * tot + 4) != ICPMI_OK) return ICPMI_ERR_HIP; // keys / values, ping-pong
+    if (c->d_qtile.ensure(c, tab * passes * nscan) != ICPMI_OK) return ICPMI_ERR_HIP;
     return ICPMI_OK;
 }
 
@@ -704,7 +704,7 @@ icpmi_status device_exclusive_scan(icpmi_ctx* c, unsigned* data, int n, unsigned
 icpmi_status device_exclusive_scan_cursor(icpmi_ctx* c, unsigned* counts, unsigned* starts, int n, unsigned total, bool zero_counts, unsigned* tail_out)
 {
     const int nb = (n + SCAN_CHUNK - 1) / SCAN_CHUNK;
-    if (ensure_cap(c, &c->d_blocksums, &c->cap_blocksums, (size_t)nb + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
+    if (c->d_blocksums.ensure(c, (size_t)nb + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
     if (nb <= SCAN2_MAX_NB) { // (the two-kernel scan, r5; tables beyond SCAN2_MAX_NB chunks take the three-kernel one)
         hipLaunchKernelGGL(scan2_sums_kernel, dim3(nb > 0 ? nb : 1), dim3(SCAN_T), 0, c->stream, (const unsigned*)counts, n, c->d_blocksums);
         hipLaunchKernelGGL(scan2_final_kernel, dim3(nb > 0 ? nb : 1), dim3(SCAN_T), 0, c->stream, (const unsigned*)counts, starts, n, (const unsigned*)c->d_blocksums, total, 1,
@@ -745,10 +745,10 @@ static icpmi_status device_scan_counts_to_cursors(icpmi_ctx* c, unsigned* counts
 // the handle's count table (c->d_fill), `words` zero words: cleared only when a previous user left it dirty or it was reallocated
 static icpmi_status counts_begin(icpmi_ctx* c, size_t words)
 {
-    const size_t cap_before = c->cap_fill;
-    if (ensure_cap(c, &c->d_fill, &c->cap_fill, words) != ICPMI_OK) return ICPMI_ERR_HIP;
-    if (c->cap_fill != cap_before) c->fill_clean = false; // a fresh allocation (the allocator may hand back the same address)
-    if (!c->fill_clean) HIP_TRY(c, hipMemsetAsync(c->d_fill, 0, c->cap_fill * sizeof(unsigned), c->stream));
+    bool fresh = false;
+    if (c->d_fill.ensure(c, words, &fresh) != ICPMI_OK) return ICPMI_ERR_HIP;
+    if (fresh) c->fill_clean = false; // a fresh allocation (the allocator may hand back the same address)
+    if (!c->fill_clean) HIP_TRY(c, hipMemsetAsync(c->d_fill, 0, c->d_fill.capacity() * sizeof(unsigned), c->stream));
     c->fill_clean = false; // (about to be counted into; device_scan_counts_to_cursors hands it back clean)
     return ICPMI_OK;
 }
@@ -761,7 +761,7 @@ icpmi_status device_scan_flags_count(icpmi_ctx* c, const unsigned* flag, unsigne
     if (n <= 0) return ICPMI_OK;
     const int nb = (n + SCAN_CHUNK - 1) / SCAN_CHUNK;
     if (nb <= SCAN2_MAX_NB) {
-        if (ensure_cap(c, &c->d_blocksums, &c->cap_blocksums, (size_t)nb + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
+        if (c->d_blocksums.ensure(c, (size_t)nb + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
         unsigned* d_word = c->d_progress + ICPMI_PROGRESS_SCAN_WORD;
         // r5: the count arrives TAGGED (words 40 / 41 as one 64-bit slot: call number << 32 | count, system-scope release) and the host spins on
         // the tag instead of draining the stream: a drained stream costs the completion signal and the restart of an empty queue (~20 us,
@@ -797,7 +797,7 @@ icpmi_status device_exclusive_scan_sum(icpmi_ctx* c, const unsigned* flag, unsig
 {
     const int nb = (n + SCAN_CHUNK - 1) / SCAN_CHUNK;
     if (n > 0 && nb <= SCAN2_MAX_NB) {
-        if (ensure_cap(c, &c->d_blocksums, &c->cap_blocksums, (size_t)nb + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
+        if (c->d_blocksums.ensure(c, (size_t)nb + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
         hipLaunchKernelGGL(scan2_sums_kernel, dim3(nb), dim3(SCAN_T), 0, c->stream, flag, n, c->d_blocksums);
         hipLaunchKernelGGL(scan2_final_kernel, dim3(nb), dim3(SCAN_T), 0, c->stream, flag, pos, n, (const unsigned*)c->d_blocksums, 0u, 0, (unsigned*)nullptr, d_sum);
         HIP_TRY(c, hipGetLastError());
@@ -813,7 +813,7 @@ icpmi_status device_exclusive_scan_sum(icpmi_ctx* c, const unsigned* flag, unsig
 icpmi_status device_exclusive_scan_io(icpmi_ctx* c, const unsigned* in, unsigned* data, int n, unsigned total)
 {
     const int nb = (n + SCAN_CHUNK - 1) / SCAN_CHUNK;
-    if (ensure_cap(c, &c->d_blocksums, &c->cap_blocksums, (size_t)nb + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
+    if (c->d_blocksums.ensure(c, (size_t)nb + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
     if (nb <= SCAN2_MAX_NB) {
         hipLaunchKernelGGL(scan2_sums_kernel, dim3(nb > 0 ? nb : 1), dim3(SCAN_T), 0, c->stream, in, n, c->d_blocksums);
         hipLaunchKernelGGL(scan2_final_kernel, dim3(nb > 0 ? nb : 1), dim3(SCAN_T), 0, c->stream, in, data, n, (const unsigned*)c->d_blocksums, total, 0, (unsigned*)nullptr);
@@ -832,7 +832,7 @@ icpmi_status device_exclusive_scan_io(icpmi_ctx* c, const unsigned* in, unsigned
 // at the NEXT build (whose bounding-box read-back has synchronised the stream by then)
 static icpmi_status grid_count(icpmi_ctx* c, const float4* d_pts, int64_t m, const GridParams& g, unsigned* h_nocc)
 {
-    if (ensure_cap(c, &c->d_cell_start, &c->cap_cells, (size_t)g.ncells + 2) != ICPMI_OK) return ICPMI_ERR_HIP;
+    if (c->d_cell_start.ensure(c, (size_t)g.ncells + 2) != ICPMI_OK) return ICPMI_ERR_HIP;
     // r5: the counts go to the handle's self-cleaning count table (c->d_fill), the starts are written in full by the scan: no memset of either
     if (counts_begin(c, (size_t)g.ncells + 2) != ICPMI_OK) return ICPMI_ERR_HIP;
     unsigned* d_nocc = c->d_fill + g.ncells + 1; // spare word behind the counts (cleared with them)
@@ -879,7 +879,7 @@ icpmi_status upload_level_table(icpmi_ctx* c)
         t[10] = (uint32_t)pp; t[11] = (uint32_t)(pp >> 32);
         t[12] = (uint32_t)pc; t[13] = (uint32_t)(pc >> 32); t[14] = (uint32_t)p0; t[15] = (uint32_t)(p0 >> 32);
     }
-    if (!c->d_lvl_tab) HIP_TRY(c, dev_malloc((void**)&c->d_lvl_tab, sizeof tab));
+    if (!c->d_lvl_tab) HIP_TRY(c, c->d_lvl_tab.alloc(ICPMI_MAXLEV * 4));
     return upload_small(c, c->d_lvl_tab, tab, sizeof tab);
 }
 
@@ -899,7 +899,7 @@ static icpmi_status map_insert(icpmi_ctx* c, const float4* d_pts, int64_t m0, in
     if (c->keep_raw && (d_pts != c->d_raw || (d_normals3 && d_normals3 != c->d_raw_n3))) return ICPMI_OK; // (an owner's index is built from its resident copy)
     // ---- the delta's sum and bounding box (one read-back, like the full build's)
     const int rblocks = (int)std::min<int64_t>((n + RB - 1) / RB, 256);
-    if (ensure_cap(c, &c->d_red, &c->cap_red, (size_t)rblocks * 9) != ICPMI_OK) return ICPMI_ERR_HIP;
+    if (c->d_red.ensure(c, (size_t)rblocks * 9) != ICPMI_OK) return ICPMI_ERR_HIP;
     hipLaunchKernelGGL(stats_kernel, dim3(rblocks), dim3(RB), 0, c->stream, d_pts + m0, n, c->d_red);
     HIP_TRY(c, hipGetLastError());
     std::vector<double> part((size_t)rblocks * 9);
@@ -931,22 +931,22 @@ static icpmi_status map_insert(icpmi_ctx* c, const float4* d_pts, int64_t m0, in
     // ---- buffers (all allocations before anything is written)
     const bool with_n = d_normals3 != nullptr;
     const bool with_pn = with_n && c->d_map_pn != nullptr && !c->single_level && c->keep_raw;
-    if (ensure_cap(c, &c->d_ins_key, &c->cap_ins_key, (size_t)n + 1) != ICPMI_OK || ensure_cap(c, &c->d_ins_rank, &c->cap_ins_rank, (size_t)n + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
+    if (c->d_ins_key.ensure(c, (size_t)n + 1) != ICPMI_OK || c->d_ins_rank.ensure(c, (size_t)n + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
     const bool twin = !c->no_centre; // (centroid 0: the sorted points ARE the raw points)
     if (twin && !c->d_raw0) return ICPMI_OK;
-    if (ensure_cap(c, &c->d_inv, &c->cap_inv, (size_t)n + 1) != ICPMI_OK) return ICPMI_ERR_HIP; // level-0 position of every delta point
-    if (ensure_cap(c, &c->d_fill, &c->cap_fill, (size_t)L.g[0].ncells + 2) != ICPMI_OK) return ICPMI_ERR_HIP;
+    if (c->d_inv.ensure(c, (size_t)n + 1) != ICPMI_OK) return ICPMI_ERR_HIP; // level-0 position of every delta point
+    if (c->d_fill.ensure(c, (size_t)L.g[0].ncells + 2) != ICPMI_OK) return ICPMI_ERR_HIP;
     c->fill_clean = false; // (used below as the delta's cell starts of the coarser levels: a full build clears it first)
-    if (ensure_cap(c, &c->d_ins_dstart0, &c->cap_ins_dstart0, (size_t)L.g[0].ncells + 2) != ICPMI_OK) return ICPMI_ERR_HIP;
-    if (twin && ensure_cap(c, &c->d_alt_raw0, &c->cap_alt_raw0, (size_t)m1 + 16) != ICPMI_OK) return ICPMI_ERR_HIP;
+    if (c->d_ins_dstart0.ensure(c, (size_t)L.g[0].ncells + 2) != ICPMI_OK) return ICPMI_ERR_HIP;
+    if (twin && c->d_alt_raw0.ensure(c, (size_t)m1 + 16) != ICPMI_OK) return ICPMI_ERR_HIP;
     for (int l = 0; l < L.nlev; ++l) {
-        if (ensure_cap(c, &c->d_alt_pts[l], &c->cap_alt_pts[l], (size_t)m1 + 16) != ICPMI_OK) return ICPMI_ERR_HIP;
-        if (ensure_cap(c, &c->d_alt_key[l], &c->cap_alt_key[l], (size_t)m1 + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
-        if (ensure_cap(c, &c->d_alt_cs[l], &c->cap_alt_cs[l], (size_t)L.g[l].ncells + 2) != ICPMI_OK) return ICPMI_ERR_HIP;
-        if (l > 0 && ensure_cap(c, &c->d_alt_pos0[l], &c->cap_alt_pos0[l], (size_t)m1 + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
+        if (c->d_alt_pts[l].ensure(c, (size_t)m1 + 16) != ICPMI_OK) return ICPMI_ERR_HIP;
+        if (c->d_alt_key[l].ensure(c, (size_t)m1 + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
+        if (c->d_alt_cs[l].ensure(c, (size_t)L.g[l].ncells + 2) != ICPMI_OK) return ICPMI_ERR_HIP;
+        if (l > 0 && c->d_alt_pos0[l].ensure(c, (size_t)m1 + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
     }
-    if (with_n && ensure_cap(c, &c->d_alt_nsorted, &c->cap_alt_nsorted, (size_t)m1 + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
-    if (with_pn && ensure_cap(c, &c->d_alt_pn, &c->cap_alt_pn, 2 * (size_t)m1 + 2) != ICPMI_OK) return ICPMI_ERR_HIP;
+    if (with_n && c->d_alt_nsorted.ensure(c, (size_t)m1 + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
+    if (with_pn && c->d_alt_pn.ensure(c, 2 * (size_t)m1 + 2) != ICPMI_OK) return ICPMI_ERR_HIP;
     // ---- per level: delta keys + counts -> prefix -> move the old points, place the delta, new cell starts
     const int gb0 = (int)((m0 + 255) / 256), gbn = (int)((n + 255) / 256);
     for (int l = 0; l < L.nlev; ++l) {
@@ -999,17 +999,13 @@ static icpmi_status map_insert(icpmi_ctx* c, const float4* d_pts, int64_t m0, in
         }
     }
     // ---- the written set becomes the index
-    std::swap(c->d_map_sorted, c->d_alt_pts[0]); std::swap(c->cap_map, c->cap_alt_pts[0]);
-    std::swap(c->d_cell_start, c->d_alt_cs[0]); std::swap(c->cap_cells, c->cap_alt_cs[0]);
-    for (int l = 0; l < L.nlev; ++l) { std::swap(c->d_lvl_key[l], c->d_alt_key[l]); std::swap(c->cap_lvl_key[l], c->cap_alt_key[l]); }
-    for (int l = 1; l < L.nlev; ++l) {
-        std::swap(c->d_lvl_pts[l], c->d_alt_pts[l]); std::swap(c->cap_lvl_pts[l], c->cap_alt_pts[l]);
-        std::swap(c->d_lvl_cs[l], c->d_alt_cs[l]); std::swap(c->cap_lvl_cs[l], c->cap_alt_cs[l]);
-        std::swap(c->d_lvl_pos0[l], c->d_alt_pos0[l]); std::swap(c->cap_lvl_pos0[l], c->cap_alt_pos0[l]);
-    }
-    if (twin) { std::swap(c->d_raw0, c->d_alt_raw0); std::swap(c->cap_raw0, c->cap_alt_raw0); }
-    if (with_n) { std::swap(c->d_normals_sorted, c->d_alt_nsorted); std::swap(c->cap_normals, c->cap_alt_nsorted); }
-    if (with_pn) { std::swap(c->d_map_pn, c->d_alt_pn); std::swap(c->cap_map_pn, c->cap_alt_pn); }
+    swap(c->d_map_sorted, c->d_alt_pts[0]);
+    swap(c->d_cell_start, c->d_alt_cs[0]);
+    for (int l = 0; l < L.nlev; ++l) swap(c->d_lvl_key[l], c->d_alt_key[l]);
+    for (int l = 1; l < L.nlev; ++l) { swap(c->d_lvl_pts[l], c->d_alt_pts[l]); swap(c->d_lvl_cs[l], c->d_alt_cs[l]); swap(c->d_lvl_pos0[l], c->d_alt_pos0[l]); }
+    if (twin) swap(c->d_raw0, c->d_alt_raw0);
+    if (with_n) swap(c->d_normals_sorted, c->d_alt_nsorted);
+    if (with_pn) swap(c->d_map_pn, c->d_alt_pn);
     for (int l = 0; l < L.nlev; ++l) {
         L.g[l] = gnew[l];
         L.pts[l] = l == 0 ? c->d_map_sorted : c->d_lvl_pts[l];
@@ -1075,7 +1071,7 @@ icpmi_status map_build(icpmi_ctx* c, const float4* d_pts, int64_t m, const float
     ++c->full_count;
     // ---- stats ----
     const int rblocks = (int)std::min<int64_t>((m + RB - 1) / RB, 1024);
-    if (ensure_cap(c, &c->d_red, &c->cap_red, (size_t)rblocks * 9) != ICPMI_OK) return ICPMI_ERR_HIP;
+    if (c->d_red.ensure(c, (size_t)rblocks * 9) != ICPMI_OK) return ICPMI_ERR_HIP;
     hipLaunchKernelGGL(stats_kernel, dim3(rblocks), dim3(RB), 0, c->stream, d_pts, m, c->d_red);
     HIP_TRY(c, hipGetLastError());
     std::vector<double> part((size_t)rblocks * 9);
@@ -1105,7 +1101,7 @@ icpmi_status map_build(icpmi_ctx* c, const float4* d_pts, int64_t m, const float
         maxabs = fmaxf(maxabs, fmaxf(fabsf(clo[r]), fabsf(chi[r])));
     }
 
-    if (ensure_cap(c, &c->d_keys, &c->cap_keys, (size_t)m) != ICPMI_OK) return ICPMI_ERR_HIP;
+    if (c->d_keys.ensure(c, (size_t)m) != ICPMI_OK) return ICPMI_ERR_HIP;
 
     // ---- choose the cell edge ----
     const double ext[3] = {(double)chi[0] - clo[0], (double)chi[1] - clo[1], (double)chi[2] - clo[2]};
@@ -1170,18 +1166,18 @@ grid_chosen:
     c->nocc_by_scan = false;
 
     // ---- scatter ----
-    if (ensure_cap(c, &c->d_map_sorted, &c->cap_map, (size_t)m + 16) != ICPMI_OK) return ICPMI_ERR_HIP;
-    if (d_normals3 && ensure_cap(c, &c->d_normals_sorted, &c->cap_normals, (size_t)m) != ICPMI_OK) return ICPMI_ERR_HIP;
+    if (c->d_map_sorted.ensure(c, (size_t)m + 16) != ICPMI_OK) return ICPMI_ERR_HIP;
+    if (d_normals3 && c->d_normals_sorted.ensure(c, (size_t)m) != ICPMI_OK) return ICPMI_ERR_HIP;
     c->has_normals = d_normals3 != nullptr;
     // resident raw copy (skipped when the caller IS the raw copy: the device-side map update)
     if (d_pts != c->d_raw && c->keep_raw) {
         ++c->raw_epoch; // the resident copy is replaced, not appended to: a private raw-frame index starts over
         c->raw_has_scalar = false; // a map handed in from outside: its scalar channel comes through icpmi_set_map_scalar
-        if (ensure_cap(c, &c->d_raw, &c->cap_raw, (size_t)m) != ICPMI_OK) return ICPMI_ERR_HIP;
+        if (c->d_raw.ensure(c, (size_t)m) != ICPMI_OK) return ICPMI_ERR_HIP;
         HIP_TRY(c, hipMemcpyAsync(c->d_raw, d_pts, (size_t)m * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
     }
     if (d_normals3 && d_normals3 != c->d_raw_n3 && c->keep_raw) {
-        if (ensure_cap(c, &c->d_raw_n3, &c->cap_raw_n3, (size_t)m * 3) != ICPMI_OK) return ICPMI_ERR_HIP;
+        if (c->d_raw_n3.ensure(c, (size_t)m * 3) != ICPMI_OK) return ICPMI_ERR_HIP;
         HIP_TRY(c, hipMemcpyAsync(c->d_raw_n3, d_normals3, (size_t)m * 3 * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
     }
     c->m_raw = c->keep_raw ? m : 0; c->raw_has_normals = c->keep_raw && d_normals3 != nullptr;
@@ -1191,8 +1187,8 @@ grid_chosen:
     const bool want_ins = (c->keep_raw || c->is_raw_index) && !c->single_level && !(c->cfg.grid_cell > 0.f);
     const bool want_twin = want_ins && !c->no_centre;
     if (want_ins) {
-        if (ensure_cap(c, &c->d_lvl_key[0], &c->cap_lvl_key[0], (size_t)m + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
-        if (want_twin && ensure_cap(c, &c->d_raw0, &c->cap_raw0, (size_t)m + 16) != ICPMI_OK) return ICPMI_ERR_HIP;
+        if (c->d_lvl_key[0].ensure(c, (size_t)m + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
+        if (want_twin && c->d_raw0.ensure(c, (size_t)m + 16) != ICPMI_OK) return ICPMI_ERR_HIP;
     }
     c->ins_ready = false;
     hipLaunchKernelGGL(scatter_kernel, dim3(blocks), dim3(256), 0, c->stream, d_pts, d_normals3, m, c->mean[0], c->mean[1], c->mean[2],
@@ -1200,7 +1196,7 @@ grid_chosen:
                        want_ins ? c->d_lvl_key[0] : (unsigned*)nullptr, want_twin ? c->d_raw0 : (float4*)nullptr);
     HIP_TRY(c, hipGetLastError());
     if (d_normals3 && !c->single_level && c->keep_raw) { // (the handles of the map-side operators never run pair sums)
-        if (ensure_cap(c, &c->d_map_pn, &c->cap_map_pn, 2 * (size_t)m + 2) != ICPMI_OK) return ICPMI_ERR_HIP;
+        if (c->d_map_pn.ensure(c, 2 * (size_t)m + 2) != ICPMI_OK) return ICPMI_ERR_HIP;
         hipLaunchKernelGGL(pn_kernel, dim3(blocks), dim3(256), 0, c->stream, (const float4*)c->d_map_sorted, (const float4*)c->d_normals_sorted, m, c->d_map_pn);
         HIP_TRY(c, hipGetLastError());
     }
@@ -1216,13 +1212,13 @@ grid_chosen:
         const bool tiny = prev.nx <= 2 && prev.ny <= 2 && prev.nz <= 2;
         if (reaches || tiny) break;
         GridParams gl = make_grid(clo, chi, prev.cell * 2.0f, maxabs);
-        if (ensure_cap(c, &c->d_lvl_cs[l], &c->cap_lvl_cs[l], (size_t)gl.ncells + 2) != ICPMI_OK) return ICPMI_ERR_HIP;
-        if (ensure_cap(c, &c->d_lvl_pts[l], &c->cap_lvl_pts[l], (size_t)m + 16) != ICPMI_OK) return ICPMI_ERR_HIP;
-        if (ensure_cap(c, &c->d_lvl_pos0[l], &c->cap_lvl_pos0[l], (size_t)m) != ICPMI_OK) return ICPMI_ERR_HIP;
+        if (c->d_lvl_cs[l].ensure(c, (size_t)gl.ncells + 2) != ICPMI_OK) return ICPMI_ERR_HIP;
+        if (c->d_lvl_pts[l].ensure(c, (size_t)m + 16) != ICPMI_OK) return ICPMI_ERR_HIP;
+        if (c->d_lvl_pos0[l].ensure(c, (size_t)m) != ICPMI_OK) return ICPMI_ERR_HIP;
         if (counts_begin(c, (size_t)gl.ncells + 2) != ICPMI_OK) return ICPMI_ERR_HIP; // (the scan of the level below left the table zero)
         hipLaunchKernelGGL(lvl_key_kernel, dim3(blocks), dim3(256), 0, c->stream, c->d_map_sorted, m, gl, c->d_keys, c->d_fill);
         if (device_scan_counts_to_cursors(c, c->d_fill, c->d_lvl_cs[l], gl.ncells, (unsigned)m) != ICPMI_OK) return ICPMI_ERR_HIP;
-        if (want_ins && ensure_cap(c, &c->d_lvl_key[l], &c->cap_lvl_key[l], (size_t)m + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
+        if (want_ins && c->d_lvl_key[l].ensure(c, (size_t)m + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
         hipLaunchKernelGGL(lvl_scatter_kernel, dim3(blocks), dim3(256), 0, c->stream, c->d_map_sorted, m, c->d_keys, c->d_lvl_cs[l] + 1,
                            c->d_lvl_pts[l], c->d_lvl_pos0[l], want_ins ? c->d_lvl_key[l] : (unsigned*)nullptr);
         HIP_TRY(c, hipGetLastError());

@@ -385,7 +385,7 @@ icpmi_status ops_octree_sample(icpmi_ctx* c, const float* in4, int64_t n, float 
     if (leaf_of_out) HIP_TRY(c, d_leaf.alloc((size_t)n));
     HIP_TRY(c, hipMemcpyAsync(d_in, in4, (size_t)n * sizeof(float4), hipMemcpyHostToDevice, c->stream));
     int64_t m = 0;
-    icpmi_status s = octree_sample_dev(c, d_in, n, max_size, max_pts, method, d_order, leaf_of_out ? d_leaf.p : nullptr, &m);
+    icpmi_status s = octree_sample_dev(c, d_in, n, max_size, max_pts, method, d_order, leaf_of_out ? d_leaf.get() : nullptr, &m);
     if (s != ICPMI_OK) return s;
     if (order_out) HIP_TRY(c, hipMemcpyAsync(order_out, d_order, (size_t)m * sizeof(int), hipMemcpyDeviceToHost, c->stream));
     if (leaf_of_out) HIP_TRY(c, hipMemcpyAsync(leaf_of_out, d_leaf, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, c->stream));

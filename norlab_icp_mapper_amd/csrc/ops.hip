@@ -793,8 +793,8 @@ static icpmi_status temp_knn(icpmi_ctx* c, TempCtx& t, const float* cloud4, int6
     if (self) {
         if (m <= 0 || !cloud4) { c->last_error = "set_map: empty cloud"; return ICPMI_ERR_INVALID_ARG; }
         const size_t cnt = (size_t)m * k + 1;
-        if (ensure_cap(tc, &tc->d_stage_in, &tc->cap_stage_in, (size_t)m + 1) != ICPMI_OK || ensure_cap(tc, &tc->d_sidx, &tc->cap_sidx, cnt) != ICPMI_OK ||
-            ensure_cap(tc, &tc->d_d2, &tc->cap_d2, cnt) != ICPMI_OK) { c->last_error = tc->last_error; return ICPMI_ERR_HIP; }
+        if (tc->d_stage_in.ensure(tc, (size_t)m + 1) != ICPMI_OK || tc->d_sidx.ensure(tc, cnt) != ICPMI_OK ||
+            tc->d_d2.ensure(tc, cnt) != ICPMI_OK) { c->last_error = tc->last_error; return ICPMI_ERR_HIP; }
         HIP_TRY(c, hipMemcpyAsync(tc->d_stage_in, cloud4, (size_t)m * sizeof(float4), hipMemcpyHostToDevice, tc->stream));
         const icpmi_status gs = selfgrid_knn(tc, tc->d_stage_in, m, k, tc->d_sidx, tc->d_d2);
         if (gs != ICPMI_OK) c->last_error = tc->last_error;
@@ -808,7 +808,7 @@ static icpmi_status temp_knn(icpmi_ctx* c, TempCtx& t, const float* cloud4, int6
     // (the cloud itself is already there: icpmi_set_map staged it in d_stage_in -- no second upload, and no re-sizing
     // of that buffer, which would drop it)
     if (!queries_are_cloud) {
-        if (ensure_cap(tc, &tc->d_stage_in, &tc->cap_stage_in, (size_t)n + 1) != ICPMI_OK) { c->last_error = tc->last_error; return ICPMI_ERR_HIP; }
+        if (tc->d_stage_in.ensure(tc, (size_t)n + 1) != ICPMI_OK) { c->last_error = tc->last_error; return ICPMI_ERR_HIP; }
         HIP_TRY(c, hipMemcpyAsync(tc->d_stage_in, q4, (size_t)n * sizeof(float4), hipMemcpyHostToDevice, tc->stream));
     }
     s = loop_prepare_reading(tc, tc->d_stage_in, n, nullptr);
@@ -816,8 +816,8 @@ static icpmi_status temp_knn(icpmi_ctx* c, TempCtx& t, const float* cloud4, int6
     LoopCfg lc = make_loop_cfg(tc, 1);
     lc.k = k; lc.max_dist = INFINITY; lc.maxr2 = INFINITY; lc.ring_max = 6; lc.inv1e = 1.f; lc.err2 = 1.f; // (a filter's search: exact whatever the matcher's epsilon)
     const size_t cnt = (size_t)n * k + 1;
-    if (ensure_cap(tc, &tc->d_sidx, &tc->cap_sidx, cnt) != ICPMI_OK || ensure_cap(tc, &tc->d_d2, &tc->cap_d2, cnt) != ICPMI_OK ||
-        ensure_cap(tc, &tc->d_hard, &tc->cap_hard, (size_t)n + 1) != ICPMI_OK) { c->last_error = tc->last_error; return ICPMI_ERR_HIP; }
+    if (tc->d_sidx.ensure(tc, cnt) != ICPMI_OK || tc->d_d2.ensure(tc, cnt) != ICPMI_OK ||
+        tc->d_hard.ensure(tc, (size_t)n + 1) != ICPMI_OK) { c->last_error = tc->last_error; return ICPMI_ERR_HIP; }
     HIP_TRY(c, hipMemsetAsync(tc->d_state, 0, sizeof(IcpState), tc->stream));
     tc->nn_hist0 = nullptr; tc->nn_iter_hint = 0; tc->nn_match_pt = nullptr;
     s = nn_launch_k(tc, tc->d_reading, n, nullptr, lc, allow_self, tc->d_sidx, tc->d_d2, tc->d_state);
@@ -844,8 +844,8 @@ icpmi_status ops_surface_normals(icpmi_ctx* c, const float* pts4, int64_t m, int
     if (mean_dist) HIP_TRY(c, d_md.alloc((size_t)m));
     if (eig_values) HIP_TRY(c, d_ev.alloc((size_t)m * 3));
     if (eig_vectors) HIP_TRY(c, d_evec.alloc((size_t)m * 9));
-    launch_normals(tc->stream, tc->d_map_sorted, tc->d_sidx, m, knn, d_n, densities ? d_dens.p : (float*)nullptr, c->cfg.is_2d,
-                   mean_dist ? d_md.p : (float*)nullptr, eig_values ? d_ev.p : (float*)nullptr, eig_vectors ? d_evec.p : (float*)nullptr);
+    launch_normals(tc->stream, tc->d_map_sorted, tc->d_sidx, m, knn, d_n, densities ? d_dens.get() : (float*)nullptr, c->cfg.is_2d,
+                   mean_dist ? d_md.get() : (float*)nullptr, eig_values ? d_ev.get() : (float*)nullptr, eig_vectors ? d_evec.get() : (float*)nullptr);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess && eig_values) e = hipMemcpyAsync(eig_values, d_ev, (size_t)m * 3 * sizeof(float), hipMemcpyDeviceToHost, tc->stream);
     if (e == hipSuccess && eig_vectors) e = hipMemcpyAsync(eig_vectors, d_evec, (size_t)m * 9 * sizeof(float), hipMemcpyDeviceToHost, tc->stream);
@@ -914,7 +914,7 @@ icpmi_status ops_filter_points(icpmi_ctx* c, const float* in4, int64_t n, const 
     FilterPack fp;
     fp.n = n_filters;
     for (int k = 0; k < n_filters; ++k) fp.f[k] = filters[k];
-    if (ensure_cap(c, &c->d_stage_in, &c->cap_stage_in, (size_t)n + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
+    if (c->d_stage_in.ensure(c, (size_t)n + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
     uint8_t* d_keep = scratch_get<uint8_t>(c, 9, (size_t)n);
     if (!d_keep) return ICPMI_ERR_HIP;
     HIP_TRY(c, hipMemcpyAsync(c->d_stage_in, in4, (size_t)n * sizeof(float4), hipMemcpyHostToDevice, c->stream));
@@ -1024,13 +1024,13 @@ static icpmi_status surface_normals_dev(icpmi_ctx* c, const float4* d_pts, int64
     if (tc->stream != c->stream) HIP_TRY(c, hipStreamSynchronize(c->stream)); // d_pts was produced on the caller's stream
     // r6: the sparse block grid (selfgrid.hip) -- index and search in one call
     const size_t cnt = (size_t)m * knn + 1;
-    if (ensure_cap(tc, &tc->d_sidx, &tc->cap_sidx, cnt) != ICPMI_OK || ensure_cap(tc, &tc->d_d2, &tc->cap_d2, cnt) != ICPMI_OK) { c->last_error = tc->last_error; return ICPMI_ERR_HIP; }
+    if (tc->d_sidx.ensure(tc, cnt) != ICPMI_OK || tc->d_d2.ensure(tc, cnt) != ICPMI_OK) { c->last_error = tc->last_error; return ICPMI_ERR_HIP; }
     const bool track = remember && d_pts == c->d_raw; // (the resident map of an append-only update: remember the k-th distances for the next append;
                                                       //  a chain program may compact or reorder the points behind its normals pass: not tracked)
     if (!track) c->dk_m = 0;
     static const bool inc_on = [] { const char* e = getenv("ICPMI_NORMALS_INCREMENTAL"); return !e || atoi(e) != 0; }(); // 0: every pass over the whole cloud (diagnostic / A-B)
     const bool incremental = inc_on && track && m_old > 0 && m_old < m && c->d_raw_dk && c->dk_m == m_old && c->dk_knn == knn && c->dk_epoch == c->raw_epoch;
-    if (track && ensure_cap_keep(c, &c->d_raw_dk, &c->cap_raw_dk, (size_t)m + 1, incremental ? (size_t)m_old : 0) != ICPMI_OK) return ICPMI_ERR_HIP;
+    if (track && c->d_raw_dk.ensure_keep(c, (size_t)m + 1, incremental ? (size_t)m_old : 0) != ICPMI_OK) return ICPMI_ERR_HIP;
     SelfGridSubset sub;
     sub.m_old = incremental ? m_old : 0; sub.d_dk = c->d_raw_dk;
     s = selfgrid_knn(tc, d_pts, m, knn, tc->d_sidx, tc->d_d2, track ? &sub : nullptr); // (tracked: the grid keeps its sorted copy for the next append)
@@ -1057,10 +1057,10 @@ icpmi_status ops_map_update_point_distance(icpmi_ctx* c, const float* scan4, int
     if (new_m) *new_m = c->m_raw;
     if (n == 0) return ICPMI_OK;
     // stage the scan (and its normals)
-    if (ensure_cap(c, &c->d_stage_in, &c->cap_stage_in, (size_t)n + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
+    if (c->d_stage_in.ensure(c, (size_t)n + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
     HIP_TRY(c, hipMemcpyAsync(c->d_stage_in, scan4, (size_t)n * sizeof(float4), hipMemcpyHostToDevice, c->stream));
     if (scan_normals3) {
-        if (ensure_cap(c, &c->d_stage_n3, &c->cap_stage_n3, (size_t)n * 3) != ICPMI_OK) return ICPMI_ERR_HIP;
+        if (c->d_stage_n3.ensure(c, (size_t)n * 3) != ICPMI_OK) return ICPMI_ERR_HIP;
         HIP_TRY(c, hipMemcpyAsync(c->d_stage_n3, scan_normals3, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
     }
     return ops_map_update_dev(c, c->d_stage_in, n, scan_normals3 ? c->d_stage_n3 : nullptr, min_dist, normals_knn, keep_out, appended, new_m);
@@ -1116,10 +1116,10 @@ icpmi_status ops_map_update_dev(icpmi_ctx* c, const float4* d_scan, int64_t n, c
         const int64_t m1 = m0 + count;
         const bool want_n = normals_knn > 0 || c->raw_has_normals || scan_normals3;
         if (m1 >= (1ll << 28)) { c->last_error = "map_update: the map would exceed 2^28-1 points"; s = ICPMI_ERR_UNSUPPORTED; }
-        if (s == ICPMI_OK) s = ensure_cap_keep(c, &c->d_raw, &c->cap_raw, (size_t)m1, (size_t)m0);
+        if (s == ICPMI_OK) s = c->d_raw.ensure_keep(c, (size_t)m1, (size_t)m0);
         if (s == ICPMI_OK && want_n) {
             const bool had = c->raw_has_normals && m0 > 0;
-            s = ensure_cap_keep(c, &c->d_raw_n3, &c->cap_raw_n3, (size_t)m1 * 3, had ? (size_t)m0 * 3 : 0);
+            s = c->d_raw_n3.ensure_keep(c, (size_t)m1 * 3, had ? (size_t)m0 * 3 : 0);
             if (s == ICPMI_OK && !had && m0 > 0) e = hipMemsetAsync(c->d_raw_n3, 0, (size_t)m0 * 3 * sizeof(float), c->stream);
         }
         if (s == ICPMI_OK && e == hipSuccess) {
@@ -1249,10 +1249,10 @@ icpmi_status chain_reserve(Chain& w, int64_t need)
 {
     icpmi_ctx* c = w.c;
     if (need >= (1ll << 28)) { c->last_error = "map_update_chain: the map would exceed 2^28-1 points"; return ICPMI_ERR_UNSUPPORTED; }
-    icpmi_status s = ensure_cap_keep(c, &c->d_raw, &c->cap_raw, (size_t)need, (size_t)w.m);
-    if (s == ICPMI_OK) s = ensure_cap_keep(c, &c->d_raw_n3, &c->cap_raw_n3, (size_t)need * 3, (size_t)w.m * 3);
-    if (s == ICPMI_OK) s = ensure_cap_keep(c, &c->d_raw_s, &c->cap_raw_s, (size_t)need, (size_t)w.m);
-    if (s == ICPMI_OK) s = ensure_cap_keep(c, &c->d_src, &c->cap_src, (size_t)need, (size_t)w.m);
+    icpmi_status s = c->d_raw.ensure_keep(c, (size_t)need, (size_t)w.m);
+    if (s == ICPMI_OK) s = c->d_raw_n3.ensure_keep(c, (size_t)need * 3, (size_t)w.m * 3);
+    if (s == ICPMI_OK) s = c->d_raw_s.ensure_keep(c, (size_t)need, (size_t)w.m);
+    if (s == ICPMI_OK) s = c->d_src.ensure_keep(c, (size_t)need, (size_t)w.m);
     return s;
 }
 
@@ -1281,16 +1281,13 @@ icpmi_status chain_compact(Chain& w, unsigned* d_flag, unsigned* d_pos)
     icpmi_status s = device_scan_flags_count(c, d_flag, d_pos, (int)m, &count);
     if (s != ICPMI_OK) return s;
     if (count == m) return ICPMI_OK; // nothing dropped
-    if (ensure_cap(c, &c->d_alt_raw, &c->cap_alt_raw, (size_t)count + 1) != ICPMI_OK || ensure_cap(c, &c->d_alt_n3, &c->cap_alt_n3, (size_t)count * 3 + 1) != ICPMI_OK ||
-        ensure_cap(c, &c->d_alt_s, &c->cap_alt_s, (size_t)count + 1) != ICPMI_OK || ensure_cap(c, &c->d_alt_src, &c->cap_alt_src, (size_t)count + 1) != ICPMI_OK)
+    if (c->d_alt_raw.ensure(c, (size_t)count + 1) != ICPMI_OK || c->d_alt_n3.ensure(c, (size_t)count * 3 + 1) != ICPMI_OK ||
+        c->d_alt_s.ensure(c, (size_t)count + 1) != ICPMI_OK || c->d_alt_src.ensure(c, (size_t)count + 1) != ICPMI_OK)
         return ICPMI_ERR_HIP;
     hipLaunchKernelGGL(chain_compact_kernel, dim3((int)((m + 255) / 256)), dim3(256), 0, c->stream, m, d_flag, d_pos, c->d_raw, c->d_raw_n3,
                        c->d_raw_s, c->d_src, c->d_alt_raw, c->d_alt_n3, c->d_alt_s, c->d_alt_src);
     HIP_TRY(c, hipGetLastError());
-    std::swap(c->d_raw, c->d_alt_raw); std::swap(c->cap_raw, c->cap_alt_raw);
-    std::swap(c->d_raw_n3, c->d_alt_n3); std::swap(c->cap_raw_n3, c->cap_alt_n3);
-    std::swap(c->d_raw_s, c->d_alt_s); std::swap(c->cap_raw_s, c->cap_alt_s);
-    std::swap(c->d_src, c->d_alt_src); std::swap(c->cap_src, c->cap_alt_src);
+    swap(c->d_raw, c->d_alt_raw); swap(c->d_raw_n3, c->d_alt_n3); swap(c->d_raw_s, c->d_alt_s); swap(c->d_src, c->d_alt_src);
     w.m = count;
     w.indexed = false;
     return ICPMI_OK;
@@ -1315,16 +1312,13 @@ __global__ __launch_bounds__(256) void chain_gather_kernel(int64_t count, const 
 icpmi_status chain_gather(Chain& w, const int* d_order, int64_t count)
 {
     icpmi_ctx* c = w.c;
-    if (ensure_cap(c, &c->d_alt_raw, &c->cap_alt_raw, (size_t)count + 1) != ICPMI_OK || ensure_cap(c, &c->d_alt_n3, &c->cap_alt_n3, (size_t)count * 3 + 1) != ICPMI_OK ||
-        ensure_cap(c, &c->d_alt_s, &c->cap_alt_s, (size_t)count + 1) != ICPMI_OK || ensure_cap(c, &c->d_alt_src, &c->cap_alt_src, (size_t)count + 1) != ICPMI_OK)
+    if (c->d_alt_raw.ensure(c, (size_t)count + 1) != ICPMI_OK || c->d_alt_n3.ensure(c, (size_t)count * 3 + 1) != ICPMI_OK ||
+        c->d_alt_s.ensure(c, (size_t)count + 1) != ICPMI_OK || c->d_alt_src.ensure(c, (size_t)count + 1) != ICPMI_OK)
         return ICPMI_ERR_HIP;
     if (count) hipLaunchKernelGGL(chain_gather_kernel, dim3((int)((count + 255) / 256)), dim3(256), 0, c->stream, count, d_order, c->d_raw, c->d_raw_n3,
                                   c->d_raw_s, c->d_src, c->d_alt_raw, c->d_alt_n3, c->d_alt_s, c->d_alt_src);
     HIP_TRY(c, hipGetLastError());
-    std::swap(c->d_raw, c->d_alt_raw); std::swap(c->cap_raw, c->cap_alt_raw);
-    std::swap(c->d_raw_n3, c->d_alt_n3); std::swap(c->cap_raw_n3, c->cap_alt_n3);
-    std::swap(c->d_raw_s, c->d_alt_s); std::swap(c->cap_raw_s, c->cap_alt_s);
-    std::swap(c->d_src, c->d_alt_src); std::swap(c->cap_src, c->cap_alt_src);
+    swap(c->d_raw, c->d_alt_raw); swap(c->d_raw_n3, c->d_alt_n3); swap(c->d_raw_s, c->d_alt_s); swap(c->d_src, c->d_alt_src);
     w.m = count;
     w.indexed = false;
     return ICPMI_OK;
@@ -1341,8 +1335,8 @@ icpmi_status chain_point_distance_flags(icpmi_ctx* c, icpmi_ctx* ic, const float
     lc.inv1e = 1.f; lc.err2 = 1.f; // (the module's predicate is exact whatever the matcher's epsilon)
     lc.k = 1; lc.n_out = 0; lc.max_dist = min_dist; lc.maxr2 = pd_radius2(lim); // a radius search with maxDist = minDist decides the same predicate
     const size_t cnt = (size_t)n + 1;
-    if (ensure_cap(ic, &ic->d_sidx, &ic->cap_sidx, cnt) != ICPMI_OK || ensure_cap(ic, &ic->d_d2, &ic->cap_d2, cnt) != ICPMI_OK ||
-        ensure_cap(ic, &ic->d_hard, &ic->cap_hard, cnt) != ICPMI_OK) { c->last_error = ic->last_error; return ICPMI_ERR_HIP; }
+    if (ic->d_sidx.ensure(ic, cnt) != ICPMI_OK || ic->d_d2.ensure(ic, cnt) != ICPMI_OK ||
+        ic->d_hard.ensure(ic, cnt) != ICPMI_OK) { c->last_error = ic->last_error; return ICPMI_ERR_HIP; }
     HIP_TRY(c, hipMemsetAsync(ic->d_state, 0, sizeof(IcpState), ic->stream));
     ic->nn_hist0 = nullptr; ic->nn_iter_hint = 0; ic->nn_match_pt = nullptr;
     s = nn_launch_k(ic, ic->d_reading, n, nullptr, lc, 0, ic->d_sidx, ic->d_d2, ic->d_state);
@@ -1422,10 +1416,10 @@ icpmi_status ops_map_update_chain(icpmi_ctx* c, const float4* d_scan, int64_t n,
     icpmi_status s = ICPMI_OK;
     {
         const bool had_n = w.has_n, had_s = m0 > 0 && c->raw_has_scalar;
-        s = ensure_cap_keep(c, &c->d_raw, &c->cap_raw, (size_t)(m0 + n + 1), (size_t)m0);
-        if (s == ICPMI_OK) s = ensure_cap_keep(c, &c->d_raw_n3, &c->cap_raw_n3, (size_t)(m0 + n + 1) * 3, had_n ? (size_t)m0 * 3 : 0);
-        if (s == ICPMI_OK) s = ensure_cap_keep(c, &c->d_raw_s, &c->cap_raw_s, (size_t)(m0 + n + 1), had_s ? (size_t)m0 : 0);
-        if (s == ICPMI_OK) s = ensure_cap(c, &c->d_src, &c->cap_src, (size_t)(m0 + n + 1));
+        s = c->d_raw.ensure_keep(c, (size_t)(m0 + n + 1), (size_t)m0);
+        if (s == ICPMI_OK) s = c->d_raw_n3.ensure_keep(c, (size_t)(m0 + n + 1) * 3, had_n ? (size_t)m0 * 3 : 0);
+        if (s == ICPMI_OK) s = c->d_raw_s.ensure_keep(c, (size_t)(m0 + n + 1), had_s ? (size_t)m0 : 0);
+        if (s == ICPMI_OK) s = c->d_src.ensure(c, (size_t)(m0 + n + 1));
         if (s != ICPMI_OK) return s;
         if (m0 > 0 && !had_n) HIP_TRY(c, hipMemsetAsync(c->d_raw_n3, 0, (size_t)m0 * 3 * sizeof(float), c->stream));
         if (m0 > 0 && !had_s) HIP_TRY(c, hipMemsetAsync(c->d_raw_s, 0, (size_t)m0 * sizeof(float), c->stream));
@@ -1485,7 +1479,7 @@ icpmi_status ops_map_update_chain(icpmi_ctx* c, const float4* d_scan, int64_t n,
                 if (ic->stream != c->stream) HIP_TRY(c, hipStreamSynchronize(c->stream));
                 int32_t acc = 0;
                 ic->cfg.max_dist = op.f[0] > 1e-3f ? op.f[0] : 1e-3f; // the levels this radius needs (see raw_index)
-                s = icpmi_set_map_dev(ic, (const float*)c->d_raw, w.m, nullptr, &acc);
+                s = icpmi_set_map_dev(ic, (const float*)c->d_raw.get(), w.m, nullptr, &acc);
                 if (s != ICPMI_OK) { c->last_error = ic->last_error; break; }
             }
             s = chain_point_distance_flags(c, ic, d_scan, n, op.f[0], d_flag);
@@ -1947,14 +1941,14 @@ static icpmi_status merge_epoch_one_collective(icpmi_ctx* c, const float correct
     const int64_t cap = c->merge_block;
     const size_t block4 = (size_t)cap + 1;
     float4* send = c->d_merge_send;
-    unsigned* d_count = reinterpret_cast<unsigned*>(c->d_comm_cnt); // (one word: the scan's sum)
+    unsigned* d_count = reinterpret_cast<unsigned*>(c->d_comm_cnt.get()); // (one word: the scan's sum)
     icpmi_status local = ICPMI_OK;
     bool fixed = true; unsigned fixed_count = 0;
     if (n > 0) {
         unsigned* d_flag = scratch_get<unsigned>(c, 6, (size_t)n + 2);
         unsigned* d_pos = scratch_get<unsigned>(c, 7, (size_t)n + 2);
         if (!d_flag || !d_pos) local = ICPMI_ERR_HIP;
-        if (local == ICPMI_OK) local = ensure_cap(c, &c->d_stage_in, &c->cap_stage_in, (size_t)n + 1);
+        if (local == ICPMI_OK) local = c->d_stage_in.ensure(c, (size_t)n + 1);
         if (local == ICPMI_OK) local = ops_transform_dev(c, correction, c->d_scan_map, n, c->d_stage_in);
         if (local == ICPMI_OK) {
             if (c->m > 0) {
@@ -2043,9 +2037,9 @@ icpmi_status ops_staged_merge_allgather(icpmi_ctx* c, const float correction[16]
     const int R = c->comm_ranks; // 1 without a communicator (or the loopback communicator's simulated ranks, comm.hip)
     const int64_t n = correction ? c->scan_map_n : 0; // no correction = nothing to contribute (empty scan / failed registration)
     // the exchange words: allocated by comm_init; a handle that is its own single rank gets them here (no peer can be left waiting)
-    if (!c->d_comm_cnt || c->cap_comm_cnt < (size_t)2 * R + 16) {
+    if (!c->d_comm_cnt || c->d_comm_cnt.capacity() < (size_t)2 * R + 16) {
         if (c->comm) { c->last_error = "staged_merge_allgather: communicator without exchange words"; return ICPMI_ERR_HIP; }
-        if (ensure_cap(c, &c->d_comm_cnt, &c->cap_comm_cnt, (size_t)2 * R + 16) != ICPMI_OK) return ICPMI_ERR_HIP;
+        if (c->d_comm_cnt.ensure(c, (size_t)2 * R + 16) != ICPMI_OK) return ICPMI_ERR_HIP;
     }
     // ---- r5: ONE collective (fixed-size blocks with a count header); the three-collective epoch below stays as the fall-back
     if (c->merge_block == 0 && !c->comm && R == 1) { const icpmi_status rs = merge_blocks_reserve(c, 1); if (rs != ICPMI_OK) return rs; } // (its own single rank: no peer to strand)
@@ -2079,8 +2073,8 @@ icpmi_status ops_staged_merge_allgather(icpmi_ctx* c, const float correction[16]
         d_flag = scratch_get<unsigned>(c, 6, (size_t)n + 2);
         d_pos = scratch_get<unsigned>(c, 7, (size_t)n + 2);
         if (!d_flag || !d_pos) local = ICPMI_ERR_HIP;
-        if (local == ICPMI_OK) local = ensure_cap(c, &c->d_stage_in, &c->cap_stage_in, (size_t)n + 1);
-        if (local == ICPMI_OK) local = ensure_cap(c, &c->d_merge_send, &c->cap_merge_send, (size_t)n + 1);
+        if (local == ICPMI_OK) local = c->d_stage_in.ensure(c, (size_t)n + 1);
+        if (local == ICPMI_OK) local = c->d_merge_send.ensure(c, (size_t)n + 1);
         if (local == ICPMI_OK) local = ops_transform_dev(c, correction, c->d_scan_map, n, c->d_stage_in);
         if (local == ICPMI_OK) {
             if (c->m > 0) {
@@ -2114,9 +2108,9 @@ icpmi_status ops_staged_merge_allgather(icpmi_ctx* c, const float correction[16]
     for (long long v : counts) { maxc = v > maxc ? v : maxc; total += v; }
     if (total == 0) { if (new_m) *new_m = c->m > 0 ? c->m_raw : 0; return ICPMI_OK; }
     // ---- buffers at the gathered sizes; `ready` exchange (collective 2, only when there are peers)
-    icpmi_status grow = ensure_cap_keep(c, &c->d_merge_send, &c->cap_merge_send, (size_t)maxc + 1, (size_t)mine);
-    if (grow == ICPMI_OK) grow = ensure_cap(c, &c->d_merge_recv, &c->cap_merge_recv, (size_t)maxc * R + 1);
-    if (grow == ICPMI_OK) grow = ensure_cap(c, &c->d_merged, &c->cap_merged, (size_t)total + 1);
+    icpmi_status grow = c->d_merge_send.ensure_keep(c, (size_t)maxc + 1, (size_t)mine);
+    if (grow == ICPMI_OK) grow = c->d_merge_recv.ensure(c, (size_t)maxc * R + 1);
+    if (grow == ICPMI_OK) grow = c->d_merged.ensure(c, (size_t)total + 1);
     const std::string grow_error = c->last_error;
     if (c->comm) {
         long long hready = grow == ICPMI_OK ? 1 : -1;
@@ -2181,7 +2175,7 @@ icpmi_status ops_staged_merged_points(icpmi_ctx* c, float* out4, int64_t capacit
 icpmi_status ops_staged_keep(icpmi_ctx* c, const float correction[16], float min_dist, uint8_t* keep_out, float* placed_out4)
 {
     const int64_t n = c->scan_map_n;
-    if (ensure_cap(c, &c->d_stage_in, &c->cap_stage_in, (size_t)n + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
+    if (c->d_stage_in.ensure(c, (size_t)n + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
     icpmi_status s = ops_transform_dev(c, correction, c->d_scan_map, n, c->d_stage_in); // Mapper.cpp:221
     if (s != ICPMI_OK) return s;
     if (placed_out4) HIP_TRY(c, hipMemcpyAsync(placed_out4, c->d_stage_in, (size_t)n * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
@@ -2208,7 +2202,7 @@ icpmi_status ops_map_scalar(icpmi_ctx* c, const float* set, float* get, int64_t 
 {
     if (c->m <= 0 || m != c->m_raw) { c->last_error = "map_scalar: size differs from the resident map"; return ICPMI_ERR_INVALID_ARG; }
     if (set) {
-        if (ensure_cap_keep(c, &c->d_raw_s, &c->cap_raw_s, (size_t)m, 0) != ICPMI_OK) return ICPMI_ERR_HIP;
+        if (c->d_raw_s.ensure_keep(c, (size_t)m, 0) != ICPMI_OK) return ICPMI_ERR_HIP;
         HIP_TRY(c, hipMemcpyAsync(c->d_raw_s, set, (size_t)m * sizeof(float), hipMemcpyHostToDevice, c->stream));
         c->raw_has_scalar = true;
     }

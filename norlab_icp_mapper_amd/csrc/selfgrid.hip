@@ -31,20 +31,21 @@
 #include <cmath>
 #include <vector>
 
+template <typename T> using SgArr = DevArr<T, GrowQuarter>; // (common.h: growth by a quarter, the stream drained before a block goes back)
 struct SelfGridCtx {
-    unsigned* d_tcnt = nullptr; size_t cap_tcnt = 0; bool tcnt_clean = false; // points per B-cell (zero between builds: the scan cleans what it read)
-    unsigned* d_tstart = nullptr; size_t cap_tstart = 0;                      // exclusive scan of d_tcnt, Morton order (+ 2 words: cursor layout while scattering)
-    unsigned* d_tbid = nullptr; size_t cap_tbid = 0;                          // B-cell -> block id (valid where the cell is occupied)
-    uint4* d_blist = nullptr; size_t cap_blist = 0;                           // block id -> {Morton index, bx, by, bz}
-    unsigned* d_f = nullptr; size_t cap_f = 0;                                // SG_F words per block
-    float4* d_coarse = nullptr; size_t cap_coarse = 0;                        // the points sorted by block (before the sort inside the blocks)
-    uint2* d_queue = nullptr; size_t cap_queue = 0;                           // {sorted position, bits of the bound on the k-th d^2} of the queries the tiled pass left
-    unsigned* d_inv = nullptr; size_t cap_inv = 0;                            // original index -> sorted position
-    float* d_part = nullptr; size_t cap_part = 0;                             // bounding-box partials
-    unsigned* d_dirty = nullptr; size_t cap_dirty = 0;                        // subset search: bitmaps of the cells appended points fell into, per level
-    float4* d_prev = nullptr; size_t cap_prev = 0; int64_t prev_m = 0; float prev_lo[3] = {0, 0, 0}, prev_hi[3] = {0, 0, 0};   // the sorted copy (and its bounding box) of the last TRACKED build (+ room for the next append): the next build of the grown cloud reads it instead of the cloud in the caller's order -- nearly sorted input, coalesced scatter
-    unsigned char* d_sel = nullptr; size_t cap_sel = 0;                       // ... selected queries by sorted position (m) and by original index (m)
-    struct SgState* d_state = nullptr;
+    SgArr<unsigned> d_tcnt; bool tcnt_clean = false; // points per B-cell (zero between builds: the scan cleans what it read)
+    SgArr<unsigned> d_tstart;   // exclusive scan of d_tcnt, Morton order (+ 2 words: cursor layout while scattering)
+    SgArr<unsigned> d_tbid;     // B-cell -> block id (valid where the cell is occupied)
+    SgArr<uint4> d_blist;       // block id -> {Morton index, bx, by, bz}
+    SgArr<unsigned> d_f;        // SG_F words per block
+    SgArr<float4> d_coarse;     // the points sorted by block (before the sort inside the blocks)
+    SgArr<uint2> d_queue;       // {sorted position, bits of the bound on the k-th d^2} of the queries the tiled pass left
+    SgArr<unsigned> d_inv;      // original index -> sorted position
+    SgArr<float> d_part;        // bounding-box partials
+    SgArr<unsigned> d_dirty;    // subset search: bitmaps of the cells appended points fell into, per level
+    SgArr<float4> d_prev; int64_t prev_m = 0; float prev_lo[3] = {0, 0, 0}, prev_hi[3] = {0, 0, 0};   // the sorted copy (and its bounding box) of the last TRACKED build (+ room for the next append): the next build of the grown cloud reads it instead of the cloud in the caller's order -- nearly sorted input, coalesced scatter
+    SgArr<unsigned char> d_sel; // ... selected queries by sorted position (m) and by original index (m)
+    SgArr<struct SgState> d_state;
     // tuning state: the edge of the previous build and what its points saw (size-biased A-cell occupancy, delivered through the mapped page)
     float cell = 0.f; int64_t m = 0; int k = 0;
     unsigned long long seq = 0;
@@ -830,18 +831,6 @@ __global__ __launch_bounds__(256) void sg_wavelist_kernel(const unsigned char* _
     }
 }
 
-template <typename T>
-icpmi_status sg_cap(icpmi_ctx* c, T** p, size_t* cap, size_t need, bool* fresh = nullptr)
-{
-    if (need <= *cap && *p) return ICPMI_OK;
-    if (*p) { HIP_TRY(c, hipStreamSynchronize(c->stream)); HIP_TRY(c, dev_free(*p)); *p = nullptr; *cap = 0; }
-    const size_t want = need + need / 4 + 64;
-    HIP_TRY(c, dev_malloc((void**)p, want * sizeof(T)));
-    *cap = want;
-    if (fresh) *fresh = true;
-    return ICPMI_OK;
-}
-
 unsigned sg_queue_cap(int64_t m) { const int64_t waves = (m + SGQ - 1) / SGQ; return (unsigned)(((waves + SG_NQ - 1) / SG_NQ) * SGQ); }
 
 void sg_launch_search(icpmi_ctx* c, SelfGridCtx* sg, const SgGrid& g, int k, int64_t m, int* d_sidx, float* d_d2, unsigned long long* sq_mapped, int diag,
@@ -865,9 +854,7 @@ void selfgrid_destroy(icpmi_ctx* c)
     SelfGridCtx* sg = c->sg;
     if (!sg) return;
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    dev_free(sg->d_tcnt); dev_free(sg->d_tstart); dev_free(sg->d_tbid); dev_free(sg->d_blist); dev_free(sg->d_f); dev_free(sg->d_coarse);
-    dev_free(sg->d_queue); dev_free(sg->d_inv); dev_free(sg->d_part); dev_free(sg->d_state); dev_free(sg->d_dirty); dev_free(sg->d_sel); dev_free(sg->d_prev);
-    delete sg;
+    delete sg; // (its arrays free themselves)
     c->sg = nullptr;
 }
 
@@ -882,21 +869,13 @@ icpmi_status selfgrid_knn(icpmi_ctx* c, const float4* d_pts, int64_t m, int k, i
     if (m > 0x7fffff00ll) { c->last_error = "self knn: cloud too large"; return ICPMI_ERR_UNSUPPORTED; }
     if (!c->sg) { c->sg = new (std::nothrow) SelfGridCtx(); if (!c->sg) { c->last_error = "out of host memory"; return ICPMI_ERR_HIP; } }
     SelfGridCtx* sg = c->sg;
-    if (!sg->d_state) HIP_TRY(c, dev_malloc((void**)&sg->d_state, sizeof(SgState)));
+    if (!sg->d_state) HIP_TRY(c, sg->d_state.alloc(1));
     // ---- r6: an appended cloud whose previous sorted copy this grid still holds is built from THAT copy + the appended tail: the points arrive
     //      nearly in the order they leave in, so the counting sort's atomics and its scatter are coalesced (10 M points: sg_key 0.47 -> , sg_scatter 0.68 -> ms)
     const float4* src = d_pts;
     int keep_w = 0;
     if (sub && sub->m_old > 0 && sub->m_old < m && sg->d_prev && sg->prev_m == sub->m_old) {
-        if ((size_t)m + 16 > sg->cap_prev) { // grow, keeping the sorted copy
-            const size_t want = (size_t)m + (size_t)m / 4 + 64;
-            float4* q = nullptr;
-            HIP_TRY(c, dev_malloc((void**)&q, want * sizeof(float4)));
-            HIP_TRY(c, hipMemcpyAsync(q, sg->d_prev, (size_t)sub->m_old * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
-            HIP_TRY(c, hipStreamSynchronize(c->stream));
-            HIP_TRY(c, dev_free(sg->d_prev));
-            sg->d_prev = q; sg->cap_prev = want;
-        }
+        if (sg->d_prev.ensure_keep(c, (size_t)m + 16, (size_t)sub->m_old) != ICPMI_OK) return ICPMI_ERR_HIP; // grow, keeping the sorted copy
         hipLaunchKernelGGL(sg_tail_kernel, dim3((int)((m - sub->m_old + 255) / 256)), dim3(256), 0, c->stream, d_pts, sub->m_old, m, sg->d_prev);
         src = sg->d_prev; keep_w = 1;
     }
@@ -906,7 +885,7 @@ icpmi_status selfgrid_knn(icpmi_ctx* c, const float4* d_pts, int64_t m, int k, i
     const int64_t bb_n = keep_w ? m - sub->m_old : m;
     const float4* bb_src = keep_w ? d_pts + sub->m_old : src;
     const int rblocks = (int)std::min<int64_t>((bb_n + SG_RB - 1) / SG_RB, 256);
-    if (sg_cap(c, &sg->d_part, &sg->cap_part, (size_t)rblocks * 6) != ICPMI_OK) return ICPMI_ERR_HIP;
+    if (sg->d_part.ensure(c, (size_t)rblocks * 6) != ICPMI_OK) return ICPMI_ERR_HIP;
     hipLaunchKernelGGL(sg_reset_kernel, dim3(1), dim3(64), 0, c->stream, sg->d_state);
     hipLaunchKernelGGL(sg_bbox_kernel, dim3(rblocks), dim3(SG_RB), 0, c->stream, bb_src, bb_n, sg->d_part, sg->d_state);
     HIP_TRY(c, hipGetLastError());
@@ -970,13 +949,13 @@ icpmi_status selfgrid_knn(icpmi_ctx* c, const float4* d_pts, int64_t m, int k, i
         g = make(cell);
         blocks_max = (unsigned)std::min<int64_t>(m, (int64_t)g.tsize);
         bool fresh = false;
-        if (sg_cap(c, &sg->d_tcnt, &sg->cap_tcnt, (size_t)g.tsize + 2, &fresh) != ICPMI_OK) return ICPMI_ERR_HIP;
-        if (fresh || !sg->tcnt_clean) HIP_TRY(c, hipMemsetAsync(sg->d_tcnt, 0, sg->cap_tcnt * sizeof(unsigned), c->stream));
+        if (sg->d_tcnt.ensure(c, (size_t)g.tsize + 2, &fresh) != ICPMI_OK) return ICPMI_ERR_HIP;
+        if (fresh || !sg->tcnt_clean) HIP_TRY(c, hipMemsetAsync(sg->d_tcnt, 0, sg->d_tcnt.capacity() * sizeof(unsigned), c->stream));
         sg->tcnt_clean = false;
-        if (sg_cap(c, &sg->d_tstart, &sg->cap_tstart, (size_t)g.tsize + 2) != ICPMI_OK || sg_cap(c, &sg->d_tbid, &sg->cap_tbid, (size_t)g.tsize + 1) != ICPMI_OK ||
-            sg_cap(c, &sg->d_blist, &sg->cap_blist, (size_t)blocks_max + 1) != ICPMI_OK || sg_cap(c, &sg->d_f, &sg->cap_f, (size_t)blocks_max * SG_F + 1) != ICPMI_OK ||
-            sg_cap(c, &sg->d_coarse, &sg->cap_coarse, (size_t)m + 16) != ICPMI_OK || sg_cap(c, &sg->d_queue, &sg->cap_queue, (size_t)sg_queue_cap(m) * SG_NQ + 1) != ICPMI_OK || sg_cap(c, &sg->d_inv, &sg->cap_inv, (size_t)m + 1) != ICPMI_OK ||
-            ensure_cap(c, &c->d_keys, &c->cap_keys, (size_t)m) != ICPMI_OK || ensure_cap(c, &c->d_map_sorted, &c->cap_map, (size_t)m + 16) != ICPMI_OK)
+        if (sg->d_tstart.ensure(c, (size_t)g.tsize + 2) != ICPMI_OK || sg->d_tbid.ensure(c, (size_t)g.tsize + 1) != ICPMI_OK ||
+            sg->d_blist.ensure(c, (size_t)blocks_max + 1) != ICPMI_OK || sg->d_f.ensure(c, (size_t)blocks_max * SG_F + 1) != ICPMI_OK ||
+            sg->d_coarse.ensure(c, (size_t)m + 16) != ICPMI_OK || sg->d_queue.ensure(c, (size_t)sg_queue_cap(m) * SG_NQ + 1) != ICPMI_OK || sg->d_inv.ensure(c, (size_t)m + 1) != ICPMI_OK ||
+            c->d_keys.ensure(c, (size_t)m) != ICPMI_OK || c->d_map_sorted.ensure(c, (size_t)m + 16) != ICPMI_OK)
             return ICPMI_ERR_HIP;
         if (trial > 0) hipLaunchKernelGGL(sg_reset_kernel, dim3(1), dim3(64), 0, c->stream, sg->d_state);
         // (tiles per workgroup: enough workgroups to fill the chip, as few atomics on the block-id counter as that allows)
@@ -1002,7 +981,7 @@ icpmi_status selfgrid_knn(icpmi_ctx* c, const float4* d_pts, int64_t m, int k, i
     }
     sg->cell = g.cell; sg->m = m; sg->k = k; ++sg->seq;
     if (sub) { // a tracked cloud (the resident map of append-only updates): leave the sorted copy behind for the build of the next append
-        if (sg_cap(c, &sg->d_prev, &sg->cap_prev, (size_t)m + 16) != ICPMI_OK) return ICPMI_ERR_HIP; // (a reallocation drops the old content: it is rewritten below)
+        if (sg->d_prev.ensure(c, (size_t)m + 16) != ICPMI_OK) return ICPMI_ERR_HIP; // (a reallocation drops the old content: it is rewritten below)
         HIP_TRY(c, hipMemcpyAsync(sg->d_prev, c->d_map_sorted, (size_t)m * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
         sg->prev_m = m;
         for (int r = 0; r < 3; ++r) { sg->prev_lo[r] = lo[r]; sg->prev_hi[r] = hi[r]; }
@@ -1030,7 +1009,7 @@ icpmi_status selfgrid_knn(icpmi_ctx* c, const float4* d_pts, int64_t m, int k, i
         // d_sel: [0, m) by sorted position, then (4-byte aligned) the list of the selected original indices
         const size_t list_at = ((size_t)m + 3) / 4 * 4;
         const size_t groups = (size_t)((m + SGQ - 1) / SGQ);
-        if (sg_cap(c, &sg->d_dirty, &sg->cap_dirty, words) != ICPMI_OK || sg_cap(c, &sg->d_sel, &sg->cap_sel, list_at + (size_t)4 * (m + groups + 2) + 64) != ICPMI_OK) return ICPMI_ERR_HIP;
+        if (sg->d_dirty.ensure(c, words) != ICPMI_OK || sg->d_sel.ensure(c, list_at + (size_t)4 * (m + groups + 2) + 64) != ICPMI_OK) return ICPMI_ERR_HIP;
         static_assert(sizeof(SgLevels) <= 64 * sizeof(unsigned), "level table");
         HIP_TRY(c, hipMemsetAsync(sg->d_dirty, 0, words * sizeof(unsigned), c->stream));
         unsigned* n_sel = sg->d_dirty + (words - 128);

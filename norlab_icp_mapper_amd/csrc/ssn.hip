@@ -249,9 +249,9 @@ __global__ __launch_bounds__(256) void ssn_emit_box_kernel(int64_t n, const unsi
 icpmi_status ssn_debug_minstd(icpmi_ctx* c, unsigned seed, unsigned n, unsigned* out)
 {
     DevBuf<unsigned> d; HIP_TRY(c, d.alloc(1));
-    hipLaunchKernelGGL(minstd_nth_kernel, dim3(1), dim3(64), 0, c->stream, seed, n, d.p);
+    hipLaunchKernelGGL(minstd_nth_kernel, dim3(1), dim3(64), 0, c->stream, seed, n, d.get());
     HIP_TRY(c, hipGetLastError());
-    if (read_back(c, out, d.p, sizeof(unsigned)) != ICPMI_OK) return ICPMI_ERR_HIP;
+    if (read_back(c, out, d.get(), sizeof(unsigned)) != ICPMI_OK) return ICPMI_ERR_HIP;
     return ICPMI_OK;
 }
 
@@ -283,43 +283,43 @@ icpmi_status ssn_sample_dev(icpmi_ctx* c, const float4* d_in, int64_t n, float r
     constexpr int RB = 64;
     HIP_TRY(c, d_part.alloc(6 * RB));
     // root box
-    hipLaunchKernelGGL(ssn_bbox_kernel, dim3(RB), dim3(256), 0, c->stream, d_in, n, d_part.p);
+    hipLaunchKernelGGL(ssn_bbox_kernel, dim3(RB), dim3(256), 0, c->stream, d_in, n, d_part.get());
     float hp[6 * RB];
-    if (read_back(c, hp, d_part.p, sizeof hp) != ICPMI_OK) return ICPMI_ERR_HIP;
+    if (read_back(c, hp, d_part.get(), sizeof hp) != ICPMI_OK) return ICPMI_ERR_HIP;
     SsnBox root;
     for (int r = 0; r < 3; ++r) { root.lo[r] = INFINITY; root.hi[r] = -INFINITY; }
     for (int b = 0; b < RB; ++b)
         for (int r = 0; r < 3; ++r) { root.lo[r] = std::min(root.lo[r], hp[6 * b + r]); root.hi[r] = std::max(root.hi[r], hp[6 * b + 3 + r]); }
-    { const icpmi_status us = upload_small(c, d_box[0].p, &root, sizeof root); if (us != ICPMI_OK) return us; }
-    hipLaunchKernelGGL(ssn_init_kernel, dim3(blocks), dim3(256), 0, c->stream, n, d_nstart.p, d_ncnt.p);
+    { const icpmi_status us = upload_small(c, d_box[0].get(), &root, sizeof root); if (us != ICPMI_OK) return us; }
+    hipLaunchKernelGGL(ssn_init_kernel, dim3(blocks), dim3(256), 0, c->stream, n, d_nstart.get(), d_ncnt.get());
     // levels: the largest node of level L + 1 holds ceil(size / 2) points
     int levels = 0;
     for (int64_t sz = n; sz > knn; sz = sz - sz / 2) ++levels;
     int cur_box = 0, half = 0;
     for (int lv = 0; lv <= levels; ++lv) { // the last round sorts finished boxes only: index order inside every box
-        hipLaunchKernelGGL(ssn_key_kernel, dim3(blocks), dim3(256), 0, c->stream, d_in, n, knn, (const unsigned*)d_nstart.p, (const unsigned*)d_ncnt.p,
-                           (const SsnBox*)d_box[cur_box].p, d_keys.p, d_vals.p);
-        const icpmi_status ss = radix_sort_pairs(c, d_keys.p, d_vals.p, n, bits, d_tab.p, &half);
+        hipLaunchKernelGGL(ssn_key_kernel, dim3(blocks), dim3(256), 0, c->stream, d_in, n, knn, (const unsigned*)d_nstart.get(), (const unsigned*)d_ncnt.get(),
+                           (const SsnBox*)d_box[cur_box].get(), d_keys.get(), d_vals.get());
+        const icpmi_status ss = radix_sort_pairs(c, d_keys.get(), d_vals.get(), n, bits, d_tab.get(), &half);
         if (ss != ICPMI_OK) return ss;
         if (lv == levels) break;
-        hipLaunchKernelGGL(ssn_split_kernel, dim3(blocks), dim3(256), 0, c->stream, d_in, n, knn, (const unsigned*)(d_vals.p + (half ? n : 0)), d_nstart.p, d_ncnt.p,
-                           (const SsnBox*)d_box[cur_box].p, d_box[cur_box ^ 1].p);
+        hipLaunchKernelGGL(ssn_split_kernel, dim3(blocks), dim3(256), 0, c->stream, d_in, n, knn, (const unsigned*)(d_vals.get() + (half ? n : 0)), d_nstart.get(), d_ncnt.get(),
+                           (const SsnBox*)d_box[cur_box].get(), d_box[cur_box ^ 1].get());
         cur_box ^= 1;
     }
-    const unsigned* d_order = d_vals.p + (half ? n : 0);
-    hipLaunchKernelGGL(ssn_fuse_kernel, dim3((int)((n + 127) / 128)), dim3(128), 0, c->stream, d_in, n, d_order, (const unsigned*)d_nstart.p, (const unsigned*)d_ncnt.p,
-                       max_box, d_bnrm.p, d_draws.p, method == 1 ? d_bmean.p : nullptr);
-    icpmi_status s = device_exclusive_scan_io(c, d_draws.p, d_rank.p, (int)n, 0u);
+    const unsigned* d_order = d_vals.get() + (half ? n : 0);
+    hipLaunchKernelGGL(ssn_fuse_kernel, dim3((int)((n + 127) / 128)), dim3(128), 0, c->stream, d_in, n, d_order, (const unsigned*)d_nstart.get(), (const unsigned*)d_ncnt.get(),
+                       max_box, d_bnrm.get(), d_draws.get(), method == 1 ? d_bmean.get() : nullptr);
+    icpmi_status s = device_exclusive_scan_io(c, d_draws.get(), d_rank.get(), (int)n, 0u);
     if (s != ICPMI_OK) return s;
     if (method == 1) { // no random number: every surviving box gives one point
-        hipLaunchKernelGGL(ssn_first_kernel, dim3(blocks), dim3(256), 0, c->stream, n, d_order, (const unsigned*)d_nstart.p, (const unsigned*)d_draws.p, d_keep.p);
-        s = device_exclusive_scan_io(c, d_keep.p, d_outpos.p, (int)n, 0u);
+        hipLaunchKernelGGL(ssn_first_kernel, dim3(blocks), dim3(256), 0, c->stream, n, d_order, (const unsigned*)d_nstart.get(), (const unsigned*)d_draws.get(), d_keep.get());
+        s = device_exclusive_scan_io(c, d_keep.get(), d_outpos.get(), (int)n, 0u);
         if (s != ICPMI_OK) return s;
         unsigned lp = 0, lk = 0, lr = 0, ld = 0;
-        if (read_back2(c, &lp, d_outpos.p + (n - 1), sizeof(unsigned), &lk, d_keep.p + (n - 1), sizeof(unsigned)) != ICPMI_OK) return ICPMI_ERR_HIP;
-        if (read_back2(c, &lr, d_rank.p + (n - 1), sizeof(unsigned), &ld, d_draws.p + (n - 1), sizeof(unsigned)) != ICPMI_OK) return ICPMI_ERR_HIP;
-        hipLaunchKernelGGL(ssn_emit_box_kernel, dim3(blocks), dim3(256), 0, c->stream, n, d_order, (const unsigned*)d_ncnt.p, (const unsigned*)d_draws.p,
-                           (const unsigned*)d_rank.p, (const unsigned*)d_keep.p, (const unsigned*)d_outpos.p, (const float*)d_bnrm.p, (const float*)d_bmean.p,
+        if (read_back2(c, &lp, d_outpos.get() + (n - 1), sizeof(unsigned), &lk, d_keep.get() + (n - 1), sizeof(unsigned)) != ICPMI_OK) return ICPMI_ERR_HIP;
+        if (read_back2(c, &lr, d_rank.get() + (n - 1), sizeof(unsigned), &ld, d_draws.get() + (n - 1), sizeof(unsigned)) != ICPMI_OK) return ICPMI_ERR_HIP;
+        hipLaunchKernelGGL(ssn_emit_box_kernel, dim3(blocks), dim3(256), 0, c->stream, n, d_order, (const unsigned*)d_ncnt.get(), (const unsigned*)d_draws.get(),
+                           (const unsigned*)d_rank.get(), (const unsigned*)d_keep.get(), (const unsigned*)d_outpos.get(), (const float*)d_bnrm.get(), (const float*)d_bmean.get(),
                            d_order_out, d_normals_out, d_mean_out, d_mstart_out, d_mcount_out, d_members_out);
         HIP_TRY(c, hipGetLastError());
         HIP_TRY(c, hipStreamSynchronize(c->stream)); // the scratch of this call is freed on return
@@ -327,13 +327,13 @@ icpmi_status ssn_sample_dev(icpmi_ctx* c, const float4* d_in, int64_t n, float r
         if (n_members_out) *n_members_out = (int64_t)lr + ld;
         return ICPMI_OK;
     }
-    hipLaunchKernelGGL(ssn_draw_kernel, dim3(blocks), dim3(256), 0, c->stream, n, (const unsigned*)d_draws.p, (const unsigned*)d_rank.p, ratio, seed, d_keep.p);
-    s = device_exclusive_scan_io(c, d_keep.p, d_outpos.p, (int)n, 0u);
+    hipLaunchKernelGGL(ssn_draw_kernel, dim3(blocks), dim3(256), 0, c->stream, n, (const unsigned*)d_draws.get(), (const unsigned*)d_rank.get(), ratio, seed, d_keep.get());
+    s = device_exclusive_scan_io(c, d_keep.get(), d_outpos.get(), (int)n, 0u);
     if (s != ICPMI_OK) return s;
     unsigned lp = 0, lk = 0;
-    if (read_back2(c, &lp, d_outpos.p + (n - 1), sizeof(unsigned), &lk, d_keep.p + (n - 1), sizeof(unsigned)) != ICPMI_OK) return ICPMI_ERR_HIP;
-    hipLaunchKernelGGL(ssn_emit_kernel, dim3(blocks), dim3(256), 0, c->stream, n, d_order, (const unsigned*)d_nstart.p, (const unsigned*)d_keep.p,
-                       (const unsigned*)d_outpos.p, (const float*)d_bnrm.p, d_order_out, d_normals_out);
+    if (read_back2(c, &lp, d_outpos.get() + (n - 1), sizeof(unsigned), &lk, d_keep.get() + (n - 1), sizeof(unsigned)) != ICPMI_OK) return ICPMI_ERR_HIP;
+    hipLaunchKernelGGL(ssn_emit_kernel, dim3(blocks), dim3(256), 0, c->stream, n, d_order, (const unsigned*)d_nstart.get(), (const unsigned*)d_keep.get(),
+                       (const unsigned*)d_outpos.get(), (const float*)d_bnrm.get(), d_order_out, d_normals_out);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipStreamSynchronize(c->stream)); // the scratch of this call is freed on return
     *n_out = (int64_t)lp + lk;
@@ -350,18 +350,18 @@ icpmi_status ops_sampling_surface_normal_ex(icpmi_ctx* c, const float* in4, int6
     DevBuf<float4> d_in; DevBuf<int> d_order, d_ms, d_mc, d_mem; DevBuf<float> d_nrm, d_mean;
     HIP_TRY(c, d_in.alloc((size_t)n)); HIP_TRY(c, d_order.alloc((size_t)n)); HIP_TRY(c, d_nrm.alloc(3 * (size_t)n));
     if (method == 1) { HIP_TRY(c, d_mean.alloc(3 * (size_t)n)); HIP_TRY(c, d_ms.alloc((size_t)n)); HIP_TRY(c, d_mc.alloc((size_t)n)); HIP_TRY(c, d_mem.alloc((size_t)n)); }
-    HIP_TRY(c, hipMemcpyAsync(d_in.p, in4, (size_t)n * sizeof(float4), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(d_in.get(), in4, (size_t)n * sizeof(float4), hipMemcpyHostToDevice, c->stream));
     int64_t kept = 0, members = 0;
-    const icpmi_status s = ssn_sample_dev(c, d_in.p, n, ratio, knn, max_box, (unsigned)seed, d_order.p, d_nrm.p, &kept, method, d_mean.p, d_ms.p, d_mc.p, d_mem.p, &members);
+    const icpmi_status s = ssn_sample_dev(c, d_in.get(), n, ratio, knn, max_box, (unsigned)seed, d_order.get(), d_nrm.get(), &kept, method, d_mean.get(), d_ms.get(), d_mc.get(), d_mem.get(), &members);
     if (s != ICPMI_OK) return s;
     if (kept > 0) {
-        if (order_out) HIP_TRY(c, hipMemcpyAsync(order_out, d_order.p, (size_t)kept * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        if (normals3_out) HIP_TRY(c, hipMemcpyAsync(normals3_out, d_nrm.p, 3 * (size_t)kept * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+        if (order_out) HIP_TRY(c, hipMemcpyAsync(order_out, d_order.get(), (size_t)kept * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        if (normals3_out) HIP_TRY(c, hipMemcpyAsync(normals3_out, d_nrm.get(), 3 * (size_t)kept * sizeof(float), hipMemcpyDeviceToHost, c->stream));
         if (method == 1) {
-            if (mean3_out) HIP_TRY(c, hipMemcpyAsync(mean3_out, d_mean.p, 3 * (size_t)kept * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-            if (mstart_out) HIP_TRY(c, hipMemcpyAsync(mstart_out, d_ms.p, (size_t)kept * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-            if (mcount_out) HIP_TRY(c, hipMemcpyAsync(mcount_out, d_mc.p, (size_t)kept * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-            if (members_out && members > 0) HIP_TRY(c, hipMemcpyAsync(members_out, d_mem.p, (size_t)members * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+            if (mean3_out) HIP_TRY(c, hipMemcpyAsync(mean3_out, d_mean.get(), 3 * (size_t)kept * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+            if (mstart_out) HIP_TRY(c, hipMemcpyAsync(mstart_out, d_ms.get(), (size_t)kept * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+            if (mcount_out) HIP_TRY(c, hipMemcpyAsync(mcount_out, d_mc.get(), (size_t)kept * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+            if (members_out && members > 0) HIP_TRY(c, hipMemcpyAsync(members_out, d_mem.get(), (size_t)members * sizeof(int), hipMemcpyDeviceToHost, c->stream));
         }
         HIP_TRY(c, hipStreamSynchronize(c->stream));
     }

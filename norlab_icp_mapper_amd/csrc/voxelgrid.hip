@@ -287,7 +287,7 @@ icpmi_status ops_voxel_grid(icpmi_ctx* c, const float* in4, int64_t n, const flo
     }
     if (m <= 0 || m > n) { c->last_error = "voxel_grid: bad voxel count"; return ICPMI_ERR_HIP; }
     hipLaunchKernelGGL(vg_sum_kernel, dim3((int)((m + VB - 1) / VB)), dim3(VB), 0, c->stream, (const float*)d_soa, n, (const unsigned*)d_vstart, m, svals,
-                       (const unsigned*)d_opos, (const float4*)d_in, (const float*)d_desc, rows, average, (int*)d_order, (float4*)d_out4.p,
+                       (const unsigned*)d_opos, (const float4*)d_in, (const float*)d_desc, rows, average, (int*)d_order, (float4*)d_out4.get(),
                        (float*)d_dout);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipMemcpyAsync(out4, d_out4, (size_t)m * 4 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
