@@ -488,6 +488,48 @@ typedef struct icpmi_point_filter { int32_t type; int32_t i; float f[6]; } icpmi
 icpmi_status icpmi_filter_points(icpmi_handle h, const float* in4, int64_t n, const icpmi_point_filter* filters, int32_t n_filters,
                                  uint8_t* keep);
 
+/* The four sensor-model DataPointsFilters of the classic mapper chain as ONE pass (libpointmatcher 1.4.x, AS RECALLED: upstream's
+ * source is not on hand): each is a per-point function of the position p = (x, y, z) (the first three feature rows), the point's
+ * `normals` column n and a sensor position s, so a run of them is one kernel and -- with a Shadow step -- one compaction.  The
+ * program holds up to 8 steps, evaluated in order for every point; od (`observationDirections`), n, the keep flag and the noise
+ * live in registers across the steps.
+ *   ICPMI_SM_OBSERVATION_DIRECTION  f[0..2] = s = (x, y, z):  od = s - p                    (ObservationDirectionDataPointsFilter)
+ *   ICPMI_SM_ORIENT_NORMALS         i = towardCenter (0 | 1): d = n_x od_x + n_y od_y + n_z od_z, summed left to right; n = -n when
+ *                                   towardCenter ? d < 0 : d > 0                             (OrientNormalsDataPointsFilter)
+ *   ICPMI_SM_SHADOW                 f[0] = eps in [0, 1]: v = | (n / |n|) . (p / |p|) |, each vector divided by its norm first, the
+ *                                   three products summed left to right; kept iff v > eps.  It reads the point's own position, not
+ *                                   od: upstream takes the cloud's origin for the sensor.  |n| == 0, |p| == 0 or a NaN make v NaN,
+ *                                   the comparison false and the point dropped, as Eigen's normalized() does upstream
+ *                                                                                            (ShadowDataPointsFilter)
+ *   ICPMI_SM_SIMPLE_SENSOR_NOISE    i = sensorType, f[0] = gain (finite, > 0); dist = |p|:
+ *                                     0 Sick LMS-1xx, 1 Hokuyo URG-04LX, 2 Hokuyo UTM-30LX with (minRadius, beamAngle, beamConst) =
+ *                                     (0.012, 0.0068, 0.0008), (0.028, 0.0013, 0.0001), (0.018, 0.0006, 0.0015):
+ *                                       t = beamAngle * dist + beamConst; noise = gain * (t > minRadius ? t : minRadius)
+ *                                     3 Kinect, 4 Xtion: noise = ((gain * 0.5) * 0.00285) * (dist * dist)
+ *                                   Whether upstream applies `gain` at all is recalled, not checked (SimpleSensorNoiseDataPointsFilter)
+ * Arithmetic: float32 throughout, every constant rounded to float32, in exactly the order written; a squared norm is
+ * x x + y y + z z summed left to right, a norm its sqrtf; products, sums, divisions and square roots are each correctly rounded and
+ * never contracted (the library is compiled with -ffp-contract=off), so the results equal a float32 restatement bit for bit.
+ * Inputs (host pointers): in4 (4 per point); normals3_in (3 per point, point-major) is needed by ORIENT_NORMALS and SHADOW: NULL gives
+ * ICPMI_ERR_MISSING_NORMALS; obs_dir3_in (3 per point) is what an ORIENT_NORMALS step reads when no OBSERVATION_DIRECTION step comes
+ * before it in the program: NULL then gives ICPMI_ERR_INVALID_ARG ("InvalidField: ... cannot find observation directions").
+ * Outputs, written only when the program produces them: normals3_out (3 n) after an ORIENT_NORMALS step (required then);
+ * obs_dir3_out (3 n) after an OBSERVATION_DIRECTION step (optional: NULL skips it); noise_out (n) after a SIMPLE_SENSOR_NOISE step
+ * (required; the last such step wins); keep_out (n bytes, 1 = kept by every SHADOW step) after a SHADOW step (required).  Steps after
+ * a SHADOW step are evaluated for dropped points too: the caller compacts every row with keep_out, which is what filtering one by
+ * one gives.  A required output that is NULL, an unknown step type, more than 8 steps, eps outside [0, 1] or not finite, a sensorType
+ * outside 0 .. 4, a gain that is not finite and > 0: ICPMI_ERR_INVALID_ARG.  n == 0: ICPMI_OK; n > 2^31 - 1: ICPMI_ERR_UNSUPPORTED.
+ * Planar handles (icpmi_config::is_2d) are served with z == 0 and 3-row normals, as elsewhere.  One thread per point, no atomics, no
+ * shared memory: two calls give the same bits (csrc/ops.hip: sensor_model_kernel). */
+typedef enum { ICPMI_SM_OBSERVATION_DIRECTION = 0, ICPMI_SM_ORIENT_NORMALS = 1,
+               ICPMI_SM_SHADOW = 2, ICPMI_SM_SIMPLE_SENSOR_NOISE = 3 } icpmi_sensor_step_type;
+typedef struct icpmi_sensor_step { int32_t type; int32_t i; float f[4]; } icpmi_sensor_step;
+icpmi_status icpmi_sensor_model(icpmi_handle h, const float* in4, int64_t n,
+                                const float* normals3_in, const float* obs_dir3_in,
+                                const icpmi_sensor_step* steps, int32_t n_steps,
+                                float* normals3_out, float* obs_dir3_out,
+                                float* noise_out, uint8_t* keep_out);
+
 /* `Map::unloadCells` binning (Map.cpp:206-209,232-235): ijk3[3 i + r] = floor(p_r / cell_size). */
 icpmi_status icpmi_bin_cells(icpmi_handle h, const float* pts4, int64_t n, float cell_size, int32_t* ijk3);
 

@@ -89,6 +89,14 @@ class PointFilter(C.Structure):
     _fields_ = [("type", C.c_int32), ("i", C.c_int32), ("f", C.c_float * 6)]
 
 
+class SensorStep(C.Structure):
+    """icpmi_sensor_step: one ObservationDirection / OrientNormals / Shadow / SimpleSensorNoise step of the fused sensor-model pass."""
+    _fields_ = [("type", C.c_int32), ("i", C.c_int32), ("f", C.c_float * 4)]
+
+
+SM_OBSERVATION_DIRECTION, SM_ORIENT_NORMALS, SM_SHADOW, SM_SIMPLE_SENSOR_NOISE = range(4)
+
+
 class CovSampInfo(C.Structure):
     """icpmi_covsamp_info: centre, torque normalisation, ascending eigenvalues and eigenbasis (basis[6 k + j] = x_k[j])."""
     _fields_ = [("center", C.c_double * 3), ("lnorm", C.c_double), ("eigval", C.c_double * 6), ("basis", C.c_double * 36)]
@@ -135,6 +143,7 @@ SYMBOLS = [
     ("icpmi_octree_sample", C.c_int, [_P, _P, C.c_int64, C.c_float, C.c_int32, C.c_int32, _P, _P, _P]),
     ("icpmi_voxel_grid", C.c_int, [_P, _P, C.c_int64, _P, C.c_int32, _P, C.c_int32, _P, _P, _P, _P]),
     ("icpmi_covariance_sampling", C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, C.c_int32, _P, _P, _P]),
+    ("icpmi_sensor_model", C.c_int, [_P, _P, C.c_int64, _P, _P, _P, C.c_int32, _P, _P, _P, _P]),
     ("icpmi_map_update_chain", C.c_int, [_P, _P, C.c_int64, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, _P, C.c_int64, _P, _P]),
     ("icpmi_map_update_chain_staged", C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, _P, C.c_int64, _P, _P]),
     ("icpmi_set_map_scalar", C.c_int, [_P, _P, C.c_int64]),

@@ -1057,6 +1057,51 @@ icpmi_status icpmi_filter_points(icpmi_handle h, const float* in4, int64_t n, co
     return ops_filter_points(h, in4, n, filters, n_filters, keep);
 }
 
+icpmi_status icpmi_sensor_model(icpmi_handle h, const float* in4, int64_t n, const float* normals3_in, const float* obs_dir3_in,
+                                const icpmi_sensor_step* steps, int32_t n_steps, float* normals3_out, float* obs_dir3_out, float* noise_out,
+                                uint8_t* keep_out)
+{
+    CHECK_H(h);
+    if (n < 0 || n_steps < 0 || n_steps > ICPMI_MAX_SENSOR_STEPS || (n_steps > 0 && !steps) || (n > 0 && !in4)) {
+        h->last_error = "sensor_model: bad arguments (at most 8 steps per call)"; return ICPMI_ERR_INVALID_ARG;
+    }
+    // what the program reads and produces, in chain order
+    bool needs_n = false, needs_od_in = false, have_od = false, orient = false, shadow = false, noise = false, n_by_orient = false;
+    for (int32_t k = 0; k < n_steps; ++k) {
+        const icpmi_sensor_step& s = steps[k];
+        switch (s.type) {
+            case ICPMI_SM_OBSERVATION_DIRECTION: have_od = true; break;
+            case ICPMI_SM_ORIENT_NORMALS: n_by_orient |= !needs_n; needs_n = orient = true; needs_od_in |= !have_od; break;
+            case ICPMI_SM_SHADOW:
+                if (!(s.f[0] >= 0.f && s.f[0] <= 1.f)) { h->last_error = "InvalidParameter: ShadowDataPointsFilter: eps must be in [0, 1]"; return ICPMI_ERR_INVALID_ARG; }
+                needs_n = shadow = true;
+                break;
+            case ICPMI_SM_SIMPLE_SENSOR_NOISE:
+                if (s.i < 0 || s.i > 4) { h->last_error = "InvalidParameter: SimpleSensorNoiseDataPointsFilter: sensorType must be 0 .. 4"; return ICPMI_ERR_INVALID_ARG; }
+                if (!(s.f[0] > 0.f) || !std::isfinite(s.f[0])) { h->last_error = "InvalidParameter: SimpleSensorNoiseDataPointsFilter: gain must be finite and > 0"; return ICPMI_ERR_INVALID_ARG; }
+                noise = true;
+                break;
+            default: h->last_error = "InvalidParameter: sensor_model: unknown step type"; return ICPMI_ERR_INVALID_ARG;
+        }
+    }
+    if (n == 0) return ICPMI_OK;
+    if (n > 0x7fffffffll) { h->last_error = "sensor_model: more than 2^31 - 1 points"; return ICPMI_ERR_UNSUPPORTED; }
+    if (needs_n && !normals3_in) {
+        h->last_error = n_by_orient ? "InvalidField: OrientNormalsDataPointsFilter: Error, cannot find normals in descriptors."
+                               : "InvalidField: ShadowDataPointsFilter: Error, cannot find normals in descriptors";
+        return ICPMI_ERR_MISSING_NORMALS;
+    }
+    if (needs_od_in && !obs_dir3_in) {
+        h->last_error = "InvalidField: OrientNormalsDataPointsFilter: Error, cannot find observation directions in descriptors.";
+        return ICPMI_ERR_INVALID_ARG;
+    }
+    if ((orient && !normals3_out) || (noise && !noise_out) || (shadow && !keep_out)) {
+        h->last_error = "sensor_model: an output the program produces is NULL (normals3_out / noise_out / keep_out)"; return ICPMI_ERR_INVALID_ARG;
+    }
+    return ops_sensor_model(h, in4, n, needs_n ? normals3_in : nullptr, needs_od_in ? obs_dir3_in : nullptr, steps, n_steps, orient ? normals3_out : nullptr,
+                            have_od ? obs_dir3_out : nullptr, noise ? noise_out : nullptr, shadow ? keep_out : nullptr);
+}
+
 icpmi_status icpmi_bin_cells(icpmi_handle h, const float* pts4, int64_t n, float cell_size, int32_t* ijk3)
 {
     CHECK_H(h);

@@ -275,6 +275,55 @@ __global__ __launch_bounds__(256) void filter_points_kernel(const float4* __rest
     keep[i] = ok ? 1 : 0;
 }
 
+// ---- fused sensor-model filters (include/icpmi.h: icpmi_sensor_model): ObservationDirection / OrientNormals / Shadow /
+// SimpleSensorNoise as one program per point; od, n, keep and noise stay in registers across the steps ----
+struct SensorPack {
+    icpmi_sensor_step s[ICPMI_MAX_SENSOR_STEPS]; int n;
+    int read_n, write_n, read_od, write_od; // which of the in/out rows the program touches
+};
+
+// n3 / od3 are read and written in place by the thread that owns the point (no __restrict__: the same buffer both ways).
+// No contraction (-ffp-contract=off): every product, sum, division and sqrtf below is one correctly rounded float32 operation.
+__global__ __launch_bounds__(256) void sensor_model_kernel(const float4* __restrict__ in, int64_t n, SensorPack sp, float* n3, float* od3,
+                                                           float* __restrict__ noise_out, uint8_t* __restrict__ keep_out)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const float4 p = in[i];
+    float nx = 0.f, ny = 0.f, nz = 0.f, ox = 0.f, oy = 0.f, oz = 0.f, noise = 0.f;
+    if (sp.read_n) { nx = n3[3 * i]; ny = n3[3 * i + 1]; nz = n3[3 * i + 2]; }
+    if (sp.read_od) { ox = od3[3 * i]; oy = od3[3 * i + 1]; oz = od3[3 * i + 2]; }
+    bool keep = true;
+    for (int k = 0; k < sp.n; ++k) {
+        const icpmi_sensor_step& s = sp.s[k];
+        if (s.type == ICPMI_SM_OBSERVATION_DIRECTION) {
+            ox = s.f[0] - p.x; oy = s.f[1] - p.y; oz = s.f[2] - p.z;
+        } else if (s.type == ICPMI_SM_ORIENT_NORMALS) {
+            const float d = nx * ox + ny * oy + nz * oz;
+            if (s.i ? d < 0.f : d > 0.f) { nx = -nx; ny = -ny; nz = -nz; }
+        } else if (s.type == ICPMI_SM_SHADOW) {
+            const float ln = sqrtf(nx * nx + ny * ny + nz * nz), lp = sqrtf(p.x * p.x + p.y * p.y + p.z * p.z);
+            const float v = fabsf((nx / ln) * (p.x / lp) + (ny / ln) * (p.y / lp) + (nz / ln) * (p.z / lp));
+            keep = keep && v > s.f[0]; // (a NaN compares false: dropped)
+        } else {
+            const float dist = sqrtf(p.x * p.x + p.y * p.y + p.z * p.z), gain = s.f[0];
+            if (s.i <= 2) {
+                const float min_radius = s.i == 0 ? 0.012f : (s.i == 1 ? 0.028f : 0.018f);
+                const float beam_angle = s.i == 0 ? 0.0068f : (s.i == 1 ? 0.0013f : 0.0006f);
+                const float beam_const = s.i == 0 ? 0.0008f : (s.i == 1 ? 0.0001f : 0.0015f);
+                const float t = beam_angle * dist + beam_const;
+                noise = gain * (t > min_radius ? t : min_radius);
+            } else {
+                noise = ((gain * 0.5f) * 0.00285f) * (dist * dist);
+            }
+        }
+    }
+    if (sp.write_n) { n3[3 * i] = nx; n3[3 * i + 1] = ny; n3[3 * i + 2] = nz; }
+    if (sp.write_od) { od3[3 * i] = ox; od3[3 * i + 1] = oy; od3[3 * i + 2] = oz; }
+    if (noise_out) noise_out[i] = noise;
+    if (keep_out) keep_out[i] = keep ? 1 : 0;
+}
+
 // ---- voxel sub-sample (OctreeMapperModule / OctreeGridDataPointsFilter stand-in, samplingMethod 0) ----
 // lattice anchored at the bounding-box minimum; voxel index floor((p - lo) / edge) per axis, 21 bits
 // each; the representative of a voxel is its point of smallest original index (order independent:
@@ -921,6 +970,35 @@ icpmi_status ops_filter_points(icpmi_ctx* c, const float* in4, int64_t n, const 
     hipLaunchKernelGGL(filter_points_kernel, dim3((int)((n + 255) / 256)), dim3(256), 0, c->stream, c->d_stage_in, n, fp, d_keep);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipMemcpyAsync(keep, d_keep, (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return ICPMI_OK;
+}
+
+// the arguments are validated by icpmi_sensor_model (api.hip): every pointer the program needs is there, an output it does not produce is NULL
+icpmi_status ops_sensor_model(icpmi_ctx* c, const float* in4, int64_t n, const float* normals3_in, const float* obs_dir3_in, const icpmi_sensor_step* steps,
+                              int n_steps, float* normals3_out, float* obs_dir3_out, float* noise_out, uint8_t* keep_out)
+{
+    if (n == 0) return ICPMI_OK;
+    SensorPack sp{};
+    sp.n = n_steps;
+    for (int k = 0; k < n_steps; ++k) sp.s[k] = steps[k];
+    sp.read_n = normals3_in ? 1 : 0; sp.write_n = normals3_out ? 1 : 0;
+    sp.read_od = obs_dir3_in ? 1 : 0; sp.write_od = obs_dir3_out ? 1 : 0;
+    if (c->d_stage_in.ensure(c, (size_t)n + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
+    float* d_n3 = nullptr; float* d_od3 = nullptr; float* d_noise = nullptr; uint8_t* d_keep = nullptr;
+    if (sp.read_n || sp.write_n) { if (c->d_stage_n3.ensure(c, (size_t)n * 3) != ICPMI_OK) return ICPMI_ERR_HIP; d_n3 = c->d_stage_n3; }
+    if ((sp.read_od || sp.write_od) && !(d_od3 = scratch_get<float>(c, 6, (size_t)n * 3))) return ICPMI_ERR_HIP;
+    if (noise_out && !(d_noise = scratch_get<float>(c, 7, (size_t)n))) return ICPMI_ERR_HIP;
+    if (keep_out && !(d_keep = scratch_get<uint8_t>(c, 9, (size_t)n))) return ICPMI_ERR_HIP;
+    HIP_TRY(c, hipMemcpyAsync(c->d_stage_in, in4, (size_t)n * sizeof(float4), hipMemcpyHostToDevice, c->stream));
+    if (sp.read_n) HIP_TRY(c, hipMemcpyAsync(d_n3, normals3_in, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    if (sp.read_od) HIP_TRY(c, hipMemcpyAsync(d_od3, obs_dir3_in, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(sensor_model_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, c->d_stage_in, n, sp, d_n3, d_od3, d_noise, d_keep);
+    HIP_TRY(c, hipGetLastError());
+    if (sp.write_n) HIP_TRY(c, hipMemcpyAsync(normals3_out, d_n3, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (sp.write_od) HIP_TRY(c, hipMemcpyAsync(obs_dir3_out, d_od3, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (noise_out) HIP_TRY(c, hipMemcpyAsync(noise_out, d_noise, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (keep_out) HIP_TRY(c, hipMemcpyAsync(keep_out, d_keep, (size_t)n, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return ICPMI_OK;
 }

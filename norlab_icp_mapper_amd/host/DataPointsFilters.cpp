@@ -159,10 +159,56 @@ struct MaxDensityFilter : DataPointsFilter {
 
 struct IdentityFilter : DataPointsFilter { void inPlaceFilter(DataPoints&) const override {} };
 
+// A run of sensor-model filters (ObservationDirection / OrientNormals / Shadow / SimpleSensorNoise; include/icpmi.h:
+// icpmi_sensor_model) as one device pass.  The missing-descriptor errors are raised here, in chain order, with the texts of the
+// filters; afterwards the container is touched exactly as filtering one by one touches it: every ObservationDirection /
+// OrientNormals step moves its descriptor to the end, SimpleSensorNoise adds or replaces its row, and one keepOnly compacts the
+// points and every row -- those produced after the Shadow step included -- when the run holds a Shadow step.
+void applySensorRun(icpmi_handle h, DataPoints& cl, const icpmi_sensor_step* steps, size_t count)
+{
+    const size_t n = cl.getNbPoints();
+    bool haveOd = false, needsNormals = false, needsOdIn = false, orient = false, shadow = false, noise = false;
+    for (size_t k = 0; k < count; ++k) {
+        switch (steps[k].type) {
+            case ICPMI_SM_OBSERVATION_DIRECTION: haveOd = true; break;
+            case ICPMI_SM_ORIENT_NORMALS:
+                if (!cl.descriptorExists("normals")) throw InvalidField("OrientNormalsDataPointsFilter: Error, cannot find normals in descriptors.");
+                if (!haveOd && !cl.descriptorExists("observationDirections")) throw InvalidField("OrientNormalsDataPointsFilter: Error, cannot find observation directions in descriptors.");
+                if (cl.getDescriptorByName("normals").span != 3 || (!haveOd && cl.getDescriptorByName("observationDirections").span != 3))
+                    throw InvalidField("OrientNormalsDataPointsFilter: normals and observationDirections must have 3 rows");
+                needsNormals = orient = true; needsOdIn |= !haveOd;
+                break;
+            case ICPMI_SM_SHADOW:
+                if (!cl.descriptorExists("normals")) throw InvalidField("ShadowDataPointsFilter: Error, cannot find normals in descriptors");
+                if (cl.getDescriptorByName("normals").span != 3) throw InvalidField("ShadowDataPointsFilter: normals must have 3 rows");
+                needsNormals = shadow = true;
+                break;
+            default: noise = true; break;
+        }
+    }
+    std::vector<float> nrm(orient ? 3 * n : 0), od(haveOd ? 3 * n : 0), nz(noise ? n : 0);
+    std::vector<uint8_t> keep(shadow ? n : 0);
+    GpuICPSequence::check(h, icpmi_sensor_model(h, cl.features.data(), (int64_t)n, needsNormals ? cl.getDescriptorByName("normals").data.data() : nullptr,
+                                                needsOdIn ? cl.getDescriptorByName("observationDirections").data.data() : nullptr, steps, (int32_t)count,
+                                                orient ? nrm.data() : nullptr, haveOd ? od.data() : nullptr, noise ? nz.data() : nullptr,
+                                                shadow ? keep.data() : nullptr));
+    for (size_t k = 0; k < count; ++k) {
+        if (steps[k].type == ICPMI_SM_OBSERVATION_DIRECTION) { cl.removeDescriptor("observationDirections"); cl.addDescriptor("observationDirections", 3, od); }
+        else if (steps[k].type == ICPMI_SM_ORIENT_NORMALS) { cl.removeDescriptor("normals"); cl.addDescriptor("normals", 3, nrm); }
+        else if (steps[k].type == ICPMI_SM_SIMPLE_SENSOR_NOISE) cl.addDescriptor("simpleSensorNoise", 1, nz);
+    }
+    if (shadow) cl.keepOnly(keep);
+}
+
 // ObservationDirectionDataPointsFilter{x 0, y 0, z 0} [UPSTREAM]: descriptor `observationDirections` = sensor position - point
-// (3 rows; it rotates with the cloud like `normals`, RigidTransformation::compute)
+// (3 rows; it rotates with the cloud like `normals`, RigidTransformation::compute).  inPlaceFilter is the path of a chain without a
+// GPU context; with one, DataPointsFilters::apply runs the step on the device (applySensorRun), with the same bits.
 struct ObservationDirectionFilter : DataPointsFilter {
     float c[3] = {0, 0, 0};
+    bool sensorStep(icpmi_sensor_step& s) const override {
+        s = icpmi_sensor_step{}; s.type = ICPMI_SM_OBSERVATION_DIRECTION; for (int r = 0; r < 3; ++r) s.f[r] = c[r];
+        return true;
+    }
     void inPlaceFilter(DataPoints& cl) const override {
         const size_t n = cl.getNbPoints();
         std::vector<float> d(3 * n);
@@ -173,9 +219,13 @@ struct ObservationDirectionFilter : DataPointsFilter {
 };
 
 // OrientNormalsDataPointsFilter{towardCenter 1} [UPSTREAM]: a normal whose scalar product with the observation direction is
-// negative (towardCenter) / positive (away) is flipped; needs `normals` and `observationDirections`
+// negative (towardCenter) / positive (away) is flipped; needs `normals` and `observationDirections`.  inPlaceFilter: as above.
 struct OrientNormalsFilter : DataPointsFilter {
     bool towardCenter = true;
+    bool sensorStep(icpmi_sensor_step& s) const override {
+        s = icpmi_sensor_step{}; s.type = ICPMI_SM_ORIENT_NORMALS; s.i = towardCenter ? 1 : 0;
+        return true;
+    }
     void inPlaceFilter(DataPoints& cl) const override {
         if (!cl.descriptorExists("normals")) throw InvalidField("OrientNormalsDataPointsFilter: Error, cannot find normals in descriptors.");
         if (!cl.descriptorExists("observationDirections")) throw InvalidField("OrientNormalsDataPointsFilter: Error, cannot find observation directions in descriptors.");
@@ -189,6 +239,40 @@ struct OrientNormalsFilter : DataPointsFilter {
         }
         cl.removeDescriptor("normals");
         cl.addDescriptor("normals", 3, std::move(nrm.data));
+    }
+};
+
+// ShadowDataPointsFilter{eps 0.1} (libpointmatcher, as recalled; the formulation is icpmi_sensor_model's in include/icpmi.h): drops
+// the points whose normal is nearly perpendicular to the beam, | n / |n| . p / |p| | <= eps -- the sensor is the cloud's origin.
+// Device only; a run of one when it stands alone.
+struct ShadowFilter : DataPointsFilter {
+    float eps = 0.1f;
+    icpmi_handle h = nullptr;
+    bool sensorStep(icpmi_sensor_step& s) const override {
+        s = icpmi_sensor_step{}; s.type = ICPMI_SM_SHADOW; s.f[0] = eps;
+        return true;
+    }
+    void inPlaceFilter(DataPoints& cl) const override {
+        if (!h) throw std::logic_error("ShadowDataPointsFilter needs a GPU context");
+        icpmi_sensor_step s; sensorStep(s);
+        applySensorRun(h, cl, &s, 1);
+    }
+};
+
+// SimpleSensorNoiseDataPointsFilter{sensorType 0, gain 1} (libpointmatcher, as recalled; icpmi_sensor_model): descriptor
+// `simpleSensorNoise` (1 row), the range noise of the sensor model at the point's distance from the origin -- what
+// ErrorMinimizer::getOverlap() reads (GpuICPSequence::operator()).  Device only; a run of one when it stands alone.
+struct SimpleSensorNoiseFilter : DataPointsFilter {
+    int sensorType = 0; float gain = 1.f;
+    icpmi_handle h = nullptr;
+    bool sensorStep(icpmi_sensor_step& s) const override {
+        s = icpmi_sensor_step{}; s.type = ICPMI_SM_SIMPLE_SENSOR_NOISE; s.i = sensorType; s.f[0] = gain;
+        return true;
+    }
+    void inPlaceFilter(DataPoints& cl) const override {
+        if (!h) throw std::logic_error("SimpleSensorNoiseDataPointsFilter needs a GPU context");
+        icpmi_sensor_step s; sensorStep(s);
+        applySensorRun(h, cl, &s, 1);
     }
 };
 
@@ -565,6 +649,24 @@ std::shared_ptr<DataPointsFilter> createDataPointsFilter(const std::string& name
         f->towardCenter = geti(p, "towardCenter", 1) != 0;
         return f;
     }
+    if (name == "ShadowDataPointsFilter") {
+        requireKnown(p, {"eps"}, name);
+        auto f = std::make_shared<ShadowFilter>();
+        f->eps = getf(p, "eps", 0.1f);
+        if (!(f->eps >= 0.f && f->eps <= 1.f)) throw InvalidParameter(name + ": eps must be in [0, 1]");
+        f->h = ctx;
+        return f;
+    }
+    if (name == "SimpleSensorNoiseDataPointsFilter") {
+        requireKnown(p, {"sensorType", "gain"}, name);
+        auto f = std::make_shared<SimpleSensorNoiseFilter>();
+        f->sensorType = geti(p, "sensorType", 0); f->gain = getf(p, "gain", 1.f);
+        if (f->sensorType < 0 || f->sensorType > 4)
+            throw InvalidParameter(name + ": sensorType must be 0 (Sick LMS-1xx), 1 (Hokuyo URG-04LX), 2 (Hokuyo UTM-30LX), 3 (Kinect) or 4 (Xtion)");
+        if (!(f->gain > 0.f) || !std::isfinite(f->gain)) throw InvalidParameter(name + ": gain must be finite and > 0");
+        f->h = ctx;
+        return f;
+    }
     if (name == "MinDistDataPointsFilter" || name == "MaxDistDataPointsFilter") {
         // the older names of DistanceLimitDataPointsFilter: MinDist{dim -1, minDist 1} keeps what lies beyond, MaxDist{dim -1, maxDist 1} within
         const bool isMin = name == "MinDistDataPointsFilter";
@@ -618,6 +720,14 @@ void DataPointsFilters::apply(DataPoints& cloud, const DataPointsFilter* leading
     for (const auto& f : filters) chain.push_back(f.get());
     size_t i = 0;
     while (i < chain.size()) {
+        std::vector<icpmi_sensor_step> steps;
+        icpmi_sensor_step st;
+        while (fuse && ctx && i + steps.size() < chain.size() && steps.size() < 8 && chain[i + steps.size()]->sensorStep(st)) steps.push_back(st);
+        if (!steps.empty()) { // (a run of one takes the same path)
+            applySensorRun(ctx, cloud, steps.data(), steps.size());
+            i += steps.size();
+            continue;
+        }
         std::vector<icpmi_point_filter> run;
         icpmi_point_filter pf;
         while (fuse && ctx && i + run.size() < chain.size() && run.size() < 16 && chain[i + run.size()]->pointFilter(pf)) run.push_back(pf);

@@ -129,6 +129,9 @@ public:
     virtual bool residentOp(icpmi_map_op& op, std::string& scalarName) const { (void)op; (void)scalarName; return false; }
     // true for per-point predicates (DistanceLimit, BoundingBox): a run of them is one icpmi_filter_points pass
     virtual bool pointFilter(icpmi_point_filter& f) const { (void)f; return false; }
+    // true for the sensor-model filters (ObservationDirection, OrientNormals, Shadow, SimpleSensorNoise): per-point functions of the
+    // position, the normal and a sensor position; a run of them is one icpmi_sensor_model pass
+    virtual bool sensorStep(icpmi_sensor_step& s) const { (void)s; return false; }
     // false when two calls on the same cloud may differ (RandomSampling seeded from std::random_device): such a filter cannot
     // serve as a readingStepDataPointsFilter, which the accelerated loop applies once instead of once per iteration
     virtual bool repeatable() const { return true; }
@@ -142,7 +145,7 @@ public:
     // a YAML sequence of single-key maps, e.g. the `input:` and `post:` sections (Mapper.cpp:82,92)
     DataPointsFilters(const yaml::Node& seq, icpmi_handle ctx);
     // the chain in order; runs of per-point predicates (optionally starting with `leading`, the mapper's radius filter,
-    // Mapper.cpp:187-191) go through one fused GPU pass and one compaction
+    // Mapper.cpp:187-191) go through one fused GPU pass and one compaction, and so do runs of sensor-model filters
     void apply(DataPoints& cloud, const DataPointsFilter* leading = nullptr) const;
     size_t size() const { return filters.size(); }
     std::vector<std::shared_ptr<DataPointsFilter>> filters;

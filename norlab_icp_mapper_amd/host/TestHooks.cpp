@@ -63,6 +63,67 @@ int nim_test_filter_chain_times(icpmi_handle h, const char* yaml_seq, const floa
     return filterChain(h, yaml_seq, in4, n, desc_name, desc_span, desc, time_name, time_span, times, out4, nullptr, out_desc, out_times, n_out, nullptr, err, err_cap);
 }
 
+// the same with ANY number of input descriptors (names / spans / data: n_desc entries, each span x n column-major) and every descriptor
+// of the result handed back: out_desc (capacity out_rows_cap x n floats) receives them one after the other in the container's order,
+// each span x n_out, and out_names "name:span;name:span;..." in that order.
+int nim_test_filter_chain_descs(icpmi_handle h, const char* yaml_seq, const float* in4, int64_t n, int n_desc, const char* const* names,
+                                const int* spans, const float* const* data, float* out4, float* out_desc, int out_rows_cap, char* out_names,
+                                int out_names_cap, int64_t* n_out, char* err, int err_cap)
+{
+    try {
+        nim::DataPoints c((size_t)n);
+        std::memcpy(c.features.data(), in4, sizeof(float) * 4 * (size_t)n);
+        for (int d = 0; d < n_desc; ++d) c.addDescriptor(names[d], spans[d], std::vector<float>(data[d], data[d] + (size_t)spans[d] * n));
+        nim::DataPointsFilters chain(nim::yaml::Load(yaml_seq), h);
+        chain.apply(c);
+        const size_t m = c.getNbPoints();
+        std::memcpy(out4, c.features.data(), sizeof(float) * 4 * m);
+        std::string all;
+        size_t rows = 0;
+        for (const auto& d : c.descriptors) {
+            if (d.data.size() != (size_t)d.span * m) throw std::logic_error("the filter chain left descriptor " + d.name + " out of step with the points");
+            if (rows + (size_t)d.span > (size_t)out_rows_cap) throw std::logic_error("more descriptor rows than the caller has room for");
+            std::memcpy(out_desc + rows * m, d.data.data(), sizeof(float) * d.data.size());
+            rows += (size_t)d.span;
+            all += d.name + ":" + std::to_string(d.span) + ";";
+        }
+        if (all.size() + 1 > (size_t)out_names_cap) throw std::logic_error("descriptor names do not fit");
+        std::memcpy(out_names, all.c_str(), all.size() + 1);
+        *n_out = (int64_t)m;
+        return 0;
+    } catch (const std::exception& e) {
+        if (err && err_cap > 0) { std::strncpy(err, e.what(), (size_t)err_cap - 1); err[err_cap - 1] = 0; }
+        return 1;
+    }
+}
+
+// GpuICPSequence on device 0: loadFromYamlNode(yaml_icp), setMap(map4 + map_normals3), then operator() on the reading (scan4 +
+// scan_normals3 as `normals`, may be NULL).  noise (n floats, may be NULL) goes to icpmi_set_reading_sensor_noise right before the
+// registration: what a caller without SimpleSensorNoiseDataPointsFilter had to do by hand.  T_out16 column-major, stats_out the
+// registration's icpmi_stats.
+int nim_test_icp_register(const char* yaml_icp, const float* map4, int64_t m, const float* map_normals3, const float* scan4, int64_t n,
+                          const float* scan_normals3, const float* noise, float* T_out16, icpmi_stats* stats_out, char* err, int err_cap)
+{
+    try {
+        nim::DataPoints map((size_t)m), scan((size_t)n);
+        std::memcpy(map.features.data(), map4, sizeof(float) * 4 * (size_t)m);
+        if (map_normals3) map.addDescriptor("normals", 3, std::vector<float>(map_normals3, map_normals3 + 3 * (size_t)m));
+        std::memcpy(scan.features.data(), scan4, sizeof(float) * 4 * (size_t)n);
+        if (scan_normals3) scan.addDescriptor("normals", 3, std::vector<float>(scan_normals3, scan_normals3 + 3 * (size_t)n));
+        nim::GpuICPSequence icp(0);
+        icp.loadFromYamlNode(nim::yaml::Load(yaml_icp));
+        if (!icp.setMap(map)) throw std::runtime_error("setMap refused the map");
+        if (noise) nim::GpuICPSequence::check(icp.handle(), icpmi_set_reading_sensor_noise(icp.handle(), noise, n));
+        const nim::Mat4 T = icp(scan);
+        std::memcpy(T_out16, T.data(), sizeof(float) * 16);
+        *stats_out = icp.stats();
+        return 0;
+    } catch (const std::exception& e) {
+        if (err && err_cap > 0) { std::strncpy(err, e.what(), (size_t)err_cap - 1); err[err_cap - 1] = 0; }
+        return 1;
+    }
+}
+
 // GpuICPSequence on device 0: loadFromYamlNode(yaml_icp) (the `icp:` sub-tree), setMap(in4), then the resident map as the core holds it
 // (downloadMap): what the referenceDataPointsFilters chain made of the cloud.  out4: capacity 4 n.  Returns 0, or 1 with the text in err.
 int nim_test_icp_set_map(const char* yaml_icp, const float* in4, int64_t n, float* out4, int64_t* n_out, char* err, int err_cap)

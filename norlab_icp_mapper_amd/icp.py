@@ -559,6 +559,61 @@ class ICPSequence:
         return order, {"center": np.array(info.center[:]), "lnorm": float(info.lnorm), "eigval": np.array(info.eigval[:]),
                        "basis": np.array(info.basis[:]).reshape(6, 6).T.copy()}
 
+    def sensorModel(self, cloud, steps, normals=None, obs_dirs=None):
+        """icpmi_sensor_model: a run of the four sensor-model DataPointsFilters as one pass.  steps = [("observation_direction", x, y, z) |
+        ("orient_normals", toward_center) | ("shadow", eps) | ("simple_sensor_noise", sensor_type, gain)], at most 8, in chain order;
+        cloud (N, 4), normals / obs_dirs (N, 3) or None.  Returns a dict with what the program produced: "normals" (N, 3) after
+        orient_normals, "observationDirections" (N, 3) after observation_direction, "simpleSensorNoise" (N,) after simple_sensor_noise,
+        "keep" (N,) bool after shadow.  Rows are NOT compacted: apply "keep" to every row, as the host shell does."""
+        c = _f32c(cloud, 4)
+        n = c.shape[0]
+        arr = (_capi.SensorStep * max(1, len(steps)))()
+        kinds = set()
+        for k, st in enumerate(steps):
+            kinds.add(st[0])
+            if st[0] == "observation_direction":
+                arr[k].type = _capi.SM_OBSERVATION_DIRECTION
+                for r in range(3):
+                    arr[k].f[r] = st[1 + r]
+            elif st[0] == "orient_normals":
+                arr[k].type = _capi.SM_ORIENT_NORMALS; arr[k].i = 1 if (st[1] if len(st) > 1 else 1) else 0
+            elif st[0] == "shadow":
+                arr[k].type = _capi.SM_SHADOW; arr[k].f[0] = st[1] if len(st) > 1 else 0.1
+            elif st[0] == "simple_sensor_noise":
+                arr[k].type = _capi.SM_SIMPLE_SENSOR_NOISE; arr[k].i = int(st[1]) if len(st) > 1 else 0
+                arr[k].f[0] = st[2] if len(st) > 2 else 1.0
+            else:
+                raise InvalidParameter("unknown sensor-model step " + str(st[0]))
+
+        def _in3(a, what):
+            if a is None:
+                return None
+            a = _f32c(a, 3)
+            if a.shape[0] != n:
+                raise InvalidParameter(what + " / cloud size mismatch")
+            return a
+        nrm, od = _in3(normals, "normals"), _in3(obs_dirs, "obs_dirs")
+        out = {}
+        if "orient_normals" in kinds:
+            out["normals"] = np.empty((n, 3), dtype=np.float32)
+        if "observation_direction" in kinds:
+            out["observationDirections"] = np.empty((n, 3), dtype=np.float32)
+        if "simple_sensor_noise" in kinds:
+            out["simpleSensorNoise"] = np.empty(n, dtype=np.float32)
+        if "shadow" in kinds:
+            out["keep"] = np.empty(n, dtype=np.uint8)
+        ptr = lambda a: None if a is None else a.ctypes.data
+        st = self._lib.icpmi_sensor_model(self._h, c.ctypes.data, n, ptr(nrm), ptr(od), arr, len(steps), ptr(out.get("normals")),
+                                          ptr(out.get("observationDirections")), ptr(out.get("simpleSensorNoise")), ptr(out.get("keep")))
+        if st == _capi.ERR_INVALID_ARG:  # a missing descriptor is upstream's InvalidField, whatever the status it travels under
+            msg = self._lib.icpmi_last_error(self._h).decode()
+            if msg.startswith("InvalidField"):
+                raise InvalidField(msg)
+        self._check(st)
+        if "keep" in out:
+            out["keep"] = out["keep"].astype(bool)
+        return out
+
     def voxelKeep(self, cloud, edge, method=0):
         """Same lattice, representative by `samplingMethod`: 0 first point, 1 pseudo-random point (smallest fmix32 of the index)."""
         c = _f32c(cloud, 4)
