@@ -611,6 +611,16 @@ icpmi_status icpmi_debug_counters(icpmi_handle h, uint64_t out[24]);
  * nothing to read: no registration yet, one that failed, a batch (icpmi_register_batch_dev), or any other call that reused the matcher's
  * buffers or changed the map after it. */
 icpmi_status icpmi_debug_last_matches(icpmi_handle h, int64_t n, int32_t k, int32_t* ids, float* d2, float T_used[16]);
+/* Test seam: the pair sums of the last COUNTED iteration of the last single registration, as its solve read them.  Off by default:
+ * icpmi_debug_keep_sums(h, 1) gives the handle a block of 32 doubles that every later single registration's solve writes (the cached loop
+ * graphs are dropped; batches never write it), icpmi_debug_keep_sums(h, 0) takes it away again.  Layout of sums[32] (double), as
+ * icpmi_minimize_step: point-to-plane -> A (upper 21, row-major packed) then b (6); point-to-point -> sum w, sum w p (3), sum w q (3),
+ * sum w q p^T (9); always [27] = sum w, [28] = number of pairs with w != 0; force2D -> [29..31] = b of the 2-D residual.  limits
+ * (8 floats, slot f = filter f of the chain: Trimmed / Median / VarTrimmed), robust_scale (RobustOutlierFilter's scale) and
+ * vt_ratio (the ratio VarTrimmedDist picked, -1 without one) are that iteration's; each may be NULL.  ICPMI_ERR_UNSUPPORTED when the sums
+ * are not kept, or under icpmi_debug_last_matches' condition: nothing of a single registration to read. */
+icpmi_status icpmi_debug_keep_sums(icpmi_handle h, int32_t on);
+icpmi_status icpmi_debug_last_sums(icpmi_handle h, double sums[32], float limits[8], float* robust_scale, float* vt_ratio);
 
 /* `errorMinimizer->getCovariance()` of PointToPlaneWithCovErrorMinimizer (upstream's formulation as recalled; Censi's closed form).
  * Needs icpmi_config::covariance = 1 (point-to-plane, 3-D clouds; force2D / force4DOF do not change the formula).  The pairs are those

@@ -333,6 +333,39 @@ icpmi_status icpmi_debug_last_matches(icpmi_handle h, int64_t n, int32_t k, int3
     return ICPMI_OK;
 }
 
+icpmi_status icpmi_debug_keep_sums(icpmi_handle h, int32_t on)
+{
+    CHECK_H(h);
+    if ((on != 0) == (h->d_keep_sums.get() != nullptr)) return ICPMI_OK;
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    // the cached loop graphs were captured with the other sums_out
+    drop_loop_graphs(h);
+    if (!on) { HIP_TRY(h, h->d_keep_sums.reset()); return ICPMI_OK; }
+    HIP_TRY(h, h->d_keep_sums.alloc(ICPMI_NV));
+    HIP_TRY(h, hipMemsetAsync(h->d_keep_sums, 0, ICPMI_NV * sizeof(double), h->stream));
+    return ICPMI_OK;
+}
+
+icpmi_status icpmi_debug_last_sums(icpmi_handle h, double sums[32], float limits[ICPMI_MAX_OUTLIER], float* robust_scale, float* vt_ratio)
+{
+    CHECK_H(h);
+    if (!sums) { h->last_error = "debug_last_sums: sums is null"; return ICPMI_ERR_INVALID_ARG; }
+    if (!h->d_keep_sums.get()) { h->last_error = "debug_last_sums: the pair sums are not kept on this handle (icpmi_debug_keep_sums)"; return ICPMI_ERR_UNSUPPORTED; }
+    if (h->last_match_n == 0) {
+        h->last_error = "debug_last_sums: no single registration's pair sums on this handle (none ran, it failed, or a batch / another call came after it)";
+        return ICPMI_ERR_UNSUPPORTED;
+    }
+    // (dead iterations behind the stop return before the solve: the block holds the last counted iteration's sums; the state is the mirror
+    // loop_run filled for that registration)
+    const icpmi_status s = read_back(h, sums, h->d_keep_sums.get(), ICPMI_NV * sizeof(double));
+    if (s != ICPMI_OK) return s;
+    const IcpState* hs = h->h_state;
+    if (limits) for (int f = 0; f < ICPMI_MAX_OUTLIER; ++f) limits[f] = hs->limits[f];
+    if (robust_scale) *robust_scale = hs->robust_scale;
+    if (vt_ratio) *vt_ratio = hs->vt_ratio;
+    return ICPMI_OK;
+}
+
 icpmi_status icpmi_get_covariance(icpmi_handle h, float cov[36])
 {
     CHECK_H(h);

@@ -607,6 +607,9 @@ struct icpmi_ctx {
     // icpmi_get_covariance (loop.hip: loop_covariance): per-workgroup partials of H / S, then the 36 floats of Cov; cov_ready = computed
     // for the last single registration (read only while last_match_n says its pairs are still the ones in the buffers)
     DevArr<double> d_cov; bool cov_ready = false;
+    // icpmi_debug_keep_sums: 32 doubles the solve kernel of a single registration writes its pair sums to (null: not kept, the default --
+    // the same launches with sums_out == nullptr); read by icpmi_debug_last_sums under the condition of icpmi_debug_last_matches
+    DevArr<double> d_keep_sums;
     DevArr<IcpState> d_state;           // ICPMI_MAX_BATCH states (a single registration uses the first)
     IcpState* h_state = nullptr;                               // pinned mirror (ICPMI_MAX_BATCH)
     bool zero_pending = false;                                 // d_state / d_selhist still to be cleared: on the stream the handle really uses, at its first call (zero_state_if_pending)

@@ -1542,7 +1542,8 @@ static icpmi_status enqueue_iteration(icpmi_ctx* c, int64_t n, const LoopCfg& lc
     if (s != ICPMI_OK) return s;
     if (nn1) HIP_TRY(c, hipEventRecord(nn1, c->stream));
     enqueue_selection(c, lc, n * lc.k);
-    enqueue_accumulate_solve(c, n, lc, nullptr, nullptr);
+    // (icpmi_debug_keep_sums: the sums of every counted iteration of a SINGLE registration; a batch's solves would all write the one block)
+    enqueue_accumulate_solve(c, n, lc, nullptr, c->batch_cur > 1 ? nullptr : c->d_keep_sums.get());
     HIP_TRY(c, hipGetLastError());
     return ICPMI_OK;
 }

@@ -892,6 +892,20 @@ class ICPSequence:
         self._check(self._lib.icpmi_debug_last_matches(self._h, n, k, ids.ctypes.data, d2.ctypes.data, T))
         return ids, d2, _T_from_c(T[:])
 
+    def keepSums(self, on=1):
+        """icpmi_debug_keep_sums: from now on (on) / no longer (off) keep the pair sums of this handle's single registrations for lastSums();
+        off by default.  Drops the cached loop graphs."""
+        self._check(self._lib.icpmi_debug_keep_sums(self._h, 1 if on else 0))
+
+    def lastSums(self):
+        """icpmi_debug_last_sums: (sums (32,) float64 in icpmi_minimize_step's layout, limits (8,) float32, robust_scale, vt_ratio) of the last
+        counted iteration of the last single registration; needs keepSums(1) before that registration."""
+        sums = (C.c_double * 32)()
+        lim = (C.c_float * 8)()
+        rs, vt = C.c_float(), C.c_float()
+        self._check(self._lib.icpmi_debug_last_sums(self._h, sums, lim, C.byref(rs), C.byref(vt)))
+        return np.array(sums[:], dtype=np.float64), np.array(lim[:], dtype=np.float32), np.float32(rs.value), np.float32(vt.value)
+
     def debugCounters(self):
         out = (C.c_uint64 * 24)()
         self._check(self._lib.icpmi_debug_counters(self._h, out))

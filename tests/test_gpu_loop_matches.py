@@ -13,16 +13,15 @@ stop).  After each run:
   - the trimmed limit is the oracle's / numpy's quantile of exactly those d2 (+inf and exact zeros dropped), `pairs` their count
     below it, and the pose after the iteration is a float64 solve over exactly those pairs composed with T_used."""
 import math
-import os
 
 import numpy as np
 import pytest
 
 import match_reference as mr
+from loop_driver import ROOT, centring, f32T, mat4_mul_f32, pose_out, scene  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 RATIO = 0.85
 # one float64 solve against the device's (test_gpu_golden.py: its step tests use the same bars)
 SOLVE_TOL_M, SOLVE_TOL_RAD = 2e-5, 2e-6
@@ -35,31 +34,6 @@ def amd():
 
 
 # ------------------------------------------------------------------------------------------------------------------ references
-def f32T(T):
-    return np.asarray(T, dtype=np.float32)
-
-
-def mat4_mul_f32(ob, A, B):
-    """A @ B as the library's host_mat4_mul forms it: column j of the product is column j of B moved by A through the transform's fmaf
-    chain (rows 0-2); row 3 of a product of rigid transforms is row 3 of B"""
-    out = ob.transform(f32T(A), np.ascontiguousarray(f32T(B).T))
-    R = np.array(out.T, dtype=np.float32)
-    R[3] = f32T(B)[3]
-    return R
-
-
-def pose_out(ob, T_c, mean):
-    """the caller-frame pose the library returns for the centred-frame T_c: [I | mean] T_c [I | -mean]"""
-    Tm = np.eye(4, dtype=np.float32); Tm[:3, 3] = mean
-    Tmi = np.eye(4, dtype=np.float32); Tmi[:3, 3] = -mean
-    return mat4_mul_f32(ob, Tm, mat4_mul_f32(ob, T_c, Tmi))
-
-
-def centring(mean):
-    T = np.eye(4, dtype=np.float32); T[:3, 3] = -mean
-    return T
-
-
 def rodrigues(x):
     th = np.linalg.norm(x[:3])
     T = np.eye(4)
@@ -86,53 +60,6 @@ def solve_step(minimizer, p, q, nrm):
     A = F.T @ F
     b = -F.T @ ((p - q) * nrm).sum(1)
     return rodrigues(np.linalg.solve(A, b))
-
-
-# ------------------------------------------------------------------------------------------------------------------ scenes
-_scenes = {}
-
-
-def scene(name):
-    """(map (M,4) f32, map normals (M,3) f32 or None, reading (N,4) f32); built once per module"""
-    if name in _scenes:
-        return _scenes[name]
-    from norlab_icp_mapper_amd import synth
-    if name in ("mid", "far", "misaligned", "exact_hits", "clusters"):
-        sc = _scenes.get("_mid_raw") or synth.make_scene(m=200_000, n=20_000)
-        _scenes["_mid_raw"] = sc
-        mp, nm, rd = sc["map"], sc["normals"], sc["scan"]
-        rng = np.random.default_rng(29)
-        if name == "far":       # 2 000 returns 100 - 250 m outside the map: unbounded maxDist sends them through the brute pass
-            far = np.ones((2000, 4), np.float32)
-            far[:, :3] = rng.uniform(-1, 1, (2000, 3)) * np.array([50.0, 50.0, 5.0]) + np.array([200.0, -150.0, 5.0])
-            rd = np.r_[rd, far]
-        elif name == "misaligned":  # ~0.15 rad / 1.5 m on top of the scene's own offset: the first seeds land far from the answer
-            Tx = synth.make_T((0.08, -0.05, 0.12), (1.2, -0.8, 0.5)).astype(np.float32)
-            import oracle_bindings as ob
-            rd = ob.transform(Tx, rd)
-        elif name == "exact_hits":  # map points inside the reading: exact zeros in the first iteration's d2
-            rd = np.r_[rd, mp[rng.choice(mp.shape[0], 1500, replace=False)]]
-        elif name == "clusters":    # 60 spots under the reading holding 30 copies of one map point each: list overflow + index ties
-            near = rng.choice(mp.shape[0], 60, replace=False)
-            mp = np.r_[mp, np.repeat(mp[near], 30, axis=0)]
-            nm = np.r_[nm, np.repeat(nm[near], 30, axis=0)]
-        out = (np.ascontiguousarray(mp), np.ascontiguousarray(nm), np.ascontiguousarray(rd))
-    elif name == "bundled":  # map = bundled scans 0-3 placed by the trajectory, reading = scan 4 placed the same way
-        import oracle_bindings as ob
-        from config4_data import quat_T
-        z = np.load(os.path.join(ROOT, "tests", "golden", "bundled_scans_all.npz"))
-        def placed(i):
-            p = np.ones((z[f"scan{i}_xyz"].shape[0], 4), np.float32); p[:, :3] = z[f"scan{i}_xyz"]
-            return ob.transform(quat_T(z["trajectory"][i][2:]), p)
-        mp = np.concatenate([placed(i) for i in range(4)])
-        out = (mp, None, placed(4))
-    elif name == "headline":
-        sc = synth.make_scene(m=1_000_000, n=100_000)
-        out = (sc["map"], sc["normals"], sc["scan"])
-    else:
-        raise ValueError(name)
-    _scenes[name] = out
-    return out
 
 
 # ------------------------------------------------------------------------------------------------------------------ one case
