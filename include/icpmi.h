@@ -103,9 +103,9 @@ typedef enum { ICPMI_STOP_NONE = 0, ICPMI_STOP_COUNTER = 1, ICPMI_STOP_DIFFERENT
  * the hot path.  icpmi_config_default() fills libpointmatcher's defaults for those modules. */
 typedef struct {
     int32_t device;            /* HIP device ordinal                                              */
-    /* matcher: KDTreeMatcher */
+    /* matcher: KDTreeMatcher (KDTreeVarDistMatcher: var_dist below) */
     int32_t knn;               /* default 1                                                       */
-    float   max_dist;          /* default +inf                                                    */
+    float   max_dist;          /* default +inf; ignored when var_dist = 1                         */
     float   epsilon;           /* default 0; > 0 is served by the EXACT search (a valid epsilon-    */
                                /* answer, but not libnabo's pick -- SURVEY.md 0.4) unless           */
                                /* epsilon_approx below asks for libnabo's pruning                   */
@@ -151,7 +151,12 @@ typedef struct {
     int32_t covariance;        /* PointToPlaneWithCovErrorMinimizer: 1 = every single registration leaves the 6 x 6 pose covariance for       */
                                /* icpmi_get_covariance (two launches after the loop); point-to-plane on 3-D clouds only.  Default 0.          */
     float   sensor_std_dev;    /* PointToPlaneWithCovErrorMinimizer.sensorStdDev: sigma of the range noise, finite and >= 0, default 0.01    */
-    int32_t reserved[2];
+    union {                    /* var_dist IS reserved[0]: a caller compiled before the field existed zeroes it with the rest of the tail         */
+        int32_t var_dist;      /* 1 = the matcher is KDTreeVarDistMatcher{knn, epsilon, maxDistField}: reading point i is matched within ITS OWN   */
+                               /* radius, entry i of the row icpmi_set_reading_max_dist hands over before every registration; max_dist is        */
+                               /* ignored.  0 (default): KDTreeMatcher, every result as before the field existed.                                 */
+        int32_t reserved[2];
+    };
 } icpmi_config;
 
 /* What PM::ICPSequence exposes after a call: errorMinimizer->getOverlap() (Mapper.cpp:219) is
@@ -208,6 +213,21 @@ icpmi_status icpmi_set_reading_sensor_noise(icpmi_handle h, const float* noise, 
  * scalar == NULL or n == 0 clears it.  Registrations of a batch with such a chain are not served (every reading needs its own row). */
 icpmi_status icpmi_set_reading_scalar(icpmi_handle h, const float* scalar, int64_t n);
 
+/* KDTreeVarDistMatcher (icpmi_config::var_dist = 1; libpointmatcher's matcher AS RECALLED: upstream's source is not on hand): the 1-row
+ * descriptor `maxDistField` (default name `maxSearchDist`) of the NEXT registration's reading -- radii[i] is the search radius of reading
+ * point i, a distance; libnabo's `knn(query, ids, dists, maxRadii, k, epsilon, flags)` squares it.  Query i gets its up-to-knn nearest map
+ * points with d2 <= radii[i]^2 (the float product, +inf for +inf: the expression that squares KDTreeMatcher's maxDist, so a constant row
+ * gives the bits of `maxDist`); the other slots stay unfilled (-1 / +inf).  Same contract as icpmi_set_reading_scalar: host pointer, n floats,
+ * one shot -- consumed by the next registration, whose n must match; a registration on a var_dist handle without a row, or with another n,
+ * fails with ICPMI_ERR_INVALID_ARG ("InvalidField: ..."), upstream's missing descriptor.  Every entry must be >= 0 or +inf: a NaN or a
+ * negative entry is ICPMI_ERR_INVALID_ARG here.  An entry 0 is valid (that point matches nothing but a coincident map point); a row whose
+ * LARGEST entry is 0 makes the registration fail with ICPMI_ERR_INVALID_ARG, as `maxDist: 0` does ("must be > 0").  radii == NULL or
+ * n == 0 clears the row.  The search itself runs with ONE bound, the largest entry of the row (+inf if any entry is +inf); only the
+ * accept test is per query.  icpmi_register_batch_dev on a var_dist handle registers one reading after the other (every reading needs
+ * its own row: the rule reading-scalar chains follow); icpmi_minimize_step is not served (ICPMI_ERR_UNSUPPORTED).  Planar handles are
+ * served as elsewhere. */
+icpmi_status icpmi_set_reading_max_dist(icpmi_handle h, const float* radii, int64_t n);
+
 /* Replaces `TransformationParameters PM::ICPSequence::operator()(const DataPoints&)`
  * (Mapper.cpp:213): scan4 is the reading already moved by the prior (Mapper.cpp:197); T_out is the
  * correction in the map frame (so that correctedPose = T_out * estimatedPose, Mapper.cpp:215).
@@ -246,6 +266,11 @@ icpmi_status icpmi_transform(icpmi_handle h, const float T[16], const float* in4
  * of PointDistanceMapperModule.cpp:36. max_dist may be +inf. */
 icpmi_status icpmi_knn(icpmi_handle h, const float* q4, int64_t n, int32_t k, float max_dist, int32_t allow_self,
                        int32_t* ids, float* d2);
+/* `KDTreeVarDistMatcher::findClosests`: the same search and the same outputs with one radius per query (radii: n floats, host pointer,
+ * each >= 0 or +inf; see icpmi_set_reading_max_dist).  radii == NULL: ICPMI_ERR_INVALID_ARG.  Works on any handle; a row armed by
+ * icpmi_set_reading_max_dist is left alone. */
+icpmi_status icpmi_knn_var(icpmi_handle h, const float* q4, int64_t n, int32_t k, const float* radii, int32_t allow_self,
+                           int32_t* ids, float* d2);
 
 /* `OutlierFilters::compute` for the handle's chain on given matches (host arrays, k x n; ids = ORIGINAL map indices, needed by
  * SurfaceNormal / GenericDescriptor / Robust; read_normals3 = the reading's `normals`, 3 x n, needed by SurfaceNormalOutlierFilter,

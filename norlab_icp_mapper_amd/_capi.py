@@ -28,7 +28,13 @@ class Outlier(C.Structure):
     _fields_ = [("type", C.c_int32), ("param", C.c_float), ("iparam", C.c_int32), ("param2", C.c_float), ("param3", C.c_float)]
 
 
+class _ConfigTail(C.Union):
+    """The tail of icpmi_config: var_dist is reserved[0]."""
+    _fields_ = [("var_dist", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
 class Config(C.Structure):
+    _anonymous_ = ("tail",)
     _fields_ = [
         ("device", C.c_int32),
         ("knn", C.c_int32),
@@ -57,7 +63,7 @@ class Config(C.Structure):
         ("epsilon_approx", C.c_int32),
         ("covariance", C.c_int32),
         ("sensor_std_dev", C.c_float),
-        ("reserved", C.c_int32 * 2),
+        ("tail", _ConfigTail),
     ]
 
 
@@ -128,6 +134,7 @@ SYMBOLS = [
     ("icpmi_register_batch_dev", C.c_int, [_P, C.c_int32, _P, _P, C.c_int32, _P, _P, _P]),
     ("icpmi_transform", C.c_int, [_P, _F, _P, C.c_int64, _P, _P, _P]),
     ("icpmi_knn", C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_float, C.c_int32, _P, _P]),
+    ("icpmi_knn_var", C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, C.c_int32, _P, _P]),
     ("icpmi_outlier_weights", C.c_int, [_P, _P, _P, C.c_int32, C.c_int64, _P, _P, _F]),
     ("icpmi_minimize_step", C.c_int, [_P, _P, C.c_int64, _P, _F, C.POINTER(C.c_double), C.POINTER(Stats)]),
     ("icpmi_surface_normals", C.c_int, [_P, _P, C.c_int64, C.c_int32, _P]),
@@ -164,6 +171,7 @@ SYMBOLS = [
     ("icpmi_stage_discard", C.c_int, [_P]),
     ("icpmi_register_prior", C.c_int, [_P, _P, C.c_int64, _P, _F, C.POINTER(Stats)]),
     ("icpmi_set_reading_scalar", C.c_int, [_P, _P, C.c_int64]),
+    ("icpmi_set_reading_max_dist", C.c_int, [_P, _P, C.c_int64]),
     ("icpmi_register_prior_dev", C.c_int, [_P, _P, C.c_int64, _P, _F, C.POINTER(Stats)]),
     ("icpmi_map_update_staged", C.c_int, [_P, _P, C.c_float, C.c_int32, _P, _P, _P]),
     ("icpmi_dynamic_points_update", C.c_int, [_P, _P, _P, _P, C.c_int64, _P, _P, C.c_int64, _P]),

@@ -91,7 +91,8 @@ void icpmi_config_default(icpmi_config* cfg)
 static icpmi_status validate_config(const icpmi_config* cfg, std::string& err)
 {
     if (cfg->knn < 1 || cfg->knn > ICPMI_MAX_K) { err = "InvalidParameter: knn must be in [1, 32]"; return ICPMI_ERR_INVALID_ARG; }
-    if (!(cfg->max_dist > 0.f)) { err = "InvalidParameter: maxDist must be > 0"; return ICPMI_ERR_INVALID_ARG; }
+    if (cfg->var_dist != 0 && cfg->var_dist != 1) { err = "InvalidParameter: var_dist must be 0 or 1"; return ICPMI_ERR_INVALID_ARG; }
+    if (!cfg->var_dist && !(cfg->max_dist > 0.f)) { err = "InvalidParameter: maxDist must be > 0"; return ICPMI_ERR_INVALID_ARG; } // (KDTreeVarDistMatcher has no maxDist)
     if (cfg->epsilon < 0.f) { err = "InvalidParameter: epsilon must be >= 0"; return ICPMI_ERR_INVALID_ARG; }
     if (cfg->n_outlier < 0 || cfg->n_outlier > ICPMI_MAX_OUTLIER) { err = "InvalidParameter: at most 8 outlier filters"; return ICPMI_ERR_INVALID_ARG; }
     for (int f = 0; f < cfg->n_outlier; ++f) {
@@ -133,6 +134,14 @@ static icpmi_status validate_config(const icpmi_config* cfg, std::string& err)
     return ICPMI_OK;
 }
 
+// KDTreeVarDistMatcher ignores max_dist: the handle keeps +inf, so that the index is built with every pyramid level -- the row, and with it the
+// bound of a search, arrives with each reading
+static void store_config(icpmi_ctx* c, const icpmi_config* cfg)
+{
+    c->cfg = *cfg;
+    if (c->cfg.var_dist) c->cfg.max_dist = INFINITY;
+}
+
 } // extern "C"
 
 // a handle without the allocation cache's handle count: what icpmi_create wraps, and what the private handles of the map-side operators are made of
@@ -151,7 +160,7 @@ icpmi_status create_handle(const icpmi_config* cfg, icpmi_handle* out)
     if (cfg->device < 0 || cfg->device >= ndev) { g_create_error = "icpmi_create: device ordinal out of range"; return ICPMI_ERR_INVALID_ARG; }
     icpmi_ctx* c = new (std::nothrow) icpmi_ctx();
     if (!c) { g_create_error = "icpmi_create: out of host memory"; return ICPMI_ERR_HIP; }
-    c->cfg = *cfg;
+    store_config(c, cfg);
     c->device = cfg->device;
 #define CR(expr)                                                                                      \
     do {                                                                                              \
@@ -208,7 +217,7 @@ icpmi_status icpmi_set_config(icpmi_handle h, const icpmi_config* cfg)
     if (vs != ICPMI_OK) return vs;
     if (cfg->device != h->device) { h->last_error = "set_config: the device of a handle cannot change"; return ICPMI_ERR_INVALID_ARG; }
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    h->cfg = *cfg;
+    store_config(h, cfg);
     // the cached loop graph was captured for the previous chain
     drop_loop_graphs(h);
     return ICPMI_OK;
@@ -479,13 +488,52 @@ static icpmi_status reject_reading_source(icpmi_ctx* h, const char* who)
     return ICPMI_OK;
 }
 
+// KDTreeVarDistMatcher: a row of radii as the matcher kernels take it -- validated (every entry >= 0 or +inf), squared by the expression that
+// squares maxDist, and its largest entry (un-squared), the uniform bound of the search
+static icpmi_status square_radii(icpmi_ctx* h, const char* who, const float* radii, int64_t n, std::vector<float>& r2, float* max_out)
+{
+    r2.resize((size_t)n);
+    float mx = 0.f;
+    for (int64_t i = 0; i < n; ++i) {
+        const float r = radii[i];
+        if (!(r >= 0.f)) { // (NaN, a negative radius, -inf)
+            h->last_error = std::string(who) + ": every radius must be >= 0 or +inf (entry " + std::to_string((long long)i) + ")";
+            return ICPMI_ERR_INVALID_ARG;
+        }
+        mx = r > mx ? r : mx;
+        r2[(size_t)i] = squared_radius(r);
+    }
+    *max_out = mx;
+    return ICPMI_OK;
+}
+
+// the one bound a search prunes with (make_loop_cfg derives the same three fields from icpmi_config::max_dist)
+static void set_search_bound(const icpmi_ctx* h, LoopCfg& lc, float max_dist)
+{
+    lc.max_dist = max_dist;
+    lc.maxr2 = squared_radius(max_dist);
+    if (std::isfinite(max_dist) && h->grid.cell > 0.f) {
+        const int need = (int)ceilf(max_dist / h->grid.cell) + 1;
+        lc.ring_max = need < 16 ? need : 16;
+    } else lc.ring_max = 6;
+    if (lc.ring_max < 1) lc.ring_max = 1;
+}
+
+// the stage entry points that run the handle's matcher carry no radii: a KDTreeVarDistMatcher chain is served by icpmi_register (and icpmi_knn_var)
+static icpmi_status reject_var_dist(icpmi_ctx* h, const char* who)
+{
+    if (!h->cfg.var_dist) return ICPMI_OK;
+    h->last_error = std::string(who) + ": KDTreeVarDistMatcher is only available inside icpmi_register and icpmi_knn_var";
+    return ICPMI_ERR_UNSUPPORTED;
+}
+
 static icpmi_status register_impl(icpmi_handle h, const float* d_scan4, int64_t n, const float* d_n3, int fixed_iters,
                                   float T_out[16], icpmi_stats* stats)
 {
     // the one-shot reading rows (icpmi_set_reading_scalar / _sensor_noise) belong to THIS call whatever becomes of it: consumed here, before
     // any early return, so that a registration that bails out cannot leave a stale row armed for the next one
-    const int64_t have_scalar_n = h->read_scalar_n, have_noise_n = h->read_noise_n;
-    h->read_scalar_n = 0; h->read_noise_n = 0;
+    const int64_t have_scalar_n = h->read_scalar_n, have_noise_n = h->read_noise_n, have_r2_n = h->read_r2_n;
+    h->read_scalar_n = 0; h->read_noise_n = 0; h->read_r2_n = 0;
     h->cov_ready = false; // (loop_run sets it again once the covariance of THIS registration is enqueued)
     if (!T_out) { h->last_error = "register: T_out is null"; return ICPMI_ERR_INVALID_ARG; }
     if (stats) { memset(stats, 0, sizeof *stats); stats->sensor_noise_overlap = -1.f; } // -1 = "not computed" on EVERY path
@@ -513,6 +561,21 @@ static icpmi_status register_impl(icpmi_handle h, const float* d_scan4, int64_t 
             return ICPMI_ERR_INVALID_ARG;
         }
         lc.read_scalar = wants ? h->d_read_scalar : nullptr;
+    }
+    // KDTreeVarDistMatcher: the radii handed over for THIS reading (one shot).  The search runs with one bound, the largest radius of the row;
+    // the kernels accept per query (nn.hip: RowR2).  nn_r2row is set for the launches of this registration only.
+    struct RowScope { icpmi_ctx* c; ~RowScope() { c->nn_r2row = nullptr; } } row_scope{h};
+    if (h->cfg.var_dist && n > 0) {
+        if (have_r2_n != n) {
+            h->last_error = "InvalidField: KDTreeVarDistMatcher needs the reading's maxDistField descriptor (icpmi_set_reading_max_dist, one radius per point)";
+            return ICPMI_ERR_INVALID_ARG;
+        }
+        if (!(h->read_r2_max > 0.f)) { // (the rule of KDTreeMatcher's maxDist, which this bound stands in for)
+            h->last_error = "InvalidParameter: KDTreeVarDistMatcher: the largest radius of the row must be > 0 (as maxDist)";
+            return ICPMI_ERR_INVALID_ARG;
+        }
+        set_search_bound(h, lc, h->read_r2_max);
+        h->nn_r2row = h->d_read_r2;
     }
     // sensor-noise overlap (icpmi_set_reading_sensor_noise): the noise row is one shot -- this registration consumes it
     // (PointToPointErrorMinimizer::getOverlap() needs `simpleSensorNoise` alone; only the point-to-plane variant also reads the reading's
@@ -559,6 +622,21 @@ icpmi_status icpmi_set_reading_scalar(icpmi_handle h, const float* scalar, int64
     return ICPMI_OK;
 }
 
+icpmi_status icpmi_set_reading_max_dist(icpmi_handle h, const float* radii, int64_t n)
+{
+    CHECK_H(h);
+    h->read_r2_n = 0;
+    if (!radii || n <= 0) return ICPMI_OK;
+    std::vector<float> r2;
+    float mx = 0.f;
+    { const icpmi_status vs = square_radii(h, "set_reading_max_dist", radii, n, r2, &mx); if (vs != ICPMI_OK) return vs; }
+    if (h->d_read_r2.ensure(h, (size_t)n + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
+    HIP_TRY(h, hipMemcpyAsync(h->d_read_r2, r2.data(), (size_t)n * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream)); // the staging vector is free on return
+    h->read_r2_n = n; h->read_r2_max = mx;
+    return ICPMI_OK;
+}
+
 icpmi_status icpmi_register_dev(icpmi_handle h, const float* d_scan4, int64_t n, const float* d_scan_normals3, float T_out[16],
                                 icpmi_stats* stats)
 {
@@ -594,6 +672,7 @@ icpmi_status icpmi_register_batch_dev(icpmi_handle h, int32_t batch, const float
         if (t == ICPMI_OUT_TRIMMEDDIST || t == ICPMI_OUT_MEDIANDIST) ++nquant;
     }
     if (nquant > 1) together = false;
+    if (h->cfg.var_dist) together = false; // (every reading needs its own row of radii)
     for (int b = 0; b < batch; ++b) if (n[b] == 0 || n[b] > 0x7fffffff / ICPMI_MAX_K) together = false;
     if (together) {
         const GridParams& top = h->levels.g[h->levels.nlev - 1];
@@ -645,15 +724,20 @@ icpmi_status icpmi_transform(icpmi_handle h, const float T[16], const float* in4
     return ops_transform(h, T, in4, n, out4, in_normals3, out_normals3);
 }
 
-icpmi_status icpmi_knn(icpmi_handle h, const float* q4, int64_t n, int32_t k, float max_dist, int32_t allow_self, int32_t* ids,
-                       float* d2)
+// icpmi_knn (radii == nullptr: max_dist for every query) and icpmi_knn_var (radii: one per query; the search runs with their maximum)
+static icpmi_status knn_impl(icpmi_handle h, const float* q4, int64_t n, int32_t k, float max_dist, const float* radii, int32_t allow_self,
+                             int32_t* ids, float* d2)
 {
-    CHECK_H(h);
-    if (n < 0 || k < 1 || k > ICPMI_MAX_K || (n > 0 && (!q4 || !ids || !d2)) || !(max_dist > 0.f)) {
+    if (n < 0 || k < 1 || k > ICPMI_MAX_K || (n > 0 && (!q4 || !ids || !d2)) || (!radii && !(max_dist > 0.f))) {
         h->last_error = "knn: bad arguments"; return ICPMI_ERR_INVALID_ARG;
     }
     if (n == 0) return ICPMI_OK;
-    if (h->m <= 0) {
+    std::vector<float> r2;
+    if (radii) {
+        const icpmi_status vs = square_radii(h, "knn_var", radii, n, r2, &max_dist);
+        if (vs != ICPMI_OK) return vs;
+    }
+    if (h->m <= 0 || !(max_dist > 0.f)) { // (no map; a row of zeros: no query accepts anything)
         for (int64_t i = 0; i < n * k; ++i) { ids[i] = -1; d2[i] = INFINITY; }
         return ICPMI_OK;
     }
@@ -663,6 +747,13 @@ icpmi_status icpmi_knn(icpmi_handle h, const float* q4, int64_t n, int32_t k, fl
         return ICPMI_ERR_HIP;
     HIP_TRY(h, hipMemcpyAsync(h->d_reading, q4, (size_t)n * sizeof(float4), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipMemsetAsync(h->d_state, 0, sizeof(IcpState), h->stream));
+    DevBuf<float> d_row; // (its own block: a row armed by icpmi_set_reading_max_dist stays armed)
+    struct RowScope { icpmi_ctx* c; ~RowScope() { c->nn_r2row = nullptr; } } row_scope{h};
+    if (radii) {
+        HIP_TRY(h, d_row.alloc((size_t)n));
+        HIP_TRY(h, hipMemcpyAsync(d_row, r2.data(), (size_t)n * sizeof(float), hipMemcpyHostToDevice, h->stream));
+        h->nn_r2row = d_row;
+    }
     if (k == 1) {
         icpmi_status ss = sort_queries(h, h->d_reading, n);
         if (ss != ICPMI_OK) return ss;
@@ -671,7 +762,7 @@ icpmi_status icpmi_knn(icpmi_handle h, const float* q4, int64_t n, int32_t k, fl
     }
     LoopCfg lc = make_loop_cfg(h, 1);
     lc.k = k; lc.max_dist = max_dist;
-    lc.maxr2 = std::isinf(max_dist) ? INFINITY : max_dist * max_dist;
+    lc.maxr2 = squared_radius(max_dist);
     if (std::isfinite(max_dist)) {
         const int need = (int)ceilf(max_dist / h->grid.cell) + 1;
         lc.ring_max = need < 16 ? need : 16;
@@ -695,6 +786,21 @@ icpmi_status icpmi_knn(icpmi_handle h, const float* q4, int64_t n, int32_t k, fl
     return ICPMI_OK;
 }
 
+icpmi_status icpmi_knn(icpmi_handle h, const float* q4, int64_t n, int32_t k, float max_dist, int32_t allow_self, int32_t* ids,
+                       float* d2)
+{
+    CHECK_H(h);
+    return knn_impl(h, q4, n, k, max_dist, nullptr, allow_self, ids, d2);
+}
+
+icpmi_status icpmi_knn_var(icpmi_handle h, const float* q4, int64_t n, int32_t k, const float* radii, int32_t allow_self, int32_t* ids,
+                           float* d2)
+{
+    CHECK_H(h);
+    if (!radii) { h->last_error = "knn_var: radii is null"; return ICPMI_ERR_INVALID_ARG; }
+    return knn_impl(h, q4, n, k, 0.f, radii, allow_self, ids, d2);
+}
+
 icpmi_status icpmi_outlier_weights(icpmi_handle h, const float* d2, const int32_t* ids, int32_t k, int64_t n,
                                    const float* read_normals3, float* weights, float* limit_out)
 {
@@ -713,6 +819,7 @@ icpmi_status icpmi_minimize_step(icpmi_handle h, const float* reading4, int64_t 
     if (n <= 0 || !reading4) { h->last_error = "minimize_step: bad arguments"; return ICPMI_ERR_INVALID_ARG; }
     { const icpmi_status es = check_ext_filters(h); if (es != ICPMI_OK) return es; }
     { const icpmi_status rs = reject_reading_source(h, "minimize_step"); if (rs != ICPMI_OK) return rs; }
+    { const icpmi_status rs = reject_var_dist(h, "minimize_step"); if (rs != ICPMI_OK) return rs; }
     if (h->m <= 0) { h->last_error = "minimize_step: no map"; return ICPMI_ERR_INVALID_ARG; }
     if (h->cfg.minimizer == ICPMI_MIN_POINT_TO_PLANE && !h->has_normals) {
         h->last_error = "InvalidField: PointToPlaneErrorMinimizer needs the descriptor 'normals' on the map";

@@ -155,6 +155,9 @@ struct BatchArgs {
     int n[ICPMI_MAX_BATCH];      // points of every reading
 };
 struct BatchSrc { const float4* p[ICPMI_MAX_BATCH]; }; // the readings as handed in (device pointers)
+// maxDist -> the squared accept radius the matcher kernels compare d2 with: THE expression for KDTreeMatcher's maxDist and for every entry
+// of a KDTreeVarDistMatcher row alike (a constant row gives the bits of maxDist)
+static inline float squared_radius(float r) { return std::isinf(r) ? INFINITY : r * r; }
 static inline BatchArgs batch_of_one(int64_t n) { BatchArgs b; memset(&b, 0, sizeof b); b.nscan = 1; b.n[0] = (int)n; return b; }
 
 // Device-side description of the ICP chain for one registration (passed by value to kernels).
@@ -550,6 +553,9 @@ struct icpmi_ctx {
     DevArr<float4> d_read_normals;
     DevArr<float> d_read_noise; int64_t read_noise_n = 0; // simpleSensorNoise of the NEXT reading (one shot)
     DevArr<float> d_read_scalar; int64_t read_scalar_n = 0; // GenericDescriptor{source: reading} row of the NEXT reading
+    // KDTreeVarDistMatcher (icpmi_set_reading_max_dist): the SQUARED radii of the NEXT reading, caller's order, and the largest radius of
+    // the row (un-squared; +inf when an entry is): the one bound the search prunes with
+    DevArr<float> d_read_r2; int64_t read_r2_n = 0; float read_r2_max = 0.f;
     DevArr<float4> d_qsorted;           // centred reading sorted by tile (NN locality)
     DevArr<int> d_qindex;               // sorted position -> original index
     DevArr<unsigned> d_qkeys;
@@ -596,6 +602,7 @@ struct icpmi_ctx {
     unsigned* nn_hist0 = nullptr;     // set by the loop when the NN kernel should build the level-0 histogram
     bool nn_builds_hist0 = false;     // set by the NN launcher: true if the launched variant did build it
     bool nn_builds_win = false;       // ... true if it counted the speculative window (ICPMI_S2_WIN: nnk_wg_kernel in a fused-selection loop)
+    const float* nn_r2row = nullptr;  // set by a KDTreeVarDistMatcher registration / icpmi_knn_var for ITS launches only: per-query squared accept radii (nn.hip: RowR2)
     int nn_iter_hint = 0;             // iteration index of the launch being enqueued (> 0: seeded by the previous match)
     DevArr<float4> d_match_pt;          // k = 1 loop: matched map point (xyz, original index bits) per query slot
     float4* nn_match_pt = nullptr;    // set by the loop: keep the loop state (sidx, d2, matched point) in query order

@@ -945,7 +945,7 @@ LoopCfg make_loop_cfg(const icpmi_ctx* c, int fixed_iterations)
     const icpmi_config& cfg = c->cfg;
     lc.k = cfg.knn < 1 ? 1 : cfg.knn;
     lc.max_dist = cfg.max_dist;
-    lc.maxr2 = std::isinf(cfg.max_dist) ? INFINITY : cfg.max_dist * cfg.max_dist;
+    lc.maxr2 = squared_radius(cfg.max_dist);
     lc.inv1e = 1.f; lc.err2 = 1.f;
     if (cfg.epsilon_approx && cfg.epsilon > 0.f) { // both rounded to the conservative side (a larger pruning radius, a stricter decision)
         const double e1 = 1.0 + (double)cfg.epsilon;
@@ -1630,7 +1630,7 @@ static uint64_t loop_sig(const icpmi_ctx* c, const LoopCfg& lc, const float4* d_
 {
     uint64_t sig = fnv(&lc, sizeof lc, 1469598103934665603ull);
     const void* ptrs[] = {d_scan, d_normals3, c->d_qkeys, c->d_qtile, c->d_reading, c->d_read_normals, c->d_sidx, c->d_d2, c->d_hard, c->d_state, c->d_match_pt,
-                          c->d_qsorted, c->d_qindex, c->d_map_sorted, c->d_normals_sorted, c->d_cell_start, c->d_selhist,
+                          c->d_qsorted, c->d_qindex, c->d_map_sorted, c->d_normals_sorted, c->d_cell_start, c->d_selhist, c->nn_r2row,
                           c->scratch[0], c->scratch[1], c->scratch[2], c->scratch[3], c->scratch[4]}; // (VarTrimmedDist passes)
     sig = fnv(ptrs, sizeof ptrs, sig);
     sig = fnv(&c->grid, sizeof c->grid, sig);

@@ -24,6 +24,28 @@ __device__ __forceinline__ float sqrt_up(float x) { return __builtin_amdgcn_sqrt
 typedef float vf4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(1))) vf4 gfloat4; // 16 bytes in global memory (global_load, not flat_load)
 
+// The ACCEPT radius of a matcher kernel (template parameter R of every kernel below; what decides filled against unfilled where the
+// results are written).  float: KDTreeMatcher's maxDist^2, one value for every query -- the kernel argument it always was.  RowR2:
+// KDTreeVarDistMatcher -- query i of the CALLER's order accepts d2 <= row[i] (the reading's `maxDistField` descriptor, squared on the host
+// by the expression that squares maxDist, common.h: squared_radius); `uni` = the maximum of the row is what the SEARCH still prunes with
+// (one bound for all queries: the grid walk, the seeds and the brute pass are the uniform matcher's).  The k nearest within the uniform
+// bound, masked per query, ARE the k nearest within the query's own radius (row[i] <= uni).
+struct RowR2 {
+    float uni;
+    const float* __restrict__ row;
+    const int* __restrict__ slot_index; // nn1_hard_kernel on query slots (the sorted loop state): slot -> caller's index; nullptr: none needed
+};
+__device__ __forceinline__ float r2_uniform(float r) { return r; }
+__device__ __forceinline__ float r2_uniform(const RowR2& r) { return r.uni; }
+// the accept radius of query qi (position in `qindex` order when qindex is given, else the caller's index); ok = the lane owns a query
+__device__ __forceinline__ float r2_query(float r, bool, const int*, int) { return r; }
+__device__ __forceinline__ float r2_query(const RowR2& r, bool ok, const int* __restrict__ qindex, int qi)
+{
+    return ok ? r.row[qindex ? qindex[qi] : qi] : 0.f;
+}
+__device__ __forceinline__ const int* r2_slot_index(float) { return nullptr; }
+__device__ __forceinline__ const int* r2_slot_index(const RowR2& r) { return r.slot_index; }
+
 struct Cand {
     unsigned long long key; // (d2 bits << 32) | original index
     int sidx;               // position in the sorted map
@@ -73,8 +95,9 @@ __device__ __forceinline__ void row_run(const GridParams& g, const unsigned* __r
 // match_pt != nullptr (r5): the loop state is kept in QUERY order (`reading` = the tile-sorted queries, the queue holds query slots): the
 // matched point goes next to the match, and -- hist0 != nullptr -- the match joins the level-0 selection histogram the NN kernel built for
 // the queries it decided itself (csrc/loop.hip, fused selection; copy 0 of the privatised tables).
+template <class R>
 __global__ __launch_bounds__(NN_BLOCK) void nn1_hard_kernel(const float4* __restrict__ reading, const float* __restrict__ Tptr,
-                                                            const float4* __restrict__ map, int m, float maxr2, int allow_self,
+                                                            const float4* __restrict__ map, int m, R maxr, int allow_self,
                                                             int* __restrict__ out_sidx, float* __restrict__ out_d2,
                                                             IcpState* __restrict__ st, const unsigned* __restrict__ hard,
                                                             float4* __restrict__ match_pt = nullptr, unsigned* __restrict__ hist0 = nullptr)
@@ -100,7 +123,7 @@ __global__ __launch_bounds__(NN_BLOCK) void nn1_hard_kernel(const float4* __rest
             for (int i = 1; i < NN_BLOCK / 64; ++i) cand_min(best, shk[i], shs[i]);
             float bd2 = __uint_as_float((unsigned)(best.key >> 32));
             int bs = best.sidx;
-            if (bs < 0 || !(bd2 <= maxr2)) { bs = -1; bd2 = INFINITY; }
+            if (bs < 0 || !(bd2 <= r2_query(maxr, true, r2_slot_index(maxr), qi))) { bs = -1; bd2 = INFINITY; }
             out_sidx[qi] = bs;
             out_d2[qi] = bd2;
             if (match_pt) match_pt[qi] = bs >= 0 ? map[bs] : make_float4(0.f, 0.f, 0.f, 0.f);
@@ -144,14 +167,15 @@ __device__ __forceinline__ void scan_run_k(const float4* __restrict__ map, unsig
     }
 }
 
-template <int KMAX>
+template <int KMAX, class R>
 __global__ __launch_bounds__(NN_BLOCK) void nnk_kernel(const float4* __restrict__ reading, int n, const float* __restrict__ Tptr,
                                                        GridParams g, const float4* __restrict__ map,
-                                                       const unsigned* __restrict__ cs, int k, float maxr2, int ring_max,
+                                                       const unsigned* __restrict__ cs, int k, R maxr, int ring_max,
                                                        int allow_self, int* __restrict__ out_sidx, float* __restrict__ out_d2,
                                                        IcpState* __restrict__ st, unsigned* __restrict__ hard,
                                                        const unsigned* __restrict__ only, const unsigned* __restrict__ only_count)
 {
+    const float maxr2 = r2_uniform(maxr);
     if (st && st->done) return;
     if (st && blockIdx.x == 0 && threadIdx.x == 0) nn_stamp_open(st);
     // `only` != nullptr: just the listed queries (the left-overs of the tiled self-search below)
@@ -228,10 +252,11 @@ __global__ __launch_bounds__(NN_BLOCK) void nnk_kernel(const float4* __restrict_
                             cz - ring <= 0 && cz + ring >= g.nz - 1;
         decided = (kth != ~0ull && kd2 <= m2) || m2 > maxr2 || covers;
     }
+    const float r2q = r2_query(maxr, true, nullptr, qi);
     for (int j = 0; j < k; ++j) {
         float d2 = __uint_as_float((unsigned)(L.key[j] >> 32));
         int s = L.sidx[j];
-        if (s < 0 || !(d2 <= maxr2)) { s = -1; d2 = INFINITY; }
+        if (s < 0 || !(d2 <= r2q)) { s = -1; d2 = INFINITY; }
         out_sidx[(size_t)k * qi + j] = s;
         out_d2[(size_t)k * qi + j] = d2;
     }
@@ -243,9 +268,9 @@ __global__ __launch_bounds__(NN_BLOCK) void nnk_kernel(const float4* __restrict_
 
 // brute pass for general k: the workgroup streams the map, every lane keeps its own list, then k
 // rounds of "extract the global minimum" merge the 256 lists.
-template <int KMAX>
+template <int KMAX, class R>
 __global__ __launch_bounds__(NN_BLOCK) void nnk_hard_kernel(const float4* __restrict__ reading, const float* __restrict__ Tptr,
-                                                            const float4* __restrict__ map, int m, int k, float maxr2,
+                                                            const float4* __restrict__ map, int m, int k, R maxr,
                                                             int allow_self, int* __restrict__ out_sidx,
                                                             float* __restrict__ out_d2, IcpState* __restrict__ st,
                                                             const unsigned* __restrict__ hard)
@@ -304,7 +329,7 @@ __global__ __launch_bounds__(NN_BLOCK) void nnk_hard_kernel(const float4* __rest
                 win_key = c.key; win_sidx = c.sidx;
                 float d2 = __uint_as_float((unsigned)(c.key >> 32));
                 int s = c.sidx;
-                if (s < 0 || !(d2 <= maxr2)) { s = -1; d2 = INFINITY; }
+                if (s < 0 || !(d2 <= r2_query(maxr, true, nullptr, qi))) { s = -1; d2 = INFINITY; } // (the queue holds the caller's indices)
                 out_sidx[(size_t)k * qi + j] = s;
                 out_d2[(size_t)k * qi + j] = d2;
             }
@@ -386,9 +411,9 @@ __device__ __forceinline__ unsigned wave_incl_scan(unsigned v)
 #else
 #define NN1_WAVES_ATTR
 #endif
-template <int NW, bool SELF>
+template <int NW, bool SELF, class R>
 __global__ __launch_bounds__(64 * NW) NN1_WAVES_ATTR void nn1_wg_kernel(const float4* __restrict__ queries, const int* __restrict__ qindex, BatchArgs ba,
-                                                     const float* __restrict__ Tptr, GridLevels L, float maxr2, int* __restrict__ out_sidx,
+                                                     const float* __restrict__ Tptr, GridLevels L, R maxr, int* __restrict__ out_sidx,
                                                      float* __restrict__ out_d2, IcpState* __restrict__ st, unsigned* __restrict__ hard,
                                                      unsigned* __restrict__ hist0, float4* __restrict__ match_pt,
                                                      const uint4* __restrict__ ltab_g, int unseeded_lev, int seed_pre, float inv1e, float err2)
@@ -396,6 +421,7 @@ __global__ __launch_bounds__(64 * NW) NN1_WAVES_ATTR void nn1_wg_kernel(const fl
     // inv1e = 1 / (1 + epsilon), err2 = (1 + epsilon)^2 (both exactly 1 for the exact search: a multiplication by 1.0f changes no bit): libnabo's
     // `new_rd * maxError2 < heap.headValue()` -- what lies farther than (best so far) / (1 + epsilon) is not visited (KDTreeMatcher's epsilon)
     static_assert(NW == 3 || NW == 4, "waves per workgroup");
+    const float maxr2 = r2_uniform(maxr); // what the search prunes with; the accept radius is asked for where the result is written
     constexpr int NT = 64 * NW, Q = 64;
     constexpr int NR = 3;                  // rows per lane in role 1b: rr = wave + NW sl
     constexpr int CAP = 16 * Q;            // pieces per pass (>= 9 Q: one piece per row always fits)
@@ -707,7 +733,7 @@ __global__ __launch_bounds__(64 * NW) NN1_WAVES_ATTR void nn1_wg_kernel(const fl
     if (w0) { best.key = qkey[slot]; best.sidx = (int)qwin[slot]; }
 
     float bd2 = __uint_as_float((unsigned)(best.key >> 32));
-    const bool found = best.key != ~0ull && bd2 <= maxr2;
+    const bool found = best.key != ~0ull && bd2 <= r2_query(maxr, active, qindex, qi);
     if (!found) bd2 = INFINITY;
     const bool writer = active;
     if (hist0) { // coarse level-0 histogram through LDS first: its barrier must not sit behind the global stores below
@@ -767,14 +793,15 @@ __global__ __launch_bounds__(64 * NW) NN1_WAVES_ATTR void nn1_wg_kernel(const fl
 // entry -- the same point seen again -- dropped).  Iterations > 0 are seeded with the previous
 // iteration's k matches (lane j fetches match j), which makes the first bound tight.
 // ------------------------------------------------------------------------------------------------
-template <int G, int KMAX>
+template <int G, int KMAX, class R>
 __global__ __launch_bounds__(NN_BLOCK) void nnk_ml_kernel(const float4* __restrict__ queries, const int* __restrict__ qindex, int n,
                                                           const float* __restrict__ Tptr, const uint4* __restrict__ ltab_g, int nlev,
-                                                          int k, float maxr2, int allow_self_i, int seeded, int* __restrict__ out_sidx,
+                                                          int k, R maxr, int allow_self_i, int seeded, int* __restrict__ out_sidx,
                                                           float* __restrict__ out_d2, IcpState* __restrict__ st,
                                                           unsigned* __restrict__ hard, int out_sorted, float inv1e, float err2)
 {
     static_assert(G == 8, "lanes per query");
+    const float maxr2 = r2_uniform(maxr);
     constexpr int NB = 4;
     constexpr int NR = (9 + G - 1) / G;
     if (st->done) return;
@@ -1011,6 +1038,7 @@ __global__ __launch_bounds__(NN_BLOCK) void nnk_ml_kernel(const float4* __restri
     }
 
     if (active) {
+        const float r2q = r2_query(maxr, true, qindex, qi);
         // lane j writes results j, j + G, ... (static select from the replicated merged list)
         for (int jj = sub; jj < k; jj += G) {
         unsigned long long key = ~0ull;
@@ -1020,7 +1048,7 @@ __global__ __launch_bounds__(NN_BLOCK) void nnk_ml_kernel(const float4* __restri
         {
             float d2 = __uint_as_float((unsigned)(key >> 32));
             int bs = -1;
-            if (key != ~0ull && d2 <= maxr2) {
+            if (key != ~0ull && d2 <= r2q) {
                 const unsigned lv = (unsigned)sx >> 28, pos = (unsigned)sx & 0x0fffffffu;
                 if (lv == 0) bs = (int)pos;
                 else {
@@ -1060,15 +1088,16 @@ __global__ __launch_bounds__(NN_BLOCK) void nnk_ml_kernel(const float4* __restri
 #ifndef NNK_WG_WAVES
 #define NNK_WG_WAVES 5
 #endif
-template <int KMAX>
+template <int KMAX, class R>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KMAX <= 8 ? NNK_WG_WAVES : 3))) void nnk_wg_kernel(const float4* __restrict__ queries, const int* __restrict__ qindex, int n,
                                                      const float* __restrict__ Tptr, const uint4* __restrict__ ltab_g, int nlev,
-                                                     int k, float maxr2, int* __restrict__ out_sidx, float* __restrict__ out_d2,
+                                                     int k, R maxr, int* __restrict__ out_sidx, float* __restrict__ out_d2,
                                                      IcpState* __restrict__ st, unsigned* __restrict__ hard, int out_sorted, int seed_pre,
                                                      unsigned long long* __restrict__ win /* speculative level 0 of the fused selection (common.h: ICPMI_S2_WIN), or nullptr */,
                                                      float inv1e, float err2 /* KDTreeMatcher's epsilon, as in nn1_wg_kernel */)
 {
     constexpr int NW = 4, NT = 64 * NW, Q = 64, NR = 3;
+    const float maxr2 = r2_uniform(maxr);
     constexpr int CAP = 14 * Q;   // pieces per pass (> 9 Q: one piece per row always fits)
 #ifndef ICPMI_NNK_PLB
 #define ICPMI_NNK_PLB 3
@@ -1428,13 +1457,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KMAX <= 8 ?
     }
     unsigned long long wcnt = 0ull;
     if (active) {
+        const float r2q = r2_query(maxr, true, qindex, qi);
         int bs[KMAX];
         float bd[KMAX];
 #pragma unroll
         for (int j = 0; j < KMAX; ++j) {
             float d2 = __uint_as_float((unsigned)(mk[j] >> 32));
             int b = -1;
-            if (mk[j] != ~0ull && d2 <= maxr2) {
+            if (mk[j] != ~0ull && d2 <= r2q) {
                 const unsigned lv = (unsigned)ms[j] >> 28, pos = (unsigned)ms[j] & 0x0fffffffu;
                 if (lv == 0) b = (int)pos;
                 else {
@@ -1507,11 +1537,22 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KMAX <= 8 ?
 
 } // namespace
 
+// the accept radius of the launch being enqueued: KDTreeMatcher's maxDist^2, or -- icpmi_ctx::nn_r2row set by the caller for exactly this
+// launch sequence -- the row of a KDTreeVarDistMatcher with the uniform bound lc.maxr2 (f is called with a float or a RowR2)
+template <class F>
+static void with_accept_radius(const icpmi_ctx* c, const LoopCfg& lc, const int* slot_index, F f)
+{
+    if (c->nn_r2row) f(RowR2{lc.maxr2, c->nn_r2row, slot_index});
+    else f(lc.maxr2);
+}
+
 void nn_launch_hard_k1(icpmi_ctx* c, const float4* d_reading, const float* d_T, const LoopCfg& lc, int allow_self, int* d_sidx,
                        float* d_d2, IcpState* d_state)
 {
-    hipLaunchKernelGGL(nn1_hard_kernel, dim3(512), dim3(NN_BLOCK), 0, c->stream, d_reading, d_T, c->d_map_sorted, (int)c->m, lc.maxr2,
-                       allow_self, d_sidx, d_d2, d_state, c->d_hard);
+    with_accept_radius(c, lc, nullptr, [&](auto maxr) {
+        hipLaunchKernelGGL(nn1_hard_kernel<decltype(maxr)>, dim3(512), dim3(NN_BLOCK), 0, c->stream, d_reading, d_T, c->d_map_sorted, (int)c->m, maxr,
+                           allow_self, d_sidx, d_d2, d_state, c->d_hard, (float4*)nullptr, (unsigned*)nullptr);
+    });
     hipLaunchKernelGGL(hard_reset_kernel, dim3(1), dim3(64), 0, c->stream, d_state);
 }
 
@@ -1550,18 +1591,22 @@ icpmi_status nn_launch_k1(icpmi_ctx* c, const float4* d_reading, int64_t n, cons
         const bool seeded = c->nn_iter_hint > 0 && allow_self;
         const int seed_pre = (seeded && c->nn_iter_hint > 1) ? 0 : 1;
 #define LAUNCH_WG(S_)                                                                                                           \
-    hipLaunchKernelGGL((nn1_wg_kernel<4, S_>), dim3((int)(((n + 63) / 64 + 7) / 8 * 8), ba.nscan), dim3(256), 0, c->stream,    \
-                       q, qi, ba, d_T, c->levels, lc.maxr2, d_sidx, d_d2, d_state, c->d_hard, h0, mp, c->d_lvl_tab, unseeded_lev, seed_pre, lc.inv1e, lc.err2)
-        if (allow_self) LAUNCH_WG(true); else LAUNCH_WG(false);
+    hipLaunchKernelGGL((nn1_wg_kernel<4, S_, decltype(maxr)>), dim3((int)(((n + 63) / 64 + 7) / 8 * 8), ba.nscan), dim3(256), 0, c->stream,    \
+                       q, qi, ba, d_T, c->levels, maxr, d_sidx, d_d2, d_state, c->d_hard, h0, mp, c->d_lvl_tab, unseeded_lev, seed_pre, lc.inv1e, lc.err2)
+        with_accept_radius(c, lc, nullptr, [&](auto maxr) { if (allow_self) LAUNCH_WG(true); else LAUNCH_WG(false); });
 #undef LAUNCH_WG
         const GridParams& top = c->levels.g[c->levels.nlev - 1];
         if (!std::isfinite(lc.max_dist) || (top.cell - top.slack) <= lc.max_dist) {
-            if (hard_sorted && mp)
-                hipLaunchKernelGGL(nn1_hard_kernel, dim3(512), dim3(NN_BLOCK), 0, c->stream, q, d_T, c->d_map_sorted, (int)c->m,
-                                   lc.maxr2, allow_self, d_sidx, d_d2, d_state, c->d_hard, mp, c->nn_builds_hist0 ? c->nn_hist0 : (unsigned*)nullptr);
+            if (hard_sorted && mp) // (the queue holds query slots: the row of a KDTreeVarDistMatcher is reached through the slot's caller index)
+                with_accept_radius(c, lc, qi, [&](auto maxr) {
+                    hipLaunchKernelGGL(nn1_hard_kernel<decltype(maxr)>, dim3(512), dim3(NN_BLOCK), 0, c->stream, q, d_T, c->d_map_sorted, (int)c->m,
+                                       maxr, allow_self, d_sidx, d_d2, d_state, c->d_hard, mp, c->nn_builds_hist0 ? c->nn_hist0 : (unsigned*)nullptr);
+                });
             else
-            hipLaunchKernelGGL(nn1_hard_kernel, dim3(512), dim3(NN_BLOCK), 0, c->stream, d_reading, d_T, c->d_map_sorted, (int)c->m,
-                               lc.maxr2, allow_self, d_sidx, d_d2, d_state, c->d_hard);
+                with_accept_radius(c, lc, nullptr, [&](auto maxr) {
+                    hipLaunchKernelGGL(nn1_hard_kernel<decltype(maxr)>, dim3(512), dim3(NN_BLOCK), 0, c->stream, d_reading, d_T, c->d_map_sorted, (int)c->m,
+                                       maxr, allow_self, d_sidx, d_d2, d_state, c->d_hard, (float4*)nullptr, (unsigned*)nullptr);
+                });
             // (the loop's solve_kernel empties the queue; a stage call -- icpmi_knn -- has no solve behind it)
             if (!(hard_sorted && mp)) hipLaunchKernelGGL(hard_reset_kernel, dim3(1), dim3(64), 0, c->stream, d_state);
         }
@@ -1597,19 +1642,22 @@ static icpmi_status nnk_launch_t(icpmi_ctx* c, const float4* d_reading, int64_t 
             // decided on the pyramid (the brute pass rewrites d2 afterwards), below 2^21 matches (the packed counts cannot carry); icpmi_config::sel_window_off: off
             const int sel_win = c->cfg.sel_window_off ? 0 : 1;
             c->nn_builds_win = use_wg && sel_win && c->nn_hist0 != nullptr && d_d2 == c->d_d2 && !needs_hard && n * (int64_t)lc.k < ICPMI_WIN_MAX_COUNT;
-            if (use_wg)
-                hipLaunchKernelGGL((nnk_wg_kernel<KM>), dim3((int)(((n + 63) / 64 + 7) / 8 * 8)), dim3(256), 0, c->stream, q, qi,
-                                   (int)n, d_T, c->d_lvl_tab, c->levels.nlev, lc.k, lc.maxr2, d_sidx, d_d2, d_state, c->d_hard, out_sorted, wg_pre,
-                                   c->nn_builds_win ? reinterpret_cast<unsigned long long*>(c->nn_hist0 + ICPMI_S2_WIN) : (unsigned long long*)nullptr,
-                                   lc.inv1e, lc.err2);
-            else
-            hipLaunchKernelGGL((nnk_ml_kernel<G, KM>), dim3(grid), dim3(NN_BLOCK), 0, c->stream, q, qi, (int)n, d_T, c->d_lvl_tab,
-                               c->levels.nlev, lc.k, lc.maxr2, allow_self, seeded, d_sidx, d_d2, d_state, c->d_hard, out_sorted, lc.inv1e, lc.err2);
-            if (!std::isfinite(lc.max_dist) || (top.cell - top.slack) <= lc.max_dist) {
-                hipLaunchKernelGGL(nnk_hard_kernel<KMAX>, dim3(512), dim3(NN_BLOCK), 0, c->stream, d_reading, d_T, c->d_map_sorted,
-                                   (int)c->m, lc.k, lc.maxr2, allow_self, d_sidx, d_d2, d_state, c->d_hard);
-                hipLaunchKernelGGL(hard_reset_kernel, dim3(1), dim3(64), 0, c->stream, d_state);
-            }
+            with_accept_radius(c, lc, nullptr, [&](auto maxr) {
+                using R = decltype(maxr);
+                if (use_wg)
+                    hipLaunchKernelGGL((nnk_wg_kernel<KM, R>), dim3((int)(((n + 63) / 64 + 7) / 8 * 8)), dim3(256), 0, c->stream, q, qi,
+                                       (int)n, d_T, c->d_lvl_tab, c->levels.nlev, lc.k, maxr, d_sidx, d_d2, d_state, c->d_hard, out_sorted, wg_pre,
+                                       c->nn_builds_win ? reinterpret_cast<unsigned long long*>(c->nn_hist0 + ICPMI_S2_WIN) : (unsigned long long*)nullptr,
+                                       lc.inv1e, lc.err2);
+                else
+                    hipLaunchKernelGGL((nnk_ml_kernel<G, KM, R>), dim3(grid), dim3(NN_BLOCK), 0, c->stream, q, qi, (int)n, d_T, c->d_lvl_tab,
+                                       c->levels.nlev, lc.k, maxr, allow_self, seeded, d_sidx, d_d2, d_state, c->d_hard, out_sorted, lc.inv1e, lc.err2);
+                if (!std::isfinite(lc.max_dist) || (top.cell - top.slack) <= lc.max_dist) {
+                    hipLaunchKernelGGL((nnk_hard_kernel<KMAX, R>), dim3(512), dim3(NN_BLOCK), 0, c->stream, d_reading, d_T, c->d_map_sorted,
+                                       (int)c->m, lc.k, maxr, allow_self, d_sidx, d_d2, d_state, c->d_hard);
+                    hipLaunchKernelGGL(hard_reset_kernel, dim3(1), dim3(64), 0, c->stream, d_state);
+                }
+            });
             HIP_TRY(c, hipGetLastError());
             return ICPMI_OK;
         }
@@ -1618,14 +1666,17 @@ static icpmi_status nnk_launch_t(icpmi_ctx* c, const float4* d_reading, int64_t 
     if constexpr (KMAX > 16) {
         const int blocks = (int)((n + NN_BLOCK - 1) / NN_BLOCK);
         if (blocks == 0) return ICPMI_OK;
-        hipLaunchKernelGGL(nnk_kernel<KMAX>, dim3(blocks), dim3(NN_BLOCK), 0, c->stream, d_reading, (int)n, d_T, c->grid,
-                           c->d_map_sorted, c->d_cell_start, lc.k, lc.maxr2, lc.ring_max, allow_self, d_sidx, d_d2, d_state, c->d_hard,
-                           (const unsigned*)nullptr, (const unsigned*)nullptr);
-        if (!std::isfinite(lc.max_dist) || lc.ring_max < (int)ceilf(lc.max_dist / c->grid.cell) + 1) {
-            hipLaunchKernelGGL(nnk_hard_kernel<KMAX>, dim3(512), dim3(NN_BLOCK), 0, c->stream, d_reading, d_T, c->d_map_sorted,
-                               (int)c->m, lc.k, lc.maxr2, allow_self, d_sidx, d_d2, d_state, c->d_hard);
-            hipLaunchKernelGGL(hard_reset_kernel, dim3(1), dim3(64), 0, c->stream, d_state);
-        }
+        with_accept_radius(c, lc, nullptr, [&](auto maxr) {
+            using R = decltype(maxr);
+            hipLaunchKernelGGL((nnk_kernel<KMAX, R>), dim3(blocks), dim3(NN_BLOCK), 0, c->stream, d_reading, (int)n, d_T, c->grid,
+                               c->d_map_sorted, c->d_cell_start, lc.k, maxr, lc.ring_max, allow_self, d_sidx, d_d2, d_state, c->d_hard,
+                               (const unsigned*)nullptr, (const unsigned*)nullptr);
+            if (!std::isfinite(lc.max_dist) || lc.ring_max < (int)ceilf(lc.max_dist / c->grid.cell) + 1) {
+                hipLaunchKernelGGL((nnk_hard_kernel<KMAX, R>), dim3(512), dim3(NN_BLOCK), 0, c->stream, d_reading, d_T, c->d_map_sorted,
+                                   (int)c->m, lc.k, maxr, allow_self, d_sidx, d_d2, d_state, c->d_hard);
+                hipLaunchKernelGGL(hard_reset_kernel, dim3(1), dim3(64), 0, c->stream, d_state);
+            }
+        });
         HIP_TRY(c, hipGetLastError());
     }
     return ICPMI_OK;

@@ -73,7 +73,7 @@ void GpuICPSequence::setDefault()
     icpmi_config_default(&cfg);
     cfg.device = dev;
     cfg.is_2d = planar ? 1 : 0;
-    genericDescName.clear(); genericReadDescName.clear();
+    genericDescName.clear(); genericReadDescName.clear(); maxDistFieldName.clear();
     cfg.n_outlier = 1;
     cfg.outlier[0].type = ICPMI_OUT_TRIMMEDDIST;
     cfg.outlier[0].param = 0.85f;
@@ -106,6 +106,34 @@ std::pair<std::string, yaml::Node> singleEntry(const yaml::Node& n, const std::s
     throw InvalidParameter("malformed " + what + " entry");
 }
 
+// the `matcher:` entry of an ICP chain into the configuration; maxDistField = KDTreeVarDistMatcher's descriptor name, empty for KDTreeMatcher
+void parseMatcher(const yaml::Node& matcher, icpmi_config& cfg, std::string& maxDistField)
+{
+    maxDistField.clear();
+    cfg.var_dist = 0;
+    auto e = singleEntry(matcher, "matcher");
+    if (e.first == "KDTreeVarDistMatcher") {
+        // every reading point searches within its own radius, the reading's 1-row descriptor `maxDistField` (operator() hands it over)
+        requireKnown(e.second, {"knn", "epsilon", "searchType", "maxDistField"}, "KDTreeVarDistMatcher");
+        cfg.var_dist = 1;
+        maxDistField = e.second["maxDistField"] ? e.second["maxDistField"].as<std::string>() : std::string("maxSearchDist");
+    } else {
+        if (e.first != "KDTreeMatcher") throw InvalidParameter("unknown matcher " + e.first);
+        requireKnown(e.second, {"knn", "epsilon", "searchType", "maxDist", "maxDistField"}, "KDTreeMatcher");
+    }
+    if (e.second["knn"]) cfg.knn = e.second["knn"].as<int>();
+    if (e.second["epsilon"]) cfg.epsilon = e.second["epsilon"].as<float>();
+    // NIM_EPSILON_APPROX=1 (deployment knob): `epsilon` prunes the search as libnabo's maxError2 does (icpmi_config::
+    // epsilon_approx); default: the exact search, which is a valid answer for every epsilon
+    static const bool approx = [] { const char* v = std::getenv("NIM_EPSILON_APPROX"); return v && std::atoi(v) != 0; }();
+    cfg.epsilon_approx = approx ? 1 : 0;
+    // NIM_KNN_WG_FROM=n (deployment knob, icpmi_config::knn_wg_from): the first iteration (n - 1) of a k > 1 loop the workgroup-cooperative matcher serves;
+    // default 0 = from iteration 2.  Same results either way; which is faster depends on how far the first solve moves the reading
+    static const int wgFrom = [] { const char* v = std::getenv("NIM_KNN_WG_FROM"); return v ? std::atoi(v) : 0; }();
+    cfg.knn_wg_from = wgFrom;
+    if (e.second["maxDist"]) cfg.max_dist = e.second["maxDist"].as<float>();
+}
+
 void GpuICPSequence::loadFromYamlNode(const yaml::Node& icp)
 {
     const int dev = cfg.device;
@@ -121,22 +149,8 @@ void GpuICPSequence::loadFromYamlNode(const yaml::Node& icp)
             if (!ok) throw InvalidParameter("unknown ICP chain key: " + kv.first);
         }
 
-    if (icp["matcher"]) {
-        auto e = singleEntry(icp["matcher"], "matcher");
-        if (e.first != "KDTreeMatcher") throw InvalidParameter("unknown matcher " + e.first);
-        requireKnown(e.second, {"knn", "epsilon", "searchType", "maxDist", "maxDistField"}, "KDTreeMatcher");
-        if (e.second["knn"]) cfg.knn = e.second["knn"].as<int>();
-        if (e.second["epsilon"]) cfg.epsilon = e.second["epsilon"].as<float>();
-        // NIM_EPSILON_APPROX=1 (deployment knob): `epsilon` prunes the search as libnabo's maxError2 does (icpmi_config::
-        // epsilon_approx); default: the exact search, which is a valid answer for every epsilon
-        static const bool approx = [] { const char* v = std::getenv("NIM_EPSILON_APPROX"); return v && std::atoi(v) != 0; }();
-        cfg.epsilon_approx = approx ? 1 : 0;
-        // NIM_KNN_WG_FROM=n (deployment knob, icpmi_config::knn_wg_from): the first iteration (n - 1) of a k > 1 loop the workgroup-cooperative matcher serves;
-        // default 0 = from iteration 2.  Same results either way; which is faster depends on how far the first solve moves the reading
-        static const int wgFrom = [] { const char* v = std::getenv("NIM_KNN_WG_FROM"); return v ? std::atoi(v) : 0; }();
-        cfg.knn_wg_from = wgFrom;
-        if (e.second["maxDist"]) cfg.max_dist = e.second["maxDist"].as<float>();
-    }
+    maxDistFieldName.clear();
+    if (icp["matcher"]) parseMatcher(icp["matcher"], cfg, maxDistFieldName);
     cfg.n_outlier = 0;
     genericDescName.clear(); genericReadDescName.clear();
     if (icp["outlierFilters"].IsSequence())
@@ -438,6 +452,11 @@ Mat4 GpuICPSequence::operator()(const DataPoints& readingIn)
         if (!reading.descriptorExists(genericReadDescName) || reading.getDescriptorByName(genericReadDescName).span != 1)
             throw InvalidField("GenericDescriptorOutlierFilter: the reading has no 1-row descriptor " + genericReadDescName);
         check(h, icpmi_set_reading_scalar(h, reading.getDescriptorByName(genericReadDescName).data.data(), (int64_t)reading.getNbPoints()));
+    }
+    if (!maxDistFieldName.empty()) { // KDTreeVarDistMatcher: the radii of the FILTERED reading, ahead of the registration (one shot)
+        if (!reading.descriptorExists(maxDistFieldName) || reading.getDescriptorByName(maxDistFieldName).span != 1)
+            throw InvalidField("KDTreeVarDistMatcher: the reading has no 1-row descriptor " + maxDistFieldName);
+        check(h, icpmi_set_reading_max_dist(h, reading.getDescriptorByName(maxDistFieldName).data.data(), (int64_t)reading.getNbPoints()));
     }
     // (PointToPointErrorMinimizer::getOverlap() needs the noise row alone, only PointToPlane also the reading's normals)
     if ((normals || cfg.minimizer == ICPMI_MIN_POINT_TO_POINT) && reading.descriptorExists("simpleSensorNoise") &&

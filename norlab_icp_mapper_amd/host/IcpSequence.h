@@ -26,6 +26,9 @@ class DataPointsFilters;
 // a `Name` / `Name: {params}` entry split into its name and parameters
 void requireKnown(const yaml::Node& params, std::initializer_list<const char*> known, const std::string& who);
 std::pair<std::string, yaml::Node> singleEntry(const yaml::Node& n, const std::string& what);
+// the `matcher:` entry of an ICP chain (KDTreeMatcher | KDTreeVarDistMatcher) into cfg; maxDistField = the descriptor name of a
+// KDTreeVarDistMatcher (default maxSearchDist), empty for KDTreeMatcher.  Needs no GPU.
+void parseMatcher(const yaml::Node& matcher, icpmi_config& cfg, std::string& maxDistField);
 
 class GpuICPSequence {
 public:
@@ -97,8 +100,10 @@ private:
     size_t stagedPoints = 0;                           // size of the scan kept on the GPU by registerWithPrior
     std::string genericDescName;                       // GenericDescriptorOutlierFilter.descName (empty: no such filter)
     std::string genericReadDescName;                   // ... of a filter with source: reading (the row goes to the device with every reading)
+    std::string maxDistFieldName;                      // KDTreeVarDistMatcher: the reading's 1-row descriptor of search radii (empty: KDTreeMatcher)
   public:
-    bool readsReadingDescriptor() const { return !genericReadDescName.empty(); }
+    bool readsReadingDescriptor() const { return !genericReadDescName.empty() || !maxDistFieldName.empty(); }
+    const std::string& maxDistField() const { return maxDistFieldName; } // KDTreeVarDistMatcher.maxDistField, or empty (KDTreeMatcher)
   private:
     bool planar = false;                               // 2-D mapping (is3D == false): icpmi_config::is_2d
     ErrorMinimizerView minimizerView{this};

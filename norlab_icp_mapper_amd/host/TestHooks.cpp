@@ -124,6 +124,25 @@ int nim_test_icp_register(const char* yaml_icp, const float* map4, int64_t m, co
     }
 }
 
+// parseMatcher on the `matcher:` entry given as YAML text (no GPU, no handle): the fields it sets, and KDTreeVarDistMatcher's descriptor
+// name (empty for KDTreeMatcher) in field_out.  Returns 0, or 1 with the exception's text in err.
+int nim_test_parse_matcher(const char* yaml_matcher, int* knn, float* epsilon, float* max_dist, int* var_dist, char* field_out, int field_cap,
+                           char* err, int err_cap)
+{
+    try {
+        icpmi_config cfg;
+        icpmi_config_default(&cfg);
+        std::string field;
+        nim::parseMatcher(nim::yaml::Load(yaml_matcher), cfg, field);
+        *knn = cfg.knn; *epsilon = cfg.epsilon; *max_dist = cfg.max_dist; *var_dist = cfg.var_dist;
+        if (field_out && field_cap > 0) { std::strncpy(field_out, field.c_str(), (size_t)field_cap - 1); field_out[field_cap - 1] = 0; }
+        return 0;
+    } catch (const std::exception& e) {
+        if (err && err_cap > 0) { std::strncpy(err, e.what(), (size_t)err_cap - 1); err[err_cap - 1] = 0; }
+        return 1;
+    }
+}
+
 // GpuICPSequence on device 0: loadFromYamlNode(yaml_icp) (the `icp:` sub-tree), setMap(in4), then the resident map as the core holds it
 // (downloadMap): what the referenceDataPointsFilters chain made of the cloud.  out4: capacity 4 n.  Returns 0, or 1 with the text in err.
 int nim_test_icp_set_map(const char* yaml_icp, const float* in4, int64_t n, float* out4, int64_t* n_out, char* err, int err_cap)

@@ -128,15 +128,26 @@ def config_from_yaml_chain(chain, **engine):
 
     matcher = chain.get("matcher", {"KDTreeMatcher": {}})
     name, p = single(matcher, "matcher")
-    if name != "KDTreeMatcher":
+    max_dist_field = None
+    if name == "KDTreeVarDistMatcher":
+        # every reading point searches within its own radius: the reading's 1-row descriptor `maxDistField` (ICPSequence.__call__ hands it over)
+        for key in p:
+            if key not in ("knn", "epsilon", "searchType", "maxDistField"):
+                raise InvalidParameter(f"KDTreeVarDistMatcher: unknown parameter {key}")
+        kw["knn"] = int(p.get("knn", 1))
+        kw["epsilon"] = float(p.get("epsilon", 0))
+        kw["var_dist"] = 1
+        max_dist_field = str(p.get("maxDistField", "maxSearchDist"))
+    elif name == "KDTreeMatcher":
+        for key in p:
+            if key not in ("knn", "epsilon", "searchType", "maxDist", "maxDistField"):
+                raise InvalidParameter(f"KDTreeMatcher: unknown parameter {key}")
+        kw["knn"] = int(p.get("knn", 1))
+        kw["epsilon"] = float(p.get("epsilon", 0))
+        md = p.get("maxDist", math.inf)
+        kw["max_dist"] = math.inf if str(md) in ("inf", ".inf") else float(md)
+    else:
         raise InvalidParameter(f"unknown matcher {name}")
-    for key in p:
-        if key not in ("knn", "epsilon", "searchType", "maxDist", "maxDistField"):
-            raise InvalidParameter(f"KDTreeMatcher: unknown parameter {key}")
-    kw["knn"] = int(p.get("knn", 1))
-    kw["epsilon"] = float(p.get("epsilon", 0))
-    md = p.get("maxDist", math.inf)
-    kw["max_dist"] = math.inf if str(md) in ("inf", ".inf") else float(md)
 
     outs = []
     for node in chain.get("outlierFilters", []) or []:
@@ -221,7 +232,10 @@ def config_from_yaml_chain(chain, **engine):
     kw.update(engine)
     kw.pop("generic_desc_name", None)  # the caller hands the descriptor over with ICPSequence.setMapScalar
     kw.pop("generic_read_desc_name", None)  # ... and the reading's with ICPSequence.setReadingScalar
-    return default_config(**kw)
+    cfg = default_config(**kw)
+    if max_dist_field is not None:
+        cfg.max_dist_field = max_dist_field  # (a Python attribute next to the C fields: the descriptor name is the host's business)
+    return cfg
 
 
 class _ErrorMinimizerView:
@@ -316,17 +330,38 @@ class ICPSequence:
         self._check(self._lib.icpmi_get_map_mean(self._h, out))
         return np.array(out[:], dtype=np.float32)
 
-    def __call__(self, scan, scan_normals=None):
+    def __call__(self, scan, scan_normals=None, descriptors=None):
+        """descriptors: {name: rows} of the reading (rows: (N,) or (rows, N)).  A KDTreeVarDistMatcher chain takes its `maxDistField` row from
+        there (InvalidField when it is missing or has more than one row), unless setReadingMaxDist armed one already."""
         scan = _f32c(scan, 4)
         nptr = None
         if scan_normals is not None:
             scan_normals = _f32c(scan_normals, 3)
             nptr = scan_normals.ctypes.data
+        if self.cfg.var_dist and descriptors is not None:
+            field = getattr(self.cfg, "max_dist_field", "maxSearchDist")
+            if field not in descriptors:
+                raise InvalidField(f"KDTreeVarDistMatcher: the reading has no descriptor {field}")
+            row = np.asarray(descriptors[field], dtype=np.float32)
+            if row.ndim == 2 and row.shape[0] == 1:
+                row = row[0]
+            if row.ndim != 1:
+                raise InvalidField(f"KDTreeVarDistMatcher: descriptor {field} must have one row, got shape {row.shape}")
+            self.setReadingMaxDist(row)
         T = (C.c_float * 16)()
         self._last_n = scan.shape[0]
         st = self._lib.icpmi_register(self._h, scan.ctypes.data, scan.shape[0], nptr, T, C.byref(self.stats))
+        if st == _capi.ERR_INVALID_ARG and self.cfg.var_dist:
+            msg = self._lib.icpmi_last_error(self._h).decode()
+            if msg.startswith("InvalidField"):
+                raise InvalidField(msg)
         self._check(st)
         return _T_from_c(T[:])
+
+    def setReadingMaxDist(self, radii):
+        """icpmi_set_reading_max_dist: the search radius of every point of the NEXT reading (KDTreeVarDistMatcher's `maxDistField` row; one shot)."""
+        r = None if radii is None else np.ascontiguousarray(radii, dtype=np.float32).ravel()
+        self._check(self._lib.icpmi_set_reading_max_dist(self._h, None if r is None else r.ctypes.data, 0 if r is None else r.shape[0]))
 
     def setReadingSensorNoise(self, noise):
         """icpmi_set_reading_sensor_noise: the `simpleSensorNoise` row of the NEXT reading (one shot; that call must bring scan_normals)."""
@@ -384,6 +419,17 @@ class ICPSequence:
         ids = np.empty((q.shape[0], k), dtype=np.int32)
         d2 = np.empty((q.shape[0], k), dtype=np.float32)
         self._check(self._lib.icpmi_knn(self._h, q.ctypes.data, q.shape[0], k, max_dist, int(allow_self), ids.ctypes.data, d2.ctypes.data))
+        return ids, d2
+
+    def knnVar(self, queries_centred, radii, k=1, allow_self=True):
+        """icpmi_knn_var: knn with one search radius per query (KDTreeVarDistMatcher::findClosests)."""
+        q = _f32c(queries_centred, 4)
+        r = np.ascontiguousarray(radii, dtype=np.float32).ravel()
+        if r.shape[0] != q.shape[0]:
+            raise InvalidParameter("knnVar: one radius per query")
+        ids = np.empty((q.shape[0], k), dtype=np.int32)
+        d2 = np.empty((q.shape[0], k), dtype=np.float32)
+        self._check(self._lib.icpmi_knn_var(self._h, q.ctypes.data, q.shape[0], k, r.ctypes.data, int(allow_self), ids.ctypes.data, d2.ctypes.data))
         return ids, d2
 
     def outlierWeights(self, d2, ids=None, read_normals=None):
