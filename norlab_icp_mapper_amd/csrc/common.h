@@ -253,7 +253,9 @@ __device__ __forceinline__ void nn_stamp_close(IcpState* st)
 // 14 scans were 14 of 37 ms).  dev_free keeps the block (after the same device-wide synchronisation hipFree implies: nothing in flight
 // can still touch it), dev_malloc hands out the smallest cached block of at least the size asked for and at most twice that + 1 MiB.
 // ICPMI_ALLOC_CACHE_MB (default 1024; 0: plain hipMalloc / hipFree) bounds what is kept; the largest blocks go first.  Blocks are cached per
-// device; icpmi_trim_cache() empties it.
+// device.  Cached blocks go back to the runtime at exactly two points: icpmi_trim_cache(), and dev_malloc's out-of-memory path.  Destroying
+// handles -- the last one of the process included -- releases nothing (icpmi_destroy only keeps the count of live handles): a process holds up
+// to ICPMI_ALLOC_CACHE_MB of HBM after its mappers are gone until it calls icpmi_trim_cache().
 // ------------------------------------------------------------------------------------------------
 // A device-wide synchronisation and a stream capture in ANOTHER thread do not mix on this runtime (scripts/r5/capture_threads.hip, ROCm 7:
 // hipDeviceSynchronize fails with "operation not permitted when stream is capturing" AND invalidates the other thread's thread-local capture;
@@ -828,6 +830,92 @@ __device__ __forceinline__ unsigned long long pack_key(float d2, unsigned id)
     return ((unsigned long long)__float_as_uint(d2) << 32) | (unsigned long long)id;
 }
 
+// a square root that never under-estimates (one v_sqrt_f32, 1 ulp, nudged up)
+__device__ __forceinline__ float sqrt_up(float x) { return __builtin_amdgcn_sqrtf(x) * 1.0000005f; }
+
+// MurmurHash3's 32-bit finaliser: a bijection of the 32-bit integers, so "smallest hash" names exactly one point
+__device__ __forceinline__ unsigned fmix32(unsigned h)
+{
+    h ^= h >> 16; h *= 0x85ebca6bu; h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16;
+    return h;
+}
+
+__device__ __forceinline__ unsigned long long mix64(unsigned long long x)
+{
+    x ^= x >> 33; x *= 0xff51afd7ed558ccdull; x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ull; x ^= x >> 33;
+    return x;
+}
+
+// float -> unsigned whose integer order is the float order (-0 sorts below +0), and back
+__device__ __forceinline__ unsigned float_key(float f) { const unsigned u = __float_as_uint(f); return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }
+__device__ __forceinline__ float float_key_inv(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
+
+// false for NaN, +-inf and anything beyond `limit` (FLT_MAX: plain finiteness)
+__device__ __forceinline__ bool finite_within(float v, float limit) { return fabsf(v) <= limit; }
+
+// ---- bounding box of a float4 cloud in two stages (octree.hip, voxelgrid.hip, ssn.hip, selfgrid.hip) ----
+// Stage 1, bbox_partials_kernel: a grid-stride pass, six floats per workgroup (part[6 b + 0..2] = lo, + 3..5 = hi) and -- COUNT_BAD -- the
+// workgroup's number of points with a coordinate that is not finite_within(limit) in bad[b].  Stage 2, bbox_fold: ONE workgroup folds the
+// partials (a kernel of the caller's, which goes on to compute what it needs from the box), or the host does after a read-back.  min / max
+// are exact, so the box does not depend on the number of workgroups.  (Internal linkage: every file that launches it carries its own copy.)
+namespace {
+constexpr int BBOX_WG = 256;
+
+// the halving LDS tree over the workgroup's 256 boxes (and counts): every lane leaves with the workgroup's
+template <bool COUNT_BAD>
+__device__ __forceinline__ void bbox_wg_reduce(float (&lo)[3], float (&hi)[3], unsigned& nbad)
+{
+    __shared__ float sl[3][BBOX_WG], sh[3][BBOX_WG];
+    __shared__ unsigned sb[COUNT_BAD ? BBOX_WG : 1];
+    const int t = threadIdx.x;
+    for (int r = 0; r < 3; ++r) { sl[r][t] = lo[r]; sh[r][t] = hi[r]; }
+    if constexpr (COUNT_BAD) sb[t] = nbad;
+    __syncthreads();
+    for (int s = BBOX_WG / 2; s > 0; s >>= 1) {
+        if (t < s) {
+            for (int r = 0; r < 3; ++r) { sl[r][t] = fminf(sl[r][t], sl[r][t + s]); sh[r][t] = fmaxf(sh[r][t], sh[r][t + s]); }
+            if constexpr (COUNT_BAD) sb[t] += sb[t + s];
+        }
+        __syncthreads();
+    }
+    for (int r = 0; r < 3; ++r) { lo[r] = sl[r][0]; hi[r] = sh[r][0]; }
+    if constexpr (COUNT_BAD) nbad = sb[0];
+}
+
+template <bool COUNT_BAD>
+__global__ __launch_bounds__(BBOX_WG) void bbox_partials_kernel(const float4* __restrict__ pts, int64_t n, float* __restrict__ part,
+                                                                unsigned* __restrict__ bad /* COUNT_BAD only */, float limit)
+{
+    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    unsigned nb = 0;
+    for (int64_t i = (int64_t)blockIdx.x * BBOX_WG + threadIdx.x; i < n; i += (int64_t)gridDim.x * BBOX_WG) {
+        const float4 p = pts[i];
+        if constexpr (COUNT_BAD) nb += (finite_within(p.x, limit) && finite_within(p.y, limit) && finite_within(p.z, limit)) ? 0u : 1u;
+        lo[0] = fminf(lo[0], p.x); lo[1] = fminf(lo[1], p.y); lo[2] = fminf(lo[2], p.z);
+        hi[0] = fmaxf(hi[0], p.x); hi[1] = fmaxf(hi[1], p.y); hi[2] = fmaxf(hi[2], p.z);
+    }
+    bbox_wg_reduce<COUNT_BAD>(lo, hi, nb);
+    if (threadIdx.x == 0) {
+        for (int r = 0; r < 3; ++r) { part[6 * blockIdx.x + r] = lo[r]; part[6 * blockIdx.x + 3 + r] = hi[r]; }
+        if constexpr (COUNT_BAD) bad[blockIdx.x] = nb;
+    }
+}
+
+// stage 2 inside a kernel of BBOX_WG lanes: the box (and the bad count) of `nparts` partials, in every lane
+template <bool COUNT_BAD>
+__device__ __forceinline__ void bbox_fold(const float* __restrict__ part, const unsigned* __restrict__ bad, int nparts, float (&lo)[3], float (&hi)[3],
+                                          unsigned& nbad)
+{
+    for (int r = 0; r < 3; ++r) { lo[r] = INFINITY; hi[r] = -INFINITY; }
+    nbad = 0;
+    for (int b = threadIdx.x; b < nparts; b += BBOX_WG) {
+        for (int r = 0; r < 3; ++r) { lo[r] = fminf(lo[r], part[6 * b + r]); hi[r] = fmaxf(hi[r], part[6 * b + 3 + r]); }
+        if constexpr (COUNT_BAD) nbad += bad[b];
+    }
+    bbox_wg_reduce<COUNT_BAD>(lo, hi, nbad);
+}
+} // namespace
+
 // bounded sorted list of (key = d2 bits << 32 | original index, sorted position): the k best of a k-NN search, in registers
 template <int KMAX>
 struct KList {
@@ -967,6 +1055,35 @@ icpmi_status loop_single_step(icpmi_ctx* c, int64_t n, const LoopCfg& lc, const 
 icpmi_status loop_outlier_weights(icpmi_ctx* c, const LoopCfg& lc, const float* d2, const int32_t* ids, int k, int64_t n,
                                   const float* read_normals3, float* weights, float* limit_out);
 LoopCfg make_loop_cfg(const icpmi_ctx* c, int fixed_iterations);
+
+// ---- shared by the operator files: pointops.hip (a caller's cloud), dynpts.hip (DynamicPoints), ops.hip (the resident map) ----
+// A 4 x 4 (col-major) as a kernel ARGUMENT: the matrix rides in the kernarg segment (scalar loads), no device copy of it and no upload
+// launch in front of the kernel that reads it (r5: the map-update chain uploaded four matrices per update, one copy kernel each).
+struct Mat16 { float v[16]; };
+static inline Mat16 mat16(const float T[16]) { Mat16 m; memcpy(m.v, T, sizeof m.v); return m; }
+// `dists(i) >= std::pow(minDistNewPoint, 2)` (PointDistanceMapperModule.cpp:42): std::pow(float, int) is evaluated in
+// double and the float distance is promoted for the comparison.  The product of two floats is exact in double.
+inline double pd_limit(float min_dist) { return (double)min_dist * (double)min_dist; }
+// squared search radius that is guaranteed to return every neighbour with d2 < limit (the smallest float >= limit)
+inline float pd_radius2(double lim) { float r = (float)lim; if ((double)r < lim) r = nextafterf(r, INFINITY); return r; }
+// helper: a private handle on the same device/stream used to index an arbitrary cloud without
+// disturbing the ICP map of the caller's handle
+// The private handle lives as long as its owner (created on first use, destroyed by icpmi_destroy): its buffers are
+// reused from call to call instead of ~20 hipMalloc / hipFree pairs per operator call.
+struct TempCtx {
+    icpmi_handle h = nullptr;
+};
+icpmi_status make_temp(icpmi_ctx* c, TempCtx& t);
+void share_stream(icpmi_ctx* c, icpmi_ctx* t); // the private handle t enqueues on its owner's stream from here on
+icpmi_status check_rigid(icpmi_ctx* c, const float T[16]); // Transformation::checkParameters
+void launch_normals(hipStream_t stream, const float4* map, const int* sidx, int64_t m, int k, float* normals3, float* densities, int dim2,
+                    float* mean_dist = nullptr, float* eig_values = nullptr, float* eig_vectors = nullptr, const unsigned* list = nullptr);
+template <typename T> // uint8_t (a host mask) or unsigned (device compaction): instantiated in pointops.hip
+icpmi_status voxel_flags_dev(icpmi_ctx* c, const float4* d_in, int64_t n, float edge, int method, T* d_keep);
+icpmi_status ops_move_dev(icpmi_ctx* c, const float T[16], float4* d_pts, float* d_n3, int64_t m);
+icpmi_status dynpts_dev(icpmi_ctx* c, const icpmi_dynpts_params* prm, const float T[16], const float4* d_in, int64_t n,
+                        const float4* d_map, const float* d_nrm, int64_t m, float* d_prob, hipStream_t stream);
+bool dynpts_side_ok(const icpmi_dynpts_params* prm);
 
 icpmi_status ops_transform(icpmi_ctx* c, const float T[16], const float* in4, int64_t n, float* out4,
                            const float* in_n3, float* out_n3);

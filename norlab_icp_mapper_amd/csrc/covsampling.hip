@@ -31,7 +31,7 @@ struct CsDev {
     int exhausted;       // the greedy loop found a list without an unselected point (cannot happen for nbSample < N)
 };
 
-__device__ __forceinline__ bool cs_finite(float v) { return fabsf(v) <= 3.402823466e38f; }
+__device__ __forceinline__ bool cs_finite(float v) { return finite_within(v, 3.402823466e38f); }
 
 // v = [ s ((p - c) x n) ; n ] in double, in the order of the formulation
 __device__ __forceinline__ void cs_vec(const float4 p, const float* __restrict__ nrm, int64_t i, const double* c, double s, double (&v)[6])

@@ -17,10 +17,9 @@ namespace {
 constexpr int NN_BLOCK = 256;
 
 typedef __attribute__((address_space(1))) unsigned gunsigned;
-// sqrt for pruning radii and level choices: one v_sqrt_f32 (1 ulp) instead of the IEEE-exact sequence (~12 instructions, and the
-// kernels take it per row), nudged UP by 2^-21 relative so that it never under-estimates -- a bound that is a hair too wide only
-// ever adds candidates, it cannot change the exact minimum
-__device__ __forceinline__ float sqrt_up(float x) { return __builtin_amdgcn_sqrtf(x) * 1.0000005f; }
+// sqrt for pruning radii and level choices (common.h: sqrt_up): one v_sqrt_f32 (1 ulp) instead of the IEEE-exact sequence (~12
+// instructions, and the kernels take it per row), nudged UP by 2^-21 relative so that it never under-estimates -- a bound that is a hair
+// too wide only ever adds candidates, it cannot change the exact minimum
 typedef float vf4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(1))) vf4 gfloat4; // 16 bytes in global memory (global_load, not flat_load)
 

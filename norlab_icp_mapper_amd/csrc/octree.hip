@@ -24,47 +24,17 @@ namespace {
 
 struct OctRoot { float cx, cy, cz, radius; int depth; int pad[3]; };
 
-constexpr int OB = 256;
-
-__global__ __launch_bounds__(OB) void oct_bbox_kernel(const float4* __restrict__ pts, int64_t n, float* __restrict__ part)
-{
-    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-    for (int64_t i = (int64_t)blockIdx.x * OB + threadIdx.x; i < n; i += (int64_t)gridDim.x * OB) {
-        const float4 p = pts[i];
-        lo[0] = fminf(lo[0], p.x); lo[1] = fminf(lo[1], p.y); lo[2] = fminf(lo[2], p.z);
-        hi[0] = fmaxf(hi[0], p.x); hi[1] = fmaxf(hi[1], p.y); hi[2] = fmaxf(hi[2], p.z);
-    }
-    __shared__ float sl[3][OB], sh[3][OB];
-    const int t = threadIdx.x;
-    for (int r = 0; r < 3; ++r) { sl[r][t] = lo[r]; sh[r][t] = hi[r]; }
-    __syncthreads();
-    for (int s = OB / 2; s > 0; s >>= 1) {
-        if (t < s)
-            for (int r = 0; r < 3; ++r) { sl[r][t] = fminf(sl[r][t], sl[r][t + s]); sh[r][t] = fmaxf(sh[r][t], sh[r][t + s]); }
-        __syncthreads();
-    }
-    if (t == 0) for (int r = 0; r < 3; ++r) { part[6 * blockIdx.x + r] = sl[r][0]; part[6 * blockIdx.x + 3 + r] = sh[r][0]; }
-}
-
-__global__ __launch_bounds__(OB) void oct_root_kernel(const float* __restrict__ part, int nb, float max_size, OctRoot* __restrict__ root,
+// one workgroup: the blocks' partials (common.h: bbox_partials_kernel) -> the root cube and the depth of the tree
+__global__ __launch_bounds__(BBOX_WG) void oct_root_kernel(const float* __restrict__ part, int nb, float max_size, OctRoot* __restrict__ root,
                                                       OctRoot* __restrict__ root_host /* host-mapped copy, may be null */, int tag)
 {
-    __shared__ float sl[3][OB], sh[3][OB];
-    const int t = threadIdx.x;
-    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-    for (int b = t; b < nb; b += OB)
-        for (int r = 0; r < 3; ++r) { lo[r] = fminf(lo[r], part[6 * b + r]); hi[r] = fmaxf(hi[r], part[6 * b + 3 + r]); }
-    for (int r = 0; r < 3; ++r) { sl[r][t] = lo[r]; sh[r][t] = hi[r]; }
-    __syncthreads();
-    for (int s = OB / 2; s > 0; s >>= 1) {
-        if (t < s)
-            for (int r = 0; r < 3; ++r) { sl[r][t] = fminf(sl[r][t], sl[r][t + s]); sh[r][t] = fmaxf(sh[r][t], sh[r][t + s]); }
-        __syncthreads();
-    }
-    if (t == 0) {
+    float lo[3], hi[3];
+    unsigned unused;
+    bbox_fold<false>(part, nullptr, nb, lo, hi, unused);
+    if (threadIdx.x == 0) {
         float c[3], radius = 0.f;
         // upstream's Octree_::build: radii = max - min; centre = min + radii * 0.5; maxRadius = max(radii) * 0.5 (the oracle's rule, r3)
-        for (int r = 0; r < 3; ++r) { const float ext = sh[r][0] - sl[r][0]; c[r] = sl[r][0] + ext * 0.5f; const float rr = ext * 0.5f; if (rr > radius) radius = rr; }
+        for (int r = 0; r < 3; ++r) { const float ext = hi[r] - lo[r]; c[r] = lo[r] + ext * 0.5f; const float rr = ext * 0.5f; if (rr > radius) radius = rr; }
         int d = 0;
         float rad = radius;
         while (d < 21 && !(rad * 2.f <= max_size)) { rad *= 0.5f; ++d; } // the first depth whose edge is <= maxSizeByNode
@@ -238,7 +208,6 @@ __global__ __launch_bounds__(256) void oct_leaf_kernel(const unsigned long long*
     flag[j] = start ? 1u : 0u;
 }
 
-__device__ __forceinline__ unsigned fmix32_dev(unsigned h) { h ^= h >> 16; h *= 0x85ebca6bu; h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16; return h; }
 
 // ordinal[j] = exclusive scan of flag: leaf number of the leaf starting at j, or of the next one; leaf of j = ordinal[j] + flag[j] - 1
 __global__ __launch_bounds__(256) void oct_pick_kernel(const unsigned* __restrict__ vals, const unsigned* __restrict__ flag,
@@ -252,7 +221,7 @@ __global__ __launch_bounds__(256) void oct_pick_kernel(const unsigned* __restric
     if (leaf_of) leaf_of[vals[j]] = (int)leaf;
     // the representative of a leaf: the smallest original index (a leaf shallower than D holds points of different paths, so
     // the first of its sorted run is not necessarily the first of upstream's list), or the smallest hash of it
-    const unsigned long long rank = method == 0 ? 0ull : (unsigned long long)fmix32_dev(vals[j]);
+    const unsigned long long rank = method == 0 ? 0ull : (unsigned long long)fmix32(vals[j]);
     atomicMin(&best[leaf], (rank << 32) | (unsigned long long)vals[j]);
 }
 
@@ -324,9 +293,9 @@ icpmi_status octree_sample_dev(icpmi_ctx* c, const float4* d_in, int64_t n, floa
     // copy launch.  A wrong guess repeats paths + sort with the right depth (tests/test_gpu_octree.py forces one).
     OctRoot* d_root_host = c->d_progress ? reinterpret_cast<OctRoot*>(c->d_progress + ICPMI_PROGRESS_OCT_WORD) : nullptr;
     const volatile OctRoot* h_root = c->h_progress ? reinterpret_cast<const volatile OctRoot*>(c->h_progress + ICPMI_PROGRESS_OCT_WORD) : nullptr;
-    hipLaunchKernelGGL(oct_bbox_kernel, dim3(rb), dim3(OB), 0, c->stream, d_in, n, d_part);
+    hipLaunchKernelGGL(bbox_partials_kernel<false>, dim3(rb), dim3(BBOX_WG), 0, c->stream, d_in, n, d_part, (unsigned*)nullptr, 0.f);
     const int root_tag = ++c->oct_tag ? c->oct_tag : ++c->oct_tag;
-    hipLaunchKernelGGL(oct_root_kernel, dim3(1), dim3(OB), 0, c->stream, (const float*)d_part, rb, max_size, d_root, d_root_host, root_tag);
+    hipLaunchKernelGGL(oct_root_kernel, dim3(1), dim3(BBOX_WG), 0, c->stream, (const float*)d_part, rb, max_size, d_root, d_root_host, root_tag);
     HIP_TRY(c, hipGetLastError());
     int depth = (h_root && c->oct_depth_hint > 0) ? c->oct_depth_hint : -1;
     if (depth < 0) {

@@ -1,609 +1,14 @@
-// ops.hip -- the map-side operators of the path that are not part of the ICP iteration itself:
-//   RigidTransformation::compute            (Mapper.cpp:197,221; Map.cpp:523,525)
-//   SurfaceNormalDataPointsFilter           (Map.cpp:524 through examples/config.yaml:26-27)
-//   PointDistanceMapperModule keep mask     (MapperModules/PointDistanceMapperModule.cpp:28-50)
-//   Map::unloadCells cell binning           (Map.cpp:206-209,232-235)
+// ops.hip -- the operators on the handle's RESIDENT map (c->d_raw and its companions), none of them part of the ICP iteration itself:
+//   the append-only update (PointDistanceMapperModule + SurfaceNormalDataPointsFilter + icp.setMap, Map.cpp:502-534),
+//   Map::updateLocalPointCloud as one program over the resident arrays (the operator chain),
+//   the map-growth epoch of the scan-sharded mapper (accept, exchange, rank-ordered merge, append).
+// The stateless operators on a caller's cloud are in pointops.hip, the DynamicPoints module in dynpts.hip; both are reached through the
+// declarations next to the ops_* block in common.h.
 #include "common.h"
 #include <chrono>
 #include <utility>
-#include <cstring>
 
 namespace {
-
-// `dists(i) >= std::pow(minDistNewPoint, 2)` (PointDistanceMapperModule.cpp:42): std::pow(float, int) is evaluated in
-// double and the float distance is promoted for the comparison.  The product of two floats is exact in double.
-inline double pd_limit(float min_dist) { return (double)min_dist * (double)min_dist; }
-// squared search radius that is guaranteed to return every neighbour with d2 < limit (the smallest float >= limit)
-inline float pd_radius2(double lim) { float r = (float)lim; if ((double)r < lim) r = nextafterf(r, INFINITY); return r; }
-
-// A 4 x 4 (col-major) as a kernel ARGUMENT: the matrix rides in the kernarg segment (scalar loads), no device copy of it and no upload
-// launch in front of the kernel that reads it (r5: the map-update chain uploaded four matrices per update, one copy kernel each).
-struct Mat16 { float v[16]; };
-static inline Mat16 mat16(const float T[16]) { Mat16 m; memcpy(m.v, T, sizeof m.v); return m; }
-
-__global__ __launch_bounds__(256) void transform_kernel(const float4* __restrict__ in, int64_t n, Mat16 M, float4* __restrict__ out)
-{
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const float* T = M.v;
-    const float4 p = in[i];
-    const float3 o = xf_point(T, p.x, p.y, p.z, p.w);
-    const float w = fmaf(T[15], p.w, fmaf(T[11], p.z, fmaf(T[7], p.y, T[3] * p.x)));
-    out[i] = make_float4(o.x, o.y, o.z, w);
-}
-
-__global__ __launch_bounds__(256) void rotate3_kernel(const float* __restrict__ in3, int64_t n, Mat16 M, float* __restrict__ out3)
-{
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const float* T = M.v;
-    const float x = in3[3 * i], y = in3[3 * i + 1], z = in3[3 * i + 2];
-    out3[3 * i] = fmaf(T[8], z, fmaf(T[4], y, T[0] * x));
-    out3[3 * i + 1] = fmaf(T[9], z, fmaf(T[5], y, T[1] * x));
-    out3[3 * i + 2] = fmaf(T[10], z, fmaf(T[6], y, T[2] * x));
-}
-
-// RigidTransformation::compute on a whole resident cloud, in place: features by T and -- n3 != nullptr -- normals by its rotation, one
-// launch (the arithmetic of transform_kernel and rotate3_kernel, element for element)
-__global__ __launch_bounds__(256) void move_kernel(float4* __restrict__ pts, float* __restrict__ n3, int64_t n, Mat16 M)
-{
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const float* T = M.v;
-    const float4 p = pts[i];
-    const float3 o = xf_point(T, p.x, p.y, p.z, p.w);
-    const float w = fmaf(T[15], p.w, fmaf(T[11], p.z, fmaf(T[7], p.y, T[3] * p.x)));
-    pts[i] = make_float4(o.x, o.y, o.z, w);
-    if (n3) {
-        const float x = n3[3 * i], y = n3[3 * i + 1], z = n3[3 * i + 2];
-        n3[3 * i] = fmaf(T[8], z, fmaf(T[4], y, T[0] * x));
-        n3[3 * i + 1] = fmaf(T[9], z, fmaf(T[5], y, T[1] * x));
-        n3[3 * i + 2] = fmaf(T[10], z, fmaf(T[6], y, T[2] * x));
-    }
-}
-
-__global__ __launch_bounds__(256) void bin_kernel(const float4* __restrict__ in, int64_t n, float cell, int* __restrict__ ijk)
-{
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const float4 p = in[i];
-    ijk[3 * i] = (int)floorf(p.x / cell);
-    ijk[3 * i + 1] = (int)floorf(p.y / cell);
-    ijk[3 * i + 2] = (int)floorf(p.z / cell);
-}
-
-__global__ __launch_bounds__(256) void keep_kernel(const float* __restrict__ d2, int64_t n, double lim, uint8_t* __restrict__ keep)
-{
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    keep[i] = (double)d2[i] >= lim ? 1 : 0; // `dists(i) >= std::pow(minDistNewPoint, 2)`: a double comparison (PointDistanceMapperModule.cpp:42)
-}
-
-// one lane per point: mean + covariance of the kNN set in double, smallest eigenvector by Jacobi
-// densities (may be null): `keepDensities` of the filter -- points per volume of the sphere that holds the neighbourhood around
-// its centroid: k / (4/3 pi r^3), r = the largest distance of a neighbour from the centroid (computeDensity)
-// mean_dist (may be null): `keepMeanDist` -- distance from the point to the mean of its neighbours.  The point is read as its own first
-// neighbour (d2 = 0 sorts first; a duplicate that wins the index tie has the same coordinates), which keeps it in the index's centred frame.
-// KMAX > 0 (k <= KMAX; r5): the row of neighbour ids and the k neighbours are requested up front -- two round trips -- and both passes (mean,
-// scatter matrix) run from registers in the same order; the generic variant (KMAX = 0: any k) walks them one dependent load after the other,
-// twice.  Same sums in the same order: same bits.
-template <int KMAX>
-__global__ __launch_bounds__(128) void normals_kernel(const float4* __restrict__ map, const int* __restrict__ sidx, int64_t m, int k,
-                                                      float* __restrict__ normals3, float* __restrict__ densities, int dim2,
-                                                      float* __restrict__ mean_dist = nullptr, float* __restrict__ eig_values = nullptr,
-                                                      float* __restrict__ eig_vectors = nullptr, const unsigned* __restrict__ list = nullptr)
-{
-    // list (r6): an appended cloud -- m entries, the points whose neighbourhood was searched again (surface_normals_dev); otherwise all m points
-    const int64_t t = (int64_t)blockIdx.x * 128 + threadIdx.x;
-    if (t >= m) return;
-    const int64_t i = list ? (int64_t)list[t] : t;
-    // (r2: walking the points in cell-sorted order instead -- coherent neighbour gathers, scattered row reads and normal
-    // writes -- measured 108 -> 164 us on the octree-ordered 0.9 M-point map and within noise on an append-ordered one: kept
-    // in the caller's order)
-    double mean[3] = {0, 0, 0};
-    int real = 0;
-    double c00 = 0, c01 = 0, c02 = 0, c11 = 0, c12 = 0, c22 = 0, rmax2 = 0;
-    float4 p0 = make_float4(0.f, 0.f, 0.f, 0.f); // the point itself (its own first neighbour), or map[0] where the row starts with "none"
-    if constexpr (KMAX > 0) {
-        int sv[KMAX];
-        float4 qv[KMAX];
-#pragma unroll
-        for (int j = 0; j < KMAX; ++j) sv[j] = j < k ? sidx[(size_t)k * i + j] : -1;
-#pragma unroll
-        for (int j = 0; j < KMAX; ++j) qv[j] = map[sv[j] < 0 ? 0 : sv[j]];
-#pragma unroll
-        for (int j = 0; j < KMAX; ++j)
-            if (sv[j] >= 0) { mean[0] += qv[j].x; mean[1] += qv[j].y; mean[2] += qv[j].z; ++real; }
-        const double inv = 1.0 / (real > 0 ? real : 1);
-        mean[0] *= inv; mean[1] *= inv; mean[2] *= inv;
-#pragma unroll
-        for (int j = 0; j < KMAX; ++j)
-            if (sv[j] >= 0) {
-                const double x = qv[j].x - mean[0], y = qv[j].y - mean[1], z = qv[j].z - mean[2];
-                c00 += x * x; c01 += x * y; c02 += x * z; c11 += y * y; c12 += y * z; c22 += z * z;
-                const double r2 = x * x + y * y + z * z;
-                rmax2 = r2 > rmax2 ? r2 : rmax2;
-            }
-        p0 = qv[0];
-    } else {
-        for (int j = 0; j < k; ++j) {
-            const int s = sidx[(size_t)k * i + j];
-            if (s < 0) continue;
-            const float4 q = map[s];
-            mean[0] += q.x; mean[1] += q.y; mean[2] += q.z; ++real;
-        }
-        const double inv = 1.0 / (real > 0 ? real : 1);
-        mean[0] *= inv; mean[1] *= inv; mean[2] *= inv;
-        for (int j = 0; j < k; ++j) {
-            const int s = sidx[(size_t)k * i + j];
-            if (s < 0) continue;
-            const float4 q = map[s];
-            const double x = q.x - mean[0], y = q.y - mean[1], z = q.z - mean[2];
-            c00 += x * x; c01 += x * y; c02 += x * z; c11 += y * y; c12 += y * z; c22 += z * z;
-            const double r2 = x * x + y * y + z * z;
-            rmax2 = r2 > rmax2 ? r2 : rmax2;
-        }
-        if (mean_dist) { const int s0 = sidx[(size_t)k * i]; p0 = map[s0 < 0 ? 0 : s0]; }
-    }
-    if (densities) {
-        const double r = sqrt(rmax2);
-        densities[i] = (float)((double)real / ((4.0 / 3.0) * 3.14159265358979323846 * (r * r * r)));
-    }
-    if (mean_dist) {
-        const double x = p0.x - mean[0], y = p0.y - mean[1], z = p0.z - mean[2];
-        mean_dist[i] = (float)sqrt(x * x + y * y + z * z);
-    }
-    // cyclic Jacobi on the symmetric 3x3
-    double A[3][3] = {{c00, c01, c02}, {c01, c11, c12}, {c02, c12, c22}};
-    double Q[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
-    for (int sweep = 0; sweep < 30; ++sweep) {
-        const double off = A[0][1] * A[0][1] + A[0][2] * A[0][2] + A[1][2] * A[1][2];
-        const double dg = A[0][0] * A[0][0] + A[1][1] * A[1][1] + A[2][2] * A[2][2];
-        if (off <= 1e-32 * dg || off < 1e-300) break;
-#pragma unroll
-        for (int p = 0; p < 2; ++p)
-#pragma unroll
-            for (int q = p + 1; q < 3; ++q) {
-                const double apq = A[p][q];
-                if (apq == 0.0) continue;
-                const double theta = (A[q][q] - A[p][p]) / (2.0 * apq);
-                const double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-                const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-#pragma unroll
-                for (int kk = 0; kk < 3; ++kk) {
-                    const double akp = A[kk][p], akq = A[kk][q];
-                    A[kk][p] = c * akp - s * akq; A[kk][q] = s * akp + c * akq;
-                }
-#pragma unroll
-                for (int kk = 0; kk < 3; ++kk) {
-                    const double apk = A[p][kk], aqk = A[q][kk];
-                    A[p][kk] = c * apk - s * aqk; A[q][kk] = s * apk + c * aqk;
-                }
-#pragma unroll
-                for (int kk = 0; kk < 3; ++kk) {
-                    const double qkp = Q[kk][p], qkq = Q[kk][q];
-                    Q[kk][p] = c * qkp - s * qkq; Q[kk][q] = s * qkp + c * qkq;
-                }
-            }
-    }
-    const double w0 = A[0][0], w1 = A[1][1], w2 = A[2][2];
-    const double wmax = fmax(fabs(w0), fmax(fabs(w1), fabs(w2)));
-    const double thr = 3.0 * 1.1920928955078125e-07 * wmax;
-    const int rank = (wmax > 0) ? ((fabs(w0) > thr) + (fabs(w1) > thr) + (fabs(w2) > thr)) : 0;
-    if ((eig_values || eig_vectors) && !dim2) {
-        // keepEigenValues / keepEigenVectors with sortEigen: 1 (r5): eigenvalues of the scatter matrix ascending (the exchange sort (0,1) (0,2)
-        // (1,2), strict), serializeEigVec of the eigenvector matrix in that column order -- entry 3 k + j = component k of eigenvector j;
-        // rank < 2: upstream's degenerate answer (zeros, identity).  Static indices only (no scratch).
-        double e0 = w0, e1 = w1, e2 = w2;
-        int o0 = 0, o1 = 1, o2 = 2;
-        if (rank >= 2) {
-            if (e1 < e0) { const double t = e0; e0 = e1; e1 = t; const int u = o0; o0 = o1; o1 = u; }
-            if (e2 < e0) { const double t = e0; e0 = e2; e2 = t; const int u = o0; o0 = o2; o2 = u; }
-            if (e2 < e1) { const double t = e1; e1 = e2; e2 = t; const int u = o1; o1 = o2; o2 = u; }
-        }
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            const int oj = j == 0 ? o0 : (j == 1 ? o1 : o2);
-            const double wj = j == 0 ? e0 : (j == 1 ? e1 : e2);
-            if (eig_values) eig_values[3 * i + j] = rank >= 2 ? (float)wj : 0.f;
-            if (eig_vectors) {
-#pragma unroll
-                for (int kk = 0; kk < 3; ++kk) {
-                    const double q = oj == 0 ? Q[kk][0] : (oj == 1 ? Q[kk][1] : Q[kk][2]);
-                    eig_vectors[9 * i + 3 * kk + j] = rank >= 2 ? (float)q : (kk == j ? 1.f : 0.f);
-                }
-            }
-        }
-    }
-    float nx = 1.f, ny = 0.f, nz = 0.f; // upstream's degenerate answer: eigenvectors = identity
-    if (dim2) {
-        // planar cloud (z == 0: the rotations with the z axis saw zero off-diagonals): the smaller eigenvector of the plane's pair;
-        // upstream needs rank + 1 >= featDim - 1 = 2 there, i.e. rank >= 1
-        const double wm2 = fmax(fabs(w0), fabs(w1));
-        const double thr2 = 2.0 * 1.1920928955078125e-07 * wm2;
-        const int rank2 = (wm2 > 0) ? ((fabs(w0) > thr2) + (fabs(w1) > thr2)) : 0;
-        if (rank2 >= 1) {
-            const int e2 = w1 < w0 ? 1 : 0;
-            nx = (float)(e2 == 0 ? Q[0][0] : Q[0][1]);
-            ny = (float)(e2 == 0 ? Q[1][0] : Q[1][1]);
-            nz = 0.f;
-        }
-    } else if (rank >= 2) {
-        int e = 0;
-        double wm = w0;
-        if (w1 < wm) { wm = w1; e = 1; }
-        if (w2 < wm) { wm = w2; e = 2; }
-        nx = (float)(e == 0 ? Q[0][0] : (e == 1 ? Q[0][1] : Q[0][2]));
-        ny = (float)(e == 0 ? Q[1][0] : (e == 1 ? Q[1][1] : Q[1][2]));
-        nz = (float)(e == 0 ? Q[2][0] : (e == 1 ? Q[2][1] : Q[2][2]));
-    }
-    normals3[3 * i] = nx; normals3[3 * i + 1] = ny; normals3[3 * i + 2] = nz;
-}
-
-// k <= 10 (the shipped SurfaceNormalDataPointsFilter{knn: 10}) and k <= 16 keep the neighbourhood in registers; ICPMI_NORMALS_REG=0: the generic walk
-static void launch_normals(hipStream_t stream, const float4* map, const int* sidx, int64_t m, int k, float* normals3, float* densities, int dim2,
-                           float* mean_dist = nullptr, float* eig_values = nullptr, float* eig_vectors = nullptr, const unsigned* list = nullptr)
-{
-    constexpr int reg = 1;
-    const dim3 grid((int)((m + 127) / 128)), block(128);
-    if (reg && k <= 10) hipLaunchKernelGGL(normals_kernel<10>, grid, block, 0, stream, map, sidx, m, k, normals3, densities, dim2, mean_dist, eig_values, eig_vectors, list);
-    else if (reg && k <= 16) hipLaunchKernelGGL(normals_kernel<16>, grid, block, 0, stream, map, sidx, m, k, normals3, densities, dim2, mean_dist, eig_values, eig_vectors, list);
-    else hipLaunchKernelGGL(normals_kernel<0>, grid, block, 0, stream, map, sidx, m, k, normals3, densities, dim2, mean_dist, eig_values, eig_vectors, list);
-}
-
-// ---- fused input filters (Mapper::applyInputFilters): one predicate pass for a run of DistanceLimit / BoundingBox filters ----
-struct FilterPack { icpmi_point_filter f[ICPMI_MAX_POINT_FILTERS]; int n; };
-
-__global__ __launch_bounds__(256) void filter_points_kernel(const float4* __restrict__ in, int64_t n, FilterPack fp, uint8_t* __restrict__ keep)
-{
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const float4 p = in[i];
-    bool ok = true;
-    for (int k = 0; k < fp.n; ++k) {
-        const icpmi_point_filter& f = fp.f[k];
-        if (f.type == ICPMI_FILT_DISTANCE_LIMIT) {
-            // sqrtf of the sum in the oracle's order (no contraction: -ffp-contract=off on both sides)
-            const float v = f.i < 0 ? sqrtf(p.x * p.x + p.y * p.y + p.z * p.z) : fabsf(f.i == 0 ? p.x : (f.i == 1 ? p.y : p.z));
-            const float ad = fabsf(f.f[0]);
-            ok &= f.f[1] != 0.f ? v > ad : v < ad;
-        } else {
-            const bool inside = p.x > f.f[0] && p.x < f.f[3] && p.y > f.f[1] && p.y < f.f[4] && p.z > f.f[2] && p.z < f.f[5];
-            ok &= f.i ? !inside : inside;
-        }
-    }
-    keep[i] = ok ? 1 : 0;
-}
-
-// ---- fused sensor-model filters (include/icpmi.h: icpmi_sensor_model): ObservationDirection / OrientNormals / Shadow /
-// SimpleSensorNoise as one program per point; od, n, keep and noise stay in registers across the steps ----
-struct SensorPack {
-    icpmi_sensor_step s[ICPMI_MAX_SENSOR_STEPS]; int n;
-    int read_n, write_n, read_od, write_od; // which of the in/out rows the program touches
-};
-
-// n3 / od3 are read and written in place by the thread that owns the point (no __restrict__: the same buffer both ways).
-// No contraction (-ffp-contract=off): every product, sum, division and sqrtf below is one correctly rounded float32 operation.
-__global__ __launch_bounds__(256) void sensor_model_kernel(const float4* __restrict__ in, int64_t n, SensorPack sp, float* n3, float* od3,
-                                                           float* __restrict__ noise_out, uint8_t* __restrict__ keep_out)
-{
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const float4 p = in[i];
-    float nx = 0.f, ny = 0.f, nz = 0.f, ox = 0.f, oy = 0.f, oz = 0.f, noise = 0.f;
-    if (sp.read_n) { nx = n3[3 * i]; ny = n3[3 * i + 1]; nz = n3[3 * i + 2]; }
-    if (sp.read_od) { ox = od3[3 * i]; oy = od3[3 * i + 1]; oz = od3[3 * i + 2]; }
-    bool keep = true;
-    for (int k = 0; k < sp.n; ++k) {
-        const icpmi_sensor_step& s = sp.s[k];
-        if (s.type == ICPMI_SM_OBSERVATION_DIRECTION) {
-            ox = s.f[0] - p.x; oy = s.f[1] - p.y; oz = s.f[2] - p.z;
-        } else if (s.type == ICPMI_SM_ORIENT_NORMALS) {
-            const float d = nx * ox + ny * oy + nz * oz;
-            if (s.i ? d < 0.f : d > 0.f) { nx = -nx; ny = -ny; nz = -nz; }
-        } else if (s.type == ICPMI_SM_SHADOW) {
-            const float ln = sqrtf(nx * nx + ny * ny + nz * nz), lp = sqrtf(p.x * p.x + p.y * p.y + p.z * p.z);
-            const float v = fabsf((nx / ln) * (p.x / lp) + (ny / ln) * (p.y / lp) + (nz / ln) * (p.z / lp));
-            keep = keep && v > s.f[0]; // (a NaN compares false: dropped)
-        } else {
-            const float dist = sqrtf(p.x * p.x + p.y * p.y + p.z * p.z), gain = s.f[0];
-            if (s.i <= 2) {
-                const float min_radius = s.i == 0 ? 0.012f : (s.i == 1 ? 0.028f : 0.018f);
-                const float beam_angle = s.i == 0 ? 0.0068f : (s.i == 1 ? 0.0013f : 0.0006f);
-                const float beam_const = s.i == 0 ? 0.0008f : (s.i == 1 ? 0.0001f : 0.0015f);
-                const float t = beam_angle * dist + beam_const;
-                noise = gain * (t > min_radius ? t : min_radius);
-            } else {
-                noise = ((gain * 0.5f) * 0.00285f) * (dist * dist);
-            }
-        }
-    }
-    if (sp.write_n) { n3[3 * i] = nx; n3[3 * i + 1] = ny; n3[3 * i + 2] = nz; }
-    if (sp.write_od) { od3[3 * i] = ox; od3[3 * i + 1] = oy; od3[3 * i + 2] = oz; }
-    if (noise_out) noise_out[i] = noise;
-    if (keep_out) keep_out[i] = keep ? 1 : 0;
-}
-
-// ---- voxel sub-sample (OctreeMapperModule / OctreeGridDataPointsFilter stand-in, samplingMethod 0) ----
-// lattice anchored at the bounding-box minimum; voxel index floor((p - lo) / edge) per axis, 21 bits
-// each; the representative of a voxel is its point of smallest original index (order independent:
-// atomicMin), so the keep mask is a function of the input alone.
-__device__ __forceinline__ unsigned fkey(float f) { const unsigned u = __float_as_uint(f); return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }
-__device__ __forceinline__ float fkey_inv(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
-
-__global__ __launch_bounds__(256) void bbox_min_kernel(const float4* __restrict__ in, int64_t n, unsigned* __restrict__ lo_keys)
-{
-    __shared__ unsigned sh[3][4];
-    unsigned kx = 0xffffffffu, ky = 0xffffffffu, kz = 0xffffffffu;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-        const float4 p = in[i];
-        kx = min(kx, fkey(p.x)); ky = min(ky, fkey(p.y)); kz = min(kz, fkey(p.z));
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        kx = min(kx, (unsigned)__shfl_xor((int)kx, off, 64));
-        ky = min(ky, (unsigned)__shfl_xor((int)ky, off, 64));
-        kz = min(kz, (unsigned)__shfl_xor((int)kz, off, 64));
-    }
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (lane == 0) { sh[0][w] = kx; sh[1][w] = ky; sh[2][w] = kz; }
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        const unsigned v = min(min(sh[threadIdx.x][0], sh[threadIdx.x][1]), min(sh[threadIdx.x][2], sh[threadIdx.x][3]));
-        atomicMin(&lo_keys[threadIdx.x], v);
-    }
-}
-
-__device__ __forceinline__ unsigned long long voxel_key(const float4 p, const unsigned* __restrict__ lo_keys, float edge)
-{
-    const float lo[3] = {fkey_inv(lo_keys[0]), fkey_inv(lo_keys[1]), fkey_inv(lo_keys[2])};
-    const float c[3] = {p.x, p.y, p.z};
-    unsigned long long key = 0;
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-        const float v = fminf(floorf((c[r] - lo[r]) / edge), 2097151.0f);
-        key = key * 2097152ull + (unsigned long long)v;
-    }
-    return key;
-}
-
-__device__ __forceinline__ unsigned long long mix64(unsigned long long x)
-{
-    x ^= x >> 33; x *= 0xff51afd7ed558ccdull; x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ull; x ^= x >> 33;
-    return x;
-}
-
-// MurmurHash3's 32-bit finaliser: a bijection of the 32-bit integers, so "smallest hash" names exactly one point
-__device__ __forceinline__ unsigned fmix32(unsigned h)
-{
-    h ^= h >> 16; h *= 0x85ebca6bu; h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16;
-    return h;
-}
-
-__global__ __launch_bounds__(256) void voxel_insert_kernel(const float4* __restrict__ in, int64_t n, const unsigned* __restrict__ lo_keys,
-                                                           float edge, int method, unsigned long long* __restrict__ tkeys,
-                                                           unsigned* __restrict__ tvals, unsigned long long mask,
-                                                           unsigned* __restrict__ slot_of)
-{
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const unsigned long long key = voxel_key(in[i], lo_keys, edge);
-    unsigned long long slot = mix64(key) & mask;
-    for (;;) {
-        const unsigned long long prev = atomicCAS(&tkeys[slot], ~0ull, key);
-        if (prev == ~0ull || prev == key) break;
-        slot = (slot + 1) & mask;
-    }
-    atomicMin(&tvals[slot], method ? fmix32((unsigned)i) : (unsigned)i);
-    slot_of[i] = (unsigned)slot;
-}
-
-// flag[i] = 1 iff i represents its voxel (T = uint8_t for the host mask, unsigned for device compaction)
-template <typename T>
-__global__ __launch_bounds__(256) void voxel_keep_kernel(int64_t n, const unsigned* __restrict__ tvals, const unsigned* __restrict__ slot_of,
-                                                         int method, T* __restrict__ keep)
-{
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    keep[i] = tvals[slot_of[i]] == (method ? fmix32((unsigned)i) : (unsigned)i) ? 1 : 0;
-}
-
-// ---- DynamicPointsMapperModule::inPlaceUpdateMap (DynamicPointsMapperModule.cpp:34-172) -------------------
-// Beams = input points in the sensor frame as (elevation, azimuth); every in-range map point looks up
-// its angularly nearest beam within 2 * beamHalfAngle (the reference builds a 2-D kd-tree per call,
-// :75-78; here: a bucket grid of that cell size built by counting sort, 3 x 3 cells per query, ties to
-// the smallest beam index) and updates its probability of being dynamic (:97-148).
-// asin / atan2 go through double and are rounded once (shared with the oracle: libm and the device
-// library then agree bit for bit); everything else is the reference's float arithmetic, with the
-// sub-expressions it writes with a double literal (`1.`) evaluated in double.
-struct DynGrid { float cell; int ne, na; float r2; };   // r2 = (2 beamHalfAngle)^2: the search radius, DYN_RINGS cells wide
-
-__device__ __forceinline__ void to_spherical(float x, float y, float z, float& radius, float& elev, float& azim)
-{
-    radius = sqrtf(x * x + y * y + z * z);
-    elev = (float)asin((double)(z / radius));
-    azim = (float)atan2((double)y, (double)x);
-}
-
-__device__ __forceinline__ int dyn_ecell(const DynGrid& g, float e)
-{
-    const int v = (int)floorf((e + 1.5707963267949f) / g.cell);
-    return v < 0 ? 0 : (v > g.ne - 1 ? g.ne - 1 : v);
-}
-__device__ __forceinline__ int dyn_acell(const DynGrid& g, float a)
-{
-    const int v = (int)floorf((a + 3.14159265358979f) / g.cell);
-    return v < 0 ? 0 : (v > g.na - 1 ? g.na - 1 : v);
-}
-
-// pass 1: beams to the sensor frame + angles + cell counts
-__global__ __launch_bounds__(256) void dyn_beams_kernel(const float4* __restrict__ in, int64_t n, Mat16 M, DynGrid g,
-                                                        float4* __restrict__ beam_xyzn, float2* __restrict__ beam_ang,
-                                                        unsigned* __restrict__ keys, unsigned* __restrict__ count)
-{
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const bool valid = i < n;
-    const float4 p = in[valid ? i : 0];
-    const float3 o = xf_point(M.v, p.x, p.y, p.z, p.w);
-    float radius, elev, azim;
-    to_spherical(o.x, o.y, o.z, radius, elev, azim);
-    const unsigned key = (unsigned)(dyn_ecell(g, elev) * g.na + dyn_acell(g, azim));
-    // a lidar scan is ordered along its beams: neighbours in the array fall into the same bucket, and same-address device atomics
-    // serialise -- one atomic per run of equal keys in the wave (r5; map_build.hip's counting sorts do the same)
-    const WaveRun r = wave_run(key, valid);
-    if (r.head) atomicAdd(&count[key], (unsigned)r.len);
-    if (!valid) return;
-    beam_xyzn[i] = make_float4(o.x, o.y, o.z, radius);
-    beam_ang[i] = make_float2(elev, azim);
-    keys[i] = key;
-}
-
-// pass 2: counting-sort scatter; a bucket entry is ONE 16-byte record {elevation, azimuth, beam index} (r5: the index used to sit in a second
-// array -- a dependent load per accepted candidate); the buckets of one elevation row are contiguous, so a row of the 3 x 3 block is one run
-__global__ __launch_bounds__(256) void dyn_scatter_kernel(int64_t n, const unsigned* __restrict__ keys, unsigned* __restrict__ cursor /* = starts + 1 */,
-                                                          const float2* __restrict__ beam_ang, float4* __restrict__ sorted_rec)
-{
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const bool valid = i < n;
-    const unsigned key = keys[valid ? i : 0];
-    const float2 a = beam_ang[valid ? i : 0];
-    const WaveRun r = wave_run(key, valid);
-    unsigned base = 0;
-    if (r.head) base = atomicAdd(&cursor[key], (unsigned)r.len);
-    base = (unsigned)__shfl((int)base, r.head_lane, 64);
-    if (!valid) return;
-    sorted_rec[base + (unsigned)r.rank] = make_float4(a.x, a.y, __uint_as_float((unsigned)i), 0.f);
-}
-
-#ifndef DYN_INFLIGHT
-#define DYN_INFLIGHT 4
-#endif
-#ifndef DYN_RINGS
-#define DYN_RINGS 2   // buckets per search radius (1: 3 x 3 block of one-radius buckets, the layout until r4)
-#endif
-struct DynPrm { float threshold_dynamic, alpha, beta, beam_half_angle, epsilon_a, epsilon_d, sensor_max_range; };
-
-__global__ __launch_bounds__(256) void dyn_update_kernel(const float4* __restrict__ map, const float* __restrict__ normals3, int64_t m,
-                                                         Mat16 M, DynGrid g, DynPrm prm,
-                                                         const float4* __restrict__ beam_xyzn, const float4* __restrict__ sorted_rec,
-                                                         const unsigned* __restrict__ start, float* __restrict__ prob)
-{
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= m) return;
-    const float* T = M.v;
-    const float eps = 0.0001f;
-    const float4 mpt = map[i];
-    const float3 mp = xf_point(T, mpt.x, mpt.y, mpt.z, mpt.w);
-    const float mapNorm = sqrtf(mp.x * mp.x + mp.y * mp.y + mp.z * mp.z);
-    if (!(mapNorm < prm.sensor_max_range)) return; // range cull (:60-69)
-    float radius, qe, qa;
-    to_spherical(mp.x, mp.y, mp.z, radius, qe, qa);
-    const int ce = dyn_ecell(g, qe), ca = dyn_acell(g, qa);
-    const float r2 = g.r2;
-    float bd = INFINITY;
-    int best = -1;
-    // The nearest beam within 2 * beamHalfAngle = DYN_RINGS bucket edges: it lies in the (2 R + 1)^2 block of buckets around the point's
-    // own.  The buckets (e, a - R .. a + R) of one elevation row are consecutive keys: the bounds of a row's buckets are 2 R + 2 consecutive
-    // words, and all of them are requested together before anything depends on them (r4 fetched the two bounds of a bucket when it got
-    // there: nine dependent round trips before the ninth bucket's records).  Own bucket first, then ring by ring: where the beams are
-    // dense the nearest one is a fraction of a bucket away, and a bucket whose nearest edge is farther than the best so far cannot hold a
-    // closer beam (nor an equally close one: the test is strict and leaves a margin for the rounding of the cell assignment).  The winner
-    // is the minimum of (angular distance, beam index): independent of the visiting order.
-    // r5: buckets of HALF the radius (R = 2, 5 x 5 block).  With one-radius buckets a point paid for every record of its own bucket before
-    // the pruning could start -- 150 records where a surface is seen at a grazing angle (the synthetic scenes; a spinning lidar's own
-    // returns are uniform in angle); a quarter bucket first, and the ring behind it mostly pruned: search 136 -> see DESIGN 13.2b.
-    // (Scanning whole rows without the per-bucket test -- fewer branches -- looked at 3 - 5 x the records and was slower: 253 vs 225 us.)
-    constexpr int R = DYN_RINGS, W = 2 * R + 1;
-    const float elo = (float)ce * g.cell - 1.5707963267949f, alo = (float)ca * g.cell - 3.14159265358979f;
-    float gapE[W], gapA[W];
-#pragma unroll
-    for (int d = 0; d < W; ++d) {
-        // distance from the query to the nearest edge of the bucket d - R cells away (0 for its own)
-        gapE[d] = d < R ? (qe - elo) + (float)(R - 1 - d) * g.cell : (d == R ? 0.f : (elo + g.cell - qe) + (float)(d - R - 1) * g.cell);
-        gapA[d] = d < R ? (qa - alo) + (float)(R - 1 - d) * g.cell : (d == R ? 0.f : (alo + g.cell - qa) + (float)(d - R - 1) * g.cell);
-    }
-    unsigned sb[W][W + 1];
-#pragma unroll
-    for (int de = 0; de < W; ++de) {
-        const int e = ce + de - R;
-        const bool row = e >= 0 && e < g.ne;
-#pragma unroll
-        for (int x = 0; x <= W; ++x) {
-            int a = ca - R + x;                       // bound x = start of bucket (e, ca - R + x)
-            a = a < 0 ? 0 : (a > g.na ? g.na : a);    // (a == na: the start of the next row's first bucket = the end of this row's last)
-            sb[de][x] = start[row ? (unsigned)(e * g.na + a) : 0u];
-        }
-    }
-#pragma unroll
-    for (int ring = 0; ring <= R; ++ring) {
-#pragma unroll
-        for (int de = 0; de < W; ++de) {
-#pragma unroll
-            for (int da = 0; da < W; ++da) {
-                const int re = de > R ? de - R : R - de, ra = da > R ? da - R : R - da;
-                if ((re > ra ? re : ra) != ring) continue;   // (compile time)
-                const int e = ce + de - R, a = ca + da - R;
-                if (e < 0 || e >= g.ne || a < 0 || a >= g.na) continue;
-                const float ge = fmaxf(gapE[de] - 1e-5f, 0.f), ga = fmaxf(gapA[da] - 1e-5f, 0.f);
-                const float dmin = ge * ge + ga * ga;
-                if (dmin > r2 || dmin > bd) continue;
-                // DYN_INFLIGHT records requested together (r5: one per trip made every record a full memory round trip of the wave's slowest lane)
-                const unsigned jend = sb[de][da + 1];
-                for (unsigned j = sb[de][da]; j < jend; j += DYN_INFLIGHT) {
-                    float4 rec[DYN_INFLIGHT];
-#pragma unroll
-                    for (int u = 0; u < DYN_INFLIGHT; ++u) rec[u] = sorted_rec[j + u < jend ? j + u : jend - 1];
-#pragma unroll
-                    for (int u = 0; u < DYN_INFLIGHT; ++u) {
-                        const float d0 = qe - rec[u].x, d1 = qa - rec[u].y;
-                        const float d = d0 * d0 + d1 * d1;
-                        if (d <= r2 && d <= bd) { // ties on the angular distance go to the smallest beam index (the bucket order is arbitrary; a clamped repeat changes nothing)
-                            const int b = (int)__float_as_uint(rec[u].z);
-                            if (d < bd || b < best) { bd = d; best = b; }
-                        }
-                    }
-                }
-            }
-        }
-    }
-    if (best < 0) return; // no beam within 2 * beamHalfAngle
-
-    const float4 ip = beam_xyzn[best];
-    const float inputNorm = ip.w;
-    const float dx = ip.x - mp.x, dy = ip.y - mp.y, dz = ip.z - mp.z;
-    const float delta = sqrtf(dx * dx + dy * dy + dz * dz);
-    const float d_max = prm.epsilon_a * inputNorm;
-    const float n0 = normals3[3 * i], n1 = normals3[3 * i + 1], n2 = normals3[3 * i + 2];
-    const float nx = fmaf(T[8], n2, fmaf(T[4], n1, T[0] * n0));
-    const float ny = fmaf(T[9], n2, fmaf(T[5], n1, T[1] * n0));
-    const float nz = fmaf(T[10], n2, fmaf(T[6], n1, T[2] * n0));
-    const float ndot = (nx * mp.x + ny * mp.y + nz * mp.z) / mapNorm;
-
-    const float w_v = (float)(eps + (1. - eps) * fabs((double)ndot));
-    const float w_d1 = (float)(eps + (1. - eps) * (1. - sqrtf(bd) / (2 * prm.beam_half_angle)));
-    const float offset = delta - prm.epsilon_d;
-    float w_d2 = 1.f;
-    if (delta < prm.epsilon_d || mapNorm > inputNorm) w_d2 = eps;
-    else if (offset < d_max) w_d2 = eps + (1 - eps) * offset / d_max;
-    float w_p2 = eps;
-    if (delta < prm.epsilon_d) w_p2 = 1.f;
-    else if (offset < d_max) w_p2 = (float)(eps + (1. - eps) * (1. - offset / d_max));
-
-    if ((inputNorm + prm.epsilon_d + d_max) >= mapNorm) {
-        const float lastDyn = prob[i];
-        const float c1 = 1 - (w_v * w_d1);
-        const float c2 = w_v * w_d1;
-        float probDynamic, probStatic;
-        if (lastDyn < prm.threshold_dynamic) {
-            probDynamic = c1 * lastDyn + c2 * w_d2 * ((1 - prm.alpha) * (1 - lastDyn) + prm.beta * lastDyn);
-            probStatic = c1 * (1 - lastDyn) + c2 * w_p2 * (prm.alpha * (1 - lastDyn) + (1 - prm.beta) * lastDyn);
-        } else { // latched: once dynamic, always dynamic
-            probDynamic = 1 - eps;
-            probStatic = eps;
-        }
-        prob[i] = probDynamic / (probDynamic + probStatic);
-    }
-}
 
 __global__ __launch_bounds__(256) void keep_flag_kernel(const float* __restrict__ d2, int64_t n, double lim, unsigned* __restrict__ flag)
 {
@@ -627,75 +32,57 @@ __global__ __launch_bounds__(256) void flag_to_keep_kernel(const unsigned* __res
     if (i < n) keep[i] = flag[i] ? 1 : 0;
 }
 
-// stable compaction by flags: kept input i goes to slot base + pos[i] (pos = exclusive scan of the flags)
-__global__ __launch_bounds__(256) void append_flagged_kernel(const float4* __restrict__ in, const float* __restrict__ in_n3, int64_t n,
-                                                             const unsigned* __restrict__ flag, const unsigned* __restrict__ pos, int64_t base,
-                                                             float4* __restrict__ raw, float* __restrict__ raw_n3)
+// ---- stable compaction by flags: kept input i goes to slot base + pos[i] (pos = exclusive scan of the 0 / 1 flags) ----
+// a float4 array; a slot at or past `cap` is not written
+__global__ __launch_bounds__(256) void compact_points_kernel(const float4* __restrict__ in, int64_t n, const unsigned* __restrict__ flag,
+                                                             const unsigned* __restrict__ pos, float4* __restrict__ out, int64_t base, int64_t cap)
 {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n || !flag[i]) return;
     const int64_t o = base + pos[i];
-    raw[o] = in[i];
-    if (raw_n3) {
-        raw_n3[3 * o] = in_n3 ? in_n3[3 * i] : 0.f;
-        raw_n3[3 * o + 1] = in_n3 ? in_n3[3 * i + 1] : 0.f;
-        raw_n3[3 * o + 2] = in_n3 ? in_n3[3 * i + 2] : 0.f;
-    }
+    if (o < cap) out[o] = in[i];
 }
+constexpr int64_t NO_CAP = INT64_MAX;
 
-// stable compaction: kept input i goes to slot base + pos[i] (pos = exclusive scan of the flags)
-__global__ __launch_bounds__(256) void append_kept_kernel(const float4* __restrict__ in, const float* __restrict__ in_n3, int64_t n,
-                                                          const float* __restrict__ d2, double lim, const unsigned* __restrict__ pos,
-                                                          int64_t base, float4* __restrict__ raw, float* __restrict__ raw_n3)
+// the point record: features with their companions -- normals (3 x N), scalar, provenance.  flag == nullptr: every input is kept;
+// pos == nullptr: slot base + i.  An output companion that is null is not written; an input companion that is null reads as zeros,
+// provenance as src_base + i.
+__global__ __launch_bounds__(256) void compact_records_kernel(int64_t n, const unsigned* __restrict__ flag, const unsigned* __restrict__ pos, int64_t base,
+                                                              const float4* __restrict__ in, const float* __restrict__ in_n3,
+                                                              const float* __restrict__ in_s, const int* __restrict__ in_src, int src_base,
+                                                              float4* __restrict__ out, float* __restrict__ out_n3, float* __restrict__ out_s,
+                                                              int* __restrict__ out_src)
 {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n || !((double)d2[i] >= lim)) return;
-    const int64_t o = base + pos[i];
-    raw[o] = in[i];
-    if (raw_n3) {
-        raw_n3[3 * o] = in_n3 ? in_n3[3 * i] : 0.f;
-        raw_n3[3 * o + 1] = in_n3 ? in_n3[3 * i + 1] : 0.f;
-        raw_n3[3 * o + 2] = in_n3 ? in_n3[3 * i + 2] : 0.f;
+    if (i >= n || (flag && !flag[i])) return;
+    const int64_t o = base + (pos ? (int64_t)pos[i] : i);
+    out[o] = in[i];
+    if (out_n3) {
+        out_n3[3 * o] = in_n3 ? in_n3[3 * i] : 0.f;
+        out_n3[3 * o + 1] = in_n3 ? in_n3[3 * i + 1] : 0.f;
+        out_n3[3 * o + 2] = in_n3 ? in_n3[3 * i + 2] : 0.f;
     }
+    if (out_s) out_s[o] = in_s ? in_s[i] : 0.f;
+    if (out_src) out_src[o] = in_src ? in_src[i] : src_base + (int)i;
+}
+
+// pos = exclusive scan of the flags, *count = how many are set: the last position plus the last flag, one small read-back.  `enqueue`
+// launches what needs only the positions, in front of that wait.  (device_scan_flags_count gets the count through host-mapped memory
+// instead; the callers of this one were timed with the read-back.)
+template <class Enqueue>
+icpmi_status scan_flags_read_count(icpmi_ctx* c, const unsigned* d_flag, unsigned* d_pos, int64_t n, int64_t* count, Enqueue enqueue)
+{
+    const icpmi_status s = device_exclusive_scan_io(c, d_flag, d_pos, (int)n, 0u);
+    if (s != ICPMI_OK) return s;
+    enqueue();
+    HIP_TRY(c, hipGetLastError());
+    unsigned lp = 0, lf = 0;
+    if (read_back2(c, &lp, d_pos + (n - 1), sizeof(unsigned), &lf, d_flag + (n - 1), sizeof(unsigned)) != ICPMI_OK) return ICPMI_ERR_HIP;
+    *count = (int64_t)lp + lf;
+    return ICPMI_OK;
 }
 
 } // namespace
-
-// helper: a private handle on the same device/stream used to index an arbitrary cloud without
-// disturbing the ICP map of the caller's handle
-// The private handle lives as long as its owner (created on first use, destroyed by icpmi_destroy): its buffers are
-// reused from call to call instead of ~20 hipMalloc / hipFree pairs per operator call.
-struct TempCtx {
-    icpmi_handle h = nullptr;
-};
-
-// private handles enqueue on the owner's stream: what they read was produced there and what they produce is consumed there,
-// so stream order replaces the hipStreamSynchronize pairs an own stream needs (r2: two per surface-normal step of a map update)
-static void share_stream(icpmi_ctx* c, icpmi_ctx* t)
-{
-    if (t->stream == c->stream) { (void)zero_state_if_pending(t); return; } // (a handle that keeps its own stream still starts from a cleared state: ADVICE r5)
-    if (t->stream) (void)hipStreamSynchronize(t->stream);
-    if (t->own_stream && t->stream) stream_release(t->stream);
-    t->stream = c->stream; t->own_stream = false;
-    drop_loop_graphs(t);
-    (void)zero_state_if_pending(t); // (on the owner's stream; an error surfaces at the handle's next call)
-}
-
-static icpmi_status make_temp(icpmi_ctx* c, TempCtx& t)
-{
-    if (!c->temp) {
-        icpmi_config cfg = c->cfg;
-        icpmi_status s = create_handle(&cfg, &c->temp);
-        if (s != ICPMI_OK) { c->last_error = icpmi_last_error(nullptr); c->temp = nullptr; return s; }
-    }
-    t.h = c->temp;
-    share_stream(c, t.h);
-    t.h->cfg = c->cfg;
-    t.h->keep_raw = false;
-    t.h->no_centre = true; // PointDistanceMapperModule.cpp:33 / SurfaceNormalDataPointsFilter build their kd-tree on the raw cloud
-    t.h->single_level = false;
-    return ICPMI_OK;
-}
 
 namespace { icpmi_status chain_point_distance_flags(icpmi_ctx* c, icpmi_ctx* ic, const float4* d_scan, int64_t n, float min_dist, unsigned* d_flag); }
 
@@ -762,326 +149,6 @@ no_view:
         c->temp_raw_version = c->map_version; c->temp_raw_epoch = c->raw_epoch; c->temp_raw_m = c->m_raw;
     }
     *out = t;
-    return ICPMI_OK;
-}
-
-// Transformation::checkParameters: rotation part must be (close to) orthonormal with det +1
-static icpmi_status check_rigid(icpmi_ctx* c, const float T[16])
-{
-    const double det = (double)T[0] * ((double)T[5] * T[10] - (double)T[9] * T[6]) - (double)T[4] * ((double)T[1] * T[10] - (double)T[9] * T[2]) +
-                       (double)T[8] * ((double)T[1] * T[6] - (double)T[5] * T[2]);
-    if (fabs(1.0 - det) > 1e-3) {
-        c->last_error = "TransformationError: RigidTransformation: rotation part is not orthonormal (|1 - det| > 1e-3)";
-        return ICPMI_ERR_INVALID_ARG;
-    }
-    return ICPMI_OK;
-}
-
-// RigidTransformation::compute on device buffers, on the handle's stream (the 4x4 goes through a small resident buffer)
-icpmi_status ops_transform_dev(icpmi_ctx* c, const float T[16], const float4* d_in, int64_t n, float4* d_out)
-{
-    icpmi_status s = check_rigid(c, T);
-    if (s != ICPMI_OK || n == 0) return s;
-    hipLaunchKernelGGL(transform_kernel, dim3((int)((n + 255) / 256)), dim3(256), 0, c->stream, d_in, n, mat16(T), d_out);
-    HIP_TRY(c, hipGetLastError());
-    return ICPMI_OK;
-}
-
-icpmi_status ops_transform(icpmi_ctx* c, const float T[16], const float* in4, int64_t n, float* out4, const float* in_n3,
-                           float* out_n3)
-{
-    icpmi_status cs = check_rigid(c, T);
-    if (cs != ICPMI_OK) return cs;
-    if (n == 0) return ICPMI_OK;
-    DevBuf<float> d_n, d_no;
-    DevBuf<float4> d_in, d_out;
-    HIP_TRY(c, d_in.alloc((size_t)n));
-    HIP_TRY(c, d_out.alloc((size_t)n));
-    hipError_t e = hipMemcpyAsync(d_in, in4, (size_t)n * sizeof(float4), hipMemcpyHostToDevice, c->stream);
-    const int blocks = (int)((n + 255) / 256);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(transform_kernel, dim3(blocks), dim3(256), 0, c->stream, d_in, n, mat16(T), d_out);
-        e = hipMemcpyAsync(out4, d_out, (size_t)n * sizeof(float4), hipMemcpyDeviceToHost, c->stream);
-    }
-    if (e == hipSuccess && in_n3 && out_n3) {
-        e = d_n.alloc((size_t)n * 3);
-        if (e == hipSuccess) e = d_no.alloc((size_t)n * 3);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_n, in_n3, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(rotate3_kernel, dim3(blocks), dim3(256), 0, c->stream, d_n, n, mat16(T), d_no);
-            e = hipMemcpyAsync(out_n3, d_no, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream);
-        }
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    HIP_TRY(c, e);
-    return ICPMI_OK;
-}
-
-icpmi_status ops_bin_cells(icpmi_ctx* c, const float* pts4, int64_t n, float cell_size, int32_t* ijk3)
-{
-    if (n == 0) return ICPMI_OK;
-    DevBuf<float4> d_in; DevBuf<int> d_o;
-    HIP_TRY(c, d_in.alloc((size_t)n));
-    HIP_TRY(c, d_o.alloc((size_t)n * 3));
-    hipError_t e = hipMemcpyAsync(d_in, pts4, (size_t)n * sizeof(float4), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(bin_kernel, dim3((int)((n + 255) / 256)), dim3(256), 0, c->stream, d_in, n, cell_size, d_o);
-        e = hipMemcpyAsync(ijk3, d_o, (size_t)n * 3 * sizeof(int), hipMemcpyDeviceToHost, c->stream);
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    HIP_TRY(c, e);
-    return ICPMI_OK;
-}
-
-// shared by surface normals and point-distance: index `cloud4` in a temp handle, kNN `q4` against it
-static icpmi_status temp_knn(icpmi_ctx* c, TempCtx& t, const float* cloud4, int64_t m, const float* q4, int64_t n, int k,
-                             int allow_self, bool queries_are_cloud)
-{
-    icpmi_ctx* tc = t.h;
-    const bool self = queries_are_cloud && allow_self; // SurfaceNormalDataPointsFilter: the cloud against itself -- the sparse block grid (selfgrid.hip)
-    if (self) {
-        if (m <= 0 || !cloud4) { c->last_error = "set_map: empty cloud"; return ICPMI_ERR_INVALID_ARG; }
-        const size_t cnt = (size_t)m * k + 1;
-        if (tc->d_stage_in.ensure(tc, (size_t)m + 1) != ICPMI_OK || tc->d_sidx.ensure(tc, cnt) != ICPMI_OK ||
-            tc->d_d2.ensure(tc, cnt) != ICPMI_OK) { c->last_error = tc->last_error; return ICPMI_ERR_HIP; }
-        HIP_TRY(c, hipMemcpyAsync(tc->d_stage_in, cloud4, (size_t)m * sizeof(float4), hipMemcpyHostToDevice, tc->stream));
-        const icpmi_status gs = selfgrid_knn(tc, tc->d_stage_in, m, k, tc->d_sidx, tc->d_d2);
-        if (gs != ICPMI_OK) c->last_error = tc->last_error;
-        return gs;
-    }
-    tc->single_level = false;
-    int32_t acc = 0;
-    icpmi_status s = icpmi_set_map(t.h, cloud4, m, nullptr, &acc);
-    if (s != ICPMI_OK) { c->last_error = tc->last_error; return s; }
-    // queries: stage + centre on the temp map's mean (the index lives in the centred frame)
-    // (the cloud itself is already there: icpmi_set_map staged it in d_stage_in -- no second upload, and no re-sizing
-    // of that buffer, which would drop it)
-    if (!queries_are_cloud) {
-        if (tc->d_stage_in.ensure(tc, (size_t)n + 1) != ICPMI_OK) { c->last_error = tc->last_error; return ICPMI_ERR_HIP; }
-        HIP_TRY(c, hipMemcpyAsync(tc->d_stage_in, q4, (size_t)n * sizeof(float4), hipMemcpyHostToDevice, tc->stream));
-    }
-    s = loop_prepare_reading(tc, tc->d_stage_in, n, nullptr);
-    if (s != ICPMI_OK) { c->last_error = tc->last_error; return s; }
-    LoopCfg lc = make_loop_cfg(tc, 1);
-    lc.k = k; lc.max_dist = INFINITY; lc.maxr2 = INFINITY; lc.ring_max = 6; lc.inv1e = 1.f; lc.err2 = 1.f; // (a filter's search: exact whatever the matcher's epsilon)
-    const size_t cnt = (size_t)n * k + 1;
-    if (tc->d_sidx.ensure(tc, cnt) != ICPMI_OK || tc->d_d2.ensure(tc, cnt) != ICPMI_OK ||
-        tc->d_hard.ensure(tc, (size_t)n + 1) != ICPMI_OK) { c->last_error = tc->last_error; return ICPMI_ERR_HIP; }
-    HIP_TRY(c, hipMemsetAsync(tc->d_state, 0, sizeof(IcpState), tc->stream));
-    tc->nn_hist0 = nullptr; tc->nn_iter_hint = 0; tc->nn_match_pt = nullptr;
-    s = nn_launch_k(tc, tc->d_reading, n, nullptr, lc, allow_self, tc->d_sidx, tc->d_d2, tc->d_state);
-    if (s != ICPMI_OK) { c->last_error = tc->last_error; return s; }
-    return ICPMI_OK;
-}
-
-icpmi_status ops_surface_normals(icpmi_ctx* c, const float* pts4, int64_t m, int knn, float* normals3, float* densities, int32_t* matched_ids,
-                                 float* mean_dist, float* eig_values, float* eig_vectors)
-{
-    if (m == 0) return ICPMI_OK;
-    if (knn < 1 || knn > ICPMI_MAX_K) { c->last_error = "surface_normals: knn must be in [1, 32]"; return ICPMI_ERR_INVALID_ARG; }
-    TempCtx t;
-    icpmi_status s = make_temp(c, t);
-    if (s != ICPMI_OK) return s;
-    s = temp_knn(c, t, pts4, m, nullptr, m, knn, 1, true);
-    if (s != ICPMI_OK) return s;
-    icpmi_ctx* tc = t.h;
-    if ((eig_values || eig_vectors) && c->cfg.is_2d) { c->last_error = "surface_normals: keepEigenValues / keepEigenVectors are not served for planar clouds"; return ICPMI_ERR_UNSUPPORTED; }
-    DevBuf<float> d_n, d_dens, d_md, d_ev, d_evec;
-    DevBuf<int> d_ids;
-    HIP_TRY(c, d_n.alloc((size_t)m * 3));
-    if (densities) HIP_TRY(c, d_dens.alloc((size_t)m));
-    if (mean_dist) HIP_TRY(c, d_md.alloc((size_t)m));
-    if (eig_values) HIP_TRY(c, d_ev.alloc((size_t)m * 3));
-    if (eig_vectors) HIP_TRY(c, d_evec.alloc((size_t)m * 9));
-    launch_normals(tc->stream, tc->d_map_sorted, tc->d_sidx, m, knn, d_n, densities ? d_dens.get() : (float*)nullptr, c->cfg.is_2d,
-                   mean_dist ? d_md.get() : (float*)nullptr, eig_values ? d_ev.get() : (float*)nullptr, eig_vectors ? d_evec.get() : (float*)nullptr);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess && eig_values) e = hipMemcpyAsync(eig_values, d_ev, (size_t)m * 3 * sizeof(float), hipMemcpyDeviceToHost, tc->stream);
-    if (e == hipSuccess && eig_vectors) e = hipMemcpyAsync(eig_vectors, d_evec, (size_t)m * 9 * sizeof(float), hipMemcpyDeviceToHost, tc->stream);
-    if (e == hipSuccess && matched_ids) { // keepMatchedIds: sorted positions -> the caller's indices
-        e = d_ids.alloc((size_t)m * knn);
-        if (e == hipSuccess && nn_ids_to_original(tc, tc->d_sidx, m * knn, d_ids) != ICPMI_OK) { c->last_error = tc->last_error; return ICPMI_ERR_HIP; }
-        if (e == hipSuccess) e = hipMemcpyAsync(matched_ids, d_ids, (size_t)m * knn * sizeof(int), hipMemcpyDeviceToHost, tc->stream);
-    }
-    if (e == hipSuccess && mean_dist) e = hipMemcpyAsync(mean_dist, d_md, (size_t)m * sizeof(float), hipMemcpyDeviceToHost, tc->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(normals3, d_n, (size_t)m * 3 * sizeof(float), hipMemcpyDeviceToHost, tc->stream);
-    if (e == hipSuccess && densities) e = hipMemcpyAsync(densities, d_dens, (size_t)m * sizeof(float), hipMemcpyDeviceToHost, tc->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(tc->stream);
-    HIP_TRY(c, e);
-    return ICPMI_OK;
-}
-
-icpmi_status ops_point_distance_keep(icpmi_ctx* c, const float* map4, int64_t m, const float* in4, int64_t n, float min_dist,
-                                     uint8_t* keep)
-{
-    if (n == 0) return ICPMI_OK;
-    if (m == 0) { memset(keep, 1, (size_t)n); return ICPMI_OK; } // no neighbour: d2 = +inf >= lim
-    TempCtx t;
-    icpmi_status s = make_temp(c, t);
-    if (s != ICPMI_OK) return s;
-    s = temp_knn(c, t, map4, m, in4, n, 1, 0, false);
-    if (s != ICPMI_OK) return s;
-    icpmi_ctx* tc = t.h;
-    DevBuf<uint8_t> d_keep;
-    HIP_TRY(c, d_keep.alloc((size_t)n));
-    const double lim = pd_limit(min_dist);
-    hipLaunchKernelGGL(keep_kernel, dim3((int)((n + 255) / 256)), dim3(256), 0, tc->stream, tc->d_d2, n, lim, d_keep);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(keep, d_keep, (size_t)n, hipMemcpyDeviceToHost, tc->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(tc->stream);
-    HIP_TRY(c, e);
-    return ICPMI_OK;
-}
-
-// decimation flags of a DEVICE cloud (T = uint8_t or unsigned), stream-ordered on c->stream
-template <typename T>
-static icpmi_status voxel_flags_dev(icpmi_ctx* c, const float4* d_in, int64_t n, float edge, int method, T* d_keep)
-{
-    if (n > 0xfffffff0ll) { c->last_error = "voxel_keep: too many points"; return ICPMI_ERR_UNSUPPORTED; }
-    unsigned long long cap = 1024;
-    while (cap < (unsigned long long)n * 2ull) cap <<= 1;
-    unsigned long long* d_keys = scratch_get<unsigned long long>(c, 0, (size_t)cap);
-    unsigned* d_vals = scratch_get<unsigned>(c, 1, (size_t)cap);
-    unsigned* d_slot = scratch_get<unsigned>(c, 2, (size_t)n);
-    unsigned* d_lo = scratch_get<unsigned>(c, 3, 4);
-    if (!d_keys || !d_vals || !d_slot || !d_lo) return ICPMI_ERR_HIP;
-    HIP_TRY(c, hipMemsetAsync(d_keys, 0xff, (size_t)cap * sizeof(unsigned long long), c->stream));
-    HIP_TRY(c, hipMemsetAsync(d_vals, 0xff, (size_t)cap * sizeof(unsigned), c->stream));
-    HIP_TRY(c, hipMemsetAsync(d_lo, 0xff, 4 * sizeof(unsigned), c->stream));
-    const int blocks = (int)((n + 255) / 256);
-    const int rb = blocks < 1024 ? blocks : 1024;
-    hipLaunchKernelGGL(bbox_min_kernel, dim3(rb), dim3(256), 0, c->stream, d_in, n, d_lo);
-    hipLaunchKernelGGL(voxel_insert_kernel, dim3(blocks), dim3(256), 0, c->stream, d_in, n, d_lo, edge, method, d_keys, d_vals, cap - 1, d_slot);
-    hipLaunchKernelGGL(voxel_keep_kernel<T>, dim3(blocks), dim3(256), 0, c->stream, n, d_vals, d_slot, method, d_keep);
-    HIP_TRY(c, hipGetLastError());
-    return ICPMI_OK;
-}
-
-icpmi_status ops_filter_points(icpmi_ctx* c, const float* in4, int64_t n, const icpmi_point_filter* filters, int n_filters, uint8_t* keep)
-{
-    if (n == 0) return ICPMI_OK;
-    FilterPack fp;
-    fp.n = n_filters;
-    for (int k = 0; k < n_filters; ++k) fp.f[k] = filters[k];
-    if (c->d_stage_in.ensure(c, (size_t)n + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
-    uint8_t* d_keep = scratch_get<uint8_t>(c, 9, (size_t)n);
-    if (!d_keep) return ICPMI_ERR_HIP;
-    HIP_TRY(c, hipMemcpyAsync(c->d_stage_in, in4, (size_t)n * sizeof(float4), hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(filter_points_kernel, dim3((int)((n + 255) / 256)), dim3(256), 0, c->stream, c->d_stage_in, n, fp, d_keep);
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(keep, d_keep, (size_t)n, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return ICPMI_OK;
-}
-
-// the arguments are validated by icpmi_sensor_model (api.hip): every pointer the program needs is there, an output it does not produce is NULL
-icpmi_status ops_sensor_model(icpmi_ctx* c, const float* in4, int64_t n, const float* normals3_in, const float* obs_dir3_in, const icpmi_sensor_step* steps,
-                              int n_steps, float* normals3_out, float* obs_dir3_out, float* noise_out, uint8_t* keep_out)
-{
-    if (n == 0) return ICPMI_OK;
-    SensorPack sp{};
-    sp.n = n_steps;
-    for (int k = 0; k < n_steps; ++k) sp.s[k] = steps[k];
-    sp.read_n = normals3_in ? 1 : 0; sp.write_n = normals3_out ? 1 : 0;
-    sp.read_od = obs_dir3_in ? 1 : 0; sp.write_od = obs_dir3_out ? 1 : 0;
-    if (c->d_stage_in.ensure(c, (size_t)n + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
-    float* d_n3 = nullptr; float* d_od3 = nullptr; float* d_noise = nullptr; uint8_t* d_keep = nullptr;
-    if (sp.read_n || sp.write_n) { if (c->d_stage_n3.ensure(c, (size_t)n * 3) != ICPMI_OK) return ICPMI_ERR_HIP; d_n3 = c->d_stage_n3; }
-    if ((sp.read_od || sp.write_od) && !(d_od3 = scratch_get<float>(c, 6, (size_t)n * 3))) return ICPMI_ERR_HIP;
-    if (noise_out && !(d_noise = scratch_get<float>(c, 7, (size_t)n))) return ICPMI_ERR_HIP;
-    if (keep_out && !(d_keep = scratch_get<uint8_t>(c, 9, (size_t)n))) return ICPMI_ERR_HIP;
-    HIP_TRY(c, hipMemcpyAsync(c->d_stage_in, in4, (size_t)n * sizeof(float4), hipMemcpyHostToDevice, c->stream));
-    if (sp.read_n) HIP_TRY(c, hipMemcpyAsync(d_n3, normals3_in, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    if (sp.read_od) HIP_TRY(c, hipMemcpyAsync(d_od3, obs_dir3_in, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(sensor_model_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, c->d_stage_in, n, sp, d_n3, d_od3, d_noise, d_keep);
-    HIP_TRY(c, hipGetLastError());
-    if (sp.write_n) HIP_TRY(c, hipMemcpyAsync(normals3_out, d_n3, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    if (sp.write_od) HIP_TRY(c, hipMemcpyAsync(obs_dir3_out, d_od3, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    if (noise_out) HIP_TRY(c, hipMemcpyAsync(noise_out, d_noise, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    if (keep_out) HIP_TRY(c, hipMemcpyAsync(keep_out, d_keep, (size_t)n, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return ICPMI_OK;
-}
-
-icpmi_status ops_voxel_keep_first(icpmi_ctx* c, const float* in4, int64_t n, float edge, int method, uint8_t* keep)
-{
-    if (n == 0) return ICPMI_OK;
-    DevBuf<float4> d_in; DevBuf<uint8_t> d_keep;
-    HIP_TRY(c, d_in.alloc((size_t)n));
-    HIP_TRY(c, d_keep.alloc((size_t)n));
-    HIP_TRY(c, hipMemcpyAsync(d_in, in4, (size_t)n * sizeof(float4), hipMemcpyHostToDevice, c->stream));
-    icpmi_status s = voxel_flags_dev<uint8_t>(c, d_in, n, edge, method, d_keep);
-    if (s != ICPMI_OK) return s;
-    HIP_TRY(c, hipMemcpyAsync(keep, d_keep, (size_t)n, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return ICPMI_OK;
-}
-
-// DynamicPointsMapperModule::inPlaceUpdateMap on DEVICE arrays (T = pose^-1 as a kernel argument); d_prob updated in place.  Its scratch is
-// its own (slots 10..19) and `stream` may be the handle's side stream: the module only touches the probabilities of the OLD map points, so
-// the map-update chain runs it next to the decimation that follows (ops_map_update_chain).
-static icpmi_status dynpts_dev(icpmi_ctx* c, const icpmi_dynpts_params* prm, const float T[16], const float4* d_in, int64_t n,
-                               const float4* d_map, const float* d_nrm, int64_t m, float* d_prob, hipStream_t stream)
-{
-    if (n == 0 || m == 0) return ICPMI_OK; // "if (beams.empty()) return"
-    DynGrid g;
-    const float reach = 2 * prm->beam_half_angle;
-    g.r2 = reach * reach;
-    g.cell = reach / (float)DYN_RINGS;
-    g.ne = (int)floorf(3.14159265358979f / g.cell) + 2;
-    g.na = (int)floorf(6.28318530717959f / g.cell) + 2;
-    const int64_t ncells = (int64_t)g.ne * g.na;
-    if (ncells > (1ll << 28)) { c->last_error = "dynamic_points_update: beamHalfAngle too small for the angular grid"; return ICPMI_ERR_UNSUPPORTED; }
-    DynPrm dp = {prm->threshold_dynamic, prm->alpha, prm->beta, prm->beam_half_angle, prm->epsilon_a, prm->epsilon_d, prm->sensor_max_range};
-    float4* d_bx = scratch_get<float4>(c, 10, (size_t)n);
-    float2* d_ba = scratch_get<float2>(c, 11, (size_t)n);
-    unsigned* d_keys = scratch_get<unsigned>(c, 12, (size_t)n);
-    unsigned* d_start = scratch_get<unsigned>(c, 13, (size_t)ncells + 2);
-    unsigned* d_cnt = scratch_get<unsigned>(c, 14, (size_t)ncells + 2);
-    float4* d_rec = scratch_get<float4>(c, 15, (size_t)n);
-    const bool side_scan = device_scan_side_ok((int)ncells);
-    unsigned* d_sums = side_scan ? scratch_get<unsigned>(c, 16, device_scan_side_words((int)ncells)) : nullptr;
-    if (!d_bx || !d_ba || !d_keys || !d_start || !d_cnt || !d_rec || (side_scan && !d_sums)) return ICPMI_ERR_HIP;
-    if (!side_scan && stream != c->stream) { c->last_error = "dynamic_points_update: internal -- side stream with a table the two-kernel scan cannot take"; return ICPMI_ERR_UNSUPPORTED; }
-    const Mat16 M = mat16(T);
-    // counts -> starts in cursor layout (map_build.hip): one table to clear, the starts are written in full by the scan
-    HIP_TRY(c, hipMemsetAsync(d_cnt, 0, ((size_t)ncells + 2) * sizeof(unsigned), stream));
-    const int nb = (int)((n + 255) / 256), mb = (int)((m + 255) / 256);
-    hipLaunchKernelGGL(dyn_beams_kernel, dim3(nb), dim3(256), 0, stream, d_in, n, M, g, d_bx, d_ba, d_keys, d_cnt);
-    icpmi_status st = side_scan ? device_exclusive_scan_cursor_side(c, stream, d_sums, d_cnt, d_start, (int)ncells, (unsigned)n)
-                                : device_exclusive_scan_cursor(c, d_cnt, d_start, (int)ncells, (unsigned)n, false);
-    if (st != ICPMI_OK) return st;
-    hipLaunchKernelGGL(dyn_scatter_kernel, dim3(nb), dim3(256), 0, stream, n, d_keys, d_start + 1, d_ba, d_rec);
-    hipLaunchKernelGGL(dyn_update_kernel, dim3(mb), dim3(256), 0, stream, d_map, d_nrm, m, M, g, dp, (const float4*)d_bx, (const float4*)d_rec, (const unsigned*)d_start, d_prob);
-    HIP_TRY(c, hipGetLastError());
-    return ICPMI_OK;
-}
-
-// whether the side scan of dynpts_dev is available for these parameters (the chain asks before it forks)
-static bool dynpts_side_ok(const icpmi_dynpts_params* prm)
-{
-    const float cell = 2 * prm->beam_half_angle / (float)DYN_RINGS;
-    const int64_t ncells = ((int64_t)floorf(3.14159265358979f / cell) + 2) * ((int64_t)floorf(6.28318530717959f / cell) + 2);
-    return ncells <= (1ll << 28) && device_scan_side_ok((int)ncells);
-}
-
-icpmi_status ops_dynamic_points_update(icpmi_ctx* c, const icpmi_dynpts_params* prm, const float to_sensor[16], const float* in4, int64_t n,
-                                       const float* map4, const float* map_normals3, int64_t m, float* prob)
-{
-    if (n == 0 || m == 0) return ICPMI_OK;
-    DevBuf<float> d_nrm, d_prob; DevBuf<float4> d_in, d_map;
-    HIP_TRY(c, d_in.alloc((size_t)n));
-    HIP_TRY(c, d_map.alloc((size_t)m));
-    HIP_TRY(c, d_nrm.alloc((size_t)m * 3));
-    HIP_TRY(c, d_prob.alloc((size_t)m));
-    HIP_TRY(c, hipMemcpyAsync(d_in, in4, (size_t)n * sizeof(float4), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(d_map, map4, (size_t)m * sizeof(float4), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(d_nrm, map_normals3, (size_t)m * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(d_prob, prob, (size_t)m * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    icpmi_status st = dynpts_dev(c, prm, to_sensor, d_in, n, d_map, d_nrm, m, d_prob, c->stream);
-    if (st != ICPMI_OK) return st;
-    HIP_TRY(c, hipMemcpyAsync(prob, d_prob, (size_t)m * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
     return ICPMI_OK;
 }
 
@@ -1178,12 +245,9 @@ icpmi_status ops_map_update_dev(icpmi_ctx* c, const float4* d_scan, int64_t n, c
             }
         }
         if (s == ICPMI_OK && e == hipSuccess) {
-            s = device_exclusive_scan_io(c, d_flag, d_pos, (int)n, 0u);
-        }
-        if (s == ICPMI_OK && e == hipSuccess) {
-            unsigned lp = 0, lf = 0;
-            if (read_back2(c, &lp, d_pos + (n - 1), sizeof(unsigned), &lf, d_flag + (n - 1), sizeof(unsigned)) != ICPMI_OK) e = hipErrorUnknown;
-            count = lp + lf;
+            int64_t kept = 0;
+            s = scan_flags_read_count(c, d_flag, d_pos, n, &kept, [] {});
+            count = (unsigned)kept;
         }
     } else {
         // PointDistanceMapperModule::createMap: the first scan is the map
@@ -1202,8 +266,9 @@ icpmi_status ops_map_update_dev(icpmi_ctx* c, const float4* d_scan, int64_t n, c
         }
         if (s == ICPMI_OK && e == hipSuccess) {
             if (m0 > 0 && !keep_all)
-                hipLaunchKernelGGL(append_flagged_kernel, dim3(blocks), dim3(256), 0, c->stream, d_scan, d_scan_n3, n, (const unsigned*)d_flag,
-                                   (const unsigned*)d_pos, m0, c->d_raw, want_n ? c->d_raw_n3 : (float*)nullptr);
+                hipLaunchKernelGGL(compact_records_kernel, dim3(blocks), dim3(256), 0, c->stream, n, (const unsigned*)d_flag, (const unsigned*)d_pos, m0, d_scan,
+                                   d_scan_n3, (const float*)nullptr, (const int*)nullptr, 0, c->d_raw.get(), want_n ? c->d_raw_n3.get() : (float*)nullptr,
+                                   (float*)nullptr, (int*)nullptr);
             else { // the first scan IS the map, or every point is kept: a plain append behind the m0 points there are
                 e = hipMemcpyAsync(c->d_raw + m0, d_scan, (size_t)n * sizeof(float4), hipMemcpyDeviceToDevice, c->stream);
                 if (e == hipSuccess && want_n) {
@@ -1260,39 +325,6 @@ __global__ __launch_bounds__(256) void chain_iota_kernel(int* __restrict__ src, 
     if (i < n) src[i] = (int)i;
 }
 
-// scan point i (kept iff flag == nullptr or flag[i]) -> slot base + (pos ? pos[i] : i); provenance src_base + i
-__global__ __launch_bounds__(256) void chain_append_kernel(const float4* __restrict__ in, const float* __restrict__ in_n3,
-                                                           const float* __restrict__ in_s, int64_t n, const unsigned* __restrict__ flag,
-                                                           const unsigned* __restrict__ pos, int64_t base, int src_base,
-                                                           float4* __restrict__ raw, float* __restrict__ raw_n3, float* __restrict__ raw_s,
-                                                           int* __restrict__ src)
-{
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n || (flag && !flag[i])) return;
-    const int64_t o = base + (pos ? (int64_t)pos[i] : i);
-    raw[o] = in[i];
-    raw_n3[3 * o] = in_n3 ? in_n3[3 * i] : 0.f;
-    raw_n3[3 * o + 1] = in_n3 ? in_n3[3 * i + 1] : 0.f;
-    raw_n3[3 * o + 2] = in_n3 ? in_n3[3 * i + 2] : 0.f;
-    raw_s[o] = in_s ? in_s[i] : 0.f;
-    src[o] = src_base + (int)i;
-}
-
-__global__ __launch_bounds__(256) void chain_compact_kernel(int64_t m, const unsigned* __restrict__ flag, const unsigned* __restrict__ pos,
-                                                            const float4* __restrict__ raw, const float* __restrict__ n3,
-                                                            const float* __restrict__ sc, const int* __restrict__ src,
-                                                            float4* __restrict__ o_raw, float* __restrict__ o_n3, float* __restrict__ o_sc,
-                                                            int* __restrict__ o_src)
-{
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= m || !flag[i]) return;
-    const int64_t o = pos[i];
-    o_raw[o] = raw[i];
-    o_n3[3 * o] = n3[3 * i]; o_n3[3 * o + 1] = n3[3 * i + 1]; o_n3[3 * o + 2] = n3[3 * i + 2];
-    o_sc[o] = sc[i];
-    o_src[o] = src[i];
-}
-
 // first j with src[j] != j (m if none): the untouched head of the map, which the host need not be told about
 __global__ __launch_bounds__(256) void chain_prefix_kernel(const int* __restrict__ src, int64_t m, unsigned* __restrict__ first_moved)
 {
@@ -1341,10 +373,26 @@ icpmi_status chain_append(Chain& w, const float4* d_scan, const float* d_n3, con
     if (count == 0) return ICPMI_OK;
     icpmi_status s = chain_reserve(w, w.m + count);
     if (s != ICPMI_OK) return s;
-    hipLaunchKernelGGL(chain_append_kernel, dim3((int)((n + 255) / 256)), dim3(256), 0, c->stream, d_scan, d_n3, d_s, n, flag, pos, w.m,
-                       src_base, c->d_raw, c->d_raw_n3, c->d_raw_s, c->d_src);
+    hipLaunchKernelGGL(compact_records_kernel, dim3((int)((n + 255) / 256)), dim3(256), 0, c->stream, n, flag, pos, w.m, d_scan, d_n3, d_s,
+                       (const int*)nullptr, src_base, c->d_raw.get(), c->d_raw_n3.get(), c->d_raw_s.get(), c->d_src.get());
     HIP_TRY(c, hipGetLastError());
     w.m += count;
+    w.indexed = false;
+    return ICPMI_OK;
+}
+
+// the ping-pong of the working set: room for `count` records in the alt arrays, `launch` fills them from the main set, the four pairs swap
+template <class Launch>
+icpmi_status chain_into_alt(Chain& w, int64_t count, Launch launch)
+{
+    icpmi_ctx* c = w.c;
+    if (c->d_alt_raw.ensure(c, (size_t)count + 1) != ICPMI_OK || c->d_alt_n3.ensure(c, (size_t)count * 3 + 1) != ICPMI_OK ||
+        c->d_alt_s.ensure(c, (size_t)count + 1) != ICPMI_OK || c->d_alt_src.ensure(c, (size_t)count + 1) != ICPMI_OK)
+        return ICPMI_ERR_HIP;
+    launch();
+    HIP_TRY(c, hipGetLastError());
+    swap(c->d_raw, c->d_alt_raw); swap(c->d_raw_n3, c->d_alt_n3); swap(c->d_raw_s, c->d_alt_s); swap(c->d_src, c->d_alt_src);
+    w.m = count;
     w.indexed = false;
     return ICPMI_OK;
 }
@@ -1359,16 +407,11 @@ icpmi_status chain_compact(Chain& w, unsigned* d_flag, unsigned* d_pos)
     icpmi_status s = device_scan_flags_count(c, d_flag, d_pos, (int)m, &count);
     if (s != ICPMI_OK) return s;
     if (count == m) return ICPMI_OK; // nothing dropped
-    if (c->d_alt_raw.ensure(c, (size_t)count + 1) != ICPMI_OK || c->d_alt_n3.ensure(c, (size_t)count * 3 + 1) != ICPMI_OK ||
-        c->d_alt_s.ensure(c, (size_t)count + 1) != ICPMI_OK || c->d_alt_src.ensure(c, (size_t)count + 1) != ICPMI_OK)
-        return ICPMI_ERR_HIP;
-    hipLaunchKernelGGL(chain_compact_kernel, dim3((int)((m + 255) / 256)), dim3(256), 0, c->stream, m, d_flag, d_pos, c->d_raw, c->d_raw_n3,
-                       c->d_raw_s, c->d_src, c->d_alt_raw, c->d_alt_n3, c->d_alt_s, c->d_alt_src);
-    HIP_TRY(c, hipGetLastError());
-    swap(c->d_raw, c->d_alt_raw); swap(c->d_raw_n3, c->d_alt_n3); swap(c->d_raw_s, c->d_alt_s); swap(c->d_src, c->d_alt_src);
-    w.m = count;
-    w.indexed = false;
-    return ICPMI_OK;
+    return chain_into_alt(w, count, [&] {
+        hipLaunchKernelGGL(compact_records_kernel, dim3((int)((m + 255) / 256)), dim3(256), 0, c->stream, m, (const unsigned*)d_flag, (const unsigned*)d_pos,
+                           (int64_t)0, (const float4*)c->d_raw.get(), (const float*)c->d_raw_n3.get(), (const float*)c->d_raw_s.get(),
+                           (const int*)c->d_src.get(), 0, c->d_alt_raw.get(), c->d_alt_n3.get(), c->d_alt_s.get(), c->d_alt_src.get());
+    });
 }
 
 // the working map re-ordered / decimated by an index list: new point j = old point order[j] (OctreeGridDataPointsFilter
@@ -1390,16 +433,10 @@ __global__ __launch_bounds__(256) void chain_gather_kernel(int64_t count, const 
 icpmi_status chain_gather(Chain& w, const int* d_order, int64_t count)
 {
     icpmi_ctx* c = w.c;
-    if (c->d_alt_raw.ensure(c, (size_t)count + 1) != ICPMI_OK || c->d_alt_n3.ensure(c, (size_t)count * 3 + 1) != ICPMI_OK ||
-        c->d_alt_s.ensure(c, (size_t)count + 1) != ICPMI_OK || c->d_alt_src.ensure(c, (size_t)count + 1) != ICPMI_OK)
-        return ICPMI_ERR_HIP;
-    if (count) hipLaunchKernelGGL(chain_gather_kernel, dim3((int)((count + 255) / 256)), dim3(256), 0, c->stream, count, d_order, c->d_raw, c->d_raw_n3,
-                                  c->d_raw_s, c->d_src, c->d_alt_raw, c->d_alt_n3, c->d_alt_s, c->d_alt_src);
-    HIP_TRY(c, hipGetLastError());
-    swap(c->d_raw, c->d_alt_raw); swap(c->d_raw_n3, c->d_alt_n3); swap(c->d_raw_s, c->d_alt_s); swap(c->d_src, c->d_alt_src);
-    w.m = count;
-    w.indexed = false;
-    return ICPMI_OK;
+    return chain_into_alt(w, count, [&] {
+        if (count) hipLaunchKernelGGL(chain_gather_kernel, dim3((int)((count + 255) / 256)), dim3(256), 0, c->stream, count, d_order, c->d_raw, c->d_raw_n3,
+                                      c->d_raw_s, c->d_src, c->d_alt_raw, c->d_alt_n3, c->d_alt_s, c->d_alt_src);
+    });
 }
 
 // PointDistanceMapperModule.cpp:33-42 on an indexing handle `ic` (the caller's own handle while its index still
@@ -1435,18 +472,6 @@ static bool chain_side_ready(icpmi_ctx* c)
     if (!c->side_fork && hipEventCreateWithFlags(&c->side_fork, hipEventDisableTiming) != hipSuccess) { c->side_fork = nullptr; return false; }
     if (!c->side_join && hipEventCreateWithFlags(&c->side_join, hipEventDisableTiming) != hipSuccess) { c->side_join = nullptr; return false; }
     return true;
-}
-
-// the working map moved by T in place: features by T, normals by its rotation (RigidTransformation::compute on the whole map,
-// Map.cpp:523 / :525)
-static icpmi_status chain_move(icpmi_ctx* c, const float T[16], int64_t m, bool has_n)
-{
-    if (m == 0) return ICPMI_OK;
-    const icpmi_status s = check_rigid(c, T);
-    if (s != ICPMI_OK) return s;
-    hipLaunchKernelGGL(move_kernel, dim3((int)((m + 255) / 256)), dim3(256), 0, c->stream, c->d_raw, has_n ? c->d_raw_n3 : (float*)nullptr, m, mat16(T));
-    HIP_TRY(c, hipGetLastError());
-    return ICPMI_OK;
 }
 
 icpmi_status ops_map_update_chain(icpmi_ctx* c, const float4* d_scan, int64_t n, const float* d_scan_n3, const float* d_scan_s,
@@ -1541,7 +566,7 @@ icpmi_status ops_map_update_chain(icpmi_ctx* c, const float4* d_scan, int64_t n,
     for (int i = 0; i < n_ops && s == ICPMI_OK; ++i) {
         const icpmi_map_op& op = ops[i];
         if (forked && op.type != ICPMI_MOP_OCTREE && op.type != ICPMI_MOP_VOXEL) { s = join(); if (s != ICPMI_OK) break; } // (cannot happen: the fork looks at the next module)
-        if (i == n_modules && round_trip) { s = chain_move(c, to_sensor, w.m, w.has_n); in_sensor = true; if (s != ICPMI_OK) break; tick("to_sensor", -1); }
+        if (i == n_modules && round_trip) { s = ops_move_dev(c, to_sensor, c->d_raw, w.has_n ? c->d_raw_n3.get() : nullptr, w.m); in_sensor = true; if (s != ICPMI_OK) break; tick("to_sensor", -1); }
         switch (op.type) {
         case ICPMI_MOP_POINT_DISTANCE: {
             if (n == 0) break;
@@ -1637,8 +662,8 @@ icpmi_status ops_map_update_chain(icpmi_ctx* c, const float4* d_scan, int64_t n,
         forked = false;
     }
     if (s == ICPMI_OK && round_trip) {
-        if (!in_sensor) s = chain_move(c, to_sensor, w.m, w.has_n); // no post filter at all: the reference still makes the trip
-        if (s == ICPMI_OK) s = chain_move(c, from_sensor, w.m, w.has_n);
+        if (!in_sensor) s = ops_move_dev(c, to_sensor, c->d_raw, w.has_n ? c->d_raw_n3.get() : nullptr, w.m); // no post filter at all: the reference still makes the trip
+        if (s == ICPMI_OK) s = ops_move_dev(c, from_sensor, c->d_raw, w.has_n ? c->d_raw_n3.get() : nullptr, w.m);
         tick("from_sensor", -2);
     }
     if (s != ICPMI_OK) {
@@ -1680,30 +705,16 @@ icpmi_status ops_map_update_chain(icpmi_ctx* c, const float4* d_scan, int64_t n,
     return ICPMI_OK;
 }
 
-// stable compaction of the flagged points of `in` behind position `base` of `out`
-__global__ __launch_bounds__(256) void merge_compact_kernel(const float4* __restrict__ in, int64_t n, const unsigned* __restrict__ flag,
-                                                            const unsigned* __restrict__ pos, float4* __restrict__ out, int64_t base)
-{
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n || !flag[i]) return;
-    out[base + pos[i]] = in[i];
-}
-
 // flags -> kept points appended to d_out[base ...): returns how many (one small read-back)
 static icpmi_status merge_append_flagged(icpmi_ctx* c, const float4* d_in, int64_t n, unsigned* d_flag, unsigned* d_pos, float4* d_out, int64_t base,
                                          int64_t* kept)
 {
     *kept = 0;
     if (n == 0) return ICPMI_OK;
-    icpmi_status s = device_exclusive_scan_io(c, d_flag, d_pos, (int)n, 0u);
-    if (s != ICPMI_OK) return s;
-    hipLaunchKernelGGL(merge_compact_kernel, dim3((int)((n + 255) / 256)), dim3(256), 0, c->stream, d_in, n, (const unsigned*)d_flag, (const unsigned*)d_pos,
-                       d_out, base);
-    HIP_TRY(c, hipGetLastError());
-    unsigned lp = 0, lf = 0;
-    if (read_back2(c, &lp, d_pos + (n - 1), sizeof(unsigned), &lf, d_flag + (n - 1), sizeof(unsigned)) != ICPMI_OK) return ICPMI_ERR_HIP;
-    *kept = (int64_t)lp + lf;
-    return ICPMI_OK;
+    return scan_flags_read_count(c, d_flag, d_pos, n, kept, [&] {
+        hipLaunchKernelGGL(compact_points_kernel, dim3((int)((n + 255) / 256)), dim3(256), 0, c->stream, d_in, n, (const unsigned*)d_flag, (const unsigned*)d_pos,
+                           d_out, base, NO_CAP);
+    });
 }
 
 // ---- rank-ordered greedy merge of the gathered blocks (r4) -------------------------------------------------------------------------
@@ -1979,16 +990,8 @@ static icpmi_status merge_greedy(icpmi_ctx* c, const float4* recv, const std::ve
 }
 
 // ---- r5: the one-collective epoch ------------------------------------------------------------------------------------------------------
-// like merge_compact_kernel, but never past `cap` points (a block has a fixed size; the header carries the true count, an overflow sends
-// every rank to the three-collective epoch)
-__global__ __launch_bounds__(256) void merge_compact_cap_kernel(const float4* __restrict__ in, int64_t n, const unsigned* __restrict__ flag,
-                                                                const unsigned* __restrict__ pos, float4* __restrict__ out, unsigned cap)
-{
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n || !flag[i]) return;
-    const unsigned p = pos[i];
-    if (p < cap) out[p] = in[i];
-}
+// (its compaction never writes past `cap` points: a block has a fixed size; the header carries the true count, an overflow sends every
+//  rank to the three-collective epoch)
 // header of this rank's block: {bits(count) | bits(-1): this rank failed before the exchange, magic}
 __global__ void merge_header_kernel(float4* __restrict__ hdr, const unsigned* __restrict__ count_word, int ok, unsigned fixed_count, int use_fixed)
 {
@@ -2035,8 +1038,8 @@ static icpmi_status merge_epoch_one_collective(icpmi_ctx* c, const float correct
                 if (local == ICPMI_OK) local = chain_point_distance_flags(c, ri, c->d_stage_in, n, min_dist, d_flag);
                 if (local == ICPMI_OK) local = device_exclusive_scan_sum(c, d_flag, d_pos, (int)n, d_count);
                 if (local == ICPMI_OK) {
-                    hipLaunchKernelGGL(merge_compact_cap_kernel, dim3((int)((n + 255) / 256)), dim3(256), 0, c->stream, (const float4*)c->d_stage_in, n,
-                                       (const unsigned*)d_flag, (const unsigned*)d_pos, send + 1, (unsigned)cap);
+                    hipLaunchKernelGGL(compact_points_kernel, dim3((int)((n + 255) / 256)), dim3(256), 0, c->stream, (const float4*)c->d_stage_in.get(), n,
+                                       (const unsigned*)d_flag, (const unsigned*)d_pos, send + 1, (int64_t)0, cap);
                     fixed = false;
                 }
             } else { // no map yet: every point is new

@@ -53,7 +53,7 @@ struct SelfGridCtx {
 
 struct SgState {
     unsigned nblk;   // occupied blocks (claimed by the key kernel)
-    unsigned bad;    // non-finite coordinates seen by the bounding-box pass
+    unsigned bad;    // (unused: the bounding-box pass counts non-finite points next to its partials)
     unsigned long long sq;     // sum over the A-cells of (points in the cell)^2 (summed from sqpart by the cell kernel)
     unsigned long long levels; // diagnostics: sum of the levels at which the level kernel's queries ended
     unsigned qcount[64];       // queries queued for the level kernel, per sub-queue
@@ -161,9 +161,6 @@ __device__ __forceinline__ float sg_margin2(const SgGrid& g, int l, const int a[
     return margin * margin;
 }
 
-// a square root that never under-estimates (one v_sqrt_f32, 1 ulp, nudged up)
-__device__ __forceinline__ float sqrt_up_sg(float x) { return __builtin_amdgcn_sqrtf(x) * 1.0000005f; }
-
 // inclusive scan over the 64 lanes: four DPP row shifts inside the rows of 16, two row broadcasts across them
 __device__ __forceinline__ unsigned sg_wave_incl_scan(unsigned v)
 {
@@ -178,30 +175,6 @@ __device__ __forceinline__ unsigned sg_wave_incl_scan(unsigned v)
 }
 
 // ---- build ------------------------------------------------------------------------------------------------------------------------------
-constexpr int SG_RB = 256;
-__global__ __launch_bounds__(SG_RB) void sg_bbox_kernel(const float4* __restrict__ pts, int64_t m, float* __restrict__ part, SgState* __restrict__ st)
-{
-    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-    bool bad = false;
-    for (int64_t i = (int64_t)blockIdx.x * SG_RB + threadIdx.x; i < m; i += (int64_t)gridDim.x * SG_RB) {
-        const float4 p = pts[i];
-        bad |= !(fabsf(p.x) <= 3.0e38f) || !(fabsf(p.y) <= 3.0e38f) || !(fabsf(p.z) <= 3.0e38f);
-        lo[0] = fminf(lo[0], p.x); lo[1] = fminf(lo[1], p.y); lo[2] = fminf(lo[2], p.z);
-        hi[0] = fmaxf(hi[0], p.x); hi[1] = fmaxf(hi[1], p.y); hi[2] = fmaxf(hi[2], p.z);
-    }
-    __shared__ float sl[3][SG_RB], sh[3][SG_RB];
-    const int t = threadIdx.x;
-    for (int r = 0; r < 3; ++r) { sl[r][t] = lo[r]; sh[r][t] = hi[r]; }
-    __syncthreads();
-    for (int s = SG_RB / 2; s > 0; s >>= 1) {
-        if (t < s)
-            for (int r = 0; r < 3; ++r) { sl[r][t] = fminf(sl[r][t], sl[r][t + s]); sh[r][t] = fmaxf(sh[r][t], sh[r][t + s]); }
-        __syncthreads();
-    }
-    if (t == 0) for (int r = 0; r < 3; ++r) { part[6 * blockIdx.x + r] = sl[r][0]; part[6 * blockIdx.x + 3 + r] = sh[r][0]; }
-    if (__ballot(bad) != 0ull && (t & 63) == 0) atomicOr(&st->bad, 1u);
-}
-
 __global__ void sg_reset_kernel(SgState* st)
 {
     if (blockIdx.x == 0) {
@@ -648,7 +621,7 @@ __global__ __launch_bounds__(64) void sg_level_kernel(SgGrid g, const float4* __
         }
         // ---- phase B: the ball of the bound ----
         if (!done) {
-            const float b = sqrt_up_sg(bound);
+            const float b = sqrt_up(bound);
             int sl = 0;
             while (sl < 30 && g.cell * (float)(1u << sl) < 0.5f * b) ++sl;
             const float reach = b * 1.00001f + (g.cell * (float)(1u << sl) * 1e-3f + g.maxabs * 4e-6f);
@@ -778,7 +751,7 @@ __global__ __launch_bounds__(256) void sg_affected_kernel(const float4* __restri
             const float d2 = dk[orig];
             if (!(d2 < INFINITY)) hit = true; // fewer than k points so far: every appended point enters
             else {
-                const float r = sqrt_up_sg(d2) * 1.00001f + (g.cell * 1e-3f + g.maxabs * 4e-6f);
+                const float r = sqrt_up(d2) * 1.00001f + (g.cell * 1e-3f + g.maxabs * 4e-6f);
                 int l = lv_lmin;
                 while (l < lv_L - 1 && g.cell * (float)(1u << l) < r) ++l;
                 const int n0 = ((g.na[0] - 1) >> l) + 1, n1 = ((g.na[1] - 1) >> l) + 1, n2 = ((g.na[2] - 1) >> l) + 1;
@@ -884,14 +857,17 @@ icpmi_status selfgrid_knn(icpmi_ctx* c, const float4* d_pts, int64_t m, int k, i
     // (an appended cloud built from its previous copy: the box of the appended points, joined with the box that copy had)
     const int64_t bb_n = keep_w ? m - sub->m_old : m;
     const float4* bb_src = keep_w ? d_pts + sub->m_old : src;
-    const int rblocks = (int)std::min<int64_t>((bb_n + SG_RB - 1) / SG_RB, 256);
-    if (sg->d_part.ensure(c, (size_t)rblocks * 6) != ICPMI_OK) return ICPMI_ERR_HIP;
+    const int rblocks = (int)std::min<int64_t>((bb_n + BBOX_WG - 1) / BBOX_WG, 256);
+    if (sg->d_part.ensure(c, (size_t)rblocks * 7) != ICPMI_OK) return ICPMI_ERR_HIP; // six floats of box and one count of non-finite points per workgroup
+    unsigned* d_nbad = reinterpret_cast<unsigned*>(sg->d_part.get() + (size_t)rblocks * 6);
     hipLaunchKernelGGL(sg_reset_kernel, dim3(1), dim3(64), 0, c->stream, sg->d_state);
-    hipLaunchKernelGGL(sg_bbox_kernel, dim3(rblocks), dim3(SG_RB), 0, c->stream, bb_src, bb_n, sg->d_part, sg->d_state);
+    hipLaunchKernelGGL(bbox_partials_kernel<true>, dim3(rblocks), dim3(BBOX_WG), 0, c->stream, bb_src, bb_n, sg->d_part.get(), d_nbad, 3.0e38f);
     HIP_TRY(c, hipGetLastError());
     std::vector<float> part((size_t)rblocks * 6);
+    std::vector<unsigned> nbad((size_t)rblocks);
+    if (read_back2(c, part.data(), sg->d_part, part.size() * sizeof(float), nbad.data(), d_nbad, nbad.size() * sizeof(unsigned)) != ICPMI_OK) return ICPMI_ERR_HIP;
     unsigned bad = 0;
-    if (read_back2(c, part.data(), sg->d_part, part.size() * sizeof(float), &bad, &sg->d_state->bad, sizeof(unsigned)) != ICPMI_OK) return ICPMI_ERR_HIP;
+    for (unsigned v : nbad) bad += v;
     float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY}, maxabs = 0.f;
     if (keep_w) for (int r = 0; r < 3; ++r) { lo[r] = sg->prev_lo[r]; hi[r] = sg->prev_hi[r]; }
     for (int b = 0; b < rblocks; ++b)

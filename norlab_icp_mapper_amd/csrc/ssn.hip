@@ -24,8 +24,7 @@ struct SsnBox { float lo[3], hi[3]; };
 __device__ __forceinline__ unsigned ordered_bits(float x)
 {
     if (x == 0.f) x = 0.f; // -0 and +0 compare equal on the host: one key
-    const unsigned u = __float_as_uint(x);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+    return float_key(x);
 }
 
 __device__ __forceinline__ int widest_dim(const SsnBox& b)
@@ -33,28 +32,6 @@ __device__ __forceinline__ int widest_dim(const SsnBox& b)
     int dim = 0;
     for (int r = 1; r < 3; ++r) if (b.hi[r] - b.lo[r] > b.hi[dim] - b.lo[dim]) dim = r;
     return dim;
-}
-
-__global__ __launch_bounds__(256) void ssn_bbox_kernel(const float4* __restrict__ p, int64_t n, float* __restrict__ part)
-{
-    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-        const float4 q = p[i];
-        lo[0] = fminf(lo[0], q.x); lo[1] = fminf(lo[1], q.y); lo[2] = fminf(lo[2], q.z);
-        hi[0] = fmaxf(hi[0], q.x); hi[1] = fmaxf(hi[1], q.y); hi[2] = fmaxf(hi[2], q.z);
-    }
-    __shared__ float sh[6][256];
-    for (int r = 0; r < 3; ++r) { sh[r][threadIdx.x] = lo[r]; sh[3 + r][threadIdx.x] = hi[r]; }
-    __syncthreads();
-    for (int off = 128; off > 0; off >>= 1) {
-        if ((int)threadIdx.x < off)
-            for (int r = 0; r < 3; ++r) {
-                sh[r][threadIdx.x] = fminf(sh[r][threadIdx.x], sh[r][threadIdx.x + off]);
-                sh[3 + r][threadIdx.x] = fmaxf(sh[3 + r][threadIdx.x], sh[3 + r][threadIdx.x + off]);
-            }
-        __syncthreads();
-    }
-    if (threadIdx.x < 6) part[6 * blockIdx.x + threadIdx.x] = sh[threadIdx.x][0];
 }
 
 __global__ __launch_bounds__(256) void ssn_init_kernel(int64_t n, unsigned* __restrict__ nstart, unsigned* __restrict__ ncnt)
@@ -283,7 +260,7 @@ icpmi_status ssn_sample_dev(icpmi_ctx* c, const float4* d_in, int64_t n, float r
     constexpr int RB = 64;
     HIP_TRY(c, d_part.alloc(6 * RB));
     // root box
-    hipLaunchKernelGGL(ssn_bbox_kernel, dim3(RB), dim3(256), 0, c->stream, d_in, n, d_part.get());
+    hipLaunchKernelGGL(bbox_partials_kernel<false>, dim3(RB), dim3(BBOX_WG), 0, c->stream, d_in, n, d_part.get(), (unsigned*)nullptr, 0.f);
     float hp[6 * RB];
     if (read_back(c, hp, d_part.get(), sizeof hp) != ICPMI_OK) return ICPMI_ERR_HIP;
     SsnBox root;

@@ -8,7 +8,7 @@
 // The points of one idx form a voxel; the voxel's output point is the centroid of its members, summed in float in index order
 // starting from the first member (the smallest index), divided by the count; the output is in ascending first-member order.
 // Here:
-//   1. min / max / finiteness reduction (vg_bbox_kernel -> vg_grid_kernel: minB, numDiv), one small read-back for the limit checks;
+//   1. min / max / finiteness reduction (common.h: bbox_partials_kernel -> vg_grid_kernel: minB, numDiv), one small read-back for the limit checks;
 //   2. idx per point (vg_key_kernel), every division correctly rounded (HIP's default for float `/`; -ffp-contract=off);
 //   3. stable LSD radix sort of (idx, index) on all 32 bits (six 6-bit passes): a voxel is one run, its members in index order;
 //   4. run heads -> voxel starts (scan A, stays on the device), first members flagged in index order -> output slots (scan B,
@@ -25,6 +25,7 @@
 namespace {
 
 constexpr int VB = 256;
+static_assert(VB == BBOX_WG, "vg_grid_kernel folds the partials with bbox_fold");
 
 struct VgGrid {
     float minB[3];
@@ -33,70 +34,24 @@ struct VgGrid {
     int nonfinite;
 };
 
-__device__ __forceinline__ bool vg_finite(float v) { return fabsf(v) <= 3.402823466e38f; }
-
-// per-block min / max of x, y, z and a count of non-finite coordinates
-__global__ __launch_bounds__(VB) void vg_bbox_kernel(const float4* __restrict__ pts, int64_t n, float* __restrict__ part, unsigned* __restrict__ bad)
-{
-    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-    unsigned nb = 0;
-    for (int64_t i = (int64_t)blockIdx.x * VB + threadIdx.x; i < n; i += (int64_t)gridDim.x * VB) {
-        const float4 p = pts[i];
-        nb += (vg_finite(p.x) && vg_finite(p.y) && vg_finite(p.z)) ? 0u : 1u;
-        lo[0] = fminf(lo[0], p.x); lo[1] = fminf(lo[1], p.y); lo[2] = fminf(lo[2], p.z);
-        hi[0] = fmaxf(hi[0], p.x); hi[1] = fmaxf(hi[1], p.y); hi[2] = fmaxf(hi[2], p.z);
-    }
-    __shared__ float sl[3][VB], sh[3][VB];
-    __shared__ unsigned sb[VB];
-    const int t = threadIdx.x;
-    for (int r = 0; r < 3; ++r) { sl[r][t] = lo[r]; sh[r][t] = hi[r]; }
-    sb[t] = nb;
-    __syncthreads();
-    for (int s = VB / 2; s > 0; s >>= 1) {
-        if (t < s) {
-            for (int r = 0; r < 3; ++r) { sl[r][t] = fminf(sl[r][t], sl[r][t + s]); sh[r][t] = fmaxf(sh[r][t], sh[r][t + s]); }
-            sb[t] += sb[t + s];
-        }
-        __syncthreads();
-    }
-    if (t < 3) { part[6 * blockIdx.x + t] = sl[t][0]; part[6 * blockIdx.x + 3 + t] = sh[t][0]; }
-    if (t == 0) bad[blockIdx.x] = sb[0];
-}
-
 // one block: the blocks' partials -> the grid (min / max are exact, so the order of the reduction does not matter)
 __global__ __launch_bounds__(VB) void vg_grid_kernel(const float* __restrict__ part, const unsigned* __restrict__ bad, int nparts, float vx, float vy,
                                                      float vz, VgGrid* __restrict__ g)
 {
-    __shared__ float sl[3][VB], sh[3][VB];
-    __shared__ unsigned sb[VB];
-    const int t = threadIdx.x;
-    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-    unsigned nb = 0;
-    for (int b = t; b < nparts; b += VB) {
-        for (int r = 0; r < 3; ++r) { lo[r] = fminf(lo[r], part[6 * b + r]); hi[r] = fmaxf(hi[r], part[6 * b + 3 + r]); }
-        nb += bad[b];
-    }
-    for (int r = 0; r < 3; ++r) { sl[r][t] = lo[r]; sh[r][t] = hi[r]; }
-    sb[t] = nb;
-    __syncthreads();
-    for (int s = VB / 2; s > 0; s >>= 1) {
-        if (t < s) {
-            for (int r = 0; r < 3; ++r) { sl[r][t] = fminf(sl[r][t], sl[r][t + s]); sh[r][t] = fmaxf(sh[r][t], sh[r][t + s]); }
-            sb[t] += sb[t + s];
-        }
-        __syncthreads();
-    }
-    if (t == 0) {
+    float lo[3], hi[3];
+    unsigned nbad;
+    bbox_fold<true>(part, bad, nparts, lo, hi, nbad);
+    if (threadIdx.x == 0) {
         const float vs[3] = {vx, vy, vz};
         for (int r = 0; r < 3; ++r) {
-            const float minB = sl[r][0] / vs[r];
-            const float maxB = sh[r][0] / vs[r];
+            const float minB = lo[r] / vs[r];
+            const float maxB = hi[r] / vs[r];
             const float nd = (1.f + maxB) - minB;
             g->minB[r] = minB;
             g->numDivF[r] = nd;
             g->numDiv[r] = (nd >= 0.f && nd < 4294967296.f) ? (unsigned)nd : 0u; // (out-of-range values are rejected by the host)
         }
-        g->nonfinite = sb[0] ? 1 : 0;
+        g->nonfinite = nbad ? 1 : 0;
     }
 }
 
@@ -242,7 +197,7 @@ icpmi_status ops_voxel_grid(icpmi_ctx* c, const float* in4, int64_t n, const flo
 
     HIP_TRY(c, hipMemcpyAsync(d_in, in4, (size_t)n * sizeof(float4), hipMemcpyHostToDevice, c->stream));
     if (rows > 0) HIP_TRY(c, hipMemcpyAsync(d_desc, desc, (size_t)rows * n * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(vg_bbox_kernel, dim3(rb), dim3(VB), 0, c->stream, (const float4*)d_in, n, d_part, d_bad);
+    hipLaunchKernelGGL(bbox_partials_kernel<true>, dim3(rb), dim3(BBOX_WG), 0, c->stream, (const float4*)d_in, n, d_part, d_bad, 3.402823466e38f /* FLT_MAX */);
     hipLaunchKernelGGL(vg_grid_kernel, dim3(1), dim3(VB), 0, c->stream, (const float*)d_part, (const unsigned*)d_bad, rb, vsize[0], vsize[1], vsize[2], d_grid);
     HIP_TRY(c, hipGetLastError());
     VgGrid g;
