@@ -356,7 +356,9 @@ icpmi_status icpmi_voxel_keep_first(icpmi_handle h, const float* in4, int64_t n,
 /* `DynamicPointsMapperModule::inPlaceUpdateMap` (DynamicPointsMapperModule.cpp:34-172; parameters :6-13).
  * `to_sensor` = pose^-1 (col-major 4x4, :51,57); input4 / map4 in the map frame; map_normals3 = descriptor `normals`
  * of the map; prob_dynamic (m floats) = descriptor `probabilityDynamic` of the map, updated in place for every
- * map point within sensor_max_range that has an input beam within 2 * beam_half_angle in (elevation, azimuth). */
+ * map point within sensor_max_range that has an input beam within 2 * beam_half_angle in (elevation, azimuth).
+ * beam_half_angle <= 0: ICPMI_ERR_INVALID_ARG; so small that the angular grid would need more than 2^28 buckets (below about 2.7e-4 rad):
+ * ICPMI_ERR_UNSUPPORTED.  Either way nothing is touched -- in icpmi_map_update_chain too, where both are checked before the program starts. */
 typedef struct icpmi_dynpts_params {
     float threshold_dynamic; /* 0.6  */
     float alpha;             /* 0.8  */

@@ -1084,6 +1084,7 @@ icpmi_status ops_move_dev(icpmi_ctx* c, const float T[16], float4* d_pts, float*
 icpmi_status dynpts_dev(icpmi_ctx* c, const icpmi_dynpts_params* prm, const float T[16], const float4* d_in, int64_t n,
                         const float4* d_map, const float* d_nrm, int64_t m, float* d_prob, hipStream_t stream);
 bool dynpts_side_ok(const icpmi_dynpts_params* prm);
+icpmi_status dynpts_check(icpmi_ctx* c, const icpmi_dynpts_params* prm); // ICPMI_ERR_UNSUPPORTED: a half angle whose angular grid is too large
 
 icpmi_status ops_transform(icpmi_ctx* c, const float T[16], const float* in4, int64_t n, float* out4,
                            const float* in_n3, float* out_n3);

@@ -12,7 +12,30 @@ namespace {
 // asin / atan2 go through double and are rounded once (shared with the oracle: libm and the device
 // library then agree bit for bit); everything else is the reference's float arithmetic, with the
 // sub-expressions it writes with a double literal (`1.`) evaluated in double.
-struct DynGrid { float cell; int ne, na; float r2; };   // r2 = (2 beamHalfAngle)^2: the search radius, DYN_RINGS cells wide
+#ifndef DYN_RINGS
+#define DYN_RINGS 2   // buckets per search radius (1: 3 x 3 block of one-radius buckets, the layout until r4)
+#endif
+struct DynGrid { float cell; int ne, na; float r2; };   // r2 = (2 beamHalfAngle)^2: the search radius, just under DYN_RINGS cells
+constexpr int64_t DYN_MAX_CELLS = 1ll << 28;
+
+// The grid of a half angle and its number of buckets: the ONE place either comes from (dynpts_dev sizes its tables with it, dynpts_side_ok
+// picks the scan route by it, dynpts_check refuses by it).  More than DYN_MAX_CELLS buckets: g is not usable (the counts of a half angle
+// near zero fit no integer; they stay floats until they are known to be small).
+int64_t dyn_grid(const icpmi_dynpts_params* prm, DynGrid& g)
+{
+    const float reach = 2 * prm->beam_half_angle;
+    g.r2 = reach * reach;
+    // A bucket is a little WIDER than reach / DYN_RINGS.  The bucket of an angle is floorf((angle + c) / cell) in float32: a sum and a
+    // quotient that round, by up to 2e-3 buckets for the smallest half angle served.  With buckets of exactly half the reach, a point one
+    // ulp below a bucket edge was rounded UP into the bucket above while a beam just under 2 * beamHalfAngle below it stayed where it
+    // was: three buckets apart, outside the (2 R + 1)^2 block, and the search missed a beam the reference finds.  1 / 256 of slack per
+    // bucket keeps every beam within the reach inside the block whatever the rounding does (R / 256 = 7.8e-3 buckets to spare).
+    g.cell = reach / (float)DYN_RINGS * (1.f + 1.f / 256.f);
+    const float fe = floorf(3.14159265358979f / g.cell) + 2.f, fa = floorf(6.28318530717959f / g.cell) + 2.f;
+    if (!(fe <= (float)DYN_MAX_CELLS && fa <= (float)DYN_MAX_CELLS)) { g.ne = g.na = 0; return INT64_MAX; }
+    g.ne = (int)fe; g.na = (int)fa;   // (exact: both are integers below 2^24 wherever the product passes the limit)
+    return (int64_t)g.ne * g.na;
+}
 
 __device__ __forceinline__ void to_spherical(float x, float y, float z, float& radius, float& elev, float& azim)
 {
@@ -73,9 +96,6 @@ __global__ __launch_bounds__(256) void dyn_scatter_kernel(int64_t n, const unsig
 
 #ifndef DYN_INFLIGHT
 #define DYN_INFLIGHT 4
-#endif
-#ifndef DYN_RINGS
-#define DYN_RINGS 2   // buckets per search radius (1: 3 x 3 block of one-radius buckets, the layout until r4)
 #endif
 struct DynPrm { float threshold_dynamic, alpha, beta, beam_half_angle, epsilon_a, epsilon_d, sensor_max_range; };
 
@@ -211,13 +231,8 @@ icpmi_status dynpts_dev(icpmi_ctx* c, const icpmi_dynpts_params* prm, const floa
 {
     if (n == 0 || m == 0) return ICPMI_OK; // "if (beams.empty()) return"
     DynGrid g;
-    const float reach = 2 * prm->beam_half_angle;
-    g.r2 = reach * reach;
-    g.cell = reach / (float)DYN_RINGS;
-    g.ne = (int)floorf(3.14159265358979f / g.cell) + 2;
-    g.na = (int)floorf(6.28318530717959f / g.cell) + 2;
-    const int64_t ncells = (int64_t)g.ne * g.na;
-    if (ncells > (1ll << 28)) { c->last_error = "dynamic_points_update: beamHalfAngle too small for the angular grid"; return ICPMI_ERR_UNSUPPORTED; }
+    const int64_t ncells = dyn_grid(prm, g);
+    if (ncells > DYN_MAX_CELLS) return dynpts_check(c, prm); // (the chain has asked already; the stage entry has not)
     DynPrm dp = {prm->threshold_dynamic, prm->alpha, prm->beta, prm->beam_half_angle, prm->epsilon_a, prm->epsilon_d, prm->sensor_max_range};
     float4* d_bx = scratch_get<float4>(c, 10, (size_t)n);
     float2* d_ba = scratch_get<float2>(c, 11, (size_t)n);
@@ -246,9 +261,17 @@ icpmi_status dynpts_dev(icpmi_ctx* c, const icpmi_dynpts_params* prm, const floa
 // whether the side scan of dynpts_dev is available for these parameters (the chain asks before it forks)
 bool dynpts_side_ok(const icpmi_dynpts_params* prm)
 {
-    const float cell = 2 * prm->beam_half_angle / (float)DYN_RINGS;
-    const int64_t ncells = ((int64_t)floorf(3.14159265358979f / cell) + 2) * ((int64_t)floorf(6.28318530717959f / cell) + 2);
-    return ncells <= (1ll << 28) && device_scan_side_ok((int)ncells);
+    DynGrid g;
+    const int64_t ncells = dyn_grid(prm, g);
+    return ncells <= DYN_MAX_CELLS && device_scan_side_ok((int)ncells);
+}
+
+// whether the module can run with these parameters at all: the map-update chain asks before it touches the resident map
+icpmi_status dynpts_check(icpmi_ctx* c, const icpmi_dynpts_params* prm)
+{
+    DynGrid g;
+    if (dyn_grid(prm, g) > DYN_MAX_CELLS) { c->last_error = "dynamic_points_update: beamHalfAngle too small for the angular grid"; return ICPMI_ERR_UNSUPPORTED; }
+    return ICPMI_OK;
 }
 
 icpmi_status ops_dynamic_points_update(icpmi_ctx* c, const icpmi_dynpts_params* prm, const float to_sensor[16], const float* in4, int64_t n,

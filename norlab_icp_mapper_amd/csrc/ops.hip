@@ -489,7 +489,14 @@ icpmi_status ops_map_update_chain(icpmi_ctx* c, const float4* d_scan, int64_t n,
         const icpmi_map_op& op = ops[i];
         switch (op.type) {
         case ICPMI_MOP_POINT_DISTANCE: if (!(op.f[0] >= 0.f)) { c->last_error = "InvalidParameter: minDistNewPoint must be >= 0"; return ICPMI_ERR_INVALID_ARG; } break;
-        case ICPMI_MOP_DYNAMIC_POINTS: uses_scalar = true; if (!(op.f[3] > 0.f)) { c->last_error = "InvalidParameter: beamHalfAngle must be > 0"; return ICPMI_ERR_INVALID_ARG; } break;
+        case ICPMI_MOP_DYNAMIC_POINTS: {
+            uses_scalar = true;
+            if (!(op.f[3] > 0.f)) { c->last_error = "InvalidParameter: beamHalfAngle must be > 0"; return ICPMI_ERR_INVALID_ARG; }
+            const icpmi_dynpts_params prm = {op.f[0], op.f[1], op.f[2], op.f[3], op.f[4], op.f[5], op.f[6]};
+            const icpmi_status ok = dynpts_check(c, &prm); // a half angle the module refuses: here, while the resident map is still whole
+            if (ok != ICPMI_OK) return ok;
+            break;
+        }
         case ICPMI_MOP_VOXEL: if (!(op.f[0] > 0.f) || (op.i != 0 && op.i != 1)) { c->last_error = "map_update_chain: voxel edge must be > 0 and samplingMethod 0 or 1"; return ICPMI_ERR_INVALID_ARG; } break;
         case ICPMI_MOP_SURFACE_NORMALS: if (op.i < 1 || op.i > ICPMI_MAX_K) { c->last_error = "surface_normals: knn must be in [1, 32]"; return ICPMI_ERR_INVALID_ARG; } break;
         case ICPMI_MOP_CUT_SCALAR: uses_scalar = true; break;
