@@ -455,6 +455,36 @@ typedef struct {
 icpmi_status icpmi_covariance_sampling(icpmi_handle h, const float* in4, int64_t n, const float* normals3, int64_t nb_sample, int32_t torque_norm,
                                        int32_t* order_out, int64_t* n_out, icpmi_covsamp_info* info_out);
 
+/* `NormalSpaceDataPointsFilter{nbSample 5000, seed 1, epsilon 0.09817}` (libpointmatcher DataPointsFilters/NormalSpace, Rusinkiewicz &
+ * Levoy 2001, AS RECALLED: upstream's source is not on hand):
+ *   1. nb_sample >= n: the cloud is returned unchanged (order_out = 0 .. n - 1, *n_out = n, bucket_out untouched), normals or not.
+ *      Otherwise normals3 (3 per point, point-major) is required: NULL gives ICPMI_ERR_MISSING_NORMALS.
+ *   2. The bucket of point i, from its normal (nx, ny, nz) taken as given (upstream assumes unit length):
+ *        theta = (float) acos((double) clamp(nz, -1, 1));
+ *        phi_d = atan2((double) ny, (double) nx), plus 2 pi (in double) when negative; phi = (float) phi_d
+ *      (both go through double and are rounded once, as the angles of the DynamicPoints module: libm and the device library agree);
+ *        bt = (unsigned) floorf(theta / epsilon), bp = (unsigned) floorf(phi / epsilon)              -- float32
+ *        stride = (unsigned) floorf(6.2831855f / epsilon);   bucket = bt * stride + bp.
+ *      This is upstream's expression, including the aliasing of a partial last phi column (bp == stride) into the next theta row.
+ *      The tables hold floorf(3.14159274f / epsilon) * stride + stride + 1 buckets, the largest index the two floors can give
+ *      (below 2^14 for every epsilon served).
+ *   3. r_i = the (i + 1)-th value of std::minstd_rand seeded with `seed` (seeds 0 and 2147483647 are the state 1, as seed 1).  Within a
+ *      bucket, points are drawn in ascending r_i (the r_i are distinct; equal ones would go in ascending index).  DEVIATION: upstream
+ *      shuffles the indices with std::shuffle(std::mt19937(seed)) -- libstdc++'s own serial Fisher-Yates -- and takes from the back of
+ *      each bucket; ours is a permutation any language reproduces and a device evaluates per point.
+ *   4. Round-robin, in closed form: c_b = the population of bucket b, S(R) = sum_b min(c_b, R), R* = the largest R with
+ *      S(R) <= nb_sample, rem = nb_sample - S(R*).  Kept: every point whose 0-based rank in its bucket is < R*, and the points of rank
+ *      R* in the first `rem` buckets, in ascending bucket index, among those with c_b > R*: exactly nb_sample points.  This is
+ *      upstream's loop: one point per non-empty bucket per round, in ascending bucket index, until nb_sample is reached.
+ *   5. order_out (capacity min(n, nb_sample)) = the kept indices in ASCENDING order (upstream sorts its kept indices before it moves
+ *      the columns), *n_out = min(n, nb_sample); nb_sample == 0 gives an empty cloud.
+ * bucket_out (n entries, may be NULL) = the device's bucket of every point, from which the selection replays bit for bit.
+ * ICPMI_ERR_INVALID_ARG (last_error says why): nb_sample < 0, seed < 0, epsilon outside [0.04908, 3.14159], a planar handle
+ * (icpmi_config::is_2d), non-finite coordinates or normals.  n > 2^31 - 1: ICPMI_ERR_UNSUPPORTED.  Entirely on the device, no
+ * atomics: two calls give the same bits (csrc/normalspace.hip). */
+icpmi_status icpmi_normal_space_sampling(icpmi_handle h, const float* in4, int64_t n, const float* normals3, int64_t nb_sample, int32_t seed, float epsilon,
+                                         int32_t* order_out, int64_t* n_out, int32_t* bucket_out);
+
 /* `Map::updateLocalPointCloud` (Map.cpp:502-534) for a whole module chain on the RESIDENT map: the mapper modules
  * (`mapperModuleVec`, Map.cpp:506-521) and then the post filters (Map.cpp:523-525) run as one program on the device copy
  * of the map; only the scan crosses PCIe.  The device tracks the features, the `normals` and ONE scalar descriptor of

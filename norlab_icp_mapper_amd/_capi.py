@@ -150,6 +150,7 @@ SYMBOLS = [
     ("icpmi_octree_sample", C.c_int, [_P, _P, C.c_int64, C.c_float, C.c_int32, C.c_int32, _P, _P, _P]),
     ("icpmi_voxel_grid", C.c_int, [_P, _P, C.c_int64, _P, C.c_int32, _P, C.c_int32, _P, _P, _P, _P]),
     ("icpmi_covariance_sampling", C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, C.c_int32, _P, _P, _P]),
+    ("icpmi_normal_space_sampling", C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, C.c_int32, C.c_float, _P, _P, _P]),
     ("icpmi_sensor_model", C.c_int, [_P, _P, C.c_int64, _P, _P, _P, C.c_int32, _P, _P, _P, _P]),
     ("icpmi_map_update_chain", C.c_int, [_P, _P, C.c_int64, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, _P, C.c_int64, _P, _P]),
     ("icpmi_map_update_chain_staged", C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, _P, C.c_int64, _P, _P]),

@@ -1100,6 +1100,29 @@ icpmi_status icpmi_covariance_sampling(icpmi_handle h, const float* in4, int64_t
     return s;
 }
 
+icpmi_status icpmi_normal_space_sampling(icpmi_handle h, const float* in4, int64_t n, const float* normals3, int64_t nb_sample, int32_t seed, float epsilon,
+                                         int32_t* order_out, int64_t* n_out, int32_t* bucket_out)
+{
+    CHECK_H(h);
+    if (n_out) *n_out = 0;
+    if (n < 0 || !n_out || (n > 0 && (!in4 || (nb_sample > 0 && !order_out)))) { h->last_error = "normal_space_sampling: bad arguments"; return ICPMI_ERR_INVALID_ARG; }
+    if (nb_sample < 0) { h->last_error = "normal_space_sampling: nbSample must be >= 0"; return ICPMI_ERR_INVALID_ARG; }
+    if (seed < 0) { h->last_error = "normal_space_sampling: seed must be in [0, 2147483647]"; return ICPMI_ERR_INVALID_ARG; }
+    if (!(epsilon >= 0.04908f && epsilon <= 3.14159f)) { h->last_error = "normal_space_sampling: epsilon must be in [0.04908, 3.14159]"; return ICPMI_ERR_INVALID_ARG; }
+    if (h->cfg.is_2d) { h->last_error = "normal_space_sampling: planar (2-D) clouds are not supported (upstream takes 3-D clouds only)"; return ICPMI_ERR_INVALID_ARG; }
+    if (n > 0x7fffffffll) { h->last_error = "normal_space_sampling: more than 2^31 - 1 points"; return ICPMI_ERR_UNSUPPORTED; }
+    if (nb_sample >= n) {
+        for (int64_t i = 0; i < n; ++i) order_out[i] = (int32_t)i;
+        *n_out = n;
+        return ICPMI_OK;
+    }
+    if (!normals3) { h->last_error = "normal_space_sampling: the cloud has no normals (InvalidField normals)"; return ICPMI_ERR_MISSING_NORMALS; }
+    if (nb_sample == 0) return ICPMI_OK;
+    const icpmi_status s = ops_normal_space_sampling(h, in4, n, normals3, nb_sample, (unsigned)seed, epsilon, order_out, bucket_out);
+    if (s == ICPMI_OK) *n_out = nb_sample;
+    return s;
+}
+
 icpmi_status icpmi_voxel_keep_first(icpmi_handle h, const float* in4, int64_t n, float edge, uint8_t* keep)
 {
     return icpmi_voxel_keep(h, in4, n, edge, 0, keep);

@@ -846,6 +846,19 @@ __device__ __forceinline__ unsigned long long mix64(unsigned long long x)
     return x;
 }
 
+__device__ __forceinline__ unsigned minstd_mulmod(unsigned a, unsigned b) { return (unsigned)(((unsigned long long)a * b) % 2147483647ull); }
+
+// the n-th value (n >= 1) of std::minstd_rand seeded with `seed`: x0 48271^n mod (2^31 - 1) by square-and-multiply -- no sequential generator.
+// [rand.predef]: the 10 000th value of a default-constructed (seed 1) minstd_rand is 399268537 (tests/test_gpu_pins.py holds this function to it).
+__device__ __forceinline__ unsigned minstd_nth(unsigned seed, unsigned n)
+{
+    unsigned x = seed % 2147483647u;
+    if (x == 0u) x = 1u;
+    unsigned e = n, base = 48271u, acc = 1u;
+    while (e) { if (e & 1u) acc = minstd_mulmod(acc, base); base = minstd_mulmod(base, base); e >>= 1; }
+    return minstd_mulmod(acc, x);
+}
+
 // float -> unsigned whose integer order is the float order (-0 sorts below +0), and back
 __device__ __forceinline__ unsigned float_key(float f) { const unsigned u = __float_as_uint(f); return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }
 __device__ __forceinline__ float float_key_inv(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
@@ -1147,3 +1160,5 @@ icpmi_status ops_voxel_grid(icpmi_ctx* c, const float* in4, int64_t n, const flo
                             int32_t* order_out, float* out4, float* desc_out, int64_t* n_out);
 icpmi_status ops_covariance_sampling(icpmi_ctx* c, const float* in4, int64_t n, const float* normals3, int64_t nb, int torque_norm, int32_t* order_out,
                                      icpmi_covsamp_info* info_out);
+icpmi_status ops_normal_space_sampling(icpmi_ctx* c, const float* in4, int64_t n, const float* normals3, int64_t nb, unsigned seed, float eps,
+                                       int32_t* order_out, int32_t* bucket_out);

@@ -150,18 +150,7 @@ __global__ __launch_bounds__(128) void ssn_fuse_kernel(const float4* __restrict_
     for (unsigned k = 0; k < cnt; ++k) draws[pos + k] = ok ? 1u : 0u;
 }
 
-__device__ __forceinline__ unsigned minstd_mulmod(unsigned a, unsigned b) { return (unsigned)(((unsigned long long)a * b) % 2147483647ull); }
-
-// the n-th value (n >= 1) of std::minstd_rand seeded with `seed`: x0 48271^n mod (2^31 - 1) by square-and-multiply -- no sequential generator.
-// [rand.predef]: the 10 000th value of a default-constructed (seed 1) minstd_rand is 399268537 (tests/test_gpu_pins.py holds this function to it).
-__device__ __forceinline__ unsigned minstd_nth(unsigned seed, unsigned n)
-{
-    unsigned x = seed % 2147483647u;
-    if (x == 0u) x = 1u;
-    unsigned e = n, base = 48271u, acc = 1u;
-    while (e) { if (e & 1u) acc = minstd_mulmod(acc, base); base = minstd_mulmod(base, base); e >>= 1; }
-    return minstd_mulmod(acc, x);
-}
+// (minstd_mulmod / minstd_nth: common.h, shared with normalspace.hip)
 __global__ void minstd_nth_kernel(unsigned seed, unsigned n, unsigned* __restrict__ out) { if (threadIdx.x == 0 && blockIdx.x == 0) out[0] = minstd_nth(seed, n); }
 
 // keep[pos] = the point's random number (the (rank + 1)-th of std::minstd_rand seeded with `seed`) is below ratio

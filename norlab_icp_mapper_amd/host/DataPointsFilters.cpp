@@ -550,6 +550,27 @@ struct CovarianceSamplingFilter : DataPointsFilter {
     }
 };
 
+// NormalSpaceDataPointsFilter{nbSample, seed, epsilon} (libpointmatcher, Rusinkiewicz & Levoy 2001, as recalled; the formulation is
+// icpmi_normal_space_sampling's in include/icpmi.h): keeps nbSample points spread evenly over the angular buckets of the normals, in
+// ascending index order.  The draw within a bucket follows std::minstd_rand(seed), never a random device: always repeatable().  The
+// whole selection runs on the device; here features, every descriptor and `times` follow the kept indices.
+struct NormalSpaceFilter : DataPointsFilter {
+    int64_t nbSample = 5000; int seed = 1; float epsilon = 0.09817f;
+    icpmi_handle h = nullptr;
+    void inPlaceFilter(DataPoints& c) const override {
+        const size_t n = c.getNbPoints();
+        if ((size_t)nbSample >= n) return;
+        const Descriptor& nrm = c.getDescriptorByName("normals"); // (InvalidField without normals, as upstream)
+        if (nrm.span != 3) throw InvalidField("descriptor normals must have 3 rows");
+        if (!h) throw std::logic_error("NormalSpaceDataPointsFilter needs a GPU context");
+        std::vector<int32_t> order((size_t)nbSample);
+        int64_t m = 0;
+        GpuICPSequence::check(h, icpmi_normal_space_sampling(h, c.features.data(), (int64_t)n, nrm.data.data(), nbSample, seed, epsilon, order.data(), &m,
+                                                             nullptr));
+        c = c.select(order.data(), (size_t)m);
+    }
+};
+
 float getf(const yaml::Node& p, const char* k, float def) { return p[k] ? p[k].as<float>() : def; }
 int geti(const yaml::Node& p, const char* k, int def) { return p[k] ? p[k].as<int>() : def; }
 
@@ -706,6 +727,27 @@ std::shared_ptr<DataPointsFilter> createDataPointsFilter(const std::string& name
         f->torqueNorm = geti(p, "torqueNorm", 1);
         if (f->nbSample < 0) throw InvalidParameter(name + ": nbSample must be >= 0");
         if (f->torqueNorm < 0 || f->torqueNorm > 2) throw InvalidParameter(name + ": torqueNorm must be 0 (L1), 1 (Lavg) or 2 (Lmax)");
+        f->h = ctx;
+        return f;
+    }
+    if (name == "NormalSpaceDataPointsFilter") {
+        requireKnown(p, {"nbSample", "seed", "epsilon"}, name);
+        auto f = std::make_shared<NormalSpaceFilter>();
+        // (64-bit: a seed above 2147483647 is refused, not wrapped)
+        auto getll = [&](const char* k, long long def) {
+            if (!p[k]) return def;
+            const std::string s = p[k].str();
+            char* end = nullptr;
+            const long long v = std::strtoll(s.c_str(), &end, 10);
+            if (end == s.c_str() || *end) throw yaml::Exception("bad integer: " + s);
+            return v;
+        };
+        const long long nb = getll("nbSample", 5000), seed = getll("seed", 1);
+        f->epsilon = getf(p, "epsilon", 0.09817f);
+        if (nb < 1) throw InvalidParameter(name + ": nbSample must be >= 1");
+        if (seed < 0 || seed > 2147483647ll) throw InvalidParameter(name + ": seed must be in [0, 2147483647]");
+        if (!(f->epsilon >= 0.04908f && f->epsilon <= 3.14159f)) throw InvalidParameter(name + ": epsilon must be in [0.04908, 3.14159]");
+        f->nbSample = nb; f->seed = (int)seed;
         f->h = ctx;
         return f;
     }

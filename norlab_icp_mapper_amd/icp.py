@@ -660,6 +660,28 @@ class ICPSequence:
             out["keep"] = out["keep"].astype(bool)
         return out
 
+    def normalSpaceSampling(self, cloud, normals, nb_sample=5000, seed=1, epsilon=0.09817, with_buckets=False):
+        """NormalSpaceDataPointsFilter{nbSample, seed, epsilon} (the formulation of icpmi_normal_space_sampling, as recalled): cloud
+        (N, 4), normals (N, 3) or None.  Returns the kept indices in ascending order (int32), or (order, buckets) with buckets (N,)
+        int32 = the device's angular bucket of every point -- None when nb_sample >= N or nb_sample == 0 (nothing sampled)."""
+        c = _f32c(cloud, 4)
+        n = c.shape[0]
+        nptr = None
+        if normals is not None:
+            normals = _f32c(normals, 3)
+            if normals.shape[0] != n:
+                raise InvalidParameter("normals / cloud size mismatch")
+            nptr = normals.ctypes.data
+        order = np.empty(max(0, min(n, int(nb_sample))), dtype=np.int32)
+        buckets = np.empty(n, dtype=np.int32) if with_buckets else None
+        m = C.c_int64(0)
+        self._check(self._lib.icpmi_normal_space_sampling(self._h, c.ctypes.data, n, nptr, int(nb_sample), int(seed), float(epsilon),
+                                                          order.ctypes.data, C.byref(m), None if buckets is None else buckets.ctypes.data))
+        order = order[:m.value].copy()
+        if not with_buckets:
+            return order
+        return order, (None if nb_sample >= n or nb_sample == 0 else buckets)
+
     def voxelKeep(self, cloud, edge, method=0):
         """Same lattice, representative by `samplingMethod`: 0 first point, 1 pseudo-random point (smallest fmix32 of the index)."""
         c = _f32c(cloud, 4)
