@@ -485,6 +485,21 @@ icpmi_status icpmi_covariance_sampling(icpmi_handle h, const float* in4, int64_t
 icpmi_status icpmi_normal_space_sampling(icpmi_handle h, const float* in4, int64_t n, const float* normals3, int64_t nb_sample, int32_t seed, float epsilon,
                                          int32_t* order_out, int64_t* n_out, int32_t* bucket_out);
 
+/* `MaxDensityDataPointsFilter{maxDensity 10, seed 1}` (libpointmatcher DataPointsFilters/MaxDensity; the host shell's MaxDensityFilter,
+ * host/DataPointsFilters.cpp, is the definition and this entry restates it bit for bit): a point in a region denser than max_density
+ * survives with probability max_density / density, decided by ONE std::minstd_rand stream that only the dense points draw from.
+ *   dense_i = densities[i] > max_density                       (a NaN density compares false: not dense, the point is kept)
+ *   rank_i  = the number of dense points with an index below i
+ *   v_i     = the (rank_i + 1)-th value of std::minstd_rand (x <- 48271 x mod 2^31 - 1) seeded with (uint32_t) seed % 2147483647, 0 taken
+ *             as 1 (the engine's constructor): seeds 0, 1 and 2147483647 are the same stream, a negative seed wraps through uint32_t
+ *   u_i     = (float) v_i / 2147483645.0f                      (randomSamplingMethod 0, "direct": x / float(max - min))
+ *   keep[i] = dense_i ? (u_i < max_density / densities[i]) : 1 (float32, each division correctly rounded, nothing contracted; a +inf
+ *             density gives the bound 0 and the point is dropped: u < 0 is false)
+ * The rank is an exclusive prefix count on the device and v_i comes from a skip-ahead, so every point decides on its own: no atomics,
+ * two calls give the same bits (csrc/maxdensity.hip).  max_density not finite or not > 0: ICPMI_ERR_INVALID_ARG; n == 0: ICPMI_OK;
+ * n > 2^31 - 1: ICPMI_ERR_UNSUPPORTED. */
+icpmi_status icpmi_max_density_keep(icpmi_handle h, const float* densities, int64_t n, float max_density, int32_t seed, uint8_t* keep);
+
 /* `Map::updateLocalPointCloud` (Map.cpp:502-534) for a whole module chain on the RESIDENT map: the mapper modules
  * (`mapperModuleVec`, Map.cpp:506-521) and then the post filters (Map.cpp:523-525) run as one program on the device copy
  * of the map; only the scan crosses PCIe.  The device tracks the features, the `normals` and ONE scalar descriptor of
@@ -498,8 +513,16 @@ icpmi_status icpmi_normal_space_sampling(icpmi_handle h, const float* in4, int64
  *                              (OctreeMapperModule.cpp:8-12,35-39 -> OctreeGridDataPointsFilter: bounding-cube root, split until the
  *                              edge is <= maxSizeByNode or the node holds <= maxPointByNode points, one point per leaf, the map left
  *                              in leaf-visiting order); ICPMI_MOP_VOXEL is the fixed-lattice decimation kept for callers that want it
- *   ICPMI_MOP_SURFACE_NORMALS  i = knn                                  (post filter, examples/config.yaml:26-27)
+ *   ICPMI_MOP_SURFACE_NORMALS  i = knn, f[0] = keepDensities 0 | 1      (post filter, examples/config.yaml:26-27)
  *   ICPMI_MOP_CUT_SCALAR       f[0] = threshold, i = useLargerThan      (CutAtDescriptorThresholdDataPointsFilter, config.yaml:29-32)
+ *   ICPMI_MOP_MAX_DENSITY      f[0] = maxDensity, i = seed              (post filter: icpmi_max_density_keep on the `densities` row, then
+ *                              the compaction)
+ * The `densities` row: a SURFACE_NORMALS step with f[0] = 1 writes it (icpmi_surface_normals_ex's densities, same pass).  Every program
+ * starts without it (the scan has none, so by DataPoints::concatenate's rule the field does not survive the modules); from that step on
+ * it moves with the points through every compaction of the program, it is not touched by the sensor-frame round trip, and it stays
+ * resident for icpmi_get_map_densities until the next program, icpmi_set_map or append.  A MAX_DENSITY step with no such step in front
+ * of it in the same program is ICPMI_ERR_INVALID_ARG ("InvalidField: MaxDensityDataPointsFilter: Error, no densities found in
+ * descriptors."), checked before the program starts: the resident map is untouched.
  * The first n_modules entries are mapper modules: on a handle without a map the first one creates the map from the scan
  * (`createMap`: PointDistance / DynamicPoints take the scan as it is, Voxel decimates it) and the others update it with
  * the same scan (Map.cpp:508-516).  scan_scalar (n floats) is the scan's value of the tracked scalar, NULL if the chain
@@ -517,7 +540,7 @@ icpmi_status icpmi_normal_space_sampling(icpmi_handle h, const float* in4, int64
  * an append-only chain downloads a few kilobytes instead of the whole vector. */
 typedef enum {
     ICPMI_MOP_POINT_DISTANCE = 0, ICPMI_MOP_DYNAMIC_POINTS = 1, ICPMI_MOP_VOXEL = 2, ICPMI_MOP_SURFACE_NORMALS = 3, ICPMI_MOP_CUT_SCALAR = 4,
-    ICPMI_MOP_OCTREE = 5
+    ICPMI_MOP_OCTREE = 5, ICPMI_MOP_MAX_DENSITY = 6
 } icpmi_map_op_type;
 typedef struct icpmi_map_op { int32_t type; int32_t i; float f[7]; } icpmi_map_op;
 icpmi_status icpmi_map_update_chain(icpmi_handle h, const float* scan4, int64_t n, const float* scan_normals3, const float* scan_scalar,
@@ -531,6 +554,9 @@ icpmi_status icpmi_map_update_chain_staged(icpmi_handle h, const float correctio
  * download next to icpmi_get_map (no map, or an empty resident map: ICPMI_OK and nothing written, like icpmi_get_map's 0 points). */
 icpmi_status icpmi_set_map_scalar(icpmi_handle h, const float* scalar, int64_t m);
 icpmi_status icpmi_get_map_scalar(icpmi_handle h, float* scalar_out, int64_t capacity);
+/* The `densities` row of the resident map (see ICPMI_MOP_SURFACE_NORMALS above), one float per point in icpmi_get_map's order.  No map,
+ * an empty resident map or no valid row: ICPMI_OK and nothing written. */
+icpmi_status icpmi_get_map_densities(icpmi_handle h, float* densities_out, int64_t capacity);
 
 /* Input-side filters as ONE pass (`Mapper::applyInputFilters`, Mapper.cpp:187-191: the DistanceLimit radius filter of
  * Mapper.cpp:27-31 followed by the `input:` chain, e.g. the two BoundingBox filters of examples/config.yaml:2-18): every

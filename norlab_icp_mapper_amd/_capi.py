@@ -108,7 +108,7 @@ class CovSampInfo(C.Structure):
     _fields_ = [("center", C.c_double * 3), ("lnorm", C.c_double), ("eigval", C.c_double * 6), ("basis", C.c_double * 36)]
 
 
-MOP_POINT_DISTANCE, MOP_DYNAMIC_POINTS, MOP_VOXEL, MOP_SURFACE_NORMALS, MOP_CUT_SCALAR, MOP_OCTREE = range(6)
+MOP_POINT_DISTANCE, MOP_DYNAMIC_POINTS, MOP_VOXEL, MOP_SURFACE_NORMALS, MOP_CUT_SCALAR, MOP_OCTREE, MOP_MAX_DENSITY = range(7)
 
 
 # every symbol include/icpmi.h declares: (name, restype, argtypes)
@@ -151,11 +151,13 @@ SYMBOLS = [
     ("icpmi_voxel_grid", C.c_int, [_P, _P, C.c_int64, _P, C.c_int32, _P, C.c_int32, _P, _P, _P, _P]),
     ("icpmi_covariance_sampling", C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, C.c_int32, _P, _P, _P]),
     ("icpmi_normal_space_sampling", C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, C.c_int32, C.c_float, _P, _P, _P]),
+    ("icpmi_max_density_keep", C.c_int, [_P, _P, C.c_int64, C.c_float, C.c_int32, _P]),
     ("icpmi_sensor_model", C.c_int, [_P, _P, C.c_int64, _P, _P, _P, C.c_int32, _P, _P, _P, _P]),
     ("icpmi_map_update_chain", C.c_int, [_P, _P, C.c_int64, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, _P, C.c_int64, _P, _P]),
     ("icpmi_map_update_chain_staged", C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, _P, C.c_int64, _P, _P]),
     ("icpmi_set_map_scalar", C.c_int, [_P, _P, C.c_int64]),
     ("icpmi_get_map_scalar", C.c_int, [_P, _P, C.c_int64]),
+    ("icpmi_get_map_densities", C.c_int, [_P, _P, C.c_int64]),
     ("icpmi_map_update_point_distance", C.c_int, [_P, _P, C.c_int64, _P, C.c_float, C.c_int32, _P, _P, _P]),
     ("icpmi_staged_point_distance_keep", C.c_int, [_P, _P, C.c_float, _P, _P]),
     ("icpmi_get_map", C.c_int, [_P, _P, _P, C.c_int64, _P]),

@@ -1194,6 +1194,21 @@ icpmi_status icpmi_get_map_scalar(icpmi_handle h, float* scalar_out, int64_t cap
     return ops_map_scalar(h, nullptr, scalar_out, h->m_raw);
 }
 
+icpmi_status icpmi_get_map_densities(icpmi_handle h, float* densities_out, int64_t capacity)
+{
+    CHECK_H(h);
+    return ops_get_map_densities(h, densities_out, capacity);
+}
+
+icpmi_status icpmi_max_density_keep(icpmi_handle h, const float* densities, int64_t n, float max_density, int32_t seed, uint8_t* keep)
+{
+    CHECK_H(h);
+    if (n < 0 || (n > 0 && (!densities || !keep))) { h->last_error = "max_density_keep: bad arguments"; return ICPMI_ERR_INVALID_ARG; }
+    if (!max_density_param_ok(max_density)) { h->last_error = "InvalidParameter: maxDensity must be finite and > 0"; return ICPMI_ERR_INVALID_ARG; }
+    if (n > 0x7fffffffll) { h->last_error = "max_density_keep: more than 2^31 - 1 points"; return ICPMI_ERR_UNSUPPORTED; }
+    return ops_max_density_keep(h, densities, n, max_density, seed, keep);
+}
+
 icpmi_status icpmi_dynamic_points_update(icpmi_handle h, const icpmi_dynpts_params* prm, const float to_sensor[16], const float* in4,
                                          int64_t n, const float* map4, const float* map_normals3, int64_t m, float* prob_dynamic)
 {

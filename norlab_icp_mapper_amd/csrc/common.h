@@ -573,10 +573,14 @@ struct icpmi_ctx {
     // one tracked scalar descriptor of the resident map (`probabilityDynamic` for the shipped chain) and the ping-pong
     // set the map-update chain compacts into (ops.hip: ops_map_update_chain)
     DevArr<float> d_raw_s; bool raw_has_scalar = false;
+    // the `densities` row a SURFACE_NORMALS step with keepDensities wrote (ops.hip: invalid at the start of every program, valid from that step
+    // on, compacted along with the points, resident afterwards; icpmi_get_map_densities hands it out)
+    DevArr<float> d_raw_d; bool raw_has_density = false;
     DevArr<int> d_src;                  // provenance of every point of the map being updated
     DevArr<float4> d_alt_raw;
     DevArr<float> d_alt_n3;
     DevArr<float> d_alt_s;
+    DevArr<float> d_alt_d;
     DevArr<int> d_alt_src;
     DevArr<float> d_stage_s;
     // scratch of the map-side operators (hash tables, beam buckets, flags): kept between calls -- a hipMalloc / hipFree
@@ -1111,6 +1115,10 @@ icpmi_status ops_sensor_model(icpmi_ctx* c, const float* in4, int64_t n, const f
                               int n_steps, float* normals3_out, float* obs_dir3_out, float* noise_out, uint8_t* keep_out);
 icpmi_status ops_staged_keep(icpmi_ctx* c, const float correction[16], float min_dist, uint8_t* keep_out, float* placed_out4);
 icpmi_status ops_map_scalar(icpmi_ctx* c, const float* set, float* get, int64_t m);
+icpmi_status ops_get_map_densities(icpmi_ctx* c, float* out, int64_t capacity);
+bool max_density_param_ok(float max_density); // finite and > 0
+icpmi_status max_density_flags_dev(icpmi_ctx* c, const float* d_dens, int64_t n, float max_density, int seed, unsigned* d_flag, unsigned* d_rank);
+icpmi_status ops_max_density_keep(icpmi_ctx* c, const float* densities, int64_t n, float max_density, int seed, uint8_t* keep);
 icpmi_status ops_surface_normals(icpmi_ctx* c, const float* pts4, int64_t m, int knn, float* normals3, float* densities = nullptr,
                                  int32_t* matched_ids = nullptr, float* mean_dist = nullptr, float* eig_values = nullptr, float* eig_vectors = nullptr);
 icpmi_status ops_dynamic_points_update(icpmi_ctx* c, const icpmi_dynpts_params* prm, const float to_sensor[16], const float* in4, int64_t n,

@@ -1173,6 +1173,7 @@ grid_chosen:
     if (d_pts != c->d_raw && c->keep_raw) {
         ++c->raw_epoch; // the resident copy is replaced, not appended to: a private raw-frame index starts over
         c->raw_has_scalar = false; // a map handed in from outside: its scalar channel comes through icpmi_set_map_scalar
+        c->raw_has_density = false; // ... and it has no `densities` row until a program writes one
         if (c->d_raw.ensure(c, (size_t)m) != ICPMI_OK) return ICPMI_ERR_HIP;
         HIP_TRY(c, hipMemcpyAsync(c->d_raw, d_pts, (size_t)m * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
     }

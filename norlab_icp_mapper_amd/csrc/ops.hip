@@ -44,14 +44,15 @@ __global__ __launch_bounds__(256) void compact_points_kernel(const float4* __res
 }
 constexpr int64_t NO_CAP = INT64_MAX;
 
-// the point record: features with their companions -- normals (3 x N), scalar, provenance.  flag == nullptr: every input is kept;
-// pos == nullptr: slot base + i.  An output companion that is null is not written; an input companion that is null reads as zeros,
+// the point record: features with their companions -- normals (3 x N), scalar, provenance, densities.  flag == nullptr: every input is
+// kept; pos == nullptr: slot base + i.  An output companion that is null is not written; an input companion that is null reads as zeros,
 // provenance as src_base + i.
 __global__ __launch_bounds__(256) void compact_records_kernel(int64_t n, const unsigned* __restrict__ flag, const unsigned* __restrict__ pos, int64_t base,
                                                               const float4* __restrict__ in, const float* __restrict__ in_n3,
                                                               const float* __restrict__ in_s, const int* __restrict__ in_src, int src_base,
                                                               float4* __restrict__ out, float* __restrict__ out_n3, float* __restrict__ out_s,
-                                                              int* __restrict__ out_src)
+                                                              int* __restrict__ out_src, const float* __restrict__ in_d = nullptr,
+                                                              float* __restrict__ out_d = nullptr)
 {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n || (flag && !flag[i])) return;
@@ -64,6 +65,7 @@ __global__ __launch_bounds__(256) void compact_records_kernel(int64_t n, const u
     }
     if (out_s) out_s[o] = in_s ? in_s[i] : 0.f;
     if (out_src) out_src[o] = in_src ? in_src[i] : src_base + (int)i;
+    if (out_d) out_d[o] = in_d ? in_d[i] : 0.f;
 }
 
 // pos = exclusive scan of the flags, *count = how many are set: the last position plus the last flag, one small read-back.  `enqueue`
@@ -157,8 +159,9 @@ no_view:
 // normals and c->d_raw_dk the d^2 of every point's k-th neighbour: only the appended points and the old points an appended point can have
 // entered the neighbourhood of are searched and solved again -- the other normals are what a pass over the whole cloud would write, bit for
 // bit (same neighbours, same coordinates, same sums).  Reference semantics unchanged: Map.cpp:524 applies the filter to the whole map.
+// d_dens (may be null; a pass over the whole cloud only, i.e. not with `remember`): the filter's keepDensities row, m floats.
 static icpmi_status surface_normals_dev(icpmi_ctx* c, const float4* d_pts, int64_t m, int knn, float* d_normals3, int64_t m_old = 0, bool remember = false,
-                                        const unsigned** changed_list = nullptr, int64_t* changed_n = nullptr)
+                                        const unsigned** changed_list = nullptr, int64_t* changed_n = nullptr, float* d_dens = nullptr)
 {
     if (changed_list) *changed_list = nullptr;
     if (changed_n) *changed_n = -1; // (-1: the whole field)
@@ -184,7 +187,7 @@ static icpmi_status surface_normals_dev(icpmi_ctx* c, const float4* d_pts, int64
     const int64_t todo = incremental ? sub.n_sel : m;
     if (incremental && changed_list && changed_n) { *changed_list = list; *changed_n = todo; } // (valid until the grid's next search)
     // rows of d_sidx follow the query order = the caller's order, so the normals land in place
-    if (todo > 0) launch_normals(tc->stream, tc->d_map_sorted, tc->d_sidx, todo, knn, d_normals3, (float*)nullptr, c->cfg.is_2d, nullptr, nullptr, nullptr, list);
+    if (todo > 0) launch_normals(tc->stream, tc->d_map_sorted, tc->d_sidx, todo, knn, d_normals3, incremental ? (float*)nullptr : d_dens, c->cfg.is_2d, nullptr, nullptr, nullptr, list);
     if (track) {
         if (todo > 0) hipLaunchKernelGGL(kth_d2_kernel, dim3((int)((todo + 255) / 256)), dim3(256), 0, tc->stream, (const float*)tc->d_d2, todo, knn, list, c->d_raw_dk);
         c->dk_m = m; c->dk_knn = knn; c->dk_epoch = c->raw_epoch;
@@ -219,6 +222,7 @@ icpmi_status ops_map_update_dev(icpmi_ctx* c, const float4* d_scan, int64_t n, c
     if (new_m) *new_m = c->m_raw;
     if (n == 0) return ICPMI_OK;
     if (normals_knn < 0 || normals_knn > ICPMI_MAX_K) { c->last_error = "map_update: normals_knn must be in [0, 32]"; return ICPMI_ERR_INVALID_ARG; }
+    c->raw_has_density = false; // (the scan has no `densities`: the row does not survive an append, DataPoints::concatenate's rule)
     const bool scan_normals3 = d_scan_n3 != nullptr;
     const int64_t m0 = c->m > 0 ? c->m_raw : 0;
     const int blocks = (int)((n + 255) / 256);
@@ -316,6 +320,11 @@ icpmi_status ops_get_map(icpmi_ctx* c, float* out4, float* normals3, int64_t cap
 // filters.  Working set = the resident arrays themselves (features, normals, one scalar descriptor, provenance);
 // compactions write into the ping-pong set and swap.  Every step is order preserving, so the result is a function
 // of the inputs alone and equals the host chain built from the single operators above.
+// The `densities` row (c->d_raw_d) joins the working set at a SURFACE_NORMALS step with f[0] = 1 (keepDensities): every
+// program starts without it -- the scan has no `densities`, so by DataPoints::concatenate's rule the field does not survive
+// the modules --, the normals pass writes it, every compaction / gather behind that step moves it along with the points,
+// a MAX_DENSITY step reads it (maxdensity.hip), and it stays resident for icpmi_get_map_densities.  It is a scalar: the
+// sensor-frame round trip leaves it alone.
 // =================================================================================================================
 namespace {
 
@@ -351,6 +360,7 @@ struct Chain {
     icpmi_ctx* c;
     int64_t m = 0;         // points in the working map
     bool has_n = false;    // its normals mean something
+    bool has_d = false;    // its `densities` row (c->d_raw_d) is valid: a SURFACE_NORMALS step with keepDensities has run
     bool indexed = false;  // the handle's own search index still describes exactly the working map
 };
 
@@ -363,6 +373,7 @@ icpmi_status chain_reserve(Chain& w, int64_t need)
     if (s == ICPMI_OK) s = c->d_raw_n3.ensure_keep(c, (size_t)need * 3, (size_t)w.m * 3);
     if (s == ICPMI_OK) s = c->d_raw_s.ensure_keep(c, (size_t)need, (size_t)w.m);
     if (s == ICPMI_OK) s = c->d_src.ensure_keep(c, (size_t)need, (size_t)w.m);
+    if (s == ICPMI_OK && w.has_d) s = c->d_raw_d.ensure_keep(c, (size_t)need, (size_t)w.m);
     return s;
 }
 
@@ -374,7 +385,8 @@ icpmi_status chain_append(Chain& w, const float4* d_scan, const float* d_n3, con
     icpmi_status s = chain_reserve(w, w.m + count);
     if (s != ICPMI_OK) return s;
     hipLaunchKernelGGL(compact_records_kernel, dim3((int)((n + 255) / 256)), dim3(256), 0, c->stream, n, flag, pos, w.m, d_scan, d_n3, d_s,
-                       (const int*)nullptr, src_base, c->d_raw.get(), c->d_raw_n3.get(), c->d_raw_s.get(), c->d_src.get());
+                       (const int*)nullptr, src_base, c->d_raw.get(), c->d_raw_n3.get(), c->d_raw_s.get(), c->d_src.get(), (const float*)nullptr,
+                       w.has_d ? c->d_raw_d.get() : (float*)nullptr);
     HIP_TRY(c, hipGetLastError());
     w.m += count;
     w.indexed = false;
@@ -382,16 +394,19 @@ icpmi_status chain_append(Chain& w, const float4* d_scan, const float* d_n3, con
 }
 
 // the ping-pong of the working set: room for `count` records in the alt arrays, `launch` fills them from the main set, the four pairs swap
+// (five with a valid `densities` row)
 template <class Launch>
 icpmi_status chain_into_alt(Chain& w, int64_t count, Launch launch)
 {
     icpmi_ctx* c = w.c;
     if (c->d_alt_raw.ensure(c, (size_t)count + 1) != ICPMI_OK || c->d_alt_n3.ensure(c, (size_t)count * 3 + 1) != ICPMI_OK ||
-        c->d_alt_s.ensure(c, (size_t)count + 1) != ICPMI_OK || c->d_alt_src.ensure(c, (size_t)count + 1) != ICPMI_OK)
+        c->d_alt_s.ensure(c, (size_t)count + 1) != ICPMI_OK || c->d_alt_src.ensure(c, (size_t)count + 1) != ICPMI_OK ||
+        (w.has_d && c->d_alt_d.ensure(c, (size_t)count + 1) != ICPMI_OK))
         return ICPMI_ERR_HIP;
     launch();
     HIP_TRY(c, hipGetLastError());
     swap(c->d_raw, c->d_alt_raw); swap(c->d_raw_n3, c->d_alt_n3); swap(c->d_raw_s, c->d_alt_s); swap(c->d_src, c->d_alt_src);
+    if (w.has_d) swap(c->d_raw_d, c->d_alt_d);
     w.m = count;
     w.indexed = false;
     return ICPMI_OK;
@@ -410,7 +425,8 @@ icpmi_status chain_compact(Chain& w, unsigned* d_flag, unsigned* d_pos)
     return chain_into_alt(w, count, [&] {
         hipLaunchKernelGGL(compact_records_kernel, dim3((int)((m + 255) / 256)), dim3(256), 0, c->stream, m, (const unsigned*)d_flag, (const unsigned*)d_pos,
                            (int64_t)0, (const float4*)c->d_raw.get(), (const float*)c->d_raw_n3.get(), (const float*)c->d_raw_s.get(),
-                           (const int*)c->d_src.get(), 0, c->d_alt_raw.get(), c->d_alt_n3.get(), c->d_alt_s.get(), c->d_alt_src.get());
+                           (const int*)c->d_src.get(), 0, c->d_alt_raw.get(), c->d_alt_n3.get(), c->d_alt_s.get(), c->d_alt_src.get(),
+                           w.has_d ? (const float*)c->d_raw_d.get() : (const float*)nullptr, w.has_d ? c->d_alt_d.get() : (float*)nullptr);
     });
 }
 
@@ -419,7 +435,7 @@ icpmi_status chain_compact(Chain& w, unsigned* d_flag, unsigned* d_pos)
 __global__ __launch_bounds__(256) void chain_gather_kernel(int64_t count, const int* __restrict__ order, const float4* __restrict__ raw,
                                                            const float* __restrict__ n3, const float* __restrict__ sc, const int* __restrict__ src,
                                                            float4* __restrict__ o_raw, float* __restrict__ o_n3, float* __restrict__ o_sc,
-                                                           int* __restrict__ o_src)
+                                                           int* __restrict__ o_src, const float* __restrict__ dn, float* __restrict__ o_dn)
 {
     const int64_t o = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (o >= count) return;
@@ -428,6 +444,7 @@ __global__ __launch_bounds__(256) void chain_gather_kernel(int64_t count, const 
     o_n3[3 * o] = n3[3 * i]; o_n3[3 * o + 1] = n3[3 * i + 1]; o_n3[3 * o + 2] = n3[3 * i + 2];
     o_sc[o] = sc[i];
     o_src[o] = src[i];
+    if (o_dn) o_dn[o] = dn[i]; // (the `densities` row, where the working map has one)
 }
 
 icpmi_status chain_gather(Chain& w, const int* d_order, int64_t count)
@@ -435,7 +452,8 @@ icpmi_status chain_gather(Chain& w, const int* d_order, int64_t count)
     icpmi_ctx* c = w.c;
     return chain_into_alt(w, count, [&] {
         if (count) hipLaunchKernelGGL(chain_gather_kernel, dim3((int)((count + 255) / 256)), dim3(256), 0, c->stream, count, d_order, c->d_raw, c->d_raw_n3,
-                                      c->d_raw_s, c->d_src, c->d_alt_raw, c->d_alt_n3, c->d_alt_s, c->d_alt_src);
+                                      c->d_raw_s, c->d_src, c->d_alt_raw, c->d_alt_n3, c->d_alt_s, c->d_alt_src,
+                                      w.has_d ? (const float*)c->d_raw_d.get() : (const float*)nullptr, w.has_d ? c->d_alt_d.get() : (float*)nullptr);
     });
 }
 
@@ -484,7 +502,7 @@ icpmi_status ops_map_update_chain(icpmi_ctx* c, const float4* d_scan, int64_t n,
     ++c->raw_epoch; // the program may move, compact or reorder the resident points: the private raw-frame index is rebuilt, not appended to
     if (n_ops < 0 || n_modules < 0 || n_modules > n_ops || (n_ops > 0 && !ops)) { c->last_error = "map_update_chain: bad program"; return ICPMI_ERR_INVALID_ARG; }
     if (src_out && src_capacity < m0 + (int64_t)n_modules * n) { c->last_error = "map_update_chain: src_capacity must be >= m_old + n_modules * n"; return ICPMI_ERR_INVALID_ARG; }
-    bool uses_scalar = false;
+    bool uses_scalar = false, writes_density = false;
     for (int i = 0; i < n_ops; ++i) {
         const icpmi_map_op& op = ops[i];
         switch (op.type) {
@@ -498,7 +516,16 @@ icpmi_status ops_map_update_chain(icpmi_ctx* c, const float4* d_scan, int64_t n,
             break;
         }
         case ICPMI_MOP_VOXEL: if (!(op.f[0] > 0.f) || (op.i != 0 && op.i != 1)) { c->last_error = "map_update_chain: voxel edge must be > 0 and samplingMethod 0 or 1"; return ICPMI_ERR_INVALID_ARG; } break;
-        case ICPMI_MOP_SURFACE_NORMALS: if (op.i < 1 || op.i > ICPMI_MAX_K) { c->last_error = "surface_normals: knn must be in [1, 32]"; return ICPMI_ERR_INVALID_ARG; } break;
+        case ICPMI_MOP_SURFACE_NORMALS:
+            if (op.i < 1 || op.i > ICPMI_MAX_K) { c->last_error = "surface_normals: knn must be in [1, 32]"; return ICPMI_ERR_INVALID_ARG; }
+            if (op.f[0] != 0.f && op.f[0] != 1.f) { c->last_error = "surface_normals: f[0] (keepDensities) must be 0 or 1"; return ICPMI_ERR_INVALID_ARG; }
+            writes_density |= op.f[0] == 1.f;
+            break;
+        case ICPMI_MOP_MAX_DENSITY:
+            if (!max_density_param_ok(op.f[0])) { c->last_error = "InvalidParameter: maxDensity must be finite and > 0"; return ICPMI_ERR_INVALID_ARG; }
+            // (the host filter's InvalidField: no step in front of this one has written the row)
+            if (!writes_density) { c->last_error = "InvalidField: MaxDensityDataPointsFilter: Error, no densities found in descriptors."; return ICPMI_ERR_INVALID_ARG; }
+            break;
         case ICPMI_MOP_CUT_SCALAR: uses_scalar = true; break;
         case ICPMI_MOP_OCTREE:
             if (!(op.f[0] >= 0.f) || (op.i != 0 && op.i != 1) || !(op.f[1] >= 0.f) || op.f[1] > 64.f) {
@@ -507,8 +534,9 @@ icpmi_status ops_map_update_chain(icpmi_ctx* c, const float4* d_scan, int64_t n,
             break;
         default: c->last_error = "map_update_chain: unknown operator"; return ICPMI_ERR_INVALID_ARG;
         }
-        if (i >= n_modules && op.type != ICPMI_MOP_SURFACE_NORMALS && op.type != ICPMI_MOP_CUT_SCALAR) { c->last_error = "map_update_chain: a mapper module after the post filters"; return ICPMI_ERR_INVALID_ARG; }
-        if (i < n_modules && (op.type == ICPMI_MOP_SURFACE_NORMALS || op.type == ICPMI_MOP_CUT_SCALAR)) { c->last_error = "map_update_chain: a post filter among the mapper modules"; return ICPMI_ERR_INVALID_ARG; }
+        const bool post = op.type == ICPMI_MOP_SURFACE_NORMALS || op.type == ICPMI_MOP_CUT_SCALAR || op.type == ICPMI_MOP_MAX_DENSITY;
+        if (i >= n_modules && !post) { c->last_error = "map_update_chain: a mapper module after the post filters"; return ICPMI_ERR_INVALID_ARG; }
+        if (i < n_modules && post) { c->last_error = "map_update_chain: a post filter among the mapper modules"; return ICPMI_ERR_INVALID_ARG; }
     }
     if (n_modules == 0) { c->last_error = "InvalidParameter: no mapper module configured"; return ICPMI_ERR_INVALID_ARG; }
     if (uses_scalar && n > 0 && !d_scan_s) { c->last_error = "InvalidField: the chain needs the tracked scalar descriptor on the input (AddDescriptorDataPointsFilter)"; return ICPMI_ERR_INVALID_ARG; }
@@ -522,6 +550,7 @@ icpmi_status ops_map_update_chain(icpmi_ctx* c, const float4* d_scan, int64_t n,
 
     Chain w;
     w.c = c; w.m = m0; w.has_n = m0 > 0 && c->raw_has_normals; w.indexed = m0 > 0;
+    c->raw_has_density = false; // (w.has_d: every program starts without the row, whatever the last one left)
     // the main set must exist before the first kernel touches it; normals / scalar a map never had read as zeros
     icpmi_status s = ICPMI_OK;
     {
@@ -649,8 +678,17 @@ icpmi_status ops_map_update_chain(icpmi_ctx* c, const float4* d_scan, int64_t n,
         }
         case ICPMI_MOP_SURFACE_NORMALS: {
             if (w.m == 0) break;
-            s = surface_normals_dev(c, c->d_raw, w.m, op.i, c->d_raw_n3);
+            const bool keep_densities = op.f[0] == 1.f;
+            if (keep_densities) { s = c->d_raw_d.ensure(c, (size_t)w.m + 1); if (s != ICPMI_OK) break; }
+            s = surface_normals_dev(c, c->d_raw, w.m, op.i, c->d_raw_n3, 0, false, nullptr, nullptr, keep_densities ? c->d_raw_d.get() : (float*)nullptr);
             w.has_n = true;
+            w.has_d |= keep_densities; // (a later pass without keepDensities leaves the row as it is: addDescriptor touched `normals` only)
+            break;
+        }
+        case ICPMI_MOP_MAX_DENSITY: {
+            if (w.m == 0) break; // (validated above: a density-writing step came first, so with points the row is valid here)
+            s = max_density_flags_dev(c, c->d_raw_d, w.m, op.f[0], op.i, d_flag, d_pos);
+            if (s == ICPMI_OK) s = chain_compact(w, d_flag, d_pos);
             break;
         }
         case ICPMI_MOP_CUT_SCALAR: {
@@ -676,14 +714,14 @@ icpmi_status ops_map_update_chain(icpmi_ctx* c, const float4* d_scan, int64_t n,
     if (s != ICPMI_OK) {
         // the resident arrays may be half way through the program: drop them, the index of the old map is intact but its
         // resident copy is not -- force the caller back to icpmi_set_map
-        c->m_raw = 0; c->raw_has_normals = false; c->raw_has_scalar = false; c->m = 0;
+        c->m_raw = 0; c->raw_has_normals = false; c->raw_has_scalar = false; c->raw_has_density = false; c->m = 0;
         return s;
     }
     if (w.m == 0) {
         // the chain removed every point (e.g. CutAtDescriptorThreshold cut the whole map): the reference goes on with an empty local
         // cloud -- `icp.setMap` ignores an empty cloud and keeps its previous map (Map.cpp:528), the next scan
         // creates the map anew (Map.cpp:505-515).  Same here: the resident copy is empty, the registration index stays.
-        c->m_raw = 0; c->raw_has_normals = false; c->raw_has_scalar = false;
+        c->m_raw = 0; c->raw_has_normals = false; c->raw_has_scalar = false; c->raw_has_density = false;
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         if (new_m) *new_m = 0;
         return ICPMI_OK;
@@ -706,6 +744,7 @@ icpmi_status ops_map_update_chain(icpmi_ctx* c, const float4* d_scan, int64_t n,
     s = map_build(c, c->d_raw, w.m, w.has_n ? c->d_raw_n3 : nullptr);
     if (s != ICPMI_OK) return s;
     c->raw_has_scalar = (m0 == 0 || c->raw_has_scalar) && (n == 0 || d_scan_s != nullptr); // both parts carried real values
+    c->raw_has_density = w.has_d;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     tick("map_build", -4);
     if (new_m) *new_m = w.m;
@@ -1298,6 +1337,16 @@ icpmi_status ops_map_scalar(icpmi_ctx* c, const float* set, float* get, int64_t 
         if (!c->raw_has_scalar) { c->last_error = "InvalidField: the map has no tracked scalar descriptor"; return ICPMI_ERR_INVALID_ARG; }
         HIP_TRY(c, hipMemcpyAsync(get, c->d_raw_s, (size_t)m * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     }
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return ICPMI_OK;
+}
+
+// the `densities` row of the resident map, in the caller's order; no valid row: nothing is written
+icpmi_status ops_get_map_densities(icpmi_ctx* c, float* out, int64_t capacity)
+{
+    if (c->m <= 0 || c->m_raw == 0 || !c->raw_has_density) return ICPMI_OK;
+    if (!out || capacity < c->m_raw) { c->last_error = "get_map_densities: capacity too small"; return ICPMI_ERR_INVALID_ARG; }
+    HIP_TRY(c, hipMemcpyAsync(out, c->d_raw_d, (size_t)c->m_raw * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return ICPMI_OK;
 }

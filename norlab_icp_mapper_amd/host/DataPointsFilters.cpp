@@ -96,9 +96,9 @@ struct SurfaceNormalFilter : DataPointsFilter {
     icpmi_handle h; int knn = 5; bool keepDensities = false, keepMatchedIds = false, keepMeanDist = false, keepEigenValues = false, keepEigenVectors = false;
     int surfaceNormalKnn() const override { return knn; }
     bool residentOp(icpmi_map_op& op, std::string&) const override {
-        op = icpmi_map_op{}; op.type = ICPMI_MOP_SURFACE_NORMALS; op.i = knn;
-        // the resident map does not track `densities`, `matchedIds` or `meanDist`
-        return knn >= 1 && knn <= 32 && !keepDensities && !keepMatchedIds && !keepMeanDist && !keepEigenValues && !keepEigenVectors;
+        op = icpmi_map_op{}; op.type = ICPMI_MOP_SURFACE_NORMALS; op.i = knn; op.f[0] = keepDensities ? 1.f : 0.f;
+        // the resident map tracks `densities` (the same pass writes the row); not `matchedIds`, `meanDist` or the eigen rows
+        return knn >= 1 && knn <= 32 && !keepMatchedIds && !keepMeanDist && !keepEigenValues && !keepEigenVectors;
     }
     void inPlaceFilter(DataPoints& c) const override {
         const size_t n = c.getNbPoints();
@@ -143,6 +143,12 @@ struct RandomSamplingFilter : DataPointsFilter {
 // a point in a region denser than maxDensity survives with probability maxDensity / density.
 struct MaxDensityFilter : DataPointsFilter {
     float maxDensity = 10.f; int seed = 1;
+    // the resident step draws from the `densities` row a SurfaceNormal{keepDensities: 1} step of the same program wrote (Map::residentPlan
+    // checks that one stands in front); a maxDensity the device entry refuses stays with the host loop
+    bool residentOp(icpmi_map_op& op, std::string&) const override {
+        op = icpmi_map_op{}; op.type = ICPMI_MOP_MAX_DENSITY; op.f[0] = maxDensity; op.i = seed;
+        return std::isfinite(maxDensity) && maxDensity > 0.f;
+    }
     void inPlaceFilter(DataPoints& c) const override {
         if (!c.descriptorExists("densities")) throw InvalidField("MaxDensityDataPointsFilter: Error, no densities found in descriptors.");
         const Descriptor& d = c.getDescriptorByName("densities");

@@ -410,6 +410,13 @@ std::vector<float> GpuICPSequence::downloadMapScalar() const
     return out;
 }
 
+std::vector<float> GpuICPSequence::downloadMapDensities() const
+{
+    std::vector<float> out((size_t)residentMapSize());
+    if (!out.empty()) check(h, icpmi_get_map_densities(h, out.data(), (int64_t)out.size()));
+    return out;
+}
+
 int64_t GpuICPSequence::residentMapSize() const
 {
     int64_t m = 0;

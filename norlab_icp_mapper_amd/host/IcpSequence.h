@@ -70,6 +70,7 @@ public:
                         int64_t& mapSize, bool wantSrc = true); // wantSrc = false: no host-side descriptor needs the provenance vector
     void uploadMapScalar(const std::vector<float>& scalar);   // the tracked scalar descriptor of the resident map
     std::vector<float> downloadMapScalar() const;
+    std::vector<float> downloadMapDensities() const;          // the `densities` row a resident SurfaceNormal{keepDensities: 1} step wrote
     int64_t residentMapSize() const;
     void setPlanar(bool on);                           // 2-D clouds (z == 0): planar minimisers and normals
     bool isPlanar() const { return planar; }

@@ -221,18 +221,20 @@ DataPoints Map::getLocalPointCloud()
 void Map::syncLocalFromDevice()
 {
     if (!deviceAhead) return;
-    // features, `normals` and the tracked scalar descriptor live on the device; every other descriptor was kept current on the host
+    // features, `normals`, `densities` and the tracked scalar descriptor live on the device; every other descriptor was kept current on the host
     DataPoints dev;
-    std::vector<float> scalar;
+    std::vector<float> scalar, densities;
     {
         std::lock_guard<std::mutex> gi(icpMapLock);
         dev = icp.downloadMap();
         if (!residentScalar.empty()) scalar = icp.downloadMapScalar();
+        if (residentDensities) densities = icp.downloadMapDensities();
     }
     localPointCloud.features = std::move(dev.features);
     localPointCloud.removeDescriptor("normals");
     if (residentNormals && dev.descriptorExists("normals")) localPointCloud.addDescriptor("normals", 3, std::move(dev.getDescriptorByName("normals").data));
     if (!residentScalar.empty()) localPointCloud.addDescriptor(residentScalar, 1, std::move(scalar));
+    if (residentDensities) { localPointCloud.removeDescriptor("densities"); localPointCloud.addDescriptor("densities", 1, std::move(densities)); }
     deviceAhead = false;
 }
 
@@ -280,6 +282,10 @@ bool Map::residentPlan(const DataPoints& input, const DataPointsFilters& postFil
         icpmi_map_op op{}; std::string name;
         if (!adopt(filter->residentOp(op, name), op, name)) return false;
         prog.computesNormals |= op.type == ICPMI_MOP_SURFACE_NORMALS;
+        prog.computesDensities |= op.type == ICPMI_MOP_SURFACE_NORMALS && op.f[0] == 1.f;
+        // MaxDensity reads the row a SurfaceNormal{keepDensities: 1} in front of it wrote; `densities` from anywhere else (the input's own
+        // descriptor) is a host descriptor: host path
+        if (op.type == ICPMI_MOP_MAX_DENSITY && !prog.computesDensities) return false;
     }
     // a point-to-plane chain needs normals on every map point: only with the SurfaceNormal post filter
     if (icp.config().minimizer == ICPMI_MIN_POINT_TO_PLANE && !prog.computesNormals) return false;
@@ -306,7 +312,7 @@ bool Map::hostDescriptorsFollow(const DataPoints& input, const ResidentProgram& 
 {
     const std::vector<Descriptor>& fields = first ? input.descriptors : localPointCloud.descriptors;
     for (const Descriptor& d : fields) {
-        if (d.name == "normals" || d.name == prog.scalarName) continue;
+        if (d.name == "normals" || d.name == prog.scalarName || (prog.computesDensities && d.name == "densities")) continue;
         if (input.descriptorExists(d.name) && input.getDescriptorByName(d.name).span == d.span) return true;
     }
     return false;
@@ -327,7 +333,7 @@ void Map::prepareResidentScalar(const ResidentProgram& prog, bool first)
 void Map::adoptResidentResult(const DataPoints& input, const ResidentProgram& prog, const std::vector<int32_t>& src, int64_t prefix,
                               int64_t mapSize, bool first)
 {
-    // `normals` and the tracked scalar live on the device; every other descriptor follows the provenance vector with
+    // `normals`, the tracked scalar and the `densities` a post filter writes live on the device; every other descriptor follows the provenance vector with
     // DataPoints::concatenate's rule (only fields both clouds have survive; the first scan brings its own set).  Features,
     // normals and the scalar of localPointCloud are stale until syncLocalFromDevice().
     const size_t m0 = first ? 0 : (size_t)residentCount;
@@ -336,7 +342,7 @@ void Map::adoptResidentResult(const DataPoints& input, const ResidentProgram& pr
     std::vector<Descriptor> next;
     const std::vector<Descriptor>& fields = first ? input.descriptors : localPointCloud.descriptors;
     for (const Descriptor& old : fields) {
-        if (old.name == "normals" || old.name == prog.scalarName) continue;
+        if (old.name == "normals" || old.name == prog.scalarName || (prog.computesDensities && old.name == "densities")) continue;
         if (!input.descriptorExists(old.name) || input.getDescriptorByName(old.name).span != old.span) continue;
         const Descriptor& in = input.getDescriptorByName(old.name);
         const size_t span = (size_t)old.span;
@@ -352,6 +358,7 @@ void Map::adoptResidentResult(const DataPoints& input, const ResidentProgram& pr
     }
     localPointCloud.descriptors = std::move(next);
     residentNormals = prog.computesNormals || (first ? inputNormals : (hadNormals && inputNormals));
+    residentDensities = prog.computesDensities;
     residentScalar = prog.scalarName;
     residentCount = mapSize;
     deviceAhead = true;
@@ -367,7 +374,7 @@ void Map::dropLocalCloudAfterFailedUpdate()
 {
     if (icp.residentMapSize() > 0) return; // validation errors leave the device state alone
     localPointCloud = DataPoints();
-    deviceAhead = false; residentCount = 0; residentNormals = false; residentScalar.clear();
+    deviceAhead = false; residentCount = 0; residentNormals = false; residentDensities = false; residentScalar.clear();
     localPointCloudEmpty.store(true);
     newLocalPointCloudAvailable = true;
 }

@@ -105,10 +105,10 @@ private:
     void loadCells(Box box);
     void unloadCells(Box box);
     // Resident path (icpmi_map_update_chain): every mapper module and every post filter describes itself as a device
-    // step (MapperModule::residentOp / DataPointsFilter::residentOp) -- the three built-in modules, SurfaceNormal and
-    // CutAtDescriptorThreshold do; a plugin that does not sends the update down the host path.  The device copy then
+    // step (MapperModule::residentOp / DataPointsFilter::residentOp) -- the three built-in modules, SurfaceNormal (with or
+    // without keepDensities), MaxDensity and CutAtDescriptorThreshold do; a plugin that does not sends the update down the host path.  The device copy then
     // runs ahead of localPointCloud, which is refreshed on the next host-side access.
-    struct ResidentProgram { std::vector<icpmi_map_op> ops; int nModules = 0; std::string scalarName; bool computesNormals = false; };
+    struct ResidentProgram { std::vector<icpmi_map_op> ops; int nModules = 0; std::string scalarName; bool computesNormals = false, computesDensities = false; };
     bool tryResidentUpdate(const DataPoints& input, const Mat4& pose, const DataPointsFilters& postFilters);
     bool residentPlan(const DataPoints& input, const DataPointsFilters& postFilters, ResidentProgram& prog) const; // lock held
     bool hostDescriptorsFollow(const DataPoints& input, const ResidentProgram& prog, bool first) const;          // lock held
@@ -119,6 +119,7 @@ private:
     void syncLocalFromDevice(); // localPointCloudLock held
     bool deviceAhead = false;
     bool residentNormals = false;      // while deviceAhead: the device map carries `normals`
+    bool residentDensities = false;    // ... and `densities` (a SurfaceNormal{keepDensities: 1} post filter of the last program)
     std::string residentScalar;        // ... and this scalar descriptor (empty: none)
     int64_t residentCount = 0;         // ... and this many points
     std::atomic<long> residentUpdates{0};

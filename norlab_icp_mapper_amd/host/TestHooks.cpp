@@ -194,4 +194,47 @@ int nim_test_mapper_replay(const char* config, int n_scans, const char* const* p
     }
 }
 
+// The same replay, handing back the map it built instead of the covariances: out4 (capacity cap points) the mapper's map, out_desc /
+// out_names every descriptor of it in nim_test_filter_chain_descs' layout, *map_updates how many scans started a map update and
+// *resident_updates Map::residentUpdateCount() -- how many of those ran on the resident map (tests/test_gpu_max_density.py).
+int nim_test_mapper_replay_map(const char* config, int n_scans, const char* const* paths, const float* poses16, const int64_t* stamps_ns,
+                               float* poses_out16, float* out4, int64_t cap, float* out_desc, int out_rows_cap, char* out_names, int out_names_cap,
+                               int64_t* n_out, int64_t* map_updates, int64_t* resident_updates, char* err, int err_cap)
+{
+    try {
+        nim::Mapper mapper(config, true, false, true, false);
+        *map_updates = 0;
+        for (int i = 0; i < n_scans; ++i) {
+            nim::DataPoints cloud = nim::DataPoints::load(paths[i]);
+            mapper.applyInputFilters(cloud);
+            nim::Mat4 pose;
+            std::memcpy(pose.data(), poses16 + 16 * i, sizeof(float) * 16);
+            mapper.processInput(cloud, pose, nim::TimePoint{std::chrono::nanoseconds(stamps_ns[i])});
+            std::memcpy(poses_out16 + 16 * i, mapper.getPose().data(), sizeof(float) * 16);
+            if (mapper.lastScanStartedMapUpdate()) ++*map_updates;
+        }
+        *resident_updates = mapper.residentMapUpdates();
+        const nim::DataPoints c = mapper.getMap();
+        const size_t m = c.getNbPoints();
+        if ((int64_t)m > cap) throw std::logic_error("the map is larger than the caller has room for");
+        std::memcpy(out4, c.features.data(), sizeof(float) * 4 * m);
+        std::string all;
+        size_t rows = 0;
+        for (const auto& d : c.descriptors) {
+            if (d.data.size() != (size_t)d.span * m) throw std::logic_error("descriptor " + d.name + " is out of step with the points");
+            if (rows + (size_t)d.span > (size_t)out_rows_cap) throw std::logic_error("more descriptor rows than the caller has room for");
+            std::memcpy(out_desc + rows * m, d.data.data(), sizeof(float) * d.data.size());
+            rows += (size_t)d.span;
+            all += d.name + ":" + std::to_string(d.span) + ";";
+        }
+        if (all.size() + 1 > (size_t)out_names_cap) throw std::logic_error("descriptor names do not fit");
+        std::memcpy(out_names, all.c_str(), all.size() + 1);
+        *n_out = (int64_t)m;
+        return 0;
+    } catch (const std::exception& e) {
+        if (err && err_cap > 0) { std::strncpy(err, e.what(), (size_t)err_cap - 1); err[err_cap - 1] = 0; }
+        return 1;
+    }
+}
+
 } // extern "C"

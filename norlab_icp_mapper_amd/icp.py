@@ -682,6 +682,13 @@ class ICPSequence:
             return order
         return order, (None if nb_sample >= n or nb_sample == 0 else buckets)
 
+    def maxDensityKeep(self, densities, max_density=10.0, seed=1):
+        """MaxDensityDataPointsFilter{maxDensity, seed} (the formulation of icpmi_max_density_keep): densities (N,) -> bool keep mask."""
+        d = np.ascontiguousarray(densities, dtype=np.float32)
+        keep = np.empty(d.shape[0], dtype=np.uint8)
+        self._check(self._lib.icpmi_max_density_keep(self._h, d.ctypes.data, d.shape[0], float(max_density), int(seed), keep.ctypes.data))
+        return keep.astype(bool)
+
     def voxelKeep(self, cloud, edge, method=0):
         """Same lattice, representative by `samplingMethod`: 0 first point, 1 pseudo-random point (smallest fmix32 of the index)."""
         c = _f32c(cloud, 4)
@@ -692,7 +699,8 @@ class ICPSequence:
     @staticmethod
     def _mapOps(modules, post):
         """[(name, params...)] -> MapOp array.  Names: 'point_distance' (min_dist), 'dynamic_points' (7 parameters in
-        icpmi_dynpts_params order), 'voxel' (edge, method), 'surface_normals' (knn), 'cut_scalar' (threshold, use_larger_than)."""
+        icpmi_dynpts_params order), 'voxel' (edge, method), 'surface_normals' (knn, keep_densities = 0), 'cut_scalar' (threshold,
+        use_larger_than), 'max_density' (max_density, seed = 1)."""
         from . import _capi
         ops = (_capi.MapOp * (len(modules) + len(post)))()
         for j, item in enumerate(list(modules) + list(post)):
@@ -710,9 +718,11 @@ class ICPSequence:
                 op.type = _capi.MOP_OCTREE; op.f[0] = args[0]; op.i = int(args[1]) if len(args) > 1 else 0
                 op.f[1] = float(args[2]) if len(args) > 2 else 1.0
             elif name == "surface_normals":
-                op.type = _capi.MOP_SURFACE_NORMALS; op.i = int(args[0])
+                op.type = _capi.MOP_SURFACE_NORMALS; op.i = int(args[0]); op.f[0] = 1.0 if len(args) > 1 and args[1] else 0.0
             elif name == "cut_scalar":
                 op.type = _capi.MOP_CUT_SCALAR; op.f[0] = args[0]; op.i = int(args[1]) if len(args) > 1 else 1
+            elif name == "max_density":
+                op.type = _capi.MOP_MAX_DENSITY; op.f[0] = args[0]; op.i = int(args[1]) if len(args) > 1 else 1
             else:
                 raise InvalidParameter("unknown map operator " + name)
         return ops
@@ -775,6 +785,17 @@ class ICPSequence:
         out = np.empty(m.value, dtype=np.float32)
         self._check(self._lib.icpmi_get_map_scalar(self._h, out.ctypes.data, out.shape[0]))
         return out
+
+    def getMapDensities(self):
+        """The `densities` row of the resident map (a 'surface_normals' step with keep_densities wrote it), or None when it has none.
+        icpmi_get_map_densities writes nothing without a valid row: the buffer goes in filled with a NaN payload no density can have."""
+        m = C.c_int64(0)
+        self._check(self._lib.icpmi_get_map(self._h, None, None, 0, C.byref(m)))
+        if m.value == 0:
+            return None
+        bits = np.full(m.value, 0x7FC0DE05, dtype=np.uint32)
+        self._check(self._lib.icpmi_get_map_densities(self._h, bits.ctypes.data, bits.shape[0]))
+        return None if (bits == 0x7FC0DE05).all() else bits.view(np.float32)
 
     def dynamicPointsUpdate(self, to_sensor, input_cloud, map_cloud, map_normals, prob_dynamic, threshold_dynamic=0.6, alpha=0.8,
                             beta=0.99, beam_half_angle=0.01, epsilon_a=0.01, epsilon_d=0.01, sensor_max_range=200.0):
