@@ -563,8 +563,8 @@ static icpmi_status register_impl(icpmi_handle h, const float* d_scan4, int64_t 
         lc.read_scalar = wants ? h->d_read_scalar : nullptr;
     }
     // KDTreeVarDistMatcher: the radii handed over for THIS reading (one shot).  The search runs with one bound, the largest radius of the row;
-    // the kernels accept per query (nn.hip: RowR2).  nn_r2row is set for the launches of this registration only.
-    struct RowScope { icpmi_ctx* c; ~RowScope() { c->nn_r2row = nullptr; } } row_scope{h};
+    // the kernels accept per query (nn.hip: RowR2).
+    const float* d_r2row = nullptr;
     if (h->cfg.var_dist && n > 0) {
         if (have_r2_n != n) {
             h->last_error = "InvalidField: KDTreeVarDistMatcher needs the reading's maxDistField descriptor (icpmi_set_reading_max_dist, one radius per point)";
@@ -575,7 +575,7 @@ static icpmi_status register_impl(icpmi_handle h, const float* d_scan4, int64_t 
             return ICPMI_ERR_INVALID_ARG;
         }
         set_search_bound(h, lc, h->read_r2_max);
-        h->nn_r2row = h->d_read_r2;
+        d_r2row = h->d_read_r2;
     }
     // sensor-noise overlap (icpmi_set_reading_sensor_noise): the noise row is one shot -- this registration consumes it
     // (PointToPointErrorMinimizer::getOverlap() needs `simpleSensorNoise` alone; only the point-to-plane variant also reads the reading's
@@ -593,7 +593,7 @@ static icpmi_status register_impl(icpmi_handle h, const float* d_scan4, int64_t 
     }
     icpmi_stats local;
     if (!stats && stats_json()) stats = &local;
-    const icpmi_status rs = loop_run(h, (const float4*)d_scan4, (needs_rn || sn) ? d_n3 : nullptr, n, lc, fixed_iters > 0, T_out, stats);
+    const icpmi_status rs = loop_run(h, (const float4*)d_scan4, (needs_rn || sn) ? d_n3 : nullptr, n, lc, d_r2row, fixed_iters > 0, T_out, stats);
     if (stats_json() && stats) write_stats_json(*stats, n, rs);
     return rs;
 }
@@ -748,11 +748,11 @@ static icpmi_status knn_impl(icpmi_handle h, const float* q4, int64_t n, int32_t
     HIP_TRY(h, hipMemcpyAsync(h->d_reading, q4, (size_t)n * sizeof(float4), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipMemsetAsync(h->d_state, 0, sizeof(IcpState), h->stream));
     DevBuf<float> d_row; // (its own block: a row armed by icpmi_set_reading_max_dist stays armed)
-    struct RowScope { icpmi_ctx* c; ~RowScope() { c->nn_r2row = nullptr; } } row_scope{h};
+    NnRequest req; // stage call: the caller's order, no quantile selection behind it
     if (radii) {
         HIP_TRY(h, d_row.alloc((size_t)n));
         HIP_TRY(h, hipMemcpyAsync(d_row, r2.data(), (size_t)n * sizeof(float), hipMemcpyHostToDevice, h->stream));
-        h->nn_r2row = d_row;
+        req.r2row = d_row;
     }
     if (k == 1) {
         icpmi_status ss = sort_queries(h, h->d_reading, n);
@@ -767,10 +767,7 @@ static icpmi_status knn_impl(icpmi_handle h, const float* q4, int64_t n, int32_t
         const int need = (int)ceilf(max_dist / h->grid.cell) + 1;
         lc.ring_max = need < 16 ? need : 16;
     } else lc.ring_max = 6;
-    h->nn_hist0 = nullptr; // stage call: no quantile selection follows
-    h->nn_match_pt = nullptr;
-    h->nn_iter_hint = 0;
-    icpmi_status s = nn_launch_k(h, h->d_reading, n, nullptr, lc, allow_self, h->d_sidx, h->d_d2, h->d_state);
+    icpmi_status s = nn_launch_k(h, req, h->d_reading, n, nullptr, lc, allow_self, h->d_sidx, h->d_d2, h->d_state);
     if (s != ICPMI_OK) return s;
     DevBuf<int> d_ids;
     HIP_TRY(h, d_ids.alloc((size_t)n * k));

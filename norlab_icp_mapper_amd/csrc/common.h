@@ -272,7 +272,7 @@ struct CaptureGate {
 };
 
 // One cached loop graph (loop.hip: capture_loop_graph): valid for the registrations whose signature is `sig`.  `sorted` is the loop state
-// order it leaves (nn_out_sorted at capture); a head graph of a checked loop also keeps its length and an LRU stamp.
+// order it leaves (NnOutcome::out_sorted of its last launch, as captured); a head graph of a checked loop also keeps its length and an LRU stamp.
 struct LoopGraph {
     hipGraphExec_t exec = nullptr; uint64_t sig = 0; int uses = 0; bool sorted = false;
     int len = 0; unsigned long used = 0;
@@ -401,8 +401,8 @@ inline hipError_t dev_free(void* p)
 // (icpmi_ctx, SelfGridCtx) and every per-call block (DevBuf) is one: it frees itself through dev_free when it dies, a ping-pong exchange
 // is one swap(a, b), and it reads as a T* wherever a pointer is expected.  It cannot be copied (`auto p = c->d_x;` does not compile) and
 // its address cannot be taken (`(void**)&c->d_x` would write a pointer past its capacity).
-// Everything that is a plain pointer BORROWS: GridLevels::pts / cs / pos0, nn_hist0, nn_match_pt, qsorted_src, d_state_mirror, d_progress,
-// d_nocc_host, kernel arguments -- views of blocks some DevArr (or pinned host memory) owns, never freed through them.
+// Everything that is a plain pointer BORROWS: GridLevels::pts / cs / pos0, the pointers of an NnRequest, qsorted_src, d_state_mirror,
+// d_progress, d_nocc_host, kernel arguments -- views of blocks some DevArr (or pinned host memory) owns, never freed through them.
 // The growth rule is part of the type: how much more than asked for a reallocation takes decides which requests the block cache can serve
 // and how much HBM a long run holds.
 // ------------------------------------------------------------------------------------------------
@@ -605,15 +605,7 @@ struct icpmi_ctx {
     DevArr<float> d_d2;                 // k x n
     DevArr<unsigned> d_hard;            // hard query list
     DevArr<unsigned> d_selhist;         // ICPMI_SELHIST_WORDS per reading of a batch
-    unsigned* nn_hist0 = nullptr;     // set by the loop when the NN kernel should build the level-0 histogram
-    bool nn_builds_hist0 = false;     // set by the NN launcher: true if the launched variant did build it
-    bool nn_builds_win = false;       // ... true if it counted the speculative window (ICPMI_S2_WIN: nnk_wg_kernel in a fused-selection loop)
-    const float* nn_r2row = nullptr;  // set by a KDTreeVarDistMatcher registration / icpmi_knn_var for ITS launches only: per-query squared accept radii (nn.hip: RowR2)
-    int nn_iter_hint = 0;             // iteration index of the launch being enqueued (> 0: seeded by the previous match)
     DevArr<float4> d_match_pt;          // k = 1 loop: matched map point (xyz, original index bits) per query slot
-    float4* nn_match_pt = nullptr;    // set by the loop: keep the loop state (sidx, d2, matched point) in query order
-    bool nn_out_sorted = false;       // set by the NN launcher: true if the launched kernel did so
-    bool nn_sorted_k = false;         // set by the loop for k > 1: keep the k matches of a query at its slot of the tile-sorted order
     // what icpmi_debug_last_matches reads: n and k of the last single registration whose matches are still in d_sidx / d_d2 (0 = none), and
     // whether they are in the tile-sorted query order (d_qindex).  Cleared by everything else that writes those buffers or moves the map.
     int64_t last_match_n = 0; int last_match_k = 0; bool last_match_sorted = false;
@@ -628,8 +620,6 @@ struct icpmi_ctx {
     bool zero_pending = false;                                 // d_state / d_selhist still to be cleared: on the stream the handle really uses, at its first call (zero_state_if_pending)
     unsigned scan_tag = 0;                                     // call number of device_scan_flags_count: the tag its count comes back with (map_build.hip)
     IcpState* d_state_mirror = nullptr;                        // ... and its device address: the solve kernel of a single registration writes the finished state there itself (r5)
-    int batch_cur = 1;                                         // readings of the launch sequence being enqueued (set by the loop)
-    BatchArgs batch_args{};                                    // their sizes / slice stride
     unsigned* d_nocc_host = nullptr; bool nocc_by_scan = false; // device address of h_nocc; the pending occupancy word is delivered by the build's scan
     unsigned* h_nocc = nullptr; int64_t nocc_m = 0;            // pinned word: occupied cells of the last index build, and that build's point count (map_build)
     unsigned char* h_pin = nullptr;                            // pinned page: [0, ICPMI_PIN_BYTES) small read-backs, behind it the ring of upload_small
@@ -1046,10 +1036,23 @@ icpmi_status sort_queries(icpmi_ctx* c, const float4* d_pts, int64_t n);
 icpmi_status sort_queries_reserve(icpmi_ctx* c, int64_t n, int nscan = 1);
 icpmi_status sort_queries_batch(icpmi_ctx* c, const float4* d_pts, const BatchArgs& ba, const SortHead* head = nullptr); // slices of d_pts -> slices of d_qsorted / d_qindex
                                                                                  // (head: d_pts is WRITTEN first, from head->raw minus the mean)
-icpmi_status nn_launch_k1(icpmi_ctx* c, const float4* d_reading, int64_t n, const float* d_T, const LoopCfg& lc,
-                          int allow_self, int* d_sidx, float* d_d2, IcpState* d_state);
-icpmi_status nn_launch_k(icpmi_ctx* c, const float4* d_reading, int64_t n, const float* d_T, const LoopCfg& lc,
-                         int allow_self, int* d_sidx, float* d_d2, IcpState* d_state);
+// What ONE launch of the matcher is asked beyond the search itself, and what it answers.  The defaults are a stage call (icpmi_knn, the
+// map-side operators): answers in the caller's order, no fused selection, unseeded, KDTreeMatcher's uniform radius, one reading.
+struct NnRequest {
+    unsigned*    hist0    = nullptr;   // build level 0 of the fused selection here if the launched variant can
+    float4*      match_pt = nullptr;   // k = 1: keep the loop state (sidx, d2, matched point) in query order
+    bool         sorted_k = false;     // k > 1: keep a query's k matches at its slot of the tile-sorted order
+    const float* r2row    = nullptr;   // KDTreeVarDistMatcher / icpmi_knn_var: squared accept radii per query, caller's order (nn.hip: RowR2)
+    int          iter     = 0;         // iteration index of this launch (> 0: seeded by the previous match)
+    BatchArgs    batch{};              // nscan > 1: the readings of a batch (loop_run_batch); otherwise the launch's one reading of n points
+};
+struct NnOutcome {
+    bool built_hist0 = false;          // the launched variant built level 0 of the fused selection
+    bool built_win   = false;          // ... it counted the speculative window (ICPMI_S2_WIN: nnk_wg_kernel in a fused-selection loop)
+    bool out_sorted  = false;          // the state it left is in query order (match_pt / sorted_k honoured)
+};
+icpmi_status nn_launch_k(icpmi_ctx* c, const NnRequest& req, const float4* d_reading, int64_t n, const float* d_T, const LoopCfg& lc,
+                         int allow_self, int* d_sidx, float* d_d2, IcpState* d_state, NnOutcome* out = nullptr);
 icpmi_status nn_ids_to_original(icpmi_ctx* c, const int* d_sidx, int64_t count, int* d_ids);
 // self k-NN of a device cloud through a sparse block grid built for the call (selfgrid.hip): rows of d_sidx / d_d2 in the cloud's order, entries =
 // positions in c->d_map_sorted (w = original index bits), which the call leaves behind for launch_normals / nn_ids_to_original
@@ -1059,8 +1062,9 @@ struct SelfGridSubset { int64_t m_old = 0; const float* d_dk = nullptr; const un
 icpmi_status selfgrid_knn(icpmi_ctx* c, const float4* d_pts, int64_t m, int k, int* d_sidx, float* d_d2, SelfGridSubset* sub = nullptr);
 void selfgrid_destroy(icpmi_ctx* c);
 icpmi_status create_handle(const icpmi_config* cfg, icpmi_handle* out); // icpmi_create without the cache's handle count (private handles)
-icpmi_status loop_run(icpmi_ctx* c, const float4* d_scan, const float* d_normals3, int64_t n, const LoopCfg& lc, bool fixed, float T_out[16],
-                      icpmi_stats* stats);
+// d_r2row: the squared accept radii of a KDTreeVarDistMatcher registration (one per point of the reading), else nullptr
+icpmi_status loop_run(icpmi_ctx* c, const float4* d_scan, const float* d_normals3, int64_t n, const LoopCfg& lc, const float* d_r2row, bool fixed,
+                      float T_out[16], icpmi_stats* stats);
 icpmi_status loop_sensor_noise_overlap(icpmi_ctx* c, int64_t n, const LoopCfg& lc, bool sorted, float* overlap);
 icpmi_status loop_covariance(icpmi_ctx* c, int64_t n, const LoopCfg& lc, bool sorted);
 const float* loop_covariance_out(const icpmi_ctx* c); // device address of the 36 floats loop_covariance leaves

@@ -1338,9 +1338,6 @@ static int acc_blocks(int64_t count, int bt = 256)
     return (int)(nb < 1 ? 1 : (nb > cap ? cap : nb));
 }
 
-// the readings the launch sequence being enqueued works on: the batch set by loop_run_batch, else the single reading
-static BatchArgs cur_batch(const icpmi_ctx* c, int64_t n) { return c->batch_cur > 1 ? c->batch_args : batch_of_one(n); }
-
 // n = points per slice, nscan slices (a single registration: one slice of n points)
 static icpmi_status ensure_loop_buffers(icpmi_ctx* c, int64_t n, int k, int nscan = 1)
 {
@@ -1384,8 +1381,9 @@ static int fused_filter_slot(const LoopCfg& lc)
     return slot;
 }
 
-// enqueue the quantile selections needed by the chain (no host sync)
-static void enqueue_selection(icpmi_ctx* c, const LoopCfg& lc, int64_t count, bool legacy = false)
+// enqueue the quantile selections needed by the chain (no host sync); ba = the readings behind d_d2, nn = what the matcher's launch in front
+// of it answered (the fused chain skips what that launch already built)
+static void enqueue_selection(icpmi_ctx* c, const LoopCfg& lc, int64_t count, const BatchArgs& ba, const NnOutcome& nn, bool legacy = false)
 {
     const int slot = legacy ? -2 : fused_filter_slot(lc);
     int hb = (int)std::min<int64_t>((count + 2047) / 2048, 256);
@@ -1440,20 +1438,18 @@ static void enqueue_selection(icpmi_ctx* c, const LoopCfg& lc, int64_t count, bo
     if (slot >= 0) {
         // fused chain: hist0 -> [scan0 + hist1] -> [scan1 + hist2]; scan2 happens inside the accumulation kernel
         const float quant = lc.out_type[slot] == ICPMI_OUT_MEDIANDIST ? 0.5f : lc.out_param[slot];
-        const BatchArgs ba = cur_batch(c, count / lc.k);
-        if (!c->nn_builds_hist0)
-        {
+        if (!nn.built_hist0) {
             // 4096 matches per workgroup: every workgroup flushes its LDS table with global atomics, fewer of them win (knn 6, 600 k
             // matches: 1024 per workgroup -6 %, 2048 baseline, 4096 +0.8 %, 8192 -4 %)
             int hb0 = (int)std::min<int64_t>((count + 4095) / 4096, 256);
             if (hb0 < 1) hb0 = 1;
             hipLaunchKernelGGL(sel2_hist0_kernel, dim3(hb0, ba.nscan), dim3(256), 0, c->stream, c->d_d2, ba, lc.k, c->d_state, c->d_selhist, quant,
-                               c->nn_builds_win ? 1 : 0);
+                               nn.built_win ? 1 : 0);
         }
         int hb2 = (int)std::min<int64_t>((count + 511) / 512, 512);
         if (hb2 < 1) hb2 = 1;
         hipLaunchKernelGGL(sel2_scan_hist_kernel, dim3(hb2, ba.nscan), dim3(256), 0, c->stream, c->d_d2, ba, lc.k, c->d_state, c->d_selhist, quant,
-                           (c->nn_builds_win && !c->nn_builds_hist0) ? 1 : 0);
+                           (nn.built_win && !nn.built_hist0) ? 1 : 0);
         return;
     }
     for (int f = 0; f < lc.n_out; ++f) {
@@ -1472,24 +1468,23 @@ static void enqueue_selection(icpmi_ctx* c, const LoopCfg& lc, int64_t count, bo
 }
 
 template <int MIN, bool FUSED, bool EXT>
-static void launch_accumulate_ext(icpmi_ctx* c, int64_t n, const LoopCfg& lc, int nb, int slot);
+static void launch_accumulate_ext(icpmi_ctx* c, const LoopCfg& lc, int nb, int slot, const BatchArgs& ba, bool sorted);
 
 template <int MIN, bool FUSED>
-static void launch_accumulate(icpmi_ctx* c, int64_t n, const LoopCfg& lc, int nb, int slot)
+static void launch_accumulate(icpmi_ctx* c, const LoopCfg& lc, int nb, int slot, const BatchArgs& ba, bool sorted)
 {
     // EXT: the chain holds a GenericDescriptor / Robust filter (rare): its own instantiation keeps the common kernels as they were
-    if (lc.ext) launch_accumulate_ext<MIN, FUSED, true>(c, n, lc, nb, slot);
-    else launch_accumulate_ext<MIN, FUSED, false>(c, n, lc, nb, slot);
+    if (lc.ext) launch_accumulate_ext<MIN, FUSED, true>(c, lc, nb, slot, ba, sorted);
+    else launch_accumulate_ext<MIN, FUSED, false>(c, lc, nb, slot, ba, sorted);
 }
 
+// sorted: the loop state is in query order (NnOutcome::out_sorted; k = 1: with the matched points, see nn1_wg_kernel; k > 1: ids and d2)
 template <int MIN, bool FUSED, bool EXT>
-static void launch_accumulate_ext(icpmi_ctx* c, int64_t n, const LoopCfg& lc, int nb, int slot)
+static void launch_accumulate_ext(icpmi_ctx* c, const LoopCfg& lc, int nb, int slot, const BatchArgs& ba, bool sorted)
 {
     const float4* rn = lc.has_read_normals ? c->d_read_normals : nullptr;
     const int is_med = slot >= 0 && lc.out_type[slot] == ICPMI_OUT_MEDIANDIST;
     const float factor = slot >= 0 ? lc.out_param[slot] : 0.f;
-    const bool sorted = c->nn_out_sorted; // loop state in query order (k = 1: with the matched points, see nn1_wg_kernel; k > 1: ids and d2)
-    const BatchArgs ba = cur_batch(c, n);
     if (lc.k > 1) {
         hipLaunchKernelGGL((accumulate_kernel<MIN, FUSED, EXT, 1024>), dim3(nb, ba.nscan), dim3(1024), 0, c->stream, sorted ? c->d_qsorted : c->d_reading, ba, acc_cap(), lc, c->d_state,
                            c->d_map_sorted, c->has_normals ? c->d_normals_sorted : (const float4*)nullptr, rn, c->d_sidx, c->d_d2, c->d_selhist, slot, is_med, factor,
@@ -1504,7 +1499,7 @@ static void launch_accumulate_ext(icpmi_ctx* c, int64_t n, const LoopCfg& lc, in
                        (lc.k > 1 && MIN == ICPMI_MIN_POINT_TO_PLANE && c->has_normals && c->d_map_pn) ? c->d_map_pn : (const float4*)nullptr);
 }
 
-static void enqueue_accumulate_solve(icpmi_ctx* c, int64_t n, const LoopCfg& lc, float* d_Tstep, double* d_sums)
+static void enqueue_accumulate_solve(icpmi_ctx* c, int64_t n, const LoopCfg& lc, const BatchArgs& ba, const NnOutcome& nn, float* d_Tstep, double* d_sums)
 {
     const int64_t count = n * lc.k;
     const int nb = acc_blocks(count, acc_threads(lc.k));
@@ -1514,36 +1509,42 @@ static void enqueue_accumulate_solve(icpmi_ctx* c, int64_t n, const LoopCfg& lc,
     // iteration against this separate 1-workgroup launch, and dragged the solver's registers and scratch
     // into the pair-sum kernel: removed.)
     if (lc.minimizer == ICPMI_MIN_POINT_TO_PLANE) {
-        if (fused) launch_accumulate<ICPMI_MIN_POINT_TO_PLANE, true>(c, n, lc, nb, slot);
-        else launch_accumulate<ICPMI_MIN_POINT_TO_PLANE, false>(c, n, lc, nb, slot);
+        if (fused) launch_accumulate<ICPMI_MIN_POINT_TO_PLANE, true>(c, lc, nb, slot, ba, nn.out_sorted);
+        else launch_accumulate<ICPMI_MIN_POINT_TO_PLANE, false>(c, lc, nb, slot, ba, nn.out_sorted);
     } else if (lc.minimizer == ICPMI_MIN_POINT_TO_POINT) {
-        if (fused) launch_accumulate<ICPMI_MIN_POINT_TO_POINT, true>(c, n, lc, nb, slot);
-        else launch_accumulate<ICPMI_MIN_POINT_TO_POINT, false>(c, n, lc, nb, slot);
+        if (fused) launch_accumulate<ICPMI_MIN_POINT_TO_POINT, true>(c, lc, nb, slot, ba, nn.out_sorted);
+        else launch_accumulate<ICPMI_MIN_POINT_TO_POINT, false>(c, lc, nb, slot, ba, nn.out_sorted);
     } else {
-        if (fused) launch_accumulate<ICPMI_MIN_IDENTITY, true>(c, n, lc, nb, slot);
-        else launch_accumulate<ICPMI_MIN_IDENTITY, false>(c, n, lc, nb, slot);
+        if (fused) launch_accumulate<ICPMI_MIN_IDENTITY, true>(c, lc, nb, slot, ba, nn.out_sorted);
+        else launch_accumulate<ICPMI_MIN_IDENTITY, false>(c, lc, nb, slot, ba, nn.out_sorted);
     }
-    const BatchArgs ba = cur_batch(c, n);
     hipLaunchKernelGGL(solve_kernel, dim3(ba.nscan), dim3(256), 0, c->stream, c->d_state, c->d_selhist, 1, lc, d_Tstep, d_sums,
                        c->d_progress, ba.nscan == 1 ? c->d_state_mirror : (IcpState*)nullptr);
 }
 
-static icpmi_status enqueue_iteration(icpmi_ctx* c, int64_t n, const LoopCfg& lc, hipEvent_t nn0, hipEvent_t nn1)
+// what every launch of a registration's loop asks of the matcher (ba: its readings; NnRequest::iter is set iteration by iteration).  Built
+// once the loop's buffers have their final size.
+static NnRequest loop_request(icpmi_ctx* c, const LoopCfg& lc, const BatchArgs& ba, const float* d_r2row)
+{
+    NnRequest req;
+    req.hist0 = fused_filter_slot(lc) >= 0 ? c->d_selhist.get() : nullptr;
+    req.match_pt = lc.k == 1 ? c->d_match_pt.get() : nullptr;
+    req.sorted_k = lc.k > 1;
+    req.r2row = d_r2row;
+    req.batch = ba;
+    return req;
+}
+
+// iteration req.iter of the loop: match, select, accumulate, solve; *nn = what the matcher's launch answered
+static icpmi_status enqueue_iteration(icpmi_ctx* c, int64_t n, const LoopCfg& lc, const NnRequest& req, NnOutcome* nn, hipEvent_t nn0, hipEvent_t nn1)
 {
     if (nn0) HIP_TRY(c, hipEventRecord(nn0, c->stream));
-    c->nn_hist0 = fused_filter_slot(lc) >= 0 ? c->d_selhist : nullptr;
-    c->nn_builds_hist0 = false;
-    c->nn_builds_win = false;
-    c->nn_match_pt = lc.k == 1 ? c->d_match_pt : nullptr;
-    c->nn_sorted_k = lc.k > 1;
-    c->nn_out_sorted = false;
-    icpmi_status s = nn_launch_k(c, c->d_reading, n, c->d_state->T_iter, lc, 1, c->d_sidx, c->d_d2, c->d_state);
-    c->nn_sorted_k = false; // (only this launch: stage calls on the same handle answer in the caller's order)
+    icpmi_status s = nn_launch_k(c, req, c->d_reading, n, c->d_state->T_iter, lc, 1, c->d_sidx, c->d_d2, c->d_state, nn);
     if (s != ICPMI_OK) return s;
     if (nn1) HIP_TRY(c, hipEventRecord(nn1, c->stream));
-    enqueue_selection(c, lc, n * lc.k);
+    enqueue_selection(c, lc, n * lc.k, req.batch, *nn);
     // (icpmi_debug_keep_sums: the sums of every counted iteration of a SINGLE registration; a batch's solves would all write the one block)
-    enqueue_accumulate_solve(c, n, lc, nullptr, c->batch_cur > 1 ? nullptr : c->d_keep_sums.get());
+    enqueue_accumulate_solve(c, n, lc, req.batch, *nn, nullptr, req.batch.nscan > 1 ? nullptr : c->d_keep_sums.get());
     HIP_TRY(c, hipGetLastError());
     return ICPMI_OK;
 }
@@ -1605,7 +1606,7 @@ static icpmi_status enqueue_registration_head(icpmi_ctx* c, const float4* d_scan
 }
 
 // Capture what enqueue() puts on the handle's stream (a head and the iterations behind it) into g, replacing what g held; g then serves the
-// registrations of signature `sig`
+// registrations of signature `sig`.  enqueue(&nn) leaves in nn what the matcher's last launch answered.
 template <class Enqueue>
 static icpmi_status capture_loop_graph(icpmi_ctx* c, LoopGraph& g, uint64_t sig, Enqueue enqueue)
 {
@@ -1613,24 +1614,25 @@ static icpmi_status capture_loop_graph(icpmi_ctx* c, LoopGraph& g, uint64_t sig,
     hipGraph_t gr = nullptr;
     CaptureGate capture_scope; // (common.h: no device-wide synchronisation of another thread while this one captures)
     HIP_TRY(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-    const icpmi_status s = enqueue();
+    NnOutcome nn;
+    const icpmi_status s = enqueue(&nn);
     const hipError_t ce = hipStreamEndCapture(c->stream, &gr);
     if (s != ICPMI_OK) { if (gr) hipGraphDestroy(gr); return s; }
     HIP_TRY(c, ce);
     const hipError_t ie = hipGraphInstantiate(&g.exec, gr, nullptr, nullptr, 0);
     hipGraphDestroy(gr);
     HIP_TRY(c, ie);
-    g.sig = sig; g.uses = 1; g.sorted = c->nn_out_sorted;
+    g.sig = sig; g.uses = 1; g.sorted = nn.out_sorted;
     return ICPMI_OK;
 }
 
 // what a graph of loop_run is valid for: the chain (its iteration count, hence the segment length, included), the reading's size, every
 // buffer its launches take a pointer to, the grid and the map epoch
-static uint64_t loop_sig(const icpmi_ctx* c, const LoopCfg& lc, const float4* d_scan, const float* d_normals3, int64_t n)
+static uint64_t loop_sig(const icpmi_ctx* c, const LoopCfg& lc, const NnRequest& req, const float4* d_scan, const float* d_normals3, int64_t n)
 {
     uint64_t sig = fnv(&lc, sizeof lc, 1469598103934665603ull);
     const void* ptrs[] = {d_scan, d_normals3, c->d_qkeys, c->d_qtile, c->d_reading, c->d_read_normals, c->d_sidx, c->d_d2, c->d_hard, c->d_state, c->d_match_pt,
-                          c->d_qsorted, c->d_qindex, c->d_map_sorted, c->d_normals_sorted, c->d_cell_start, c->d_selhist, c->nn_r2row,
+                          c->d_qsorted, c->d_qindex, c->d_map_sorted, c->d_normals_sorted, c->d_cell_start, c->d_selhist, req.r2row,
                           c->scratch[0], c->scratch[1], c->scratch[2], c->scratch[3], c->scratch[4]}; // (VarTrimmedDist passes)
     sig = fnv(ptrs, sizeof ptrs, sig);
     sig = fnv(&c->grid, sizeof c->grid, sig);
@@ -1650,8 +1652,8 @@ static bool go_eager(icpmi_ctx* c, int* wasted, bool cached, uint64_t sig)
     return true;
 }
 
-icpmi_status loop_run(icpmi_ctx* c, const float4* d_scan, const float* d_normals3, int64_t n, const LoopCfg& lc_in, bool fixed,
-                      float T_out[16], icpmi_stats* stats)
+icpmi_status loop_run(icpmi_ctx* c, const float4* d_scan, const float* d_normals3, int64_t n, const LoopCfg& lc_in, const float* d_r2row,
+                      bool fixed, float T_out[16], icpmi_stats* stats)
 {
     LoopCfg lc = lc_in;
     c->last_match_n = 0; c->cov_ready = false;
@@ -1661,6 +1663,8 @@ icpmi_status loop_run(icpmi_ctx* c, const float4* d_scan, const float* d_normals
     if (c->d_reading.ensure(c, (size_t)n + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
     if (d_normals3 && c->d_read_normals.ensure(c, (size_t)n + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
     if (c->cfg.knn <= 8 && sort_queries_reserve(c, n) != ICPMI_OK) return ICPMI_ERR_HIP;
+    NnRequest req = loop_request(c, lc, batch_of_one(n), d_r2row);
+    NnOutcome last; // what the last eagerly enqueued iteration's launch answered (a graph keeps its own: LoopGraph::sorted)
 
     const bool profile = c->cfg.profile != 0;
     bool graph = c->cfg.use_graph != 0 && fixed && !profile;
@@ -1679,15 +1683,15 @@ icpmi_status loop_run(icpmi_ctx* c, const float4* d_scan, const float* d_normals
     bool segmented = !graph && !profile && c->cfg.use_graph != 0 && (lc.use_diff || lc.use_bound) && lc.max_iter < 0xfff && lc.max_iter > 1;
     const int S = std::min(4, lc.max_iter);
     LoopGraphs& gs = c->graphs;
-    const uint64_t sig = (graph || segmented) ? loop_sig(c, lc, d_scan, d_normals3, n) : 0;
+    const uint64_t sig = (graph || segmented) ? loop_sig(c, lc, req, d_scan, d_normals3, n) : 0;
     const bool cached = segmented ? gs.seg[0].holds(sig) && gs.seg[1].holds(sig) : gs.fixed.holds(sig);
     if (segmented && go_eager(c, &c->seg_wasted, cached, sig)) segmented = false;
     // (the same rule for the one-graph registration of a Counter-only chain: the shipped configuration, examples/config.yaml:54-57)
     if (graph && go_eager(c, &c->graph_wasted, cached, sig)) graph = false;
     // head (when asked) + `count` iterations from iteration `first` on, in the order every path enqueues them
-    auto enqueue_loop = [&](bool with_head, int first, int count) {
+    auto enqueue_loop = [&](bool with_head, int first, int count, NnOutcome* nn) {
         icpmi_status s = with_head ? enqueue_registration_head(c, d_scan, d_normals3, n) : ICPMI_OK;
-        for (int it = 0; it < count && s == ICPMI_OK; ++it) { c->nn_iter_hint = first + it; s = enqueue_iteration(c, n, lc, nullptr, nullptr); }
+        for (int it = 0; it < count && s == ICPMI_OK; ++it) { req.iter = first + it; s = enqueue_iteration(c, n, lc, req, nn, nullptr, nullptr); }
         return s;
     };
     if (!graph && !segmented) {
@@ -1700,7 +1704,7 @@ icpmi_status loop_run(icpmi_ctx* c, const float4* d_scan, const float* d_normals
             for (LoopGraph& hd : gs.heads) hd.reset(); // (captured the same pointers)
             // (later segments: every iteration is seeded and past the wide first launches -- one graph serves them all)
             for (int g = 0; g < 2; ++g) {
-                const icpmi_status s = capture_loop_graph(c, gs.seg[g], sig, [&] { return enqueue_loop(g == 0, g == 0 ? 0 : S, S); });
+                const icpmi_status s = capture_loop_graph(c, gs.seg[g], sig, [&](NnOutcome* nn) { return enqueue_loop(g == 0, g == 0 ? 0 : S, S, nn); });
                 if (s != ICPMI_OK) return s;
             }
         }
@@ -1717,7 +1721,7 @@ icpmi_status loop_run(icpmi_ctx* c, const float4* d_scan, const float* d_normals
             if (!head) {
                 head = &gs.heads[0];
                 for (LoopGraph& hd : gs.heads) if (!hd.exec) { head = &hd; break; } else if (hd.used < head->used) head = &hd;
-                const icpmi_status s = capture_loop_graph(c, *head, sig, [&] { return enqueue_loop(true, 0, L); });
+                const icpmi_status s = capture_loop_graph(c, *head, sig, [&](NnOutcome* nn) { return enqueue_loop(true, 0, L, nn); });
                 if (s != ICPMI_OK) return s;
                 head->len = L;
             }
@@ -1745,7 +1749,7 @@ icpmi_status loop_run(icpmi_ctx* c, const float4* d_scan, const float* d_normals
         // buffer, the map and the chain stay the same
         ++gs.fixed.uses;
         if (!cached) {
-            const icpmi_status s = capture_loop_graph(c, gs.fixed, sig, [&] { return enqueue_loop(true, 0, lc.max_iter); });
+            const icpmi_status s = capture_loop_graph(c, gs.fixed, sig, [&](NnOutcome* nn) { return enqueue_loop(true, 0, lc.max_iter, nn); });
             if (s != ICPMI_OK) return s;
         }
         HIP_TRY(c, hipGraphLaunch(gs.fixed.exec, c->stream));
@@ -1767,8 +1771,8 @@ icpmi_status loop_run(icpmi_ctx* c, const float4* d_scan, const float* d_normals
         bool stopped = false;
         for (int it = 0; it < lc.max_iter && !stopped; ++it) {
             hipEvent_t e0 = profile ? c->nn_events[2 * it] : nullptr, e1 = profile ? c->nn_events[2 * it + 1] : nullptr;
-            c->nn_iter_hint = it;
-            icpmi_status s = enqueue_iteration(c, n, lc, e0, e1);
+            req.iter = it;
+            icpmi_status s = enqueue_iteration(c, n, lc, req, &last, e0, e1);
             if (s != ICPMI_OK) return s;
             ++launched;
             if (it + 1 >= lc.max_iter) break;
@@ -1856,7 +1860,7 @@ icpmi_status loop_run(icpmi_ctx* c, const float4* d_scan, const float* d_normals
         stats->sensor_noise_overlap = -1.f;
     }
     // the last counted iteration's matches stay in the loop's buffers (dead iterations behind the stop early-exit before they write)
-    const bool sorted_state = graph ? c->graphs.fixed.sorted : (segmented ? c->graphs.seg[1].sorted : c->nn_out_sorted);
+    const bool sorted_state = graph ? c->graphs.fixed.sorted : (segmented ? c->graphs.seg[1].sorted : last.out_sorted);
     if (!c->h_state->error && c->h_state->iter > 0) { c->last_match_n = n; c->last_match_k = lc.k; c->last_match_sorted = sorted_state; }
     if (lc.sensor_noise && stats && !c->h_state->error && c->h_state->iter > 0) {
         // ErrorMinimizer::getOverlap() with sensor noise: one pass over the last iteration's pairs, still in the loop's buffers
@@ -1915,8 +1919,9 @@ icpmi_status loop_run_batch(icpmi_ctx* c, int B, const float* const* d_scans4, c
     if (ensure_loop_buffers(c, NS, lc.k, B) != ICPMI_OK) return ICPMI_ERR_HIP;
     if (c->d_reading.ensure(c, (size_t)NS * B + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
     if (sort_queries_reserve(c, NS, B) != ICPMI_OK) return ICPMI_ERR_HIP;
-    struct Scope { icpmi_ctx* c; ~Scope() { c->batch_cur = 1; c->qsorted_n = -1; c->qsorted_src = nullptr; } } scope{c};
-    c->batch_cur = B; c->batch_args = ba;
+    struct Scope { icpmi_ctx* c; ~Scope() { c->qsorted_n = -1; c->qsorted_src = nullptr; } } scope{c};
+    NnRequest req = loop_request(c, lc, ba, nullptr); // (no var-dist row: such a chain registers its readings one by one)
+    NnOutcome last; // (of the eager iterations; nothing behind the loop reads a batch's matches)
 
     auto head = [&]() -> icpmi_status {
         const int blocks = (int)((nmax + 255) / 256);
@@ -1948,9 +1953,9 @@ icpmi_status loop_run_batch(icpmi_ctx* c, int B, const float* const* d_scans4, c
         sig = fnv(ptrs, sizeof ptrs, sig);
         sig = fnv(&c->grid, sizeof c->grid, sig);
         if (!c->graphs.batch.holds(sig)) {
-            const icpmi_status s = capture_loop_graph(c, c->graphs.batch, sig, [&] {
+            const icpmi_status s = capture_loop_graph(c, c->graphs.batch, sig, [&](NnOutcome* nn) {
                 icpmi_status s = head();
-                for (int it = 0; it < lc.max_iter && s == ICPMI_OK; ++it) { c->nn_iter_hint = it; s = enqueue_iteration(c, nmax, lc, nullptr, nullptr); }
+                for (int it = 0; it < lc.max_iter && s == ICPMI_OK; ++it) { req.iter = it; s = enqueue_iteration(c, nmax, lc, req, nn, nullptr, nullptr); }
                 return s;
             });
             if (s != ICPMI_OK) return s;
@@ -1963,8 +1968,8 @@ icpmi_status loop_run_batch(icpmi_ctx* c, int B, const float* const* d_scans4, c
         const bool poll = (lc.use_diff || lc.use_bound) && lc.max_iter < 0xfff;
         bool stopped = false;
         for (int it = 0; it < lc.max_iter && !stopped; ++it) {
-            c->nn_iter_hint = it;
-            s = enqueue_iteration(c, nmax, lc, nullptr, nullptr);
+            req.iter = it;
+            s = enqueue_iteration(c, nmax, lc, req, &last, nullptr, nullptr);
             if (s != ICPMI_OK) return s;
             if (it + 1 >= lc.max_iter || !poll) continue;
             // as loop_run: stay `ahead` iterations in front of the slowest reading still running; stop when all have stopped, or when the
@@ -2020,17 +2025,14 @@ icpmi_status loop_single_step(icpmi_ctx* c, int64_t n, const LoopCfg& lc, const 
     HIP_TRY(c, hipMemsetAsync(d_Tstep, 0, 16 * sizeof(float), c->stream));
     LoopCfg l1 = lc;
     l1.max_iter = 1; l1.use_diff = 0; l1.use_bound = 0;
-    c->nn_iter_hint = 0;
-    c->nn_hist0 = fused_filter_slot(l1) >= 0 ? c->d_selhist : nullptr;
-    c->nn_builds_hist0 = false;
-    c->nn_builds_win = false;
-    c->nn_match_pt = nullptr;
-    c->nn_sorted_k = false;
-    c->nn_out_sorted = false;
-    icpmi_status s = nn_launch_k(c, c->d_reading, n, c->d_state->T_iter, l1, 1, c->d_sidx, c->d_d2, c->d_state);
+    NnRequest req; // (one unseeded launch that answers in the caller's order)
+    req.hist0 = fused_filter_slot(l1) >= 0 ? c->d_selhist.get() : nullptr;
+    req.batch = batch_of_one(n);
+    NnOutcome nn;
+    icpmi_status s = nn_launch_k(c, req, c->d_reading, n, c->d_state->T_iter, l1, 1, c->d_sidx, c->d_d2, c->d_state, &nn);
     if (s == ICPMI_OK) {
-        enqueue_selection(c, l1, n * l1.k);
-        enqueue_accumulate_solve(c, n, l1, d_Tstep, d_sums);
+        enqueue_selection(c, l1, n * l1.k, req.batch, nn);
+        enqueue_accumulate_solve(c, n, l1, req.batch, nn, d_Tstep, d_sums);
     }
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(c->h_state, c->d_state, sizeof(IcpState), hipMemcpyDeviceToHost, c->stream);
@@ -2095,7 +2097,7 @@ icpmi_status loop_outlier_weights(icpmi_ctx* c, const LoopCfg& lc, const float* 
     HIP_TRY(c, hipMemcpyAsync(c->d_d2, d2, (size_t)count * sizeof(float), hipMemcpyHostToDevice, c->stream));
     if (needs_ids && ids) HIP_TRY(c, hipMemcpyAsync(c->d_sidx, ids, (size_t)count * sizeof(int), hipMemcpyHostToDevice, c->stream));
     else HIP_TRY(c, hipMemsetAsync(c->d_sidx, 0, (size_t)count * sizeof(int), c->stream));
-    enqueue_selection(c, l1, count, true);
+    enqueue_selection(c, l1, count, batch_of_one(n), NnOutcome(), true); // (no matcher launch in front: the caller's d2)
     DevBuf<float> d_w;
     HIP_TRY(c, d_w.alloc((size_t)count));
     const int blocks = (int)((count + 255) / 256);

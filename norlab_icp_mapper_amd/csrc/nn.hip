@@ -1536,161 +1536,156 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KMAX <= 8 ?
 
 } // namespace
 
-// the accept radius of the launch being enqueued: KDTreeMatcher's maxDist^2, or -- icpmi_ctx::nn_r2row set by the caller for exactly this
-// launch sequence -- the row of a KDTreeVarDistMatcher with the uniform bound lc.maxr2 (f is called with a float or a RowR2)
+// the accept radius of a launch: KDTreeMatcher's maxDist^2, or -- NnRequest::r2row -- the row of a KDTreeVarDistMatcher with the uniform
+// bound lc.maxr2 (f is called with a float or a RowR2)
 template <class F>
-static void with_accept_radius(const icpmi_ctx* c, const LoopCfg& lc, const int* slot_index, F f)
+static void with_accept_radius(const NnRequest& req, const LoopCfg& lc, const int* slot_index, F f)
 {
-    if (c->nn_r2row) f(RowR2{lc.maxr2, c->nn_r2row, slot_index});
+    if (req.r2row) f(RowR2{lc.maxr2, req.r2row, slot_index});
     else f(lc.maxr2);
 }
 
-void nn_launch_hard_k1(icpmi_ctx* c, const float4* d_reading, const float* d_T, const LoopCfg& lc, int allow_self, int* d_sidx,
-                       float* d_d2, IcpState* d_state)
+// the pyramid cannot decide every query (unbounded maxDist -- PM::ICPSequence::setDefault() --, or a maxDist beyond the top level's block):
+// the brute pass runs behind the pyramid kernel
+static bool needs_hard_pass(const icpmi_ctx* c, const LoopCfg& lc)
 {
-    with_accept_radius(c, lc, nullptr, [&](auto maxr) {
-        hipLaunchKernelGGL(nn1_hard_kernel<decltype(maxr)>, dim3(512), dim3(NN_BLOCK), 0, c->stream, d_reading, d_T, c->d_map_sorted, (int)c->m, maxr,
-                           allow_self, d_sidx, d_d2, d_state, c->d_hard, (float4*)nullptr, (unsigned*)nullptr);
-    });
-    hipLaunchKernelGGL(hard_reset_kernel, dim3(1), dim3(64), 0, c->stream, d_state);
+    const GridParams& top = c->levels.g[c->levels.nlev - 1];
+    return !std::isfinite(lc.max_dist) || (top.cell - top.slack) <= lc.max_dist;
 }
 
-icpmi_status nn_launch_k1(icpmi_ctx* c, const float4* d_reading, int64_t n, const float* d_T, const LoopCfg& lc, int allow_self,
-                          int* d_sidx, float* d_d2, IcpState* d_state)
+static icpmi_status nn_launch_k1(icpmi_ctx* c, const NnRequest& req, const float4* d_reading, int64_t n, const float* d_T, const LoopCfg& lc,
+                                 int allow_self, int* d_sidx, float* d_d2, IcpState* d_state, NnOutcome* out)
 {
-    c->nn_out_sorted = false;
-    {
-        // grid pyramid; sorted queries when the caller prepared them for exactly this cloud
-        const bool sorted = c->batch_cur > 1 || (c->qsorted_n == n && c->qsorted_src == d_reading); // a batch is always tile-sorted
-        const float4* q = sorted ? c->d_qsorted : d_reading;
-        const int* qi = sorted ? c->d_qindex : nullptr;
-        if (n == 0) return ICPMI_OK;
-        // the brute pass may still overwrite d2 of queued queries: only build the histogram here when
-        // every query is decided on the pyramid
-        const GridParams& topg = c->levels.g[c->levels.nlev - 1];
-        const bool needs_hard = !std::isfinite(lc.max_dist) || (topg.cell - topg.slack) <= lc.max_dist;
-        // The NN kernel builds level 0 of the fused quantile selection itself (loop.hip): fine bins by
-        // direct atomics, the hot coarse bins through LDS and privatised copies.  (r1 measurement: a
-        // single 2048-bin level-0 histogram flushed by every workgroup cost +20 us in same-address
-        // atomics; the two-tier layout removes that.)  ICPMI_NN_FUSE_HIST0=0 falls back to the
-        // stand-alone builder kernel.
-        const int unseeded_lev = 0;
-        // r5: a chain that may need the brute pass (unbounded maxDist -- PM::ICPSequence::setDefault() --, or a maxDist beyond the top level's
-        // block) keeps the fast path: the queue holds query slots and the brute pass writes the same state (point, histogram) for what it decides.
-        const bool hard_sorted = needs_hard && allow_self && sorted && c->batch_cur <= 1;
-        unsigned* h0 = (needs_hard && !hard_sorted) ? nullptr : c->nn_hist0;
-        c->nn_builds_hist0 = h0 != nullptr;
-        // loop mode keeps the per-query state in query order
-        float4* mp = ((needs_hard && !hard_sorted) || !sorted) ? nullptr : c->nn_match_pt;
-        c->nn_out_sorted = mp != nullptr;
-        // a batch (c->batch_cur > 1, set by loop_run_batch): grid.y = readings, grid.x sized for the largest one
-        const BatchArgs ba = c->batch_cur > 1 ? c->batch_args : batch_of_one(n);
-        // the first solve moves the reading by the whole initial misalignment, so the seeds of iteration 1 bound the search no better than a
-        // fresh own-row scan: that launch starts with the own-row pass at level 0 (seed_pre), the later ones go straight to their seed
-        const bool seeded = c->nn_iter_hint > 0 && allow_self;
-        const int seed_pre = (seeded && c->nn_iter_hint > 1) ? 0 : 1;
+    if (n == 0) return ICPMI_OK;
+    // grid pyramid; sorted queries when the caller prepared them for exactly this cloud
+    const bool batch = req.batch.nscan > 1;
+    const bool sorted = batch || (c->qsorted_n == n && c->qsorted_src == d_reading); // a batch is always tile-sorted
+    const float4* q = sorted ? c->d_qsorted : d_reading;
+    const int* qi = sorted ? c->d_qindex : nullptr;
+    // the brute pass may still overwrite d2 of queued queries: only build the histogram here when
+    // every query is decided on the pyramid
+    const bool needs_hard = needs_hard_pass(c, lc);
+    // The NN kernel builds level 0 of the fused quantile selection itself (loop.hip): fine bins by
+    // direct atomics, the hot coarse bins through LDS and privatised copies.  (r1 measurement: a
+    // single 2048-bin level-0 histogram flushed by every workgroup cost +20 us in same-address
+    // atomics; the two-tier layout removes that.)  ICPMI_NN_FUSE_HIST0=0 falls back to the
+    // stand-alone builder kernel.
+    const int unseeded_lev = 0;
+    // r5: a chain that may need the brute pass keeps the fast path: the queue holds query slots and the brute pass writes the same state
+    // (point, histogram) for what it decides.
+    const bool hard_sorted = needs_hard && allow_self && sorted && !batch;
+    unsigned* h0 = (needs_hard && !hard_sorted) ? nullptr : req.hist0;
+    out->built_hist0 = h0 != nullptr;
+    // loop mode keeps the per-query state in query order
+    float4* mp = ((needs_hard && !hard_sorted) || !sorted) ? nullptr : req.match_pt;
+    out->out_sorted = mp != nullptr;
+    // a batch (loop_run_batch): grid.y = readings, grid.x sized for the largest one
+    const BatchArgs ba = batch ? req.batch : batch_of_one(n);
+    // the first solve moves the reading by the whole initial misalignment, so the seeds of iteration 1 bound the search no better than a
+    // fresh own-row scan: that launch starts with the own-row pass at level 0 (seed_pre), the later ones go straight to their seed
+    const bool seeded = req.iter > 0 && allow_self;
+    const int seed_pre = (seeded && req.iter > 1) ? 0 : 1;
 #define LAUNCH_WG(S_)                                                                                                           \
     hipLaunchKernelGGL((nn1_wg_kernel<4, S_, decltype(maxr)>), dim3((int)(((n + 63) / 64 + 7) / 8 * 8), ba.nscan), dim3(256), 0, c->stream,    \
                        q, qi, ba, d_T, c->levels, maxr, d_sidx, d_d2, d_state, c->d_hard, h0, mp, c->d_lvl_tab, unseeded_lev, seed_pre, lc.inv1e, lc.err2)
-        with_accept_radius(c, lc, nullptr, [&](auto maxr) { if (allow_self) LAUNCH_WG(true); else LAUNCH_WG(false); });
+    with_accept_radius(req, lc, nullptr, [&](auto maxr) { if (allow_self) LAUNCH_WG(true); else LAUNCH_WG(false); });
 #undef LAUNCH_WG
-        const GridParams& top = c->levels.g[c->levels.nlev - 1];
-        if (!std::isfinite(lc.max_dist) || (top.cell - top.slack) <= lc.max_dist) {
-            if (hard_sorted && mp) // (the queue holds query slots: the row of a KDTreeVarDistMatcher is reached through the slot's caller index)
-                with_accept_radius(c, lc, qi, [&](auto maxr) {
-                    hipLaunchKernelGGL(nn1_hard_kernel<decltype(maxr)>, dim3(512), dim3(NN_BLOCK), 0, c->stream, q, d_T, c->d_map_sorted, (int)c->m,
-                                       maxr, allow_self, d_sidx, d_d2, d_state, c->d_hard, mp, c->nn_builds_hist0 ? c->nn_hist0 : (unsigned*)nullptr);
-                });
-            else
-                with_accept_radius(c, lc, nullptr, [&](auto maxr) {
-                    hipLaunchKernelGGL(nn1_hard_kernel<decltype(maxr)>, dim3(512), dim3(NN_BLOCK), 0, c->stream, d_reading, d_T, c->d_map_sorted, (int)c->m,
-                                       maxr, allow_self, d_sidx, d_d2, d_state, c->d_hard, (float4*)nullptr, (unsigned*)nullptr);
-                });
-            // (the loop's solve_kernel empties the queue; a stage call -- icpmi_knn -- has no solve behind it)
-            if (!(hard_sorted && mp)) hipLaunchKernelGGL(hard_reset_kernel, dim3(1), dim3(64), 0, c->stream, d_state);
-        }
-        HIP_TRY(c, hipGetLastError());
-        return ICPMI_OK;
+    if (needs_hard) {
+        if (hard_sorted && mp) // (the queue holds query slots: the row of a KDTreeVarDistMatcher is reached through the slot's caller index)
+            with_accept_radius(req, lc, qi, [&](auto maxr) {
+                hipLaunchKernelGGL(nn1_hard_kernel<decltype(maxr)>, dim3(512), dim3(NN_BLOCK), 0, c->stream, q, d_T, c->d_map_sorted, (int)c->m,
+                                   maxr, allow_self, d_sidx, d_d2, d_state, c->d_hard, mp, h0);
+            });
+        else
+            with_accept_radius(req, lc, nullptr, [&](auto maxr) {
+                hipLaunchKernelGGL(nn1_hard_kernel<decltype(maxr)>, dim3(512), dim3(NN_BLOCK), 0, c->stream, d_reading, d_T, c->d_map_sorted, (int)c->m,
+                                   maxr, allow_self, d_sidx, d_d2, d_state, c->d_hard, (float4*)nullptr, (unsigned*)nullptr);
+            });
+        // (the loop's solve_kernel empties the queue; a stage call -- icpmi_knn -- has no solve behind it)
+        if (!(hard_sorted && mp)) hipLaunchKernelGGL(hard_reset_kernel, dim3(1), dim3(64), 0, c->stream, d_state);
     }
+    HIP_TRY(c, hipGetLastError());
+    return ICPMI_OK;
 }
 
 template <int KMAX>
-static icpmi_status nnk_launch_t(icpmi_ctx* c, const float4* d_reading, int64_t n, const float* d_T, const LoopCfg& lc,
-                                 int allow_self, int* d_sidx, float* d_d2, IcpState* d_state)
+static icpmi_status nnk_launch_t(icpmi_ctx* c, const NnRequest& req, const float4* d_reading, int64_t n, const float* d_T, const LoopCfg& lc,
+                                 int allow_self, int* d_sidx, float* d_d2, IcpState* d_state, NnOutcome* out)
 {
-    if constexpr (KMAX <= 16) if (n > 0) {
-        constexpr int KM = KMAX; // (k <= 16: the cooperative kernels; r2 stopped at 8 and left knn 10 on the one-lane kernel, 5 x slower)
-        {
-            constexpr int G = 8;
-            const bool sorted = c->qsorted_n == n && c->qsorted_src == d_reading;
-            const float4* q = sorted ? c->d_qsorted : d_reading;
-            const int* qi = sorted ? c->d_qindex : nullptr;
-            const int seeded = (c->nn_iter_hint > 0 && allow_self) ? 3 : 0; // bit 1: wide seeds start with the own-row pass at level 0 (nnk_ml_kernel)
-            const int grid = (int)(((n * G + NN_BLOCK - 1) / NN_BLOCK + 7) / 8 * 8);
-            const GridParams& top = c->levels.g[c->levels.nlev - 1];
-            const bool needs_hard = !std::isfinite(lc.max_dist) || (top.cell - top.slack) <= lc.max_dist;
-            // loop mode: results in query order (the brute-force pass works in the caller's order: chains that may need it stay there)
-            const int out_sorted = (c->nn_sorted_k && sorted && !needs_hard) ? 1 : 0;
-            c->nn_out_sorted = out_sorted != 0;
-            // the loop's seeded launches from iteration 2 on: nnk_wg_kernel; iterations 0 / 1 (no seed / seeds the first solve moved far), batches and
-            // stage calls: nnk_ml_kernel.  (icpmi_config::knn_wg_from, a test seam: -1 = nnk_ml_kernel everywhere, 0 / 1 = nnk_wg_kernel earlier.)
-            const int wg_from = c->cfg.knn_wg_from == 0 ? 2 : (c->cfg.knn_wg_from < 0 ? -1 : c->cfg.knn_wg_from - 1);
-            const int wg_pre = 1;
-            const bool use_wg = wg_from >= 0 && allow_self && c->nn_iter_hint >= wg_from && c->batch_cur <= 1;
-            // (r5) the speculative window of the fused selection (common.h: ICPMI_S2_WIN): loops with one quantile filter whose every query is
-            // decided on the pyramid (the brute pass rewrites d2 afterwards), below 2^21 matches (the packed counts cannot carry); icpmi_config::sel_window_off: off
-            const int sel_win = c->cfg.sel_window_off ? 0 : 1;
-            c->nn_builds_win = use_wg && sel_win && c->nn_hist0 != nullptr && d_d2 == c->d_d2 && !needs_hard && n * (int64_t)lc.k < ICPMI_WIN_MAX_COUNT;
-            with_accept_radius(c, lc, nullptr, [&](auto maxr) {
-                using R = decltype(maxr);
-                if (use_wg)
-                    hipLaunchKernelGGL((nnk_wg_kernel<KM, R>), dim3((int)(((n + 63) / 64 + 7) / 8 * 8)), dim3(256), 0, c->stream, q, qi,
-                                       (int)n, d_T, c->d_lvl_tab, c->levels.nlev, lc.k, maxr, d_sidx, d_d2, d_state, c->d_hard, out_sorted, wg_pre,
-                                       c->nn_builds_win ? reinterpret_cast<unsigned long long*>(c->nn_hist0 + ICPMI_S2_WIN) : (unsigned long long*)nullptr,
-                                       lc.inv1e, lc.err2);
-                else
-                    hipLaunchKernelGGL((nnk_ml_kernel<G, KM, R>), dim3(grid), dim3(NN_BLOCK), 0, c->stream, q, qi, (int)n, d_T, c->d_lvl_tab,
-                                       c->levels.nlev, lc.k, maxr, allow_self, seeded, d_sidx, d_d2, d_state, c->d_hard, out_sorted, lc.inv1e, lc.err2);
-                if (!std::isfinite(lc.max_dist) || (top.cell - top.slack) <= lc.max_dist) {
-                    hipLaunchKernelGGL((nnk_hard_kernel<KMAX, R>), dim3(512), dim3(NN_BLOCK), 0, c->stream, d_reading, d_T, c->d_map_sorted,
-                                       (int)c->m, lc.k, maxr, allow_self, d_sidx, d_d2, d_state, c->d_hard);
-                    hipLaunchKernelGGL(hard_reset_kernel, dim3(1), dim3(64), 0, c->stream, d_state);
-                }
-            });
-            HIP_TRY(c, hipGetLastError());
-            return ICPMI_OK;
-        }
-    }
-    // k = 17 .. 32: one lane per query, ring search (the cooperative kernels keep their lists in registers up to k = 16)
-    if constexpr (KMAX > 16) {
+    if (n == 0) return ICPMI_OK;
+    if constexpr (KMAX <= 16) { // the cooperative kernels (r2 stopped at 8 and left knn 10 on the one-lane kernel, 5 x slower)
+        constexpr int G = 8;
+        const bool sorted = c->qsorted_n == n && c->qsorted_src == d_reading;
+        const float4* q = sorted ? c->d_qsorted : d_reading;
+        const int* qi = sorted ? c->d_qindex : nullptr;
+        const int seeded = (req.iter > 0 && allow_self) ? 3 : 0; // bit 1: wide seeds start with the own-row pass at level 0 (nnk_ml_kernel)
+        const int grid = (int)(((n * G + NN_BLOCK - 1) / NN_BLOCK + 7) / 8 * 8);
+        const bool needs_hard = needs_hard_pass(c, lc);
+        // loop mode: results in query order (the brute-force pass works in the caller's order: chains that may need it stay there)
+        const int out_sorted = (req.sorted_k && sorted && !needs_hard) ? 1 : 0;
+        out->out_sorted = out_sorted != 0;
+        // the loop's seeded launches from iteration 2 on: nnk_wg_kernel; iterations 0 / 1 (no seed / seeds the first solve moved far), batches and
+        // stage calls: nnk_ml_kernel.  (icpmi_config::knn_wg_from, a test seam: -1 = nnk_ml_kernel everywhere, 0 / 1 = nnk_wg_kernel earlier.)
+        const int wg_from = c->cfg.knn_wg_from == 0 ? 2 : (c->cfg.knn_wg_from < 0 ? -1 : c->cfg.knn_wg_from - 1);
+        const int wg_pre = 1;
+        const bool use_wg = wg_from >= 0 && allow_self && req.iter >= wg_from && req.batch.nscan <= 1;
+        // (r5) the speculative window of the fused selection (common.h: ICPMI_S2_WIN): loops with one quantile filter whose every query is
+        // decided on the pyramid (the brute pass rewrites d2 afterwards), below 2^21 matches (the packed counts cannot carry); icpmi_config::sel_window_off: off
+        const int sel_win = c->cfg.sel_window_off ? 0 : 1;
+        const bool win = use_wg && sel_win && req.hist0 != nullptr && d_d2 == c->d_d2 && !needs_hard && n * (int64_t)lc.k < ICPMI_WIN_MAX_COUNT;
+        out->built_win = win;
+        with_accept_radius(req, lc, nullptr, [&](auto maxr) {
+            using R = decltype(maxr);
+            if (use_wg)
+                hipLaunchKernelGGL((nnk_wg_kernel<KMAX, R>), dim3((int)(((n + 63) / 64 + 7) / 8 * 8)), dim3(256), 0, c->stream, q, qi,
+                                   (int)n, d_T, c->d_lvl_tab, c->levels.nlev, lc.k, maxr, d_sidx, d_d2, d_state, c->d_hard, out_sorted, wg_pre,
+                                   win ? reinterpret_cast<unsigned long long*>(req.hist0 + ICPMI_S2_WIN) : (unsigned long long*)nullptr,
+                                   lc.inv1e, lc.err2);
+            else
+                hipLaunchKernelGGL((nnk_ml_kernel<G, KMAX, R>), dim3(grid), dim3(NN_BLOCK), 0, c->stream, q, qi, (int)n, d_T, c->d_lvl_tab,
+                                   c->levels.nlev, lc.k, maxr, allow_self, seeded, d_sidx, d_d2, d_state, c->d_hard, out_sorted, lc.inv1e, lc.err2);
+            if (needs_hard) {
+                hipLaunchKernelGGL((nnk_hard_kernel<KMAX, R>), dim3(512), dim3(NN_BLOCK), 0, c->stream, d_reading, d_T, c->d_map_sorted,
+                                   (int)c->m, lc.k, maxr, allow_self, d_sidx, d_d2, d_state, c->d_hard);
+                hipLaunchKernelGGL(hard_reset_kernel, dim3(1), dim3(64), 0, c->stream, d_state);
+            }
+        });
+    } else { // k = 17 .. 32: one lane per query, ring search (the cooperative kernels keep their lists in registers up to k = 16)
         const int blocks = (int)((n + NN_BLOCK - 1) / NN_BLOCK);
-        if (blocks == 0) return ICPMI_OK;
-        with_accept_radius(c, lc, nullptr, [&](auto maxr) {
+        with_accept_radius(req, lc, nullptr, [&](auto maxr) {
             using R = decltype(maxr);
             hipLaunchKernelGGL((nnk_kernel<KMAX, R>), dim3(blocks), dim3(NN_BLOCK), 0, c->stream, d_reading, (int)n, d_T, c->grid,
                                c->d_map_sorted, c->d_cell_start, lc.k, maxr, lc.ring_max, allow_self, d_sidx, d_d2, d_state, c->d_hard,
                                (const unsigned*)nullptr, (const unsigned*)nullptr);
+            // (the ring search's own rule: the rings it walked do not cover maxDist)
             if (!std::isfinite(lc.max_dist) || lc.ring_max < (int)ceilf(lc.max_dist / c->grid.cell) + 1) {
                 hipLaunchKernelGGL((nnk_hard_kernel<KMAX, R>), dim3(512), dim3(NN_BLOCK), 0, c->stream, d_reading, d_T, c->d_map_sorted,
                                    (int)c->m, lc.k, maxr, allow_self, d_sidx, d_d2, d_state, c->d_hard);
                 hipLaunchKernelGGL(hard_reset_kernel, dim3(1), dim3(64), 0, c->stream, d_state);
             }
         });
-        HIP_TRY(c, hipGetLastError());
     }
+    HIP_TRY(c, hipGetLastError());
     return ICPMI_OK;
 }
 
-icpmi_status nn_launch_k(icpmi_ctx* c, const float4* d_reading, int64_t n, const float* d_T, const LoopCfg& lc, int allow_self,
-                         int* d_sidx, float* d_d2, IcpState* d_state)
+// One search of n queries for their lc.k nearest map points.  What the launch is asked beyond that comes in `req`, what it decided goes to
+// `*out` (common.h: NnRequest / NnOutcome); of the handle it changes last_match_n and, on failure, last_error -- nothing else.
+icpmi_status nn_launch_k(icpmi_ctx* c, const NnRequest& req, const float4* d_reading, int64_t n, const float* d_T, const LoopCfg& lc,
+                         int allow_self, int* d_sidx, float* d_d2, IcpState* d_state, NnOutcome* out)
 {
+    NnOutcome unread;
+    if (!out) out = &unread;
+    *out = NnOutcome();
     c->last_match_n = 0; // (loop_run sets it again once its last iteration is in)
-    if (lc.k == 1) return nn_launch_k1(c, d_reading, n, d_T, lc, allow_self, d_sidx, d_d2, d_state);
-    if (lc.k <= 4) return nnk_launch_t<4>(c, d_reading, n, d_T, lc, allow_self, d_sidx, d_d2, d_state);
-    if (lc.k <= 6) return nnk_launch_t<6>(c, d_reading, n, d_T, lc, allow_self, d_sidx, d_d2, d_state); // knn 6: the documented chain
-    if (lc.k <= 8) return nnk_launch_t<8>(c, d_reading, n, d_T, lc, allow_self, d_sidx, d_d2, d_state);
-    if (lc.k <= 16) return nnk_launch_t<16>(c, d_reading, n, d_T, lc, allow_self, d_sidx, d_d2, d_state);
-    if (lc.k <= 32) return nnk_launch_t<32>(c, d_reading, n, d_T, lc, allow_self, d_sidx, d_d2, d_state);
+#define NNK(KMAX_) nnk_launch_t<KMAX_>(c, req, d_reading, n, d_T, lc, allow_self, d_sidx, d_d2, d_state, out)
+    if (lc.k == 1) return nn_launch_k1(c, req, d_reading, n, d_T, lc, allow_self, d_sidx, d_d2, d_state, out);
+    if (lc.k <= 4) return NNK(4);
+    if (lc.k <= 6) return NNK(6); // knn 6: the documented chain
+    if (lc.k <= 8) return NNK(8);
+    if (lc.k <= 16) return NNK(16);
+    if (lc.k <= 32) return NNK(32);
+#undef NNK
     c->last_error = "knn > 32 is not supported";
     return ICPMI_ERR_UNSUPPORTED;
 }

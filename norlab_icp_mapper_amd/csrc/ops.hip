@@ -471,8 +471,7 @@ icpmi_status chain_point_distance_flags(icpmi_ctx* c, icpmi_ctx* ic, const float
     if (ic->d_sidx.ensure(ic, cnt) != ICPMI_OK || ic->d_d2.ensure(ic, cnt) != ICPMI_OK ||
         ic->d_hard.ensure(ic, cnt) != ICPMI_OK) { c->last_error = ic->last_error; return ICPMI_ERR_HIP; }
     HIP_TRY(c, hipMemsetAsync(ic->d_state, 0, sizeof(IcpState), ic->stream));
-    ic->nn_hist0 = nullptr; ic->nn_iter_hint = 0; ic->nn_match_pt = nullptr;
-    s = nn_launch_k(ic, ic->d_reading, n, nullptr, lc, 0, ic->d_sidx, ic->d_d2, ic->d_state);
+    s = nn_launch_k(ic, NnRequest(), ic->d_reading, n, nullptr, lc, 0, ic->d_sidx, ic->d_d2, ic->d_state);
     if (s != ICPMI_OK) { c->last_error = ic->last_error; return s; }
     hipLaunchKernelGGL(keep_flag_kernel, dim3((int)((n + 255) / 256)), dim3(256), 0, ic->stream, ic->d_d2, n, lim, d_flag);
     HIP_TRY(c, hipGetLastError());
