@@ -613,6 +613,63 @@ icpmi_status icpmi_sensor_model(icpmi_handle h, const float* in4, int64_t n,
                                 float* normals3_out, float* obs_dir3_out,
                                 float* noise_out, uint8_t* keep_out);
 
+/* Sweep deskewing: per-point motion compensation of one scan.  A spinning lidar takes ~0.1 s per sweep, and the reference tells its
+ * users to switch deskewing on (docs/UsingInRos.md:211-224); there it lives in the ROS wrapper, in front of applyInputFilters ->
+ * processInput, because it needs tf2's interpolation.  The semantics are tf2's lookup AS RECALLED (the wrapper's source is not on
+ * hand): the caller gives the sensor's motion over the sweep as K timed poses of the sensor in a fixed frame, translation p_k and unit
+ * quaternion q_k at time s_k; the pose T(tau) at s_k <= tau <= s_{k+1} has its translation interpolated linearly and its rotation by
+ * slerp along the shorter arc; deskewing to the time ref sends a point x_i measured at tau_i to T(ref)^-1 T(tau_i) x_i, and rows
+ * that rotate with the cloud (`normals`) are rotated by the rotation part of the same transform, as icpmi_transform does.
+ *
+ * icpmi_deskew_table (no handle, no device call, double precision) is the preparation every call makes, exposed so that it can be
+ * checked on its own: T(ref_s) is interpolated from the table; M_k = T(ref_s)^-1 T_k is formed for every k and its quaternion
+ * normalised; walking k upwards, q_{k+1} is negated when q_k . q_{k+1} < 0; per segment Omega_k = 2 atan2(|q_{k+1} - q_k|,
+ * |q_{k+1} + q_k|) and inv_sin_k = 1 / sin(Omega_k), or 0 when Omega_k < 2^-20 (a zero marks the segment as plain lerp); everything is
+ * then rounded to float32: q4 (4 K: x y z w), p3 (3 K), omega (K - 1), inv_sin (K - 1).  The poses being relative to ref, the
+ * translations are the centimetres of one sweep and not map coordinates, and the angle never comes from acosf of a number next to 1:
+ * that is what makes float32 enough on the device.
+ *
+ * The device pass, one thread per point, no atomics (csrc/deskew.hip: deskew_kernel).  float32 unless marked, in exactly the order
+ * written, every product, sum and division correctly rounded and never contracted (-ffp-contract=off), so a float32 restatement is
+ * unambiguous up to sinf:
+ *   tau = (double)t_rel[i] * time_unit_s                                  (fp64); a NaN raises the error flag
+ *   round_s > 0:  tau = rint(tau / round_s) * round_s                     (fp64, ties to even)
+ *   tau outside [s_0, s_{K-1}]:  extrapolate ? clamped to the bound : the error flag
+ *   k = the largest index in [0, K - 2] with s_k <= tau  (s_k <= tau < s_{k+1}; tau == s_{K-1} belongs to the last segment, u = 1)
+ *   u = (float)((tau - s_k) / (s_{k+1} - s_k))                            (fp64, rounded once);  um = 1 - u
+ *   inv_sin_k == 0 ?  w0 = um, w1 = u  :  w0 = sinf(um * Omega_k) * inv_sin_k,  w1 = sinf(u * Omega_k) * inv_sin_k
+ *   q = w0 q_k + w1 q_{k+1}  (per component, not renormalised, as in tf2);   p = um p_k + u p_{k+1}  (per component)
+ *   xx = qx qx, yy = qy qy, zz = qz qz, xy = qx qy, xz = qx qz, yz = qy qz, wx = qw qx, wy = qw qy, wz = qw qz
+ *   R = [ 1 - 2 (yy + zz), 2 (xy - wz), 2 (xz + wy) ;  2 (xy + wz), 1 - 2 (xx + zz), 2 (yz - wx) ;  2 (xz - wy), 2 (yz + wx), 1 - 2 (xx + yy) ]
+ *   out_r = ((R_r0 x + R_r1 y) + R_r2 z) + p_r;  the fourth component is copied through;  normal_r = (R_r0 nx + R_r1 ny) + R_r2 nz
+ * in4 / out4: 4 per point; t_rel: one float per point, the point's time in units of time_unit_s from the scan's stamp (the bundled
+ * scans' `t` descriptor: nanoseconds, time_unit_s = 1e-9); in_normals3 / out_normals3 (3 per point) both or neither.
+ * ICPMI_ERR_INVALID_ARG with a message (icpmi_last_error(h); icpmi_last_error(NULL) after icpmi_deskew_table): a NULL pointer, n_poses
+ * outside 2 .. ICPMI_DESKEW_MAX_POSES, stamps not strictly increasing, a non-finite entry, a quaternion with | |q| - 1 | > 1e-3, ref_s
+ * outside [stamp_s[0], stamp_s[n_poses - 1]], time_unit_s not finite and > 0, round_s not finite and >= 0; a raised error flag (the
+ * flag is one word, written with an ordinary store of the constant 1: out4 is then unspecified, and the host-pointer variant does not
+ * copy it back).  n == 0: ICPMI_OK; n > 2^31 - 1: ICPMI_ERR_UNSUPPORTED.  A planar handle (icpmi_config::is_2d) takes planar motion
+ * only -- tz, qx and qy of every pose exactly 0, else ICPMI_ERR_INVALID_ARG -- and such a motion keeps z = 0 exactly: the third row
+ * and column of R are then exactly those of the identity.  Two calls give the same bits. */
+enum { ICPMI_DESKEW_MAX_POSES = 1024 };
+typedef struct icpmi_sweep_motion {
+    int32_t n_poses;        /* 2 .. ICPMI_DESKEW_MAX_POSES */
+    int32_t extrapolate;    /* 0: a point time outside [stamp_s[0], stamp_s[n-1]] fails the call (tf2's ExtrapolationException); 1: clamped to the span */
+    const double* stamp_s;  /* n_poses, strictly increasing, seconds relative to the scan's stamp */
+    const double* pose7;    /* n_poses x (tx ty tz qx qy qz qw); | |q| - 1 | <= 1e-3 */
+    double ref_s;           /* the time the output is expressed at, inside the span */
+    double time_unit_s;     /* seconds per unit of t_rel: 1e-9 for the bundled `t`, 1 for seconds; finite, > 0 */
+    double round_s;         /* > 0: point times are rounded to the nearest multiple (rint, ties to even) first -- the wrapper's deskewing_round_to_nanosecs; 0: none */
+} icpmi_sweep_motion;
+icpmi_status icpmi_deskew_table(const icpmi_sweep_motion* m, float* q4, float* p3, float* omega, float* inv_sin);
+icpmi_status icpmi_deskew(icpmi_handle h, const float* in4, int64_t n, const float* t_rel, const icpmi_sweep_motion* m,
+                          float* out4, const float* in_normals3, float* out_normals3);
+/* the same with in4 / t_rel / out4 / the normals as device pointers, on the handle's stream; out4 == d_in4 and d_out_normals3 ==
+ * d_in_normals3 are allowed (a thread reads its point before it writes it).  The call waits for the error flag before it returns.
+ * In place and followed by icpmi_register_prior_dev, a scan that is already in HBM is deskewed and registered without crossing PCIe. */
+icpmi_status icpmi_deskew_dev(icpmi_handle h, const float* d_in4, int64_t n, const float* d_t_rel, const icpmi_sweep_motion* m,
+                              float* d_out4, const float* d_in_normals3, float* d_out_normals3);
+
 /* `Map::unloadCells` binning (Map.cpp:206-209,232-235): ijk3[3 i + r] = floor(p_r / cell_size). */
 icpmi_status icpmi_bin_cells(icpmi_handle h, const float* pts4, int64_t n, float cell_size, int32_t* ijk3);
 

@@ -108,6 +108,14 @@ class CovSampInfo(C.Structure):
     _fields_ = [("center", C.c_double * 3), ("lnorm", C.c_double), ("eigval", C.c_double * 6), ("basis", C.c_double * 36)]
 
 
+class SweepMotion(C.Structure):
+    """icpmi_sweep_motion: the sensor's motion over one sweep as timed poses (tx ty tz qx qy qz qw), for icpmi_deskew*."""
+    _fields_ = [("n_poses", C.c_int32), ("extrapolate", C.c_int32), ("stamp_s", C.POINTER(C.c_double)), ("pose7", C.POINTER(C.c_double)),
+                ("ref_s", C.c_double), ("time_unit_s", C.c_double), ("round_s", C.c_double)]
+
+
+DESKEW_MAX_POSES = 1024
+
 MOP_POINT_DISTANCE, MOP_DYNAMIC_POINTS, MOP_VOXEL, MOP_SURFACE_NORMALS, MOP_CUT_SCALAR, MOP_OCTREE, MOP_MAX_DENSITY = range(7)
 
 
@@ -153,6 +161,9 @@ SYMBOLS = [
     ("icpmi_normal_space_sampling", C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, C.c_int32, C.c_float, _P, _P, _P]),
     ("icpmi_max_density_keep", C.c_int, [_P, _P, C.c_int64, C.c_float, C.c_int32, _P]),
     ("icpmi_sensor_model", C.c_int, [_P, _P, C.c_int64, _P, _P, _P, C.c_int32, _P, _P, _P, _P]),
+    ("icpmi_deskew_table", C.c_int, [C.POINTER(SweepMotion), _P, _P, _P, _P]),
+    ("icpmi_deskew", C.c_int, [_P, _P, C.c_int64, _P, C.POINTER(SweepMotion), _P, _P, _P]),
+    ("icpmi_deskew_dev", C.c_int, [_P, _P, C.c_int64, _P, C.POINTER(SweepMotion), _P, _P, _P]),
     ("icpmi_map_update_chain", C.c_int, [_P, _P, C.c_int64, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, _P, C.c_int64, _P, _P]),
     ("icpmi_map_update_chain_staged", C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, _P, C.c_int64, _P, _P]),
     ("icpmi_set_map_scalar", C.c_int, [_P, _P, C.c_int64]),

@@ -1277,6 +1277,31 @@ icpmi_status icpmi_sensor_model(icpmi_handle h, const float* in4, int64_t n, con
                             have_od ? obs_dir3_out : nullptr, noise ? noise_out : nullptr, shadow ? keep_out : nullptr);
 }
 
+icpmi_status icpmi_deskew_table(const icpmi_sweep_motion* m, float* q4, float* p3, float* omega, float* inv_sin)
+{
+    return deskew_table_host(m, q4, p3, omega, inv_sin, g_create_error); // (no handle: icpmi_last_error(NULL) has the message)
+}
+
+icpmi_status icpmi_deskew(icpmi_handle h, const float* in4, int64_t n, const float* t_rel, const icpmi_sweep_motion* m, float* out4,
+                          const float* in_normals3, float* out_normals3)
+{
+    CHECK_H(h);
+    if (n < 0 || (n > 0 && (!in4 || !t_rel || !out4 || (in_normals3 != nullptr) != (out_normals3 != nullptr)))) {
+        h->last_error = "deskew: bad arguments (in4, t_rel and out4 are needed; the normals come in and out together)"; return ICPMI_ERR_INVALID_ARG;
+    }
+    return ops_deskew(h, in4, n, t_rel, m, out4, in_normals3, out_normals3, false);
+}
+
+icpmi_status icpmi_deskew_dev(icpmi_handle h, const float* d_in4, int64_t n, const float* d_t_rel, const icpmi_sweep_motion* m, float* d_out4,
+                              const float* d_in_normals3, float* d_out_normals3)
+{
+    CHECK_H(h);
+    if (n < 0 || (n > 0 && (!d_in4 || !d_t_rel || !d_out4 || (d_in_normals3 != nullptr) != (d_out_normals3 != nullptr)))) {
+        h->last_error = "deskew_dev: bad arguments (d_in4, d_t_rel and d_out4 are needed; the normals come in and out together)"; return ICPMI_ERR_INVALID_ARG;
+    }
+    return ops_deskew(h, d_in4, n, d_t_rel, m, d_out4, d_in_normals3, d_out_normals3, true);
+}
+
 icpmi_status icpmi_bin_cells(icpmi_handle h, const float* pts4, int64_t n, float cell_size, int32_t* ijk3)
 {
     CHECK_H(h);

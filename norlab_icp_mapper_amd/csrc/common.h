@@ -1174,3 +1174,7 @@ icpmi_status ops_covariance_sampling(icpmi_ctx* c, const float* in4, int64_t n, 
                                      icpmi_covsamp_info* info_out);
 icpmi_status ops_normal_space_sampling(icpmi_ctx* c, const float* in4, int64_t n, const float* normals3, int64_t nb, unsigned seed, float eps,
                                        int32_t* order_out, int32_t* bucket_out);
+// deskew.hip: the table of icpmi_deskew_table (host, no device call), and icpmi_deskew (dev == false) / icpmi_deskew_dev (dev == true)
+icpmi_status deskew_table_host(const icpmi_sweep_motion* m, float* q4, float* p3, float* omega, float* inv_sin, std::string& err);
+icpmi_status ops_deskew(icpmi_ctx* c, const float* in4, int64_t n, const float* t_rel, const icpmi_sweep_motion* m, float* out4,
+                        const float* in_normals3, float* out_normals3, bool dev);

@@ -169,6 +169,59 @@ void Mapper::setDefaultMapperModule()
     map.addMapperModule(registrar.create("PointDistanceMapperModule", yaml::Load("{minDistNewPoint: 0.15}"), icp.handle()));
 }
 
+void deskewSweep(icpmi_handle ctx, DataPoints& cloud, const SweepMotion& motion, TimePoint stamp, const DeskewOptions& opts)
+{
+    const size_t n = cloud.getNbPoints();
+    const int64_t stampNs = (int64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(stamp.time_since_epoch()).count();
+    // the points' times as offsets from the stamp: the float descriptor, or else the int64 row of absolute nanoseconds
+    std::vector<float> tRel;
+    double unit = opts.timeUnit;
+    if (cloud.descriptorExists(opts.timeField)) {
+        const Descriptor& d = cloud.getDescriptorByName(opts.timeField);
+        if (d.span != 1) throw InvalidField("deskew: descriptor " + opts.timeField + " must have one row");
+        tRel = d.data;
+    } else if (cloud.timeExists(opts.timeField)) {
+        const TimeField& t = cloud.getTimeByName(opts.timeField);
+        if (t.span != 1) throw InvalidField("deskew: time " + opts.timeField + " must have one row");
+        tRel.resize(n);
+        for (size_t i = 0; i < n; ++i) tRel[i] = (float)(t.data[i] - stampNs);
+        unit = 1e-9;
+    } else {
+        throw InvalidField("deskew: the cloud has neither a descriptor nor a time row called " + opts.timeField);
+    }
+    if (motion.stampNs.size() != motion.pose.size()) throw InvalidParameter("deskew: the motion has " + std::to_string(motion.stampNs.size()) +
+                                                                            " stamps for " + std::to_string(motion.pose.size()) + " poses");
+    // the sign-continued table is built from this once per call: one call per scan (a second one for observationDirections)
+    std::vector<double> stampS(motion.stampNs.size()), pose7(7 * motion.pose.size());
+    for (size_t k = 0; k < stampS.size(); ++k) {
+        stampS[k] = 1e-9 * (double)(motion.stampNs[k] - stampNs);
+        std::copy(motion.pose[k].begin(), motion.pose[k].end(), pose7.begin() + 7 * k);
+    }
+    icpmi_sweep_motion m{};
+    m.n_poses = (int32_t)std::min<size_t>(stampS.size(), (size_t)ICPMI_DESKEW_MAX_POSES + 1);
+    m.extrapolate = opts.extrapolate ? 1 : 0;
+    m.stamp_s = stampS.data(); m.pose7 = pose7.data();
+    m.ref_s = 0.0; m.time_unit_s = unit; m.round_s = 1e-9 * (double)opts.roundToNs;
+    std::vector<float> out(4 * n);
+    const bool hasNormals = cloud.descriptorExists("normals"), hasObs = cloud.descriptorExists("observationDirections");
+    for (const char* name : {"normals", "observationDirections"})
+        if (cloud.descriptorExists(name) && cloud.getDescriptorByName(name).span != 3) throw InvalidField(std::string("deskew: descriptor ") + name + " must have three rows");
+    std::vector<float> rotated;
+    if (hasNormals || !hasObs) {
+        float* nrm = hasNormals ? cloud.getDescriptorByName("normals").data.data() : nullptr;
+        if (hasNormals) rotated.resize(3 * n);
+        GpuICPSequence::check(ctx, icpmi_deskew(ctx, cloud.features.data(), (int64_t)n, tRel.data(), &m, out.data(), nrm, hasNormals ? rotated.data() : nullptr));
+        if (hasNormals) cloud.getDescriptorByName("normals").data.swap(rotated);
+    }
+    if (hasObs) { // the same pass with that row in the normals slot
+        rotated.assign(3 * n, 0.f);
+        GpuICPSequence::check(ctx, icpmi_deskew(ctx, cloud.features.data(), (int64_t)n, tRel.data(), &m, out.data(),
+                                                cloud.getDescriptorByName("observationDirections").data.data(), rotated.data()));
+        cloud.getDescriptorByName("observationDirections").data.swap(rotated);
+    }
+    cloud.features.swap(out);
+}
+
 void Mapper::applyInputFilters(DataPoints& inputInSensorFrame)
 {
     inputFilters.apply(inputInSensorFrame, radiusFilter.get()); // radius filter first, then the `input:` chain

@@ -45,11 +45,34 @@ struct UpdatePolicy {
     }
 };
 
+// Sweep deskewing (include/icpmi.h: icpmi_deskew; the reference's wrapper does it in front of applyInputFilters, docs/UsingInRos.md:211-224).
+// The sensor's motion over the sweep: poses (tx ty tz qx qy qz qw) of the sensor in a fixed frame at stamps in nanoseconds on the clock
+// of the scans' TimePoint stamps.
+struct SweepMotion {
+    std::vector<int64_t> stampNs;
+    std::vector<std::array<double, 7>> pose;
+};
+struct DeskewOptions {
+    std::string timeField = "t";  // float descriptor of offsets from the scan's stamp, or else an int64 `times` row of absolute nanoseconds
+    double timeUnit = 1e-9;       // seconds per unit of the float descriptor (the bundled scans' `t`: nanoseconds)
+    int64_t roundToNs = 0;        // > 0: point times are rounded to multiples of it first (the wrapper's deskewing_round_to_nanosecs)
+    bool extrapolate = false;     // false: a point time outside the motion's stamps is an error (tf2's ExtrapolationException)
+};
+// every point of the cloud moved to where the sensor saw it from at `stamp`: features by T(stamp)^-1 T(point time), `normals` and
+// `observationDirections` by its rotation; every other descriptor and the `times` rows stay.  InvalidField when the cloud has neither
+// a float descriptor nor an int64 time row called opts.timeField.
+void deskewSweep(icpmi_handle ctx, DataPoints& inputInSensorFrame, const SweepMotion& motion, TimePoint stamp, const DeskewOptions& opts = DeskewOptions());
+
 class Mapper {
 public:
     Mapper(const std::string& configFilePath, bool is3D, bool isOnline, bool isMapping, bool saveMapCellsOnHardDrive, int device = 0);
     ~Mapper();
 
+    // the call a host places in front of applyInputFilters when the sensor moved during the sweep (no reference analogue in the library:
+    // the ROS wrapper does it, docs/UsingInRos.md:211-224)
+    void deskew(DataPoints& inputInSensorFrame, const SweepMotion& motion, TimePoint stamp, const DeskewOptions& opts = DeskewOptions()) {
+        deskewSweep(icp.handle(), inputInSensorFrame, motion, stamp, opts);
+    }
     void applyInputFilters(DataPoints& inputInSensorFrame);                                   // Mapper.cpp:187-191
     void processInput(const DataPoints& inputInSensorFrame, const Mat4& estimatedPose, const TimePoint& timeStamp); // :194-238
     DataPoints getMap() { return map.getGlobalPointCloud(); }

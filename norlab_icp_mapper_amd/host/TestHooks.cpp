@@ -1,6 +1,8 @@
 // TestHooks.cpp -- a C entry into the host shell for the Python parity tests (tests/test_host_filters.py): runs a YAML sequence
 // of DataPointsFilters (what `input:` / `post:` / the ICP chains' filter lists hold) on one cloud.  Not part of the reference
 // surface; the product never calls it.
+#include <algorithm>
+#include <cmath>
 #include <cstring>
 
 #include "IcpSequence.h"
@@ -141,6 +143,90 @@ int nim_test_parse_matcher(const char* yaml_matcher, int* knn, float* epsilon, f
         if (err && err_cap > 0) { std::strncpy(err, e.what(), (size_t)err_cap - 1); err[err_cap - 1] = 0; }
         return 1;
     }
+}
+
+// nim::deskewSweep (what Mapper::deskew runs on its own handle) on handle h.  The cloud: in4 + n_desc float descriptors (names / spans /
+// data, each span x n column-major) + one optional int64 row group (time_name / times, one row; may be NULL).  The motion: n_poses
+// stamps (ns) and poses (7 doubles each); stamp_ns the scan's stamp.  Back come out4, every descriptor in nim_test_filter_chain_descs'
+// layout and the time row (out_times, may be NULL).  Returns 0; 2 with the text in err for an InvalidField; 1 for any other exception.
+int nim_test_deskew(icpmi_handle h, const float* in4, int64_t n, int n_desc, const char* const* names, const int* spans, const float* const* data,
+                    const char* time_name, const int64_t* times, int n_poses, const int64_t* pose_stamp_ns, const double* pose7, int64_t stamp_ns,
+                    const char* time_field, double time_unit, int64_t round_to_ns, int extrapolate, float* out4, float* out_desc,
+                    int out_rows_cap, char* out_names, int out_names_cap, int64_t* out_times, char* err, int err_cap)
+{
+    const auto fail = [&](const std::exception& e, int rc) {
+        if (err && err_cap > 0) { std::strncpy(err, e.what(), (size_t)err_cap - 1); err[err_cap - 1] = 0; }
+        return rc;
+    };
+    try {
+        nim::DataPoints c((size_t)n);
+        std::memcpy(c.features.data(), in4, sizeof(float) * 4 * (size_t)n);
+        for (int d = 0; d < n_desc; ++d) c.addDescriptor(names[d], spans[d], std::vector<float>(data[d], data[d] + (size_t)spans[d] * n));
+        if (time_name && times) c.addTime(time_name, 1, std::vector<int64_t>(times, times + (size_t)n));
+        nim::SweepMotion motion;
+        for (int k = 0; k < n_poses; ++k) {
+            motion.stampNs.push_back(pose_stamp_ns[k]);
+            std::array<double, 7> p;
+            std::memcpy(p.data(), pose7 + 7 * (size_t)k, sizeof p);
+            motion.pose.push_back(p);
+        }
+        nim::DeskewOptions opts;
+        opts.timeField = time_field; opts.timeUnit = time_unit; opts.roundToNs = round_to_ns; opts.extrapolate = extrapolate != 0;
+        nim::deskewSweep(h, c, motion, nim::TimePoint{std::chrono::nanoseconds(stamp_ns)}, opts);
+        if (c.getNbPoints() != (size_t)n) throw std::logic_error("deskewing changed the number of points");
+        std::memcpy(out4, c.features.data(), sizeof(float) * 4 * (size_t)n);
+        std::string all;
+        size_t rows = 0;
+        for (const auto& d : c.descriptors) {
+            if (d.data.size() != (size_t)d.span * n) throw std::logic_error("deskewing left descriptor " + d.name + " out of step with the points");
+            if (rows + (size_t)d.span > (size_t)out_rows_cap) throw std::logic_error("more descriptor rows than the caller has room for");
+            std::memcpy(out_desc + rows * (size_t)n, d.data.data(), sizeof(float) * d.data.size());
+            rows += (size_t)d.span;
+            all += d.name + ":" + std::to_string(d.span) + ";";
+        }
+        if (all.size() + 1 > (size_t)out_names_cap) throw std::logic_error("descriptor names do not fit");
+        std::memcpy(out_names, all.c_str(), all.size() + 1);
+        if (time_name && out_times && c.timeExists(time_name)) std::memcpy(out_times, c.getTimeByName(time_name).data.data(), sizeof(int64_t) * (size_t)n);
+        return 0;
+    } catch (const nim::InvalidField& e) {
+        return fail(e, 2);
+    } catch (const std::exception& e) {
+        return fail(e, 1);
+    }
+}
+
+// The arithmetic of icpmi_deskew as one host thread runs it, float32, from the table icpmi_deskew_table builds: what a caller without the
+// device pass has to do, and the point of comparison of scripts/deskew_bench.py.  Times are taken as valid (no NaN, inside the stamps
+// or clamped to them); no handle, no GPU.  Returns 0, or 1 with the library's message in err.
+int nim_test_deskew_host_loop(const float* in4, int64_t n, const float* t_rel, const icpmi_sweep_motion* m, float* out4, char* err, int err_cap)
+{
+    const int K = m->n_poses;
+    std::vector<float> q(4 * (size_t)std::max(K, 2)), p(3 * q.size() / 4), om(q.size() / 4), is(q.size() / 4);
+    if (icpmi_deskew_table(m, q.data(), p.data(), om.data(), is.data()) != ICPMI_OK) {
+        if (err && err_cap > 0) { std::strncpy(err, icpmi_last_error(nullptr), (size_t)err_cap - 1); err[err_cap - 1] = 0; }
+        return 1;
+    }
+    const double* s = m->stamp_s;
+    for (int64_t i = 0; i < n; ++i) {
+        double tau = (double)t_rel[i] * m->time_unit_s;
+        if (m->round_s > 0.0) tau = std::rint(tau / m->round_s) * m->round_s;
+        tau = std::min(std::max(tau, s[0]), s[K - 1]);
+        int lo = 0, hi = K - 1;
+        while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (s[mid] <= tau) lo = mid; else hi = mid; }
+        const float u = (float)((tau - s[lo]) / (s[lo + 1] - s[lo])), um = 1.0f - u;
+        float w0 = um, w1 = u;
+        if (is[lo] != 0.0f) { w0 = std::sin(um * om[lo]) * is[lo]; w1 = std::sin(u * om[lo]) * is[lo]; }
+        const float* qa = &q[4 * (size_t)lo]; const float* pa = &p[3 * (size_t)lo];
+        const float qx = w0 * qa[0] + w1 * qa[4], qy = w0 * qa[1] + w1 * qa[5], qz = w0 * qa[2] + w1 * qa[6], qw = w0 * qa[3] + w1 * qa[7];
+        const float px = um * pa[0] + u * pa[3], py = um * pa[1] + u * pa[4], pz = um * pa[2] + u * pa[5];
+        const float xx = qx * qx, yy = qy * qy, zz = qz * qz, xy = qx * qy, xz = qx * qz, yz = qy * qz, wx = qw * qx, wy = qw * qy, wz = qw * qz;
+        const float* x = in4 + 4 * i; float* o = out4 + 4 * i;
+        o[0] = (((1.0f - 2.0f * (yy + zz)) * x[0] + (2.0f * (xy - wz)) * x[1]) + (2.0f * (xz + wy)) * x[2]) + px;
+        o[1] = (((2.0f * (xy + wz)) * x[0] + (1.0f - 2.0f * (xx + zz)) * x[1]) + (2.0f * (yz - wx)) * x[2]) + py;
+        o[2] = (((2.0f * (xz - wy)) * x[0] + (2.0f * (yz + wx)) * x[1]) + (1.0f - 2.0f * (xx + yy)) * x[2]) + pz;
+        o[3] = x[3];
+    }
+    return 0;
 }
 
 // GpuICPSequence on device 0: loadFromYamlNode(yaml_icp) (the `icp:` sub-tree), setMap(in4), then the resident map as the core holds it

@@ -660,6 +660,48 @@ class ICPSequence:
             out["keep"] = out["keep"].astype(bool)
         return out
 
+    @staticmethod
+    def _sweepMotion(stamps, poses, ref, unit, round, extrapolate):
+        """(icpmi_sweep_motion, the arrays it points into): stamps (K,) seconds from the scan's stamp, poses (K, 7) tx ty tz qx qy qz qw"""
+        s = np.ascontiguousarray(stamps, dtype=np.float64).ravel()
+        p = np.ascontiguousarray(poses, dtype=np.float64)
+        if p.ndim != 2 or p.shape[1] != 7 or p.shape[0] != s.shape[0]:
+            raise InvalidParameter(f"expected {s.shape[0]} poses as a (K, 7) array (tx ty tz qx qy qz qw), got {p.shape}")
+        m = _capi.SweepMotion(n_poses=s.shape[0], extrapolate=1 if extrapolate else 0, stamp_s=s.ctypes.data_as(C.POINTER(C.c_double)),
+                              pose7=p.ctypes.data_as(C.POINTER(C.c_double)), ref_s=float(ref), time_unit_s=float(unit), round_s=float(round))
+        return m, (s, p)
+
+    def deskew(self, points, t_rel, stamps, poses, ref=0.0, unit=1e-9, round=0.0, extrapolate=False, normals=None):
+        """icpmi_deskew: motion compensation of one sweep.  points (N, 4); t_rel (N,) the points' times in units of `unit` seconds from
+        the scan's stamp; stamps (K,) seconds from the scan's stamp and poses (K, 7) (tx ty tz qx qy qz qw) the sensor's motion; the
+        output is expressed at time `ref`.  round > 0 rounds the point times to multiples of it (seconds) first; extrapolate clamps
+        times outside the table instead of failing.  Returns the deskewed cloud, or (cloud, normals) when normals (N, 3) are given."""
+        c = _f32c(points, 4)
+        n = c.shape[0]
+        t = np.ascontiguousarray(t_rel, dtype=np.float32).ravel()
+        if t.shape[0] != n:
+            raise InvalidParameter("t_rel / cloud size mismatch")
+        m, keep = self._sweepMotion(stamps, poses, ref, unit, round, extrapolate)
+        out = np.empty_like(c)
+        nin = nout = outn = None
+        if normals is not None:
+            normals = _f32c(normals, 3)
+            if normals.shape[0] != n:
+                raise InvalidParameter("normals / cloud size mismatch")
+            outn = np.empty_like(normals)
+            nin, nout = normals.ctypes.data, outn.ctypes.data
+        self._check(self._lib.icpmi_deskew(self._h, c.ctypes.data, n, t.ctypes.data, C.byref(m), out.ctypes.data, nin, nout))
+        return (out, outn) if normals is not None else out
+
+    def deskewDev(self, d_points_ptr, n, d_t_rel_ptr, stamps, poses, ref=0.0, unit=1e-9, round=0.0, extrapolate=False, d_out_ptr=None,
+                  d_normals_ptr=None, d_normals_out_ptr=None):
+        """icpmi_deskew_dev: the same on device pointers, on the handle's stream; in place unless d_out_ptr / d_normals_out_ptr are given."""
+        m, keep = self._sweepMotion(stamps, poses, ref, unit, round, extrapolate)
+        if d_normals_ptr is not None and d_normals_out_ptr is None:
+            d_normals_out_ptr = d_normals_ptr
+        self._check(self._lib.icpmi_deskew_dev(self._h, d_points_ptr, int(n), d_t_rel_ptr, C.byref(m), d_points_ptr if d_out_ptr is None else d_out_ptr,
+                                               d_normals_ptr, d_normals_out_ptr))
+
     def normalSpaceSampling(self, cloud, normals, nb_sample=5000, seed=1, epsilon=0.09817, with_buckets=False):
         """NormalSpaceDataPointsFilter{nbSample, seed, epsilon} (the formulation of icpmi_normal_space_sampling, as recalled): cloud
         (N, 4), normals (N, 3) or None.  Returns the kept indices in ascending order (int32), or (order, buckets) with buckets (N,)
