@@ -783,6 +783,63 @@ icpmi_status icpmi_debug_last_sums(icpmi_handle h, double sums[32], float limits
  * registration yet, one that failed, a batch (icpmi_register_batch_dev), or any other call that reused the matcher's buffers or changed
  * the map after it -- the same rule as icpmi_debug_last_matches. */
 icpmi_status icpmi_get_covariance(icpmi_handle h, float cov[36]);
+
+/* `errorMinimizer->getResidualError(filteredReading, filteredReference, outlierWeights, matches)` under a GIVEN pose: how well a reading
+ * fits the handle's map (upstream's formulation as recalled, not checked against upstream's source).  One matcher pass, one pass of the chain's
+ * outlier filters and one reduction, all on the device; a call of its own, no registration needed before it and none changed by it.
+ *   1. every reading point is moved by T and matched against the map with the chain's matcher (knn, maxDist or the armed maxDistField row,
+ *      epsilon / epsilon_approx): the search the first iteration of icpmi_register would run from T.
+ *   2. the chain's outlier filters weigh those matches.  An ERROR ELEMENT is a pair whose match is filled and whose weight is != 0
+ *      (upstream's getMatchedPoints).  A soft weight (GenericDescriptor, Robust) counts as one pair like any other: the weight decides
+ *      whether a pair is in, it does not scale the residual.
+ *   3. per pair, in float32, p = the moved reading point, q = the matched map point, n = its normal, d = p - q:
+ *        point-to-point:  r = sqrtf(d2), d2 the matcher's squared distance of the pair (upstream sums the norms of the deltas)
+ *        point-to-plane:  r = |dx nx + dy ny + dz nz| (plain multiplies and adds in that order, no fused multiply-add);
+ *                         force_2d / is_2d: the x and y terms only (upstream's forcedDim)
+ *   4. sum_abs = sum of r over the error elements, in double: getResidualError().  The same reduction returns sum_sq = sum r^2,
+ *      max_abs = max r, pairs = the number of error elements P, weight_sum = sum w and weighted_point_used_ratio = sum w / (knn n):
+ *      getOverlap() under the evaluated pose.  trimmed_limit as icpmi_stats.  kind = what was computed (1 or 2).
+ *   5. P == 0: ICPMI_ERR_NO_POINT_TO_MINIMIZE (upstream's ConvergenceError); a Trimmed / Median filter that finds no filled match:
+ *      ICPMI_ERR_NO_OUTLIER_TO_FILTER, as in a registration.
+ * The sums run per workgroup and then in a fixed order, without atomics: two identical calls give the same bits.
+ * scan4 / T mean what they mean for icpmi_register: the reading is already moved by the prior, T (column-major, NULL = identity) is a
+ * correction in the map frame -- icpmi_residual_error(scan, T_out of icpmi_register(scan)) scores the registration just made.  The matcher
+ * works in the centred frame (the map minus its mean mu): it moves p - mu by [R | t + R mu - mu], that translation formed in double and
+ * rounded to float.  |1 - det R| > 1e-3: ICPMI_ERR_INVALID_ARG, as icpmi_transform.
+ * kind: ICPMI_RES_CHAIN takes it from the handle's minimizer (IdentityErrorMinimizer: ICPMI_ERR_UNSUPPORTED -- upstream's base class has no
+ * residual); ICPMI_RES_POINT_TO_PLANE without map normals: ICPMI_ERR_MISSING_NORMALS.  No map: ICPMI_ERR_INVALID_ARG.
+ * Every outlier filter of the chain is served.  SurfaceNormalOutlierFilter needs scan_normals3 (rotated by T, as the loop does) and map
+ * normals, else ICPMI_ERR_MISSING_NORMALS.  The rows armed by icpmi_set_reading_scalar / icpmi_set_reading_max_dist /
+ * icpmi_set_reading_sensor_noise are consumed as a registration consumes them (the noise row is not read).  A filter whose answer is state
+ * of a registration's iterations -- RobustOutlierFilter with scaleEstimator berg, or with nbIterationForScale > 0 -- is
+ * ICPMI_ERR_UNSUPPORTED: it is not served with a guess.
+ * _dev: the reading (and its normals) in HBM.  _staged: the scan icpmi_register_prior* left in HBM (the stage icpmi_map_update_staged
+ * consumes; no upload), ICPMI_ERR_INVALID_ARG without one.
+ * Afterwards icpmi_get_covariance still returns the covariance of the registration before the call; icpmi_debug_last_matches and
+ * icpmi_debug_last_sums have nothing to read (the matcher's buffers were reused), as after icpmi_knn. */
+typedef struct {
+    double  sum_abs;   /* getResidualError() */
+    double  sum_sq;
+    float   max_abs;
+    float   weighted_point_used_ratio;
+    double  weight_sum;
+    int64_t pairs;
+    float   trimmed_limit;   /* as icpmi_stats */
+    int32_t kind;            /* what was computed: 1 or 2 */
+    int32_t reserved[4];
+} icpmi_residual;
+
+typedef enum {
+    ICPMI_RES_CHAIN = 0,
+    ICPMI_RES_POINT_TO_POINT = 1,
+    ICPMI_RES_POINT_TO_PLANE = 2
+} icpmi_residual_kind;
+
+icpmi_status icpmi_residual_error(icpmi_handle h, const float* scan4, int64_t n, const float* scan_normals3, const float T[16],
+                                  int32_t kind, icpmi_residual* out);
+icpmi_status icpmi_residual_error_dev(icpmi_handle h, const float* d_scan4, int64_t n, const float* d_scan_normals3, const float T[16],
+                                      int32_t kind, icpmi_residual* out);
+icpmi_status icpmi_residual_error_staged(icpmi_handle h, const float T[16], int32_t kind, icpmi_residual* out);
 /* Test seam: the n-th value (n >= 1) of the std::minstd_rand stream as the DEVICE computes it by skip-ahead (csrc/ssn.hip, behind
  * SamplingSurfaceNormalDataPointsFilter -- PM::ICPSequence::setDefault(), Mapper.cpp:74-78).  [rand.predef]: seed 1, n = 10 000 -> 399268537. */
 icpmi_status icpmi_debug_minstd_nth(icpmi_handle h, uint32_t seed, uint32_t n, uint32_t* out);

@@ -85,6 +85,24 @@ class Stats(C.Structure):
     ]
 
 
+class Residual(C.Structure):
+    """icpmi_residual: what icpmi_residual_error* returns (sum_abs = getResidualError())."""
+    _fields_ = [
+        ("sum_abs", C.c_double),
+        ("sum_sq", C.c_double),
+        ("max_abs", C.c_float),
+        ("weighted_point_used_ratio", C.c_float),
+        ("weight_sum", C.c_double),
+        ("pairs", C.c_int64),
+        ("trimmed_limit", C.c_float),
+        ("kind", C.c_int32),
+        ("reserved", C.c_int32 * 4),
+    ]
+
+
+RES_CHAIN, RES_POINT_TO_POINT, RES_POINT_TO_PLANE = 0, 1, 2
+
+
 class MapOp(C.Structure):
     """icpmi_map_op: one step of the resident map-update chain."""
     _fields_ = [("type", C.c_int32), ("i", C.c_int32), ("f", C.c_float * 7)]
@@ -196,6 +214,9 @@ SYMBOLS = [
     ("icpmi_debug_keep_sums", C.c_int, [_P, C.c_int32]),
     ("icpmi_debug_last_sums", C.c_int, [_P, C.POINTER(C.c_double), _F, _F, _F]),
     ("icpmi_get_covariance", C.c_int, [_P, _F]),
+    ("icpmi_residual_error", C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int32, C.POINTER(Residual)]),
+    ("icpmi_residual_error_dev", C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int32, C.POINTER(Residual)]),
+    ("icpmi_residual_error_staged", C.c_int, [_P, _P, C.c_int32, C.POINTER(Residual)]),
     ("icpmi_debug_minstd_nth", C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]),
     ("icpmi_get_grid_info", C.c_int, [_P, _F, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
 ]

@@ -380,7 +380,7 @@ icpmi_status icpmi_get_covariance(icpmi_handle h, float cov[36])
     CHECK_H(h);
     if (!cov) { h->last_error = "get_covariance: cov is null"; return ICPMI_ERR_INVALID_ARG; }
     if (!h->cfg.covariance) { h->last_error = "get_covariance: the chain does not ask for a covariance (icpmi_config::covariance)"; return ICPMI_ERR_UNSUPPORTED; }
-    if (!h->cov_ready || h->last_match_n == 0) {
+    if (!h->cov_ready || (h->last_match_n == 0 && !h->cov_kept)) {
         h->last_error = "get_covariance: no covariance of a single registration on this handle (none ran, it failed, or a batch / another call came after it)";
         return ICPMI_ERR_UNSUPPORTED;
     }
@@ -714,6 +714,131 @@ icpmi_status icpmi_register(icpmi_handle h, const float* scan4, int64_t n, const
         d_scan = scan4; // no map: never dereferenced
     }
     return register_impl(h, d_scan, n, d_n3, 0, T_out, stats);
+}
+
+// icpmi_residual_error*: the checks and the chain set-up of register_impl, then one matcher pass under T and the reduction (loop_residual)
+static icpmi_status residual_impl(icpmi_handle h, const char* who, const float* d_scan4, int64_t n, const float* d_n3, const float T[16], int32_t kind,
+                                  icpmi_residual* out)
+{
+    // the one-shot reading rows belong to THIS call whatever becomes of it, as in register_impl
+    const int64_t have_scalar_n = h->read_scalar_n, have_r2_n = h->read_r2_n;
+    h->read_scalar_n = 0; h->read_noise_n = 0; h->read_r2_n = 0;
+    if (!out) { h->last_error = std::string(who) + ": out is null"; return ICPMI_ERR_INVALID_ARG; }
+    memset(out, 0, sizeof *out);
+    out->trimmed_limit = -1.f;
+    if (n < 0 || (n > 0 && !d_scan4) || kind < ICPMI_RES_CHAIN || kind > ICPMI_RES_POINT_TO_PLANE) {
+        h->last_error = std::string(who) + ": bad arguments"; return ICPMI_ERR_INVALID_ARG;
+    }
+    if (h->m <= 0) { h->last_error = std::string(who) + ": no map"; return ICPMI_ERR_INVALID_ARG; }
+    if (n > 0x7fffffff / ICPMI_MAX_K) { h->last_error = std::string(who) + ": too many points"; return ICPMI_ERR_UNSUPPORTED; }
+    float Tid[16];
+    identity16(Tid);
+    if (!T) T = Tid;
+    { const icpmi_status rs = check_rigid(h, T); if (rs != ICPMI_OK) return rs; }
+    if (kind == ICPMI_RES_CHAIN) {
+        if (h->cfg.minimizer != ICPMI_MIN_POINT_TO_POINT && h->cfg.minimizer != ICPMI_MIN_POINT_TO_PLANE) {
+            h->last_error = std::string(who) + ": IdentityErrorMinimizer has no residual (name ICPMI_RES_POINT_TO_POINT or ICPMI_RES_POINT_TO_PLANE)";
+            return ICPMI_ERR_UNSUPPORTED;
+        }
+        kind = h->cfg.minimizer == ICPMI_MIN_POINT_TO_POINT ? ICPMI_RES_POINT_TO_POINT : ICPMI_RES_POINT_TO_PLANE;
+    }
+    if (kind == ICPMI_RES_POINT_TO_PLANE && !h->has_normals) {
+        h->last_error = "InvalidField: the point-to-plane residual needs the descriptor 'normals' on the map";
+        return ICPMI_ERR_MISSING_NORMALS;
+    }
+    bool needs_rn = false;
+    for (int f = 0; f < h->cfg.n_outlier; ++f) {
+        const icpmi_outlier& o = h->cfg.outlier[f];
+        needs_rn |= o.type == ICPMI_OUT_SURFACENORMAL;
+        if (o.type == ICPMI_OUT_ROBUST && (((o.iparam >> 4) & 15) == ICPMI_SCALE_BERG || (int)o.param2 > 0)) {
+            h->last_error = std::string(who) + ": RobustOutlierFilter with scaleEstimator berg or nbIterationForScale > 0 keeps its scale from one "
+                            "iteration of a registration to the next: no single pass can answer for it";
+            return ICPMI_ERR_UNSUPPORTED;
+        }
+    }
+    if (needs_rn && (!d_n3 || !h->has_normals)) {
+        h->last_error = "InvalidField: SurfaceNormalOutlierFilter needs 'normals' on both reading and map";
+        return ICPMI_ERR_MISSING_NORMALS;
+    }
+    { const icpmi_status es = check_ext_filters(h); if (es != ICPMI_OK) return es; }
+    LoopCfg lc = make_loop_cfg(h, 1);
+    {   // GenericDescriptorOutlierFilter{source: reading}: the row handed over for THIS reading (one shot)
+        bool wants = false;
+        for (int f = 0; f < h->cfg.n_outlier; ++f) wants |= h->cfg.outlier[f].type == ICPMI_OUT_GENERICDESCRIPTOR && (h->cfg.outlier[f].iparam & ICPMI_GEN_SOURCE_READING);
+        if (wants && n > 0 && have_scalar_n != n) {
+            h->last_error = "InvalidField: GenericDescriptorOutlierFilter{source: reading} needs the reading's descriptor (icpmi_set_reading_scalar, one row per point)";
+            return ICPMI_ERR_INVALID_ARG;
+        }
+        lc.read_scalar = wants ? h->d_read_scalar : nullptr;
+    }
+    const float* d_r2row = nullptr;
+    if (h->cfg.var_dist && n > 0) { // KDTreeVarDistMatcher: the radii handed over for THIS reading (one shot), as in register_impl
+        if (have_r2_n != n) {
+            h->last_error = "InvalidField: KDTreeVarDistMatcher needs the reading's maxDistField descriptor (icpmi_set_reading_max_dist, one radius per point)";
+            return ICPMI_ERR_INVALID_ARG;
+        }
+        if (!(h->read_r2_max > 0.f)) {
+            h->last_error = "InvalidParameter: KDTreeVarDistMatcher: the largest radius of the row must be > 0 (as maxDist)";
+            return ICPMI_ERR_INVALID_ARG;
+        }
+        set_search_bound(h, lc, h->read_r2_max);
+        d_r2row = h->d_read_r2;
+    }
+    lc.sensor_noise = 0;
+    lc.has_read_normals = needs_rn ? 1 : 0;
+    if (n == 0) { // upstream: Trimmed / Median throw "no outlier to filter", otherwise "no point to minimize"
+        bool quant = false;
+        for (int f = 0; f < lc.n_out; ++f) quant |= lc.out_type[f] == ICPMI_OUT_TRIMMEDDIST || lc.out_type[f] == ICPMI_OUT_MEDIANDIST || lc.out_type[f] == ICPMI_OUT_VARTRIMMEDDIST;
+        h->last_error = quant ? "ConvergenceError: no outlier to filter" : "ConvergenceError: ErrorMinimizer: no point to minimize";
+        return quant ? ICPMI_ERR_NO_OUTLIER_TO_FILTER : ICPMI_ERR_NO_POINT_TO_MINIMIZE;
+    }
+    // centring, the padded normals and the tile order of the reading, as a registration's head prepares them
+    { const icpmi_status ps = loop_prepare_reading(h, (const float4*)d_scan4, n, needs_rn ? d_n3 : nullptr); if (ps != ICPMI_OK) return ps; }
+    // the pose in the centred frame: [R | t + R mu - mu]
+    float Tc[16];
+    memcpy(Tc, T, sizeof Tc);
+    for (int r = 0; r < 3; ++r)
+        Tc[12 + r] = (float)(((double)T[12 + r] + (((double)T[r] * (double)h->mean[0] + (double)T[4 + r] * (double)h->mean[1]) + (double)T[8 + r] * (double)h->mean[2])) -
+                             (double)h->mean[r]);
+    Tc[3] = Tc[7] = Tc[11] = 0.f; Tc[15] = 1.f;
+    return loop_residual(h, n, lc, Tc, kind, (h->cfg.force_2d != 0 || h->cfg.is_2d != 0) ? 1 : 0, d_r2row, out);
+}
+
+icpmi_status icpmi_residual_error_dev(icpmi_handle h, const float* d_scan4, int64_t n, const float* d_scan_normals3, const float T[16],
+                                      int32_t kind, icpmi_residual* out)
+{
+    CHECK_H(h);
+    return residual_impl(h, "residual_error_dev", d_scan4, n, d_scan_normals3, T, kind, out);
+}
+
+icpmi_status icpmi_residual_error(icpmi_handle h, const float* scan4, int64_t n, const float* scan_normals3, const float T[16],
+                                  int32_t kind, icpmi_residual* out)
+{
+    CHECK_H(h);
+    if (n < 0 || (n > 0 && !scan4)) { h->last_error = "residual_error: bad arguments"; return ICPMI_ERR_INVALID_ARG; }
+    const float* d_scan = scan4; // (n == 0 or no map: never dereferenced)
+    const float* d_n3 = nullptr;
+    if (n > 0 && h->m > 0) {
+        // staged through the operator scratch: the handle's stage buffers stay what icpmi_register_prior left them
+        float4* d_in = scratch_get<float4>(h, 8, (size_t)n);
+        if (!d_in) return ICPMI_ERR_HIP;
+        HIP_TRY(h, hipMemcpyAsync(d_in, scan4, (size_t)n * sizeof(float4), hipMemcpyHostToDevice, h->stream));
+        d_scan = (const float*)d_in;
+        if (scan_normals3) {
+            float* d_n = scratch_get<float>(h, 9, (size_t)n * 3);
+            if (!d_n) return ICPMI_ERR_HIP;
+            HIP_TRY(h, hipMemcpyAsync(d_n, scan_normals3, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, h->stream));
+            d_n3 = d_n;
+        }
+    }
+    return residual_impl(h, "residual_error", d_scan, n, d_n3, T, kind, out);
+}
+
+icpmi_status icpmi_residual_error_staged(icpmi_handle h, const float T[16], int32_t kind, icpmi_residual* out)
+{
+    CHECK_H(h);
+    if (h->scan_map_n <= 0) { h->last_error = "residual_error_staged: no scan staged by icpmi_register_prior"; return ICPMI_ERR_INVALID_ARG; }
+    return residual_impl(h, "residual_error_staged", (const float*)h->d_scan_map.get(), h->scan_map_n, nullptr, T, kind, out);
 }
 
 icpmi_status icpmi_transform(icpmi_handle h, const float T[16], const float* in4, int64_t n, float* out4, const float* in_normals3,

@@ -612,6 +612,7 @@ struct icpmi_ctx {
     // icpmi_get_covariance (loop.hip: loop_covariance): per-workgroup partials of H / S, then the 36 floats of Cov; cov_ready = computed
     // for the last single registration (read only while last_match_n says its pairs are still the ones in the buffers)
     DevArr<double> d_cov; bool cov_ready = false;
+    bool cov_kept = false; // an icpmi_residual_error* call reused the matcher's buffers behind that registration: d_cov still holds its covariance
     // icpmi_debug_keep_sums: 32 doubles the solve kernel of a single registration writes its pair sums to (null: not kept, the default --
     // the same launches with sums_out == nullptr); read by icpmi_debug_last_sums under the condition of icpmi_debug_last_matches
     DevArr<double> d_keep_sums;
@@ -728,7 +729,7 @@ static inline void drop_loop_graphs(icpmi_ctx* c)
     if (c->graphs.seg[0].exec) c->seg_wasted = c->graphs.seg[0].uses <= 1 ? c->seg_wasted + 1 : 0;
     ++c->map_epoch;
     c->graphs.reset();
-    c->last_match_n = 0;
+    c->last_match_n = 0; c->cov_kept = false;
 }
 
 // Small device -> host read through the pinned page: a copy into pageable memory is staged and blocks for tens of
@@ -1073,6 +1074,9 @@ icpmi_status loop_run_batch(icpmi_ctx* c, int batch, const float* const* d_scans
                             float* T_out, icpmi_stats* stats, icpmi_status* status);
 icpmi_status loop_single_step(icpmi_ctx* c, int64_t n, const LoopCfg& lc, const float* T_iter_host, float T_step[16],
                               double sums[32], icpmi_stats* stats);
+// getResidualError() of the centred reading in c->d_reading under the centred-frame pose T (host, column-major); kind 1 / 2
+icpmi_status loop_residual(icpmi_ctx* c, int64_t n, const LoopCfg& lc, const float T[16], int kind, int planar, const float* d_r2row,
+                           icpmi_residual* out);
 icpmi_status loop_outlier_weights(icpmi_ctx* c, const LoopCfg& lc, const float* d2, const int32_t* ids, int k, int64_t n,
                                   const float* read_normals3, float* weights, float* limit_out);
 LoopCfg make_loop_cfg(const icpmi_ctx* c, int fixed_iterations);

@@ -1656,7 +1656,7 @@ icpmi_status loop_run(icpmi_ctx* c, const float4* d_scan, const float* d_normals
                       bool fixed, float T_out[16], icpmi_stats* stats)
 {
     LoopCfg lc = lc_in;
-    c->last_match_n = 0; c->cov_ready = false;
+    c->last_match_n = 0; c->cov_ready = false; c->cov_kept = false;
     // all allocations up front: none may happen while the stream is capturing
     if (ensure_loop_buffers(c, n, lc.k) != ICPMI_OK) return ICPMI_ERR_HIP;
     if (chain_has_vartrimmed(lc)) { VtBuffers vb; if (vt_buffers(c, n * lc.k, &vb) != ICPMI_OK) return ICPMI_ERR_HIP; }
@@ -1907,7 +1907,7 @@ static void batch_result(icpmi_ctx* c, const LoopCfg& lc, const IcpState* hs, in
 icpmi_status loop_run_batch(icpmi_ctx* c, int B, const float* const* d_scans4, const int64_t* nn, const LoopCfg& lc, bool fixed, float* T_out,
                             icpmi_stats* stats, icpmi_status* status)
 {
-    c->last_match_n = 0; // (icpmi_debug_last_matches serves single registrations only)
+    c->last_match_n = 0; c->cov_kept = false; // (icpmi_debug_last_matches serves single registrations only)
     int64_t nmax = 0;
     for (int b = 0; b < B; ++b) nmax = nn[b] > nmax ? nn[b] : nmax;
     const int64_t NS = (nmax + 63) / 64 * 64; // slice stride of the per-query arrays
@@ -2049,10 +2049,181 @@ icpmi_status loop_single_step(icpmi_ctx* c, int64_t n, const LoopCfg& lc, const 
     return ICPMI_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// ErrorMinimizer::getResidualError() under a given pose (include/icpmi.h: icpmi_residual_error has the formulation).  The state is set up
+// as loop_single_step sets it up, the matcher's launch and the selection are the ones of a registration's first iteration; in place of the
+// pair sums and the solve, two launches outside any graph: pass 1 walks the n * k slots and every workgroup writes five partials (sum r,
+// sum r^2, sum w, pairs in double; max r), pass 2 (one workgroup) adds them in a fixed order.  No atomics: the same bits on every call.
+// ---------------------------------------------------------------------------------------------
+#define ICPMI_RES_NB 256   // pass-1 workgroups, one per CU (fixed, as ICPMI_COV_NB: the summation order depends on the slot count alone)
+#define ICPMI_RES_NV 5     // [0] sum r, [1] sum r^2, [2] sum w, [3] pairs, [4] max r
+#define ICPMI_RES_CH 8     // pass 2: eight threads per value, each over every eighth workgroup partial
+
+struct ResBlock { double sum_abs, sum_sq, weight_sum; long long pairs; float max_abs, limit; int error, pad; };
+
+// fused_slot >= 0: the chain's one quantile filter went through the fused selection, whose last level the pair-sum kernel of an iteration
+// resolves -- here every workgroup does (the same lookup, the same limit)
+__global__ __launch_bounds__(256) void res_pairs_kernel(const float4* __restrict__ reading, const int* __restrict__ qindex, int n, LoopCfg lc,
+                                                        int kind, int planar, IcpState* __restrict__ st, const float4* __restrict__ map,
+                                                        const float4* __restrict__ ref_normals, const float4* __restrict__ read_normals,
+                                                        const float* __restrict__ ref_scalar, const int* __restrict__ sidx,
+                                                        const float* __restrict__ d2a, const float4* __restrict__ match_pt,
+                                                        const unsigned* __restrict__ hists, int fused_slot, int is_median, float factor,
+                                                        double* __restrict__ partial)
+{
+    __shared__ unsigned shsel[16];
+    __shared__ double sh[4][ICPMI_RES_NV];
+    float fused_limit = 0.f;
+    if (fused_slot >= 0) {
+        const unsigned cv = hists[ICPMI_S2_C1 + threadIdx.x];
+        unsigned bin, rem, total;
+        block_find_rank_2tier<1>(cv, hists + ICPMI_S2_F1, false, 0.f, st->sel_rank_l[0], shsel, bin, rem, total);
+        const float q = __uint_as_float((st->sel_prefix_l[0] << 16) | bin);
+        fused_limit = is_median ? factor * q : q;
+        if (blockIdx.x == 0 && threadIdx.x == 0) st->limits[fused_slot] = fused_limit;
+    }
+    const float* T = st->T_iter;
+    const int64_t total_e = (int64_t)n * lc.k;
+    double sr = 0.0, sq = 0.0, sw = 0.0, cnt = 0.0;
+    float mx = 0.f;
+    const bool live = st->error == 0; // (a selection that found nothing to filter: the partials are written, all zero)
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; live && e < total_e; e += (int64_t)gridDim.x * 256) {
+        const float d2 = d2a[e];
+        if (d2 == INFINITY) continue;
+        const int qi = (int)(e / lc.k);
+        const int oi = qindex ? qindex[qi] : qi;
+        const int s = sidx[e];
+        const float4 r4 = reading[qi];
+        const float3 p = xf_point(T, r4.x, r4.y, r4.z, r4.w);
+        const float4 q = match_pt ? match_pt[e] : map[s];
+        const float dx = p.x - q.x, dy = p.y - q.y, dz = p.z - q.z;
+        float dot = 0.f, dot2 = 0.f;
+        if (ref_normals) {
+            const float4 nm = ref_normals[s];
+            dot = dx * nm.x + dy * nm.y + dz * nm.z;
+            dot2 = dx * nm.x + dy * nm.y; // forcedDim = 2
+        }
+        float w;
+        if (lc.ext) w = match_weight<true>(lc, st, d2, T, read_normals, oi, ref_normals, s, fused_slot, fused_limit, ref_scalar, __float_as_int(q.w), dot * dot);
+        else w = match_weight(lc, st, d2, T, read_normals, oi, ref_normals, s, fused_slot, fused_limit);
+        if (w == 0.f) continue;
+        const float r = kind == ICPMI_RES_POINT_TO_POINT ? sqrtf(d2) : fabsf(planar ? dot2 : dot);
+        sr += (double)r; sq += (double)r * (double)r; sw += (double)w; cnt += 1.0;
+        mx = fmaxf(mx, r);
+    }
+    // wave butterfly, then the four waves in order: a fixed pattern, the same sums on every call
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    double acc[ICPMI_RES_NV] = {sr, sq, sw, cnt, (double)mx};
+#pragma unroll
+    for (int i = 0; i < ICPMI_RES_NV; ++i) {
+        double v = acc[i];
+#pragma unroll
+        for (int m = 32; m > 0; m >>= 1) {
+            const double o = __shfl_xor(v, m, 64);
+            v = i == 4 ? fmax(v, o) : v + o;
+        }
+        if (lane == 0) sh[wv][i] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < ICPMI_RES_NV) {
+        const int i = threadIdx.x;
+        partial[(size_t)blockIdx.x * ICPMI_RES_NV + i] = i == 4 ? fmax(fmax(fmax(sh[0][i], sh[1][i]), sh[2][i]), sh[3][i])
+                                                                 : ((sh[0][i] + sh[1][i]) + sh[2][i]) + sh[3][i];
+    }
+}
+
+__global__ __launch_bounds__(64) void res_finish_kernel(const double* __restrict__ partial, const IcpState* __restrict__ st, int limit_slot,
+                                                        ResBlock* __restrict__ out)
+{
+    __shared__ double part[ICPMI_RES_NV][ICPMI_RES_CH];
+    if (threadIdx.x < ICPMI_RES_NV * ICPMI_RES_CH) {
+        // every load issued before the first add (cov_solve_kernel)
+        constexpr int PER = ICPMI_RES_NB / ICPMI_RES_CH;
+        const int v = threadIdx.x / ICPMI_RES_CH, ch = threadIdx.x % ICPMI_RES_CH;
+        double x[PER];
+#pragma unroll
+        for (int i = 0; i < PER; ++i) x[i] = partial[(size_t)(ch + ICPMI_RES_CH * i) * ICPMI_RES_NV + v];
+        double acc = 0.0;
+#pragma unroll
+        for (int i = 0; i < PER; ++i) acc = v == 4 ? fmax(acc, x[i]) : acc + x[i];
+        part[v][ch] = acc;
+    }
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    double tot[ICPMI_RES_NV];
+#pragma unroll
+    for (int v = 0; v < ICPMI_RES_NV; ++v) {
+        double acc = 0.0;
+#pragma unroll
+        for (int ch = 0; ch < ICPMI_RES_CH; ++ch) acc = v == 4 ? fmax(acc, part[v][ch]) : acc + part[v][ch];
+        tot[v] = acc;
+    }
+    out->sum_abs = tot[0]; out->sum_sq = tot[1]; out->weight_sum = tot[2];
+    out->pairs = (long long)tot[3];
+    out->max_abs = (float)tot[4];
+    out->limit = limit_slot >= 0 ? st->limits[limit_slot] : -1.f;
+    out->error = st->error; out->pad = 0;
+}
+static_assert(ICPMI_RES_NB % ICPMI_RES_CH == 0 && ICPMI_RES_NV * ICPMI_RES_CH <= 64, "pass 2 of the residual: one wave, whole chunks");
+
+// the centred reading is in c->d_reading (loop_prepare_reading); T_host = the pose in the centred frame (column-major), kind 1 or 2
+icpmi_status loop_residual(icpmi_ctx* c, int64_t n, const LoopCfg& lc, const float T_host[16], int kind, int planar, const float* d_r2row,
+                           icpmi_residual* out)
+{
+    // the covariance of the registration before this call lives in d_cov, which nothing here touches: it stays readable
+    const bool cov_keep = c->cov_ready && (c->last_match_n != 0 || c->cov_kept);
+    if (ensure_loop_buffers(c, n, lc.k) != ICPMI_OK) return ICPMI_ERR_HIP;
+    if (chain_has_vartrimmed(lc)) { VtBuffers vb; if (vt_buffers(c, n * lc.k, &vb) != ICPMI_OK) return ICPMI_ERR_HIP; } // reserved here: enqueue_selection cannot fail
+    // scratch 5: the partials, the result block, the pose
+    constexpr size_t RES_DOUBLES = (sizeof(ResBlock) + sizeof(double) - 1) / sizeof(double);
+    double* d_part = scratch_get<double>(c, 5, (size_t)ICPMI_RES_NB * ICPMI_RES_NV + RES_DOUBLES + 8);
+    if (!d_part) return ICPMI_ERR_HIP;
+    ResBlock* d_res = reinterpret_cast<ResBlock*>(d_part + ICPMI_RES_NB * ICPMI_RES_NV);
+    float* d_T0 = reinterpret_cast<float*>(d_part + ICPMI_RES_NB * ICPMI_RES_NV + RES_DOUBLES);
+    { const icpmi_status us = upload_small(c, d_T0, T_host, 16 * sizeof(float)); if (us != ICPMI_OK) return us; }
+    hipLaunchKernelGGL(init_state_kernel, dim3(1), dim3(64), 0, c->stream, c->d_state, (const float*)d_T0, 0u, (unsigned*)nullptr);
+    HIP_TRY(c, hipMemsetAsync(c->d_selhist, 0, ICPMI_SELHIST_WORDS * sizeof(unsigned), c->stream));
+    LoopCfg l1 = lc;
+    l1.max_iter = 1; l1.use_diff = 0; l1.use_bound = 0;
+    NnRequest req = loop_request(c, l1, batch_of_one(n), d_r2row); // (iter 0: what a registration's first iteration asks of the matcher)
+    NnOutcome nn;
+    const icpmi_status s = nn_launch_k(c, req, c->d_reading, n, c->d_state->T_iter, l1, 1, c->d_sidx, c->d_d2, c->d_state, &nn);
+    if (s != ICPMI_OK) return s;
+    enqueue_selection(c, l1, n * l1.k, req.batch, nn);
+    const int slot = fused_filter_slot(l1);
+    int limit_slot = -1;
+    for (int f = 0; f < l1.n_out; ++f)
+        if (l1.out_type[f] == ICPMI_OUT_TRIMMEDDIST || l1.out_type[f] == ICPMI_OUT_MEDIANDIST || l1.out_type[f] == ICPMI_OUT_VARTRIMMEDDIST) limit_slot = f;
+    const bool sorted = nn.out_sorted;
+    hipLaunchKernelGGL(res_pairs_kernel, dim3(ICPMI_RES_NB), dim3(256), 0, c->stream, sorted ? (const float4*)c->d_qsorted : (const float4*)c->d_reading,
+                       sorted ? (const int*)c->d_qindex : (const int*)nullptr, (int)n, l1, kind, planar, c->d_state, (const float4*)c->d_map_sorted,
+                       c->has_normals ? (const float4*)c->d_normals_sorted : (const float4*)nullptr,
+                       l1.has_read_normals ? (const float4*)c->d_read_normals : (const float4*)nullptr,
+                       (l1.ext && c->raw_has_scalar) ? (const float*)c->d_raw_s : (const float*)nullptr, (const int*)c->d_sidx, (const float*)c->d_d2,
+                       (sorted && l1.k == 1) ? (const float4*)c->d_match_pt : (const float4*)nullptr, (const unsigned*)c->d_selhist, slot >= 0 ? slot : -1,
+                       (slot >= 0 && l1.out_type[slot] == ICPMI_OUT_MEDIANDIST) ? 1 : 0, slot >= 0 ? l1.out_param[slot] : 0.f, d_part);
+    hipLaunchKernelGGL(res_finish_kernel, dim3(1), dim3(64), 0, c->stream, (const double*)d_part, (const IcpState*)c->d_state, limit_slot, d_res);
+    HIP_TRY(c, hipGetLastError());
+    ResBlock hr;
+    if (read_back(c, &hr, d_res, sizeof hr) != ICPMI_OK) return ICPMI_ERR_HIP;
+    c->cov_kept = cov_keep; // (the matcher's launch dropped last_match_n: icpmi_debug_last_matches has nothing to read any more)
+    if (hr.error) {
+        c->last_error = hr.error == ICPMI_ERR_NO_OUTLIER_TO_FILTER ? "ConvergenceError: no outlier to filter" : "residual_error: device-side convergence error";
+        return (icpmi_status)hr.error;
+    }
+    if (hr.pairs <= 0) { c->last_error = "ConvergenceError: ErrorMinimizer: no point to minimize"; return ICPMI_ERR_NO_POINT_TO_MINIMIZE; }
+    out->sum_abs = hr.sum_abs; out->sum_sq = hr.sum_sq; out->max_abs = hr.max_abs;
+    out->weight_sum = hr.weight_sum; out->pairs = hr.pairs;
+    out->weighted_point_used_ratio = (float)(hr.weight_sum / ((double)l1.k * (double)n));
+    out->trimmed_limit = hr.limit;
+    out->kind = kind;
+    return ICPMI_OK;
+}
+
 icpmi_status loop_outlier_weights(icpmi_ctx* c, const LoopCfg& lc, const float* d2, const int32_t* ids, int k, int64_t n,
                                   const float* read_normals3, float* weights, float* limit_out)
 {
-    c->last_match_n = 0; // (d2 / ids of the caller go through the loop's buffers)
+    c->last_match_n = 0; c->cov_kept = false; // (d2 / ids of the caller go through the loop's buffers)
     // matches arrive with ORIGINAL ids; the device's normals table is in sorted order.  SurfaceNormalOutlierFilter (r4) reads the map's
     // normals from the resident copy instead, which IS in the caller's order (d_raw_n3, padded to float4 for the kernel).
     bool needs_sn = false;

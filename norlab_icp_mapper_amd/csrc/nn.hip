@@ -1670,14 +1670,14 @@ static icpmi_status nnk_launch_t(icpmi_ctx* c, const NnRequest& req, const float
 }
 
 // One search of n queries for their lc.k nearest map points.  What the launch is asked beyond that comes in `req`, what it decided goes to
-// `*out` (common.h: NnRequest / NnOutcome); of the handle it changes last_match_n and, on failure, last_error -- nothing else.
+// `*out` (common.h: NnRequest / NnOutcome); of the handle it changes last_match_n (cov_kept with it) and, on failure, last_error -- nothing else.
 icpmi_status nn_launch_k(icpmi_ctx* c, const NnRequest& req, const float4* d_reading, int64_t n, const float* d_T, const LoopCfg& lc,
                          int allow_self, int* d_sidx, float* d_d2, IcpState* d_state, NnOutcome* out)
 {
     NnOutcome unread;
     if (!out) out = &unread;
     *out = NnOutcome();
-    c->last_match_n = 0; // (loop_run sets it again once its last iteration is in)
+    c->last_match_n = 0; c->cov_kept = false; // (loop_run sets it again once its last iteration is in)
 #define NNK(KMAX_) nnk_launch_t<KMAX_>(c, req, d_reading, n, d_T, lc, allow_self, d_sidx, d_d2, d_state, out)
     if (lc.k == 1) return nn_launch_k1(c, req, d_reading, n, d_T, lc, allow_self, d_sidx, d_d2, d_state, out);
     if (lc.k <= 4) return NNK(4);

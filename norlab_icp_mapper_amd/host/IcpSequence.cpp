@@ -475,6 +475,41 @@ Mat4 GpuICPSequence::operator()(const DataPoints& readingIn)
     return T;
 }
 
+icpmi_residual GpuICPSequence::residual(const DataPoints& readingIn, const Mat4& T, int kind) const
+{
+    DataPoints owned;
+    if (hasReadingFilters()) owned = filteredReading(readingIn);
+    const DataPoints& reading = hasReadingFilters() ? owned : readingIn;
+    const float* normals = nullptr;
+    if (reading.descriptorExists("normals") && reading.getDescriptorByName("normals").span == 3)
+        normals = reading.getDescriptorByName("normals").data.data();
+    if (!genericReadDescName.empty()) { // GenericDescriptorOutlierFilter{source: reading}
+        if (!reading.descriptorExists(genericReadDescName) || reading.getDescriptorByName(genericReadDescName).span != 1)
+            throw InvalidField("GenericDescriptorOutlierFilter: the reading has no 1-row descriptor " + genericReadDescName);
+        check(h, icpmi_set_reading_scalar(h, reading.getDescriptorByName(genericReadDescName).data.data(), (int64_t)reading.getNbPoints()));
+    }
+    if (!maxDistFieldName.empty()) { // KDTreeVarDistMatcher: the radii of the FILTERED reading (one shot)
+        if (!reading.descriptorExists(maxDistFieldName) || reading.getDescriptorByName(maxDistFieldName).span != 1)
+            throw InvalidField("KDTreeVarDistMatcher: the reading has no 1-row descriptor " + maxDistFieldName);
+        check(h, icpmi_set_reading_max_dist(h, reading.getDescriptorByName(maxDistFieldName).data.data(), (int64_t)reading.getNbPoints()));
+    }
+    icpmi_residual out{};
+    check(h, icpmi_residual_error(h, reading.features.data(), (int64_t)reading.getNbPoints(), normals, T.data(), kind, &out));
+    return out;
+}
+
+icpmi_residual GpuICPSequence::residualStaged(const Mat4& T, int kind) const
+{
+    icpmi_residual out{};
+    check(h, icpmi_residual_error_staged(h, T.data(), kind, &out));
+    return out;
+}
+
+float GpuICPSequence::ErrorMinimizerView::getResidualError(const DataPoints& reading, const Mat4& T) const
+{
+    return (float)owner->residual(reading, T).sum_abs;
+}
+
 // ------------------------------------------------------------------------------------------------
 DataPoints RigidTransformation::compute(const DataPoints& cloud, const Mat4& T) const
 {

@@ -39,6 +39,9 @@ public:
         // PointToPlaneWithCovErrorMinimizer::getCovariance(): 6 x 6 column-major, (tx, ty, tz, alpha, beta, gamma), centred frame, of the
         // last registration (include/icpmi.h: icpmi_get_covariance); throws through check() when there is none
         std::array<float, 36> getCovariance() const;
+        // ErrorMinimizer::getResidualError of `reading` against the map under the correction T, by the chain's minimizer: the sum over the
+        // error elements of |p - q| (point-to-point) or |(p - q) . n| (point-to-plane) -- GpuICPSequence::residual(reading, T).sum_abs
+        float getResidualError(const DataPoints& reading, const Mat4& T) const;
     };
 
     explicit GpuICPSequence(int device = 0);
@@ -52,6 +55,12 @@ public:
     bool hasMap() const;
     Mat4 operator()(const DataPoints& reading);        // correction in the map frame
     const ErrorMinimizerView* errorMinimizer = &minimizerView;
+    // How well `reading` (in the map frame by the prior, as for operator()) fits the map under the correction T: one matcher pass and the
+    // chain's outlier filters on the device (include/icpmi.h: icpmi_residual_error).  The chain's reading filters are applied as operator()
+    // applies them; `normals` and the rows the chain reads go with the reading.  Throws what operator() throws.  Leaves stats() alone.
+    icpmi_residual residual(const DataPoints& reading, const Mat4& T, int kind = ICPMI_RES_CHAIN) const;
+    // ... of the scan registerWithPrior left on the GPU (icpmi_residual_error_staged): no upload
+    icpmi_residual residualStaged(const Mat4& T, int kind = ICPMI_RES_CHAIN) const;
 
     icpmi_handle handle() const { return h; }          // for the operators that share the GPU context
     // Map::updateLocalPointCloud for the PointDistance chain on the resident map (icpmi_map_update_point_distance)

@@ -246,7 +246,10 @@ void Mapper::processInput(const DataPoints& filteredInputInSensorFrame, const Ma
             std::lock_guard<std::mutex> g(icpMapLock);
             lastSeenMapVersion = map.icpMapVersion();
             correction = icp.registerWithPrior(filteredInputInSensorFrame, estimatedPose); // identity while there is no map
+            lastScoreValid = false;
+            if (scoreRegistrations && !bootstrap && icp.hasMap()) { lastScore = icp.residualStaged(correction); lastScoreValid = true; }
         }
+        lastCorrectionMat = bootstrap ? Mat4::identity() : correction;
         lastRegMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tReg).count();
         const Mat4 correctedPose = bootstrap ? estimatedPose : correction * estimatedPose;
         map.updatePose(correctedPose);
@@ -276,11 +279,14 @@ void Mapper::processInput(const DataPoints& filteredInputInSensorFrame, const Ma
     lastScanGrewMap = false;
     lastUpdMs = 0.0;
     const auto tReg = std::chrono::steady_clock::now();
+    lastScoreValid = false;
     if (!bootstrap) {
         std::lock_guard<std::mutex> g(icpMapLock);
         lastSeenMapVersion = map.icpMapVersion();
         correction = icp(scanInMap);
+        if (scoreRegistrations && icp.hasMap()) { lastScore = icp.residual(scanInMap, correction); lastScoreValid = true; }
     }
+    lastCorrectionMat = correction;
     lastRegMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tReg).count();
     const Mat4 correctedPose = bootstrap ? estimatedPose : correction * estimatedPose;
     map.updatePose(correctedPose);

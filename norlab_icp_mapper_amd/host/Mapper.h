@@ -93,6 +93,13 @@ public:
     void loadYamlConfigFromString(const std::string& text);
     const icpmi_stats& lastIcpStats() const { return icp.stats(); }
     const GpuICPSequence& icpSequence() const { return icp; } // (errorMinimizer->getCovariance() of the last registration)
+    // Score every successful registration (off by default; no YAML key: the `mapper:` keys mirror the reference's): right after the ICP
+    // call processInput evaluates the scan under the correction it got (GpuICPSequence::residualStaged on the one-upload path, residual
+    // on the host path) and keeps the answer.  lastResidualValid(): the last processInput registered a scan and scored it.
+    void setScoreRegistrations(bool on) { scoreRegistrations = on; }
+    const icpmi_residual& lastResidual() const { return lastScore; }
+    bool lastResidualValid() const { return lastScoreValid; }
+    const Mat4& lastCorrection() const { return lastCorrectionMat; } // the correction of the last processInput's ICP call (identity: none ran)
     // the last processInput: version of the registration map it ran against (Map::icpMapVersion, read under the ICP lock) and
     // whether it started a map update -- what a replay needs to reproduce a free-running online run scan by scan
     long lastRegistrationMapVersion() const { return lastSeenMapVersion; }
@@ -117,6 +124,9 @@ private:
     long lastSeenMapVersion = 0;
     bool lastScanGrewMap = false;
     double lastRegMs = 0.0, lastUpdMs = 0.0;
+    bool scoreRegistrations = false, lastScoreValid = false;
+    icpmi_residual lastScore{};
+    Mat4 lastCorrectionMat = Mat4::identity();
     std::atomic_bool isMapping;
     Map map;
     Mat4 pose = Mat4::identity();

@@ -323,4 +323,80 @@ int nim_test_mapper_replay_map(const char* config, int n_scans, const char* cons
     }
 }
 
+// GpuICPSequence on device 0: loadFromYamlNode(yaml_icp), setMap(map4 + map_normals3), then -- T16 == NULL -- operator() on the reading
+// (scan4 + scan_normals3 as `normals`, may be NULL) and residual(reading, T of that registration, kind); with T16 (column-major) no
+// registration, residual(reading, T16, kind).  *out the icpmi_residual, T_out16 the T used, *residual_error_out what
+// errorMinimizer->getResidualError(reading, T) returns (kind 0 only; else the same sum).  Returns 0; 2 ConvergenceError, 3 InvalidField,
+// 4 InvalidParameter, 1 any other exception, the text in err.
+int nim_test_icp_residual(const char* yaml_icp, const float* map4, int64_t m, const float* map_normals3, const float* scan4, int64_t n,
+                          const float* scan_normals3, const float* T16, int kind, icpmi_residual* out, float* T_out16,
+                          float* residual_error_out, char* err, int err_cap)
+{
+    const auto fail = [&](const std::exception& e, int rc) {
+        if (err && err_cap > 0) { std::strncpy(err, e.what(), (size_t)err_cap - 1); err[err_cap - 1] = 0; }
+        return rc;
+    };
+    try {
+        nim::DataPoints map((size_t)m), scan((size_t)n);
+        std::memcpy(map.features.data(), map4, sizeof(float) * 4 * (size_t)m);
+        if (map_normals3) map.addDescriptor("normals", 3, std::vector<float>(map_normals3, map_normals3 + 3 * (size_t)m));
+        std::memcpy(scan.features.data(), scan4, sizeof(float) * 4 * (size_t)n);
+        if (scan_normals3) scan.addDescriptor("normals", 3, std::vector<float>(scan_normals3, scan_normals3 + 3 * (size_t)n));
+        nim::GpuICPSequence icp(0);
+        icp.loadFromYamlNode(nim::yaml::Load(yaml_icp));
+        if (!icp.setMap(map)) throw std::runtime_error("setMap refused the map");
+        nim::Mat4 T;
+        if (T16) std::memcpy(T.data(), T16, sizeof(float) * 16);
+        else T = icp(scan);
+        *out = icp.residual(scan, T, kind);
+        std::memcpy(T_out16, T.data(), sizeof(float) * 16);
+        *residual_error_out = kind == ICPMI_RES_CHAIN ? icp.errorMinimizer->getResidualError(scan, T) : (float)out->sum_abs;
+        return 0;
+    } catch (const nim::ConvergenceError& e) {
+        return fail(e, 2);
+    } catch (const nim::InvalidField& e) {
+        return fail(e, 3);
+    } catch (const nim::InvalidParameter& e) {
+        return fail(e, 4);
+    } catch (const std::exception& e) {
+        return fail(e, 1);
+    }
+}
+
+// The offline replay of nim_test_mapper_replay with Mapper::setScoreRegistrations(score).  freeze_after_first: the mapper stops mapping
+// behind the first scan, so that every later scan registers against the map that scan built.  After every processInput: the pose,
+// lastResidualValid() / lastResidual(), and -- by_hand != NULL and the scan was scored -- GpuICPSequence::residual called by hand on the
+// same filtered scan moved by the same prior, under Mapper::lastCorrection() (the map must not have changed in between: freeze).
+int nim_test_mapper_replay_scored(const char* config, int n_scans, const char* const* paths, const float* poses16, const int64_t* stamps_ns,
+                                  int score, int freeze_after_first, float* poses_out16, icpmi_residual* res_out, int32_t* res_valid,
+                                  icpmi_residual* by_hand, char* err, int err_cap)
+{
+    try {
+        nim::Mapper mapper(config, true, false, true, false);
+        mapper.setScoreRegistrations(score != 0);
+        for (int i = 0; i < n_scans; ++i) {
+            nim::DataPoints cloud = nim::DataPoints::load(paths[i]);
+            mapper.applyInputFilters(cloud);
+            nim::Mat4 pose;
+            std::memcpy(pose.data(), poses16 + 16 * i, sizeof(float) * 16);
+            mapper.processInput(cloud, pose, nim::TimePoint{std::chrono::nanoseconds(stamps_ns[i])});
+            std::memcpy(poses_out16 + 16 * i, mapper.getPose().data(), sizeof(float) * 16);
+            res_valid[i] = mapper.lastResidualValid() ? 1 : 0;
+            res_out[i] = mapper.lastResidual();
+            if (by_hand) {
+                std::memset(by_hand + i, 0, sizeof *by_hand);
+                if (mapper.lastResidualValid()) {
+                    const nim::DataPoints inMap = nim::RigidTransformation(mapper.icpSequence().handle()).compute(cloud, pose);
+                    by_hand[i] = mapper.icpSequence().residual(inMap, mapper.lastCorrection());
+                }
+            }
+            if (i == 0 && freeze_after_first) mapper.setIsMapping(false);
+        }
+        return 0;
+    } catch (const std::exception& e) {
+        if (err && err_cap > 0) { std::strncpy(err, e.what(), (size_t)err_cap - 1); err[err_cap - 1] = 0; }
+        return 1;
+    }
+}
+
 } // extern "C"

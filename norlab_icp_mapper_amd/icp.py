@@ -238,6 +238,25 @@ def config_from_yaml_chain(chain, **engine):
     return cfg
 
 
+class Residual:
+    """icpmi_residual as plain Python values (sum_abs = ErrorMinimizer::getResidualError())."""
+    __slots__ = ("sum_abs", "sum_sq", "max_abs", "weighted_point_used_ratio", "weight_sum", "pairs", "trimmed_limit", "kind")
+
+    def __init__(self, c):
+        self.sum_abs, self.sum_sq, self.weight_sum = float(c.sum_abs), float(c.sum_sq), float(c.weight_sum)
+        self.max_abs, self.weighted_point_used_ratio = np.float32(c.max_abs), np.float32(c.weighted_point_used_ratio)
+        self.trimmed_limit = np.float32(c.trimmed_limit)
+        self.pairs, self.kind = int(c.pairs), int(c.kind)
+
+    def bits(self):
+        """every field as raw bits (bit-for-bit comparisons)"""
+        return (np.float64([self.sum_abs, self.sum_sq, self.weight_sum]).view(np.uint64).tolist(),
+                np.float32([self.max_abs, self.weighted_point_used_ratio, self.trimmed_limit]).view(np.uint32).tolist(), self.pairs, self.kind)
+
+    def __repr__(self):
+        return "Residual(" + ", ".join(f"{k}={getattr(self, k)!r}" for k in self.__slots__) + ")"
+
+
 class _ErrorMinimizerView:
     def __init__(self, owner):
         self._o = owner
@@ -260,6 +279,11 @@ class _ErrorMinimizerView:
         out = (C.c_float * 36)()
         self._o._check(self._o._lib.icpmi_get_covariance(self._o._h, out))
         return np.array(out[:], dtype=np.float32).reshape(6, 6).T.copy()
+
+    def getResidualError(self, reading, T=None):
+        """ErrorMinimizer::getResidualError of `reading` against the map under the correction T (None: identity), by the chain's
+        minimizer: the sum over the error elements of |p - q| (point-to-point) or |(p - q) . n| (point-to-plane) -- ICPSequence.residual"""
+        return float(self._o.residual(reading, T).sum_abs)
 
 
 class ICPSequence:
@@ -357,6 +381,48 @@ class ICPSequence:
                 raise InvalidField(msg)
         self._check(st)
         return _T_from_c(T[:])
+
+    # ---- how well a reading fits the map under a given pose (icpmi_residual_error*) ----
+    def _residual_out(self, st, res):
+        if st == _capi.ERR_INVALID_ARG:
+            msg = self._lib.icpmi_last_error(self._h).decode()
+            if msg.startswith("InvalidField"):
+                raise InvalidField(msg)
+            if msg.startswith("TransformationError"):
+                raise TransformationError(msg)
+        self._check(st)
+        return Residual(res)
+
+    def residual(self, reading, T=None, normals=None, kind=0):
+        """icpmi_residual_error: `reading` (N, 4), already moved by the prior as for __call__, matched once against the map under the
+        correction T (4x4, None: identity) and weighed by the chain's outlier filters.  kind 0: by the chain's minimizer, 1: point-to-point,
+        2: point-to-plane.  normals (N, 3): the reading's, for a SurfaceNormalOutlierFilter.  Returns a Residual: sum_abs
+        (getResidualError()), sum_sq, max_abs, pairs, weight_sum, weighted_point_used_ratio, trimmed_limit, kind."""
+        scan = _f32c(reading, 4)
+        nptr = None
+        if normals is not None:
+            normals = _f32c(normals, 3)
+            nptr = normals.ctypes.data
+        Tc = None if T is None else _T_to_c(T)
+        res = _capi.Residual()
+        st = self._lib.icpmi_residual_error(self._h, scan.ctypes.data, scan.shape[0], nptr, None if Tc is None else Tc.ctypes.data, int(kind),
+                                            C.byref(res))
+        return self._residual_out(st, res)
+
+    def residualDev(self, d_scan_ptr, n, T=None, d_normals_ptr=None, kind=0):
+        """icpmi_residual_error_dev: residual() for a reading (and its normals) already in HBM."""
+        Tc = None if T is None else _T_to_c(T)
+        res = _capi.Residual()
+        st = self._lib.icpmi_residual_error_dev(self._h, d_scan_ptr, int(n), d_normals_ptr, None if Tc is None else Tc.ctypes.data, int(kind),
+                                                C.byref(res))
+        return self._residual_out(st, res)
+
+    def residualStaged(self, T=None, kind=0):
+        """icpmi_residual_error_staged: residual() of the scan registerWithPrior left in HBM (no upload), under the correction T."""
+        Tc = None if T is None else _T_to_c(T)
+        res = _capi.Residual()
+        st = self._lib.icpmi_residual_error_staged(self._h, None if Tc is None else Tc.ctypes.data, int(kind), C.byref(res))
+        return self._residual_out(st, res)
 
     def setReadingMaxDist(self, radii):
         """icpmi_set_reading_max_dist: the search radius of every point of the NEXT reading (KDTreeVarDistMatcher's `maxDistField` row; one shot)."""
