@@ -751,6 +751,17 @@ icpmi_status icpmi_debug_counters(icpmi_handle h, uint64_t out[24]);
  * nothing to read: no registration yet, one that failed, a batch (icpmi_register_batch_dev), or any other call that reused the matcher's
  * buffers or changed the map after it. */
 icpmi_status icpmi_debug_last_matches(icpmi_handle h, int64_t n, int32_t k, int32_t* ids, float* d2, float T_used[16]);
+/* Test seam: the self k-NN search behind icpmi_surface_normals*, and nothing else -- the same private search handle, so the cell-edge tuner's
+ * history is shared with the filter.  ids (m x k, row i = the neighbours of point i) are ORIGINAL indices, laid out and converted as
+ * matched_ids of icpmi_surface_normals_ex2, ascending by (d2, index); d2 (m x k) as the search kernels computed it; unfilled slots -1 / +inf.
+ * info (may be NULL) describes the grid the call built: [0] the bits of the A-cell edge (float32), [1 .. 3] A-cells per axis, [4] entries of
+ * the block table T, [5] queries the cell kernel queued for the level kernel, [6] builds the tuner ran, [7] 0.  No production path calls it. */
+icpmi_status icpmi_debug_self_knn(icpmi_handle h, const float* pts4, int64_t m, int32_t k, int32_t* ids, float* d2, uint64_t info[8]);
+/* Test seam: the squared distance of every resident point's k-th neighbour (itself counted) as the SurfaceNormal pass of the last append-only
+ * update remembered it -- the state the next append's subset search selects from; +inf where fewer than k points exist.  m must be the
+ * resident map's size; *knn_out (may be NULL) = that pass's knn.  ICPMI_ERR_UNSUPPORTED unless the row describes the resident map as it is
+ * (a tracked pass ran and nothing rewrote the map since).  No production path calls it. */
+icpmi_status icpmi_debug_resident_kth_d2(icpmi_handle h, int64_t m, float* out, int32_t* knn_out);
 /* Test seam: the pair sums of the last COUNTED iteration of the last single registration, as its solve read them.  Off by default:
  * icpmi_debug_keep_sums(h, 1) gives the handle a block of 32 doubles that every later single registration's solve writes (the cached loop
  * graphs are dropped; batches never write it), icpmi_debug_keep_sums(h, 0) takes it away again.  Layout of sums[32] (double), as

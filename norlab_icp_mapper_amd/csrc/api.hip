@@ -342,6 +342,20 @@ icpmi_status icpmi_debug_last_matches(icpmi_handle h, int64_t n, int32_t k, int3
     return ICPMI_OK;
 }
 
+icpmi_status icpmi_debug_self_knn(icpmi_handle h, const float* pts4, int64_t m, int32_t k, int32_t* ids, float* d2, uint64_t info[8])
+{
+    CHECK_H(h);
+    if (m < 1 || !pts4 || !ids || !d2) { h->last_error = "debug_self_knn: bad arguments"; return ICPMI_ERR_INVALID_ARG; }
+    return ops_debug_self_knn(h, pts4, m, k, ids, d2, info);
+}
+
+icpmi_status icpmi_debug_resident_kth_d2(icpmi_handle h, int64_t m, float* out, int32_t* knn_out)
+{
+    CHECK_H(h);
+    if (m < 1 || !out) { h->last_error = "debug_resident_kth_d2: bad arguments"; return ICPMI_ERR_INVALID_ARG; }
+    return ops_debug_resident_kth_d2(h, m, out, knn_out);
+}
+
 icpmi_status icpmi_debug_keep_sums(icpmi_handle h, int32_t on)
 {
     CHECK_H(h);

@@ -1062,6 +1062,7 @@ icpmi_status nn_ids_to_original(icpmi_ctx* c, const int* d_sidx, int64_t count, 
 struct SelfGridSubset { int64_t m_old = 0; const float* d_dk = nullptr; const unsigned* d_list = nullptr; int64_t n_sel = 0; };
 icpmi_status selfgrid_knn(icpmi_ctx* c, const float4* d_pts, int64_t m, int k, int* d_sidx, float* d_d2, SelfGridSubset* sub = nullptr);
 void selfgrid_destroy(icpmi_ctx* c);
+icpmi_status selfgrid_debug_info(icpmi_ctx* c, uint64_t info[8]); // test seam: the grid of the handle's last selfgrid_knn
 icpmi_status create_handle(const icpmi_config* cfg, icpmi_handle* out); // icpmi_create without the cache's handle count (private handles)
 // d_r2row: the squared accept radii of a KDTreeVarDistMatcher registration (one per point of the reading), else nullptr
 icpmi_status loop_run(icpmi_ctx* c, const float4* d_scan, const float* d_normals3, int64_t n, const LoopCfg& lc, const float* d_r2row, bool fixed,
@@ -1129,6 +1130,9 @@ icpmi_status max_density_flags_dev(icpmi_ctx* c, const float* d_dens, int64_t n,
 icpmi_status ops_max_density_keep(icpmi_ctx* c, const float* densities, int64_t n, float max_density, int seed, uint8_t* keep);
 icpmi_status ops_surface_normals(icpmi_ctx* c, const float* pts4, int64_t m, int knn, float* normals3, float* densities = nullptr,
                                  int32_t* matched_ids = nullptr, float* mean_dist = nullptr, float* eig_values = nullptr, float* eig_vectors = nullptr);
+// test seams (icpmi_debug_self_knn / icpmi_debug_resident_kth_d2)
+icpmi_status ops_debug_self_knn(icpmi_ctx* c, const float* pts4, int64_t m, int k, int32_t* ids, float* d2, uint64_t* info);
+icpmi_status ops_debug_resident_kth_d2(icpmi_ctx* c, int64_t m, float* out, int32_t* knn_out);
 icpmi_status ops_dynamic_points_update(icpmi_ctx* c, const icpmi_dynpts_params* prm, const float to_sensor[16], const float* in4, int64_t n,
                                        const float* map4, const float* map_normals3, int64_t m, float* prob);
 icpmi_status ops_map_update_point_distance(icpmi_ctx* c, const float* scan4, int64_t n, const float* scan_normals3, float min_dist,

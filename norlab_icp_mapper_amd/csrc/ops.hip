@@ -198,6 +198,20 @@ static icpmi_status surface_normals_dev(icpmi_ctx* c, const float4* d_pts, int64
     return ICPMI_OK;
 }
 
+// Test seam (icpmi_debug_resident_kth_d2): the remembered k-th distances, served only while they describe the resident map
+icpmi_status ops_debug_resident_kth_d2(icpmi_ctx* c, int64_t m, float* out, int32_t* knn_out)
+{
+    if (!c->d_raw_dk || c->dk_m <= 0 || c->dk_m != c->m_raw || c->dk_epoch != c->raw_epoch) {
+        c->last_error = "debug_resident_kth_d2: no k-th distances of the resident map on this handle (no tracked normals pass, or the map was rewritten since)";
+        return ICPMI_ERR_UNSUPPORTED;
+    }
+    if (m != c->dk_m) { c->last_error = "debug_resident_kth_d2: m differs from the resident map's size"; return ICPMI_ERR_INVALID_ARG; }
+    if (knn_out) *knn_out = c->dk_knn;
+    HIP_TRY(c, hipMemcpyAsync(out, c->d_raw_dk, (size_t)m * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return ICPMI_OK;
+}
+
 icpmi_status ops_map_update_point_distance(icpmi_ctx* c, const float* scan4, int64_t n, const float* scan_normals3, float min_dist,
                                            int normals_knn, uint8_t* keep_out, int64_t* appended, int64_t* new_m)
 {

@@ -570,6 +570,31 @@ icpmi_status ops_surface_normals(icpmi_ctx* c, const float* pts4, int64_t m, int
     return ICPMI_OK;
 }
 
+// Test seam (icpmi_debug_self_knn): the search of ops_surface_normals and nothing behind it -- the same private handle (its grid's tuning
+// history is the filter's), ids through keepMatchedIds' conversion, d2 as the search kernels left them
+icpmi_status ops_debug_self_knn(icpmi_ctx* c, const float* pts4, int64_t m, int k, int32_t* ids, float* d2, uint64_t* info)
+{
+    if (k < 1 || k > ICPMI_MAX_K) { c->last_error = "debug_self_knn: k must be in [1, 32]"; return ICPMI_ERR_INVALID_ARG; }
+    TempCtx t;
+    icpmi_status s = make_temp(c, t);
+    if (s != ICPMI_OK) return s;
+    s = temp_knn(c, t, pts4, m, nullptr, m, k, 1, true);
+    if (s != ICPMI_OK) return s;
+    icpmi_ctx* tc = t.h;
+    const size_t cnt = (size_t)m * k;
+    DevBuf<int> d_ids;
+    HIP_TRY(c, d_ids.alloc(cnt));
+    if (nn_ids_to_original(tc, tc->d_sidx, (int64_t)cnt, d_ids) != ICPMI_OK) { c->last_error = tc->last_error; return ICPMI_ERR_HIP; }
+    HIP_TRY(c, hipMemcpyAsync(ids, d_ids, cnt * sizeof(int), hipMemcpyDeviceToHost, tc->stream));
+    HIP_TRY(c, hipMemcpyAsync(d2, tc->d_d2, cnt * sizeof(float), hipMemcpyDeviceToHost, tc->stream));
+    HIP_TRY(c, hipStreamSynchronize(tc->stream));
+    if (info) {
+        s = selfgrid_debug_info(tc, info);
+        if (s != ICPMI_OK) c->last_error = tc->last_error;
+    }
+    return s;
+}
+
 icpmi_status ops_point_distance_keep(icpmi_ctx* c, const float* map4, int64_t m, const float* in4, int64_t n, float min_dist,
                                      uint8_t* keep)
 {

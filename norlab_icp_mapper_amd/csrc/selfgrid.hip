@@ -24,7 +24,7 @@
 //     the others are dealt to the lanes 64 at a time.  The top level covers the grid: every query ends here, there is no brute pass.
 // Exactness: both kernels return the k smallest keys (d^2 bits << 32 | original index) over candidate sets that contain every point within the
 // k-th distance -- the same k points in the same order whatever the grid (the oracle's and r5's bits: tests/test_gpu_parity.py, test_pins.py,
-// test_gpu_map_chain.py, test_gpu_configs.py).
+// test_gpu_map_chain.py, test_gpu_configs.py; every branch below at its edge, query by query: tests/test_gpu_self_knn.py).
 #include "common.h"
 
 #include <algorithm>
@@ -49,6 +49,7 @@ struct SelfGridCtx {
     // tuning state: the edge of the previous build and what its points saw (size-biased A-cell occupancy, delivered through the mapped page)
     float cell = 0.f; int64_t m = 0; int k = 0;
     unsigned long long seq = 0;
+    int last_na[3] = {0, 0, 0}, last_tsize = 0, last_trials = 0; // the last build's grid, for the test seam (selfgrid_debug_info)
 };
 
 struct SgState {
@@ -831,6 +832,23 @@ void selfgrid_destroy(icpmi_ctx* c)
     c->sg = nullptr;
 }
 
+// Test seam (icpmi_debug_self_knn): the grid of this handle's last selfgrid_knn -- bits of the A-cell edge, na[0 .. 2], entries of T, queries the
+// cell kernel queued for the level kernel (the ONE place that sums qcount: no search path reads it back), builds the tuner ran; [7] = 0
+icpmi_status selfgrid_debug_info(icpmi_ctx* c, uint64_t info[8])
+{
+    SelfGridCtx* sg = c->sg;
+    if (!sg || !sg->d_state || sg->seq == 0) { c->last_error = "self knn: no grid was built on this handle"; return ICPMI_ERR_UNSUPPORTED; }
+    unsigned qc[SG_NQ];
+    if (read_back(c, qc, sg->d_state->qcount, sizeof qc) != ICPMI_OK) return ICPMI_ERR_HIP;
+    uint64_t queued = 0;
+    for (int i = 0; i < SG_NQ; ++i) queued += qc[i];
+    uint32_t cell_bits;
+    memcpy(&cell_bits, &sg->cell, sizeof cell_bits);
+    info[0] = cell_bits; info[1] = (uint64_t)sg->last_na[0]; info[2] = (uint64_t)sg->last_na[1]; info[3] = (uint64_t)sg->last_na[2];
+    info[4] = (uint64_t)sg->last_tsize; info[5] = queued; info[6] = (uint64_t)sg->last_trials; info[7] = 0;
+    return ICPMI_OK;
+}
+
 // sub (may be null): d_pts[0 .. m_old) is the cloud of an earlier call whose k-th neighbour distances are in d_dk (original order): only the
 // appended points and the old points an appended point may have entered the neighbourhood of are searched; their rows of d_sidx / d_d2 are
 // written; sub->d_list (original indices, owned by the handle's grid) says which, sub->n_sel how many.
@@ -921,8 +939,10 @@ icpmi_status selfgrid_knn(icpmi_ctx* c, const float4* d_pts, int64_t m, int k, i
     const int blocks256 = (int)((m + 255) / 256);
     SgGrid g{};
     unsigned blocks_max = 0;
+    int built = 0;
     for (int trial = 0; trial < trials; ++trial) {
         g = make(cell);
+        built = trial + 1;
         blocks_max = (unsigned)std::min<int64_t>(m, (int64_t)g.tsize);
         bool fresh = false;
         if (sg->d_tcnt.ensure(c, (size_t)g.tsize + 2, &fresh) != ICPMI_OK) return ICPMI_ERR_HIP;
@@ -956,6 +976,7 @@ icpmi_status selfgrid_knn(icpmi_ctx* c, const float4* d_pts, int64_t m, int k, i
         cell = next;
     }
     sg->cell = g.cell; sg->m = m; sg->k = k; ++sg->seq;
+    sg->last_na[0] = g.na[0]; sg->last_na[1] = g.na[1]; sg->last_na[2] = g.na[2]; sg->last_tsize = g.tsize; sg->last_trials = built;
     if (sub) { // a tracked cloud (the resident map of append-only updates): leave the sorted copy behind for the build of the next append
         if (sg->d_prev.ensure(c, (size_t)m + 16) != ICPMI_OK) return ICPMI_ERR_HIP; // (a reallocation drops the old content: it is rewritten below)
         HIP_TRY(c, hipMemcpyAsync(sg->d_prev, c->d_map_sorted, (size_t)m * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));

@@ -1089,6 +1089,29 @@ class ICPSequence:
         self._check(self._lib.icpmi_debug_last_matches(self._h, n, k, ids.ctypes.data, d2.ctypes.data, T))
         return ids, d2, _T_from_c(T[:])
 
+    def debugSelfKnn(self, cloud, k, with_info=False):
+        """icpmi_debug_self_knn: (ids (m, k) int32 original indices, d2 (m, k) float32) of the self k-NN search behind surfaceNormals, on the same
+        private search handle; with_info: also a dict of the grid that call built (cell, na, tsize, queued, trials)."""
+        c = _f32c(cloud, 4); m = c.shape[0]; k = int(k)
+        ids = np.empty((m, k), dtype=np.int32); d2 = np.empty((m, k), dtype=np.float32)
+        info = (C.c_uint64 * 8)()
+        self._check(self._lib.icpmi_debug_self_knn(self._h, c.ctypes.data, m, k, ids.ctypes.data, d2.ctypes.data, info if with_info else None))
+        if not with_info:
+            return ids, d2
+        cell = float(np.array([info[0]], dtype=np.uint32).view(np.float32)[0])
+        return ids, d2, {"cell": cell, "na": (int(info[1]), int(info[2]), int(info[3])), "tsize": int(info[4]), "queued": int(info[5]),
+                         "trials": int(info[6])}
+
+    def debugResidentKthD2(self):
+        """icpmi_debug_resident_kth_d2: (d2 of every resident point's k-th neighbour (m,) float32, that k) as the last append-only update's
+        SurfaceNormal pass remembered them; raises when they do not describe the resident map."""
+        m = C.c_int64(0)
+        self._check(self._lib.icpmi_get_map(self._h, None, None, 0, C.byref(m)))
+        out = np.empty(max(m.value, 1), dtype=np.float32)
+        knn = C.c_int32(0)
+        self._check(self._lib.icpmi_debug_resident_kth_d2(self._h, m.value, out.ctypes.data, C.byref(knn)))
+        return out[:m.value], int(knn.value)
+
     def keepSums(self, on=1):
         """icpmi_debug_keep_sums: from now on (on) / no longer (off) keep the pair sums of this handle's single registrations for lastSums();
         off by default.  Drops the cached loop graphs."""

@@ -125,7 +125,7 @@ def check_matches(map_c, q, ids, d2, k, max_dist, eps=0.0, use_oracle=True, wher
     bad = np.nonzero((filled & ~(own <= tk * (1 + RANK_REL))).any(1))[0]
     if bad.size: _fail(where, "the j-th returned neighbour is farther than the true j-th (a nearer point was missed)", bad)
     # filled exactly where at least j points lie within maxDist (either answer inside the band around maxDist^2)
-    inside = tk <= r2 * (1 - MAXD_REL)
+    inside = np.isfinite(tk) & (tk <= r2 * (1 - MAXD_REL))   # (a rank the map has no point for is +inf: never inside, whatever maxDist)
     outside = tk > r2 * (1 + MAXD_REL)
     bad = np.nonzero((inside & ~filled).any(1))[0]
     if bad.size: _fail(where, "a slot is unfilled although j points lie within maxDist", bad)
