@@ -851,6 +851,43 @@ icpmi_status icpmi_residual_error(icpmi_handle h, const float* scan4, int64_t n,
 icpmi_status icpmi_residual_error_dev(icpmi_handle h, const float* d_scan4, int64_t n, const float* d_scan_normals3, const float T[16],
                                       int32_t kind, icpmi_residual* out);
 icpmi_status icpmi_residual_error_staged(icpmi_handle h, const float T[16], int32_t kind, icpmi_residual* out);
+
+/* The same reading under MANY poses in one call: what ranks the start poses of a relocalisation.  T holds n_poses (1 .. 4096) matrices of
+ * 16 floats, column-major; out[p] and status[p] are, bit for bit (the doubles too), what
+ *     icpmi_residual_error_dev(h, d_scan4, n, d_scan_normals3, T + 16 p, kind, &out[p])
+ * returns on the same handle, whichever poses share a launch and in whatever order they come.
+ *   Errors of the whole call are the return value, found before anything is enqueued, with the codes of the single call: no map, NULL
+ *   arguments, a bad kind, n_poses out of range, n == 0 (the convergence error of an empty reading), missing normals, the refused Robust
+ *   filters, IdentityErrorMinimizer under ICPMI_RES_CHAIN, a missing one-shot row.  out and status are then all zero.
+ *   Errors of one pose go to status[p]: a T[p] that is not rigid (ICPMI_ERR_INVALID_ARG; that pose is not launched),
+ *   ICPMI_ERR_NO_OUTLIER_TO_FILTER, ICPMI_ERR_NO_POINT_TO_MINIMIZE.  status == NULL: the first of them is the return value, as in
+ *   icpmi_register_batch_dev.
+ * The rows armed by icpmi_set_reading_scalar / icpmi_set_reading_max_dist belong to the reading: the call consumes them once and every pose
+ * uses them.  The reading is centred and tile-sorted once per call.
+ * The chains icpmi_register_batch_dev runs together (knn 1 on the grid pyramid, a finite maxDist below the top level's cell, at most one
+ * Trimmed / Median filter, no filter that reads descriptors, no maxDistField row) go in chunks of up to 16 poses: per chunk one matcher
+ * launch, one selection and the two reduction kernels of the single call with one slice, one loop state and one set of histograms per
+ * pose, the chunks back to back on the handle's stream, and ONE read-back of the n_poses results at the end.  Every other chain runs pose
+ * after pose through the single call's path on the prepared reading.  *batched (may be NULL) = the poses that took the batched launches
+ * (the rigid ones, or 0).
+ * Afterwards the handle is as after icpmi_residual_error.  The variant without _dev takes the reading (and its normals) from the host and
+ * uploads them once. */
+icpmi_status icpmi_residual_error_poses_dev(icpmi_handle h, const float* d_scan4, int64_t n, const float* d_scan_normals3, const float* T,
+                                            int32_t n_poses, int32_t kind, icpmi_residual* out, icpmi_status* status, int32_t* batched);
+icpmi_status icpmi_residual_error_poses(icpmi_handle h, const float* scan4, int64_t n, const float* scan_normals3, const float* T,
+                                        int32_t n_poses, int32_t kind, icpmi_residual* out, icpmi_status* status, int32_t* batched);
+
+/* One sensor-frame scan in HBM registered from n_starts (1 .. 16) priors at once: the scan is moved by every prior on the device
+ * (the transform of icpmi_register_prior_dev) into slices of its own and the slices go through icpmi_register_batch_dev's loop
+ * (fixed_iterations as there; a chain the batch does not serve registers them one after the other).  T_out + 16 s, stats[s] and status[s]
+ * are bit for bit what icpmi_register_prior_dev(h, d_scan4, n, priors + 16 s, ...) returns alone; a prior that is not rigid gets
+ * ICPMI_ERR_INVALID_ARG and an identity.  status == NULL: the first error is the return value.  No scan is left staged (icpmi_map_update_staged
+ * afterwards is ICPMI_ERR_INVALID_ARG) and there is no covariance, as after any batch. */
+icpmi_status icpmi_register_multistart_dev(icpmi_handle h, const float* d_scan4, int64_t n, const float* priors, int32_t n_starts,
+                                           int32_t fixed_iterations, float* T_out, icpmi_stats* stats, icpmi_status* status);
+/* ... with the scan on the host: one upload (as icpmi_register_prior), then the call above */
+icpmi_status icpmi_register_multistart(icpmi_handle h, const float* scan4, int64_t n, const float* priors, int32_t n_starts,
+                                       int32_t fixed_iterations, float* T_out, icpmi_stats* stats, icpmi_status* status);
 /* Test seam: the n-th value (n >= 1) of the std::minstd_rand stream as the DEVICE computes it by skip-ahead (csrc/ssn.hip, behind
  * SamplingSurfaceNormalDataPointsFilter -- PM::ICPSequence::setDefault(), Mapper.cpp:74-78).  [rand.predef]: seed 1, n = 10 000 -> 399268537. */
 icpmi_status icpmi_debug_minstd_nth(icpmi_handle h, uint32_t seed, uint32_t n, uint32_t* out);

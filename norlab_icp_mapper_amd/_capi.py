@@ -219,6 +219,10 @@ SYMBOLS = [
     ("icpmi_residual_error", C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int32, C.POINTER(Residual)]),
     ("icpmi_residual_error_dev", C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int32, C.POINTER(Residual)]),
     ("icpmi_residual_error_staged", C.c_int, [_P, _P, C.c_int32, C.POINTER(Residual)]),
+    ("icpmi_residual_error_poses", C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int32, C.c_int32, _P, _P, C.POINTER(C.c_int32)]),
+    ("icpmi_residual_error_poses_dev", C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int32, C.c_int32, _P, _P, C.POINTER(C.c_int32)]),
+    ("icpmi_register_multistart_dev", C.c_int, [_P, _P, C.c_int64, _P, C.c_int32, C.c_int32, _P, _P, _P]),
+    ("icpmi_register_multistart", C.c_int, [_P, _P, C.c_int64, _P, C.c_int32, C.c_int32, _P, _P, _P]),
     ("icpmi_debug_minstd_nth", C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]),
     ("icpmi_get_grid_info", C.c_int, [_P, _F, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
 ]

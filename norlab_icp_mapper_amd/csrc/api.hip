@@ -666,6 +666,26 @@ icpmi_status icpmi_register_fixed_dev(icpmi_handle h, const float* d_scan4, int6
     return register_impl(h, d_scan4, n, d_scan_normals3, iterations, T_out, stats);
 }
 
+// the chains whose kernels take a batch (blockIdx.y = reading): k = 1 on the grid pyramid without a brute-force pass, at most one quantile
+// filter, no filter that reads descriptors of the reading, no row of radii per reading
+static bool chain_takes_batch(const icpmi_ctx* h)
+{
+    bool together = h->m > 0 && h->cfg.knn == 1 && (h->cfg.minimizer != ICPMI_MIN_POINT_TO_PLANE || h->has_normals);
+    int nquant = 0;
+    for (int f = 0; f < h->cfg.n_outlier; ++f) {
+        const int t = h->cfg.outlier[f].type;
+        if (t == ICPMI_OUT_SURFACENORMAL || t == ICPMI_OUT_GENERICDESCRIPTOR || t == ICPMI_OUT_ROBUST || t == ICPMI_OUT_VARTRIMMEDDIST) together = false;
+        if (t == ICPMI_OUT_TRIMMEDDIST || t == ICPMI_OUT_MEDIANDIST) ++nquant;
+    }
+    if (nquant > 1) together = false;
+    if (h->cfg.var_dist) together = false; // (every reading needs its own row of radii)
+    if (together) {
+        const GridParams& top = h->levels.g[h->levels.nlev - 1];
+        if (!std::isfinite(h->cfg.max_dist) || (top.cell - top.slack) <= h->cfg.max_dist) together = false; // would need the brute-force pass
+    }
+    return together;
+}
+
 icpmi_status icpmi_register_batch_dev(icpmi_handle h, int32_t batch, const float* const* d_scans4, const int64_t* n, int32_t fixed_iterations,
                                       float* T_out, icpmi_stats* stats, icpmi_status* status)
 {
@@ -678,20 +698,8 @@ icpmi_status icpmi_register_batch_dev(icpmi_handle h, int32_t batch, const float
     // The one-launch-per-iteration path serves the chains whose kernels take a batch: k = 1 on the grid pyramid without a
     // brute-force pass, at most one quantile filter, no filter that reads descriptors of the reading.  Everything else --
     // and empty readings, a handle without a map -- runs the readings one after the other: same results, no sharing.
-    bool together = batch > 1 && h->m > 0 && h->cfg.knn == 1 && (h->cfg.minimizer != ICPMI_MIN_POINT_TO_PLANE || h->has_normals);
-    int nquant = 0;
-    for (int f = 0; f < h->cfg.n_outlier; ++f) {
-        const int t = h->cfg.outlier[f].type;
-        if (t == ICPMI_OUT_SURFACENORMAL || t == ICPMI_OUT_GENERICDESCRIPTOR || t == ICPMI_OUT_ROBUST || t == ICPMI_OUT_VARTRIMMEDDIST) together = false;
-        if (t == ICPMI_OUT_TRIMMEDDIST || t == ICPMI_OUT_MEDIANDIST) ++nquant;
-    }
-    if (nquant > 1) together = false;
-    if (h->cfg.var_dist) together = false; // (every reading needs its own row of radii)
+    bool together = batch > 1 && chain_takes_batch(h);
     for (int b = 0; b < batch; ++b) if (n[b] == 0 || n[b] > 0x7fffffff / ICPMI_MAX_K) together = false;
-    if (together) {
-        const GridParams& top = h->levels.g[h->levels.nlev - 1];
-        if (!std::isfinite(h->cfg.max_dist) || (top.cell - top.slack) <= h->cfg.max_dist) together = false; // would need the brute-force pass
-    }
     if (!together) {
         icpmi_status first = ICPMI_OK;
         for (int b = 0; b < batch; ++b) {
@@ -730,7 +738,86 @@ icpmi_status icpmi_register(icpmi_handle h, const float* scan4, int64_t n, const
     return register_impl(h, d_scan, n, d_n3, 0, T_out, stats);
 }
 
-// icpmi_residual_error*: the checks and the chain set-up of register_impl, then one matcher pass under T and the reduction (loop_residual)
+// icpmi_residual_error*: what the chain asks of a residual call whatever the pose -- the checks and the chain set-up of register_impl.
+// have_*: the one-shot rows the call consumed; *kind comes back as 1 or 2
+static icpmi_status residual_chain_setup(icpmi_handle h, const char* who, int64_t n, const float* d_n3, int64_t have_scalar_n, int64_t have_r2_n,
+                                         int32_t* kind_io, LoopCfg* lc_out, const float** d_r2row_out, bool* needs_rn_out)
+{
+    int32_t kind = *kind_io;
+    if (kind == ICPMI_RES_CHAIN) {
+        if (h->cfg.minimizer != ICPMI_MIN_POINT_TO_POINT && h->cfg.minimizer != ICPMI_MIN_POINT_TO_PLANE) {
+            h->last_error = std::string(who) + ": IdentityErrorMinimizer has no residual (name ICPMI_RES_POINT_TO_POINT or ICPMI_RES_POINT_TO_PLANE)";
+            return ICPMI_ERR_UNSUPPORTED;
+        }
+        kind = h->cfg.minimizer == ICPMI_MIN_POINT_TO_POINT ? ICPMI_RES_POINT_TO_POINT : ICPMI_RES_POINT_TO_PLANE;
+    }
+    *kind_io = kind;
+    if (kind == ICPMI_RES_POINT_TO_PLANE && !h->has_normals) {
+        h->last_error = "InvalidField: the point-to-plane residual needs the descriptor 'normals' on the map";
+        return ICPMI_ERR_MISSING_NORMALS;
+    }
+    bool needs_rn = false;
+    for (int f = 0; f < h->cfg.n_outlier; ++f) {
+        const icpmi_outlier& o = h->cfg.outlier[f];
+        needs_rn |= o.type == ICPMI_OUT_SURFACENORMAL;
+        if (o.type == ICPMI_OUT_ROBUST && (((o.iparam >> 4) & 15) == ICPMI_SCALE_BERG || (int)o.param2 > 0)) {
+            h->last_error = std::string(who) + ": RobustOutlierFilter with scaleEstimator berg or nbIterationForScale > 0 keeps its scale from one "
+                            "iteration of a registration to the next: no single pass can answer for it";
+            return ICPMI_ERR_UNSUPPORTED;
+        }
+    }
+    *needs_rn_out = needs_rn;
+    if (needs_rn && (!d_n3 || !h->has_normals)) {
+        h->last_error = "InvalidField: SurfaceNormalOutlierFilter needs 'normals' on both reading and map";
+        return ICPMI_ERR_MISSING_NORMALS;
+    }
+    { const icpmi_status es = check_ext_filters(h); if (es != ICPMI_OK) return es; }
+    LoopCfg lc = make_loop_cfg(h, 1);
+    {   // GenericDescriptorOutlierFilter{source: reading}: the row handed over for THIS reading (one shot)
+        bool wants = false;
+        for (int f = 0; f < h->cfg.n_outlier; ++f) wants |= h->cfg.outlier[f].type == ICPMI_OUT_GENERICDESCRIPTOR && (h->cfg.outlier[f].iparam & ICPMI_GEN_SOURCE_READING);
+        if (wants && n > 0 && have_scalar_n != n) {
+            h->last_error = "InvalidField: GenericDescriptorOutlierFilter{source: reading} needs the reading's descriptor (icpmi_set_reading_scalar, one row per point)";
+            return ICPMI_ERR_INVALID_ARG;
+        }
+        lc.read_scalar = wants ? h->d_read_scalar : nullptr;
+    }
+    *d_r2row_out = nullptr;
+    if (h->cfg.var_dist && n > 0) { // KDTreeVarDistMatcher: the radii handed over for THIS reading (one shot), as in register_impl
+        if (have_r2_n != n) {
+            h->last_error = "InvalidField: KDTreeVarDistMatcher needs the reading's maxDistField descriptor (icpmi_set_reading_max_dist, one radius per point)";
+            return ICPMI_ERR_INVALID_ARG;
+        }
+        if (!(h->read_r2_max > 0.f)) {
+            h->last_error = "InvalidParameter: KDTreeVarDistMatcher: the largest radius of the row must be > 0 (as maxDist)";
+            return ICPMI_ERR_INVALID_ARG;
+        }
+        set_search_bound(h, lc, h->read_r2_max);
+        *d_r2row_out = h->d_read_r2;
+    }
+    lc.sensor_noise = 0;
+    lc.has_read_normals = needs_rn ? 1 : 0;
+    *lc_out = lc;
+    if (n == 0) { // upstream: Trimmed / Median throw "no outlier to filter", otherwise "no point to minimize"
+        bool quant = false;
+        for (int f = 0; f < lc.n_out; ++f) quant |= lc.out_type[f] == ICPMI_OUT_TRIMMEDDIST || lc.out_type[f] == ICPMI_OUT_MEDIANDIST || lc.out_type[f] == ICPMI_OUT_VARTRIMMEDDIST;
+        h->last_error = quant ? "ConvergenceError: no outlier to filter" : "ConvergenceError: ErrorMinimizer: no point to minimize";
+        return quant ? ICPMI_ERR_NO_OUTLIER_TO_FILTER : ICPMI_ERR_NO_POINT_TO_MINIMIZE;
+    }
+    return ICPMI_OK;
+}
+
+// the pose in the centred frame: [R | t + R mu - mu]
+static void centred_pose(const icpmi_ctx* h, const float T[16], float Tc[16])
+{
+    memcpy(Tc, T, 16 * sizeof(float));
+    for (int r = 0; r < 3; ++r)
+        Tc[12 + r] = (float)(((double)T[12 + r] + (((double)T[r] * (double)h->mean[0] + (double)T[4 + r] * (double)h->mean[1]) + (double)T[8 + r] * (double)h->mean[2])) -
+                             (double)h->mean[r]);
+    Tc[3] = Tc[7] = Tc[11] = 0.f; Tc[15] = 1.f;
+}
+
+// ... then one matcher pass under T and the reduction (loop_residual)
 static icpmi_status residual_impl(icpmi_handle h, const char* who, const float* d_scan4, int64_t n, const float* d_n3, const float T[16], int32_t kind,
                                   icpmi_residual* out)
 {
@@ -749,73 +836,78 @@ static icpmi_status residual_impl(icpmi_handle h, const char* who, const float* 
     identity16(Tid);
     if (!T) T = Tid;
     { const icpmi_status rs = check_rigid(h, T); if (rs != ICPMI_OK) return rs; }
-    if (kind == ICPMI_RES_CHAIN) {
-        if (h->cfg.minimizer != ICPMI_MIN_POINT_TO_POINT && h->cfg.minimizer != ICPMI_MIN_POINT_TO_PLANE) {
-            h->last_error = std::string(who) + ": IdentityErrorMinimizer has no residual (name ICPMI_RES_POINT_TO_POINT or ICPMI_RES_POINT_TO_PLANE)";
-            return ICPMI_ERR_UNSUPPORTED;
-        }
-        kind = h->cfg.minimizer == ICPMI_MIN_POINT_TO_POINT ? ICPMI_RES_POINT_TO_POINT : ICPMI_RES_POINT_TO_PLANE;
-    }
-    if (kind == ICPMI_RES_POINT_TO_PLANE && !h->has_normals) {
-        h->last_error = "InvalidField: the point-to-plane residual needs the descriptor 'normals' on the map";
-        return ICPMI_ERR_MISSING_NORMALS;
-    }
-    bool needs_rn = false;
-    for (int f = 0; f < h->cfg.n_outlier; ++f) {
-        const icpmi_outlier& o = h->cfg.outlier[f];
-        needs_rn |= o.type == ICPMI_OUT_SURFACENORMAL;
-        if (o.type == ICPMI_OUT_ROBUST && (((o.iparam >> 4) & 15) == ICPMI_SCALE_BERG || (int)o.param2 > 0)) {
-            h->last_error = std::string(who) + ": RobustOutlierFilter with scaleEstimator berg or nbIterationForScale > 0 keeps its scale from one "
-                            "iteration of a registration to the next: no single pass can answer for it";
-            return ICPMI_ERR_UNSUPPORTED;
-        }
-    }
-    if (needs_rn && (!d_n3 || !h->has_normals)) {
-        h->last_error = "InvalidField: SurfaceNormalOutlierFilter needs 'normals' on both reading and map";
-        return ICPMI_ERR_MISSING_NORMALS;
-    }
-    { const icpmi_status es = check_ext_filters(h); if (es != ICPMI_OK) return es; }
-    LoopCfg lc = make_loop_cfg(h, 1);
-    {   // GenericDescriptorOutlierFilter{source: reading}: the row handed over for THIS reading (one shot)
-        bool wants = false;
-        for (int f = 0; f < h->cfg.n_outlier; ++f) wants |= h->cfg.outlier[f].type == ICPMI_OUT_GENERICDESCRIPTOR && (h->cfg.outlier[f].iparam & ICPMI_GEN_SOURCE_READING);
-        if (wants && n > 0 && have_scalar_n != n) {
-            h->last_error = "InvalidField: GenericDescriptorOutlierFilter{source: reading} needs the reading's descriptor (icpmi_set_reading_scalar, one row per point)";
-            return ICPMI_ERR_INVALID_ARG;
-        }
-        lc.read_scalar = wants ? h->d_read_scalar : nullptr;
-    }
+    LoopCfg lc;
     const float* d_r2row = nullptr;
-    if (h->cfg.var_dist && n > 0) { // KDTreeVarDistMatcher: the radii handed over for THIS reading (one shot), as in register_impl
-        if (have_r2_n != n) {
-            h->last_error = "InvalidField: KDTreeVarDistMatcher needs the reading's maxDistField descriptor (icpmi_set_reading_max_dist, one radius per point)";
-            return ICPMI_ERR_INVALID_ARG;
-        }
-        if (!(h->read_r2_max > 0.f)) {
-            h->last_error = "InvalidParameter: KDTreeVarDistMatcher: the largest radius of the row must be > 0 (as maxDist)";
-            return ICPMI_ERR_INVALID_ARG;
-        }
-        set_search_bound(h, lc, h->read_r2_max);
-        d_r2row = h->d_read_r2;
-    }
-    lc.sensor_noise = 0;
-    lc.has_read_normals = needs_rn ? 1 : 0;
-    if (n == 0) { // upstream: Trimmed / Median throw "no outlier to filter", otherwise "no point to minimize"
-        bool quant = false;
-        for (int f = 0; f < lc.n_out; ++f) quant |= lc.out_type[f] == ICPMI_OUT_TRIMMEDDIST || lc.out_type[f] == ICPMI_OUT_MEDIANDIST || lc.out_type[f] == ICPMI_OUT_VARTRIMMEDDIST;
-        h->last_error = quant ? "ConvergenceError: no outlier to filter" : "ConvergenceError: ErrorMinimizer: no point to minimize";
-        return quant ? ICPMI_ERR_NO_OUTLIER_TO_FILTER : ICPMI_ERR_NO_POINT_TO_MINIMIZE;
-    }
+    bool needs_rn = false;
+    { const icpmi_status cs = residual_chain_setup(h, who, n, d_n3, have_scalar_n, have_r2_n, &kind, &lc, &d_r2row, &needs_rn); if (cs != ICPMI_OK) return cs; }
     // centring, the padded normals and the tile order of the reading, as a registration's head prepares them
     { const icpmi_status ps = loop_prepare_reading(h, (const float4*)d_scan4, n, needs_rn ? d_n3 : nullptr); if (ps != ICPMI_OK) return ps; }
-    // the pose in the centred frame: [R | t + R mu - mu]
     float Tc[16];
-    memcpy(Tc, T, sizeof Tc);
-    for (int r = 0; r < 3; ++r)
-        Tc[12 + r] = (float)(((double)T[12 + r] + (((double)T[r] * (double)h->mean[0] + (double)T[4 + r] * (double)h->mean[1]) + (double)T[8 + r] * (double)h->mean[2])) -
-                             (double)h->mean[r]);
-    Tc[3] = Tc[7] = Tc[11] = 0.f; Tc[15] = 1.f;
+    centred_pose(h, T, Tc);
     return loop_residual(h, n, lc, Tc, kind, (h->cfg.force_2d != 0 || h->cfg.is_2d != 0) ? 1 : 0, d_r2row, out);
+}
+
+// icpmi_residual_error_poses*: the reading's checks once, then every rigid pose -- through the batched launches when the chain takes a
+// batch (loop_residual_poses), else one after the other through loop_residual on the reading prepared once
+static icpmi_status residual_poses_impl(icpmi_handle h, const char* who, const float* d_scan4, int64_t n, const float* d_n3, const float* T,
+                                        int32_t n_poses, int32_t kind, icpmi_residual* out, icpmi_status* status, int32_t* batched)
+{
+    const int64_t have_scalar_n = h->read_scalar_n, have_r2_n = h->read_r2_n;
+    h->read_scalar_n = 0; h->read_noise_n = 0; h->read_r2_n = 0;
+    if (batched) *batched = 0;
+    const bool range_ok = n_poses >= 1 && n_poses <= 4096;
+    // zeroed on every whole-call error.  (A count above the limit included: the caller vouches for n_poses entries either way -- a call
+    // that succeeds writes as many.)
+    const auto zero_all = [&] {
+        if (out && n_poses >= 1) memset(out, 0, sizeof(icpmi_residual) * (size_t)n_poses);
+        if (status && n_poses >= 1) memset(status, 0, sizeof(icpmi_status) * (size_t)n_poses);
+    };
+    zero_all();
+    if (!out || !T || !range_ok || n < 0 || (n > 0 && !d_scan4) || kind < ICPMI_RES_CHAIN || kind > ICPMI_RES_POINT_TO_PLANE) {
+        h->last_error = std::string(who) + ": bad arguments (1 <= n_poses <= 4096)"; return ICPMI_ERR_INVALID_ARG;
+    }
+    if (h->m <= 0) { h->last_error = std::string(who) + ": no map"; return ICPMI_ERR_INVALID_ARG; }
+    if (n > 0x7fffffff / ICPMI_MAX_K) { h->last_error = std::string(who) + ": too many points"; return ICPMI_ERR_UNSUPPORTED; }
+    LoopCfg lc;
+    const float* d_r2row = nullptr;
+    bool needs_rn = false;
+    { const icpmi_status cs = residual_chain_setup(h, who, n, d_n3, have_scalar_n, have_r2_n, &kind, &lc, &d_r2row, &needs_rn); if (cs != ICPMI_OK) return cs; }
+    const int planar = (h->cfg.force_2d != 0 || h->cfg.is_2d != 0) ? 1 : 0;
+    // per pose from here on
+    std::vector<icpmi_status> st((size_t)n_poses, ICPMI_OK);
+    std::vector<int> live;              // the rigid poses, in the caller's order
+    std::vector<float> Tc;              // ... in the centred frame
+    for (int p = 0; p < n_poses; ++p) {
+        out[p].trimmed_limit = -1.f;
+        st[(size_t)p] = check_rigid(h, T + 16 * (size_t)p);
+        if (st[(size_t)p] != ICPMI_OK) continue;
+        live.push_back(p);
+        Tc.resize(Tc.size() + 16);
+        centred_pose(h, T + 16 * (size_t)p, Tc.data() + Tc.size() - 16);
+    }
+    if (!live.empty() && chain_takes_batch(h)) {
+        std::vector<icpmi_residual> ro(live.size());
+        std::vector<icpmi_status> rs(live.size(), ICPMI_OK);
+        for (icpmi_residual& r : ro) { memset(&r, 0, sizeof r); r.trimmed_limit = -1.f; }
+        const icpmi_status ls = loop_residual_poses(h, (const float4*)d_scan4, n, lc, Tc.data(), (int)live.size(), kind, planar, ro.data(), rs.data());
+        if (ls != ICPMI_OK) { zero_all(); return ls; }
+        for (size_t i = 0; i < live.size(); ++i) { out[live[i]] = ro[i]; st[(size_t)live[i]] = rs[i]; }
+        if (batched) *batched = (int32_t)live.size();
+    } else if (!live.empty()) {
+        { const icpmi_status ps = loop_prepare_reading(h, (const float4*)d_scan4, n, needs_rn ? d_n3 : nullptr); if (ps != ICPMI_OK) { zero_all(); return ps; } }
+        for (size_t i = 0; i < live.size(); ++i) {
+            const icpmi_status s = loop_residual(h, n, lc, Tc.data() + 16 * i, kind, planar, d_r2row, out + live[i]);
+            if (s == ICPMI_ERR_HIP) { zero_all(); return s; }
+            st[(size_t)live[i]] = s;
+        }
+    }
+    icpmi_status first = ICPMI_OK;
+    for (int p = 0; p < n_poses; ++p) {
+        if (status) status[p] = st[(size_t)p];
+        if (st[(size_t)p] != ICPMI_OK && first == ICPMI_OK) first = st[(size_t)p];
+    }
+    if (first != ICPMI_OK) h->last_error = std::string(who) + ": a pose ended with an error (see the per-pose status)";
+    return status ? ICPMI_OK : first;
 }
 
 icpmi_status icpmi_residual_error_dev(icpmi_handle h, const float* d_scan4, int64_t n, const float* d_scan_normals3, const float T[16],
@@ -853,6 +945,109 @@ icpmi_status icpmi_residual_error_staged(icpmi_handle h, const float T[16], int3
     CHECK_H(h);
     if (h->scan_map_n <= 0) { h->last_error = "residual_error_staged: no scan staged by icpmi_register_prior"; return ICPMI_ERR_INVALID_ARG; }
     return residual_impl(h, "residual_error_staged", (const float*)h->d_scan_map.get(), h->scan_map_n, nullptr, T, kind, out);
+}
+
+icpmi_status icpmi_residual_error_poses_dev(icpmi_handle h, const float* d_scan4, int64_t n, const float* d_scan_normals3, const float* T,
+                                            int32_t n_poses, int32_t kind, icpmi_residual* out, icpmi_status* status, int32_t* batched)
+{
+    CHECK_H(h);
+    return residual_poses_impl(h, "residual_error_poses_dev", d_scan4, n, d_scan_normals3, T, n_poses, kind, out, status, batched);
+}
+
+icpmi_status icpmi_residual_error_poses(icpmi_handle h, const float* scan4, int64_t n, const float* scan_normals3, const float* T,
+                                        int32_t n_poses, int32_t kind, icpmi_residual* out, icpmi_status* status, int32_t* batched)
+{
+    CHECK_H(h);
+    const auto zero_all = [&] { // (a whole-call error leaves out and status zeroed: these returns come before residual_poses_impl does it)
+        if (out && n_poses >= 1) memset(out, 0, sizeof(icpmi_residual) * (size_t)n_poses);
+        if (status && n_poses >= 1) memset(status, 0, sizeof(icpmi_status) * (size_t)n_poses);
+        if (batched) *batched = 0;
+    };
+    const float* d_scan = scan4; // (n == 0, no map or bad arguments: never dereferenced)
+    const float* d_n3 = nullptr;
+    if (n > 0 && scan4 && h->m > 0) { // staged through the operator scratch, as icpmi_residual_error: once for all poses
+        float4* d_in = scratch_get<float4>(h, 8, (size_t)n);
+        if (!d_in) { zero_all(); return ICPMI_ERR_HIP; }
+        if (hipMemcpyAsync(d_in, scan4, (size_t)n * sizeof(float4), hipMemcpyHostToDevice, h->stream) != hipSuccess) { zero_all(); h->last_error = "residual_error_poses: the upload failed"; return ICPMI_ERR_HIP; }
+        d_scan = (const float*)d_in;
+        if (scan_normals3) {
+            float* d_n = scratch_get<float>(h, 9, (size_t)n * 3);
+            if (!d_n) { zero_all(); return ICPMI_ERR_HIP; }
+            if (hipMemcpyAsync(d_n, scan_normals3, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, h->stream) != hipSuccess) { zero_all(); h->last_error = "residual_error_poses: the upload failed"; return ICPMI_ERR_HIP; }
+            d_n3 = d_n;
+        }
+    }
+    return residual_poses_impl(h, "residual_error_poses", d_scan, n, d_n3, T, n_poses, kind, out, status, batched);
+}
+
+icpmi_status icpmi_register_multistart_dev(icpmi_handle h, const float* d_scan4, int64_t n, const float* priors, int32_t n_starts,
+                                           int32_t fixed_iterations, float* T_out, icpmi_stats* stats, icpmi_status* status)
+{
+    CHECK_H(h);
+    if (n_starts < 1 || n_starts > ICPMI_MAX_BATCH || n < 0 || (n > 0 && !d_scan4) || !priors || !T_out || fixed_iterations < 0) {
+        h->last_error = "register_multistart: bad arguments (1 <= n_starts <= 16)"; return ICPMI_ERR_INVALID_ARG;
+    }
+    h->scan_map_n = 0; // (the slices below reuse the stage of icpmi_register_prior: nothing is left staged)
+    const int64_t NS = (n + 63) / 64 * 64;
+    if (h->d_scan_map.ensure(h, (size_t)NS * n_starts + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
+    icpmi_status st[ICPMI_MAX_BATCH];
+    int idx[ICPMI_MAX_BATCH], nlive = 0;
+    for (int s = 0; s < n_starts; ++s) {
+        identity16(T_out + 16 * s);
+        if (stats) { memset(stats + s, 0, sizeof(icpmi_stats)); stats[s].sensor_noise_overlap = -1.f; }
+        st[s] = check_rigid(h, priors + 16 * s);
+        if (st[s] == ICPMI_OK) idx[nlive++] = s;
+    }
+    if (nlive > 1 && n > 0 && n <= 0x7fffffff / ICPMI_MAX_K && chain_takes_batch(h)) {
+        // one slice per start, one loop for all of them
+        const float* ptrs[ICPMI_MAX_BATCH];
+        int64_t ns[ICPMI_MAX_BATCH];
+        for (int i = 0; i < nlive; ++i) {
+            float4* slice = h->d_scan_map.get() + (size_t)i * NS;
+            const icpmi_status ts = ops_transform_dev(h, priors + 16 * idx[i], (const float4*)d_scan4, n, slice); // Mapper.cpp:197, once per start
+            if (ts != ICPMI_OK) return ts;
+            ptrs[i] = (const float*)slice; ns[i] = n;
+        }
+        float Tl[16 * ICPMI_MAX_BATCH];
+        icpmi_stats sl[ICPMI_MAX_BATCH];
+        icpmi_status stl[ICPMI_MAX_BATCH];
+        const icpmi_status bs = icpmi_register_batch_dev(h, nlive, ptrs, ns, fixed_iterations, Tl, sl, stl);
+        if (bs != ICPMI_OK) return bs;
+        for (int i = 0; i < nlive; ++i) {
+            memcpy(T_out + 16 * idx[i], Tl + 16 * i, 16 * sizeof(float));
+            if (stats) stats[idx[i]] = sl[i];
+            st[idx[i]] = stl[i];
+        }
+    } else {
+        // a chain the batch does not serve: start after start through the ONE buffer icpmi_register_prior_dev uses, so that the loop's
+        // cached graphs (keyed by the scan's address) serve every start
+        for (int i = 0; i < nlive; ++i) {
+            const int s = idx[i];
+            st[s] = ops_transform_dev(h, priors + 16 * s, (const float4*)d_scan4, n, h->d_scan_map);
+            if (st[s] == ICPMI_OK) st[s] = register_impl(h, (const float*)h->d_scan_map.get(), n, nullptr, fixed_iterations, T_out + 16 * s, stats ? stats + s : nullptr);
+            if (st[s] == ICPMI_ERR_HIP) return st[s];
+        }
+    }
+    h->cov_ready = false; // (no covariance per start, as after any batch)
+    icpmi_status first = ICPMI_OK;
+    for (int s = 0; s < n_starts; ++s) {
+        if (status) status[s] = st[s];
+        if (st[s] != ICPMI_OK && first == ICPMI_OK) first = st[s];
+    }
+    if (first != ICPMI_OK) h->last_error = "register_multistart: a start ended with an error (see the per-start status)";
+    return status ? ICPMI_OK : first;
+}
+
+icpmi_status icpmi_register_multistart(icpmi_handle h, const float* scan4, int64_t n, const float* priors, int32_t n_starts,
+                                       int32_t fixed_iterations, float* T_out, icpmi_stats* stats, icpmi_status* status)
+{
+    CHECK_H(h);
+    if (n < 0 || (n > 0 && !scan4)) { h->last_error = "register_multistart: bad arguments"; return ICPMI_ERR_INVALID_ARG; }
+    if (n > 0) { // one upload, as icpmi_register_prior
+        if (h->d_stage_in.ensure(h, (size_t)n + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
+        HIP_TRY(h, hipMemcpyAsync(h->d_stage_in, scan4, (size_t)n * sizeof(float4), hipMemcpyHostToDevice, h->stream));
+    }
+    return icpmi_register_multistart_dev(h, n > 0 ? (const float*)h->d_stage_in.get() : nullptr, n, priors, n_starts, fixed_iterations, T_out, stats, status);
 }
 
 icpmi_status icpmi_transform(icpmi_handle h, const float T[16], const float* in4, int64_t n, float* out4, const float* in_normals3,

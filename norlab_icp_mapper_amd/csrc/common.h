@@ -1078,6 +1078,10 @@ icpmi_status loop_single_step(icpmi_ctx* c, int64_t n, const LoopCfg& lc, const 
 // getResidualError() of the centred reading in c->d_reading under the centred-frame pose T (host, column-major); kind 1 / 2
 icpmi_status loop_residual(icpmi_ctx* c, int64_t n, const LoopCfg& lc, const float T[16], int kind, int planar, const float* d_r2row,
                            icpmi_residual* out);
+// ... of the raw reading d_scan under n_poses centred-frame poses (16 floats each) through batched launches (blockIdx.y = pose); centres and
+// sorts the reading itself, once.  out[p] arrives initialised; status[p] = what loop_residual would return for pose p
+icpmi_status loop_residual_poses(icpmi_ctx* c, const float4* d_scan, int64_t n, const LoopCfg& lc, const float* T, int n_poses, int kind, int planar,
+                                 icpmi_residual* out, icpmi_status* status);
 icpmi_status loop_outlier_weights(icpmi_ctx* c, const LoopCfg& lc, const float* d2, const int32_t* ids, int k, int64_t n,
                                   const float* read_normals3, float* weights, float* limit_out);
 LoopCfg make_loop_cfg(const icpmi_ctx* c, int fixed_iterations);

@@ -9,6 +9,7 @@
 #include "common.h"
 #include "solve.h"
 #include <cstring>
+#include <vector>
 
 namespace {
 
@@ -902,11 +903,14 @@ __global__ __launch_bounds__(256) void pad_normals_kernel(const float* __restric
     out[i] = make_float4(n3[3 * i], n3[3 * i + 1], n3[3 * i + 2], 0.f);
 }
 
-__global__ void init_state_kernel(IcpState* st, const float* T0, unsigned seq, unsigned* progress, const unsigned* seq_src = nullptr)
+// T0_stride: floats between the start poses of the readings (0: every reading starts from the one T0; 16: a table, one pose per reading)
+__global__ void init_state_kernel(IcpState* st, const float* T0, unsigned seq, unsigned* progress, const unsigned* seq_src = nullptr,
+                                  int T0_stride = 0)
 {
     if (threadIdx.x != 0) return;
     st[blockIdx.x].t_start = (unsigned long long)wall_clock64(); // (a head that is not folded into the query sort: this kernel stands for its start)
-    init_state_dev(st + blockIdx.x, T0, seq, progress ? progress + blockIdx.x : nullptr, seq_src); // one state per reading of a batch
+    init_state_dev(st + blockIdx.x, T0 ? T0 + (size_t)blockIdx.x * T0_stride : nullptr, seq, progress ? progress + blockIdx.x : nullptr,
+                   seq_src); // one state per reading of a batch
 }
 
 __global__ __launch_bounds__(256) void weights_kernel(int64_t count, LoopCfg lc, const IcpState* __restrict__ st,
@@ -2063,7 +2067,9 @@ struct ResBlock { double sum_abs, sum_sq, weight_sum; long long pairs; float max
 
 // fused_slot >= 0: the chain's one quantile filter went through the fused selection, whose last level the pair-sum kernel of an iteration
 // resolves -- here every workgroup does (the same lookup, the same limit)
-__global__ __launch_bounds__(256) void res_pairs_kernel(const float4* __restrict__ reading, const int* __restrict__ qindex, int n, LoopCfg lc,
+// blockIdx.y = pose of a batch (icpmi_residual_error_poses: one slice of the per-query arrays, one IcpState, one set of histograms and one
+// row of ICPMI_RES_NB partials per pose); a single call is the batch of one, so a pose is scored to the same bits alone or among others
+__global__ __launch_bounds__(256) void res_pairs_kernel(const float4* __restrict__ reading, const int* __restrict__ qindex, BatchArgs ba, LoopCfg lc,
                                                         int kind, int planar, IcpState* __restrict__ st, const float4* __restrict__ map,
                                                         const float4* __restrict__ ref_normals, const float4* __restrict__ read_normals,
                                                         const float* __restrict__ ref_scalar, const int* __restrict__ sidx,
@@ -2071,6 +2077,16 @@ __global__ __launch_bounds__(256) void res_pairs_kernel(const float4* __restrict
                                                         const unsigned* __restrict__ hists, int fused_slot, int is_median, float factor,
                                                         double* __restrict__ partial)
 {
+    const int n = ba.n[blockIdx.y];
+    {
+        const size_t qo = (size_t)blockIdx.y * (size_t)ba.qstride;
+        reading += qo; sidx += qo * lc.k; d2a += qo * lc.k;
+        if (qindex) qindex += qo;
+        if (match_pt) match_pt += qo;
+        hists += (size_t)blockIdx.y * ICPMI_SELHIST_WORDS;
+        partial += (size_t)blockIdx.y * (ICPMI_RES_NB * ICPMI_RES_NV);
+        st += blockIdx.y;
+    }
     __shared__ unsigned shsel[16];
     __shared__ double sh[4][ICPMI_RES_NV];
     float fused_limit = 0.f;
@@ -2132,9 +2148,13 @@ __global__ __launch_bounds__(256) void res_pairs_kernel(const float4* __restrict
     }
 }
 
+// blockIdx.x = pose of a batch: its row of partials, its IcpState, its ResBlock
 __global__ __launch_bounds__(64) void res_finish_kernel(const double* __restrict__ partial, const IcpState* __restrict__ st, int limit_slot,
                                                         ResBlock* __restrict__ out)
 {
+    partial += (size_t)blockIdx.x * (ICPMI_RES_NB * ICPMI_RES_NV);
+    st += blockIdx.x;
+    out += blockIdx.x;
     __shared__ double part[ICPMI_RES_NV][ICPMI_RES_CH];
     if (threadIdx.x < ICPMI_RES_NV * ICPMI_RES_CH) {
         // every load issued before the first add (cov_solve_kernel)
@@ -2166,6 +2186,22 @@ __global__ __launch_bounds__(64) void res_finish_kernel(const double* __restrict
 }
 static_assert(ICPMI_RES_NB % ICPMI_RES_CH == 0 && ICPMI_RES_NV * ICPMI_RES_CH <= 64, "pass 2 of the residual: one wave, whole chunks");
 
+// what a call answers from a pose's result block: the convergence errors of a registration's first iteration, or the residual
+static icpmi_status res_block_out(icpmi_ctx* c, const ResBlock& hr, int k, int64_t n, int kind, icpmi_residual* out)
+{
+    if (hr.error) {
+        c->last_error = hr.error == ICPMI_ERR_NO_OUTLIER_TO_FILTER ? "ConvergenceError: no outlier to filter" : "residual_error: device-side convergence error";
+        return (icpmi_status)hr.error;
+    }
+    if (hr.pairs <= 0) { c->last_error = "ConvergenceError: ErrorMinimizer: no point to minimize"; return ICPMI_ERR_NO_POINT_TO_MINIMIZE; }
+    out->sum_abs = hr.sum_abs; out->sum_sq = hr.sum_sq; out->max_abs = hr.max_abs;
+    out->weight_sum = hr.weight_sum; out->pairs = hr.pairs;
+    out->weighted_point_used_ratio = (float)(hr.weight_sum / ((double)k * (double)n));
+    out->trimmed_limit = hr.limit;
+    out->kind = kind;
+    return ICPMI_OK;
+}
+
 // the centred reading is in c->d_reading (loop_prepare_reading); T_host = the pose in the centred frame (column-major), kind 1 or 2
 icpmi_status loop_residual(icpmi_ctx* c, int64_t n, const LoopCfg& lc, const float T_host[16], int kind, int planar, const float* d_r2row,
                            icpmi_residual* out)
@@ -2196,7 +2232,7 @@ icpmi_status loop_residual(icpmi_ctx* c, int64_t n, const LoopCfg& lc, const flo
         if (l1.out_type[f] == ICPMI_OUT_TRIMMEDDIST || l1.out_type[f] == ICPMI_OUT_MEDIANDIST || l1.out_type[f] == ICPMI_OUT_VARTRIMMEDDIST) limit_slot = f;
     const bool sorted = nn.out_sorted;
     hipLaunchKernelGGL(res_pairs_kernel, dim3(ICPMI_RES_NB), dim3(256), 0, c->stream, sorted ? (const float4*)c->d_qsorted : (const float4*)c->d_reading,
-                       sorted ? (const int*)c->d_qindex : (const int*)nullptr, (int)n, l1, kind, planar, c->d_state, (const float4*)c->d_map_sorted,
+                       sorted ? (const int*)c->d_qindex : (const int*)nullptr, batch_of_one(n), l1, kind, planar, c->d_state, (const float4*)c->d_map_sorted,
                        c->has_normals ? (const float4*)c->d_normals_sorted : (const float4*)nullptr,
                        l1.has_read_normals ? (const float4*)c->d_read_normals : (const float4*)nullptr,
                        (l1.ext && c->raw_has_scalar) ? (const float*)c->d_raw_s : (const float*)nullptr, (const int*)c->d_sidx, (const float*)c->d_d2,
@@ -2207,16 +2243,81 @@ icpmi_status loop_residual(icpmi_ctx* c, int64_t n, const LoopCfg& lc, const flo
     ResBlock hr;
     if (read_back(c, &hr, d_res, sizeof hr) != ICPMI_OK) return ICPMI_ERR_HIP;
     c->cov_kept = cov_keep; // (the matcher's launch dropped last_match_n: icpmi_debug_last_matches has nothing to read any more)
-    if (hr.error) {
-        c->last_error = hr.error == ICPMI_ERR_NO_OUTLIER_TO_FILTER ? "ConvergenceError: no outlier to filter" : "residual_error: device-side convergence error";
-        return (icpmi_status)hr.error;
+    return res_block_out(c, hr, l1.k, n, kind, out);
+}
+
+// slices 1 .. gridDim.y of the tile-sorted reading and its index row from slice 0 (the pose batch: one reading, centred and sorted once)
+__global__ __launch_bounds__(256) void res_replicate_kernel(float4* __restrict__ qsorted, int* __restrict__ qindex, int n, int qstride)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const size_t o = (size_t)(blockIdx.y + 1) * (size_t)qstride + i;
+    qsorted[o] = qsorted[i];
+    qindex[o] = qindex[i];
+}
+
+// icpmi_residual_error_poses on the batched route (api.hip decides which chains take it: the ones icpmi_register_batch_dev runs together).
+// The centred reading of n points is in c->d_reading (nothing prepared yet: this function centres and sorts it once, after its
+// allocations); T_host = n_poses poses in the centred frame.  Chunks of up to ICPMI_MAX_BATCH poses go through the launches of
+// loop_residual with blockIdx.y = pose, back to back; one read-back of the n_poses result blocks ends the call.
+icpmi_status loop_residual_poses(icpmi_ctx* c, const float4* d_scan, int64_t n, const LoopCfg& lc, const float* T_host, int n_poses, int kind,
+                                 int planar, icpmi_residual* out, icpmi_status* status)
+{
+    const bool cov_keep = c->cov_ready && (c->last_match_n != 0 || c->cov_kept);
+    const int B = n_poses < ICPMI_MAX_BATCH ? n_poses : ICPMI_MAX_BATCH;
+    const int64_t NS = (n + 63) / 64 * 64; // slice stride of the per-query arrays, as loop_run_batch
+    // all allocations before the first launch (a later one could move the sorted reading)
+    if (ensure_loop_buffers(c, NS, lc.k, B) != ICPMI_OK) return ICPMI_ERR_HIP;
+    if (c->d_reading.ensure(c, (size_t)n + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
+    if (sort_queries_reserve(c, NS, B) != ICPMI_OK) return ICPMI_ERR_HIP;
+    // scratch 5: the partials of one chunk, then per pose its result block and its pose
+    constexpr size_t RES_DOUBLES = (sizeof(ResBlock) + sizeof(double) - 1) / sizeof(double);
+    static_assert(sizeof(ResBlock) % sizeof(double) == 0, "an array of result blocks behind the partials");
+    const size_t part_doubles = (size_t)B * ICPMI_RES_NB * ICPMI_RES_NV;
+    double* d_part = scratch_get<double>(c, 5, part_doubles + (size_t)n_poses * (RES_DOUBLES + 8) + 8);
+    if (!d_part) return ICPMI_ERR_HIP;
+    ResBlock* d_res = reinterpret_cast<ResBlock*>(d_part + part_doubles);
+    float* d_T = reinterpret_cast<float*>(d_part + part_doubles + (size_t)n_poses * RES_DOUBLES);
+    std::vector<ResBlock> hr((size_t)n_poses);
+
+    { const icpmi_status ps = loop_prepare_reading(c, d_scan, n, nullptr); if (ps != ICPMI_OK) return ps; }
+    HIP_TRY(c, hipMemcpyAsync(d_T, T_host, (size_t)n_poses * 16 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    if (B > 1)
+        hipLaunchKernelGGL(res_replicate_kernel, dim3((int)((n + 255) / 256), B - 1), dim3(256), 0, c->stream, c->d_qsorted.get(), c->d_qindex.get(),
+                           (int)n, (int)NS);
+    LoopCfg l1 = lc;
+    l1.max_iter = 1; l1.use_diff = 0; l1.use_bound = 0;
+    const int slot = fused_filter_slot(l1);
+    int limit_slot = -1;
+    for (int f = 0; f < l1.n_out; ++f)
+        if (l1.out_type[f] == ICPMI_OUT_TRIMMEDDIST || l1.out_type[f] == ICPMI_OUT_MEDIANDIST || l1.out_type[f] == ICPMI_OUT_VARTRIMMEDDIST) limit_slot = f;
+    for (int p0 = 0; p0 < n_poses; p0 += B) {
+        const int Bc = n_poses - p0 < B ? n_poses - p0 : B;
+        BatchArgs ba; memset(&ba, 0, sizeof ba);
+        ba.nscan = Bc; ba.qstride = Bc > 1 ? (int)NS : 0;
+        for (int b = 0; b < Bc; ++b) ba.n[b] = (int)n;
+        hipLaunchKernelGGL(init_state_kernel, dim3(Bc), dim3(64), 0, c->stream, c->d_state, (const float*)(d_T + 16 * (size_t)p0), 0u, (unsigned*)nullptr,
+                           (const unsigned*)nullptr, 16);
+        HIP_TRY(c, hipMemsetAsync(c->d_selhist, 0, (size_t)ICPMI_SELHIST_WORDS * Bc * sizeof(unsigned), c->stream));
+        NnRequest req = loop_request(c, l1, ba, nullptr); // (iter 0: what a registration's first iteration asks of the matcher)
+        NnOutcome nn;
+        const icpmi_status s = nn_launch_k(c, req, c->d_reading, n, c->d_state->T_iter, l1, 1, c->d_sidx, c->d_d2, c->d_state, &nn);
+        if (s != ICPMI_OK) return s;
+        enqueue_selection(c, l1, n * l1.k, ba, nn);
+        const bool sorted = nn.out_sorted;
+        hipLaunchKernelGGL(res_pairs_kernel, dim3(ICPMI_RES_NB, Bc), dim3(256), 0, c->stream, sorted ? (const float4*)c->d_qsorted : (const float4*)c->d_reading,
+                           sorted ? (const int*)c->d_qindex : (const int*)nullptr, ba, l1, kind, planar, c->d_state, (const float4*)c->d_map_sorted,
+                           c->has_normals ? (const float4*)c->d_normals_sorted : (const float4*)nullptr,
+                           l1.has_read_normals ? (const float4*)c->d_read_normals : (const float4*)nullptr,
+                           (l1.ext && c->raw_has_scalar) ? (const float*)c->d_raw_s : (const float*)nullptr, (const int*)c->d_sidx, (const float*)c->d_d2, (sorted && l1.k == 1) ? (const float4*)c->d_match_pt : (const float4*)nullptr,
+                           (const unsigned*)c->d_selhist, slot >= 0 ? slot : -1, (slot >= 0 && l1.out_type[slot] == ICPMI_OUT_MEDIANDIST) ? 1 : 0,
+                           slot >= 0 ? l1.out_param[slot] : 0.f, d_part);
+        hipLaunchKernelGGL(res_finish_kernel, dim3(Bc), dim3(64), 0, c->stream, (const double*)d_part, (const IcpState*)c->d_state, limit_slot, d_res + p0);
+        HIP_TRY(c, hipGetLastError());
     }
-    if (hr.pairs <= 0) { c->last_error = "ConvergenceError: ErrorMinimizer: no point to minimize"; return ICPMI_ERR_NO_POINT_TO_MINIMIZE; }
-    out->sum_abs = hr.sum_abs; out->sum_sq = hr.sum_sq; out->max_abs = hr.max_abs;
-    out->weight_sum = hr.weight_sum; out->pairs = hr.pairs;
-    out->weighted_point_used_ratio = (float)(hr.weight_sum / ((double)l1.k * (double)n));
-    out->trimmed_limit = hr.limit;
-    out->kind = kind;
+    if (read_back(c, hr.data(), d_res, sizeof(ResBlock) * (size_t)n_poses) != ICPMI_OK) return ICPMI_ERR_HIP;
+    c->cov_kept = cov_keep;
+    for (int p = 0; p < n_poses; ++p) status[p] = res_block_out(c, hr[(size_t)p], l1.k, n, kind, out + p);
     return ICPMI_OK;
 }
 

@@ -505,6 +505,142 @@ icpmi_residual GpuICPSequence::residualStaged(const Mat4& T, int kind) const
     return out;
 }
 
+// ---- relocalisation ----------------------------------------------------------------------------
+std::vector<int> rankCandidates(const PoseScores& scores, size_t n, float minPairsRatio)
+{
+    const double need = (double)minPairsRatio * (double)n;
+    std::vector<std::pair<double, int>> keyed;
+    for (size_t i = 0; i < scores.size(); ++i) {
+        const icpmi_residual& r = scores.residual[i];
+        if (scores.status[i] != ICPMI_OK || r.pairs <= 0 || (double)r.pairs < need) continue;
+        keyed.emplace_back(r.sum_abs / (double)r.pairs, (int)i);
+    }
+    std::sort(keyed.begin(), keyed.end()); // (the index breaks ties)
+    std::vector<int> order;
+    for (const auto& kv : keyed) order.push_back(kv.second);
+    return order;
+}
+
+std::vector<Mat4> candidateGrid(const Mat4& centre, float halfX, float halfY, float halfYaw, int stepsX, int stepsY, int stepsYaw)
+{
+    if (stepsX < 0 || stepsY < 0 || stepsYaw < 0) throw InvalidParameter("candidateGrid: steps must be >= 0");
+    auto off = [](float half, int k, int steps) { return steps == 0 ? 0.0 : (double)half * (double)k / (double)steps; };
+    std::vector<Mat4> out;
+    out.push_back(centre);
+    for (int ia = -stepsYaw; ia <= stepsYaw; ++ia) {
+        const double a = off(halfYaw, ia, stepsYaw);
+        const double ca = std::cos(a), sa = std::sin(a);
+        const double Rz[3][3] = {{ca, -sa, 0.0}, {sa, ca, 0.0}, {0.0, 0.0, 1.0}};
+        for (int iy = -stepsY; iy <= stepsY; ++iy)
+            for (int ix = -stepsX; ix <= stepsX; ++ix) {
+                if (ia == 0 && iy == 0 && ix == 0) continue;
+                Mat4 c = centre;
+                for (int r = 0; r < 3; ++r)
+                    for (int col = 0; col < 3; ++col)
+                        c(r, col) = (float)((Rz[r][0] * (double)centre(0, col) + Rz[r][1] * (double)centre(1, col)) + Rz[r][2] * (double)centre(2, col));
+                c(0, 3) = (float)((double)centre(0, 3) + off(halfX, ix, stepsX));
+                c(1, 3) = (float)((double)centre(1, 3) + off(halfY, iy, stepsY));
+                out.push_back(c);
+            }
+    }
+    return out;
+}
+
+PoseScores GpuICPSequence::residualsFiltered(const DataPoints& reading, const std::vector<Mat4>& poses, int kind) const
+{
+    const float* normals = nullptr;
+    if (reading.descriptorExists("normals") && reading.getDescriptorByName("normals").span == 3)
+        normals = reading.getDescriptorByName("normals").data.data();
+    if (!genericReadDescName.empty()) { // GenericDescriptorOutlierFilter{source: reading}: one row for all poses
+        if (!reading.descriptorExists(genericReadDescName) || reading.getDescriptorByName(genericReadDescName).span != 1)
+            throw InvalidField("GenericDescriptorOutlierFilter: the reading has no 1-row descriptor " + genericReadDescName);
+        check(h, icpmi_set_reading_scalar(h, reading.getDescriptorByName(genericReadDescName).data.data(), (int64_t)reading.getNbPoints()));
+    }
+    if (!maxDistFieldName.empty()) { // KDTreeVarDistMatcher: the radii of the FILTERED reading (one shot, for all poses)
+        if (!reading.descriptorExists(maxDistFieldName) || reading.getDescriptorByName(maxDistFieldName).span != 1)
+            throw InvalidField("KDTreeVarDistMatcher: the reading has no 1-row descriptor " + maxDistFieldName);
+        check(h, icpmi_set_reading_max_dist(h, reading.getDescriptorByName(maxDistFieldName).data.data(), (int64_t)reading.getNbPoints()));
+    }
+    PoseScores out;
+    out.residual.assign(poses.size(), icpmi_residual{});
+    out.status.assign(poses.size(), ICPMI_OK);
+    std::vector<float> T(16 * poses.size());
+    for (size_t p = 0; p < poses.size(); ++p) std::copy(poses[p].m.begin(), poses[p].m.end(), T.begin() + 16 * p);
+    int32_t batched = 0;
+    check(h, icpmi_residual_error_poses(h, reading.features.data(), (int64_t)reading.getNbPoints(), normals, T.data(), (int32_t)poses.size(), kind,
+                                        out.residual.data(), out.status.data(), &batched));
+    out.batched = batched;
+    return out;
+}
+
+PoseScores GpuICPSequence::residuals(const DataPoints& readingIn, const std::vector<Mat4>& poses, int kind) const
+{
+    if (!hasReadingFilters()) return residualsFiltered(readingIn, poses, kind);
+    return residualsFiltered(filteredReading(readingIn), poses, kind);
+}
+
+// icpmi_register_multistart carries the points alone, as icpmi_register_prior does: a chain that reads the reading's normals or one of its
+// descriptor rows cannot go through it (Mapper::processInput keeps such chains off the prior path for the same reason)
+void GpuICPSequence::requireBareReadingChain(const char* who) const
+{
+    if (chainNeedsReadingNormals())
+        throw InvalidParameter(std::string(who) + ": the chain's SurfaceNormalOutlierFilter reads the reading's normals, which the multistart registration does not carry");
+    if (readsReadingDescriptor())
+        throw InvalidParameter(std::string(who) + ": the chain reads a descriptor row of the reading (" +
+                               (!genericReadDescName.empty() ? genericReadDescName : maxDistFieldName) + "), which the multistart registration does not carry");
+}
+
+MultiStartResult GpuICPSequence::multiStartFiltered(const DataPoints& reading, const std::vector<Mat4>& priors)
+{
+    requireBareReadingChain("registerMultiStart");
+    MultiStartResult out;
+    out.correction.assign(priors.size(), Mat4::identity());
+    out.stats.assign(priors.size(), icpmi_stats{});
+    out.status.assign(priors.size(), ICPMI_OK);
+    std::vector<float> P(16 * priors.size()), T(16 * priors.size());
+    for (size_t s = 0; s < priors.size(); ++s) std::copy(priors[s].m.begin(), priors[s].m.end(), P.begin() + 16 * s);
+    stagedPoints = 0;
+    haveCovariance = false;
+    check(h, icpmi_register_multistart(h, reading.features.data(), (int64_t)reading.getNbPoints(), P.data(), (int32_t)priors.size(), 0, T.data(),
+                                       out.stats.data(), out.status.data()));
+    for (size_t s = 0; s < priors.size(); ++s) std::copy(T.begin() + 16 * s, T.begin() + 16 * s + 16, out.correction[s].m.begin());
+    return out;
+}
+
+MultiStartResult GpuICPSequence::registerMultiStart(const DataPoints& readingIn, const std::vector<Mat4>& priors)
+{
+    if (!hasReadingFilters()) return multiStartFiltered(readingIn, priors);
+    return multiStartFiltered(filteredReading(readingIn), priors);
+}
+
+Relocalization GpuICPSequence::relocalize(const DataPoints& readingIn, const std::vector<Mat4>& candidates, const RelocalizeOptions& options)
+{
+    if (candidates.empty()) throw InvalidParameter("relocalize: no candidates");
+    requireBareReadingChain("relocalize"); // (before anything is scored: the refinement could not run)
+    DataPoints owned;
+    if (hasReadingFilters()) owned = filteredReading(readingIn); // once for the three passes
+    const DataPoints& reading = hasReadingFilters() ? owned : readingIn;
+    const size_t n = reading.getNbPoints();
+    Relocalization out;
+    out.scores = residualsFiltered(reading, candidates, options.kind);
+    const std::vector<int> order = rankCandidates(out.scores, n, options.minPairsRatio);
+    if (order.empty()) throw ConvergenceError("relocalize: no candidate survived the scoring");
+    const size_t k = std::min<size_t>(order.size(), (size_t)std::max(1, std::min(options.refine, 16)));
+    std::vector<Mat4> best(k), refined(k);
+    for (size_t i = 0; i < k; ++i) best[i] = candidates[(size_t)order[i]];
+    const MultiStartResult ms = multiStartFiltered(reading, best);
+    for (size_t i = 0; i < k; ++i) refined[i] = ms.correction[i] * best[i];
+    PoseScores again = residualsFiltered(reading, refined, options.kind);
+    for (size_t i = 0; i < k; ++i) if (ms.status[i] != ICPMI_OK) again.status[i] = ms.status[i]; // a start that did not converge is out
+    const std::vector<int> fin = rankCandidates(again, n, options.minPairsRatio);
+    if (fin.empty()) throw ConvergenceError("relocalize: no refined candidate survived the scoring");
+    const size_t w = (size_t)fin[0];
+    out.pose = refined[w];
+    out.residual = again.residual[w];
+    out.index = order[w];
+    return out;
+}
+
 float GpuICPSequence::ErrorMinimizerView::getResidualError(const DataPoints& reading, const Mat4& T) const
 {
     return (float)owner->residual(reading, T).sum_abs;

@@ -30,6 +30,39 @@ std::pair<std::string, yaml::Node> singleEntry(const yaml::Node& n, const std::s
 // KDTreeVarDistMatcher (default maxSearchDist), empty for KDTreeMatcher.  Needs no GPU.
 void parseMatcher(const yaml::Node& matcher, icpmi_config& cfg, std::string& maxDistField);
 
+// ---- relocalisation: one reading under many poses (include/icpmi.h: icpmi_residual_error_poses, icpmi_register_multistart) ----
+// one icpmi_residual and one status per pose (a pose whose status is not ICPMI_OK keeps an empty residual); batched = the poses that
+// went through the batched launches
+struct PoseScores {
+    std::vector<icpmi_residual> residual;
+    std::vector<icpmi_status> status;
+    int batched = 0;
+    size_t size() const { return residual.size(); }
+};
+struct MultiStartResult {
+    std::vector<Mat4> correction;       // per start, as registerWithPrior alone (identity where the status is not ICPMI_OK)
+    std::vector<icpmi_stats> stats;
+    std::vector<icpmi_status> status;
+};
+struct RelocalizeOptions {
+    float minPairsRatio = 0.5f;         // a candidate needs pairs >= minPairsRatio * N
+    int refine = 4;                     // how many of the best candidates are refined (at most 16)
+    int kind = ICPMI_RES_CHAIN;
+};
+struct Relocalization {
+    Mat4 pose = Mat4::identity();       // the winner's corrected pose: correction * candidate
+    icpmi_residual residual{};          // ... scored under it
+    int index = -1;                     // ... its index among the candidates
+    PoseScores scores;                  // every candidate's first score
+};
+// The order in which a relocalisation prefers its candidates: status not ICPMI_OK or pairs < minPairsRatio * n (in double) are dropped, the
+// rest come by sum_abs / pairs ascending (double), ties by the lower index.  Needs no GPU.
+std::vector<int> rankCandidates(const PoseScores& scores, size_t n, float minPairsRatio);
+// The start poses around `centre`: translations t + (dx, dy, 0), rotations Rz(dyaw) R, dx = halfX i / stepsX for i = -stepsX .. stepsX
+// (likewise dy, dyaw; 0 steps: that axis stays), formed in double and rounded to float.  `centre` comes first, then yaw outermost, y, x
+// innermost, each ascending: (2 stepsX + 1)(2 stepsY + 1)(2 stepsYaw + 1) poses.  Needs no GPU.
+std::vector<Mat4> candidateGrid(const Mat4& centre, float halfX, float halfY, float halfYaw, int stepsX = 1, int stepsY = 1, int stepsYaw = 1);
+
 class GpuICPSequence {
 public:
     struct ErrorMinimizerView {
@@ -61,6 +94,18 @@ public:
     icpmi_residual residual(const DataPoints& reading, const Mat4& T, int kind = ICPMI_RES_CHAIN) const;
     // ... of the scan registerWithPrior left on the GPU (icpmi_residual_error_staged): no upload
     icpmi_residual residualStaged(const Mat4& T, int kind = ICPMI_RES_CHAIN) const;
+    // residual(reading, T) for every T of `poses` in one call (icpmi_residual_error_poses): the reading filtered, uploaded, centred and
+    // sorted once.  Errors of one pose are in its status; errors of the whole call throw what residual throws.
+    PoseScores residuals(const DataPoints& reading, const std::vector<Mat4>& poses, int kind = ICPMI_RES_CHAIN) const;
+    // the sensor-frame reading registered from every prior (at most 16) at once (icpmi_register_multistart): each start as
+    // registerWithPrior alone.  Leaves no scan staged, no covariance and stats() alone.  The call carries the points alone: a chain that reads
+    // the reading's normals (SurfaceNormalOutlierFilter) or a descriptor row (GenericDescriptor{source: reading}, maxDistField) is refused
+    // with InvalidParameter, here and in relocalize (residuals serves such chains).
+    MultiStartResult registerMultiStart(const DataPoints& readingInSensorFrame, const std::vector<Mat4>& priors);
+    // Where is the sensor, given candidate poses?  Scores every candidate, drops and ranks them (rankCandidates), refines the best
+    // options.refine with registerMultiStart, scores the refined poses once more and returns the winner by the same rule.
+    // ConvergenceError when no candidate survives.
+    Relocalization relocalize(const DataPoints& readingInSensorFrame, const std::vector<Mat4>& candidates, const RelocalizeOptions& options = RelocalizeOptions());
 
     icpmi_handle handle() const { return h; }          // for the operators that share the GPU context
     // Map::updateLocalPointCloud for the PointDistance chain on the resident map (icpmi_map_update_point_distance)
@@ -104,6 +149,9 @@ public:
 private:
     void recreate();
     DataPoints filteredReading(const DataPoints& reading) const;
+    PoseScores residualsFiltered(const DataPoints& reading, const std::vector<Mat4>& poses, int kind) const; // (the reading as the chain's filters left it)
+    MultiStartResult multiStartFiltered(const DataPoints& reading, const std::vector<Mat4>& priors);
+    void requireBareReadingChain(const char* who) const;    // InvalidParameter for a chain that reads the reading's normals or descriptors
     icpmi_handle h = nullptr;
     icpmi_config cfg;
     icpmi_stats lastStats{};

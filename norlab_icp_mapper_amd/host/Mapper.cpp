@@ -304,6 +304,21 @@ void Mapper::processInput(const DataPoints& filteredInputInSensorFrame, const Ma
     { std::lock_guard<std::mutex> g(trajectoryLock); trajectory.addPose(correctedPose, timeStamp); }
 }
 
+Relocalization Mapper::relocalize(const DataPoints& inputInSensorFrame, const std::vector<Mat4>& candidates, const TimePoint& timeStamp,
+                                  const RelocalizeOptions& options)
+{
+    DataPoints scan = inputInSensorFrame;
+    applyInputFilters(scan);
+    Relocalization found;
+    {
+        std::lock_guard<std::mutex> g(icpMapLock);
+        found = icp.relocalize(scan, candidates, options);
+    }
+    { std::lock_guard<std::mutex> g(poseLock); pose = found.pose; }
+    { std::lock_guard<std::mutex> g(trajectoryLock); trajectory.addPose(found.pose, timeStamp); }
+    return found;
+}
+
 bool Mapper::mapUpdateIsDue(const TimePoint& now, const Mat4& poseNow, float overlap) const
 {
     if (!isMapping.load()) return false;

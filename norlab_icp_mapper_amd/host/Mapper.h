@@ -75,6 +75,13 @@ public:
     }
     void applyInputFilters(DataPoints& inputInSensorFrame);                                   // Mapper.cpp:187-191
     void processInput(const DataPoints& inputInSensorFrame, const Mat4& estimatedPose, const TimePoint& timeStamp); // :194-238
+    // Relocalisation against the current map: the input filters are applied to a copy of the scan, GpuICPSequence::relocalize picks and
+    // refines the best of `candidates`, and its pose becomes the mapper's (getPose(): what the next processInput starts from; the
+    // trajectory gets it under `timeStamp`).  The map is NOT updated, and neither is anything the last processInput left
+    // (lastRegistrationMapVersion(), lastResidual(), ...); Map::updatePose is not called either, so after a jump to a distant pose the map's
+    // cells are paged by the next processInput, not here.  Throws what GpuICPSequence::relocalize throws; the pose then stays.
+    Relocalization relocalize(const DataPoints& inputInSensorFrame, const std::vector<Mat4>& candidates, const TimePoint& timeStamp,
+                              const RelocalizeOptions& options = RelocalizeOptions());
     DataPoints getMap() { return map.getGlobalPointCloud(); }
     long residentMapUpdates() const { return map.residentUpdateCount(); }
     size_t localMapSize() { return map.localSize(); }

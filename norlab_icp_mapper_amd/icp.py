@@ -257,6 +257,92 @@ class Residual:
         return "Residual(" + ", ".join(f"{k}={getattr(self, k)!r}" for k in self.__slots__) + ")"
 
 
+class PoseScores:
+    """What icpmi_residual_error_poses* returns: one Residual and one status per pose (a pose whose status is not 0 keeps an empty Residual),
+    and `batched`, the number of poses that went through the batched launches."""
+
+    def __init__(self, residuals, status, batched):
+        self.residuals, self.status, self.batched = list(residuals), [int(s) for s in status], int(batched)
+
+    def __len__(self):
+        return len(self.residuals)
+
+    def table(self):
+        """(status, pairs, sum_abs) per pose: what rank_candidates reads"""
+        return [(st, r.pairs, r.sum_abs) for st, r in zip(self.status, self.residuals)]
+
+    def bits(self):
+        return [(st, r.bits()) for st, r in zip(self.status, self.residuals)]
+
+
+def rank_candidates(scores, n, min_pairs_ratio=0.5):
+    """The order in which a relocalisation prefers its candidates.  scores: a PoseScores, or (status, pairs, sum_abs) per candidate; n: points
+    of the reading.  A candidate whose status is not 0 or whose pairs < min_pairs_ratio * n (the ratio as float32, the product in
+    double) is dropped; the rest come by sum_abs / pairs ascending (double), ties by the lower index.  Returns the list of indices."""
+    table = scores.table() if isinstance(scores, PoseScores) else list(scores)
+    need = float(np.float32(min_pairs_ratio)) * float(n)
+    keyed = []
+    for i, (st, pairs, sum_abs) in enumerate(table):
+        if int(st) != 0 or int(pairs) <= 0 or float(int(pairs)) < need:
+            continue
+        keyed.append((float(sum_abs) / float(int(pairs)), i))
+    keyed.sort()
+    return [i for _, i in keyed]
+
+
+def candidate_grid(pose, half_x, half_y, half_yaw, steps_x=1, steps_y=1, steps_yaw=1):
+    """The start poses of a relocalisation around `pose` (4x4): translations pose.t + (dx, dy, 0) and rotations Rz(dyaw) pose.R with
+    dx = half_x i / steps_x for i = -steps_x .. steps_x (likewise dy, dyaw; 0 steps: that axis stays), formed in double and rounded to
+    float32.  `pose` itself comes first, then yaw outermost, y, x innermost, each ascending.  Returns (N, 4, 4) float32,
+    N = (2 steps_x + 1)(2 steps_y + 1)(2 steps_yaw + 1)."""
+    P = np.asarray(pose, dtype=np.float32).reshape(4, 4)
+    if min(steps_x, steps_y, steps_yaw) < 0:
+        raise InvalidParameter("candidate_grid: steps must be >= 0")
+    out = [P.copy()]
+    R = P[:3, :3].astype(np.float64)
+    t = P[:3, 3].astype(np.float64)
+    off = lambda half, k, steps: 0.0 if steps == 0 else float(half) * float(k) / float(steps)
+    for ia in range(-steps_yaw, steps_yaw + 1):
+        a = off(half_yaw, ia, steps_yaw)
+        ca, sa = math.cos(a), math.sin(a)
+        Rz = np.array([[ca, -sa, 0.0], [sa, ca, 0.0], [0.0, 0.0, 1.0]])
+        for iy in range(-steps_y, steps_y + 1):
+            for ix in range(-steps_x, steps_x + 1):
+                if ia == 0 and iy == 0 and ix == 0:
+                    continue
+                C4 = P.copy()
+                Rn = np.empty((3, 3))
+                for r in range(3):
+                    for c in range(3):
+                        Rn[r, c] = (Rz[r, 0] * R[0, c] + Rz[r, 1] * R[1, c]) + Rz[r, 2] * R[2, c]
+                C4[:3, :3] = Rn.astype(np.float32)
+                C4[0, 3] = np.float32(t[0] + off(half_x, ix, steps_x))
+                C4[1, 3] = np.float32(t[1] + off(half_y, iy, steps_y))
+                out.append(C4)
+    return np.stack(out).astype(np.float32)
+
+
+def compose_pose(A, B):
+    """A B for two 4x4 float32 matrices the way the host shell's Mat4 multiplies: every entry summed over k = 0 .. 3 in float32, one
+    multiply and one add per term -- the same bits on both sides of the C ABI (host/Makefile compiles the shell with -ffp-contract=off
+    for this: a fused multiply-add would round once where this rounds twice)."""
+    A = np.asarray(A, dtype=np.float32).reshape(4, 4)
+    B = np.asarray(B, dtype=np.float32).reshape(4, 4)
+    S = np.zeros((4, 4), dtype=np.float32)
+    for k in range(4):
+        S = (S + (A[:, k:k + 1] * B[k:k + 1, :]).astype(np.float32)).astype(np.float32)
+    return S
+
+
+class Relocalization:
+    """What ICPSequence.relocalize returns: the winner's corrected pose (4x4), its Residual, its index among the candidates and the
+    PoseScores of all candidates."""
+    __slots__ = ("pose", "residual", "index", "scores")
+
+    def __init__(self, pose, residual, index, scores):
+        self.pose, self.residual, self.index, self.scores = pose, residual, int(index), scores
+
+
 class _ErrorMinimizerView:
     def __init__(self, owner):
         self._o = owner
@@ -423,6 +509,111 @@ class ICPSequence:
         res = _capi.Residual()
         st = self._lib.icpmi_residual_error_staged(self._h, None if Tc is None else Tc.ctypes.data, int(kind), C.byref(res))
         return self._residual_out(st, res)
+
+    # ---- the same reading under many poses, and relocalisation from them (icpmi_residual_error_poses*, icpmi_register_multistart*) ----
+    @staticmethod
+    def _poses_to_c(poses):
+        P = np.asarray(poses, dtype=np.float32)
+        if P.ndim == 2:
+            P = P[None]
+        if P.ndim != 3 or P.shape[1:] != (4, 4):
+            raise InvalidParameter(f"expected (P, 4, 4) poses, got {P.shape}")
+        return np.ascontiguousarray(np.transpose(P, (0, 2, 1))).reshape(-1)  # column-major, 16 floats per pose
+
+    def _poses_out(self, st, res, status, batched):
+        if st == _capi.ERR_INVALID_ARG:
+            msg = self._lib.icpmi_last_error(self._h).decode()
+            if msg.startswith("InvalidField"):
+                raise InvalidField(msg)
+        self._check(st)
+        return PoseScores([Residual(r) for r in res], [int(x) for x in status], batched.value)
+
+    def residuals(self, reading, poses, normals=None, kind=0):
+        """icpmi_residual_error_poses: residual(reading, T) for every T of `poses` (P, 4, 4) in one call -- the reading uploaded, centred and
+        sorted once, the poses in chunks of 16 through batched launches where the chain allows.  Returns a PoseScores; errors of one pose
+        (a matrix that is not rigid, nothing to filter, no pair) are in its status, errors of the whole call raise."""
+        scan = _f32c(reading, 4)
+        nptr = None
+        if normals is not None:
+            normals = _f32c(normals, 3)
+            nptr = normals.ctypes.data
+        Tc = self._poses_to_c(poses)
+        P = Tc.shape[0] // 16
+        res = (_capi.Residual * max(P, 1))()
+        status = (C.c_int * max(P, 1))()
+        batched = C.c_int32(0)
+        st = self._lib.icpmi_residual_error_poses(self._h, scan.ctypes.data, scan.shape[0], nptr, Tc.ctypes.data, P, int(kind), res, status,
+                                                  C.byref(batched))
+        return self._poses_out(st, res[:P], status[:P], batched)
+
+    def residualsDev(self, d_scan_ptr, n, poses, d_normals_ptr=None, kind=0):
+        """icpmi_residual_error_poses_dev: residuals() for a reading (and its normals) already in HBM."""
+        Tc = self._poses_to_c(poses)
+        P = Tc.shape[0] // 16
+        res = (_capi.Residual * max(P, 1))()
+        status = (C.c_int * max(P, 1))()
+        batched = C.c_int32(0)
+        st = self._lib.icpmi_residual_error_poses_dev(self._h, d_scan_ptr, int(n), d_normals_ptr, Tc.ctypes.data, P, int(kind), res, status,
+                                                      C.byref(batched))
+        return self._poses_out(st, res[:P], status[:P], batched)
+
+    def _require_bare_reading_chain(self, who):
+        """icpmi_register_multistart carries the points alone, as icpmi_register_prior does: a chain that reads the reading's normals or one
+        of its descriptor rows cannot go through it (residuals serves such chains)"""
+        for f in range(self.cfg.n_outlier):
+            o = self.cfg.outlier[f]
+            if o.type == 5:
+                raise InvalidParameter(f"{who}: the chain's SurfaceNormalOutlierFilter reads the reading's normals, which the multistart registration does not carry")
+            if o.type == 6 and (o.iparam & 1):
+                raise InvalidParameter(f"{who}: the chain's GenericDescriptorOutlierFilter reads a descriptor row of the reading, which the multistart registration does not carry")
+        if self.cfg.var_dist:
+            raise InvalidParameter(f"{who}: KDTreeVarDistMatcher reads the reading's maxDistField row, which the multistart registration does not carry")
+
+    def _multistart(self, fn, scan_ptr, n, priors, fixed_iterations):
+        self._require_bare_reading_chain("registerMultiStart")
+        Tc = self._poses_to_c(priors)
+        S = Tc.shape[0] // 16
+        T = (C.c_float * (16 * max(S, 1)))()
+        stats = (_capi.Stats * max(S, 1))()
+        status = (C.c_int * max(S, 1))()
+        self._check(fn(self._h, scan_ptr, int(n), Tc.ctypes.data, S, int(fixed_iterations), T, stats, status))
+        return [_T_from_c(T[16 * s:16 * s + 16]) for s in range(S)], [stats[s] for s in range(S)], [int(status[s]) for s in range(S)]
+
+    def registerMultiStartDev(self, d_scan_ptr, n, priors, fixed_iterations=0):
+        """icpmi_register_multistart_dev: the sensor-frame scan in HBM registered from every prior of `priors` (S <= 16, (S, 4, 4)) at once.
+        Returns (list of 4x4 corrections, list of Stats, list of status codes), each start as registerWithPrior alone."""
+        return self._multistart(self._lib.icpmi_register_multistart_dev, d_scan_ptr, n, priors, fixed_iterations)
+
+    def registerMultiStart(self, scan, priors, fixed_iterations=0):
+        """icpmi_register_multistart: registerMultiStartDev for a scan on the host (one upload)."""
+        scan = _f32c(scan, 4)
+        return self._multistart(self._lib.icpmi_register_multistart, scan.ctypes.data, scan.shape[0], priors, fixed_iterations)
+
+    def relocalize(self, reading, candidates, min_pairs_ratio=0.5, refine=4, kind=0):
+        """Where is the sensor, given candidate poses?  Every candidate is scored (residuals), the failed ones and those with fewer than
+        min_pairs_ratio * N pairs are dropped, the rest ranked by sum_abs / pairs (rank_candidates); the best `refine` (<= 16) are refined
+        (registerMultiStart), the refined poses scored once more and ranked by the same rule.  Returns a Relocalization; ConvergenceError
+        when no candidate survives."""
+        scan = _f32c(reading, 4)
+        cand = np.asarray(candidates, dtype=np.float32).reshape(-1, 4, 4)
+        if cand.shape[0] == 0:
+            raise InvalidParameter("relocalize: no candidates")
+        self._require_bare_reading_chain("relocalize")  # (before anything is scored: the refinement could not run)
+        n = scan.shape[0]
+        scores = self.residuals(scan, cand, kind=kind)
+        order = rank_candidates(scores, n, min_pairs_ratio)
+        if not order:
+            raise ConvergenceError("relocalize: no candidate survived the scoring")
+        best = order[:max(1, min(int(refine), 16))]
+        corr, _, status = self.registerMultiStart(scan, cand[best])
+        refined = np.stack([compose_pose(corr[i], cand[best[i]]) for i in range(len(best))])
+        again = self.residuals(scan, refined, kind=kind)
+        again.status = [a if s == 0 else s for a, s in zip(again.status, status)]  # a start that did not converge is out
+        final = rank_candidates(again, n, min_pairs_ratio)
+        if not final:
+            raise ConvergenceError("relocalize: no refined candidate survived the scoring")
+        w = final[0]
+        return Relocalization(refined[w].copy(), again.residuals[w], best[w], scores)
 
     def setReadingMaxDist(self, radii):
         """icpmi_set_reading_max_dist: the search radius of every point of the NEXT reading (KDTreeVarDistMatcher's `maxDistField` row; one shot)."""
