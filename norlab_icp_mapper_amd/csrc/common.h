@@ -4,6 +4,7 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stddef.h>
 #include <math.h>
 #include <cstring>
 #include <string>
@@ -191,14 +192,33 @@ struct LoopCfg {
 
 // Device-resident loop state (one per handle).  Everything the iteration needs between kernels
 // lives here so that the loop never synchronises with the host.
-struct IcpState {
+// The words the per-iteration kernels READ sit together at the front (LoopHdr: 42 dwords on two adjacent 128-byte lines), so that a
+// kernel fetches them with ONE load instruction of one wave (hdr_load below: lane l takes dword l) issued next to its first data loads,
+// instead of one dependent miss per field on five different lines.  Everything a kernel only writes, or only the solve's checkers and
+// the host read, stays behind the header.
+struct alignas(128) LoopHdr {
     float T_iter[16];
     int   iter;
     int   done;
     int   error;           // icpmi_status (0 = ok)
-    int   stop_reason;
     int   counter;
     int   hist_n;          // number of poses pushed to the differential checker
+    unsigned seq;          // registration sequence number (tag of the progress word, see icpmi_ctx::h_progress)
+    unsigned hard_count;
+    unsigned n_valid;
+    unsigned sel_prefix_l[3];  // fused selection: one slot per radix level (written by level L,
+    unsigned sel_rank_l[3];    // read by level L + 1 -- never both in one kernel)
+    float robust_scale;    // RobustOutlierFilter::scale, kept between iterations (nbIterationForScale)
+    unsigned pad_hdr;
+    float limits[ICPMI_MAX_OUTLIER];
+    // r6: device clock at which the last NN launch's first workgroup started (0: no interval open), see t_nn_sum below
+    unsigned long long t_nn_begin;
+};
+static_assert(sizeof(LoopHdr) == 256 && alignof(LoopHdr) == 128, "the loop header is two 128-byte lines: one dword per lane of a wave");
+#define ICPMI_HDR_W(field) ((int)(offsetof(LoopHdr, field) / 4))   // dword index of a header field = the lane that holds it after hdr_load
+
+struct IcpState : LoopHdr {
+    int   stop_reason;
     double hq[(ICPMI_MAX_SMOOTH + 1) * 4];
     double ht[(ICPMI_MAX_SMOOTH + 1) * 3];
     double hrot[ICPMI_MAX_SMOOTH + 1];   // |angular distance| and translation distance between pose slot i and the pose before it
@@ -207,21 +227,14 @@ struct IcpState {
     // quantile selection
     unsigned sel_prefix;
     unsigned sel_rank;
-    unsigned n_valid;
-    unsigned sel_prefix_l[3];  // fused selection: one slot per radix level (written by level L,
-    unsigned sel_rank_l[3];    // read by level L + 1 -- never both in one kernel)
-    float limits[ICPMI_MAX_OUTLIER];
     unsigned vt_valid;     // VarTrimmedDist: number of valid matches of this iteration (counted by vt_keys_kernel, cleared by vt_pick_kernel)
     float vt_ratio;        // ... and the ratio optimizeInlierRatio picked (diagnostic)
     float robust_med;      // RobustOutlierFilter{mad}: median of the finite d2 of this iteration
-    float robust_scale;    // RobustOutlierFilter::scale, kept between iterations (nbIterationForScale)
     // statistics of the last iteration
     long long pairs;
     double wsum;
-    unsigned hard_count;
     unsigned ticket;             // workgroups of the pair-sum kernel that have published their partials (last one solves)
     unsigned long long hard_total;
-    unsigned seq;                // registration sequence number (tag of the progress word, see icpmi_ctx::h_progress)
     unsigned long long dbg[24];  // diagnostics: NN phase cycles with -DICPMI_NN_TIMING (scripts/nn_phase.py), [20]/[21] serial solve cycles / calls
     float T_prev[16];            // T_iter BEFORE the last minimisation: the pose the last counted iteration's pairs were formed under
     // result
@@ -229,20 +242,36 @@ struct IcpState {
     // r5: device clocks (wall_clock64, 100 MHz) of the first kernel of the registration's head and of the solve that stopped the loop:
     // stats->loop_ms without a HIP event to wait for (loop_run's fast finish).  t_done == 0: the loop was not stopped by a solve.
     unsigned long long t_start, t_done;
-    // r6: device-clock interval of every NN launch, summed over the registration: opened by the NN kernel's first workgroup, closed by the first
-    // workgroup of whatever kernel runs next (so one kernel boundary is inside) -- icpmi_stats::nn_ms_avg of a loop that is NOT in profile mode,
-    // i.e. bench.py's roofline duration taken from the timed graph replay itself
-    unsigned long long t_nn_begin, t_nn_sum;
+    // r6: device-clock interval of every NN launch, summed over the registration: opened by the NN kernel's first workgroup (t_nn_begin),
+    // closed by the first workgroup of whatever kernel runs next (so one kernel boundary is inside) -- icpmi_stats::nn_ms_avg of a loop that
+    // is NOT in profile mode, i.e. bench.py's roofline duration taken from the timed graph replay itself
+    unsigned long long t_nn_sum;
     unsigned nn_count, pad_nn;
 };
 
 #ifdef __HIPCC__
+// One trip for the loop header: every lane of the calling wave (all 64 active) loads the dword of its lane number; a field is then a
+// readlane of that register (uniform, no memory access).  Issue it in front of the kernel's first data loads and join the two at one point.
+__device__ __forceinline__ unsigned hdr_load(const IcpState* st) { return reinterpret_cast<const unsigned*>(st)[threadIdx.x & 63]; }
+struct HdrView {
+    unsigned w; // lane l: dword l of the header
+    __device__ __forceinline__ unsigned u(int i) const { return (unsigned)__builtin_amdgcn_readlane((int)w, i); }
+    __device__ __forceinline__ int i(int idx) const { return __builtin_amdgcn_readlane((int)w, idx); }
+    __device__ __forceinline__ float f(int idx) const { return __int_as_float(__builtin_amdgcn_readlane((int)w, idx)); }
+    __device__ __forceinline__ unsigned long long u64(int idx) const { return (unsigned long long)u(idx) | ((unsigned long long)u(idx + 1) << 32); }
+};
 __device__ __forceinline__ void nn_stamp_open(IcpState* st) { st->t_nn_begin = (unsigned long long)wall_clock64(); }
-__device__ __forceinline__ void nn_stamp_close(IcpState* st)
+// close the interval the last NN launch opened.  `b` = t_nn_begin as the caller already holds it (from its header read): no load at all,
+// the sum and the count go out as no-return atomics.  Several kernels may follow one NN launch: whoever finds the interval open closes it.
+__device__ __forceinline__ void nn_stamp_close(IcpState* st, unsigned long long b)
 {
-    const unsigned long long b = st->t_nn_begin;
-    if (b) { st->t_nn_sum += (unsigned long long)wall_clock64() - b; ++st->nn_count; st->t_nn_begin = 0; }
+    if (b) {
+        atomicAdd(&st->t_nn_sum, (unsigned long long)wall_clock64() - b);
+        atomicAdd(&st->nn_count, 1u);
+        st->t_nn_begin = 0;
+    }
 }
+__device__ __forceinline__ void nn_stamp_close(IcpState* st) { nn_stamp_close(st, st->t_nn_begin); }
 #endif
 
 

@@ -356,22 +356,26 @@ __global__ __launch_bounds__(256) void sel2_scan_hist_kernel(const float* __rest
                                                              unsigned* __restrict__ hists, float quantile, int use_win)
 {
     // blockIdx.y = reading of a batch (common.h: BatchArgs)
+    asm volatile("" ::"s"(ba.n[blockIdx.y]), "s"(ba.qstride), "s"(k), "s"(d2), "s"(hists), "s"(st), "s"(quantile), "s"(use_win)); // the kernel arguments in one batch (as in nn.hip)
     const int64_t count = (int64_t)ba.n[blockIdx.y] * k;
     d2 += (size_t)blockIdx.y * (size_t)ba.qstride * k;
     hists += (size_t)blockIdx.y * ICPMI_SELHIST_WORDS;
     st += blockIdx.y;
-    // the lane's elements and the coarse counts are requested together (one round trip)
+    // first trip: the loop header, the lane's elements and the coarse counts are requested together and joined below -- nothing of the
+    // loop state is read from memory after that
     constexpr int PF = 2;
     const int64_t stride = (int64_t)gridDim.x * 256;
     const int64_t i0 = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    HdrView hv{hdr_load(st)};
     float pv[PF];
 #pragma unroll
     for (int u = 0; u < PF; ++u) pv[u] = i0 + u * stride < count ? d2[i0 + u * stride] : INFINITY;
     unsigned cv = 0;
 #pragma unroll
     for (int cpy = 0; cpy < ICPMI_S2_COPIES; ++cpy) cv += hists[ICPMI_S2_C0 + cpy * 256 + threadIdx.x];
-    if (st->done) return;
-    if (blockIdx.x == 0 && threadIdx.x == 0) nn_stamp_close(const_cast<IcpState*>(st));
+    asm volatile("" : "+v"(hv.w), "+v"(pv[0]), "+v"(pv[1]), "+v"(cv)); // the join
+    if (hv.i(ICPMI_HDR_W(done))) return;
+    if (blockIdx.x == 0 && threadIdx.x == 0) nn_stamp_close(st, hv.u64(ICPMI_HDR_W(t_nn_begin)));
     __shared__ unsigned sh[16];
     unsigned prefix, rem, total;
     // (r5) k > 1: the NN kernel's window around the previous prefix first (the stand-alone builder took the same decision from the same words)
@@ -655,6 +659,10 @@ __global__ __launch_bounds__(BT) void accumulate_kernel(const float4* __restrict
 {
     // pnm != nullptr (k > 1, point-to-plane): matched point and its normal sit side by side -- one gather, one 64-byte sector
     // blockIdx.y = reading of a batch (common.h: BatchArgs); a single registration is the batch of one
+    // every kernel argument the prologue reads, requested from the kernarg segment in ONE batch (the idiom of nn.hip's prologue)
+    asm volatile("" ::"s"(ba.n[blockIdx.y]), "s"(ba.qstride), "s"(acc_cap), "s"(lc.k), "s"(lc.n_out), "s"(lc.out_type[0]), "s"(lc.out_param[0]),
+                 "s"(reading), "s"(sidx), "s"(d2a), "s"(match_pt), "s"(qindex), "s"(read_normals), "s"(hists), "s"(st), "s"(map), "s"(normals),
+                 "s"(pnm), "s"(fused_slot), "s"(is_median), "s"(factor));
     const int n = ba.n[blockIdx.y];
     const int nbe = acc_blocks_dev((int64_t)n * lc.k, acc_cap, BT);
     if ((int)blockIdx.x >= nbe) return;
@@ -670,8 +678,8 @@ __global__ __launch_bounds__(BT) void accumulate_kernel(const float4* __restrict
     // `reading`, sidx, d2a (and match_pt, the matched map points kept by the NN kernel) share one
     // order: the caller's, or -- qindex != nullptr -- the tile-sorted query order of the k = 1 loop,
     // where qindex maps a slot back to the caller's index (needed for reading descriptors only).
-    // The first two elements of every lane are requested before anything else so that their round
-    // trip overlaps the histogram scan below.
+    // The first two (k > 1: three) elements of every lane are requested before anything else, behind the
+    // loop header (hdr_load: one dword per lane) and in front of the level-1 coarse counts: one trip.
     const int64_t count = (int64_t)n * lc.k;
     const int64_t stride = (int64_t)nbe * BT;                                // (of the clears below: every thread of the reading's grid)
     const int64_t gtid = (int64_t)blockIdx.x * BT + threadIdx.x;
@@ -691,6 +699,7 @@ __global__ __launch_bounds__(BT) void accumulate_kernel(const float4* __restrict
     // (k > 1: 1024-thread workgroups, one per CU, up to 600 k pairs at knn 6 -- three pairs per lane; a third pair walked AFTER the first two
     // is two more dependent round trips, so all three are requested up front)
     constexpr int PF = BT > 256 ? 3 : 2;
+    unsigned hw = hdr_load(st);
     float pd2[PF]; int ps[PF]; float4 pr[PF], pq[PF];
 #pragma unroll
     for (int u = 0; u < PF; ++u) {
@@ -701,21 +710,31 @@ __global__ __launch_bounds__(BT) void accumulate_kernel(const float4* __restrict
         pr[u] = ld_stream(reading + (in ? (int)(e / lc.k) : 0));
         pq[u] = (match_pt && in) ? ld_stream(match_pt + e) : ((pnm && ps[u] >= 0) ? pnm[2 * (size_t)ps[u]] : make_float4(0.f, 0.f, 0.f, 0.f));
     }
-    const unsigned cv = (FUSED && threadIdx.x < 256) ? hists[ICPMI_S2_C1 + threadIdx.x] : 0u; // same round trip as the elements
+    unsigned cv = (FUSED && threadIdx.x < 256) ? hists[ICPMI_S2_C1 + threadIdx.x] : 0u; // same round trip as the elements
+    // the join: ONE point for the header and the coarse counts (issued last: the pairs in front of them have arrived with them).  Every
+    // field this kernel needs becomes a scalar here, under the full exec mask; the header register is dead after that
+    asm volatile("" : "+v"(hw), "+v"(cv));
+    const HdrView hv{hw};
+    const int done = hv.i(ICPMI_HDR_W(done));
+    const unsigned long long t_nn_begin = hv.u64(ICPMI_HDR_W(t_nn_begin));
+    const unsigned sel_rank0 = hv.u(ICPMI_HDR_W(sel_rank_l)), sel_prefix0 = hv.u(ICPMI_HDR_W(sel_prefix_l));
+    float T[16]; // the pose stays in scalar registers across the pair loop
+#pragma unroll
+    for (int i = 0; i < 16; ++i) T[i] = hv.f(ICPMI_HDR_W(T_iter) + i);
     // second round trip, overlapping the fine-histogram read of the selection scan: the matched normals
     float4 pn[PF];
 #pragma unroll
     for (int u = 0; u < PF; ++u)
         pn[u] = (MIN == ICPMI_MIN_POINT_TO_PLANE && ps[u] >= 0) ? (pnm ? pnm[2 * (size_t)ps[u] + 1] : normals[ps[u]]) : make_float4(0.f, 0.f, 0.f, 0.f);
-    if (st->done) return;
-    if (blockIdx.x == 0 && threadIdx.x == 0) nn_stamp_close(const_cast<IcpState*>(st));
+    if (done) return;
+    if (blockIdx.x == 0 && threadIdx.x == 0) nn_stamp_close(st, t_nn_begin);
     float fused_limit = 0.f;
     if (FUSED) {
         // scan of level 1: the selected element's bit pattern is prefix(16) | bin(16)
         __shared__ unsigned shsel[16];
         unsigned bin, rem, total;
-        block_find_rank_2tier<1>(cv, hists + ICPMI_S2_F1, false, 0.f, st->sel_rank_l[0], shsel, bin, rem, total);
-        const float q = __uint_as_float((st->sel_prefix_l[0] << 16) | bin);
+        block_find_rank_2tier<1>(cv, hists + ICPMI_S2_F1, false, 0.f, sel_rank0, shsel, bin, rem, total);
+        const float q = __uint_as_float((sel_prefix0 << 16) | bin);
         fused_limit = is_median ? factor * q : q;
         if (blockIdx.x == 0 && threadIdx.x == 0) st->limits[fused_slot] = fused_limit;
         // level 0 is dead (its only reader ran in the previous kernel): clear it for the next iteration
@@ -729,7 +748,6 @@ __global__ __launch_bounds__(BT) void accumulate_kernel(const float4* __restrict
     for (int i = 0; i < (NVAL > 0 ? NVAL : 1); ++i) acc[i] = 0.0;
     double wsum = 0.0, cnt = 0.0;
     double b2d[3] = {0.0, 0.0, 0.0}; // force2D: b of the 2-D residual (EXT variant only)
-    const float* T = st->T_iter;
     auto pair = [&](int64_t e, float d2, int s, float4 r, float4 qkept, float4 nkept, bool have_n) {
         if (d2 == INFINITY) return;
         const int qi = (int)(e / lc.k);
@@ -1503,7 +1521,9 @@ static void launch_accumulate_ext(icpmi_ctx* c, const LoopCfg& lc, int nb, int s
                        (lc.k > 1 && MIN == ICPMI_MIN_POINT_TO_PLANE && c->has_normals && c->d_map_pn) ? c->d_map_pn : (const float4*)nullptr);
 }
 
-static void enqueue_accumulate_solve(icpmi_ctx* c, int64_t n, const LoopCfg& lc, const BatchArgs& ba, const NnOutcome& nn, float* d_Tstep, double* d_sums)
+// publish = false: this solve leaves the progress word alone (an iteration inside a fixed-count graph: see loop_run)
+static void enqueue_accumulate_solve(icpmi_ctx* c, int64_t n, const LoopCfg& lc, const BatchArgs& ba, const NnOutcome& nn, float* d_Tstep, double* d_sums,
+                                     bool publish = true)
 {
     const int64_t count = n * lc.k;
     const int nb = acc_blocks(count, acc_threads(lc.k));
@@ -1523,7 +1543,7 @@ static void enqueue_accumulate_solve(icpmi_ctx* c, int64_t n, const LoopCfg& lc,
         else launch_accumulate<ICPMI_MIN_IDENTITY, false>(c, lc, nb, slot, ba, nn.out_sorted);
     }
     hipLaunchKernelGGL(solve_kernel, dim3(ba.nscan), dim3(256), 0, c->stream, c->d_state, c->d_selhist, 1, lc, d_Tstep, d_sums,
-                       c->d_progress, ba.nscan == 1 ? c->d_state_mirror : (IcpState*)nullptr);
+                       publish ? c->d_progress : (unsigned*)nullptr, ba.nscan == 1 ? c->d_state_mirror : (IcpState*)nullptr);
 }
 
 // what every launch of a registration's loop asks of the matcher (ba: its readings; NnRequest::iter is set iteration by iteration).  Built
@@ -1540,7 +1560,8 @@ static NnRequest loop_request(icpmi_ctx* c, const LoopCfg& lc, const BatchArgs& 
 }
 
 // iteration req.iter of the loop: match, select, accumulate, solve; *nn = what the matcher's launch answered
-static icpmi_status enqueue_iteration(icpmi_ctx* c, int64_t n, const LoopCfg& lc, const NnRequest& req, NnOutcome* nn, hipEvent_t nn0, hipEvent_t nn1)
+static icpmi_status enqueue_iteration(icpmi_ctx* c, int64_t n, const LoopCfg& lc, const NnRequest& req, NnOutcome* nn, hipEvent_t nn0, hipEvent_t nn1,
+                                      bool publish = true)
 {
     if (nn0) HIP_TRY(c, hipEventRecord(nn0, c->stream));
     icpmi_status s = nn_launch_k(c, req, c->d_reading, n, c->d_state->T_iter, lc, 1, c->d_sidx, c->d_d2, c->d_state, nn);
@@ -1548,7 +1569,7 @@ static icpmi_status enqueue_iteration(icpmi_ctx* c, int64_t n, const LoopCfg& lc
     if (nn1) HIP_TRY(c, hipEventRecord(nn1, c->stream));
     enqueue_selection(c, lc, n * lc.k, req.batch, *nn);
     // (icpmi_debug_keep_sums: the sums of every counted iteration of a SINGLE registration; a batch's solves would all write the one block)
-    enqueue_accumulate_solve(c, n, lc, req.batch, *nn, nullptr, req.batch.nscan > 1 ? nullptr : c->d_keep_sums.get());
+    enqueue_accumulate_solve(c, n, lc, req.batch, *nn, nullptr, req.batch.nscan > 1 ? nullptr : c->d_keep_sums.get(), publish);
     HIP_TRY(c, hipGetLastError());
     return ICPMI_OK;
 }
@@ -1693,9 +1714,13 @@ icpmi_status loop_run(icpmi_ctx* c, const float4* d_scan, const float* d_normals
     // (the same rule for the one-graph registration of a Counter-only chain: the shipped configuration, examples/config.yaml:54-57)
     if (graph && go_eager(c, &c->graph_wasted, cached, sig)) graph = false;
     // head (when asked) + `count` iterations from iteration `first` on, in the order every path enqueues them
-    auto enqueue_loop = [&](bool with_head, int first, int count, NnOutcome* nn) {
+    // last_word_only: only the last of the `count` solves publishes the progress word
+    auto enqueue_loop = [&](bool with_head, int first, int count, NnOutcome* nn, bool last_word_only = false) {
         icpmi_status s = with_head ? enqueue_registration_head(c, d_scan, d_normals3, n) : ICPMI_OK;
-        for (int it = 0; it < count && s == ICPMI_OK; ++it) { req.iter = first + it; s = enqueue_iteration(c, n, lc, req, nn, nullptr, nullptr); }
+        for (int it = 0; it < count && s == ICPMI_OK; ++it) {
+            req.iter = first + it;
+            s = enqueue_iteration(c, n, lc, req, nn, nullptr, nullptr, !last_word_only || it + 1 == count);
+        }
         return s;
     };
     if (!graph && !segmented) {
@@ -1753,7 +1778,10 @@ icpmi_status loop_run(icpmi_ctx* c, const float4* d_scan, const float* d_normals
         // buffer, the map and the chain stay the same
         ++gs.fixed.uses;
         if (!cached) {
-            const icpmi_status s = capture_loop_graph(c, gs.fixed, sig, [&](NnOutcome* nn) { return enqueue_loop(true, 0, lc.max_iter, nn); });
+            // Nobody reads the progress word of a fixed-count graph before its last solve: the host waits for "done", which only that solve
+            // (or, behind an error, its early-exit path) can report with the loop's last kernel behind it.  The solves in front of it skip
+            // the word and with it the system-scope release that goes with the store.
+            const icpmi_status s = capture_loop_graph(c, gs.fixed, sig, [&](NnOutcome* nn) { return enqueue_loop(true, 0, lc.max_iter, nn, true); });
             if (s != ICPMI_OK) return s;
         }
         HIP_TRY(c, hipGraphLaunch(gs.fixed.exec, c->stream));
