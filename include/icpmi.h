@@ -155,6 +155,13 @@ typedef struct {
         int32_t var_dist;      /* 1 = the matcher is KDTreeVarDistMatcher{knn, epsilon, maxDistField}: reading point i is matched within ITS OWN   */
                                /* radius, entry i of the row icpmi_set_reading_max_dist hands over before every registration; max_dist is        */
                                /* ignored.  0 (default): KDTreeMatcher, every result as before the field existed.                                 */
+        struct {               /* degeneracy_threshold IS reserved[1], the same way                                                                */
+            int32_t var_dist_;
+            float degeneracy_threshold; /* degeneracy-aware point-to-plane minimiser (icpmi_get_localizability): 0 (default) = off, every result  */
+                               /* as before the field existed; t > 0 = solve every iteration only in the span of the directions whose normalised   */
+                               /* information mu exceeds t, and report; t < 0 = report only, flags against |t|, poses bit-identical to 0.  Finite;  */
+                               /* point-to-plane on 3-D clouds only (no force_2d / is_2d).                                                         */
+        };
         int32_t reserved[2];
     };
 } icpmi_config;
@@ -282,7 +289,9 @@ icpmi_status icpmi_outlier_weights(icpmi_handle h, const float* d2, const int32_
  * with T_iter applied on the device first (T_iter may be NULL = identity). Runs NN + outlier
  * filters + minimiser of the handle's chain once. Outputs: T_step (4x4), and for inspection
  * sums[32] (double): point-to-plane -> A (upper 21, row-major packed) then b (6); point-to-point ->
- * sum w, sum w p (3), sum w q (3), sum w q p^T (9). Any output pointer may be NULL. */
+ * sum w, sum w p (3), sum w q (3), sum w q p^T (9). Any output pointer may be NULL.
+ * icpmi_config::degeneracy_threshold is honoured: T_step is the constrained step when it is > 0, and icpmi_get_localizability
+ * afterwards reports this step's system (c0 and L are those of reading4 as given). */
 icpmi_status icpmi_minimize_step(icpmi_handle h, const float* reading4, int64_t n, const float* T_iter,
                                  float T_step[16], double sums[32], icpmi_stats* stats);
 
@@ -794,6 +803,40 @@ icpmi_status icpmi_debug_last_sums(icpmi_handle h, double sums[32], float limits
  * registration yet, one that failed, a batch (icpmi_register_batch_dev), or any other call that reused the matcher's buffers or changed
  * the map after it -- the same rule as icpmi_debug_last_matches. */
 icpmi_status icpmi_get_covariance(icpmi_handle h, float cov[36]);
+
+/* Localizability of the point-to-plane system (Zhang & Singh's solution remapping as LOAM / LeGO-LOAM / LIO-SAM carry it; NOT a
+ * libpointmatcher feature).  Needs icpmi_config::degeneracy_threshold != 0 (point-to-plane, 3-D clouds, 6-DOF or force_4dof).  For one
+ * iteration, from its pair sums A (6 x 6), b (6), W = sum w in double, unknown x = (omega, t):
+ *   c0 = mean of the reading (centred map frame, before any pose), L = mean |p - c0| over the reading (1 when 0): one reduction per
+ *        registration, both rigid-invariant; c = T c0 with T the pose the iteration's pairs were formed under
+ *   1. pivot    K = [[I, -[c]x], [0, I]]:  A_c = K A K^T, b_c = K b   (rows of F become [(p - c) x n; n], unknown (omega, t + omega x c))
+ *   2. scale    S = diag(1/L, 1/L, 1/L, 1, 1, 1):  A_s = S A_c S, b_s = S b_c
+ *   3. decompose  force_4dof: the {2, 3, 4, 5} sub-system (n = 4), else n = 6; eigenpairs (lambda_e, v_e) of A_s ascending (double Jacobi),
+ *                 mu_e = lambda_e / W -- dimensionless, independent of where the map's centroid lies; for a translation it is the share
+ *                 of the pair weight that constrains the direction
+ *   4. classify   direction e is degenerate when mu_e <= |threshold| or lambda_e <= n eps_f lambda_max (the solver's rank rule)
+ *   5. step (threshold > 0 only)  y = sum over the non-degenerate e of v_e (v_e . b_s) / lambda_e;  omega = y_omega / L,
+ *                 t = y_t - omega x c;  x is rounded to float once and goes on as the Cholesky's x does.  No direction left: x = 0.
+ * The call reports the LAST COUNTED iteration of the last single registration (icpmi_register*, every variant; icpmi_minimize_step too).
+ * A column of `basis` is a twist in the pivoted, scaled coordinates: turn it into a physical one as rotation omega' / lnorm about `pivot`,
+ * translation as is.  ICPMI_ERR_UNSUPPORTED when there is nothing to read: the option is off, no registration yet, one that failed, a
+ * batch / multistart call came after it, or the map (icpmi_set_map*, any map update), the chain (icpmi_set_config) or the stream changed
+ * after it -- read the report before the map update that follows the registration, as icpmi_get_covariance.  Two identical calls give the same bits (no atomics anywhere in it). */
+typedef struct {
+    int32_t n;               /* 6, or 4 (force_4dof: yaw + translation)                                                              */
+    int32_t n_degenerate;    /* number of degenerate directions                                                                      */
+    int32_t degenerate[6];   /* flag per direction e (ascending eigenvalue); entries >= n are 0                                       */
+    double  eigval[6];       /* mu_e, ascending; entries >= n are 0                                                                  */
+    double  basis[36];       /* column-major: basis[6 e + i] = component i of v_e in (omega' (3), t' (3)); force_4dof: components 0, 1 */
+                             /* and columns 4, 5 are 0; the sign is the solver's                                                      */
+    double  pivot[3];        /* c in the map frame (the caller's frame: the map mean added back)                                     */
+    double  lnorm;           /* L                                                                                                    */
+    double  weight_sum;      /* W                                                                                                    */
+    int64_t pairs;           /* pairs with w != 0 of that iteration                                                                  */
+    int32_t iterations;      /* the iteration the report is for (1 = the first)                                                      */
+    int32_t reserved[3];
+} icpmi_localizability;
+icpmi_status icpmi_get_localizability(icpmi_handle h, icpmi_localizability* out);
 
 /* `errorMinimizer->getResidualError(filteredReading, filteredReference, outlierWeights, matches)` under a GIVEN pose: how well a reading
  * fits the handle's map (upstream's formulation as recalled, not checked against upstream's source).  One matcher pass, one pass of the chain's

@@ -28,9 +28,14 @@ class Outlier(C.Structure):
     _fields_ = [("type", C.c_int32), ("param", C.c_float), ("iparam", C.c_int32), ("param2", C.c_float), ("param3", C.c_float)]
 
 
+class _ConfigTailWords(C.Structure):
+    _fields_ = [("var_dist_", C.c_int32), ("degeneracy_threshold", C.c_float)]
+
+
 class _ConfigTail(C.Union):
-    """The tail of icpmi_config: var_dist is reserved[0]."""
-    _fields_ = [("var_dist", C.c_int32), ("reserved", C.c_int32 * 2)]
+    """The tail of icpmi_config: var_dist is reserved[0], degeneracy_threshold is reserved[1]."""
+    _anonymous_ = ("words",)
+    _fields_ = [("var_dist", C.c_int32), ("words", _ConfigTailWords), ("reserved", C.c_int32 * 2)]
 
 
 class Config(C.Structure):
@@ -101,6 +106,23 @@ class Residual(C.Structure):
 
 
 RES_CHAIN, RES_POINT_TO_POINT, RES_POINT_TO_PLANE = 0, 1, 2
+
+
+class Localizability(C.Structure):
+    """icpmi_localizability: the report of icpmi_get_localizability (basis[6 e + i] = component i of eigenvector e)."""
+    _fields_ = [
+        ("n", C.c_int32),
+        ("n_degenerate", C.c_int32),
+        ("degenerate", C.c_int32 * 6),
+        ("eigval", C.c_double * 6),
+        ("basis", C.c_double * 36),
+        ("pivot", C.c_double * 3),
+        ("lnorm", C.c_double),
+        ("weight_sum", C.c_double),
+        ("pairs", C.c_int64),
+        ("iterations", C.c_int32),
+        ("reserved", C.c_int32 * 3),
+    ]
 
 
 class MapOp(C.Structure):
@@ -216,6 +238,7 @@ SYMBOLS = [
     ("icpmi_debug_keep_sums", C.c_int, [_P, C.c_int32]),
     ("icpmi_debug_last_sums", C.c_int, [_P, C.POINTER(C.c_double), _F, _F, _F]),
     ("icpmi_get_covariance", C.c_int, [_P, _F]),
+    ("icpmi_get_localizability", C.c_int, [_P, C.POINTER(Localizability)]),
     ("icpmi_residual_error", C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int32, C.POINTER(Residual)]),
     ("icpmi_residual_error_dev", C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int32, C.POINTER(Residual)]),
     ("icpmi_residual_error_staged", C.c_int, [_P, _P, C.c_int32, C.POINTER(Residual)]),

@@ -131,6 +131,11 @@ static icpmi_status validate_config(const icpmi_config* cfg, std::string& err)
         if (cfg->is_2d) { err = "InvalidParameter: PointToPlaneWithCovErrorMinimizer: no covariance of planar (2-D) clouds"; return ICPMI_ERR_INVALID_ARG; }
         if (!std::isfinite(cfg->sensor_std_dev) || cfg->sensor_std_dev < 0.f) { err = "InvalidParameter: PointToPlaneWithCovErrorMinimizer: sensorStdDev must be finite and >= 0"; return ICPMI_ERR_INVALID_ARG; }
     }
+    if (cfg->degeneracy_threshold != 0.f) {
+        if (!std::isfinite(cfg->degeneracy_threshold)) { err = "InvalidParameter: degeneracyThreshold must be finite"; return ICPMI_ERR_INVALID_ARG; }
+        if (cfg->minimizer != ICPMI_MIN_POINT_TO_PLANE) { err = "InvalidParameter: degeneracyThreshold needs the point-to-plane minimizer"; return ICPMI_ERR_INVALID_ARG; }
+        if (cfg->force_2d || cfg->is_2d) { err = "InvalidParameter: degeneracyThreshold: no degeneracy analysis with force2D or of planar (2-D) clouds"; return ICPMI_ERR_INVALID_ARG; }
+    }
     return ICPMI_OK;
 }
 
@@ -218,6 +223,7 @@ icpmi_status icpmi_set_config(icpmi_handle h, const icpmi_config* cfg)
     if (cfg->device != h->device) { h->last_error = "set_config: the device of a handle cannot change"; return ICPMI_ERR_INVALID_ARG; }
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     store_config(h, cfg);
+    h->degen_ready = false; // (a report belongs to the chain that produced it)
     // the cached loop graph was captured for the previous chain
     drop_loop_graphs(h);
     return ICPMI_OK;
@@ -401,6 +407,22 @@ icpmi_status icpmi_get_covariance(icpmi_handle h, float cov[36])
     return read_back(h, cov, loop_covariance_out(h), 36 * sizeof(float));
 }
 
+icpmi_status icpmi_get_localizability(icpmi_handle h, icpmi_localizability* out)
+{
+    CHECK_H(h);
+    if (!out) { h->last_error = "get_localizability: out is null"; return ICPMI_ERR_INVALID_ARG; }
+    memset(out, 0, sizeof *out);
+    if (h->cfg.degeneracy_threshold == 0.f) { h->last_error = "get_localizability: the chain does not ask for it (icpmi_config::degeneracy_threshold)"; return ICPMI_ERR_UNSUPPORTED; }
+    if (!h->degen_ready || !h->d_degen.get()) {
+        h->last_error = "get_localizability: no report of a single registration on this handle (none ran, it failed, a batch / multistart call came after it, or the map or the chain changed since)";
+        return ICPMI_ERR_UNSUPPORTED;
+    }
+    const icpmi_status s = read_back(h, out, h->d_degen.get() + ICPMI_DG_OUT, sizeof *out);
+    if (s != ICPMI_OK) { memset(out, 0, sizeof *out); return s; }
+    for (int r = 0; r < 3; ++r) out->pivot[r] += (double)h->mean[r]; // (the side block keeps c in the centred frame)
+    return ICPMI_OK;
+}
+
 icpmi_status icpmi_debug_minstd_nth(icpmi_handle h, uint32_t seed, uint32_t n, uint32_t* out)
 {
     CHECK_H(h);
@@ -541,6 +563,15 @@ static icpmi_status reject_var_dist(icpmi_ctx* h, const char* who)
     return ICPMI_ERR_UNSUPPORTED;
 }
 
+// the side block of the degeneracy-aware solve, before make_loop_cfg looks for it (allocated once, zeroed; never while a stream captures)
+static icpmi_status ensure_degen_block(icpmi_ctx* h)
+{
+    if (h->cfg.degeneracy_threshold == 0.f || h->d_degen.get()) return ICPMI_OK;
+    HIP_TRY(h, h->d_degen.alloc(ICPMI_DG_DOUBLES));
+    HIP_TRY(h, hipMemsetAsync(h->d_degen.get(), 0, ICPMI_DG_DOUBLES * sizeof(double), h->stream));
+    return ICPMI_OK;
+}
+
 static icpmi_status register_impl(icpmi_handle h, const float* d_scan4, int64_t n, const float* d_n3, int fixed_iters,
                                   float T_out[16], icpmi_stats* stats)
 {
@@ -549,6 +580,7 @@ static icpmi_status register_impl(icpmi_handle h, const float* d_scan4, int64_t 
     const int64_t have_scalar_n = h->read_scalar_n, have_noise_n = h->read_noise_n, have_r2_n = h->read_r2_n;
     h->read_scalar_n = 0; h->read_noise_n = 0; h->read_r2_n = 0;
     h->cov_ready = false; // (loop_run sets it again once the covariance of THIS registration is enqueued)
+    h->degen_ready = false; // (... and the localizability report)
     if (!T_out) { h->last_error = "register: T_out is null"; return ICPMI_ERR_INVALID_ARG; }
     if (stats) { memset(stats, 0, sizeof *stats); stats->sensor_noise_overlap = -1.f; } // -1 = "not computed" on EVERY path
     identity16(T_out);
@@ -566,6 +598,7 @@ static icpmi_status register_impl(icpmi_handle h, const float* d_scan4, int64_t 
         return ICPMI_ERR_MISSING_NORMALS;
     }
     { const icpmi_status es = check_ext_filters(h); if (es != ICPMI_OK) return es; }
+    { const icpmi_status ds = ensure_degen_block(h); if (ds != ICPMI_OK) return ds; }
     LoopCfg lc = make_loop_cfg(h, fixed_iters);
     {   // GenericDescriptorOutlierFilter{source: reading}: the row handed over for THIS reading (one shot)
         bool wants = false;
@@ -679,6 +712,7 @@ static bool chain_takes_batch(const icpmi_ctx* h)
     }
     if (nquant > 1) together = false;
     if (h->cfg.var_dist) together = false; // (every reading needs its own row of radii)
+    if (h->cfg.degeneracy_threshold != 0.f) together = false; // (one side block per handle: the degeneracy-aware solve serves single registrations)
     if (together) {
         const GridParams& top = h->levels.g[h->levels.nlev - 1];
         if (!std::isfinite(h->cfg.max_dist) || (top.cell - top.slack) <= h->cfg.max_dist) together = false; // would need the brute-force pass
@@ -708,6 +742,7 @@ icpmi_status icpmi_register_batch_dev(icpmi_handle h, int32_t batch, const float
             if (sb != ICPMI_OK && first == ICPMI_OK) first = sb;
         }
         h->cov_ready = false; // (no covariance per reading of a batch)
+        h->degen_ready = false; // (... and no localizability report)
         return status ? ICPMI_OK : first;
     }
     if (stats) { memset(stats, 0, sizeof(icpmi_stats) * batch); for (int b = 0; b < batch; ++b) stats[b].sensor_noise_overlap = -1.f; }
@@ -1029,6 +1064,7 @@ icpmi_status icpmi_register_multistart_dev(icpmi_handle h, const float* d_scan4,
         }
     }
     h->cov_ready = false; // (no covariance per start, as after any batch)
+    h->degen_ready = false;
     icpmi_status first = ICPMI_OK;
     for (int s = 0; s < n_starts; ++s) {
         if (status) status[s] = st[s];
@@ -1162,6 +1198,7 @@ icpmi_status icpmi_minimize_step(icpmi_handle h, const float* reading4, int64_t 
     // d_reading has new contents: a tile-sorted copy of what was there before (an icpmi_knn with the same n) must not be searched in
     // its place (r3: tests/test_gpu_golden.py found the step computed on the previous call's queries)
     h->qsorted_n = -1; h->qsorted_src = nullptr;
+    { const icpmi_status ds = ensure_degen_block(h); if (ds != ICPMI_OK) return ds; }
     LoopCfg lc = make_loop_cfg(h, 1);
     for (int f = 0; f < lc.n_out; ++f)
         if (lc.out_type[f] == ICPMI_OUT_SURFACENORMAL) { h->last_error = "minimize_step: SurfaceNormal filter needs icpmi_register"; return ICPMI_ERR_UNSUPPORTED; }

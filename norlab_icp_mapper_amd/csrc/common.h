@@ -188,7 +188,24 @@ struct LoopCfg {
     int   has_read_normals;
     int   sensor_noise;    // the reading carries simpleSensorNoise + normals: getOverlap() is the sensor-noise count (loop.hip: overlap pass)
     const float* read_scalar; // GenericDescriptorOutlierFilter{source: reading}: that descriptor of the reading, caller's order (device)
+    // degeneracy-aware point-to-plane solve (icpmi_config::degeneracy_threshold; solve.h: degen_*): 0 off, ICPMI_DG_REPORT, ICPMI_DG_CONSTRAIN
+    int   degen;
+    float degen_thr;          // |degeneracy_threshold|
+    double* degen_blk;        // the handle's side block (layout below), null when off
 };
+
+// the side block of the degeneracy-aware solve (icpmi_ctx::d_degen), in doubles
+#define ICPMI_DG_REPORT 1
+#define ICPMI_DG_CONSTRAIN 2
+#define ICPMI_DG_C0 0        // c0 (3) and L: the reading's statistics, once per registration (loop.hip: degen_stats_*)
+#define ICPMI_DG_SUMS 8      // tot[0..28] of the last counted iteration, as its solve read them
+#define ICPMI_DG_T 40        // the 16 floats of T_iter that iteration's pairs were formed under
+#define ICPMI_DG_ITER 56     // the iteration's number (1 = the first)
+#define ICPMI_DG_OUT 64      // icpmi_localizability as degen_report_kernel leaves it (pivot still in the centred frame)
+#define ICPMI_DG_PART 128    // ICPMI_DG_NB x 4 partial sums of the statistics
+#define ICPMI_DG_NB 64
+#define ICPMI_DG_DOUBLES (ICPMI_DG_PART + 4 * ICPMI_DG_NB)
+static_assert(sizeof(icpmi_localizability) <= (ICPMI_DG_PART - ICPMI_DG_OUT) * sizeof(double), "the report fits its slot of the side block");
 
 // Device-resident loop state (one per handle).  Everything the iteration needs between kernels
 // lives here so that the loop never synchronises with the host.
@@ -645,7 +662,10 @@ struct icpmi_ctx {
     // icpmi_debug_keep_sums: 32 doubles the solve kernel of a single registration writes its pair sums to (null: not kept, the default --
     // the same launches with sums_out == nullptr); read by icpmi_debug_last_sums under the condition of icpmi_debug_last_matches
     DevArr<double> d_keep_sums;
-    DevArr<IcpState> d_state;           // ICPMI_MAX_BATCH states (a single registration uses the first)
+    // icpmi_get_localizability: the side block of the degeneracy-aware solve (ICPMI_DG_*; allocated when a chain first asks for it) and
+    // whether it holds the report of the last single registration (cleared by batches, multistart and whatever clears cov_ready)
+    DevArr<double> d_degen; bool degen_ready = false;
+    DevArr<IcpState> d_state;          // ICPMI_MAX_BATCH states (a single registration uses the first)
     IcpState* h_state = nullptr;                               // pinned mirror (ICPMI_MAX_BATCH)
     bool zero_pending = false;                                 // d_state / d_selhist still to be cleared: on the stream the handle really uses, at its first call (zero_state_if_pending)
     unsigned scan_tag = 0;                                     // call number of device_scan_flags_count: the tag its count comes back with (map_build.hip)
@@ -759,6 +779,7 @@ static inline void drop_loop_graphs(icpmi_ctx* c)
     ++c->map_epoch;
     c->graphs.reset();
     c->last_match_n = 0; c->cov_kept = false;
+    c->degen_ready = false; // (the report's pivot is kept in the centred frame of the map it was registered against: gone with that map)
 }
 
 // Small device -> host read through the pinned page: a copy into pageable memory is staged and blocks for tens of
@@ -1099,6 +1120,8 @@ icpmi_status loop_run(icpmi_ctx* c, const float4* d_scan, const float* d_normals
 icpmi_status loop_sensor_noise_overlap(icpmi_ctx* c, int64_t n, const LoopCfg& lc, bool sorted, float* overlap);
 icpmi_status loop_covariance(icpmi_ctx* c, int64_t n, const LoopCfg& lc, bool sorted);
 const float* loop_covariance_out(const icpmi_ctx* c); // device address of the 36 floats loop_covariance leaves
+icpmi_status loop_degen_stats(icpmi_ctx* c, int64_t n, const LoopCfg& lc);  // c0, L of the centred reading in c->d_reading -> lc.degen_blk (three launches)
+icpmi_status loop_degen_report(icpmi_ctx* c, const LoopCfg& lc);            // the side block's last counted iteration -> its icpmi_localizability (one launch)
 icpmi_status loop_prepare_reading(icpmi_ctx* c, const float4* d_scan, int64_t n, const float* d_normals3, bool* head_done = nullptr);
 icpmi_status loop_run_batch(icpmi_ctx* c, int batch, const float* const* d_scans4, const int64_t* n, const LoopCfg& lc, bool fixed,
                             float* T_out, icpmi_stats* stats, icpmi_status* status);

@@ -876,6 +876,7 @@ __device__ __forceinline__ void mirror_state(const IcpState* st, IcpState* mirro
     for (int i = threadIdx.x; i < W; i += 64) dst[i] = __hip_atomic_load(src + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+template <bool DEGEN> // (solve.h: solve_serial)
 __global__ __launch_bounds__(256) void solve_kernel(IcpState* __restrict__ st, unsigned* __restrict__ hists, int clear, LoopCfg lc,
                                                     float* __restrict__ T_step_out, double* __restrict__ sums_out, unsigned* __restrict__ progress,
                                                     IcpState* __restrict__ mirror)
@@ -892,7 +893,7 @@ __global__ __launch_bounds__(256) void solve_kernel(IcpState* __restrict__ st, u
         if (threadIdx.x == 0) publish_progress(st, progress);
         return;
     }
-    solve_body(st, acc, clear != 0, lc, T_step_out, sums_out);
+    solve_body<DEGEN>(st, acc, clear != 0, lc, T_step_out, sums_out);
     if (threadIdx.x == 0 && st->done) st->t_done = (unsigned long long)wall_clock64();
     if (mirror) {
         __syncthreads(); // thread 0's stores to the state are issued
@@ -1003,6 +1004,12 @@ LoopCfg make_loop_cfg(const icpmi_ctx* c, int fixed_iterations)
     lc.min_rot = cfg.min_diff_rot; lc.min_trans = cfg.min_diff_trans;
     lc.smooth = cfg.smooth_length < 1 ? 1 : (cfg.smooth_length > ICPMI_MAX_SMOOTH ? ICPMI_MAX_SMOOTH : cfg.smooth_length);
     lc.max_rot = cfg.max_rot_norm; lc.max_trans = cfg.max_trans_norm;
+    // degeneracy-aware solve: only once the handle has the side block (the entry points that run a solve allocate it first: api.hip)
+    if (cfg.degeneracy_threshold != 0.f && cfg.minimizer == ICPMI_MIN_POINT_TO_PLANE && c->d_degen.get()) {
+        lc.degen = cfg.degeneracy_threshold > 0.f ? ICPMI_DG_CONSTRAIN : ICPMI_DG_REPORT;
+        lc.degen_thr = fabsf(cfg.degeneracy_threshold);
+        lc.degen_blk = c->d_degen.get();
+    }
     return lc;
 }
 
@@ -1312,6 +1319,114 @@ icpmi_status loop_covariance(icpmi_ctx* c, int64_t n, const LoopCfg& lc, bool so
     return ICPMI_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Degeneracy-aware point-to-plane solve (solve.h: degen_*; include/icpmi.h: icpmi_get_localizability): the reading's statistics in the
+// registration's head, the report behind the loop.  c0 = mean of the centred reading, L = mean |p - c0|: double, per-workgroup partials in
+// a fixed order and then the ICPMI_DG_NB partials in a fixed order -- no atomics, two calls give the same bits.  Launched only when the
+// chain asks for the option.
+// ---------------------------------------------------------------------------------------------
+namespace {
+
+// fixed-order sum of the workgroup's 256 values; the result in every thread
+__device__ __forceinline__ double degen_block_sum(double v, double* sh /* 256 */)
+{
+    sh[threadIdx.x] = v;
+    __syncthreads();
+    for (int h = 128; h > 0; h >>= 1) {
+        if ((int)threadIdx.x < h) sh[threadIdx.x] += sh[threadIdx.x + h];
+        __syncthreads();
+    }
+    const double r = sh[0];
+    __syncthreads();
+    return r;
+}
+
+// the mean from the per-workgroup sums, the same order wherever it is formed
+__device__ __forceinline__ void degen_mean(const double* __restrict__ blk, int64_t n, double* c0)
+{
+    double s[3] = {0.0, 0.0, 0.0};
+    for (int b = 0; b < ICPMI_DG_NB; ++b)
+        for (int r = 0; r < 3; ++r) s[r] += blk[ICPMI_DG_PART + 4 * b + r];
+    for (int r = 0; r < 3; ++r) c0[r] = s[r] / (double)n;
+}
+
+// MODE 0: per-workgroup sums of x, y, z; MODE 1: per-workgroup sum of |p - c0|
+template <int MODE>
+__global__ __launch_bounds__(256) void degen_stats_kernel(const float4* __restrict__ reading, int64_t n, double* __restrict__ blk)
+{
+    __shared__ double sh[256];
+    double c0[3] = {0.0, 0.0, 0.0};
+    if (MODE == 1) degen_mean(blk, n, c0);
+    double a[3] = {0.0, 0.0, 0.0};
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)ICPMI_DG_NB * 256) {
+        const float4 p = reading[i];
+        if (MODE == 0) { a[0] += (double)p.x; a[1] += (double)p.y; a[2] += (double)p.z; }
+        else {
+            const double x = (double)p.x - c0[0], y = (double)p.y - c0[1], z = (double)p.z - c0[2];
+            a[0] += sqrt((x * x + y * y) + z * z);
+        }
+    }
+    for (int r = 0; r < (MODE == 0 ? 3 : 1); ++r) {
+        const double s = degen_block_sum(a[r], sh);
+        if (threadIdx.x == 0) blk[ICPMI_DG_PART + 4 * blockIdx.x + (MODE == 0 ? r : 3)] = s;
+    }
+}
+
+__global__ __launch_bounds__(64) void degen_stats_final_kernel(int64_t n, double* __restrict__ blk)
+{
+    if (threadIdx.x != 0) return;
+    double c0[3];
+    degen_mean(blk, n, c0);
+    double s = 0.0;
+    for (int b = 0; b < ICPMI_DG_NB; ++b) s += blk[ICPMI_DG_PART + 4 * b + 3];
+    const double L = s / (double)n;
+    for (int r = 0; r < 3; ++r) blk[ICPMI_DG_C0 + r] = c0[r];
+    blk[ICPMI_DG_C0 + 3] = L == 0.0 ? 1.0 : L;
+}
+
+// one lane: steps 1 - 4 on the kept sums of the last counted iteration -> icpmi_localizability (pivot in the centred frame: the host adds the mean)
+__global__ __launch_bounds__(64) void degen_report_kernel(double* __restrict__ blk, int four_dof, float thr)
+{
+    if (threadIdx.x != 0) return;
+    __shared__ DegenSys S;
+    degen_pivot(blk + ICPMI_DG_T, blk + ICPMI_DG_C0, S.c);
+    S.L = blk[ICPMI_DG_C0 + 3];
+    degen_decompose(blk + ICPMI_DG_SUMS, four_dof, thr, &S);
+    icpmi_localizability* out = reinterpret_cast<icpmi_localizability*>(blk + ICPMI_DG_OUT);
+    const int n = S.n, o = four_dof ? 2 : 0;
+    out->n = n; out->n_degenerate = S.ndeg;
+    for (int e = 0; e < 6; ++e) {
+        out->degenerate[e] = S.deg[e];
+        out->eigval[e] = (e < n && S.W > 0.0) ? S.w[e] / S.W : 0.0;
+        for (int i = 0; i < 6; ++i) out->basis[6 * e + i] = 0.0;
+        if (e < n) for (int i = 0; i < n; ++i) out->basis[6 * e + o + i] = S.Q[n * e + i];
+    }
+    for (int r = 0; r < 3; ++r) out->pivot[r] = S.c[r];
+    out->lnorm = S.L; out->weight_sum = S.W;
+    out->pairs = (long long)(blk[ICPMI_DG_SUMS + 28] + 0.5);
+    out->iterations = (int)blk[ICPMI_DG_ITER];
+    for (int i = 0; i < 3; ++i) out->reserved[i] = 0;
+}
+
+} // namespace
+
+icpmi_status loop_degen_stats(icpmi_ctx* c, int64_t n, const LoopCfg& lc)
+{
+    if (!lc.degen || n <= 0) return ICPMI_OK;
+    hipLaunchKernelGGL(degen_stats_kernel<0>, dim3(ICPMI_DG_NB), dim3(256), 0, c->stream, (const float4*)c->d_reading.get(), n, lc.degen_blk);
+    hipLaunchKernelGGL(degen_stats_kernel<1>, dim3(ICPMI_DG_NB), dim3(256), 0, c->stream, (const float4*)c->d_reading.get(), n, lc.degen_blk);
+    hipLaunchKernelGGL(degen_stats_final_kernel, dim3(1), dim3(64), 0, c->stream, n, lc.degen_blk);
+    HIP_TRY(c, hipGetLastError());
+    return ICPMI_OK;
+}
+
+icpmi_status loop_degen_report(icpmi_ctx* c, const LoopCfg& lc)
+{
+    hipLaunchKernelGGL(degen_report_kernel, dim3(1), dim3(64), 0, c->stream, lc.degen_blk, lc.force_4dof, lc.degen_thr);
+    HIP_TRY(c, hipGetLastError());
+    return ICPMI_OK;
+}
+
 // head_done: the caller wants the loop state initialised too (enqueue_registration_head); set when the sort's kernels did it.  Centring,
 // loop-state initialisation and the clearing of the selection histograms ride in the kernels of the query sort (SortHead) -- the head of a
 // registration is 3 graph nodes instead of 8
@@ -1542,8 +1657,12 @@ static void enqueue_accumulate_solve(icpmi_ctx* c, int64_t n, const LoopCfg& lc,
         if (fused) launch_accumulate<ICPMI_MIN_IDENTITY, true>(c, lc, nb, slot, ba, nn.out_sorted);
         else launch_accumulate<ICPMI_MIN_IDENTITY, false>(c, lc, nb, slot, ba, nn.out_sorted);
     }
-    hipLaunchKernelGGL(solve_kernel, dim3(ba.nscan), dim3(256), 0, c->stream, c->d_state, c->d_selhist, 1, lc, d_Tstep, d_sums,
-                       publish ? c->d_progress : (unsigned*)nullptr, ba.nscan == 1 ? c->d_state_mirror : (IcpState*)nullptr);
+    if (lc.degen) // (a single registration: chain_takes_batch keeps such a handle out of the batched loop)
+        hipLaunchKernelGGL(solve_kernel<true>, dim3(ba.nscan), dim3(256), 0, c->stream, c->d_state, c->d_selhist, 1, lc, d_Tstep, d_sums,
+                           publish ? c->d_progress : (unsigned*)nullptr, ba.nscan == 1 ? c->d_state_mirror : (IcpState*)nullptr);
+    else
+        hipLaunchKernelGGL(solve_kernel<false>, dim3(ba.nscan), dim3(256), 0, c->stream, c->d_state, c->d_selhist, 1, lc, d_Tstep, d_sums,
+                           publish ? c->d_progress : (unsigned*)nullptr, ba.nscan == 1 ? c->d_state_mirror : (IcpState*)nullptr);
 }
 
 // what every launch of a registration's loop asks of the matcher (ba: its readings; NnRequest::iter is set iteration by iteration).  Built
@@ -1616,11 +1735,12 @@ static void pose_out(const icpmi_ctx* c, const float* T_iter, float* T_out)
 
 // everything a registration enqueues before its first iteration: centring + tile sort of the reading,
 // loop state, selection histograms
-static icpmi_status enqueue_registration_head(icpmi_ctx* c, const float4* d_scan, const float* d_normals3, int64_t n)
+static icpmi_status enqueue_registration_head(icpmi_ctx* c, const float4* d_scan, const float* d_normals3, int64_t n, const LoopCfg& lc)
 {
     bool head_done = false;
     icpmi_status s = loop_prepare_reading(c, d_scan, n, d_normals3, &head_done);
     if (s != ICPMI_OK) return s;
+    if (lc.degen) { s = loop_degen_stats(c, n, lc); if (s != ICPMI_OK) return s; } // (c0, L of the centred reading: once per registration)
     if (head_done) return ICPMI_OK;
     // (the registration's sequence number: loop_run stores it in h_progress[32] before it launches anything)
     hipLaunchKernelGGL(init_state_kernel, dim3(1), dim3(64), 0, c->stream, c->d_state, (const float*)nullptr, c->reg_seq, c->d_progress,
@@ -1681,7 +1801,7 @@ icpmi_status loop_run(icpmi_ctx* c, const float4* d_scan, const float* d_normals
                       bool fixed, float T_out[16], icpmi_stats* stats)
 {
     LoopCfg lc = lc_in;
-    c->last_match_n = 0; c->cov_ready = false; c->cov_kept = false;
+    c->last_match_n = 0; c->cov_ready = false; c->cov_kept = false; c->degen_ready = false;
     // all allocations up front: none may happen while the stream is capturing
     if (ensure_loop_buffers(c, n, lc.k) != ICPMI_OK) return ICPMI_ERR_HIP;
     if (chain_has_vartrimmed(lc)) { VtBuffers vb; if (vt_buffers(c, n * lc.k, &vb) != ICPMI_OK) return ICPMI_ERR_HIP; }
@@ -1716,7 +1836,7 @@ icpmi_status loop_run(icpmi_ctx* c, const float4* d_scan, const float* d_normals
     // head (when asked) + `count` iterations from iteration `first` on, in the order every path enqueues them
     // last_word_only: only the last of the `count` solves publishes the progress word
     auto enqueue_loop = [&](bool with_head, int first, int count, NnOutcome* nn, bool last_word_only = false) {
-        icpmi_status s = with_head ? enqueue_registration_head(c, d_scan, d_normals3, n) : ICPMI_OK;
+        icpmi_status s = with_head ? enqueue_registration_head(c, d_scan, d_normals3, n, lc) : ICPMI_OK;
         for (int it = 0; it < count && s == ICPMI_OK; ++it) {
             req.iter = first + it;
             s = enqueue_iteration(c, n, lc, req, nn, nullptr, nullptr, !last_word_only || it + 1 == count);
@@ -1724,7 +1844,7 @@ icpmi_status loop_run(icpmi_ctx* c, const float4* d_scan, const float* d_normals
         return s;
     };
     if (!graph && !segmented) {
-        icpmi_status s = enqueue_registration_head(c, d_scan, d_normals3, n);
+        icpmi_status s = enqueue_registration_head(c, d_scan, d_normals3, n, lc);
         if (s != ICPMI_OK) return s;
     }
     if (segmented) {
@@ -1905,6 +2025,12 @@ icpmi_status loop_run(icpmi_ctx* c, const float4* d_scan, const float* d_normals
         if (cs != ICPMI_OK) return cs;
         c->cov_ready = true;
     }
+    if (lc.degen && !c->h_state->error && c->h_state->iter > 0) {
+        // icpmi_get_localizability: one launch on what the last counted iteration's solve kept in the side block
+        const icpmi_status ds = loop_degen_report(c, lc);
+        if (ds != ICPMI_OK) return ds;
+        c->degen_ready = true;
+    }
     const IcpState* hs = c->h_state;
     if (hs->error) {
         switch (hs->error) {
@@ -1939,7 +2065,7 @@ static void batch_result(icpmi_ctx* c, const LoopCfg& lc, const IcpState* hs, in
 icpmi_status loop_run_batch(icpmi_ctx* c, int B, const float* const* d_scans4, const int64_t* nn, const LoopCfg& lc, bool fixed, float* T_out,
                             icpmi_stats* stats, icpmi_status* status)
 {
-    c->last_match_n = 0; c->cov_kept = false; // (icpmi_debug_last_matches serves single registrations only)
+    c->last_match_n = 0; c->cov_kept = false; c->degen_ready = false; // (icpmi_debug_last_matches serves single registrations only)
     int64_t nmax = 0;
     for (int b = 0; b < B; ++b) nmax = nn[b] > nmax ? nn[b] : nmax;
     const int64_t NS = (nmax + 63) / 64 * 64; // slice stride of the per-query arrays
@@ -2057,6 +2183,8 @@ icpmi_status loop_single_step(icpmi_ctx* c, int64_t n, const LoopCfg& lc, const 
     HIP_TRY(c, hipMemsetAsync(d_Tstep, 0, 16 * sizeof(float), c->stream));
     LoopCfg l1 = lc;
     l1.max_iter = 1; l1.use_diff = 0; l1.use_bound = 0;
+    c->degen_ready = false;
+    { const icpmi_status ds = loop_degen_stats(c, n, l1); if (ds != ICPMI_OK) return ds; } // (the reading is in d_reading, centred by the caller)
     NnRequest req; // (one unseeded launch that answers in the caller's order)
     req.hist0 = fused_filter_slot(l1) >= 0 ? c->d_selhist.get() : nullptr;
     req.batch = batch_of_one(n);
@@ -2065,6 +2193,7 @@ icpmi_status loop_single_step(icpmi_ctx* c, int64_t n, const LoopCfg& lc, const 
     if (s == ICPMI_OK) {
         enqueue_selection(c, l1, n * l1.k, req.batch, nn);
         enqueue_accumulate_solve(c, n, l1, req.batch, nn, d_Tstep, d_sums);
+        if (l1.degen) (void)loop_degen_report(c, l1); // (an error state leaves the sums of an earlier call: degen_ready stays false below)
     }
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(c->h_state, c->d_state, sizeof(IcpState), hipMemcpyDeviceToHost, c->stream);
@@ -2078,6 +2207,7 @@ icpmi_status loop_single_step(icpmi_ctx* c, int64_t n, const LoopCfg& lc, const 
     if (c->h_state->error) { c->last_error = "minimize_step: device-side convergence error"; return (icpmi_status)c->h_state->error; }
     if (T_step) memcpy(T_step, hT, sizeof hT);
     if (sums) memcpy(sums, hS, sizeof hS);
+    c->degen_ready = l1.degen != 0;
     return ICPMI_OK;
 }
 

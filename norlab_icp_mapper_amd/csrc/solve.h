@@ -376,6 +376,127 @@ __device__ __noinline__ void solve_min_norm(int n, const float* A, const float* 
     for (int i = 0; i < n; ++i) x[i] = (float)xd[i];
 }
 
+// ---------------------------------------------------------------------------------------------
+// Degeneracy-aware point-to-plane solve (icpmi_config::degeneracy_threshold; include/icpmi.h: icpmi_get_localizability states the
+// quantity).  Everything in double from the pair sums themselves, one lane, work arrays in LDS like solve_min_norm's; out of line, so
+// that the common path keeps its registers.
+// ---------------------------------------------------------------------------------------------
+struct DegenSys {
+    int n, ndeg, deg[6];
+    double w[6], Q[36];  // eigenvalues ascending, eigenvectors (column e = Q[n e ..]) of the pivoted, scaled (sub-)system
+    double bs[6];        // its right-hand side (n entries)
+    double c[3], L, W;
+};
+
+// c = T c0: the reading's mean under the pose the iteration's pairs were formed under (T column-major, float or double)
+template <typename TT>
+__device__ __forceinline__ void degen_pivot(const TT* T, const double* c0, double* c)
+{
+    for (int r = 0; r < 3; ++r) c[r] = (((double)T[r] * c0[0] + (double)T[4 + r] * c0[1]) + (double)T[8 + r] * c0[2]) + (double)T[12 + r];
+}
+
+// steps 1 - 4: pivot, scale, decompose, classify.  tot: the iteration's pair sums (A packed in 0..20, b in 21..26, W in 27); S->c, S->L set
+__device__ __noinline__ void degen_decompose(const double* tot, int four_dof, float thr, DegenSys* S)
+{
+    __shared__ double A[36], B[9], G[9], R[9], As[36], bc[6];
+    {
+        int idx = 0;
+        for (int a = 0; a < 6; ++a)
+            for (int b = a; b < 6; ++b) { const double v = tot[idx++]; A[6 * a + b] = v; A[6 * b + a] = v; }
+    }
+    // K = [[I, B], [0, I]] with B = -[c]x touches the blocks only: with A = [[Arr, Art], [Atr, Att]] (column-major, A(i, j) = A[6 j + i])
+    //   (K A K^T)_rt = G = Art + B Att,   (K A K^T)_rr = Arr + B Atr + G B^T,   (K A K^T)_tt = Att;   (K b)_r = b_r + B b_t
+    // -- three 3 x 3 products on the one lane (rolled: operands in LDS) instead of two 6 x 6 ones
+    const double* c = S->c;
+    B[0] = 0.0;   B[3] = c[2];  B[6] = -c[1];
+    B[1] = -c[2]; B[4] = 0.0;   B[7] = c[0];
+    B[2] = c[1];  B[5] = -c[0]; B[8] = 0.0;
+#pragma unroll 1
+    for (int j = 0; j < 3; ++j)
+#pragma unroll 1
+        for (int i = 0; i < 3; ++i) {
+            double s = A[6 * (3 + j) + i];
+            for (int kk = 0; kk < 3; ++kk) s += B[3 * kk + i] * A[6 * (3 + j) + 3 + kk];
+            G[3 * j + i] = s;
+        }
+#pragma unroll 1
+    for (int j = 0; j < 3; ++j)
+#pragma unroll 1
+        for (int i = 0; i < 3; ++i) {
+            double s = A[6 * j + i];
+            for (int kk = 0; kk < 3; ++kk) s += B[3 * kk + i] * A[6 * j + 3 + kk];
+            for (int kk = 0; kk < 3; ++kk) s += G[3 * kk + i] * B[3 * kk + j];
+            R[3 * j + i] = s;
+        }
+    const double iL = 1.0 / S->L; // S = diag(1 / L, 1 / L, 1 / L, 1, 1, 1)
+    for (int j = 0; j < 3; ++j)
+        for (int i = 0; i < 3; ++i) {
+            A[6 * j + i] = R[3 * j + i] * (iL * iL);
+            A[6 * (3 + j) + i] = G[3 * j + i] * iL;
+            A[6 * i + 3 + j] = G[3 * j + i] * iL;
+        }
+    for (int i = 0; i < 3; ++i) {
+        double s = tot[21 + i];
+        for (int kk = 0; kk < 3; ++kk) s += B[3 * kk + i] * tot[24 + kk];
+        bc[i] = s * iL;
+        bc[3 + i] = tot[24 + i];
+    }
+    const int n = four_dof ? 4 : 6, o = four_dof ? 2 : 0;
+    for (int j = 0; j < n; ++j)
+        for (int i = 0; i < n; ++i) As[n * j + i] = 0.5 * (A[6 * (j + o) + (i + o)] + A[6 * (i + o) + (j + o)]); // (exactly symmetric for the Jacobi sweeps)
+    for (int i = 0; i < 6; ++i) S->bs[i] = i < n ? bc[i + o] : 0.0;
+    jacobi_eig(n, As, S->w, S->Q);
+    for (int a = 0; a + 1 < n; ++a) { // ascending; columns travel with their eigenvalue
+        int m = a;
+        for (int b = a + 1; b < n; ++b) if (S->w[b] < S->w[m]) m = b;
+        if (m == a) continue;
+        const double t = S->w[a]; S->w[a] = S->w[m]; S->w[m] = t;
+        for (int i = 0; i < n; ++i) { const double q = S->Q[n * a + i]; S->Q[n * a + i] = S->Q[n * m + i]; S->Q[n * m + i] = q; }
+    }
+    const double W = tot[27];
+    const double rank = (double)n * 1.1920928955078125e-07 * S->w[n - 1];
+    S->n = n; S->W = W; S->ndeg = 0;
+    for (int e = 0; e < 6; ++e) {
+        S->deg[e] = 0;
+        if (e >= n) continue;
+        const double mu = W > 0.0 ? S->w[e] / W : 0.0;
+        S->deg[e] = (!(mu > (double)thr) || !(S->w[e] > rank)) ? 1 : 0;
+        S->ndeg += S->deg[e];
+    }
+}
+
+// step 5: the step in the span of the non-degenerate directions, x = (omega, t) rounded to float once
+__device__ __noinline__ void solve_degenerate(const double* tot, const float* T_iter, const LoopCfg& lc, float* x)
+{
+    __shared__ DegenSys S;
+    __shared__ double y[6];
+    degen_pivot(T_iter, lc.degen_blk + ICPMI_DG_C0, S.c);
+    S.L = lc.degen_blk[ICPMI_DG_C0 + 3];
+    degen_decompose(tot, lc.force_4dof, lc.degen_thr, &S);
+    const int n = S.n, o = lc.force_4dof ? 2 : 0;
+    for (int i = 0; i < 6; ++i) y[i] = 0.0;
+    for (int e = 0; e < n; ++e) {
+        if (S.deg[e]) continue;
+        double proj = 0.0;
+        for (int i = 0; i < n; ++i) proj += S.Q[n * e + i] * S.bs[i];
+        proj /= S.w[e];
+        for (int i = 0; i < n; ++i) y[o + i] += proj * S.Q[n * e + i];
+    }
+    const double om[3] = {y[0] / S.L, y[1] / S.L, y[2] / S.L};
+    x[0] = (float)om[0]; x[1] = (float)om[1]; x[2] = (float)om[2];
+    x[3] = (float)(y[3] - (om[1] * S.c[2] - om[2] * S.c[1]));
+    x[4] = (float)(y[4] - (om[2] * S.c[0] - om[0] * S.c[2]));
+    x[5] = (float)(y[5] - (om[0] * S.c[1] - om[1] * S.c[0]));
+}
+
+// both modes: what icpmi_get_localizability's kernel needs of the counted iteration (its sums, the pose its pairs were formed under, its number)
+__device__ __noinline__ void degen_keep(const IcpState* st, const double* tot, double* blk)
+{
+    for (int i = 0; i < 29; ++i) blk[ICPMI_DG_SUMS + i] = tot[i];
+    for (int i = 0; i < 16; ++i) blk[ICPMI_DG_T + i] = (double)st->T_iter[i];
+    blk[ICPMI_DG_ITER] = (double)(st->iter + 1);
+}
+
 __device__ void angle_axis_T(const float* x3, float* T)
 {
     for (int i = 0; i < 16; ++i) T[i] = (i % 5 == 0) ? 1.f : 0.f;
@@ -463,6 +584,9 @@ __device__ __forceinline__ void read_pair_sums(unsigned long long* __restrict__ 
 // workgroup redoes in its prologue) or in global memory (solve_kernel).  Every array the solver indexes dynamically is a __shared__
 // array (exactly one lane of a workgroup runs this code): with stack arrays the kernel needs scratch memory, and 1 568 workgroups
 // walking 100 KB of scratch each turned a 2 us solve into +20 us per NN launch (r4, first version).
+// DEGEN: the instantiation of a chain with icpmi_config::degeneracy_threshold != 0.  <false> holds no call into the degeneracy-aware
+// routines: its registers, scratch and instructions are those of the solve before the option existed.
+template <bool DEGEN>
 __device__ void solve_serial(IcpState* st, const double* tot, const LoopCfg& lc, float* T_step_out)
 {
     const long long tsolve0 = clock64();
@@ -506,8 +630,13 @@ __device__ void solve_serial(IcpState* st, const double* tot, const LoopCfg& lc,
                 for (int bb = a; bb < 6; ++bb) { const float v = (float)tot[idx++]; A[6 * a + bb] = v; A[6 * bb + a] = v; }
             for (int a = 0; a < 6; ++a) b[a] = (float)tot[21 + a];
         };
-        if (lc.force_2d || lc.force_4dof) fill_Ab();
-        if (lc.force_2d) {
+        if constexpr (DEGEN) degen_keep(st, tot, lc.degen_blk);
+        const bool constrain = DEGEN && lc.degen == ICPMI_DG_CONSTRAIN; // (never with force_2d: validate_config)
+        if ((lc.force_2d || lc.force_4dof) && !constrain) fill_Ab();
+        if (constrain) {
+            // the step in the span of the informative directions, from the double sums (6-DOF and force4DOF alike)
+            if constexpr (DEGEN) solve_degenerate(tot, st->T_iter, lc, x);
+        } else if (lc.force_2d) {
             // force2D: F = [x ny - y nx; nx; ny] -- rows 2..4 of the 6-DOF F --, b from the 2-D residual (tot[29..31]); x = (yaw, tx, ty)
             __shared__ float A3[9], b3[3], x3[3];
             for (int c = 0; c < 3; ++c) { b3[c] = (float)tot[29 + c]; for (int r = 0; r < 3; ++r) A3[3 * c + r] = A[6 * (2 + c) + (2 + r)]; }
@@ -595,6 +724,7 @@ __device__ void solve_serial(IcpState* st, const double* tot, const LoopCfg& lc,
 }
 
 // the stand-alone solve: 256 threads read the accumulators (and clear them when asked), thread 0 solves
+template <bool DEGEN>
 __device__ void solve_body(IcpState* __restrict__ st, unsigned long long* __restrict__ acc, bool clear, const LoopCfg& lc,
                            float* __restrict__ T_step_out, double* __restrict__ sums_out)
 {
@@ -604,7 +734,7 @@ __device__ void solve_body(IcpState* __restrict__ st, unsigned long long* __rest
     read_pair_sums(acc, tot, clear, &nonfinite, pair_sum_mask(lc));
     if (t < ICPMI_NV && sums_out) sums_out[t] = tot[t];
     if (nonfinite) { if (t == 0) { st->error = ICPMI_ERR_NAN; st->done = 1; } return; }
-    if (t == 0) solve_serial(st, tot, lc, T_step_out);
+    if (t == 0) solve_serial<DEGEN>(st, tot, lc, T_step_out);
 }
 
 // progress word (icpmi_ctx::h_progress): visible to the host while the stream keeps running

@@ -29,6 +29,15 @@ void GpuICPSequence::check(icpmi_handle h, icpmi_status s)
 void GpuICPSequence::keepCovariance()
 {
     haveCovariance = cfg.covariance != 0 && icpmi_get_covariance(h, covariance.data()) == ICPMI_OK;
+    haveLocalizability = cfg.degeneracy_threshold != 0.f && icpmi_get_localizability(h, &localizability) == ICPMI_OK;
+}
+
+icpmi_localizability GpuICPSequence::ErrorMinimizerView::getLocalizability() const
+{
+    if (owner->haveLocalizability) return owner->localizability;
+    icpmi_localizability r{};
+    check(owner->h, icpmi_get_localizability(owner->h, &r)); // (throws: nothing to read)
+    return r;
 }
 
 std::array<float, 36> GpuICPSequence::ErrorMinimizerView::getCovariance() const
@@ -231,13 +240,20 @@ void GpuICPSequence::loadFromYamlNode(const yaml::Node& icp)
         else if (e.first == "PointToPlaneErrorMinimizer" || e.first == "PointToPlaneWithCovErrorMinimizer") {
             cfg.minimizer = ICPMI_MIN_POINT_TO_PLANE;
             if (e.first == "PointToPlaneWithCovErrorMinimizer") { // the same registration, plus getCovariance() (icpmi_get_covariance)
-                requireKnown(e.second, {"sensorStdDev", "force2D", "force4DOF"}, e.first);
+                requireKnown(e.second, {"sensorStdDev", "force2D", "force4DOF", "degeneracyThreshold", "degeneracyAction"}, e.first);
                 cfg.covariance = 1;
                 if (e.second["sensorStdDev"]) cfg.sensor_std_dev = e.second["sensorStdDev"].as<float>();
-            }
+            } else requireKnown(e.second, {"force2D", "force4DOF", "degeneracyThreshold", "degeneracyAction"}, e.first); // (a misspelt key must not leave the option off in silence)
             cfg.force_4dof = (e.second["force4DOF"] && e.second["force4DOF"].as<int>() != 0) ? 1 : 0;
             cfg.force_2d = (e.second["force2D"] && e.second["force2D"].as<int>() != 0) ? 1 : 0;
             if (cfg.force_4dof && cfg.force_2d) throw InvalidParameter("PointToPlaneErrorMinimizer: force2D and force4DOF exclude each other");
+            // degeneracy-aware solve (not libpointmatcher's): degeneracyThreshold >= 0 (0: off), degeneracyAction constrain | report
+            const float thr = e.second["degeneracyThreshold"] ? e.second["degeneracyThreshold"].as<float>() : 0.f;
+            const std::string action = e.second["degeneracyAction"] ? e.second["degeneracyAction"].as<std::string>() : std::string("constrain");
+            if (!(thr >= 0.f) || !std::isfinite(thr)) throw InvalidParameter(e.first + ": degeneracyThreshold must be finite and >= 0");
+            if (action != "constrain" && action != "report") throw InvalidParameter(e.first + ": degeneracyAction must be constrain or report");
+            if (thr > 0.f && cfg.force_2d) throw InvalidParameter(e.first + ": degeneracyThreshold and force2D exclude each other");
+            cfg.degeneracy_threshold = action == "constrain" ? thr : -thr;
         } else throw InvalidParameter("unknown error minimizer " + e.first);
     }
     if (icp["transformationCheckers"].IsSequence())
@@ -355,7 +371,7 @@ Mat4 GpuICPSequence::registerWithPrior(const DataPoints& scan, const Mat4& prior
 {
     Mat4 T = Mat4::identity();
     stagedPoints = scan.getNbPoints();
-    haveCovariance = false;
+    haveCovariance = false; haveLocalizability = false;
     check(h, icpmi_register_prior(h, scan.features.data(), (int64_t)scan.getNbPoints(), prior.data(), T.data(), &lastStats));
     keepCovariance();
     return T;
@@ -469,7 +485,7 @@ Mat4 GpuICPSequence::operator()(const DataPoints& readingIn)
     if ((normals || cfg.minimizer == ICPMI_MIN_POINT_TO_POINT) && reading.descriptorExists("simpleSensorNoise") &&
         reading.getDescriptorByName("simpleSensorNoise").span == 1)
         check(h, icpmi_set_reading_sensor_noise(h, reading.getDescriptorByName("simpleSensorNoise").data.data(), (int64_t)reading.getNbPoints()));
-    haveCovariance = false;
+    haveCovariance = false; haveLocalizability = false;
     check(h, icpmi_register(h, reading.features.data(), (int64_t)reading.getNbPoints(), normals, T.data(), &lastStats));
     keepCovariance();
     return T;
@@ -600,7 +616,7 @@ MultiStartResult GpuICPSequence::multiStartFiltered(const DataPoints& reading, c
     std::vector<float> P(16 * priors.size()), T(16 * priors.size());
     for (size_t s = 0; s < priors.size(); ++s) std::copy(priors[s].m.begin(), priors[s].m.end(), P.begin() + 16 * s);
     stagedPoints = 0;
-    haveCovariance = false;
+    haveCovariance = false; haveLocalizability = false;
     check(h, icpmi_register_multistart(h, reading.features.data(), (int64_t)reading.getNbPoints(), P.data(), (int32_t)priors.size(), 0, T.data(),
                                        out.stats.data(), out.status.data()));
     for (size_t s = 0; s < priors.size(); ++s) std::copy(T.begin() + 16 * s, T.begin() + 16 * s + 16, out.correction[s].m.begin());

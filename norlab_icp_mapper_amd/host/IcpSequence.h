@@ -72,6 +72,9 @@ public:
         // PointToPlaneWithCovErrorMinimizer::getCovariance(): 6 x 6 column-major, (tx, ty, tz, alpha, beta, gamma), centred frame, of the
         // last registration (include/icpmi.h: icpmi_get_covariance); throws through check() when there is none
         std::array<float, 36> getCovariance() const;
+        // degeneracyThreshold > 0 on the point-to-plane minimiser (not libpointmatcher's): which directions the last registration's last
+        // counted iteration did not constrain (include/icpmi.h: icpmi_get_localizability); throws through check() when there is none
+        icpmi_localizability getLocalizability() const;
         // ErrorMinimizer::getResidualError of `reading` against the map under the correction T, by the chain's minimizer: the sum over the
         // error elements of |p - q| (point-to-point) or |(p - q) . n| (point-to-plane) -- GpuICPSequence::residual(reading, T).sum_abs
         float getResidualError(const DataPoints& reading, const Mat4& T) const;
@@ -168,6 +171,10 @@ private:
     void keepCovariance();
     std::array<float, 36> covariance{};                // of the last registration, when the chain asks for it
     bool haveCovariance = false;
+    icpmi_localizability localizability{};             // ... and its degeneracy report
+    bool haveLocalizability = false;
+  public:
+    bool hasLocalizability() const { return haveLocalizability; } // the last registration left a report (Mapper's map-update veto reads it)
 };
 
 // PM::Transformation created with "RigidTransformation": features' = T * features, descriptors named

@@ -248,6 +248,7 @@ void Mapper::processInput(const DataPoints& filteredInputInSensorFrame, const Ma
             correction = icp.registerWithPrior(filteredInputInSensorFrame, estimatedPose); // identity while there is no map
             lastScoreValid = false;
             if (scoreRegistrations && !bootstrap && icp.hasMap()) { lastScore = icp.residualStaged(correction); lastScoreValid = true; }
+            keepLocalizability(!bootstrap && icp.hasMap());
         }
         lastCorrectionMat = bootstrap ? Mat4::identity() : correction;
         lastRegMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tReg).count();
@@ -280,11 +281,13 @@ void Mapper::processInput(const DataPoints& filteredInputInSensorFrame, const Ma
     lastUpdMs = 0.0;
     const auto tReg = std::chrono::steady_clock::now();
     lastScoreValid = false;
+    lastLocalizabilityValid = false;
     if (!bootstrap) {
         std::lock_guard<std::mutex> g(icpMapLock);
         lastSeenMapVersion = map.icpMapVersion();
         correction = icp(scanInMap);
         if (scoreRegistrations && icp.hasMap()) { lastScore = icp.residual(scanInMap, correction); lastScoreValid = true; }
+        keepLocalizability(icp.hasMap());
     }
     lastCorrectionMat = correction;
     lastRegMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tReg).count();
@@ -302,6 +305,19 @@ void Mapper::processInput(const DataPoints& filteredInputInSensorFrame, const Ma
     if (mapUpdateFuture.valid() && mapUpdateFuture.wait_for(std::chrono::milliseconds(1)) == std::future_status::ready) mapUpdateFuture.get();
     { std::lock_guard<std::mutex> g(poseLock); pose = correctedPose; }
     { std::lock_guard<std::mutex> g(trajectoryLock); trajectory.addPose(correctedPose, timeStamp); }
+}
+
+// the degeneracy report of the registration that just ran (registered = one did), for getLocalizability() and the map-update veto
+void Mapper::keepLocalizability(bool registered)
+{
+    lastLocalizabilityValid = registered && icp.hasLocalizability();
+    if (lastLocalizabilityValid) lastLocalizabilityReport = icp.errorMinimizer->getLocalizability();
+}
+
+icpmi_localizability Mapper::getLocalizability() const
+{
+    if (!lastLocalizabilityValid) throw std::runtime_error("Mapper::getLocalizability: the last processInput left no report (degeneracyThreshold is 0, or no scan was registered)");
+    return lastLocalizabilityReport;
 }
 
 Relocalization Mapper::relocalize(const DataPoints& inputInSensorFrame, const std::vector<Mat4>& candidates, const TimePoint& timeStamp,
@@ -322,6 +338,8 @@ Relocalization Mapper::relocalize(const DataPoints& inputInSensorFrame, const st
 bool Mapper::mapUpdateIsDue(const TimePoint& now, const Mat4& poseNow, float overlap) const
 {
     if (!isMapping.load()) return false;
+    // setMaxDegenerateDirectionsForUpdate: a scan whose registration left more directions unconstrained than that is not written into the map
+    if (maxDegenerateForUpdate >= 0 && lastLocalizabilityValid && lastLocalizabilityReport.n_degenerate > maxDegenerateForUpdate) return false;
     const bool updateInFlight = isOnline && mapUpdateFuture.valid() && mapUpdateFuture.wait_for(std::chrono::milliseconds(0)) != std::future_status::ready;
     if (updateInFlight) return false;
     float travelled2 = 0.f;

@@ -106,6 +106,13 @@ public:
     void setScoreRegistrations(bool on) { scoreRegistrations = on; }
     const icpmi_residual& lastResidual() const { return lastScore; }
     bool lastResidualValid() const { return lastScoreValid; }
+    // degeneracyThreshold on the point-to-plane minimiser (no reference analogue): the report of the last processInput's registration
+    // (include/icpmi.h: icpmi_get_localizability); throws std::runtime_error when that call registered nothing or the option is off
+    icpmi_localizability getLocalizability() const;
+    bool lastLocalizabilityIsValid() const { return lastLocalizabilityValid; }
+    // -1 (default): never veto.  Otherwise a scan whose registration reported MORE degenerate directions than this is not written into
+    // the map (the update policy is not even asked); its pose is published as always.
+    void setMaxDegenerateDirectionsForUpdate(int n) { maxDegenerateForUpdate = n; }
     const Mat4& lastCorrection() const { return lastCorrectionMat; } // the correction of the last processInput's ICP call (identity: none ran)
     // the last processInput: version of the registration map it ran against (Map::icpMapVersion, read under the ICP lock) and
     // whether it started a map update -- what a replay needs to reproduce a free-running online run scan by scan
@@ -133,6 +140,10 @@ private:
     double lastRegMs = 0.0, lastUpdMs = 0.0;
     bool scoreRegistrations = false, lastScoreValid = false;
     icpmi_residual lastScore{};
+    void keepLocalizability(bool registered);
+    icpmi_localizability lastLocalizabilityReport{};
+    bool lastLocalizabilityValid = false;
+    int maxDegenerateForUpdate = -1;
     Mat4 lastCorrectionMat = Mat4::identity();
     std::atomic_bool isMapping;
     Map map;

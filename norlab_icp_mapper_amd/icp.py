@@ -200,13 +200,28 @@ def config_from_yaml_chain(chain, **engine):
     if name == "PointToPlaneWithCovErrorMinimizer":
         # registers as PointToPlaneErrorMinimizer and leaves the pose covariance (errorMinimizer.getCovariance())
         for key in p:
-            if key not in ("sensorStdDev", "force2D", "force4DOF"):
+            if key not in ("sensorStdDev", "force2D", "force4DOF", "degeneracyThreshold", "degeneracyAction"):
                 raise InvalidParameter(f"{name}: unknown parameter {key}")
         kw["covariance"] = 1
         kw["sensor_std_dev"] = float(p.get("sensorStdDev", 0.01))
         name = "PointToPlaneErrorMinimizer"
+    elif name == "PointToPlaneErrorMinimizer":
+        for key in p:  # (a misspelt degeneracyThreshold must not leave the option off in silence)
+            if key not in ("force2D", "force4DOF", "degeneracyThreshold", "degeneracyAction"):
+                raise InvalidParameter(f"{name}: unknown parameter {key}")
     if name not in _MINIMIZERS:
         raise InvalidParameter(f"unknown error minimizer {name}")
+    if name == "PointToPlaneErrorMinimizer":
+        # degeneracy-aware solve (not libpointmatcher's): degeneracyThreshold >= 0 (0 = off), degeneracyAction constrain | report
+        thr = float(p.get("degeneracyThreshold", 0.0))
+        action = str(p.get("degeneracyAction", "constrain"))
+        if not (thr >= 0.0 and math.isfinite(thr)):
+            raise InvalidParameter(f"{name}: degeneracyThreshold must be finite and >= 0")
+        if action not in ("constrain", "report"):
+            raise InvalidParameter(f"{name}: degeneracyAction must be constrain or report")
+        if thr > 0.0 and int(p.get("force2D", 0)):
+            raise InvalidParameter(f"{name}: degeneracyThreshold and force2D exclude each other")
+        kw["degeneracy_threshold"] = thr if action == "constrain" else -thr
     kw["minimizer"] = _MINIMIZERS[name]
     kw["force_4dof"] = 1 if (name == "PointToPlaneErrorMinimizer" and int(p.get("force4DOF", 0))) else 0
     kw["force_2d"] = 1 if (name == "PointToPlaneErrorMinimizer" and int(p.get("force2D", 0))) else 0
@@ -366,6 +381,10 @@ class _ErrorMinimizerView:
         self._o._check(self._o._lib.icpmi_get_covariance(self._o._h, out))
         return np.array(out[:], dtype=np.float32).reshape(6, 6).T.copy()
 
+    def getLocalizability(self):
+        """the degeneracy report of the last single registration (ICPSequence.localizability)"""
+        return self._o.localizability()
+
     def getResidualError(self, reading, T=None):
         """ErrorMinimizer::getResidualError of `reading` against the map under the correction T (None: identity), by the chain's
         minimizer: the sum over the error elements of |p - q| (point-to-point) or |(p - q) . n| (point-to-plane) -- ICPSequence.residual"""
@@ -467,6 +486,19 @@ class ICPSequence:
                 raise InvalidField(msg)
         self._check(st)
         return _T_from_c(T[:])
+
+    # ---- which directions the last registration constrained (icpmi_get_localizability; errorMinimizer.getCovariance() is its neighbour) ----
+    def localizability(self):
+        """icpmi_get_localizability as a dict (degeneracy_threshold != 0): n, n_degenerate, degenerate (n bools), eigval (n, mu ascending),
+        basis ((6, n) float64, column e = eigenvector e in the pivoted, scaled coordinates), pivot (3, map frame), lnorm, weight_sum, pairs,
+        iterations -- of the last counted iteration of the last single registration; NotImplementedError when there is none"""
+        r = _capi.Localizability()
+        self._check(self._lib.icpmi_get_localizability(self._h, C.byref(r)))
+        n = int(r.n)
+        return dict(n=n, n_degenerate=int(r.n_degenerate), degenerate=np.array(r.degenerate[:n], dtype=bool),
+                    eigval=np.array(r.eigval[:n], dtype=np.float64), basis=np.array(r.basis[:], dtype=np.float64).reshape(6, 6).T[:, :n].copy(),
+                    pivot=np.array(r.pivot[:], dtype=np.float64), lnorm=float(r.lnorm), weight_sum=float(r.weight_sum), pairs=int(r.pairs),
+                    iterations=int(r.iterations))
 
     # ---- how well a reading fits the map under a given pose (icpmi_residual_error*) ----
     def _residual_out(self, st, res):
