@@ -572,6 +572,56 @@ static icpmi_status ensure_degen_block(icpmi_ctx* h)
     return ICPMI_OK;
 }
 
+// What a chain asks of a call that runs its first iteration on a reading, a registration and a residual call alike: its checks, its
+// LoopCfg (iters: make_loop_cfg's count) and the one-shot rows the call consumed (have_*), in upstream's order of complaint.
+// Out: the LoopCfg, the KDTreeVarDistMatcher row (null without one), whether the chain reads the reading's normals
+static icpmi_status chain_setup(icpmi_handle h, int64_t n, const float* d_n3, int64_t have_scalar_n, int64_t have_r2_n, int iters, LoopCfg* lc_out,
+                                const float** d_r2row_out, bool* needs_rn_out)
+{
+    bool needs_rn = false, wants_scalar = false;
+    for (int f = 0; f < h->cfg.n_outlier; ++f) {
+        const icpmi_outlier& o = h->cfg.outlier[f];
+        needs_rn |= o.type == ICPMI_OUT_SURFACENORMAL;
+        wants_scalar |= o.type == ICPMI_OUT_GENERICDESCRIPTOR && (o.iparam & ICPMI_GEN_SOURCE_READING);
+    }
+    *needs_rn_out = needs_rn;
+    if (needs_rn && (!d_n3 || !h->has_normals)) {
+        h->last_error = "InvalidField: SurfaceNormalOutlierFilter needs 'normals' on both reading and map";
+        return ICPMI_ERR_MISSING_NORMALS;
+    }
+    { const icpmi_status es = check_ext_filters(h); if (es != ICPMI_OK) return es; }
+    LoopCfg& lc = *lc_out;
+    lc = make_loop_cfg(h, iters);
+    // GenericDescriptorOutlierFilter{source: reading}: the row handed over for THIS reading (one shot)
+    if (wants_scalar && n > 0 && have_scalar_n != n) {
+        h->last_error = "InvalidField: GenericDescriptorOutlierFilter{source: reading} needs the reading's descriptor (icpmi_set_reading_scalar, one row per point)";
+        return ICPMI_ERR_INVALID_ARG;
+    }
+    lc.read_scalar = wants_scalar ? h->d_read_scalar : nullptr;
+    // KDTreeVarDistMatcher: the radii handed over for THIS reading (one shot).  The search runs with one bound, the largest radius of the row;
+    // the kernels accept per query (nn.hip: RowR2).
+    *d_r2row_out = nullptr;
+    if (h->cfg.var_dist && n > 0) {
+        if (have_r2_n != n) {
+            h->last_error = "InvalidField: KDTreeVarDistMatcher needs the reading's maxDistField descriptor (icpmi_set_reading_max_dist, one radius per point)";
+            return ICPMI_ERR_INVALID_ARG;
+        }
+        if (!(h->read_r2_max > 0.f)) { // (the rule of KDTreeMatcher's maxDist, which this bound stands in for)
+            h->last_error = "InvalidParameter: KDTreeVarDistMatcher: the largest radius of the row must be > 0 (as maxDist)";
+            return ICPMI_ERR_INVALID_ARG;
+        }
+        set_search_bound(h, lc, h->read_r2_max);
+        *d_r2row_out = h->d_read_r2;
+    }
+    lc.has_read_normals = needs_rn ? 1 : 0;
+    if (n == 0) { // upstream: Trimmed / Median throw "no outlier to filter", otherwise "no point to minimize"
+        const bool quant = chain_has_quantile(lc);
+        h->last_error = quant ? "ConvergenceError: no outlier to filter" : "ConvergenceError: ErrorMinimizer: no point to minimize";
+        return quant ? ICPMI_ERR_NO_OUTLIER_TO_FILTER : ICPMI_ERR_NO_POINT_TO_MINIMIZE;
+    }
+    return ICPMI_OK;
+}
+
 static icpmi_status register_impl(icpmi_handle h, const float* d_scan4, int64_t n, const float* d_n3, int fixed_iters,
                                   float T_out[16], icpmi_stats* stats)
 {
@@ -591,53 +641,18 @@ static icpmi_status register_impl(icpmi_handle h, const float* d_scan4, int64_t 
         h->last_error = "InvalidField: PointToPlaneErrorMinimizer needs the descriptor 'normals' on the map";
         return ICPMI_ERR_MISSING_NORMALS;
     }
-    bool needs_rn = false;
-    for (int f = 0; f < h->cfg.n_outlier; ++f) needs_rn |= h->cfg.outlier[f].type == ICPMI_OUT_SURFACENORMAL;
-    if (needs_rn && (!d_n3 || !h->has_normals)) {
-        h->last_error = "InvalidField: SurfaceNormalOutlierFilter needs 'normals' on both reading and map";
-        return ICPMI_ERR_MISSING_NORMALS;
-    }
-    { const icpmi_status es = check_ext_filters(h); if (es != ICPMI_OK) return es; }
     { const icpmi_status ds = ensure_degen_block(h); if (ds != ICPMI_OK) return ds; }
-    LoopCfg lc = make_loop_cfg(h, fixed_iters);
-    {   // GenericDescriptorOutlierFilter{source: reading}: the row handed over for THIS reading (one shot)
-        bool wants = false;
-        for (int f = 0; f < h->cfg.n_outlier; ++f) wants |= h->cfg.outlier[f].type == ICPMI_OUT_GENERICDESCRIPTOR && (h->cfg.outlier[f].iparam & ICPMI_GEN_SOURCE_READING);
-        if (wants && n > 0 && have_scalar_n != n) {
-            h->last_error = "InvalidField: GenericDescriptorOutlierFilter{source: reading} needs the reading's descriptor (icpmi_set_reading_scalar, one row per point)";
-            return ICPMI_ERR_INVALID_ARG;
-        }
-        lc.read_scalar = wants ? h->d_read_scalar : nullptr;
-    }
-    // KDTreeVarDistMatcher: the radii handed over for THIS reading (one shot).  The search runs with one bound, the largest radius of the row;
-    // the kernels accept per query (nn.hip: RowR2).
+    LoopCfg lc;
     const float* d_r2row = nullptr;
-    if (h->cfg.var_dist && n > 0) {
-        if (have_r2_n != n) {
-            h->last_error = "InvalidField: KDTreeVarDistMatcher needs the reading's maxDistField descriptor (icpmi_set_reading_max_dist, one radius per point)";
-            return ICPMI_ERR_INVALID_ARG;
-        }
-        if (!(h->read_r2_max > 0.f)) { // (the rule of KDTreeMatcher's maxDist, which this bound stands in for)
-            h->last_error = "InvalidParameter: KDTreeVarDistMatcher: the largest radius of the row must be > 0 (as maxDist)";
-            return ICPMI_ERR_INVALID_ARG;
-        }
-        set_search_bound(h, lc, h->read_r2_max);
-        d_r2row = h->d_read_r2;
-    }
+    bool needs_rn = false;
+    { const icpmi_status cs = chain_setup(h, n, d_n3, have_scalar_n, have_r2_n, fixed_iters, &lc, &d_r2row, &needs_rn); if (cs != ICPMI_OK) return cs; }
     // sensor-noise overlap (icpmi_set_reading_sensor_noise): the noise row is one shot -- this registration consumes it
     // (PointToPointErrorMinimizer::getOverlap() needs `simpleSensorNoise` alone; only the point-to-plane variant also reads the reading's
     // `normals` -- ADVICE r3)
-    const bool sn = have_noise_n == n && n > 0 && !lc.ext && !lc.is_2d &&
+    const bool sn = have_noise_n == n && !lc.ext && !lc.is_2d &&
                     (lc.minimizer == ICPMI_MIN_POINT_TO_POINT || (lc.minimizer == ICPMI_MIN_POINT_TO_PLANE && d_n3));
     lc.sensor_noise = sn ? 1 : 0;
-    lc.has_read_normals = (needs_rn || (sn && d_n3)) ? 1 : 0;
-    if (n == 0) {
-        // upstream: Trimmed/Median throw "no outlier to filter", otherwise "no point to minimize"
-        bool quant = false;
-        for (int f = 0; f < lc.n_out; ++f) quant |= lc.out_type[f] == ICPMI_OUT_TRIMMEDDIST || lc.out_type[f] == ICPMI_OUT_MEDIANDIST || lc.out_type[f] == ICPMI_OUT_VARTRIMMEDDIST;
-        h->last_error = quant ? "ConvergenceError: no outlier to filter" : "ConvergenceError: ErrorMinimizer: no point to minimize";
-        return quant ? ICPMI_ERR_NO_OUTLIER_TO_FILTER : ICPMI_ERR_NO_POINT_TO_MINIMIZE;
-    }
+    if (sn && d_n3) lc.has_read_normals = 1;
     icpmi_stats local;
     if (!stats && stats_json()) stats = &local;
     const icpmi_status rs = loop_run(h, (const float4*)d_scan4, (needs_rn || sn) ? d_n3 : nullptr, n, lc, d_r2row, fixed_iters > 0, T_out, stats);
@@ -735,15 +750,12 @@ icpmi_status icpmi_register_batch_dev(icpmi_handle h, int32_t batch, const float
     bool together = batch > 1 && chain_takes_batch(h);
     for (int b = 0; b < batch; ++b) if (n[b] == 0 || n[b] > 0x7fffffff / ICPMI_MAX_K) together = false;
     if (!together) {
-        icpmi_status first = ICPMI_OK;
-        for (int b = 0; b < batch; ++b) {
-            const icpmi_status sb = register_impl(h, d_scans4[b], n[b], nullptr, fixed_iterations, T_out + 16 * b, stats ? stats + b : nullptr);
-            if (status) status[b] = sb;
-            if (sb != ICPMI_OK && first == ICPMI_OK) first = sb;
-        }
+        icpmi_status sb[ICPMI_MAX_BATCH];
+        for (int b = 0; b < batch; ++b)
+            sb[b] = register_impl(h, d_scans4[b], n[b], nullptr, fixed_iterations, T_out + 16 * b, stats ? stats + b : nullptr);
         h->cov_ready = false; // (no covariance per reading of a batch)
         h->degen_ready = false; // (... and no localizability report)
-        return status ? ICPMI_OK : first;
+        return fold_status(h, status, sb, batch, nullptr); // (last_error: what the last reading that failed said)
     }
     if (stats) { memset(stats, 0, sizeof(icpmi_stats) * batch); for (int b = 0; b < batch; ++b) stats[b].sensor_noise_overlap = -1.f; }
     LoopCfg lc = make_loop_cfg(h, fixed_iterations);
@@ -773,7 +785,7 @@ icpmi_status icpmi_register(icpmi_handle h, const float* scan4, int64_t n, const
     return register_impl(h, d_scan, n, d_n3, 0, T_out, stats);
 }
 
-// icpmi_residual_error*: what the chain asks of a residual call whatever the pose -- the checks and the chain set-up of register_impl.
+// icpmi_residual_error*: what the chain asks of a residual call whatever the pose -- its own refusals, then chain_setup.
 // have_*: the one-shot rows the call consumed; *kind comes back as 1 or 2
 static icpmi_status residual_chain_setup(icpmi_handle h, const char* who, int64_t n, const float* d_n3, int64_t have_scalar_n, int64_t have_r2_n,
                                          int32_t* kind_io, LoopCfg* lc_out, const float** d_r2row_out, bool* needs_rn_out)
@@ -791,55 +803,15 @@ static icpmi_status residual_chain_setup(icpmi_handle h, const char* who, int64_
         h->last_error = "InvalidField: the point-to-plane residual needs the descriptor 'normals' on the map";
         return ICPMI_ERR_MISSING_NORMALS;
     }
-    bool needs_rn = false;
     for (int f = 0; f < h->cfg.n_outlier; ++f) {
         const icpmi_outlier& o = h->cfg.outlier[f];
-        needs_rn |= o.type == ICPMI_OUT_SURFACENORMAL;
         if (o.type == ICPMI_OUT_ROBUST && (((o.iparam >> 4) & 15) == ICPMI_SCALE_BERG || (int)o.param2 > 0)) {
             h->last_error = std::string(who) + ": RobustOutlierFilter with scaleEstimator berg or nbIterationForScale > 0 keeps its scale from one "
                             "iteration of a registration to the next: no single pass can answer for it";
             return ICPMI_ERR_UNSUPPORTED;
         }
     }
-    *needs_rn_out = needs_rn;
-    if (needs_rn && (!d_n3 || !h->has_normals)) {
-        h->last_error = "InvalidField: SurfaceNormalOutlierFilter needs 'normals' on both reading and map";
-        return ICPMI_ERR_MISSING_NORMALS;
-    }
-    { const icpmi_status es = check_ext_filters(h); if (es != ICPMI_OK) return es; }
-    LoopCfg lc = make_loop_cfg(h, 1);
-    {   // GenericDescriptorOutlierFilter{source: reading}: the row handed over for THIS reading (one shot)
-        bool wants = false;
-        for (int f = 0; f < h->cfg.n_outlier; ++f) wants |= h->cfg.outlier[f].type == ICPMI_OUT_GENERICDESCRIPTOR && (h->cfg.outlier[f].iparam & ICPMI_GEN_SOURCE_READING);
-        if (wants && n > 0 && have_scalar_n != n) {
-            h->last_error = "InvalidField: GenericDescriptorOutlierFilter{source: reading} needs the reading's descriptor (icpmi_set_reading_scalar, one row per point)";
-            return ICPMI_ERR_INVALID_ARG;
-        }
-        lc.read_scalar = wants ? h->d_read_scalar : nullptr;
-    }
-    *d_r2row_out = nullptr;
-    if (h->cfg.var_dist && n > 0) { // KDTreeVarDistMatcher: the radii handed over for THIS reading (one shot), as in register_impl
-        if (have_r2_n != n) {
-            h->last_error = "InvalidField: KDTreeVarDistMatcher needs the reading's maxDistField descriptor (icpmi_set_reading_max_dist, one radius per point)";
-            return ICPMI_ERR_INVALID_ARG;
-        }
-        if (!(h->read_r2_max > 0.f)) {
-            h->last_error = "InvalidParameter: KDTreeVarDistMatcher: the largest radius of the row must be > 0 (as maxDist)";
-            return ICPMI_ERR_INVALID_ARG;
-        }
-        set_search_bound(h, lc, h->read_r2_max);
-        *d_r2row_out = h->d_read_r2;
-    }
-    lc.sensor_noise = 0;
-    lc.has_read_normals = needs_rn ? 1 : 0;
-    *lc_out = lc;
-    if (n == 0) { // upstream: Trimmed / Median throw "no outlier to filter", otherwise "no point to minimize"
-        bool quant = false;
-        for (int f = 0; f < lc.n_out; ++f) quant |= lc.out_type[f] == ICPMI_OUT_TRIMMEDDIST || lc.out_type[f] == ICPMI_OUT_MEDIANDIST || lc.out_type[f] == ICPMI_OUT_VARTRIMMEDDIST;
-        h->last_error = quant ? "ConvergenceError: no outlier to filter" : "ConvergenceError: ErrorMinimizer: no point to minimize";
-        return quant ? ICPMI_ERR_NO_OUTLIER_TO_FILTER : ICPMI_ERR_NO_POINT_TO_MINIMIZE;
-    }
-    return ICPMI_OK;
+    return chain_setup(h, n, d_n3, have_scalar_n, have_r2_n, 1, lc_out, d_r2row_out, needs_rn_out);
 }
 
 // the pose in the centred frame: [R | t + R mu - mu]
@@ -936,13 +908,23 @@ static icpmi_status residual_poses_impl(icpmi_handle h, const char* who, const f
             st[(size_t)live[i]] = s;
         }
     }
-    icpmi_status first = ICPMI_OK;
-    for (int p = 0; p < n_poses; ++p) {
-        if (status) status[p] = st[(size_t)p];
-        if (st[(size_t)p] != ICPMI_OK && first == ICPMI_OK) first = st[(size_t)p];
-    }
-    if (first != ICPMI_OK) h->last_error = std::string(who) + ": a pose ended with an error (see the per-pose status)";
-    return status ? ICPMI_OK : first;
+    return fold_status(h, status, st.data(), n_poses, (std::string(who) + ": a pose ended with an error (see the per-pose status)").c_str());
+}
+
+// a host reading and its optional normals into the operator scratch (slots 8 and 9): the handle's stage buffers stay what
+// icpmi_register_prior left them
+static icpmi_status stage_in_scratch(icpmi_ctx* h, const float* scan4, int64_t n, const float* normals3, const float** d_scan, const float** d_n3)
+{
+    float4* d_in = scratch_get<float4>(h, 8, (size_t)n);
+    if (!d_in) return ICPMI_ERR_HIP;
+    HIP_TRY(h, hipMemcpyAsync(d_in, scan4, (size_t)n * sizeof(float4), hipMemcpyHostToDevice, h->stream));
+    *d_scan = (const float*)d_in;
+    if (!normals3) return ICPMI_OK;
+    float* d_n = scratch_get<float>(h, 9, (size_t)n * 3);
+    if (!d_n) return ICPMI_ERR_HIP;
+    HIP_TRY(h, hipMemcpyAsync(d_n, normals3, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    *d_n3 = d_n;
+    return ICPMI_OK;
 }
 
 icpmi_status icpmi_residual_error_dev(icpmi_handle h, const float* d_scan4, int64_t n, const float* d_scan_normals3, const float T[16],
@@ -959,19 +941,7 @@ icpmi_status icpmi_residual_error(icpmi_handle h, const float* scan4, int64_t n,
     if (n < 0 || (n > 0 && !scan4)) { h->last_error = "residual_error: bad arguments"; return ICPMI_ERR_INVALID_ARG; }
     const float* d_scan = scan4; // (n == 0 or no map: never dereferenced)
     const float* d_n3 = nullptr;
-    if (n > 0 && h->m > 0) {
-        // staged through the operator scratch: the handle's stage buffers stay what icpmi_register_prior left them
-        float4* d_in = scratch_get<float4>(h, 8, (size_t)n);
-        if (!d_in) return ICPMI_ERR_HIP;
-        HIP_TRY(h, hipMemcpyAsync(d_in, scan4, (size_t)n * sizeof(float4), hipMemcpyHostToDevice, h->stream));
-        d_scan = (const float*)d_in;
-        if (scan_normals3) {
-            float* d_n = scratch_get<float>(h, 9, (size_t)n * 3);
-            if (!d_n) return ICPMI_ERR_HIP;
-            HIP_TRY(h, hipMemcpyAsync(d_n, scan_normals3, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, h->stream));
-            d_n3 = d_n;
-        }
-    }
+    if (n > 0 && h->m > 0) { const icpmi_status ss = stage_in_scratch(h, scan4, n, scan_normals3, &d_scan, &d_n3); if (ss != ICPMI_OK) return ss; }
     return residual_impl(h, "residual_error", d_scan, n, d_n3, T, kind, out);
 }
 
@@ -1000,17 +970,9 @@ icpmi_status icpmi_residual_error_poses(icpmi_handle h, const float* scan4, int6
     };
     const float* d_scan = scan4; // (n == 0, no map or bad arguments: never dereferenced)
     const float* d_n3 = nullptr;
-    if (n > 0 && scan4 && h->m > 0) { // staged through the operator scratch, as icpmi_residual_error: once for all poses
-        float4* d_in = scratch_get<float4>(h, 8, (size_t)n);
-        if (!d_in) { zero_all(); return ICPMI_ERR_HIP; }
-        if (hipMemcpyAsync(d_in, scan4, (size_t)n * sizeof(float4), hipMemcpyHostToDevice, h->stream) != hipSuccess) { zero_all(); h->last_error = "residual_error_poses: the upload failed"; return ICPMI_ERR_HIP; }
-        d_scan = (const float*)d_in;
-        if (scan_normals3) {
-            float* d_n = scratch_get<float>(h, 9, (size_t)n * 3);
-            if (!d_n) { zero_all(); return ICPMI_ERR_HIP; }
-            if (hipMemcpyAsync(d_n, scan_normals3, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, h->stream) != hipSuccess) { zero_all(); h->last_error = "residual_error_poses: the upload failed"; return ICPMI_ERR_HIP; }
-            d_n3 = d_n;
-        }
+    if (n > 0 && scan4 && h->m > 0) { // once for all poses
+        const icpmi_status ss = stage_in_scratch(h, scan4, n, scan_normals3, &d_scan, &d_n3);
+        if (ss != ICPMI_OK) { zero_all(); return ss; }
     }
     return residual_poses_impl(h, "residual_error_poses", d_scan, n, d_n3, T, n_poses, kind, out, status, batched);
 }
@@ -1065,13 +1027,7 @@ icpmi_status icpmi_register_multistart_dev(icpmi_handle h, const float* d_scan4,
     }
     h->cov_ready = false; // (no covariance per start, as after any batch)
     h->degen_ready = false;
-    icpmi_status first = ICPMI_OK;
-    for (int s = 0; s < n_starts; ++s) {
-        if (status) status[s] = st[s];
-        if (st[s] != ICPMI_OK && first == ICPMI_OK) first = st[s];
-    }
-    if (first != ICPMI_OK) h->last_error = "register_multistart: a start ended with an error (see the per-start status)";
-    return status ? ICPMI_OK : first;
+    return fold_status(h, status, st, n_starts, "register_multistart: a start ended with an error (see the per-start status)");
 }
 
 icpmi_status icpmi_register_multistart(icpmi_handle h, const float* scan4, int64_t n, const float* priors, int32_t n_starts,
@@ -1131,12 +1087,8 @@ static icpmi_status knn_impl(icpmi_handle h, const float* q4, int64_t n, int32_t
         h->qsorted_n = -1; h->qsorted_src = nullptr;
     }
     LoopCfg lc = make_loop_cfg(h, 1);
-    lc.k = k; lc.max_dist = max_dist;
-    lc.maxr2 = squared_radius(max_dist);
-    if (std::isfinite(max_dist)) {
-        const int need = (int)ceilf(max_dist / h->grid.cell) + 1;
-        lc.ring_max = need < 16 ? need : 16;
-    } else lc.ring_max = 6;
+    lc.k = k;
+    set_search_bound(h, lc, max_dist); // (m > 0 here, and every index that was built has grid.cell > 0: map_build.hip clamp_cell)
     icpmi_status s = nn_launch_k(h, req, h->d_reading, n, nullptr, lc, allow_self, h->d_sidx, h->d_d2, h->d_state);
     if (s != ICPMI_OK) return s;
     DevBuf<int> d_ids;

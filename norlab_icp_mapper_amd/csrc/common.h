@@ -193,6 +193,16 @@ struct LoopCfg {
     float degen_thr;          // |degeneracy_threshold|
     double* degen_blk;        // the handle's side block (layout below), null when off
 };
+// slot of the chain's Trimmed / Median / VarTrimmed filter (the last of them: the one whose limit a call reports), or -1.  Upstream, a
+// chain with one throws "no outlier to filter" on an empty reading where any other throws "no point to minimize".
+static inline int quantile_slot(const LoopCfg& lc)
+{
+    int slot = -1;
+    for (int f = 0; f < lc.n_out; ++f)
+        if (lc.out_type[f] == ICPMI_OUT_TRIMMEDDIST || lc.out_type[f] == ICPMI_OUT_MEDIANDIST || lc.out_type[f] == ICPMI_OUT_VARTRIMMEDDIST) slot = f;
+    return slot;
+}
+static inline bool chain_has_quantile(const LoopCfg& lc) { return quantile_slot(lc) >= 0; }
 
 // the side block of the degeneracy-aware solve (icpmi_ctx::d_degen), in doubles
 #define ICPMI_DG_REPORT 1
@@ -1137,6 +1147,19 @@ icpmi_status loop_residual_poses(icpmi_ctx* c, const float4* d_scan, int64_t n, 
 icpmi_status loop_outlier_weights(icpmi_ctx* c, const LoopCfg& lc, const float* d2, const int32_t* ids, int k, int64_t n,
                                   const float* read_normals3, float* weights, float* limit_out);
 LoopCfg make_loop_cfg(const icpmi_ctx* c, int fixed_iterations);
+// How a call over many items (the readings of a batch, the starts of a multistart, the poses of a residual call) ends: per_item goes to
+// status_out when the caller took that array, and the call then returns OK; otherwise it returns the first error.  text: what last_error
+// says when an item failed (null: the failed item's own words stay)
+static inline icpmi_status fold_status(icpmi_ctx* c, icpmi_status* status_out, const icpmi_status* per_item, int count, const char* text)
+{
+    icpmi_status first = ICPMI_OK;
+    for (int i = 0; i < count; ++i) {
+        if (status_out) status_out[i] = per_item[i];
+        if (per_item[i] != ICPMI_OK && first == ICPMI_OK) first = per_item[i];
+    }
+    if (first != ICPMI_OK && text) c->last_error = text;
+    return status_out ? ICPMI_OK : first;
+}
 
 // ---- shared by the operator files: pointops.hip (a caller's cloud), dynpts.hip (DynamicPoints), ops.hip (the resident map) ----
 // A 4 x 4 (col-major) as a kernel ARGUMENT: the matrix rides in the kernarg segment (scalar loads), no device copy of it and no upload

@@ -1475,19 +1475,6 @@ static int acc_blocks(int64_t count, int bt = 256)
     return (int)(nb < 1 ? 1 : (nb > cap ? cap : nb));
 }
 
-// n = points per slice, nscan slices (a single registration: one slice of n points)
-static icpmi_status ensure_loop_buffers(icpmi_ctx* c, int64_t n, int k, int nscan = 1)
-{
-    const size_t cnt = (size_t)n * k * nscan + 1;
-    if (c->d_sidx.ensure(c, cnt) != ICPMI_OK) return ICPMI_ERR_HIP;
-    if (c->d_d2.ensure(c, cnt) != ICPMI_OK) return ICPMI_ERR_HIP;
-    if (c->d_hard.ensure(c, (size_t)n * nscan + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
-    if (k == 1 && c->d_match_pt.ensure(c, (size_t)n * nscan + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
-    if (c->d_selhist.ensure(c, (size_t)ICPMI_SELHIST_WORDS * nscan) != ICPMI_OK) return ICPMI_ERR_HIP;
-    return ICPMI_OK;
-}
-
-
 // scratch of the VarTrimmedDist passes (operator scratch slots 0..4, shared with the map-side operators: never live at the
 // same time on one handle); reserved before a capture starts, looked up again -- same pointers -- when the passes are enqueued
 struct VtBuffers { unsigned long long* keys; unsigned* vals; unsigned* tab; double* sums; double* best_val; long long* best_idx; int nchunks; };
@@ -1506,6 +1493,21 @@ static icpmi_status vt_buffers(icpmi_ctx* c, int64_t count, VtBuffers* b)
     b->best_idx = scratch_get<long long>(c, 4, (size_t)b->nchunks + 1);
     if (!b->keys || !b->vals || !b->tab || !b->sums || !b->best_idx) return ICPMI_ERR_HIP;
     b->best_val = b->sums + b->nchunks + 1;
+    return ICPMI_OK;
+}
+
+// everything the loop's launches for chain lc write to: n = points per slice, nscan slices (a single registration: one slice of n points).
+// The VarTrimmedDist scratch is reserved here too, so that enqueue_selection cannot fail (such a chain never takes a batch).
+static icpmi_status ensure_loop_buffers(icpmi_ctx* c, int64_t n, const LoopCfg& lc, int nscan = 1)
+{
+    const size_t cnt = (size_t)n * lc.k * nscan + 1;
+    if (c->d_sidx.ensure(c, cnt) != ICPMI_OK) return ICPMI_ERR_HIP;
+    if (c->d_d2.ensure(c, cnt) != ICPMI_OK) return ICPMI_ERR_HIP;
+    if (c->d_hard.ensure(c, (size_t)n * nscan + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
+    if (lc.k == 1 && c->d_match_pt.ensure(c, (size_t)n * nscan + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
+    if (c->d_selhist.ensure(c, (size_t)ICPMI_SELHIST_WORDS * nscan) != ICPMI_OK) return ICPMI_ERR_HIP;
+    VtBuffers vb;
+    if (chain_has_vartrimmed(lc) && vt_buffers(c, n * lc.k, &vb) != ICPMI_OK) return ICPMI_ERR_HIP;
     return ICPMI_OK;
 }
 
@@ -1678,15 +1680,40 @@ static NnRequest loop_request(icpmi_ctx* c, const LoopCfg& lc, const BatchArgs& 
     return req;
 }
 
-// iteration req.iter of the loop: match, select, accumulate, solve; *nn = what the matcher's launch answered
+// the chain as the entry points that run ONE pass of it see it: one iteration, no checkers
+static LoopCfg one_pass_cfg(const LoopCfg& lc)
+{
+    LoopCfg l1 = lc;
+    l1.max_iter = 1; l1.use_diff = 0; l1.use_bound = 0;
+    return l1;
+}
+
+// nstates fresh loop states outside a registration (no sequence number, no progress word) and their cleared selection histograms;
+// d_T0: one pose of 16 floats per state, null = identity
+static icpmi_status enqueue_fresh_states(icpmi_ctx* c, int nstates, const float* d_T0)
+{
+    hipLaunchKernelGGL(init_state_kernel, dim3(nstates), dim3(64), 0, c->stream, c->d_state, d_T0, 0u, (unsigned*)nullptr, (const unsigned*)nullptr, 16);
+    HIP_TRY(c, hipMemsetAsync(c->d_selhist, 0, (size_t)ICPMI_SELHIST_WORDS * nstates * sizeof(unsigned), c->stream));
+    return ICPMI_OK;
+}
+
+// the front of an iteration: the matcher's launch under the states' T_iter, then the chain's selections; *nn = what the launch answered.
+// matched: recorded between the two (a profiled registration times its matcher)
+static icpmi_status enqueue_match_select(icpmi_ctx* c, int64_t n, const LoopCfg& lc, const NnRequest& req, NnOutcome* nn, hipEvent_t matched = nullptr)
+{
+    const icpmi_status s = nn_launch_k(c, req, c->d_reading, n, c->d_state->T_iter, lc, 1, c->d_sidx, c->d_d2, c->d_state, nn);
+    if (s != ICPMI_OK) return s;
+    if (matched) HIP_TRY(c, hipEventRecord(matched, c->stream));
+    enqueue_selection(c, lc, n * lc.k, req.batch, *nn);
+    return ICPMI_OK;
+}
+
+// iteration req.iter of the loop: match, select, accumulate, solve
 static icpmi_status enqueue_iteration(icpmi_ctx* c, int64_t n, const LoopCfg& lc, const NnRequest& req, NnOutcome* nn, hipEvent_t nn0, hipEvent_t nn1,
                                       bool publish = true)
 {
     if (nn0) HIP_TRY(c, hipEventRecord(nn0, c->stream));
-    icpmi_status s = nn_launch_k(c, req, c->d_reading, n, c->d_state->T_iter, lc, 1, c->d_sidx, c->d_d2, c->d_state, nn);
-    if (s != ICPMI_OK) return s;
-    if (nn1) HIP_TRY(c, hipEventRecord(nn1, c->stream));
-    enqueue_selection(c, lc, n * lc.k, req.batch, *nn);
+    { const icpmi_status s = enqueue_match_select(c, n, lc, req, nn, nn1); if (s != ICPMI_OK) return s; }
     // (icpmi_debug_keep_sums: the sums of every counted iteration of a SINGLE registration; a batch's solves would all write the one block)
     enqueue_accumulate_solve(c, n, lc, req.batch, *nn, nullptr, req.batch.nscan > 1 ? nullptr : c->d_keep_sums.get(), publish);
     HIP_TRY(c, hipGetLastError());
@@ -1703,9 +1730,8 @@ static void fill_stats(const IcpState* hs, const LoopCfg& lc, int64_t n, icpmi_s
     const double denom = (double)lc.k * (double)n;
     stats->point_used_ratio = denom > 0 ? (float)hs->pairs / (float)denom : 0.f;
     stats->weighted_point_used_ratio = denom > 0 ? (float)(hs->wsum / denom) : 0.f;
-    stats->trimmed_limit = -1.f;
-    for (int f = 0; f < lc.n_out; ++f)
-        if (lc.out_type[f] == ICPMI_OUT_TRIMMEDDIST || lc.out_type[f] == ICPMI_OUT_MEDIANDIST || lc.out_type[f] == ICPMI_OUT_VARTRIMMEDDIST) stats->trimmed_limit = hs->limits[f];
+    const int q = quantile_slot(lc);
+    stats->trimmed_limit = q >= 0 ? hs->limits[q] : -1.f;
     stats->hard_queries = (int64_t)hs->hard_total;
     stats->sensor_noise_overlap = -1.f; // "not computed" unless loop_run's sensor-noise pass overwrites it
     for (int i = 0; i < 2 && with_dbg; ++i) { stats->reserved[2 * i] = (int32_t)(hs->dbg[i] & 0xffffffffu); stats->reserved[2 * i + 1] = (int32_t)(hs->dbg[i] >> 32); }
@@ -1803,8 +1829,7 @@ icpmi_status loop_run(icpmi_ctx* c, const float4* d_scan, const float* d_normals
     LoopCfg lc = lc_in;
     c->last_match_n = 0; c->cov_ready = false; c->cov_kept = false; c->degen_ready = false;
     // all allocations up front: none may happen while the stream is capturing
-    if (ensure_loop_buffers(c, n, lc.k) != ICPMI_OK) return ICPMI_ERR_HIP;
-    if (chain_has_vartrimmed(lc)) { VtBuffers vb; if (vt_buffers(c, n * lc.k, &vb) != ICPMI_OK) return ICPMI_ERR_HIP; }
+    if (ensure_loop_buffers(c, n, lc) != ICPMI_OK) return ICPMI_ERR_HIP;
     if (c->d_reading.ensure(c, (size_t)n + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
     if (d_normals3 && c->d_read_normals.ensure(c, (size_t)n + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
     if (c->cfg.knn <= 8 && sort_queries_reserve(c, n) != ICPMI_OK) return ICPMI_ERR_HIP;
@@ -2074,29 +2099,20 @@ icpmi_status loop_run_batch(icpmi_ctx* c, int B, const float* const* d_scans4, c
     ba.nscan = B; ba.qstride = (int)NS;
     for (int b = 0; b < B; ++b) { ba.n[b] = (int)nn[b]; src.p[b] = (const float4*)d_scans4[b]; }
     // all allocations up front: none may happen while the stream is capturing
-    if (ensure_loop_buffers(c, NS, lc.k, B) != ICPMI_OK) return ICPMI_ERR_HIP;
+    if (ensure_loop_buffers(c, NS, lc, B) != ICPMI_OK) return ICPMI_ERR_HIP;
     if (c->d_reading.ensure(c, (size_t)NS * B + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
     if (sort_queries_reserve(c, NS, B) != ICPMI_OK) return ICPMI_ERR_HIP;
     struct Scope { icpmi_ctx* c; ~Scope() { c->qsorted_n = -1; c->qsorted_src = nullptr; } } scope{c};
     NnRequest req = loop_request(c, lc, ba, nullptr); // (no var-dist row: such a chain registers its readings one by one)
     NnOutcome last; // (of the eager iterations; nothing behind the loop reads a batch's matches)
 
+    // centring, loop states and selection histograms ride in the kernels of the query sort (no reading of a batch is empty: api.hip sends
+    // such a batch through the one-by-one route)
     auto head = [&]() -> icpmi_status {
-        const int blocks = (int)((nmax + 255) / 256);
-        if (nmax > 0) {
-            c->reg_seq = (c->reg_seq + 1) & 0x7ffffu;
-            SortHead h; h.raw = src; h.mean[0] = c->mean[0]; h.mean[1] = c->mean[1]; h.mean[2] = c->mean[2];
-            h.st = c->d_state; h.seq = c->reg_seq; h.progress = c->d_progress; h.seq_src = nullptr; h.selhist = c->d_selhist;
-            return sort_queries_batch(c, c->d_reading, ba, &h);
-        }
-        hipLaunchKernelGGL(centre_kernel, dim3(blocks, B), dim3(256), 0, c->stream, src, ba, c->mean[0], c->mean[1], c->mean[2], c->d_reading);
-        icpmi_status s = sort_queries_batch(c, c->d_reading, ba);
-        if (s != ICPMI_OK) return s;
         c->reg_seq = (c->reg_seq + 1) & 0x7ffffu;
-        hipLaunchKernelGGL(init_state_kernel, dim3(B), dim3(64), 0, c->stream, c->d_state, (const float*)nullptr, c->reg_seq, c->d_progress);
-        HIP_TRY(c, hipMemsetAsync(c->d_selhist, 0, (size_t)ICPMI_SELHIST_WORDS * B * sizeof(unsigned), c->stream));
-        HIP_TRY(c, hipGetLastError());
-        return ICPMI_OK;
+        SortHead h; h.raw = src; h.mean[0] = c->mean[0]; h.mean[1] = c->mean[1]; h.mean[2] = c->mean[2];
+        h.st = c->d_state; h.seq = c->reg_seq; h.progress = c->d_progress; h.seq_src = nullptr; h.selhist = c->d_selhist;
+        return sort_queries_batch(c, c->d_reading, ba, &h);
     };
 
     const bool graph = c->cfg.use_graph != 0 && fixed && c->cfg.profile == 0;
@@ -2155,43 +2171,35 @@ icpmi_status loop_run_batch(icpmi_ctx* c, int B, const float* const* d_scans4, c
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     float ms = 0.f;
     (void)hipEventElapsedTime(&ms, c->ev0, c->ev1);
-    icpmi_status first = ICPMI_OK;
+    icpmi_status sb[ICPMI_MAX_BATCH];
     for (int b = 0; b < B; ++b) {
-        icpmi_status sb = ICPMI_OK;
-        batch_result(c, lc, c->h_state + b, nn[b], T_out + 16 * b, stats ? stats + b : nullptr, &sb);
+        batch_result(c, lc, c->h_state + b, nn[b], T_out + 16 * b, stats ? stats + b : nullptr, &sb[b]);
         if (stats) stats[b].loop_ms = ms;
-        if (status) status[b] = sb;
-        if (sb != ICPMI_OK && first == ICPMI_OK) { first = sb; c->last_error = "register_batch: a reading ended with a convergence error (see the per-reading status)"; }
     }
-    return status ? ICPMI_OK : first;
+    return fold_status(c, status, sb, B, "register_batch: a reading ended with a convergence error (see the per-reading status)");
 }
 
 icpmi_status loop_single_step(icpmi_ctx* c, int64_t n, const LoopCfg& lc, const float* T_iter_host, float T_step[16],
                               double sums[32], icpmi_stats* stats)
 {
-    if (ensure_loop_buffers(c, n, lc.k) != ICPMI_OK) return ICPMI_ERR_HIP;
-    if (chain_has_vartrimmed(lc)) { VtBuffers vb; if (vt_buffers(c, n * lc.k, &vb) != ICPMI_OK) return ICPMI_ERR_HIP; } // reserved here: enqueue_selection cannot fail
+    if (ensure_loop_buffers(c, n, lc) != ICPMI_OK) return ICPMI_ERR_HIP;
     DevBuf<float> d_Tstep; // [0,16): T_step out, [16,32): T_iter in
     DevBuf<double> d_sums;
     HIP_TRY(c, d_Tstep.alloc(32));
     HIP_TRY(c, d_sums.alloc(ICPMI_NV));
     float* d_T0 = d_Tstep.get() + 16;
     if (T_iter_host) HIP_TRY(c, hipMemcpyAsync(d_T0, T_iter_host, 16 * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(init_state_kernel, dim3(1), dim3(64), 0, c->stream, c->d_state, T_iter_host ? (const float*)d_T0 : (const float*)nullptr, 0u,
-                       (unsigned*)nullptr);
-    HIP_TRY(c, hipMemsetAsync(c->d_selhist, 0, ICPMI_SELHIST_WORDS * sizeof(unsigned), c->stream));
+    { const icpmi_status is = enqueue_fresh_states(c, 1, T_iter_host ? d_T0 : nullptr); if (is != ICPMI_OK) return is; }
     HIP_TRY(c, hipMemsetAsync(d_Tstep, 0, 16 * sizeof(float), c->stream));
-    LoopCfg l1 = lc;
-    l1.max_iter = 1; l1.use_diff = 0; l1.use_bound = 0;
+    const LoopCfg l1 = one_pass_cfg(lc);
     c->degen_ready = false;
     { const icpmi_status ds = loop_degen_stats(c, n, l1); if (ds != ICPMI_OK) return ds; } // (the reading is in d_reading, centred by the caller)
     NnRequest req; // (one unseeded launch that answers in the caller's order)
     req.hist0 = fused_filter_slot(l1) >= 0 ? c->d_selhist.get() : nullptr;
     req.batch = batch_of_one(n);
     NnOutcome nn;
-    icpmi_status s = nn_launch_k(c, req, c->d_reading, n, c->d_state->T_iter, l1, 1, c->d_sidx, c->d_d2, c->d_state, &nn);
+    const icpmi_status s = enqueue_match_select(c, n, l1, req, &nn);
     if (s == ICPMI_OK) {
-        enqueue_selection(c, l1, n * l1.k, req.batch, nn);
         enqueue_accumulate_solve(c, n, l1, req.batch, nn, d_Tstep, d_sums);
         if (l1.degen) (void)loop_degen_report(c, l1); // (an error state leaves the sums of an earlier call: degen_ready stays false below)
     }
@@ -2360,14 +2368,31 @@ static icpmi_status res_block_out(icpmi_ctx* c, const ResBlock& hr, int k, int64
     return ICPMI_OK;
 }
 
+// the two passes behind enqueue_match_select: the partials of ba's poses into d_part, their result blocks into d_res (one per pose)
+static icpmi_status enqueue_residual_sums(icpmi_ctx* c, const BatchArgs& ba, const LoopCfg& l1, int kind, int planar, const NnOutcome& nn, double* d_part,
+                                          ResBlock* d_res)
+{
+    const int slot = fused_filter_slot(l1);
+    const bool sorted = nn.out_sorted;
+    hipLaunchKernelGGL(res_pairs_kernel, dim3(ICPMI_RES_NB, ba.nscan), dim3(256), 0, c->stream, sorted ? (const float4*)c->d_qsorted : (const float4*)c->d_reading,
+                       sorted ? (const int*)c->d_qindex : (const int*)nullptr, ba, l1, kind, planar, c->d_state, (const float4*)c->d_map_sorted,
+                       c->has_normals ? (const float4*)c->d_normals_sorted : (const float4*)nullptr,
+                       l1.has_read_normals ? (const float4*)c->d_read_normals : (const float4*)nullptr,
+                       (l1.ext && c->raw_has_scalar) ? (const float*)c->d_raw_s : (const float*)nullptr, (const int*)c->d_sidx, (const float*)c->d_d2,
+                       (sorted && l1.k == 1) ? (const float4*)c->d_match_pt : (const float4*)nullptr, (const unsigned*)c->d_selhist, slot >= 0 ? slot : -1,
+                       (slot >= 0 && l1.out_type[slot] == ICPMI_OUT_MEDIANDIST) ? 1 : 0, slot >= 0 ? l1.out_param[slot] : 0.f, d_part);
+    hipLaunchKernelGGL(res_finish_kernel, dim3(ba.nscan), dim3(64), 0, c->stream, (const double*)d_part, (const IcpState*)c->d_state, quantile_slot(l1), d_res);
+    HIP_TRY(c, hipGetLastError());
+    return ICPMI_OK;
+}
+
 // the centred reading is in c->d_reading (loop_prepare_reading); T_host = the pose in the centred frame (column-major), kind 1 or 2
 icpmi_status loop_residual(icpmi_ctx* c, int64_t n, const LoopCfg& lc, const float T_host[16], int kind, int planar, const float* d_r2row,
                            icpmi_residual* out)
 {
     // the covariance of the registration before this call lives in d_cov, which nothing here touches: it stays readable
     const bool cov_keep = c->cov_ready && (c->last_match_n != 0 || c->cov_kept);
-    if (ensure_loop_buffers(c, n, lc.k) != ICPMI_OK) return ICPMI_ERR_HIP;
-    if (chain_has_vartrimmed(lc)) { VtBuffers vb; if (vt_buffers(c, n * lc.k, &vb) != ICPMI_OK) return ICPMI_ERR_HIP; } // reserved here: enqueue_selection cannot fail
+    if (ensure_loop_buffers(c, n, lc) != ICPMI_OK) return ICPMI_ERR_HIP;
     // scratch 5: the partials, the result block, the pose
     constexpr size_t RES_DOUBLES = (sizeof(ResBlock) + sizeof(double) - 1) / sizeof(double);
     double* d_part = scratch_get<double>(c, 5, (size_t)ICPMI_RES_NB * ICPMI_RES_NV + RES_DOUBLES + 8);
@@ -2375,29 +2400,12 @@ icpmi_status loop_residual(icpmi_ctx* c, int64_t n, const LoopCfg& lc, const flo
     ResBlock* d_res = reinterpret_cast<ResBlock*>(d_part + ICPMI_RES_NB * ICPMI_RES_NV);
     float* d_T0 = reinterpret_cast<float*>(d_part + ICPMI_RES_NB * ICPMI_RES_NV + RES_DOUBLES);
     { const icpmi_status us = upload_small(c, d_T0, T_host, 16 * sizeof(float)); if (us != ICPMI_OK) return us; }
-    hipLaunchKernelGGL(init_state_kernel, dim3(1), dim3(64), 0, c->stream, c->d_state, (const float*)d_T0, 0u, (unsigned*)nullptr);
-    HIP_TRY(c, hipMemsetAsync(c->d_selhist, 0, ICPMI_SELHIST_WORDS * sizeof(unsigned), c->stream));
-    LoopCfg l1 = lc;
-    l1.max_iter = 1; l1.use_diff = 0; l1.use_bound = 0;
-    NnRequest req = loop_request(c, l1, batch_of_one(n), d_r2row); // (iter 0: what a registration's first iteration asks of the matcher)
+    { const icpmi_status is = enqueue_fresh_states(c, 1, d_T0); if (is != ICPMI_OK) return is; }
+    const LoopCfg l1 = one_pass_cfg(lc);
+    const NnRequest req = loop_request(c, l1, batch_of_one(n), d_r2row); // (iter 0: what a registration's first iteration asks of the matcher)
     NnOutcome nn;
-    const icpmi_status s = nn_launch_k(c, req, c->d_reading, n, c->d_state->T_iter, l1, 1, c->d_sidx, c->d_d2, c->d_state, &nn);
-    if (s != ICPMI_OK) return s;
-    enqueue_selection(c, l1, n * l1.k, req.batch, nn);
-    const int slot = fused_filter_slot(l1);
-    int limit_slot = -1;
-    for (int f = 0; f < l1.n_out; ++f)
-        if (l1.out_type[f] == ICPMI_OUT_TRIMMEDDIST || l1.out_type[f] == ICPMI_OUT_MEDIANDIST || l1.out_type[f] == ICPMI_OUT_VARTRIMMEDDIST) limit_slot = f;
-    const bool sorted = nn.out_sorted;
-    hipLaunchKernelGGL(res_pairs_kernel, dim3(ICPMI_RES_NB), dim3(256), 0, c->stream, sorted ? (const float4*)c->d_qsorted : (const float4*)c->d_reading,
-                       sorted ? (const int*)c->d_qindex : (const int*)nullptr, batch_of_one(n), l1, kind, planar, c->d_state, (const float4*)c->d_map_sorted,
-                       c->has_normals ? (const float4*)c->d_normals_sorted : (const float4*)nullptr,
-                       l1.has_read_normals ? (const float4*)c->d_read_normals : (const float4*)nullptr,
-                       (l1.ext && c->raw_has_scalar) ? (const float*)c->d_raw_s : (const float*)nullptr, (const int*)c->d_sidx, (const float*)c->d_d2,
-                       (sorted && l1.k == 1) ? (const float4*)c->d_match_pt : (const float4*)nullptr, (const unsigned*)c->d_selhist, slot >= 0 ? slot : -1,
-                       (slot >= 0 && l1.out_type[slot] == ICPMI_OUT_MEDIANDIST) ? 1 : 0, slot >= 0 ? l1.out_param[slot] : 0.f, d_part);
-    hipLaunchKernelGGL(res_finish_kernel, dim3(1), dim3(64), 0, c->stream, (const double*)d_part, (const IcpState*)c->d_state, limit_slot, d_res);
-    HIP_TRY(c, hipGetLastError());
+    { const icpmi_status s = enqueue_match_select(c, n, l1, req, &nn); if (s != ICPMI_OK) return s; }
+    { const icpmi_status s = enqueue_residual_sums(c, req.batch, l1, kind, planar, nn, d_part, d_res); if (s != ICPMI_OK) return s; }
     ResBlock hr;
     if (read_back(c, &hr, d_res, sizeof hr) != ICPMI_OK) return ICPMI_ERR_HIP;
     c->cov_kept = cov_keep; // (the matcher's launch dropped last_match_n: icpmi_debug_last_matches has nothing to read any more)
@@ -2425,7 +2433,7 @@ icpmi_status loop_residual_poses(icpmi_ctx* c, const float4* d_scan, int64_t n, 
     const int B = n_poses < ICPMI_MAX_BATCH ? n_poses : ICPMI_MAX_BATCH;
     const int64_t NS = (n + 63) / 64 * 64; // slice stride of the per-query arrays, as loop_run_batch
     // all allocations before the first launch (a later one could move the sorted reading)
-    if (ensure_loop_buffers(c, NS, lc.k, B) != ICPMI_OK) return ICPMI_ERR_HIP;
+    if (ensure_loop_buffers(c, NS, lc, B) != ICPMI_OK) return ICPMI_ERR_HIP;
     if (c->d_reading.ensure(c, (size_t)n + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
     if (sort_queries_reserve(c, NS, B) != ICPMI_OK) return ICPMI_ERR_HIP;
     // scratch 5: the partials of one chunk, then per pose its result block and its pose
@@ -2443,35 +2451,17 @@ icpmi_status loop_residual_poses(icpmi_ctx* c, const float4* d_scan, int64_t n, 
     if (B > 1)
         hipLaunchKernelGGL(res_replicate_kernel, dim3((int)((n + 255) / 256), B - 1), dim3(256), 0, c->stream, c->d_qsorted.get(), c->d_qindex.get(),
                            (int)n, (int)NS);
-    LoopCfg l1 = lc;
-    l1.max_iter = 1; l1.use_diff = 0; l1.use_bound = 0;
-    const int slot = fused_filter_slot(l1);
-    int limit_slot = -1;
-    for (int f = 0; f < l1.n_out; ++f)
-        if (l1.out_type[f] == ICPMI_OUT_TRIMMEDDIST || l1.out_type[f] == ICPMI_OUT_MEDIANDIST || l1.out_type[f] == ICPMI_OUT_VARTRIMMEDDIST) limit_slot = f;
+    const LoopCfg l1 = one_pass_cfg(lc);
     for (int p0 = 0; p0 < n_poses; p0 += B) {
         const int Bc = n_poses - p0 < B ? n_poses - p0 : B;
         BatchArgs ba; memset(&ba, 0, sizeof ba);
         ba.nscan = Bc; ba.qstride = Bc > 1 ? (int)NS : 0;
         for (int b = 0; b < Bc; ++b) ba.n[b] = (int)n;
-        hipLaunchKernelGGL(init_state_kernel, dim3(Bc), dim3(64), 0, c->stream, c->d_state, (const float*)(d_T + 16 * (size_t)p0), 0u, (unsigned*)nullptr,
-                           (const unsigned*)nullptr, 16);
-        HIP_TRY(c, hipMemsetAsync(c->d_selhist, 0, (size_t)ICPMI_SELHIST_WORDS * Bc * sizeof(unsigned), c->stream));
-        NnRequest req = loop_request(c, l1, ba, nullptr); // (iter 0: what a registration's first iteration asks of the matcher)
+        { const icpmi_status is = enqueue_fresh_states(c, Bc, d_T + 16 * (size_t)p0); if (is != ICPMI_OK) return is; }
+        const NnRequest req = loop_request(c, l1, ba, nullptr); // (iter 0: what a registration's first iteration asks of the matcher)
         NnOutcome nn;
-        const icpmi_status s = nn_launch_k(c, req, c->d_reading, n, c->d_state->T_iter, l1, 1, c->d_sidx, c->d_d2, c->d_state, &nn);
-        if (s != ICPMI_OK) return s;
-        enqueue_selection(c, l1, n * l1.k, ba, nn);
-        const bool sorted = nn.out_sorted;
-        hipLaunchKernelGGL(res_pairs_kernel, dim3(ICPMI_RES_NB, Bc), dim3(256), 0, c->stream, sorted ? (const float4*)c->d_qsorted : (const float4*)c->d_reading,
-                           sorted ? (const int*)c->d_qindex : (const int*)nullptr, ba, l1, kind, planar, c->d_state, (const float4*)c->d_map_sorted,
-                           c->has_normals ? (const float4*)c->d_normals_sorted : (const float4*)nullptr,
-                           l1.has_read_normals ? (const float4*)c->d_read_normals : (const float4*)nullptr,
-                           (l1.ext && c->raw_has_scalar) ? (const float*)c->d_raw_s : (const float*)nullptr, (const int*)c->d_sidx, (const float*)c->d_d2, (sorted && l1.k == 1) ? (const float4*)c->d_match_pt : (const float4*)nullptr,
-                           (const unsigned*)c->d_selhist, slot >= 0 ? slot : -1, (slot >= 0 && l1.out_type[slot] == ICPMI_OUT_MEDIANDIST) ? 1 : 0,
-                           slot >= 0 ? l1.out_param[slot] : 0.f, d_part);
-        hipLaunchKernelGGL(res_finish_kernel, dim3(Bc), dim3(64), 0, c->stream, (const double*)d_part, (const IcpState*)c->d_state, limit_slot, d_res + p0);
-        HIP_TRY(c, hipGetLastError());
+        { const icpmi_status s = enqueue_match_select(c, n, l1, req, &nn); if (s != ICPMI_OK) return s; }
+        { const icpmi_status s = enqueue_residual_sums(c, ba, l1, kind, planar, nn, d_part, d_res + p0); if (s != ICPMI_OK) return s; }
     }
     if (read_back(c, hr.data(), d_res, sizeof(ResBlock) * (size_t)n_poses) != ICPMI_OK) return ICPMI_ERR_HIP;
     c->cov_kept = cov_keep;
@@ -2519,11 +2509,9 @@ icpmi_status loop_outlier_weights(icpmi_ctx* c, const LoopCfg& lc, const float* 
         needs_ids |= lc.out_type[f] == ICPMI_OUT_GENERICDESCRIPTOR || lc.out_type[f] == ICPMI_OUT_ROBUST || lc.out_type[f] == ICPMI_OUT_SURFACENORMAL;
     }
     const int64_t count = (int64_t)k * n;
-    if (ensure_loop_buffers(c, n, k) != ICPMI_OK) return ICPMI_ERR_HIP;
-    if (chain_has_vartrimmed(lc)) { VtBuffers vb; if (vt_buffers(c, (int64_t)k * n, &vb) != ICPMI_OK) return ICPMI_ERR_HIP; }
     LoopCfg l1 = lc; l1.k = k;
-    hipLaunchKernelGGL(init_state_kernel, dim3(1), dim3(64), 0, c->stream, c->d_state, (const float*)nullptr, 0u, (unsigned*)nullptr);
-    HIP_TRY(c, hipMemsetAsync(c->d_selhist, 0, ICPMI_SELHIST_WORDS * sizeof(unsigned), c->stream));
+    if (ensure_loop_buffers(c, n, l1) != ICPMI_OK) return ICPMI_ERR_HIP;
+    { const icpmi_status is = enqueue_fresh_states(c, 1, nullptr); if (is != ICPMI_OK) return is; }
     HIP_TRY(c, hipMemcpyAsync(c->d_d2, d2, (size_t)count * sizeof(float), hipMemcpyHostToDevice, c->stream));
     if (needs_ids && ids) HIP_TRY(c, hipMemcpyAsync(c->d_sidx, ids, (size_t)count * sizeof(int), hipMemcpyHostToDevice, c->stream));
     else HIP_TRY(c, hipMemsetAsync(c->d_sidx, 0, (size_t)count * sizeof(int), c->stream));
@@ -2543,8 +2531,9 @@ icpmi_status loop_outlier_weights(icpmi_ctx* c, const LoopCfg& lc, const float* 
     if (c->h_state->error) { c->last_error = "ConvergenceError: no outlier to filter"; return (icpmi_status)c->h_state->error; }
     if (limit_out) {
         *limit_out = -1.f;
+        const int q = quantile_slot(l1); // (... or the scale of a Robust filter behind it)
         for (int f = 0; f < l1.n_out; ++f)
-            if (l1.out_type[f] == ICPMI_OUT_TRIMMEDDIST || l1.out_type[f] == ICPMI_OUT_MEDIANDIST || l1.out_type[f] == ICPMI_OUT_VARTRIMMEDDIST) *limit_out = c->h_state->limits[f];
+            if (f == q) *limit_out = c->h_state->limits[f];
             else if (l1.out_type[f] == ICPMI_OUT_ROBUST && ((l1.out_iparam[f] >> 4) & 15) != ICPMI_SCALE_NONE) *limit_out = c->h_state->robust_scale;
     }
     return ICPMI_OK;
