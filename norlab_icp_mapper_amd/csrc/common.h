@@ -54,7 +54,7 @@
 #define ICPMI_ACC_IDX(copy, i, limb) ((((copy) * ICPMI_NV + (i)) * 2 + (limb)) * ICPMI_ACC_PAD)
 #define ICPMI_ACC_FLAG (ICPMI_ACC_IDX(0, 0, 0) + 8)                    // a non-finite partial was met (NaN must reach the solver: ICPMI_ERR_NAN)
 #define ICPMI_S2_ACC (ICPMI_S2_F1 + 65536)                             // u32 word offset of the accumulators (128-byte aligned)
-// (r5) Speculative level 0 for the k > 1 loop (nnk_wg_kernel builds it, loop.hip: win_lookup reads it).  The 16-bit prefix the selection
+// (r5) Speculative level 0 for the k > 1 loop (nnk_wg_kernel builds it, select.hip: win_lookup reads it).  The 16-bit prefix the selection
 // picks moves by a fraction of a bin from one iteration to the next once the registration settles, and the stand-alone level-0 builder
 // costs 10.7 us per iteration at knn 6 (116 k device atomics: DESIGN 11.6, 12.8).  So the NN kernel counts its own k x 64 distances into
 // ICPMI_WIN_BINS bins around the PREVIOUS iteration's prefix plus "below" and "above" -- nine counts, reduced inside the wave, three
@@ -83,6 +83,62 @@
 // launches fetches the same 20.6 MB past the L2 as the first), so there is no map slice for these streams to push out between launches;
 // inside a launch the hint changed nothing measurable.  Kept as a switch; plain loads / stores by default.
 #ifdef __HIPCC__
+// Rank lookups in the fused selection's histograms, shared by the kernels that build them (select.hip) and the consumers that resolve the
+// last level (loop.hip: accumulate_kernel, res_pairs_kernel).
+// All 256 threads call with one bin count `v` each (bin = threadIdx.x).  Finds the bin holding element
+// `rank` (0-based, ascending); when from_quantile, rank = (unsigned)(float(total) * quantile) like
+// getDistsQuantile.  Results are uniform across the block.
+__device__ __forceinline__ void block_find_rank256(unsigned v, bool from_quantile, float quantile, unsigned rank_in,
+                                                   unsigned* sh /* >= 16 words */, unsigned& bin, unsigned& rank_rem, unsigned& total)
+{
+    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    unsigned incl = v;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const unsigned o = __shfl_up(incl, off, 64);
+        if (lane >= off) incl += o;
+    }
+    if (lane == 63) sh[wv] = incl;
+    __syncthreads();
+    const unsigned w0 = sh[0], w1 = sh[1], w2 = sh[2], w3 = sh[3];
+    total = w0 + w1 + w2 + w3;
+    incl += wv == 0 ? 0u : (wv == 1 ? w0 : (wv == 2 ? w0 + w1 : w0 + w1 + w2));
+    const unsigned excl = incl - v;
+    unsigned rank = rank_in;
+    if (from_quantile) {
+        if (total == 0) rank = 0;
+        else if (quantile == 1.0f) rank = total - 1;
+        else {
+            rank = (unsigned)((float)total * quantile);
+            if (rank > total - 1) rank = total - 1;
+        }
+    }
+    if (total != 0 && rank >= excl && rank < incl) { sh[8] = (unsigned)t; sh[9] = rank - excl; }
+    __syncthreads();
+    bin = sh[8];
+    rank_rem = sh[9];
+    __syncthreads();
+}
+
+// two-tier lookup: coarse bin from `coarse_v` (this thread's coarse count), then the fine bin under it
+template <int FCOPIES>
+__device__ __forceinline__ void block_find_rank_2tier(unsigned coarse_v, const unsigned* __restrict__ fine, bool from_quantile,
+                                                      float quantile, unsigned rank_in, unsigned* sh, unsigned& bin16,
+                                                      unsigned& rank_rem, unsigned& total)
+{
+    unsigned cb, rem, tot2;
+    block_find_rank256(coarse_v, from_quantile, quantile, rank_in, sh, cb, rem, total);
+    if (total == 0) { bin16 = 0; rank_rem = 0; return; }
+    unsigned fv = 0;
+    if (threadIdx.x < 256) { // (workgroups wider than 256 threads: the extra waves carry empty bins through the scan)
+#pragma unroll
+        for (int cpy = 0; cpy < FCOPIES; ++cpy) fv += fine[cpy * 65536 + ICPMI_S2_FIDX(cb * 256 + threadIdx.x)];
+    }
+    unsigned fb;
+    block_find_rank256(fv, false, 0.f, rem, sh, fb, rank_rem, tot2);
+    bin16 = (cb << 8) | fb;
+}
+
 typedef float icpmi_vf4 __attribute__((ext_vector_type(4)));
 #ifdef ICPMI_NT_STREAMS
 __device__ __forceinline__ float4 ld_stream(const float4* p) { const icpmi_vf4 v = __builtin_nontemporal_load(reinterpret_cast<const icpmi_vf4*>(p)); return make_float4(v.x, v.y, v.z, v.w); }
@@ -203,6 +259,30 @@ static inline int quantile_slot(const LoopCfg& lc)
     return slot;
 }
 static inline bool chain_has_quantile(const LoopCfg& lc) { return quantile_slot(lc) >= 0; }
+// index of the single quantile-type filter of the chain, or -1 (none) / -2 (more than one)
+static inline int fused_filter_slot(const LoopCfg& lc)
+{
+    int slot = -1;
+    for (int f = 0; f < lc.n_out; ++f)
+        if (lc.out_type[f] == ICPMI_OUT_TRIMMEDDIST || lc.out_type[f] == ICPMI_OUT_MEDIANDIST) slot = slot == -1 ? f : -2;
+    return slot;
+}
+
+// The matcher's output as the passes that walk it see it (loop.hip: pair_view fills it on the host, walk_pairs reads it on the device): slot
+// e of the n * k belongs to query e / k of `reading`; `reading`, sidx, d2 (and match_pt, the matched points the k = 1 matcher keeps) share one
+// order -- the caller's, or, qindex != nullptr, the tile-sorted one, where qindex maps a query back to the caller's index (read_normals and
+// the reading's other descriptors stay in the caller's order).  A null pointer = the chain has no such array.
+struct PairView {
+    const float4* __restrict__ reading;
+    const int*    __restrict__ qindex;
+    const int*    __restrict__ sidx;
+    const float*  __restrict__ d2;
+    const float4* __restrict__ match_pt;
+    const float4* __restrict__ map;          // cell-sorted map points, w = original index bits
+    const float4* __restrict__ ref_normals;  // of the map, same order
+    const float4* __restrict__ read_normals;
+    const float*  __restrict__ ref_scalar;   // the map's tracked scalar descriptor, by ORIGINAL index (EXT chains)
+};
 
 // the side block of the degeneracy-aware solve (icpmi_ctx::d_degen), in doubles
 #define ICPMI_DG_REPORT 1
@@ -1115,6 +1195,12 @@ struct NnOutcome {
 icpmi_status nn_launch_k(icpmi_ctx* c, const NnRequest& req, const float4* d_reading, int64_t n, const float* d_T, const LoopCfg& lc,
                          int allow_self, int* d_sidx, float* d_d2, IcpState* d_state, NnOutcome* out = nullptr);
 icpmi_status nn_ids_to_original(icpmi_ctx* c, const int* d_sidx, int64_t count, int* d_ids);
+// select.hip: enqueue the quantile / scale selections chain lc needs over the `count` entries of c->d_d2 (no host sync); ba = the readings
+// behind d_d2, nn = what the matcher's launch in front of it answered (the fused chain skips what that launch already built); legacy = the
+// 11/11/10 passes even for a single quantile filter (no consumer kernel behind it to resolve a fused last level)
+void enqueue_selection(icpmi_ctx* c, const LoopCfg& lc, int64_t count, const BatchArgs& ba, const NnOutcome& nn, bool legacy = false);
+// ... and what those launches need allocated (a VarTrimmedDist chain's scratch), before a capture starts: enqueue_selection then cannot fail
+icpmi_status selection_reserve(icpmi_ctx* c, const LoopCfg& lc, int64_t count);
 // self k-NN of a device cloud through a sparse block grid built for the call (selfgrid.hip): rows of d_sidx / d_d2 in the cloud's order, entries =
 // positions in c->d_map_sorted (w = original index bits), which the call leaves behind for launch_normals / nn_ids_to_original
 // subset search of an appended cloud (selfgrid.hip): in -- m_old, d_dk (d^2 of the k-th neighbour of the first m_old points, original order);

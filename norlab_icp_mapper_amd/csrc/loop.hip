@@ -2,555 +2,17 @@
 // norlab_icp_mapper/Mapper.cpp:213; loop body SURVEY.md B.1):
 //     transform (fused into the NN query load) -> kNN -> outlier weights -> pair sums -> solve ->
 //     compose -> checkers
-// Per iteration the stream carries: the NN kernel (nn.hip), for each quantile-type outlier filter a
-// 3-pass radix select on the float bits of d^2 (exact nth_element equivalent), one accumulation
-// kernel and one single-wave solve kernel.  All decisions (convergence, errors) stay on the device
-// in IcpState; kernels of a finished loop exit on st->done.
+// Per iteration the stream carries: the NN kernel (nn.hip), the chain's quantile / scale selections
+// on the float bits of d^2 (select.hip), one accumulation kernel and one single-wave solve kernel.
+// All decisions (convergence, errors) stay on the device in IcpState; kernels of a finished loop
+// exit on st->done.  Behind the loop: the passes over the last iteration's pairs (overlap,
+// covariance, residual), which share one walk (walk_pairs) and one ordered double sum.
 #include "common.h"
 #include "solve.h"
 #include <cstring>
 #include <vector>
 
 namespace {
-
-// ---------------------------------------------------------------------------------------------
-// quantile selection == Matches::getDistsQuantile: over entries that are finite
-// and > 0, element of rank (size_t)(count * quantile) [float product], quantile == 1 -> max.
-// d2 >= 0 so the IEEE bit pattern orders like an unsigned integer: 3 radix passes 11/11/10 bits.
-// ---------------------------------------------------------------------------------------------
-// MODE 0: the quantile of the finite positive d2 (getDistsQuantile); MODE 3: the same values, at iteration 1 only
-// (RobustOutlierFilter{scaleEstimator: berg}).  MODE 1 / 2: RobustOutlierFilter{scaleEstimator: mad} --
-// Matches::getMedianAbsDeviation takes every finite d2 (zeros included): 1 = the values themselves, 2 = |d2 - median|;
-// nb_scale: the estimate is only refreshed while iteration <= nbIterationForScale (0 = always).
-template <int PASS, int MODE = 0>
-__global__ __launch_bounds__(256) void sel_hist_kernel(const float* __restrict__ d2, int64_t count,
-                                                       const IcpState* __restrict__ st, unsigned* __restrict__ ghist, int nb_scale = 0)
-{
-    if (st->done) return;
-    if (blockIdx.x == 0 && threadIdx.x == 0) nn_stamp_close(const_cast<IcpState*>(st));
-    if (MODE != 0 && nb_scale != 0 && st->iter + 1 > nb_scale) return;
-    if (MODE == 3 && st->iter != 0) return; // berg: the median is taken at iteration 1 only
-    __shared__ unsigned h[ICPMI_SEL_BINS];
-    for (int b = threadIdx.x; b < ICPMI_SEL_BINS; b += 256) h[b] = 0;
-    __syncthreads();
-    const unsigned prefix = st->sel_prefix;
-    const float med = MODE == 2 ? st->robust_med : 0.f;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < count; i += (int64_t)gridDim.x * 256) {
-        float v = d2[i];
-        if (MODE == 0 || MODE == 3) { if (!(v != INFINITY && v > 0.f)) continue; }
-        else {
-            if (v == INFINITY) continue;
-            if (MODE == 2) v = fabsf(v - med);
-        }
-        const unsigned bits = __float_as_uint(v);
-        if (PASS == 0) atomicAdd(&h[bits >> 21], 1u);
-        else if (PASS == 1) { if ((bits >> 21) == prefix) atomicAdd(&h[(bits >> 10) & 2047u], 1u); }
-        else { if ((bits >> 10) == prefix) atomicAdd(&h[bits & 1023u], 1u); }
-    }
-    __syncthreads();
-    for (int b = threadIdx.x; b < ICPMI_SEL_BINS; b += 256)
-        if (h[b]) atomicAdd(&ghist[b], h[b]);
-}
-
-// RobustOutlierFilter{scaleEstimator: std}: Matches::getStandardDeviation over EVERY entry of the distance matrix.  Two rounds
-// (PASS 0: sum d -> mean, kept in robust_med; PASS 1: sum (d - mean)^2 -> robust_scale = sqrt(sqrt(sum / (size - 1)))), each a
-// fixed grid of fixed-order partial sums in double (`part`, one per workgroup) and a one-workgroup tail: same bits every run.
-template <int PASS>
-__global__ __launch_bounds__(256) void std_part_kernel(const float* __restrict__ d2, int64_t count, const IcpState* __restrict__ st,
-                                                       double* __restrict__ part, int nb_scale)
-{
-    if (st->done) return;
-    if (blockIdx.x == 0 && threadIdx.x == 0) nn_stamp_close(const_cast<IcpState*>(st));
-    if (nb_scale != 0 && st->iter + 1 > nb_scale) return;
-    __shared__ double sh[256];
-    const float mean = PASS == 1 ? st->robust_med : 0.f;
-    double s = 0.0;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < count; i += (int64_t)gridDim.x * 256) {
-        const float v = d2[i];
-        if (PASS == 0) s += (double)v;
-        else { const float dv = __fsub_rn(v, mean); s += (double)__fmul_rn(dv, dv); }
-    }
-    sh[threadIdx.x] = s;
-    __syncthreads();
-    for (int off = 128; off > 0; off >>= 1) {
-        if ((int)threadIdx.x < off) sh[threadIdx.x] += sh[threadIdx.x + off];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) part[blockIdx.x] = sh[0];
-}
-
-template <int PASS>
-__global__ __launch_bounds__(256) void std_tail_kernel(IcpState* __restrict__ st, const double* __restrict__ part, int nparts, int64_t count,
-                                                       int nb_scale)
-{
-    if (st->done) return;
-    if (nb_scale != 0 && st->iter + 1 > nb_scale) return;
-    __shared__ double sh[256];
-    sh[threadIdx.x] = (int)threadIdx.x < nparts ? part[threadIdx.x] : 0.0;
-    __syncthreads();
-    for (int off = 128; off > 0; off >>= 1) {
-        if ((int)threadIdx.x < off) sh[threadIdx.x] += sh[threadIdx.x + off];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        if (PASS == 0) st->robust_med = (float)(sh[0] / (double)count);
-        else st->robust_scale = sqrtf(sqrtf((float)sh[0] / (float)(count - 1)));
-    }
-}
-
-// single workgroup: locate the bin holding the wanted rank, narrow prefix / rank, clear the histogram
-template <int PASS>
-__global__ __launch_bounds__(256) void sel_scan_kernel(IcpState* __restrict__ st, unsigned* __restrict__ ghist, float quantile,
-                                                       int filter_slot, int is_median, float factor, int dest = 0, int nb_scale = 0)
-{
-    // dest 0: limits[filter_slot] (quantile filters); 1: robust_med, 2: robust_scale = sqrt(mad) -- rank size / 2 (quantile < 0);
-    // 3: berg -- robust_scale = 1.9 sqrt(quantile) at iteration 1, 0.85 (scale - target) + target afterwards (factor = target)
-    if (st->done) return;
-    if (dest != 0 && nb_scale != 0 && st->iter + 1 > nb_scale) return;
-    if (dest == 3 && st->iter != 0) {
-        if (PASS == 2 && threadIdx.x == 0) st->robust_scale = __fadd_rn(__fmul_rn(0.85f, __fsub_rn(st->robust_scale, factor)), factor);
-        return;
-    }
-    __shared__ unsigned sh[256];
-    __shared__ unsigned s_rank;
-    const int t = threadIdx.x;
-    unsigned v[8], s = 0;
-    for (int e = 0; e < 8; ++e) { v[e] = ghist[t * 8 + e]; s += v[e]; ghist[t * 8 + e] = 0; }
-    sh[t] = s;
-    __syncthreads();
-    for (int off = 1; off < 256; off <<= 1) {
-        unsigned add = t >= off ? sh[t - off] : 0u;
-        __syncthreads();
-        sh[t] += add;
-        __syncthreads();
-    }
-    const unsigned incl = sh[t], excl = incl - s, total = sh[255];
-    if (t == 0) {
-        if (PASS == 0) {
-            st->n_valid = total;
-            if (total == 0) { st->error = ICPMI_ERR_NO_OUTLIER_TO_FILTER; st->done = 1; s_rank = 0; }
-            else {
-                unsigned r;
-                if (quantile < 0.f) r = total / 2;
-                else if (quantile == 1.0f) r = total - 1;
-                else {
-                    r = (unsigned)((float)total * quantile);
-                    if (r > total - 1) r = total - 1;
-                }
-                s_rank = r;
-            }
-        } else s_rank = st->sel_rank;
-    }
-    __syncthreads();
-    if (total == 0) return;
-    const unsigned rank = s_rank;
-    if (rank >= excl && rank < incl) {
-        unsigned acc = excl;
-        int bin = t * 8;
-        for (int e = 0; e < 8; ++e) {
-            if (rank < acc + v[e]) { bin = t * 8 + e; break; }
-            acc += v[e];
-        }
-        const unsigned prev = PASS == 0 ? 0u : st->sel_prefix;
-        const unsigned np = PASS == 0 ? (unsigned)bin : (PASS == 1 ? ((prev << 11) | (unsigned)bin) : ((prev << 10) | (unsigned)bin));
-        st->sel_prefix = np;
-        st->sel_rank = rank - acc;
-        if (PASS == 2) {
-            const float q = __uint_as_float(np);
-            if (dest == 1) st->robust_med = q;
-            else if (dest == 2) st->robust_scale = sqrtf(q);
-            else if (dest == 3) st->robust_scale = (float)(1.9 * (double)sqrtf(q));
-            else st->limits[filter_slot] = is_median ? factor * q : q;
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// Fused selection (exactly one quantile-type filter in the chain -- the common case).  Two 16-bit
-// radix levels (common.h: ICPMI_S2_*), chain per iteration
-//   NN (builds level 0) -> sel2_scan_hist (scans level 0, builds level 1) -> [scan level 1 + pair sums] -> solve.
-// Every workgroup of a consumer kernel redoes the scan of the histogram it needs (256 coarse bins,
-// then the 256 fine bins under the selected coarse one) -- cheaper than a kernel boundary.
-// Clearing: level 0 is cleared by the pair-sum kernel (after its last reader), level 1 by whoever
-// builds level 0 of the next iteration (before its next builder).
-// ---------------------------------------------------------------------------------------------
-// All 256 threads call with one bin count `v` each (bin = threadIdx.x).  Finds the bin holding element
-// `rank` (0-based, ascending); when from_quantile, rank = (unsigned)(float(total) * quantile) like
-// getDistsQuantile.  Results are uniform across the block.
-__device__ __forceinline__ void block_find_rank256(unsigned v, bool from_quantile, float quantile, unsigned rank_in,
-                                                   unsigned* sh /* >= 16 words */, unsigned& bin, unsigned& rank_rem, unsigned& total)
-{
-    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-    unsigned incl = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const unsigned o = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += o;
-    }
-    if (lane == 63) sh[wv] = incl;
-    __syncthreads();
-    const unsigned w0 = sh[0], w1 = sh[1], w2 = sh[2], w3 = sh[3];
-    total = w0 + w1 + w2 + w3;
-    incl += wv == 0 ? 0u : (wv == 1 ? w0 : (wv == 2 ? w0 + w1 : w0 + w1 + w2));
-    const unsigned excl = incl - v;
-    unsigned rank = rank_in;
-    if (from_quantile) {
-        if (total == 0) rank = 0;
-        else if (quantile == 1.0f) rank = total - 1;
-        else {
-            rank = (unsigned)((float)total * quantile);
-            if (rank > total - 1) rank = total - 1;
-        }
-    }
-    if (total != 0 && rank >= excl && rank < incl) { sh[8] = (unsigned)t; sh[9] = rank - excl; }
-    __syncthreads();
-    bin = sh[8];
-    rank_rem = sh[9];
-    __syncthreads();
-}
-
-// two-tier lookup: coarse bin from `coarse_v` (this thread's coarse count), then the fine bin under it
-template <int FCOPIES>
-__device__ __forceinline__ void block_find_rank_2tier(unsigned coarse_v, const unsigned* __restrict__ fine, bool from_quantile,
-                                                      float quantile, unsigned rank_in, unsigned* sh, unsigned& bin16,
-                                                      unsigned& rank_rem, unsigned& total)
-{
-    unsigned cb, rem, tot2;
-    block_find_rank256(coarse_v, from_quantile, quantile, rank_in, sh, cb, rem, total);
-    if (total == 0) { bin16 = 0; rank_rem = 0; return; }
-    unsigned fv = 0;
-    if (threadIdx.x < 256) { // (workgroups wider than 256 threads: the extra waves carry empty bins through the scan)
-#pragma unroll
-        for (int cpy = 0; cpy < FCOPIES; ++cpy) fv += fine[cpy * 65536 + ICPMI_S2_FIDX(cb * 256 + threadIdx.x)];
-    }
-    unsigned fb;
-    block_find_rank256(fv, false, 0.f, rem, sh, fb, rank_rem, tot2);
-    bin16 = (cb << 8) | fb;
-}
-
-// (r5) The speculative window of the k > 1 loop (common.h: ICPMI_S2_WIN; counted by nnk_wg_kernel around the previous iteration's prefix).
-// All 256 threads call; true = the selected rank lies in one of the window's bins: `prefix` is that bin, `rank_rem` the rank inside it,
-// `total` the number of finite positive distances -- what block_find_rank_2tier would return from a full level 0, without one.
-// false = no window this iteration, or the rank falls below / above it (the caller goes on with the full histogram).
-__device__ __forceinline__ bool win_lookup(const unsigned* __restrict__ hists, float quantile, unsigned* sh /* >= 16 words */,
-                                           unsigned& prefix, unsigned& rank_rem, unsigned& total)
-{
-    const unsigned long long* __restrict__ W = reinterpret_cast<const unsigned long long*>(hists + ICPMI_S2_WIN);
-    const int t = threadIdx.x, w = t >> 6, l = t & 63;
-    // wave w < 3 sums word w over the copies (the packed fields cannot carry: every field's total is below 2^21), wave 3 fetches the header
-    static_assert(ICPMI_WIN_COPIES <= 64, "one lane per copy");
-    unsigned long long v = 0ull;
-    if (w < 3) { if (l < ICPMI_WIN_COPIES) v = W[(size_t)(l * 3 + w) * ICPMI_WIN_PAD]; }
-    else if (l == 0) v = W[ICPMI_WIN_HDR];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += (unsigned long long)__shfl_xor((long long)v, off, 64);
-    if (l == 0) {
-        if (w < 3) {
-#pragma unroll
-            for (int j = 0; j < 3; ++j) sh[3 * w + j] = (unsigned)(v >> (21 * j)) & 0x1fffffu;
-        } else sh[9] = (unsigned)v;
-    }
-    __syncthreads();
-    if (t == 0) {
-        const unsigned lo1 = sh[9], below = sh[0], above = sh[ICPMI_WIN_BINS + 1];
-        unsigned inwin = 0u;
-        for (int b = 0; b < ICPMI_WIN_BINS; ++b) inwin += sh[1 + b];
-        const unsigned tot = below + inwin + above;
-        unsigned hit = 0u, pf = 0u, rr = 0u;
-        if (lo1 != 0u && tot != 0u) {
-            unsigned rank; // getDistsQuantile's index, as block_find_rank256 forms it
-            if (quantile == 1.0f) rank = tot - 1;
-            else {
-                rank = (unsigned)((float)tot * quantile);
-                if (rank > tot - 1) rank = tot - 1;
-            }
-            if (rank >= below && rank - below < inwin) {
-                unsigned r = rank - below;
-                for (int b = 0; b < ICPMI_WIN_BINS; ++b) {
-                    const unsigned cb = sh[1 + b];
-                    if (r < cb) { pf = lo1 - 1u + (unsigned)b; rr = r; hit = 1u; break; }
-                    r -= cb;
-                }
-            }
-        }
-        sh[10] = hit; sh[11] = pf; sh[12] = rr; sh[13] = tot;
-    }
-    __syncthreads();
-    const bool hit = sh[10] != 0u;
-    prefix = sh[11]; rank_rem = sh[12]; total = sh[13];
-    __syncthreads();
-    return hit;
-}
-
-// level-0 histograms as a stand-alone kernel (NN variants that do not build them: k > 1, chains that may
-// need the brute-force pass).  Also clears level 1, like the NN kernel does when it is the builder.
-__global__ __launch_bounds__(256) void sel2_hist0_kernel(const float* __restrict__ d2, BatchArgs ba, int k, const IcpState* __restrict__ st,
-                                                         unsigned* __restrict__ hists, float quantile, int use_win)
-{
-    const int64_t count = (int64_t)ba.n[blockIdx.y] * k; // blockIdx.y = reading of a batch
-    d2 += (size_t)blockIdx.y * (size_t)ba.qstride * k;
-    hists += (size_t)blockIdx.y * ICPMI_SELHIST_WORDS;
-    st += blockIdx.y;
-    if (blockIdx.x == 0 && threadIdx.x == 0 && !st->done) nn_stamp_close(const_cast<IcpState*>(st));
-    if (use_win) { // (r5) the NN kernel's window holds the selected element (and that kernel cleared level 1): nothing to do in this launch
-        if (st->done) return;
-        __shared__ unsigned shw[16];
-        unsigned pf, rr, tot;
-        if (win_lookup(hists, quantile, shw, pf, rr, tot)) return;
-    }
-#ifndef ICPMI_H0_PF
-#define ICPMI_H0_PF 16
-#endif
-    constexpr int PF = ICPMI_H0_PF; // all of a thread's matches in flight before the first LDS atomic (4096 per workgroup: 16 per thread)
-    const int64_t stride = (int64_t)gridDim.x * 256;
-    const int64_t i0 = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    float pv[PF];
-#pragma unroll
-    for (int u = 0; u < PF; ++u) pv[u] = i0 + u * stride < count ? d2[i0 + u * stride] : INFINITY;
-    if (st->done) return;
-    // Fine bins (top 16 bits of d^2) are counted in LDS first, in a direct-mapped window of 4096 bins = 32 octaves that ends
-    // just above the largest value of the workgroup's FIRST batch of matches (the matches of a launch span a few octaves below
-    // the matcher's radius; whatever falls outside goes to memory directly): ONE LDS atomic per match -- r2 used a 1024-slot hash
-    // (compare-and-swap, then the count) plus the coarse bin, three dependent LDS atomics on addresses that most lanes of a
-    // wave share.  The coarse bins are summed from the window when it is flushed.
-    constexpr int WIN = 4096;
-    __shared__ unsigned h[256];
-    __shared__ unsigned win[WIN];
-    __shared__ unsigned s_top;
-    h[threadIdx.x] = 0;
-    for (int i = threadIdx.x; i < WIN; i += 256) win[i] = 0;
-    if (threadIdx.x == 0) s_top = 0u;
-    for (int64_t i = i0; i < 256 + 65536; i += stride) hists[ICPMI_S2_C1 + i] = 0;
-    __syncthreads();
-    {
-        unsigned mx = 0;
-#pragma unroll
-        for (int u = 0; u < PF; ++u) if (pv[u] != INFINITY && pv[u] > 0.f) mx = max(mx, __float_as_uint(pv[u]) >> 16);
-        for (int off = 32; off > 0; off >>= 1) mx = max(mx, (unsigned)__shfl_xor((int)mx, off, 64));
-        if ((threadIdx.x & 63) == 0 && mx) atomicMax(&s_top, mx);
-    }
-    __syncthreads();
-    const unsigned top = s_top + 1u, lo = top > (unsigned)WIN ? top - (unsigned)WIN : 0u;
-    unsigned* fine = hists + ICPMI_S2_F0 + (blockIdx.x % ICPMI_S2_FCOPIES) * 65536;
-    auto add = [&](float v) {
-        if (!(v != INFINITY && v > 0.f)) return;
-        const unsigned bits = __float_as_uint(v);
-        const unsigned bin = bits >> 16, rel = bin - lo;
-        if (rel < (unsigned)WIN) atomicAdd(&win[rel], 1u);
-        else { atomicAdd(&h[bits >> 24], 1u); atomicAdd(&fine[ICPMI_S2_FIDX(bin)], 1u); }
-    };
-#pragma unroll
-    for (int u = 0; u < PF; ++u) add(pv[u]);
-    for (int64_t i = i0 + PF * stride; i < count; i += stride) add(d2[i]);
-    __syncthreads();
-    for (int i = threadIdx.x; i < WIN; i += 256) {
-        const unsigned cnt = win[i];
-        if (cnt) { const unsigned bin = lo + (unsigned)i; atomicAdd(&h[bin >> 8], cnt); atomicAdd(&fine[ICPMI_S2_FIDX(bin)], cnt); }
-    }
-    __syncthreads();
-    if (h[threadIdx.x]) atomicAdd(&hists[ICPMI_S2_C0 + (blockIdx.x % ICPMI_S2_COPIES) * 256 + threadIdx.x], h[threadIdx.x]);
-}
-
-// scan level 0 (top 16 bits), build level 1 (low 16 bits) from the elements under the selected prefix
-__global__ __launch_bounds__(256) void sel2_scan_hist_kernel(const float* __restrict__ d2, BatchArgs ba, int k, IcpState* __restrict__ st,
-                                                             unsigned* __restrict__ hists, float quantile, int use_win)
-{
-    // blockIdx.y = reading of a batch (common.h: BatchArgs)
-    asm volatile("" ::"s"(ba.n[blockIdx.y]), "s"(ba.qstride), "s"(k), "s"(d2), "s"(hists), "s"(st), "s"(quantile), "s"(use_win)); // the kernel arguments in one batch (as in nn.hip)
-    const int64_t count = (int64_t)ba.n[blockIdx.y] * k;
-    d2 += (size_t)blockIdx.y * (size_t)ba.qstride * k;
-    hists += (size_t)blockIdx.y * ICPMI_SELHIST_WORDS;
-    st += blockIdx.y;
-    // first trip: the loop header, the lane's elements and the coarse counts are requested together and joined below -- nothing of the
-    // loop state is read from memory after that
-    constexpr int PF = 2;
-    const int64_t stride = (int64_t)gridDim.x * 256;
-    const int64_t i0 = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    HdrView hv{hdr_load(st)};
-    float pv[PF];
-#pragma unroll
-    for (int u = 0; u < PF; ++u) pv[u] = i0 + u * stride < count ? d2[i0 + u * stride] : INFINITY;
-    unsigned cv = 0;
-#pragma unroll
-    for (int cpy = 0; cpy < ICPMI_S2_COPIES; ++cpy) cv += hists[ICPMI_S2_C0 + cpy * 256 + threadIdx.x];
-    asm volatile("" : "+v"(hv.w), "+v"(pv[0]), "+v"(pv[1]), "+v"(cv)); // the join
-    if (hv.i(ICPMI_HDR_W(done))) return;
-    if (blockIdx.x == 0 && threadIdx.x == 0) nn_stamp_close(st, hv.u64(ICPMI_HDR_W(t_nn_begin)));
-    __shared__ unsigned sh[16];
-    unsigned prefix, rem, total;
-    // (r5) k > 1: the NN kernel's window around the previous prefix first (the stand-alone builder took the same decision from the same words)
-    const bool win_hit = use_win && win_lookup(hists, quantile, sh, prefix, rem, total);
-    if (!win_hit) block_find_rank_2tier<ICPMI_S2_FCOPIES>(cv, hists + ICPMI_S2_F0, true, quantile, 0u, sh, prefix, rem, total);
-#ifndef ICPMI_NN_TIMING
-    if (use_win && blockIdx.x == 0 && threadIdx.x == 0) st->dbg[win_hit ? 12 : 13] += 1ull; // diagnostics: iterations served by the window / by the full level 0
-#endif
-    if (total == 0) {
-        if (blockIdx.x == 0 && threadIdx.x == 0) { st->n_valid = 0; st->error = ICPMI_ERR_NO_OUTLIER_TO_FILTER; st->done = 1; }
-        return;
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) { st->sel_prefix_l[0] = prefix; st->sel_rank_l[0] = rem; st->n_valid = total; }
-    // only the elements under the selected 16-bit prefix contribute (a few hundred): no contention
-    auto add = [&](float v) {
-        if (!(v != INFINITY && v > 0.f)) return;
-        const unsigned bits = __float_as_uint(v);
-        if ((bits >> 16) != prefix) return;
-        atomicAdd(&hists[ICPMI_S2_C1 + ((bits >> 8) & 255u)], 1u);
-        atomicAdd(&hists[ICPMI_S2_F1 + ICPMI_S2_FIDX(bits & 0xffffu)], 1u);
-    };
-#pragma unroll
-    for (int u = 0; u < PF; ++u) add(pv[u]);
-    for (int64_t i = i0 + PF * stride; i < count; i += stride) add(d2[i]);
-}
-
-// ---------------------------------------------------------------------------------------------
-// VarTrimmedDistOutlierFilter (optimizeInlierRatio, Phillips et al. 2007): the valid d2 sorted (radix sort of the bit
-// patterns, octree.hip), their running sum in double, FRMS(i) = cum(i) / ((i + 1) ((i + 1) / N)^(2 lambda)) minimised over
-// minEl <= i < min(maxEl, V); the limit is then the quantile at i_min / N read straight from the sorted array.
-//   vt_keys -> radix_sort_pairs -> vt_chunk_sums -> vt_chunk_offsets -> vt_frms -> vt_pick        (a rare chain: not batched)
-// ---------------------------------------------------------------------------------------------
-constexpr int VT_CHUNK = 2048; // elements per workgroup of the scan (256 threads x 8)
-
-__global__ __launch_bounds__(256) void vt_keys_kernel(const float* __restrict__ d2, int64_t count, IcpState* __restrict__ st,
-                                                      unsigned long long* __restrict__ keys, unsigned* __restrict__ vals)
-{
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (blockIdx.x == 0 && threadIdx.x == 0 && !st->done) nn_stamp_close(st);
-    const float v = i < count ? d2[i] : INFINITY;
-    const bool valid = v != INFINITY && v > 0.f;
-    if (i < count) { keys[i] = valid ? (unsigned long long)__float_as_uint(v) : 0xffffffffull; vals[i] = 0u; } // invalid entries sort to the end
-    __shared__ unsigned cnt;
-    if (threadIdx.x == 0) cnt = 0;
-    __syncthreads();
-    const unsigned long long b = __ballot(valid);
-    if ((threadIdx.x & 63) == 0 && b) atomicAdd(&cnt, (unsigned)__popcll(b));
-    __syncthreads();
-    if (threadIdx.x == 0 && cnt) atomicAdd(&st->vt_valid, cnt);
-}
-
-__device__ __forceinline__ double vt_value(const unsigned long long* __restrict__ sorted, int64_t i, int64_t V)
-{
-    return i < V ? (double)__uint_as_float((unsigned)sorted[i]) : 0.0;
-}
-
-__global__ __launch_bounds__(256) void vt_chunk_sums_kernel(const unsigned long long* __restrict__ sorted, const IcpState* __restrict__ st,
-                                                            double* __restrict__ sums)
-{
-    const int64_t V = st->vt_valid;
-    const int64_t base = (int64_t)blockIdx.x * VT_CHUNK + threadIdx.x * 8;
-    double s = 0.0;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) s += vt_value(sorted, base + e, V);
-    __shared__ double sh[256];
-    sh[threadIdx.x] = s;
-    __syncthreads();
-    for (int off = 128; off > 0; off >>= 1) {
-        if (threadIdx.x < off) sh[threadIdx.x] += sh[threadIdx.x + off];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) sums[blockIdx.x] = sh[0];
-}
-
-// one workgroup: sums[b] -> sum of the chunks before b, in chunk order (tiles of 1024 through LDS; lane 0 adds them up in order)
-__global__ __launch_bounds__(256) void vt_chunk_offsets_kernel(double* __restrict__ sums, int nchunks)
-{
-    __shared__ double sh[1024];
-    __shared__ double carry;
-    if (threadIdx.x == 0) carry = 0.0;
-    for (int base = 0; base < nchunks; base += 1024) {
-        __syncthreads();
-        for (int i = threadIdx.x; i < 1024; i += 256) sh[i] = base + i < nchunks ? sums[base + i] : 0.0;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            double run = carry;
-            const int lim = nchunks - base < 1024 ? nchunks - base : 1024;
-            for (int i = 0; i < lim; ++i) { const double v = sh[i]; sh[i] = run; run += v; }
-            carry = run;
-        }
-        __syncthreads();
-        for (int i = threadIdx.x; i < 1024; i += 256) if (base + i < nchunks) sums[base + i] = sh[i];
-    }
-}
-
-__global__ __launch_bounds__(256) void vt_frms_kernel(const unsigned long long* __restrict__ sorted, int64_t count, const IcpState* __restrict__ st,
-                                                      const double* __restrict__ offsets, long long min_el, long long max_el, float lambda,
-                                                      double* __restrict__ best_val, long long* __restrict__ best_idx)
-{
-    const int64_t V = st->vt_valid;
-    const int64_t hi = max_el < V ? max_el : V;
-    const int64_t base = (int64_t)blockIdx.x * VT_CHUNK + threadIdx.x * 8;
-    double v[8], s = 0.0;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) { v[e] = vt_value(sorted, base + e, V); s += v[e]; }
-    __shared__ double sh[256];
-    __shared__ long long shi[256];
-    sh[threadIdx.x] = s;
-    __syncthreads();
-    for (int off = 1; off < 256; off <<= 1) { // inclusive scan of the thread totals
-        const double add = threadIdx.x >= off ? sh[threadIdx.x - off] : 0.0;
-        __syncthreads();
-        sh[threadIdx.x] += add;
-        __syncthreads();
-    }
-    double cum = offsets[blockIdx.x] + (sh[threadIdx.x] - s);
-    __syncthreads();
-    double bv = INFINITY; long long bi = -1;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const int64_t i = base + e;
-        cum += v[e];
-        if (i >= min_el && i < hi) {
-            const double ids = (double)(i + 1), ratio = ids / (double)count;
-            const double frms = cum / (ids * pow(ratio, 2.0 * (double)lambda));
-            if (bi < 0 || frms < bv) { bv = frms; bi = i; }
-        }
-    }
-    sh[threadIdx.x] = bv; shi[threadIdx.x] = bi;
-    __syncthreads();
-    for (int off = 128; off > 0; off >>= 1) { // first minimum: smaller value, or the same value at a smaller rank
-        if (threadIdx.x < off) {
-            const double ov = sh[threadIdx.x + off]; const long long oi = shi[threadIdx.x + off];
-            const long long mi = shi[threadIdx.x];
-            if (oi >= 0 && (mi < 0 || ov < sh[threadIdx.x] || (ov == sh[threadIdx.x] && oi < mi))) { sh[threadIdx.x] = ov; shi[threadIdx.x] = oi; }
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) { best_val[blockIdx.x] = sh[0]; best_idx[blockIdx.x] = shi[0]; }
-}
-
-__global__ __launch_bounds__(256) void vt_pick_kernel(const unsigned long long* __restrict__ sorted, int64_t count, IcpState* __restrict__ st,
-                                                      const double* __restrict__ best_val, const long long* __restrict__ best_idx, int nchunks,
-                                                      long long min_el, int filter_slot)
-{
-    __shared__ double sh[256];
-    __shared__ long long shi[256];
-    double bv = INFINITY; long long bi = -1;
-    for (int b = threadIdx.x; b < nchunks; b += 256) {
-        const double ov = best_val[b]; const long long oi = best_idx[b];
-        if (oi >= 0 && (bi < 0 || ov < bv || (ov == bv && oi < bi))) { bv = ov; bi = oi; }
-    }
-    sh[threadIdx.x] = bv; shi[threadIdx.x] = bi;
-    __syncthreads();
-    for (int off = 128; off > 0; off >>= 1) {
-        if (threadIdx.x < off) {
-            const double ov = sh[threadIdx.x + off]; const long long oi = shi[threadIdx.x + off];
-            const long long mi = shi[threadIdx.x];
-            if (oi >= 0 && (mi < 0 || ov < sh[threadIdx.x] || (ov == sh[threadIdx.x] && oi < mi))) { sh[threadIdx.x] = ov; shi[threadIdx.x] = oi; }
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x != 0) return;
-    const unsigned V = st->vt_valid;
-    st->vt_valid = 0; // for the next iteration's count
-    if (st->done) return;
-    if (V == 0) { st->error = ICPMI_ERR_NO_OUTLIER_TO_FILTER; st->done = 1; return; }
-    long long best = shi[0] >= 0 ? shi[0] : min_el;
-    const float ratio = (float)best / (float)count;
-    st->vt_ratio = ratio;
-    unsigned r; // getDistsQuantile(ratio) over the V valid entries
-    if (ratio == 1.0f) r = V - 1;
-    else { r = (unsigned)((float)V * ratio); if (r > V - 1) r = V - 1; }
-    st->limits[filter_slot] = __uint_as_float((unsigned)sorted[r]);
-}
 
 // ---------------------------------------------------------------------------------------------
 // outlier weight of one match (OutlierFilters::compute; weights multiply)
@@ -625,6 +87,126 @@ __device__ __forceinline__ float match_weight(const LoopCfg& lc, const IcpState*
         }
     }
     return w;
+}
+
+// ---------------------------------------------------------------------------------------------
+// The passes over the matcher's output OUTSIDE the iteration (overlap, covariance, residual) share one walk and one way to sum.
+// ---------------------------------------------------------------------------------------------
+// one live slot (d2 finite) as walk_pairs hands it to a pass: p = the reading's point under T, q = its match, (dx, dy, dz) = p - q in
+// float as the pair-sum kernel forms it, nm / dot = the match's normal and (p - q) . nm (zero without map normals), w = the chain's weight
+struct PairSlot { int64_t e; int qi, oi, s; float d2; float3 p; float4 q, nm; float dx, dy, dz, dot, w; };
+
+// slice blockIdx.y of the per-query arrays (a pose batch: common.h, BatchArgs); the reading's descriptors are not sliced
+__device__ __forceinline__ void pair_view_slice(PairView& v, const BatchArgs& ba, int k)
+{
+    const size_t qo = (size_t)blockIdx.y * (size_t)ba.qstride;
+    v.reading += qo; v.sidx += qo * k; v.d2 += qo * k;
+    if (v.qindex) v.qindex += qo;
+    if (v.match_pt) v.match_pt += qo;
+}
+
+// Grid-stride walk of the n * lc.k slots by 256-thread workgroups; body(slot) runs for every slot with a match.  The weight goes to the
+// body as it is: each pass has its own acceptance test.  fused_slot / fused_limit: match_weight's (a limit the caller resolved itself).
+template <class Body>
+__device__ __forceinline__ void walk_pairs(const PairView& v, int n, const LoopCfg& lc, const IcpState* __restrict__ st,
+                                           const float* __restrict__ T, Body body, int fused_slot = -1, float fused_limit = 0.f)
+{
+    const int64_t total = (int64_t)n * lc.k;
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
+        PairSlot a;
+        a.d2 = v.d2[e];
+        if (a.d2 == INFINITY) continue;
+        a.e = e;
+        a.qi = (int)(e / lc.k);
+        a.oi = v.qindex ? v.qindex[a.qi] : a.qi;
+        a.s = v.sidx[e];
+        // the three gathers of a pair are requested together, in front of the first use of any of them (with k > 1 the matched point and
+        // its normal both hang on s: a normal fetched behind p - q is one more round trip per pair, 2 us of a knn-6 pass)
+        const float4 r = v.reading[a.qi];
+        a.q = v.match_pt ? v.match_pt[e] : v.map[a.s];
+        a.nm = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (v.ref_normals) a.nm = v.ref_normals[a.s];
+        a.p = xf_point(T, r.x, r.y, r.z, r.w);
+        a.dx = a.p.x - a.q.x; a.dy = a.p.y - a.q.y; a.dz = a.p.z - a.q.z;
+        a.dot = v.ref_normals ? a.dx * a.nm.x + a.dy * a.nm.y + a.dz * a.nm.z : 0.f;
+        // EXT: the filters that read the pair itself, as the pair-sum kernel evaluates them
+        if (lc.ext) a.w = match_weight<true>(lc, st, a.d2, T, v.read_normals, a.oi, v.ref_normals, a.s, fused_slot, fused_limit, v.ref_scalar,
+                                             __float_as_int(a.q.w), a.dot * a.dot);
+        else a.w = match_weight(lc, st, a.d2, T, v.read_normals, a.oi, v.ref_normals, a.s, fused_slot, fused_limit);
+        body(a);
+    }
+}
+
+// Ordered double sums: a fixed pattern at every level, so a pass gives the same bits on every call (include/icpmi.h rests on it).
+// Level 1, all 256 threads: acc[NV] per thread -> xor butterfly 32 .. 1 inside the wave -> the four waves in order -> row[NV], this
+// workgroup's row of partials.  Slots whose bit is set in MAXMASK combine with fmax instead of +.
+template <int NV, unsigned MAXMASK = 0u>
+__device__ __forceinline__ void block_partial_row(const double (&acc)[NV], double* __restrict__ row)
+{
+    __shared__ double sh[4][NV];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        double v = acc[i];
+#pragma unroll
+        for (int m = 32; m > 0; m >>= 1) {
+            const double o = __shfl_xor(v, m, 64);
+            v = (MAXMASK >> i & 1u) ? fmax(v, o) : v + o;
+        }
+        if (lane == 0) sh[wv][i] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < NV) {
+        const int i = threadIdx.x;
+        row[i] = (MAXMASK >> i & 1u) ? fmax(fmax(fmax(sh[0][i], sh[1][i]), sh[2][i]), sh[3][i]) : ((sh[0][i] + sh[1][i]) + sh[2][i]) + sh[3][i];
+    }
+}
+
+// Level 2, one workgroup of at least NV * CH threads: the first nb <= NB rows -> tot[NV] (LDS, valid in every thread on return).  Thread
+// v * CH + ch adds rows ch, ch + CH, ... of value v in that order -- every load issued before the first add (a loop of dependent loads and
+// adds was 35 us at 128 rows) -- and thread v then adds the CH chunk sums in order.
+template <int NV, int CH, int NB, unsigned MAXMASK = 0u>
+__device__ __forceinline__ void block_ordered_total(const double* __restrict__ partial, int nb, double* tot)
+{
+    __shared__ double part[NV][CH];
+    if (threadIdx.x < NV * CH) {
+        constexpr int PER = (NB + CH - 1) / CH;
+        const int v = threadIdx.x / CH, ch = threadIdx.x % CH;
+        double x[PER];
+#pragma unroll
+        for (int i = 0; i < PER; ++i) {
+            const int b = ch + CH * i;
+            x[i] = b < nb ? partial[(size_t)b * NV + v] : 0.0;
+        }
+        double acc = 0.0;
+#pragma unroll
+        for (int i = 0; i < PER; ++i) acc = (MAXMASK >> v & 1u) ? fmax(acc, x[i]) : acc + x[i];
+        part[v][ch] = acc;
+    }
+    __syncthreads();
+    if (threadIdx.x < NV) {
+        const int v = threadIdx.x;
+        double acc = 0.0;
+#pragma unroll
+        for (int ch = 0; ch < CH; ++ch) acc = (MAXMASK >> v & 1u) ? fmax(acc, part[v][ch]) : acc + part[v][ch];
+        tot[v] = acc;
+    }
+    __syncthreads();
+}
+
+// fixed-order sum (halving tree 128 .. 1) of the workgroup's 256 values; the result in every thread
+template <class V>
+__device__ __forceinline__ V block_tree_sum(V v, V* sh /* 256 */)
+{
+    sh[threadIdx.x] = v;
+    __syncthreads();
+    for (int h = 128; h > 0; h >>= 1) {
+        if ((int)threadIdx.x < h) sh[threadIdx.x] += sh[threadIdx.x + h];
+        __syncthreads();
+    }
+    const V r = sh[0];
+    __syncthreads();
+    return r;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1013,6 +595,27 @@ LoopCfg make_loop_cfg(const icpmi_ctx* c, int fixed_iterations)
     return lc;
 }
 
+// Which of the handle's buffers hold the matcher's last output under chain lc; sorted = NnOutcome::out_sorted of that launch (k = 1: with
+// the matched points, see nn1_wg_kernel; k > 1: ids and d2).  THE place where this is decided: the pair-sum launch and every pass behind
+// the loop read from it.  Before it, the covariance pass took d_normals_sorted and the overlap pass d_read_normals unconditionally; the
+// conditional forms here are the same pointers wherever a kernel dereferences them -- the covariance runs for point-to-plane only, which
+// api.hip (register_impl) refuses without map normals, and the overlap pass runs with !lc.ext and reads the reading's normals in its
+// point-to-plane branch only, for which register_impl sets has_read_normals (a SurfaceNormal filter sets it through chain_setup).
+static PairView pair_view(const icpmi_ctx* c, const LoopCfg& lc, bool sorted)
+{
+    PairView v;
+    v.reading = sorted ? c->d_qsorted : c->d_reading;
+    v.qindex = sorted ? c->d_qindex : nullptr;
+    v.sidx = c->d_sidx;
+    v.d2 = c->d_d2;
+    v.match_pt = (sorted && lc.k == 1) ? c->d_match_pt : nullptr;
+    v.map = c->d_map_sorted;
+    v.ref_normals = c->has_normals ? c->d_normals_sorted : nullptr;
+    v.read_normals = lc.has_read_normals ? c->d_read_normals : nullptr;
+    v.ref_scalar = (lc.ext && c->raw_has_scalar) ? c->d_raw_s : nullptr;
+    return v;
+}
+
 // ---------------------------------------------------------------------------------------------
 // ErrorMinimizer::getOverlap() for a reading that carries `simpleSensorNoise` and `normals` (read at Mapper.cpp:219).
 // The pairs are the last iteration's error elements: reading point under T_prev, its match, weight != 0.
@@ -1021,54 +624,39 @@ LoopCfg make_loop_cfg(const icpmi_ctx* c, int fixed_iterations)
 // MODE 0: per-workgroup partial sums {pairs, sum of dists} in a fixed order (p2p needs the mean first); MODE 1: the count.
 // ---------------------------------------------------------------------------------------------
 template <int MODE>
-__global__ __launch_bounds__(256) void overlap_kernel(const float4* __restrict__ reading, const int* __restrict__ qindex, int n, LoopCfg lc,
-                                                      const IcpState* __restrict__ st, const float4* __restrict__ map,
-                                                      const float4* __restrict__ ref_normals, const float4* __restrict__ read_normals,
-                                                      const float* __restrict__ noise, const int* __restrict__ sidx, const float* __restrict__ d2a,
-                                                      const float4* __restrict__ match_pt, float mean, double* __restrict__ partial,
+__global__ __launch_bounds__(256) void overlap_kernel(PairView pv, int n, LoopCfg lc, const IcpState* __restrict__ st,
+                                                      const float* __restrict__ noise, float mean, double* __restrict__ partial,
                                                       unsigned long long* __restrict__ count)
 {
     const float* T = st->T_prev;
-    const int64_t total = (int64_t)n * lc.k;
     double np = 0.0, sd = 0.0;
     unsigned long long cnt = 0;
-    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
-        const float d2 = d2a[e];
-        if (d2 == INFINITY) continue;
-        const int qi = (int)(e / lc.k);
-        const int oi = qindex ? qindex[qi] : qi;
-        const int s = sidx[e];
-        const float w = match_weight(lc, st, d2, T, read_normals, oi, ref_normals, s);
-        if (w == 0.f) continue;
-        const float4 r = reading[qi];
-        const float3 p = xf_point(T, r.x, r.y, r.z, r.w);
-        const float4 q = match_pt ? match_pt[e] : map[s];
-        const float dx = p.x - q.x, dy = p.y - q.y, dz = p.z - q.z;
-        if (lc.minimizer == ICPMI_MIN_POINT_TO_POINT) {
-            const float dist = sqrtf(fmaf(dz, dz, fmaf(dy, dy, dx * dx)));
-            if (MODE == 0) { np += 1.0; sd += (double)dist; }
-            else if (dist < mean + noise[oi]) ++cnt;
+    walk_pairs(pv, n, lc, st, T, [&](const PairSlot& a) {
+        if (a.w == 0.f) return;
+        const bool p2p = lc.minimizer == ICPMI_MIN_POINT_TO_POINT;
+        if (MODE == 0) { // (one statement per sum: the sums stay in registers)
+            np += 1.0;
+            sd += p2p ? (double)sqrtf(fmaf(a.dz, a.dz, fmaf(a.dy, a.dy, a.dx * a.dx))) : 0.0;
+        } else if (p2p) {
+            const float dist = sqrtf(fmaf(a.dz, a.dz, fmaf(a.dy, a.dy, a.dx * a.dx)));
+            if (dist < mean + noise[a.oi]) ++cnt;
         } else {
-            const float4 a = read_normals[oi];
-            const float nx = fmaf(T[8], a.z, fmaf(T[4], a.y, T[0] * a.x)), ny = fmaf(T[9], a.z, fmaf(T[5], a.y, T[1] * a.x)),
-                        nz = fmaf(T[10], a.z, fmaf(T[6], a.y, T[2] * a.x));
+            const float4 rn = pv.read_normals[a.oi];
+            const float nx = fmaf(T[8], rn.z, fmaf(T[4], rn.y, T[0] * rn.x)), ny = fmaf(T[9], rn.z, fmaf(T[5], rn.y, T[1] * rn.x)),
+                        nz = fmaf(T[10], rn.z, fmaf(T[6], rn.y, T[2] * rn.x));
             const float nn = sqrtf(fmaf(nz, nz, fmaf(ny, ny, nx * nx)));
-            const float proj = fmaf(dz, nz / nn, fmaf(dy, ny / nn, dx * (nx / nn)));
-            if (MODE == 0) np += 1.0;
-            else if (fabsf(proj) < noise[oi]) ++cnt;
+            const float proj = fmaf(a.dz, nz / nn, fmaf(a.dy, ny / nn, a.dx * (nx / nn)));
+            if (fabsf(proj) < noise[a.oi]) ++cnt;
         }
-    }
-    __shared__ double sh[2][256];
-    __shared__ unsigned long long shc[256];
-    sh[0][threadIdx.x] = np; sh[1][threadIdx.x] = sd; shc[threadIdx.x] = cnt;
-    __syncthreads();
-    for (int off = 128; off > 0; off >>= 1) {
-        if ((int)threadIdx.x < off) { sh[0][threadIdx.x] += sh[0][threadIdx.x + off]; sh[1][threadIdx.x] += sh[1][threadIdx.x + off]; shc[threadIdx.x] += shc[threadIdx.x + off]; }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        if (MODE == 0) { partial[2 * blockIdx.x] = sh[0][0]; partial[2 * blockIdx.x + 1] = sh[1][0]; }
-        else if (shc[0]) atomicAdd(count, shc[0]);
+    });
+    if (MODE == 0) {
+        __shared__ double sh[256];
+        const double pairs = block_tree_sum(np, sh), dists = block_tree_sum(sd, sh);
+        if (threadIdx.x == 0) { partial[2 * blockIdx.x] = pairs; partial[2 * blockIdx.x + 1] = dists; }
+    } else {
+        __shared__ unsigned long long shc[256];
+        const unsigned long long c = block_tree_sum(cnt, shc);
+        if (threadIdx.x == 0 && c) atomicAdd(count, c);
     }
 }
 
@@ -1080,20 +668,15 @@ icpmi_status loop_sensor_noise_overlap(icpmi_ctx* c, int64_t n, const LoopCfg& l
     if (!d_part) return ICPMI_ERR_HIP;
     unsigned long long* d_cnt = reinterpret_cast<unsigned long long*>(d_part + 2 * NB);
     HIP_TRY(c, hipMemsetAsync(d_cnt, 0, sizeof(unsigned long long), c->stream));
-    const float4* rd = sorted ? c->d_qsorted : c->d_reading;
-    const int* qi = sorted ? c->d_qindex : nullptr;
-    const float4* mp = (sorted && lc.k == 1) ? c->d_match_pt : nullptr;
-    const float4* rnm = c->has_normals ? c->d_normals_sorted : nullptr;
-    hipLaunchKernelGGL(overlap_kernel<0>, dim3(NB), dim3(256), 0, c->stream, rd, qi, (int)n, lc, c->d_state, c->d_map_sorted, rnm, c->d_read_normals,
-                       c->d_read_noise, c->d_sidx, c->d_d2, mp, 0.f, d_part, d_cnt);
+    const PairView pv = pair_view(c, lc, sorted);
+    hipLaunchKernelGGL(overlap_kernel<0>, dim3(NB), dim3(256), 0, c->stream, pv, (int)n, lc, c->d_state, c->d_read_noise, 0.f, d_part, d_cnt);
     double hp[2 * NB];
     if (read_back(c, hp, d_part, sizeof hp) != ICPMI_OK) return ICPMI_ERR_HIP;
     double pairs = 0.0, sum = 0.0;
     for (int b = 0; b < NB; ++b) { pairs += hp[2 * b]; sum += hp[2 * b + 1]; }
     if (!(pairs > 0.0)) return ICPMI_OK;
     const float mean = (float)(sum / pairs);
-    hipLaunchKernelGGL(overlap_kernel<1>, dim3(NB), dim3(256), 0, c->stream, rd, qi, (int)n, lc, c->d_state, c->d_map_sorted, rnm, c->d_read_normals,
-                       c->d_read_noise, c->d_sidx, c->d_d2, mp, mean, d_part, d_cnt);
+    hipLaunchKernelGGL(overlap_kernel<1>, dim3(NB), dim3(256), 0, c->stream, pv, (int)n, lc, c->d_state, c->d_read_noise, mean, d_part, d_cnt);
     unsigned long long hc = 0;
     if (read_back(c, &hc, d_cnt, sizeof hc) != ICPMI_OK) return ICPMI_ERR_HIP;
     HIP_TRY(c, hipGetLastError());
@@ -1126,41 +709,19 @@ __device__ inline void cov_step_params(const IcpState* st, double* x)
     x[5] = atan2(R[1][0] / cb, R[0][0] / cb);
 }
 
-__global__ __launch_bounds__(256) void cov_pairs_kernel(const float4* __restrict__ reading, const int* __restrict__ qindex, int n, LoopCfg lc,
-                                                        const IcpState* __restrict__ st, const float4* __restrict__ map,
-                                                        const float4* __restrict__ ref_normals, const float4* __restrict__ read_normals,
-                                                        const float* __restrict__ ref_scalar, const int* __restrict__ sidx,
-                                                        const float* __restrict__ d2a, const float4* __restrict__ match_pt,
+__global__ __launch_bounds__(256) void cov_pairs_kernel(PairView pv, int n, LoopCfg lc, const IcpState* __restrict__ st,
                                                         double* __restrict__ partial)
 {
     __shared__ double xs[6];
-    __shared__ double sh[4][ICPMI_COV_NV];
     if (threadIdx.x == 0) cov_step_params(st, xs);
     __syncthreads();
     const double tx = xs[0], ty = xs[1], tz = xs[2], al = xs[3], be = xs[4], ga = xs[5];
-    const float* T = st->T_prev;
-    const int64_t total = (int64_t)n * lc.k;
     double acc[ICPMI_COV_NV];
 #pragma unroll
     for (int i = 0; i < ICPMI_COV_NV; ++i) acc[i] = 0.0;
-    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
-        const float d2 = d2a[e];
-        if (d2 == INFINITY) continue;
-        const int qi = (int)(e / lc.k);
-        const int oi = qindex ? qindex[qi] : qi;
-        const int s = sidx[e];
-        const float4 r4 = reading[qi];
-        const float3 p = xf_point(T, r4.x, r4.y, r4.z, r4.w);
-        const float4 q = match_pt ? match_pt[e] : map[s];
-        const float4 nm = ref_normals[s];
-        float w;
-        if (lc.ext) { // the filters that read the pair itself, as the pair-sum kernel evaluates them
-            const float dx = p.x - q.x, dy = p.y - q.y, dz = p.z - q.z;
-            const float dot = dx * nm.x + dy * nm.y + dz * nm.z;
-            w = match_weight<true>(lc, st, d2, T, read_normals, oi, ref_normals, s, -1, 0.f, ref_scalar, __float_as_int(q.w), dot * dot);
-        } else w = match_weight(lc, st, d2, T, read_normals, oi, ref_normals, s);
-        if (!(w > 0.f)) continue;
-        const double px = p.x, py = p.y, pz = p.z, qx = q.x, qy = q.y, qz = q.z, nx = nm.x, ny = nm.y, nz = nm.z;
+    walk_pairs(pv, n, lc, st, st->T_prev, [&](const PairSlot& s) {
+        if (!(s.w > 0.f)) return;
+        const double px = s.p.x, py = s.p.y, pz = s.p.z, qx = s.q.x, qy = s.q.y, qz = s.q.z, nx = s.nm.x, ny = s.nm.y, nz = s.nm.z;
         const double r = sqrt(px * px + py * py + pz * pz), rho = sqrt(qx * qx + qy * qy + qz * qz);
         const double ir = 1.0 / r, irho = 1.0 / rho; // (two double divisions per pair instead of six)
         const double dx = px * ir, dy = py * ir, dz = pz * ir, ux = qx * irho, uy = qy * irho, uz = qz * irho;
@@ -1183,51 +744,15 @@ __global__ __launch_bounds__(256) void cov_pairs_kernel(const float4* __restrict
                 acc[idx] += h[i] * h[j];
                 acc[21 + idx] += a[i] * a[j] + b[i] * b[j];
             }
-    }
-    // wave butterfly, then the four waves in order: a fixed pattern, the same sums on every call
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int i = 0; i < ICPMI_COV_NV; ++i) {
-        double v = acc[i];
-#pragma unroll
-        for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m, 64);
-        if (lane == 0) sh[wv][i] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < ICPMI_COV_NV) {
-        const int i = threadIdx.x;
-        partial[(size_t)blockIdx.x * ICPMI_COV_NV + i] = ((sh[0][i] + sh[1][i]) + sh[2][i]) + sh[3][i];
-    }
+    });
+    block_partial_row<ICPMI_COV_NV>(acc, partial + (size_t)blockIdx.x * ICPMI_COV_NV);
 }
 
 #define ICPMI_COV_CH 6     // pass 2: six threads per value, each over every sixth workgroup partial
 __global__ __launch_bounds__(256) void cov_solve_kernel(const double* __restrict__ partial, int nb, float sigma, float* __restrict__ cov)
 {
-    __shared__ double part[ICPMI_COV_NV][ICPMI_COV_CH];
     __shared__ double tot[ICPMI_COV_NV];
-    if (threadIdx.x < ICPMI_COV_NV * ICPMI_COV_CH) {
-        // every load issued before the first add (a loop of dependent loads and adds was 35 us at 128 partials)
-        constexpr int PER = (ICPMI_COV_NB + ICPMI_COV_CH - 1) / ICPMI_COV_CH;
-        const int v = threadIdx.x / ICPMI_COV_CH, ch = threadIdx.x % ICPMI_COV_CH;
-        double x[PER];
-#pragma unroll
-        for (int i = 0; i < PER; ++i) {
-            const int b = ch + ICPMI_COV_CH * i;
-            x[i] = b < nb ? partial[(size_t)b * ICPMI_COV_NV + v] : 0.0;
-        }
-        double acc = 0.0;
-#pragma unroll
-        for (int i = 0; i < PER; ++i) acc += x[i];
-        part[v][ch] = acc;
-    }
-    __syncthreads();
-    if (threadIdx.x < ICPMI_COV_NV) {
-        double acc = 0.0;
-#pragma unroll
-        for (int ch = 0; ch < ICPMI_COV_CH; ++ch) acc += part[threadIdx.x][ch];
-        tot[threadIdx.x] = acc;
-    }
-    __syncthreads();
+    block_ordered_total<ICPMI_COV_NV, ICPMI_COV_CH, ICPMI_COV_NB>(partial, nb, tot);
     if (threadIdx.x != 0) return;
     double H[6][6], S[6][6], L[6][6], Hi[6][6], M[6][6];
     int idx = 0;
@@ -1306,13 +831,7 @@ const float* loop_covariance_out(const icpmi_ctx* c) { return reinterpret_cast<c
 icpmi_status loop_covariance(icpmi_ctx* c, int64_t n, const LoopCfg& lc, bool sorted)
 {
     if (c->d_cov.ensure(c, (size_t)ICPMI_COV_NB * ICPMI_COV_NV + 18) != ICPMI_OK) return ICPMI_ERR_HIP; // (+ 36 floats)
-    const float4* rd = sorted ? c->d_qsorted : c->d_reading;
-    const int* qi = sorted ? c->d_qindex : nullptr;
-    const float4* mp = (sorted && lc.k == 1) ? c->d_match_pt : nullptr;
-    const float4* rn = lc.has_read_normals ? c->d_read_normals : nullptr;
-    const float* rs = (lc.ext && c->raw_has_scalar) ? c->d_raw_s : nullptr;
-    hipLaunchKernelGGL(cov_pairs_kernel, dim3(ICPMI_COV_NB), dim3(256), 0, c->stream, rd, qi, (int)n, lc, c->d_state, c->d_map_sorted,
-                       c->d_normals_sorted, rn, rs, c->d_sidx, c->d_d2, mp, c->d_cov);
+    hipLaunchKernelGGL(cov_pairs_kernel, dim3(ICPMI_COV_NB), dim3(256), 0, c->stream, pair_view(c, lc, sorted), (int)n, lc, c->d_state, c->d_cov);
     hipLaunchKernelGGL(cov_solve_kernel, dim3(1), dim3(256), 0, c->stream, c->d_cov, ICPMI_COV_NB, c->cfg.sensor_std_dev,
                        const_cast<float*>(loop_covariance_out(c)));
     HIP_TRY(c, hipGetLastError());
@@ -1326,20 +845,6 @@ icpmi_status loop_covariance(icpmi_ctx* c, int64_t n, const LoopCfg& lc, bool so
 // chain asks for the option.
 // ---------------------------------------------------------------------------------------------
 namespace {
-
-// fixed-order sum of the workgroup's 256 values; the result in every thread
-__device__ __forceinline__ double degen_block_sum(double v, double* sh /* 256 */)
-{
-    sh[threadIdx.x] = v;
-    __syncthreads();
-    for (int h = 128; h > 0; h >>= 1) {
-        if ((int)threadIdx.x < h) sh[threadIdx.x] += sh[threadIdx.x + h];
-        __syncthreads();
-    }
-    const double r = sh[0];
-    __syncthreads();
-    return r;
-}
 
 // the mean from the per-workgroup sums, the same order wherever it is formed
 __device__ __forceinline__ void degen_mean(const double* __restrict__ blk, int64_t n, double* c0)
@@ -1367,7 +872,7 @@ __global__ __launch_bounds__(256) void degen_stats_kernel(const float4* __restri
         }
     }
     for (int r = 0; r < (MODE == 0 ? 3 : 1); ++r) {
-        const double s = degen_block_sum(a[r], sh);
+        const double s = block_tree_sum(a[r], sh);
         if (threadIdx.x == 0) blk[ICPMI_DG_PART + 4 * blockIdx.x + (MODE == 0 ? r : 3)] = s;
     }
 }
@@ -1475,27 +980,6 @@ static int acc_blocks(int64_t count, int bt = 256)
     return (int)(nb < 1 ? 1 : (nb > cap ? cap : nb));
 }
 
-// scratch of the VarTrimmedDist passes (operator scratch slots 0..4, shared with the map-side operators: never live at the
-// same time on one handle); reserved before a capture starts, looked up again -- same pointers -- when the passes are enqueued
-struct VtBuffers { unsigned long long* keys; unsigned* vals; unsigned* tab; double* sums; double* best_val; long long* best_idx; int nchunks; };
-static bool chain_has_vartrimmed(const LoopCfg& lc)
-{
-    for (int f = 0; f < lc.n_out; ++f) if (lc.out_type[f] == ICPMI_OUT_VARTRIMMEDDIST) return true;
-    return false;
-}
-static icpmi_status vt_buffers(icpmi_ctx* c, int64_t count, VtBuffers* b)
-{
-    b->nchunks = (int)((count + VT_CHUNK - 1) / VT_CHUNK);
-    b->keys = scratch_get<unsigned long long>(c, 0, (size_t)2 * count + 2);
-    b->vals = scratch_get<unsigned>(c, 1, (size_t)2 * count + 2);
-    b->tab = scratch_get<unsigned>(c, 2, radix_sort_tab_words(count, 32));
-    b->sums = scratch_get<double>(c, 3, (size_t)2 * b->nchunks + 2);
-    b->best_idx = scratch_get<long long>(c, 4, (size_t)b->nchunks + 1);
-    if (!b->keys || !b->vals || !b->tab || !b->sums || !b->best_idx) return ICPMI_ERR_HIP;
-    b->best_val = b->sums + b->nchunks + 1;
-    return ICPMI_OK;
-}
-
 // everything the loop's launches for chain lc write to: n = points per slice, nscan slices (a single registration: one slice of n points).
 // The VarTrimmedDist scratch is reserved here too, so that enqueue_selection cannot fail (such a chain never takes a batch).
 static icpmi_status ensure_loop_buffers(icpmi_ctx* c, int64_t n, const LoopCfg& lc, int nscan = 1)
@@ -1506,104 +990,7 @@ static icpmi_status ensure_loop_buffers(icpmi_ctx* c, int64_t n, const LoopCfg& 
     if (c->d_hard.ensure(c, (size_t)n * nscan + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
     if (lc.k == 1 && c->d_match_pt.ensure(c, (size_t)n * nscan + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
     if (c->d_selhist.ensure(c, (size_t)ICPMI_SELHIST_WORDS * nscan) != ICPMI_OK) return ICPMI_ERR_HIP;
-    VtBuffers vb;
-    if (chain_has_vartrimmed(lc) && vt_buffers(c, n * lc.k, &vb) != ICPMI_OK) return ICPMI_ERR_HIP;
-    return ICPMI_OK;
-}
-
-// index of the single quantile-type filter of the chain, or -1 (none) / -2 (more than one)
-static int fused_filter_slot(const LoopCfg& lc)
-{
-    int slot = -1;
-    for (int f = 0; f < lc.n_out; ++f)
-        if (lc.out_type[f] == ICPMI_OUT_TRIMMEDDIST || lc.out_type[f] == ICPMI_OUT_MEDIANDIST) slot = slot == -1 ? f : -2;
-    return slot;
-}
-
-// enqueue the quantile selections needed by the chain (no host sync); ba = the readings behind d_d2, nn = what the matcher's launch in front
-// of it answered (the fused chain skips what that launch already built)
-static void enqueue_selection(icpmi_ctx* c, const LoopCfg& lc, int64_t count, const BatchArgs& ba, const NnOutcome& nn, bool legacy = false)
-{
-    const int slot = legacy ? -2 : fused_filter_slot(lc);
-    int hb = (int)std::min<int64_t>((count + 2047) / 2048, 256);
-    if (hb < 1) hb = 1;
-    // RobustOutlierFilter{scaleEstimator: mad}: scale = sqrt(median |d2 - median(d2)|) -- two more selections on the legacy bins
-    // (disjoint from the fused levels), on the single-registration path only (a batch with such a chain runs reading by reading)
-    for (int f = 0; f < lc.n_out; ++f) {
-        if (lc.out_type[f] != ICPMI_OUT_ROBUST) continue;
-        const int se = (lc.out_iparam[f] >> 4) & 15;
-        const int nb = (int)lc.out_param2[f];
-        if (se == ICPMI_SCALE_MAD) {
-            for (int dest = 1; dest <= 2; ++dest) {
-#define MAD_PASS(P) \
-                if (dest == 1) hipLaunchKernelGGL((sel_hist_kernel<P, 1>), dim3(hb), dim3(256), 0, c->stream, c->d_d2, count, c->d_state, c->d_selhist, nb); \
-                else hipLaunchKernelGGL((sel_hist_kernel<P, 2>), dim3(hb), dim3(256), 0, c->stream, c->d_d2, count, c->d_state, c->d_selhist, nb); \
-                hipLaunchKernelGGL(sel_scan_kernel<P>, dim3(1), dim3(256), 0, c->stream, c->d_state, c->d_selhist, -1.f, f, 0, 0.f, dest, nb);
-                MAD_PASS(0) MAD_PASS(1) MAD_PASS(2)
-#undef MAD_PASS
-            }
-        } else if (se == ICPMI_SCALE_BERG) {
-            // iteration 1: the median of the finite positive d2 on the legacy bins; later iterations: the last scan kernel alone does the recurrence
-#define BERG_PASS(P) \
-            hipLaunchKernelGGL((sel_hist_kernel<P, 3>), dim3(hb), dim3(256), 0, c->stream, c->d_d2, count, c->d_state, c->d_selhist, nb); \
-            hipLaunchKernelGGL(sel_scan_kernel<P>, dim3(1), dim3(256), 0, c->stream, c->d_state, c->d_selhist, 0.5f, f, 0, lc.out_param[f], 3, nb);
-            BERG_PASS(0) BERG_PASS(1) BERG_PASS(2)
-#undef BERG_PASS
-        } else if (se == ICPMI_SCALE_STD) {
-            double* part = reinterpret_cast<double*>(c->d_selhist + ICPMI_SEL_BINS); // 256 doubles between the legacy bins and the fused levels
-            static_assert(ICPMI_SEL_BINS + 512 <= ICPMI_S2_C0, "partials of the std estimator fit in front of the fused histograms");
-            hipLaunchKernelGGL(std_part_kernel<0>, dim3(hb), dim3(256), 0, c->stream, c->d_d2, count, c->d_state, part, nb);
-            hipLaunchKernelGGL(std_tail_kernel<0>, dim3(1), dim3(256), 0, c->stream, c->d_state, part, hb, count, nb);
-            hipLaunchKernelGGL(std_part_kernel<1>, dim3(hb), dim3(256), 0, c->stream, c->d_d2, count, c->d_state, part, nb);
-            hipLaunchKernelGGL(std_tail_kernel<1>, dim3(1), dim3(256), 0, c->stream, c->d_state, part, hb, count, nb);
-        }
-    }
-    for (int f = 0; f < lc.n_out; ++f) {
-        if (lc.out_type[f] != ICPMI_OUT_VARTRIMMEDDIST) continue;
-        VtBuffers vb;
-        if (vt_buffers(c, count, &vb) != ICPMI_OK) return; // reserved by the caller: cannot fail here
-        const long long min_el = (long long)floorf(lc.out_param[f] * (float)count), max_el = (long long)floorf(lc.out_param2[f] * (float)count);
-        hipLaunchKernelGGL(vt_keys_kernel, dim3((int)((count + 255) / 256)), dim3(256), 0, c->stream, c->d_d2, count, c->d_state, vb.keys, vb.vals);
-        int half = 0;
-        if (radix_sort_pairs(c, vb.keys, vb.vals, count, 32, vb.tab, &half) != ICPMI_OK) return;
-        const unsigned long long* sorted = vb.keys + (half ? count : 0);
-        hipLaunchKernelGGL(vt_chunk_sums_kernel, dim3(vb.nchunks), dim3(256), 0, c->stream, sorted, c->d_state, vb.sums);
-        hipLaunchKernelGGL(vt_chunk_offsets_kernel, dim3(1), dim3(256), 0, c->stream, vb.sums, vb.nchunks);
-        hipLaunchKernelGGL(vt_frms_kernel, dim3(vb.nchunks), dim3(256), 0, c->stream, sorted, count, c->d_state, (const double*)vb.sums, min_el, max_el,
-                           lc.out_param3[f], vb.best_val, vb.best_idx);
-        hipLaunchKernelGGL(vt_pick_kernel, dim3(1), dim3(256), 0, c->stream, sorted, count, c->d_state, (const double*)vb.best_val,
-                           (const long long*)vb.best_idx, vb.nchunks, min_el, f);
-    }
-    if (slot >= 0) {
-        // fused chain: hist0 -> [scan0 + hist1] -> [scan1 + hist2]; scan2 happens inside the accumulation kernel
-        const float quant = lc.out_type[slot] == ICPMI_OUT_MEDIANDIST ? 0.5f : lc.out_param[slot];
-        if (!nn.built_hist0) {
-            // 4096 matches per workgroup: every workgroup flushes its LDS table with global atomics, fewer of them win (knn 6, 600 k
-            // matches: 1024 per workgroup -6 %, 2048 baseline, 4096 +0.8 %, 8192 -4 %)
-            int hb0 = (int)std::min<int64_t>((count + 4095) / 4096, 256);
-            if (hb0 < 1) hb0 = 1;
-            hipLaunchKernelGGL(sel2_hist0_kernel, dim3(hb0, ba.nscan), dim3(256), 0, c->stream, c->d_d2, ba, lc.k, c->d_state, c->d_selhist, quant,
-                               nn.built_win ? 1 : 0);
-        }
-        int hb2 = (int)std::min<int64_t>((count + 511) / 512, 512);
-        if (hb2 < 1) hb2 = 1;
-        hipLaunchKernelGGL(sel2_scan_hist_kernel, dim3(hb2, ba.nscan), dim3(256), 0, c->stream, c->d_d2, ba, lc.k, c->d_state, c->d_selhist, quant,
-                           (nn.built_win && !nn.built_hist0) ? 1 : 0);
-        return;
-    }
-    for (int f = 0; f < lc.n_out; ++f) {
-        const int type = lc.out_type[f];
-        if (type != ICPMI_OUT_TRIMMEDDIST && type != ICPMI_OUT_MEDIANDIST) continue;
-        const int is_med = type == ICPMI_OUT_MEDIANDIST;
-        const float quant = is_med ? 0.5f : lc.out_param[f];
-        const float factor = lc.out_param[f];
-        hipLaunchKernelGGL((sel_hist_kernel<0, 0>), dim3(hb), dim3(256), 0, c->stream, c->d_d2, count, c->d_state, c->d_selhist, 0);
-        hipLaunchKernelGGL(sel_scan_kernel<0>, dim3(1), dim3(256), 0, c->stream, c->d_state, c->d_selhist, quant, f, is_med, factor, 0, 0);
-        hipLaunchKernelGGL((sel_hist_kernel<1, 0>), dim3(hb), dim3(256), 0, c->stream, c->d_d2, count, c->d_state, c->d_selhist, 0);
-        hipLaunchKernelGGL(sel_scan_kernel<1>, dim3(1), dim3(256), 0, c->stream, c->d_state, c->d_selhist, quant, f, is_med, factor, 0, 0);
-        hipLaunchKernelGGL((sel_hist_kernel<2, 0>), dim3(hb), dim3(256), 0, c->stream, c->d_d2, count, c->d_state, c->d_selhist, 0);
-        hipLaunchKernelGGL(sel_scan_kernel<2>, dim3(1), dim3(256), 0, c->stream, c->d_state, c->d_selhist, quant, f, is_med, factor, 0, 0);
-    }
+    return selection_reserve(c, lc, n * lc.k);
 }
 
 template <int MIN, bool FUSED, bool EXT>
@@ -1621,21 +1008,17 @@ static void launch_accumulate(icpmi_ctx* c, const LoopCfg& lc, int nb, int slot,
 template <int MIN, bool FUSED, bool EXT>
 static void launch_accumulate_ext(icpmi_ctx* c, const LoopCfg& lc, int nb, int slot, const BatchArgs& ba, bool sorted)
 {
-    const float4* rn = lc.has_read_normals ? c->d_read_normals : nullptr;
+    const PairView v = pair_view(c, lc, sorted); // (EXT == (lc.ext != 0): launch_accumulate; match_pt is null for k > 1)
     const int is_med = slot >= 0 && lc.out_type[slot] == ICPMI_OUT_MEDIANDIST;
     const float factor = slot >= 0 ? lc.out_param[slot] : 0.f;
-    if (lc.k > 1) {
-        hipLaunchKernelGGL((accumulate_kernel<MIN, FUSED, EXT, 1024>), dim3(nb, ba.nscan), dim3(1024), 0, c->stream, sorted ? c->d_qsorted : c->d_reading, ba, acc_cap(), lc, c->d_state,
-                           c->d_map_sorted, c->has_normals ? c->d_normals_sorted : (const float4*)nullptr, rn, c->d_sidx, c->d_d2, c->d_selhist, slot, is_med, factor,
-                           (const float4*)nullptr, sorted ? c->d_qindex : (const int*)nullptr, (EXT && c->raw_has_scalar) ? c->d_raw_s : (const float*)nullptr,
-                           (MIN == ICPMI_MIN_POINT_TO_PLANE && c->has_normals && c->d_map_pn) ? c->d_map_pn : (const float4*)nullptr);
-        return;
-    }
-    hipLaunchKernelGGL((accumulate_kernel<MIN, FUSED, EXT>), dim3(nb, ba.nscan), dim3(256), 0, c->stream, sorted ? c->d_qsorted : c->d_reading, ba, acc_cap(), lc, c->d_state,
-                       c->d_map_sorted, c->has_normals ? c->d_normals_sorted : (const float4*)nullptr, rn, c->d_sidx, c->d_d2, c->d_selhist, slot, is_med, factor,
-                       (sorted && lc.k == 1) ? c->d_match_pt : (const float4*)nullptr, sorted ? c->d_qindex : (const int*)nullptr,
-                       (EXT && c->raw_has_scalar) ? c->d_raw_s : (const float*)nullptr,
-                       (lc.k > 1 && MIN == ICPMI_MIN_POINT_TO_PLANE && c->has_normals && c->d_map_pn) ? c->d_map_pn : (const float4*)nullptr);
+    // k > 1, point-to-plane: matched point and its normal side by side (map_build.hip: pn_kernel)
+    const float4* pnm = (lc.k > 1 && MIN == ICPMI_MIN_POINT_TO_PLANE && c->has_normals && c->d_map_pn) ? c->d_map_pn.get() : nullptr;
+    if (lc.k > 1)
+        hipLaunchKernelGGL((accumulate_kernel<MIN, FUSED, EXT, 1024>), dim3(nb, ba.nscan), dim3(1024), 0, c->stream, v.reading, ba, acc_cap(), lc, c->d_state,
+                           v.map, v.ref_normals, v.read_normals, v.sidx, v.d2, c->d_selhist, slot, is_med, factor, v.match_pt, v.qindex, v.ref_scalar, pnm);
+    else
+        hipLaunchKernelGGL((accumulate_kernel<MIN, FUSED, EXT>), dim3(nb, ba.nscan), dim3(256), 0, c->stream, v.reading, ba, acc_cap(), lc, c->d_state,
+                           v.map, v.ref_normals, v.read_normals, v.sidx, v.d2, c->d_selhist, slot, is_med, factor, v.match_pt, v.qindex, v.ref_scalar, pnm);
 }
 
 // publish = false: this solve leaves the progress word alone (an iteration inside a fixed-count graph: see loop_run)
@@ -2228,6 +1611,7 @@ icpmi_status loop_single_step(icpmi_ctx* c, int64_t n, const LoopCfg& lc, const 
 #define ICPMI_RES_NB 256   // pass-1 workgroups, one per CU (fixed, as ICPMI_COV_NB: the summation order depends on the slot count alone)
 #define ICPMI_RES_NV 5     // [0] sum r, [1] sum r^2, [2] sum w, [3] pairs, [4] max r
 #define ICPMI_RES_CH 8     // pass 2: eight threads per value, each over every eighth workgroup partial
+#define ICPMI_RES_MAX (1u << 4) // the slots that combine with fmax
 
 struct ResBlock { double sum_abs, sum_sq, weight_sum; long long pairs; float max_abs, limit; int error, pad; };
 
@@ -2235,26 +1619,16 @@ struct ResBlock { double sum_abs, sum_sq, weight_sum; long long pairs; float max
 // resolves -- here every workgroup does (the same lookup, the same limit)
 // blockIdx.y = pose of a batch (icpmi_residual_error_poses: one slice of the per-query arrays, one IcpState, one set of histograms and one
 // row of ICPMI_RES_NB partials per pose); a single call is the batch of one, so a pose is scored to the same bits alone or among others
-__global__ __launch_bounds__(256) void res_pairs_kernel(const float4* __restrict__ reading, const int* __restrict__ qindex, BatchArgs ba, LoopCfg lc,
-                                                        int kind, int planar, IcpState* __restrict__ st, const float4* __restrict__ map,
-                                                        const float4* __restrict__ ref_normals, const float4* __restrict__ read_normals,
-                                                        const float* __restrict__ ref_scalar, const int* __restrict__ sidx,
-                                                        const float* __restrict__ d2a, const float4* __restrict__ match_pt,
+__global__ __launch_bounds__(256) void res_pairs_kernel(PairView pv, BatchArgs ba, LoopCfg lc, int kind, int planar, IcpState* __restrict__ st,
                                                         const unsigned* __restrict__ hists, int fused_slot, int is_median, float factor,
                                                         double* __restrict__ partial)
 {
     const int n = ba.n[blockIdx.y];
-    {
-        const size_t qo = (size_t)blockIdx.y * (size_t)ba.qstride;
-        reading += qo; sidx += qo * lc.k; d2a += qo * lc.k;
-        if (qindex) qindex += qo;
-        if (match_pt) match_pt += qo;
-        hists += (size_t)blockIdx.y * ICPMI_SELHIST_WORDS;
-        partial += (size_t)blockIdx.y * (ICPMI_RES_NB * ICPMI_RES_NV);
-        st += blockIdx.y;
-    }
+    pair_view_slice(pv, ba, lc.k);
+    hists += (size_t)blockIdx.y * ICPMI_SELHIST_WORDS;
+    partial += (size_t)blockIdx.y * (ICPMI_RES_NB * ICPMI_RES_NV);
+    st += blockIdx.y;
     __shared__ unsigned shsel[16];
-    __shared__ double sh[4][ICPMI_RES_NV];
     float fused_limit = 0.f;
     if (fused_slot >= 0) {
         const unsigned cv = hists[ICPMI_S2_C1 + threadIdx.x];
@@ -2264,54 +1638,19 @@ __global__ __launch_bounds__(256) void res_pairs_kernel(const float4* __restrict
         fused_limit = is_median ? factor * q : q;
         if (blockIdx.x == 0 && threadIdx.x == 0) st->limits[fused_slot] = fused_limit;
     }
-    const float* T = st->T_iter;
-    const int64_t total_e = (int64_t)n * lc.k;
     double sr = 0.0, sq = 0.0, sw = 0.0, cnt = 0.0;
     float mx = 0.f;
-    const bool live = st->error == 0; // (a selection that found nothing to filter: the partials are written, all zero)
-    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; live && e < total_e; e += (int64_t)gridDim.x * 256) {
-        const float d2 = d2a[e];
-        if (d2 == INFINITY) continue;
-        const int qi = (int)(e / lc.k);
-        const int oi = qindex ? qindex[qi] : qi;
-        const int s = sidx[e];
-        const float4 r4 = reading[qi];
-        const float3 p = xf_point(T, r4.x, r4.y, r4.z, r4.w);
-        const float4 q = match_pt ? match_pt[e] : map[s];
-        const float dx = p.x - q.x, dy = p.y - q.y, dz = p.z - q.z;
-        float dot = 0.f, dot2 = 0.f;
-        if (ref_normals) {
-            const float4 nm = ref_normals[s];
-            dot = dx * nm.x + dy * nm.y + dz * nm.z;
-            dot2 = dx * nm.x + dy * nm.y; // forcedDim = 2
-        }
-        float w;
-        if (lc.ext) w = match_weight<true>(lc, st, d2, T, read_normals, oi, ref_normals, s, fused_slot, fused_limit, ref_scalar, __float_as_int(q.w), dot * dot);
-        else w = match_weight(lc, st, d2, T, read_normals, oi, ref_normals, s, fused_slot, fused_limit);
-        if (w == 0.f) continue;
-        const float r = kind == ICPMI_RES_POINT_TO_POINT ? sqrtf(d2) : fabsf(planar ? dot2 : dot);
-        sr += (double)r; sq += (double)r * (double)r; sw += (double)w; cnt += 1.0;
-        mx = fmaxf(mx, r);
-    }
-    // wave butterfly, then the four waves in order: a fixed pattern, the same sums on every call
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    double acc[ICPMI_RES_NV] = {sr, sq, sw, cnt, (double)mx};
-#pragma unroll
-    for (int i = 0; i < ICPMI_RES_NV; ++i) {
-        double v = acc[i];
-#pragma unroll
-        for (int m = 32; m > 0; m >>= 1) {
-            const double o = __shfl_xor(v, m, 64);
-            v = i == 4 ? fmax(v, o) : v + o;
-        }
-        if (lane == 0) sh[wv][i] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < ICPMI_RES_NV) {
-        const int i = threadIdx.x;
-        partial[(size_t)blockIdx.x * ICPMI_RES_NV + i] = i == 4 ? fmax(fmax(fmax(sh[0][i], sh[1][i]), sh[2][i]), sh[3][i])
-                                                                 : ((sh[0][i] + sh[1][i]) + sh[2][i]) + sh[3][i];
-    }
+    const bool have_n = pv.ref_normals != nullptr;
+    if (st->error == 0) // (otherwise a selection that found nothing to filter: the partials are written, all zero)
+        walk_pairs(pv, n, lc, st, st->T_iter, [&](const PairSlot& a) {
+            if (a.w == 0.f) return;
+            const float dot2 = have_n ? a.dx * a.nm.x + a.dy * a.nm.y : 0.f; // forcedDim = 2
+            const float r = kind == ICPMI_RES_POINT_TO_POINT ? sqrtf(a.d2) : fabsf(planar ? dot2 : a.dot);
+            sr += (double)r; sq += (double)r * (double)r; sw += (double)a.w; cnt += 1.0;
+            mx = fmaxf(mx, r);
+        }, fused_slot, fused_limit);
+    const double acc[ICPMI_RES_NV] = {sr, sq, sw, cnt, (double)mx};
+    block_partial_row<ICPMI_RES_NV, ICPMI_RES_MAX>(acc, partial + (size_t)blockIdx.x * ICPMI_RES_NV);
 }
 
 // blockIdx.x = pose of a batch: its row of partials, its IcpState, its ResBlock
@@ -2321,29 +1660,9 @@ __global__ __launch_bounds__(64) void res_finish_kernel(const double* __restrict
     partial += (size_t)blockIdx.x * (ICPMI_RES_NB * ICPMI_RES_NV);
     st += blockIdx.x;
     out += blockIdx.x;
-    __shared__ double part[ICPMI_RES_NV][ICPMI_RES_CH];
-    if (threadIdx.x < ICPMI_RES_NV * ICPMI_RES_CH) {
-        // every load issued before the first add (cov_solve_kernel)
-        constexpr int PER = ICPMI_RES_NB / ICPMI_RES_CH;
-        const int v = threadIdx.x / ICPMI_RES_CH, ch = threadIdx.x % ICPMI_RES_CH;
-        double x[PER];
-#pragma unroll
-        for (int i = 0; i < PER; ++i) x[i] = partial[(size_t)(ch + ICPMI_RES_CH * i) * ICPMI_RES_NV + v];
-        double acc = 0.0;
-#pragma unroll
-        for (int i = 0; i < PER; ++i) acc = v == 4 ? fmax(acc, x[i]) : acc + x[i];
-        part[v][ch] = acc;
-    }
-    __syncthreads();
+    __shared__ double tot[ICPMI_RES_NV];
+    block_ordered_total<ICPMI_RES_NV, ICPMI_RES_CH, ICPMI_RES_NB, ICPMI_RES_MAX>(partial, ICPMI_RES_NB, tot);
     if (threadIdx.x != 0) return;
-    double tot[ICPMI_RES_NV];
-#pragma unroll
-    for (int v = 0; v < ICPMI_RES_NV; ++v) {
-        double acc = 0.0;
-#pragma unroll
-        for (int ch = 0; ch < ICPMI_RES_CH; ++ch) acc = v == 4 ? fmax(acc, part[v][ch]) : acc + part[v][ch];
-        tot[v] = acc;
-    }
     out->sum_abs = tot[0]; out->sum_sq = tot[1]; out->weight_sum = tot[2];
     out->pairs = (long long)tot[3];
     out->max_abs = (float)tot[4];
@@ -2373,13 +1692,8 @@ static icpmi_status enqueue_residual_sums(icpmi_ctx* c, const BatchArgs& ba, con
                                           ResBlock* d_res)
 {
     const int slot = fused_filter_slot(l1);
-    const bool sorted = nn.out_sorted;
-    hipLaunchKernelGGL(res_pairs_kernel, dim3(ICPMI_RES_NB, ba.nscan), dim3(256), 0, c->stream, sorted ? (const float4*)c->d_qsorted : (const float4*)c->d_reading,
-                       sorted ? (const int*)c->d_qindex : (const int*)nullptr, ba, l1, kind, planar, c->d_state, (const float4*)c->d_map_sorted,
-                       c->has_normals ? (const float4*)c->d_normals_sorted : (const float4*)nullptr,
-                       l1.has_read_normals ? (const float4*)c->d_read_normals : (const float4*)nullptr,
-                       (l1.ext && c->raw_has_scalar) ? (const float*)c->d_raw_s : (const float*)nullptr, (const int*)c->d_sidx, (const float*)c->d_d2,
-                       (sorted && l1.k == 1) ? (const float4*)c->d_match_pt : (const float4*)nullptr, (const unsigned*)c->d_selhist, slot >= 0 ? slot : -1,
+    hipLaunchKernelGGL(res_pairs_kernel, dim3(ICPMI_RES_NB, ba.nscan), dim3(256), 0, c->stream, pair_view(c, l1, nn.out_sorted), ba, l1, kind, planar,
+                       c->d_state, (const unsigned*)c->d_selhist, slot >= 0 ? slot : -1,
                        (slot >= 0 && l1.out_type[slot] == ICPMI_OUT_MEDIANDIST) ? 1 : 0, slot >= 0 ? l1.out_param[slot] : 0.f, d_part);
     hipLaunchKernelGGL(res_finish_kernel, dim3(ba.nscan), dim3(64), 0, c->stream, (const double*)d_part, (const IcpState*)c->d_state, quantile_slot(l1), d_res);
     HIP_TRY(c, hipGetLastError());

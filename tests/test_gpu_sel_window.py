@@ -1,5 +1,5 @@
 """r5, the k > 1 loop (docs/MapperConfiguration.md:174-189, knn 6): the speculative level 0 of the fused quantile selection (common.h:
-ICPMI_S2_WIN; nn.hip: nnk_wg_kernel's tail; loop.hip: win_lookup) may only change WHERE a count comes from, never the count.
+ICPMI_S2_WIN; nn.hip: nnk_wg_kernel's tail; select.hip: win_lookup) may only change WHERE a count comes from, never the count.
 
 The NN kernel counts its distances into seven bins around the previous iteration's 16-bit prefix + below + above; when the selected
 rank falls inside, the stand-alone level-0 builder has nothing to do.  Hit or miss the counts are exact: trim limit, pair count and pose
