@@ -56,7 +56,22 @@ typedef enum {
 typedef enum {
     ICPMI_MIN_IDENTITY = 0,       /* IdentityErrorMinimizer (examples/config.yaml:62-63) */
     ICPMI_MIN_POINT_TO_POINT = 1, /* PointToPointErrorMinimizer                          */
-    ICPMI_MIN_POINT_TO_PLANE = 2  /* PointToPlaneErrorMinimizer (docs/MapperConfiguration.md:174-189) */
+    ICPMI_MIN_POINT_TO_PLANE = 2, /* PointToPlaneErrorMinimizer (docs/MapperConfiguration.md:174-189) */
+    /* PlaneToPlaneErrorMinimizer{epsilon, force4DOF}: generalized ICP (Segal, Haehnel, Thrun 2009) with plane-regularised covariances
+     * from the normals of BOTH clouds -- not libpointmatcher's.  Per pair, p = T_iter x, q its match, n_q the match's normal, n_p = R n_x
+     * the reading point's normal under T_iter's rotation (each normalised; a zero or non-finite normal: that side's covariance is I):
+     *     C(n) = I - (1 - eps) n n^T,  M = (C(n_q) + C(n_p))^-1 (adjugate / determinant, float),  J = [-[p]x  I],  d = p - q
+     *     A += w J^T M J,  b -= w J^T M d      (x = (omega, t); with M = n n^T this IS the point-to-plane system)
+     * M is re-formed every iteration from the current rotation and held during the solve.  The sums fill the point-to-plane slots
+     * (icpmi_minimize_step_normals: sums[0..20] A, [21..26] b, [27] sum w, [28] pairs) and the point-to-plane solve runs on them, force4DOF
+     * included.  eps: icpmi_set_plane_epsilon (default 1e-3).  The map AND the reading must carry normals: the entry points that take
+     * scan_normals3 serve it (icpmi_register, _dev, _fixed_dev, icpmi_minimize_step_normals) and return ICPMI_ERR_MISSING_NORMALS when the
+     * map has none or scan_normals3 is NULL -- as icpmi_register_prior* do, which carry none; icpmi_register_batch_dev,
+     * icpmi_register_multistart* and icpmi_minimize_step cannot carry them: ICPMI_ERR_UNSUPPORTED.  Rejected with ICPMI_ERR_INVALID_ARG:
+     * force_2d / is_2d, covariance = 1 (Censi's form is derived for the scalar residual), degeneracy_threshold != 0 (mu = lambda / sum w
+     * assumes unit-information pairs; M's scale is 1 / (2 eps)).  icpmi_residual_error* on such a handle reports the point-to-plane
+     * residual |(p - q) . n_q| (ICPMI_RES_CHAIN = ICPMI_RES_POINT_TO_PLANE); the sensor-noise overlap is the point-to-plane count. */
+    ICPMI_MIN_PLANE_TO_PLANE = 3
 } icpmi_minimizer;
 
 /* OutlierFilters (icp.outlierFilters) */
@@ -294,6 +309,17 @@ icpmi_status icpmi_outlier_weights(icpmi_handle h, const float* d2, const int32_
  * afterwards reports this step's system (c0 and L are those of reading4 as given). */
 icpmi_status icpmi_minimize_step(icpmi_handle h, const float* reading4, int64_t n, const float* T_iter,
                                  float T_step[16], double sums[32], icpmi_stats* stats);
+/* ... with the reading's `normals` (read_normals3: 3 per point, the frame of reading4; rotated by T_iter on the device).  Serves every
+ * minimiser: ICPMI_MIN_PLANE_TO_PLANE needs them (NULL: ICPMI_ERR_MISSING_NORMALS), for the others they feed
+ * SurfaceNormalOutlierFilter only (which icpmi_minimize_step refuses) and NULL makes the call icpmi_minimize_step. */
+icpmi_status icpmi_minimize_step_normals(icpmi_handle h, const float* reading4, int64_t n, const float* read_normals3, const float* T_iter,
+                                         float T_step[16], double sums[32], icpmi_stats* stats);
+
+/* epsilon of ICPMI_MIN_PLANE_TO_PLANE's covariances C(n) = I - (1 - eps) n n^T: finite, 0 < eps <= 1 (else ICPMI_ERR_INVALID_ARG and the
+ * value stays); default 1e-3.  State of the handle: icpmi_set_config leaves it.  It is part of what a cached loop graph is valid for, so the
+ * next registration runs with the new value.  eps = 1 makes every covariance I: A = 0.5 sum w J^T J. */
+icpmi_status icpmi_set_plane_epsilon(icpmi_handle h, float eps);
+icpmi_status icpmi_get_plane_epsilon(icpmi_handle h, float* eps);
 
 /* ---- map-side operators on the path ---- */
 

@@ -120,7 +120,12 @@ static icpmi_status validate_config(const icpmi_config* cfg, std::string& err)
         if (t == ICPMI_OUT_TRIMMEDDIST && !(p >= 0.f && p <= 1.f)) { err = "InvalidParameter: TrimmedDist ratio must be in [0, 1]"; return ICPMI_ERR_INVALID_ARG; }
         if ((t == ICPMI_OUT_MAXDIST || t == ICPMI_OUT_MINDIST || t == ICPMI_OUT_MEDIANDIST) && !(p >= 0.f)) { err = "InvalidParameter: negative outlier filter parameter"; return ICPMI_ERR_INVALID_ARG; }
     }
-    if (cfg->minimizer < ICPMI_MIN_IDENTITY || cfg->minimizer > ICPMI_MIN_POINT_TO_PLANE) { err = "InvalidParameter: unknown error minimizer"; return ICPMI_ERR_INVALID_ARG; }
+    if (cfg->minimizer < ICPMI_MIN_IDENTITY || cfg->minimizer > ICPMI_MIN_PLANE_TO_PLANE) { err = "InvalidParameter: unknown error minimizer"; return ICPMI_ERR_INVALID_ARG; }
+    if (cfg->minimizer == ICPMI_MIN_PLANE_TO_PLANE) {
+        if (cfg->force_2d || cfg->is_2d) { err = "InvalidParameter: PlaneToPlaneErrorMinimizer: no planar mode (force2D / 2-D clouds)"; return ICPMI_ERR_INVALID_ARG; }
+        if (cfg->covariance) { err = "InvalidParameter: PlaneToPlaneErrorMinimizer: no pose covariance (Censi's form is derived for the scalar point-to-plane residual)"; return ICPMI_ERR_INVALID_ARG; }
+        if (cfg->degeneracy_threshold != 0.f) { err = "InvalidParameter: PlaneToPlaneErrorMinimizer: no degeneracyThreshold (mu = lambda / sum w assumes unit-information pairs)"; return ICPMI_ERR_INVALID_ARG; }
+    }
     if (cfg->force_4dof && cfg->force_2d) { err = "InvalidParameter: force2D and force4DOF exclude each other"; return ICPMI_ERR_INVALID_ARG; }
     if (cfg->max_iterations < 1) { err = "InvalidParameter: maxIterationCount must be >= 1"; return ICPMI_ERR_INVALID_ARG; }
     if (cfg->use_differential && (cfg->smooth_length < 1 || cfg->smooth_length > ICPMI_MAX_SMOOTH)) { err = "InvalidParameter: smoothLength must be in [1, 16]"; return ICPMI_ERR_INVALID_ARG; }
@@ -622,6 +627,15 @@ static icpmi_status chain_setup(icpmi_handle h, int64_t n, const float* d_n3, in
     return ICPMI_OK;
 }
 
+// the entry points that cannot carry the reading's normals do not serve PlaneToPlaneErrorMinimizer
+static icpmi_status reject_plane_to_plane(icpmi_ctx* h, const char* who)
+{
+    if (h->cfg.minimizer != ICPMI_MIN_PLANE_TO_PLANE) return ICPMI_OK;
+    h->last_error = std::string(who) + ": PlaneToPlaneErrorMinimizer needs the reading's normals, which this entry point cannot carry "
+                    "(icpmi_register*, icpmi_minimize_step_normals take them)";
+    return ICPMI_ERR_UNSUPPORTED;
+}
+
 static icpmi_status register_impl(icpmi_handle h, const float* d_scan4, int64_t n, const float* d_n3, int fixed_iters,
                                   float T_out[16], icpmi_stats* stats)
 {
@@ -641,6 +655,11 @@ static icpmi_status register_impl(icpmi_handle h, const float* d_scan4, int64_t 
         h->last_error = "InvalidField: PointToPlaneErrorMinimizer needs the descriptor 'normals' on the map";
         return ICPMI_ERR_MISSING_NORMALS;
     }
+    const bool gicp = h->cfg.minimizer == ICPMI_MIN_PLANE_TO_PLANE;
+    if (gicp && (!h->has_normals || (n > 0 && !d_n3))) {
+        h->last_error = "InvalidField: PlaneToPlaneErrorMinimizer needs the descriptor 'normals' on both reading and map";
+        return ICPMI_ERR_MISSING_NORMALS;
+    }
     { const icpmi_status ds = ensure_degen_block(h); if (ds != ICPMI_OK) return ds; }
     LoopCfg lc;
     const float* d_r2row = nullptr;
@@ -653,9 +672,10 @@ static icpmi_status register_impl(icpmi_handle h, const float* d_scan4, int64_t 
                     (lc.minimizer == ICPMI_MIN_POINT_TO_POINT || (lc.minimizer == ICPMI_MIN_POINT_TO_PLANE && d_n3));
     lc.sensor_noise = sn ? 1 : 0;
     if (sn && d_n3) lc.has_read_normals = 1;
+    if (gicp) lc.has_read_normals = 1; // (the pair sums read them)
     icpmi_stats local;
     if (!stats && stats_json()) stats = &local;
-    const icpmi_status rs = loop_run(h, (const float4*)d_scan4, (needs_rn || sn) ? d_n3 : nullptr, n, lc, d_r2row, fixed_iters > 0, T_out, stats);
+    const icpmi_status rs = loop_run(h, (const float4*)d_scan4, (needs_rn || sn || gicp) ? d_n3 : nullptr, n, lc, d_r2row, fixed_iters > 0, T_out, stats);
     if (stats_json() && stats) write_stats_json(*stats, n, rs);
     return rs;
 }
@@ -727,6 +747,7 @@ static bool chain_takes_batch(const icpmi_ctx* h)
     }
     if (nquant > 1) together = false;
     if (h->cfg.var_dist) together = false; // (every reading needs its own row of radii)
+    if (h->cfg.minimizer == ICPMI_MIN_PLANE_TO_PLANE) together = false; // (... and its own normals)
     if (h->cfg.degeneracy_threshold != 0.f) together = false; // (one side block per handle: the degeneracy-aware solve serves single registrations)
     if (together) {
         const GridParams& top = h->levels.g[h->levels.nlev - 1];
@@ -744,6 +765,7 @@ icpmi_status icpmi_register_batch_dev(icpmi_handle h, int32_t batch, const float
     }
     for (int b = 0; b < batch; ++b)
         if (n[b] < 0 || (n[b] > 0 && !d_scans4[b])) { h->last_error = "register_batch: bad arguments"; return ICPMI_ERR_INVALID_ARG; }
+    { const icpmi_status ps = reject_plane_to_plane(h, "register_batch"); if (ps != ICPMI_OK) return ps; }
     // The one-launch-per-iteration path serves the chains whose kernels take a batch: k = 1 on the grid pyramid without a
     // brute-force pass, at most one quantile filter, no filter that reads descriptors of the reading.  Everything else --
     // and empty readings, a handle without a map -- runs the readings one after the other: same results, no sharing.
@@ -792,7 +814,7 @@ static icpmi_status residual_chain_setup(icpmi_handle h, const char* who, int64_
 {
     int32_t kind = *kind_io;
     if (kind == ICPMI_RES_CHAIN) {
-        if (h->cfg.minimizer != ICPMI_MIN_POINT_TO_POINT && h->cfg.minimizer != ICPMI_MIN_POINT_TO_PLANE) {
+        if (h->cfg.minimizer == ICPMI_MIN_IDENTITY) {
             h->last_error = std::string(who) + ": IdentityErrorMinimizer has no residual (name ICPMI_RES_POINT_TO_POINT or ICPMI_RES_POINT_TO_PLANE)";
             return ICPMI_ERR_UNSUPPORTED;
         }
@@ -984,6 +1006,7 @@ icpmi_status icpmi_register_multistart_dev(icpmi_handle h, const float* d_scan4,
     if (n_starts < 1 || n_starts > ICPMI_MAX_BATCH || n < 0 || (n > 0 && !d_scan4) || !priors || !T_out || fixed_iterations < 0) {
         h->last_error = "register_multistart: bad arguments (1 <= n_starts <= 16)"; return ICPMI_ERR_INVALID_ARG;
     }
+    { const icpmi_status ps = reject_plane_to_plane(h, "register_multistart"); if (ps != ICPMI_OK) return ps; }
     h->scan_map_n = 0; // (the slices below reuse the stage of icpmi_register_prior: nothing is left staged)
     const int64_t NS = (n + 63) / 64 * 64;
     if (h->d_scan_map.ensure(h, (size_t)NS * n_starts + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
@@ -1131,10 +1154,10 @@ icpmi_status icpmi_outlier_weights(icpmi_handle h, const float* d2, const int32_
     return loop_outlier_weights(h, lc, d2, ids, k, n, read_normals3, weights, limit_out);
 }
 
-icpmi_status icpmi_minimize_step(icpmi_handle h, const float* reading4, int64_t n, const float* T_iter, float T_step[16],
-                                 double sums[32], icpmi_stats* stats)
+// icpmi_minimize_step (read_normals3 == nullptr) and icpmi_minimize_step_normals
+static icpmi_status minimize_step_impl(icpmi_handle h, const float* reading4, int64_t n, const float* read_normals3, const float* T_iter,
+                                       float T_step[16], double sums[32], icpmi_stats* stats)
 {
-    CHECK_H(h);
     if (n <= 0 || !reading4) { h->last_error = "minimize_step: bad arguments"; return ICPMI_ERR_INVALID_ARG; }
     { const icpmi_status es = check_ext_filters(h); if (es != ICPMI_OK) return es; }
     { const icpmi_status rs = reject_reading_source(h, "minimize_step"); if (rs != ICPMI_OK) return rs; }
@@ -1142,6 +1165,10 @@ icpmi_status icpmi_minimize_step(icpmi_handle h, const float* reading4, int64_t 
     if (h->m <= 0) { h->last_error = "minimize_step: no map"; return ICPMI_ERR_INVALID_ARG; }
     if (h->cfg.minimizer == ICPMI_MIN_POINT_TO_PLANE && !h->has_normals) {
         h->last_error = "InvalidField: PointToPlaneErrorMinimizer needs the descriptor 'normals' on the map";
+        return ICPMI_ERR_MISSING_NORMALS;
+    }
+    if (h->cfg.minimizer == ICPMI_MIN_PLANE_TO_PLANE && (!h->has_normals || !read_normals3)) {
+        h->last_error = "InvalidField: PlaneToPlaneErrorMinimizer needs the descriptor 'normals' on both reading and map";
         return ICPMI_ERR_MISSING_NORMALS;
     }
     if (stats) { memset(stats, 0, sizeof *stats); stats->sensor_noise_overlap = -1.f; }
@@ -1153,8 +1180,47 @@ icpmi_status icpmi_minimize_step(icpmi_handle h, const float* reading4, int64_t 
     { const icpmi_status ds = ensure_degen_block(h); if (ds != ICPMI_OK) return ds; }
     LoopCfg lc = make_loop_cfg(h, 1);
     for (int f = 0; f < lc.n_out; ++f)
-        if (lc.out_type[f] == ICPMI_OUT_SURFACENORMAL) { h->last_error = "minimize_step: SurfaceNormal filter needs icpmi_register"; return ICPMI_ERR_UNSUPPORTED; }
+        if (lc.out_type[f] == ICPMI_OUT_SURFACENORMAL) {
+            if (!read_normals3) { h->last_error = "minimize_step: SurfaceNormal filter needs icpmi_register"; return ICPMI_ERR_UNSUPPORTED; }
+            if (!h->has_normals) { h->last_error = "InvalidField: SurfaceNormalOutlierFilter needs 'normals' on both reading and map"; return ICPMI_ERR_MISSING_NORMALS; }
+        }
+    if (read_normals3) {
+        const icpmi_status us = loop_upload_read_normals(h, read_normals3, n);
+        if (us != ICPMI_OK) return us;
+        lc.has_read_normals = 1;
+    }
     return loop_single_step(h, n, lc, T_iter, T_step, sums, stats);
+}
+
+icpmi_status icpmi_minimize_step(icpmi_handle h, const float* reading4, int64_t n, const float* T_iter, float T_step[16],
+                                 double sums[32], icpmi_stats* stats)
+{
+    CHECK_H(h);
+    { const icpmi_status ps = reject_plane_to_plane(h, "minimize_step"); if (ps != ICPMI_OK) return ps; }
+    return minimize_step_impl(h, reading4, n, nullptr, T_iter, T_step, sums, stats);
+}
+
+icpmi_status icpmi_minimize_step_normals(icpmi_handle h, const float* reading4, int64_t n, const float* read_normals3, const float* T_iter,
+                                         float T_step[16], double sums[32], icpmi_stats* stats)
+{
+    CHECK_H(h);
+    return minimize_step_impl(h, reading4, n, read_normals3, T_iter, T_step, sums, stats);
+}
+
+icpmi_status icpmi_set_plane_epsilon(icpmi_handle h, float eps)
+{
+    CHECK_H(h);
+    if (!std::isfinite(eps) || !(eps > 0.f) || eps > 1.f) { h->last_error = "set_plane_epsilon: epsilon must be finite and in (0, 1]"; return ICPMI_ERR_INVALID_ARG; }
+    h->plane_eps = eps; // (no graph to drop: make_loop_cfg puts it into the LoopCfg, which loop_sig hashes)
+    return ICPMI_OK;
+}
+
+icpmi_status icpmi_get_plane_epsilon(icpmi_handle h, float* eps)
+{
+    CHECK_H(h);
+    if (!eps) { h->last_error = "get_plane_epsilon: eps is null"; return ICPMI_ERR_INVALID_ARG; }
+    *eps = h->plane_eps;
+    return ICPMI_OK;
 }
 
 icpmi_status icpmi_surface_normals(icpmi_handle h, const float* pts4, int64_t m, int32_t knn, float* normals3)

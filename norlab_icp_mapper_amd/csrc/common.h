@@ -249,6 +249,9 @@ struct LoopCfg {
     float degen_thr;          // |degeneracy_threshold|
     double* degen_blk;        // the handle's side block (layout below), null when off
 };
+// ICPMI_MIN_PLANE_TO_PLANE travels as a point-to-plane chain (its pair sums fill the same slots, the solve is the same) whose degen_thr, free
+// because the degeneracy-aware solve is rejected with it, carries the covariances' epsilon: > 0 picks the plane-to-plane pair sums
+static inline float plane_to_plane_eps(const LoopCfg& lc) { return (lc.minimizer == ICPMI_MIN_POINT_TO_PLANE && lc.degen == 0) ? lc.degen_thr : 0.f; }
 // slot of the chain's Trimmed / Median / VarTrimmed filter (the last of them: the one whose limit a call reports), or -1.  Upstream, a
 // chain with one throws "no outlier to filter" on an empty reading where any other throws "no point to minimize".
 static inline int quantile_slot(const LoopCfg& lc)
@@ -755,6 +758,9 @@ struct icpmi_ctx {
     // icpmi_get_localizability: the side block of the degeneracy-aware solve (ICPMI_DG_*; allocated when a chain first asks for it) and
     // whether it holds the report of the last single registration (cleared by batches, multistart and whatever clears cov_ready)
     DevArr<double> d_degen; bool degen_ready = false;
+    // icpmi_set_plane_epsilon: epsilon of the plane-to-plane minimiser's covariances; handle state (icpmi_set_config leaves it), carried into
+    // the kernels -- and into the signature of a cached loop graph -- by make_loop_cfg
+    float plane_eps = 1e-3f;
     DevArr<IcpState> d_state;          // ICPMI_MAX_BATCH states (a single registration uses the first)
     IcpState* h_state = nullptr;                               // pinned mirror (ICPMI_MAX_BATCH)
     bool zero_pending = false;                                 // d_state / d_selhist still to be cleared: on the stream the handle really uses, at its first call (zero_state_if_pending)
@@ -1223,6 +1229,8 @@ icpmi_status loop_run_batch(icpmi_ctx* c, int batch, const float* const* d_scans
                             float* T_out, icpmi_stats* stats, icpmi_status* status);
 icpmi_status loop_single_step(icpmi_ctx* c, int64_t n, const LoopCfg& lc, const float* T_iter_host, float T_step[16],
                               double sums[32], icpmi_stats* stats);
+// the reading's normals (host, 3 per point) into c->d_read_normals, padded as a registration's head pads them
+icpmi_status loop_upload_read_normals(icpmi_ctx* c, const float* normals3, int64_t n);
 // getResidualError() of the centred reading in c->d_reading under the centred-frame pose T (host, column-major); kind 1 / 2
 icpmi_status loop_residual(icpmi_ctx* c, int64_t n, const LoopCfg& lc, const float T[16], int kind, int planar, const float* d_r2row,
                            icpmi_residual* out);

@@ -46,7 +46,7 @@ __device__ __forceinline__ float match_weight(const LoopCfg& lc, const IcpState*
                                               const float* __restrict__ T, const float4* __restrict__ read_normals, int qi,
                                               const float4* __restrict__ ref_normals, int sidx, int fused_slot = -1,
                                               float fused_limit = 0.f, const float* __restrict__ ref_scalar = nullptr, int orig = 0,
-                                              float plane2 = 0.f)
+                                              float plane2 = 0.f, const float4* rn_kept = nullptr)
 {
     float w = 1.f;
     for (int f = 0; f < lc.n_out; ++f) {
@@ -57,7 +57,7 @@ __device__ __forceinline__ float match_weight(const LoopCfg& lc, const IcpState*
         else if (type == ICPMI_OUT_MEDIANDIST || type == ICPMI_OUT_TRIMMEDDIST || type == ICPMI_OUT_VARTRIMMEDDIST)
             w *= (d2 <= (f == fused_slot ? fused_limit : st->limits[f])) ? 1.f : 0.f;
         else if (type == ICPMI_OUT_SURFACENORMAL) {
-            const float4 a = read_normals[qi];
+            const float4 a = rn_kept ? *rn_kept : read_normals[qi]; // (rn_kept: the plane-to-plane pair sums hold the reading's normal already)
             float ax = a.x, ay = a.y, az = a.z;
             if (T) { // descriptors named "normals" rotate with the cloud
                 const float rx = fmaf(T[8], az, fmaf(T[4], ay, T[0] * ax));
@@ -212,7 +212,7 @@ __device__ __forceinline__ V block_tree_sum(V v, V* sh /* 256 */)
 // ---------------------------------------------------------------------------------------------
 // pair sums (ErrorMinimizer::compute gather + the products of SURVEY.md B.5 / B.6)
 // layout of the ICPMI_NV doubles:
-//   point-to-plane: [0..20] upper triangle of A row-major, [21..26] b
+//   point-to-plane: [0..20] upper triangle of A row-major, [21..26] b (plane-to-plane: the same slots)
 //   point-to-point: [0] sum w, [1..3] sum w p, [4..6] sum w q, [7 + 3c + r] sum w q_r p_c
 //   always:         [27] sum w, [28] number of pairs
 // ---------------------------------------------------------------------------------------------
@@ -227,6 +227,22 @@ __host__ __device__ __forceinline__ int acc_blocks_dev(int64_t count, int cap, i
     const int64_t nb = (count + bt - 1) / bt;
     return (int)(nb < 1 ? 1 : (nb > cap ? cap : nb));
 }
+
+// plane-to-plane: a normal scaled to length 1; a zero or non-finite one is "no surface model" (zero: that side's covariance becomes I)
+__device__ __forceinline__ float3 unit_or_zero(float x, float y, float z)
+{
+    const float l2 = x * x + y * y + z * z;
+    const bool ok = l2 > 0.f && l2 < INFINITY;
+    const float inv = ok ? 1.f / sqrtf(l2) : 0.f;
+    return ok ? make_float3(x * inv, y * inv, z * inv) : make_float3(0.f, 0.f, 0.f);
+}
+// a normal's three components (its fourth word is padding: 12 bytes requested, three registers held while the load is in flight)
+__device__ __forceinline__ float4 ld_normal(const float4* __restrict__ p)
+{
+    const float3 v = *reinterpret_cast<const float3*>(p);
+    return make_float4(v.x, v.y, v.z, 0.f);
+}
+__device__ __forceinline__ float3 cross3(float3 a, float3 b) { return make_float3(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x); }
 
 template <int MIN, bool FUSED, bool EXT, int BT = 256>
 __global__ __launch_bounds__(BT) void accumulate_kernel(const float4* __restrict__ reading, BatchArgs ba, int acc_cap, LoopCfg lc,
@@ -283,6 +299,7 @@ __global__ __launch_bounds__(BT) void accumulate_kernel(const float4* __restrict
     constexpr int PF = BT > 256 ? 3 : 2;
     unsigned hw = hdr_load(st);
     float pd2[PF]; int ps[PF]; float4 pr[PF], pq[PF];
+    int po[PF]; // plane-to-plane: the caller's index of the reading point, whose normal the second trip fetches
 #pragma unroll
     for (int u = 0; u < PF; ++u) {
         const int64_t e = e_first + u * estep;
@@ -290,7 +307,11 @@ __global__ __launch_bounds__(BT) void accumulate_kernel(const float4* __restrict
         pd2[u] = in ? ld_stream(d2a + e) : INFINITY;
         ps[u] = in ? ld_stream(sidx + e) : -1;
         pr[u] = ld_stream(reading + (in ? (int)(e / lc.k) : 0));
-        pq[u] = (match_pt && in) ? ld_stream(match_pt + e) : ((pnm && ps[u] >= 0) ? pnm[2 * (size_t)ps[u]] : make_float4(0.f, 0.f, 0.f, 0.f));
+        if constexpr (MIN == ICPMI_MIN_PLANE_TO_PLANE) po[u] = in ? (qindex ? ld_stream(qindex + (int)(e / lc.k)) : (int)(e / lc.k)) : -1;
+        if constexpr (MIN == ICPMI_MIN_PLANE_TO_PLANE) // (every pair arrives at the sums with all four of its gathers: no dependent load behind them)
+            pq[u] = (match_pt && in) ? ld_stream(match_pt + e) : (ps[u] >= 0 ? (pnm ? pnm[2 * (size_t)ps[u]] : map[ps[u]]) : make_float4(0.f, 0.f, 0.f, 0.f));
+        else
+            pq[u] = (match_pt && in) ? ld_stream(match_pt + e) : ((pnm && ps[u] >= 0) ? pnm[2 * (size_t)ps[u]] : make_float4(0.f, 0.f, 0.f, 0.f));
     }
     unsigned cv = (FUSED && threadIdx.x < 256) ? hists[ICPMI_S2_C1 + threadIdx.x] : 0u; // same round trip as the elements
     // the join: ONE point for the header and the coarse counts (issued last: the pairs in front of them have arrived with them).  Every
@@ -304,10 +325,19 @@ __global__ __launch_bounds__(BT) void accumulate_kernel(const float4* __restrict
 #pragma unroll
     for (int i = 0; i < 16; ++i) T[i] = hv.f(ICPMI_HDR_W(T_iter) + i);
     // second round trip, overlapping the fine-histogram read of the selection scan: the matched normals
-    float4 pn[PF];
+    // (plane-to-plane: ... and the reading's own normals, by the caller's index that arrived with the first trip)
+    constexpr bool USES_N = MIN == ICPMI_MIN_POINT_TO_PLANE || MIN == ICPMI_MIN_PLANE_TO_PLANE;
+    float4 pn[PF], prn[PF];
 #pragma unroll
-    for (int u = 0; u < PF; ++u)
-        pn[u] = (MIN == ICPMI_MIN_POINT_TO_PLANE && ps[u] >= 0) ? (pnm ? pnm[2 * (size_t)ps[u] + 1] : normals[ps[u]]) : make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int u = 0; u < PF; ++u) {
+        prn[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if constexpr (MIN == ICPMI_MIN_PLANE_TO_PLANE) {
+            pn[u] = ps[u] >= 0 ? ld_normal(pnm ? pnm + 2 * (size_t)ps[u] + 1 : normals + ps[u]) : make_float4(0.f, 0.f, 0.f, 0.f);
+            if (po[u] >= 0) prn[u] = ld_normal(read_normals + po[u]);
+        } else {
+            pn[u] = (USES_N && ps[u] >= 0) ? (pnm ? pnm[2 * (size_t)ps[u] + 1] : normals[ps[u]]) : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+    }
     if (done) return;
     if (blockIdx.x == 0 && threadIdx.x == 0) nn_stamp_close(st, t_nn_begin);
     float fused_limit = 0.f;
@@ -324,35 +354,38 @@ __global__ __launch_bounds__(BT) void accumulate_kernel(const float4* __restrict
         // ... and so is the speculative window of the k > 1 loop (its readers ran in the two kernels before this one)
         if (lc.k > 1) for (int64_t i = gtid; i < 2 * ICPMI_WIN_U64; i += stride) hists[ICPMI_S2_WIN + i] = 0;
     }
-    constexpr int NVAL = MIN == ICPMI_MIN_POINT_TO_PLANE ? 27 : (MIN == ICPMI_MIN_POINT_TO_POINT ? 16 : 0);
+    constexpr int NVAL = USES_N ? 27 : (MIN == ICPMI_MIN_POINT_TO_POINT ? 16 : 0);
     double acc[NVAL > 0 ? NVAL : 1];
 #pragma unroll
     for (int i = 0; i < (NVAL > 0 ? NVAL : 1); ++i) acc[i] = 0.0;
     double wsum = 0.0, cnt = 0.0;
     double b2d[3] = {0.0, 0.0, 0.0}; // force2D: b of the 2-D residual (EXT variant only)
-    auto pair = [&](int64_t e, float d2, int s, float4 r, float4 qkept, float4 nkept, bool have_n) {
+    // plane-to-plane (GICP): the caller hands over everything the pair needs -- q, n_q, the reading's normal and its caller's index okept
+    constexpr bool GICP = MIN == ICPMI_MIN_PLANE_TO_PLANE;
+    auto pair = [&](int64_t e, float d2, int s, float4 r, float4 qkept, float4 nkept, bool have_n, float4 rnkept, int okept) {
         if (d2 == INFINITY) return;
         const int qi = (int)(e / lc.k);
         float w;
         if (EXT) {
             // the filters that read the pair itself: original index of the matched point (its .w), point-to-plane residual
             const float3 pe = xf_point(T, r.x, r.y, r.z, r.w);
-            const float4 qe = (match_pt || (pnm && have_n)) ? qkept : (pnm ? pnm[2 * (size_t)s] : map[s]);
+            const float4 qe = (GICP || match_pt || (pnm && have_n)) ? qkept : (pnm ? pnm[2 * (size_t)s] : map[s]);
             float plane2 = 0.f;
             if (normals) {
-                const float4 ne = have_n && MIN == ICPMI_MIN_POINT_TO_PLANE ? nkept : (pnm ? pnm[2 * (size_t)s + 1] : normals[s]);
+                const float4 ne = GICP || (have_n && USES_N) ? nkept : (pnm ? pnm[2 * (size_t)s + 1] : normals[s]);
                 const float dx = pe.x - qe.x, dy = pe.y - qe.y, dz = pe.z - qe.z;
                 const float dot = dx * ne.x + dy * ne.y + dz * ne.z;
                 plane2 = dot * dot;
             }
-            w = match_weight<true>(lc, st, d2, T, read_normals, qindex ? qindex[qi] : qi, normals, s, FUSED ? fused_slot : -1, fused_limit,
-                                   ref_scalar, __float_as_int(qe.w), plane2);
-        } else w = match_weight(lc, st, d2, T, read_normals, qindex ? qindex[qi] : qi, normals, s, FUSED ? fused_slot : -1, fused_limit);
+            w = match_weight<true>(lc, st, d2, T, read_normals, GICP ? okept : (qindex ? qindex[qi] : qi), normals, s, FUSED ? fused_slot : -1, fused_limit,
+                                   ref_scalar, __float_as_int(qe.w), plane2, GICP ? &rnkept : nullptr);
+        } else w = match_weight(lc, st, d2, T, read_normals, GICP ? okept : (qindex ? qindex[qi] : qi), normals, s, FUSED ? fused_slot : -1, fused_limit,
+                                nullptr, 0, 0.f, GICP ? &rnkept : nullptr);
         if (w == 0.f) return;
         wsum += w; cnt += 1.0;
         if (MIN == ICPMI_MIN_IDENTITY) return;
         const float3 p = xf_point(T, r.x, r.y, r.z, r.w);
-        const float4 q = (match_pt || (pnm && have_n)) ? qkept : (pnm ? pnm[2 * (size_t)s] : map[s]);
+        const float4 q = (GICP || match_pt || (pnm && have_n)) ? qkept : (pnm ? pnm[2 * (size_t)s] : map[s]);
         if (MIN == ICPMI_MIN_POINT_TO_POINT) {
             const double dw = w;
             acc[0] += dw;
@@ -383,13 +416,56 @@ __global__ __launch_bounds__(BT) void accumulate_kernel(const float4* __restrict
 #pragma unroll
                 for (int a = 0; a < 3; ++a) b2d[a] -= ((double)w * F[2 + a]) * dot2;
             }
+        } else if constexpr (MIN == ICPMI_MIN_PLANE_TO_PLANE) {
+            // generalized ICP with plane-regularised covariances: A += w G M G^T, b -= w G M d with G = J^T = [[p]x; I],
+            // M = (C(n_q) + C(R n_x))^-1, C(n) = I - (1 - eps) n n^T.  M = n n^T would give the point-to-plane branch above: G n = F.
+            const float4 nq = nkept, rn = rnkept;
+            const float g = 1.f - lc.degen_thr; // (the slot carries epsilon for this instantiation: common.h, plane_to_plane_eps)
+            const float3 uq = unit_or_zero(nq.x, nq.y, nq.z);
+            const float3 up = unit_or_zero(fmaf(T[8], rn.z, fmaf(T[4], rn.y, T[0] * rn.x)), fmaf(T[9], rn.z, fmaf(T[5], rn.y, T[1] * rn.x)),
+                                           fmaf(T[10], rn.z, fmaf(T[6], rn.y, T[2] * rn.x)));
+            // S = C(n_q) + C(n_p), symmetric: xx xy xz yy yz zz
+            const float sxx = 2.f - g * (uq.x * uq.x + up.x * up.x), syy = 2.f - g * (uq.y * uq.y + up.y * up.y), szz = 2.f - g * (uq.z * uq.z + up.z * up.z);
+            const float sxy = -g * (uq.x * uq.y + up.x * up.y), sxz = -g * (uq.x * uq.z + up.x * up.z), syz = -g * (uq.y * uq.z + up.y * up.z);
+            // M = adj(S) / det(S)
+            const float c00 = syy * szz - syz * syz, c01 = sxz * syz - sxy * szz, c02 = sxy * syz - sxz * syy;
+            const float c11 = sxx * szz - sxz * sxz, c12 = sxy * sxz - sxx * syz, c22 = sxx * syy - sxy * sxy;
+            const float idet = 1.f / (sxx * c00 + sxy * c01 + sxz * c02);
+            const float3 m0 = make_float3(c00 * idet, c01 * idet, c02 * idet), m1 = make_float3(m0.y, c11 * idet, c12 * idet),
+                         m2 = make_float3(m0.z, m1.z, c22 * idet);
+            // every group joins its sums as soon as it exists (the live floats of a pair stay few: three pairs are in flight at knn > 1)
+            const double dw = w;
+            acc[15] += dw * m0.x; acc[16] += dw * m0.y; acc[17] += dw * m0.z; acc[18] += dw * m1.y; acc[19] += dw * m1.z; acc[20] += dw * m2.z;
+            const float dx = p.x - q.x, dy = p.y - q.y, dz = p.z - q.z;
+            const float3 md = make_float3(m0.x * dx + m0.y * dy + m0.z * dz, m1.x * dx + m1.y * dy + m1.z * dz, m2.x * dx + m2.y * dy + m2.z * dz);
+            const float3 pmd = cross3(p, md);
+            acc[21] -= dw * pmd.x; acc[22] -= dw * pmd.y; acc[23] -= dw * pmd.z; acc[24] -= dw * md.x; acc[25] -= dw * md.y; acc[26] -= dw * md.z;
+            // P M with P = [p]x: column j is p x (column j of M); row i of P M P^T is p x (row i of P M)
+            const float3 k0 = cross3(p, m0), k1 = cross3(p, m1), k2 = cross3(p, m2);
+            const float3 pm0 = make_float3(k0.x, k1.x, k2.x), pm1 = make_float3(k0.y, k1.y, k2.y), pm2 = make_float3(k0.z, k1.z, k2.z);
+            acc[3] += dw * pm0.x; acc[4] += dw * pm0.y; acc[5] += dw * pm0.z;
+            acc[8] += dw * pm1.x; acc[9] += dw * pm1.y; acc[10] += dw * pm1.z;
+            acc[12] += dw * pm2.x; acc[13] += dw * pm2.y; acc[14] += dw * pm2.z;
+            const float3 r0 = cross3(p, pm0), r1 = cross3(p, pm1), r2 = cross3(p, pm2);
+            acc[0] += dw * r0.x; acc[1] += dw * r0.y; acc[2] += dw * r0.z; acc[6] += dw * r1.y; acc[7] += dw * r1.z; acc[11] += dw * r2.z;
         }
     };
 #pragma unroll
-    for (int u = 0; u < PF; ++u) pair(e_first + u * estep, pd2[u], ps[u], pr[u], pq[u], pn[u], true);
-    for (int64_t e = e_first + PF * estep; e < e_end; e += estep)
-        pair(e, d2a[e], sidx[e], reading[(int)(e / lc.k)], match_pt ? match_pt[e] : make_float4(0.f, 0.f, 0.f, 0.f),
-             make_float4(0.f, 0.f, 0.f, 0.f), false);
+    for (int u = 0; u < PF; ++u) pair(e_first + u * estep, pd2[u], ps[u], pr[u], pq[u], pn[u], true, prn[u], GICP ? po[u] : 0);
+    if constexpr (GICP) {
+        for (int64_t e = e_first + PF * estep; e < e_end; e += estep) { // (past a full grid: the four gathers of a pair requested together)
+            const float d2 = d2a[e];
+            const int s = sidx[e], qi = (int)(e / lc.k), oi = qindex ? qindex[qi] : qi;
+            if (s < 0) continue; // (no match: d2 is +inf)
+            const float4 r = reading[qi], q = match_pt ? match_pt[e] : (pnm ? pnm[2 * (size_t)s] : map[s]);
+            const float4 nq = ld_normal(pnm ? pnm + 2 * (size_t)s + 1 : normals + s), rn = ld_normal(read_normals + oi);
+            pair(e, d2, s, r, q, nq, true, rn, oi);
+        }
+    } else {
+        for (int64_t e = e_first + PF * estep; e < e_end; e += estep)
+            pair(e, d2a[e], sidx[e], reading[(int)(e / lc.k)], match_pt ? match_pt[e] : make_float4(0.f, 0.f, 0.f, 0.f),
+                 make_float4(0.f, 0.f, 0.f, 0.f), false, make_float4(0.f, 0.f, 0.f, 0.f), 0);
+    }
     // ---- workgroup reduction: wave64 shuffles, then LDS across the 4 waves ----
     // Transposed butterfly: at the step with partner lane ^ m every lane hands over the half of its
     // values the partner keeps, so 32 values x 64 lanes fold with 16+8+4+2+1+1 = 32 exchanges instead
@@ -563,7 +639,9 @@ LoopCfg make_loop_cfg(const icpmi_ctx* c, int fixed_iterations)
         lc.ring_max = need < RING_CAP ? need : RING_CAP;
     } else lc.ring_max = 6;
     if (lc.ring_max < 1) lc.ring_max = 1;
-    lc.minimizer = cfg.minimizer;
+    // plane-to-plane fills the point-to-plane slots of the sums: every kernel behind the pair sums sees a point-to-plane chain
+    const bool gicp = cfg.minimizer == ICPMI_MIN_PLANE_TO_PLANE;
+    lc.minimizer = gicp ? ICPMI_MIN_POINT_TO_PLANE : cfg.minimizer;
     lc.n_out = cfg.n_outlier;
     for (int f = 0; f < cfg.n_outlier && f < ICPMI_MAX_OUTLIER; ++f) {
         lc.out_type[f] = cfg.outlier[f].type;
@@ -573,7 +651,7 @@ LoopCfg make_loop_cfg(const icpmi_ctx* c, int fixed_iterations)
         lc.out_param3[f] = cfg.outlier[f].param3;
         if (lc.out_type[f] == ICPMI_OUT_GENERICDESCRIPTOR || lc.out_type[f] == ICPMI_OUT_ROBUST) lc.ext = 1;
     }
-    lc.force_4dof = cfg.force_4dof != 0 && cfg.minimizer == ICPMI_MIN_POINT_TO_PLANE;
+    lc.force_4dof = cfg.force_4dof != 0 && lc.minimizer == ICPMI_MIN_POINT_TO_PLANE;
     lc.is_2d = cfg.is_2d != 0;
     lc.force_2d = (cfg.force_2d != 0 || cfg.is_2d != 0) && cfg.minimizer == ICPMI_MIN_POINT_TO_PLANE;
     if (lc.force_2d) lc.ext = 1;
@@ -592,6 +670,7 @@ LoopCfg make_loop_cfg(const icpmi_ctx* c, int fixed_iterations)
         lc.degen_thr = fabsf(cfg.degeneracy_threshold);
         lc.degen_blk = c->d_degen.get();
     }
+    if (gicp) lc.degen_thr = c->plane_eps; // (degen stays 0: validate_config rejects the combination; common.h: plane_to_plane_eps)
     return lc;
 }
 
@@ -1012,7 +1091,7 @@ static void launch_accumulate_ext(icpmi_ctx* c, const LoopCfg& lc, int nb, int s
     const int is_med = slot >= 0 && lc.out_type[slot] == ICPMI_OUT_MEDIANDIST;
     const float factor = slot >= 0 ? lc.out_param[slot] : 0.f;
     // k > 1, point-to-plane: matched point and its normal side by side (map_build.hip: pn_kernel)
-    const float4* pnm = (lc.k > 1 && MIN == ICPMI_MIN_POINT_TO_PLANE && c->has_normals && c->d_map_pn) ? c->d_map_pn.get() : nullptr;
+    const float4* pnm = (lc.k > 1 && (MIN == ICPMI_MIN_POINT_TO_PLANE || MIN == ICPMI_MIN_PLANE_TO_PLANE) && c->has_normals && c->d_map_pn) ? c->d_map_pn.get() : nullptr;
     if (lc.k > 1)
         hipLaunchKernelGGL((accumulate_kernel<MIN, FUSED, EXT, 1024>), dim3(nb, ba.nscan), dim3(1024), 0, c->stream, v.reading, ba, acc_cap(), lc, c->d_state,
                            v.map, v.ref_normals, v.read_normals, v.sidx, v.d2, c->d_selhist, slot, is_med, factor, v.match_pt, v.qindex, v.ref_scalar, pnm);
@@ -1032,7 +1111,10 @@ static void enqueue_accumulate_solve(icpmi_ctx* c, int64_t n, const LoopCfg& lc,
     // (r1: letting the last pair-sum workgroup solve -- ticket + device fences -- measured +3.5 us per
     // iteration against this separate 1-workgroup launch, and dragged the solver's registers and scratch
     // into the pair-sum kernel: removed.)
-    if (lc.minimizer == ICPMI_MIN_POINT_TO_PLANE) {
+    if (plane_to_plane_eps(lc) > 0.f) { // (its own instantiation of the pair sums; the solve below reads lc.minimizer: point-to-plane)
+        if (fused) launch_accumulate<ICPMI_MIN_PLANE_TO_PLANE, true>(c, lc, nb, slot, ba, nn.out_sorted);
+        else launch_accumulate<ICPMI_MIN_PLANE_TO_PLANE, false>(c, lc, nb, slot, ba, nn.out_sorted);
+    } else if (lc.minimizer == ICPMI_MIN_POINT_TO_PLANE) {
         if (fused) launch_accumulate<ICPMI_MIN_POINT_TO_PLANE, true>(c, lc, nb, slot, ba, nn.out_sorted);
         else launch_accumulate<ICPMI_MIN_POINT_TO_PLANE, false>(c, lc, nb, slot, ba, nn.out_sorted);
     } else if (lc.minimizer == ICPMI_MIN_POINT_TO_POINT) {
@@ -1599,6 +1681,17 @@ icpmi_status loop_single_step(icpmi_ctx* c, int64_t n, const LoopCfg& lc, const 
     if (T_step) memcpy(T_step, hT, sizeof hT);
     if (sums) memcpy(sums, hS, sizeof hS);
     c->degen_ready = l1.degen != 0;
+    return ICPMI_OK;
+}
+
+icpmi_status loop_upload_read_normals(icpmi_ctx* c, const float* normals3, int64_t n)
+{
+    float* d_n3 = scratch_get<float>(c, 9, (size_t)3 * n + 3);
+    if (!d_n3 || c->d_read_normals.ensure(c, (size_t)n + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
+    HIP_TRY(c, hipMemcpyAsync(d_n3, normals3, (size_t)3 * n * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(pad_normals_kernel, dim3((int)((n + 255) / 256)), dim3(256), 0, c->stream, (const float*)d_n3, n, c->d_read_normals);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(c->stream)); // (pageable host memory: the caller's buffer is free on return)
     return ICPMI_OK;
 }
 

@@ -143,10 +143,45 @@ void parseMatcher(const yaml::Node& matcher, icpmi_config& cfg, std::string& max
     if (e.second["maxDist"]) cfg.max_dist = e.second["maxDist"].as<float>();
 }
 
+// the `errorMinimizer:` entry of an ICP chain into the configuration; planeEpsilon = PlaneToPlaneErrorMinimizer.epsilon (left alone by the others)
+void parseErrorMinimizer(const yaml::Node& node, icpmi_config& cfg, float& planeEpsilon)
+{
+    auto e = singleEntry(node, "errorMinimizer");
+    if (e.first == "IdentityErrorMinimizer") cfg.minimizer = ICPMI_MIN_IDENTITY;
+    else if (e.first == "PointToPointErrorMinimizer") cfg.minimizer = ICPMI_MIN_POINT_TO_POINT;
+    else if (e.first == "PointToPlaneErrorMinimizer" || e.first == "PointToPlaneWithCovErrorMinimizer") {
+        cfg.minimizer = ICPMI_MIN_POINT_TO_PLANE;
+        if (e.first == "PointToPlaneWithCovErrorMinimizer") { // the same registration, plus getCovariance() (icpmi_get_covariance)
+            requireKnown(e.second, {"sensorStdDev", "force2D", "force4DOF", "degeneracyThreshold", "degeneracyAction"}, e.first);
+            cfg.covariance = 1;
+            if (e.second["sensorStdDev"]) cfg.sensor_std_dev = e.second["sensorStdDev"].as<float>();
+        } else requireKnown(e.second, {"force2D", "force4DOF", "degeneracyThreshold", "degeneracyAction"}, e.first); // (a misspelt key must not leave the option off in silence)
+        cfg.force_4dof = (e.second["force4DOF"] && e.second["force4DOF"].as<int>() != 0) ? 1 : 0;
+        cfg.force_2d = (e.second["force2D"] && e.second["force2D"].as<int>() != 0) ? 1 : 0;
+        if (cfg.force_4dof && cfg.force_2d) throw InvalidParameter("PointToPlaneErrorMinimizer: force2D and force4DOF exclude each other");
+        // degeneracy-aware solve (not libpointmatcher's): degeneracyThreshold >= 0 (0: off), degeneracyAction constrain | report
+        const float thr = e.second["degeneracyThreshold"] ? e.second["degeneracyThreshold"].as<float>() : 0.f;
+        const std::string action = e.second["degeneracyAction"] ? e.second["degeneracyAction"].as<std::string>() : std::string("constrain");
+        if (!(thr >= 0.f) || !std::isfinite(thr)) throw InvalidParameter(e.first + ": degeneracyThreshold must be finite and >= 0");
+        if (action != "constrain" && action != "report") throw InvalidParameter(e.first + ": degeneracyAction must be constrain or report");
+        if (thr > 0.f && cfg.force_2d) throw InvalidParameter(e.first + ": degeneracyThreshold and force2D exclude each other");
+        cfg.degeneracy_threshold = action == "constrain" ? thr : -thr;
+    } else if (e.first == "PlaneToPlaneErrorMinimizer") {
+        // generalized ICP from the normals of both clouds (not libpointmatcher's; include/icpmi.h: ICPMI_MIN_PLANE_TO_PLANE)
+        requireKnown(e.second, {"epsilon", "force4DOF"}, e.first);
+        cfg.minimizer = ICPMI_MIN_PLANE_TO_PLANE;
+        cfg.force_4dof = (e.second["force4DOF"] && e.second["force4DOF"].as<int>() != 0) ? 1 : 0;
+        if (e.second["epsilon"]) planeEpsilon = e.second["epsilon"].as<float>();
+        if (!std::isfinite(planeEpsilon) || !(planeEpsilon > 0.f) || planeEpsilon > 1.f)
+            throw InvalidParameter(e.first + ": epsilon must be finite and in (0, 1]");
+    } else throw InvalidParameter("unknown error minimizer " + e.first);
+}
+
 void GpuICPSequence::loadFromYamlNode(const yaml::Node& icp)
 {
     const int dev = cfg.device;
     icpmi_config_default(&cfg);
+    planeEpsilon = 1e-3f; // PlaneToPlaneErrorMinimizer.epsilon
     cfg.device = dev;
     cfg.is_2d = planar ? 1 : 0;
     if (icp.IsMap())
@@ -233,29 +268,7 @@ void GpuICPSequence::loadFromYamlNode(const yaml::Node& icp)
             if (cfg.n_outlier >= 8) throw InvalidParameter("at most 8 outlier filters");
             cfg.outlier[cfg.n_outlier++] = o;
         }
-    if (icp["errorMinimizer"]) {
-        auto e = singleEntry(icp["errorMinimizer"], "errorMinimizer");
-        if (e.first == "IdentityErrorMinimizer") cfg.minimizer = ICPMI_MIN_IDENTITY;
-        else if (e.first == "PointToPointErrorMinimizer") cfg.minimizer = ICPMI_MIN_POINT_TO_POINT;
-        else if (e.first == "PointToPlaneErrorMinimizer" || e.first == "PointToPlaneWithCovErrorMinimizer") {
-            cfg.minimizer = ICPMI_MIN_POINT_TO_PLANE;
-            if (e.first == "PointToPlaneWithCovErrorMinimizer") { // the same registration, plus getCovariance() (icpmi_get_covariance)
-                requireKnown(e.second, {"sensorStdDev", "force2D", "force4DOF", "degeneracyThreshold", "degeneracyAction"}, e.first);
-                cfg.covariance = 1;
-                if (e.second["sensorStdDev"]) cfg.sensor_std_dev = e.second["sensorStdDev"].as<float>();
-            } else requireKnown(e.second, {"force2D", "force4DOF", "degeneracyThreshold", "degeneracyAction"}, e.first); // (a misspelt key must not leave the option off in silence)
-            cfg.force_4dof = (e.second["force4DOF"] && e.second["force4DOF"].as<int>() != 0) ? 1 : 0;
-            cfg.force_2d = (e.second["force2D"] && e.second["force2D"].as<int>() != 0) ? 1 : 0;
-            if (cfg.force_4dof && cfg.force_2d) throw InvalidParameter("PointToPlaneErrorMinimizer: force2D and force4DOF exclude each other");
-            // degeneracy-aware solve (not libpointmatcher's): degeneracyThreshold >= 0 (0: off), degeneracyAction constrain | report
-            const float thr = e.second["degeneracyThreshold"] ? e.second["degeneracyThreshold"].as<float>() : 0.f;
-            const std::string action = e.second["degeneracyAction"] ? e.second["degeneracyAction"].as<std::string>() : std::string("constrain");
-            if (!(thr >= 0.f) || !std::isfinite(thr)) throw InvalidParameter(e.first + ": degeneracyThreshold must be finite and >= 0");
-            if (action != "constrain" && action != "report") throw InvalidParameter(e.first + ": degeneracyAction must be constrain or report");
-            if (thr > 0.f && cfg.force_2d) throw InvalidParameter(e.first + ": degeneracyThreshold and force2D exclude each other");
-            cfg.degeneracy_threshold = action == "constrain" ? thr : -thr;
-        } else throw InvalidParameter("unknown error minimizer " + e.first);
-    }
+    if (icp["errorMinimizer"]) parseErrorMinimizer(icp["errorMinimizer"], cfg, planeEpsilon);
     if (icp["transformationCheckers"].IsSequence())
         for (const auto& item : icp["transformationCheckers"].seq) {
             auto e = singleEntry(item, "transformation checker");
@@ -276,6 +289,7 @@ void GpuICPSequence::loadFromYamlNode(const yaml::Node& icp)
             } else throw InvalidParameter("unknown transformation checker " + e.first);
         }
     recreate();
+    check(h, icpmi_set_plane_epsilon(h, planeEpsilon));
     auto chain = [&](const char* key) -> std::shared_ptr<DataPointsFilters> {
         if (!icp[key] || !icp[key].IsSequence() || icp[key].seq.empty()) return nullptr;
         return std::make_shared<DataPointsFilters>(icp[key], h);
@@ -444,7 +458,7 @@ bool GpuICPSequence::chainNeedsReadingNormals() const
 {
     for (int f = 0; f < cfg.n_outlier; ++f)
         if (cfg.outlier[f].type == ICPMI_OUT_SURFACENORMAL) return true;
-    return false;
+    return cfg.minimizer == ICPMI_MIN_PLANE_TO_PLANE;
 }
 
 DataPoints GpuICPSequence::downloadMap() const
@@ -600,7 +614,7 @@ PoseScores GpuICPSequence::residuals(const DataPoints& readingIn, const std::vec
 void GpuICPSequence::requireBareReadingChain(const char* who) const
 {
     if (chainNeedsReadingNormals())
-        throw InvalidParameter(std::string(who) + ": the chain's SurfaceNormalOutlierFilter reads the reading's normals, which the multistart registration does not carry");
+        throw InvalidParameter(std::string(who) + ": the chain (SurfaceNormalOutlierFilter, PlaneToPlaneErrorMinimizer) reads the reading's normals, which the multistart registration does not carry");
     if (readsReadingDescriptor())
         throw InvalidParameter(std::string(who) + ": the chain reads a descriptor row of the reading (" +
                                (!genericReadDescName.empty() ? genericReadDescName : maxDistFieldName) + "), which the multistart registration does not carry");

@@ -288,7 +288,7 @@ bool Map::residentPlan(const DataPoints& input, const DataPointsFilters& postFil
         if (op.type == ICPMI_MOP_MAX_DENSITY && !prog.computesDensities) return false;
     }
     // a point-to-plane chain needs normals on every map point: only with the SurfaceNormal post filter
-    if (icp.config().minimizer == ICPMI_MIN_POINT_TO_PLANE && !prog.computesNormals) return false;
+    if ((icp.config().minimizer == ICPMI_MIN_POINT_TO_PLANE || icp.config().minimizer == ICPMI_MIN_PLANE_TO_PLANE) && !prog.computesNormals) return false;
     const bool first = isLocalPointCloudEmpty();
     if (first && icp.hasMap()) return false; // the ICP map is not the local cloud (cells just unloaded)
     const bool inputNormals = input.descriptorExists("normals") && input.getDescriptorByName("normals").span == 3;

@@ -145,6 +145,25 @@ int nim_test_parse_matcher(const char* yaml_matcher, int* knn, float* epsilon, f
     }
 }
 
+// parseErrorMinimizer on the `errorMinimizer:` entry of the ICP chain given as YAML text (no GPU, no handle): the fields it sets and PlaneToPlaneErrorMinimizer's
+// epsilon (0.001 unless the entry names one).  Returns 0, or 1 with the exception's text in err.
+int nim_test_parse_error_minimizer(const char* yaml_icp, int* minimizer, int* force_4dof, int* force_2d, int* covariance, float* degeneracy_threshold,
+                                   float* plane_epsilon, char* err, int err_cap)
+{
+    try {
+        icpmi_config cfg;
+        icpmi_config_default(&cfg);
+        float eps = 1e-3f;
+        nim::parseErrorMinimizer(nim::yaml::Load(yaml_icp)["errorMinimizer"], cfg, eps);
+        *minimizer = cfg.minimizer; *force_4dof = cfg.force_4dof; *force_2d = cfg.force_2d; *covariance = cfg.covariance;
+        *degeneracy_threshold = cfg.degeneracy_threshold; *plane_epsilon = eps;
+        return 0;
+    } catch (const std::exception& e) {
+        if (err && err_cap > 0) { std::strncpy(err, e.what(), (size_t)err_cap - 1); err[err_cap - 1] = 0; }
+        return 1;
+    }
+}
+
 // nim::deskewSweep (what Mapper::deskew runs on its own handle) on handle h.  The cloud: in4 + n_desc float descriptors (names / spans /
 // data, each span x n column-major) + one optional int64 row group (time_name / times, one row; may be NULL).  The motion: n_poses
 // stamps (ns) and poses (7 doubles each); stamp_ns the scan's stamp.  Back come out4, every descriptor in nim_test_filter_chain_descs'

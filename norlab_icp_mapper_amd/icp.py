@@ -61,7 +61,17 @@ _MINIMIZERS = {
     "IdentityErrorMinimizer": _capi.MIN_IDENTITY,
     "PointToPointErrorMinimizer": _capi.MIN_POINT_TO_POINT,
     "PointToPlaneErrorMinimizer": _capi.MIN_POINT_TO_PLANE,
+    "PlaneToPlaneErrorMinimizer": _capi.MIN_PLANE_TO_PLANE,
 }
+PLANE_EPSILON_DEFAULT = 1e-3
+
+
+def _check_plane_epsilon(eps):
+    eps = float(eps)
+    if not (math.isfinite(eps) and 0.0 < eps <= 1.0):
+        raise InvalidParameter("PlaneToPlaneErrorMinimizer: epsilon must be finite and in (0, 1]")
+    return eps
+
 
 
 def _f32c(a, cols):
@@ -209,6 +219,13 @@ def config_from_yaml_chain(chain, **engine):
         for key in p:  # (a misspelt degeneracyThreshold must not leave the option off in silence)
             if key not in ("force2D", "force4DOF", "degeneracyThreshold", "degeneracyAction"):
                 raise InvalidParameter(f"{name}: unknown parameter {key}")
+    plane_epsilon = None
+    if name == "PlaneToPlaneErrorMinimizer":
+        # generalized ICP from the normals of both clouds (not libpointmatcher's; include/icpmi.h: ICPMI_MIN_PLANE_TO_PLANE)
+        for key in p:
+            if key not in ("epsilon", "force4DOF"):
+                raise InvalidParameter(f"{name}: unknown parameter {key}")
+        plane_epsilon = _check_plane_epsilon(p.get("epsilon", PLANE_EPSILON_DEFAULT))
     if name not in _MINIMIZERS:
         raise InvalidParameter(f"unknown error minimizer {name}")
     if name == "PointToPlaneErrorMinimizer":
@@ -223,7 +240,7 @@ def config_from_yaml_chain(chain, **engine):
             raise InvalidParameter(f"{name}: degeneracyThreshold and force2D exclude each other")
         kw["degeneracy_threshold"] = thr if action == "constrain" else -thr
     kw["minimizer"] = _MINIMIZERS[name]
-    kw["force_4dof"] = 1 if (name == "PointToPlaneErrorMinimizer" and int(p.get("force4DOF", 0))) else 0
+    kw["force_4dof"] = 1 if (name in ("PointToPlaneErrorMinimizer", "PlaneToPlaneErrorMinimizer") and int(p.get("force4DOF", 0))) else 0
     kw["force_2d"] = 1 if (name == "PointToPlaneErrorMinimizer" and int(p.get("force2D", 0))) else 0
     if kw["force_4dof"] and kw["force_2d"]:
         raise InvalidParameter("PointToPlaneErrorMinimizer: force2D and force4DOF exclude each other")
@@ -250,6 +267,8 @@ def config_from_yaml_chain(chain, **engine):
     cfg = default_config(**kw)
     if max_dist_field is not None:
         cfg.max_dist_field = max_dist_field  # (a Python attribute next to the C fields: the descriptor name is the host's business)
+    if plane_epsilon is not None:
+        cfg.plane_epsilon = plane_epsilon  # (likewise: icpmi_config has no word left; ICPSequence hands it to icpmi_set_plane_epsilon)
     return cfg
 
 
@@ -394,9 +413,14 @@ class _ErrorMinimizerView:
 class ICPSequence:
     """``PM::ICPSequence`` backed by one icpmi handle (one GPU, one stream)."""
 
-    def __init__(self, cfg=None, **kw):
+    def __init__(self, cfg=None, plane_epsilon=None, **kw):
+        """plane_epsilon: epsilon of PlaneToPlaneErrorMinimizer (icpmi_set_plane_epsilon; default: the chain's, else 1e-3)"""
         self._lib = _capi.load()
         self.cfg = cfg if cfg is not None else default_config(**kw)
+        if plane_epsilon is None:
+            plane_epsilon = getattr(self.cfg, "plane_epsilon", None)
+        if plane_epsilon is not None:
+            plane_epsilon = _check_plane_epsilon(plane_epsilon)
         h = C.c_void_p()
         st = self._lib.icpmi_create(C.byref(self.cfg), C.byref(h))
         if st != _capi.ICPMI_OK:
@@ -406,6 +430,8 @@ class ICPSequence:
         self.stats = _capi.Stats()
         self.errorMinimizer = _ErrorMinimizerView(self)
         self._last_n = 0
+        if plane_epsilon is not None:
+            self.setPlaneEpsilon(plane_epsilon)
 
     @classmethod
     def loadFromYaml(cls, chain, **engine):
@@ -416,6 +442,15 @@ class ICPSequence:
         new = cfg if cfg is not None else default_config(device=self.cfg.device, **kw)
         self._check(self._lib.icpmi_set_config(self._h, C.byref(new)))
         self.cfg = new
+
+    def setPlaneEpsilon(self, eps):
+        """icpmi_set_plane_epsilon: handle state (setConfig leaves it); the next registration runs with it"""
+        self._check(self._lib.icpmi_set_plane_epsilon(self._h, float(eps)))
+
+    def getPlaneEpsilon(self):
+        out = C.c_float(0)
+        self._check(self._lib.icpmi_get_plane_epsilon(self._h, C.byref(out)))
+        return float(out.value)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -737,7 +772,8 @@ class ICPSequence:
         self._check(self._lib.icpmi_outlier_weights(self._h, d2.ctypes.data, idp, k, n, rnp, w.ctypes.data, C.byref(lim)))
         return w, float(lim.value)
 
-    def minimizeStep(self, reading_centred, T_iter=None):
+    def minimizeStep(self, reading_centred, T_iter=None, read_normals=None):
+        """icpmi_minimize_step; read_normals (N, 3): icpmi_minimize_step_normals (PlaneToPlaneErrorMinimizer, SurfaceNormalOutlierFilter)"""
         r = _f32c(reading_centred, 4)
         T = (C.c_float * 16)()
         sums = (C.c_double * 32)()
@@ -745,7 +781,13 @@ class ICPSequence:
         if T_iter is not None:
             Tc = _T_to_c(T_iter)
             tptr = Tc.ctypes.data
-        self._check(self._lib.icpmi_minimize_step(self._h, r.ctypes.data, r.shape[0], tptr, T, sums, C.byref(self.stats)))
+        if read_normals is not None:
+            rn = _f32c(read_normals, 3)
+            if rn.shape[0] != r.shape[0]:
+                raise InvalidParameter("normals / cloud size mismatch")
+            self._check(self._lib.icpmi_minimize_step_normals(self._h, r.ctypes.data, r.shape[0], rn.ctypes.data, tptr, T, sums, C.byref(self.stats)))
+        else:
+            self._check(self._lib.icpmi_minimize_step(self._h, r.ctypes.data, r.shape[0], tptr, T, sums, C.byref(self.stats)))
         return _T_from_c(T[:]), np.array(sums[:])
 
     def surfaceNormals(self, cloud, knn=5, with_densities=False, with_matched_ids=False, with_mean_dist=False):
