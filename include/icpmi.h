@@ -70,7 +70,9 @@ typedef enum {
      * icpmi_register_multistart* and icpmi_minimize_step cannot carry them: ICPMI_ERR_UNSUPPORTED.  Rejected with ICPMI_ERR_INVALID_ARG:
      * force_2d / is_2d, covariance = 1 (Censi's form is derived for the scalar residual), degeneracy_threshold != 0 (mu = lambda / sum w
      * assumes unit-information pairs; M's scale is 1 / (2 eps)).  icpmi_residual_error* on such a handle reports the point-to-plane
-     * residual |(p - q) . n_q| (ICPMI_RES_CHAIN = ICPMI_RES_POINT_TO_PLANE); the sensor-noise overlap is the point-to-plane count. */
+     * residual |(p - q) . n_q| (ICPMI_RES_CHAIN = ICPMI_RES_POINT_TO_PLANE); the sensor-noise overlap is the point-to-plane count.
+     * This is the pair model ICPMI_PLANE_MODEL_GICP, the default; icpmi_set_plane_pair_model puts the symmetric point-to-plane model
+     * (ICPMI_PLANE_MODEL_SYMMETRIC, below) on the same path. */
     ICPMI_MIN_PLANE_TO_PLANE = 3
 } icpmi_minimizer;
 
@@ -320,6 +322,28 @@ icpmi_status icpmi_minimize_step_normals(icpmi_handle h, const float* reading4, 
  * next registration runs with the new value.  eps = 1 makes every covariance I: A = 0.5 sum w J^T J. */
 icpmi_status icpmi_set_plane_epsilon(icpmi_handle h, float eps);
 icpmi_status icpmi_get_plane_epsilon(icpmi_handle h, float* eps);
+
+/* The pair model that minimizer == ICPMI_MIN_PLANE_TO_PLANE runs.  State of the handle next to epsilon: icpmi_set_config leaves it, a cached
+ * loop graph is valid for one model only, anything but the two values is ICPMI_ERR_INVALID_ARG and the state stays.
+ *
+ * ICPMI_PLANE_MODEL_SYMMETRIC -- SymmetricPointToPlaneErrorMinimizer{force4DOF}: the symmetric point-to-plane objective of S. Rusinkiewicz,
+ * "A Symmetric Objective Function for ICP", ACM Trans. Graph. 38(4) (SIGGRAPH 2019), in its rotated-normals form: the normals are frozen per
+ * iteration and the step is the ordinary linear one (no split rotation).  Not libpointmatcher's.  Per pair with weight w != 0: p = T_iter x,
+ * q its match, u_q = n_q / |n_q|, u_p = R n_x / |R n_x| (R of T_iter; a zero or non-finite normal: u = 0), c = u_q . u_p, and the pair normal
+ *     n_s = ( |c| u_q + c u_p ) / 2            (u_p = 0: n_s = u_q, which is point-to-plane; u_q = 0: n_s = u_p; both 0: the pair only counts)
+ * then the point-to-plane sums with n_s for the normal: F = [p x n_s; n_s], A += w F F^T, b -= w F ((p - q) . n_s); per-pair terms in float,
+ * the weight's product and the sums in double.  n_s is continuous in both normals (perpendicular ones weigh the pair down to a quarter),
+ * the sign of either normal cancels bit for bit (unoriented normals are fine), u_q = u_p gives point-to-plane with the unit map normal, and
+ * with c ~ 1 the residual is (p - q) . (n_q + n_p) / 2, which vanishes for two points of a surface of constant curvature.
+ * Everything else is ICPMI_MIN_PLANE_TO_PLANE's: the slots of the sums, the solve with force4DOF, the entry points that serve it and those that
+ * refuse it (their message names this minimiser), the rejected options (planar mode, covariance, degeneracy_threshold), the point-to-plane
+ * residual of icpmi_residual_error*.  plane epsilon is ignored by this model, and kept. */
+typedef enum {
+    ICPMI_PLANE_MODEL_GICP = 0,     /* PlaneToPlaneErrorMinimizer: generalized ICP (the default) */
+    ICPMI_PLANE_MODEL_SYMMETRIC = 1 /* SymmetricPointToPlaneErrorMinimizer                        */
+} icpmi_plane_pair_model;
+icpmi_status icpmi_set_plane_pair_model(icpmi_handle h, int32_t model);
+icpmi_status icpmi_get_plane_pair_model(icpmi_handle h, int32_t* model);
 
 /* ---- map-side operators on the path ---- */
 

@@ -15,6 +15,7 @@ ICPMI_OK = 0
 ERR_INVALID_ARG, ERR_HIP, ERR_NO_POINT_TO_MINIMIZE, ERR_NO_OUTLIER_TO_FILTER = 1, 2, 3, 4
 ERR_BOUND, ERR_NAN, ERR_MISSING_NORMALS, ERR_UNSUPPORTED = 5, 6, 7, 8
 MIN_IDENTITY, MIN_POINT_TO_POINT, MIN_POINT_TO_PLANE, MIN_PLANE_TO_PLANE = 0, 1, 2, 3
+PLANE_MODEL_GICP, PLANE_MODEL_SYMMETRIC = 0, 1  # the pair model of MIN_PLANE_TO_PLANE (icpmi_set_plane_pair_model)
 OUT_MAXDIST, OUT_MINDIST, OUT_MEDIANDIST, OUT_TRIMMEDDIST, OUT_SURFACENORMAL = 1, 2, 3, 4, 5
 OUT_GENERICDESCRIPTOR, OUT_ROBUST, OUT_VARTRIMMEDDIST = 6, 7, 8
 GEN_SOURCE_READING, GEN_SOFT, GEN_LARGER = 1, 2, 4
@@ -188,6 +189,8 @@ SYMBOLS = [
     ("icpmi_minimize_step_normals", C.c_int, [_P, _P, C.c_int64, _P, _P, _F, C.POINTER(C.c_double), C.POINTER(Stats)]),
     ("icpmi_set_plane_epsilon", C.c_int, [_P, C.c_float]),
     ("icpmi_get_plane_epsilon", C.c_int, [_P, _F]),
+    ("icpmi_set_plane_pair_model", C.c_int, [_P, C.c_int32]),
+    ("icpmi_get_plane_pair_model", C.c_int, [_P, C.POINTER(C.c_int32)]),
     ("icpmi_surface_normals", C.c_int, [_P, _P, C.c_int64, C.c_int32, _P]),
     ("icpmi_surface_normals_ex", C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, _P]),
     ("icpmi_surface_normals_ex2", C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, _P, _P, _P]),

@@ -627,11 +627,17 @@ static icpmi_status chain_setup(icpmi_handle h, int64_t n, const float* d_n3, in
     return ICPMI_OK;
 }
 
-// the entry points that cannot carry the reading's normals do not serve PlaneToPlaneErrorMinimizer
+// the name of the minimiser an ICPMI_MIN_PLANE_TO_PLANE handle runs, as the user configured it (icpmi_set_plane_pair_model)
+static const char* plane_minimizer_name(const icpmi_ctx* h)
+{
+    return h->plane_model == ICPMI_PLANE_MODEL_SYMMETRIC ? "SymmetricPointToPlaneErrorMinimizer" : "PlaneToPlaneErrorMinimizer";
+}
+
+// the entry points that cannot carry the reading's normals do not serve PlaneToPlaneErrorMinimizer (either pair model)
 static icpmi_status reject_plane_to_plane(icpmi_ctx* h, const char* who)
 {
     if (h->cfg.minimizer != ICPMI_MIN_PLANE_TO_PLANE) return ICPMI_OK;
-    h->last_error = std::string(who) + ": PlaneToPlaneErrorMinimizer needs the reading's normals, which this entry point cannot carry "
+    h->last_error = std::string(who) + ": " + plane_minimizer_name(h) + " needs the reading's normals, which this entry point cannot carry "
                     "(icpmi_register*, icpmi_minimize_step_normals take them)";
     return ICPMI_ERR_UNSUPPORTED;
 }
@@ -657,7 +663,7 @@ static icpmi_status register_impl(icpmi_handle h, const float* d_scan4, int64_t 
     }
     const bool gicp = h->cfg.minimizer == ICPMI_MIN_PLANE_TO_PLANE;
     if (gicp && (!h->has_normals || (n > 0 && !d_n3))) {
-        h->last_error = "InvalidField: PlaneToPlaneErrorMinimizer needs the descriptor 'normals' on both reading and map";
+        h->last_error = std::string("InvalidField: ") + plane_minimizer_name(h) + " needs the descriptor 'normals' on both reading and map";
         return ICPMI_ERR_MISSING_NORMALS;
     }
     { const icpmi_status ds = ensure_degen_block(h); if (ds != ICPMI_OK) return ds; }
@@ -1168,7 +1174,7 @@ static icpmi_status minimize_step_impl(icpmi_handle h, const float* reading4, in
         return ICPMI_ERR_MISSING_NORMALS;
     }
     if (h->cfg.minimizer == ICPMI_MIN_PLANE_TO_PLANE && (!h->has_normals || !read_normals3)) {
-        h->last_error = "InvalidField: PlaneToPlaneErrorMinimizer needs the descriptor 'normals' on both reading and map";
+        h->last_error = std::string("InvalidField: ") + plane_minimizer_name(h) + " needs the descriptor 'normals' on both reading and map";
         return ICPMI_ERR_MISSING_NORMALS;
     }
     if (stats) { memset(stats, 0, sizeof *stats); stats->sensor_noise_overlap = -1.f; }
@@ -1220,6 +1226,24 @@ icpmi_status icpmi_get_plane_epsilon(icpmi_handle h, float* eps)
     CHECK_H(h);
     if (!eps) { h->last_error = "get_plane_epsilon: eps is null"; return ICPMI_ERR_INVALID_ARG; }
     *eps = h->plane_eps;
+    return ICPMI_OK;
+}
+
+icpmi_status icpmi_set_plane_pair_model(icpmi_handle h, int32_t model)
+{
+    CHECK_H(h);
+    if (model != ICPMI_PLANE_MODEL_GICP && model != ICPMI_PLANE_MODEL_SYMMETRIC) {
+        h->last_error = "set_plane_pair_model: model must be ICPMI_PLANE_MODEL_GICP or ICPMI_PLANE_MODEL_SYMMETRIC"; return ICPMI_ERR_INVALID_ARG;
+    }
+    h->plane_model = model; // (no graph to drop: make_loop_cfg puts it into the LoopCfg, which loop_sig hashes)
+    return ICPMI_OK;
+}
+
+icpmi_status icpmi_get_plane_pair_model(icpmi_handle h, int32_t* model)
+{
+    CHECK_H(h);
+    if (!model) { h->last_error = "get_plane_pair_model: model is null"; return ICPMI_ERR_INVALID_ARG; }
+    *model = h->plane_model;
     return ICPMI_OK;
 }
 

@@ -252,6 +252,10 @@ struct LoopCfg {
 // ICPMI_MIN_PLANE_TO_PLANE travels as a point-to-plane chain (its pair sums fill the same slots, the solve is the same) whose degen_thr, free
 // because the degeneracy-aware solve is rejected with it, carries the covariances' epsilon: > 0 picks the plane-to-plane pair sums
 static inline float plane_to_plane_eps(const LoopCfg& lc) { return (lc.minimizer == ICPMI_MIN_POINT_TO_PLANE && lc.degen == 0) ? lc.degen_thr : 0.f; }
+// ... and epsilon lives in (0, 1] (icpmi_set_plane_epsilon), so a value past 1 in that slot names the other pair model of the same path:
+// ICPMI_PLANE_MODEL_SYMMETRIC, which has no epsilon.  The slot is part of the LoopCfg that loop_sig hashes: a model change misses a cached graph.
+#define ICPMI_PLANE_SLOT_SYMMETRIC 2.f
+static inline bool plane_pair_symmetric(const LoopCfg& lc) { return plane_to_plane_eps(lc) > 1.f; }
 // slot of the chain's Trimmed / Median / VarTrimmed filter (the last of them: the one whose limit a call reports), or -1.  Upstream, a
 // chain with one throws "no outlier to filter" on an empty reading where any other throws "no point to minimize".
 static inline int quantile_slot(const LoopCfg& lc)
@@ -761,6 +765,8 @@ struct icpmi_ctx {
     // icpmi_set_plane_epsilon: epsilon of the plane-to-plane minimiser's covariances; handle state (icpmi_set_config leaves it), carried into
     // the kernels -- and into the signature of a cached loop graph -- by make_loop_cfg
     float plane_eps = 1e-3f;
+    // icpmi_set_plane_pair_model: the pair model ICPMI_MIN_PLANE_TO_PLANE runs (ICPMI_PLANE_MODEL_*); handle state like plane_eps, and carried likewise
+    int plane_model = ICPMI_PLANE_MODEL_GICP;
     DevArr<IcpState> d_state;          // ICPMI_MAX_BATCH states (a single registration uses the first)
     IcpState* h_state = nullptr;                               // pinned mirror (ICPMI_MAX_BATCH)
     bool zero_pending = false;                                 // d_state / d_selhist still to be cleared: on the stream the handle really uses, at its first call (zero_state_if_pending)

@@ -244,6 +244,10 @@ __device__ __forceinline__ float4 ld_normal(const float4* __restrict__ p)
 }
 __device__ __forceinline__ float3 cross3(float3 a, float3 b) { return make_float3(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x); }
 
+// the symmetric pair model of the plane-to-plane path (include/icpmi.h: ICPMI_PLANE_MODEL_SYMMETRIC): a tag of this file for accumulate_kernel's
+// MIN, next to the icpmi_minimizer values -- no minimizer of the interface (4 stays unknown there)
+constexpr int PAIR_SYMMETRIC = 16;
+
 template <int MIN, bool FUSED, bool EXT, int BT = 256>
 __global__ __launch_bounds__(BT) void accumulate_kernel(const float4* __restrict__ reading, BatchArgs ba, int acc_cap, LoopCfg lc,
                                                          IcpState* __restrict__ st, const float4* __restrict__ map,
@@ -297,6 +301,8 @@ __global__ __launch_bounds__(BT) void accumulate_kernel(const float4* __restrict
     // (k > 1: 1024-thread workgroups, one per CU, up to 600 k pairs at knn 6 -- three pairs per lane; a third pair walked AFTER the first two
     // is two more dependent round trips, so all three are requested up front)
     constexpr int PF = BT > 256 ? 3 : 2;
+    // the pair models that read the normals of BOTH clouds (plane-to-plane and the symmetric one): same gathers, same two trips
+    constexpr bool BOTH_N = MIN == ICPMI_MIN_PLANE_TO_PLANE || MIN == PAIR_SYMMETRIC;
     unsigned hw = hdr_load(st);
     float pd2[PF]; int ps[PF]; float4 pr[PF], pq[PF];
     int po[PF]; // plane-to-plane: the caller's index of the reading point, whose normal the second trip fetches
@@ -307,8 +313,8 @@ __global__ __launch_bounds__(BT) void accumulate_kernel(const float4* __restrict
         pd2[u] = in ? ld_stream(d2a + e) : INFINITY;
         ps[u] = in ? ld_stream(sidx + e) : -1;
         pr[u] = ld_stream(reading + (in ? (int)(e / lc.k) : 0));
-        if constexpr (MIN == ICPMI_MIN_PLANE_TO_PLANE) po[u] = in ? (qindex ? ld_stream(qindex + (int)(e / lc.k)) : (int)(e / lc.k)) : -1;
-        if constexpr (MIN == ICPMI_MIN_PLANE_TO_PLANE) // (every pair arrives at the sums with all four of its gathers: no dependent load behind them)
+        if constexpr (BOTH_N) po[u] = in ? (qindex ? ld_stream(qindex + (int)(e / lc.k)) : (int)(e / lc.k)) : -1;
+        if constexpr (BOTH_N) // (every pair arrives at the sums with all four of its gathers: no dependent load behind them)
             pq[u] = (match_pt && in) ? ld_stream(match_pt + e) : (ps[u] >= 0 ? (pnm ? pnm[2 * (size_t)ps[u]] : map[ps[u]]) : make_float4(0.f, 0.f, 0.f, 0.f));
         else
             pq[u] = (match_pt && in) ? ld_stream(match_pt + e) : ((pnm && ps[u] >= 0) ? pnm[2 * (size_t)ps[u]] : make_float4(0.f, 0.f, 0.f, 0.f));
@@ -326,12 +332,12 @@ __global__ __launch_bounds__(BT) void accumulate_kernel(const float4* __restrict
     for (int i = 0; i < 16; ++i) T[i] = hv.f(ICPMI_HDR_W(T_iter) + i);
     // second round trip, overlapping the fine-histogram read of the selection scan: the matched normals
     // (plane-to-plane: ... and the reading's own normals, by the caller's index that arrived with the first trip)
-    constexpr bool USES_N = MIN == ICPMI_MIN_POINT_TO_PLANE || MIN == ICPMI_MIN_PLANE_TO_PLANE;
+    constexpr bool USES_N = MIN == ICPMI_MIN_POINT_TO_PLANE || BOTH_N;
     float4 pn[PF], prn[PF];
 #pragma unroll
     for (int u = 0; u < PF; ++u) {
         prn[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-        if constexpr (MIN == ICPMI_MIN_PLANE_TO_PLANE) {
+        if constexpr (BOTH_N) {
             pn[u] = ps[u] >= 0 ? ld_normal(pnm ? pnm + 2 * (size_t)ps[u] + 1 : normals + ps[u]) : make_float4(0.f, 0.f, 0.f, 0.f);
             if (po[u] >= 0) prn[u] = ld_normal(read_normals + po[u]);
         } else {
@@ -360,8 +366,7 @@ __global__ __launch_bounds__(BT) void accumulate_kernel(const float4* __restrict
     for (int i = 0; i < (NVAL > 0 ? NVAL : 1); ++i) acc[i] = 0.0;
     double wsum = 0.0, cnt = 0.0;
     double b2d[3] = {0.0, 0.0, 0.0}; // force2D: b of the 2-D residual (EXT variant only)
-    // plane-to-plane (GICP): the caller hands over everything the pair needs -- q, n_q, the reading's normal and its caller's index okept
-    constexpr bool GICP = MIN == ICPMI_MIN_PLANE_TO_PLANE;
+    // BOTH_N: the caller hands over everything the pair needs -- q, n_q, the reading's normal and its caller's index okept
     auto pair = [&](int64_t e, float d2, int s, float4 r, float4 qkept, float4 nkept, bool have_n, float4 rnkept, int okept) {
         if (d2 == INFINITY) return;
         const int qi = (int)(e / lc.k);
@@ -369,23 +374,23 @@ __global__ __launch_bounds__(BT) void accumulate_kernel(const float4* __restrict
         if (EXT) {
             // the filters that read the pair itself: original index of the matched point (its .w), point-to-plane residual
             const float3 pe = xf_point(T, r.x, r.y, r.z, r.w);
-            const float4 qe = (GICP || match_pt || (pnm && have_n)) ? qkept : (pnm ? pnm[2 * (size_t)s] : map[s]);
+            const float4 qe = (BOTH_N || match_pt || (pnm && have_n)) ? qkept : (pnm ? pnm[2 * (size_t)s] : map[s]);
             float plane2 = 0.f;
             if (normals) {
-                const float4 ne = GICP || (have_n && USES_N) ? nkept : (pnm ? pnm[2 * (size_t)s + 1] : normals[s]);
+                const float4 ne = BOTH_N || (have_n && USES_N) ? nkept : (pnm ? pnm[2 * (size_t)s + 1] : normals[s]);
                 const float dx = pe.x - qe.x, dy = pe.y - qe.y, dz = pe.z - qe.z;
                 const float dot = dx * ne.x + dy * ne.y + dz * ne.z;
                 plane2 = dot * dot;
             }
-            w = match_weight<true>(lc, st, d2, T, read_normals, GICP ? okept : (qindex ? qindex[qi] : qi), normals, s, FUSED ? fused_slot : -1, fused_limit,
-                                   ref_scalar, __float_as_int(qe.w), plane2, GICP ? &rnkept : nullptr);
-        } else w = match_weight(lc, st, d2, T, read_normals, GICP ? okept : (qindex ? qindex[qi] : qi), normals, s, FUSED ? fused_slot : -1, fused_limit,
-                                nullptr, 0, 0.f, GICP ? &rnkept : nullptr);
+            w = match_weight<true>(lc, st, d2, T, read_normals, BOTH_N ? okept : (qindex ? qindex[qi] : qi), normals, s, FUSED ? fused_slot : -1, fused_limit,
+                                   ref_scalar, __float_as_int(qe.w), plane2, BOTH_N ? &rnkept : nullptr);
+        } else w = match_weight(lc, st, d2, T, read_normals, BOTH_N ? okept : (qindex ? qindex[qi] : qi), normals, s, FUSED ? fused_slot : -1, fused_limit,
+                                nullptr, 0, 0.f, BOTH_N ? &rnkept : nullptr);
         if (w == 0.f) return;
         wsum += w; cnt += 1.0;
         if (MIN == ICPMI_MIN_IDENTITY) return;
         const float3 p = xf_point(T, r.x, r.y, r.z, r.w);
-        const float4 q = (GICP || match_pt || (pnm && have_n)) ? qkept : (pnm ? pnm[2 * (size_t)s] : map[s]);
+        const float4 q = (BOTH_N || match_pt || (pnm && have_n)) ? qkept : (pnm ? pnm[2 * (size_t)s] : map[s]);
         if (MIN == ICPMI_MIN_POINT_TO_POINT) {
             const double dw = w;
             acc[0] += dw;
@@ -448,11 +453,33 @@ __global__ __launch_bounds__(BT) void accumulate_kernel(const float4* __restrict
             acc[12] += dw * pm2.x; acc[13] += dw * pm2.y; acc[14] += dw * pm2.z;
             const float3 r0 = cross3(p, pm0), r1 = cross3(p, pm1), r2 = cross3(p, pm2);
             acc[0] += dw * r0.x; acc[1] += dw * r0.y; acc[2] += dw * r0.z; acc[6] += dw * r1.y; acc[7] += dw * r1.z; acc[11] += dw * r2.z;
+        } else if constexpr (MIN == PAIR_SYMMETRIC) {
+            // symmetric point-to-plane in its rotated-normals form (Rusinkiewicz 2019): the point-to-plane branch above with the
+            // pair normal n_s = (|c| u_q + c u_p) / 2, c = u_q . u_p -- continuous in both normals, and the sign of either cancels bit for bit
+            const float4 nq = nkept, rn = rnkept;
+            const float3 uq = unit_or_zero(nq.x, nq.y, nq.z);
+            const float3 up = unit_or_zero(fmaf(T[8], rn.z, fmaf(T[4], rn.y, T[0] * rn.x)), fmaf(T[9], rn.z, fmaf(T[5], rn.y, T[1] * rn.x)),
+                                           fmaf(T[10], rn.z, fmaf(T[6], rn.y, T[2] * rn.x)));
+            const bool hq = uq.x != 0.f || uq.y != 0.f || uq.z != 0.f, hp = up.x != 0.f || up.y != 0.f || up.z != 0.f;
+            const float c = uq.x * up.x + uq.y * up.y + uq.z * up.z, ac = fabsf(c);
+            // no surface model on one side: the other side's normal alone (reading side: this IS point-to-plane); on neither: u_q = 0, nothing is added
+            const float3 nn = !hp ? uq : (!hq ? up : make_float3(0.5f * (ac * uq.x + c * up.x), 0.5f * (ac * uq.y + c * up.y), 0.5f * (ac * uq.z + c * up.z)));
+            const float F[6] = {p.y * nn.z - p.z * nn.y, p.z * nn.x - p.x * nn.z, p.x * nn.y - p.y * nn.x, nn.x, nn.y, nn.z};
+            const float dx = p.x - q.x, dy = p.y - q.y, dz = p.z - q.z;
+            const float dot = dx * nn.x + dy * nn.y + dz * nn.z;
+            int idx = 0;
+#pragma unroll
+            for (int a = 0; a < 6; ++a) {
+                const double wf = (double)w * F[a];
+#pragma unroll
+                for (int b = a; b < 6; ++b) acc[idx++] += wf * F[b];
+                acc[21 + a] -= wf * dot;
+            }
         }
     };
 #pragma unroll
-    for (int u = 0; u < PF; ++u) pair(e_first + u * estep, pd2[u], ps[u], pr[u], pq[u], pn[u], true, prn[u], GICP ? po[u] : 0);
-    if constexpr (GICP) {
+    for (int u = 0; u < PF; ++u) pair(e_first + u * estep, pd2[u], ps[u], pr[u], pq[u], pn[u], true, prn[u], BOTH_N ? po[u] : 0);
+    if constexpr (BOTH_N) {
         for (int64_t e = e_first + PF * estep; e < e_end; e += estep) { // (past a full grid: the four gathers of a pair requested together)
             const float d2 = d2a[e];
             const int s = sidx[e], qi = (int)(e / lc.k), oi = qindex ? qindex[qi] : qi;
@@ -670,7 +697,7 @@ LoopCfg make_loop_cfg(const icpmi_ctx* c, int fixed_iterations)
         lc.degen_thr = fabsf(cfg.degeneracy_threshold);
         lc.degen_blk = c->d_degen.get();
     }
-    if (gicp) lc.degen_thr = c->plane_eps; // (degen stays 0: validate_config rejects the combination; common.h: plane_to_plane_eps)
+    if (gicp) lc.degen_thr = c->plane_model == ICPMI_PLANE_MODEL_SYMMETRIC ? ICPMI_PLANE_SLOT_SYMMETRIC : c->plane_eps; // (degen stays 0: validate_config rejects the combination; common.h: plane_to_plane_eps)
     return lc;
 }
 
@@ -1091,7 +1118,7 @@ static void launch_accumulate_ext(icpmi_ctx* c, const LoopCfg& lc, int nb, int s
     const int is_med = slot >= 0 && lc.out_type[slot] == ICPMI_OUT_MEDIANDIST;
     const float factor = slot >= 0 ? lc.out_param[slot] : 0.f;
     // k > 1, point-to-plane: matched point and its normal side by side (map_build.hip: pn_kernel)
-    const float4* pnm = (lc.k > 1 && (MIN == ICPMI_MIN_POINT_TO_PLANE || MIN == ICPMI_MIN_PLANE_TO_PLANE) && c->has_normals && c->d_map_pn) ? c->d_map_pn.get() : nullptr;
+    const float4* pnm = (lc.k > 1 && (MIN == ICPMI_MIN_POINT_TO_PLANE || MIN == ICPMI_MIN_PLANE_TO_PLANE || MIN == PAIR_SYMMETRIC) && c->has_normals && c->d_map_pn) ? c->d_map_pn.get() : nullptr;
     if (lc.k > 1)
         hipLaunchKernelGGL((accumulate_kernel<MIN, FUSED, EXT, 1024>), dim3(nb, ba.nscan), dim3(1024), 0, c->stream, v.reading, ba, acc_cap(), lc, c->d_state,
                            v.map, v.ref_normals, v.read_normals, v.sidx, v.d2, c->d_selhist, slot, is_med, factor, v.match_pt, v.qindex, v.ref_scalar, pnm);
@@ -1111,7 +1138,10 @@ static void enqueue_accumulate_solve(icpmi_ctx* c, int64_t n, const LoopCfg& lc,
     // (r1: letting the last pair-sum workgroup solve -- ticket + device fences -- measured +3.5 us per
     // iteration against this separate 1-workgroup launch, and dragged the solver's registers and scratch
     // into the pair-sum kernel: removed.)
-    if (plane_to_plane_eps(lc) > 0.f) { // (its own instantiation of the pair sums; the solve below reads lc.minimizer: point-to-plane)
+    if (plane_pair_symmetric(lc)) { // (the other pair model of that path: common.h)
+        if (fused) launch_accumulate<PAIR_SYMMETRIC, true>(c, lc, nb, slot, ba, nn.out_sorted);
+        else launch_accumulate<PAIR_SYMMETRIC, false>(c, lc, nb, slot, ba, nn.out_sorted);
+    } else if (plane_to_plane_eps(lc) > 0.f) { // (its own instantiation of the pair sums; the solve below reads lc.minimizer: point-to-plane)
         if (fused) launch_accumulate<ICPMI_MIN_PLANE_TO_PLANE, true>(c, lc, nb, slot, ba, nn.out_sorted);
         else launch_accumulate<ICPMI_MIN_PLANE_TO_PLANE, false>(c, lc, nb, slot, ba, nn.out_sorted);
     } else if (lc.minimizer == ICPMI_MIN_POINT_TO_PLANE) {

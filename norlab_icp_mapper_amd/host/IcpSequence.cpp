@@ -143,8 +143,9 @@ void parseMatcher(const yaml::Node& matcher, icpmi_config& cfg, std::string& max
     if (e.second["maxDist"]) cfg.max_dist = e.second["maxDist"].as<float>();
 }
 
-// the `errorMinimizer:` entry of an ICP chain into the configuration; planeEpsilon = PlaneToPlaneErrorMinimizer.epsilon (left alone by the others)
-void parseErrorMinimizer(const yaml::Node& node, icpmi_config& cfg, float& planeEpsilon)
+// the `errorMinimizer:` entry of an ICP chain into the configuration; planeEpsilon = PlaneToPlaneErrorMinimizer.epsilon (left alone by the
+// others), planeModel = the pair model of ICPMI_MIN_PLANE_TO_PLANE (SymmetricPointToPlaneErrorMinimizer sets it; left alone by the others)
+void parseErrorMinimizer(const yaml::Node& node, icpmi_config& cfg, float& planeEpsilon, int& planeModel)
 {
     auto e = singleEntry(node, "errorMinimizer");
     if (e.first == "IdentityErrorMinimizer") cfg.minimizer = ICPMI_MIN_IDENTITY;
@@ -174,6 +175,13 @@ void parseErrorMinimizer(const yaml::Node& node, icpmi_config& cfg, float& plane
         if (e.second["epsilon"]) planeEpsilon = e.second["epsilon"].as<float>();
         if (!std::isfinite(planeEpsilon) || !(planeEpsilon > 0.f) || planeEpsilon > 1.f)
             throw InvalidParameter(e.first + ": epsilon must be finite and in (0, 1]");
+    } else if (e.first == "SymmetricPointToPlaneErrorMinimizer") {
+        // symmetric point-to-plane from the normals of both clouds (not libpointmatcher's; include/icpmi.h: ICPMI_PLANE_MODEL_SYMMETRIC):
+        // the plane-to-plane path under its other pair model
+        requireKnown(e.second, {"force4DOF"}, e.first);
+        cfg.minimizer = ICPMI_MIN_PLANE_TO_PLANE;
+        planeModel = ICPMI_PLANE_MODEL_SYMMETRIC;
+        cfg.force_4dof = (e.second["force4DOF"] && e.second["force4DOF"].as<int>() != 0) ? 1 : 0;
     } else throw InvalidParameter("unknown error minimizer " + e.first);
 }
 
@@ -182,6 +190,7 @@ void GpuICPSequence::loadFromYamlNode(const yaml::Node& icp)
     const int dev = cfg.device;
     icpmi_config_default(&cfg);
     planeEpsilon = 1e-3f; // PlaneToPlaneErrorMinimizer.epsilon
+    planeModel = ICPMI_PLANE_MODEL_GICP; // (SymmetricPointToPlaneErrorMinimizer: the other one)
     cfg.device = dev;
     cfg.is_2d = planar ? 1 : 0;
     if (icp.IsMap())
@@ -268,7 +277,7 @@ void GpuICPSequence::loadFromYamlNode(const yaml::Node& icp)
             if (cfg.n_outlier >= 8) throw InvalidParameter("at most 8 outlier filters");
             cfg.outlier[cfg.n_outlier++] = o;
         }
-    if (icp["errorMinimizer"]) parseErrorMinimizer(icp["errorMinimizer"], cfg, planeEpsilon);
+    if (icp["errorMinimizer"]) parseErrorMinimizer(icp["errorMinimizer"], cfg, planeEpsilon, planeModel);
     if (icp["transformationCheckers"].IsSequence())
         for (const auto& item : icp["transformationCheckers"].seq) {
             auto e = singleEntry(item, "transformation checker");
@@ -290,6 +299,7 @@ void GpuICPSequence::loadFromYamlNode(const yaml::Node& icp)
         }
     recreate();
     check(h, icpmi_set_plane_epsilon(h, planeEpsilon));
+    check(h, icpmi_set_plane_pair_model(h, planeModel));
     auto chain = [&](const char* key) -> std::shared_ptr<DataPointsFilters> {
         if (!icp[key] || !icp[key].IsSequence() || icp[key].seq.empty()) return nullptr;
         return std::make_shared<DataPointsFilters>(icp[key], h);
@@ -614,7 +624,7 @@ PoseScores GpuICPSequence::residuals(const DataPoints& readingIn, const std::vec
 void GpuICPSequence::requireBareReadingChain(const char* who) const
 {
     if (chainNeedsReadingNormals())
-        throw InvalidParameter(std::string(who) + ": the chain (SurfaceNormalOutlierFilter, PlaneToPlaneErrorMinimizer) reads the reading's normals, which the multistart registration does not carry");
+        throw InvalidParameter(std::string(who) + ": the chain (SurfaceNormalOutlierFilter, PlaneToPlaneErrorMinimizer, SymmetricPointToPlaneErrorMinimizer) reads the reading's normals, which the multistart registration does not carry");
     if (readsReadingDescriptor())
         throw InvalidParameter(std::string(who) + ": the chain reads a descriptor row of the reading (" +
                                (!genericReadDescName.empty() ? genericReadDescName : maxDistFieldName) + "), which the multistart registration does not carry");

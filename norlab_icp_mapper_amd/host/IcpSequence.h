@@ -30,8 +30,9 @@ std::pair<std::string, yaml::Node> singleEntry(const yaml::Node& n, const std::s
 // KDTreeVarDistMatcher (default maxSearchDist), empty for KDTreeMatcher.  Needs no GPU.
 void parseMatcher(const yaml::Node& matcher, icpmi_config& cfg, std::string& maxDistField);
 // the `errorMinimizer:` entry into cfg (minimizer, force2D / force4DOF, covariance, degeneracy options); planeEpsilon = the epsilon of a
-// PlaneToPlaneErrorMinimizer (default 0.001; the others leave it alone).  Needs no GPU.
-void parseErrorMinimizer(const yaml::Node& node, icpmi_config& cfg, float& planeEpsilon);
+// PlaneToPlaneErrorMinimizer (default 0.001; the others leave it alone); planeModel = ICPMI_PLANE_MODEL_SYMMETRIC under
+// SymmetricPointToPlaneErrorMinimizer, which travels as ICPMI_MIN_PLANE_TO_PLANE (the others leave it alone).  Needs no GPU.
+void parseErrorMinimizer(const yaml::Node& node, icpmi_config& cfg, float& planeEpsilon, int& planeModel);
 
 // ---- relocalisation: one reading under many poses (include/icpmi.h: icpmi_residual_error_poses, icpmi_register_multistart) ----
 // one icpmi_residual and one status per pose (a pose whose status is not ICPMI_OK keeps an empty residual); batched = the poses that
@@ -135,7 +136,7 @@ public:
     void setPlanar(bool on);                           // 2-D clouds (z == 0): planar minimisers and normals
     bool isPlanar() const { return planar; }
     const std::string& genericDescriptorName() const { return genericDescName; } // GenericDescriptorOutlierFilter.descName, or empty
-    bool chainNeedsReadingNormals() const;             // SurfaceNormalOutlierFilter or PlaneToPlaneErrorMinimizer in the chain
+    bool chainNeedsReadingNormals() const;             // SurfaceNormalOutlierFilter or PlaneToPlaneErrorMinimizer / SymmetricPointToPlaneErrorMinimizer in the chain
     // true when the chain filters the reading inside operator() (readingDataPointsFilters / readingStepDataPointsFilters):
     // the staged-scan path of Mapper::processInput hands the unfiltered scan to the GPU and must not be taken then
     bool hasReadingFilters() const;
@@ -162,6 +163,7 @@ private:
     icpmi_config cfg;
     icpmi_stats lastStats{};
     float planeEpsilon = 1e-3f;                        // PlaneToPlaneErrorMinimizer.epsilon (icpmi_set_plane_epsilon)
+    int planeModel = ICPMI_PLANE_MODEL_GICP;           // ... and its pair model (icpmi_set_plane_pair_model): SymmetricPointToPlaneErrorMinimizer
     size_t stagedPoints = 0;                           // size of the scan kept on the GPU by registerWithPrior
     std::string genericDescName;                       // GenericDescriptorOutlierFilter.descName (empty: no such filter)
     std::string genericReadDescName;                   // ... of a filter with source: reading (the row goes to the device with every reading)

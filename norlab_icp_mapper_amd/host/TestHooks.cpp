@@ -154,9 +154,28 @@ int nim_test_parse_error_minimizer(const char* yaml_icp, int* minimizer, int* fo
         icpmi_config cfg;
         icpmi_config_default(&cfg);
         float eps = 1e-3f;
-        nim::parseErrorMinimizer(nim::yaml::Load(yaml_icp)["errorMinimizer"], cfg, eps);
+        int model = ICPMI_PLANE_MODEL_GICP;
+        nim::parseErrorMinimizer(nim::yaml::Load(yaml_icp)["errorMinimizer"], cfg, eps, model);
         *minimizer = cfg.minimizer; *force_4dof = cfg.force_4dof; *force_2d = cfg.force_2d; *covariance = cfg.covariance;
         *degeneracy_threshold = cfg.degeneracy_threshold; *plane_epsilon = eps;
+        return 0;
+    } catch (const std::exception& e) {
+        if (err && err_cap > 0) { std::strncpy(err, e.what(), (size_t)err_cap - 1); err[err_cap - 1] = 0; }
+        return 1;
+    }
+}
+
+// ... and the pair model of ICPMI_MIN_PLANE_TO_PLANE with it (ICPMI_PLANE_MODEL_*: SymmetricPointToPlaneErrorMinimizer names the symmetric one)
+int nim_test_parse_error_minimizer_model(const char* yaml_icp, int* minimizer, int* force_4dof, float* plane_epsilon, int* plane_model,
+                                         char* err, int err_cap)
+{
+    try {
+        icpmi_config cfg;
+        icpmi_config_default(&cfg);
+        float eps = 1e-3f;
+        int model = ICPMI_PLANE_MODEL_GICP;
+        nim::parseErrorMinimizer(nim::yaml::Load(yaml_icp)["errorMinimizer"], cfg, eps, model);
+        *minimizer = cfg.minimizer; *force_4dof = cfg.force_4dof; *plane_epsilon = eps; *plane_model = model;
         return 0;
     } catch (const std::exception& e) {
         if (err && err_cap > 0) { std::strncpy(err, e.what(), (size_t)err_cap - 1); err[err_cap - 1] = 0; }

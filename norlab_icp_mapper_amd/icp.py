@@ -62,8 +62,11 @@ _MINIMIZERS = {
     "PointToPointErrorMinimizer": _capi.MIN_POINT_TO_POINT,
     "PointToPlaneErrorMinimizer": _capi.MIN_POINT_TO_PLANE,
     "PlaneToPlaneErrorMinimizer": _capi.MIN_PLANE_TO_PLANE,
+    "SymmetricPointToPlaneErrorMinimizer": _capi.MIN_PLANE_TO_PLANE,  # (the same path under its other pair model: _PLANE_MODELS)
 }
 PLANE_EPSILON_DEFAULT = 1e-3
+_PLANE_MODELS = {"gicp": _capi.PLANE_MODEL_GICP, "symmetric": _capi.PLANE_MODEL_SYMMETRIC}
+_PLANE_MODEL_NAMES = {v: k for k, v in _PLANE_MODELS.items()}
 
 
 def _check_plane_epsilon(eps):
@@ -72,6 +75,12 @@ def _check_plane_epsilon(eps):
         raise InvalidParameter("PlaneToPlaneErrorMinimizer: epsilon must be finite and in (0, 1]")
     return eps
 
+
+
+def _check_plane_model(model):
+    if model not in _PLANE_MODELS:
+        raise InvalidParameter(f"plane_model must be one of {sorted(_PLANE_MODELS)}, not {model!r}")
+    return model
 
 
 def _f32c(a, cols):
@@ -226,6 +235,13 @@ def config_from_yaml_chain(chain, **engine):
             if key not in ("epsilon", "force4DOF"):
                 raise InvalidParameter(f"{name}: unknown parameter {key}")
         plane_epsilon = _check_plane_epsilon(p.get("epsilon", PLANE_EPSILON_DEFAULT))
+    plane_model = None
+    if name == "SymmetricPointToPlaneErrorMinimizer":
+        # symmetric point-to-plane from the normals of both clouds (not libpointmatcher's; include/icpmi.h: ICPMI_PLANE_MODEL_SYMMETRIC)
+        for key in p:
+            if key != "force4DOF":
+                raise InvalidParameter(f"{name}: unknown parameter {key}")
+        plane_model = "symmetric"
     if name not in _MINIMIZERS:
         raise InvalidParameter(f"unknown error minimizer {name}")
     if name == "PointToPlaneErrorMinimizer":
@@ -240,7 +256,7 @@ def config_from_yaml_chain(chain, **engine):
             raise InvalidParameter(f"{name}: degeneracyThreshold and force2D exclude each other")
         kw["degeneracy_threshold"] = thr if action == "constrain" else -thr
     kw["minimizer"] = _MINIMIZERS[name]
-    kw["force_4dof"] = 1 if (name in ("PointToPlaneErrorMinimizer", "PlaneToPlaneErrorMinimizer") and int(p.get("force4DOF", 0))) else 0
+    kw["force_4dof"] = 1 if (name in ("PointToPlaneErrorMinimizer", "PlaneToPlaneErrorMinimizer", "SymmetricPointToPlaneErrorMinimizer") and int(p.get("force4DOF", 0))) else 0
     kw["force_2d"] = 1 if (name == "PointToPlaneErrorMinimizer" and int(p.get("force2D", 0))) else 0
     if kw["force_4dof"] and kw["force_2d"]:
         raise InvalidParameter("PointToPlaneErrorMinimizer: force2D and force4DOF exclude each other")
@@ -269,6 +285,8 @@ def config_from_yaml_chain(chain, **engine):
         cfg.max_dist_field = max_dist_field  # (a Python attribute next to the C fields: the descriptor name is the host's business)
     if plane_epsilon is not None:
         cfg.plane_epsilon = plane_epsilon  # (likewise: icpmi_config has no word left; ICPSequence hands it to icpmi_set_plane_epsilon)
+    if plane_model is not None:
+        cfg.plane_model = plane_model  # (likewise: ICPSequence hands it to icpmi_set_plane_pair_model)
     return cfg
 
 
@@ -413,14 +431,19 @@ class _ErrorMinimizerView:
 class ICPSequence:
     """``PM::ICPSequence`` backed by one icpmi handle (one GPU, one stream)."""
 
-    def __init__(self, cfg=None, plane_epsilon=None, **kw):
-        """plane_epsilon: epsilon of PlaneToPlaneErrorMinimizer (icpmi_set_plane_epsilon; default: the chain's, else 1e-3)"""
+    def __init__(self, cfg=None, plane_epsilon=None, plane_model=None, **kw):
+        """plane_epsilon: epsilon of PlaneToPlaneErrorMinimizer (icpmi_set_plane_epsilon; default: the chain's, else 1e-3)
+        plane_model: "gicp" | "symmetric", the pair model of minimizer 3 (icpmi_set_plane_pair_model; default: the chain's, else "gicp")"""
         self._lib = _capi.load()
         self.cfg = cfg if cfg is not None else default_config(**kw)
         if plane_epsilon is None:
             plane_epsilon = getattr(self.cfg, "plane_epsilon", None)
         if plane_epsilon is not None:
             plane_epsilon = _check_plane_epsilon(plane_epsilon)
+        if plane_model is None:
+            plane_model = getattr(self.cfg, "plane_model", None)
+        if plane_model is not None:
+            _check_plane_model(plane_model)
         h = C.c_void_p()
         st = self._lib.icpmi_create(C.byref(self.cfg), C.byref(h))
         if st != _capi.ICPMI_OK:
@@ -432,6 +455,8 @@ class ICPSequence:
         self._last_n = 0
         if plane_epsilon is not None:
             self.setPlaneEpsilon(plane_epsilon)
+        if plane_model is not None:
+            self.setPlaneModel(plane_model)
 
     @classmethod
     def loadFromYaml(cls, chain, **engine):
@@ -446,6 +471,15 @@ class ICPSequence:
     def setPlaneEpsilon(self, eps):
         """icpmi_set_plane_epsilon: handle state (setConfig leaves it); the next registration runs with it"""
         self._check(self._lib.icpmi_set_plane_epsilon(self._h, float(eps)))
+
+    def setPlaneModel(self, model):
+        """icpmi_set_plane_pair_model ("gicp" | "symmetric"): handle state (setConfig leaves it); the next registration runs with it"""
+        self._check(self._lib.icpmi_set_plane_pair_model(self._h, _PLANE_MODELS[_check_plane_model(model)]))
+
+    def getPlaneModel(self):
+        out = C.c_int32(0)
+        self._check(self._lib.icpmi_get_plane_pair_model(self._h, C.byref(out)))
+        return _PLANE_MODEL_NAMES[int(out.value)]
 
     def getPlaneEpsilon(self):
         out = C.c_float(0)
