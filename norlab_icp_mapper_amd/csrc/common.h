@@ -200,6 +200,20 @@ struct GridLevels {
     const unsigned* pos0[ICPMI_MAXLEV]; // level position -> level-0 position (nullptr for level 0)
 };
 
+// One level of the pyramid as the NN kernels read it: c->d_lvl_tab holds ICPMI_MAXLEV of these (upload_level_table, map_build.hip), a kernel
+// copies them into LDS as four uint4 words per level and reads them through level_grid / level_cs / level_pts / level_pos0 below.
+struct LevelRow {
+    float ox, oy, oz, cell;       // word 0
+    float inv_cell, slack;        // word 1
+    int nx, ny;
+    int nz, ncells;               // word 2
+    const float4* pts;
+    const unsigned* cs;           // word 3
+    const unsigned* pos0;
+};
+static_assert(sizeof(LevelRow) == 64 && offsetof(LevelRow, inv_cell) == 16 && offsetof(LevelRow, nz) == 32 && offsetof(LevelRow, pts) == 40 &&
+              offsetof(LevelRow, cs) == 48 && offsetof(LevelRow, pos0) == 56, "four uint4 words, pointers in the halves the readers take them from");
+
 // Batched registration (icpmi_register_batch_dev): B independent readings against the same map go through ONE launch
 // of every kernel of the loop, blockIdx.y = reading.  Per-reading arrays are slices of one allocation (slice b starts
 // at b * qstride elements; selection histograms, pair-sum partials and the IcpState array have their own fixed
@@ -979,6 +993,99 @@ __device__ __forceinline__ unsigned long long pack_key(float d2, unsigned id)
 
 // a square root that never under-estimates (one v_sqrt_f32, 1 ulp, nudged up)
 __device__ __forceinline__ float sqrt_up(float x) { return __builtin_amdgcn_sqrtf(x) * 1.0000005f; }
+
+// ---- the pieces every grid matcher of nn.hip is written on ("Shared pieces of the matcher kernels") ----
+typedef float vf4 __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(1))) vf4 gfloat4;          // 16 bytes in global memory (global_load, not flat_load)
+typedef __attribute__((address_space(1))) unsigned gunsigned;
+
+// Readers of the level table (LevelRow) over the uint4 view a kernel keeps of it, in LDS or in global memory.  A pointer rebuilt from
+// integers would be read through the flat path: P names the address space, global by default.
+__device__ __forceinline__ GridParams level_grid(const uint4* ltab, int lv)
+{
+    const uint4 a = ltab[4 * lv], b = ltab[4 * lv + 1], c = ltab[4 * lv + 2];
+    GridParams g;
+    g.ox = __uint_as_float(a.x); g.oy = __uint_as_float(a.y); g.oz = __uint_as_float(a.z); g.cell = __uint_as_float(a.w);
+    g.inv_cell = __uint_as_float(b.x); g.slack = __uint_as_float(b.y); g.nx = (int)b.z; g.ny = (int)b.w;
+    g.nz = (int)c.x; g.ncells = (int)c.y;
+    return g;
+}
+template <class P = const gfloat4*>
+__device__ __forceinline__ P level_pts(const uint4* ltab, int lv) { const uint4 c = ltab[4 * lv + 2]; return reinterpret_cast<P>(((unsigned long long)c.w << 32) | c.z); }
+template <class P = const gunsigned*>
+__device__ __forceinline__ P level_cs(const uint4* ltab, int lv) { const uint4 d = ltab[4 * lv + 3]; return reinterpret_cast<P>(((unsigned long long)d.y << 32) | d.x); }
+template <class P = const gunsigned*>
+__device__ __forceinline__ P level_pos0(const uint4* ltab, int lv) { const uint4 d = ltab[4 * lv + 3]; return reinterpret_cast<P>(((unsigned long long)d.w << 32) | d.z); }
+
+// where a point sits in a level: scaled coordinates, their floors, the integer cell (clamped: far outside the box stays representable) and
+// mf = the distance to the nearest face of its own cell, in cells (0 for a NaN coordinate: no margin is ever claimed for it)
+struct CellPos {
+    float fx, fy, fz, flx, fly, flz;
+    int cx, cy, cz;
+    float mf;
+};
+__device__ __forceinline__ CellPos cell_pos(float x, float y, float z, const GridParams& g)
+{
+    CellPos c;
+    c.fx = (x - g.ox) * g.inv_cell; c.fy = (y - g.oy) * g.inv_cell; c.fz = (z - g.oz) * g.inv_cell;
+    c.flx = floorf(c.fx); c.fly = floorf(c.fy); c.flz = floorf(c.fz);
+    c.cx = (int)fminf(fmaxf(c.flx, -1.0e6f), 1.0e6f);
+    c.cy = (int)fminf(fmaxf(c.fly, -1.0e6f), 1.0e6f);
+    c.cz = (int)fminf(fmaxf(c.flz, -1.0e6f), 1.0e6f);
+    float mf = fminf(c.fx - c.flx, 1.0f - (c.fx - c.flx));
+    mf = fminf(mf, fminf(c.fy - c.fly, 1.0f - (c.fy - c.fly)));
+    mf = fminf(mf, fminf(c.fz - c.flz, 1.0f - (c.fz - c.flz)));
+    if (!(mf >= 0.f)) mf = 0.f;
+    c.mf = mf;
+    return c;
+}
+
+// The exactness rule of the search.  Every point within block_margin of the query lies inside the (2 ring + 1)^3 block of cells around the
+// query's cell: a k-th distance within it decides the query.  block_margin_seed is the same reach claimed BEFORE a search, from a bound
+// that was computed elsewhere (two slacks); block_covers: the block holds the whole grid, nothing is left to look at.
+__device__ __forceinline__ float block_margin(float mf, float cell, float slack, int ring = 1) { return fmaxf(((float)ring + mf) * cell - slack, 0.f); }
+__device__ __forceinline__ float block_margin_seed(float mf, float cell, float slack) { return (1.0f + mf) * cell - 2.0f * slack; }
+__device__ __forceinline__ bool block_covers(const CellPos& c, const GridParams& g, int ring = 1)
+{
+    return c.cx - ring <= 0 && c.cx + ring >= g.nx - 1 && c.cy - ring <= 0 && c.cy + ring >= g.ny - 1 && c.cz - ring <= 0 && c.cz + ring >= g.nz - 1;
+}
+// the 3 x 3 x 3 block of level g around the point holds the ball of radius ub around it
+__device__ __forceinline__ bool block_holds_ball(float x, float y, float z, const GridParams& g, float ub)
+{
+    return ub <= block_margin_seed(cell_pos(x, y, z, g).mf, g.cell, g.slack);
+}
+// first level >= from (the top level at the latest) whose block holds that ball
+__device__ __forceinline__ int level_holding_ball(const uint4* ltab, int nlev, int from, float x, float y, float z, float ub)
+{
+    int l = from;
+    for (; l < nlev - 1; ++l)
+        if (block_holds_ball(x, y, z, level_grid(ltab, l), ub)) break;
+    return l;
+}
+
+// x-range [xa, xb] of row (dy, dz) of the 3 x 3 x 3 block around c that the ball of squared radius rub2 (+inf: none) around the point can
+// reach: the block's own three cells, clipped by what the row's distance leaves of the radius.  false: the ball misses the row.
+__device__ __forceinline__ bool clip_row_x(const CellPos& c, const GridParams& g, float x, int dy, int dz, float rub2, int& xa, int& xb)
+{
+    const float ylo = (c.fy - c.fly) * g.cell, yhi = (1.0f - (c.fy - c.fly)) * g.cell;
+    const float zlo = (c.fz - c.flz) * g.cell, zhi = (1.0f - (c.fz - c.flz)) * g.cell;
+    const float ddy = dy == 0 ? 0.f : (dy < 0 ? ylo : yhi);
+    const float ddz = dz == 0 ? 0.f : (dz < 0 ? zlo : zhi);
+    const float rem2 = rub2 - (ddy * ddy + ddz * ddz); // +inf without a bound
+    xa = c.cx - 1; xb = c.cx + 1;
+    if (rem2 != INFINITY) {
+        const float rem = sqrt_up(fmaxf(rem2, 0.f));
+        const int xl = (int)fmaxf(floorf((x - rem - g.ox) * g.inv_cell), -1.0e6f);
+        const int xh = (int)fminf(floorf((x + rem - g.ox) * g.inv_cell), 1.0e6f);
+        xa = xl > xa ? xl : xa;
+        xb = xh < xb ? xh : xb;
+    }
+    return rem2 >= 0.f;
+}
+
+// XCD-aware order of a launch's nblocks (a multiple of 8) workgroups: workgroup b runs on XCD b % 8; each XCD gets one contiguous eighth
+template <class N>
+__device__ __forceinline__ int xcd_block(unsigned b, N nblocks) { const int chunk = nblocks >> 3; return (int)((b & 7) * chunk + (b >> 3)); }
 
 // MurmurHash3's 32-bit finaliser: a bijection of the 32-bit integers, so "smallest hash" names exactly one point
 __device__ __forceinline__ unsigned fmix32(unsigned h)

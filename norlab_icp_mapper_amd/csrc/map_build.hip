@@ -865,20 +865,18 @@ static GridParams make_grid(const float lo[3], const float hi[3], float cell, fl
 
 icpmi_status upload_level_table(icpmi_ctx* c)
 {
-    // level table for the NN kernels: per level [ox oy oz cell][inv_cell slack nx ny][nz ncells pts][cs pos0]
-    GridLevels& L = c->levels;
-    uint32_t tab[ICPMI_MAXLEV * 16] = {0};
-    auto fbits = [](float f) { uint32_t u; memcpy(&u, &f, 4); return u; };
+    // level table for the NN kernels (common.h: LevelRow); levels beyond nlev stay zero
+    const GridLevels& L = c->levels;
+    LevelRow tab[ICPMI_MAXLEV] = {};
     for (int l = 0; l < L.nlev; ++l) {
-        uint32_t* t = tab + 16 * l;
+        LevelRow& t = tab[l];
         const GridParams& gl = L.g[l];
-        t[0] = fbits(gl.ox); t[1] = fbits(gl.oy); t[2] = fbits(gl.oz); t[3] = fbits(gl.cell);
-        t[4] = fbits(gl.inv_cell); t[5] = fbits(gl.slack); t[6] = (uint32_t)gl.nx; t[7] = (uint32_t)gl.ny;
-        t[8] = (uint32_t)gl.nz; t[9] = (uint32_t)gl.ncells;
-        const uint64_t pp = (uint64_t)(uintptr_t)L.pts[l], pc = (uint64_t)(uintptr_t)L.cs[l], p0 = (uint64_t)(uintptr_t)L.pos0[l];
-        t[10] = (uint32_t)pp; t[11] = (uint32_t)(pp >> 32);
-        t[12] = (uint32_t)pc; t[13] = (uint32_t)(pc >> 32); t[14] = (uint32_t)p0; t[15] = (uint32_t)(p0 >> 32);
+        t.ox = gl.ox; t.oy = gl.oy; t.oz = gl.oz; t.cell = gl.cell;
+        t.inv_cell = gl.inv_cell; t.slack = gl.slack; t.nx = gl.nx; t.ny = gl.ny;
+        t.nz = gl.nz; t.ncells = gl.ncells;
+        t.pts = L.pts[l]; t.cs = L.cs[l]; t.pos0 = L.pos0[l];
     }
+    static_assert(sizeof tab == ICPMI_MAXLEV * 4 * sizeof(uint4), "the kernels read it as four uint4 per level");
     if (!c->d_lvl_tab) HIP_TRY(c, c->d_lvl_tab.alloc(ICPMI_MAXLEV * 4));
     return upload_small(c, c->d_lvl_tab, tab, sizeof tab);
 }

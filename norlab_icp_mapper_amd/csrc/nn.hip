@@ -16,12 +16,9 @@ namespace {
 
 constexpr int NN_BLOCK = 256;
 
-typedef __attribute__((address_space(1))) unsigned gunsigned;
 // sqrt for pruning radii and level choices (common.h: sqrt_up): one v_sqrt_f32 (1 ulp) instead of the IEEE-exact sequence (~12
 // instructions, and the kernels take it per row), nudged UP by 2^-21 relative so that it never under-estimates -- a bound that is a hair
 // too wide only ever adds candidates, it cannot change the exact minimum
-typedef float vf4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(1))) vf4 gfloat4; // 16 bytes in global memory (global_load, not flat_load)
 
 // The ACCEPT radius of a matcher kernel (template parameter R of every kernel below; what decides filled against unfilled where the
 // results are written).  float: KDTreeMatcher's maxDist^2, one value for every query -- the kernel argument it always was.  RowR2:
@@ -185,22 +182,15 @@ __global__ __launch_bounds__(NN_BLOCK) void nnk_kernel(const float4* __restrict_
     float3 p;
     if (Tptr) p = xf_point(Tptr, r.x, r.y, r.z, r.w);
     else p = make_float3(r.x, r.y, r.z);
-    const float fx = (p.x - g.ox) * g.inv_cell, fy = (p.y - g.oy) * g.inv_cell, fz = (p.z - g.oz) * g.inv_cell;
-    const float flx = floorf(fx), fly = floorf(fy), flz = floorf(fz);
-    const int cx = (int)fminf(fmaxf(flx, -1.0e6f), 1.0e6f);
-    const int cy = (int)fminf(fmaxf(fly, -1.0e6f), 1.0e6f);
-    const int cz = (int)fminf(fmaxf(flz, -1.0e6f), 1.0e6f);
-    float mf = fminf(fx - flx, 1.0f - (fx - flx));
-    mf = fminf(mf, fminf(fy - fly, 1.0f - (fy - fly)));
-    mf = fminf(mf, fminf(fz - flz, 1.0f - (fz - flz)));
-    if (!(mf >= 0.f)) mf = 0.f;
+    const CellPos c = cell_pos(p.x, p.y, p.z, g);
+    const int cx = c.cx, cy = c.cy, cz = c.cz;
 
     KList<KMAX> L; L.init(k);
     bool decided = false;
     int ring = 0;
     // distances from the query to the faces of its cell along y and z (for pruning rows of ring 1)
-    const float ylo = (fy - fly) * g.cell, yhi = (1.0f - (fy - fly)) * g.cell;
-    const float zlo = (fz - flz) * g.cell, zhi = (1.0f - (fz - flz)) * g.cell;
+    const float ylo = (c.fy - c.fly) * g.cell, yhi = (1.0f - (c.fy - c.fly)) * g.cell;
+    const float zlo = (c.fz - c.flz) * g.cell, zhi = (1.0f - (c.fz - c.flz)) * g.cell;
     while (!decided && ring < ring_max) {
         ++ring;
         const int side = 2 * ring + 1;
@@ -213,7 +203,7 @@ __global__ __launch_bounds__(NN_BLOCK) void nnk_kernel(const float4* __restrict_
             unsigned s, e;
             if (full_row) {
                 int xa = cx - ring, xb = cx + ring;
-                if (ring == 1) {
+                if (ring == 1) { // (clip_row_x's range with the IEEE sqrtf this kernel has always used: the two differ by a rounding)
                     unsigned long long kth = ~0ull;
 #pragma unroll
                     for (int i = 0; i < KMAX; ++i) if (i == k - 1) kth = L.key[i];
@@ -243,12 +233,11 @@ __global__ __launch_bounds__(NN_BLOCK) void nnk_kernel(const float4* __restrict_
                 }
             }
         }
-        const float margin = fmaxf(((float)ring + mf) * g.cell - g.slack, 0.f);
+        const float margin = block_margin(c.mf, g.cell, g.slack, ring);
         const float m2 = margin * margin;
         const unsigned long long kth = L.key[k - 1];
         const float kd2 = __uint_as_float((unsigned)(kth >> 32));
-        const bool covers = cx - ring <= 0 && cx + ring >= g.nx - 1 && cy - ring <= 0 && cy + ring >= g.ny - 1 &&
-                            cz - ring <= 0 && cz + ring >= g.nz - 1;
+        const bool covers = block_covers(c, g, ring);
         decided = (kth != ~0ull && kd2 <= m2) || m2 > maxr2 || covers;
     }
     const float r2q = r2_query(maxr, true, nullptr, qi);
@@ -349,12 +338,25 @@ __global__ __launch_bounds__(256) void ids_kernel(const float4* __restrict__ map
 }
 
 // ------------------------------------------------------------------------------------------------
-// k = 1 over the grid pyramid.  (r1 - r2: nn1_ml_kernel, G lanes per query; r3: nn1_wq_kernel, a one-wave workgroup alternating
-// between lane-per-query and lane-per-piece; both were kept selectable through r5 and were removed in r6 -- git history has them,
-// DESIGN_history.md sections 5 / 11.2 their measurements.  What runs is nn1_wg_kernel below.)
+// k = 1 over the grid pyramid: nn1_wg_kernel below.  (Its predecessors nn1_ml_kernel and nn1_wq_kernel: DESIGN_history.md, section 14.)
 // ------------------------------------------------------------------------------------------------
 #ifdef ICPMI_NN_TIMING
 #define NN_TICK(i) do { __builtin_amdgcn_s_waitcnt(0); const long long t_ = clock64(); tacc[i] += t_ - tlast; tlast = t_; } while (0)
+// a workgroup matcher's accumulators (tacc[0..5] phase ticks, [6] passes, [7] pieces) -> IcpState::dbg, by thread 0 of a sample of the workgroups
+__device__ __forceinline__ void nn_timing_flush(IcpState* st, const long long (&tacc)[8], int st_iter, long long t_c0)
+{
+    if (threadIdx.x == 0 && st_iter > 1 && (blockIdx.x % 7) == 0) { // the heaviest of a sample of the steady launches' workgroups: its life and its pieces
+        atomicMax(&st->dbg[20], (unsigned long long)(clock64() - t_c0));
+        atomicMax(&st->dbg[21], (unsigned long long)tacc[7]);
+    }
+    if (threadIdx.x == 0 && (blockIdx.x % 61) == 0) { // a sample: same-address atomics from every wave would dominate
+        const int tb = st_iter > 1 ? 8 : 0; // steady launches in dbg[8..15], the first two in dbg[0..7]
+        for (int i = 0; i < 6; ++i) atomicAdd(&st->dbg[tb + i], (unsigned long long)tacc[i]);
+        atomicAdd(&st->dbg[tb + 6], (unsigned long long)tacc[6]);
+        atomicAdd(&st->dbg[tb + 7], 1ull);
+        atomicAdd(&st->dbg[16 + (st_iter > 1 ? 1 : 0)], (unsigned long long)tacc[7]);
+    }
+}
 #else
 #define NN_TICK(i) do { } while (0)
 #endif
@@ -384,20 +386,117 @@ __device__ __forceinline__ unsigned wave_incl_scan(unsigned v)
 }
 
 // ------------------------------------------------------------------------------------------------
+// Phase (1b) of the workgroup matchers (nn1_wg_kernel, nnk_wg_kernel): all NW waves, lane = query slot, WAVE = ROW GROUP (rows w, w + NW,
+// ... of the 3 x 3 block).  wg_row_setup reads the record wave 0 left in LDS (qrec: point, w = level bits; qaux: squared pruning radius,
+// flags 1 = searching, 2 = own row only); wg_rows_to_pieces looks the rows up and cuts them into the workgroup's piece list.
+// ------------------------------------------------------------------------------------------------
+struct RowSetup {
+    GridParams g;
+    const gunsigned* cs; // (global address space: rebuilt from integers, it would be read through the flat path)
+    CellPos c;
+    float x, rub2;
+    bool run, pre;
+};
+__device__ __forceinline__ RowSetup wg_row_setup(const uint4* ltab, const float4* qrec, const float2* qaux, int slot)
+{
+    const float4 qr = qrec[slot];
+    const float2 qa = qaux[slot];
+    const int lv = __float_as_int(qr.w);
+    const int fl = __float_as_int(qa.y);
+    RowSetup s;
+    s.g = level_grid(ltab, lv);
+    s.cs = level_cs(ltab, lv);
+    s.c = cell_pos(qr.x, qr.y, qr.z, s.g);
+    s.x = qr.x; s.rub2 = qa.x;
+    s.run = (fl & 1) != 0; s.pre = (fl & 2) != 0;
+    return s;
+}
+// pieces[]: {position of the first candidate in its level array, count << 8 | query slot}, CAP of them (>= 9 Q: one piece per row always
+// fits); s_total[2]: the piece count of either round, zeroed by wave 0 in (1a).  Contains one workgroup barrier per round.
+template <int NW, int NR, int Q, int CAP, int PLB>
+__device__ __forceinline__ void wg_rows_to_pieces(const RowSetup& s, uint2* pieces, unsigned* s_total, int slot, int wave, int lane)
+{
+    const GridParams& g = s.g;
+    __builtin_assume(wave >= 0 && wave < NW); // (said here, the row -> (dy, dz) arithmetic below is compiled knowing it, as it was inside the kernels)
+    // row ranges: branch-free so that all 2 NR loads of a lane leave together (unreached rows read cs[0] twice)
+    unsigned rs[NR], rn[NR];
+    {
+        unsigned ia[NR], ib[NR];
+#pragma unroll
+        for (int sl = 0; sl < NR; ++sl) {
+            const int rr = wave + sl * NW; // wave-uniform
+            const int dy = (rr % 3) - 1, dz = (rr / 3) - 1;
+            bool reach = s.run && rr < 9 && (!s.pre || rr == 4);
+            int xa, xb;
+            reach = clip_row_x(s.c, g, s.x, dy, dz, s.rub2, xa, xb) && reach;
+            const int y = s.c.cy + dy, z = s.c.cz + dz;
+            xa = xa < 0 ? 0 : xa;
+            xb = xb > g.nx - 1 ? g.nx - 1 : xb;
+            reach = reach && y >= 0 && y < g.ny && z >= 0 && z < g.nz && xa <= xb;
+            const int rowbase = (z * g.ny + y) * g.nx;
+            ia[sl] = reach ? (unsigned)(rowbase + xa) : 0u;
+            ib[sl] = reach ? (unsigned)(rowbase + xb + 1) : 0u;
+        }
+#pragma unroll
+        for (int sl = 0; sl < NR; ++sl) { rs[sl] = s.cs[ia[sl]]; rn[sl] = s.cs[ib[sl]]; }
+#pragma unroll
+        for (int sl = 0; sl < NR; ++sl) rn[sl] -= rs[sl]; // 0 for unreached rows (both loads hit cs[0])
+    }
+    // pieces: length 2^PLB; a lane's pieces start at the wave's exclusive prefix (DPP scan) behind the wave's share of the list
+    // (one LDS atomic per wave).  If the workgroup's pieces overflow the list (dense cells, degenerate maps), everybody
+    // repeats the count with pieces long enough to fit.
+    int plb = PLB;
+    unsigned base = 0;
+#pragma unroll 1
+    for (int round = 0; round < 2; ++round) {
+        unsigned np = 0;
+#pragma unroll
+        for (int sl = 0; sl < NR; ++sl) np += (rn[sl] + ((1u << plb) - 1u)) >> plb;
+        const unsigned incl = wave_incl_scan(np);
+        const unsigned wtot = (unsigned)__builtin_amdgcn_readlane((int)incl, 63);
+        unsigned wb = 0;
+        if (lane == 63 && wtot) wb = atomicAdd(&s_total[round], wtot);
+        wb = (unsigned)__builtin_amdgcn_readlane((int)wb, 63);
+        base = wb + incl - np;
+        __syncthreads();
+        const unsigned tot = s_total[round];
+        if (tot <= (unsigned)CAP) break;
+        // sum over rows of ceil(c / 2^(plb + k)) <= tot / 2^k + (number of rows <= 9 Q)
+        int k = 1;
+        while ((tot >> k) > (unsigned)(CAP - 9 * Q)) ++k;
+        plb += k;
+    }
+#pragma unroll
+    for (int sl = 0; sl < NR; ++sl) {
+        unsigned st = rs[sl], c = rn[sl];
+        while (c) {
+            const unsigned t = c < (1u << plb) ? c : (1u << plb);
+            pieces[base++] = make_uint2(st, (t << 8) | (unsigned)slot);
+            st += t; c -= t;
+        }
+    }
+}
+
+// a result's packed place (position in its level | level << 28) -> position in level 0, what the callers are given
+__device__ __forceinline__ int resolve_level0(const uint4* ltab, unsigned packed_sidx)
+{
+    const unsigned lv = packed_sidx >> 28, pos = packed_sidx & 0x0fffffffu;
+    return lv == 0 ? (int)pos : (int)level_pos0<const unsigned*>(ltab, (int)lv)[pos];
+}
+
+// ------------------------------------------------------------------------------------------------
 // nn1_wg_kernel: the wave-queue scheme with the roles given to DIFFERENT NUMBERS OF WAVES.
-// (r4 carried an FSOLVE variant -- the previous iteration's solve in every workgroup's prologue, three launches per iteration.  r5 moved its
-//  loads into the query round trip and measured again: fixed-count point-to-point +1.8 %, point-to-plane -1.8 %, checked 6-iteration
-//  registrations -4 ... -6 %; the kernel needed scratch memory for the solver's cold paths.  Removed: DESIGN 13.3.)  The per-query set-up is cheapest
+// (The FSOLVE variant it once carried: DESIGN_history.md, section 14.)  The per-query set-up is cheapest
 // with one lane per query (every instruction of it then serves 64 queries; with LPQ lanes per query it is paid LPQ times), but
 // one wave that also looks up the nine rows and works off the ~330 pieces of its 64 queries lives for ten dependent steps --
 // and at 100 k queries there are only 1.5 such waves per SIMD to hide that behind.  Here a workgroup of four waves owns 64
 // queries:
 //   (1a) wave 0, lane per query: transform, seed, level, pruning radius -> LDS record (the other waves are parked at the
 //        barrier and issue nothing);
-//   (1b) all four waves, lane = query, WAVE = ROW GROUP (rows w, w + 4, w + 8 of the 3 x 3 block): row ranges, pieces;
+//   (1b) all four waves, lane = query, WAVE = ROW GROUP (rows w, w + 4, w + 8 of the 3 x 3 block): row ranges, pieces
+//        (wg_row_setup / wg_rows_to_pieces above, shared with nnk_wg_kernel);
 //   (2)  all four waves, lane per piece (one or two steps for 64 queries);
 //   (3)  wave 0 decides and stores.
-// Same keys and exactness rules as the r1 - r3 kernels it replaced: same bits.
 // ------------------------------------------------------------------------------------------------
 // r6: seven waves per SIMD = seven workgroups per CU = 1 792 resident workgroups: the 1 568 of a 100 k-query launch are all resident at once (at six, 32 of
 // them waited for a slot: +0.8 ... 2.4 us per launch).  72 VGPRs without a spill since the query's point and its best-so-far moved into LDS (below);
@@ -469,9 +568,7 @@ __global__ __launch_bounds__(64 * NW) NN1_WAVES_ATTR void nn1_wg_kernel(const fl
 #endif
     const int wgs = (int)((((long long)n + Q - 1) / Q + 7) / 8 * 8);
     if ((int)blockIdx.x >= wgs) return;
-    // the workgroup's queries, XCD-aware order as nn1_ml_kernel: workgroup b runs on XCD b % 8; each XCD gets one contiguous eighth.
-    const int chunk = wgs >> 3;
-    const int lb = (blockIdx.x & 7) * chunk + (blockIdx.x >> 3);
+    const int lb = xcd_block(blockIdx.x, wgs); // the workgroup's queries
     const int slot = lane;
     const int qi = lb * Q + slot;
     const bool active = w0 && qi < n; // only wave 0 owns queries
@@ -504,7 +601,7 @@ __global__ __launch_bounds__(64 * NW) NN1_WAVES_ATTR void nn1_wg_kernel(const fl
     Cand best; best.key = ~0ull; best.sidx = -1; // sidx = position in its level | level << 28
     bool decided = !active;
     int lev0 = unseeded_lev;
-    if (w0) {   // seed: see nn1_ml_kernel -- the previous match bounds the answer; start at the first level whose block holds that ball
+    if (w0) {   // seed: the previous match bounds the answer; start at the first level whose block holds that ball
         int sp = -1;
         float4 qs = make_float4(0.f, 0.f, 0.f, 0.f);
         if (active && allow_self && st_iter > 0) {
@@ -515,13 +612,7 @@ __global__ __launch_bounds__(64 * NW) NN1_WAVES_ATTR void nn1_wg_kernel(const fl
         const float ub2 = sqdist3(p.x, p.y, p.z, qs.x, qs.y, qs.z);
         const float ub = sqrt_up(ub2);
         auto try_level = [&](int lev, const GridParams& gl) {
-            const float fx = (p.x - gl.ox) * gl.inv_cell, fy = (p.y - gl.oy) * gl.inv_cell, fz = (p.z - gl.oz) * gl.inv_cell;
-            float mfl = fminf(fx - floorf(fx), 1.0f - (fx - floorf(fx)));
-            mfl = fminf(mfl, fminf(fy - floorf(fy), 1.0f - (fy - floorf(fy))));
-            mfl = fminf(mfl, fminf(fz - floorf(fz), 1.0f - (fz - floorf(fz))));
-            if (!(mfl >= 0.f)) mfl = 0.f;
-            const float margin = (1.0f + mfl) * gl.cell - 2.0f * gl.slack;
-            if (want && ub * inv1e * 1.000001f <= margin) {
+            if (want && block_holds_ball(p.x, p.y, p.z, gl, ub * inv1e * 1.000001f)) {
                 lev0 = lev;
                 best.key = pack_key(ub2, __float_as_uint(qs.w));
                 best.sidx = sp; // level 0 position
@@ -560,8 +651,7 @@ __global__ __launch_bounds__(64 * NW) NN1_WAVES_ATTR void nn1_wg_kernel(const fl
                 prescan = run && !did_pre && (bk == ~0ull || (widepre && lev == 0));
                 float rub2 = INFINITY; // squared pruning radius (with slack), +inf = no pruning
                 if (!prescan && bk != ~0ull) {
-                    const float slack = __uint_as_float(ltab[4 * lv + 1].y);
-                    const float rub = sqrt_up(__uint_as_float((unsigned)(bk >> 32))) * inv1e * 1.000001f + slack;
+                    const float rub = sqrt_up(__uint_as_float((unsigned)(bk >> 32))) * inv1e * 1.000001f + level_grid(ltab, lv).slack;
                     rub2 = rub * rub;
                 }
                 reinterpret_cast<float*>(&qrec[slot])[3] = __int_as_float(lv);
@@ -573,103 +663,9 @@ __global__ __launch_bounds__(64 * NW) NN1_WAVES_ATTR void nn1_wg_kernel(const fl
         NN_TICK(1);
         // ---- (1b) all waves: lane = query, wave = row group
         {
-            float mf, g_cell, g_slack;
-            bool covers;
-            const float4 qr = qrec[slot];
-            const float2 qa = qaux[slot];
-            const int lv = __float_as_int(qr.w);
-            const int fl = __float_as_int(qa.y);
-            const bool qrun = (fl & 1) != 0, qpre = (fl & 2) != 0;
-            const float rub2 = qa.x;
-            GridParams g;
-            const gunsigned* __restrict__ cs; // (global address space: rebuilt from integers, it would be read through the flat path)
-            {
-                const uint4 a = ltab[4 * lv], b = ltab[4 * lv + 1], c2 = ltab[4 * lv + 2], d = ltab[4 * lv + 3];
-                g.ox = __uint_as_float(a.x); g.oy = __uint_as_float(a.y); g.oz = __uint_as_float(a.z); g.cell = __uint_as_float(a.w);
-                g.inv_cell = __uint_as_float(b.x); g.slack = __uint_as_float(b.y); g.nx = (int)b.z; g.ny = (int)b.w;
-                g.nz = (int)c2.x; g.ncells = (int)c2.y;
-                cs = reinterpret_cast<const gunsigned*>(((unsigned long long)d.y << 32) | d.x);
-            }
-            const float fx = (qr.x - g.ox) * g.inv_cell, fy = (qr.y - g.oy) * g.inv_cell, fz = (qr.z - g.oz) * g.inv_cell;
-            const float flx = floorf(fx), fly = floorf(fy), flz = floorf(fz);
-            const int cx = (int)fminf(fmaxf(flx, -1.0e6f), 1.0e6f);
-            const int cy = (int)fminf(fmaxf(fly, -1.0e6f), 1.0e6f);
-            const int cz = (int)fminf(fmaxf(flz, -1.0e6f), 1.0e6f);
-            mf = fminf(fx - flx, 1.0f - (fx - flx));
-            mf = fminf(mf, fminf(fy - fly, 1.0f - (fy - fly)));
-            mf = fminf(mf, fminf(fz - flz, 1.0f - (fz - flz)));
-            if (!(mf >= 0.f)) mf = 0.f;
-            g_cell = g.cell; g_slack = g.slack;
-            covers = cx - 1 <= 0 && cx + 1 >= g.nx - 1 && cy - 1 <= 0 && cy + 1 >= g.ny - 1 && cz - 1 <= 0 && cz + 1 >= g.nz - 1;
-            if (w0) { const float margin = fmaxf((1.0f + mf) * g_cell - g_slack, 0.f); qdec[slot] = make_float2(margin * margin, covers ? 1.f : 0.f); } // (not carried in registers across the piece steps)
-            // row ranges: branch-free so that all 2 NR loads of a lane leave together (unreached rows read cs[0] twice)
-            unsigned rs[NR], rn[NR];
-            {
-                const float ylo = (fy - fly) * g.cell, yhi = (1.0f - (fy - fly)) * g.cell;
-                const float zlo = (fz - flz) * g.cell, zhi = (1.0f - (fz - flz)) * g.cell;
-                unsigned ia[NR], ib[NR];
-#pragma unroll
-                for (int sl = 0; sl < NR; ++sl) {
-                    const int rr = wave + sl * NW; // wave-uniform
-                    const int dy = (rr % 3) - 1, dz = (rr / 3) - 1;
-                    bool reach = qrun && rr < 9 && (!qpre || rr == 4);
-                    const float ddy = dy == 0 ? 0.f : (dy < 0 ? ylo : yhi);
-                    const float ddz = dz == 0 ? 0.f : (dz < 0 ? zlo : zhi);
-                    const float rem2 = rub2 - (ddy * ddy + ddz * ddz); // +inf without a bound
-                    reach = reach && rem2 >= 0.f;
-                    int xa = cx - 1, xb = cx + 1;
-                    if (rem2 != INFINITY) {
-                        const float rem = sqrt_up(fmaxf(rem2, 0.f));
-                        const int xl = (int)fmaxf(floorf((qr.x - rem - g.ox) * g.inv_cell), -1.0e6f);
-                        const int xh = (int)fminf(floorf((qr.x + rem - g.ox) * g.inv_cell), 1.0e6f);
-                        xa = xl > xa ? xl : xa;
-                        xb = xh < xb ? xh : xb;
-                    }
-                    const int y = cy + dy, z = cz + dz;
-                    xa = xa < 0 ? 0 : xa;
-                    xb = xb > g.nx - 1 ? g.nx - 1 : xb;
-                    reach = reach && y >= 0 && y < g.ny && z >= 0 && z < g.nz && xa <= xb;
-                    const int rowbase = (z * g.ny + y) * g.nx;
-                    ia[sl] = reach ? (unsigned)(rowbase + xa) : 0u;
-                    ib[sl] = reach ? (unsigned)(rowbase + xb + 1) : 0u;
-                }
-#pragma unroll
-                for (int sl = 0; sl < NR; ++sl) { rs[sl] = cs[ia[sl]]; rn[sl] = cs[ib[sl]]; }
-#pragma unroll
-                for (int sl = 0; sl < NR; ++sl) rn[sl] -= rs[sl]; // 0 for unreached rows (both loads hit cs[0])
-            }
-            // pieces: length 8; a lane's pieces start at the wave's exclusive prefix (DPP scan) behind the wave's share of the list
-            // (one LDS atomic per wave).  If the workgroup's pieces overflow the list (dense cells, degenerate maps), everybody
-            // repeats the count with pieces long enough to fit.
-            int plb = PLB;
-            unsigned base = 0;
-            for (int round = 0; round < 2; ++round) {
-                unsigned np = 0;
-#pragma unroll
-                for (int sl = 0; sl < NR; ++sl) np += (rn[sl] + ((1u << plb) - 1u)) >> plb;
-                const unsigned incl = wave_incl_scan(np);
-                const unsigned wtot = (unsigned)__builtin_amdgcn_readlane((int)incl, 63);
-                unsigned wb = 0;
-                if (lane == 63 && wtot) wb = atomicAdd(&s_total[round], wtot);
-                wb = (unsigned)__builtin_amdgcn_readlane((int)wb, 63);
-                base = wb + incl - np;
-                __syncthreads();
-                const unsigned tot = s_total[round];
-                if (tot <= (unsigned)CAP) break;
-                // sum over rows of ceil(c / 2^(plb + k)) <= tot / 2^k + (number of rows <= 9 Q)
-                int k = 1;
-                while ((tot >> k) > (unsigned)(CAP - 9 * Q)) ++k;
-                plb += k;
-            }
-#pragma unroll
-            for (int sl = 0; sl < NR; ++sl) {
-                unsigned s = rs[sl], c = rn[sl];
-                while (c) {
-                    const unsigned t = c < (1u << plb) ? c : (1u << plb);
-                    pieces[base++] = make_uint2(s, (t << 8) | (unsigned)slot);
-                    s += t; c -= t;
-                }
-            }
+            const RowSetup rs = wg_row_setup(ltab, qrec, qaux, slot);
+            if (w0) { const float margin = block_margin(rs.c.mf, rs.g.cell, rs.g.slack); qdec[slot] = make_float2(margin * margin, block_covers(rs.c, rs.g) ? 1.f : 0.f); } // (not carried in registers across the piece steps)
+            wg_rows_to_pieces<NW, NR, Q, CAP, PLB>(rs, pieces, s_total, slot, wave, lane);
         }
         __syncthreads();
         const unsigned total = s_total[1] ? s_total[1] : s_total[0];
@@ -686,8 +682,7 @@ __global__ __launch_bounds__(64 * NW) NN1_WAVES_ATTR void nn1_wg_kernel(const fl
             const unsigned qsl = e.y & 255u, cnt = has ? e.y >> 8 : 0u;
             const float4 qr = qrec[qsl];
             // (global address space: a pointer rebuilt from integers would otherwise be loaded through the flat path)
-            const uint4 lt2 = ltab[4 * __float_as_int(qr.w) + 2];
-            const gfloat4* mp = reinterpret_cast<const gfloat4*>((((unsigned long long)lt2.w << 32) | lt2.z) + (unsigned long long)e.x * 16ull);
+            const gfloat4* mp = level_pts(ltab, __float_as_int(qr.w)) + e.x;
             unsigned long long kb = ~0ull;
             unsigned pb = 0;
             float bx = 0.f, by = 0.f, bz = 0.f; // the best candidate's coordinates ride along (a reload would be one more trip)
@@ -744,15 +739,7 @@ __global__ __launch_bounds__(64 * NW) NN1_WAVES_ATTR void nn1_wg_kernel(const fl
     if (writer) {
         int bs = -1;
         float4 mpt = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (found) {
-            const unsigned lvb = (unsigned)best.sidx >> 28, pos = (unsigned)best.sidx & 0x0fffffffu;
-            if (lvb == 0) bs = (int)pos;
-            else {
-                const uint4 d = ltab[4 * lvb + 3];
-                bs = (int)reinterpret_cast<const unsigned*>(((unsigned long long)d.w << 32) | d.z)[pos];
-            }
-            mpt = qpt[slot];
-        }
+        if (found) { bs = resolve_level0(ltab, (unsigned)best.sidx); mpt = qpt[slot]; }
         st_stream(out_sidx + orig, bs);
         st_stream(out_d2 + orig, bd2);
         if (match_pt) st_stream(match_pt + orig, make_float4(mpt.x, mpt.y, mpt.z, __uint_as_float((unsigned)(best.key & 0xffffffffull))));
@@ -767,16 +754,8 @@ __global__ __launch_bounds__(64 * NW) NN1_WAVES_ATTR void nn1_wg_kernel(const fl
     }
 #ifdef ICPMI_NN_TIMING
     NN_TICK(5);
-    if (threadIdx.x == 0 && st_iter > 1 && (blockIdx.x % 7) == 0) { // the heaviest of a sample of the steady launches' workgroups: its life and its pieces
-        atomicMax(&st->dbg[20], (unsigned long long)(clock64() - t_c0));
-        atomicMax(&st->dbg[21], (unsigned long long)tacc[7]);
-    }
-    if (threadIdx.x == 0 && (blockIdx.x % 61) == 0) { // a sample: same-address atomics from every wave would dominate
-        const int tb = st_iter > 1 ? 8 : 0; // steady launches in dbg[8..15], the first two in dbg[0..7]
-        for (int i = 0; i < 6; ++i) atomicAdd(&st->dbg[tb + i], (unsigned long long)tacc[i]);
-        atomicAdd(&st->dbg[tb + 6], (unsigned long long)tacc[6]);
-        atomicAdd(&st->dbg[tb + 7], 1ull);
-        atomicAdd(&st->dbg[16 + (st_iter > 1 ? 1 : 0)], (unsigned long long)tacc[7]);
+    nn_timing_flush(st, tacc, st_iter, t_c0);
+    if (threadIdx.x == 0 && (blockIdx.x % 61) == 0) {
         atomicAdd(&st->dbg[22], (unsigned long long)(clock64() - t_c0));       // shader clock ticks of this workgroup's life
         atomicAdd(&st->dbg[23], (unsigned long long)(wall_clock64() - t_w0));  // ... and 100 MHz constant-clock ticks of the same
     }
@@ -785,7 +764,7 @@ __global__ __launch_bounds__(64 * NW) NN1_WAVES_ATTR void nn1_wg_kernel(const fl
 
 // ------------------------------------------------------------------------------------------------
 // 2 <= k <= 8 over the grid pyramid: the k = 1 scheme with a sorted list per lane.  G lanes serve one
-// query; candidates of a level pass are dealt to the lanes as in nn1_ml_kernel, every lane keeps the
+// query; candidates of a level pass are dealt round-robin to the lanes of the group, every lane keeps the
 // KMAX best of ITS candidates; after a pass the group merges by KMAX rounds of "extract the group
 // minimum" (shuffle butterfly) into a list replicated in all lanes, whose k-th key bounds the next
 // pass (rows / cells beyond it are skipped, candidates beyond it dropped, candidates equal to a merged
@@ -808,9 +787,7 @@ __global__ __launch_bounds__(NN_BLOCK) void nnk_ml_kernel(const float4* __restri
     __shared__ uint4 ltab[ICPMI_MAXLEV * 4];
     if (threadIdx.x < ICPMI_MAXLEV * 4) ltab[threadIdx.x] = ltab_g[threadIdx.x];
     const bool allow_self = allow_self_i != 0;
-    const int chunk = gridDim.x >> 3;
-    const int lb = (blockIdx.x & 7) * chunk + (blockIdx.x >> 3);
-    const int tid = lb * NN_BLOCK + threadIdx.x;
+    const int tid = xcd_block(blockIdx.x, gridDim.x) * NN_BLOCK + threadIdx.x;
     const int qi = tid / G;
     const int sub = tid % G;
     const bool active = qi < n;
@@ -895,7 +872,7 @@ __global__ __launch_bounds__(NN_BLOCK) void nnk_ml_kernel(const float4* __restri
             if (sub < k) {
                 const int sp = out_sidx[(size_t)k * orig + sub];
                 if (sp >= 0) {
-                    const float4 q = reinterpret_cast<const float4*>(((unsigned long long)ltab[2].w << 32) | ltab[2].z)[sp];
+                    const float4 q = level_pts<const float4*>(ltab, 0)[sp];
                     pk[0] = pack_key(sqdist3(p.x, p.y, p.z, q.x, q.y, q.z), __float_as_uint(q.w));
                     ps[0] = sp;
                 }
@@ -904,7 +881,7 @@ __global__ __launch_bounds__(NN_BLOCK) void nnk_ml_kernel(const float4* __restri
             for (int j = sub; j < k; j += G) {
                 const int sp = out_sidx[(size_t)k * orig + j];
                 if (sp >= 0) {
-                    const float4 q = reinterpret_cast<const float4*>(((unsigned long long)ltab[2].w << 32) | ltab[2].z)[sp];
+                    const float4 q = level_pts<const float4*>(ltab, 0)[sp];
                     offer(pack_key(sqdist3(p.x, p.y, p.z, q.x, q.y, q.z), __float_as_uint(q.w)), sp);
                 }
             }
@@ -913,17 +890,7 @@ __global__ __launch_bounds__(NN_BLOCK) void nnk_ml_kernel(const float4* __restri
     if (seeded & 1) {
         merge();
         if (bound != ~0ull) { // first level whose block contains the ball of the k-th seed
-            const float ub = sqrtf(__uint_as_float((unsigned)(bound >> 32))) * inv1e * 1.000001f;
-            for (; lev < nlev - 1; ++lev) {
-                const uint4 a = ltab[4 * lev], b = ltab[4 * lev + 1];
-                const float inv = __uint_as_float(b.x);
-                const float fx = (p.x - __uint_as_float(a.x)) * inv, fy = (p.y - __uint_as_float(a.y)) * inv, fz = (p.z - __uint_as_float(a.z)) * inv;
-                float mfl = fminf(fx - floorf(fx), 1.0f - (fx - floorf(fx)));
-                mfl = fminf(mfl, fminf(fy - floorf(fy), 1.0f - (fy - floorf(fy))));
-                mfl = fminf(mfl, fminf(fz - floorf(fz), 1.0f - (fz - floorf(fz))));
-                if (!(mfl >= 0.f)) mfl = 0.f;
-                if (ub <= (1.0f + mfl) * __uint_as_float(a.w) - 2.0f * __uint_as_float(b.y)) break;
-            }
+            lev = level_holding_ball(ltab, nlev, 0, p.x, p.y, p.z, sqrtf(__uint_as_float((unsigned)(bound >> 32))) * inv1e * 1.000001f);
         }
     }
 
@@ -936,26 +903,13 @@ __global__ __launch_bounds__(NN_BLOCK) void nnk_ml_kernel(const float4* __restri
     // the unseeded one, 115 us)
     if ((seeded & 2) && lev > 0) { lev = 0; rowonly = true; }
     while (lev < nlev && !decided) {
-        GridParams g;
-        const float4* __restrict__ map;
-        const unsigned* __restrict__ cs;
-        {
-            const uint4 a = ltab[4 * lev], b = ltab[4 * lev + 1], c2 = ltab[4 * lev + 2], d = ltab[4 * lev + 3];
-            g.ox = __uint_as_float(a.x); g.oy = __uint_as_float(a.y); g.oz = __uint_as_float(a.z); g.cell = __uint_as_float(a.w);
-            g.inv_cell = __uint_as_float(b.x); g.slack = __uint_as_float(b.y); g.nx = (int)b.z; g.ny = (int)b.w;
-            g.nz = (int)c2.x; g.ncells = (int)c2.y;
-            map = reinterpret_cast<const float4*>(((unsigned long long)c2.w << 32) | c2.z);
-            cs = reinterpret_cast<const unsigned*>(((unsigned long long)d.y << 32) | d.x);
-        }
-        const float fx = (p.x - g.ox) * g.inv_cell, fy = (p.y - g.oy) * g.inv_cell, fz = (p.z - g.oz) * g.inv_cell;
-        const float flx = floorf(fx), fly = floorf(fy), flz = floorf(fz);
-        const int cx = (int)fminf(fmaxf(flx, -1.0e6f), 1.0e6f);
-        const int cy = (int)fminf(fmaxf(fly, -1.0e6f), 1.0e6f);
-        const int cz = (int)fminf(fmaxf(flz, -1.0e6f), 1.0e6f);
-        float mf = fminf(fx - flx, 1.0f - (fx - flx));
-        mf = fminf(mf, fminf(fy - fly, 1.0f - (fy - fly)));
-        mf = fminf(mf, fminf(fz - flz, 1.0f - (fz - flz)));
-        if (!(mf >= 0.f)) mf = 0.f;
+        // (this kernel has always read the level arrays through generic pointers, and taken the IEEE sqrtf where the workgroup matchers take
+        //  sqrt_up: its row clip below is clip_row_x's but for that rounding, so it stays written out)
+        const GridParams g = level_grid(ltab, lev);
+        const float4* __restrict__ map = level_pts<const float4*>(ltab, lev);
+        const unsigned* __restrict__ cs = level_cs<const unsigned*>(ltab, lev);
+        const CellPos c = cell_pos(p.x, p.y, p.z, g);
+        const int cx = c.cx, cy = c.cy, cz = c.cz;
 
         float rub2 = INFINITY;
         if (bound != ~0ull) {
@@ -964,8 +918,8 @@ __global__ __launch_bounds__(NN_BLOCK) void nnk_ml_kernel(const float4* __restri
         }
         unsigned rs[NR], rn[NR];
         {
-            const float ylo = (fy - fly) * g.cell, yhi = (1.0f - (fy - fly)) * g.cell;
-            const float zlo = (fz - flz) * g.cell, zhi = (1.0f - (fz - flz)) * g.cell;
+            const float ylo = (c.fy - c.fly) * g.cell, yhi = (1.0f - (c.fy - c.fly)) * g.cell;
+            const float zlo = (c.fz - c.flz) * g.cell, zhi = (1.0f - (c.fz - c.flz)) * g.cell;
 #pragma unroll
             for (int sl = 0; sl < NR; ++sl) {
                 const int rr = sub + sl * G;
@@ -1028,10 +982,10 @@ __global__ __launch_bounds__(NN_BLOCK) void nnk_ml_kernel(const float4* __restri
         }
         merge();
         if (rowonly) { rowonly = false; continue; }
-        const float margin = fmaxf((1.0f + mf) * g.cell - g.slack, 0.f);
+        const float margin = block_margin(c.mf, g.cell, g.slack);
         const float m2 = margin * margin;
         const float kd2 = __uint_as_float((unsigned)(bound >> 32));
-        const bool covers = cx - 1 <= 0 && cx + 1 >= g.nx - 1 && cy - 1 <= 0 && cy + 1 >= g.ny - 1 && cz - 1 <= 0 && cz + 1 >= g.nz - 1;
+        const bool covers = block_covers(c, g);
         decided = (bound != ~0ull && kd2 <= m2 * err2) || m2 > maxr2 || covers;
         ++lev;
     }
@@ -1047,14 +1001,8 @@ __global__ __launch_bounds__(NN_BLOCK) void nnk_ml_kernel(const float4* __restri
         {
             float d2 = __uint_as_float((unsigned)(key >> 32));
             int bs = -1;
-            if (key != ~0ull && d2 <= r2q) {
-                const unsigned lv = (unsigned)sx >> 28, pos = (unsigned)sx & 0x0fffffffu;
-                if (lv == 0) bs = (int)pos;
-                else {
-                    const uint4 d = ltab[4 * lv + 3];
-                    bs = (int)reinterpret_cast<const unsigned*>(((unsigned long long)d.w << 32) | d.z)[pos];
-                }
-            } else d2 = INFINITY;
+            if (key != ~0ull && d2 <= r2q) bs = resolve_level0(ltab, (unsigned)sx);
+            else d2 = INFINITY;
             out_sidx[(size_t)k * orig + jj] = bs;
             out_d2[(size_t)k * orig + jj] = d2;
         }
@@ -1072,7 +1020,7 @@ __global__ __launch_bounds__(NN_BLOCK) void nnk_ml_kernel(const float4* __restri
 //   (1a) wave 0, lane per query: keeps the query's sorted k-list in registers (seeded with the previous iteration's k matches
 //        under the current transform), publishes the level, the pruning radius and the ACCEPT BOUND (k-th key held, else the
 //        key of maxr2);
-//   (1b) all waves, lane = query, wave = row group: row ranges -> pieces of 8 candidates;
+//   (1b) all waves, lane = query, wave = row group: row ranges -> pieces of 8 candidates (wg_row_setup / wg_rows_to_pieces);
 //   (2)  all waves, lane per piece: candidates with key <= bound go to the query's list in LDS (one LDS atomic per piece);
 //   (3)  wave 0 merges its query's list into the k-list (the same point seen again is dropped by its key) and decides.
 // A list that overflows (CAPQ entries) is not lost work: the k-list of what DID arrive tightens the bound, and the pass is
@@ -1080,9 +1028,8 @@ __global__ __launch_bounds__(NN_BLOCK) void nnk_ml_kernel(const float4* __restri
 // exactness rule per level and the output are those of nnk_ml_kernel: the same k points in the same order.
 // Measured (r3, knn 6, 100 k queries, 1 M points): steady launches 37.3 -> 25 us.  NOT for wide bounds: a launch whose seeds
 // moved far (iteration 1) overflows the lists and repeats passes (172 us here; nnk_ml_kernel with its own-row pass first: 75 us),
-// the unseeded launch takes 270 us against 115 us -- the launcher keeps nnk_ml_kernel for iterations 0 and 1.  Level 0 of the fused quantile selection
-// from this kernel's tail (k atomics per query on the fine bins) made a launch 55 us; the stand-alone builder (12.5 us), which
-// combines 4096 matches in LDS before it touches memory, stays.
+// the unseeded launch takes 270 us against 115 us -- the launcher keeps nnk_ml_kernel for iterations 0 and 1.
+// (Level 0 of the fused selection built in this kernel's tail, the variant the speculative window below replaced: DESIGN_history.md, section 14.)
 // ------------------------------------------------------------------------------------------------
 #ifndef NNK_WG_WAVES
 #define NNK_WG_WAVES 5
@@ -1122,8 +1069,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KMAX <= 8 ?
     const bool w0 = wave == 0;
     const int wgs = (int)((((long long)n + Q - 1) / Q + 7) / 8 * 8);
     if ((int)blockIdx.x >= wgs) return;
-    const int chunk = wgs >> 3;
-    const int lb = (blockIdx.x & 7) * chunk + (blockIdx.x >> 3);
+    const int lb = xcd_block(blockIdx.x, wgs);
     const int slot = lane;
     const int qi = lb * Q + slot;
     const bool active = w0 && qi < n;
@@ -1174,21 +1120,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KMAX <= 8 ?
         return v;
     };
     const unsigned long long maxkey = pack_key(maxr2, 0xffffffffu);
-    // first level >= from whose 3 x 3 x 3 block contains the ball of this key's distance around the query
+    // first level >= from whose 3 x 3 x 3 block contains the ball of this key's distance around the query (the table is read from global
+    // memory here: wave 0 asks before the barrier that makes the LDS copy visible)
     auto level_for = [&](unsigned long long b, int from) {
-        const float ub = sqrtf(__uint_as_float((unsigned)(b >> 32))) * inv1e * 1.000001f;
-        int l = from;
-        for (; l < nlev - 1; ++l) {
-            const uint4 a = ltab_g[4 * l], bb = ltab_g[4 * l + 1];
-            const float inv = __uint_as_float(bb.x);
-            const float fx = (p.x - __uint_as_float(a.x)) * inv, fy = (p.y - __uint_as_float(a.y)) * inv, fz = (p.z - __uint_as_float(a.z)) * inv;
-            float mfl = fminf(fx - floorf(fx), 1.0f - (fx - floorf(fx)));
-            mfl = fminf(mfl, fminf(fy - floorf(fy), 1.0f - (fy - floorf(fy))));
-            mfl = fminf(mfl, fminf(fz - floorf(fz), 1.0f - (fz - floorf(fz))));
-            if (!(mfl >= 0.f)) mfl = 0.f;
-            if (ub <= (1.0f + mfl) * __uint_as_float(a.w) - 2.0f * __uint_as_float(bb.y)) break;
-        }
-        return l;
+        return level_holding_ball(ltab_g, nlev, from, p.x, p.y, p.z, sqrtf(__uint_as_float((unsigned)(b >> 32))) * inv1e * 1.000001f);
     };
     bool widepre = false;
     int lev = 0;
@@ -1199,7 +1134,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KMAX <= 8 ?
         if (Tptr) p = xf_point(Tptr, r.x, r.y, r.z, r.w);
         else p = make_float3(r.x, r.y, r.z);
         if (active && st->iter > 0) { // the previous k matches under the current transform (all loads first, then the insertions)
-            const gfloat4* l0 = reinterpret_cast<const gfloat4*>(((unsigned long long)ltab_g[2].w << 32) | ltab_g[2].z);
+            const gfloat4* l0 = level_pts(ltab_g, 0);
             int sp[KMAX];
             vf4 sq[KMAX];
 #pragma unroll
@@ -1251,7 +1186,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KMAX <= 8 ?
                 const unsigned long long acc = b < maxkey ? b : maxkey;
                 float rub2 = INFINITY;
                 if (!prescan && acc < 0x7f80000000000000ull) { // (a finite radius: the k-th held, or the matcher's maxDist)
-                    const float slack = __uint_as_float(ltab[4 * lv + 1].y);
+                    const float slack = level_grid(ltab, lv).slack;
                     // (the k-th held shrinks by 1 / (1 + epsilon); the matcher's maxDist does not: libnabo tests `new_rd <= maxRadius2` as it is)
                     float rad = sqrt_up(__uint_as_float((unsigned)(acc >> 32)));
                     if (b != ~0ull) rad = fminf(rad, sqrt_up(__uint_as_float((unsigned)(b >> 32))) * inv1e);
@@ -1267,100 +1202,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KMAX <= 8 ?
         __syncthreads();
         if (!s_any) break;
         NN_TICK(1);
-        // ---- (1b) all waves: lane = query, wave = row group (as nn1_wg_kernel)
-        float mf, g_cell, g_slack;
-        bool covers;
-        {
-            const float4 qr = qrec[slot];
-            const float2 qa = qaux[slot];
-            const int lv = __float_as_int(qr.w);
-            const int fl = __float_as_int(qa.y);
-            const bool qrun = (fl & 1) != 0, qpre = (fl & 2) != 0;
-            const float rub2 = qa.x;
-            GridParams g;
-            const gunsigned* __restrict__ cs;
-            {
-                const uint4 a = ltab[4 * lv], b = ltab[4 * lv + 1], c2 = ltab[4 * lv + 2], d = ltab[4 * lv + 3];
-                g.ox = __uint_as_float(a.x); g.oy = __uint_as_float(a.y); g.oz = __uint_as_float(a.z); g.cell = __uint_as_float(a.w);
-                g.inv_cell = __uint_as_float(b.x); g.slack = __uint_as_float(b.y); g.nx = (int)b.z; g.ny = (int)b.w;
-                g.nz = (int)c2.x; g.ncells = (int)c2.y;
-                cs = reinterpret_cast<const gunsigned*>(((unsigned long long)d.y << 32) | d.x);
-            }
-            const float fx = (qr.x - g.ox) * g.inv_cell, fy = (qr.y - g.oy) * g.inv_cell, fz = (qr.z - g.oz) * g.inv_cell;
-            const float flx = floorf(fx), fly = floorf(fy), flz = floorf(fz);
-            const int cx = (int)fminf(fmaxf(flx, -1.0e6f), 1.0e6f);
-            const int cy = (int)fminf(fmaxf(fly, -1.0e6f), 1.0e6f);
-            const int cz = (int)fminf(fmaxf(flz, -1.0e6f), 1.0e6f);
-            mf = fminf(fx - flx, 1.0f - (fx - flx));
-            mf = fminf(mf, fminf(fy - fly, 1.0f - (fy - fly)));
-            mf = fminf(mf, fminf(fz - flz, 1.0f - (fz - flz)));
-            if (!(mf >= 0.f)) mf = 0.f;
-            g_cell = g.cell; g_slack = g.slack;
-            covers = cx - 1 <= 0 && cx + 1 >= g.nx - 1 && cy - 1 <= 0 && cy + 1 >= g.ny - 1 && cz - 1 <= 0 && cz + 1 >= g.nz - 1;
-            unsigned rs[NR], rn[NR];
-            {
-                const float ylo = (fy - fly) * g.cell, yhi = (1.0f - (fy - fly)) * g.cell;
-                const float zlo = (fz - flz) * g.cell, zhi = (1.0f - (fz - flz)) * g.cell;
-                unsigned ia[NR], ib[NR];
-#pragma unroll
-                for (int sl = 0; sl < NR; ++sl) {
-                    const int rr = wave + sl * NW;
-                    const int dy = (rr % 3) - 1, dz = (rr / 3) - 1;
-                    bool reach = qrun && rr < 9 && (!qpre || rr == 4);
-                    const float ddy = dy == 0 ? 0.f : (dy < 0 ? ylo : yhi);
-                    const float ddz = dz == 0 ? 0.f : (dz < 0 ? zlo : zhi);
-                    const float rem2 = rub2 - (ddy * ddy + ddz * ddz);
-                    reach = reach && rem2 >= 0.f;
-                    int xa = cx - 1, xb = cx + 1;
-                    if (rem2 != INFINITY) {
-                        const float rem = sqrt_up(fmaxf(rem2, 0.f));
-                        const int xl = (int)fmaxf(floorf((qr.x - rem - g.ox) * g.inv_cell), -1.0e6f);
-                        const int xh = (int)fminf(floorf((qr.x + rem - g.ox) * g.inv_cell), 1.0e6f);
-                        xa = xl > xa ? xl : xa;
-                        xb = xh < xb ? xh : xb;
-                    }
-                    const int y = cy + dy, z = cz + dz;
-                    xa = xa < 0 ? 0 : xa;
-                    xb = xb > g.nx - 1 ? g.nx - 1 : xb;
-                    reach = reach && y >= 0 && y < g.ny && z >= 0 && z < g.nz && xa <= xb;
-                    const int rowbase = (z * g.ny + y) * g.nx;
-                    ia[sl] = reach ? (unsigned)(rowbase + xa) : 0u;
-                    ib[sl] = reach ? (unsigned)(rowbase + xb + 1) : 0u;
-                }
-#pragma unroll
-                for (int sl = 0; sl < NR; ++sl) { rs[sl] = cs[ia[sl]]; rn[sl] = cs[ib[sl]]; }
-#pragma unroll
-                for (int sl = 0; sl < NR; ++sl) rn[sl] -= rs[sl];
-            }
-            int plb = PLB;
-            unsigned base = 0;
-            for (int round = 0; round < 2; ++round) {
-                unsigned np = 0;
-#pragma unroll
-                for (int sl = 0; sl < NR; ++sl) np += (rn[sl] + ((1u << plb) - 1u)) >> plb;
-                const unsigned incl = wave_incl_scan(np);
-                const unsigned wtot = (unsigned)__builtin_amdgcn_readlane((int)incl, 63);
-                unsigned wb = 0;
-                if (lane == 63 && wtot) wb = atomicAdd(&s_total[round], wtot);
-                wb = (unsigned)__builtin_amdgcn_readlane((int)wb, 63);
-                base = wb + incl - np;
-                __syncthreads();
-                const unsigned tot = s_total[round];
-                if (tot <= (unsigned)CAP) break;
-                int kk = 1;
-                while ((tot >> kk) > (unsigned)(CAP - 9 * Q)) ++kk;
-                plb += kk;
-            }
-#pragma unroll
-            for (int sl = 0; sl < NR; ++sl) {
-                unsigned s = rs[sl], c = rn[sl];
-                while (c) {
-                    const unsigned t = c < (1u << plb) ? c : (1u << plb);
-                    pieces[base++] = make_uint2(s, (t << 8) | (unsigned)slot);
-                    s += t; c -= t;
-                }
-            }
-        }
+        // ---- (1b) all waves: lane = query, wave = row group
+        const RowSetup rs = wg_row_setup(ltab, qrec, qaux, slot);
+        const bool covers = block_covers(rs.c, rs.g); // (wave 0 decides with this and the block's margin in (3))
+        wg_rows_to_pieces<NW, NR, Q, CAP, PLB>(rs, pieces, s_total, slot, wave, lane);
         __syncthreads();
         const unsigned total = s_total[1] ? s_total[1] : s_total[0];
         NN_TICK(2);
@@ -1377,8 +1222,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KMAX <= 8 ?
             const unsigned long long bnd = qbound[qsl];
             const unsigned bh = (unsigned)(bnd >> 32), bl = (unsigned)bnd;
             const unsigned lvbits = __float_as_uint(qr.w) << 28;
-            const uint4 lt2 = ltab[4 * __float_as_int(qr.w) + 2];
-            const gfloat4* mp = reinterpret_cast<const gfloat4*>((((unsigned long long)lt2.w << 32) | lt2.z) + (unsigned long long)e.x * 16ull);
+            const gfloat4* mp = level_pts(ltab, __float_as_int(qr.w)) + e.x;
             for (unsigned c0 = 0; c0 < cnt; c0 += 8u) {
                 vf4 q[8];
 #pragma unroll
@@ -1444,7 +1288,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KMAX <= 8 ?
                 } else if (offered > (unsigned)CAPQ) { } // tighter bound, same level again
                 else {
                     const unsigned long long b = kth();
-                    const float margin = fmaxf((1.0f + mf) * g_cell - g_slack, 0.f);
+                    const float margin = block_margin(rs.c.mf, rs.g.cell, rs.g.slack);
                     const float m2 = margin * margin;
                     const float kd2 = __uint_as_float((unsigned)(b >> 32));
                     decided = (b != ~0ull && kd2 <= m2 * err2) || m2 > maxr2 || covers;
@@ -1463,14 +1307,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KMAX <= 8 ?
         for (int j = 0; j < KMAX; ++j) {
             float d2 = __uint_as_float((unsigned)(mk[j] >> 32));
             int b = -1;
-            if (mk[j] != ~0ull && d2 <= r2q) {
-                const unsigned lv = (unsigned)ms[j] >> 28, pos = (unsigned)ms[j] & 0x0fffffffu;
-                if (lv == 0) b = (int)pos;
-                else {
-                    const uint4 d = ltab[4 * lv + 3];
-                    b = (int)reinterpret_cast<const unsigned*>(((unsigned long long)d.w << 32) | d.z)[pos];
-                }
-            } else d2 = INFINITY;
+            if (mk[j] != ~0ull && d2 <= r2q) b = resolve_level0(ltab, (unsigned)ms[j]);
+            else d2 = INFINITY;
             bs[j] = b; bd[j] = d2;
         }
 #pragma unroll
@@ -1520,17 +1358,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KMAX <= 8 ?
 #ifdef ICPMI_NN_TIMING
     NN_TICK(5);
     if (w0 && st_iter > 1 && (blockIdx.x % 61) == 0) { atomicAdd(&st->dbg[18], t_ovf); atomicAdd(&st->dbg[19], t_off); }
-    if (threadIdx.x == 0 && st_iter > 1 && (blockIdx.x % 7) == 0) {
-        atomicMax(&st->dbg[20], (unsigned long long)(clock64() - t_c0));
-        atomicMax(&st->dbg[21], (unsigned long long)tacc[7]);
-    }
-    if (threadIdx.x == 0 && (blockIdx.x % 61) == 0) {
-        const int tb = st_iter > 1 ? 8 : 0;
-        for (int i = 0; i < 6; ++i) atomicAdd(&st->dbg[tb + i], (unsigned long long)tacc[i]);
-        atomicAdd(&st->dbg[tb + 6], (unsigned long long)tacc[6]);
-        atomicAdd(&st->dbg[tb + 7], 1ull);
-        atomicAdd(&st->dbg[16 + (st_iter > 1 ? 1 : 0)], (unsigned long long)tacc[7]);
-    }
+    nn_timing_flush(st, tacc, st_iter, t_c0);
 #endif
 }
 

@@ -34,6 +34,14 @@ def centring(mean):
 
 # ------------------------------------------------------------------------------------------------------------------ scenes
 _scenes = {}
+DENSE_SPOT_MAP, DENSE_SPOT_READING = 2000, 256   # the sizes of scene "dense_spot" (test_piece_list_overflow states what they guarantee)
+
+
+def ball(rng, count, radius):
+    """count points uniform in the ball of that radius around the origin, float64"""
+    v = rng.normal(size=(count, 3))
+    v /= np.linalg.norm(v, axis=1)[:, None]
+    return v * (radius * rng.uniform(0.0, 1.0, (count, 1)) ** (1.0 / 3.0))
 
 
 def scene(name):
@@ -41,7 +49,7 @@ def scene(name):
     if name in _scenes:
         return _scenes[name]
     from norlab_icp_mapper_amd import synth
-    if name in ("mid", "far", "misaligned", "exact_hits", "clusters"):
+    if name in ("mid", "far", "misaligned", "exact_hits", "clusters", "dense_spot"):
         sc = _scenes.get("_mid_raw") or synth.make_scene(m=200_000, n=20_000)
         _scenes["_mid_raw"] = sc
         mp, nm, rd = sc["map"], sc["normals"], sc["scan"]
@@ -60,6 +68,18 @@ def scene(name):
             near = rng.choice(mp.shape[0], 60, replace=False)
             mp = np.r_[mp, np.repeat(mp[near], 30, axis=0)]
             nm = np.r_[nm, np.repeat(nm[near], 30, axis=0)]
+        elif name == "dense_spot":  # 2 000 distinct map points and 256 reading points inside one 2 cm ball each: the piece list overflows
+            i0 = int(rng.integers(0, rd.shape[0]))
+            spot = (sc["T_gt"] @ rd[i0].astype(np.float64))[:3]           # where reading point i0 lies in the map frame
+            extra = np.ones((DENSE_SPOT_MAP, 4), np.float32)
+            extra[:, :3] = spot + ball(rng, DENSE_SPOT_MAP, 0.02)
+            assert np.unique(extra[:, :3], axis=0).shape[0] == DENSE_SPOT_MAP    # distinct positions: nnk_wg_kernel's CAPQ passes shrink
+            nearest = np.argmin(((mp[:, :3].astype(np.float64) - spot) ** 2).sum(1))
+            mp = np.r_[mp, extra]
+            nm = np.r_[nm, np.repeat(nm[nearest][None, :], DENSE_SPOT_MAP, axis=0)]
+            more = np.ones((DENSE_SPOT_READING, 4), np.float32)
+            more[:, :3] = rd[i0, :3].astype(np.float64) + ball(rng, DENSE_SPOT_READING, 0.02)
+            rd = np.r_[rd, more]
         out = (np.ascontiguousarray(mp), np.ascontiguousarray(nm), np.ascontiguousarray(rd))
     elif name == "bundled":  # map = bundled scans 0-3 placed by the trajectory, reading = scan 4 placed the same way
         import oracle_bindings as ob

@@ -203,6 +203,19 @@ def test_identical_point_clusters(amd, oracle, k):
 
 
 @pytest.mark.parametrize("k", [1, 6])
+def test_piece_list_overflow(amd, oracle, k):
+    """The second round of the workgroup matchers' piece count (wg_rows_to_pieces: more pieces than the list holds, so every lane counts
+    again with longer pieces).  Scene `dense_spot`: 2 000 distinct map points in a 2 cm ball around the place of one reading point, and 256
+    more reading points in a 2 cm ball around that point.  The tile sort puts the 256 next to each other, so whole workgroups of 64 hold
+    nothing else; once the registration has converged each of them has the 2 000 among its candidates (split over several rows they make
+    more pieces, not fewer), and a workgroup needs only 9 such queries to overflow:  k = 1 (nn1_wg_kernel, pieces of 16, list of 1 024): 9 x ceil(2000 / 16) = 1 125
+    > 1 024;  k = 6 (nnk_wg_kernel from iteration 1 on, pieces of 8, list of 896): 9 x ceil(2000 / 8) = 2 250 > 896.  The test cannot see
+    the branch: these sizes are what guarantees it, and the matches of iterations 1 - 3 and of the checked chain's last counted iteration are
+    held row by row to the oracle and the exact float64 search like every other scene's."""
+    run_case(amd, oracle, "dense_spot", base(knn=k, knn_wg_from=1) if k == 6 else base(knn=k))
+
+
+@pytest.mark.parametrize("k", [1, 6])
 def test_large_initial_misalignment(amd, oracle, k):
     run_case(amd, oracle, "misaligned", base(knn=k))
 

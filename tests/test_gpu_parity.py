@@ -75,9 +75,11 @@ def test_knn_far_queries_and_self_match(amd, oracle, small_scene):
     assert (ids[:, 0] != np.arange(2000)).all()
 
 
-@pytest.mark.parametrize("shape", ["single", "identical", "planar", "collinear", "duplicates", "far_offset", "two_clusters"])
+@pytest.mark.parametrize("shape", ["single", "identical", "planar", "collinear", "duplicates", "far_offset", "two_clusters", "dense_spot"])
 def test_knn_degenerate_maps(amd, oracle, shape):
-    """Degenerate geometry through the grid pyramid: zero extents, ties, k larger than the map, big offsets."""
+    """Degenerate geometry through the grid pyramid: zero extents, ties, k larger than the map, big offsets.  dense_spot: 3 000 points in a
+    1 cm ball among 400 in a 4 m cube, the 64 queries within 5 cm of it: every query's own row holds at least the 3 000, 64 x ceil(3000 / 16)
+    = 12 032 pieces against the k = 1 kernel's list of 1 024 -- the second round of its piece count (longer pieces until the list fits)."""
     rng = np.random.default_rng(7)
     def cloud(xyz):
         c = np.ones((xyz.shape[0], 4), dtype=np.float32); c[:, :3] = xyz.astype(np.float32); return c
@@ -93,9 +95,16 @@ def test_knn_degenerate_maps(amd, oracle, shape):
         base = rng.uniform(-2, 2, (200, 3)); m = cloud(np.r_[base, base, base[:50]])
     elif shape == "far_offset":
         m = cloud(rng.uniform(-1, 1, (400, 3)) + np.array([8000.0, -6000.0, 120.0]))
-    else:
+    elif shape == "two_clusters":
         m = cloud(np.r_[rng.normal(0, 0.05, (150, 3)), rng.normal(0, 0.05, (150, 3)) + 40.0])
-    q = cloud(m[rng.integers(0, m.shape[0], 64), :3] + rng.normal(0, 0.3, (64, 3)))
+    else:
+        from loop_driver import ball
+        sparse = rng.uniform(-2, 2, (400, 3))
+        m = cloud(np.r_[sparse, sparse[0] + ball(rng, 3000, 0.01)])
+    if shape == "dense_spot":
+        q = cloud(m[0, :3] + ball(rng, 64, 0.05))
+    else:
+        q = cloud(m[rng.integers(0, m.shape[0], 64), :3] + rng.normal(0, 0.3, (64, 3)))
     q = np.concatenate([q, m[: min(8, m.shape[0])]])  # exact hits (d2 = 0)
     for k in (1, 3, 6, 10, 16):               # (9..16: the cooperative kernels since r3; k may exceed the map)
         for md in (math.inf, 0.5):
