@@ -173,6 +173,30 @@ __device__ __forceinline__ WaveRun wave_run(unsigned key, bool valid)
     r.len = end - r.head_lane;
     return r;
 }
+// ---- the flagged lanes of a wave append to a list with ONE atomic on its counter (by lane 0: every lane of the wave must be active);
+// returns the slot of a flagged lane (flagged lanes in lane order), nothing of use for the others ----
+__device__ __forceinline__ unsigned wave_append(unsigned* counter, bool flag)
+{
+    const unsigned long long bal = __ballot(flag);
+    if (!bal) return 0u;
+    const int lane = threadIdx.x & 63;
+    unsigned base = 0;
+    if (lane == 0) base = atomicAdd(counter, (unsigned)__popcll(bal));
+    base = (unsigned)__builtin_amdgcn_readlane((int)base, 0);
+    return base + (unsigned)__popcll(bal & ((1ull << lane) - 1ull));
+}
+// inclusive prefix sum over the 64 lanes of a wave in registers (DPP: shifts within rows of 16 lanes, then the row totals
+// broadcast into the following rows); every lane must be active
+__device__ __forceinline__ unsigned wave_incl_scan(unsigned v)
+{
+    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false); // row_shr:1
+    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false); // row_shr:2
+    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, false); // row_shr:4
+    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, false); // row_shr:8
+    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false); // row_bcast:15 -> rows 1, 3
+    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false); // row_bcast:31 -> rows 2, 3
+    return v;
+}
 #endif
 
 // ------------------------------------------------------------------------------------------------

@@ -159,6 +159,7 @@ __global__ __launch_bounds__(SCAN_T) void scan_final_kernel(unsigned* __restrict
 // `out` (the flag -> position scans of the compactions copied their input first).  Integer sums: the result is the three-kernel scan's.
 constexpr int SCAN2_MAX_NB = 8192;
 
+// (kept beside common.h's DPP wave_incl_scan: every scan of a map update runs through this one, and a switch has not been measured on them)
 __device__ __forceinline__ unsigned wave_incl_scan_u32(unsigned v)
 {
     const int lane = threadIdx.x & 63;

@@ -371,20 +371,7 @@ __device__ __forceinline__ void nn_timing_flush(IcpState* st, const long long (&
 //   (3) lane per query again: read the slot, apply the level's exactness rule; undecided queries repeat at the next level (or, for a
 //       query that held no bound yet, with the bound its own row just gave it).
 //   The candidates of all Q queries are thus spread evenly over the lanes however unevenly they are spread over the queries.
-// ------------------------------------------------------------------------------------------------
-// inclusive prefix sum over the 64 lanes of a wave in registers (DPP: shifts within rows of 16 lanes, then the row totals
-// broadcast into the following rows); every lane must be active
-__device__ __forceinline__ unsigned wave_incl_scan(unsigned v)
-{
-    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false); // row_shr:1
-    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false); // row_shr:2
-    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, false); // row_shr:4
-    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, false); // row_shr:8
-    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false); // row_bcast:15 -> rows 1, 3
-    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false); // row_bcast:31 -> rows 2, 3
-    return v;
-}
-
+// (the prefix sums over a wave's lanes: wave_incl_scan, common.h)
 // ------------------------------------------------------------------------------------------------
 // Phase (1b) of the workgroup matchers (nn1_wg_kernel, nnk_wg_kernel): all NW waves, lane = query slot, WAVE = ROW GROUP (rows w, w + NW,
 // ... of the 3 x 3 block).  wg_row_setup reads the record wave 0 left in LDS (qrec: point, w = level bits; qaux: squared pruning radius,

@@ -1,12 +1,7 @@
 // selfgrid.hip -- self k-NN of a cloud (SurfaceNormalDataPointsFilter over the whole map: reference norlab_icp_mapper/Map.cpp:523-525 applies
 // the `post:` filters to the local map on every update, examples/config.yaml:25-27 `SurfaceNormalDataPointsFilter: knn: 10`; upstream body:
 // libpointmatcher DataPointsFilters/SurfaceNormal.cpp -> Nabo::NNS::knn of the cloud against itself) through a SPARSE BLOCK GRID.
-//
-// Why not the dense single-level grid of r2 - r5 (nn.hip: nnk_self_tiled_kernel + ring kernel + brute pass): a vehicle's lidar map is dense
-// along the trajectory and sparse far out (BASELINE config 4: 104 k points in a 283 x 349 x 22 m box, 10-th neighbour at 0.3 m for the median
-// point, 2.3 m for the 99-th percentile, 25 m for the last) -- one cell edge is wrong for most of it, the cell table of the bounding box is
-// 99.7 % empty (8 M cells: its scan alone was 60 us), 6 - 8 % of the points went through up to six rings and 400 - 500 through a brute pass
-// over the whole map: 457 us per update.
+// (Why a sparse grid and not the dense single-level one it replaced: DESIGN_history.md, section 15.)
 //
 // Structure (one build per call, 6 launches):
 //   * A-cells of edge `cell`, grouped 4 x 4 x 4 into B-blocks; a dense table T over the B-cells in MORTON order (bits of the three axes
@@ -32,6 +27,14 @@
 #include <vector>
 
 template <typename T> using SgArr = DevArr<T, GrowQuarter>; // (common.h: growth by a quarter, the stream drained before a block goes back)
+// the sorted copy (and its bounding box) of the last TRACKED build (+ room for the next append): the next build of the grown cloud reads it
+// instead of the cloud in the caller's order -- nearly sorted input, coalesced scatter
+struct SgPrev { SgArr<float4> d_pts; int64_t m = 0; float lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0}; };
+// tuning state: the edge of the previous build and what it was built for (what its points saw -- the size-biased A-cell occupancy -- comes
+// through the mapped page)
+struct SgTuned { float cell = 0.f; int64_t m = 0; int k = 0; };
+// the last build's grid, for the test seam (selfgrid_debug_info)
+struct SgLast { int na[3] = {0, 0, 0}, tsize = 0, trials = 0; unsigned long long seq = 0; };
 struct SelfGridCtx {
     SgArr<unsigned> d_tcnt; bool tcnt_clean = false; // points per B-cell (zero between builds: the scan cleans what it read)
     SgArr<unsigned> d_tstart;   // exclusive scan of d_tcnt, Morton order (+ 2 words: cursor layout while scattering)
@@ -43,22 +46,18 @@ struct SelfGridCtx {
     SgArr<unsigned> d_inv;      // original index -> sorted position
     SgArr<float> d_part;        // bounding-box partials
     SgArr<unsigned> d_dirty;    // subset search: bitmaps of the cells appended points fell into, per level
-    SgArr<float4> d_prev; int64_t prev_m = 0; float prev_lo[3] = {0, 0, 0}, prev_hi[3] = {0, 0, 0};   // the sorted copy (and its bounding box) of the last TRACKED build (+ room for the next append): the next build of the grown cloud reads it instead of the cloud in the caller's order -- nearly sorted input, coalesced scatter
     SgArr<unsigned char> d_sel; // ... selected queries by sorted position (m) and by original index (m)
     SgArr<struct SgState> d_state;
-    // tuning state: the edge of the previous build and what its points saw (size-biased A-cell occupancy, delivered through the mapped page)
-    float cell = 0.f; int64_t m = 0; int k = 0;
-    unsigned long long seq = 0;
-    int last_na[3] = {0, 0, 0}, last_tsize = 0, last_trials = 0; // the last build's grid, for the test seam (selfgrid_debug_info)
+    SgPrev prev;
+    SgTuned tuned;
+    SgLast last;
 };
 
 struct SgState {
     unsigned nblk;   // occupied blocks (claimed by the key kernel)
-    unsigned bad;    // (unused: the bounding-box pass counts non-finite points next to its partials)
-    unsigned long long sq;     // sum over the A-cells of (points in the cell)^2 (summed from sqpart by the cell kernel)
     unsigned long long levels; // diagnostics: sum of the levels at which the level kernel's queries ended
     unsigned qcount[64];       // queries queued for the level kernel, per sub-queue
-    unsigned long long sqpart[64]; // partial sums of sq, by workgroup % 64 (thousands of atomics on ONE address serialise at 10 - 25 ns each)
+    unsigned long long sqpart[64]; // sum over the A-cells of (points in the cell)^2, in parts by workgroup % 64 (thousands of atomics on ONE address serialise at 10 - 25 ns each)
 };
 
 namespace {
@@ -78,6 +77,23 @@ __device__ __forceinline__ int sg_cell_of(float v, float o, float inv, int n)
     int c = (int)floorf((v - o) * inv);
     return c < 0 ? 0 : (c >= n ? n - 1 : c);
 }
+// the A-cell of a point
+__device__ __forceinline__ void sg_cell3(const SgGrid& g, const float4& p, int a[3])
+{
+    a[0] = sg_cell_of(p.x, g.ox, g.inv_cell, g.na[0]); a[1] = sg_cell_of(p.y, g.oy, g.inv_cell, g.na[1]); a[2] = sg_cell_of(p.z, g.oz, g.inv_cell, g.na[2]);
+}
+// a query in the grid: its A-cell and its position inside it (in cells, clamped to [0, 1]: a point may sit a rounding outside its cell)
+struct SgCellPos { int a[3]; float fa[3]; };
+__device__ __forceinline__ SgCellPos sg_cell_pos(const SgGrid& g, const float4& p)
+{
+    SgCellPos c;
+    const float fx = (p.x - g.ox) * g.inv_cell, fy = (p.y - g.oy) * g.inv_cell, fz = (p.z - g.oz) * g.inv_cell;
+    sg_cell3(g, p, c.a);
+    c.fa[0] = fminf(fmaxf(fx - (float)c.a[0], 0.f), 1.f); c.fa[1] = fminf(fmaxf(fy - (float)c.a[1], 0.f), 1.f); c.fa[2] = fminf(fmaxf(fz - (float)c.a[2], 0.f), 1.f);
+    return c;
+}
+// cells per axis at level l (edge cell * 2^l) of an axis of na A-cells
+__host__ __device__ __forceinline__ int sg_level_dim(int na, int l) { return ((na - 1) >> l) + 1; }
 // bits of v into the set positions of mask, lowest first (a software pdep; masks carry at most ~10 bits)
 __device__ __forceinline__ unsigned sg_dep(unsigned v, unsigned mask)
 {
@@ -108,6 +124,11 @@ __device__ __forceinline__ unsigned sg_hb(const SgGrid& g, int bx, int by, int b
 __device__ __forceinline__ unsigned sg_sub(int x, int y, int z)
 {
     return (unsigned)((x & 1) | ((y & 1) << 1) | ((z & 1) << 2) | ((x & 2) << 2) | ((y & 2) << 3) | ((z & 2) << 4));
+}
+__device__ __forceinline__ unsigned sg_sub_of(const SgGrid& g, const float4& p) // ... of a point's A-cell
+{
+    int a[3]; sg_cell3(g, p, a);
+    return sg_sub(a[0] & 3, a[1] & 3, a[2] & 3);
 }
 
 // the points of the level-l cell (cx, cy, cz) -- edge cell * 2^l, coordinates in cells of that level -- as a run [s, e) of the sorted array;
@@ -152,7 +173,7 @@ __device__ __forceinline__ float sg_margin2(const SgGrid& g, int l, const int a[
     float mn = INFINITY;
 #pragma unroll
     for (int ax = 0; ax < 3; ++ax) {
-        const int c = a[ax] >> l, nl = ((g.na[ax] - 1) >> l) + 1;
+        const int c = a[ax] >> l, nl = sg_level_dim(g.na[ax], l);
         const float fr = ((float)(a[ax] & ((1 << l) - 1)) + fa[ax]) / (float)(1u << l);
         if (c >= 2) mn = fminf(mn, (1.0f + fr) * cl);          // cells below the block exist
         if (c + 2 <= nl - 1) mn = fminf(mn, (2.0f - fr) * cl); // cells above it exist
@@ -162,24 +183,15 @@ __device__ __forceinline__ float sg_margin2(const SgGrid& g, int l, const int a[
     return margin * margin;
 }
 
-// inclusive scan over the 64 lanes: four DPP row shifts inside the rows of 16, two row broadcasts across them
-__device__ __forceinline__ unsigned sg_wave_incl_scan(unsigned v)
-{
-    int x = (int)v;
-    x += __builtin_amdgcn_update_dpp(0, x, 0x111, 0xF, 0xF, true); // row_shr:1
-    x += __builtin_amdgcn_update_dpp(0, x, 0x112, 0xF, 0xF, true); // row_shr:2
-    x += __builtin_amdgcn_update_dpp(0, x, 0x114, 0xF, 0xF, true); // row_shr:4
-    x += __builtin_amdgcn_update_dpp(0, x, 0x118, 0xF, 0xF, true); // row_shr:8
-    x += __builtin_amdgcn_update_dpp(0, x, 0x142, 0xA, 0xF, true); // row_bcast:15 -> rows 1, 3
-    x += __builtin_amdgcn_update_dpp(0, x, 0x143, 0xC, 0xF, true); // row_bcast:31 -> rows 2, 3
-    return (unsigned)x;
-}
+// the radius a search must reach to hold every point within d2 of the query: the rounded-up root, padded by what a point may sit outside
+// a cell of edge `edge` (the ball query of the level kernel, the dirty-cell test of the subset search)
+__device__ __forceinline__ float sg_reach(const SgGrid& g, float d2, float edge) { return sqrt_up(d2) * 1.00001f + (edge * 1e-3f + g.maxabs * 4e-6f); }
 
 // ---- build ------------------------------------------------------------------------------------------------------------------------------
 __global__ void sg_reset_kernel(SgState* st)
 {
     if (blockIdx.x == 0) {
-        if (threadIdx.x == 0) { st->nblk = 0; st->bad = 0; st->sq = 0ull; st->levels = 0ull; }
+        if (threadIdx.x == 0) { st->nblk = 0; st->levels = 0ull; }
         if (threadIdx.x < 64) { st->qcount[threadIdx.x] = 0; st->sqpart[threadIdx.x] = 0ull; }
     }
 }
@@ -204,11 +216,10 @@ __global__ __launch_bounds__(256) void sg_key_kernel(const float4* __restrict__ 
         const int64_t i = ((int64_t)blockIdx.x * tiles + t) * 256 + threadIdx.x;
         const bool valid = i < m;
         const float4 p = pts[valid ? i : 0];
-        const int ax = sg_cell_of(p.x, g.ox, g.inv_cell, g.na[0]);
-        const int ay = sg_cell_of(p.y, g.oy, g.inv_cell, g.na[1]);
-        const int az = sg_cell_of(p.z, g.oz, g.inv_cell, g.na[2]);
-        const unsigned hb = sg_hb(g, ax >> 2, ay >> 2, az >> 2);
-        if (valid) keys[i] = (hb << 6) | sg_sub(ax & 3, ay & 3, az & 3);
+        int a[3];
+        sg_cell3(g, p, a);
+        const unsigned hb = sg_hb(g, a[0] >> 2, a[1] >> 2, a[2] >> 2);
+        if (valid) keys[i] = (hb << 6) | sg_sub(a[0] & 3, a[1] & 3, a[2] & 3);
         const WaveRun r = wave_run(hb, valid);
         const bool first = r.head && atomicAdd(&tcnt[hb], (unsigned)r.len) == 0u;
         hbs[t] = hb;
@@ -282,14 +293,13 @@ __global__ __launch_bounds__(64) void sg_block_sort_kernel(const float4* __restr
         unsigned sub0 = 0;
         for (unsigned i = lane; i < n; i += 64) {
             const float4 p = in[s0 + i];
-            const unsigned sub = sg_sub(sg_cell_of(p.x, g.ox, g.inv_cell, g.na[0]) & 3, sg_cell_of(p.y, g.oy, g.inv_cell, g.na[1]) & 3,
-                                        sg_cell_of(p.z, g.oz, g.inv_cell, g.na[2]) & 3);
+            const unsigned sub = sg_sub_of(g, p);
             if (i < 64) { p0 = p; sub0 = sub; }
             atomicAdd(&cnt[sub], 1u);
         }
         __syncthreads();
         const unsigned c = cnt[lane];
-        const unsigned off = sg_wave_incl_scan(c) - c;
+        const unsigned off = wave_incl_scan(c) - c;
         f[(size_t)b * SG_F + lane] = s0 + off;
         if (lane == 0) f[(size_t)b * SG_F + 64] = e0;
         cur[lane] = off;
@@ -298,11 +308,7 @@ __global__ __launch_bounds__(64) void sg_block_sort_kernel(const float4* __restr
         for (unsigned i = lane; i < n; i += 64) {
             float4 p = p0;
             unsigned sub = sub0;
-            if (i >= 64) {
-                p = in[s0 + i];
-                sub = sg_sub(sg_cell_of(p.x, g.ox, g.inv_cell, g.na[0]) & 3, sg_cell_of(p.y, g.oy, g.inv_cell, g.na[1]) & 3,
-                             sg_cell_of(p.z, g.oz, g.inv_cell, g.na[2]) & 3);
-            }
+            if (i >= 64) { p = in[s0 + i]; sub = sg_sub_of(g, p); }
             const unsigned r = atomicAdd(&cur[sub], 1u);
             out[s0 + r] = p;
             inv[__float_as_uint(p.w)] = s0 + r;
@@ -412,6 +418,82 @@ __device__ __forceinline__ void sg_absorb(unsigned long long& best, unsigned lon
 constexpr int SG_NQ = 64; // sub-queues between the two search kernels (a wave appends to queue blockIdx % SG_NQ: ~100 atomics per counter
                           // instead of thousands on one address -- same-address device atomics serialise at 10 - 25 ns each)
 
+// ---- the pieces both search kernels are written on (one wave; the LDS tables are the caller's, and so are the barriers around them) ----
+// Run table of the 27 level-l cells around (cx, cy, cz), nearest first: starts[j] = where cell j's points begin in the sorted array,
+// prefix[j] = candidates in the cells before it (prefix[27] = all of them, returned).  All 64 lanes call it.
+__device__ __forceinline__ unsigned sg_runs27(const SgGrid& g, const unsigned* __restrict__ tstart, const unsigned* __restrict__ tbid,
+                                              const unsigned* __restrict__ f, int l, int cx, int cy, int cz, unsigned* starts, unsigned* prefix)
+{
+    const int lane = threadIdx.x;
+    unsigned s = 0, e = 0;
+    if (lane < 27) sg_cell_range(g, tstart, tbid, f, l, cx + SG_ORD[lane][0], cy + SG_ORD[lane][1], cz + SG_ORD[lane][2], s, e);
+    const unsigned incl = wave_incl_scan(e - s);
+    if (lane < 27) { prefix[lane + 1] = incl; starts[lane] = s; }
+    if (lane == 0) prefix[0] = 0;
+    return (unsigned)__builtin_amdgcn_readlane((int)incl, 63);
+}
+// flat candidate index -> sorted position: the run of candidate fl is the last whose prefix is <= fl (n_runs <= 2^STEPS)
+template <int STEPS>
+__device__ __forceinline__ unsigned sg_flat_locate(const unsigned* prefix, const unsigned* starts, int n_runs, unsigned fl)
+{
+    int lo = 0, hi = n_runs;
+#pragma unroll
+    for (int it = 0; it < STEPS; ++it) { const int mid = (lo + hi) >> 1; if (prefix[mid] <= fl) lo = mid; else hi = mid; }
+    return starts[lo] + (fl - prefix[lo]);
+}
+__device__ __forceinline__ float sg_key_d2(unsigned long long key) { return __uint_as_float((unsigned)(key >> 32)); }
+// The candidates of a run table past one wave, 64 at a time, four batches requested before any is looked at: the first batch is sorted,
+// the rest absorbed.  Returns the k smallest keys in lanes [0, k) (~0: nothing).  BOUNDED: keys beyond `bound` are dropped at once and
+// the first batch that HOLDS anything is the one sorted.  self: a sorted position that is safe to load for the lanes past the end.
+template <bool BOUNDED, int STEPS>
+__device__ __forceinline__ unsigned long long sg_stream(const float4* __restrict__ map, const unsigned* prefix, const unsigned* starts, int n_runs,
+                                                        unsigned total, float x, float y, float z, unsigned self, int k, float bound)
+{
+    const int lane = threadIdx.x;
+    unsigned long long best = ~0ull;
+    bool first = true;
+    for (unsigned base = 0; base < total; base += 256u) {
+        float4 q[4];
+        bool val[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const unsigned fl = base + 64u * u + (unsigned)lane;
+            unsigned pos = self;
+            val[u] = fl < total;
+            if (val[u]) pos = sg_flat_locate<STEPS>(prefix, starts, n_runs, fl);
+            q[u] = map[pos];
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            if (base + 64u * u >= total) break; // (uniform)
+            const float d2 = sqdist3(x, y, z, q[u].x, q[u].y, q[u].z);
+            const unsigned long long key = (val[u] && (!BOUNDED || d2 <= bound)) ? pack_key(d2, __float_as_uint(q[u].w)) : ~0ull;
+            if constexpr (BOUNDED) {
+                if (first) {
+                    if (__ballot(key != ~0ull) != 0ull) { best = key; sg_sort64<false>(best); first = false; }
+                } else sg_absorb(best, key, k);
+            } else {
+                if (first) { best = key; sg_sort64<false>(best, total); first = false; }
+                else sg_absorb(best, key, k);
+            }
+        }
+    }
+    return best;
+}
+// the exactness rule: the k-th key found (kth; ~0: fewer than k) settles a query whose candidates held every point within margin^2 = m2
+__device__ __forceinline__ bool sg_decided(unsigned long long kth, float m2) { return m2 == INFINITY || (kth != ~0ull && sg_key_d2(kth) <= m2); }
+// a query's row of the result: lane j < k writes the j-th neighbour (pos: its sorted position, looked up by the caller), -1 / +inf where
+// the cloud has fewer
+__device__ __forceinline__ void sg_write_row(int* __restrict__ out_sidx, float* __restrict__ out_d2, int k, unsigned orig, unsigned long long best, int pos)
+{
+    const int lane = threadIdx.x;
+    if (lane < k) {
+        const bool valid = best != ~0ull;
+        out_sidx[(size_t)k * orig + lane] = valid ? pos : -1;
+        out_d2[(size_t)k * orig + lane] = valid ? sg_key_d2(best) : INFINITY;
+    }
+}
+
 // One wave per SGQ consecutive points of the sorted array (= a few A-cells).  Per cell: 27 look-ups (one lane each, nearest cells first), the
 // neighbourhood's points into registers (lane j holds candidates j, j + 64, ...); per query: distances, one sort of the first 64, the rest
 // absorbed.  A query is decided when its k-th distance fits the margin to the border of its 3 x 3 x 3 cells; the others are queued for the
@@ -432,7 +514,7 @@ __global__ __launch_bounds__(64) void sg_cell_kernel(SgGrid g, const float4* __r
     if (blockIdx.x == 0 && sq_mapped) {
         unsigned long long sq = st->sqpart[lane];
         for (int o = 32; o > 0; o >>= 1) sq += __shfl_xor(sq, o, 64);
-        if (lane == 0) { *sq_mapped = sq; st->sq = sq; }
+        if (lane == 0) *sq_mapped = sq;
     }
     const unsigned INF_BITS = 0x7f800000u;
     unsigned grp = blockIdx.x;
@@ -446,10 +528,8 @@ __global__ __launch_bounds__(64) void sg_cell_kernel(SgGrid g, const float4* __r
     }
     // the wave's queries, one trip; what a query needs besides its coordinates is computed by its lane and read with v_readlane below
     const float4 mine = map[min(q0 + (unsigned)lane, m - 1)];
-    const float mfx = (mine.x - g.ox) * g.inv_cell, mfy = (mine.y - g.oy) * g.inv_cell, mfz = (mine.z - g.oz) * g.inv_cell;
-    const int ma3[3] = {sg_cell_of(mine.x, g.ox, g.inv_cell, g.na[0]), sg_cell_of(mine.y, g.oy, g.inv_cell, g.na[1]), sg_cell_of(mine.z, g.oz, g.inv_cell, g.na[2])};
-    const float mfa[3] = {fminf(fmaxf(mfx - (float)ma3[0], 0.f), 1.f), fminf(fmaxf(mfy - (float)ma3[1], 0.f), 1.f), fminf(fmaxf(mfz - (float)ma3[2], 0.f), 1.f)};
-    const float mm2 = sg_margin2(g, 0, ma3, mfa);
+    const SgCellPos mc = sg_cell_pos(g, mine);
+    const float mm2 = sg_margin2(g, 0, mc.a, mc.fa);
     int pa0 = -1, pa1 = -1, pa2 = -1;
     unsigned N = 0, nund = 0;
     bool big = false;
@@ -464,29 +544,19 @@ __global__ __launch_bounds__(64) void sg_cell_kernel(SgGrid g, const float4* __r
         const float mex = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mine.x), src)), mey = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mine.y), src)),
                     mez = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mine.z), src));
         const unsigned orig_q = (unsigned)__builtin_amdgcn_readlane(__float_as_int(mine.w), src);
-        const int a0 = __builtin_amdgcn_readlane(ma3[0], src), a1 = __builtin_amdgcn_readlane(ma3[1], src), a2 = __builtin_amdgcn_readlane(ma3[2], src);
+        const int a0 = __builtin_amdgcn_readlane(mc.a[0], src), a1 = __builtin_amdgcn_readlane(mc.a[1], src), a2 = __builtin_amdgcn_readlane(mc.a[2], src);
         const float m2 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mm2), src));
         if (a0 != pa0 || a1 != pa1 || a2 != pa2) { // (wave-uniform) a new cell: its neighbourhood
             pa0 = a0; pa1 = a1; pa2 = a2;
             __syncthreads();
-            unsigned s = 0, e = 0;
-            if (lane < 27) sg_cell_range(g, tstart, tbid, f, 0, a0 + SG_ORD[lane][0], a1 + SG_ORD[lane][1], a2 + SG_ORD[lane][2], s, e);
-            const unsigned incl = sg_wave_incl_scan(e - s);
-            if (lane < 27) { pre[lane + 1] = incl; cst[lane] = s; }
-            if (lane == 0) pre[0] = 0;
-            N = (unsigned)__builtin_amdgcn_readlane((int)incl, 63);
+            N = sg_runs27(g, tstart, tbid, f, 0, a0, a1, a2, cst, pre);
             __syncthreads();
             big = !packed_ok || N > (unsigned)(64 * SG_R);
 #pragma unroll
             for (int r = 0; r < SG_R; ++r) {
                 const unsigned fl = (unsigned)(lane + 64 * r);
                 unsigned pos = ~0u;
-                if (fl < N) {
-                    int lo = 0, hi = 27; // the cell of flat candidate fl: the last offset <= fl
-#pragma unroll
-                    for (int it = 0; it < 5; ++it) { const int mid = (lo + hi) >> 1; if (pre[mid] <= fl) lo = mid; else hi = mid; }
-                    pos = cst[lo] + (fl - pre[lo]);
-                }
+                if (fl < N) pos = sg_flat_locate<5>(pre, cst, 27, fl);
                 cval[r] = pos != ~0u;
                 cand[r] = map[cval[r] ? pos : qi];
                 cpos[fl] = pos;
@@ -509,26 +579,17 @@ __global__ __launch_bounds__(64) void sg_cell_kernel(SgGrid g, const float4* __r
                 const unsigned fl = c0 + (unsigned)lane;
                 unsigned long long key = ~0ull;
                 if (fl < N) {
-                    int lo = 0, hi = 27;
-#pragma unroll
-                    for (int it = 0; it < 5; ++it) { const int mid = (lo + hi) >> 1; if (pre[mid] <= fl) lo = mid; else hi = mid; }
-                    const float4 q = map[cst[lo] + (fl - pre[lo])];
+                    const float4 q = map[sg_flat_locate<5>(pre, cst, 27, fl)];
                     key = pack_key(sqdist3(mex, mey, mez, q.x, q.y, q.z), __float_as_uint(q.w));
                 }
                 sg_absorb(best, key, k);
             }
         }
         const unsigned long long kth = sg_readlane64(best, k - 1);
-        const float kd2 = __uint_as_float((unsigned)(kth >> 32));
-        const bool decided = m2 == INFINITY || (kth != ~0ull && kd2 <= m2);
-        if (decided) {
-            if (lane < k) {
-                const bool valid = best != ~0ull;
-                int pos = -1;
-                if (valid) pos = big ? (int)inv[(unsigned)best] : (int)cpos[(unsigned)best & 0xffu];
-                out_sidx[(size_t)k * orig_q + lane] = pos;
-                out_d2[(size_t)k * orig_q + lane] = valid ? __uint_as_float((unsigned)(best >> 32)) : INFINITY;
-            }
+        if (sg_decided(kth, m2)) {
+            int pos = -1;
+            if (lane < k && best != ~0ull) pos = big ? (int)inv[(unsigned)best] : (int)cpos[(unsigned)best & 0xffu];
+            sg_write_row(out_sidx, out_d2, k, orig_q, best, pos);
         } else {
             if (lane == 0) undq[nund] = make_uint2(qi, kth != ~0ull ? (unsigned)(kth >> 32) : INF_BITS);
             ++nund;
@@ -537,10 +598,8 @@ __global__ __launch_bounds__(64) void sg_cell_kernel(SgGrid g, const float4* __r
     if (nund) { // (uniform) one atomic per wave, on one of SG_NQ counters
         __syncthreads();
         const unsigned qn = blockIdx.x % SG_NQ;
-        unsigned base = 0;
-        if (lane == 0) base = atomicAdd(&st->qcount[qn], nund);
-        base = (unsigned)__builtin_amdgcn_readlane((int)base, 0);
-        if ((unsigned)lane < nund) queue[(size_t)qn * qcap + base + lane] = undq[lane];
+        const unsigned slot = wave_append(&st->qcount[qn], (unsigned)lane < nund);
+        if ((unsigned)lane < nund) queue[(size_t)qn * qcap + slot] = undq[lane];
     }
 }
 
@@ -551,16 +610,7 @@ __global__ __launch_bounds__(64) void sg_cell_kernel(SgGrid g, const float4* __r
 // dropped, the points of the others dealt to the lanes 64 at a time (a flat index over the runs' prefix sums, in LDS), four batches
 // requested before any is looked at; keys beyond b are dropped at once, the first batch that holds anything is sorted, the rest absorbed.
 // Every point within b of the query lies in those cells (a point's cell index is monotone in its coordinate), k of them exist: exact, and
-// done -- r6's first version climbed the levels to the end and a query in the sparse periphery of a lidar map streamed the thousands of
-// points of a 50 m block past one wave.
-__device__ __forceinline__ void sg_flat_locate(const unsigned* __restrict__ rp, const unsigned* __restrict__ rs, int n_runs_pow2_steps, int n_runs,
-                                               unsigned fl, unsigned& pos)
-{
-    int lo = 0, hi = n_runs; // the run of flat candidate fl: the last offset <= fl
-    for (int it = 0; it < n_runs_pow2_steps; ++it) { const int mid = (lo + hi) >> 1; if (rp[mid] <= fl) lo = mid; else hi = mid; }
-    pos = rs[lo] + (fl - rp[lo]);
-}
-
+// done.
 __global__ __launch_bounds__(64) void sg_level_kernel(SgGrid g, const float4* __restrict__ map, const unsigned* __restrict__ tstart,
                                                       const unsigned* __restrict__ tbid, const unsigned* __restrict__ f,
                                                       const unsigned* __restrict__ inv, SgState* __restrict__ st, int k,
@@ -576,64 +626,36 @@ __global__ __launch_bounds__(64) void sg_level_kernel(SgGrid g, const float4* __
         const uint2 qe = queue[(size_t)qn * qcap + w];
         const float4 me = map[qe.x];
         float bound = __uint_as_float(qe.y);
-        const float fx = (me.x - g.ox) * g.inv_cell, fy = (me.y - g.oy) * g.inv_cell, fz = (me.z - g.oz) * g.inv_cell;
-        const int a3[3] = {sg_cell_of(me.x, g.ox, g.inv_cell, g.na[0]), sg_cell_of(me.y, g.oy, g.inv_cell, g.na[1]), sg_cell_of(me.z, g.oz, g.inv_cell, g.na[2])};
-        const float fa[3] = {fminf(fmaxf(fx - (float)a3[0], 0.f), 1.f), fminf(fmaxf(fy - (float)a3[1], 0.f), 1.f), fminf(fmaxf(fz - (float)a3[2], 0.f), 1.f)};
+        const SgCellPos mc = sg_cell_pos(g, me);
         unsigned long long best = ~0ull;
         bool done = false;
         int l = 0;
         // ---- phase A: any k points ----
         while (bound == INFINITY) {
             ++l;
-            const float m2 = sg_margin2(g, l, a3, fa);
+            const float m2 = sg_margin2(g, l, mc.a, mc.fa);
             __syncthreads(); // (rs / rp of the previous level consumed)
-            unsigned s = 0, e = 0;
-            if (lane < 27) sg_cell_range(g, tstart, tbid, f, l, (a3[0] >> l) + SG_ORD[lane][0], (a3[1] >> l) + SG_ORD[lane][1], (a3[2] >> l) + SG_ORD[lane][2], s, e);
-            const unsigned incl = sg_wave_incl_scan(e - s);
-            if (lane < 27) { rp[lane + 1] = incl; rs[lane] = s; }
-            if (lane == 0) rp[0] = 0;
-            const unsigned total = (unsigned)__builtin_amdgcn_readlane((int)incl, 63);
+            const unsigned total = sg_runs27(g, tstart, tbid, f, l, mc.a[0] >> l, mc.a[1] >> l, mc.a[2] >> l, rs, rp);
             __syncthreads();
-            best = ~0ull;
-            bool first = true;
-            for (unsigned base = 0; base < total; base += 256u) {
-                float4 q[4];
-                bool val[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const unsigned fl = base + 64u * u + (unsigned)lane;
-                    unsigned pos = qe.x;
-                    val[u] = fl < total;
-                    if (val[u]) sg_flat_locate(rp, rs, 5, 27, fl, pos);
-                    q[u] = map[pos];
-                }
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    if (base + 64u * u >= total) break; // (uniform)
-                    const unsigned long long key = val[u] ? pack_key(sqdist3(me.x, me.y, me.z, q[u].x, q[u].y, q[u].z), __float_as_uint(q[u].w)) : ~0ull;
-                    if (first) { best = key; sg_sort64<false>(best, total); first = false; }
-                    else sg_absorb(best, key, k);
-                }
-            }
+            best = sg_stream<false, 5>(map, rp, rs, 27, total, me.x, me.y, me.z, qe.x, k, 0.f);
             const unsigned long long kth = sg_readlane64(best, k - 1);
-            const float kd2 = __uint_as_float((unsigned)(kth >> 32));
-            if (m2 == INFINITY || (kth != ~0ull && kd2 <= m2) || l >= 31) { done = true; break; } // the block holds every point that matters
-            if (kth != ~0ull) bound = kd2; // k real points within kd2: the answer's k-th is no farther
+            if (sg_decided(kth, m2) || l >= 31) { done = true; break; } // the block holds every point that matters
+            if (kth != ~0ull) bound = sg_key_d2(kth); // k real points within that: the answer's k-th is no farther
         }
         // ---- phase B: the ball of the bound ----
         if (!done) {
             const float b = sqrt_up(bound);
             int sl = 0;
             while (sl < 30 && g.cell * (float)(1u << sl) < 0.5f * b) ++sl;
-            const float reach = b * 1.00001f + (g.cell * (float)(1u << sl) * 1e-3f + g.maxabs * 4e-6f);
+            const float cs = g.cell * (float)(1u << sl);
+            const float reach = sg_reach(g, bound, cs);
             int c0[3], nc[3];
             const float pme[3] = {me.x, me.y, me.z}, org[3] = {g.ox, g.oy, g.oz};
 #pragma unroll
-            for (int ax = 0; ax < 3; ++ax) {
+            for (int ax = 0; ax < 3; ++ax) { // (axis by axis, not two sg_cell3: that form keeps six more registers live in this kernel)
                 const int lo_c = sg_cell_of(pme[ax] - reach, org[ax], g.inv_cell, g.na[ax]) >> sl, hi_c = sg_cell_of(pme[ax] + reach, org[ax], g.inv_cell, g.na[ax]) >> sl;
                 c0[ax] = lo_c; nc[ax] = min(hi_c - lo_c + 1, 6); // (at most 6 by the choice of sl; the clamp only guards the arithmetic)
             }
-            const float cs = g.cell * (float)(1u << sl);
             const float slack = cs * 2e-3f + g.maxabs * 2e-6f;
             __syncthreads();
             unsigned total = 0;
@@ -651,43 +673,18 @@ __global__ __launch_bounds__(64) void sg_level_kernel(SgGrid g, const float4* __
                     const float gz = fmaxf(fmaxf(loz - me.z, me.z - (loz + cs)) - slack, 0.f);
                     if (!(fmaf(gz, gz, fmaf(gy, gy, gx * gx)) > bound)) sg_cell_range(g, tstart, tbid, f, sl, sx, sy, sz, s, e);
                 }
-                const unsigned incl = sg_wave_incl_scan(e - s);
+                const unsigned incl = wave_incl_scan(e - s);
                 if (idx < 216) { rs[idx] = s; rp[idx + 1] = total + incl; }
                 total += (unsigned)__builtin_amdgcn_readlane((int)incl, 63);
             }
             if (lane == 0) rp[0] = 0;
             __syncthreads();
-            best = ~0ull;
-            bool first = true;
-            for (unsigned base = 0; base < total; base += 256u) {
-                float4 q[4];
-                bool val[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const unsigned fl = base + 64u * u + (unsigned)lane;
-                    unsigned pos = qe.x;
-                    val[u] = fl < total;
-                    if (val[u]) sg_flat_locate(rp, rs, 8, 216, fl, pos);
-                    q[u] = map[pos];
-                }
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    if (base + 64u * u >= total) break; // (uniform)
-                    const float d2 = sqdist3(me.x, me.y, me.z, q[u].x, q[u].y, q[u].z);
-                    const unsigned long long key = (val[u] && d2 <= bound) ? pack_key(d2, __float_as_uint(q[u].w)) : ~0ull;
-                    if (first) {
-                        if (__ballot(key != ~0ull) != 0ull) { best = key; sg_sort64<false>(best); first = false; }
-                    } else sg_absorb(best, key, k);
-                }
-            }
+            best = sg_stream<true, 8>(map, rp, rs, 216, total, me.x, me.y, me.z, qe.x, k, bound);
         }
         lev_sum += (unsigned long long)l;
-        if (lane < k) {
-            const bool valid = best != ~0ull;
-            const unsigned orig = __float_as_uint(me.w);
-            out_sidx[(size_t)k * orig + lane] = valid ? (int)inv[(unsigned)best] : -1;
-            out_d2[(size_t)k * orig + lane] = valid ? __uint_as_float((unsigned)(best >> 32)) : INFINITY;
-        }
+        int pos = -1;
+        if (lane < k && best != ~0ull) pos = (int)inv[(unsigned)best];
+        sg_write_row(out_sidx, out_d2, k, __float_as_uint(me.w), best, pos);
     }
     if (diag && lane == 0 && lev_sum) atomicAdd(&st->levels, lev_sum); // (ICPMI_SELF_DIAG only: thousands of atomics on one address)
 }
@@ -700,8 +697,10 @@ __global__ __launch_bounds__(64) void sg_level_kernel(SgGrid g, const float4* __
 // cells appended points fell into.  A false positive is searched again and finds what it had.
 struct SgLevels {
     int L, lmin;                    // levels lmin .. L - 1 have a bitmap (the top one is a single cell); a ball narrower than level lmin is tested there
-    unsigned long long off[26];     // first bit of level l (cells per axis at level l: ((na - 1) >> l) + 1)
+    unsigned long long off[26];     // first bit of level l (cells per axis at level l: sg_level_dim)
 };
+// the bit of the level's cell (x, y, z); off: the level's first bit, n0 / n1: its cells along x / y
+__device__ __forceinline__ unsigned long long sg_level_bit(unsigned long long off, int n0, int n1, int x, int y, int z) { return off + ((unsigned long long)z * n1 + (unsigned long long)y) * n0 + (unsigned long long)x; }
 
 // one lane per (appended point, level): blockIdx.y = level.  The lanes of a wave that hit the same word (at the coarse levels: all of them)
 // send ONE atomic -- thousands of atomics on one address serialise at 10 - 25 ns each.
@@ -714,9 +713,9 @@ __global__ __launch_bounds__(256) void sg_dirty_kernel(const float4* __restrict_
     unsigned long long b = 0;
     if (valid) {
         const float4 p = pts[i];
-        const int a0 = sg_cell_of(p.x, g.ox, g.inv_cell, g.na[0]) >> l, a1 = sg_cell_of(p.y, g.oy, g.inv_cell, g.na[1]) >> l, a2 = sg_cell_of(p.z, g.oz, g.inv_cell, g.na[2]) >> l;
-        const int n0 = ((g.na[0] - 1) >> l) + 1, n1 = ((g.na[1] - 1) >> l) + 1;
-        b = lvp->off[l] + ((unsigned long long)a2 * n1 + (unsigned long long)a1) * n0 + (unsigned long long)a0;
+        int a[3];
+        sg_cell3(g, p, a);
+        b = sg_level_bit(lvp->off[l], sg_level_dim(g.na[0], l), sg_level_dim(g.na[1], l), a[0] >> l, a[1] >> l, a[2] >> l);
     }
     const unsigned word = (unsigned)(b >> 5);
     unsigned mask = valid ? 1u << (unsigned)(b & 31u) : 0u;
@@ -752,22 +751,21 @@ __global__ __launch_bounds__(256) void sg_affected_kernel(const float4* __restri
             const float d2 = dk[orig];
             if (!(d2 < INFINITY)) hit = true; // fewer than k points so far: every appended point enters
             else {
-                const float r = sqrt_up(d2) * 1.00001f + (g.cell * 1e-3f + g.maxabs * 4e-6f);
+                const float r = sg_reach(g, d2, g.cell);
                 int l = lv_lmin;
                 while (l < lv_L - 1 && g.cell * (float)(1u << l) < r) ++l;
-                const int n0 = ((g.na[0] - 1) >> l) + 1, n1 = ((g.na[1] - 1) >> l) + 1, n2 = ((g.na[2] - 1) >> l) + 1;
+                const int n0 = sg_level_dim(g.na[0], l), n1 = sg_level_dim(g.na[1], l), n2 = sg_level_dim(g.na[2], l);
                 const unsigned long long off = lvp->off[l];
-                const int c0 = sg_cell_of(p.x, g.ox, g.inv_cell, g.na[0]) >> l, c1 = sg_cell_of(p.y, g.oy, g.inv_cell, g.na[1]) >> l,
-                          c2 = sg_cell_of(p.z, g.oz, g.inv_cell, g.na[2]) >> l;
+                int c[3];
+                sg_cell3(g, p, c);
                 for (int dz = -1; dz <= 1 && !hit; ++dz)
                     for (int dy = -1; dy <= 1 && !hit; ++dy) {
-                        const int z = c2 + dz, y = c1 + dy;
+                        const int z = (c[2] >> l) + dz, y = (c[1] >> l) + dy;
                         if (z < 0 || y < 0 || z >= n2 || y >= n1) continue;
-                        const unsigned long long row = off + ((unsigned long long)z * n1 + (unsigned long long)y) * n0;
                         for (int dx = -1; dx <= 1; ++dx) {
-                            const int x = c0 + dx;
+                            const int x = (c[0] >> l) + dx;
                             if (x < 0 || x >= n0) continue;
-                            const unsigned long long b = row + (unsigned long long)x;
+                            const unsigned long long b = sg_level_bit(off, n0, n1, x, y, z);
                             if (bits[b >> 5] & (1u << (b & 31u))) { hit = true; break; }
                         }
                     }
@@ -775,14 +773,8 @@ __global__ __launch_bounds__(256) void sg_affected_kernel(const float4* __restri
         }
         sel_sorted[i] = hit ? 1 : 0;
     }
-    const unsigned long long bal = __ballot(hit);
-    if (bal) {
-        const int lane = threadIdx.x & 63;
-        unsigned base = 0;
-        if (lane == 0) base = atomicAdd(n_sel, (unsigned)__popcll(bal));
-        base = (unsigned)__builtin_amdgcn_readlane((int)base, 0);
-        if (hit) list[base + (unsigned)__popcll(bal & ((1ull << lane) - 1ull))] = orig;
-    }
+    const unsigned slot = wave_append(n_sel, hit);
+    if (hit) list[slot] = orig;
 }
 
 // the groups of SGQ consecutive sorted positions (one wave of the cell kernel each) that hold a selected query: wlist[0] = count, then the groups
@@ -795,14 +787,8 @@ __global__ __launch_bounds__(256) void sg_wavelist_kernel(const unsigned char* _
         if ((gq + 1) * SGQ <= m) { const uint4 v = reinterpret_cast<const uint4*>(sel_sorted)[gq]; any = (v.x | v.y | v.z | v.w) != 0u; }
         else for (unsigned i = gq * SGQ; i < m; ++i) any |= sel_sorted[i] != 0;
     }
-    const unsigned long long bal = __ballot(any);
-    if (bal) {
-        const int lane = threadIdx.x & 63;
-        unsigned base = 0;
-        if (lane == 0) base = atomicAdd(&wlist[0], (unsigned)__popcll(bal));
-        base = (unsigned)__builtin_amdgcn_readlane((int)base, 0);
-        if (any) wlist[1 + base + (unsigned)__popcll(bal & ((1ull << lane) - 1ull))] = gq;
-    }
+    const unsigned slot = wave_append(&wlist[0], any);
+    if (any) wlist[1 + slot] = gq;
 }
 
 unsigned sg_queue_cap(int64_t m) { const int64_t waves = (m + SGQ - 1) / SGQ; return (unsigned)(((waves + SG_NQ - 1) / SG_NQ) * SGQ); }
@@ -821,6 +807,222 @@ void sg_launch_search(icpmi_ctx* c, SelfGridCtx* sg, const SgGrid& g, int k, int
                        (const uint2*)sg->d_queue, qcap, diag);
 }
 
+// ---- the steps of selfgrid_knn, in the order it takes them ---------------------------------------------------------------------------------
+struct SgBox { float lo[3], hi[3], maxabs; double ext[3]; };
+
+// An appended cloud whose previous sorted copy this grid still holds is built from THAT copy + the appended tail (src, keep_w = 1: w already
+// carries the original index): the points arrive nearly in the order they leave in, so the counting sort's atomics and its scatter are coalesced
+icpmi_status sg_take_previous(icpmi_ctx* c, SgPrev& pv, const float4* d_pts, int64_t m, const SelfGridSubset* sub, const float4*& src, int& keep_w)
+{
+    src = d_pts; keep_w = 0;
+    if (sub && sub->m_old > 0 && sub->m_old < m && pv.d_pts && pv.m == sub->m_old) {
+        if (pv.d_pts.ensure_keep(c, (size_t)m + 16, (size_t)sub->m_old) != ICPMI_OK) return ICPMI_ERR_HIP; // grow, keeping the sorted copy
+        hipLaunchKernelGGL(sg_tail_kernel, dim3((int)((m - sub->m_old + 255) / 256)), dim3(256), 0, c->stream, d_pts, sub->m_old, m, pv.d_pts);
+        src = pv.d_pts; keep_w = 1;
+    }
+    pv.m = 0; // (valid again once this build has left its copy behind)
+    return ICPMI_OK;
+}
+
+// The bounding box of pts[0 .. n) (one read-back: the table sizes depend on it), joined with the box of the previous sorted copy when the
+// build reads that copy (pts are the appended points then).  Clears the build's state first.
+icpmi_status sg_bounding_box(icpmi_ctx* c, SelfGridCtx* sg, const float4* pts, int64_t n, bool join_prev, SgBox& box)
+{
+    const int rblocks = (int)std::min<int64_t>((n + BBOX_WG - 1) / BBOX_WG, 256);
+    if (sg->d_part.ensure(c, (size_t)rblocks * 7) != ICPMI_OK) return ICPMI_ERR_HIP; // six floats of box and one count of non-finite points per workgroup
+    unsigned* d_nbad = reinterpret_cast<unsigned*>(sg->d_part.get() + (size_t)rblocks * 6);
+    hipLaunchKernelGGL(sg_reset_kernel, dim3(1), dim3(64), 0, c->stream, sg->d_state);
+    hipLaunchKernelGGL(bbox_partials_kernel<true>, dim3(rblocks), dim3(BBOX_WG), 0, c->stream, pts, n, sg->d_part.get(), d_nbad, 3.0e38f);
+    HIP_TRY(c, hipGetLastError());
+    std::vector<float> part((size_t)rblocks * 6);
+    std::vector<unsigned> nbad((size_t)rblocks);
+    if (read_back2(c, part.data(), sg->d_part, part.size() * sizeof(float), nbad.data(), d_nbad, nbad.size() * sizeof(unsigned)) != ICPMI_OK) return ICPMI_ERR_HIP;
+    unsigned bad = 0;
+    for (unsigned v : nbad) bad += v;
+    for (int r = 0; r < 3; ++r) { box.lo[r] = join_prev ? sg->prev.lo[r] : INFINITY; box.hi[r] = join_prev ? sg->prev.hi[r] : -INFINITY; }
+    for (int b = 0; b < rblocks; ++b)
+        for (int r = 0; r < 3; ++r) { box.lo[r] = fminf(box.lo[r], part[(size_t)b * 6 + r]); box.hi[r] = fmaxf(box.hi[r], part[(size_t)b * 6 + 3 + r]); }
+    box.maxabs = 0.f;
+    for (int r = 0; r < 3; ++r) {
+        if (bad || !(box.lo[r] <= box.hi[r]) || !std::isfinite(box.lo[r]) || !std::isfinite(box.hi[r])) { c->last_error = "set_map: non-finite coordinates in the map cloud"; return ICPMI_ERR_INVALID_ARG; }
+        box.maxabs = fmaxf(box.maxabs, fmaxf(fabsf(box.lo[r]), fabsf(box.hi[r])));
+        box.ext[r] = (double)box.hi[r] - box.lo[r];
+    }
+    return ICPMI_OK;
+}
+
+// the grid of A-cell edge `cell_d` over the box (the edge grows until T fits)
+SgGrid sg_make_grid(const SgBox& box, double cell_d)
+{
+    SgGrid g;
+    const double max_ext = std::max(box.ext[0], std::max(box.ext[1], box.ext[2]));
+    double cell = std::max(cell_d, std::max(max_ext * 1e-6, 1e-6));
+    for (int it = 0; it < 96; ++it) { // keep T within 2^24 entries
+        int bits = 0;
+        for (int r = 0; r < 3; ++r) { const long long nb = ((long long)floor(box.ext[r] / cell) + 1 + 3) / 4; int b = 0; while ((1ll << b) < nb) ++b; bits += b; }
+        if (bits <= 24) break;
+        cell *= 1.26;
+    }
+    g.ox = box.lo[0]; g.oy = box.lo[1]; g.oz = box.lo[2]; g.cell = (float)cell; g.inv_cell = 1.0f / g.cell; g.maxabs = box.maxabs;
+    int pos = 0, maxb = 0;
+    for (int r = 0; r < 3; ++r) {
+        g.na[r] = (int)floorf((box.hi[r] - box.lo[r]) * g.inv_cell) + 1;
+        const int nb = (g.na[r] + 3) / 4;
+        int b = 0; while ((1 << b) < nb) ++b;
+        g.nbits[r] = b; g.mask[r] = 0; maxb = std::max(maxb, b);
+    }
+    for (int j = 0; j < maxb; ++j) for (int r = 0; r < 3; ++r) if (j < g.nbits[r]) g.mask[r] |= 1u << pos++;
+    g.tsize = 1 << pos;
+    return g;
+}
+
+// The edge of an A-cell to begin with, and how many builds may correct it.  What the search pays for is the number of points an average POINT
+// finds in its cell (size-biased occupancy: sum of squared cell counts / points; target: where it should be); sq_seen: that sum as the
+// previous build of this handle left it in the host-mapped page (0: nothing there).
+double sg_first_cell(const SgTuned& t, const SgBox& box, int64_t m, int k, double target, unsigned long long sq_seen, int& trials)
+{
+    const bool like_before = t.cell > 0.f && t.m > 0 && t.k == k && (double)m > 0.7 * (double)t.m && (double)m < 1.4 * (double)t.m;
+    trials = 1;
+    if (like_before) {
+        double cell = t.cell;
+        const double sb = (double)sq_seen / (double)t.m;
+        if (sb > 0.0 && !(sb > 0.85 * target && sb < 1.18 * target)) cell *= std::min(2.0, std::max(0.5, sqrt(target / sb))); // surfaces: occupancy ~ edge^2
+        return cell;
+    }
+    const double vol = std::max(box.ext[0], 1e-3) * std::max(box.ext[1], 1e-3) * std::max(box.ext[2], 1e-3);
+    trials = 5; // a cloud this handle has not seen the like of: build, look at the occupancy, correct
+    return cbrt(vol / (double)m) * 1.2;
+}
+
+// one build of the grid g over src[0 .. m): the arrays, then key, scan, scatter, block sort (again: not the call's first build -- the state is cleared)
+icpmi_status sg_build(icpmi_ctx* c, SelfGridCtx* sg, const SgGrid& g, const float4* src, int64_t m, int keep_w, bool again)
+{
+    const int blocks256 = (int)((m + 255) / 256);
+    const unsigned blocks_max = (unsigned)std::min<int64_t>(m, (int64_t)g.tsize);
+    bool fresh = false;
+    if (sg->d_tcnt.ensure(c, (size_t)g.tsize + 2, &fresh) != ICPMI_OK) return ICPMI_ERR_HIP;
+    if (fresh || !sg->tcnt_clean) HIP_TRY(c, hipMemsetAsync(sg->d_tcnt, 0, sg->d_tcnt.capacity() * sizeof(unsigned), c->stream));
+    sg->tcnt_clean = false;
+    if (sg->d_tstart.ensure(c, (size_t)g.tsize + 2) != ICPMI_OK || sg->d_tbid.ensure(c, (size_t)g.tsize + 1) != ICPMI_OK ||
+        sg->d_blist.ensure(c, (size_t)blocks_max + 1) != ICPMI_OK || sg->d_f.ensure(c, (size_t)blocks_max * SG_F + 1) != ICPMI_OK ||
+        sg->d_coarse.ensure(c, (size_t)m + 16) != ICPMI_OK || sg->d_queue.ensure(c, (size_t)sg_queue_cap(m) * SG_NQ + 1) != ICPMI_OK || sg->d_inv.ensure(c, (size_t)m + 1) != ICPMI_OK ||
+        c->d_keys.ensure(c, (size_t)m) != ICPMI_OK || c->d_map_sorted.ensure(c, (size_t)m + 16) != ICPMI_OK)
+        return ICPMI_ERR_HIP;
+    if (again) hipLaunchKernelGGL(sg_reset_kernel, dim3(1), dim3(64), 0, c->stream, sg->d_state);
+    // (tiles per workgroup: enough workgroups to fill the chip, as few atomics on the block-id counter as that allows)
+    const int key_tiles = (int)std::max<int64_t>(1, std::min<int64_t>(SG_KEY_TILES, blocks256 / 2048));
+    hipLaunchKernelGGL(sg_key_kernel, dim3((blocks256 + key_tiles - 1) / key_tiles), dim3(256), 0, c->stream, src, m, g, c->d_keys, sg->d_tcnt, sg->d_tbid, sg->d_blist,
+                       sg->d_state, key_tiles);
+    HIP_TRY(c, hipGetLastError());
+    if (device_exclusive_scan_cursor(c, sg->d_tcnt, sg->d_tstart, g.tsize, (unsigned)m, true) != ICPMI_OK) return ICPMI_ERR_HIP;
+    sg->tcnt_clean = true;
+    hipLaunchKernelGGL(sg_scatter_kernel, dim3(blocks256), dim3(256), 0, c->stream, src, m, (const unsigned*)c->d_keys, sg->d_tstart + 1, sg->d_coarse, keep_w);
+    hipLaunchKernelGGL(sg_block_sort_kernel, dim3(std::max(1u, std::min(blocks_max, 8192u))), dim3(64), 0, c->stream, (const float4*)sg->d_coarse,
+                       c->d_map_sorted, g, (const unsigned*)sg->d_tstart, (const uint4*)sg->d_blist, sg->d_f, sg->d_inv, sg->d_state);
+    HIP_TRY(c, hipGetLastError());
+    return ICPMI_OK;
+}
+
+// the sum of squared A-cell counts the block sort of the last build left (one read-back)
+icpmi_status sg_read_sq(icpmi_ctx* c, SelfGridCtx* sg, unsigned long long& sq)
+{
+    unsigned long long sqp[64];
+    if (read_back(c, sqp, sg->d_state->sqpart, sizeof sqp) != ICPMI_OK) return ICPMI_ERR_HIP;
+    sq = 0;
+    for (int i = 0; i < 64; ++i) sq += sqp[i];
+    return ICPMI_OK;
+}
+// the edge the next trial should take after a build of edge `cell` whose points saw sq; 0: keep this build
+double sg_retune(unsigned long long sq, int64_t m, double target, float cell)
+{
+    const double sb = (double)sq / (double)m;
+    if (sb > 0.85 * target && sb < 1.18 * target) return 0.0;
+    const double next = (double)cell * std::min(4.0, std::max(0.25, sqrt(target / sb)));
+    if (fabs(next - (double)cell) < 0.05 * (double)cell) return 0.0;
+    return next;
+}
+
+// a tracked cloud (the resident map of append-only updates): leave the sorted copy behind for the build of the next append
+icpmi_status sg_keep_sorted_copy(icpmi_ctx* c, SgPrev& pv, int64_t m, const SgBox& box)
+{
+    if (pv.d_pts.ensure(c, (size_t)m + 16) != ICPMI_OK) return ICPMI_ERR_HIP; // (a reallocation drops the old content: it is rewritten below)
+    HIP_TRY(c, hipMemcpyAsync(pv.d_pts, c->d_map_sorted, (size_t)m * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
+    pv.m = m;
+    for (int r = 0; r < 3; ++r) { pv.lo[r] = box.lo[r]; pv.hi[r] = box.hi[r]; }
+    return ICPMI_OK;
+}
+
+// the level table of the subset search over a grid of na A-cells; returns the bits of all its bitmaps
+unsigned long long sg_level_table(const int na[3], SgLevels& lv)
+{
+    auto cells_at = [&](int l) { return (unsigned long long)sg_level_dim(na[0], l) * (unsigned long long)sg_level_dim(na[1], l) * (unsigned long long)sg_level_dim(na[2], l); };
+    unsigned long long bits_total = 0;
+    int L = 0;
+    for (; L < 26; ++L) if (cells_at(L) == 1) { ++L; break; }
+    lv.L = L;
+    // fine levels of a huge sparse box are folded into the first level whose bitmaps fit 2^31 bits (256 MB): conservative, rarely needed
+    for (lv.lmin = 0; lv.lmin < L - 1; ++lv.lmin) {
+        bits_total = 0;
+        for (int l = lv.lmin; l < L; ++l) bits_total += cells_at(l);
+        if (bits_total <= (1ull << 31)) break;
+    }
+    bits_total = 0;
+    for (int l = lv.lmin; l < L; ++l) { lv.off[l] = bits_total; bits_total += cells_at(l); }
+    return bits_total;
+}
+
+// The subset of an appended cloud: the cells the appended points fell into, the points whose neighbourhood they may have entered (qsel: by
+// sorted position; sub->d_list / n_sel: their original indices, one small read-back for the count: the normals are solved from it), the
+// groups of the cell kernel that hold one (wlist)
+icpmi_status sg_select_subset(icpmi_ctx* c, SelfGridCtx* sg, const SgGrid& g, const float4* d_pts, int64_t m, SelfGridSubset* sub, int diag,
+                              const unsigned char*& qsel, const unsigned*& wlist)
+{
+    SgLevels lv{};
+    const unsigned long long bits_total = sg_level_table(g.na, lv);
+    const size_t words = (size_t)((bits_total + 31) / 32) + 128; // + 64 words: the counter of the selection, + 64: the level table
+    // d_sel: [0, m) by sorted position, then (4-byte aligned) the list of the selected original indices
+    const size_t list_at = ((size_t)m + 3) / 4 * 4;
+    const size_t groups = (size_t)((m + SGQ - 1) / SGQ);
+    if (sg->d_dirty.ensure(c, words) != ICPMI_OK || sg->d_sel.ensure(c, list_at + (size_t)4 * (m + groups + 2) + 64) != ICPMI_OK) return ICPMI_ERR_HIP;
+    static_assert(sizeof(SgLevels) <= 64 * sizeof(unsigned), "level table");
+    HIP_TRY(c, hipMemsetAsync(sg->d_dirty, 0, words * sizeof(unsigned), c->stream));
+    unsigned* n_sel = sg->d_dirty + (words - 128);
+    const SgLevels* d_lv = reinterpret_cast<const SgLevels*>(sg->d_dirty + (words - 64));
+    { const icpmi_status us = upload_small(c, sg->d_dirty + (words - 64), &lv, sizeof lv); if (us != ICPMI_OK) return us; }
+    unsigned* list = reinterpret_cast<unsigned*>(sg->d_sel + list_at);
+    const int64_t added = m - sub->m_old;
+    hipLaunchKernelGGL(sg_dirty_kernel, dim3((int)((added + 255) / 256), lv.L - lv.lmin), dim3(256), 0, c->stream, d_pts, sub->m_old, m, g, d_lv, sg->d_dirty);
+    hipLaunchKernelGGL(sg_affected_kernel, dim3((int)((m + 255) / 256)), dim3(256), 0, c->stream, (const float4*)c->d_map_sorted, m, (unsigned)sub->m_old, sub->d_dk, g, d_lv,
+                       (const unsigned*)sg->d_dirty, sg->d_sel, list, n_sel);
+    HIP_TRY(c, hipGetLastError());
+    unsigned* d_wl = list + m; // [0] = count (cleared here), then the groups
+    HIP_TRY(c, hipMemsetAsync(d_wl, 0, sizeof(unsigned), c->stream));
+    hipLaunchKernelGGL(sg_wavelist_kernel, dim3((int)((groups + 255) / 256)), dim3(256), 0, c->stream, (const unsigned char*)sg->d_sel, (unsigned)m, d_wl);
+    HIP_TRY(c, hipGetLastError());
+    qsel = sg->d_sel; wlist = d_wl;
+    sub->d_list = list;
+    unsigned cnt = 0;
+    if (read_back(c, &cnt, n_sel, sizeof cnt) != ICPMI_OK) return ICPMI_ERR_HIP;
+    sub->n_sel = (int64_t)cnt;
+    if (diag) fprintf(stderr, "[icpmi self-knn] subset: %lld of %lld points searched (%lld appended), levels %d..%d, %llu bitmap bits\n", (long long)sub->n_sel,
+                      (long long)m, (long long)added, lv.lmin, lv.L - 1, bits_total);
+    return ICPMI_OK;
+}
+
+// the ICPMI_SELF_DIAG line of a call
+void sg_report(icpmi_ctx* c, SelfGridCtx* sg, const SgGrid& g, int64_t m, int k, double target)
+{
+    SgState hs{};
+    unsigned qtot = 0;
+    unsigned long long sq = 0;
+    if (read_back(c, &hs, sg->d_state, sizeof hs) == ICPMI_OK) for (int i = 0; i < 64; ++i) { qtot += hs.qcount[i]; sq += hs.sqpart[i]; }
+    if (qtot || hs.nblk)
+        fprintf(stderr, "[icpmi self-knn] m %lld k %d: A-cell %.3f (%d x %d x %d), T %d entries, %u blocks, size-biased occupancy %.1f (target %.1f); "
+                        "%u queries (%.2f %%) through the levels, mean end level %.2f\n",
+                (long long)m, k, (double)g.cell, g.na[0], g.na[1], g.na[2], g.tsize, hs.nblk, (double)sq / (double)m, target, qtot,
+                100.0 * qtot / (double)m, qtot ? (double)hs.levels / (double)qtot : 0.0);
+}
+
 } // namespace
 
 void selfgrid_destroy(icpmi_ctx* c)
@@ -837,15 +1039,15 @@ void selfgrid_destroy(icpmi_ctx* c)
 icpmi_status selfgrid_debug_info(icpmi_ctx* c, uint64_t info[8])
 {
     SelfGridCtx* sg = c->sg;
-    if (!sg || !sg->d_state || sg->seq == 0) { c->last_error = "self knn: no grid was built on this handle"; return ICPMI_ERR_UNSUPPORTED; }
+    if (!sg || !sg->d_state || sg->last.seq == 0) { c->last_error = "self knn: no grid was built on this handle"; return ICPMI_ERR_UNSUPPORTED; }
     unsigned qc[SG_NQ];
     if (read_back(c, qc, sg->d_state->qcount, sizeof qc) != ICPMI_OK) return ICPMI_ERR_HIP;
     uint64_t queued = 0;
     for (int i = 0; i < SG_NQ; ++i) queued += qc[i];
     uint32_t cell_bits;
-    memcpy(&cell_bits, &sg->cell, sizeof cell_bits);
-    info[0] = cell_bits; info[1] = (uint64_t)sg->last_na[0]; info[2] = (uint64_t)sg->last_na[1]; info[3] = (uint64_t)sg->last_na[2];
-    info[4] = (uint64_t)sg->last_tsize; info[5] = queued; info[6] = (uint64_t)sg->last_trials; info[7] = 0;
+    memcpy(&cell_bits, &sg->tuned.cell, sizeof cell_bits);
+    info[0] = cell_bits; info[1] = (uint64_t)sg->last.na[0]; info[2] = (uint64_t)sg->last.na[1]; info[3] = (uint64_t)sg->last.na[2];
+    info[4] = (uint64_t)sg->last.tsize; info[5] = queued; info[6] = (uint64_t)sg->last.trials; info[7] = 0;
     return ICPMI_OK;
 }
 
@@ -861,189 +1063,43 @@ icpmi_status selfgrid_knn(icpmi_ctx* c, const float4* d_pts, int64_t m, int k, i
     if (!c->sg) { c->sg = new (std::nothrow) SelfGridCtx(); if (!c->sg) { c->last_error = "out of host memory"; return ICPMI_ERR_HIP; } }
     SelfGridCtx* sg = c->sg;
     if (!sg->d_state) HIP_TRY(c, sg->d_state.alloc(1));
-    // ---- r6: an appended cloud whose previous sorted copy this grid still holds is built from THAT copy + the appended tail: the points arrive
-    //      nearly in the order they leave in, so the counting sort's atomics and its scatter are coalesced (10 M points: sg_key 0.47 -> , sg_scatter 0.68 -> ms)
-    const float4* src = d_pts;
-    int keep_w = 0;
-    if (sub && sub->m_old > 0 && sub->m_old < m && sg->d_prev && sg->prev_m == sub->m_old) {
-        if (sg->d_prev.ensure_keep(c, (size_t)m + 16, (size_t)sub->m_old) != ICPMI_OK) return ICPMI_ERR_HIP; // grow, keeping the sorted copy
-        hipLaunchKernelGGL(sg_tail_kernel, dim3((int)((m - sub->m_old + 255) / 256)), dim3(256), 0, c->stream, d_pts, sub->m_old, m, sg->d_prev);
-        src = sg->d_prev; keep_w = 1;
-    }
-    sg->prev_m = 0; // (valid again once this build has left its copy behind)
-    // ---- bounding box (one read-back: the table sizes depend on it) ----
-    // (an appended cloud built from its previous copy: the box of the appended points, joined with the box that copy had)
-    const int64_t bb_n = keep_w ? m - sub->m_old : m;
-    const float4* bb_src = keep_w ? d_pts + sub->m_old : src;
-    const int rblocks = (int)std::min<int64_t>((bb_n + BBOX_WG - 1) / BBOX_WG, 256);
-    if (sg->d_part.ensure(c, (size_t)rblocks * 7) != ICPMI_OK) return ICPMI_ERR_HIP; // six floats of box and one count of non-finite points per workgroup
-    unsigned* d_nbad = reinterpret_cast<unsigned*>(sg->d_part.get() + (size_t)rblocks * 6);
-    hipLaunchKernelGGL(sg_reset_kernel, dim3(1), dim3(64), 0, c->stream, sg->d_state);
-    hipLaunchKernelGGL(bbox_partials_kernel<true>, dim3(rblocks), dim3(BBOX_WG), 0, c->stream, bb_src, bb_n, sg->d_part.get(), d_nbad, 3.0e38f);
-    HIP_TRY(c, hipGetLastError());
-    std::vector<float> part((size_t)rblocks * 6);
-    std::vector<unsigned> nbad((size_t)rblocks);
-    if (read_back2(c, part.data(), sg->d_part, part.size() * sizeof(float), nbad.data(), d_nbad, nbad.size() * sizeof(unsigned)) != ICPMI_OK) return ICPMI_ERR_HIP;
-    unsigned bad = 0;
-    for (unsigned v : nbad) bad += v;
-    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY}, maxabs = 0.f;
-    if (keep_w) for (int r = 0; r < 3; ++r) { lo[r] = sg->prev_lo[r]; hi[r] = sg->prev_hi[r]; }
-    for (int b = 0; b < rblocks; ++b)
-        for (int r = 0; r < 3; ++r) { lo[r] = fminf(lo[r], part[(size_t)b * 6 + r]); hi[r] = fmaxf(hi[r], part[(size_t)b * 6 + 3 + r]); }
-    for (int r = 0; r < 3; ++r) {
-        if (bad || !(lo[r] <= hi[r]) || !std::isfinite(lo[r]) || !std::isfinite(hi[r])) { c->last_error = "set_map: non-finite coordinates in the map cloud"; return ICPMI_ERR_INVALID_ARG; }
-        maxabs = fmaxf(maxabs, fmaxf(fabsf(lo[r]), fabsf(hi[r])));
-    }
-    const double ext[3] = {(double)hi[0] - lo[0], (double)hi[1] - lo[1], (double)hi[2] - lo[2]};
-    const double max_ext = std::max(ext[0], std::max(ext[1], ext[2]));
+    static const int diag = [] { const char* e = getenv("ICPMI_SELF_DIAG"); return e ? atoi(e) : 0; }();
+    icpmi_status s;
 
-    // ---- the edge of an A-cell.  What the search pays for is the number of points an average POINT finds in its cell (size-biased occupancy:
-    //      sum of squared cell counts / points); the previous build of this handle left that number in the host-mapped page ----
+    const float4* src;
+    int keep_w;
+    if ((s = sg_take_previous(c, sg->prev, d_pts, m, sub, src, keep_w)) != ICPMI_OK) return s;
+    SgBox box;
+    const int64_t from = keep_w ? sub->m_old : 0; // (built from the previous copy: the box of the appended points, joined with the box that copy had)
+    if ((s = sg_bounding_box(c, sg, d_pts + from, m - from, keep_w != 0, box)) != ICPMI_OK) return s;
+
     const double target = std::max(2.0, 0.8 * (double)k);
     volatile unsigned long long* h_sq = c->h_progress ? reinterpret_cast<volatile unsigned long long*>(c->h_progress + ICPMI_PROGRESS_SELF_WORD) : nullptr;
     unsigned long long* d_sq = c->d_progress ? reinterpret_cast<unsigned long long*>(c->d_progress + ICPMI_PROGRESS_SELF_WORD) : nullptr;
-    auto make = [&](double cell_d) {
-        SgGrid g;
-        double cell = std::max(cell_d, std::max(max_ext * 1e-6, 1e-6));
-        for (int it = 0; it < 96; ++it) { // keep T within 2^24 entries
-            int bits = 0;
-            for (int r = 0; r < 3; ++r) { const long long nb = ((long long)floor(ext[r] / cell) + 1 + 3) / 4; int b = 0; while ((1ll << b) < nb) ++b; bits += b; }
-            if (bits <= 24) break;
-            cell *= 1.26;
-        }
-        g.ox = lo[0]; g.oy = lo[1]; g.oz = lo[2]; g.cell = (float)cell; g.inv_cell = 1.0f / g.cell; g.maxabs = maxabs;
-        int pos = 0, maxb = 0;
-        for (int r = 0; r < 3; ++r) {
-            g.na[r] = (int)floorf((hi[r] - lo[r]) * g.inv_cell) + 1;
-            const int nb = (g.na[r] + 3) / 4;
-            int b = 0; while ((1 << b) < nb) ++b;
-            g.nbits[r] = b; g.mask[r] = 0; maxb = std::max(maxb, b);
-        }
-        for (int j = 0; j < maxb; ++j) for (int r = 0; r < 3; ++r) if (j < g.nbits[r]) g.mask[r] |= 1u << pos++;
-        g.tsize = 1 << pos;
-        return g;
-    };
-    const bool like_before = sg->cell > 0.f && sg->m > 0 && sg->k == k && (double)m > 0.7 * (double)sg->m && (double)m < 1.4 * (double)sg->m;
-    double cell = 0.0;
-    int trials = 1;
-    if (like_before) {
-        cell = sg->cell;
-        const double sb = h_sq ? (double)*h_sq / (double)sg->m : 0.0;
-        if (sb > 0.0 && !(sb > 0.85 * target && sb < 1.18 * target)) cell *= std::min(2.0, std::max(0.5, sqrt(target / sb))); // surfaces: occupancy ~ edge^2
-    } else {
-        const double vol = std::max(ext[0], 1e-3) * std::max(ext[1], 1e-3) * std::max(ext[2], 1e-3);
-        cell = cbrt(vol / (double)m) * 1.2;
-        trials = 5; // a cloud this handle has not seen the like of: build, look at the occupancy, correct
-    }
-    static const int diag = [] { const char* e = getenv("ICPMI_SELF_DIAG"); return e ? atoi(e) : 0; }();
-    const int blocks256 = (int)((m + 255) / 256);
+    int trials;
+    double cell = sg_first_cell(sg->tuned, box, m, k, target, h_sq ? *h_sq : 0ull, trials);
     SgGrid g{};
-    unsigned blocks_max = 0;
     int built = 0;
     for (int trial = 0; trial < trials; ++trial) {
-        g = make(cell);
+        g = sg_make_grid(box, cell);
         built = trial + 1;
-        blocks_max = (unsigned)std::min<int64_t>(m, (int64_t)g.tsize);
-        bool fresh = false;
-        if (sg->d_tcnt.ensure(c, (size_t)g.tsize + 2, &fresh) != ICPMI_OK) return ICPMI_ERR_HIP;
-        if (fresh || !sg->tcnt_clean) HIP_TRY(c, hipMemsetAsync(sg->d_tcnt, 0, sg->d_tcnt.capacity() * sizeof(unsigned), c->stream));
-        sg->tcnt_clean = false;
-        if (sg->d_tstart.ensure(c, (size_t)g.tsize + 2) != ICPMI_OK || sg->d_tbid.ensure(c, (size_t)g.tsize + 1) != ICPMI_OK ||
-            sg->d_blist.ensure(c, (size_t)blocks_max + 1) != ICPMI_OK || sg->d_f.ensure(c, (size_t)blocks_max * SG_F + 1) != ICPMI_OK ||
-            sg->d_coarse.ensure(c, (size_t)m + 16) != ICPMI_OK || sg->d_queue.ensure(c, (size_t)sg_queue_cap(m) * SG_NQ + 1) != ICPMI_OK || sg->d_inv.ensure(c, (size_t)m + 1) != ICPMI_OK ||
-            c->d_keys.ensure(c, (size_t)m) != ICPMI_OK || c->d_map_sorted.ensure(c, (size_t)m + 16) != ICPMI_OK)
-            return ICPMI_ERR_HIP;
-        if (trial > 0) hipLaunchKernelGGL(sg_reset_kernel, dim3(1), dim3(64), 0, c->stream, sg->d_state);
-        // (tiles per workgroup: enough workgroups to fill the chip, as few atomics on the block-id counter as that allows)
-        const int key_tiles = (int)std::max<int64_t>(1, std::min<int64_t>(SG_KEY_TILES, blocks256 / 2048));
-        hipLaunchKernelGGL(sg_key_kernel, dim3((blocks256 + key_tiles - 1) / key_tiles), dim3(256), 0, c->stream, src, m, g, c->d_keys, sg->d_tcnt, sg->d_tbid, sg->d_blist,
-                           sg->d_state, key_tiles);
-        HIP_TRY(c, hipGetLastError());
-        if (device_exclusive_scan_cursor(c, sg->d_tcnt, sg->d_tstart, g.tsize, (unsigned)m, true) != ICPMI_OK) return ICPMI_ERR_HIP;
-        sg->tcnt_clean = true;
-        hipLaunchKernelGGL(sg_scatter_kernel, dim3(blocks256), dim3(256), 0, c->stream, src, m, (const unsigned*)c->d_keys, sg->d_tstart + 1, sg->d_coarse, keep_w);
-        hipLaunchKernelGGL(sg_block_sort_kernel, dim3(std::max(1u, std::min(blocks_max, 8192u))), dim3(64), 0, c->stream, (const float4*)sg->d_coarse,
-                           c->d_map_sorted, g, (const unsigned*)sg->d_tstart, (const uint4*)sg->d_blist, sg->d_f, sg->d_inv, sg->d_state);
-        HIP_TRY(c, hipGetLastError());
+        if ((s = sg_build(c, sg, g, src, m, keep_w, trial > 0)) != ICPMI_OK) return s;
         if (trial + 1 >= trials) break;
-        unsigned long long sqp[64], sq = 0;
-        if (read_back(c, sqp, sg->d_state->sqpart, sizeof sqp) != ICPMI_OK) return ICPMI_ERR_HIP;
-        for (int i = 0; i < 64; ++i) sq += sqp[i];
-        const double sb = (double)sq / (double)m;
-        if (sb > 0.85 * target && sb < 1.18 * target) break;
-        const double next = (double)g.cell * std::min(4.0, std::max(0.25, sqrt(target / sb)));
-        if (fabs(next - (double)g.cell) < 0.05 * (double)g.cell) break;
+        unsigned long long sq;
+        if ((s = sg_read_sq(c, sg, sq)) != ICPMI_OK) return s;
+        const double next = sg_retune(sq, m, target, g.cell);
+        if (next == 0.0) break;
         cell = next;
     }
-    sg->cell = g.cell; sg->m = m; sg->k = k; ++sg->seq;
-    sg->last_na[0] = g.na[0]; sg->last_na[1] = g.na[1]; sg->last_na[2] = g.na[2]; sg->last_tsize = g.tsize; sg->last_trials = built;
-    if (sub) { // a tracked cloud (the resident map of append-only updates): leave the sorted copy behind for the build of the next append
-        if (sg->d_prev.ensure(c, (size_t)m + 16) != ICPMI_OK) return ICPMI_ERR_HIP; // (a reallocation drops the old content: it is rewritten below)
-        HIP_TRY(c, hipMemcpyAsync(sg->d_prev, c->d_map_sorted, (size_t)m * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
-        sg->prev_m = m;
-        for (int r = 0; r < 3; ++r) { sg->prev_lo[r] = lo[r]; sg->prev_hi[r] = hi[r]; }
-    }
+    sg->tuned.cell = g.cell; sg->tuned.m = m; sg->tuned.k = k;
+    sg->last.na[0] = g.na[0]; sg->last.na[1] = g.na[1]; sg->last.na[2] = g.na[2]; sg->last.tsize = g.tsize; sg->last.trials = built; ++sg->last.seq;
+    if (sub && (s = sg_keep_sorted_copy(c, sg->prev, m, box)) != ICPMI_OK) return s;
 
-    // ---- the subset of an appended cloud ----
     const unsigned char* qsel = nullptr;
     const unsigned* wlist = nullptr;
-    if (sub && sub->m_old > 0 && sub->m_old < m && sub->d_dk) {
-        SgLevels lv{};
-        unsigned long long bits_total = 0;
-        auto cells_at = [&](int l) { return (unsigned long long)(((g.na[0] - 1) >> l) + 1) * (unsigned long long)(((g.na[1] - 1) >> l) + 1) * (unsigned long long)(((g.na[2] - 1) >> l) + 1); };
-        int L = 0;
-        for (; L < 26; ++L) if (cells_at(L) == 1) { ++L; break; }
-        lv.L = L;
-        // fine levels of a huge sparse box are folded into the first level whose bitmaps fit 2^31 bits (256 MB): conservative, rarely needed
-        for (lv.lmin = 0; lv.lmin < L - 1; ++lv.lmin) {
-            bits_total = 0;
-            for (int l = lv.lmin; l < L; ++l) bits_total += cells_at(l);
-            if (bits_total <= (1ull << 31)) break;
-        }
-        bits_total = 0;
-        for (int l = lv.lmin; l < L; ++l) { lv.off[l] = bits_total; bits_total += cells_at(l); }
-        const size_t words = (size_t)((bits_total + 31) / 32) + 128; // + 64 words: the counter of the selection, + 64: the level table
-        // d_sel: [0, m) by sorted position, then (4-byte aligned) the list of the selected original indices
-        const size_t list_at = ((size_t)m + 3) / 4 * 4;
-        const size_t groups = (size_t)((m + SGQ - 1) / SGQ);
-        if (sg->d_dirty.ensure(c, words) != ICPMI_OK || sg->d_sel.ensure(c, list_at + (size_t)4 * (m + groups + 2) + 64) != ICPMI_OK) return ICPMI_ERR_HIP;
-        static_assert(sizeof(SgLevels) <= 64 * sizeof(unsigned), "level table");
-        HIP_TRY(c, hipMemsetAsync(sg->d_dirty, 0, words * sizeof(unsigned), c->stream));
-        unsigned* n_sel = sg->d_dirty + (words - 128);
-        const SgLevels* d_lv = reinterpret_cast<const SgLevels*>(sg->d_dirty + (words - 64));
-        { const icpmi_status us = upload_small(c, sg->d_dirty + (words - 64), &lv, sizeof lv); if (us != ICPMI_OK) return us; }
-        unsigned* list = reinterpret_cast<unsigned*>(sg->d_sel + list_at);
-        const int64_t added = m - sub->m_old;
-        hipLaunchKernelGGL(sg_dirty_kernel, dim3((int)((added + 255) / 256), lv.L - lv.lmin), dim3(256), 0, c->stream, d_pts, sub->m_old, m, g, d_lv, sg->d_dirty);
-        hipLaunchKernelGGL(sg_affected_kernel, dim3(blocks256), dim3(256), 0, c->stream, (const float4*)c->d_map_sorted, m, (unsigned)sub->m_old, sub->d_dk, g, d_lv,
-                           (const unsigned*)sg->d_dirty, sg->d_sel, list, n_sel);
-        HIP_TRY(c, hipGetLastError());
-        unsigned* d_wl = list + m; // [0] = count (cleared here), then the groups
-        HIP_TRY(c, hipMemsetAsync(d_wl, 0, sizeof(unsigned), c->stream));
-        hipLaunchKernelGGL(sg_wavelist_kernel, dim3((int)((groups + 255) / 256)), dim3(256), 0, c->stream, (const unsigned char*)sg->d_sel, (unsigned)m, d_wl);
-        HIP_TRY(c, hipGetLastError());
-        qsel = sg->d_sel; wlist = d_wl;
-        sub->d_list = list;
-        {   // the size of the list: the normals are solved from it (one small read-back)
-            unsigned cnt = 0;
-            if (read_back(c, &cnt, n_sel, sizeof cnt) != ICPMI_OK) return ICPMI_ERR_HIP;
-            sub->n_sel = (int64_t)cnt;
-            if (diag) fprintf(stderr, "[icpmi self-knn] subset: %lld of %lld points searched (%lld appended), levels %d..%d, %llu bitmap bits\n", (long long)sub->n_sel,
-                              (long long)m, (long long)added, lv.lmin, lv.L - 1, bits_total);
-        }
-    }
-    // ---- search ----
+    if (sub && sub->m_old > 0 && sub->m_old < m && sub->d_dk && (s = sg_select_subset(c, sg, g, d_pts, m, sub, diag, qsel, wlist)) != ICPMI_OK) return s;
     sg_launch_search(c, sg, g, k, m, d_sidx, d_d2, d_sq, diag, qsel, wlist, sub ? sub->n_sel : 0);
     HIP_TRY(c, hipGetLastError());
-    if (diag) {
-        SgState hs{};
-        unsigned qtot = 0;
-        if (read_back(c, &hs, sg->d_state, sizeof hs) == ICPMI_OK) for (int i = 0; i < 64; ++i) qtot += hs.qcount[i];
-        if (qtot || hs.nblk)
-            fprintf(stderr, "[icpmi self-knn] m %lld k %d: A-cell %.3f (%d x %d x %d), T %d entries, %u blocks, size-biased occupancy %.1f (target %.1f); "
-                            "%u queries (%.2f %%) through the levels, mean end level %.2f\n",
-                    (long long)m, k, (double)g.cell, g.na[0], g.na[1], g.na[2], g.tsize, hs.nblk, (double)hs.sq / (double)m, target, qtot,
-                    100.0 * qtot / (double)m, qtot ? (double)hs.levels / (double)qtot : 0.0);
-    }
+    if (diag) sg_report(c, sg, g, m, k, target);
     return ICPMI_OK;
 }
