@@ -729,6 +729,88 @@ icpmi_status icpmi_deskew(icpmi_handle h, const float* in4, int64_t n, const flo
 icpmi_status icpmi_deskew_dev(icpmi_handle h, const float* d_in4, int64_t n, const float* d_t_rel, const icpmi_sweep_motion* m,
                               float* d_out4, const float* d_in_normals3, float* d_out_normals3);
 
+/* Sweep registration: the sensor's motion WITHIN one scan estimated by ICP, for callers that have no IMU or odometry to hand to
+ * icpmi_deskew (continuous-time ICP in its simplest linear form: Dellenbach et al. 2022, CT-ICP, with two poses per sweep).  Not
+ * libpointmatcher's; off unless called.  Served on a 3-D handle with ICPMI_MIN_POINT_TO_PLANE and a map with normals.
+ *
+ * Unknowns: the sensor's poses in the map frame at sweep begin, T_b, and at sweep end, T_e, held on the host in double as translation
+ * + unit quaternion.  Point i has the time fraction
+ *   alpha_i = clamp(((double)t_rel[i] * time_unit_s - begin_s) / (end_s - begin_s), 0, 1)      (fp64, rounded once to float32)
+ * kept in a device row in the caller's order; a NaN time is ICPMI_ERR_INVALID_ARG.  One iteration:
+ *  1. deskew: deskew_kernel as icpmi_deskew_dev runs it, out of place, with the table of the motion {stamps begin_s, end_s; poses T_b,
+ *     T_e; ref_s = end_s; extrapolate = 1; round_s = 0}: the work buffer holds the scan as seen from the end pose.  With T_b == T_e the
+ *     table is exactly the identity (q = (0, 0, 0, 1), p = 0) and the work buffer equals the scan bit for bit.
+ *  2. match and select: the front of icpmi_residual_error_dev for the work buffer under T_e -- centring and tile sort, the pose in the
+ *     centred frame formed in double as [R | t + R mu - mu] (mu = icpmi_get_map_mean), the matcher's launch and the chain's outlier
+ *     filters as a registration's first iteration runs them.
+ *  3. pair sums (csrc/sweep.hip: sweep_pairs_kernel).  Per pair with weight w != 0, in float32 exactly as the point-to-plane pair sums
+ *     form them: p = the reading's point under the centred pose, q = its match, n = the match's normal,
+ *       F = [p.y n.z - p.z n.y, p.z n.x - p.x n.z, p.x n.y - p.y n.x, n.x, n.y, n.z],   r = (p.x - q.x) n.x + (p.y - q.y) n.y + (p.z - q.z) n.z
+ *     and a = alpha[original index of the reading's point].  In double: wf_i = (double)w * F_i, m_ij = wf_i * F_j (i <= j), gr_i = wf_i * r,
+ *       M0_ij += m_ij,  M1_ij += a m_ij,  M2_ij += (a a) m_ij,   g0_i += gr_i,  g1_i += a gr_i,   sum w,  pairs += 1,  sum w r^2 += ((double)w * r) * r
+ *     sums[80]: [0..20] M0, upper triangle row-major ((0,0) .. (0,5), (1,1) .. (5,5)); [21..41] M1; [42..62] M2; [63..68] g0; [69..74]
+ *     g1; [75] sum w; [76] pairs; [77] sum w r^2; [78], [79] zero.  (icpmi_minimize_step's sums hold b = -g0 at [21..26].)
+ *     No atomics: 256 workgroups walk the n * knn slots with a grid stride, each reduces its threads' sums in a fixed butterfly and
+ *     writes one row of partials; one workgroup of 640 threads then adds the rows: value v is the sum over c = 0 .. 7, in that order,
+ *     of the sums over i = 0 .. 31, in that order, of row c + 8 i.  Two calls give the same bits.
+ *  4. the 80 doubles, the state's error word and the quantile filter's limit come back in one copy.
+ *  5. the step, on the host in double (icpmi_sweep_solve): x = (xi_b, xi_e), each (omega, t), for the model in which point i moves by
+ *     omega(a) x p + t(a) with (omega(a), t(a)) = (1 - a) xi_b + a xi_e:
+ *       A = [[M0 - 2 M1 + M2, M1 - M2], [M1 - M2, M2]],   rhs = -[g0 - g1 ; g1]
+ *     Motion prior (lambda_rot, lambda_trans >= 0): L = (sum w) diag(lambda_rot x 3, lambda_trans x 3), D = [-I I]; A += D^T L D, rhs -=
+ *     D^T L d, where d is the sum of xi_e - xi_b over the call's earlier iterations: a first-order pull of the relative motion towards
+ *     the one the caller's two priors have.  The system is factored in the variables (xi_b, delta = xi_e - xi_b), a congruence with unit
+ *     determinant under which it reads [[M0, M1], [M1, M2 + L]] (xi_b ; delta) = [-g0 ; -g1 - L d] -- the prior sits in one block, so large
+ *     weights cancel nothing -- by Cholesky; a pivot <= 1e-12 x the largest diagonal entry is ICPMI_ERR_NAN ("the motion within the sweep
+ *     is not observable: a prior weight is needed"); pairs == 0 is ICPMI_ERR_NO_POINT_TO_MINIMIZE.  xi_e = xi_b + delta.
+ *     Each step becomes a rigid transform as the loop's steps do -- the rotation exp([omega]x), the translation t as it is -- moves from
+ *     the centred frame to the map frame, S = [R_s | t + mu - R_s mu], and T_b <- S(xi_b) T_b, T_e <- S(xi_e) T_e (quaternions renormalised).
+ *  6. stop: after max_iterations (ICPMI_STOP_COUNTER), or as soon as both steps have |omega| < min_step_rot and |t| < min_step_trans
+ *     (ICPMI_STOP_DIFFERENTIAL; the steps of that iteration are applied).
+ * out4 (may be NULL): the scan deskewed to the end pose, in the sensor frame, under the final motion -- one more launch of step 1;
+ * icpmi_deskew with stamps {begin_s, end_s}, poses result->pose7, ref_s = end_s, extrapolate = 1 gives the same bits.
+ * ICPMI_ERR_INVALID_ARG with a message: a NULL pointer, force_4dof, force_2d, is_2d, covariance or a non-zero degeneracy_threshold in
+ * the handle's config, another minimiser, no map, a prior that is not rigid (the check of icpmi_residual_error), begin_s >= end_s, a
+ * non-finite option, a negative prior weight, a NaN point time.  ICPMI_ERR_MISSING_NORMALS: a map without normals.  Outlier filters whose
+ * answer is iteration state are refused as icpmi_residual_error refuses them.  n == 0: ICPMI_OK with the priors.  A later registration
+ * on the handle returns the bits it would have returned without the sweep call; the covariance and the localizability report of the
+ * registration before it are dropped. */
+typedef struct icpmi_sweep_options {
+    double begin_s, end_s;   /* the sweep's span, seconds relative to the scan's stamp; begin_s < end_s */
+    double time_unit_s;      /* seconds per unit of t_rel (icpmi_sweep_motion::time_unit_s); finite, > 0 */
+    int32_t max_iterations;  /* >= 1; icpmi_sweep_options_default: 12 */
+    float min_step_rot;      /* rad; < 0: the chain's min_diff_rot */
+    float min_step_trans;    /* m; < 0: the chain's min_diff_trans */
+    int32_t pad;
+    double lambda_rot;       /* prior weights, >= 0; icpmi_sweep_options_default: 0 */
+    double lambda_trans;
+    int32_t reserved[8];     /* zero */
+} icpmi_sweep_options;
+typedef struct icpmi_sweep_result {
+    float T_begin[16], T_end[16]; /* column-major 4 x 4, map frame */
+    double pose7[14];             /* the same two poses in double: tx ty tz qx qy qz qw of begin, then of end */
+    int32_t iterations;           /* iterations run (icpmi_sweep_sums: 0) */
+    int32_t stop_reason;          /* ICPMI_STOP_COUNTER or ICPMI_STOP_DIFFERENTIAL */
+    int64_t pairs;                /* the rest: of the last iteration's pair sums */
+    double weight_sum;
+    double sum_sq;                /* sum w r^2 */
+    float weighted_point_used_ratio;
+    float trimmed_limit;          /* -1 without a quantile filter */
+    int32_t reserved[8];
+} icpmi_sweep_result;
+void icpmi_sweep_options_default(icpmi_sweep_options* opts); /* span 0 .. 0.1 s, time_unit_s 1e-9, 12 iterations, the chain's thresholds, no prior */
+icpmi_status icpmi_register_sweep(icpmi_handle h, const float* scan4, int64_t n, const float* t_rel, const float prior_begin16[16],
+                                  const float prior_end16[16], const icpmi_sweep_options* opts, icpmi_sweep_result* result, float* out4);
+/* the same with scan4 / t_rel / out4 as device pointers, on the handle's stream; d_out4 must not be d_scan4 */
+icpmi_status icpmi_register_sweep_dev(icpmi_handle h, const float* d_scan4, int64_t n, const float* d_t_rel, const float prior_begin16[16],
+                                      const float prior_end16[16], const icpmi_sweep_options* opts, icpmi_sweep_result* result, float* d_out4);
+/* the stage call (the analogue of icpmi_minimize_step): steps 1 to 4 once under the given poses; stats (may be NULL): the poses as
+ * given and the figures of that pass.  n >= 1. */
+icpmi_status icpmi_sweep_sums(icpmi_handle h, const float* scan4, int64_t n, const float* t_rel, const float T_begin16[16],
+                              const float T_end16[16], const icpmi_sweep_options* opts, double sums80[80], icpmi_sweep_result* stats);
+/* step 5's system alone: no handle, no device call (messages: icpmi_last_error(NULL)).  d6: NULL = zero.  x12 = (xi_b, xi_e). */
+icpmi_status icpmi_sweep_solve(const double sums80[80], double lambda_rot, double lambda_trans, const double d6[6], double x12[12]);
+
 /* `Map::unloadCells` binning (Map.cpp:206-209,232-235): ijk3[3 i + r] = floor(p_r / cell_size). */
 icpmi_status icpmi_bin_cells(icpmi_handle h, const float* pts4, int64_t n, float cell_size, int32_t* ijk3);
 

@@ -157,6 +157,21 @@ class SweepMotion(C.Structure):
 
 DESKEW_MAX_POSES = 1024
 
+
+class SweepOptions(C.Structure):
+    """icpmi_sweep_options: the span of the sweep, the unit of the point times, the iteration's limits and the motion prior's weights."""
+    _fields_ = [("begin_s", C.c_double), ("end_s", C.c_double), ("time_unit_s", C.c_double), ("max_iterations", C.c_int32),
+                ("min_step_rot", C.c_float), ("min_step_trans", C.c_float), ("pad", C.c_int32), ("lambda_rot", C.c_double),
+                ("lambda_trans", C.c_double), ("reserved", C.c_int32 * 8)]
+
+
+class SweepResult(C.Structure):
+    """icpmi_sweep_result: the two poses (column-major 4 x 4 and tx ty tz qx qy qz qw in double) and the last iteration's figures."""
+    _fields_ = [("T_begin", C.c_float * 16), ("T_end", C.c_float * 16), ("pose7", C.c_double * 14), ("iterations", C.c_int32),
+                ("stop_reason", C.c_int32), ("pairs", C.c_int64), ("weight_sum", C.c_double), ("sum_sq", C.c_double),
+                ("weighted_point_used_ratio", C.c_float), ("trimmed_limit", C.c_float), ("reserved", C.c_int32 * 8)]
+
+
 MOP_POINT_DISTANCE, MOP_DYNAMIC_POINTS, MOP_VOXEL, MOP_SURFACE_NORMALS, MOP_CUT_SCALAR, MOP_OCTREE, MOP_MAX_DENSITY = range(7)
 
 
@@ -210,6 +225,11 @@ SYMBOLS = [
     ("icpmi_deskew_table", C.c_int, [C.POINTER(SweepMotion), _P, _P, _P, _P]),
     ("icpmi_deskew", C.c_int, [_P, _P, C.c_int64, _P, C.POINTER(SweepMotion), _P, _P, _P]),
     ("icpmi_deskew_dev", C.c_int, [_P, _P, C.c_int64, _P, C.POINTER(SweepMotion), _P, _P, _P]),
+    ("icpmi_sweep_options_default", None, [C.POINTER(SweepOptions)]),
+    ("icpmi_register_sweep", C.c_int, [_P, _P, C.c_int64, _P, _P, _P, C.POINTER(SweepOptions), C.POINTER(SweepResult), _P]),
+    ("icpmi_register_sweep_dev", C.c_int, [_P, _P, C.c_int64, _P, _P, _P, C.POINTER(SweepOptions), C.POINTER(SweepResult), _P]),
+    ("icpmi_sweep_sums", C.c_int, [_P, _P, C.c_int64, _P, _P, _P, C.POINTER(SweepOptions), C.POINTER(C.c_double), C.POINTER(SweepResult)]),
+    ("icpmi_sweep_solve", C.c_int, [C.POINTER(C.c_double), C.c_double, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     ("icpmi_map_update_chain", C.c_int, [_P, _P, C.c_int64, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, _P, C.c_int64, _P, _P]),
     ("icpmi_map_update_chain_staged", C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, _P, C.c_int64, _P, _P]),
     ("icpmi_set_map_scalar", C.c_int, [_P, _P, C.c_int64]),

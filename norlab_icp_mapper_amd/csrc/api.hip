@@ -1715,6 +1715,101 @@ icpmi_status icpmi_deskew_dev(icpmi_handle h, const float* d_in4, int64_t n, con
     return ops_deskew(h, d_in4, n, d_t_rel, m, d_out4, d_in_normals3, d_out_normals3, true);
 }
 
+// ---- sweep registration (include/icpmi.h: icpmi_register_sweep; csrc/sweep.hip) ----
+void icpmi_sweep_options_default(icpmi_sweep_options* opts)
+{
+    if (!opts) return;
+    memset(opts, 0, sizeof *opts);
+    opts->begin_s = 0.0; opts->end_s = 0.1; opts->time_unit_s = 1e-9;
+    opts->max_iterations = 12;
+    opts->min_step_rot = -1.f; opts->min_step_trans = -1.f;
+}
+
+icpmi_status icpmi_sweep_solve(const double sums80[80], double lambda_rot, double lambda_trans, const double d6[6], double x12[12])
+{
+    return sweep_solve_host(sums80, lambda_rot, lambda_trans, d6, x12, g_create_error); // (no handle: icpmi_last_error(NULL) has the message)
+}
+
+// icpmi_register_sweep* (sums80 == nullptr) and icpmi_sweep_sums: the refusals of the path, the chain's set-up, the call.  Device pointers.
+static icpmi_status sweep_impl(icpmi_handle h, const char* who, const float* d_scan4, int64_t n, const float* d_t_rel, const float* T_begin,
+                               const float* T_end, const icpmi_sweep_options* opts, icpmi_sweep_result* result, float* d_out4, double* sums80)
+{
+    const int64_t have_scalar_n = h->read_scalar_n, have_r2_n = h->read_r2_n;
+    h->read_scalar_n = 0; h->read_noise_n = 0; h->read_r2_n = 0;
+    if (result) { memset(result, 0, sizeof *result); result->trimmed_limit = -1.f; }
+    if (sums80) memset(sums80, 0, 80 * sizeof(double));
+    if (n < 0 || (n > 0 && (!d_scan4 || !d_t_rel)) || !T_begin || !T_end || (!sums80 && !result) || (sums80 && n < 1) ||
+        (d_out4 && d_out4 == d_scan4)) {
+        h->last_error = std::string(who) + ": bad arguments"; return ICPMI_ERR_INVALID_ARG;
+    }
+    { const icpmi_status os = sweep_check_options(opts, h->last_error); if (os != ICPMI_OK) return os; }
+    const icpmi_config& cfg = h->cfg;
+    if (cfg.force_4dof || cfg.force_2d || cfg.is_2d || cfg.covariance || cfg.degeneracy_threshold != 0.f) {
+        h->last_error = std::string(who) + ": not served with force_4dof, force_2d, is_2d, covariance or a degeneracy_threshold"; return ICPMI_ERR_INVALID_ARG;
+    }
+    if (cfg.minimizer != ICPMI_MIN_POINT_TO_PLANE) {
+        h->last_error = std::string(who) + ": served for PointToPlaneErrorMinimizer only"; return ICPMI_ERR_INVALID_ARG;
+    }
+    { const icpmi_status rs = check_rigid(h, T_begin); if (rs != ICPMI_OK) return rs; }
+    { const icpmi_status rs = check_rigid(h, T_end); if (rs != ICPMI_OK) return rs; }
+    for (int i = 0; i < 16; ++i)
+        if (!std::isfinite(T_begin[i]) || !std::isfinite(T_end[i])) { h->last_error = std::string(who) + ": a non-finite prior"; return ICPMI_ERR_INVALID_ARG; }
+    if (n == 0) { sweep_result_priors(T_begin, T_end, result); return ICPMI_OK; }
+    if (h->m <= 0) { h->last_error = std::string(who) + ": no map"; return ICPMI_ERR_INVALID_ARG; }
+    if (n > 0x7fffffff / ICPMI_MAX_K) { h->last_error = std::string(who) + ": too many points"; return ICPMI_ERR_UNSUPPORTED; }
+    int32_t kind = ICPMI_RES_POINT_TO_PLANE; // (without map normals: ICPMI_ERR_MISSING_NORMALS)
+    LoopCfg lc;
+    const float* d_r2row = nullptr;
+    bool needs_rn = false;
+    { const icpmi_status cs = residual_chain_setup(h, who, n, nullptr, have_scalar_n, have_r2_n, &kind, &lc, &d_r2row, &needs_rn); if (cs != ICPMI_OK) return cs; }
+    if (sums80) return sweep_sums_dev(h, (const float4*)d_scan4, n, d_t_rel, lc, d_r2row, T_begin, T_end, opts, sums80, result);
+    return sweep_register_dev(h, (const float4*)d_scan4, n, d_t_rel, lc, d_r2row, T_begin, T_end, opts, result, (float4*)d_out4);
+}
+
+// the host-pointer calls: scan, point times and (want_out) the deskewed scan in scratch slot 22, [n float4][n float4][n float]
+static icpmi_status sweep_stage(icpmi_ctx* h, const float* scan4, int64_t n, const float* t_rel, const float** d_scan, const float** d_t, float** d_out)
+{
+    float4* blk = scratch_get<float4>(h, 22, (size_t)2 * n + ((size_t)n + 3) / 4);
+    if (!blk) return ICPMI_ERR_HIP;
+    HIP_TRY(h, hipMemcpyAsync(blk, scan4, (size_t)n * sizeof(float4), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(blk + 2 * n, t_rel, (size_t)n * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    *d_scan = (const float*)blk; *d_out = (float*)(blk + n); *d_t = (const float*)(blk + 2 * n);
+    return ICPMI_OK;
+}
+
+icpmi_status icpmi_register_sweep_dev(icpmi_handle h, const float* d_scan4, int64_t n, const float* d_t_rel, const float prior_begin16[16],
+                                      const float prior_end16[16], const icpmi_sweep_options* opts, icpmi_sweep_result* result, float* d_out4)
+{
+    CHECK_H(h);
+    return sweep_impl(h, "register_sweep_dev", d_scan4, n, d_t_rel, prior_begin16, prior_end16, opts, result, d_out4, nullptr);
+}
+
+icpmi_status icpmi_register_sweep(icpmi_handle h, const float* scan4, int64_t n, const float* t_rel, const float prior_begin16[16],
+                                  const float prior_end16[16], const icpmi_sweep_options* opts, icpmi_sweep_result* result, float* out4)
+{
+    CHECK_H(h);
+    const float* d_scan = scan4; const float* d_t = t_rel; float* d_out = nullptr; // (n == 0, no map or bad arguments: never dereferenced)
+    if (n > 0 && scan4 && t_rel && h->m > 0) { const icpmi_status ss = sweep_stage(h, scan4, n, t_rel, &d_scan, &d_t, &d_out); if (ss != ICPMI_OK) return ss; }
+    const icpmi_status s = sweep_impl(h, "register_sweep", d_scan, n, d_t, prior_begin16, prior_end16, opts, result, out4 ? d_out : nullptr, nullptr);
+    // (staged or not, the stream is drained: the caller's arrays are free on every return)
+    if (s != ICPMI_OK) { (void)hipStreamSynchronize(h->stream); return s; }
+    if (out4 && n > 0 && d_out) HIP_TRY(h, hipMemcpyAsync(out4, d_out, (size_t)n * sizeof(float4), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return ICPMI_OK;
+}
+
+icpmi_status icpmi_sweep_sums(icpmi_handle h, const float* scan4, int64_t n, const float* t_rel, const float T_begin16[16], const float T_end16[16],
+                              const icpmi_sweep_options* opts, double sums80[80], icpmi_sweep_result* stats)
+{
+    CHECK_H(h);
+    if (!sums80) { h->last_error = "sweep_sums: sums80 is NULL"; return ICPMI_ERR_INVALID_ARG; }
+    const float* d_scan = scan4; const float* d_t = t_rel; float* d_out = nullptr;
+    if (n > 0 && scan4 && t_rel && h->m > 0) { const icpmi_status ss = sweep_stage(h, scan4, n, t_rel, &d_scan, &d_t, &d_out); if (ss != ICPMI_OK) return ss; }
+    const icpmi_status s = sweep_impl(h, "sweep_sums", d_scan, n, d_t, T_begin16, T_end16, opts, stats, nullptr, sums80);
+    (void)hipStreamSynchronize(h->stream);
+    return s;
+}
+
 icpmi_status icpmi_bin_cells(icpmi_handle h, const float* pts4, int64_t n, float cell_size, int32_t* ijk3)
 {
     CHECK_H(h);

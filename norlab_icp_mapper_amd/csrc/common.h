@@ -664,7 +664,7 @@ inline void stream_release(hipStream_t s)
     (void)hipStreamDestroy(s);
 }
 
-#define ICPMI_SCRATCH_SLOTS 20
+#define ICPMI_SCRATCH_SLOTS 24
 struct icpmi_ctx {
     icpmi_config cfg;
     int device = 0;
@@ -766,7 +766,7 @@ struct icpmi_ctx {
     DevArr<float> d_stage_s;
     // scratch of the map-side operators (hash tables, beam buckets, flags): kept between calls -- a hipMalloc / hipFree
     // pair costs more than most of the kernels that use them
-    DevArr<unsigned char, GrowScratch> scratch[ICPMI_SCRATCH_SLOTS];// slots 0..9: operators on the handle's stream; 10..19: the DynamicPoints module (may run on `side`)
+    DevArr<unsigned char, GrowScratch> scratch[ICPMI_SCRATCH_SLOTS];// slots 0..9: operators on the handle's stream; 10..19: the DynamicPoints module (may run on `side`); 20..23: sweep registration (sweep.hip)
     hipStream_t side = nullptr;                              // map-update chain: DynamicPoints next to the decimation that follows it (ops.hip)
     hipEvent_t side_fork = nullptr, side_join = nullptr;
     // the scan of the last icpmi_register_prior, in the map frame by its prior (what Mapper::processInput calls `input`)
@@ -1377,6 +1377,14 @@ icpmi_status loop_residual_poses(icpmi_ctx* c, const float4* d_scan, int64_t n, 
                                  icpmi_residual* out, icpmi_status* status);
 icpmi_status loop_outlier_weights(icpmi_ctx* c, const LoopCfg& lc, const float* d2, const int32_t* ids, int k, int64_t n,
                                   const float* read_normals3, float* weights, float* limit_out);
+// the one-pass front of loop_residual, shared with sweep.hip (each is described where loop.hip defines it): the loop's buffers, fresh
+// states, the chain as one pass, what that pass asks of the matcher, the matcher's launch + the selections, and the view of what they leave
+icpmi_status ensure_loop_buffers(icpmi_ctx* c, int64_t n, const LoopCfg& lc, int nscan = 1);
+icpmi_status enqueue_fresh_states(icpmi_ctx* c, int nstates, const float* d_T0);
+LoopCfg one_pass_cfg(const LoopCfg& lc);
+NnRequest loop_request(icpmi_ctx* c, const LoopCfg& lc, const BatchArgs& ba, const float* d_r2row);
+icpmi_status enqueue_match_select(icpmi_ctx* c, int64_t n, const LoopCfg& lc, const NnRequest& req, NnOutcome* nn, hipEvent_t matched = nullptr);
+PairView pair_view(const icpmi_ctx* c, const LoopCfg& lc, bool sorted);
 LoopCfg make_loop_cfg(const icpmi_ctx* c, int fixed_iterations);
 // How a call over many items (the readings of a batch, the starts of a multistart, the poses of a residual call) ends: per_item goes to
 // status_out when the caller took that array, and the call then returns OK; otherwise it returns the first error.  text: what last_error
@@ -1496,3 +1504,197 @@ icpmi_status ops_normal_space_sampling(icpmi_ctx* c, const float* in4, int64_t n
 icpmi_status deskew_table_host(const icpmi_sweep_motion* m, float* q4, float* p3, float* omega, float* inv_sin, std::string& err);
 icpmi_status ops_deskew(icpmi_ctx* c, const float* in4, int64_t n, const float* t_rel, const icpmi_sweep_motion* m, float* out4,
                         const float* in_normals3, float* out_normals3, bool dev);
+// ... and the kernel alone on device pointers, no wait for its error flag (the caller has checked the point times; deskew.hip has the rules)
+icpmi_status deskew_enqueue_dev(icpmi_ctx* c, const float4* d_in, int64_t n, const float* d_t_rel, const icpmi_sweep_motion* m, unsigned char* d_tab,
+                                float4* d_out);
+// sweep.hip: sweep registration (include/icpmi.h: icpmi_register_sweep has the formulation).  d_scan / d_t_rel: the raw scan and its point
+// times on the device; lc: the chain as chain_setup built it.  sweep_sums_dev: steps 1 to 4 once under the given poses (column-major 4 x 4);
+// sweep_register_dev: the iteration; d_out4 (may be null): the scan deskewed to the end pose under the final motion
+icpmi_status sweep_sums_dev(icpmi_ctx* c, const float4* d_scan, int64_t n, const float* d_t_rel, const LoopCfg& lc, const float* d_r2row,
+                            const float T_begin[16], const float T_end[16], const icpmi_sweep_options* opts, double sums[80], icpmi_sweep_result* res);
+icpmi_status sweep_register_dev(icpmi_ctx* c, const float4* d_scan, int64_t n, const float* d_t_rel, const LoopCfg& lc, const float* d_r2row,
+                                const float T_begin[16], const float T_end[16], const icpmi_sweep_options* opts, icpmi_sweep_result* res, float4* d_out4);
+icpmi_status sweep_check_options(const icpmi_sweep_options* opts, std::string& err);
+void sweep_result_priors(const float T_begin[16], const float T_end[16], icpmi_sweep_result* res);
+icpmi_status sweep_solve_host(const double sums[80], double lambda_rot, double lambda_trans, const double* d6, double x12[12], std::string& err);
+
+// ---- shared by the passes over the matcher's output: loop.hip (overlap, covariance, residual) and sweep.hip (the sweep's pair sums) ----
+// ---------------------------------------------------------------------------------------------
+// outlier weight of one match (OutlierFilters::compute; weights multiply)
+// ---------------------------------------------------------------------------------------------
+// M-estimator weight of RobustOutlierFilter for the scaled squared residual e2 (tuning k); exp / pow through double so that
+// host libm and device ocml round to the same float
+__device__ __forceinline__ float robust_weight(int fct, float e2, float kk)
+{
+    const float k2 = kk * kk;
+    float w;
+    switch (fct) {
+    case ICPMI_ROB_CAUCHY: w = 1.f / (1.f + e2 / k2); break;
+    case ICPMI_ROB_WELSCH: w = (float)exp((double)(-e2 / k2)); break;
+    case ICPMI_ROB_SC: { const float t = kk + e2; w = e2 >= kk ? 4.f * k2 * (1.f / (t * t)) : 1.f; break; }
+    case ICPMI_ROB_GM: { const float t = kk + e2; w = k2 * (1.f / (t * t)); break; }
+    case ICPMI_ROB_TUKEY: { const float t = 1.f - e2 / k2; w = e2 >= k2 ? 0.f : t * t; break; }
+    case ICPMI_ROB_HUBER: w = e2 >= k2 ? kk * (1.f / sqrtf(e2)) : 1.f; break;
+    case ICPMI_ROB_L1: w = 1.f / sqrtf(e2); break;
+    default: {
+        const float pw = (float)pow((double)(1.f + e2 / kk), (double)(-(kk + 3.f) / 2.f));
+        w = pw * (kk + 3.f) * (1.f / (kk + e2));
+        break; }
+    }
+    return w <= 0.f ? 0.f : w;
+}
+
+// EXT: chains with GenericDescriptor / Robust filters -- ref_scalar (per ORIGINAL map index `orig`) and the squared
+// point-to-plane distance of the pair (plane2) come from the caller
+template <bool EXT = false>
+__device__ __forceinline__ float match_weight(const LoopCfg& lc, const IcpState* __restrict__ st, float d2,
+                                              const float* __restrict__ T, const float4* __restrict__ read_normals, int qi,
+                                              const float4* __restrict__ ref_normals, int sidx, int fused_slot = -1,
+                                              float fused_limit = 0.f, const float* __restrict__ ref_scalar = nullptr, int orig = 0,
+                                              float plane2 = 0.f, const float4* rn_kept = nullptr)
+{
+    float w = 1.f;
+    for (int f = 0; f < lc.n_out; ++f) {
+        const int type = lc.out_type[f];
+        const float prm = lc.out_param[f];
+        if (type == ICPMI_OUT_MAXDIST) w *= (d2 <= prm * prm) ? 1.f : 0.f;
+        else if (type == ICPMI_OUT_MINDIST) w *= (d2 >= prm * prm) ? 1.f : 0.f;
+        else if (type == ICPMI_OUT_MEDIANDIST || type == ICPMI_OUT_TRIMMEDDIST || type == ICPMI_OUT_VARTRIMMEDDIST)
+            w *= (d2 <= (f == fused_slot ? fused_limit : st->limits[f])) ? 1.f : 0.f;
+        else if (type == ICPMI_OUT_SURFACENORMAL) {
+            const float4 a = rn_kept ? *rn_kept : read_normals[qi]; // (rn_kept: the plane-to-plane pair sums hold the reading's normal already)
+            float ax = a.x, ay = a.y, az = a.z;
+            if (T) { // descriptors named "normals" rotate with the cloud
+                const float rx = fmaf(T[8], az, fmaf(T[4], ay, T[0] * ax));
+                const float ry = fmaf(T[9], az, fmaf(T[5], ay, T[1] * ax));
+                const float rz = fmaf(T[10], az, fmaf(T[6], ay, T[2] * ax));
+                ax = rx; ay = ry; az = rz;
+            }
+            const float4 b = ref_normals[sidx];
+            const float dot = fmaf(az, b.z, fmaf(ay, b.y, ax * b.x));
+            w *= (dot > cosf(prm)) ? 1.f : 0.f;
+        } else if (EXT && type == ICPMI_OUT_GENERICDESCRIPTOR) {
+            const int ip = lc.out_iparam[f];
+            const float v = (ip & ICPMI_GEN_SOURCE_READING) ? lc.read_scalar[qi] : ref_scalar[orig];
+            w *= (ip & ICPMI_GEN_SOFT) ? v : ((ip & ICPMI_GEN_LARGER) ? (v > prm ? 1.f : 0.f) : (v < prm ? 1.f : 0.f));
+        } else if (EXT && type == ICPMI_OUT_ROBUST) {
+            const int ip = lc.out_iparam[f];
+            const int se = (ip >> 4) & 15, fct = ip & 15;
+            const float sc = se != ICPMI_SCALE_NONE ? st->robust_scale : 1.f;
+            const float res = ((ip >> 8) & 15) == ICPMI_DIST_POINT2PLANE ? plane2 : d2;
+            // berg: `tuning` is the scale the estimate converges to; the M-estimator runs on Bergstrom's constants
+            const float kk = se != ICPMI_SCALE_BERG ? prm : (fct == ICPMI_ROB_CAUCHY ? 4.3040f : fct == ICPMI_ROB_TUKEY ? 7.0589f : fct == ICPMI_ROB_HUBER ? 2.0138f : prm);
+            const float e2 = res / (sc * sc);
+            const float apx = lc.out_param3[f];
+            float rw = robust_weight(fct, e2, kk);
+            if (apx > 0.f && apx != INFINITY && e2 >= apx * apx) rw = 0.f;
+            w *= rw;
+        }
+    }
+    return w;
+}
+
+// ---------------------------------------------------------------------------------------------
+// The passes over the matcher's output OUTSIDE the iteration (overlap, covariance, residual) share one walk and one way to sum.
+// ---------------------------------------------------------------------------------------------
+// one live slot (d2 finite) as walk_pairs hands it to a pass: p = the reading's point under T, q = its match, (dx, dy, dz) = p - q in
+// float as the pair-sum kernel forms it, nm / dot = the match's normal and (p - q) . nm (zero without map normals), w = the chain's weight
+struct PairSlot { int64_t e; int qi, oi, s; float d2; float3 p; float4 q, nm; float dx, dy, dz, dot, w; };
+
+// slice blockIdx.y of the per-query arrays (a pose batch: common.h, BatchArgs); the reading's descriptors are not sliced
+__device__ __forceinline__ void pair_view_slice(PairView& v, const BatchArgs& ba, int k)
+{
+    const size_t qo = (size_t)blockIdx.y * (size_t)ba.qstride;
+    v.reading += qo; v.sidx += qo * k; v.d2 += qo * k;
+    if (v.qindex) v.qindex += qo;
+    if (v.match_pt) v.match_pt += qo;
+}
+
+// Grid-stride walk of the n * lc.k slots by 256-thread workgroups; body(slot) runs for every slot with a match.  The weight goes to the
+// body as it is: each pass has its own acceptance test.  fused_slot / fused_limit: match_weight's (a limit the caller resolved itself).
+template <class Body>
+__device__ __forceinline__ void walk_pairs(const PairView& v, int n, const LoopCfg& lc, const IcpState* __restrict__ st,
+                                           const float* __restrict__ T, Body body, int fused_slot = -1, float fused_limit = 0.f)
+{
+    const int64_t total = (int64_t)n * lc.k;
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
+        PairSlot a;
+        a.d2 = v.d2[e];
+        if (a.d2 == INFINITY) continue;
+        a.e = e;
+        a.qi = (int)(e / lc.k);
+        a.oi = v.qindex ? v.qindex[a.qi] : a.qi;
+        a.s = v.sidx[e];
+        // the three gathers of a pair are requested together, in front of the first use of any of them (with k > 1 the matched point and
+        // its normal both hang on s: a normal fetched behind p - q is one more round trip per pair, 2 us of a knn-6 pass)
+        const float4 r = v.reading[a.qi];
+        a.q = v.match_pt ? v.match_pt[e] : v.map[a.s];
+        a.nm = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (v.ref_normals) a.nm = v.ref_normals[a.s];
+        a.p = xf_point(T, r.x, r.y, r.z, r.w);
+        a.dx = a.p.x - a.q.x; a.dy = a.p.y - a.q.y; a.dz = a.p.z - a.q.z;
+        a.dot = v.ref_normals ? a.dx * a.nm.x + a.dy * a.nm.y + a.dz * a.nm.z : 0.f;
+        // EXT: the filters that read the pair itself, as the pair-sum kernel evaluates them
+        if (lc.ext) a.w = match_weight<true>(lc, st, a.d2, T, v.read_normals, a.oi, v.ref_normals, a.s, fused_slot, fused_limit, v.ref_scalar,
+                                             __float_as_int(a.q.w), a.dot * a.dot);
+        else a.w = match_weight(lc, st, a.d2, T, v.read_normals, a.oi, v.ref_normals, a.s, fused_slot, fused_limit);
+        body(a);
+    }
+}
+
+// Ordered double sums: a fixed pattern at every level, so a pass gives the same bits on every call (include/icpmi.h rests on it).
+// Level 1, all 256 threads: acc[NV] per thread -> xor butterfly 32 .. 1 inside the wave -> the four waves in order -> row[NV], this
+// workgroup's row of partials.  Slots whose bit is set in MAXMASK combine with fmax instead of +.
+template <int NV, unsigned MAXMASK = 0u>
+__device__ __forceinline__ void block_partial_row(const double (&acc)[NV], double* __restrict__ row)
+{
+    __shared__ double sh[4][NV];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        double v = acc[i];
+#pragma unroll
+        for (int m = 32; m > 0; m >>= 1) {
+            const double o = __shfl_xor(v, m, 64);
+            v = (MAXMASK >> i & 1u) ? fmax(v, o) : v + o;
+        }
+        if (lane == 0) sh[wv][i] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < NV) {
+        const int i = threadIdx.x;
+        row[i] = (MAXMASK >> i & 1u) ? fmax(fmax(fmax(sh[0][i], sh[1][i]), sh[2][i]), sh[3][i]) : ((sh[0][i] + sh[1][i]) + sh[2][i]) + sh[3][i];
+    }
+}
+
+// Level 2, one workgroup of at least NV * CH threads: the first nb <= NB rows -> tot[NV] (LDS, valid in every thread on return).  Thread
+// v * CH + ch adds rows ch, ch + CH, ... of value v in that order -- every load issued before the first add (a loop of dependent loads and
+// adds was 35 us at 128 rows) -- and thread v then adds the CH chunk sums in order.
+template <int NV, int CH, int NB, unsigned MAXMASK = 0u>
+__device__ __forceinline__ void block_ordered_total(const double* __restrict__ partial, int nb, double* tot)
+{
+    __shared__ double part[NV][CH];
+    if (threadIdx.x < NV * CH) {
+        constexpr int PER = (NB + CH - 1) / CH;
+        const int v = threadIdx.x / CH, ch = threadIdx.x % CH;
+        double x[PER];
+#pragma unroll
+        for (int i = 0; i < PER; ++i) {
+            const int b = ch + CH * i;
+            x[i] = b < nb ? partial[(size_t)b * NV + v] : 0.0;
+        }
+        double acc = 0.0;
+#pragma unroll
+        for (int i = 0; i < PER; ++i) acc = (MAXMASK >> v & 1u) ? fmax(acc, x[i]) : acc + x[i];
+        part[v][ch] = acc;
+    }
+    __syncthreads();
+    if (threadIdx.x < NV) {
+        const int v = threadIdx.x;
+        double acc = 0.0;
+#pragma unroll
+        for (int ch = 0; ch < CH; ++ch) acc = (MAXMASK >> v & 1u) ? fmax(acc, part[v][ch]) : acc + part[v][ch];
+        tot[v] = acc;
+    }
+    __syncthreads();
+}

@@ -174,7 +174,54 @@ bool deskew_prepare(const icpmi_sweep_motion* m, DeskewTable& t, std::string& er
     return true;
 }
 
+// the table as one block (layout: DeskewView), the cleared flag word in front: one upload
+struct DeskewBlob { std::vector<unsigned char> bytes; size_t off_stamp, off_q, off_p, off_seg; };
+DeskewBlob deskew_blob(const DeskewTable& t, int K)
+{
+    DeskewBlob b;
+    b.off_stamp = 16; b.off_q = (b.off_stamp + sizeof(double) * (size_t)K + 15) & ~(size_t)15; b.off_p = b.off_q + sizeof(float4) * (size_t)K;
+    b.off_seg = b.off_p + sizeof(float4) * (size_t)K;
+    b.bytes.assign(b.off_seg + sizeof(float2) * (size_t)(K - 1), 0);
+    memcpy(b.bytes.data() + b.off_stamp, t.stamp.data(), sizeof(double) * (size_t)K);
+    float* bq = (float*)(b.bytes.data() + b.off_q); float* bp = (float*)(b.bytes.data() + b.off_p); float* bs = (float*)(b.bytes.data() + b.off_seg);
+    for (int k = 0; k < K; ++k) {
+        for (int r = 0; r < 4; ++r) bq[4 * k + r] = t.q4[4 * (size_t)k + r];
+        for (int r = 0; r < 3; ++r) bp[4 * k + r] = t.p3[3 * (size_t)k + r];
+        if (k < K - 1) { bs[2 * k] = t.omega[(size_t)k]; bs[2 * k + 1] = t.inv_sin[(size_t)k]; }
+    }
+    return b;
+}
+// ... and the kernel's view of its device copy
+DeskewView deskew_view(unsigned char* d_tab, const DeskewBlob& b, const icpmi_sweep_motion* m)
+{
+    DeskewView v;
+    v.flag = (unsigned*)d_tab; v.stamp = (const double*)(d_tab + b.off_stamp); v.q = (const float4*)(d_tab + b.off_q);
+    v.p = (const float4*)(d_tab + b.off_p); v.seg = (const float2*)(d_tab + b.off_seg);
+    v.K = m->n_poses; v.extrapolate = m->extrapolate ? 1 : 0; v.unit = m->time_unit_s; v.round_s = m->round_s;
+    return v;
+}
+
 } // namespace
+
+// deskew_kernel on device pointers WITHOUT the wait for its error flag: for a caller that has checked the point times itself and set
+// extrapolate, so that no point can raise the flag (sweep.hip: every iteration of a sweep registration deskews the raw scan again).
+// d_tab: the caller's block for the table, at least ICPMI_UP_SLOT bytes, not reused before the kernel has run.  The table travels
+// through one slot of the pinned upload ring, so it must fit one (a two-pose table is 104 bytes).  d_out != d_in.
+icpmi_status deskew_enqueue_dev(icpmi_ctx* c, const float4* d_in, int64_t n, const float* d_t_rel, const icpmi_sweep_motion* m, unsigned char* d_tab,
+                                float4* d_out)
+{
+    DeskewTable t;
+    if (!deskew_prepare(m, t, c->last_error)) return ICPMI_ERR_INVALID_ARG;
+    if (n == 0) return ICPMI_OK;
+    const DeskewBlob b = deskew_blob(t, m->n_poses);
+    if (b.bytes.size() > ICPMI_UP_SLOT) { c->last_error = "deskew: the table does not fit one upload slot"; return ICPMI_ERR_UNSUPPORTED; }
+    { const icpmi_status us = upload_small(c, d_tab, b.bytes.data(), b.bytes.size()); if (us != ICPMI_OK) return us; }
+    if (!c->h_pin) HIP_TRY(c, hipStreamSynchronize(c->stream)); // (no pinned ring: the copy read `b` itself)
+    hipLaunchKernelGGL(deskew_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, d_in, n, d_t_rel, deskew_view(d_tab, b, m), d_out,
+                       (const float*)nullptr, (float*)nullptr);
+    HIP_TRY(c, hipGetLastError());
+    return ICPMI_OK;
+}
 
 // icpmi_deskew_table: no handle, no device call
 icpmi_status deskew_table_host(const icpmi_sweep_motion* m, float* q4, float* p3, float* omega, float* inv_sin, std::string& err)
@@ -207,17 +254,9 @@ icpmi_status ops_deskew(icpmi_ctx* c, const float* in4, int64_t n, const float* 
     }
     if (n == 0) return ICPMI_OK;
     if (n > 0x7fffffffll) { c->last_error = "deskew: more than 2^31 - 1 points"; return ICPMI_ERR_UNSUPPORTED; }
-    // the table as one block (layout: DeskewView), the cleared flag word in front: one upload
-    const size_t off_stamp = 16, off_q = (off_stamp + sizeof(double) * (size_t)K + 15) & ~(size_t)15, off_p = off_q + sizeof(float4) * (size_t)K,
-                 off_seg = off_p + sizeof(float4) * (size_t)K, bytes = off_seg + sizeof(float2) * (size_t)(K - 1);
-    std::vector<unsigned char> blob(bytes, 0);
-    memcpy(blob.data() + off_stamp, t.stamp.data(), sizeof(double) * (size_t)K);
-    float* bq = (float*)(blob.data() + off_q); float* bp = (float*)(blob.data() + off_p); float* bs = (float*)(blob.data() + off_seg);
-    for (int k = 0; k < K; ++k) {
-        for (int r = 0; r < 4; ++r) bq[4 * k + r] = t.q4[4 * (size_t)k + r];
-        for (int r = 0; r < 3; ++r) bp[4 * k + r] = t.p3[3 * (size_t)k + r];
-        if (k < K - 1) { bs[2 * k] = t.omega[(size_t)k]; bs[2 * k + 1] = t.inv_sin[(size_t)k]; }
-    }
+    const DeskewBlob b = deskew_blob(t, K);
+    const std::vector<unsigned char>& blob = b.bytes;
+    const size_t bytes = blob.size();
     // every block first: nothing below gives up between an upload from `blob` and the wait at the flag's read-back
     unsigned char* d_tab = scratch_get<unsigned char>(c, 17, bytes);
     if (!d_tab) return ICPMI_ERR_HIP;
@@ -228,10 +267,7 @@ icpmi_status ops_deskew(icpmi_ctx* c, const float* in4, int64_t n, const float* 
         if (!(d_ts = scratch_get<float>(c, 18, (size_t)n))) return ICPMI_ERR_HIP;
     }
     { const icpmi_status us = upload_small(c, d_tab, blob.data(), bytes); if (us != ICPMI_OK) return us; }
-    DeskewView v;
-    v.flag = (unsigned*)d_tab; v.stamp = (const double*)(d_tab + off_stamp); v.q = (const float4*)(d_tab + off_q);
-    v.p = (const float4*)(d_tab + off_p); v.seg = (const float2*)(d_tab + off_seg);
-    v.K = K; v.extrapolate = m->extrapolate ? 1 : 0; v.unit = m->time_unit_s; v.round_s = m->round_s;
+    const DeskewView v = deskew_view(d_tab, b, m);
     const float4* d_in = (const float4*)in4; float4* d_out = (float4*)out4;
     const float* d_t = t_rel; const float* d_nin = in_normals3; float* d_nout = out_normals3;
     if (!dev) { // staged on the handle, deskewed in place there

@@ -14,186 +14,6 @@
 
 namespace {
 
-// ---------------------------------------------------------------------------------------------
-// outlier weight of one match (OutlierFilters::compute; weights multiply)
-// ---------------------------------------------------------------------------------------------
-// M-estimator weight of RobustOutlierFilter for the scaled squared residual e2 (tuning k); exp / pow through double so that
-// host libm and device ocml round to the same float
-__device__ __forceinline__ float robust_weight(int fct, float e2, float kk)
-{
-    const float k2 = kk * kk;
-    float w;
-    switch (fct) {
-    case ICPMI_ROB_CAUCHY: w = 1.f / (1.f + e2 / k2); break;
-    case ICPMI_ROB_WELSCH: w = (float)exp((double)(-e2 / k2)); break;
-    case ICPMI_ROB_SC: { const float t = kk + e2; w = e2 >= kk ? 4.f * k2 * (1.f / (t * t)) : 1.f; break; }
-    case ICPMI_ROB_GM: { const float t = kk + e2; w = k2 * (1.f / (t * t)); break; }
-    case ICPMI_ROB_TUKEY: { const float t = 1.f - e2 / k2; w = e2 >= k2 ? 0.f : t * t; break; }
-    case ICPMI_ROB_HUBER: w = e2 >= k2 ? kk * (1.f / sqrtf(e2)) : 1.f; break;
-    case ICPMI_ROB_L1: w = 1.f / sqrtf(e2); break;
-    default: {
-        const float pw = (float)pow((double)(1.f + e2 / kk), (double)(-(kk + 3.f) / 2.f));
-        w = pw * (kk + 3.f) * (1.f / (kk + e2));
-        break; }
-    }
-    return w <= 0.f ? 0.f : w;
-}
-
-// EXT: chains with GenericDescriptor / Robust filters -- ref_scalar (per ORIGINAL map index `orig`) and the squared
-// point-to-plane distance of the pair (plane2) come from the caller
-template <bool EXT = false>
-__device__ __forceinline__ float match_weight(const LoopCfg& lc, const IcpState* __restrict__ st, float d2,
-                                              const float* __restrict__ T, const float4* __restrict__ read_normals, int qi,
-                                              const float4* __restrict__ ref_normals, int sidx, int fused_slot = -1,
-                                              float fused_limit = 0.f, const float* __restrict__ ref_scalar = nullptr, int orig = 0,
-                                              float plane2 = 0.f, const float4* rn_kept = nullptr)
-{
-    float w = 1.f;
-    for (int f = 0; f < lc.n_out; ++f) {
-        const int type = lc.out_type[f];
-        const float prm = lc.out_param[f];
-        if (type == ICPMI_OUT_MAXDIST) w *= (d2 <= prm * prm) ? 1.f : 0.f;
-        else if (type == ICPMI_OUT_MINDIST) w *= (d2 >= prm * prm) ? 1.f : 0.f;
-        else if (type == ICPMI_OUT_MEDIANDIST || type == ICPMI_OUT_TRIMMEDDIST || type == ICPMI_OUT_VARTRIMMEDDIST)
-            w *= (d2 <= (f == fused_slot ? fused_limit : st->limits[f])) ? 1.f : 0.f;
-        else if (type == ICPMI_OUT_SURFACENORMAL) {
-            const float4 a = rn_kept ? *rn_kept : read_normals[qi]; // (rn_kept: the plane-to-plane pair sums hold the reading's normal already)
-            float ax = a.x, ay = a.y, az = a.z;
-            if (T) { // descriptors named "normals" rotate with the cloud
-                const float rx = fmaf(T[8], az, fmaf(T[4], ay, T[0] * ax));
-                const float ry = fmaf(T[9], az, fmaf(T[5], ay, T[1] * ax));
-                const float rz = fmaf(T[10], az, fmaf(T[6], ay, T[2] * ax));
-                ax = rx; ay = ry; az = rz;
-            }
-            const float4 b = ref_normals[sidx];
-            const float dot = fmaf(az, b.z, fmaf(ay, b.y, ax * b.x));
-            w *= (dot > cosf(prm)) ? 1.f : 0.f;
-        } else if (EXT && type == ICPMI_OUT_GENERICDESCRIPTOR) {
-            const int ip = lc.out_iparam[f];
-            const float v = (ip & ICPMI_GEN_SOURCE_READING) ? lc.read_scalar[qi] : ref_scalar[orig];
-            w *= (ip & ICPMI_GEN_SOFT) ? v : ((ip & ICPMI_GEN_LARGER) ? (v > prm ? 1.f : 0.f) : (v < prm ? 1.f : 0.f));
-        } else if (EXT && type == ICPMI_OUT_ROBUST) {
-            const int ip = lc.out_iparam[f];
-            const int se = (ip >> 4) & 15, fct = ip & 15;
-            const float sc = se != ICPMI_SCALE_NONE ? st->robust_scale : 1.f;
-            const float res = ((ip >> 8) & 15) == ICPMI_DIST_POINT2PLANE ? plane2 : d2;
-            // berg: `tuning` is the scale the estimate converges to; the M-estimator runs on Bergstrom's constants
-            const float kk = se != ICPMI_SCALE_BERG ? prm : (fct == ICPMI_ROB_CAUCHY ? 4.3040f : fct == ICPMI_ROB_TUKEY ? 7.0589f : fct == ICPMI_ROB_HUBER ? 2.0138f : prm);
-            const float e2 = res / (sc * sc);
-            const float apx = lc.out_param3[f];
-            float rw = robust_weight(fct, e2, kk);
-            if (apx > 0.f && apx != INFINITY && e2 >= apx * apx) rw = 0.f;
-            w *= rw;
-        }
-    }
-    return w;
-}
-
-// ---------------------------------------------------------------------------------------------
-// The passes over the matcher's output OUTSIDE the iteration (overlap, covariance, residual) share one walk and one way to sum.
-// ---------------------------------------------------------------------------------------------
-// one live slot (d2 finite) as walk_pairs hands it to a pass: p = the reading's point under T, q = its match, (dx, dy, dz) = p - q in
-// float as the pair-sum kernel forms it, nm / dot = the match's normal and (p - q) . nm (zero without map normals), w = the chain's weight
-struct PairSlot { int64_t e; int qi, oi, s; float d2; float3 p; float4 q, nm; float dx, dy, dz, dot, w; };
-
-// slice blockIdx.y of the per-query arrays (a pose batch: common.h, BatchArgs); the reading's descriptors are not sliced
-__device__ __forceinline__ void pair_view_slice(PairView& v, const BatchArgs& ba, int k)
-{
-    const size_t qo = (size_t)blockIdx.y * (size_t)ba.qstride;
-    v.reading += qo; v.sidx += qo * k; v.d2 += qo * k;
-    if (v.qindex) v.qindex += qo;
-    if (v.match_pt) v.match_pt += qo;
-}
-
-// Grid-stride walk of the n * lc.k slots by 256-thread workgroups; body(slot) runs for every slot with a match.  The weight goes to the
-// body as it is: each pass has its own acceptance test.  fused_slot / fused_limit: match_weight's (a limit the caller resolved itself).
-template <class Body>
-__device__ __forceinline__ void walk_pairs(const PairView& v, int n, const LoopCfg& lc, const IcpState* __restrict__ st,
-                                           const float* __restrict__ T, Body body, int fused_slot = -1, float fused_limit = 0.f)
-{
-    const int64_t total = (int64_t)n * lc.k;
-    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
-        PairSlot a;
-        a.d2 = v.d2[e];
-        if (a.d2 == INFINITY) continue;
-        a.e = e;
-        a.qi = (int)(e / lc.k);
-        a.oi = v.qindex ? v.qindex[a.qi] : a.qi;
-        a.s = v.sidx[e];
-        // the three gathers of a pair are requested together, in front of the first use of any of them (with k > 1 the matched point and
-        // its normal both hang on s: a normal fetched behind p - q is one more round trip per pair, 2 us of a knn-6 pass)
-        const float4 r = v.reading[a.qi];
-        a.q = v.match_pt ? v.match_pt[e] : v.map[a.s];
-        a.nm = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (v.ref_normals) a.nm = v.ref_normals[a.s];
-        a.p = xf_point(T, r.x, r.y, r.z, r.w);
-        a.dx = a.p.x - a.q.x; a.dy = a.p.y - a.q.y; a.dz = a.p.z - a.q.z;
-        a.dot = v.ref_normals ? a.dx * a.nm.x + a.dy * a.nm.y + a.dz * a.nm.z : 0.f;
-        // EXT: the filters that read the pair itself, as the pair-sum kernel evaluates them
-        if (lc.ext) a.w = match_weight<true>(lc, st, a.d2, T, v.read_normals, a.oi, v.ref_normals, a.s, fused_slot, fused_limit, v.ref_scalar,
-                                             __float_as_int(a.q.w), a.dot * a.dot);
-        else a.w = match_weight(lc, st, a.d2, T, v.read_normals, a.oi, v.ref_normals, a.s, fused_slot, fused_limit);
-        body(a);
-    }
-}
-
-// Ordered double sums: a fixed pattern at every level, so a pass gives the same bits on every call (include/icpmi.h rests on it).
-// Level 1, all 256 threads: acc[NV] per thread -> xor butterfly 32 .. 1 inside the wave -> the four waves in order -> row[NV], this
-// workgroup's row of partials.  Slots whose bit is set in MAXMASK combine with fmax instead of +.
-template <int NV, unsigned MAXMASK = 0u>
-__device__ __forceinline__ void block_partial_row(const double (&acc)[NV], double* __restrict__ row)
-{
-    __shared__ double sh[4][NV];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        double v = acc[i];
-#pragma unroll
-        for (int m = 32; m > 0; m >>= 1) {
-            const double o = __shfl_xor(v, m, 64);
-            v = (MAXMASK >> i & 1u) ? fmax(v, o) : v + o;
-        }
-        if (lane == 0) sh[wv][i] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < NV) {
-        const int i = threadIdx.x;
-        row[i] = (MAXMASK >> i & 1u) ? fmax(fmax(fmax(sh[0][i], sh[1][i]), sh[2][i]), sh[3][i]) : ((sh[0][i] + sh[1][i]) + sh[2][i]) + sh[3][i];
-    }
-}
-
-// Level 2, one workgroup of at least NV * CH threads: the first nb <= NB rows -> tot[NV] (LDS, valid in every thread on return).  Thread
-// v * CH + ch adds rows ch, ch + CH, ... of value v in that order -- every load issued before the first add (a loop of dependent loads and
-// adds was 35 us at 128 rows) -- and thread v then adds the CH chunk sums in order.
-template <int NV, int CH, int NB, unsigned MAXMASK = 0u>
-__device__ __forceinline__ void block_ordered_total(const double* __restrict__ partial, int nb, double* tot)
-{
-    __shared__ double part[NV][CH];
-    if (threadIdx.x < NV * CH) {
-        constexpr int PER = (NB + CH - 1) / CH;
-        const int v = threadIdx.x / CH, ch = threadIdx.x % CH;
-        double x[PER];
-#pragma unroll
-        for (int i = 0; i < PER; ++i) {
-            const int b = ch + CH * i;
-            x[i] = b < nb ? partial[(size_t)b * NV + v] : 0.0;
-        }
-        double acc = 0.0;
-#pragma unroll
-        for (int i = 0; i < PER; ++i) acc = (MAXMASK >> v & 1u) ? fmax(acc, x[i]) : acc + x[i];
-        part[v][ch] = acc;
-    }
-    __syncthreads();
-    if (threadIdx.x < NV) {
-        const int v = threadIdx.x;
-        double acc = 0.0;
-#pragma unroll
-        for (int ch = 0; ch < CH; ++ch) acc = (MAXMASK >> v & 1u) ? fmax(acc, part[v][ch]) : acc + part[v][ch];
-        tot[v] = acc;
-    }
-    __syncthreads();
-}
-
 // fixed-order sum (halving tree 128 .. 1) of the workgroup's 256 values; the result in every thread
 template <class V>
 __device__ __forceinline__ V block_tree_sum(V v, V* sh /* 256 */)
@@ -707,7 +527,7 @@ LoopCfg make_loop_cfg(const icpmi_ctx* c, int fixed_iterations)
 // conditional forms here are the same pointers wherever a kernel dereferences them -- the covariance runs for point-to-plane only, which
 // api.hip (register_impl) refuses without map normals, and the overlap pass runs with !lc.ext and reads the reading's normals in its
 // point-to-plane branch only, for which register_impl sets has_read_normals (a SurfaceNormal filter sets it through chain_setup).
-static PairView pair_view(const icpmi_ctx* c, const LoopCfg& lc, bool sorted)
+PairView pair_view(const icpmi_ctx* c, const LoopCfg& lc, bool sorted)
 {
     PairView v;
     v.reading = sorted ? c->d_qsorted : c->d_reading;
@@ -1088,7 +908,7 @@ static int acc_blocks(int64_t count, int bt = 256)
 
 // everything the loop's launches for chain lc write to: n = points per slice, nscan slices (a single registration: one slice of n points).
 // The VarTrimmedDist scratch is reserved here too, so that enqueue_selection cannot fail (such a chain never takes a batch).
-static icpmi_status ensure_loop_buffers(icpmi_ctx* c, int64_t n, const LoopCfg& lc, int nscan = 1)
+icpmi_status ensure_loop_buffers(icpmi_ctx* c, int64_t n, const LoopCfg& lc, int nscan)
 {
     const size_t cnt = (size_t)n * lc.k * nscan + 1;
     if (c->d_sidx.ensure(c, cnt) != ICPMI_OK) return ICPMI_ERR_HIP;
@@ -1164,7 +984,7 @@ static void enqueue_accumulate_solve(icpmi_ctx* c, int64_t n, const LoopCfg& lc,
 
 // what every launch of a registration's loop asks of the matcher (ba: its readings; NnRequest::iter is set iteration by iteration).  Built
 // once the loop's buffers have their final size.
-static NnRequest loop_request(icpmi_ctx* c, const LoopCfg& lc, const BatchArgs& ba, const float* d_r2row)
+NnRequest loop_request(icpmi_ctx* c, const LoopCfg& lc, const BatchArgs& ba, const float* d_r2row)
 {
     NnRequest req;
     req.hist0 = fused_filter_slot(lc) >= 0 ? c->d_selhist.get() : nullptr;
@@ -1176,7 +996,7 @@ static NnRequest loop_request(icpmi_ctx* c, const LoopCfg& lc, const BatchArgs& 
 }
 
 // the chain as the entry points that run ONE pass of it see it: one iteration, no checkers
-static LoopCfg one_pass_cfg(const LoopCfg& lc)
+LoopCfg one_pass_cfg(const LoopCfg& lc)
 {
     LoopCfg l1 = lc;
     l1.max_iter = 1; l1.use_diff = 0; l1.use_bound = 0;
@@ -1185,7 +1005,7 @@ static LoopCfg one_pass_cfg(const LoopCfg& lc)
 
 // nstates fresh loop states outside a registration (no sequence number, no progress word) and their cleared selection histograms;
 // d_T0: one pose of 16 floats per state, null = identity
-static icpmi_status enqueue_fresh_states(icpmi_ctx* c, int nstates, const float* d_T0)
+icpmi_status enqueue_fresh_states(icpmi_ctx* c, int nstates, const float* d_T0)
 {
     hipLaunchKernelGGL(init_state_kernel, dim3(nstates), dim3(64), 0, c->stream, c->d_state, d_T0, 0u, (unsigned*)nullptr, (const unsigned*)nullptr, 16);
     HIP_TRY(c, hipMemsetAsync(c->d_selhist, 0, (size_t)ICPMI_SELHIST_WORDS * nstates * sizeof(unsigned), c->stream));
@@ -1194,7 +1014,7 @@ static icpmi_status enqueue_fresh_states(icpmi_ctx* c, int nstates, const float*
 
 // the front of an iteration: the matcher's launch under the states' T_iter, then the chain's selections; *nn = what the launch answered.
 // matched: recorded between the two (a profiled registration times its matcher)
-static icpmi_status enqueue_match_select(icpmi_ctx* c, int64_t n, const LoopCfg& lc, const NnRequest& req, NnOutcome* nn, hipEvent_t matched = nullptr)
+icpmi_status enqueue_match_select(icpmi_ctx* c, int64_t n, const LoopCfg& lc, const NnRequest& req, NnOutcome* nn, hipEvent_t matched)
 {
     const icpmi_status s = nn_launch_k(c, req, c->d_reading, n, c->d_state->T_iter, lc, 1, c->d_sidx, c->d_d2, c->d_state, nn);
     if (s != ICPMI_OK) return s;

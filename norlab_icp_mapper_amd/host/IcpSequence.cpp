@@ -401,6 +401,20 @@ Mat4 GpuICPSequence::registerWithPrior(const DataPoints& scan, const Mat4& prior
     return T;
 }
 
+SweepRegistration GpuICPSequence::registerSweep(const DataPoints& scan, const std::vector<float>& tRel, const Mat4& priorBegin, const Mat4& priorEnd,
+                                                const icpmi_sweep_options& opts)
+{
+    if (tRel.size() != scan.getNbPoints()) throw InvalidParameter("registerSweep: one point time per point is needed");
+    if (hasReadingFilters()) throw InvalidParameter("registerSweep: readingDataPointsFilters would drop points behind their times; filter the input instead");
+    SweepRegistration r;
+    haveCovariance = false; haveLocalizability = false; // (the matcher's buffers are reused)
+    check(h, icpmi_register_sweep(h, scan.features.data(), (int64_t)scan.getNbPoints(), tRel.data(), priorBegin.data(), priorEnd.data(), &opts, &r.stats,
+                                  nullptr));
+    std::memcpy(r.begin.data(), r.stats.T_begin, sizeof(float) * 16);
+    std::memcpy(r.end.data(), r.stats.T_end, sizeof(float) * 16);
+    return r;
+}
+
 void GpuICPSequence::mapUpdateStaged(const Mat4& correction, float minDist, int normalsKnn, std::vector<uint8_t>& keep, int64_t& appended,
                                      int64_t& mapSize)
 {

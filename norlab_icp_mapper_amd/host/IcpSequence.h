@@ -67,6 +67,13 @@ std::vector<int> rankCandidates(const PoseScores& scores, size_t n, float minPai
 // innermost, each ascending: (2 stepsX + 1)(2 stepsY + 1)(2 stepsYaw + 1) poses.  Needs no GPU.
 std::vector<Mat4> candidateGrid(const Mat4& centre, float halfX, float halfY, float halfYaw, int stepsX = 1, int stepsY = 1, int stepsYaw = 1);
 
+// What GpuICPSequence::registerSweep returns: the sensor's pose in the map at sweep begin and at sweep end, and the call's figures
+// (include/icpmi.h: icpmi_sweep_result; stats.pose7 holds the two poses in double, as icpmi_sweep_motion takes them)
+struct SweepRegistration {
+    Mat4 begin = Mat4::identity(), end = Mat4::identity();
+    icpmi_sweep_result stats{};
+};
+
 class GpuICPSequence {
 public:
     struct ErrorMinimizerView {
@@ -114,6 +121,12 @@ public:
     // ConvergenceError when no candidate survives.
     Relocalization relocalize(const DataPoints& readingInSensorFrame, const std::vector<Mat4>& candidates, const RelocalizeOptions& options = RelocalizeOptions());
 
+    // Sweep registration (include/icpmi.h: icpmi_register_sweep; not libpointmatcher's): the skewed scan in the sensor frame with its point
+    // times tRel (one per point, in units of opts.time_unit_s from the scan's stamp) registered as a motion -- the two poses estimated by
+    // the chain's matcher and outlier filters.  Point-to-plane chains without reading filters; throws what operator() throws.  Leaves
+    // stats() and the staged scan alone; the covariance and the localizability report of the registration before it are dropped.
+    SweepRegistration registerSweep(const DataPoints& scanInSensorFrame, const std::vector<float>& tRel, const Mat4& priorBegin, const Mat4& priorEnd,
+                                    const icpmi_sweep_options& opts);
     icpmi_handle handle() const { return h; }          // for the operators that share the GPU context
     // Map::updateLocalPointCloud for the PointDistance chain on the resident map (icpmi_map_update_point_distance)
     void mapUpdatePointDistance(const DataPoints& inputInMapFrame, float minDist, int normalsKnn, std::vector<uint8_t>& keep, int64_t& appended,

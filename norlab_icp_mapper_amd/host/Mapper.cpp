@@ -169,26 +169,32 @@ void Mapper::setDefaultMapperModule()
     map.addMapperModule(registrar.create("PointDistanceMapperModule", yaml::Load("{minDistNewPoint: 0.15}"), icp.handle()));
 }
 
+// the points' times as offsets from the stamp: the float descriptor, or else the int64 row of absolute nanoseconds; returns seconds per unit
+static double sweepPointTimes(const DataPoints& cloud, int64_t stampNs, const std::string& timeField, double timeUnit, const char* who, std::vector<float>& tRel)
+{
+    const size_t n = cloud.getNbPoints();
+    if (cloud.descriptorExists(timeField)) {
+        const Descriptor& d = cloud.getDescriptorByName(timeField);
+        if (d.span != 1) throw InvalidField(std::string(who) + ": descriptor " + timeField + " must have one row");
+        tRel = d.data;
+        return timeUnit;
+    }
+    if (cloud.timeExists(timeField)) {
+        const TimeField& t = cloud.getTimeByName(timeField);
+        if (t.span != 1) throw InvalidField(std::string(who) + ": time " + timeField + " must have one row");
+        tRel.resize(n);
+        for (size_t i = 0; i < n; ++i) tRel[i] = (float)(t.data[i] - stampNs);
+        return 1e-9;
+    }
+    throw InvalidField(std::string(who) + ": the cloud has neither a descriptor nor a time row called " + timeField);
+}
+
 void deskewSweep(icpmi_handle ctx, DataPoints& cloud, const SweepMotion& motion, TimePoint stamp, const DeskewOptions& opts)
 {
     const size_t n = cloud.getNbPoints();
     const int64_t stampNs = (int64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(stamp.time_since_epoch()).count();
-    // the points' times as offsets from the stamp: the float descriptor, or else the int64 row of absolute nanoseconds
     std::vector<float> tRel;
-    double unit = opts.timeUnit;
-    if (cloud.descriptorExists(opts.timeField)) {
-        const Descriptor& d = cloud.getDescriptorByName(opts.timeField);
-        if (d.span != 1) throw InvalidField("deskew: descriptor " + opts.timeField + " must have one row");
-        tRel = d.data;
-    } else if (cloud.timeExists(opts.timeField)) {
-        const TimeField& t = cloud.getTimeByName(opts.timeField);
-        if (t.span != 1) throw InvalidField("deskew: time " + opts.timeField + " must have one row");
-        tRel.resize(n);
-        for (size_t i = 0; i < n; ++i) tRel[i] = (float)(t.data[i] - stampNs);
-        unit = 1e-9;
-    } else {
-        throw InvalidField("deskew: the cloud has neither a descriptor nor a time row called " + opts.timeField);
-    }
+    const double unit = sweepPointTimes(cloud, stampNs, opts.timeField, opts.timeUnit, "deskew", tRel);
     if (motion.stampNs.size() != motion.pose.size()) throw InvalidParameter("deskew: the motion has " + std::to_string(motion.stampNs.size()) +
                                                                             " stamps for " + std::to_string(motion.pose.size()) + " poses");
     // the sign-continued table is built from this once per call: one call per scan (a second one for observationDirections)
@@ -201,7 +207,7 @@ void deskewSweep(icpmi_handle ctx, DataPoints& cloud, const SweepMotion& motion,
     m.n_poses = (int32_t)std::min<size_t>(stampS.size(), (size_t)ICPMI_DESKEW_MAX_POSES + 1);
     m.extrapolate = opts.extrapolate ? 1 : 0;
     m.stamp_s = stampS.data(); m.pose7 = pose7.data();
-    m.ref_s = 0.0; m.time_unit_s = unit; m.round_s = 1e-9 * (double)opts.roundToNs;
+    m.ref_s = opts.refS; m.time_unit_s = unit; m.round_s = 1e-9 * (double)opts.roundToNs;
     std::vector<float> out(4 * n);
     const bool hasNormals = cloud.descriptorExists("normals"), hasObs = cloud.descriptorExists("observationDirections");
     for (const char* name : {"normals", "observationDirections"})
@@ -305,6 +311,60 @@ void Mapper::processInput(const DataPoints& filteredInputInSensorFrame, const Ma
     if (mapUpdateFuture.valid() && mapUpdateFuture.wait_for(std::chrono::milliseconds(1)) == std::future_status::ready) mapUpdateFuture.get();
     { std::lock_guard<std::mutex> g(poseLock); pose = correctedPose; }
     { std::lock_guard<std::mutex> g(trajectoryLock); trajectory.addPose(correctedPose, timeStamp); }
+}
+
+SweepRegistration Mapper::processSweep(const DataPoints& filteredInputInSensorFrame, const Mat4& estimatedPoseBegin, const Mat4& estimatedPoseEnd,
+                                       const TimePoint& timeStamp, const SweepOptions& opts)
+{
+    const int64_t stampNs = (int64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(timeStamp.time_since_epoch()).count();
+    std::vector<float> tRel;
+    icpmi_sweep_options o;
+    icpmi_sweep_options_default(&o);
+    o.time_unit_s = sweepPointTimes(filteredInputInSensorFrame, stampNs, opts.timeField, opts.timeUnit, "processSweep", tRel);
+    o.begin_s = opts.beginS; o.end_s = opts.endS;
+    o.max_iterations = opts.maxIterations; o.min_step_rot = opts.minStepRot; o.min_step_trans = opts.minStepTrans;
+    o.lambda_rot = opts.lambdaRot; o.lambda_trans = opts.lambdaTrans;
+    const bool bootstrap = map.isLocalPointCloudEmpty(); // nothing to register against: the priors are the motion
+    SweepRegistration reg;
+    lastScanGrewMap = false;
+    lastUpdMs = 0.0;
+    lastScoreValid = false;
+    lastLocalizabilityValid = false;
+    const auto tReg = std::chrono::steady_clock::now();
+    {
+        std::lock_guard<std::mutex> g(icpMapLock);
+        if (!bootstrap) lastSeenMapVersion = map.icpMapVersion();
+        // (an empty reading, or no map on the handle yet: the call answers with the priors and their double form)
+        DataPoints none(0);
+        reg = icp.registerSweep(bootstrap ? none : filteredInputInSensorFrame, bootstrap ? std::vector<float>() : tRel, estimatedPoseBegin, estimatedPoseEnd, o);
+    }
+    lastRegMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tReg).count();
+    // the cloud as seen from the end pose under that motion
+    DataPoints deskewed = filteredInputInSensorFrame;
+    SweepMotion motion;
+    motion.stampNs = {stampNs + (int64_t)std::llround(opts.beginS * 1e9), stampNs + (int64_t)std::llround(opts.endS * 1e9)};
+    for (int k = 0; k < 2; ++k) {
+        std::array<double, 7> p;
+        std::copy(reg.stats.pose7 + 7 * k, reg.stats.pose7 + 7 * k + 7, p.begin());
+        motion.pose.push_back(p);
+    }
+    DeskewOptions dopts;
+    dopts.timeField = opts.timeField; dopts.timeUnit = opts.timeUnit; dopts.extrapolate = true;
+    dopts.refS = 1e-9 * (double)(motion.stampNs[1] - stampNs);
+    deskewSweep(icp.handle(), deskewed, motion, timeStamp, dopts);
+    // ... and from here on processInput's host path for that cloud at the end pose, the registration already done
+    const Mat4 correctedPose = reg.end;
+    lastCorrectionMat = Mat4::identity();
+    const DataPoints scanInMap = transformation.compute(deskewed, correctedPose);
+    map.updatePose(correctedPose);
+    const auto tUpd = std::chrono::steady_clock::now();
+    const float overlap = bootstrap ? 0.f : reg.stats.weighted_point_used_ratio;
+    if (bootstrap || mapUpdateIsDue(timeStamp, correctedPose, overlap)) { growMap(scanInMap, correctedPose, timeStamp); lastScanGrewMap = true; }
+    if (lastScanGrewMap) lastUpdMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tUpd).count();
+    if (mapUpdateFuture.valid() && mapUpdateFuture.wait_for(std::chrono::milliseconds(1)) == std::future_status::ready) mapUpdateFuture.get();
+    { std::lock_guard<std::mutex> g(poseLock); pose = correctedPose; }
+    { std::lock_guard<std::mutex> g(trajectoryLock); trajectory.addPose(correctedPose, timeStamp); }
+    return reg;
 }
 
 // the degeneracy report of the registration that just ran (registered = one did), for getLocalizability() and the map-update veto

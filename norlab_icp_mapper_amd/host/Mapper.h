@@ -57,6 +57,17 @@ struct DeskewOptions {
     double timeUnit = 1e-9;       // seconds per unit of the float descriptor (the bundled scans' `t`: nanoseconds)
     int64_t roundToNs = 0;        // > 0: point times are rounded to multiples of it first (the wrapper's deskewing_round_to_nanosecs)
     bool extrapolate = false;     // false: a point time outside the motion's stamps is an error (tf2's ExtrapolationException)
+    double refS = 0.0;            // the time the output is expressed at, seconds from the scan's stamp (0: the stamp itself)
+};
+// Sweep registration (include/icpmi.h: icpmi_register_sweep; not libpointmatcher's): the span of the sweep in seconds from the scan's stamp,
+// where the point times are (as DeskewOptions), the iteration's limits (< 0: the chain's minDiff*) and the motion prior's weights
+struct SweepOptions {
+    double beginS = 0.0, endS = 0.1;
+    std::string timeField = "t";
+    double timeUnit = 1e-9;
+    int maxIterations = 12;
+    float minStepRot = -1.f, minStepTrans = -1.f;
+    double lambdaRot = 0.0, lambdaTrans = 0.0;
 };
 // every point of the cloud moved to where the sensor saw it from at `stamp`: features by T(stamp)^-1 T(point time), `normals` and
 // `observationDirections` by its rotation; every other descriptor and the `times` rows stay.  InvalidField when the cloud has neither
@@ -75,6 +86,13 @@ public:
     }
     void applyInputFilters(DataPoints& inputInSensorFrame);                                   // Mapper.cpp:187-191
     void processInput(const DataPoints& inputInSensorFrame, const Mat4& estimatedPose, const TimePoint& timeStamp); // :194-238
+    // processInput for a scan that is still skewed and whose motion within the sweep nobody knows: the two priors (the sensor's pose in the map
+    // at opts.beginS and at opts.endS from the stamp) are refined by GpuICPSequence::registerSweep against the current map, the cloud is
+    // deskewed to the end pose under the estimated motion (deskewSweep: `normals` and `observationDirections` follow), and the call goes on as
+    // processInput does for that cloud at the end pose: paging, update policy, map update, trajectory.  On an empty map the priors are the
+    // motion.  Point times as Mapper::deskew takes them.  Returns the motion it used.
+    SweepRegistration processSweep(const DataPoints& filteredInputInSensorFrame, const Mat4& estimatedPoseBegin, const Mat4& estimatedPoseEnd,
+                                   const TimePoint& timeStamp, const SweepOptions& opts = SweepOptions());
     // Relocalisation against the current map: the input filters are applied to a copy of the scan, GpuICPSequence::relocalize picks and
     // refines the best of `candidates`, and its pose becomes the mapper's (getPose(): what the next processInput starts from; the
     // trajectory gets it under `timeStamp`).  The map is NOT updated, and neither is anything the last processInput left

@@ -437,4 +437,49 @@ int nim_test_mapper_replay_scored(const char* config, int n_scans, const char* c
     }
 }
 
+// Mapper::processSweep scan by scan on an offline mapper built from `config`: scan i is scans4[i] (ns[i] points, sensor frame, skewed) with
+// its point times t_rel[i] as the float descriptor `t` (nanoseconds from the stamp), the priors priors_begin16 / priors_end16 (column-major,
+// 16 floats per scan), the sweep spanning [begin_s, end_s].  Back per scan: the two poses processSweep returned, the icpmi_sweep_result, the
+// mapper's pose (getPose()) and the size of its map after the call.  Returns 0; 2 ConvergenceError, 3 InvalidField, 4 InvalidParameter, 1
+// any other exception, the text in err.
+int nim_test_mapper_sweep(const char* config, int n_scans, const float* const* scans4, const int64_t* ns, const float* const* t_rel,
+                          const float* priors_begin16, const float* priors_end16, const int64_t* stamps_ns, double begin_s, double end_s,
+                          int max_iterations, float* begin_out16, float* end_out16, icpmi_sweep_result* res_out, float* pose_out16,
+                          int64_t* map_sizes, char* err, int err_cap)
+{
+    const auto fail = [&](const std::exception& e, int rc) {
+        if (err && err_cap > 0) { std::strncpy(err, e.what(), (size_t)err_cap - 1); err[err_cap - 1] = 0; }
+        return rc;
+    };
+    try {
+        nim::Mapper mapper(config, true, false, true, false);
+        nim::SweepOptions opts;
+        opts.beginS = begin_s; opts.endS = end_s; opts.maxIterations = max_iterations;
+        for (int i = 0; i < n_scans; ++i) {
+            const size_t n = (size_t)ns[i];
+            nim::DataPoints cloud(n);
+            std::memcpy(cloud.features.data(), scans4[i], sizeof(float) * 4 * n);
+            cloud.addDescriptor("t", 1, std::vector<float>(t_rel[i], t_rel[i] + n));
+            nim::Mat4 pb, pe;
+            std::memcpy(pb.data(), priors_begin16 + 16 * i, sizeof(float) * 16);
+            std::memcpy(pe.data(), priors_end16 + 16 * i, sizeof(float) * 16);
+            const nim::SweepRegistration reg = mapper.processSweep(cloud, pb, pe, nim::TimePoint{std::chrono::nanoseconds(stamps_ns[i])}, opts);
+            std::memcpy(begin_out16 + 16 * i, reg.begin.data(), sizeof(float) * 16);
+            std::memcpy(end_out16 + 16 * i, reg.end.data(), sizeof(float) * 16);
+            res_out[i] = reg.stats;
+            std::memcpy(pose_out16 + 16 * i, mapper.getPose().data(), sizeof(float) * 16);
+            map_sizes[i] = (int64_t)mapper.getMap().getNbPoints();
+        }
+        return 0;
+    } catch (const nim::ConvergenceError& e) {
+        return fail(e, 2);
+    } catch (const nim::InvalidField& e) {
+        return fail(e, 3);
+    } catch (const nim::InvalidParameter& e) {
+        return fail(e, 4);
+    } catch (const std::exception& e) {
+        return fail(e, 1);
+    }
+}
+
 } // extern "C"

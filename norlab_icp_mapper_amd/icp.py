@@ -309,6 +309,48 @@ class Residual:
         return "Residual(" + ", ".join(f"{k}={getattr(self, k)!r}" for k in self.__slots__) + ")"
 
 
+class SweepResult:
+    """icpmi_sweep_result as plain Python values: T_begin / T_end (4, 4) float32, pose7 (2, 7) float64 (tx ty tz qx qy qz qw)."""
+    __slots__ = ("T_begin", "T_end", "pose7", "iterations", "stop_reason", "pairs", "weight_sum", "sum_sq", "weighted_point_used_ratio",
+                 "trimmed_limit")
+
+    def __init__(self, c):
+        self.T_begin, self.T_end = _T_from_c(c.T_begin[:]), _T_from_c(c.T_end[:])
+        self.pose7 = np.array(c.pose7[:], dtype=np.float64).reshape(2, 7)
+        self.iterations, self.stop_reason, self.pairs = int(c.iterations), int(c.stop_reason), int(c.pairs)
+        self.weight_sum, self.sum_sq = float(c.weight_sum), float(c.sum_sq)
+        self.weighted_point_used_ratio, self.trimmed_limit = np.float32(c.weighted_point_used_ratio), np.float32(c.trimmed_limit)
+
+    def bits(self):
+        """every field as raw bits (bit-for-bit comparisons)"""
+        return (self.T_begin.view(np.uint32).tolist(), self.T_end.view(np.uint32).tolist(), self.pose7.view(np.uint64).tolist(), self.iterations,
+                self.stop_reason, self.pairs, np.float64([self.weight_sum, self.sum_sq]).view(np.uint64).tolist(),
+                np.float32([self.weighted_point_used_ratio, self.trimmed_limit]).view(np.uint32).tolist())
+
+    def __repr__(self):
+        return "SweepResult(" + ", ".join(f"{k}={getattr(self, k)!r}" for k in self.__slots__) + ")"
+
+
+def sweep_solve(sums, lambda_rot=0.0, lambda_trans=0.0, d=None):
+    """icpmi_sweep_solve: host only, needs neither a handle nor a device.  sums (80,) as icpmi_sweep_sums lays them out, d (6,) the sum of
+    xi_e - xi_b over earlier iterations (None: zero).  Returns x = (xi_b, xi_e) (12,) float64; ConvergenceError when the system is
+    rank-deficient (a prior weight is needed) or holds no pair."""
+    lib = _capi.load()
+    s = np.ascontiguousarray(sums, dtype=np.float64).ravel()
+    if s.shape[0] != 80:
+        raise InvalidParameter(f"expected 80 sums, got {s.shape[0]}")
+    dd = None if d is None else np.ascontiguousarray(d, dtype=np.float64).ravel()
+    if dd is not None and dd.shape[0] != 6:
+        raise InvalidParameter(f"expected d of 6 values, got {dd.shape[0]}")
+    x = np.zeros(12, dtype=np.float64)
+    P = C.POINTER(C.c_double)
+    st = lib.icpmi_sweep_solve(s.ctypes.data_as(P), float(lambda_rot), float(lambda_trans), None if dd is None else dd.ctypes.data_as(P),
+                               x.ctypes.data_as(P))
+    if st != _capi.ICPMI_OK:
+        raise _STATUS_EXC.get(st, RuntimeError)(lib.icpmi_last_error(None).decode())
+    return x
+
+
 class PoseScores:
     """What icpmi_residual_error_poses* returns: one Residual and one status per pose (a pose whose status is not 0 keeps an empty Residual),
     and `batched`, the number of poses that went through the batched launches."""
@@ -1066,6 +1108,74 @@ class ICPSequence:
             d_normals_out_ptr = d_normals_ptr
         self._check(self._lib.icpmi_deskew_dev(self._h, d_points_ptr, int(n), d_t_rel_ptr, C.byref(m), d_points_ptr if d_out_ptr is None else d_out_ptr,
                                                d_normals_ptr, d_normals_out_ptr))
+
+    # ---- sweep registration: the motion within one scan estimated by ICP (icpmi_register_sweep*, icpmi_sweep_sums, icpmi_sweep_solve) ----
+    def _sweepOptions(self, begin, end, unit, max_iterations, min_step_rot, min_step_trans, lambda_rot, lambda_trans):
+        o = _capi.SweepOptions()
+        self._lib.icpmi_sweep_options_default(C.byref(o))
+        o.begin_s, o.end_s, o.time_unit_s = float(begin), float(end), float(unit)
+        o.max_iterations = int(max_iterations)
+        o.min_step_rot = -1.0 if min_step_rot is None else float(min_step_rot)
+        o.min_step_trans = -1.0 if min_step_trans is None else float(min_step_trans)
+        o.lambda_rot, o.lambda_trans = float(lambda_rot), float(lambda_trans)
+        return o
+
+    def _sweep_out(self, st):
+        if st == _capi.ERR_INVALID_ARG:
+            msg = self._lib.icpmi_last_error(self._h).decode()
+            if msg.startswith("TransformationError"):
+                raise TransformationError(msg)
+        self._check(st)
+
+    def register_sweep(self, scan, t_rel, prior_begin, prior_end, begin=0.0, end=0.1, unit=1e-9, max_iterations=12, min_step_rot=None,
+                       min_step_trans=None, lambda_rot=0.0, lambda_trans=0.0, with_cloud=False):
+        """icpmi_register_sweep: scan (N, 4) in the sensor frame as measured (skewed), t_rel (N,) the points' times in units of `unit`
+        seconds from the scan's stamp, the sweep spanning [begin, end] seconds; prior_begin / prior_end: 4 x 4 guesses of the sensor's
+        pose in the map at the two ends.  Returns a SweepResult (T_begin, T_end, pose7 (2, 7), iterations, stop_reason, pairs, weight_sum,
+        sum_sq, weighted_point_used_ratio, trimmed_limit), or (result, cloud) with the scan deskewed to the end pose when with_cloud."""
+        c = _f32c(scan, 4)
+        n = c.shape[0]
+        t = np.ascontiguousarray(t_rel, dtype=np.float32).ravel()
+        if t.shape[0] != n:
+            raise InvalidParameter("t_rel / cloud size mismatch")
+        o = self._sweepOptions(begin, end, unit, max_iterations, min_step_rot, min_step_trans, lambda_rot, lambda_trans)
+        res = _capi.SweepResult()
+        out = np.empty_like(c) if with_cloud else None
+        Tb, Te = _T_to_c(prior_begin), _T_to_c(prior_end)
+        self._sweep_out(self._lib.icpmi_register_sweep(self._h, c.ctypes.data, n, t.ctypes.data, Tb.ctypes.data, Te.ctypes.data, C.byref(o),
+                                                       C.byref(res), None if out is None else out.ctypes.data))
+        r = SweepResult(res)
+        return (r, out) if with_cloud else r
+
+    def register_sweep_dev(self, d_scan_ptr, n, d_t_rel_ptr, prior_begin, prior_end, begin=0.0, end=0.1, unit=1e-9, max_iterations=12,
+                           min_step_rot=None, min_step_trans=None, lambda_rot=0.0, lambda_trans=0.0, d_out_ptr=None):
+        """icpmi_register_sweep_dev: register_sweep on device pointers, on the handle's stream; d_out_ptr (not the scan) receives the cloud."""
+        o = self._sweepOptions(begin, end, unit, max_iterations, min_step_rot, min_step_trans, lambda_rot, lambda_trans)
+        res = _capi.SweepResult()
+        Tb, Te = _T_to_c(prior_begin), _T_to_c(prior_end)
+        self._sweep_out(self._lib.icpmi_register_sweep_dev(self._h, d_scan_ptr, int(n), d_t_rel_ptr, Tb.ctypes.data, Te.ctypes.data, C.byref(o),
+                                                           C.byref(res), d_out_ptr))
+        return SweepResult(res)
+
+    def sweep_sums(self, scan, t_rel, T_begin, T_end, begin=0.0, end=0.1, unit=1e-9):
+        """icpmi_sweep_sums: one pass (deskew, match, select, pair sums) under the given poses.  Returns (sums (80,) float64, SweepResult)."""
+        c = _f32c(scan, 4)
+        n = c.shape[0]
+        t = np.ascontiguousarray(t_rel, dtype=np.float32).ravel()
+        if t.shape[0] != n:
+            raise InvalidParameter("t_rel / cloud size mismatch")
+        o = self._sweepOptions(begin, end, unit, 1, None, None, 0.0, 0.0)
+        res = _capi.SweepResult()
+        sums = np.zeros(80, dtype=np.float64)
+        Tb, Te = _T_to_c(T_begin), _T_to_c(T_end)
+        self._sweep_out(self._lib.icpmi_sweep_sums(self._h, c.ctypes.data, n, t.ctypes.data, Tb.ctypes.data, Te.ctypes.data, C.byref(o),
+                                                   sums.ctypes.data_as(C.POINTER(C.c_double)), C.byref(res)))
+        return sums, SweepResult(res)
+
+    @staticmethod
+    def sweep_solve(sums, lambda_rot=0.0, lambda_trans=0.0, d=None):
+        """icpmi_sweep_solve (host only, no handle): the step x = (xi_b, xi_e) (12,) float64 of the system in sums (80,)."""
+        return sweep_solve(sums, lambda_rot, lambda_trans, d)
 
     def normalSpaceSampling(self, cloud, normals, nb_sample=5000, seed=1, epsilon=0.09817, with_buckets=False):
         """NormalSpaceDataPointsFilter{nbSample, seed, epsilon} (the formulation of icpmi_normal_space_sampling, as recalled): cloud
