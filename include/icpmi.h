@@ -345,6 +345,49 @@ typedef enum {
 icpmi_status icpmi_set_plane_pair_model(icpmi_handle h, int32_t model);
 icpmi_status icpmi_get_plane_pair_model(icpmi_handle h, int32_t* model);
 
+/* ---- IntensityPointToPlaneErrorMinimizer: a photometric term on ICPMI_MIN_POINT_TO_PLANE.  Not libpointmatcher's: the joint
+ * geometric + photometric objective of Park, Zhou, Koltun, "Colored Point Cloud Registration Revisited" (ICCV 2017), one scalar channel.
+ *
+ * Map side, once per map: for every map point i with unit normal u = n_i / |n_i| an intensity gradient g_i in its tangent plane, from its K
+ * nearest OTHER map points j (the self search of icpmi_surface_normals with k = K + 1, the point itself first; 1 <= K <= 31; unfilled slots and
+ * neighbours with a non-finite intensity are skipped):  e1 = normalise(u x axis), axis = the coordinate axis of the smallest |u| component,
+ * e2 = u x e1;  d = (x_j - x_i) - u (u . (x_j - x_i)), a = d . e1, b = d . e2, dI = I_j - I_i;  S = sum [a b]^T [a b], r = sum [a b]^T dI in float,
+ * neighbour order;  g2 = S^-1 r in closed form, g_i = g2.x e1 + g2.y e2.  g_i = 0 when the normal is zero or non-finite, I_i is non-finite, fewer
+ * than 2 neighbours are usable, or det S <= 1e-4 (tr S / 2)^2 (the neighbours lie on a line, or on the point).
+ *
+ * Per pair with weight w != 0 (p = T_iter x, q its match with normal n as the point-to-plane sums read it, (g, I_q) of the match, I_p of the
+ * reading point), lambda = 1 - weight:
+ *     r_G = (p - q) . n,  F_G = [p x n; n]                                   (the point-to-plane terms, bit for bit)
+ *     m = g - n (g . n),  p' = p - n r_G,  r_I = I_q + g . (p' - q) - I_p,  F_I = [p x m; m]
+ *     A += w (lambda F_G F_G^T + (1 - lambda) F_I F_I^T),   b -= w (lambda F_G r_G + (1 - lambda) F_I r_I)
+ * per-pair terms in float, the weight's products and the sums in double, in the point-to-plane slots of sums[32]; a pair whose I_p or I_q is
+ * non-finite adds the geometric part only; sums[27] and sums[28] are point-to-plane's.  Intensities are taken as given: scaling them by s acts
+ * like a photometric weight s^2.
+ *
+ * icpmi_set_intensity_weight: w = 1 - lambda, finite, 0 <= w < 1 (else ICPMI_ERR_INVALID_ARG and the value stays).  0, the default, is off: no
+ * result changes by a bit and no other kernel runs.  State of the handle next to the plane epsilon: icpmi_set_config leaves it, and it is
+ * part of what a cached loop graph is valid for.  With w > 0:
+ *   - icpmi_register, _dev, _fixed_dev, icpmi_register_prior*, icpmi_minimize_step and icpmi_minimize_step_normals serve the term.  They need
+ *     the map's channel and the reading's row: without either, ICPMI_ERR_INVALID_ARG with "InvalidField: ..." naming the missing setter;
+ *   - every minimizer but ICPMI_MIN_POINT_TO_PLANE, force_2d / is_2d, covariance = 1 and degeneracy_threshold != 0 are refused by those entry
+ *     points, and icpmi_register_batch_dev, icpmi_register_multistart*, icpmi_register_sweep* / icpmi_sweep_sums refuse the handle
+ *     (ICPMI_ERR_UNSUPPORTED, the message names the term);
+ *   - icpmi_residual_error* report the point-to-plane residual, unchanged. */
+icpmi_status icpmi_set_intensity_weight(icpmi_handle h, float w);
+icpmi_status icpmi_get_intensity_weight(icpmi_handle h, float* w);
+/* The resident map's intensity, one value per point in the caller's order (host pointer; m must equal the map's size: else
+ * ICPMI_ERR_INVALID_ARG; a map without normals: ICPMI_ERR_MISSING_NORMALS; knn = K above).  Computes the gradients on the device and keeps
+ * (g.x, g.y, g.z, I) per map point in the index's order.  Every call that changes the resident map (icpmi_set_map*, the map updates and chains,
+ * inserts, epochs) drops the channel. */
+icpmi_status icpmi_set_map_intensity(icpmi_handle h, const float* intensity, int64_t m, int32_t knn);
+/* The intensity of the NEXT reading, one value per point in the caller's order: a one-shot row with the contract of icpmi_set_reading_scalar
+ * (consumed by the next call that takes a reading, whatever becomes of it; n must match that reading). */
+icpmi_status icpmi_set_reading_intensity(icpmi_handle h, const float* row, int64_t n);
+/* The gradient operator by itself, on host pointers (pts4: 4 x m, normals3: 3 x m, intensity: m, grad3_out: 3 x m, knn = K): the kernel of
+ * icpmi_set_map_intensity; touches no state of the handle but its private search handle, like icpmi_surface_normals. */
+icpmi_status icpmi_intensity_gradient(icpmi_handle h, const float* pts4, int64_t m, const float* normals3, const float* intensity, int32_t knn,
+                                      float* grad3_out);
+
 /* ---- map-side operators on the path ---- */
 
 /* `SurfaceNormalDataPointsFilter{knn}` (Map.cpp:524 via examples/config.yaml:26-27). */

@@ -206,6 +206,11 @@ SYMBOLS = [
     ("icpmi_get_plane_epsilon", C.c_int, [_P, _F]),
     ("icpmi_set_plane_pair_model", C.c_int, [_P, C.c_int32]),
     ("icpmi_get_plane_pair_model", C.c_int, [_P, C.POINTER(C.c_int32)]),
+    ("icpmi_set_intensity_weight", C.c_int, [_P, C.c_float]),
+    ("icpmi_get_intensity_weight", C.c_int, [_P, _F]),
+    ("icpmi_set_map_intensity", C.c_int, [_P, _P, C.c_int64, C.c_int32]),
+    ("icpmi_set_reading_intensity", C.c_int, [_P, _P, C.c_int64]),
+    ("icpmi_intensity_gradient", C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int32, _P]),
     ("icpmi_surface_normals", C.c_int, [_P, _P, C.c_int64, C.c_int32, _P]),
     ("icpmi_surface_normals_ex", C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, _P]),
     ("icpmi_surface_normals_ex2", C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, _P, _P, _P]),

@@ -642,13 +642,50 @@ static icpmi_status reject_plane_to_plane(icpmi_ctx* h, const char* who)
     return ICPMI_ERR_UNSUPPORTED;
 }
 
+// The photometric term (icpmi_set_intensity_weight > 0) is served on plain point-to-plane chains by the entry points that run
+// the loop's pair sums on ONE reading.  Everything else says so:
+// ... the entry points that cannot carry it
+static icpmi_status reject_intensity(icpmi_ctx* h, const char* who)
+{
+    if (!(h->intensity_w > 0.f)) return ICPMI_OK;
+    h->last_error = std::string(who) + ": the intensity term (icpmi_set_intensity_weight > 0) is served by icpmi_register*, icpmi_register_prior* and "
+                    "icpmi_minimize_step* only; set the weight to 0 for this entry point";
+    return ICPMI_ERR_UNSUPPORTED;
+}
+// ... the chains it is not defined for, then what it needs: the map's channel and the row of THIS reading (have_int_n: what the call consumed).
+// On success lc carries both (common.h: intensity_weight).
+static icpmi_status intensity_setup(icpmi_ctx* h, const char* who, int64_t n, int64_t have_int_n, LoopCfg* lc)
+{
+    if (!(h->intensity_w > 0.f)) return ICPMI_OK;
+    const icpmi_config& cfg = h->cfg;
+    const char* why = nullptr;
+    if (cfg.minimizer != ICPMI_MIN_POINT_TO_PLANE) why = "is defined on ICPMI_MIN_POINT_TO_PLANE only";
+    else if (cfg.force_2d || cfg.is_2d) why = "is not served with force_2d / is_2d";
+    else if (cfg.covariance) why = "is not served with covariance = 1 (Censi's form is derived for the point-to-plane residual alone)";
+    else if (cfg.degeneracy_threshold != 0.f) why = "is not served with a degeneracy_threshold (the localizability report is defined on the geometric term)";
+    if (why) {
+        h->last_error = std::string(who) + ": the intensity term (icpmi_set_intensity_weight > 0) " + why;
+        return ICPMI_ERR_UNSUPPORTED;
+    }
+    if (!map_intensity_ready(h)) {
+        h->last_error = "InvalidField: the intensity term needs the map's intensity channel (icpmi_set_map_intensity, after every change of the map)";
+        return ICPMI_ERR_INVALID_ARG;
+    }
+    if (have_int_n != n) {
+        h->last_error = "InvalidField: the intensity term needs the reading's intensity (icpmi_set_reading_intensity, one value per point)";
+        return ICPMI_ERR_INVALID_ARG;
+    }
+    lc->read_scalar = h->d_read_scalar; // (the intensity row sits n floats behind the GenericDescriptor row)
+    return ICPMI_OK;
+}
+
 static icpmi_status register_impl(icpmi_handle h, const float* d_scan4, int64_t n, const float* d_n3, int fixed_iters,
                                   float T_out[16], icpmi_stats* stats)
 {
     // the one-shot reading rows (icpmi_set_reading_scalar / _sensor_noise) belong to THIS call whatever becomes of it: consumed here, before
     // any early return, so that a registration that bails out cannot leave a stale row armed for the next one
-    const int64_t have_scalar_n = h->read_scalar_n, have_noise_n = h->read_noise_n, have_r2_n = h->read_r2_n;
-    h->read_scalar_n = 0; h->read_noise_n = 0; h->read_r2_n = 0;
+    const int64_t have_scalar_n = h->read_scalar_n, have_noise_n = h->read_noise_n, have_r2_n = h->read_r2_n, have_int_n = h->read_int_n;
+    h->read_scalar_n = 0; h->read_noise_n = 0; h->read_r2_n = 0; h->read_int_n = 0;
     h->cov_ready = false; // (loop_run sets it again once the covariance of THIS registration is enqueued)
     h->degen_ready = false; // (... and the localizability report)
     if (!T_out) { h->last_error = "register: T_out is null"; return ICPMI_ERR_INVALID_ARG; }
@@ -671,6 +708,7 @@ static icpmi_status register_impl(icpmi_handle h, const float* d_scan4, int64_t 
     const float* d_r2row = nullptr;
     bool needs_rn = false;
     { const icpmi_status cs = chain_setup(h, n, d_n3, have_scalar_n, have_r2_n, fixed_iters, &lc, &d_r2row, &needs_rn); if (cs != ICPMI_OK) return cs; }
+    { const icpmi_status is = intensity_setup(h, "register", n, have_int_n, &lc); if (is != ICPMI_OK) return is; }
     // sensor-noise overlap (icpmi_set_reading_sensor_noise): the noise row is one shot -- this registration consumes it
     // (PointToPointErrorMinimizer::getOverlap() needs `simpleSensorNoise` alone; only the point-to-plane variant also reads the reading's
     // `normals` -- ADVICE r3)
@@ -703,10 +741,24 @@ icpmi_status icpmi_set_reading_scalar(icpmi_handle h, const float* scalar, int64
     CHECK_H(h);
     h->read_scalar_n = 0;
     if (!scalar || n <= 0) return ICPMI_OK;
-    if (h->d_read_scalar.ensure(h, (size_t)n + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
+    if (h->d_read_scalar.ensure_keep(h, 2 * (size_t)n + 1, h->read_int_n == n ? 2 * (size_t)n : 0) != ICPMI_OK) return ICPMI_ERR_HIP; // (row 2: icpmi_set_reading_intensity)
     HIP_TRY(h, hipMemcpyAsync(h->d_read_scalar, scalar, (size_t)n * sizeof(float), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream)); // the caller's buffer is free on return
     h->read_scalar_n = n;
+    return ICPMI_OK;
+}
+
+// (the two one-shot rows share d_read_scalar: [0, n) the GenericDescriptor row, [n, 2 n) the intensity row -- a row armed with the same n
+//  survives the other setter's growth of the buffer)
+icpmi_status icpmi_set_reading_intensity(icpmi_handle h, const float* row, int64_t n)
+{
+    CHECK_H(h);
+    h->read_int_n = 0;
+    if (!row || n <= 0) return ICPMI_OK;
+    if (h->d_read_scalar.ensure_keep(h, 2 * (size_t)n + 1, h->read_scalar_n == n ? (size_t)n : 0) != ICPMI_OK) return ICPMI_ERR_HIP;
+    HIP_TRY(h, hipMemcpyAsync(h->d_read_scalar + n, row, (size_t)n * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream)); // the caller's buffer is free on return
+    h->read_int_n = n;
     return ICPMI_OK;
 }
 
@@ -772,6 +824,7 @@ icpmi_status icpmi_register_batch_dev(icpmi_handle h, int32_t batch, const float
     for (int b = 0; b < batch; ++b)
         if (n[b] < 0 || (n[b] > 0 && !d_scans4[b])) { h->last_error = "register_batch: bad arguments"; return ICPMI_ERR_INVALID_ARG; }
     { const icpmi_status ps = reject_plane_to_plane(h, "register_batch"); if (ps != ICPMI_OK) return ps; }
+    { const icpmi_status is = reject_intensity(h, "register_batch"); if (is != ICPMI_OK) return is; }
     // The one-launch-per-iteration path serves the chains whose kernels take a batch: k = 1 on the grid pyramid without a
     // brute-force pass, at most one quantile filter, no filter that reads descriptors of the reading.  Everything else --
     // and empty readings, a handle without a map -- runs the readings one after the other: same results, no sharing.
@@ -858,7 +911,7 @@ static icpmi_status residual_impl(icpmi_handle h, const char* who, const float* 
 {
     // the one-shot reading rows belong to THIS call whatever becomes of it, as in register_impl
     const int64_t have_scalar_n = h->read_scalar_n, have_r2_n = h->read_r2_n;
-    h->read_scalar_n = 0; h->read_noise_n = 0; h->read_r2_n = 0;
+    h->read_scalar_n = 0; h->read_noise_n = 0; h->read_r2_n = 0; h->read_int_n = 0;
     if (!out) { h->last_error = std::string(who) + ": out is null"; return ICPMI_ERR_INVALID_ARG; }
     memset(out, 0, sizeof *out);
     out->trimmed_limit = -1.f;
@@ -888,7 +941,7 @@ static icpmi_status residual_poses_impl(icpmi_handle h, const char* who, const f
                                         int32_t n_poses, int32_t kind, icpmi_residual* out, icpmi_status* status, int32_t* batched)
 {
     const int64_t have_scalar_n = h->read_scalar_n, have_r2_n = h->read_r2_n;
-    h->read_scalar_n = 0; h->read_noise_n = 0; h->read_r2_n = 0;
+    h->read_scalar_n = 0; h->read_noise_n = 0; h->read_r2_n = 0; h->read_int_n = 0;
     if (batched) *batched = 0;
     const bool range_ok = n_poses >= 1 && n_poses <= 4096;
     // zeroed on every whole-call error.  (A count above the limit included: the caller vouches for n_poses entries either way -- a call
@@ -1013,6 +1066,7 @@ icpmi_status icpmi_register_multistart_dev(icpmi_handle h, const float* d_scan4,
         h->last_error = "register_multistart: bad arguments (1 <= n_starts <= 16)"; return ICPMI_ERR_INVALID_ARG;
     }
     { const icpmi_status ps = reject_plane_to_plane(h, "register_multistart"); if (ps != ICPMI_OK) return ps; }
+    { const icpmi_status is = reject_intensity(h, "register_multistart"); if (is != ICPMI_OK) return is; }
     h->scan_map_n = 0; // (the slices below reuse the stage of icpmi_register_prior: nothing is left staged)
     const int64_t NS = (n + 63) / 64 * 64;
     if (h->d_scan_map.ensure(h, (size_t)NS * n_starts + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
@@ -1164,6 +1218,8 @@ icpmi_status icpmi_outlier_weights(icpmi_handle h, const float* d2, const int32_
 static icpmi_status minimize_step_impl(icpmi_handle h, const float* reading4, int64_t n, const float* read_normals3, const float* T_iter,
                                        float T_step[16], double sums[32], icpmi_stats* stats)
 {
+    const int64_t have_int_n = h->read_int_n; // (the one-shot intensity row belongs to THIS call whatever becomes of it)
+    h->read_int_n = 0;
     if (n <= 0 || !reading4) { h->last_error = "minimize_step: bad arguments"; return ICPMI_ERR_INVALID_ARG; }
     { const icpmi_status es = check_ext_filters(h); if (es != ICPMI_OK) return es; }
     { const icpmi_status rs = reject_reading_source(h, "minimize_step"); if (rs != ICPMI_OK) return rs; }
@@ -1190,6 +1246,7 @@ static icpmi_status minimize_step_impl(icpmi_handle h, const float* reading4, in
             if (!read_normals3) { h->last_error = "minimize_step: SurfaceNormal filter needs icpmi_register"; return ICPMI_ERR_UNSUPPORTED; }
             if (!h->has_normals) { h->last_error = "InvalidField: SurfaceNormalOutlierFilter needs 'normals' on both reading and map"; return ICPMI_ERR_MISSING_NORMALS; }
         }
+    { const icpmi_status is = intensity_setup(h, "minimize_step", n, have_int_n, &lc); if (is != ICPMI_OK) return is; }
     if (read_normals3) {
         const icpmi_status us = loop_upload_read_normals(h, read_normals3, n);
         if (us != ICPMI_OK) return us;
@@ -1245,6 +1302,39 @@ icpmi_status icpmi_get_plane_pair_model(icpmi_handle h, int32_t* model)
     if (!model) { h->last_error = "get_plane_pair_model: model is null"; return ICPMI_ERR_INVALID_ARG; }
     *model = h->plane_model;
     return ICPMI_OK;
+}
+
+icpmi_status icpmi_set_intensity_weight(icpmi_handle h, float w)
+{
+    CHECK_H(h);
+    if (!std::isfinite(w) || !(w >= 0.f) || !(w < 1.f)) { h->last_error = "set_intensity_weight: the weight (1 - lambdaGeometric) must be finite and in [0, 1)"; return ICPMI_ERR_INVALID_ARG; }
+    h->intensity_w = w; // (no graph to drop: make_loop_cfg puts it into the LoopCfg, which loop_sig hashes)
+    return ICPMI_OK;
+}
+
+icpmi_status icpmi_get_intensity_weight(icpmi_handle h, float* w)
+{
+    CHECK_H(h);
+    if (!w) { h->last_error = "get_intensity_weight: w is null"; return ICPMI_ERR_INVALID_ARG; }
+    *w = h->intensity_w;
+    return ICPMI_OK;
+}
+
+icpmi_status icpmi_set_map_intensity(icpmi_handle h, const float* intensity, int64_t m, int32_t knn)
+{
+    CHECK_H(h);
+    h->gi_m = 0; // (a failed call leaves no channel)
+    if (!intensity || m <= 0 || m != h->m) { h->last_error = "set_map_intensity: one intensity per point of the resident map (m must equal its size)"; return ICPMI_ERR_INVALID_ARG; }
+    if (!h->has_normals) { h->last_error = "InvalidField: set_map_intensity needs the descriptor 'normals' on the map (the gradients live in its tangent planes)"; return ICPMI_ERR_MISSING_NORMALS; }
+    return ops_set_map_intensity(h, intensity, m, knn);
+}
+
+icpmi_status icpmi_intensity_gradient(icpmi_handle h, const float* pts4, int64_t m, const float* normals3, const float* intensity, int32_t knn,
+                                      float* grad3_out)
+{
+    CHECK_H(h);
+    if (m < 0 || (m > 0 && (!pts4 || !normals3 || !intensity || !grad3_out))) { h->last_error = "intensity_gradient: bad arguments"; return ICPMI_ERR_INVALID_ARG; }
+    return ops_intensity_gradient(h, pts4, m, normals3, intensity, knn, grad3_out);
 }
 
 icpmi_status icpmi_surface_normals(icpmi_handle h, const float* pts4, int64_t m, int32_t knn, float* normals3)
@@ -1735,7 +1825,7 @@ static icpmi_status sweep_impl(icpmi_handle h, const char* who, const float* d_s
                                const float* T_end, const icpmi_sweep_options* opts, icpmi_sweep_result* result, float* d_out4, double* sums80)
 {
     const int64_t have_scalar_n = h->read_scalar_n, have_r2_n = h->read_r2_n;
-    h->read_scalar_n = 0; h->read_noise_n = 0; h->read_r2_n = 0;
+    h->read_scalar_n = 0; h->read_noise_n = 0; h->read_r2_n = 0; h->read_int_n = 0;
     if (result) { memset(result, 0, sizeof *result); result->trimmed_limit = -1.f; }
     if (sums80) memset(sums80, 0, 80 * sizeof(double));
     if (n < 0 || (n > 0 && (!d_scan4 || !d_t_rel)) || !T_begin || !T_end || (!sums80 && !result) || (sums80 && n < 1) ||
@@ -1743,6 +1833,7 @@ static icpmi_status sweep_impl(icpmi_handle h, const char* who, const float* d_s
         h->last_error = std::string(who) + ": bad arguments"; return ICPMI_ERR_INVALID_ARG;
     }
     { const icpmi_status os = sweep_check_options(opts, h->last_error); if (os != ICPMI_OK) return os; }
+    { const icpmi_status is = reject_intensity(h, who); if (is != ICPMI_OK) return is; }
     const icpmi_config& cfg = h->cfg;
     if (cfg.force_4dof || cfg.force_2d || cfg.is_2d || cfg.covariance || cfg.degeneracy_threshold != 0.f) {
         h->last_error = std::string(who) + ": not served with force_4dof, force_2d, is_2d, covariance or a degeneracy_threshold"; return ICPMI_ERR_INVALID_ARG;

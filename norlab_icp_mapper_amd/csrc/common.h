@@ -294,6 +294,11 @@ static inline float plane_to_plane_eps(const LoopCfg& lc) { return (lc.minimizer
 // ICPMI_PLANE_MODEL_SYMMETRIC, which has no epsilon.  The slot is part of the LoopCfg that loop_sig hashes: a model change misses a cached graph.
 #define ICPMI_PLANE_SLOT_SYMMETRIC 2.f
 static inline bool plane_pair_symmetric(const LoopCfg& lc) { return plane_to_plane_eps(lc) > 1.f; }
+// ... and a NEGATIVE value names the photometric term of the point-to-plane path (icpmi_set_intensity_weight): the slot carries
+// -(1 - lambda), in (-1, 0).  That instantiation of the pair sums owns two more slots the degeneracy-aware solve and the GenericDescriptor
+// filter leave it: degen_blk (free with degen == 0) points at the map's (g.x, g.y, g.z, I) float4 per point, in the index's order, and the
+// reading's intensity row sits behind the GenericDescriptor row in the one buffer read_scalar points at: read_scalar + n, caller's order.
+static inline float intensity_weight(const LoopCfg& lc) { return (lc.minimizer == ICPMI_MIN_POINT_TO_PLANE && lc.degen == 0 && lc.degen_thr < 0.f) ? -lc.degen_thr : 0.f; }
 // slot of the chain's Trimmed / Median / VarTrimmed filter (the last of them: the one whose limit a call reports), or -1.  Upstream, a
 // chain with one throws "no outlier to filter" on an empty reading where any other throws "no point to minimize".
 static inline int quantile_slot(const LoopCfg& lc)
@@ -736,6 +741,7 @@ struct icpmi_ctx {
     DevArr<float4> d_read_normals;
     DevArr<float> d_read_noise; int64_t read_noise_n = 0; // simpleSensorNoise of the NEXT reading (one shot)
     DevArr<float> d_read_scalar; int64_t read_scalar_n = 0; // GenericDescriptor{source: reading} row of the NEXT reading
+    int64_t read_int_n = 0; // icpmi_set_reading_intensity: the intensity row of the NEXT reading (one shot), n floats behind the n of the row above
     // KDTreeVarDistMatcher (icpmi_set_reading_max_dist): the SQUARED radii of the NEXT reading, caller's order, and the largest radius of
     // the row (un-squared; +inf when an entry is): the one bound the search prunes with
     DevArr<float> d_read_r2; int64_t read_r2_n = 0; float read_r2_max = 0.f;
@@ -805,6 +811,11 @@ struct icpmi_ctx {
     float plane_eps = 1e-3f;
     // icpmi_set_plane_pair_model: the pair model ICPMI_MIN_PLANE_TO_PLANE runs (ICPMI_PLANE_MODEL_*); handle state like plane_eps, and carried likewise
     int plane_model = ICPMI_PLANE_MODEL_GICP;
+    // icpmi_set_intensity_weight: 1 - lambdaGeometric of the photometric term on ICPMI_MIN_POINT_TO_PLANE (0: off); handle state like plane_eps,
+    // and carried likewise.  icpmi_set_map_intensity: (g.x, g.y, g.z, I) per map point in the index's order, valid for the index of map_version
+    // gi_version with gi_m points -- every map_build moves on and thereby drops the channel
+    float intensity_w = 0.f;
+    DevArr<float4> d_map_gi; uint64_t gi_version = 0; int64_t gi_m = 0;
     DevArr<IcpState> d_state;          // ICPMI_MAX_BATCH states (a single registration uses the first)
     IcpState* h_state = nullptr;                               // pinned mirror (ICPMI_MAX_BATCH)
     bool zero_pending = false;                                 // d_state / d_selhist still to be cleared: on the stream the handle really uses, at its first call (zero_state_if_pending)
@@ -909,6 +920,9 @@ static inline icpmi_status zero_state_if_pending(icpmi_ctx* c)
     c->zero_pending = false;
     return ICPMI_OK;
 }
+
+// icpmi_set_map_intensity's channel belongs to the index it was computed for
+static inline bool map_intensity_ready(const icpmi_ctx* c) { return c->d_map_gi.get() && c->gi_m > 0 && c->gi_m == c->m && c->gi_version == c->map_version; }
 
 static inline void drop_loop_graphs(icpmi_ctx* c)
 {
@@ -1448,6 +1462,9 @@ icpmi_status max_density_flags_dev(icpmi_ctx* c, const float* d_dens, int64_t n,
 icpmi_status ops_max_density_keep(icpmi_ctx* c, const float* densities, int64_t n, float max_density, int seed, uint8_t* keep);
 icpmi_status ops_surface_normals(icpmi_ctx* c, const float* pts4, int64_t m, int knn, float* normals3, float* densities = nullptr,
                                  int32_t* matched_ids = nullptr, float* mean_dist = nullptr, float* eig_values = nullptr, float* eig_vectors = nullptr);
+// pointops.hip: the intensity gradients of a cloud with normals (host pointers), and the resident map's (g, I) channel from the caller's row
+icpmi_status ops_intensity_gradient(icpmi_ctx* c, const float* pts4, int64_t m, const float* normals3, const float* intensity, int knn, float* grad3);
+icpmi_status ops_set_map_intensity(icpmi_ctx* c, const float* intensity, int64_t m, int knn);
 // test seams (icpmi_debug_self_knn / icpmi_debug_resident_kth_d2)
 icpmi_status ops_debug_self_knn(icpmi_ctx* c, const float* pts4, int64_t m, int k, int32_t* ids, float* d2, uint64_t* info);
 icpmi_status ops_debug_resident_kth_d2(icpmi_ctx* c, int64_t m, float* out, int32_t* knn_out);

@@ -67,6 +67,9 @@ __device__ __forceinline__ float3 cross3(float3 a, float3 b) { return make_float
 // the symmetric pair model of the plane-to-plane path (include/icpmi.h: ICPMI_PLANE_MODEL_SYMMETRIC): a tag of this file for accumulate_kernel's
 // MIN, next to the icpmi_minimizer values -- no minimizer of the interface (4 stays unknown there)
 constexpr int PAIR_SYMMETRIC = 16;
+// the photometric term on the point-to-plane path (icpmi_set_intensity_weight): likewise a tag of this file, launched in place of
+// <ICPMI_MIN_POINT_TO_PLANE, ...> when the weight is non-zero (common.h: intensity_weight has the slots this instantiation owns)
+constexpr int PAIR_INTENSITY = 17;
 
 template <int MIN, bool FUSED, bool EXT, int BT = 256>
 __global__ __launch_bounds__(BT) void accumulate_kernel(const float4* __restrict__ reading, BatchArgs ba, int acc_cap, LoopCfg lc,
@@ -123,6 +126,12 @@ __global__ __launch_bounds__(BT) void accumulate_kernel(const float4* __restrict
     constexpr int PF = BT > 256 ? 3 : 2;
     // the pair models that read the normals of BOTH clouds (plane-to-plane and the symmetric one): same gathers, same two trips
     constexpr bool BOTH_N = MIN == ICPMI_MIN_PLANE_TO_PLANE || MIN == PAIR_SYMMETRIC;
+    // the photometric term reads the match's (g, I) and the reading's intensity by the caller's index: the same two trips, q and the caller's
+    // index with the first (TRIP1_Q: the pair models whose second trip needs them)
+    constexpr bool INTENS = MIN == PAIR_INTENSITY;
+    constexpr bool TRIP1_Q = BOTH_N || INTENS;
+    const float4* __restrict__ map_gi = INTENS ? reinterpret_cast<const float4*>(lc.degen_blk) : nullptr; // (common.h: intensity_weight)
+    const float* __restrict__ read_int = (INTENS && lc.read_scalar) ? lc.read_scalar + n : nullptr;
     unsigned hw = hdr_load(st);
     float pd2[PF]; int ps[PF]; float4 pr[PF], pq[PF];
     int po[PF]; // plane-to-plane: the caller's index of the reading point, whose normal the second trip fetches
@@ -133,8 +142,8 @@ __global__ __launch_bounds__(BT) void accumulate_kernel(const float4* __restrict
         pd2[u] = in ? ld_stream(d2a + e) : INFINITY;
         ps[u] = in ? ld_stream(sidx + e) : -1;
         pr[u] = ld_stream(reading + (in ? (int)(e / lc.k) : 0));
-        if constexpr (BOTH_N) po[u] = in ? (qindex ? ld_stream(qindex + (int)(e / lc.k)) : (int)(e / lc.k)) : -1;
-        if constexpr (BOTH_N) // (every pair arrives at the sums with all four of its gathers: no dependent load behind them)
+        if constexpr (TRIP1_Q) po[u] = in ? (qindex ? ld_stream(qindex + (int)(e / lc.k)) : (int)(e / lc.k)) : -1;
+        if constexpr (TRIP1_Q) // (every pair arrives at the sums with all four of its gathers: no dependent load behind them)
             pq[u] = (match_pt && in) ? ld_stream(match_pt + e) : (ps[u] >= 0 ? (pnm ? pnm[2 * (size_t)ps[u]] : map[ps[u]]) : make_float4(0.f, 0.f, 0.f, 0.f));
         else
             pq[u] = (match_pt && in) ? ld_stream(match_pt + e) : ((pnm && ps[u] >= 0) ? pnm[2 * (size_t)ps[u]] : make_float4(0.f, 0.f, 0.f, 0.f));
@@ -152,12 +161,18 @@ __global__ __launch_bounds__(BT) void accumulate_kernel(const float4* __restrict
     for (int i = 0; i < 16; ++i) T[i] = hv.f(ICPMI_HDR_W(T_iter) + i);
     // second round trip, overlapping the fine-histogram read of the selection scan: the matched normals
     // (plane-to-plane: ... and the reading's own normals, by the caller's index that arrived with the first trip)
-    constexpr bool USES_N = MIN == ICPMI_MIN_POINT_TO_PLANE || BOTH_N;
+    constexpr bool USES_N = MIN == ICPMI_MIN_POINT_TO_PLANE || BOTH_N || INTENS;
     float4 pn[PF], prn[PF];
+    float pip[PF]; // the photometric term: the reading point's intensity (prn carries the match's (g, I) there)
 #pragma unroll
     for (int u = 0; u < PF; ++u) {
         prn[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-        if constexpr (BOTH_N) {
+        pip[u] = 0.f;
+        if constexpr (INTENS) { // (a missing channel or row never gets here -- api.hip refuses the call; NaN would leave the geometric part)
+            pn[u] = ps[u] >= 0 ? (pnm ? pnm[2 * (size_t)ps[u] + 1] : normals[ps[u]]) : make_float4(0.f, 0.f, 0.f, 0.f);
+            prn[u] = (map_gi && ps[u] >= 0) ? map_gi[ps[u]] : make_float4(0.f, 0.f, 0.f, NAN);
+            pip[u] = (read_int && po[u] >= 0) ? read_int[po[u]] : NAN;
+        } else if constexpr (BOTH_N) {
             pn[u] = ps[u] >= 0 ? ld_normal(pnm ? pnm + 2 * (size_t)ps[u] + 1 : normals + ps[u]) : make_float4(0.f, 0.f, 0.f, 0.f);
             if (po[u] >= 0) prn[u] = ld_normal(read_normals + po[u]);
         } else {
@@ -187,30 +202,30 @@ __global__ __launch_bounds__(BT) void accumulate_kernel(const float4* __restrict
     double wsum = 0.0, cnt = 0.0;
     double b2d[3] = {0.0, 0.0, 0.0}; // force2D: b of the 2-D residual (EXT variant only)
     // BOTH_N: the caller hands over everything the pair needs -- q, n_q, the reading's normal and its caller's index okept
-    auto pair = [&](int64_t e, float d2, int s, float4 r, float4 qkept, float4 nkept, bool have_n, float4 rnkept, int okept) {
+    auto pair = [&](int64_t e, float d2, int s, float4 r, float4 qkept, float4 nkept, bool have_n, float4 rnkept, int okept, float ipkept) {
         if (d2 == INFINITY) return;
         const int qi = (int)(e / lc.k);
         float w;
         if (EXT) {
             // the filters that read the pair itself: original index of the matched point (its .w), point-to-plane residual
             const float3 pe = xf_point(T, r.x, r.y, r.z, r.w);
-            const float4 qe = (BOTH_N || match_pt || (pnm && have_n)) ? qkept : (pnm ? pnm[2 * (size_t)s] : map[s]);
+            const float4 qe = (TRIP1_Q || match_pt || (pnm && have_n)) ? qkept : (pnm ? pnm[2 * (size_t)s] : map[s]);
             float plane2 = 0.f;
             if (normals) {
-                const float4 ne = BOTH_N || (have_n && USES_N) ? nkept : (pnm ? pnm[2 * (size_t)s + 1] : normals[s]);
+                const float4 ne = TRIP1_Q || (have_n && USES_N) ? nkept : (pnm ? pnm[2 * (size_t)s + 1] : normals[s]);
                 const float dx = pe.x - qe.x, dy = pe.y - qe.y, dz = pe.z - qe.z;
                 const float dot = dx * ne.x + dy * ne.y + dz * ne.z;
                 plane2 = dot * dot;
             }
-            w = match_weight<true>(lc, st, d2, T, read_normals, BOTH_N ? okept : (qindex ? qindex[qi] : qi), normals, s, FUSED ? fused_slot : -1, fused_limit,
+            w = match_weight<true>(lc, st, d2, T, read_normals, TRIP1_Q ? okept : (qindex ? qindex[qi] : qi), normals, s, FUSED ? fused_slot : -1, fused_limit,
                                    ref_scalar, __float_as_int(qe.w), plane2, BOTH_N ? &rnkept : nullptr);
-        } else w = match_weight(lc, st, d2, T, read_normals, BOTH_N ? okept : (qindex ? qindex[qi] : qi), normals, s, FUSED ? fused_slot : -1, fused_limit,
+        } else w = match_weight(lc, st, d2, T, read_normals, TRIP1_Q ? okept : (qindex ? qindex[qi] : qi), normals, s, FUSED ? fused_slot : -1, fused_limit,
                                 nullptr, 0, 0.f, BOTH_N ? &rnkept : nullptr);
         if (w == 0.f) return;
         wsum += w; cnt += 1.0;
         if (MIN == ICPMI_MIN_IDENTITY) return;
         const float3 p = xf_point(T, r.x, r.y, r.z, r.w);
-        const float4 q = (BOTH_N || match_pt || (pnm && have_n)) ? qkept : (pnm ? pnm[2 * (size_t)s] : map[s]);
+        const float4 q = (TRIP1_Q || match_pt || (pnm && have_n)) ? qkept : (pnm ? pnm[2 * (size_t)s] : map[s]);
         if (MIN == ICPMI_MIN_POINT_TO_POINT) {
             const double dw = w;
             acc[0] += dw;
@@ -240,6 +255,42 @@ __global__ __launch_bounds__(BT) void accumulate_kernel(const float4* __restrict
                 const float dot2 = dx * nn.x + dy * nn.y; // upstream drops the z row of the features and of the normals
 #pragma unroll
                 for (int a = 0; a < 3; ++a) b2d[a] -= ((double)w * F[2 + a]) * dot2;
+            }
+        } else if constexpr (MIN == PAIR_INTENSITY) {
+            // joint geometric + photometric point-to-plane: two rank-1 updates per pair into the point-to-plane slots,
+            // A += w (lambda F_G F_G^T + (1 - lambda) F_I F_I^T), b -= w (lambda F_G r_G + (1 - lambda) F_I r_I).  The geometric terms are the
+            // point-to-plane branch's, bit for bit; per-pair terms in float, the weight's products and the sums in double
+            const float4 nn = nkept, gi = rnkept;
+            const float wi = -lc.degen_thr, lam = 1.f - wi; // (the slot carries -(1 - lambda) for this instantiation: common.h, intensity_weight)
+            const float F[6] = {p.y * nn.z - p.z * nn.y, p.z * nn.x - p.x * nn.z, p.x * nn.y - p.y * nn.x, nn.x, nn.y, nn.z};
+            const float dx = p.x - q.x, dy = p.y - q.y, dz = p.z - q.z;
+            const float dot = dx * nn.x + dy * nn.y + dz * nn.z;
+            const double wg = (double)w * (double)lam;
+            int idx = 0;
+#pragma unroll
+            for (int a = 0; a < 6; ++a) {
+                const double wf = wg * F[a];
+#pragma unroll
+                for (int b = a; b < 6; ++b) acc[idx++] += wf * F[b];
+                acc[21 + a] -= wf * dot;
+            }
+            // a pair whose I_p or I_q is not finite adds the geometric part only
+            if (fabsf(gi.w) < INFINITY && fabsf(ipkept) < INFINITY) {
+                // m = g - n (g . n): the gradient's part in the match's plane; p' = p - n r_G: the reading point's foot on that plane
+                const float gn = gi.x * nn.x + gi.y * nn.y + gi.z * nn.z;
+                const float mx = gi.x - nn.x * gn, my = gi.y - nn.y * gn, mz = gi.z - nn.z * gn;
+                const float ex = dx - nn.x * dot, ey = dy - nn.y * dot, ez = dz - nn.z * dot;
+                const float ri = (gi.w + (gi.x * ex + gi.y * ey + gi.z * ez)) - ipkept;
+                const float G[6] = {p.y * mz - p.z * my, p.z * mx - p.x * mz, p.x * my - p.y * mx, mx, my, mz};
+                const double wp = (double)w * (double)wi;
+                idx = 0;
+#pragma unroll
+                for (int a = 0; a < 6; ++a) {
+                    const double wf = wp * G[a];
+#pragma unroll
+                    for (int b = a; b < 6; ++b) acc[idx++] += wf * G[b];
+                    acc[21 + a] -= wf * ri;
+                }
             }
         } else if constexpr (MIN == ICPMI_MIN_PLANE_TO_PLANE) {
             // generalized ICP with plane-regularised covariances: A += w G M G^T, b -= w G M d with G = J^T = [[p]x; I],
@@ -298,7 +349,7 @@ __global__ __launch_bounds__(BT) void accumulate_kernel(const float4* __restrict
         }
     };
 #pragma unroll
-    for (int u = 0; u < PF; ++u) pair(e_first + u * estep, pd2[u], ps[u], pr[u], pq[u], pn[u], true, prn[u], BOTH_N ? po[u] : 0);
+    for (int u = 0; u < PF; ++u) pair(e_first + u * estep, pd2[u], ps[u], pr[u], pq[u], pn[u], true, prn[u], TRIP1_Q ? po[u] : 0, pip[u]);
     if constexpr (BOTH_N) {
         for (int64_t e = e_first + PF * estep; e < e_end; e += estep) { // (past a full grid: the four gathers of a pair requested together)
             const float d2 = d2a[e];
@@ -306,12 +357,22 @@ __global__ __launch_bounds__(BT) void accumulate_kernel(const float4* __restrict
             if (s < 0) continue; // (no match: d2 is +inf)
             const float4 r = reading[qi], q = match_pt ? match_pt[e] : (pnm ? pnm[2 * (size_t)s] : map[s]);
             const float4 nq = ld_normal(pnm ? pnm + 2 * (size_t)s + 1 : normals + s), rn = ld_normal(read_normals + oi);
-            pair(e, d2, s, r, q, nq, true, rn, oi);
+            pair(e, d2, s, r, q, nq, true, rn, oi, 0.f);
+        }
+    } else if constexpr (INTENS) {
+        for (int64_t e = e_first + PF * estep; e < e_end; e += estep) { // (likewise: everything a pair reads is requested together)
+            const float d2 = d2a[e];
+            const int s = sidx[e], qi = (int)(e / lc.k), oi = qindex ? qindex[qi] : qi;
+            if (s < 0) continue; // (no match: d2 is +inf)
+            const float4 r = reading[qi], q = match_pt ? match_pt[e] : (pnm ? pnm[2 * (size_t)s] : map[s]);
+            const float4 nq = pnm ? pnm[2 * (size_t)s + 1] : normals[s];
+            const float4 gi = map_gi ? map_gi[s] : make_float4(0.f, 0.f, 0.f, NAN);
+            pair(e, d2, s, r, q, nq, true, gi, oi, read_int ? read_int[oi] : NAN);
         }
     } else {
         for (int64_t e = e_first + PF * estep; e < e_end; e += estep)
             pair(e, d2a[e], sidx[e], reading[(int)(e / lc.k)], match_pt ? match_pt[e] : make_float4(0.f, 0.f, 0.f, 0.f),
-                 make_float4(0.f, 0.f, 0.f, 0.f), false, make_float4(0.f, 0.f, 0.f, 0.f), 0);
+                 make_float4(0.f, 0.f, 0.f, 0.f), false, make_float4(0.f, 0.f, 0.f, 0.f), 0, 0.f);
     }
     // ---- workgroup reduction: wave64 shuffles, then LDS across the 4 waves ----
     // Transposed butterfly: at the step with partner lane ^ m every lane hands over the half of its
@@ -516,6 +577,12 @@ LoopCfg make_loop_cfg(const icpmi_ctx* c, int fixed_iterations)
         lc.degen = cfg.degeneracy_threshold > 0.f ? ICPMI_DG_CONSTRAIN : ICPMI_DG_REPORT;
         lc.degen_thr = fabsf(cfg.degeneracy_threshold);
         lc.degen_blk = c->d_degen.get();
+    }
+    // the photometric term of the point-to-plane path (common.h: intensity_weight): its weight and the map's (g, I) array in the two slots the
+    // degeneracy-aware solve leaves free (api.hip rejects the combination) -- both part of the LoopCfg that loop_sig hashes
+    if (c->intensity_w > 0.f && cfg.minimizer == ICPMI_MIN_POINT_TO_PLANE && lc.degen == 0) {
+        lc.degen_thr = -c->intensity_w;
+        lc.degen_blk = map_intensity_ready(c) ? reinterpret_cast<double*>(c->d_map_gi.get()) : nullptr;
     }
     if (gicp) lc.degen_thr = c->plane_model == ICPMI_PLANE_MODEL_SYMMETRIC ? ICPMI_PLANE_SLOT_SYMMETRIC : c->plane_eps; // (degen stays 0: validate_config rejects the combination; common.h: plane_to_plane_eps)
     return lc;
@@ -938,7 +1005,7 @@ static void launch_accumulate_ext(icpmi_ctx* c, const LoopCfg& lc, int nb, int s
     const int is_med = slot >= 0 && lc.out_type[slot] == ICPMI_OUT_MEDIANDIST;
     const float factor = slot >= 0 ? lc.out_param[slot] : 0.f;
     // k > 1, point-to-plane: matched point and its normal side by side (map_build.hip: pn_kernel)
-    const float4* pnm = (lc.k > 1 && (MIN == ICPMI_MIN_POINT_TO_PLANE || MIN == ICPMI_MIN_PLANE_TO_PLANE || MIN == PAIR_SYMMETRIC) && c->has_normals && c->d_map_pn) ? c->d_map_pn.get() : nullptr;
+    const float4* pnm = (lc.k > 1 && (MIN == ICPMI_MIN_POINT_TO_PLANE || MIN == ICPMI_MIN_PLANE_TO_PLANE || MIN == PAIR_SYMMETRIC || MIN == PAIR_INTENSITY) && c->has_normals && c->d_map_pn) ? c->d_map_pn.get() : nullptr;
     if (lc.k > 1)
         hipLaunchKernelGGL((accumulate_kernel<MIN, FUSED, EXT, 1024>), dim3(nb, ba.nscan), dim3(1024), 0, c->stream, v.reading, ba, acc_cap(), lc, c->d_state,
                            v.map, v.ref_normals, v.read_normals, v.sidx, v.d2, c->d_selhist, slot, is_med, factor, v.match_pt, v.qindex, v.ref_scalar, pnm);
@@ -964,6 +1031,9 @@ static void enqueue_accumulate_solve(icpmi_ctx* c, int64_t n, const LoopCfg& lc,
     } else if (plane_to_plane_eps(lc) > 0.f) { // (its own instantiation of the pair sums; the solve below reads lc.minimizer: point-to-plane)
         if (fused) launch_accumulate<ICPMI_MIN_PLANE_TO_PLANE, true>(c, lc, nb, slot, ba, nn.out_sorted);
         else launch_accumulate<ICPMI_MIN_PLANE_TO_PLANE, false>(c, lc, nb, slot, ba, nn.out_sorted);
+    } else if (intensity_weight(lc) > 0.f) { // (point-to-plane with the photometric term: likewise its own instantiation, the same solve)
+        if (fused) launch_accumulate<PAIR_INTENSITY, true>(c, lc, nb, slot, ba, nn.out_sorted);
+        else launch_accumulate<PAIR_INTENSITY, false>(c, lc, nb, slot, ba, nn.out_sorted);
     } else if (lc.minimizer == ICPMI_MIN_POINT_TO_PLANE) {
         if (fused) launch_accumulate<ICPMI_MIN_POINT_TO_PLANE, true>(c, lc, nb, slot, ba, nn.out_sorted);
         else launch_accumulate<ICPMI_MIN_POINT_TO_PLANE, false>(c, lc, nb, slot, ba, nn.out_sorted);

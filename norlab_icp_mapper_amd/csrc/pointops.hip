@@ -229,6 +229,89 @@ __global__ __launch_bounds__(128) void normals_kernel(const float4* __restrict__
     normals3[3 * i] = nx; normals3[3 * i + 1] = ny; normals3[3 * i + 2] = nz;
 }
 
+// ---- intensity gradients of a cloud with normals (icpmi_intensity_gradient / icpmi_set_map_intensity) ----
+// the intensities in the order of the search index: position s of `sorted` holds the cloud's point float_as_uint(sorted[s].w), whose
+// intensity is inten[that index] -- or, iperm != nullptr (the resident map: the cloud is the registration index's sorted array, the row is
+// in the caller's order), inten[float_as_uint(iperm[that index].w)]
+__global__ __launch_bounds__(256) void intensity_gather_kernel(const float4* __restrict__ sorted, int64_t m, const float* __restrict__ inten,
+                                                               const float4* __restrict__ iperm, float* __restrict__ out)
+{
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    for (int64_t s = (int64_t)blockIdx.x * 256 + threadIdx.x; s < m; s += stride) {
+        unsigned o = __float_as_uint(sorted[s].w);
+        if (iperm && o < (unsigned)m) o = __float_as_uint(iperm[o].w);
+        out[s] = o < (unsigned)m ? inten[o] : NAN; // (an index past the row: never for a cloud the search built; NaN = no intensity)
+    }
+}
+
+// One lane per point of the cloud, grid-stride: the least-squares gradient of the intensity over its K = k - 1 nearest other points, in the
+// tangent plane of its normal.  rows of sidx: the cloud's order, entries = positions in `sorted` (-1: unfilled), the point itself (or a
+// duplicate of it) first; isorted: intensity_gather_kernel's row.  nrm: the normals in the cloud's order, nstride floats apart.  Float
+// arithmetic in neighbour order, no atomics: the same bits on every call.  The neighbour ids of a chunk are requested together, then their
+// points and intensities: two round trips per CH neighbours.
+// Out: grad3 (3 floats per point) and / or gi4 = (g.x, g.y, g.z, I) per point.
+__global__ __launch_bounds__(256) void intensity_gradient_kernel(const float4* __restrict__ sorted, const int* __restrict__ sidx, const float* __restrict__ isorted,
+                                                                 const float* __restrict__ nrm, int nstride, const float* __restrict__ inten,
+                                                                 const float4* __restrict__ iperm, int64_t m, int k, float* __restrict__ grad3,
+                                                                 float4* __restrict__ gi4)
+{
+    constexpr int CH = 8;
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < m; i += stride) {
+        const int* row = sidx + (size_t)k * i;
+        const int s0 = row[0];
+        const float nx = nrm[(size_t)nstride * i], ny = nrm[(size_t)nstride * i + 1], nz = nrm[(size_t)nstride * i + 2];
+        unsigned io = (unsigned)i;
+        if (iperm) io = __float_as_uint(iperm[i].w);
+        const float Ii = io < (unsigned)m ? inten[io] : NAN;
+        const float4 xi = sorted[s0 < 0 ? 0 : s0];
+        // u = n / |n|; a zero or non-finite normal has no tangent plane
+        const float l2 = nx * nx + ny * ny + nz * nz;
+        const bool ok = s0 >= 0 && l2 > 0.f && l2 < INFINITY && fabsf(Ii) < INFINITY;
+        const float inv = 1.f / sqrtf(ok ? l2 : 1.f);
+        const float ux = nx * inv, uy = ny * inv, uz = nz * inv;
+        // e1 = normalise(u x axis), axis = the coordinate axis of the smallest |u| component (the first of equals); e2 = u x e1
+        const float ax = fabsf(ux), ay = fabsf(uy), az = fabsf(uz);
+        float cx, cy, cz;
+        if (ax <= ay && ax <= az) { cx = 0.f; cy = uz; cz = -uy; }
+        else if (ay <= az) { cx = -uz; cy = 0.f; cz = ux; }
+        else { cx = uy; cy = -ux; cz = 0.f; }
+        const float cinv = 1.f / sqrtf(cx * cx + cy * cy + cz * cz);
+        const float e1x = cx * cinv, e1y = cy * cinv, e1z = cz * cinv;
+        const float e2x = uy * e1z - uz * e1y, e2y = uz * e1x - ux * e1z, e2z = ux * e1y - uy * e1x;
+        float saa = 0.f, sab = 0.f, sbb = 0.f, ra = 0.f, rb = 0.f;
+        int used = 0;
+        for (int j0 = 1; j0 < k && ok; j0 += CH) {
+            int sv[CH]; float4 xv[CH]; float iv[CH];
+#pragma unroll
+            for (int j = 0; j < CH; ++j) sv[j] = j0 + j < k ? row[j0 + j] : -1;
+#pragma unroll
+            for (int j = 0; j < CH; ++j) { xv[j] = sorted[sv[j] < 0 ? 0 : sv[j]]; iv[j] = isorted[sv[j] < 0 ? 0 : sv[j]]; }
+#pragma unroll
+            for (int j = 0; j < CH; ++j) {
+                if (sv[j] < 0 || !(fabsf(iv[j]) < INFINITY)) continue; // unfilled slot; a neighbour without an intensity
+                const float dx = xv[j].x - xi.x, dy = xv[j].y - xi.y, dz = xv[j].z - xi.z;
+                const float t = dx * ux + dy * uy + dz * uz;
+                const float px = dx - ux * t, py = dy - uy * t, pz = dz - uz * t;
+                const float a = px * e1x + py * e1y + pz * e1z, b = px * e2x + py * e2y + pz * e2z;
+                const float dI = iv[j] - Ii;
+                saa += a * a; sab += a * b; sbb += b * b;
+                ra += a * dI; rb += b * dI;
+                ++used;
+            }
+        }
+        // g2 = S^-1 r in closed form; neighbours on a line or on the point itself (det S <= 1e-4 (tr S / 2)^2) give no gradient
+        const float det = saa * sbb - sab * sab, htr = (saa + sbb) * 0.5f;
+        float gx = 0.f, gy = 0.f, gz = 0.f;
+        if (ok && used >= 2 && det > 1e-4f * (htr * htr)) {
+            const float g2x = (sbb * ra - sab * rb) / det, g2y = (saa * rb - sab * ra) / det;
+            gx = g2x * e1x + g2y * e2x; gy = g2x * e1y + g2y * e2y; gz = g2x * e1z + g2y * e2z;
+        }
+        if (grad3) { grad3[3 * i] = gx; grad3[3 * i + 1] = gy; grad3[3 * i + 2] = gz; }
+        if (gi4) gi4[i] = make_float4(gx, gy, gz, Ii);
+    }
+}
+
 } // namespace
 
 // k <= 10 (the shipped SurfaceNormalDataPointsFilter{knn: 10}) and k <= 16 keep the neighbourhood in registers; ICPMI_NORMALS_REG=0: the generic walk
@@ -567,6 +650,77 @@ icpmi_status ops_surface_normals(icpmi_ctx* c, const float* pts4, int64_t m, int
     if (e == hipSuccess && densities) e = hipMemcpyAsync(densities, d_dens, (size_t)m * sizeof(float), hipMemcpyDeviceToHost, tc->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(tc->stream);
     HIP_TRY(c, e);
+    return ICPMI_OK;
+}
+
+// workgroups of the two intensity kernels: one lane per point up to 2048 workgroups, a grid-stride walk past that
+static int intensity_grid(int64_t m) { const int64_t nb = (m + 255) / 256; return (int)(nb > 2048 ? 2048 : nb); }
+
+// the gradient pass behind a self search of the private handle tc over a cloud of m points with k = knn + 1 (rows in tc->d_sidx, the search's
+// order in tc->d_map_sorted): d_nrm / nstride, d_inten, iperm as intensity_gradient_kernel takes them; d_isorted: m floats of scratch
+static void launch_intensity_gradient(icpmi_ctx* tc, int64_t m, int k, const float* d_nrm, int nstride, const float* d_inten, const float4* iperm,
+                                      float* d_isorted, float* d_grad3, float4* d_gi4)
+{
+    const int nb = intensity_grid(m);
+    hipLaunchKernelGGL(intensity_gather_kernel, dim3(nb), dim3(256), 0, tc->stream, (const float4*)tc->d_map_sorted, m, d_inten, iperm, d_isorted);
+    hipLaunchKernelGGL(intensity_gradient_kernel, dim3(nb), dim3(256), 0, tc->stream, (const float4*)tc->d_map_sorted, (const int*)tc->d_sidx,
+                       (const float*)d_isorted, d_nrm, nstride, d_inten, iperm, m, k, d_grad3, d_gi4);
+}
+
+// icpmi_intensity_gradient: the operator on host pointers -- the self search of ops_surface_normals with k = knn + 1, then the gradient pass
+icpmi_status ops_intensity_gradient(icpmi_ctx* c, const float* pts4, int64_t m, const float* normals3, const float* intensity, int knn, float* grad3)
+{
+    if (m == 0) return ICPMI_OK;
+    if (knn < 1 || knn > ICPMI_MAX_K - 1) { c->last_error = "intensity_gradient: knn must be in [1, 31]"; return ICPMI_ERR_INVALID_ARG; }
+    TempCtx t;
+    icpmi_status s = make_temp(c, t);
+    if (s != ICPMI_OK) return s;
+    c->dk_m = 0; // (the private handle's grid is searched over another cloud: the k-th distances remembered for the resident map's next append are gone)
+    s = temp_knn(c, t, pts4, m, nullptr, m, knn + 1, 1, true);
+    if (s != ICPMI_OK) return s;
+    icpmi_ctx* tc = t.h;
+    DevBuf<float> d_n, d_i, d_is, d_g;
+    HIP_TRY(c, d_n.alloc((size_t)m * 3));
+    HIP_TRY(c, d_i.alloc((size_t)m));
+    HIP_TRY(c, d_is.alloc((size_t)m));
+    HIP_TRY(c, d_g.alloc((size_t)m * 3));
+    HIP_TRY(c, hipMemcpyAsync(d_n, normals3, (size_t)m * 3 * sizeof(float), hipMemcpyHostToDevice, tc->stream));
+    HIP_TRY(c, hipMemcpyAsync(d_i, intensity, (size_t)m * sizeof(float), hipMemcpyHostToDevice, tc->stream));
+    launch_intensity_gradient(tc, m, knn + 1, d_n, 3, d_i, nullptr, d_is, d_g, nullptr);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(grad3, d_g, (size_t)m * 3 * sizeof(float), hipMemcpyDeviceToHost, tc->stream));
+    HIP_TRY(c, hipStreamSynchronize(tc->stream));
+    return ICPMI_OK;
+}
+
+// icpmi_set_map_intensity: the same two kernels over the resident map AS THE INDEX HOLDS IT -- the cloud is c->d_map_sorted (a gradient does
+// not see the centring), its normals c->d_normals_sorted, so the (g, I) row comes out in the index's order, the way the normals are kept; the
+// caller's row is read through the original index in every sorted point's w.  The caller has checked m == c->m and the normals.
+icpmi_status ops_set_map_intensity(icpmi_ctx* c, const float* intensity, int64_t m, int knn)
+{
+    if (knn < 1 || knn > ICPMI_MAX_K - 1) { c->last_error = "set_map_intensity: knn must be in [1, 31]"; return ICPMI_ERR_INVALID_ARG; }
+    c->gi_m = 0;
+    TempCtx t;
+    icpmi_status s = make_temp(c, t);
+    if (s != ICPMI_OK) return s;
+    icpmi_ctx* tc = t.h;
+    const int k = knn + 1;
+    const size_t cnt = (size_t)m * k + 1;
+    if (tc->d_sidx.ensure(tc, cnt) != ICPMI_OK || tc->d_d2.ensure(tc, cnt) != ICPMI_OK) { c->last_error = tc->last_error; return ICPMI_ERR_HIP; }
+    if (c->d_map_gi.ensure(c, (size_t)m + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
+    float* d_i = scratch_get<float>(c, 6, (size_t)m);
+    float* d_is = scratch_get<float>(c, 7, (size_t)m);
+    if (!d_i || !d_is) return ICPMI_ERR_HIP;
+    HIP_TRY(c, hipMemcpyAsync(d_i, intensity, (size_t)m * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    if (tc->stream != c->stream) HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->dk_m = 0; // (as in ops_intensity_gradient)
+    s = selfgrid_knn(tc, (const float4*)c->d_map_sorted, m, k, tc->d_sidx, tc->d_d2);
+    if (s != ICPMI_OK) { c->last_error = tc->last_error; return s; }
+    launch_intensity_gradient(tc, m, k, reinterpret_cast<const float*>(c->d_normals_sorted.get()), 4, d_i, (const float4*)c->d_map_sorted, d_is, nullptr,
+                              c->d_map_gi);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(tc->stream)); // the caller's row is free on return
+    c->gi_m = m; c->gi_version = c->map_version;
     return ICPMI_OK;
 }
 

@@ -83,12 +83,14 @@ void GpuICPSequence::setDefault()
     cfg.device = dev;
     cfg.is_2d = planar ? 1 : 0;
     genericDescName.clear(); genericReadDescName.clear(); maxDistFieldName.clear();
+    intensity = IntensityTerm{};
     cfg.n_outlier = 1;
     cfg.outlier[0].type = ICPMI_OUT_TRIMMEDDIST;
     cfg.outlier[0].param = 0.85f;
     cfg.minimizer = ICPMI_MIN_POINT_TO_PLANE;
     cfg.use_differential = 1;
     recreate();
+    check(h, icpmi_set_intensity_weight(h, 0.f)); // (handle state, which icpmi_set_config leaves: a chain loaded before may have set it)
     readingDataPointsFilters = std::make_shared<DataPointsFilters>();
     readingDataPointsFilters->ctx = h;
     readingDataPointsFilters->filters.push_back(createDataPointsFilter("RandomSamplingDataPointsFilter", yaml::Node(), h));
@@ -145,9 +147,10 @@ void parseMatcher(const yaml::Node& matcher, icpmi_config& cfg, std::string& max
 
 // the `errorMinimizer:` entry of an ICP chain into the configuration; planeEpsilon = PlaneToPlaneErrorMinimizer.epsilon (left alone by the
 // others), planeModel = the pair model of ICPMI_MIN_PLANE_TO_PLANE (SymmetricPointToPlaneErrorMinimizer sets it; left alone by the others)
-void parseErrorMinimizer(const yaml::Node& node, icpmi_config& cfg, float& planeEpsilon, int& planeModel)
+void parseErrorMinimizer(const yaml::Node& node, icpmi_config& cfg, float& planeEpsilon, int& planeModel, IntensityTerm* intensity)
 {
     auto e = singleEntry(node, "errorMinimizer");
+    if (intensity) *intensity = IntensityTerm{};
     if (e.first == "IdentityErrorMinimizer") cfg.minimizer = ICPMI_MIN_IDENTITY;
     else if (e.first == "PointToPointErrorMinimizer") cfg.minimizer = ICPMI_MIN_POINT_TO_POINT;
     else if (e.first == "PointToPlaneErrorMinimizer" || e.first == "PointToPlaneWithCovErrorMinimizer") {
@@ -182,6 +185,21 @@ void parseErrorMinimizer(const yaml::Node& node, icpmi_config& cfg, float& plane
         cfg.minimizer = ICPMI_MIN_PLANE_TO_PLANE;
         planeModel = ICPMI_PLANE_MODEL_SYMMETRIC;
         cfg.force_4dof = (e.second["force4DOF"] && e.second["force4DOF"].as<int>() != 0) ? 1 : 0;
+    } else if (e.first == "IntensityPointToPlaneErrorMinimizer") {
+        // point-to-plane with a photometric term from one scalar descriptor of both clouds (not libpointmatcher's; include/icpmi.h:
+        // icpmi_set_intensity_weight): the point-to-plane path with a weight on the handle
+        requireKnown(e.second, {"lambdaGeometric", "descName", "gradientKnn", "force4DOF"}, e.first);
+        cfg.minimizer = ICPMI_MIN_POINT_TO_PLANE;
+        cfg.force_4dof = (e.second["force4DOF"] && e.second["force4DOF"].as<int>() != 0) ? 1 : 0;
+        IntensityTerm t;
+        const float lambda = e.second["lambdaGeometric"] ? e.second["lambdaGeometric"].as<float>() : 0.968f;
+        if (!std::isfinite(lambda) || !(lambda > 0.f) || lambda > 1.f) throw InvalidParameter(e.first + ": lambdaGeometric must be finite and in (0, 1]");
+        t.weight = 1.f - lambda;
+        t.knn = e.second["gradientKnn"] ? e.second["gradientKnn"].as<int>() : 10;
+        if (t.knn < 1 || t.knn > 31) throw InvalidParameter(e.first + ": gradientKnn must be in [1, 31]");
+        t.descName = e.second["descName"] ? e.second["descName"].str() : std::string("intensity");
+        if (t.descName.empty()) throw InvalidParameter(e.first + ": descName must name a descriptor");
+        if (intensity) *intensity = t;
     } else throw InvalidParameter("unknown error minimizer " + e.first);
 }
 
@@ -277,7 +295,8 @@ void GpuICPSequence::loadFromYamlNode(const yaml::Node& icp)
             if (cfg.n_outlier >= 8) throw InvalidParameter("at most 8 outlier filters");
             cfg.outlier[cfg.n_outlier++] = o;
         }
-    if (icp["errorMinimizer"]) parseErrorMinimizer(icp["errorMinimizer"], cfg, planeEpsilon, planeModel);
+    intensity = IntensityTerm{};
+    if (icp["errorMinimizer"]) parseErrorMinimizer(icp["errorMinimizer"], cfg, planeEpsilon, planeModel, &intensity);
     if (icp["transformationCheckers"].IsSequence())
         for (const auto& item : icp["transformationCheckers"].seq) {
             auto e = singleEntry(item, "transformation checker");
@@ -300,6 +319,7 @@ void GpuICPSequence::loadFromYamlNode(const yaml::Node& icp)
     recreate();
     check(h, icpmi_set_plane_epsilon(h, planeEpsilon));
     check(h, icpmi_set_plane_pair_model(h, planeModel));
+    check(h, icpmi_set_intensity_weight(h, intensity.weight));
     auto chain = [&](const char* key) -> std::shared_ptr<DataPointsFilters> {
         if (!icp[key] || !icp[key].IsSequence() || icp[key].seq.empty()) return nullptr;
         return std::make_shared<DataPointsFilters>(icp[key], h);
@@ -377,7 +397,22 @@ bool GpuICPSequence::setMap(const DataPoints& mapIn)
             throw InvalidField("GenericDescriptorOutlierFilter: the reference has no 1-row descriptor " + genericDescName);
         uploadMapScalar(map.getDescriptorByName(genericDescName).data);
     }
+    if (accepted && !intensity.descName.empty()) {
+        // IntensityPointToPlaneErrorMinimizer: the map's row of its descriptor, behind every index build (the device computes the gradients)
+        if (!map.descriptorExists(intensity.descName) || map.getDescriptorByName(intensity.descName).span != 1)
+            throw InvalidField("IntensityPointToPlaneErrorMinimizer: the reference has no 1-row descriptor " + intensity.descName);
+        if (normals) check(h, icpmi_set_map_intensity(h, map.getDescriptorByName(intensity.descName).data.data(), (int64_t)map.getNbPoints(), intensity.knn));
+        // (without `normals` the registration raises InvalidField("normals"), as for PointToPlaneErrorMinimizer)
+    }
     return accepted != 0;
+}
+
+void GpuICPSequence::armReadingIntensity(const DataPoints& reading) const
+{
+    if (intensity.descName.empty()) return;
+    if (!reading.descriptorExists(intensity.descName) || reading.getDescriptorByName(intensity.descName).span != 1)
+        throw InvalidField("IntensityPointToPlaneErrorMinimizer: the reading has no 1-row descriptor " + intensity.descName);
+    check(h, icpmi_set_reading_intensity(h, reading.getDescriptorByName(intensity.descName).data.data(), (int64_t)reading.getNbPoints()));
 }
 
 void GpuICPSequence::mapUpdatePointDistance(const DataPoints& input, float minDist, int normalsKnn, std::vector<uint8_t>& keep, int64_t& appended,
@@ -396,6 +431,7 @@ Mat4 GpuICPSequence::registerWithPrior(const DataPoints& scan, const Mat4& prior
     Mat4 T = Mat4::identity();
     stagedPoints = scan.getNbPoints();
     haveCovariance = false; haveLocalizability = false;
+    armReadingIntensity(scan); // IntensityPointToPlaneErrorMinimizer: a descriptor row does not move with the prior
     check(h, icpmi_register_prior(h, scan.features.data(), (int64_t)scan.getNbPoints(), prior.data(), T.data(), &lastStats));
     keepCovariance();
     return T;
@@ -519,6 +555,7 @@ Mat4 GpuICPSequence::operator()(const DataPoints& readingIn)
             throw InvalidField("KDTreeVarDistMatcher: the reading has no 1-row descriptor " + maxDistFieldName);
         check(h, icpmi_set_reading_max_dist(h, reading.getDescriptorByName(maxDistFieldName).data.data(), (int64_t)reading.getNbPoints()));
     }
+    armReadingIntensity(reading); // IntensityPointToPlaneErrorMinimizer
     // (PointToPointErrorMinimizer::getOverlap() needs the noise row alone, only PointToPlane also the reading's normals)
     if ((normals || cfg.minimizer == ICPMI_MIN_POINT_TO_POINT) && reading.descriptorExists("simpleSensorNoise") &&
         reading.getDescriptorByName("simpleSensorNoise").span == 1)
@@ -641,7 +678,7 @@ void GpuICPSequence::requireBareReadingChain(const char* who) const
         throw InvalidParameter(std::string(who) + ": the chain (SurfaceNormalOutlierFilter, PlaneToPlaneErrorMinimizer, SymmetricPointToPlaneErrorMinimizer) reads the reading's normals, which the multistart registration does not carry");
     if (readsReadingDescriptor())
         throw InvalidParameter(std::string(who) + ": the chain reads a descriptor row of the reading (" +
-                               (!genericReadDescName.empty() ? genericReadDescName : maxDistFieldName) + "), which the multistart registration does not carry");
+                               (!genericReadDescName.empty() ? genericReadDescName : !maxDistFieldName.empty() ? maxDistFieldName : intensity.descName) + "), which the multistart registration does not carry");
 }
 
 MultiStartResult GpuICPSequence::multiStartFiltered(const DataPoints& reading, const std::vector<Mat4>& priors)

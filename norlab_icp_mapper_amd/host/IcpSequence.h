@@ -32,7 +32,14 @@ void parseMatcher(const yaml::Node& matcher, icpmi_config& cfg, std::string& max
 // the `errorMinimizer:` entry into cfg (minimizer, force2D / force4DOF, covariance, degeneracy options); planeEpsilon = the epsilon of a
 // PlaneToPlaneErrorMinimizer (default 0.001; the others leave it alone); planeModel = ICPMI_PLANE_MODEL_SYMMETRIC under
 // SymmetricPointToPlaneErrorMinimizer, which travels as ICPMI_MIN_PLANE_TO_PLANE (the others leave it alone).  Needs no GPU.
-void parseErrorMinimizer(const yaml::Node& node, icpmi_config& cfg, float& planeEpsilon, int& planeModel);
+// intensity (may be null: the entry is still parsed and checked) = the photometric term of IntensityPointToPlaneErrorMinimizer, which travels as
+// ICPMI_MIN_POINT_TO_PLANE with icpmi_set_intensity_weight (the others leave it alone: weight 0, off)
+struct IntensityTerm {
+    float weight = 0.f;                 // 1 - lambdaGeometric (icpmi_set_intensity_weight); 0: no such minimiser in the chain
+    int knn = 10;                       // gradientKnn: neighbours of a map-side gradient (icpmi_set_map_intensity)
+    std::string descName;               // descName: the 1-row descriptor both clouds carry (empty: no such minimiser)
+};
+void parseErrorMinimizer(const yaml::Node& node, icpmi_config& cfg, float& planeEpsilon, int& planeModel, IntensityTerm* intensity = nullptr);
 
 // ---- relocalisation: one reading under many poses (include/icpmi.h: icpmi_residual_error_poses, icpmi_register_multistart) ----
 // one icpmi_residual and one status per pose (a pose whose status is not ICPMI_OK keeps an empty residual); batched = the poses that
@@ -181,8 +188,11 @@ private:
     std::string genericDescName;                       // GenericDescriptorOutlierFilter.descName (empty: no such filter)
     std::string genericReadDescName;                   // ... of a filter with source: reading (the row goes to the device with every reading)
     std::string maxDistFieldName;                      // KDTreeVarDistMatcher: the reading's 1-row descriptor of search radii (empty: KDTreeMatcher)
+    IntensityTerm intensity;                           // IntensityPointToPlaneErrorMinimizer (descName empty: not in the chain)
+    void armReadingIntensity(const DataPoints& reading) const; // the reading's row of that descriptor, ahead of the call that takes the reading (one shot)
   public:
-    bool readsReadingDescriptor() const { return !genericReadDescName.empty() || !maxDistFieldName.empty(); }
+    bool readsReadingDescriptor() const { return !genericReadDescName.empty() || !maxDistFieldName.empty() || !intensity.descName.empty(); }
+    const std::string& intensityDescriptorName() const { return intensity.descName; } // IntensityPointToPlaneErrorMinimizer.descName, or empty
     const std::string& maxDistField() const { return maxDistFieldName; } // KDTreeVarDistMatcher.maxDistField, or empty (KDTreeMatcher)
   private:
     bool planar = false;                               // 2-D mapping (is3D == false): icpmi_config::is_2d

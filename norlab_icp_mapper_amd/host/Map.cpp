@@ -259,7 +259,8 @@ bool Map::residentPlan(const DataPoints& input, const DataPointsFilters& postFil
     // (planar maps too, r3: the clouds keep z == 0 in the 4 x N layout and a planar pose maps z = 0 to z = 0 exactly, so the chain's
     //  kernels see what the host-pointer operators see -- spherical coordinates with elevation asin(0 / r) = 0, the reference's
     //  is3D == false branch of DynamicPointsMapperModule.cpp:156-172; normals through the planar eigen-solve, icpmi_config::is_2d)
-    if (!enabled || mapperModuleVec.empty() || icp.hasReferenceFilters() || !icp.genericDescriptorName().empty()) return false;
+    // (IntensityPointToPlaneErrorMinimizer likewise: the resident chain does not carry its descriptor, nor the gradients, across an update)
+    if (!enabled || mapperModuleVec.empty() || icp.hasReferenceFilters() || !icp.genericDescriptorName().empty() || !icp.intensityDescriptorName().empty()) return false;
     if (!is3D && !planarCloud(input)) return false;
     prog = ResidentProgram{};
     auto adopt = [&](bool ok, const icpmi_map_op& op, const std::string& name) {

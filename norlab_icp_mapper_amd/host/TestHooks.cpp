@@ -165,6 +165,26 @@ int nim_test_parse_error_minimizer(const char* yaml_icp, int* minimizer, int* fo
     }
 }
 
+// ... and the photometric term of IntensityPointToPlaneErrorMinimizer with it (weight 0, knn 10 and an empty name under every other entry)
+int nim_test_parse_error_minimizer_intensity(const char* yaml_icp, int* minimizer, int* force_4dof, float* weight, int* knn, char* desc_name, int desc_cap,
+                                             char* err, int err_cap)
+{
+    try {
+        icpmi_config cfg;
+        icpmi_config_default(&cfg);
+        float eps = 1e-3f;
+        int model = ICPMI_PLANE_MODEL_GICP;
+        nim::IntensityTerm term;
+        nim::parseErrorMinimizer(nim::yaml::Load(yaml_icp)["errorMinimizer"], cfg, eps, model, &term);
+        *minimizer = cfg.minimizer; *force_4dof = cfg.force_4dof; *weight = term.weight; *knn = term.knn;
+        if (desc_name && desc_cap > 0) { std::strncpy(desc_name, term.descName.c_str(), (size_t)desc_cap - 1); desc_name[desc_cap - 1] = 0; }
+        return 0;
+    } catch (const std::exception& e) {
+        if (err && err_cap > 0) { std::strncpy(err, e.what(), (size_t)err_cap - 1); err[err_cap - 1] = 0; }
+        return 1;
+    }
+}
+
 // ... and the pair model of ICPMI_MIN_PLANE_TO_PLANE with it (ICPMI_PLANE_MODEL_*: SymmetricPointToPlaneErrorMinimizer names the symmetric one)
 int nim_test_parse_error_minimizer_model(const char* yaml_icp, int* minimizer, int* force_4dof, float* plane_epsilon, int* plane_model,
                                          char* err, int err_cap)
@@ -469,6 +489,45 @@ int nim_test_mapper_sweep(const char* config, int n_scans, const float* const* s
             res_out[i] = reg.stats;
             std::memcpy(pose_out16 + 16 * i, mapper.getPose().data(), sizeof(float) * 16);
             map_sizes[i] = (int64_t)mapper.getMap().getNbPoints();
+        }
+        return 0;
+    } catch (const nim::ConvergenceError& e) {
+        return fail(e, 2);
+    } catch (const nim::InvalidField& e) {
+        return fail(e, 3);
+    } catch (const nim::InvalidParameter& e) {
+        return fail(e, 4);
+    } catch (const std::exception& e) {
+        return fail(e, 1);
+    }
+}
+
+// Mapper::processInput scan by scan on an offline mapper built from `config`: scan i is scans4[i] (ns[i] points, sensor frame) with the 1-row
+// descriptor `desc_name` = descs[i], under the prior poses16 (column-major, 16 floats per scan).  Back per scan: the mapper's pose, the size
+// of its map after the call and whether that map carries the descriptor.  Returns 0; 2 ConvergenceError, 3 InvalidField, 4 InvalidParameter,
+// 1 any other exception, the text in err.
+int nim_test_mapper_descriptor_scans(const char* config, int n_scans, const float* const* scans4, const int64_t* ns, const char* desc_name,
+                                     const float* const* descs, const float* poses16, const int64_t* stamps_ns, float* pose_out16, int64_t* map_sizes,
+                                     int* map_has_desc, char* err, int err_cap)
+{
+    const auto fail = [&](const std::exception& e, int rc) {
+        if (err && err_cap > 0) { std::strncpy(err, e.what(), (size_t)err_cap - 1); err[err_cap - 1] = 0; }
+        return rc;
+    };
+    try {
+        nim::Mapper mapper(config, true, false, true, false);
+        for (int i = 0; i < n_scans; ++i) {
+            const size_t n = (size_t)ns[i];
+            nim::DataPoints cloud(n);
+            std::memcpy(cloud.features.data(), scans4[i], sizeof(float) * 4 * n);
+            cloud.addDescriptor(desc_name, 1, std::vector<float>(descs[i], descs[i] + n));
+            nim::Mat4 prior;
+            std::memcpy(prior.data(), poses16 + 16 * i, sizeof(float) * 16);
+            mapper.processInput(cloud, prior, nim::TimePoint{std::chrono::nanoseconds(stamps_ns[i])});
+            std::memcpy(pose_out16 + 16 * i, mapper.getPose().data(), sizeof(float) * 16);
+            const nim::DataPoints map = mapper.getMap();
+            map_sizes[i] = (int64_t)map.getNbPoints();
+            map_has_desc[i] = map.descriptorExists(desc_name) ? 1 : 0;
         }
         return 0;
     } catch (const nim::ConvergenceError& e) {

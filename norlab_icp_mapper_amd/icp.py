@@ -63,7 +63,9 @@ _MINIMIZERS = {
     "PointToPlaneErrorMinimizer": _capi.MIN_POINT_TO_PLANE,
     "PlaneToPlaneErrorMinimizer": _capi.MIN_PLANE_TO_PLANE,
     "SymmetricPointToPlaneErrorMinimizer": _capi.MIN_PLANE_TO_PLANE,  # (the same path under its other pair model: _PLANE_MODELS)
+    "IntensityPointToPlaneErrorMinimizer": _capi.MIN_POINT_TO_PLANE,  # (point-to-plane with the photometric term: icpmi_set_intensity_weight)
 }
+INTENSITY_LAMBDA_DEFAULT, INTENSITY_KNN_DEFAULT, INTENSITY_DESC_DEFAULT = 0.968, 10, "intensity"
 PLANE_EPSILON_DEFAULT = 1e-3
 _PLANE_MODELS = {"gicp": _capi.PLANE_MODEL_GICP, "symmetric": _capi.PLANE_MODEL_SYMMETRIC}
 _PLANE_MODEL_NAMES = {v: k for k, v in _PLANE_MODELS.items()}
@@ -75,6 +77,19 @@ def _check_plane_epsilon(eps):
         raise InvalidParameter("PlaneToPlaneErrorMinimizer: epsilon must be finite and in (0, 1]")
     return eps
 
+
+
+def _check_intensity_weight(w):
+    w = float(w)
+    if not (math.isfinite(w) and 0.0 <= w < 1.0):
+        raise InvalidParameter("IntensityPointToPlaneErrorMinimizer: the intensity weight (1 - lambdaGeometric) must be finite and in [0, 1)")
+    return w
+
+
+def _check_intensity_knn(k):
+    if int(k) != k or not 1 <= int(k) <= 31:
+        raise InvalidParameter("IntensityPointToPlaneErrorMinimizer: gradientKnn must be an integer in [1, 31]")
+    return int(k)
 
 
 def _check_plane_model(model):
@@ -242,6 +257,18 @@ def config_from_yaml_chain(chain, **engine):
             if key != "force4DOF":
                 raise InvalidParameter(f"{name}: unknown parameter {key}")
         plane_model = "symmetric"
+    intensity = None
+    if name == "IntensityPointToPlaneErrorMinimizer":
+        # point-to-plane with a photometric term from one scalar descriptor of both clouds (not libpointmatcher's; include/icpmi.h:
+        # icpmi_set_intensity_weight): lambdaGeometric in (0, 1], descName the descriptor, gradientKnn the neighbours of a map-side gradient
+        for key in p:
+            if key not in ("lambdaGeometric", "descName", "gradientKnn", "force4DOF"):
+                raise InvalidParameter(f"{name}: unknown parameter {key}")
+        lam = float(p.get("lambdaGeometric", INTENSITY_LAMBDA_DEFAULT))
+        if not (math.isfinite(lam) and 0.0 < lam <= 1.0):
+            raise InvalidParameter(f"{name}: lambdaGeometric must be finite and in (0, 1]")
+        intensity = (_check_intensity_weight(1.0 - lam), _check_intensity_knn(p.get("gradientKnn", INTENSITY_KNN_DEFAULT)),
+                     str(p.get("descName", INTENSITY_DESC_DEFAULT)))
     if name not in _MINIMIZERS:
         raise InvalidParameter(f"unknown error minimizer {name}")
     if name == "PointToPlaneErrorMinimizer":
@@ -256,7 +283,7 @@ def config_from_yaml_chain(chain, **engine):
             raise InvalidParameter(f"{name}: degeneracyThreshold and force2D exclude each other")
         kw["degeneracy_threshold"] = thr if action == "constrain" else -thr
     kw["minimizer"] = _MINIMIZERS[name]
-    kw["force_4dof"] = 1 if (name in ("PointToPlaneErrorMinimizer", "PlaneToPlaneErrorMinimizer", "SymmetricPointToPlaneErrorMinimizer") and int(p.get("force4DOF", 0))) else 0
+    kw["force_4dof"] = 1 if (name in ("PointToPlaneErrorMinimizer", "PlaneToPlaneErrorMinimizer", "SymmetricPointToPlaneErrorMinimizer", "IntensityPointToPlaneErrorMinimizer") and int(p.get("force4DOF", 0))) else 0
     kw["force_2d"] = 1 if (name == "PointToPlaneErrorMinimizer" and int(p.get("force2D", 0))) else 0
     if kw["force_4dof"] and kw["force_2d"]:
         raise InvalidParameter("PointToPlaneErrorMinimizer: force2D and force4DOF exclude each other")
@@ -287,6 +314,9 @@ def config_from_yaml_chain(chain, **engine):
         cfg.plane_epsilon = plane_epsilon  # (likewise: icpmi_config has no word left; ICPSequence hands it to icpmi_set_plane_epsilon)
     if plane_model is not None:
         cfg.plane_model = plane_model  # (likewise: ICPSequence hands it to icpmi_set_plane_pair_model)
+    if intensity is not None:
+        # (likewise: ICPSequence hands the weight to icpmi_set_intensity_weight; the descriptor's name and the knn are the host's business)
+        cfg.intensity_weight, cfg.intensity_knn, cfg.intensity_desc_name = intensity
     return cfg
 
 
@@ -473,9 +503,11 @@ class _ErrorMinimizerView:
 class ICPSequence:
     """``PM::ICPSequence`` backed by one icpmi handle (one GPU, one stream)."""
 
-    def __init__(self, cfg=None, plane_epsilon=None, plane_model=None, **kw):
+    def __init__(self, cfg=None, plane_epsilon=None, plane_model=None, intensity_weight=None, intensity_knn=None, **kw):
         """plane_epsilon: epsilon of PlaneToPlaneErrorMinimizer (icpmi_set_plane_epsilon; default: the chain's, else 1e-3)
-        plane_model: "gicp" | "symmetric", the pair model of minimizer 3 (icpmi_set_plane_pair_model; default: the chain's, else "gicp")"""
+        plane_model: "gicp" | "symmetric", the pair model of minimizer 3 (icpmi_set_plane_pair_model; default: the chain's, else "gicp")
+        intensity_weight: 1 - lambdaGeometric of the photometric term on minimizer 2 (icpmi_set_intensity_weight; default: the chain's, else 0 = off)
+        intensity_knn: neighbours of a map-side intensity gradient, setMapIntensity's default (default: the chain's, else 10)"""
         self._lib = _capi.load()
         self.cfg = cfg if cfg is not None else default_config(**kw)
         if plane_epsilon is None:
@@ -486,6 +518,13 @@ class ICPSequence:
             plane_model = getattr(self.cfg, "plane_model", None)
         if plane_model is not None:
             _check_plane_model(plane_model)
+        if intensity_weight is None:
+            intensity_weight = getattr(self.cfg, "intensity_weight", None)
+        if intensity_weight is not None:
+            intensity_weight = _check_intensity_weight(intensity_weight)
+        if intensity_knn is None:
+            intensity_knn = getattr(self.cfg, "intensity_knn", INTENSITY_KNN_DEFAULT)
+        self.intensity_knn = _check_intensity_knn(intensity_knn)
         h = C.c_void_p()
         st = self._lib.icpmi_create(C.byref(self.cfg), C.byref(h))
         if st != _capi.ICPMI_OK:
@@ -495,10 +534,13 @@ class ICPSequence:
         self.stats = _capi.Stats()
         self.errorMinimizer = _ErrorMinimizerView(self)
         self._last_n = 0
+        self._intensity_on = False
         if plane_epsilon is not None:
             self.setPlaneEpsilon(plane_epsilon)
         if plane_model is not None:
             self.setPlaneModel(plane_model)
+        if intensity_weight is not None:
+            self.setIntensityWeight(intensity_weight)
 
     @classmethod
     def loadFromYaml(cls, chain, **engine):
@@ -527,6 +569,40 @@ class ICPSequence:
         out = C.c_float(0)
         self._check(self._lib.icpmi_get_plane_epsilon(self._h, C.byref(out)))
         return float(out.value)
+
+    # ---- the photometric term on point-to-plane (IntensityPointToPlaneErrorMinimizer; include/icpmi.h: icpmi_set_intensity_weight) ----
+    def setIntensityWeight(self, w):
+        """icpmi_set_intensity_weight (1 - lambdaGeometric, 0 = off): handle state (setConfig leaves it); the next registration runs with it"""
+        self._check(self._lib.icpmi_set_intensity_weight(self._h, float(w)))
+        self._intensity_on = float(w) > 0.0
+
+    def getIntensityWeight(self):
+        out = C.c_float(0)
+        self._check(self._lib.icpmi_get_intensity_weight(self._h, C.byref(out)))
+        return float(out.value)
+
+    def setMapIntensity(self, intensity, knn=None):
+        """icpmi_set_map_intensity: one intensity per point of the resident map, in the order setMap took them; the gradients (knn nearest other
+        points each, default intensity_knn) are computed on the device.  Every change of the map drops the channel."""
+        row = np.ascontiguousarray(intensity, dtype=np.float32).reshape(-1)
+        st = self._lib.icpmi_set_map_intensity(self._h, row.ctypes.data, row.shape[0], _check_intensity_knn(self.intensity_knn if knn is None else knn))
+        self._check(st)
+
+    def setReadingIntensity(self, intensity):
+        """icpmi_set_reading_intensity: the intensity row of the NEXT reading (one shot, like setReadingScalar)"""
+        row = np.ascontiguousarray(intensity, dtype=np.float32).reshape(-1)
+        self._check(self._lib.icpmi_set_reading_intensity(self._h, row.ctypes.data, row.shape[0]))
+
+    def intensityGradient(self, cloud, normals, intensity, knn=None):
+        """icpmi_intensity_gradient: the (N, 3) tangent-plane intensity gradients of a cloud with normals, as setMapIntensity computes them"""
+        cloud, normals = _f32c(cloud, 4), _f32c(normals, 3)
+        row = np.ascontiguousarray(intensity, dtype=np.float32).reshape(-1)
+        if normals.shape[0] != cloud.shape[0] or row.shape[0] != cloud.shape[0]:
+            raise InvalidParameter("normals / intensity / cloud size mismatch")
+        out = np.zeros((cloud.shape[0], 3), dtype=np.float32)
+        self._check(self._lib.icpmi_intensity_gradient(self._h, cloud.ctypes.data, cloud.shape[0], normals.ctypes.data, row.ctypes.data,
+                                                       _check_intensity_knn(self.intensity_knn if knn is None else knn), out.ctypes.data))
+        return out
 
     def close(self):
         if getattr(self, "_h", None):
@@ -572,7 +648,8 @@ class ICPSequence:
 
     def __call__(self, scan, scan_normals=None, descriptors=None):
         """descriptors: {name: rows} of the reading (rows: (N,) or (rows, N)).  A KDTreeVarDistMatcher chain takes its `maxDistField` row from
-        there (InvalidField when it is missing or has more than one row), unless setReadingMaxDist armed one already."""
+        there (InvalidField when it is missing or has more than one row), unless setReadingMaxDist armed one already; with an intensity
+        weight set, the chain's intensity descriptor (default `intensity`) is armed from there as setReadingIntensity does."""
         scan = _f32c(scan, 4)
         nptr = None
         if scan_normals is not None:
@@ -588,10 +665,14 @@ class ICPSequence:
             if row.ndim != 1:
                 raise InvalidField(f"KDTreeVarDistMatcher: descriptor {field} must have one row, got shape {row.shape}")
             self.setReadingMaxDist(row)
+        if self._intensity_on and descriptors is not None:  # IntensityPointToPlaneErrorMinimizer: the chain's descName row, unless setReadingIntensity armed one
+            field = getattr(self.cfg, "intensity_desc_name", INTENSITY_DESC_DEFAULT)
+            if field in descriptors:
+                self.setReadingIntensity(descriptors[field])
         T = (C.c_float * 16)()
         self._last_n = scan.shape[0]
         st = self._lib.icpmi_register(self._h, scan.ctypes.data, scan.shape[0], nptr, T, C.byref(self.stats))
-        if st == _capi.ERR_INVALID_ARG and self.cfg.var_dist:
+        if st == _capi.ERR_INVALID_ARG and (self.cfg.var_dist or self._intensity_on):  # (a missing descriptor row is upstream's InvalidField)
             msg = self._lib.icpmi_last_error(self._h).decode()
             if msg.startswith("InvalidField"):
                 raise InvalidField(msg)
