@@ -345,6 +345,42 @@ typedef enum {
 icpmi_status icpmi_set_plane_pair_model(icpmi_handle h, int32_t model);
 icpmi_status icpmi_get_plane_pair_model(icpmi_handle h, int32_t* model);
 
+/* VoxelMatcher: voxelised plane-to-plane ICP with no neighbour search (Koide et al., ICRA 2021; one voxel per reading point, the
+ * "DIRECT1" neighbourhood).  Not a libpointmatcher module.  The resident map keeps one record per occupied voxel of its
+ * CENTRED frame (points minus icpmi_get_map_mean): count, mean mu and N = (1/count) sum u u^T over the unit normals u of its points (a zero
+ * or non-finite normal adds nothing).  A reading point p = T_iter x is paired with the voxel it falls into -- one table lookup, no voxel:
+ * no pair -- with q = mu and M = (C_v + C(R n_x))^-1, C_v = I - (1 - eps) N, C(n) and eps as for ICPMI_MIN_PLANE_TO_PLANE; weight 1 per
+ * pair.  The sums, the solve, the checkers and force_4dof are that minimiser's.  One iteration is two launches: no matcher, no selection.
+ *   Keys: per axis i = (int)floorf(x / size) in float32 (correctly rounded division); a point takes part iff its coordinates are finite
+ *   and every |i| < 2^20.  A MAP point that fails makes the build fail with ICPMI_ERR_INVALID_ARG; a reading point that fails has no pair.
+ *   key = (i_x + 2^20) << 42 | (i_y + 2^20) << 21 | (i_z + 2^20).  The lookup is an open-addressing table with linear probing, capacity the
+ *   smallest power of two >= max(2, 2 * voxels), a key's first slot = ((key * 0x9E3779B97F4A7C15 mod 2^64) >> 32) & (capacity - 1).
+ *   Sums are in double in a fixed order and rounded once; no float atomics: two builds of one map give the same bits.
+ * icpmi_set_voxel_matcher: size finite and >= 0 (else ICPMI_ERR_INVALID_ARG and the value stays).  0, the default, is off: no result changes
+ * by a bit and no new kernel runs.  Handle state like the plane epsilon: icpmi_set_config leaves it.  The table is built lazily, by the
+ * first call that needs it after the map or the size changed; a map without normals: ICPMI_ERR_MISSING_NORMALS.
+ * With size > 0 on an ICPMI_MIN_PLANE_TO_PLANE handle with ICPMI_PLANE_MODEL_GICP, icpmi_register, _dev, _fixed_dev and
+ * icpmi_minimize_step_normals run the voxel path (the reading must carry normals: ICPMI_ERR_MISSING_NORMALS); icpmi_config's knn, max_dist
+ * and epsilon are not read by the loop; no pair at all is ICPMI_ERR_NO_POINT_TO_MINIMIZE; the sensor-noise overlap is not computed (-1).
+ * Refused with a message that names the voxel matcher, never served by another path in silence:
+ *   ICPMI_ERR_INVALID_ARG ("InvalidParameter: ..."): every other minimiser, the symmetric pair model, any outlier filter, var_dist, a
+ *     non-zero intensity weight, covariance, degeneracy_threshold, force_2d / is_2d;
+ *   ICPMI_ERR_UNSUPPORTED: icpmi_register_batch_dev, icpmi_register_multistart*, icpmi_register_sweep*, icpmi_sweep_sums, icpmi_minimize_step.
+ * icpmi_residual_error* are unchanged: they score the pose through the nearest-neighbour matcher, as on any plane-to-plane handle.
+ * icpmi_get_voxel_map: the table in ascending key order (builds it if need be).  ijk3 (3 per voxel), mean3 (3, centred frame), moments6
+ *   (xx xy xz yy yz zz) and count have capacity cap voxels and may each be NULL; *n_voxels = the count; cap below it:
+ *   ICPMI_ERR_INVALID_ARG with *n_voxels set.
+ * icpmi_voxel_lookup (test seam and inspection): for n centred-frame queries (x, y, z, w) the index into that order, -1 for no voxel. */
+icpmi_status icpmi_set_voxel_matcher(icpmi_handle h, float size);
+icpmi_status icpmi_get_voxel_matcher(icpmi_handle h, float* size);
+icpmi_status icpmi_get_voxel_map(icpmi_handle h, int64_t cap, int32_t* ijk3, float* mean3, float* moments6, int32_t* count, int64_t* n_voxels);
+icpmi_status icpmi_voxel_lookup(icpmi_handle h, const float* q4_centred, int64_t n, int32_t* voxel);
+/* diagnostics (scripts/voxel_bench.py): rebuilds the table and reports the milliseconds of its sort, reduce and fill stages */
+icpmi_status icpmi_debug_voxel_build_times(icpmi_handle h, float times_ms3[3]);
+/* ... and looks n centred-frame queries up `reps` times through the table (ms2[0]: mean milliseconds of one launch) and by a binary search over
+ * the sorted keys (ms2[1]); *mismatch (may be NULL) = queries the two answer differently (0) */
+icpmi_status icpmi_debug_voxel_lookup_times(icpmi_handle h, const float* q4_centred, int64_t n, int32_t reps, float ms2[2], int64_t* mismatch);
+
 /* ---- IntensityPointToPlaneErrorMinimizer: a photometric term on ICPMI_MIN_POINT_TO_PLANE.  Not libpointmatcher's: the joint
  * geometric + photometric objective of Park, Zhou, Koltun, "Colored Point Cloud Registration Revisited" (ICCV 2017), one scalar channel.
  *

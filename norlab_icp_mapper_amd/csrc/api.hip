@@ -679,6 +679,35 @@ static icpmi_status intensity_setup(icpmi_ctx* h, const char* who, int64_t n, in
     return ICPMI_OK;
 }
 
+// VoxelMatcher (icpmi_set_voxel_matcher > 0) is served on plane-to-plane chains with the GICP pair model and no outlier
+// filter, by the entry points that carry the reading's normals and run ONE reading.  Everything else says so and names the matcher; nothing
+// is served by the nearest-neighbour path in silence.  served = this entry point can run it
+static icpmi_status voxel_check(icpmi_ctx* h, const char* who, bool served)
+{
+    if (!(h->voxel_size > 0.f)) return ICPMI_OK;
+    if (!served) {
+        h->last_error = std::string(who) + ": the voxel matcher (icpmi_set_voxel_matcher > 0) is served by icpmi_register, icpmi_register_dev, "
+                        "icpmi_register_fixed_dev and icpmi_minimize_step_normals only; set the size to 0 for this entry point";
+        return ICPMI_ERR_UNSUPPORTED;
+    }
+    const icpmi_config& cfg = h->cfg;
+    const char* why = nullptr;
+    if (cfg.minimizer != ICPMI_MIN_PLANE_TO_PLANE) why = "is defined on PlaneToPlaneErrorMinimizer only";
+    else if (h->plane_model != ICPMI_PLANE_MODEL_GICP) why = "is not served with the symmetric pair model (SymmetricPointToPlaneErrorMinimizer)";
+    else if (cfg.n_outlier > 0) why = "is not served with outlier filters (a pair is a point and the voxel it falls into: there is no match distance to filter on)";
+    else if (cfg.var_dist) why = "is not served with KDTreeVarDistMatcher (var_dist)";
+    else if (h->intensity_w > 0.f) why = "is not served with the intensity term (icpmi_set_intensity_weight > 0)";
+    // (belt and braces: icpmi_set_config refuses the three below for ICPMI_MIN_PLANE_TO_PLANE already, and any other minimiser is answered above)
+    else if (cfg.covariance) why = "is not served with covariance = 1";
+    else if (cfg.degeneracy_threshold != 0.f) why = "is not served with a degeneracy_threshold";
+    else if (cfg.force_2d || cfg.is_2d) why = "is not served with force_2d / is_2d";
+    if (why) {
+        h->last_error = std::string("InvalidParameter: ") + who + ": the voxel matcher (icpmi_set_voxel_matcher > 0) " + why;
+        return ICPMI_ERR_INVALID_ARG;
+    }
+    return ICPMI_OK;
+}
+
 static icpmi_status register_impl(icpmi_handle h, const float* d_scan4, int64_t n, const float* d_n3, int fixed_iters,
                                   float T_out[16], icpmi_stats* stats)
 {
@@ -692,6 +721,7 @@ static icpmi_status register_impl(icpmi_handle h, const float* d_scan4, int64_t 
     if (stats) { memset(stats, 0, sizeof *stats); stats->sensor_noise_overlap = -1.f; } // -1 = "not computed" on EVERY path
     identity16(T_out);
     if (n < 0 || (n > 0 && !d_scan4)) { h->last_error = "register: bad arguments"; return ICPMI_ERR_INVALID_ARG; }
+    { const icpmi_status vs = voxel_check(h, "register", true); if (vs != ICPMI_OK) return vs; }
     if (h->m <= 0) return ICPMI_OK; // "Ignoring attempt to perform ICP with an empty map" -> identity
     if (n > 0x7fffffff / ICPMI_MAX_K) { h->last_error = "register: too many points"; return ICPMI_ERR_UNSUPPORTED; }
     if (h->cfg.minimizer == ICPMI_MIN_POINT_TO_PLANE && !h->has_normals) {
@@ -712,7 +742,10 @@ static icpmi_status register_impl(icpmi_handle h, const float* d_scan4, int64_t 
     // sensor-noise overlap (icpmi_set_reading_sensor_noise): the noise row is one shot -- this registration consumes it
     // (PointToPointErrorMinimizer::getOverlap() needs `simpleSensorNoise` alone; only the point-to-plane variant also reads the reading's
     // `normals` -- ADVICE r3)
-    const bool sn = have_noise_n == n && !lc.ext && !lc.is_2d &&
+    const bool voxel = voxel_path(h); // (voxel_check passed: the chain is one the voxel matcher serves)
+    if (voxel) { const icpmi_status ts = voxel_ensure_table(h, nullptr); if (ts != ICPMI_OK) return ts; } // (before the loop: it allocates and waits)
+    // (a voxel loop leaves no matched pairs behind for the overlap pass: the row is consumed, the overlap stays "not computed")
+    const bool sn = !voxel && have_noise_n == n && !lc.ext && !lc.is_2d &&
                     (lc.minimizer == ICPMI_MIN_POINT_TO_POINT || (lc.minimizer == ICPMI_MIN_POINT_TO_PLANE && d_n3));
     lc.sensor_noise = sn ? 1 : 0;
     if (sn && d_n3) lc.has_read_normals = 1;
@@ -823,6 +856,7 @@ icpmi_status icpmi_register_batch_dev(icpmi_handle h, int32_t batch, const float
     }
     for (int b = 0; b < batch; ++b)
         if (n[b] < 0 || (n[b] > 0 && !d_scans4[b])) { h->last_error = "register_batch: bad arguments"; return ICPMI_ERR_INVALID_ARG; }
+    { const icpmi_status vs = voxel_check(h, "register_batch", false); if (vs != ICPMI_OK) return vs; }
     { const icpmi_status ps = reject_plane_to_plane(h, "register_batch"); if (ps != ICPMI_OK) return ps; }
     { const icpmi_status is = reject_intensity(h, "register_batch"); if (is != ICPMI_OK) return is; }
     // The one-launch-per-iteration path serves the chains whose kernels take a batch: k = 1 on the grid pyramid without a
@@ -1065,6 +1099,7 @@ icpmi_status icpmi_register_multistart_dev(icpmi_handle h, const float* d_scan4,
     if (n_starts < 1 || n_starts > ICPMI_MAX_BATCH || n < 0 || (n > 0 && !d_scan4) || !priors || !T_out || fixed_iterations < 0) {
         h->last_error = "register_multistart: bad arguments (1 <= n_starts <= 16)"; return ICPMI_ERR_INVALID_ARG;
     }
+    { const icpmi_status vs = voxel_check(h, "register_multistart", false); if (vs != ICPMI_OK) return vs; }
     { const icpmi_status ps = reject_plane_to_plane(h, "register_multistart"); if (ps != ICPMI_OK) return ps; }
     { const icpmi_status is = reject_intensity(h, "register_multistart"); if (is != ICPMI_OK) return is; }
     h->scan_map_n = 0; // (the slices below reuse the stage of icpmi_register_prior: nothing is left staged)
@@ -1221,6 +1256,7 @@ static icpmi_status minimize_step_impl(icpmi_handle h, const float* reading4, in
     const int64_t have_int_n = h->read_int_n; // (the one-shot intensity row belongs to THIS call whatever becomes of it)
     h->read_int_n = 0;
     if (n <= 0 || !reading4) { h->last_error = "minimize_step: bad arguments"; return ICPMI_ERR_INVALID_ARG; }
+    { const icpmi_status vs = voxel_check(h, "minimize_step", true); if (vs != ICPMI_OK) return vs; }
     { const icpmi_status es = check_ext_filters(h); if (es != ICPMI_OK) return es; }
     { const icpmi_status rs = reject_reading_source(h, "minimize_step"); if (rs != ICPMI_OK) return rs; }
     { const icpmi_status rs = reject_var_dist(h, "minimize_step"); if (rs != ICPMI_OK) return rs; }
@@ -1234,6 +1270,7 @@ static icpmi_status minimize_step_impl(icpmi_handle h, const float* reading4, in
         return ICPMI_ERR_MISSING_NORMALS;
     }
     if (stats) { memset(stats, 0, sizeof *stats); stats->sensor_noise_overlap = -1.f; }
+    if (voxel_path(h)) { const icpmi_status ts = voxel_ensure_table(h, nullptr); if (ts != ICPMI_OK) return ts; }
     if (h->d_reading.ensure(h, (size_t)n + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
     HIP_TRY(h, hipMemcpyAsync(h->d_reading, reading4, (size_t)n * sizeof(float4), hipMemcpyHostToDevice, h->stream));
     // d_reading has new contents: a tile-sorted copy of what was there before (an icpmi_knn with the same n) must not be searched in
@@ -1259,6 +1296,7 @@ icpmi_status icpmi_minimize_step(icpmi_handle h, const float* reading4, int64_t 
                                  double sums[32], icpmi_stats* stats)
 {
     CHECK_H(h);
+    { const icpmi_status vs = voxel_check(h, "minimize_step", false); if (vs != ICPMI_OK) return vs; }
     { const icpmi_status ps = reject_plane_to_plane(h, "minimize_step"); if (ps != ICPMI_OK) return ps; }
     return minimize_step_impl(h, reading4, n, nullptr, T_iter, T_step, sums, stats);
 }
@@ -1302,6 +1340,53 @@ icpmi_status icpmi_get_plane_pair_model(icpmi_handle h, int32_t* model)
     if (!model) { h->last_error = "get_plane_pair_model: model is null"; return ICPMI_ERR_INVALID_ARG; }
     *model = h->plane_model;
     return ICPMI_OK;
+}
+
+icpmi_status icpmi_set_voxel_matcher(icpmi_handle h, float size)
+{
+    CHECK_H(h);
+    if (!std::isfinite(size) || size < 0.f) { h->last_error = "set_voxel_matcher: the voxel size must be finite and >= 0 (0: off)"; return ICPMI_ERR_INVALID_ARG; }
+    h->voxel_size = size; // (no graph to drop: loop_sig hashes the size and the table's generation; the table follows lazily)
+    return ICPMI_OK;
+}
+
+icpmi_status icpmi_get_voxel_matcher(icpmi_handle h, float* size)
+{
+    CHECK_H(h);
+    if (!size) { h->last_error = "get_voxel_matcher: size is null"; return ICPMI_ERR_INVALID_ARG; }
+    *size = h->voxel_size;
+    return ICPMI_OK;
+}
+
+icpmi_status icpmi_get_voxel_map(icpmi_handle h, int64_t cap, int32_t* ijk3, float* mean3, float* moments6, int32_t* count, int64_t* n_voxels)
+{
+    CHECK_H(h);
+    if (n_voxels) *n_voxels = 0;
+    if (cap < 0) { h->last_error = "get_voxel_map: bad arguments"; return ICPMI_ERR_INVALID_ARG; }
+    return voxel_get_map(h, cap, ijk3, mean3, moments6, count, n_voxels);
+}
+
+icpmi_status icpmi_voxel_lookup(icpmi_handle h, const float* q4_centred, int64_t n, int32_t* voxel)
+{
+    CHECK_H(h);
+    if (n < 0 || (n > 0 && (!q4_centred || !voxel))) { h->last_error = "voxel_lookup: bad arguments"; return ICPMI_ERR_INVALID_ARG; }
+    return voxel_lookup(h, q4_centred, n, voxel);
+}
+
+// test seam of scripts/voxel_bench.py: rebuilds the table and reports what its three stages took (sort, reduce, fill; milliseconds by HIP events)
+icpmi_status icpmi_debug_voxel_build_times(icpmi_handle h, float times_ms3[3])
+{
+    CHECK_H(h);
+    if (!times_ms3) { h->last_error = "debug_voxel_build_times: times is null"; return ICPMI_ERR_INVALID_ARG; }
+    return voxel_ensure_table(h, times_ms3);
+}
+
+// ... and what one lookup launch of n queries takes through the table (ms2[0]) and by binary search over the sorted keys (ms2[1])
+icpmi_status icpmi_debug_voxel_lookup_times(icpmi_handle h, const float* q4_centred, int64_t n, int32_t reps, float ms2[2], int64_t* mismatch)
+{
+    CHECK_H(h);
+    if (!q4_centred || n < 1 || reps < 1 || !ms2) { h->last_error = "debug_voxel_lookup_times: bad arguments"; return ICPMI_ERR_INVALID_ARG; }
+    return voxel_lookup_times(h, q4_centred, n, reps, ms2, mismatch);
 }
 
 icpmi_status icpmi_set_intensity_weight(icpmi_handle h, float w)
@@ -1834,6 +1919,7 @@ static icpmi_status sweep_impl(icpmi_handle h, const char* who, const float* d_s
     }
     { const icpmi_status os = sweep_check_options(opts, h->last_error); if (os != ICPMI_OK) return os; }
     { const icpmi_status is = reject_intensity(h, who); if (is != ICPMI_OK) return is; }
+    { const icpmi_status vs = voxel_check(h, who, false); if (vs != ICPMI_OK) return vs; }
     const icpmi_config& cfg = h->cfg;
     if (cfg.force_4dof || cfg.force_2d || cfg.is_2d || cfg.covariance || cfg.degeneracy_threshold != 0.f) {
         h->last_error = std::string(who) + ": not served with force_4dof, force_2d, is_2d, covariance or a degeneracy_threshold"; return ICPMI_ERR_INVALID_ARG;

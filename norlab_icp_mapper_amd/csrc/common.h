@@ -816,6 +816,14 @@ struct icpmi_ctx {
     // gi_version with gi_m points -- every map_build moves on and thereby drops the channel
     float intensity_w = 0.f;
     DevArr<float4> d_map_gi; uint64_t gi_version = 0; int64_t gi_m = 0;
+    // icpmi_set_voxel_matcher: the voxel size (0: off); handle state like plane_eps.  The table of the resident map (voxel.hip): the occupied
+    // voxels' keys and records in ascending key order and the open-addressing table (64-byte slots, vox_mask + 1 of them) the kernels probe.
+    // Built lazily by voxel_ensure_table; current while the map (map_version, map_epoch) and the size are those it was built for.  vox_gen
+    // counts the builds: loop_sig hashes it with the size, neither is part of the LoopCfg.
+    float voxel_size = 0.f;
+    DevArr<unsigned long long> d_vox_keys; DevArr<float4> d_vox_rec; DevArr<uint4> d_vox_tab;
+    int64_t vox_nv = 0; unsigned vox_mask = 0; bool vox_ready = false;
+    uint64_t vox_map_version = 0, vox_epoch = 0, vox_gen = 0; float vox_built_size = 0.f;
     DevArr<IcpState> d_state;          // ICPMI_MAX_BATCH states (a single registration uses the first)
     IcpState* h_state = nullptr;                               // pinned mirror (ICPMI_MAX_BATCH)
     bool zero_pending = false;                                 // d_state / d_selhist still to be cleared: on the stream the handle really uses, at its first call (zero_state_if_pending)
@@ -1380,6 +1388,18 @@ icpmi_status loop_run_batch(icpmi_ctx* c, int batch, const float* const* d_scans
                             float* T_out, icpmi_stats* stats, icpmi_status* status);
 icpmi_status loop_single_step(icpmi_ctx* c, int64_t n, const LoopCfg& lc, const float* T_iter_host, float T_step[16],
                               double sums[32], icpmi_stats* stats);
+// VoxelMatcher (voxel.hip).  A handle runs it when the size is set and its minimiser is plane-to-plane with the GICP pair
+// model; api.hip refuses every other combination before a loop starts
+static inline bool voxel_path(const icpmi_ctx* c)
+{
+    return c->voxel_size > 0.f && c->cfg.minimizer == ICPMI_MIN_PLANE_TO_PLANE && c->plane_model == ICPMI_PLANE_MODEL_GICP;
+}
+bool voxel_table_current(const icpmi_ctx* c);
+icpmi_status voxel_ensure_table(icpmi_ctx* c, float* times_ms); // times_ms (3 floats: sort, reduce, fill) forces a rebuild
+void voxel_enqueue_pairs(icpmi_ctx* c, int64_t n, int nb, float eps); // one launch on c->stream: the sums of c->d_reading under d_state->T_iter
+icpmi_status voxel_get_map(icpmi_ctx* c, int64_t cap, int32_t* ijk3, float* mean3, float* moments6, int32_t* count, int64_t* n_voxels);
+icpmi_status voxel_lookup(icpmi_ctx* c, const float* q4_centred, int64_t n, int32_t* voxel);
+icpmi_status voxel_lookup_times(icpmi_ctx* c, const float* q4_centred, int64_t n, int reps, float ms[2], int64_t* mismatch); // table against binary search
 // the reading's normals (host, 3 per point) into c->d_read_normals, padded as a registration's head pads them
 icpmi_status loop_upload_read_normals(icpmi_ctx* c, const float* normals3, int64_t n);
 // getResidualError() of the centred reading in c->d_reading under the centred-frame pose T (host, column-major); kind 1 / 2

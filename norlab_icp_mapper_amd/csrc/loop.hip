@@ -932,7 +932,10 @@ icpmi_status loop_prepare_reading(icpmi_ctx* c, const float4* d_scan, int64_t n,
 {
     if (c->d_reading.ensure(c, (size_t)n + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
     const int blocks = (int)((n + 255) / 256);
-    const bool fused = head_done && c->cfg.knn <= 8 && n > 0;
+    // (the head of a VoxelMatcher registration: nothing on that path reads the tile-sorted copy, so the reading is centred and left in the
+    // caller's order -- centre_kernel below, the loop state by enqueue_registration_head)
+    const bool no_sort = head_done && voxel_path(c);
+    const bool fused = head_done && c->cfg.knn <= 8 && n > 0 && !no_sort;
     if (head_done) *head_done = fused;
     if (blocks && !fused) {
         BatchSrc src; memset(&src, 0, sizeof src); src.p[0] = d_scan;
@@ -951,7 +954,7 @@ icpmi_status loop_prepare_reading(icpmi_ctx* c, const float4* d_scan, int64_t n,
         h.selhist = c->d_selhist;
         return sort_queries_batch(c, c->d_reading, batch_of_one(n), &h);
     }
-    if (c->cfg.knn <= 8 && n > 0) return sort_queries(c, c->d_reading, n);
+    if (c->cfg.knn <= 8 && n > 0 && !no_sort) return sort_queries(c, c->d_reading, n);
     return ICPMI_OK;
 }
 
@@ -1052,6 +1055,15 @@ static void enqueue_accumulate_solve(icpmi_ctx* c, int64_t n, const LoopCfg& lc,
                            publish ? c->d_progress : (unsigned*)nullptr, ba.nscan == 1 ? c->d_state_mirror : (IcpState*)nullptr);
 }
 
+// the iteration of a VoxelMatcher handle (voxel_path; a single registration): voxel_pairs_kernel fills the point-to-plane slots of the
+// accumulators, the solve reads them as it reads plane-to-plane's (lc carries epsilon in degen_thr: common.h, plane_to_plane_eps)
+static void enqueue_voxel_solve(icpmi_ctx* c, int64_t n, const LoopCfg& lc, float* d_Tstep, double* d_sums, bool publish)
+{
+    voxel_enqueue_pairs(c, n, acc_blocks(n), plane_to_plane_eps(lc));
+    hipLaunchKernelGGL(solve_kernel<false>, dim3(1), dim3(256), 0, c->stream, c->d_state, c->d_selhist, 1, lc, d_Tstep, d_sums,
+                       publish ? c->d_progress : (unsigned*)nullptr, c->d_state_mirror);
+}
+
 // what every launch of a registration's loop asks of the matcher (ba: its readings; NnRequest::iter is set iteration by iteration).  Built
 // once the loop's buffers have their final size.
 NnRequest loop_request(icpmi_ctx* c, const LoopCfg& lc, const BatchArgs& ba, const float* d_r2row)
@@ -1098,6 +1110,12 @@ static icpmi_status enqueue_iteration(icpmi_ctx* c, int64_t n, const LoopCfg& lc
                                       bool publish = true)
 {
     if (nn0) HIP_TRY(c, hipEventRecord(nn0, c->stream));
+    if (voxel_path(c)) { // VoxelMatcher (voxel.hip): no matcher, no selection -- the voxel pair sums, then the solve every chain ends in
+        enqueue_voxel_solve(c, n, lc, nullptr, c->d_keep_sums.get(), publish);
+        if (nn1) HIP_TRY(c, hipEventRecord(nn1, c->stream));
+        HIP_TRY(c, hipGetLastError());
+        return ICPMI_OK;
+    }
     { const icpmi_status s = enqueue_match_select(c, n, lc, req, nn, nn1); if (s != ICPMI_OK) return s; }
     // (icpmi_debug_keep_sums: the sums of every counted iteration of a SINGLE registration; a batch's solves would all write the one block)
     enqueue_accumulate_solve(c, n, lc, req.batch, *nn, nullptr, req.batch.nscan > 1 ? nullptr : c->d_keep_sums.get(), publish);
@@ -1193,6 +1211,12 @@ static uint64_t loop_sig(const icpmi_ctx* c, const LoopCfg& lc, const NnRequest&
     sig = fnv(ptrs, sizeof ptrs, sig);
     sig = fnv(&c->grid, sizeof c->grid, sig);
     sig = fnv(&c->map_epoch, sizeof c->map_epoch, sig);
+    if (voxel_path(c)) { // (the voxel size and the table are arguments of voxel_pairs_kernel alone, not part of the LoopCfg)
+        const void* tab = c->d_vox_tab.get();
+        sig = fnv(&c->voxel_size, sizeof c->voxel_size, sig);
+        sig = fnv(&c->vox_gen, sizeof c->vox_gen, sig);
+        sig = fnv(&tab, sizeof tab, sig);
+    }
     return fnv(&n, sizeof n, sig);
 }
 
@@ -1217,7 +1241,9 @@ icpmi_status loop_run(icpmi_ctx* c, const float4* d_scan, const float* d_normals
     if (ensure_loop_buffers(c, n, lc) != ICPMI_OK) return ICPMI_ERR_HIP;
     if (c->d_reading.ensure(c, (size_t)n + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
     if (d_normals3 && c->d_read_normals.ensure(c, (size_t)n + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
-    if (c->cfg.knn <= 8 && sort_queries_reserve(c, n) != ICPMI_OK) return ICPMI_ERR_HIP;
+    const bool voxel = voxel_path(c);
+    if (voxel) { c->qsorted_n = -1; c->qsorted_src = nullptr; } // (d_reading gets new contents and no sorted copy: a stale one must not be searched in its place)
+    else if (c->cfg.knn <= 8 && sort_queries_reserve(c, n) != ICPMI_OK) return ICPMI_ERR_HIP;
     NnRequest req = loop_request(c, lc, batch_of_one(n), d_r2row);
     NnOutcome last; // what the last eagerly enqueued iteration's launch answered (a graph keeps its own: LoopGraph::sorted)
 
@@ -1288,7 +1314,7 @@ icpmi_status loop_run(icpmi_ctx* c, const float4* d_scan, const float* d_normals
         }
         const int head_len = head == &gs.seg[0] ? S : L;
         HIP_TRY(c, hipGraphLaunch(head->exec, c->stream));
-        if (c->cfg.knn <= 8) { c->qsorted_n = n; c->qsorted_src = c->d_reading; } // what the replayed head leaves in d_qsorted
+        if (c->cfg.knn <= 8 && !voxel) { c->qsorted_n = n; c->qsorted_src = c->d_reading; } // what the replayed head leaves in d_qsorted
         int launched = head_len;
         while (launched < lc.max_iter) {
             // (behind a predicted head: no look-ahead -- the next segment goes out only once the head has run and the loop is still going)
@@ -1315,7 +1341,7 @@ icpmi_status loop_run(icpmi_ctx* c, const float4* d_scan, const float* d_normals
             if (s != ICPMI_OK) return s;
         }
         HIP_TRY(c, hipGraphLaunch(gs.fixed.exec, c->stream));
-        if (c->cfg.knn <= 8) { c->qsorted_n = n; c->qsorted_src = c->d_reading; } // what the replayed head leaves in d_qsorted
+        if (c->cfg.knn <= 8 && !voxel) { c->qsorted_n = n; c->qsorted_src = c->d_reading; } // what the replayed head leaves in d_qsorted
     } else {
         const int check_every = (lc.use_diff || lc.use_bound) ? 4 : lc.max_iter;
         if (profile && c->nn_events.size() < (size_t)2 * lc.max_iter) {
@@ -1423,7 +1449,8 @@ icpmi_status loop_run(icpmi_ctx* c, const float4* d_scan, const float* d_normals
     }
     // the last counted iteration's matches stay in the loop's buffers (dead iterations behind the stop early-exit before they write)
     const bool sorted_state = graph ? c->graphs.fixed.sorted : (segmented ? c->graphs.seg[1].sorted : last.out_sorted);
-    if (!c->h_state->error && c->h_state->iter > 0) { c->last_match_n = n; c->last_match_k = lc.k; c->last_match_sorted = sorted_state; }
+    // (a VoxelMatcher loop leaves no matches behind: icpmi_debug_last_matches and the passes over the last pairs have nothing to read)
+    if (!c->h_state->error && c->h_state->iter > 0 && !voxel) { c->last_match_n = n; c->last_match_k = lc.k; c->last_match_sorted = sorted_state; }
     if (lc.sensor_noise && stats && !c->h_state->error && c->h_state->iter > 0) {
         // ErrorMinimizer::getOverlap() with sensor noise: one pass over the last iteration's pairs, still in the loop's buffers
         const icpmi_status os = loop_sensor_noise_overlap(c, n, lc, sorted_state, &stats->sensor_noise_overlap);
@@ -1583,8 +1610,10 @@ icpmi_status loop_single_step(icpmi_ctx* c, int64_t n, const LoopCfg& lc, const 
     req.hist0 = fused_filter_slot(l1) >= 0 ? c->d_selhist.get() : nullptr;
     req.batch = batch_of_one(n);
     NnOutcome nn;
-    const icpmi_status s = enqueue_match_select(c, n, l1, req, &nn);
-    if (s == ICPMI_OK) {
+    const bool voxel = voxel_path(c); // (the table is current: api.hip built it before the reading went up)
+    const icpmi_status s = voxel ? ICPMI_OK : enqueue_match_select(c, n, l1, req, &nn);
+    if (voxel) enqueue_voxel_solve(c, n, l1, d_Tstep, d_sums, true);
+    else if (s == ICPMI_OK) {
         enqueue_accumulate_solve(c, n, l1, req.batch, nn, d_Tstep, d_sums);
         if (l1.degen) (void)loop_degen_report(c, l1); // (an error state leaves the sums of an earlier call: degen_ready stays false below)
     }

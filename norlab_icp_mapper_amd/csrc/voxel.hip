@@ -1,0 +1,485 @@
+// voxel.hip -- VoxelMatcher: voxelised plane-to-plane ICP with no neighbour search (Koide et al., ICRA 2021, with one voxel
+// per reading point: the "DIRECT1" neighbourhood).
+//   the table of the resident map:  key kernel -> radix_sort_pairs (63 bits, stable: a voxel's members stay in ascending resident index)
+//                                   -> head flags + scan -> one wave per voxel sums its run in double -> open-addressing fill (one CAS per voxel)
+//   the iteration's pair sums:      voxel_pairs_kernel: one point load, one probe, the sums of DESIGN.md 4.15 with q = mu and
+//                                   M = (C_v + C(u_p))^-1, into the fixed-point accumulators the existing solve kernel reads
+// No float atomics anywhere: two builds of one map give the same bits, and so do two registrations.
+#include "common.h"
+#include <vector>
+
+namespace {
+
+constexpr unsigned long long VOX_EMPTY = ~0ull;          // (a key has 63 bits: never all ones)
+constexpr float VOX_RANGE = 1048576.f;                   // |index| < 2^20 on every axis
+constexpr int VOX_BIAS = 1 << 20;
+
+// The key of a centred point: per axis i = (int)floorf(x / size) in float32 (the division correctly rounded), biased by 2^20 into 21 bits;
+// x in the top field, so ascending keys are ascending (ix, iy, iz).  false: a coordinate is not finite or an index is out of range.
+__host__ __device__ __forceinline__ bool vox_key(float x, float y, float z, float size, unsigned long long* key)
+{
+    const float fx = floorf(x / size), fy = floorf(y / size), fz = floorf(z / size);
+    if (!(fabsf(fx) < VOX_RANGE && fabsf(fy) < VOX_RANGE && fabsf(fz) < VOX_RANGE)) return false; // (NaN and +-inf fail here too)
+    *key = ((unsigned long long)((int)fx + VOX_BIAS) << 42) | ((unsigned long long)((int)fy + VOX_BIAS) << 21) | (unsigned long long)((int)fz + VOX_BIAS);
+    return true;
+}
+// where a key's probe sequence starts (include/icpmi.h states it: tests build colliding key sets from it)
+__host__ __device__ __forceinline__ unsigned vox_hash(unsigned long long key, unsigned mask)
+{
+    return (unsigned)((key * 0x9E3779B97F4A7C15ull) >> 32) & mask;
+}
+
+// A slot of the table is one 64-byte line, read as four 16-byte words that one probe requests together:
+//   [0] key lo, key hi, ordinal in ascending key order, count     [1] mu.x mu.y mu.z Nxx     [2] Nxy Nxz Nyy Nyz     [3] Nzz 0 0 0
+// The sorted records (what icpmi_get_voxel_map hands out) are words [1..3] with the count in [3].y.
+struct VoxHit { float4 a, b, c; int ordinal; };
+
+__device__ __forceinline__ bool vox_probe(const uint4* __restrict__ tab, unsigned mask, unsigned long long key, VoxHit* hit)
+{
+    unsigned slot = vox_hash(key, mask);
+    // (load factor <= 1/2: an empty slot ends every sequence; the bound is belt and braces against a table that is not what the host says)
+    for (unsigned step = 0; step <= mask; ++step) {
+        const uint4* s = tab + 4 * (size_t)slot;
+        const uint4 w0 = s[0], w1 = s[1], w2 = s[2], w3 = s[3]; // one line, one trip
+        const unsigned long long k = (unsigned long long)w0.x | ((unsigned long long)w0.y << 32);
+        if (k == key) {
+            hit->ordinal = (int)w0.z;
+            hit->a = make_float4(__uint_as_float(w1.x), __uint_as_float(w1.y), __uint_as_float(w1.z), __uint_as_float(w1.w));
+            hit->b = make_float4(__uint_as_float(w2.x), __uint_as_float(w2.y), __uint_as_float(w2.z), __uint_as_float(w2.w));
+            hit->c = make_float4(__uint_as_float(w3.x), 0.f, 0.f, 0.f);
+            return true;
+        }
+        if (k == VOX_EMPTY) return false;
+        slot = (slot + 1) & mask;
+    }
+    return false;
+}
+
+// ---- the table ----------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void vox_key_kernel(const float4* __restrict__ pts, int64_t m, float size, unsigned long long* __restrict__ keys,
+                                                      unsigned* __restrict__ vals, unsigned* __restrict__ bad)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= m) return;
+    const float4 p = pts[i];
+    unsigned long long k = 0;
+    if (!vox_key(p.x, p.y, p.z, size, &k)) atomicOr(bad, 1u);
+    keys[i] = k;
+    vals[i] = (unsigned)i;
+}
+
+__global__ __launch_bounds__(256) void vox_head_kernel(const unsigned long long* __restrict__ skeys, int64_t m, unsigned* __restrict__ head)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < m) head[i] = (i == 0 || skeys[i] != skeys[i - 1]) ? 1u : 0u;
+}
+
+// start of every voxel's run in the sorted order; vstart[nv] = m is written by the thread of the last element
+__global__ __launch_bounds__(256) void vox_start_kernel(const unsigned* __restrict__ head, const unsigned* __restrict__ pos, int64_t m,
+                                                        unsigned* __restrict__ vstart)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= m) return;
+    if (head[i]) vstart[pos[i]] = (unsigned)i;
+    if (i == m - 1) vstart[pos[i] + head[i]] = (unsigned)m;
+}
+
+// a normal scaled to length 1; a zero or non-finite one is "no surface model" (loop.hip's unit_or_zero, kept as a copy: that file's kernels
+// stay instruction for instruction what they were)
+__device__ __forceinline__ float3 vox_unit_or_zero(float x, float y, float z)
+{
+    const float l2 = x * x + y * y + z * z;
+    const bool ok = l2 > 0.f && l2 < INFINITY;
+    const float inv = ok ? 1.f / sqrtf(l2) : 0.f;
+    return ok ? make_float3(x * inv, y * inv, z * inv) : make_float3(0.f, 0.f, 0.f);
+}
+
+// One wave per voxel: lane l adds the members l, l + 64, ... of the run in that order, the 64 lane sums fold in a fixed butterfly; all in
+// double, rounded once.  The order is a function of the run alone -- the same bits on every build.
+__global__ __launch_bounds__(256) void vox_reduce_kernel(const unsigned long long* __restrict__ skeys, const unsigned* __restrict__ svals,
+                                                         const unsigned* __restrict__ vstart, int64_t nv, const float4* __restrict__ pts,
+                                                         const float4* __restrict__ normals, unsigned long long* __restrict__ ukeys,
+                                                         float4* __restrict__ rec)
+{
+    const int64_t v = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (v >= nv) return; // (wave-uniform)
+    const unsigned s0 = vstart[v], s1 = vstart[v + 1];
+    double a[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    for (unsigned i = s0 + lane; i < s1; i += 64) {
+        const unsigned s = svals[i];
+        const float4 p = pts[s];
+        const float3 nr = *reinterpret_cast<const float3*>(normals + s);
+        const float3 u = vox_unit_or_zero(nr.x, nr.y, nr.z);
+        a[0] += (double)p.x; a[1] += (double)p.y; a[2] += (double)p.z;
+        a[3] += (double)u.x * (double)u.x; a[4] += (double)u.x * (double)u.y; a[5] += (double)u.x * (double)u.z;
+        a[6] += (double)u.y * (double)u.y; a[7] += (double)u.y * (double)u.z; a[8] += (double)u.z * (double)u.z;
+    }
+#pragma unroll
+    for (int j = 0; j < 9; ++j)
+#pragma unroll
+        for (int mk = 1; mk < 64; mk <<= 1) a[j] += __shfl_xor(a[j], mk, 64);
+    if (lane == 0) {
+        const unsigned cnt = s1 - s0;
+        const double inv = 1.0 / (double)cnt;
+        ukeys[v] = skeys[s0];
+        rec[3 * v + 0] = make_float4((float)(a[0] * inv), (float)(a[1] * inv), (float)(a[2] * inv), (float)(a[3] * inv));
+        rec[3 * v + 1] = make_float4((float)(a[4] * inv), (float)(a[5] * inv), (float)(a[6] * inv), (float)(a[7] * inv));
+        rec[3 * v + 2] = make_float4((float)(a[8] * inv), __uint_as_float(cnt), 0.f, 0.f);
+    }
+}
+
+// one compare-and-swap per voxel claims a slot; which slot a voxel lands in may depend on arrival order, what a lookup answers may not
+__global__ __launch_bounds__(256) void vox_fill_kernel(const unsigned long long* __restrict__ ukeys, const float4* __restrict__ rec, int64_t nv,
+                                                       uint4* __restrict__ tab, unsigned mask)
+{
+    const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (v >= nv) return;
+    const unsigned long long key = ukeys[v];
+    const float4 r0 = rec[3 * v], r1 = rec[3 * v + 1], r2 = rec[3 * v + 2];
+    unsigned slot = vox_hash(key, mask);
+    for (unsigned step = 0; step <= mask; ++step) {
+        unsigned long long* kw = reinterpret_cast<unsigned long long*>(tab + 4 * (size_t)slot);
+        if (atomicCAS(kw, VOX_EMPTY, key) == VOX_EMPTY) {
+            uint4* s = tab + 4 * (size_t)slot;
+            // (word 0's key half is set by the CAS: the ordinal and the count go in as two 32-bit stores behind it)
+            reinterpret_cast<unsigned*>(s)[2] = (unsigned)v;
+            reinterpret_cast<unsigned*>(s)[3] = __float_as_uint(r2.y);
+            s[1] = make_uint4(__float_as_uint(r0.x), __float_as_uint(r0.y), __float_as_uint(r0.z), __float_as_uint(r0.w));
+            s[2] = make_uint4(__float_as_uint(r1.x), __float_as_uint(r1.y), __float_as_uint(r1.z), __float_as_uint(r1.w));
+            s[3] = make_uint4(__float_as_uint(r2.x), 0u, 0u, 0u);
+            return;
+        }
+        slot = (slot + 1) & mask;
+    }
+}
+
+__global__ __launch_bounds__(256) void vox_lookup_kernel(const float4* __restrict__ q, int64_t n, float size, const uint4* __restrict__ tab, unsigned mask,
+                                                         int* __restrict__ out)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const float4 p = q[i];
+    unsigned long long key = 0;
+    VoxHit hit;
+    out[i] = (vox_key(p.x, p.y, p.z, size, &key) && vox_probe(tab, mask, key, &hit)) ? hit.ordinal : -1;
+}
+
+// the alternative the table was measured against (scripts/voxel_bench.py): a binary search over the sorted unique keys --
+// log2(voxels) dependent loads per query where the table takes one.  Kept as a diagnostic; nothing else runs it.
+__global__ __launch_bounds__(256) void vox_lookup_bsearch_kernel(const float4* __restrict__ q, int64_t n, float size,
+                                                                 const unsigned long long* __restrict__ ukeys, int64_t nv, int* __restrict__ out)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const float4 p = q[i];
+    unsigned long long key = 0;
+    int found = -1;
+    if (vox_key(p.x, p.y, p.z, size, &key)) {
+        int64_t lo = 0, hi = nv; // first position with ukeys[pos] >= key
+        while (lo < hi) {
+            const int64_t mid = (lo + hi) >> 1;
+            if (ukeys[mid] < key) lo = mid + 1; else hi = mid;
+        }
+        if (lo < nv && ukeys[lo] == key) found = (int)lo;
+    }
+    out[i] = found;
+}
+
+// ---- the pair sums ------------------------------------------------------------------------------
+__device__ __forceinline__ float3 vcross3(float3 a, float3 b) { return make_float3(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x); }
+
+// Per reading point: p = T_iter x, the voxel p falls into (none: no pair), q = mu, M = (C_v + C(u_p))^-1 with C_v = I - (1 - eps) N and
+// u_p = unit_or_zero(R n_x); then the sums of DESIGN.md 4.15 with weight 1.  Per-pair terms in float without contraction, sums in double.
+// The reduction (transposed butterfly, LDS across the four waves, two fixed-point limbs per value) is accumulate_kernel's tail, kept here
+// as a COPY: sharing it through common.h would have to leave loop.hip's kernels instruction for instruction the parent's.
+__global__ __launch_bounds__(256) void voxel_pairs_kernel(const float4* __restrict__ reading, const float4* __restrict__ read_normals, int n,
+                                                          IcpState* __restrict__ st, const uint4* __restrict__ tab, unsigned mask, float size, float eps,
+                                                          unsigned* __restrict__ hists)
+{
+    asm volatile("" ::"s"(reading), "s"(read_normals), "s"(n), "s"(st), "s"(tab), "s"(mask), "s"(size), "s"(eps), "s"(hists));
+    unsigned hw = hdr_load(st);
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    const int64_t e0 = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    // the first two points of every lane and their normals are requested with the header: one trip, the probe is the second.  A lane past
+    // the reading loads nothing (an empty reading, or one without a normals array, never has an address formed for it)
+    constexpr int PF = 2;
+    float4 pr[PF]; float3 pn[PF];
+#pragma unroll
+    for (int u = 0; u < PF; ++u) {
+        const int64_t e = e0 + u * stride;
+        const bool in = e < n;
+        pr[u] = in ? ld_stream(reading + e) : make_float4(0.f, 0.f, 0.f, 0.f);
+        pn[u] = (in && read_normals) ? *reinterpret_cast<const float3*>(read_normals + e) : make_float3(0.f, 0.f, 0.f);
+    }
+    asm volatile("" : "+v"(hw));
+    const HdrView hv{hw};
+    const int done = hv.i(ICPMI_HDR_W(done));
+    float T[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) T[i] = hv.f(ICPMI_HDR_W(T_iter) + i);
+    if (done) return;
+    const float g = 1.f - eps;
+    double acc[27];
+#pragma unroll
+    for (int i = 0; i < 27; ++i) acc[i] = 0.0;
+    double cnt = 0.0;
+    auto pair = [&](float4 r, float3 rn) {
+        const float3 p = xf_point(T, r.x, r.y, r.z, r.w);
+        unsigned long long key = 0;
+        VoxHit h;
+        if (!vox_key(p.x, p.y, p.z, size, &key) || !vox_probe(tab, mask, key, &h)) return;
+        cnt += 1.0;
+        const float3 up = vox_unit_or_zero(fmaf(T[8], rn.z, fmaf(T[4], rn.y, T[0] * rn.x)), fmaf(T[9], rn.z, fmaf(T[5], rn.y, T[1] * rn.x)),
+                                           fmaf(T[10], rn.z, fmaf(T[6], rn.y, T[2] * rn.x)));
+        const float nxx = h.a.w, nxy = h.b.x, nxz = h.b.y, nyy = h.b.z, nyz = h.b.w, nzz = h.c.x;
+        // S = C_v + C(u_p) = 2 I - (1 - eps)(N + u_p u_p^T), symmetric: xx xy xz yy yz zz
+        const float sxx = 2.f - g * (nxx + up.x * up.x), syy = 2.f - g * (nyy + up.y * up.y), szz = 2.f - g * (nzz + up.z * up.z);
+        const float sxy = -g * (nxy + up.x * up.y), sxz = -g * (nxz + up.x * up.z), syz = -g * (nyz + up.y * up.z);
+        // M = adj(S) / det(S)
+        const float c00 = syy * szz - syz * syz, c01 = sxz * syz - sxy * szz, c02 = sxy * syz - sxz * syy;
+        const float c11 = sxx * szz - sxz * sxz, c12 = sxy * sxz - sxx * syz, c22 = sxx * syy - sxy * sxy;
+        const float idet = 1.f / (sxx * c00 + sxy * c01 + sxz * c02);
+        const float3 m0 = make_float3(c00 * idet, c01 * idet, c02 * idet), m1 = make_float3(m0.y, c11 * idet, c12 * idet),
+                     m2 = make_float3(m0.z, m1.z, c22 * idet);
+        acc[15] += (double)m0.x; acc[16] += (double)m0.y; acc[17] += (double)m0.z; acc[18] += (double)m1.y; acc[19] += (double)m1.z; acc[20] += (double)m2.z;
+        const float dx = p.x - h.a.x, dy = p.y - h.a.y, dz = p.z - h.a.z;
+        const float3 md = make_float3(m0.x * dx + m0.y * dy + m0.z * dz, m1.x * dx + m1.y * dy + m1.z * dz, m2.x * dx + m2.y * dy + m2.z * dz);
+        const float3 pmd = vcross3(p, md);
+        acc[21] -= (double)pmd.x; acc[22] -= (double)pmd.y; acc[23] -= (double)pmd.z; acc[24] -= (double)md.x; acc[25] -= (double)md.y; acc[26] -= (double)md.z;
+        // P M with P = [p]x: column j is p x (column j of M); row i of P M P^T is p x (row i of P M)
+        const float3 k0 = vcross3(p, m0), k1 = vcross3(p, m1), k2 = vcross3(p, m2);
+        const float3 pm0 = make_float3(k0.x, k1.x, k2.x), pm1 = make_float3(k0.y, k1.y, k2.y), pm2 = make_float3(k0.z, k1.z, k2.z);
+        acc[3] += (double)pm0.x; acc[4] += (double)pm0.y; acc[5] += (double)pm0.z;
+        acc[8] += (double)pm1.x; acc[9] += (double)pm1.y; acc[10] += (double)pm1.z;
+        acc[12] += (double)pm2.x; acc[13] += (double)pm2.y; acc[14] += (double)pm2.z;
+        const float3 r0 = vcross3(p, pm0), r1 = vcross3(p, pm1), r2 = vcross3(p, pm2);
+        acc[0] += (double)r0.x; acc[1] += (double)r0.y; acc[2] += (double)r0.z; acc[6] += (double)r1.y; acc[7] += (double)r1.z; acc[11] += (double)r2.z;
+    };
+#pragma unroll
+    for (int u = 0; u < PF; ++u)
+        if (e0 + u * stride < n) pair(pr[u], pn[u]);
+    for (int64_t e = e0 + PF * stride; e < n; e += stride)
+        pair(reading[e], read_normals ? *reinterpret_cast<const float3*>(read_normals + e) : make_float3(0.f, 0.f, 0.f));
+
+    // ---- workgroup reduction: accumulate_kernel's, value for value (32 values x 64 lanes fold with 32 exchanges; fixed pattern) ----
+    __shared__ double sh[4][ICPMI_NV];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    double val[ICPMI_NV];
+#pragma unroll
+    for (int i = 0; i < ICPMI_NV; ++i) val[i] = i < 27 ? acc[i < 27 ? i : 0] : 0.0;
+    val[27] = cnt; val[28] = cnt; // (weight 1 per pair: sum w = the pair count)
+#pragma unroll
+    for (int s = 0; s < 5; ++s) {
+        const int m = 1 << s;
+        const int nkeep = 16 >> s;
+        const bool upper = (lane & m) != 0;
+#pragma unroll
+        for (int i = 0; i < nkeep; ++i) {
+            const double send = upper ? val[i] : val[i + nkeep];
+            const double keep = upper ? val[i + nkeep] : val[i];
+            val[i] = keep + __shfl_xor(send, m, 64);
+        }
+    }
+    val[0] += __shfl_xor(val[0], 32, 64);
+    if (lane < 32) {
+        const int idx = ((lane & 1) << 4) | ((lane & 2) << 2) | (lane & 4) | ((lane & 8) >> 2) | ((lane & 16) >> 4);
+        sh[wv][idx] = val[0];
+    }
+    __syncthreads();
+    if (threadIdx.x < ICPMI_NV) {
+        const int i = threadIdx.x;
+        double v = 0.0;
+        if (i < 29) v = sh[0][i] + sh[1][i] + sh[2][i] + sh[3][i]; // fixed order
+        unsigned long long* out = reinterpret_cast<unsigned long long*>(hists + ICPMI_S2_ACC);
+        if (v != 0.0) {
+            if (!(fabs(v) < 0x1p77)) atomicOr(reinterpret_cast<unsigned*>(out + ICPMI_ACC_FLAG), 1u);
+            else {
+                const double hi = rint(v * 0x1p-16);
+                const double lo = v - hi * 65536.0;                 // exact: a multiple of ulp(v) below 2^15
+                const long long H = (long long)hi, Lq = __double2ll_rn(lo * 0x1p40);
+                const int cp = blockIdx.x & (ICPMI_ACC_COPIES - 1);
+                if (H) atomicAdd(out + ICPMI_ACC_IDX(cp, i, 0), (unsigned long long)H);
+                if (Lq) atomicAdd(out + ICPMI_ACC_IDX(cp, i, 1), (unsigned long long)Lq);
+            }
+        }
+    }
+}
+
+// the HIP events of a timed diagnostic: created together, destroyed on every way out of the call
+template <int N>
+struct EventSet {
+    hipEvent_t ev[N] = {};
+    EventSet() = default;
+    EventSet(const EventSet&) = delete;
+    EventSet& operator=(const EventSet&) = delete;
+    ~EventSet() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
+    hipError_t create() { for (hipEvent_t& e : ev) { const hipError_t s = hipEventCreate(&e); if (s != hipSuccess) { e = nullptr; return s; } } return hipSuccess; }
+};
+
+} // namespace
+
+bool voxel_table_current(const icpmi_ctx* c)
+{
+    return c->vox_ready && c->vox_nv > 0 && c->vox_map_version == c->map_version && c->vox_epoch == c->map_epoch && c->vox_built_size == c->voxel_size;
+}
+
+// Builds the table of the resident map for c->voxel_size unless the handle holds it already (lazily: the first call that needs it after
+// the map or the size changed).  Stream-ordered but for one read-back (voxel count and range flag).  times_ms (may be null): sort, reduce,
+// fill as HIP events measure them (scripts/voxel_bench.py); asking for them forces a rebuild.
+icpmi_status voxel_ensure_table(icpmi_ctx* c, float* times_ms)
+{
+    if (!(c->voxel_size > 0.f)) { c->last_error = "voxel matcher: no voxel size set (icpmi_set_voxel_matcher)"; return ICPMI_ERR_INVALID_ARG; }
+    if (c->m <= 0) { c->last_error = "voxel matcher: no map"; return ICPMI_ERR_INVALID_ARG; }
+    if (!c->has_normals || !c->d_normals_sorted.get()) {
+        c->last_error = "InvalidField: VoxelMatcher needs the descriptor 'normals' on the map"; return ICPMI_ERR_MISSING_NORMALS;
+    }
+    if (!times_ms && voxel_table_current(c)) return ICPMI_OK;
+    c->vox_ready = false;
+    const int64_t m = c->m;
+    const int blocks = (int)((m + 255) / 256);
+    unsigned long long* d_keys = scratch_get<unsigned long long>(c, 0, (size_t)2 * m + 2);
+    unsigned* d_vals = scratch_get<unsigned>(c, 1, (size_t)2 * m + 2);
+    unsigned* d_tab = scratch_get<unsigned>(c, 2, radix_sort_tab_words(m, 63));
+    const int64_t fs = m + 2; // the scan writes out[m] (its total) behind its output
+    unsigned* d_flag = scratch_get<unsigned>(c, 4, (size_t)2 * fs + 4); // head | pos | range flag
+    unsigned* d_vstart = scratch_get<unsigned>(c, 5, (size_t)m + 2);
+    if (!d_keys || !d_vals || !d_tab || !d_flag || !d_vstart) return ICPMI_ERR_HIP;
+    unsigned* d_head = d_flag; unsigned* d_pos = d_flag + fs; unsigned* d_bad = d_flag + 2 * fs;
+    EventSet<4> evs; // (destroyed on every way out)
+    hipEvent_t* ev = evs.ev;
+    if (times_ms) HIP_TRY(c, evs.create());
+
+    HIP_TRY(c, hipMemsetAsync(d_bad, 0, sizeof(unsigned), c->stream));
+    if (ev[0]) (void)hipEventRecord(ev[0], c->stream);
+    hipLaunchKernelGGL(vox_key_kernel, dim3(blocks), dim3(256), 0, c->stream, (const float4*)c->d_map_sorted, m, c->voxel_size, d_keys, d_vals, d_bad);
+    HIP_TRY(c, hipGetLastError());
+    int half = 0;
+    { const icpmi_status s = radix_sort_pairs(c, d_keys, d_vals, m, 63, d_tab, &half); if (s != ICPMI_OK) return s; }
+    const unsigned long long* skeys = d_keys + (half ? m : 0);
+    const unsigned* svals = d_vals + (half ? m : 0);
+    hipLaunchKernelGGL(vox_head_kernel, dim3(blocks), dim3(256), 0, c->stream, skeys, m, d_head);
+    HIP_TRY(c, hipGetLastError());
+    if (ev[1]) (void)hipEventRecord(ev[1], c->stream);
+    int64_t nv = 0;
+    { const icpmi_status s = device_scan_flags_count(c, d_head, d_pos, (int)m, &nv); if (s != ICPMI_OK) return s; }
+    unsigned bad = 0;
+    if (read_back(c, &bad, d_bad, sizeof bad) != ICPMI_OK) return ICPMI_ERR_HIP;
+    if (bad) {
+        c->last_error = "voxel matcher: a map point has a non-finite coordinate or lies 2^20 or more voxels from the map's centroid on one axis";
+        return ICPMI_ERR_INVALID_ARG;
+    }
+    if (nv <= 0 || nv > m) { c->last_error = "voxel matcher: bad voxel count"; return ICPMI_ERR_HIP; }
+    unsigned cap = 2;
+    while ((uint64_t)cap < 2 * (uint64_t)nv) cap <<= 1;
+    if (c->d_vox_keys.ensure(c, (size_t)nv) != ICPMI_OK || c->d_vox_rec.ensure(c, (size_t)3 * nv) != ICPMI_OK ||
+        c->d_vox_tab.ensure(c, (size_t)4 * cap) != ICPMI_OK) return ICPMI_ERR_HIP;
+    hipLaunchKernelGGL(vox_start_kernel, dim3(blocks), dim3(256), 0, c->stream, (const unsigned*)d_head, (const unsigned*)d_pos, m, d_vstart);
+    hipLaunchKernelGGL(vox_reduce_kernel, dim3((int)((nv + 3) / 4)), dim3(256), 0, c->stream, skeys, svals, (const unsigned*)d_vstart, nv,
+                       (const float4*)c->d_map_sorted, (const float4*)c->d_normals_sorted, c->d_vox_keys.get(), c->d_vox_rec.get());
+    HIP_TRY(c, hipGetLastError());
+    if (ev[2]) (void)hipEventRecord(ev[2], c->stream);
+    HIP_TRY(c, hipMemsetAsync(c->d_vox_tab.get(), 0xff, (size_t)cap * 64, c->stream));
+    hipLaunchKernelGGL(vox_fill_kernel, dim3((int)((nv + 255) / 256)), dim3(256), 0, c->stream, (const unsigned long long*)c->d_vox_keys.get(),
+                       (const float4*)c->d_vox_rec.get(), nv, c->d_vox_tab.get(), cap - 1);
+    HIP_TRY(c, hipGetLastError());
+    if (ev[3]) (void)hipEventRecord(ev[3], c->stream);
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (times_ms) {
+        for (int i = 0; i < 3; ++i) { times_ms[i] = 0.f; (void)hipEventElapsedTime(&times_ms[i], ev[i], ev[i + 1]); }
+    }
+    c->vox_nv = nv; c->vox_mask = cap - 1;
+    c->vox_map_version = c->map_version; c->vox_epoch = c->map_epoch; c->vox_built_size = c->voxel_size;
+    ++c->vox_gen;
+    c->vox_ready = true;
+    return ICPMI_OK;
+}
+
+// the iteration's pair sums on the handle's stream (no allocation, no wait: loop.hip captures it); the table is current (voxel_ensure_table)
+void voxel_enqueue_pairs(icpmi_ctx* c, int64_t n, int nb, float eps)
+{
+    hipLaunchKernelGGL(voxel_pairs_kernel, dim3(nb), dim3(256), 0, c->stream, (const float4*)c->d_reading, (const float4*)c->d_read_normals, (int)n,
+                       c->d_state.get(), (const uint4*)c->d_vox_tab.get(), c->vox_mask, c->voxel_size, eps, c->d_selhist.get());
+}
+
+icpmi_status voxel_get_map(icpmi_ctx* c, int64_t cap, int32_t* ijk3, float* mean3, float* moments6, int32_t* count, int64_t* n_voxels)
+{
+    { const icpmi_status s = voxel_ensure_table(c, nullptr); if (s != ICPMI_OK) return s; }
+    const int64_t nv = c->vox_nv;
+    if (n_voxels) *n_voxels = nv;
+    if (cap < nv) { c->last_error = "get_voxel_map: capacity below the voxel count (*n_voxels has it)"; return ICPMI_ERR_INVALID_ARG; }
+    std::vector<unsigned long long> keys((size_t)nv);
+    std::vector<float> rec((size_t)12 * nv);
+    HIP_TRY(c, hipMemcpyAsync(keys.data(), c->d_vox_keys.get(), (size_t)nv * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(rec.data(), c->d_vox_rec.get(), (size_t)nv * 12 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    for (int64_t v = 0; v < nv; ++v) {
+        const float* r = rec.data() + 12 * v;
+        if (ijk3) {
+            ijk3[3 * v + 0] = (int)((keys[v] >> 42) & 0x1fffff) - VOX_BIAS;
+            ijk3[3 * v + 1] = (int)((keys[v] >> 21) & 0x1fffff) - VOX_BIAS;
+            ijk3[3 * v + 2] = (int)(keys[v] & 0x1fffff) - VOX_BIAS;
+        }
+        if (mean3) for (int j = 0; j < 3; ++j) mean3[3 * v + j] = r[j];
+        if (moments6) for (int j = 0; j < 6; ++j) moments6[6 * v + j] = r[3 + j];
+        if (count) { unsigned cw; memcpy(&cw, r + 9, sizeof cw); count[v] = (int32_t)cw; }
+    }
+    return ICPMI_OK;
+}
+
+icpmi_status voxel_lookup(icpmi_ctx* c, const float* q4_centred, int64_t n, int32_t* voxel)
+{
+    { const icpmi_status s = voxel_ensure_table(c, nullptr); if (s != ICPMI_OK) return s; }
+    if (n == 0) return ICPMI_OK;
+    DevBuf<float4> d_q; DevBuf<int> d_out;
+    HIP_TRY(c, d_q.alloc((size_t)n));
+    HIP_TRY(c, d_out.alloc((size_t)n));
+    HIP_TRY(c, hipMemcpyAsync(d_q.get(), q4_centred, (size_t)n * sizeof(float4), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(vox_lookup_kernel, dim3((int)((n + 255) / 256)), dim3(256), 0, c->stream, (const float4*)d_q.get(), n, c->voxel_size,
+                       (const uint4*)c->d_vox_tab.get(), c->vox_mask, d_out.get());
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(voxel, d_out.get(), (size_t)n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return ICPMI_OK;
+}
+
+// diagnostics (scripts/voxel_bench.py): n centred-frame queries looked up `reps` times through the table and `reps` times by binary search
+// over the sorted keys; ms[0] / ms[1] = the mean milliseconds of one launch of either, *mismatch = queries the two answer differently
+icpmi_status voxel_lookup_times(icpmi_ctx* c, const float* q4_centred, int64_t n, int reps, float ms[2], int64_t* mismatch)
+{
+    { const icpmi_status s = voxel_ensure_table(c, nullptr); if (s != ICPMI_OK) return s; }
+    DevBuf<float4> d_q; DevBuf<int> d_a, d_b;
+    HIP_TRY(c, d_q.alloc((size_t)n));
+    HIP_TRY(c, d_a.alloc((size_t)n));
+    HIP_TRY(c, d_b.alloc((size_t)n));
+    HIP_TRY(c, hipMemcpyAsync(d_q.get(), q4_centred, (size_t)n * sizeof(float4), hipMemcpyHostToDevice, c->stream));
+    EventSet<3> evs; // (destroyed on every way out)
+    hipEvent_t* ev = evs.ev;
+    HIP_TRY(c, evs.create());
+    const dim3 grid((int)((n + 255) / 256));
+    for (int pass = 0; pass < 2; ++pass) { // (pass 0 warms both)
+        (void)hipEventRecord(ev[0], c->stream);
+        for (int r = 0; r < reps; ++r)
+            hipLaunchKernelGGL(vox_lookup_kernel, grid, dim3(256), 0, c->stream, (const float4*)d_q.get(), n, c->voxel_size, (const uint4*)c->d_vox_tab.get(),
+                               c->vox_mask, d_a.get());
+        (void)hipEventRecord(ev[1], c->stream);
+        for (int r = 0; r < reps; ++r)
+            hipLaunchKernelGGL(vox_lookup_bsearch_kernel, grid, dim3(256), 0, c->stream, (const float4*)d_q.get(), n, c->voxel_size,
+                               (const unsigned long long*)c->d_vox_keys.get(), c->vox_nv, d_b.get());
+        (void)hipEventRecord(ev[2], c->stream);
+    }
+    const hipError_t se = hipStreamSynchronize(c->stream);
+    ms[0] = ms[1] = 0.f;
+    (void)hipEventElapsedTime(&ms[0], ev[0], ev[1]);
+    (void)hipEventElapsedTime(&ms[1], ev[1], ev[2]);
+    HIP_TRY(c, se);
+    HIP_TRY(c, hipGetLastError());
+    ms[0] /= (float)reps; ms[1] /= (float)reps;
+    std::vector<int> a((size_t)n), b((size_t)n);
+    HIP_TRY(c, hipMemcpy(a.data(), d_a.get(), (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(b.data(), d_b.get(), (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
+    int64_t bad = 0;
+    for (int64_t i = 0; i < n; ++i) bad += a[(size_t)i] != b[(size_t)i];
+    if (mismatch) *mismatch = bad;
+    return ICPMI_OK;
+}

@@ -65,6 +65,13 @@ void GpuICPSequence::setPlanar(bool on)
     recreate();
 }
 
+// icpmi_set_voxel_matcher: the voxel size of VoxelMatcher (0: off); handle state, kept across setPlanar
+void GpuICPSequence::setVoxelMatcher(float size)
+{
+    check(h, icpmi_set_voxel_matcher(h, size));
+    voxelSize = size;
+}
+
 void GpuICPSequence::recreate()
 {
     // the handle is created once and re-configured afterwards: filters, modules and transformations
@@ -91,6 +98,8 @@ void GpuICPSequence::setDefault()
     cfg.use_differential = 1;
     recreate();
     check(h, icpmi_set_intensity_weight(h, 0.f)); // (handle state, which icpmi_set_config leaves: a chain loaded before may have set it)
+    voxelSize = 0.f;
+    check(h, icpmi_set_voxel_matcher(h, 0.f));    // (likewise)
     readingDataPointsFilters = std::make_shared<DataPointsFilters>();
     readingDataPointsFilters->ctx = h;
     readingDataPointsFilters->filters.push_back(createDataPointsFilter("RandomSamplingDataPointsFilter", yaml::Node(), h));
@@ -118,11 +127,27 @@ std::pair<std::string, yaml::Node> singleEntry(const yaml::Node& n, const std::s
 }
 
 // the `matcher:` entry of an ICP chain into the configuration; maxDistField = KDTreeVarDistMatcher's descriptor name, empty for KDTreeMatcher
-void parseMatcher(const yaml::Node& matcher, icpmi_config& cfg, std::string& maxDistField)
+void parseMatcher(const yaml::Node& matcher, icpmi_config& cfg, std::string& maxDistField, float* voxelSize)
 {
     maxDistField.clear();
     cfg.var_dist = 0;
+    if (voxelSize) *voxelSize = 0.f;
     auto e = singleEntry(matcher, "matcher");
+    if (e.first == "VoxelMatcher") {
+        // voxelised plane-to-plane ICP (not libpointmatcher's; include/icpmi.h: icpmi_set_voxel_matcher): a reading point is paired with the
+        // map voxel it falls into -- no search, hence no knn / maxDist / epsilon
+        requireKnown(e.second, {"voxelSize"}, "VoxelMatcher");
+        const float size = e.second["voxelSize"] ? e.second["voxelSize"].as<float>() : 1.f;
+        if (!std::isfinite(size) || !(size > 0.f)) throw InvalidParameter("VoxelMatcher: voxelSize must be finite and > 0");
+        if (!voxelSize) throw InvalidParameter("VoxelMatcher: not available here");
+        *voxelSize = size;
+        // the loop reads none of KDTreeMatcher's parameters; getResidualError, which scores the pose through the nearest-neighbour matcher,
+        // runs it with that matcher's defaults whatever an earlier chain left in cfg
+        icpmi_config def;
+        icpmi_config_default(&def);
+        cfg.knn = def.knn; cfg.epsilon = def.epsilon; cfg.epsilon_approx = def.epsilon_approx; cfg.max_dist = def.max_dist;
+        return;
+    }
     if (e.first == "KDTreeVarDistMatcher") {
         // every reading point searches within its own radius, the reading's 1-row descriptor `maxDistField` (operator() hands it over)
         requireKnown(e.second, {"knn", "epsilon", "searchType", "maxDistField"}, "KDTreeVarDistMatcher");
@@ -203,6 +228,18 @@ void parseErrorMinimizer(const yaml::Node& node, icpmi_config& cfg, float& plane
     } else throw InvalidParameter("unknown error minimizer " + e.first);
 }
 
+// VoxelMatcher is accepted with PlaneToPlaneErrorMinimizer and an empty outlier list only -- the C call's wording (csrc/api.hip: voxel_check)
+void checkVoxelChain(float voxelSize, int nOutlier, int minimizer, int planeModel)
+{
+    if (!(voxelSize > 0.f)) return;
+    const std::string who = "register: the voxel matcher (icpmi_set_voxel_matcher > 0) ";
+    if (nOutlier > 0)
+        throw InvalidParameter(who + "is not served with outlier filters (a pair is a point and the voxel it falls into: there is no match distance to filter on)");
+    if (minimizer == ICPMI_MIN_PLANE_TO_PLANE && planeModel != ICPMI_PLANE_MODEL_GICP)
+        throw InvalidParameter(who + "is not served with the symmetric pair model (SymmetricPointToPlaneErrorMinimizer)");
+    if (minimizer != ICPMI_MIN_PLANE_TO_PLANE) throw InvalidParameter(who + "is defined on PlaneToPlaneErrorMinimizer only");
+}
+
 void GpuICPSequence::loadFromYamlNode(const yaml::Node& icp)
 {
     const int dev = cfg.device;
@@ -221,7 +258,8 @@ void GpuICPSequence::loadFromYamlNode(const yaml::Node& icp)
         }
 
     maxDistFieldName.clear();
-    if (icp["matcher"]) parseMatcher(icp["matcher"], cfg, maxDistFieldName);
+    voxelSize = 0.f;
+    if (icp["matcher"]) parseMatcher(icp["matcher"], cfg, maxDistFieldName, &voxelSize);
     cfg.n_outlier = 0;
     genericDescName.clear(); genericReadDescName.clear();
     if (icp["outlierFilters"].IsSequence())
@@ -297,6 +335,7 @@ void GpuICPSequence::loadFromYamlNode(const yaml::Node& icp)
         }
     intensity = IntensityTerm{};
     if (icp["errorMinimizer"]) parseErrorMinimizer(icp["errorMinimizer"], cfg, planeEpsilon, planeModel, &intensity);
+    checkVoxelChain(voxelSize, cfg.n_outlier, cfg.minimizer, planeModel);
     if (icp["transformationCheckers"].IsSequence())
         for (const auto& item : icp["transformationCheckers"].seq) {
             auto e = singleEntry(item, "transformation checker");
@@ -320,6 +359,7 @@ void GpuICPSequence::loadFromYamlNode(const yaml::Node& icp)
     check(h, icpmi_set_plane_epsilon(h, planeEpsilon));
     check(h, icpmi_set_plane_pair_model(h, planeModel));
     check(h, icpmi_set_intensity_weight(h, intensity.weight));
+    check(h, icpmi_set_voxel_matcher(h, voxelSize));
     auto chain = [&](const char* key) -> std::shared_ptr<DataPointsFilters> {
         if (!icp[key] || !icp[key].IsSequence() || icp[key].seq.empty()) return nullptr;
         return std::make_shared<DataPointsFilters>(icp[key], h);

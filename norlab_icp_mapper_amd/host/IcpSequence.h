@@ -28,7 +28,7 @@ void requireKnown(const yaml::Node& params, std::initializer_list<const char*> k
 std::pair<std::string, yaml::Node> singleEntry(const yaml::Node& n, const std::string& what);
 // the `matcher:` entry of an ICP chain (KDTreeMatcher | KDTreeVarDistMatcher) into cfg; maxDistField = the descriptor name of a
 // KDTreeVarDistMatcher (default maxSearchDist), empty for KDTreeMatcher.  Needs no GPU.
-void parseMatcher(const yaml::Node& matcher, icpmi_config& cfg, std::string& maxDistField);
+void parseMatcher(const yaml::Node& matcher, icpmi_config& cfg, std::string& maxDistField, float* voxelSize = nullptr); // voxelSize: VoxelMatcher.voxelSize, 0 for the others (null: VoxelMatcher is refused)
 // the `errorMinimizer:` entry into cfg (minimizer, force2D / force4DOF, covariance, degeneracy options); planeEpsilon = the epsilon of a
 // PlaneToPlaneErrorMinimizer (default 0.001; the others leave it alone); planeModel = ICPMI_PLANE_MODEL_SYMMETRIC under
 // SymmetricPointToPlaneErrorMinimizer, which travels as ICPMI_MIN_PLANE_TO_PLANE (the others leave it alone).  Needs no GPU.
@@ -39,6 +39,8 @@ struct IntensityTerm {
     int knn = 10;                       // gradientKnn: neighbours of a map-side gradient (icpmi_set_map_intensity)
     std::string descName;               // descName: the 1-row descriptor both clouds carry (empty: no such minimiser)
 };
+// throws InvalidParameter unless a chain with VoxelMatcher (voxelSize > 0) has PlaneToPlaneErrorMinimizer (the GICP pair model) and no outlier filter
+void checkVoxelChain(float voxelSize, int nOutlier, int minimizer, int planeModel);
 void parseErrorMinimizer(const yaml::Node& node, icpmi_config& cfg, float& planeEpsilon, int& planeModel, IntensityTerm* intensity = nullptr);
 
 // ---- relocalisation: one reading under many poses (include/icpmi.h: icpmi_residual_error_poses, icpmi_register_multistart) ----
@@ -104,6 +106,8 @@ public:
     GpuICPSequence& operator=(const GpuICPSequence&) = delete;
 
     void setDefault();                                 // PM::ICPSequence::setDefault
+    void setVoxelMatcher(float size);                  // icpmi_set_voxel_matcher (0: off): VoxelMatcher on a PlaneToPlaneErrorMinimizer chain
+    float getVoxelMatcher() const { return voxelSize; }
     void loadFromYamlNode(const yaml::Node& icpNode);  // the `icp:` sub-tree
     bool setMap(const DataPoints& map);                // false on an empty cloud, state unchanged
     bool hasMap() const;
@@ -183,6 +187,7 @@ private:
     icpmi_config cfg;
     icpmi_stats lastStats{};
     float planeEpsilon = 1e-3f;                        // PlaneToPlaneErrorMinimizer.epsilon (icpmi_set_plane_epsilon)
+    float voxelSize = 0.f;                             // VoxelMatcher.voxelSize (icpmi_set_voxel_matcher; 0: a KDTree matcher)
     int planeModel = ICPMI_PLANE_MODEL_GICP;           // ... and its pair model (icpmi_set_plane_pair_model): SymmetricPointToPlaneErrorMinimizer
     size_t stagedPoints = 0;                           // size of the scan kept on the GPU by registerWithPrior
     std::string genericDescName;                       // GenericDescriptorOutlierFilter.descName (empty: no such filter)

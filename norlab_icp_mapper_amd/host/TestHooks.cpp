@@ -165,6 +165,29 @@ int nim_test_parse_error_minimizer(const char* yaml_icp, int* minimizer, int* fo
     }
 }
 
+// the matcher, the number of outlier filters and the error minimiser of an ICP chain given as YAML text, as loadFromYamlNode reads them for
+// VoxelMatcher (no GPU, no handle): its voxel size (0 for another matcher) and the minimiser.  Returns 0, or 1 with the exception's text in err.
+int nim_test_parse_voxel_chain(const char* yaml_icp, float* voxel_size, int* minimizer, int* plane_model, char* err, int err_cap)
+{
+    try {
+        icpmi_config cfg;
+        icpmi_config_default(&cfg);
+        const nim::yaml::Node icp = nim::yaml::Load(yaml_icp);
+        std::string field;
+        float size = 0.f, eps = 1e-3f;
+        int model = ICPMI_PLANE_MODEL_GICP;
+        if (icp["matcher"]) nim::parseMatcher(icp["matcher"], cfg, field, &size);
+        const int n_out = icp["outlierFilters"].IsSequence() ? (int)icp["outlierFilters"].seq.size() : 0;
+        if (icp["errorMinimizer"]) nim::parseErrorMinimizer(icp["errorMinimizer"], cfg, eps, model);
+        nim::checkVoxelChain(size, n_out, cfg.minimizer, model);
+        *voxel_size = size; *minimizer = cfg.minimizer; *plane_model = model;
+        return 0;
+    } catch (const std::exception& e) {
+        if (err && err_cap > 0) { std::strncpy(err, e.what(), (size_t)err_cap - 1); err[err_cap - 1] = 0; }
+        return 1;
+    }
+}
+
 // ... and the photometric term of IntensityPointToPlaneErrorMinimizer with it (weight 0, knn 10 and an empty name under every other entry)
 int nim_test_parse_error_minimizer_intensity(const char* yaml_icp, int* minimizer, int* force_4dof, float* weight, int* knn, char* desc_name, int desc_cap,
                                              char* err, int err_cap)

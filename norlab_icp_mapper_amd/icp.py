@@ -92,6 +92,18 @@ def _check_intensity_knn(k):
     return int(k)
 
 
+VOXEL_SIZE_DEFAULT = 1.0
+# the C call's wording (csrc/api.hip: voxel_check), as the chain parser sees the same combinations
+_VOXEL_REFUSAL = "register: the voxel matcher (icpmi_set_voxel_matcher > 0) "
+
+
+def _check_voxel_size(size):
+    size = float(size)
+    if not (math.isfinite(size) and size >= 0.0):
+        raise InvalidParameter("VoxelMatcher: voxelSize must be finite and >= 0 (0: off)")
+    return size
+
+
 def _check_plane_model(model):
     if model not in _PLANE_MODELS:
         raise InvalidParameter(f"plane_model must be one of {sorted(_PLANE_MODELS)}, not {model!r}")
@@ -163,7 +175,17 @@ def config_from_yaml_chain(chain, **engine):
     matcher = chain.get("matcher", {"KDTreeMatcher": {}})
     name, p = single(matcher, "matcher")
     max_dist_field = None
-    if name == "KDTreeVarDistMatcher":
+    voxel_size = None
+    if name == "VoxelMatcher":
+        # voxelised plane-to-plane ICP (not libpointmatcher's; include/icpmi.h: icpmi_set_voxel_matcher): a reading point is paired with the
+        # map voxel it falls into -- no search, hence no knn / maxDist / epsilon
+        for key in p:
+            if key != "voxelSize":
+                raise InvalidParameter(f"VoxelMatcher: unknown parameter {key}")
+        voxel_size = _check_voxel_size(p.get("voxelSize", VOXEL_SIZE_DEFAULT))
+        if not voxel_size > 0.0:
+            raise InvalidParameter("VoxelMatcher: voxelSize must be finite and > 0")
+    elif name == "KDTreeVarDistMatcher":
         # every reading point searches within its own radius: the reading's 1-row descriptor `maxDistField` (ICPSequence.__call__ hands it over)
         for key in p:
             if key not in ("knn", "epsilon", "searchType", "maxDistField"):
@@ -229,6 +251,8 @@ def config_from_yaml_chain(chain, **engine):
                 raise InvalidParameter(f"{name}: unknown parameter {key}")
         outs.append((t, float(p.get(pname, default))))
     kw["outliers"] = outs
+    if voxel_size is not None and outs:
+        raise InvalidParameter(_VOXEL_REFUSAL + "is not served with outlier filters (a pair is a point and the voxel it falls into: there is no match distance to filter on)")
 
     name, p = single(chain.get("errorMinimizer", "PointToPlaneErrorMinimizer"), "errorMinimizer")
     if name == "PointToPlaneWithCovErrorMinimizer":
@@ -271,6 +295,10 @@ def config_from_yaml_chain(chain, **engine):
                      str(p.get("descName", INTENSITY_DESC_DEFAULT)))
     if name not in _MINIMIZERS:
         raise InvalidParameter(f"unknown error minimizer {name}")
+    if voxel_size is not None and name == "SymmetricPointToPlaneErrorMinimizer":
+        raise InvalidParameter(_VOXEL_REFUSAL + "is not served with the symmetric pair model (SymmetricPointToPlaneErrorMinimizer)")
+    if voxel_size is not None and name != "PlaneToPlaneErrorMinimizer":
+        raise InvalidParameter(_VOXEL_REFUSAL + "is defined on PlaneToPlaneErrorMinimizer only")
     if name == "PointToPlaneErrorMinimizer":
         # degeneracy-aware solve (not libpointmatcher's): degeneracyThreshold >= 0 (0 = off), degeneracyAction constrain | report
         thr = float(p.get("degeneracyThreshold", 0.0))
@@ -310,6 +338,8 @@ def config_from_yaml_chain(chain, **engine):
     cfg = default_config(**kw)
     if max_dist_field is not None:
         cfg.max_dist_field = max_dist_field  # (a Python attribute next to the C fields: the descriptor name is the host's business)
+    if voxel_size is not None:
+        cfg.voxel_size = voxel_size  # (likewise: ICPSequence hands it to icpmi_set_voxel_matcher)
     if plane_epsilon is not None:
         cfg.plane_epsilon = plane_epsilon  # (likewise: icpmi_config has no word left; ICPSequence hands it to icpmi_set_plane_epsilon)
     if plane_model is not None:
@@ -503,7 +533,7 @@ class _ErrorMinimizerView:
 class ICPSequence:
     """``PM::ICPSequence`` backed by one icpmi handle (one GPU, one stream)."""
 
-    def __init__(self, cfg=None, plane_epsilon=None, plane_model=None, intensity_weight=None, intensity_knn=None, **kw):
+    def __init__(self, cfg=None, plane_epsilon=None, plane_model=None, intensity_weight=None, intensity_knn=None, voxel_size=None, **kw):
         """plane_epsilon: epsilon of PlaneToPlaneErrorMinimizer (icpmi_set_plane_epsilon; default: the chain's, else 1e-3)
         plane_model: "gicp" | "symmetric", the pair model of minimizer 3 (icpmi_set_plane_pair_model; default: the chain's, else "gicp")
         intensity_weight: 1 - lambdaGeometric of the photometric term on minimizer 2 (icpmi_set_intensity_weight; default: the chain's, else 0 = off)
@@ -514,6 +544,10 @@ class ICPSequence:
             plane_epsilon = getattr(self.cfg, "plane_epsilon", None)
         if plane_epsilon is not None:
             plane_epsilon = _check_plane_epsilon(plane_epsilon)
+        if voxel_size is None:
+            voxel_size = getattr(self.cfg, "voxel_size", None)
+        if voxel_size is not None:
+            voxel_size = _check_voxel_size(voxel_size)
         if plane_model is None:
             plane_model = getattr(self.cfg, "plane_model", None)
         if plane_model is not None:
@@ -539,6 +573,8 @@ class ICPSequence:
             self.setPlaneEpsilon(plane_epsilon)
         if plane_model is not None:
             self.setPlaneModel(plane_model)
+        if voxel_size is not None:
+            self.setVoxelMatcher(voxel_size)
         if intensity_weight is not None:
             self.setIntensityWeight(intensity_weight)
 
@@ -555,6 +591,38 @@ class ICPSequence:
     def setPlaneEpsilon(self, eps):
         """icpmi_set_plane_epsilon: handle state (setConfig leaves it); the next registration runs with it"""
         self._check(self._lib.icpmi_set_plane_epsilon(self._h, float(eps)))
+
+    def setVoxelMatcher(self, size):
+        """icpmi_set_voxel_matcher: the voxel size of VoxelMatcher (0: off); handle state (setConfig leaves it).  Served with minimizer 3
+        and plane_model "gicp", no outlier filter, by __call__ / registerFixed / minimizeStep with read_normals"""
+        self._check(self._lib.icpmi_set_voxel_matcher(self._h, _check_voxel_size(size)))
+
+    def getVoxelMatcher(self):
+        out = C.c_float(0)
+        self._check(self._lib.icpmi_get_voxel_matcher(self._h, C.byref(out)))
+        return out.value
+
+    def voxelMap(self):
+        """icpmi_get_voxel_map: (ijk (V, 3) int32, mean (V, 3) in the centred frame, moments (V, 6): xx xy xz yy yz zz, count (V,)) in
+        ascending key order"""
+        nv = C.c_int64(0)
+        st = self._lib.icpmi_get_voxel_map(self._h, 0, None, None, None, None, C.byref(nv))
+        if nv.value == 0:
+            self._check(st)
+        v = nv.value
+        ijk, mean = np.zeros((v, 3), np.int32), np.zeros((v, 3), np.float32)
+        mom, cnt = np.zeros((v, 6), np.float32), np.zeros(v, np.int32)
+        self._check(self._lib.icpmi_get_voxel_map(self._h, v, ijk.ctypes.data, mean.ctypes.data, mom.ctypes.data, cnt.ctypes.data, C.byref(nv)))
+        return ijk, mean, mom, cnt
+
+    def voxelLookup(self, q_centred):
+        """icpmi_voxel_lookup: for (N, 3) or (N, 4) centred-frame points the index into voxelMap()'s order, -1 for no voxel"""
+        q = np.asarray(q_centred, np.float32)
+        q4 = np.ones((q.shape[0], 4), np.float32)
+        q4[:, :q.shape[1]] = q
+        out = np.full(q.shape[0], -2, np.int32)
+        self._check(self._lib.icpmi_voxel_lookup(self._h, q4.ctypes.data, q4.shape[0], out.ctypes.data))
+        return out
 
     def setPlaneModel(self, model):
         """icpmi_set_plane_pair_model ("gicp" | "symmetric"): handle state (setConfig leaves it); the next registration runs with it"""
