@@ -982,6 +982,16 @@ icpmi_status icpmi_debug_self_knn(icpmi_handle h, const float* pts4, int64_t m, 
  * resident map's size; *knn_out (may be NULL) = that pass's knn.  ICPMI_ERR_UNSUPPORTED unless the row describes the resident map as it is
  * (a tracked pass ran and nothing rewrote the map since).  No production path calls it. */
 icpmi_status icpmi_debug_resident_kth_d2(icpmi_handle h, int64_t m, float* out, int32_t* knn_out);
+/* Test seam: the rank-ordered merge of icpmi_staged_merge_allgather, and nothing else, on blocks the caller hands in -- no map, no
+ * communicator, nothing appended.  pts4 holds the n_ranks blocks back to back, unpadded (sum(counts) points, x y z w); the call lays block r
+ * at r * stride of a device buffer of stride * n_ranks points whose padding stays uninitialised, as a gathered buffer's is, and runs the
+ * epoch's merge on it.  mode 0: the epoch's own choice between the single launch and the per-block launches; 1: the per-block launches.
+ * merged_out4 gets what fits in `capacity` points, *merged_n always the full count; kept_out (may be NULL) one byte per input point in input
+ * order; *path_out 0 when nothing had to be decided (one non-empty block, or min_dist <= 0), 1 for the single launch, 2 for the per-block
+ * launches.  ICPMI_ERR_INVALID_ARG (the message names the argument): n_ranks outside 1 .. 256, a negative count, a count above stride, a null
+ * pointer where points exist; the merge's own refusals (2^31 span, 2^29 points) are ICPMI_ERR_UNSUPPORTED.  No production path calls it. */
+icpmi_status icpmi_debug_merge_blocks(icpmi_handle h, const float* pts4, const int64_t* counts, int32_t n_ranks, int64_t stride, float min_dist, int32_t mode,
+                                      float* merged_out4, int64_t capacity, int64_t* merged_n, uint8_t* kept_out, int32_t* path_out);
 /* Test seam: the pair sums of the last COUNTED iteration of the last single registration, as its solve read them.  Off by default:
  * icpmi_debug_keep_sums(h, 1) gives the handle a block of 32 doubles that every later single registration's solve writes (the cached loop
  * graphs are dropped; batches never write it), icpmi_debug_keep_sums(h, 0) takes it away again.  Layout of sums[32] (double), as

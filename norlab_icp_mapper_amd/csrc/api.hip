@@ -367,6 +367,25 @@ icpmi_status icpmi_debug_resident_kth_d2(icpmi_handle h, int64_t m, float* out, 
     return ops_debug_resident_kth_d2(h, m, out, knn_out);
 }
 
+icpmi_status icpmi_debug_merge_blocks(icpmi_handle h, const float* pts4, const int64_t* counts, int32_t n_ranks, int64_t stride, float min_dist, int32_t mode,
+                                      float* merged_out4, int64_t capacity, int64_t* merged_n, uint8_t* kept_out, int32_t* path_out)
+{
+    CHECK_H(h);
+    if (n_ranks < 1 || n_ranks > 256) { h->last_error = "debug_merge_blocks: n_ranks must be in [1, 256]"; return ICPMI_ERR_INVALID_ARG; }
+    if (!counts) { h->last_error = "debug_merge_blocks: counts is null"; return ICPMI_ERR_INVALID_ARG; }
+    if (!merged_n || !path_out) { h->last_error = "debug_merge_blocks: merged_n / path_out is null"; return ICPMI_ERR_INVALID_ARG; }
+    if (mode != 0 && mode != 1) { h->last_error = "debug_merge_blocks: mode must be 0 or 1"; return ICPMI_ERR_INVALID_ARG; }
+    int64_t total = 0;
+    for (int r = 0; r < n_ranks; ++r) {
+        if (counts[r] < 0) { h->last_error = "debug_merge_blocks: counts[" + std::to_string(r) + "] is negative"; return ICPMI_ERR_INVALID_ARG; }
+        if (counts[r] > stride) { h->last_error = "debug_merge_blocks: counts[" + std::to_string(r) + "] is above stride"; return ICPMI_ERR_INVALID_ARG; }
+        total += counts[r];
+    }
+    if (total > 0 && !pts4) { h->last_error = "debug_merge_blocks: pts4 is null"; return ICPMI_ERR_INVALID_ARG; }
+    if (capacity < 0 || (total > 0 && capacity > 0 && !merged_out4)) { h->last_error = "debug_merge_blocks: merged_out4 is null (or capacity negative)"; return ICPMI_ERR_INVALID_ARG; }
+    return ops_debug_merge_blocks(h, pts4, counts, n_ranks, stride, min_dist, mode, merged_out4, capacity, merged_n, kept_out, path_out);
+}
+
 icpmi_status icpmi_debug_keep_sums(icpmi_handle h, int32_t on)
 {
     CHECK_H(h);

@@ -1488,6 +1488,8 @@ icpmi_status ops_set_map_intensity(icpmi_ctx* c, const float* intensity, int64_t
 // test seams (icpmi_debug_self_knn / icpmi_debug_resident_kth_d2)
 icpmi_status ops_debug_self_knn(icpmi_ctx* c, const float* pts4, int64_t m, int k, int32_t* ids, float* d2, uint64_t* info);
 icpmi_status ops_debug_resident_kth_d2(icpmi_ctx* c, int64_t m, float* out, int32_t* knn_out);
+icpmi_status ops_debug_merge_blocks(icpmi_ctx* c, const float* pts4, const int64_t* counts, int n_ranks, int64_t stride, float min_dist, int mode,
+                                    float* merged_out4, int64_t capacity, int64_t* merged_n, uint8_t* kept_out, int32_t* path_out);
 icpmi_status ops_dynamic_points_update(icpmi_ctx* c, const icpmi_dynpts_params* prm, const float to_sensor[16], const float* in4, int64_t n,
                                        const float* map4, const float* map_normals3, int64_t m, float* prob);
 icpmi_status ops_map_update_point_distance(icpmi_ctx* c, const float* scan4, int64_t n, const float* scan_normals3, float min_dist,

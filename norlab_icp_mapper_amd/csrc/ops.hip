@@ -967,10 +967,15 @@ __global__ __launch_bounds__(256) void merge_flag_all_kernel(const float4* __res
 
 
 // recv: block r = recv[r * maxc .. r * maxc + counts[r]) (maxc = the stride of the padded layout)
-static icpmi_status merge_greedy(icpmi_ctx* c, const float4* recv, const std::vector<long long>& counts, long long maxc, float min_dist, int64_t* merged_n)
+// path (the test seam's, ops_debug_merge_blocks; null for the epochs): in, != 0 takes the per-block launches whatever the span; out, what
+// decided the flags -- 0 nothing to decide, 1 the single launch, 2 the per-block launches
+static icpmi_status merge_greedy(icpmi_ctx* c, const float4* recv, const std::vector<long long>& counts, long long maxc, float min_dist, int64_t* merged_n,
+                                 int* path = nullptr)
 {
     const int R = (int)counts.size();
     *merged_n = 0;
+    const bool per_block = path && *path != 0;
+    if (path) *path = 0;
     const long long span = maxc * R; // padded layout of d_merge_recv: global index g = r * maxc + i
     if (span <= 0) return ICPMI_OK;
     if (span >= (1ll << 31)) { c->last_error = "staged_merge_allgather: gathered set too large"; return ICPMI_ERR_UNSUPPORTED; }
@@ -1012,7 +1017,9 @@ static icpmi_status merge_greedy(icpmi_ctx* c, const float4* recv, const std::ve
         HIP_TRY(c, hipMemsetAsync(tkeys, 0xff, (size_t)cap * sizeof(unsigned long long), c->stream));
         HIP_TRY(c, hipMemsetAsync(tcnt, 0, ((size_t)cap + 2) * sizeof(unsigned), c->stream));
         // cell edge: a little above minDist (a relative 1e-3 dwarfs the rounding of v * inv_h for coordinates up to ~10^4 cells from the origin;
-        // beyond that the margin grows with the coordinate's ulp)
+        // beyond that the margin grows with the coordinate's ulp: the coordinates of a near pair are themselves spaced at least as widely as
+        // the products, so the pair's real difference stays that much below minDist.  tests/test_merge_reference_cpu.py searches near
+        // pairs across cell faces out to cell 2^20, the power-of-two indices where the product's spacing doubles included: never two apart)
         const float h = min_dist * 1.001f + 1e-6f;
         const float inv_h = 1.0f / h;
         hipLaunchKernelGGL(merge_hash_insert_kernel, dim3(gblocks), dim3(256), 0, c->stream, recv, maxc, R, mb, inv_h, tkeys, tcnt,
@@ -1024,7 +1031,8 @@ static icpmi_status merge_greedy(icpmi_ctx* c, const float4* recv, const std::ve
                            (const unsigned*)rank_of, recv, cell_pts);
         const double lim = pd_limit(min_dist);
         // (sets too large to trust co-dispatch take the R - 1 launches of r4)
-        if (span <= (1ll << 22)) {
+        if (span <= (1ll << 22) && !per_block) {
+            if (path) *path = 1;
             unsigned* status = scratch_get<unsigned>(c, 8, (size_t)span + 2);
             if (!status) return ICPMI_ERR_HIP;
             HIP_TRY(c, hipMemsetAsync(status, 0, ((size_t)span + 2) * sizeof(unsigned), c->stream));
@@ -1034,6 +1042,7 @@ static icpmi_status merge_greedy(icpmi_ctx* c, const float4* recv, const std::ve
         } else
         for (int r = first_block; r < R; ++r) {
             if (counts[(size_t)r] == 0) continue;
+            if (path) *path = 2;
             hipLaunchKernelGGL(merge_flag_kernel, dim3((int)((counts[(size_t)r] + 255) / 256)), dim3(256), 0, c->stream, recv, maxc, r,
                                counts[(size_t)r], r == first_block ? 1 : 0, inv_h, lim, (const unsigned long long*)tkeys, (const unsigned*)tcnt, cap - 1,
                                (const float4*)cell_pts, kept, (const unsigned*)bits);
@@ -1045,6 +1054,48 @@ static icpmi_status merge_greedy(icpmi_ctx* c, const float4* recv, const std::ve
     icpmi_status s = merge_append_flagged(c, recv, span, kept, pos, c->d_merged, 0, &n_kept);
     if (s != ICPMI_OK) return s;
     *merged_n = n_kept;
+    return ICPMI_OK;
+}
+
+// Test seam (icpmi_debug_merge_blocks): merge_greedy and nothing around it, on blocks the caller hands in -- no map, no communicator, no
+// append.  Block r goes to r * stride of a buffer of stride * R points; only the real points are uploaded, the padding stays whatever the
+// allocator left there, as a gathered buffer's does.  kept_out: the flags merge_greedy compacted from (scratch 6), in input order.
+icpmi_status ops_debug_merge_blocks(icpmi_ctx* c, const float* pts4, const int64_t* counts, int n_ranks, int64_t stride, float min_dist, int mode,
+                                    float* merged_out4, int64_t capacity, int64_t* merged_n, uint8_t* kept_out, int32_t* path_out)
+{
+    *merged_n = 0; *path_out = 0;
+    std::vector<long long> cnt((size_t)n_ranks);
+    long long total = 0;
+    for (int r = 0; r < n_ranks; ++r) { cnt[(size_t)r] = counts[r]; total += counts[r]; }
+    const long long span = stride < (1ll << 31) ? (long long)stride * n_ranks : 1ll << 31;
+    if (span >= (1ll << 31)) { c->last_error = "staged_merge_allgather: gathered set too large"; return ICPMI_ERR_UNSUPPORTED; } // (merge_greedy's own, before the buffer exists)
+    DevBuf<float4> d_blocks;
+    HIP_TRY(c, d_blocks.alloc((size_t)span + 1));
+    const float4* src = reinterpret_cast<const float4*>(pts4);
+    for (int r = 0; r < n_ranks; ++r) {
+        if (cnt[(size_t)r] > 0)
+            HIP_TRY(c, hipMemcpyAsync(d_blocks.get() + (size_t)r * (size_t)stride, src, (size_t)cnt[(size_t)r] * sizeof(float4), hipMemcpyHostToDevice, c->stream));
+        src += cnt[(size_t)r];
+    }
+    if (c->d_merged.ensure(c, (size_t)total + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
+    int path = mode != 0 ? 1 : 0;
+    int64_t acc = 0;
+    const icpmi_status s = merge_greedy(c, d_blocks, cnt, stride, min_dist, &acc, &path);
+    if (s != ICPMI_OK) { (void)hipStreamSynchronize(c->stream); return s; }
+    *merged_n = acc; *path_out = path;
+    const int64_t cp = acc < capacity ? acc : capacity;
+    if (merged_out4 && cp > 0) HIP_TRY(c, hipMemcpyAsync(merged_out4, c->d_merged, (size_t)cp * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+    std::vector<unsigned> flags;
+    if (kept_out && total > 0) {
+        flags.resize((size_t)span);
+        HIP_TRY(c, hipMemcpyAsync(flags.data(), (const unsigned*)c->scratch[6].get(), (size_t)span * sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+    }
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (kept_out && total > 0) {
+        size_t o = 0;
+        for (int r = 0; r < n_ranks; ++r)
+            for (long long i = 0; i < cnt[(size_t)r]; ++i) kept_out[o++] = flags[(size_t)r * (size_t)stride + (size_t)i] ? 1 : 0;
+    }
     return ICPMI_OK;
 }
 

@@ -1660,6 +1660,31 @@ class ICPSequence:
         return ids, d2, {"cell": cell, "na": (int(info[1]), int(info[2]), int(info[3])), "tsize": int(info[4]), "queued": int(info[5]),
                          "trials": int(info[6])}
 
+    def debugMergeBlocks(self, blocks, min_dist, stride=None, mode=0, capacity=None):
+        """icpmi_debug_merge_blocks: the epoch's rank-ordered merge on `blocks` (one (n_r, 4) array per rank, empty ones included), block r
+        laid at r * stride (default: the largest count).  mode 0: the epoch's choice of kernel, 1: the per-block launches.  Returns
+        (merged (n, 4) float32, [kept (n_r,) bool per block], path); capacity (default: all) bounds the copy-out only -- merged then holds
+        what fits and the full count is returned as a fourth value."""
+        blocks = [_f32c(b, 4) for b in blocks]
+        counts = np.array([b.shape[0] for b in blocks], dtype=np.int64)
+        total = int(counts.sum())
+        if stride is None:
+            stride = int(counts.max()) if counts.size else 0
+        pts = np.concatenate(blocks) if total else np.zeros((0, 4), dtype=np.float32)
+        cap = total if capacity is None else int(capacity)
+        out = np.empty((max(cap, 1), 4), dtype=np.float32)
+        kept = np.zeros(max(total, 1), dtype=np.uint8)
+        mn, path = C.c_int64(0), C.c_int32(-1)
+        self._check(self._lib.icpmi_debug_merge_blocks(self._h, pts.ctypes.data if total else None, counts.ctypes.data if counts.size else None,
+                                                       len(blocks), int(stride), float(min_dist), int(mode), out.ctypes.data, cap, C.byref(mn),
+                                                       kept.ctypes.data, C.byref(path)))
+        ends = np.cumsum(counts)
+        kept_list = [kept[e - n:e].astype(bool) for e, n in zip(ends, counts)]
+        merged = out[:min(mn.value, cap)].copy()
+        if capacity is None:
+            return merged, kept_list, int(path.value)
+        return merged, kept_list, int(path.value), int(mn.value)
+
     def debugResidentKthD2(self):
         """icpmi_debug_resident_kth_d2: (d2 of every resident point's k-th neighbour (m,) float32, that k) as the last append-only update's
         SurfaceNormal pass remembered them; raises when they do not describe the resident map."""
