@@ -672,7 +672,7 @@ static icpmi_status reject_intensity(icpmi_ctx* h, const char* who)
     return ICPMI_ERR_UNSUPPORTED;
 }
 // ... the chains it is not defined for, then what it needs: the map's channel and the row of THIS reading (have_int_n: what the call consumed).
-// On success lc carries both (common.h: intensity_weight).
+// On success lc carries both (common.h: LoopCfg::map_gi from make_loop_cfg, read_intensity from here, where n is known).
 static icpmi_status intensity_setup(icpmi_ctx* h, const char* who, int64_t n, int64_t have_int_n, LoopCfg* lc)
 {
     if (!(h->intensity_w > 0.f)) return ICPMI_OK;
@@ -694,7 +694,7 @@ static icpmi_status intensity_setup(icpmi_ctx* h, const char* who, int64_t n, in
         h->last_error = "InvalidField: the intensity term needs the reading's intensity (icpmi_set_reading_intensity, one value per point)";
         return ICPMI_ERR_INVALID_ARG;
     }
-    lc->read_scalar = h->d_read_scalar; // (the intensity row sits n floats behind the GenericDescriptor row)
+    lc->read_intensity = h->d_read_scalar.get() + n; // (the intensity row sits n floats behind the GenericDescriptor row in the one buffer)
     return ICPMI_OK;
 }
 

@@ -255,6 +255,15 @@ struct BatchSrc { const float4* p[ICPMI_MAX_BATCH]; }; // the readings as handed
 static inline float squared_radius(float r) { return std::isinf(r) ? INFINITY : r * r; }
 static inline BatchArgs batch_of_one(int64_t n) { BatchArgs b; memset(&b, 0, sizeof b); b.nscan = 1; b.n[0] = (int)n; return b; }
 
+// What the pair-sum kernel adds per pair (loop.hip: accumulate_kernel's template parameter).  make_loop_cfg chooses it; LoopCfg::minimizer
+// beside it stays the kind of normal equations every kernel BEHIND the pair sums sees: the last four all fill the point-to-plane slots.
+enum PairModel { PAIR_IDENTITY, PAIR_POINT_TO_POINT, PAIR_POINT_TO_PLANE, PAIR_PLANE_TO_PLANE, PAIR_SYMMETRIC, PAIR_INTENSITY };
+// ... the models that read the map's normals (and fill the 27 point-to-plane slots)
+constexpr bool pair_reads_map_normals(PairModel pm)
+{
+    return pm == PAIR_POINT_TO_PLANE || pm == PAIR_PLANE_TO_PLANE || pm == PAIR_SYMMETRIC || pm == PAIR_INTENSITY;
+}
+
 // Device-side description of the ICP chain for one registration (passed by value to kernels).
 struct LoopCfg {
     int   k;
@@ -286,19 +295,14 @@ struct LoopCfg {
     int   degen;
     float degen_thr;          // |degeneracy_threshold|
     double* degen_blk;        // the handle's side block (layout below), null when off
+    // the pair sums' model and what it alone reads; each field is 0 unless pair_model owns it (loop_sig hashes the bytes: a change of model,
+    // epsilon or weight misses a cached graph)
+    int   pair_model;         // PairModel
+    float plane_eps;          // PAIR_PLANE_TO_PLANE: epsilon of the covariances C(n) = I - (1 - eps) n n^T, in (0, 1]
+    float intensity_w;        // PAIR_INTENSITY: the photometric weight 1 - lambda, in (0, 1)
+    const float4* map_gi;     // ... the map's (g.x, g.y, g.z, I) per point, in the index's order (null: no current channel)
+    const float* read_intensity; // ... the intensity row of THIS reading, caller's order (api.hip: intensity_setup)
 };
-// ICPMI_MIN_PLANE_TO_PLANE travels as a point-to-plane chain (its pair sums fill the same slots, the solve is the same) whose degen_thr, free
-// because the degeneracy-aware solve is rejected with it, carries the covariances' epsilon: > 0 picks the plane-to-plane pair sums
-static inline float plane_to_plane_eps(const LoopCfg& lc) { return (lc.minimizer == ICPMI_MIN_POINT_TO_PLANE && lc.degen == 0) ? lc.degen_thr : 0.f; }
-// ... and epsilon lives in (0, 1] (icpmi_set_plane_epsilon), so a value past 1 in that slot names the other pair model of the same path:
-// ICPMI_PLANE_MODEL_SYMMETRIC, which has no epsilon.  The slot is part of the LoopCfg that loop_sig hashes: a model change misses a cached graph.
-#define ICPMI_PLANE_SLOT_SYMMETRIC 2.f
-static inline bool plane_pair_symmetric(const LoopCfg& lc) { return plane_to_plane_eps(lc) > 1.f; }
-// ... and a NEGATIVE value names the photometric term of the point-to-plane path (icpmi_set_intensity_weight): the slot carries
-// -(1 - lambda), in (-1, 0).  That instantiation of the pair sums owns two more slots the degeneracy-aware solve and the GenericDescriptor
-// filter leave it: degen_blk (free with degen == 0) points at the map's (g.x, g.y, g.z, I) float4 per point, in the index's order, and the
-// reading's intensity row sits behind the GenericDescriptor row in the one buffer read_scalar points at: read_scalar + n, caller's order.
-static inline float intensity_weight(const LoopCfg& lc) { return (lc.minimizer == ICPMI_MIN_POINT_TO_PLANE && lc.degen == 0 && lc.degen_thr < 0.f) ? -lc.degen_thr : 0.f; }
 // slot of the chain's Trimmed / Median / VarTrimmed filter (the last of them: the one whose limit a call reports), or -1.  Upstream, a
 // chain with one throws "no outlier to filter" on an empty reading where any other throws "no point to minimize".
 static inline int quantile_slot(const LoopCfg& lc)
@@ -1631,6 +1635,107 @@ __device__ __forceinline__ float match_weight(const LoopCfg& lc, const IcpState*
         }
     }
     return w;
+}
+
+// ---------------------------------------------------------------------------------------------
+// The pair sums of the iteration: what loop.hip's accumulate_kernel and voxel.hip's voxel_pairs_kernel add per pair, and how a workgroup's
+// sums join the iteration's accumulator.  Per-pair terms in float without contraction, the weight's products and the sums in double.
+// ---------------------------------------------------------------------------------------------
+// a normal scaled to length 1; a zero or non-finite one is "no surface model" (zero: that side's covariance becomes I)
+__device__ __forceinline__ float3 unit_or_zero(float x, float y, float z)
+{
+    const float l2 = x * x + y * y + z * z;
+    const bool ok = l2 > 0.f && l2 < INFINITY;
+    const float inv = ok ? 1.f / sqrtf(l2) : 0.f;
+    return ok ? make_float3(x * inv, y * inv, z * inv) : make_float3(0.f, 0.f, 0.f);
+}
+__device__ __forceinline__ float3 cross3(float3 a, float3 b) { return make_float3(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x); }
+
+// generalized ICP: A += w G M G^T, b -= w G M d with G = J^T = [[p]x; I], M = S^-1, S = the sum of the pair's two
+// covariances (symmetric: xx xy xz yy yz zz), d = p - q.  M = n n^T would give the point-to-plane sums: G n = F.  WEIGHTED = false: weight 1, and
+// no multiplication by it.  Every group joins its sums as soon as it exists: the live floats of a pair stay few.
+template <bool WEIGHTED>
+__device__ __forceinline__ void gicp_pair_sums(double (&acc)[27], float sxx, float sxy, float sxz, float syy, float syz, float szz, float3 p, float3 d,
+                                               double dw)
+{
+    auto wt = [&](float v) { return WEIGHTED ? dw * v : (double)v; };
+    // M = adj(S) / det(S)
+    const float c00 = syy * szz - syz * syz, c01 = sxz * syz - sxy * szz, c02 = sxy * syz - sxz * syy;
+    const float c11 = sxx * szz - sxz * sxz, c12 = sxy * sxz - sxx * syz, c22 = sxx * syy - sxy * sxy;
+    const float idet = 1.f / (sxx * c00 + sxy * c01 + sxz * c02);
+    const float3 m0 = make_float3(c00 * idet, c01 * idet, c02 * idet), m1 = make_float3(m0.y, c11 * idet, c12 * idet),
+                 m2 = make_float3(m0.z, m1.z, c22 * idet);
+    acc[15] += wt(m0.x); acc[16] += wt(m0.y); acc[17] += wt(m0.z); acc[18] += wt(m1.y); acc[19] += wt(m1.z); acc[20] += wt(m2.z);
+    const float3 md = make_float3(m0.x * d.x + m0.y * d.y + m0.z * d.z, m1.x * d.x + m1.y * d.y + m1.z * d.z, m2.x * d.x + m2.y * d.y + m2.z * d.z);
+    const float3 pmd = cross3(p, md);
+    acc[21] -= wt(pmd.x); acc[22] -= wt(pmd.y); acc[23] -= wt(pmd.z); acc[24] -= wt(md.x); acc[25] -= wt(md.y); acc[26] -= wt(md.z);
+    // P M with P = [p]x: column j is p x (column j of M); row i of P M P^T is p x (row i of P M)
+    const float3 k0 = cross3(p, m0), k1 = cross3(p, m1), k2 = cross3(p, m2);
+    const float3 pm0 = make_float3(k0.x, k1.x, k2.x), pm1 = make_float3(k0.y, k1.y, k2.y), pm2 = make_float3(k0.z, k1.z, k2.z);
+    acc[3] += wt(pm0.x); acc[4] += wt(pm0.y); acc[5] += wt(pm0.z);
+    acc[8] += wt(pm1.x); acc[9] += wt(pm1.y); acc[10] += wt(pm1.z);
+    acc[12] += wt(pm2.x); acc[13] += wt(pm2.y); acc[14] += wt(pm2.z);
+    const float3 r0 = cross3(p, pm0), r1 = cross3(p, pm1), r2 = cross3(p, pm2);
+    acc[0] += wt(r0.x); acc[1] += wt(r0.y); acc[2] += wt(r0.z); acc[6] += wt(r1.y); acc[7] += wt(r1.z); acc[11] += wt(r2.z);
+}
+
+// The workgroup's sums (BT threads; acc: the NVAL values of the model, then sum w and the pair count, EXT: force2D's b, else b2d is not
+// read) join the iteration's accumulator at hists + ICPMI_S2_ACC.  wave64 shuffles, then LDS across the waves.
+// Transposed butterfly: at the step with partner lane ^ m every lane hands over the half of its values the partner keeps, so 32 values x
+// 64 lanes fold with 16+8+4+2+1+1 = 32 exchanges instead of 32 x 6.  After the five halving steps lane l holds value bitrev5(l & 31)
+// summed over its 32-lane half; the last exchange joins the halves.  Fixed pattern => deterministic sums.
+// (voxel.hip's caller.  loop.hip's accumulate_kernel keeps the same fold spelled out in its body, value for value: see there.)
+template <int BT, int NVAL, bool EXT>
+__device__ __forceinline__ void pair_sums_fold(const double (&acc)[NVAL > 0 ? NVAL : 1], double wsum, double cnt, const double* b2d, unsigned* hists)
+{
+    __shared__ double sh[BT / 64][ICPMI_NV];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    double val[ICPMI_NV];
+#pragma unroll
+    for (int i = 0; i < ICPMI_NV; ++i) val[i] = i < NVAL ? acc[i < NVAL ? i : 0] : 0.0;
+    val[27] = wsum; val[28] = cnt;
+    if constexpr (EXT) { val[29] = b2d[0]; val[30] = b2d[1]; val[31] = b2d[2]; }
+#pragma unroll
+    for (int s = 0; s < 5; ++s) {
+        const int m = 1 << s;
+        const int nkeep = 16 >> s;
+        const bool upper = (lane & m) != 0;
+#pragma unroll
+        for (int i = 0; i < nkeep; ++i) {
+            const double send = upper ? val[i] : val[i + nkeep];
+            const double keep = upper ? val[i + nkeep] : val[i];
+            val[i] = keep + __shfl_xor(send, m, 64);
+        }
+    }
+    val[0] += __shfl_xor(val[0], 32, 64);
+    if (lane < 32) {
+        const int idx = ((lane & 1) << 4) | ((lane & 2) << 2) | (lane & 4) | ((lane & 8) >> 2) | ((lane & 16) >> 4);
+        sh[wv][idx] = val[0];
+    }
+    __syncthreads();
+    if (threadIdx.x < ICPMI_NV) {
+        const int i = threadIdx.x;
+        double v = 0.0;
+        if (i < NVAL || i == 27 || i == 28 || (EXT && i > 28)) {
+            v = sh[0][i] + sh[1][i] + sh[2][i] + sh[3][i];
+#pragma unroll
+            for (int w2 = 4; w2 < BT / 64; ++w2) v += sh[w2][i]; // fixed order
+        }
+        // the workgroup's sum joins the iteration's accumulator as two fixed-point limbs (ICPMI_ACC_*): integer atomics, so the total is
+        // the same whatever order the workgroups arrive in
+        unsigned long long* out = reinterpret_cast<unsigned long long*>(hists + ICPMI_S2_ACC);
+        if (v != 0.0) {
+            if (!(fabs(v) < 0x1p77)) atomicOr(reinterpret_cast<unsigned*>(out + ICPMI_ACC_FLAG), 1u);
+            else {
+                const double hi = rint(v * 0x1p-16);
+                const double lo = v - hi * 65536.0;                 // exact: a multiple of ulp(v) below 2^15
+                const long long H = (long long)hi, Lq = __double2ll_rn(lo * 0x1p40);
+                const int cp = blockIdx.x & (ICPMI_ACC_COPIES - 1);
+                if (H) atomicAdd(out + ICPMI_ACC_IDX(cp, i, 0), (unsigned long long)H);
+                if (Lq) atomicAdd(out + ICPMI_ACC_IDX(cp, i, 1), (unsigned long long)Lq);
+            }
+        }
+    }
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -10,6 +10,7 @@
 #include "common.h"
 #include "solve.h"
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 namespace {
@@ -48,30 +49,15 @@ __host__ __device__ __forceinline__ int acc_blocks_dev(int64_t count, int cap, i
     return (int)(nb < 1 ? 1 : (nb > cap ? cap : nb));
 }
 
-// plane-to-plane: a normal scaled to length 1; a zero or non-finite one is "no surface model" (zero: that side's covariance becomes I)
-__device__ __forceinline__ float3 unit_or_zero(float x, float y, float z)
-{
-    const float l2 = x * x + y * y + z * z;
-    const bool ok = l2 > 0.f && l2 < INFINITY;
-    const float inv = ok ? 1.f / sqrtf(l2) : 0.f;
-    return ok ? make_float3(x * inv, y * inv, z * inv) : make_float3(0.f, 0.f, 0.f);
-}
 // a normal's three components (its fourth word is padding: 12 bytes requested, three registers held while the load is in flight)
 __device__ __forceinline__ float4 ld_normal(const float4* __restrict__ p)
 {
     const float3 v = *reinterpret_cast<const float3*>(p);
     return make_float4(v.x, v.y, v.z, 0.f);
 }
-__device__ __forceinline__ float3 cross3(float3 a, float3 b) { return make_float3(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x); }
 
-// the symmetric pair model of the plane-to-plane path (include/icpmi.h: ICPMI_PLANE_MODEL_SYMMETRIC): a tag of this file for accumulate_kernel's
-// MIN, next to the icpmi_minimizer values -- no minimizer of the interface (4 stays unknown there)
-constexpr int PAIR_SYMMETRIC = 16;
-// the photometric term on the point-to-plane path (icpmi_set_intensity_weight): likewise a tag of this file, launched in place of
-// <ICPMI_MIN_POINT_TO_PLANE, ...> when the weight is non-zero (common.h: intensity_weight has the slots this instantiation owns)
-constexpr int PAIR_INTENSITY = 17;
-
-template <int MIN, bool FUSED, bool EXT, int BT = 256>
+// PM: the pair model (common.h: PairModel; lc.pair_model picks the instantiation, enqueue_accumulate_solve)
+template <PairModel PM, bool FUSED, bool EXT, int BT>
 __global__ __launch_bounds__(BT) void accumulate_kernel(const float4* __restrict__ reading, BatchArgs ba, int acc_cap, LoopCfg lc,
                                                          IcpState* __restrict__ st, const float4* __restrict__ map,
                                                          const float4* __restrict__ normals,
@@ -125,13 +111,12 @@ __global__ __launch_bounds__(BT) void accumulate_kernel(const float4* __restrict
     // is two more dependent round trips, so all three are requested up front)
     constexpr int PF = BT > 256 ? 3 : 2;
     // the pair models that read the normals of BOTH clouds (plane-to-plane and the symmetric one): same gathers, same two trips
-    constexpr bool BOTH_N = MIN == ICPMI_MIN_PLANE_TO_PLANE || MIN == PAIR_SYMMETRIC;
+    constexpr bool BOTH_N = PM == PAIR_PLANE_TO_PLANE || PM == PAIR_SYMMETRIC;
     // the photometric term reads the match's (g, I) and the reading's intensity by the caller's index: the same two trips, q and the caller's
     // index with the first (TRIP1_Q: the pair models whose second trip needs them)
-    constexpr bool INTENS = MIN == PAIR_INTENSITY;
+    constexpr bool INTENS = PM == PAIR_INTENSITY;
     constexpr bool TRIP1_Q = BOTH_N || INTENS;
-    const float4* __restrict__ map_gi = INTENS ? reinterpret_cast<const float4*>(lc.degen_blk) : nullptr; // (common.h: intensity_weight)
-    const float* __restrict__ read_int = (INTENS && lc.read_scalar) ? lc.read_scalar + n : nullptr;
+    const float4* __restrict__ map_gi = INTENS ? lc.map_gi : nullptr;
     unsigned hw = hdr_load(st);
     float pd2[PF]; int ps[PF]; float4 pr[PF], pq[PF];
     int po[PF]; // plane-to-plane: the caller's index of the reading point, whose normal the second trip fetches
@@ -161,7 +146,7 @@ __global__ __launch_bounds__(BT) void accumulate_kernel(const float4* __restrict
     for (int i = 0; i < 16; ++i) T[i] = hv.f(ICPMI_HDR_W(T_iter) + i);
     // second round trip, overlapping the fine-histogram read of the selection scan: the matched normals
     // (plane-to-plane: ... and the reading's own normals, by the caller's index that arrived with the first trip)
-    constexpr bool USES_N = MIN == ICPMI_MIN_POINT_TO_PLANE || BOTH_N || INTENS;
+    constexpr bool USES_N = pair_reads_map_normals(PM);
     float4 pn[PF], prn[PF];
     float pip[PF]; // the photometric term: the reading point's intensity (prn carries the match's (g, I) there)
 #pragma unroll
@@ -171,7 +156,7 @@ __global__ __launch_bounds__(BT) void accumulate_kernel(const float4* __restrict
         if constexpr (INTENS) { // (a missing channel or row never gets here -- api.hip refuses the call; NaN would leave the geometric part)
             pn[u] = ps[u] >= 0 ? (pnm ? pnm[2 * (size_t)ps[u] + 1] : normals[ps[u]]) : make_float4(0.f, 0.f, 0.f, 0.f);
             prn[u] = (map_gi && ps[u] >= 0) ? map_gi[ps[u]] : make_float4(0.f, 0.f, 0.f, NAN);
-            pip[u] = (read_int && po[u] >= 0) ? read_int[po[u]] : NAN;
+            pip[u] = (lc.read_intensity && po[u] >= 0) ? lc.read_intensity[po[u]] : NAN;
         } else if constexpr (BOTH_N) {
             pn[u] = ps[u] >= 0 ? ld_normal(pnm ? pnm + 2 * (size_t)ps[u] + 1 : normals + ps[u]) : make_float4(0.f, 0.f, 0.f, 0.f);
             if (po[u] >= 0) prn[u] = ld_normal(read_normals + po[u]);
@@ -195,7 +180,7 @@ __global__ __launch_bounds__(BT) void accumulate_kernel(const float4* __restrict
         // ... and so is the speculative window of the k > 1 loop (its readers ran in the two kernels before this one)
         if (lc.k > 1) for (int64_t i = gtid; i < 2 * ICPMI_WIN_U64; i += stride) hists[ICPMI_S2_WIN + i] = 0;
     }
-    constexpr int NVAL = USES_N ? 27 : (MIN == ICPMI_MIN_POINT_TO_POINT ? 16 : 0);
+    constexpr int NVAL = USES_N ? 27 : (PM == PAIR_POINT_TO_POINT ? 16 : 0);
     double acc[NVAL > 0 ? NVAL : 1];
 #pragma unroll
     for (int i = 0; i < (NVAL > 0 ? NVAL : 1); ++i) acc[i] = 0.0;
@@ -223,10 +208,10 @@ __global__ __launch_bounds__(BT) void accumulate_kernel(const float4* __restrict
                                 nullptr, 0, 0.f, BOTH_N ? &rnkept : nullptr);
         if (w == 0.f) return;
         wsum += w; cnt += 1.0;
-        if (MIN == ICPMI_MIN_IDENTITY) return;
+        if (PM == PAIR_IDENTITY) return;
         const float3 p = xf_point(T, r.x, r.y, r.z, r.w);
         const float4 q = (TRIP1_Q || match_pt || (pnm && have_n)) ? qkept : (pnm ? pnm[2 * (size_t)s] : map[s]);
-        if (MIN == ICPMI_MIN_POINT_TO_POINT) {
+        if constexpr (PM == PAIR_POINT_TO_POINT) {
             const double dw = w;
             acc[0] += dw;
             acc[1] += dw * p.x; acc[2] += dw * p.y; acc[3] += dw * p.z;
@@ -237,7 +222,7 @@ __global__ __launch_bounds__(BT) void accumulate_kernel(const float4* __restrict
             for (int c = 0; c < 3; ++c)
 #pragma unroll
                 for (int rr = 0; rr < 3; ++rr) acc[7 + 3 * c + rr] += wq[rr] * pc[c];
-        } else if (MIN == ICPMI_MIN_POINT_TO_PLANE) {
+        } else if constexpr (PM == PAIR_POINT_TO_PLANE) {
             const float4 nn = have_n ? nkept : (pnm ? pnm[2 * (size_t)s + 1] : normals[s]);
             // per-pair quantities in float exactly as the oracle (and Eigen) form them
             const float F[6] = {p.y * nn.z - p.z * nn.y, p.z * nn.x - p.x * nn.z, p.x * nn.y - p.y * nn.x, nn.x, nn.y, nn.z};
@@ -256,12 +241,12 @@ __global__ __launch_bounds__(BT) void accumulate_kernel(const float4* __restrict
 #pragma unroll
                 for (int a = 0; a < 3; ++a) b2d[a] -= ((double)w * F[2 + a]) * dot2;
             }
-        } else if constexpr (MIN == PAIR_INTENSITY) {
+        } else if constexpr (PM == PAIR_INTENSITY) {
             // joint geometric + photometric point-to-plane: two rank-1 updates per pair into the point-to-plane slots,
             // A += w (lambda F_G F_G^T + (1 - lambda) F_I F_I^T), b -= w (lambda F_G r_G + (1 - lambda) F_I r_I).  The geometric terms are the
             // point-to-plane branch's, bit for bit; per-pair terms in float, the weight's products and the sums in double
             const float4 nn = nkept, gi = rnkept;
-            const float wi = -lc.degen_thr, lam = 1.f - wi; // (the slot carries -(1 - lambda) for this instantiation: common.h, intensity_weight)
+            const float wi = lc.intensity_w, lam = 1.f - wi;
             const float F[6] = {p.y * nn.z - p.z * nn.y, p.z * nn.x - p.x * nn.z, p.x * nn.y - p.y * nn.x, nn.x, nn.y, nn.z};
             const float dx = p.x - q.x, dy = p.y - q.y, dz = p.z - q.z;
             const float dot = dx * nn.x + dy * nn.y + dz * nn.z;
@@ -292,39 +277,18 @@ __global__ __launch_bounds__(BT) void accumulate_kernel(const float4* __restrict
                     acc[21 + a] -= wf * ri;
                 }
             }
-        } else if constexpr (MIN == ICPMI_MIN_PLANE_TO_PLANE) {
-            // generalized ICP with plane-regularised covariances: A += w G M G^T, b -= w G M d with G = J^T = [[p]x; I],
-            // M = (C(n_q) + C(R n_x))^-1, C(n) = I - (1 - eps) n n^T.  M = n n^T would give the point-to-plane branch above: G n = F.
+        } else if constexpr (PM == PAIR_PLANE_TO_PLANE) {
+            // generalized ICP with plane-regularised covariances (common.h: gicp_pair_sums): M = (C(n_q) + C(R n_x))^-1, C(n) = I - (1 - eps) n n^T
             const float4 nq = nkept, rn = rnkept;
-            const float g = 1.f - lc.degen_thr; // (the slot carries epsilon for this instantiation: common.h, plane_to_plane_eps)
+            const float g = 1.f - lc.plane_eps;
             const float3 uq = unit_or_zero(nq.x, nq.y, nq.z);
             const float3 up = unit_or_zero(fmaf(T[8], rn.z, fmaf(T[4], rn.y, T[0] * rn.x)), fmaf(T[9], rn.z, fmaf(T[5], rn.y, T[1] * rn.x)),
                                            fmaf(T[10], rn.z, fmaf(T[6], rn.y, T[2] * rn.x)));
             // S = C(n_q) + C(n_p), symmetric: xx xy xz yy yz zz
             const float sxx = 2.f - g * (uq.x * uq.x + up.x * up.x), syy = 2.f - g * (uq.y * uq.y + up.y * up.y), szz = 2.f - g * (uq.z * uq.z + up.z * up.z);
             const float sxy = -g * (uq.x * uq.y + up.x * up.y), sxz = -g * (uq.x * uq.z + up.x * up.z), syz = -g * (uq.y * uq.z + up.y * up.z);
-            // M = adj(S) / det(S)
-            const float c00 = syy * szz - syz * syz, c01 = sxz * syz - sxy * szz, c02 = sxy * syz - sxz * syy;
-            const float c11 = sxx * szz - sxz * sxz, c12 = sxy * sxz - sxx * syz, c22 = sxx * syy - sxy * sxy;
-            const float idet = 1.f / (sxx * c00 + sxy * c01 + sxz * c02);
-            const float3 m0 = make_float3(c00 * idet, c01 * idet, c02 * idet), m1 = make_float3(m0.y, c11 * idet, c12 * idet),
-                         m2 = make_float3(m0.z, m1.z, c22 * idet);
-            // every group joins its sums as soon as it exists (the live floats of a pair stay few: three pairs are in flight at knn > 1)
-            const double dw = w;
-            acc[15] += dw * m0.x; acc[16] += dw * m0.y; acc[17] += dw * m0.z; acc[18] += dw * m1.y; acc[19] += dw * m1.z; acc[20] += dw * m2.z;
-            const float dx = p.x - q.x, dy = p.y - q.y, dz = p.z - q.z;
-            const float3 md = make_float3(m0.x * dx + m0.y * dy + m0.z * dz, m1.x * dx + m1.y * dy + m1.z * dz, m2.x * dx + m2.y * dy + m2.z * dz);
-            const float3 pmd = cross3(p, md);
-            acc[21] -= dw * pmd.x; acc[22] -= dw * pmd.y; acc[23] -= dw * pmd.z; acc[24] -= dw * md.x; acc[25] -= dw * md.y; acc[26] -= dw * md.z;
-            // P M with P = [p]x: column j is p x (column j of M); row i of P M P^T is p x (row i of P M)
-            const float3 k0 = cross3(p, m0), k1 = cross3(p, m1), k2 = cross3(p, m2);
-            const float3 pm0 = make_float3(k0.x, k1.x, k2.x), pm1 = make_float3(k0.y, k1.y, k2.y), pm2 = make_float3(k0.z, k1.z, k2.z);
-            acc[3] += dw * pm0.x; acc[4] += dw * pm0.y; acc[5] += dw * pm0.z;
-            acc[8] += dw * pm1.x; acc[9] += dw * pm1.y; acc[10] += dw * pm1.z;
-            acc[12] += dw * pm2.x; acc[13] += dw * pm2.y; acc[14] += dw * pm2.z;
-            const float3 r0 = cross3(p, pm0), r1 = cross3(p, pm1), r2 = cross3(p, pm2);
-            acc[0] += dw * r0.x; acc[1] += dw * r0.y; acc[2] += dw * r0.z; acc[6] += dw * r1.y; acc[7] += dw * r1.z; acc[11] += dw * r2.z;
-        } else if constexpr (MIN == PAIR_SYMMETRIC) {
+            gicp_pair_sums<true>(acc, sxx, sxy, sxz, syy, syz, szz, p, make_float3(p.x - q.x, p.y - q.y, p.z - q.z), (double)w);
+        } else if constexpr (PM == PAIR_SYMMETRIC) {
             // symmetric point-to-plane in its rotated-normals form (Rusinkiewicz 2019): the point-to-plane branch above with the
             // pair normal n_s = (|c| u_q + c u_p) / 2, c = u_q . u_p -- continuous in both normals, and the sign of either cancels bit for bit
             const float4 nq = nkept, rn = rnkept;
@@ -367,14 +331,16 @@ __global__ __launch_bounds__(BT) void accumulate_kernel(const float4* __restrict
             const float4 r = reading[qi], q = match_pt ? match_pt[e] : (pnm ? pnm[2 * (size_t)s] : map[s]);
             const float4 nq = pnm ? pnm[2 * (size_t)s + 1] : normals[s];
             const float4 gi = map_gi ? map_gi[s] : make_float4(0.f, 0.f, 0.f, NAN);
-            pair(e, d2, s, r, q, nq, true, gi, oi, read_int ? read_int[oi] : NAN);
+            pair(e, d2, s, r, q, nq, true, gi, oi, lc.read_intensity ? lc.read_intensity[oi] : NAN);
         }
     } else {
         for (int64_t e = e_first + PF * estep; e < e_end; e += estep)
             pair(e, d2a[e], sidx[e], reading[(int)(e / lc.k)], match_pt ? match_pt[e] : make_float4(0.f, 0.f, 0.f, 0.f),
                  make_float4(0.f, 0.f, 0.f, 0.f), false, make_float4(0.f, 0.f, 0.f, 0.f), 0, 0.f);
     }
-    // ---- workgroup reduction: wave64 shuffles, then LDS across the 4 waves ----
+    // ---- workgroup reduction: wave64 shuffles, then LDS across the waves ----
+    // (common.h: pair_sums_fold is this fold as a function, for voxel.hip.  Here it stays spelled out, and so do the rank-1 updates above: the EXT
+    // instantiations at 1024 threads sit at the 128-VGPR cap, where the inlined helpers order the same operations differently and spill more)
     // Transposed butterfly: at the step with partner lane ^ m every lane hands over the half of its
     // values the partner keeps, so 32 values x 64 lanes fold with 16+8+4+2+1+1 = 32 exchanges instead
     // of 32 x 6.  After the five halving steps lane l holds value bitrev5(l & 31) summed over its
@@ -578,13 +544,16 @@ LoopCfg make_loop_cfg(const icpmi_ctx* c, int fixed_iterations)
         lc.degen_thr = fabsf(cfg.degeneracy_threshold);
         lc.degen_blk = c->d_degen.get();
     }
-    // the photometric term of the point-to-plane path (common.h: intensity_weight): its weight and the map's (g, I) array in the two slots the
-    // degeneracy-aware solve leaves free (api.hip rejects the combination) -- both part of the LoopCfg that loop_sig hashes
-    if (c->intensity_w > 0.f && cfg.minimizer == ICPMI_MIN_POINT_TO_PLANE && lc.degen == 0) {
-        lc.degen_thr = -c->intensity_w;
-        lc.degen_blk = map_intensity_ready(c) ? reinterpret_cast<double*>(c->d_map_gi.get()) : nullptr;
-    }
-    if (gicp) lc.degen_thr = c->plane_model == ICPMI_PLANE_MODEL_SYMMETRIC ? ICPMI_PLANE_SLOT_SYMMETRIC : c->plane_eps; // (degen stays 0: validate_config rejects the combination; common.h: plane_to_plane_eps)
+    // THE place that chooses the pair sums' model; the fields a model owns are set for it alone (the others stay 0 from the memset)
+    if (gicp && c->plane_model == ICPMI_PLANE_MODEL_SYMMETRIC) lc.pair_model = PAIR_SYMMETRIC;
+    else if (gicp) {
+        lc.pair_model = PAIR_PLANE_TO_PLANE;
+        lc.plane_eps = c->plane_eps;
+    } else if (c->intensity_w > 0.f && cfg.minimizer == ICPMI_MIN_POINT_TO_PLANE && lc.degen == 0) { // (api.hip refuses the term with the degeneracy-aware solve)
+        lc.pair_model = PAIR_INTENSITY;
+        lc.intensity_w = c->intensity_w;
+        lc.map_gi = map_intensity_ready(c) ? c->d_map_gi.get() : nullptr; // (the reading's row: api.hip, intensity_setup)
+    } else lc.pair_model = cfg.minimizer == ICPMI_MIN_POINT_TO_PLANE ? PAIR_POINT_TO_PLANE : (cfg.minimizer == ICPMI_MIN_POINT_TO_POINT ? PAIR_POINT_TO_POINT : PAIR_IDENTITY);
     return lc;
 }
 
@@ -989,32 +958,32 @@ icpmi_status ensure_loop_buffers(icpmi_ctx* c, int64_t n, const LoopCfg& lc, int
     return selection_reserve(c, lc, n * lc.k);
 }
 
-template <int MIN, bool FUSED, bool EXT>
-static void launch_accumulate_ext(icpmi_ctx* c, const LoopCfg& lc, int nb, int slot, const BatchArgs& ba, bool sorted);
-
-template <int MIN, bool FUSED>
+// The pair sums of model PM on the stream.  THE place that resolves the kernel's other three variants: FUSED (slot >= 0: the chain's single
+// quantile filter, whose last selection level the kernel scans itself), EXT (a GenericDescriptor / Robust filter or force2D: rare, its own
+// instantiation keeps the common kernels as they were) and the workgroup size (acc_threads).
+// sorted: the loop state is in query order (NnOutcome::out_sorted; k = 1: with the matched points, see nn1_wg_kernel; k > 1: ids and d2)
+template <PairModel PM>
 static void launch_accumulate(icpmi_ctx* c, const LoopCfg& lc, int nb, int slot, const BatchArgs& ba, bool sorted)
 {
-    // EXT: the chain holds a GenericDescriptor / Robust filter (rare): its own instantiation keeps the common kernels as they were
-    if (lc.ext) launch_accumulate_ext<MIN, FUSED, true>(c, lc, nb, slot, ba, sorted);
-    else launch_accumulate_ext<MIN, FUSED, false>(c, lc, nb, slot, ba, sorted);
-}
-
-// sorted: the loop state is in query order (NnOutcome::out_sorted; k = 1: with the matched points, see nn1_wg_kernel; k > 1: ids and d2)
-template <int MIN, bool FUSED, bool EXT>
-static void launch_accumulate_ext(icpmi_ctx* c, const LoopCfg& lc, int nb, int slot, const BatchArgs& ba, bool sorted)
-{
-    const PairView v = pair_view(c, lc, sorted); // (EXT == (lc.ext != 0): launch_accumulate; match_pt is null for k > 1)
+    const PairView v = pair_view(c, lc, sorted); // (match_pt is null for k > 1)
     const int is_med = slot >= 0 && lc.out_type[slot] == ICPMI_OUT_MEDIANDIST;
     const float factor = slot >= 0 ? lc.out_param[slot] : 0.f;
-    // k > 1, point-to-plane: matched point and its normal side by side (map_build.hip: pn_kernel)
-    const float4* pnm = (lc.k > 1 && (MIN == ICPMI_MIN_POINT_TO_PLANE || MIN == ICPMI_MIN_PLANE_TO_PLANE || MIN == PAIR_SYMMETRIC || MIN == PAIR_INTENSITY) && c->has_normals && c->d_map_pn) ? c->d_map_pn.get() : nullptr;
-    if (lc.k > 1)
-        hipLaunchKernelGGL((accumulate_kernel<MIN, FUSED, EXT, 1024>), dim3(nb, ba.nscan), dim3(1024), 0, c->stream, v.reading, ba, acc_cap(), lc, c->d_state,
-                           v.map, v.ref_normals, v.read_normals, v.sidx, v.d2, c->d_selhist, slot, is_med, factor, v.match_pt, v.qindex, v.ref_scalar, pnm);
-    else
-        hipLaunchKernelGGL((accumulate_kernel<MIN, FUSED, EXT>), dim3(nb, ba.nscan), dim3(256), 0, c->stream, v.reading, ba, acc_cap(), lc, c->d_state,
-                           v.map, v.ref_normals, v.read_normals, v.sidx, v.d2, c->d_selhist, slot, is_med, factor, v.match_pt, v.qindex, v.ref_scalar, pnm);
+    // k > 1, a model that reads the map's normals: matched point and its normal side by side (map_build.hip: pn_kernel)
+    const float4* pnm = (lc.k > 1 && pair_reads_map_normals(PM) && c->has_normals && c->d_map_pn) ? c->d_map_pn.get() : nullptr;
+    const auto launch = [&](auto fused, auto ext, auto bt) {
+        hipLaunchKernelGGL((accumulate_kernel<PM, fused.value, ext.value, bt.value>), dim3(nb, ba.nscan), dim3(bt.value), 0, c->stream, v.reading, ba, acc_cap(), lc,
+                           c->d_state, v.map, v.ref_normals, v.read_normals, v.sidx, v.d2, c->d_selhist, slot, is_med, factor, v.match_pt, v.qindex,
+                           v.ref_scalar, pnm);
+    };
+    const auto sized = [&](auto fused, auto ext) {
+        if (acc_threads(lc.k) == 1024) launch(fused, ext, std::integral_constant<int, 1024>{});
+        else launch(fused, ext, std::integral_constant<int, 256>{});
+    };
+    const bool fused = slot >= 0, ext = lc.ext != 0;
+    if (fused && ext) sized(std::true_type{}, std::true_type{});
+    else if (fused) sized(std::true_type{}, std::false_type{});
+    else if (ext) sized(std::false_type{}, std::true_type{});
+    else sized(std::false_type{}, std::false_type{});
 }
 
 // publish = false: this solve leaves the progress word alone (an iteration inside a fixed-count graph: see loop_run)
@@ -1024,28 +993,16 @@ static void enqueue_accumulate_solve(icpmi_ctx* c, int64_t n, const LoopCfg& lc,
     const int64_t count = n * lc.k;
     const int nb = acc_blocks(count, acc_threads(lc.k));
     const int slot = fused_filter_slot(lc);
-    const bool fused = slot >= 0;
     // (r1: letting the last pair-sum workgroup solve -- ticket + device fences -- measured +3.5 us per
     // iteration against this separate 1-workgroup launch, and dragged the solver's registers and scratch
     // into the pair-sum kernel: removed.)
-    if (plane_pair_symmetric(lc)) { // (the other pair model of that path: common.h)
-        if (fused) launch_accumulate<PAIR_SYMMETRIC, true>(c, lc, nb, slot, ba, nn.out_sorted);
-        else launch_accumulate<PAIR_SYMMETRIC, false>(c, lc, nb, slot, ba, nn.out_sorted);
-    } else if (plane_to_plane_eps(lc) > 0.f) { // (its own instantiation of the pair sums; the solve below reads lc.minimizer: point-to-plane)
-        if (fused) launch_accumulate<ICPMI_MIN_PLANE_TO_PLANE, true>(c, lc, nb, slot, ba, nn.out_sorted);
-        else launch_accumulate<ICPMI_MIN_PLANE_TO_PLANE, false>(c, lc, nb, slot, ba, nn.out_sorted);
-    } else if (intensity_weight(lc) > 0.f) { // (point-to-plane with the photometric term: likewise its own instantiation, the same solve)
-        if (fused) launch_accumulate<PAIR_INTENSITY, true>(c, lc, nb, slot, ba, nn.out_sorted);
-        else launch_accumulate<PAIR_INTENSITY, false>(c, lc, nb, slot, ba, nn.out_sorted);
-    } else if (lc.minimizer == ICPMI_MIN_POINT_TO_PLANE) {
-        if (fused) launch_accumulate<ICPMI_MIN_POINT_TO_PLANE, true>(c, lc, nb, slot, ba, nn.out_sorted);
-        else launch_accumulate<ICPMI_MIN_POINT_TO_PLANE, false>(c, lc, nb, slot, ba, nn.out_sorted);
-    } else if (lc.minimizer == ICPMI_MIN_POINT_TO_POINT) {
-        if (fused) launch_accumulate<ICPMI_MIN_POINT_TO_POINT, true>(c, lc, nb, slot, ba, nn.out_sorted);
-        else launch_accumulate<ICPMI_MIN_POINT_TO_POINT, false>(c, lc, nb, slot, ba, nn.out_sorted);
-    } else {
-        if (fused) launch_accumulate<ICPMI_MIN_IDENTITY, true>(c, lc, nb, slot, ba, nn.out_sorted);
-        else launch_accumulate<ICPMI_MIN_IDENTITY, false>(c, lc, nb, slot, ba, nn.out_sorted);
+    switch (lc.pair_model) { // (the solve below reads lc.minimizer: point-to-plane for the last four)
+    case PAIR_SYMMETRIC: launch_accumulate<PAIR_SYMMETRIC>(c, lc, nb, slot, ba, nn.out_sorted); break;
+    case PAIR_PLANE_TO_PLANE: launch_accumulate<PAIR_PLANE_TO_PLANE>(c, lc, nb, slot, ba, nn.out_sorted); break;
+    case PAIR_INTENSITY: launch_accumulate<PAIR_INTENSITY>(c, lc, nb, slot, ba, nn.out_sorted); break;
+    case PAIR_POINT_TO_PLANE: launch_accumulate<PAIR_POINT_TO_PLANE>(c, lc, nb, slot, ba, nn.out_sorted); break;
+    case PAIR_POINT_TO_POINT: launch_accumulate<PAIR_POINT_TO_POINT>(c, lc, nb, slot, ba, nn.out_sorted); break;
+    default: launch_accumulate<PAIR_IDENTITY>(c, lc, nb, slot, ba, nn.out_sorted); break;
     }
     if (lc.degen) // (a single registration: chain_takes_batch keeps such a handle out of the batched loop)
         hipLaunchKernelGGL(solve_kernel<true>, dim3(ba.nscan), dim3(256), 0, c->stream, c->d_state, c->d_selhist, 1, lc, d_Tstep, d_sums,
@@ -1056,10 +1013,10 @@ static void enqueue_accumulate_solve(icpmi_ctx* c, int64_t n, const LoopCfg& lc,
 }
 
 // the iteration of a VoxelMatcher handle (voxel_path; a single registration): voxel_pairs_kernel fills the point-to-plane slots of the
-// accumulators, the solve reads them as it reads plane-to-plane's (lc carries epsilon in degen_thr: common.h, plane_to_plane_eps)
+// accumulators, the solve reads them as it reads plane-to-plane's (lc.plane_eps: the same epsilon)
 static void enqueue_voxel_solve(icpmi_ctx* c, int64_t n, const LoopCfg& lc, float* d_Tstep, double* d_sums, bool publish)
 {
-    voxel_enqueue_pairs(c, n, acc_blocks(n), plane_to_plane_eps(lc));
+    voxel_enqueue_pairs(c, n, acc_blocks(n), lc.plane_eps);
     hipLaunchKernelGGL(solve_kernel<false>, dim3(1), dim3(256), 0, c->stream, c->d_state, c->d_selhist, 1, lc, d_Tstep, d_sums,
                        publish ? c->d_progress : (unsigned*)nullptr, c->d_state_mirror);
 }

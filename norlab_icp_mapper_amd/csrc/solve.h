@@ -465,15 +465,16 @@ __device__ __noinline__ void degen_decompose(const double* tot, int four_dof, fl
     }
 }
 
-// step 5: the step in the span of the non-degenerate directions, x = (omega, t) rounded to float once
-__device__ __noinline__ void solve_degenerate(const double* tot, const float* T_iter, const LoopCfg& lc, float* x)
+// step 5: the step in the span of the non-degenerate directions, x = (omega, t) rounded to float once.  blk, force_4dof, thr: LoopCfg's
+// degen_blk, force_4dof and degen_thr (by value: a reference to the chain would pin the kernel's whole LoopCfg argument in scratch)
+__device__ __noinline__ void solve_degenerate(const double* tot, const float* T_iter, const double* blk, int force_4dof, float thr, float* x)
 {
     __shared__ DegenSys S;
     __shared__ double y[6];
-    degen_pivot(T_iter, lc.degen_blk + ICPMI_DG_C0, S.c);
-    S.L = lc.degen_blk[ICPMI_DG_C0 + 3];
-    degen_decompose(tot, lc.force_4dof, lc.degen_thr, &S);
-    const int n = S.n, o = lc.force_4dof ? 2 : 0;
+    degen_pivot(T_iter, blk + ICPMI_DG_C0, S.c);
+    S.L = blk[ICPMI_DG_C0 + 3];
+    degen_decompose(tot, force_4dof, thr, &S);
+    const int n = S.n, o = force_4dof ? 2 : 0;
     for (int i = 0; i < 6; ++i) y[i] = 0.0;
     for (int e = 0; e < n; ++e) {
         if (S.deg[e]) continue;
@@ -635,7 +636,7 @@ __device__ void solve_serial(IcpState* st, const double* tot, const LoopCfg& lc,
         if ((lc.force_2d || lc.force_4dof) && !constrain) fill_Ab();
         if (constrain) {
             // the step in the span of the informative directions, from the double sums (6-DOF and force4DOF alike)
-            if constexpr (DEGEN) solve_degenerate(tot, st->T_iter, lc, x);
+            if constexpr (DEGEN) solve_degenerate(tot, st->T_iter, lc.degen_blk, lc.force_4dof, lc.degen_thr, x);
         } else if (lc.force_2d) {
             // force2D: F = [x ny - y nx; nx; ny] -- rows 2..4 of the 6-DOF F --, b from the 2-D residual (tot[29..31]); x = (yaw, tx, ty)
             __shared__ float A3[9], b3[3], x3[3];

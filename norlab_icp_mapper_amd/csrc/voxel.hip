@@ -84,16 +84,6 @@ __global__ __launch_bounds__(256) void vox_start_kernel(const unsigned* __restri
     if (i == m - 1) vstart[pos[i] + head[i]] = (unsigned)m;
 }
 
-// a normal scaled to length 1; a zero or non-finite one is "no surface model" (loop.hip's unit_or_zero, kept as a copy: that file's kernels
-// stay instruction for instruction what they were)
-__device__ __forceinline__ float3 vox_unit_or_zero(float x, float y, float z)
-{
-    const float l2 = x * x + y * y + z * z;
-    const bool ok = l2 > 0.f && l2 < INFINITY;
-    const float inv = ok ? 1.f / sqrtf(l2) : 0.f;
-    return ok ? make_float3(x * inv, y * inv, z * inv) : make_float3(0.f, 0.f, 0.f);
-}
-
 // One wave per voxel: lane l adds the members l, l + 64, ... of the run in that order, the 64 lane sums fold in a fixed butterfly; all in
 // double, rounded once.  The order is a function of the run alone -- the same bits on every build.
 __global__ __launch_bounds__(256) void vox_reduce_kernel(const unsigned long long* __restrict__ skeys, const unsigned* __restrict__ svals,
@@ -110,7 +100,7 @@ __global__ __launch_bounds__(256) void vox_reduce_kernel(const unsigned long lon
         const unsigned s = svals[i];
         const float4 p = pts[s];
         const float3 nr = *reinterpret_cast<const float3*>(normals + s);
-        const float3 u = vox_unit_or_zero(nr.x, nr.y, nr.z);
+        const float3 u = unit_or_zero(nr.x, nr.y, nr.z);
         a[0] += (double)p.x; a[1] += (double)p.y; a[2] += (double)p.z;
         a[3] += (double)u.x * (double)u.x; a[4] += (double)u.x * (double)u.y; a[5] += (double)u.x * (double)u.z;
         a[6] += (double)u.y * (double)u.y; a[7] += (double)u.y * (double)u.z; a[8] += (double)u.z * (double)u.z;
@@ -187,12 +177,9 @@ __global__ __launch_bounds__(256) void vox_lookup_bsearch_kernel(const float4* _
 }
 
 // ---- the pair sums ------------------------------------------------------------------------------
-__device__ __forceinline__ float3 vcross3(float3 a, float3 b) { return make_float3(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x); }
-
 // Per reading point: p = T_iter x, the voxel p falls into (none: no pair), q = mu, M = (C_v + C(u_p))^-1 with C_v = I - (1 - eps) N and
-// u_p = unit_or_zero(R n_x); then the sums of DESIGN.md 4.15 with weight 1.  Per-pair terms in float without contraction, sums in double.
-// The reduction (transposed butterfly, LDS across the four waves, two fixed-point limbs per value) is accumulate_kernel's tail, kept here
-// as a COPY: sharing it through common.h would have to leave loop.hip's kernels instruction for instruction the parent's.
+// u_p = unit_or_zero(R n_x); then the sums of DESIGN.md 4.15 with weight 1 (common.h: gicp_pair_sums) and accumulate_kernel's workgroup fold
+// as a function (common.h: pair_sums_fold).
 __global__ __launch_bounds__(256) void voxel_pairs_kernel(const float4* __restrict__ reading, const float4* __restrict__ read_normals, int n,
                                                           IcpState* __restrict__ st, const uint4* __restrict__ tab, unsigned mask, float size, float eps,
                                                           unsigned* __restrict__ hists)
@@ -230,31 +217,13 @@ __global__ __launch_bounds__(256) void voxel_pairs_kernel(const float4* __restri
         VoxHit h;
         if (!vox_key(p.x, p.y, p.z, size, &key) || !vox_probe(tab, mask, key, &h)) return;
         cnt += 1.0;
-        const float3 up = vox_unit_or_zero(fmaf(T[8], rn.z, fmaf(T[4], rn.y, T[0] * rn.x)), fmaf(T[9], rn.z, fmaf(T[5], rn.y, T[1] * rn.x)),
-                                           fmaf(T[10], rn.z, fmaf(T[6], rn.y, T[2] * rn.x)));
+        const float3 up = unit_or_zero(fmaf(T[8], rn.z, fmaf(T[4], rn.y, T[0] * rn.x)), fmaf(T[9], rn.z, fmaf(T[5], rn.y, T[1] * rn.x)),
+                                       fmaf(T[10], rn.z, fmaf(T[6], rn.y, T[2] * rn.x)));
         const float nxx = h.a.w, nxy = h.b.x, nxz = h.b.y, nyy = h.b.z, nyz = h.b.w, nzz = h.c.x;
         // S = C_v + C(u_p) = 2 I - (1 - eps)(N + u_p u_p^T), symmetric: xx xy xz yy yz zz
         const float sxx = 2.f - g * (nxx + up.x * up.x), syy = 2.f - g * (nyy + up.y * up.y), szz = 2.f - g * (nzz + up.z * up.z);
         const float sxy = -g * (nxy + up.x * up.y), sxz = -g * (nxz + up.x * up.z), syz = -g * (nyz + up.y * up.z);
-        // M = adj(S) / det(S)
-        const float c00 = syy * szz - syz * syz, c01 = sxz * syz - sxy * szz, c02 = sxy * syz - sxz * syy;
-        const float c11 = sxx * szz - sxz * sxz, c12 = sxy * sxz - sxx * syz, c22 = sxx * syy - sxy * sxy;
-        const float idet = 1.f / (sxx * c00 + sxy * c01 + sxz * c02);
-        const float3 m0 = make_float3(c00 * idet, c01 * idet, c02 * idet), m1 = make_float3(m0.y, c11 * idet, c12 * idet),
-                     m2 = make_float3(m0.z, m1.z, c22 * idet);
-        acc[15] += (double)m0.x; acc[16] += (double)m0.y; acc[17] += (double)m0.z; acc[18] += (double)m1.y; acc[19] += (double)m1.z; acc[20] += (double)m2.z;
-        const float dx = p.x - h.a.x, dy = p.y - h.a.y, dz = p.z - h.a.z;
-        const float3 md = make_float3(m0.x * dx + m0.y * dy + m0.z * dz, m1.x * dx + m1.y * dy + m1.z * dz, m2.x * dx + m2.y * dy + m2.z * dz);
-        const float3 pmd = vcross3(p, md);
-        acc[21] -= (double)pmd.x; acc[22] -= (double)pmd.y; acc[23] -= (double)pmd.z; acc[24] -= (double)md.x; acc[25] -= (double)md.y; acc[26] -= (double)md.z;
-        // P M with P = [p]x: column j is p x (column j of M); row i of P M P^T is p x (row i of P M)
-        const float3 k0 = vcross3(p, m0), k1 = vcross3(p, m1), k2 = vcross3(p, m2);
-        const float3 pm0 = make_float3(k0.x, k1.x, k2.x), pm1 = make_float3(k0.y, k1.y, k2.y), pm2 = make_float3(k0.z, k1.z, k2.z);
-        acc[3] += (double)pm0.x; acc[4] += (double)pm0.y; acc[5] += (double)pm0.z;
-        acc[8] += (double)pm1.x; acc[9] += (double)pm1.y; acc[10] += (double)pm1.z;
-        acc[12] += (double)pm2.x; acc[13] += (double)pm2.y; acc[14] += (double)pm2.z;
-        const float3 r0 = vcross3(p, pm0), r1 = vcross3(p, pm1), r2 = vcross3(p, pm2);
-        acc[0] += (double)r0.x; acc[1] += (double)r0.y; acc[2] += (double)r0.z; acc[6] += (double)r1.y; acc[7] += (double)r1.z; acc[11] += (double)r2.z;
+        gicp_pair_sums<false>(acc, sxx, sxy, sxz, syy, syz, szz, p, make_float3(p.x - h.a.x, p.y - h.a.y, p.z - h.a.z), 1.0);
     };
 #pragma unroll
     for (int u = 0; u < PF; ++u)
@@ -262,48 +231,7 @@ __global__ __launch_bounds__(256) void voxel_pairs_kernel(const float4* __restri
     for (int64_t e = e0 + PF * stride; e < n; e += stride)
         pair(reading[e], read_normals ? *reinterpret_cast<const float3*>(read_normals + e) : make_float3(0.f, 0.f, 0.f));
 
-    // ---- workgroup reduction: accumulate_kernel's, value for value (32 values x 64 lanes fold with 32 exchanges; fixed pattern) ----
-    __shared__ double sh[4][ICPMI_NV];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    double val[ICPMI_NV];
-#pragma unroll
-    for (int i = 0; i < ICPMI_NV; ++i) val[i] = i < 27 ? acc[i < 27 ? i : 0] : 0.0;
-    val[27] = cnt; val[28] = cnt; // (weight 1 per pair: sum w = the pair count)
-#pragma unroll
-    for (int s = 0; s < 5; ++s) {
-        const int m = 1 << s;
-        const int nkeep = 16 >> s;
-        const bool upper = (lane & m) != 0;
-#pragma unroll
-        for (int i = 0; i < nkeep; ++i) {
-            const double send = upper ? val[i] : val[i + nkeep];
-            const double keep = upper ? val[i + nkeep] : val[i];
-            val[i] = keep + __shfl_xor(send, m, 64);
-        }
-    }
-    val[0] += __shfl_xor(val[0], 32, 64);
-    if (lane < 32) {
-        const int idx = ((lane & 1) << 4) | ((lane & 2) << 2) | (lane & 4) | ((lane & 8) >> 2) | ((lane & 16) >> 4);
-        sh[wv][idx] = val[0];
-    }
-    __syncthreads();
-    if (threadIdx.x < ICPMI_NV) {
-        const int i = threadIdx.x;
-        double v = 0.0;
-        if (i < 29) v = sh[0][i] + sh[1][i] + sh[2][i] + sh[3][i]; // fixed order
-        unsigned long long* out = reinterpret_cast<unsigned long long*>(hists + ICPMI_S2_ACC);
-        if (v != 0.0) {
-            if (!(fabs(v) < 0x1p77)) atomicOr(reinterpret_cast<unsigned*>(out + ICPMI_ACC_FLAG), 1u);
-            else {
-                const double hi = rint(v * 0x1p-16);
-                const double lo = v - hi * 65536.0;                 // exact: a multiple of ulp(v) below 2^15
-                const long long H = (long long)hi, Lq = __double2ll_rn(lo * 0x1p40);
-                const int cp = blockIdx.x & (ICPMI_ACC_COPIES - 1);
-                if (H) atomicAdd(out + ICPMI_ACC_IDX(cp, i, 0), (unsigned long long)H);
-                if (Lq) atomicAdd(out + ICPMI_ACC_IDX(cp, i, 1), (unsigned long long)Lq);
-            }
-        }
-    }
+    pair_sums_fold<256, 27, false>(acc, cnt, cnt, nullptr, hists); // (weight 1 per pair: sum w = the pair count)
 }
 
 // the HIP events of a timed diagnostic: created together, destroyed on every way out of the call
