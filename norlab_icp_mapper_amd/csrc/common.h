@@ -83,20 +83,85 @@
 // launches fetches the same 20.6 MB past the L2 as the first), so there is no map slice for these streams to push out between launches;
 // inside a launch the hint changed nothing measurable.  Kept as a switch; plain loads / stores by default.
 #ifdef __HIPCC__
+// ---- exchanges between the lanes of a wave, in registers.  PRECONDITION of everything in this block: every lane of the wave is active at
+// the call (a DPP / permlane read of an inactive lane does not give that lane's value) ----
+// inclusive prefix sum over the 64 lanes of a wave (DPP: shifts within rows of 16 lanes, then the row totals broadcast into the following
+// rows)
+__device__ __forceinline__ unsigned wave_incl_scan(unsigned v)
+{
+    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false); // row_shr:1
+    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false); // row_shr:2
+    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, false); // row_shr:4
+    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, false); // row_shr:8
+    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false); // row_bcast:15 -> rows 1, 3
+    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false); // row_bcast:31 -> rows 2, 3
+    return v;
+}
+// value of lane (lane ^ J), without the LDS crossbar: DPP quad permutes / row shifts / row rotate inside a row of 16 lanes, gfx950's
+// v_permlane16_swap / v_permlane32_swap across rows (a sort written with __shfl_xor is 42 ds_bpermute_b32 round trips, one behind the other)
+template <int J>
+__device__ __forceinline__ unsigned lane_xor(unsigned v)
+{
+    static_assert(J == 1 || J == 2 || J == 4 || J == 8 || J == 16 || J == 32, "one bit of the lane index");
+    const int x = (int)v;
+    if constexpr (J == 1) return (unsigned)__builtin_amdgcn_update_dpp(x, x, 0xB1, 0xF, 0xF, false);      // quad_perm [1, 0, 3, 2]
+    else if constexpr (J == 2) return (unsigned)__builtin_amdgcn_update_dpp(x, x, 0x4E, 0xF, 0xF, false); // quad_perm [2, 3, 0, 1]
+    else if constexpr (J == 4) {
+        const int t = __builtin_amdgcn_update_dpp(x, x, 0x104, 0xF, 0x5, false);                            // row_shl:4 into banks 0, 2
+        return (unsigned)__builtin_amdgcn_update_dpp(t, x, 0x114, 0xF, 0xA, false);                         // row_shr:4 into banks 1, 3
+    } else if constexpr (J == 8) return (unsigned)__builtin_amdgcn_update_dpp(x, x, 0x128, 0xF, 0xF, false); // row_ror:8
+    else if constexpr (J == 16) {
+        const auto r = __builtin_amdgcn_permlane16_swap(v, v, false, false); // r[0]: odd rows <- even rows; r[1]: even rows <- odd rows
+        return (threadIdx.x & 16) ? r[0] : r[1];
+    } else {
+        const auto r = __builtin_amdgcn_permlane32_swap(v, v, false, false);
+        return (threadIdx.x & 32) ? r[0] : r[1];
+    }
+}
+template <int J>
+__device__ __forceinline__ unsigned long long lane_xor64(unsigned long long v)
+{
+    return ((unsigned long long)lane_xor<J>((unsigned)(v >> 32)) << 32) | (unsigned long long)lane_xor<J>((unsigned)v);
+}
+template <int J> // a double travels as its two 32-bit halves: the bits arrive as they left
+__device__ __forceinline__ double lane_xor(double v)
+{
+    return __longlong_as_double((long long)lane_xor64<J>((unsigned long long)__double_as_longlong(v)));
+}
+// the same with the partner's bit as a value: for unrolled loops over m = 1, 2, .. 32 (m is a constant in every unrolled body, and only
+// that body's exchange is left of the switch)
+__device__ __forceinline__ double lane_xor_bit(double v, int m)
+{
+    switch (m) {
+    case 1: return lane_xor<1>(v);
+    case 2: return lane_xor<2>(v);
+    case 4: return lane_xor<4>(v);
+    case 8: return lane_xor<8>(v);
+    case 16: return lane_xor<16>(v);
+    default: return lane_xor<32>(v);
+    }
+}
+
 // Rank lookups in the fused selection's histograms, shared by the kernels that build them (select.hip) and the consumers that resolve the
 // last level (loop.hip: accumulate_kernel, res_pairs_kernel).
 // All 256 threads call with one bin count `v` each (bin = threadIdx.x).  Finds the bin holding element
 // `rank` (0-based, ascending); when from_quantile, rank = (unsigned)(float(total) * quantile) like
 // getDistsQuantile.  Results are uniform across the block.
+// REG_SCAN: the wave's prefix sums in registers (wave_incl_scan); false: the __shfl_up scan, for a caller that spills more with the former
+// (integer adds: the same sums either way).
+template <bool REG_SCAN = true>
 __device__ __forceinline__ void block_find_rank256(unsigned v, bool from_quantile, float quantile, unsigned rank_in,
                                                    unsigned* sh /* >= 16 words */, unsigned& bin, unsigned& rank_rem, unsigned& total)
 {
     const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
     unsigned incl = v;
+    if constexpr (REG_SCAN) incl = wave_incl_scan(v);
+    else {
 #pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const unsigned o = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += o;
+        for (int off = 1; off < 64; off <<= 1) {
+            const unsigned o = __shfl_up(incl, off, 64);
+            if (lane >= off) incl += o;
+        }
     }
     if (lane == 63) sh[wv] = incl;
     __syncthreads();
@@ -117,17 +182,17 @@ __device__ __forceinline__ void block_find_rank256(unsigned v, bool from_quantil
     __syncthreads();
     bin = sh[8];
     rank_rem = sh[9];
-    __syncthreads();
+    __syncthreads(); // (stays: in a 1024-thread workgroup the next call's sh[wv] reaches words 8 and 9 in front of its first barrier)
 }
 
 // two-tier lookup: coarse bin from `coarse_v` (this thread's coarse count), then the fine bin under it
-template <int FCOPIES>
+template <int FCOPIES, bool REG_SCAN = true>
 __device__ __forceinline__ void block_find_rank_2tier(unsigned coarse_v, const unsigned* __restrict__ fine, bool from_quantile,
                                                       float quantile, unsigned rank_in, unsigned* sh, unsigned& bin16,
                                                       unsigned& rank_rem, unsigned& total)
 {
     unsigned cb, rem, tot2;
-    block_find_rank256(coarse_v, from_quantile, quantile, rank_in, sh, cb, rem, total);
+    block_find_rank256<REG_SCAN>(coarse_v, from_quantile, quantile, rank_in, sh, cb, rem, total);
     if (total == 0) { bin16 = 0; rank_rem = 0; return; }
     unsigned fv = 0;
     if (threadIdx.x < 256) { // (workgroups wider than 256 threads: the extra waves carry empty bins through the scan)
@@ -135,7 +200,7 @@ __device__ __forceinline__ void block_find_rank_2tier(unsigned coarse_v, const u
         for (int cpy = 0; cpy < FCOPIES; ++cpy) fv += fine[cpy * 65536 + ICPMI_S2_FIDX(cb * 256 + threadIdx.x)];
     }
     unsigned fb;
-    block_find_rank256(fv, false, 0.f, rem, sh, fb, rank_rem, tot2);
+    block_find_rank256<REG_SCAN>(fv, false, 0.f, rem, sh, fb, rank_rem, tot2);
     bin16 = (cb << 8) | fb;
 }
 
@@ -185,18 +250,7 @@ __device__ __forceinline__ unsigned wave_append(unsigned* counter, bool flag)
     base = (unsigned)__builtin_amdgcn_readlane((int)base, 0);
     return base + (unsigned)__popcll(bal & ((1ull << lane) - 1ull));
 }
-// inclusive prefix sum over the 64 lanes of a wave in registers (DPP: shifts within rows of 16 lanes, then the row totals
-// broadcast into the following rows); every lane must be active
-__device__ __forceinline__ unsigned wave_incl_scan(unsigned v)
-{
-    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false); // row_shr:1
-    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false); // row_shr:2
-    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, false); // row_shr:4
-    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, false); // row_shr:8
-    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false); // row_bcast:15 -> rows 1, 3
-    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false); // row_bcast:31 -> rows 2, 3
-    return v;
-}
+// (the prefix sum over a wave's lanes, wave_incl_scan, stands with the lane exchanges above)
 #endif
 
 // ------------------------------------------------------------------------------------------------
@@ -1680,7 +1734,7 @@ __device__ __forceinline__ void gicp_pair_sums(double (&acc)[27], float sxx, flo
 }
 
 // The workgroup's sums (BT threads; acc: the NVAL values of the model, then sum w and the pair count, EXT: force2D's b, else b2d is not
-// read) join the iteration's accumulator at hists + ICPMI_S2_ACC.  wave64 shuffles, then LDS across the waves.
+// read) join the iteration's accumulator at hists + ICPMI_S2_ACC.  Lane exchanges in registers (lane_xor), then LDS across the waves.
 // Transposed butterfly: at the step with partner lane ^ m every lane hands over the half of its values the partner keeps, so 32 values x
 // 64 lanes fold with 16+8+4+2+1+1 = 32 exchanges instead of 32 x 6.  After the five halving steps lane l holds value bitrev5(l & 31)
 // summed over its 32-lane half; the last exchange joins the halves.  Fixed pattern => deterministic sums.
@@ -1704,10 +1758,10 @@ __device__ __forceinline__ void pair_sums_fold(const double (&acc)[NVAL > 0 ? NV
         for (int i = 0; i < nkeep; ++i) {
             const double send = upper ? val[i] : val[i + nkeep];
             const double keep = upper ? val[i + nkeep] : val[i];
-            val[i] = keep + __shfl_xor(send, m, 64);
+            val[i] = keep + lane_xor_bit(send, m); // (the partner is lane ^ m, as with __shfl_xor: the same tree of additions)
         }
     }
-    val[0] += __shfl_xor(val[0], 32, 64);
+    val[0] += lane_xor<32>(val[0]);
     if (lane < 32) {
         const int idx = ((lane & 1) << 4) | ((lane & 2) << 2) | (lane & 4) | ((lane & 8) >> 2) | ((lane & 16) >> 4);
         sh[wv][idx] = val[0];
@@ -1799,7 +1853,7 @@ __device__ __forceinline__ void block_partial_row(const double (&acc)[NV], doubl
         double v = acc[i];
 #pragma unroll
         for (int m = 32; m > 0; m >>= 1) {
-            const double o = __shfl_xor(v, m, 64);
+            const double o = lane_xor_bit(v, m);
             v = (MAXMASK >> i & 1u) ? fmax(v, o) : v + o;
         }
         if (lane == 0) sh[wv][i] = v;

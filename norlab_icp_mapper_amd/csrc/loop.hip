@@ -166,12 +166,15 @@ __global__ __launch_bounds__(BT) void accumulate_kernel(const float4* __restrict
     }
     if (done) return;
     if (blockIdx.x == 0 && threadIdx.x == 0) nn_stamp_close(st, t_nn_begin);
+    // The lane exchanges of this kernel run in registers (common.h: wave_incl_scan, lane_xor) except in the two instantiations that spill more
+    // with them than with the shuffles (profiles/tail_dpp_isa_diff.txt): the same partners and operand order, the same bits either way.
+    constexpr bool REG_LANES = !(FUSED && EXT && BT == 1024 && (PM == PAIR_PLANE_TO_PLANE || PM == PAIR_SYMMETRIC));
     float fused_limit = 0.f;
     if (FUSED) {
         // scan of level 1: the selected element's bit pattern is prefix(16) | bin(16)
         __shared__ unsigned shsel[16];
         unsigned bin, rem, total;
-        block_find_rank_2tier<1>(cv, hists + ICPMI_S2_F1, false, 0.f, sel_rank0, shsel, bin, rem, total);
+        block_find_rank_2tier<1, REG_LANES>(cv, hists + ICPMI_S2_F1, false, 0.f, sel_rank0, shsel, bin, rem, total);
         const float q = __uint_as_float((sel_prefix0 << 16) | bin);
         fused_limit = is_median ? factor * q : q;
         if (blockIdx.x == 0 && threadIdx.x == 0) st->limits[fused_slot] = fused_limit;
@@ -338,7 +341,7 @@ __global__ __launch_bounds__(BT) void accumulate_kernel(const float4* __restrict
             pair(e, d2a[e], sidx[e], reading[(int)(e / lc.k)], match_pt ? match_pt[e] : make_float4(0.f, 0.f, 0.f, 0.f),
                  make_float4(0.f, 0.f, 0.f, 0.f), false, make_float4(0.f, 0.f, 0.f, 0.f), 0, 0.f);
     }
-    // ---- workgroup reduction: wave64 shuffles, then LDS across the waves ----
+    // ---- workgroup reduction: lane exchanges inside the wave, then LDS across the waves ----
     // (common.h: pair_sums_fold is this fold as a function, for voxel.hip.  Here it stays spelled out, and so do the rank-1 updates above: the EXT
     // instantiations at 1024 threads sit at the 128-VGPR cap, where the inlined helpers order the same operations differently and spill more)
     // Transposed butterfly: at the step with partner lane ^ m every lane hands over the half of its
@@ -361,10 +364,12 @@ __global__ __launch_bounds__(BT) void accumulate_kernel(const float4* __restrict
         for (int i = 0; i < nkeep; ++i) {
             const double send = upper ? val[i] : val[i + nkeep];
             const double keep = upper ? val[i + nkeep] : val[i];
-            val[i] = keep + __shfl_xor(send, m, 64);
+            if constexpr (REG_LANES) val[i] = keep + lane_xor_bit(send, m); // (common.h: lane ^ m in registers, no trip through the LDS crossbar)
+            else val[i] = keep + __shfl_xor(send, m, 64);
         }
     }
-    val[0] += __shfl_xor(val[0], 32, 64);
+    if constexpr (REG_LANES) val[0] += lane_xor<32>(val[0]);
+    else val[0] += __shfl_xor(val[0], 32, 64);
     if (lane < 32) {
         const int idx = ((lane & 1) << 4) | ((lane & 2) << 2) | (lane & 4) | ((lane & 8) >> 2) | ((lane & 16) >> 4);
         sh[wv][idx] = val[0];

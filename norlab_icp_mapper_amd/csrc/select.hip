@@ -322,7 +322,9 @@ __global__ __launch_bounds__(256) void sel2_scan_hist_kernel(const float* __rest
     unsigned prefix, rem, total;
     // (r5) k > 1: the NN kernel's window around the previous prefix first (the stand-alone builder took the same decision from the same words)
     const bool win_hit = use_win && win_lookup(hists, quantile, sh, prefix, rem, total);
-    if (!win_hit) block_find_rank_2tier<ICPMI_S2_FCOPIES>(cv, hists + ICPMI_S2_F0, true, quantile, 0u, sh, prefix, rem, total);
+    // (the shuffle scan: with common.h's register scan this kernel traced 5.24 against 5.36 us, inside the 0.24 us its own runs differ by --
+    // DESIGN.md 4.2, profiles/tail_dpp_kernel_stats.csv)
+    if (!win_hit) block_find_rank_2tier<ICPMI_S2_FCOPIES, false>(cv, hists + ICPMI_S2_F0, true, quantile, 0u, sh, prefix, rem, total);
 #ifndef ICPMI_NN_TIMING
     if (use_win && blockIdx.x == 0 && threadIdx.x == 0) st->dbg[win_hit ? 12 : 13] += 1ull; // diagnostics: iterations served by the window / by the full level 0
 #endif

@@ -334,31 +334,7 @@ __device__ const signed char SG_ORD[27][3] = { // the 27 cells of a neighbourhoo
     {-1, -1, 0}, {1, -1, 0}, {-1, 1, 0}, {1, 1, 0}, {-1, 0, -1}, {1, 0, -1}, {-1, 0, 1}, {1, 0, 1}, {0, -1, -1}, {0, 1, -1}, {0, -1, 1}, {0, 1, 1},
     {-1, -1, -1}, {1, -1, -1}, {-1, 1, -1}, {1, 1, -1}, {-1, -1, 1}, {1, -1, 1}, {-1, 1, 1}, {1, 1, 1}};
 
-// value of lane (lane ^ J), without the LDS crossbar: DPP quad permutes / row shifts / row rotate inside a row of 16 lanes, gfx950's
-// v_permlane16_swap / v_permlane32_swap across rows (a sort written with __shfl_xor is 42 ds_bpermute_b32 round trips, one behind the other)
-template <int J>
-__device__ __forceinline__ unsigned sg_lane_xor(unsigned v)
-{
-    const int x = (int)v;
-    if constexpr (J == 1) return (unsigned)__builtin_amdgcn_update_dpp(x, x, 0xB1, 0xF, 0xF, false);      // quad_perm [1, 0, 3, 2]
-    else if constexpr (J == 2) return (unsigned)__builtin_amdgcn_update_dpp(x, x, 0x4E, 0xF, 0xF, false); // quad_perm [2, 3, 0, 1]
-    else if constexpr (J == 4) {
-        const int t = __builtin_amdgcn_update_dpp(x, x, 0x104, 0xF, 0x5, false);                            // row_shl:4 into banks 0, 2
-        return (unsigned)__builtin_amdgcn_update_dpp(t, x, 0x114, 0xF, 0xA, false);                         // row_shr:4 into banks 1, 3
-    } else if constexpr (J == 8) return (unsigned)__builtin_amdgcn_update_dpp(x, x, 0x128, 0xF, 0xF, false); // row_ror:8
-    else if constexpr (J == 16) {
-        const auto r = __builtin_amdgcn_permlane16_swap(v, v, false, false); // r[0]: odd rows <- even rows; r[1]: even rows <- odd rows
-        return (threadIdx.x & 16) ? r[0] : r[1];
-    } else {
-        const auto r = __builtin_amdgcn_permlane32_swap(v, v, false, false);
-        return (threadIdx.x & 32) ? r[0] : r[1];
-    }
-}
-template <int J>
-__device__ __forceinline__ unsigned long long sg_lane_xor64(unsigned long long v)
-{
-    return ((unsigned long long)sg_lane_xor<J>((unsigned)(v >> 32)) << 32) | (unsigned long long)sg_lane_xor<J>((unsigned)v);
-}
+// (the value of lane (lane ^ J) without the LDS crossbar: common.h, lane_xor / lane_xor64)
 __device__ __forceinline__ unsigned long long sg_readlane64(unsigned long long v, int l /* uniform */)
 {
     return ((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), l) << 32) |
@@ -367,7 +343,7 @@ __device__ __forceinline__ unsigned long long sg_readlane64(unsigned long long v
 
 // bitonic sort across the 64 lanes (keys are unique, or ~0 = nothing): ascending, or DESC: descending.  n (uniform): only lanes [0, n) hold
 // real keys -- the phases that merge halves of nothing are skipped (n <= 16: 10 steps, n <= 32: 15, else 21)
-#define SG_CE(K2, J) { const unsigned long long other = sg_lane_xor64<J>(key); \
+#define SG_CE(K2, J) { const unsigned long long other = lane_xor64<J>(key); \
                        const bool take_min = ((((K2) >= 64) || (lane & (K2)) == 0) == ((lane & (J)) == 0)) != DESC; \
                        key = (take_min == (other < key)) ? other : key; }
 template <bool DESC>

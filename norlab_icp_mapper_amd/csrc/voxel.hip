@@ -108,7 +108,7 @@ __global__ __launch_bounds__(256) void vox_reduce_kernel(const unsigned long lon
 #pragma unroll
     for (int j = 0; j < 9; ++j)
 #pragma unroll
-        for (int mk = 1; mk < 64; mk <<= 1) a[j] += __shfl_xor(a[j], mk, 64);
+        for (int mk = 1; mk < 64; mk <<= 1) a[j] += lane_xor_bit(a[j], mk); // (the wave is whole again behind the loop above)
     if (lane == 0) {
         const unsigned cnt = s1 - s0;
         const double inv = 1.0 / (double)cnt;
