@@ -381,6 +381,38 @@ icpmi_status icpmi_debug_voxel_build_times(icpmi_handle h, float times_ms3[3]);
  * the sorted keys (ms2[1]); *mismatch (may be NULL) = queries the two answer differently (0) */
 icpmi_status icpmi_debug_voxel_lookup_times(icpmi_handle h, const float* q4_centred, int64_t n, int32_t reps, float ms2[2], int64_t* mismatch);
 
+/* A schedule of voxel sizes: coarse-to-fine registration on the voxel path.  sizes[0..n) with n in 0..4, every size finite
+ * and > 0, strictly descending (coarsest first); anything else: ICPMI_ERR_INVALID_ARG ("InvalidParameter: ...") and the schedule stays.
+ * n = 0 switches the matcher off; n = 1 is icpmi_set_voxel_matcher(sizes[0]), bit for bit; icpmi_set_voxel_matcher(size) is a schedule of
+ * one (or none at 0), and icpmi_get_voxel_matcher answers the finest size.
+ * Level l uses the table of sizes[l], built by the one build path (its sorted records are bit for bit those of a one-size handle with that
+ * size), lazily, and rebuilt when the map, its normals or the schedule change.  A level costs 64 B x its table's capacity.
+ * A registration starts at level 0 and runs each level as an ICP run of its own on the chain's checkers: the Differential checker's history
+ * and the Counter start afresh at each level (max_iterations bounds a LEVEL, the registration is bounded by levels x that count; the
+ * history of a level after the first begins empty -- the pose carried over is not an entry, so such a level runs at least
+ * smooth_length + 1 iterations); a stop by
+ * either at a level before the last moves on to the next level with the pose unchanged; at the last level it ends the registration as on
+ * a one-size handle.  The Bound checker (measured from the registration's start) and a level with no pair
+ * (ICPMI_ERR_NO_POINT_TO_MINIMIZE) end the registration at once.  icpmi_register_fixed_dev runs its count at EVERY level.  The level
+ * switch happens on the device, inside the one enqueued loop: no host wait between levels.  icpmi_stats::iterations is the total.
+ * A schedule widens the basin of the finest size; it does not guarantee it: a level whose size divides the scene's own dimensions can have
+ * a false minimum, and a schedule that starts there stays there (DESIGN.md 4.21 has the measured case).
+ * Everything refused on a one-size handle is refused on a scheduled one, with the same messages.
+ * icpmi_get_voxel_map and icpmi_voxel_lookup answer for the finest level, the _level variants for level `level` (0 = the coarsest; no such
+ *   level: ICPMI_ERR_INVALID_ARG).
+ * icpmi_get_voxel_schedule_report (two or more levels, else ICPMI_ERR_INVALID_ARG): of the handle's last registration, *levels = the levels
+ *   entered, and per level the iterations run and the pair counts of its first and of its last iteration (0 for a level not entered; a
+ *   level that found no pair reports 0 iterations and 0 pairs).
+ * icpmi_minimize_step_normals on a scheduled handle evaluates at the finest level; icpmi_debug_voxel_step_level (test seam) selects
+ *   another, -1 the finest again; a new schedule resets it. */
+icpmi_status icpmi_set_voxel_schedule(icpmi_handle h, const float* sizes, int32_t n);
+icpmi_status icpmi_get_voxel_schedule(icpmi_handle h, float sizes[4], int32_t* n);
+icpmi_status icpmi_get_voxel_map_level(icpmi_handle h, int32_t level, int64_t cap, int32_t* ijk3, float* mean3, float* moments6, int32_t* count,
+                                       int64_t* n_voxels);
+icpmi_status icpmi_voxel_lookup_level(icpmi_handle h, int32_t level, const float* q4_centred, int64_t n, int32_t* voxel);
+icpmi_status icpmi_get_voxel_schedule_report(icpmi_handle h, int32_t* levels, int32_t iterations[4], int32_t pairs_first[4], int32_t pairs_last[4]);
+icpmi_status icpmi_debug_voxel_step_level(icpmi_handle h, int32_t level);
+
 /* ---- IntensityPointToPlaneErrorMinimizer: a photometric term on ICPMI_MIN_POINT_TO_PLANE.  Not libpointmatcher's: the joint
  * geometric + photometric objective of Park, Zhou, Koltun, "Colored Point Cloud Registration Revisited" (ICCV 2017), one scalar channel.
  *

@@ -210,6 +210,12 @@ SYMBOLS = [
     ("icpmi_get_voxel_matcher", C.c_int, [_P, _F]),
     ("icpmi_get_voxel_map", C.c_int, [_P, C.c_int64, _P, _P, _P, _P, C.POINTER(C.c_int64)]),
     ("icpmi_voxel_lookup", C.c_int, [_P, _P, C.c_int64, _P]),
+    ("icpmi_set_voxel_schedule", C.c_int, [_P, _P, C.c_int32]),
+    ("icpmi_get_voxel_schedule", C.c_int, [_P, _P, C.POINTER(C.c_int32)]),
+    ("icpmi_get_voxel_map_level", C.c_int, [_P, C.c_int32, C.c_int64, _P, _P, _P, _P, C.POINTER(C.c_int64)]),
+    ("icpmi_voxel_lookup_level", C.c_int, [_P, C.c_int32, _P, C.c_int64, _P]),
+    ("icpmi_get_voxel_schedule_report", C.c_int, [_P, C.POINTER(C.c_int32), _P, _P, _P]),
+    ("icpmi_debug_voxel_step_level", C.c_int, [_P, C.c_int32]),
     ("icpmi_debug_voxel_build_times", C.c_int, [_P, _P]),
     ("icpmi_debug_voxel_lookup_times", C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, C.POINTER(C.c_int64)]),
     ("icpmi_set_intensity_weight", C.c_int, [_P, C.c_float]),

@@ -698,7 +698,7 @@ static icpmi_status intensity_setup(icpmi_ctx* h, const char* who, int64_t n, in
     return ICPMI_OK;
 }
 
-// VoxelMatcher (icpmi_set_voxel_matcher > 0) is served on plane-to-plane chains with the GICP pair model and no outlier
+// VoxelMatcher (icpmi_set_voxel_matcher > 0 or icpmi_set_voxel_schedule with a size) is served on plane-to-plane chains with the GICP pair model and no outlier
 // filter, by the entry points that carry the reading's normals and run ONE reading.  Everything else says so and names the matcher; nothing
 // is served by the nearest-neighbour path in silence.  served = this entry point can run it
 static icpmi_status voxel_check(icpmi_ctx* h, const char* who, bool served)
@@ -1361,11 +1361,26 @@ icpmi_status icpmi_get_plane_pair_model(icpmi_handle h, int32_t* model)
     return ICPMI_OK;
 }
 
+// the handle's schedule becomes sizes[0..n) (validated by the caller); a level whose size stays keeps its table
+static void voxel_apply_schedule(icpmi_ctx* h, const float* sizes, int n)
+{
+    for (int l = 0; l < ICPMI_MAX_VOXEL_LEVELS; ++l) h->vox_sizes[l] = l < n ? sizes[l] : 0.f;
+    for (int l = n; l < ICPMI_MAX_VOXEL_LEVELS; ++l) { // a level the schedule no longer has gives its table back
+        VoxLevel& lv = h->vox[l];
+        (void)lv.keys.reset(); (void)lv.rec.reset(); (void)lv.tab.reset();
+        lv.ready = false; lv.nv = 0;
+    }
+    h->vox_levels = n;
+    h->voxel_size = n > 0 ? sizes[n - 1] : 0.f; // (no graph to drop: loop_sig hashes the level count and every level's size, generation and table; the tables follow lazily)
+    h->vox_step_level = -1;
+    for (int i = 0; i < 1 + 3 * ICPMI_MAX_VOXEL_LEVELS; ++i) h->vox_report[i] = 0;
+}
+
 icpmi_status icpmi_set_voxel_matcher(icpmi_handle h, float size)
 {
     CHECK_H(h);
     if (!std::isfinite(size) || size < 0.f) { h->last_error = "set_voxel_matcher: the voxel size must be finite and >= 0 (0: off)"; return ICPMI_ERR_INVALID_ARG; }
-    h->voxel_size = size; // (no graph to drop: loop_sig hashes the size and the table's generation; the table follows lazily)
+    voxel_apply_schedule(h, &size, size > 0.f ? 1 : 0);
     return ICPMI_OK;
 }
 
@@ -1377,19 +1392,90 @@ icpmi_status icpmi_get_voxel_matcher(icpmi_handle h, float* size)
     return ICPMI_OK;
 }
 
+icpmi_status icpmi_set_voxel_schedule(icpmi_handle h, const float* sizes, int32_t n)
+{
+    CHECK_H(h);
+    if (n < 0 || n > ICPMI_MAX_VOXEL_LEVELS || (n > 0 && !sizes)) {
+        h->last_error = "InvalidParameter: set_voxel_schedule: VoxelMatcher takes 0 (off) to 4 voxel sizes"; return ICPMI_ERR_INVALID_ARG;
+    }
+    for (int l = 0; l < n; ++l) {
+        if (!std::isfinite(sizes[l]) || !(sizes[l] > 0.f)) {
+            h->last_error = "InvalidParameter: set_voxel_schedule: every voxel size of the VoxelMatcher schedule must be finite and > 0"; return ICPMI_ERR_INVALID_ARG;
+        }
+        if (l > 0 && !(sizes[l] < sizes[l - 1])) {
+            h->last_error = "InvalidParameter: set_voxel_schedule: the voxel sizes of the VoxelMatcher schedule must be strictly descending (coarsest first)";
+            return ICPMI_ERR_INVALID_ARG;
+        }
+    }
+    voxel_apply_schedule(h, sizes, n);
+    return ICPMI_OK;
+}
+
+icpmi_status icpmi_get_voxel_schedule(icpmi_handle h, float sizes[4], int32_t* n)
+{
+    CHECK_H(h);
+    if (!sizes || !n) { h->last_error = "get_voxel_schedule: null argument"; return ICPMI_ERR_INVALID_ARG; }
+    for (int l = 0; l < ICPMI_MAX_VOXEL_LEVELS; ++l) sizes[l] = h->vox_sizes[l];
+    *n = h->vox_levels;
+    return ICPMI_OK;
+}
+
+icpmi_status icpmi_get_voxel_schedule_report(icpmi_handle h, int32_t* levels, int32_t iterations[4], int32_t pairs_first[4], int32_t pairs_last[4])
+{
+    CHECK_H(h);
+    if (!levels || !iterations || !pairs_first || !pairs_last) { h->last_error = "get_voxel_schedule_report: null argument"; return ICPMI_ERR_INVALID_ARG; }
+    if (h->vox_levels < 2) { h->last_error = "get_voxel_schedule_report: the handle has no schedule of two or more voxel sizes (icpmi_set_voxel_schedule)"; return ICPMI_ERR_INVALID_ARG; }
+    *levels = h->vox_report[0];
+    for (int l = 0; l < ICPMI_MAX_VOXEL_LEVELS; ++l) {
+        iterations[l] = h->vox_report[1 + l];
+        pairs_first[l] = h->vox_report[1 + ICPMI_MAX_VOXEL_LEVELS + l];
+        pairs_last[l] = h->vox_report[1 + 2 * ICPMI_MAX_VOXEL_LEVELS + l];
+    }
+    return ICPMI_OK;
+}
+
+// test seam: the level icpmi_minimize_step_normals evaluates on a scheduled handle (-1: the finest again); a new schedule resets it
+icpmi_status icpmi_debug_voxel_step_level(icpmi_handle h, int32_t level)
+{
+    CHECK_H(h);
+    if (level < -1 || level >= h->vox_levels) { h->last_error = "debug_voxel_step_level: no such level in the voxel schedule"; return ICPMI_ERR_INVALID_ARG; }
+    h->vox_step_level = level;
+    return ICPMI_OK;
+}
+
+static icpmi_status get_voxel_map_impl(icpmi_handle h, int level, int64_t cap, int32_t* ijk3, float* mean3, float* moments6, int32_t* count, int64_t* n_voxels)
+{
+    if (n_voxels) *n_voxels = 0;
+    if (cap < 0) { h->last_error = "get_voxel_map: bad arguments"; return ICPMI_ERR_INVALID_ARG; }
+    return voxel_get_map(h, level, cap, ijk3, mean3, moments6, count, n_voxels);
+}
+
 icpmi_status icpmi_get_voxel_map(icpmi_handle h, int64_t cap, int32_t* ijk3, float* mean3, float* moments6, int32_t* count, int64_t* n_voxels)
 {
     CHECK_H(h);
-    if (n_voxels) *n_voxels = 0;
-    if (cap < 0) { h->last_error = "get_voxel_map: bad arguments"; return ICPMI_ERR_INVALID_ARG; }
-    return voxel_get_map(h, cap, ijk3, mean3, moments6, count, n_voxels);
+    return get_voxel_map_impl(h, -1, cap, ijk3, mean3, moments6, count, n_voxels);
+}
+
+icpmi_status icpmi_get_voxel_map_level(icpmi_handle h, int32_t level, int64_t cap, int32_t* ijk3, float* mean3, float* moments6, int32_t* count,
+                                       int64_t* n_voxels)
+{
+    CHECK_H(h);
+    if (level < 0) { if (n_voxels) *n_voxels = 0; h->last_error = "get_voxel_map_level: no such level in the voxel schedule"; return ICPMI_ERR_INVALID_ARG; }
+    return get_voxel_map_impl(h, level, cap, ijk3, mean3, moments6, count, n_voxels);
 }
 
 icpmi_status icpmi_voxel_lookup(icpmi_handle h, const float* q4_centred, int64_t n, int32_t* voxel)
 {
     CHECK_H(h);
     if (n < 0 || (n > 0 && (!q4_centred || !voxel))) { h->last_error = "voxel_lookup: bad arguments"; return ICPMI_ERR_INVALID_ARG; }
-    return voxel_lookup(h, q4_centred, n, voxel);
+    return voxel_lookup(h, -1, q4_centred, n, voxel);
+}
+
+icpmi_status icpmi_voxel_lookup_level(icpmi_handle h, int32_t level, const float* q4_centred, int64_t n, int32_t* voxel)
+{
+    CHECK_H(h);
+    if (level < 0 || n < 0 || (n > 0 && (!q4_centred || !voxel))) { h->last_error = "voxel_lookup_level: bad arguments"; return ICPMI_ERR_INVALID_ARG; }
+    return voxel_lookup(h, level, q4_centred, n, voxel);
 }
 
 // test seam of scripts/voxel_bench.py: rebuilds the table and reports what its three stages took (sort, reduce, fill; milliseconds by HIP events)

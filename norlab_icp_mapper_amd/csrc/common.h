@@ -424,7 +424,7 @@ struct alignas(128) LoopHdr {
     unsigned sel_prefix_l[3];  // fused selection: one slot per radix level (written by level L,
     unsigned sel_rank_l[3];    // read by level L + 1 -- never both in one kernel)
     float robust_scale;    // RobustOutlierFilter::scale, kept between iterations (nbIterationForScale)
-    unsigned pad_hdr;
+    unsigned vox_level;    // scheduled VoxelMatcher handles only (voxel.hip sets, reads and raises it; nothing else touches the word): the current level
     float limits[ICPMI_MAX_OUTLIER];
     // r6: device clock at which the last NN launch's first workgroup started (0: no interval open), see t_nn_sum below
     unsigned long long t_nn_begin;
@@ -727,6 +727,25 @@ inline void stream_release(hipStream_t s)
     (void)hipStreamDestroy(s);
 }
 
+// One level of a VoxelMatcher handle (voxel.hip): the occupied voxels' keys and records in ascending key order and
+// the open-addressing table (64-byte slots, mask + 1 of them) the kernels probe, built for `built_size`.  gen counts the level's builds.
+#define ICPMI_MAX_VOXEL_LEVELS 4
+struct VoxLevel {
+    DevArr<unsigned long long> keys; DevArr<float4> rec; DevArr<uint4> tab;
+    int64_t nv = 0; unsigned mask = 0; bool ready = false;
+    uint64_t map_version = 0, epoch = 0, gen = 0; float built_size = 0.f;
+};
+// The device block of a scheduled handle (two or more levels), in dwords: 16 of level descriptors (per level: table address lo, hi, mask,
+// size bits -- voxel_pairs_sched_kernel takes them in one load, lane l dword l), then what voxel_advance_kernel keeps between iterations:
+// the iteration count at which the current level began, and per level the iterations run and the pair counts of its first and last
+// iteration.  The current level itself is the loop header's vox_level.
+#define ICPMI_VS_DESC 0
+#define ICPMI_VS_BASE 16
+#define ICPMI_VS_ITERS 17
+#define ICPMI_VS_FIRST 21
+#define ICPMI_VS_LAST 25
+#define ICPMI_VS_WORDS 32
+
 #define ICPMI_SCRATCH_SLOTS 24
 struct icpmi_ctx {
     icpmi_config cfg;
@@ -874,14 +893,19 @@ struct icpmi_ctx {
     // gi_version with gi_m points -- every map_build moves on and thereby drops the channel
     float intensity_w = 0.f;
     DevArr<float4> d_map_gi; uint64_t gi_version = 0; int64_t gi_m = 0;
-    // icpmi_set_voxel_matcher: the voxel size (0: off); handle state like plane_eps.  The table of the resident map (voxel.hip): the occupied
-    // voxels' keys and records in ascending key order and the open-addressing table (64-byte slots, vox_mask + 1 of them) the kernels probe.
-    // Built lazily by voxel_ensure_table; current while the map (map_version, map_epoch) and the size are those it was built for.  vox_gen
-    // counts the builds: loop_sig hashes it with the size, neither is part of the LoopCfg.
+    // icpmi_set_voxel_schedule / icpmi_set_voxel_matcher: the voxel sizes, coarsest first (vox_levels = 0: off); handle state like
+    // plane_eps.  voxel_size is the finest of them, the size of a one-size handle.  One table of the resident map per level (VoxLevel), built
+    // lazily by voxel_ensure_table; a level is current while the map (map_version, map_epoch) and its size are those it was built for.
+    // loop_sig hashes the level count and every level's size, generation and table address: none is part of the LoopCfg.
+    // d_vox_sched (ICPMI_VS_WORDS dwords; two or more levels): the level descriptors as uploaded for vox_sched_sig, and the advance's report.
+    // vox_step_level: the level icpmi_minimize_step_normals evaluates (-1: the finest; icpmi_debug_voxel_step_level).  vox_report: the last
+    // registration's levels entered, then per level iterations, first and last pair count (icpmi_get_voxel_schedule_report).
     float voxel_size = 0.f;
-    DevArr<unsigned long long> d_vox_keys; DevArr<float4> d_vox_rec; DevArr<uint4> d_vox_tab;
-    int64_t vox_nv = 0; unsigned vox_mask = 0; bool vox_ready = false;
-    uint64_t vox_map_version = 0, vox_epoch = 0, vox_gen = 0; float vox_built_size = 0.f;
+    int vox_levels = 0; float vox_sizes[ICPMI_MAX_VOXEL_LEVELS] = {0.f, 0.f, 0.f, 0.f};
+    VoxLevel vox[ICPMI_MAX_VOXEL_LEVELS];
+    DevArr<unsigned> d_vox_sched; uint64_t vox_sched_sig = 0;
+    int vox_step_level = -1;
+    int32_t vox_report[1 + 3 * ICPMI_MAX_VOXEL_LEVELS] = {0};
     DevArr<IcpState> d_state;          // ICPMI_MAX_BATCH states (a single registration uses the first)
     IcpState* h_state = nullptr;                               // pinned mirror (ICPMI_MAX_BATCH)
     bool zero_pending = false;                                 // d_state / d_selhist still to be cleared: on the stream the handle really uses, at its first call (zero_state_if_pending)
@@ -1010,6 +1034,7 @@ static inline void drop_loop_graphs(icpmi_ctx* c)
 #define ICPMI_MERGE_MAGIC 0x49435035u // 'ICP5' in the header's y
 #define ICPMI_PROGRESS_OCT_WORD 48  // ... and 8 words for the octree's root cube (octree.hip)
 #define ICPMI_PROGRESS_SELF_WORD 56 // ... two words: sum over the A-cells of (points in the cell)^2 of the handle's last self search (selfgrid.hip: the next build tunes its edge with it)
+#define ICPMI_PROGRESS_VOX_WORD 320  // ... 13 words: the report of a scheduled VoxelMatcher registration (voxel.hip: voxel_advance_kernel), final behind the "done" word
 #define ICPMI_PROGRESS_SCAN_WORD 40 // word of the host-mapped progress page (api.hip: h_progress, 64 words) that device_scan_flags_count reports into
 
 // Host wait on `count` words of host-mapped memory that the stream's kernels write: spins on them (v = a fresh snapshot) until ready(v),
@@ -1452,11 +1477,22 @@ static inline bool voxel_path(const icpmi_ctx* c)
 {
     return c->voxel_size > 0.f && c->cfg.minimizer == ICPMI_MIN_PLANE_TO_PLANE && c->plane_model == ICPMI_PLANE_MODEL_GICP;
 }
+// ... with a schedule of two or more levels: the pair kernel that reads the level, and the advance behind the solve
+static inline bool voxel_scheduled(const icpmi_ctx* c) { return voxel_path(c) && c->vox_levels >= 2; }
+// FNV-1a over n bytes, continued from h: what the signatures of captured loops are made of (loop.hip: loop_sig; voxel.hip: voxel_sched_sig)
+static inline uint64_t fnv(const void* p, size_t n, uint64_t h)
+{
+    const unsigned char* b = (const unsigned char*)p;
+    for (size_t i = 0; i < n; ++i) { h ^= b[i]; h *= 1099511628211ull; }
+    return h;
+}
+uint64_t voxel_sched_sig(const icpmi_ctx* c, uint64_t h); // hash of what a captured voxel loop depends on, continued from h (0: a fresh one)
 bool voxel_table_current(const icpmi_ctx* c);
-icpmi_status voxel_ensure_table(icpmi_ctx* c, float* times_ms); // times_ms (3 floats: sort, reduce, fill) forces a rebuild
+icpmi_status voxel_ensure_table(icpmi_ctx* c, float* times_ms); // every level; times_ms (3 floats: sort, reduce, fill) forces a rebuild of the finest
 void voxel_enqueue_pairs(icpmi_ctx* c, int64_t n, int nb, float eps); // one launch on c->stream: the sums of c->d_reading under d_state->T_iter
-icpmi_status voxel_get_map(icpmi_ctx* c, int64_t cap, int32_t* ijk3, float* mean3, float* moments6, int32_t* count, int64_t* n_voxels);
-icpmi_status voxel_lookup(icpmi_ctx* c, const float* q4_centred, int64_t n, int32_t* voxel);
+// (scheduled handles: the level word is set and raised by loop.hip's voxel_sched_reset_kernel and voxel_advance_kernel)
+icpmi_status voxel_get_map(icpmi_ctx* c, int level, int64_t cap, int32_t* ijk3, float* mean3, float* moments6, int32_t* count, int64_t* n_voxels);
+icpmi_status voxel_lookup(icpmi_ctx* c, int level, const float* q4_centred, int64_t n, int32_t* voxel);
 icpmi_status voxel_lookup_times(icpmi_ctx* c, const float* q4_centred, int64_t n, int reps, float ms[2], int64_t* mismatch); // table against binary search
 // the reading's normals (host, 3 per point) into c->d_read_normals, padded as a registration's head pads them
 icpmi_status loop_upload_read_normals(icpmi_ctx* c, const float* normals3, int64_t n);

@@ -439,6 +439,64 @@ __global__ __launch_bounds__(256) void solve_kernel(IcpState* __restrict__ st, u
     if (threadIdx.x == 0) publish_progress(st, progress);
 }
 
+// ---- scheduled VoxelMatcher handles ---------------------------------------------
+// The level word of the header and the report of the handle's device block (common.h: ICPMI_VS_*), set behind init_state: a registration's
+// head starts at level 0, a one-pass evaluation (icpmi_minimize_step_normals) at the level it asks for.
+__global__ __launch_bounds__(64) void voxel_sched_reset_kernel(IcpState* __restrict__ st, unsigned* __restrict__ sched, unsigned level)
+{
+    if (threadIdx.x == 0) st->vox_level = level;
+    if (threadIdx.x < ICPMI_VS_WORDS - ICPMI_VS_BASE) sched[ICPMI_VS_BASE + threadIdx.x] = 0u;
+}
+
+// One wave behind every solve of a scheduled handle.  The solve is the one every chain runs and knows nothing of levels: when a checker
+// stops the loop it sets `done`.  This kernel keeps the level's report (iterations, pair count of its first and of its last iteration:
+// the same values again on the dead iterations behind the end), and while a level remains and the stop is no error it makes the stop a
+// level switch: `done` cleared, the Counter at zero, the Differential checker's history empty, the level raised.  T_iter, iter (the total
+// over the levels: what the progress word and the stats carry) and init_q (the Bound checker measures from the registration's start) stay.
+// For the host it does what the solve of a one-size handle does itself: the finished state into the mirror, here with the report beside
+// it (host_report: 13 words of the progress page), then the word.
+__global__ __launch_bounds__(64) void voxel_advance_kernel(IcpState* __restrict__ st, unsigned* __restrict__ sched, int nlevels,
+                                                           unsigned* __restrict__ progress, IcpState* __restrict__ mirror,
+                                                           unsigned* __restrict__ host_report)
+{
+    if (threadIdx.x == 0) {
+        const int L = (int)(st->vox_level & (ICPMI_MAX_VOXEL_LEVELS - 1));
+        const int it = st->iter - (int)sched[ICPMI_VS_BASE];
+        const unsigned pairs = (unsigned)st->pairs;
+        sched[ICPMI_VS_ITERS + L] = (unsigned)it;
+        if (it == 1 && pairs) sched[ICPMI_VS_FIRST + L] = pairs; // (a level whose iteration found no pair did not count it)
+        sched[ICPMI_VS_LAST + L] = pairs;
+        if (st->done && !st->error && L + 1 < nlevels) {
+            st->done = 0; st->stop_reason = 0; st->counter = 0; st->t_done = 0;
+            // the history begins EMPTY: the pose carried over is not an entry (include/icpmi.h), so the first step the checker may count is
+            // the one between the level's first two poses.  The solve has no such state of its own (init_state leaves one entry), so it is
+            // built from states it has: the ring exactly full (hist_n = RING: the level's first pose goes to slot 0 and is measured against
+            // slot RING - 1), that slot a pose 1e30 m away (the step against it is finite and far over any threshold), and every stored step
+            // +inf.  A window that still holds a step from before the level's second pose then has an infinite mean -- not under the
+            // thresholds, and no NaN (inf - inf never forms: the steps are only added) -- and the first window of the level's own steps is
+            // the one behind iteration smoothLength + 1.
+            constexpr int RING = ICPMI_MAX_SMOOTH + 1; // (solve.h: the ring of solve_serial's Differential checker)
+            for (int i = 0; i < RING; ++i) { st->hrot[i] = INFINITY; st->htr[i] = INFINITY; }
+            quat_from_T(st->T_iter, st->hq + 4 * (RING - 1));
+            for (int r = 0; r < 3; ++r) st->ht[3 * (RING - 1) + r] = 1e30;
+            st->hist_n = RING;
+            sched[ICPMI_VS_BASE] = (unsigned)st->iter;
+            st->vox_level = (unsigned)(L + 1);
+        }
+    }
+    __syncthreads(); // thread 0's stores to the state and the report are issued
+    if (__hip_atomic_load(&st->done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
+        if (mirror) mirror_state(st, mirror);
+        if (progress && threadIdx.x < 1 + 3 * ICPMI_MAX_VOXEL_LEVELS) {
+            const int t = threadIdx.x;
+            const unsigned v = t == 0 ? __hip_atomic_load(&st->vox_level, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1u
+                                      : __hip_atomic_load(sched + ICPMI_VS_ITERS + (t - 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            host_report[t] = v;
+        }
+    }
+    if (threadIdx.x == 0) publish_progress(st, progress);
+}
+
 __global__ __launch_bounds__(256) void centre_kernel(BatchSrc src, BatchArgs ba, float mx, float my, float mz, float4* __restrict__ out)
 {
     // blockIdx.y = reading of a batch: its own source pointer, slice blockIdx.y of `out`
@@ -487,13 +545,6 @@ __global__ __launch_bounds__(256) void weights_kernel(int64_t count, LoopCfg lc,
     else if (lc.ext) wt = match_weight<true>(lc, st, d2a[e], nullptr, read_normals, (int)(e / lc.k), normals, s < 0 ? 0 : s, -1, 0.f, ref_scalar, s < 0 ? 0 : s, 0.f);
     else wt = match_weight(lc, st, d2a[e], nullptr, read_normals, (int)(e / lc.k), normals, s < 0 ? 0 : s);
     w[e] = wt;
-}
-
-uint64_t fnv(const void* p, size_t n, uint64_t h)
-{
-    const unsigned char* b = (const unsigned char*)p;
-    for (size_t i = 0; i < n; ++i) { h ^= b[i]; h *= 1099511628211ull; }
-    return h;
 }
 
 } // namespace
@@ -1019,9 +1070,19 @@ static void enqueue_accumulate_solve(icpmi_ctx* c, int64_t n, const LoopCfg& lc,
 
 // the iteration of a VoxelMatcher handle (voxel_path; a single registration): voxel_pairs_kernel fills the point-to-plane slots of the
 // accumulators, the solve reads them as it reads plane-to-plane's (lc.plane_eps: the same epsilon)
-static void enqueue_voxel_solve(icpmi_ctx* c, int64_t n, const LoopCfg& lc, float* d_Tstep, double* d_sums, bool publish)
+static void enqueue_voxel_solve(icpmi_ctx* c, int64_t n, const LoopCfg& lc, float* d_Tstep, double* d_sums, bool publish, bool advance = true)
 {
     voxel_enqueue_pairs(c, n, acc_blocks(n), lc.plane_eps);
+    if (voxel_scheduled(c)) {
+        // a schedule: the solve tells the host nothing -- its stop may be a level switch; voxel_advance_kernel behind it
+        // decides, and mirrors and publishes in its place.  advance = false: one pass at a fixed level (loop_single_step), no switch to make
+        hipLaunchKernelGGL(solve_kernel<false>, dim3(1), dim3(256), 0, c->stream, c->d_state, c->d_selhist, 1, lc, d_Tstep, d_sums, (unsigned*)nullptr,
+                           (IcpState*)nullptr);
+        if (advance)
+            hipLaunchKernelGGL(voxel_advance_kernel, dim3(1), dim3(64), 0, c->stream, c->d_state.get(), c->d_vox_sched.get(), c->vox_levels,
+                               publish ? c->d_progress : (unsigned*)nullptr, c->d_state_mirror, c->d_progress + ICPMI_PROGRESS_VOX_WORD);
+        return;
+    }
     hipLaunchKernelGGL(solve_kernel<false>, dim3(1), dim3(256), 0, c->stream, c->d_state, c->d_selhist, 1, lc, d_Tstep, d_sums,
                        publish ? c->d_progress : (unsigned*)nullptr, c->d_state_mirror);
 }
@@ -1137,6 +1198,8 @@ static icpmi_status enqueue_registration_head(icpmi_ctx* c, const float4* d_scan
     hipLaunchKernelGGL(init_state_kernel, dim3(1), dim3(64), 0, c->stream, c->d_state, (const float*)nullptr, c->reg_seq, c->d_progress,
                        (const unsigned*)(c->d_progress + 32));
     HIP_TRY(c, hipMemsetAsync(c->d_selhist, 0, ICPMI_SELHIST_WORDS * sizeof(unsigned), c->stream));
+    if (voxel_scheduled(c)) // (every registration starts at level 0 with a clean report)
+        hipLaunchKernelGGL(voxel_sched_reset_kernel, dim3(1), dim3(64), 0, c->stream, c->d_state.get(), c->d_vox_sched.get(), 0u);
     HIP_TRY(c, hipGetLastError());
     return ICPMI_OK;
 }
@@ -1173,11 +1236,11 @@ static uint64_t loop_sig(const icpmi_ctx* c, const LoopCfg& lc, const NnRequest&
     sig = fnv(ptrs, sizeof ptrs, sig);
     sig = fnv(&c->grid, sizeof c->grid, sig);
     sig = fnv(&c->map_epoch, sizeof c->map_epoch, sig);
-    if (voxel_path(c)) { // (the voxel size and the table are arguments of voxel_pairs_kernel alone, not part of the LoopCfg)
-        const void* tab = c->d_vox_tab.get();
-        sig = fnv(&c->voxel_size, sizeof c->voxel_size, sig);
-        sig = fnv(&c->vox_gen, sizeof c->vox_gen, sig);
-        sig = fnv(&tab, sizeof tab, sig);
+    if (voxel_path(c)) { // (sizes and tables are arguments of the voxel pair kernels alone, not part of the LoopCfg: the level count, every level's
+                         // size, table generation and table address, and the block the descriptors sit in)
+        const void* sched = c->d_vox_sched.get();
+        sig = voxel_sched_sig(c, sig);
+        sig = fnv(&sched, sizeof sched, sig);
     }
     return fnv(&n, sizeof n, sig);
 }
@@ -1204,6 +1267,13 @@ icpmi_status loop_run(icpmi_ctx* c, const float4* d_scan, const float* d_normals
     if (c->d_reading.ensure(c, (size_t)n + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
     if (d_normals3 && c->d_read_normals.ensure(c, (size_t)n + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
     const bool voxel = voxel_path(c);
+    // a schedule: lc.max_iter bounds a LEVEL (the solve's Counter starts afresh at each), the loop as the host enqueues it
+    // is bounded by levels x that count; the progress word counts the iterations of all levels
+    const bool sched = voxel_scheduled(c);
+    const int total_iter = sched ? (lc.max_iter < 0xfff ? lc.max_iter * c->vox_levels : lc.max_iter) : lc.max_iter;
+    // (the report words of the host page are left alone here: dead iterations of the handle's previous registration may still be writing
+    // their own final values; this registration's advance overwrites them in stream order, in front of its "done" word)
+    if (sched) for (int i = 0; i < 1 + 3 * ICPMI_MAX_VOXEL_LEVELS; ++i) c->vox_report[i] = 0;
     if (voxel) { c->qsorted_n = -1; c->qsorted_src = nullptr; } // (d_reading gets new contents and no sorted copy: a stale one must not be searched in its place)
     else if (c->cfg.knn <= 8 && sort_queries_reserve(c, n) != ICPMI_OK) return ICPMI_ERR_HIP;
     NnRequest req = loop_request(c, lc, batch_of_one(n), d_r2row);
@@ -1216,14 +1286,14 @@ icpmi_status loop_run(icpmi_ctx* c, const float4* d_scan, const float* d_normals
     __atomic_store_n(c->h_progress + 32, c->reg_seq, __ATOMIC_RELEASE);
     // r5 (fast finish, see the end of this function): the finished state reaches the host by itself and carries the device clocks of its
     // start and stop -- no event pair, no copy, no drain
-    const bool fast_ok = !profile && c->d_state_mirror && lc.max_iter < 0xfff;
+    const bool fast_ok = !profile && c->d_state_mirror && total_iter < 0xfff;
     if (!fast_ok) HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
     // A checked loop (Counter + Differential / Bound: what Mapper::processInput runs) as SEGMENT graphs (r3):
     // head + the first S iterations are one graph, S further iterations another; a segment is launched when the progress word
     // says the loop is still running and within S / 2 iterations of the end of what is enqueued.  Iterations past the stop are
     // early-exit kernels (every kernel of the loop returns on st->done): at most S - 1 of them, against eager launches -- and
     // their wider kernel-to-kernel gaps -- for every real iteration.
-    bool segmented = !graph && !profile && c->cfg.use_graph != 0 && (lc.use_diff || lc.use_bound) && lc.max_iter < 0xfff && lc.max_iter > 1;
+    bool segmented = !graph && !profile && c->cfg.use_graph != 0 && (lc.use_diff || lc.use_bound) && total_iter < 0xfff && lc.max_iter > 1;
     const int S = std::min(4, lc.max_iter);
     LoopGraphs& gs = c->graphs;
     const uint64_t sig = (graph || segmented) ? loop_sig(c, lc, req, d_scan, d_normals3, n) : 0;
@@ -1262,7 +1332,7 @@ icpmi_status loop_run(icpmi_ctx* c, const float4* d_scan, const float* d_normals
         // is over) and goes on with ordinary segments only if it is not.
         LoopGraph* head = &gs.seg[0];
         const int L = c->seg_prev_iters;
-        if (L >= 2 && L != S && L <= 24 && L < lc.max_iter) {
+        if (L >= 2 && L != S && L <= 24 && L < total_iter) {
             head = nullptr;
             for (LoopGraph& hd : gs.heads) if (hd.exec && hd.len == L) head = &hd;
             if (!head) {
@@ -1278,7 +1348,7 @@ icpmi_status loop_run(icpmi_ctx* c, const float4* d_scan, const float* d_normals
         HIP_TRY(c, hipGraphLaunch(head->exec, c->stream));
         if (c->cfg.knn <= 8 && !voxel) { c->qsorted_n = n; c->qsorted_src = c->d_reading; } // what the replayed head leaves in d_qsorted
         int launched = head_len;
-        while (launched < lc.max_iter) {
+        while (launched < total_iter) {
             // (behind a predicted head: no look-ahead -- the next segment goes out only once the head has run and the loop is still going)
             const int lead = (launched == head_len && head_len != S) ? 0 : (S > 1 ? S / 2 : 1);
             unsigned v = 0; bool idle = false;
@@ -1299,15 +1369,15 @@ icpmi_status loop_run(icpmi_ctx* c, const float4* d_scan, const float* d_normals
             // Nobody reads the progress word of a fixed-count graph before its last solve: the host waits for "done", which only that solve
             // (or, behind an error, its early-exit path) can report with the loop's last kernel behind it.  The solves in front of it skip
             // the word and with it the system-scope release that goes with the store.
-            const icpmi_status s = capture_loop_graph(c, gs.fixed, sig, [&](NnOutcome* nn) { return enqueue_loop(true, 0, lc.max_iter, nn, true); });
+            const icpmi_status s = capture_loop_graph(c, gs.fixed, sig, [&](NnOutcome* nn) { return enqueue_loop(true, 0, total_iter, nn, true); });
             if (s != ICPMI_OK) return s;
         }
         HIP_TRY(c, hipGraphLaunch(gs.fixed.exec, c->stream));
         if (c->cfg.knn <= 8 && !voxel) { c->qsorted_n = n; c->qsorted_src = c->d_reading; } // what the replayed head leaves in d_qsorted
     } else {
-        const int check_every = (lc.use_diff || lc.use_bound) ? 4 : lc.max_iter;
-        if (profile && c->nn_events.size() < (size_t)2 * lc.max_iter) {
-            while (c->nn_events.size() < (size_t)2 * lc.max_iter) {
+        const int check_every = (lc.use_diff || lc.use_bound) ? 4 : total_iter;
+        if (profile && c->nn_events.size() < (size_t)2 * total_iter) {
+            while (c->nn_events.size() < (size_t)2 * total_iter) {
                 hipEvent_t e; HIP_TRY(c, hipEventCreate(&e)); c->nn_events.push_back(e);
             }
         }
@@ -1316,16 +1386,16 @@ icpmi_status loop_run(icpmi_ctx* c, const float4* d_scan, const float* d_normals
         // a hipMemcpy + hipStreamSynchronize every 4 iterations, ~25 us of idle GPU each), and at most `ahead` iterations
         // run as early-exit kernels after the loop has stopped.
         constexpr int ahead = 2;
-        const bool poll = !profile && (lc.use_diff || lc.use_bound) && lc.max_iter < 0xfff;
+        const bool poll = !profile && (lc.use_diff || lc.use_bound) && total_iter < 0xfff;
         int launched = 0;
         bool stopped = false;
-        for (int it = 0; it < lc.max_iter && !stopped; ++it) {
+        for (int it = 0; it < total_iter && !stopped; ++it) {
             hipEvent_t e0 = profile ? c->nn_events[2 * it] : nullptr, e1 = profile ? c->nn_events[2 * it + 1] : nullptr;
             req.iter = it;
             icpmi_status s = enqueue_iteration(c, n, lc, req, &last, e0, e1);
             if (s != ICPMI_OK) return s;
             ++launched;
-            if (it + 1 >= lc.max_iter) break;
+            if (it + 1 >= total_iter) break;
             if (poll) {
                 // go on as soon as the GPU has finished all but `ahead` of the iterations enqueued so far; an idle stream leaves the word
                 // final (a kernel that stops the loop without passing through the solve kernel cannot leave the host waiting)
@@ -1345,11 +1415,11 @@ icpmi_status loop_run(icpmi_ctx* c, const float4* d_scan, const float* d_normals
         }
         if (profile) {
             // back-to-back event pair: what two records cost with nothing in between (subtracted below)
-            if (c->nn_events.size() < (size_t)2 * lc.max_iter + 2) {
-                while (c->nn_events.size() < (size_t)2 * lc.max_iter + 2) { hipEvent_t e; HIP_TRY(c, hipEventCreate(&e)); c->nn_events.push_back(e); }
+            if (c->nn_events.size() < (size_t)2 * total_iter + 2) {
+                while (c->nn_events.size() < (size_t)2 * total_iter + 2) { hipEvent_t e; HIP_TRY(c, hipEventCreate(&e)); c->nn_events.push_back(e); }
             }
-            HIP_TRY(c, hipEventRecord(c->nn_events[2 * lc.max_iter], c->stream));
-            HIP_TRY(c, hipEventRecord(c->nn_events[2 * lc.max_iter + 1], c->stream));
+            HIP_TRY(c, hipEventRecord(c->nn_events[2 * total_iter], c->stream));
+            HIP_TRY(c, hipEventRecord(c->nn_events[2 * total_iter + 1], c->stream));
             HIP_TRY(c, hipStreamSynchronize(c->stream));
             HIP_TRY(c, hipMemcpy(c->h_state, c->d_state, sizeof(IcpState), hipMemcpyDeviceToHost));
             const int iters_done = c->h_state->iter < launched ? c->h_state->iter : launched;
@@ -1358,7 +1428,7 @@ icpmi_status loop_run(icpmi_ctx* c, const float4* d_scan, const float* d_normals
                 if (hipEventElapsedTime(&ms, c->nn_events[2 * it], c->nn_events[2 * it + 1]) == hipSuccess) { nn_ms_sum += ms; ++nn_cnt; }
             }
             float gap = 0.f;
-            if (hipEventElapsedTime(&gap, c->nn_events[2 * lc.max_iter], c->nn_events[2 * lc.max_iter + 1]) == hipSuccess && nn_cnt) {
+            if (hipEventElapsedTime(&gap, c->nn_events[2 * total_iter], c->nn_events[2 * total_iter + 1]) == hipSuccess && nn_cnt) {
                 nn_ms_sum -= gap * nn_cnt;
                 if (nn_ms_sum < 0.f) nn_ms_sum = 0.f;
             }
@@ -1389,6 +1459,14 @@ icpmi_status loop_run(icpmi_ctx* c, const float4* d_scan, const float* d_normals
     }
 
     fill_stats(c->h_state, lc, n, stats);
+    if (sched) { // (final: the advance wrote it in front of the "done" word, or the stream has drained)
+        __atomic_thread_fence(__ATOMIC_ACQUIRE);
+        for (int i = 0; i < 1 + 3 * ICPMI_MAX_VOXEL_LEVELS; ++i) c->vox_report[i] = (int32_t)__atomic_load_n(c->h_progress + ICPMI_PROGRESS_VOX_WORD + i, __ATOMIC_RELAXED);
+        if (!c->h_state->done) { // (the host's bound ended a loop no checker stopped: the stream has drained, the report is still on the device)
+            c->vox_report[0] = (int32_t)(c->h_state->vox_level & (ICPMI_MAX_VOXEL_LEVELS - 1)) + 1;
+            HIP_TRY(c, hipMemcpy(c->vox_report + 1, c->d_vox_sched.get() + ICPMI_VS_ITERS, 3 * ICPMI_MAX_VOXEL_LEVELS * sizeof(int32_t), hipMemcpyDeviceToHost));
+        }
+    }
     if (segmented) { // what the next checked registration's head graph is cut to (the larger of the last two counts: one dead iteration costs
                      // less than a head that ends one iteration early and a segment behind it)
         const int it_now = c->h_state->error ? 0 : c->h_state->iter;
@@ -1574,7 +1652,11 @@ icpmi_status loop_single_step(icpmi_ctx* c, int64_t n, const LoopCfg& lc, const 
     NnOutcome nn;
     const bool voxel = voxel_path(c); // (the table is current: api.hip built it before the reading went up)
     const icpmi_status s = voxel ? ICPMI_OK : enqueue_match_select(c, n, l1, req, &nn);
-    if (voxel) enqueue_voxel_solve(c, n, l1, d_Tstep, d_sums, true);
+    if (voxel && voxel_scheduled(c)) { // (the level word: enqueue_fresh_states knows nothing of it)
+        const int lvl = c->vox_step_level >= 0 && c->vox_step_level < c->vox_levels ? c->vox_step_level : c->vox_levels - 1;
+        hipLaunchKernelGGL(voxel_sched_reset_kernel, dim3(1), dim3(64), 0, c->stream, c->d_state.get(), c->d_vox_sched.get(), (unsigned)lvl);
+    }
+    if (voxel) enqueue_voxel_solve(c, n, l1, d_Tstep, d_sums, true, false);
     else if (s == ICPMI_OK) {
         enqueue_accumulate_solve(c, n, l1, req.batch, nn, d_Tstep, d_sums);
         if (l1.degen) (void)loop_degen_report(c, l1); // (an error state leaves the sums of an earlier call: degen_ready stays false below)

@@ -1050,7 +1050,7 @@ __global__ __launch_bounds__(256) void patch_normals_kernel(const unsigned* __re
 icpmi_status map_patch_normals(icpmi_ctx* c, const unsigned* d_list, int64_t n_list, const float4* d_raw, const float* d_normals3)
 {
     if (n_list <= 0 || !c->d_normals_sorted || c->m <= 0) return ICPMI_OK;
-    c->vox_ready = false; // (the voxel table's second moments are sums over these normals: voxel.hip rebuilds it at its next use)
+    for (VoxLevel& lv : c->vox) lv.ready = false; // (the voxel tables' second moments are sums over these normals: voxel.hip rebuilds them at their next use)
     const bool with_pn = c->d_map_pn != nullptr && !c->single_level && c->keep_raw;
     hipLaunchKernelGGL(patch_normals_kernel, dim3((int)((n_list + 255) / 256)), dim3(256), 0, c->stream, d_list, n_list, d_raw, c->mean[0], c->mean[1], c->mean[2],
                        c->levels.g[0], (const unsigned*)c->d_cell_start, (const float4*)c->d_map_sorted, d_normals3, c->d_normals_sorted,

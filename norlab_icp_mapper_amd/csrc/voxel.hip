@@ -4,6 +4,8 @@
 //                                   -> head flags + scan -> one wave per voxel sums its run in double -> open-addressing fill (one CAS per voxel)
 //   the iteration's pair sums:      voxel_pairs_kernel: one point load, one probe, the sums of DESIGN.md 4.15 with q = mu and
 //                                   M = (C_v + C(u_p))^-1, into the fixed-point accumulators the existing solve kernel reads
+//   a schedule of sizes (4.21):     one table per level by the same build; voxel_pairs_sched_kernel: the same pair sums with table, mask and
+//                                   size taken from the level descriptors by the level the loop header holds (loop.hip raises it)
 // No float atomics anywhere: two builds of one map give the same bits, and so do two registrations.
 #include "common.h"
 #include <vector>
@@ -234,6 +236,67 @@ __global__ __launch_bounds__(256) void voxel_pairs_kernel(const float4* __restri
     pair_sums_fold<256, 27, false>(acc, cnt, cnt, nullptr, hists); // (weight 1 per pair: sum w = the pair count)
 }
 
+// The pair sums of a handle with a schedule of two or more levels: voxel_pairs_kernel's body, but for where table, mask
+// and size come from.  `sched` is the handle's block of level descriptors (common.h: ICPMI_VS_DESC; 16 dwords, lane l takes dword l & 15),
+// requested with the header and the prefetched points in the one first trip; the current level is the header's vox_level, and the
+// descriptor's four words are readlanes at 4 * level.  (The level is masked to 0..3 and the host fills all four slots with real tables: no
+// value of the word makes the kernel probe an address that is not a table.)  voxel_pairs_kernel keeps serving one-size handles.
+__global__ __launch_bounds__(256) void voxel_pairs_sched_kernel(const float4* __restrict__ reading, const float4* __restrict__ read_normals, int n,
+                                                                IcpState* __restrict__ st, const unsigned* __restrict__ sched, float eps,
+                                                                unsigned* __restrict__ hists)
+{
+    asm volatile("" ::"s"(reading), "s"(read_normals), "s"(n), "s"(st), "s"(sched), "s"(eps), "s"(hists));
+    unsigned hw = hdr_load(st);
+    unsigned dw = sched[ICPMI_VS_DESC + (threadIdx.x & 15)];
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    const int64_t e0 = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    constexpr int PF = 2;
+    float4 pr[PF]; float3 pn[PF];
+#pragma unroll
+    for (int u = 0; u < PF; ++u) {
+        const int64_t e = e0 + u * stride;
+        const bool in = e < n;
+        pr[u] = in ? ld_stream(reading + e) : make_float4(0.f, 0.f, 0.f, 0.f);
+        pn[u] = (in && read_normals) ? *reinterpret_cast<const float3*>(read_normals + e) : make_float3(0.f, 0.f, 0.f);
+    }
+    asm volatile("" : "+v"(hw), "+v"(dw));
+    const HdrView hv{hw}, dv{dw};
+    const int done = hv.i(ICPMI_HDR_W(done));
+    const int lvl = hv.i(ICPMI_HDR_W(vox_level)) & (ICPMI_MAX_VOXEL_LEVELS - 1);
+    const uint4* __restrict__ tab = reinterpret_cast<const uint4*>((uintptr_t)dv.u64(4 * lvl));
+    const unsigned mask = dv.u(4 * lvl + 2);
+    const float size = dv.f(4 * lvl + 3);
+    float T[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) T[i] = hv.f(ICPMI_HDR_W(T_iter) + i);
+    if (done) return;
+    const float g = 1.f - eps;
+    double acc[27];
+#pragma unroll
+    for (int i = 0; i < 27; ++i) acc[i] = 0.0;
+    double cnt = 0.0;
+    auto pair = [&](float4 r, float3 rn) {
+        const float3 p = xf_point(T, r.x, r.y, r.z, r.w);
+        unsigned long long key = 0;
+        VoxHit h;
+        if (!vox_key(p.x, p.y, p.z, size, &key) || !vox_probe(tab, mask, key, &h)) return;
+        cnt += 1.0;
+        const float3 up = unit_or_zero(fmaf(T[8], rn.z, fmaf(T[4], rn.y, T[0] * rn.x)), fmaf(T[9], rn.z, fmaf(T[5], rn.y, T[1] * rn.x)),
+                                       fmaf(T[10], rn.z, fmaf(T[6], rn.y, T[2] * rn.x)));
+        const float nxx = h.a.w, nxy = h.b.x, nxz = h.b.y, nyy = h.b.z, nyz = h.b.w, nzz = h.c.x;
+        const float sxx = 2.f - g * (nxx + up.x * up.x), syy = 2.f - g * (nyy + up.y * up.y), szz = 2.f - g * (nzz + up.z * up.z);
+        const float sxy = -g * (nxy + up.x * up.y), sxz = -g * (nxz + up.x * up.z), syz = -g * (nyz + up.y * up.z);
+        gicp_pair_sums<false>(acc, sxx, sxy, sxz, syy, syz, szz, p, make_float3(p.x - h.a.x, p.y - h.a.y, p.z - h.a.z), 1.0);
+    };
+#pragma unroll
+    for (int u = 0; u < PF; ++u)
+        if (e0 + u * stride < n) pair(pr[u], pn[u]);
+    for (int64_t e = e0 + PF * stride; e < n; e += stride)
+        pair(reading[e], read_normals ? *reinterpret_cast<const float3*>(read_normals + e) : make_float3(0.f, 0.f, 0.f));
+
+    pair_sums_fold<256, 27, false>(acc, cnt, cnt, nullptr, hists);
+}
+
 // the HIP events of a timed diagnostic: created together, destroyed on every way out of the call
 template <int N>
 struct EventSet {
@@ -247,23 +310,27 @@ struct EventSet {
 
 } // namespace
 
-bool voxel_table_current(const icpmi_ctx* c)
+static bool voxel_level_current(const icpmi_ctx* c, int l)
 {
-    return c->vox_ready && c->vox_nv > 0 && c->vox_map_version == c->map_version && c->vox_epoch == c->map_epoch && c->vox_built_size == c->voxel_size;
+    const VoxLevel& v = c->vox[l];
+    return v.ready && v.nv > 0 && v.map_version == c->map_version && v.epoch == c->map_epoch && v.built_size == c->vox_sizes[l];
 }
 
-// Builds the table of the resident map for c->voxel_size unless the handle holds it already (lazily: the first call that needs it after
-// the map or the size changed).  Stream-ordered but for one read-back (voxel count and range flag).  times_ms (may be null): sort, reduce,
-// fill as HIP events measure them (scripts/voxel_bench.py); asking for them forces a rebuild.
-icpmi_status voxel_ensure_table(icpmi_ctx* c, float* times_ms)
+bool voxel_table_current(const icpmi_ctx* c)
 {
-    if (!(c->voxel_size > 0.f)) { c->last_error = "voxel matcher: no voxel size set (icpmi_set_voxel_matcher)"; return ICPMI_ERR_INVALID_ARG; }
-    if (c->m <= 0) { c->last_error = "voxel matcher: no map"; return ICPMI_ERR_INVALID_ARG; }
-    if (!c->has_normals || !c->d_normals_sorted.get()) {
-        c->last_error = "InvalidField: VoxelMatcher needs the descriptor 'normals' on the map"; return ICPMI_ERR_MISSING_NORMALS;
-    }
-    if (!times_ms && voxel_table_current(c)) return ICPMI_OK;
-    c->vox_ready = false;
+    for (int l = 0; l < c->vox_levels; ++l) if (!voxel_level_current(c, l)) return false;
+    return c->vox_levels > 0;
+}
+
+// Builds level l's table of the resident map for c->vox_sizes[l] unless the handle holds it already (lazily: the first call that needs it
+// after the map or the size changed).  Stream-ordered but for one read-back (voxel count and range flag).  times_ms (may be null): sort,
+// reduce, fill as HIP events measure them (scripts/voxel_bench.py); asking for them forces a rebuild.
+static icpmi_status voxel_ensure_level(icpmi_ctx* c, int l, float* times_ms)
+{
+    VoxLevel& lv = c->vox[l];
+    const float size = c->vox_sizes[l];
+    if (!times_ms && voxel_level_current(c, l)) return ICPMI_OK;
+    lv.ready = false;
     const int64_t m = c->m;
     const int blocks = (int)((m + 255) / 256);
     unsigned long long* d_keys = scratch_get<unsigned long long>(c, 0, (size_t)2 * m + 2);
@@ -280,7 +347,7 @@ icpmi_status voxel_ensure_table(icpmi_ctx* c, float* times_ms)
 
     HIP_TRY(c, hipMemsetAsync(d_bad, 0, sizeof(unsigned), c->stream));
     if (ev[0]) (void)hipEventRecord(ev[0], c->stream);
-    hipLaunchKernelGGL(vox_key_kernel, dim3(blocks), dim3(256), 0, c->stream, (const float4*)c->d_map_sorted, m, c->voxel_size, d_keys, d_vals, d_bad);
+    hipLaunchKernelGGL(vox_key_kernel, dim3(blocks), dim3(256), 0, c->stream, (const float4*)c->d_map_sorted, m, size, d_keys, d_vals, d_bad);
     HIP_TRY(c, hipGetLastError());
     int half = 0;
     { const icpmi_status s = radix_sort_pairs(c, d_keys, d_vals, m, 63, d_tab, &half); if (s != ICPMI_OK) return s; }
@@ -300,46 +367,107 @@ icpmi_status voxel_ensure_table(icpmi_ctx* c, float* times_ms)
     if (nv <= 0 || nv > m) { c->last_error = "voxel matcher: bad voxel count"; return ICPMI_ERR_HIP; }
     unsigned cap = 2;
     while ((uint64_t)cap < 2 * (uint64_t)nv) cap <<= 1;
-    if (c->d_vox_keys.ensure(c, (size_t)nv) != ICPMI_OK || c->d_vox_rec.ensure(c, (size_t)3 * nv) != ICPMI_OK ||
-        c->d_vox_tab.ensure(c, (size_t)4 * cap) != ICPMI_OK) return ICPMI_ERR_HIP;
+    if (lv.keys.ensure(c, (size_t)nv) != ICPMI_OK || lv.rec.ensure(c, (size_t)3 * nv) != ICPMI_OK ||
+        lv.tab.ensure(c, (size_t)4 * cap) != ICPMI_OK) return ICPMI_ERR_HIP;
     hipLaunchKernelGGL(vox_start_kernel, dim3(blocks), dim3(256), 0, c->stream, (const unsigned*)d_head, (const unsigned*)d_pos, m, d_vstart);
     hipLaunchKernelGGL(vox_reduce_kernel, dim3((int)((nv + 3) / 4)), dim3(256), 0, c->stream, skeys, svals, (const unsigned*)d_vstart, nv,
-                       (const float4*)c->d_map_sorted, (const float4*)c->d_normals_sorted, c->d_vox_keys.get(), c->d_vox_rec.get());
+                       (const float4*)c->d_map_sorted, (const float4*)c->d_normals_sorted, lv.keys.get(), lv.rec.get());
     HIP_TRY(c, hipGetLastError());
     if (ev[2]) (void)hipEventRecord(ev[2], c->stream);
-    HIP_TRY(c, hipMemsetAsync(c->d_vox_tab.get(), 0xff, (size_t)cap * 64, c->stream));
-    hipLaunchKernelGGL(vox_fill_kernel, dim3((int)((nv + 255) / 256)), dim3(256), 0, c->stream, (const unsigned long long*)c->d_vox_keys.get(),
-                       (const float4*)c->d_vox_rec.get(), nv, c->d_vox_tab.get(), cap - 1);
+    HIP_TRY(c, hipMemsetAsync(lv.tab.get(), 0xff, (size_t)cap * 64, c->stream));
+    hipLaunchKernelGGL(vox_fill_kernel, dim3((int)((nv + 255) / 256)), dim3(256), 0, c->stream, (const unsigned long long*)lv.keys.get(),
+                       (const float4*)lv.rec.get(), nv, lv.tab.get(), cap - 1);
     HIP_TRY(c, hipGetLastError());
     if (ev[3]) (void)hipEventRecord(ev[3], c->stream);
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (times_ms) {
         for (int i = 0; i < 3; ++i) { times_ms[i] = 0.f; (void)hipEventElapsedTime(&times_ms[i], ev[i], ev[i + 1]); }
     }
-    c->vox_nv = nv; c->vox_mask = cap - 1;
-    c->vox_map_version = c->map_version; c->vox_epoch = c->map_epoch; c->vox_built_size = c->voxel_size;
-    ++c->vox_gen;
-    c->vox_ready = true;
+    lv.nv = nv; lv.mask = cap - 1;
+    lv.map_version = c->map_version; lv.epoch = c->map_epoch; lv.built_size = size;
+    ++lv.gen;
+    lv.ready = true;
     return ICPMI_OK;
+}
+
+// Every level of the handle's schedule, by the one build path, coarsest first; then, with two or more levels, the level descriptors on the
+// device (uploaded again whenever a table or a size is not the one they describe).  times_ms: the finest level's build, forced.
+icpmi_status voxel_ensure_table(icpmi_ctx* c, float* times_ms)
+{
+    if (c->vox_levels <= 0 || !(c->voxel_size > 0.f)) { c->last_error = "voxel matcher: no voxel size set (icpmi_set_voxel_matcher)"; return ICPMI_ERR_INVALID_ARG; }
+    if (c->m <= 0) { c->last_error = "voxel matcher: no map"; return ICPMI_ERR_INVALID_ARG; }
+    if (!c->has_normals || !c->d_normals_sorted.get()) {
+        c->last_error = "InvalidField: VoxelMatcher needs the descriptor 'normals' on the map"; return ICPMI_ERR_MISSING_NORMALS;
+    }
+    const int L = c->vox_levels;
+    for (int l = 0; l < L; ++l) {
+        const icpmi_status s = voxel_ensure_level(c, l, l == L - 1 ? times_ms : nullptr);
+        if (s != ICPMI_OK) return s;
+    }
+    if (L < 2) return ICPMI_OK;
+    unsigned desc[4 * ICPMI_MAX_VOXEL_LEVELS];
+    for (int l = 0; l < ICPMI_MAX_VOXEL_LEVELS; ++l) { // (the slots behind the last level repeat it: whatever the level word holds, the kernel probes a real table)
+        const int src = l < L ? l : L - 1;
+        const unsigned long long a = (unsigned long long)(uintptr_t)c->vox[src].tab.get();
+        desc[4 * l + 0] = (unsigned)a; desc[4 * l + 1] = (unsigned)(a >> 32); desc[4 * l + 2] = c->vox[src].mask;
+        memcpy(desc + 4 * l + 3, c->vox_sizes + src, sizeof(float));
+    }
+    const uint64_t sig = voxel_sched_sig(c, 0);
+    if (c->d_vox_sched.get() && c->vox_sched_sig == sig) return ICPMI_OK;
+    if (c->d_vox_sched.ensure(c, ICPMI_VS_WORDS) != ICPMI_OK) return ICPMI_ERR_HIP;
+    HIP_TRY(c, hipMemsetAsync(c->d_vox_sched.get(), 0, ICPMI_VS_WORDS * sizeof(unsigned), c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->d_vox_sched.get() + ICPMI_VS_DESC, desc, sizeof desc, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream)); // (desc is on this frame)
+    c->vox_sched_sig = voxel_sched_sig(c, 0);
+    return ICPMI_OK;
+}
+
+// what a captured loop, and the uploaded descriptors, are valid for on the voxel path: the level count and every level's size, table
+// generation and table address (h: the hash so far)
+uint64_t voxel_sched_sig(const icpmi_ctx* c, uint64_t h)
+{
+    h = fnv(&c->vox_levels, sizeof c->vox_levels, h ? h : 1469598103934665603ull);
+    for (int l = 0; l < c->vox_levels; ++l) {
+        const void* tab = c->vox[l].tab.get();
+        h = fnv(&c->vox_sizes[l], sizeof(float), h);
+        h = fnv(&c->vox[l].gen, sizeof c->vox[l].gen, h);
+        h = fnv(&tab, sizeof tab, h);
+    }
+    return h;
 }
 
 // the iteration's pair sums on the handle's stream (no allocation, no wait: loop.hip captures it); the table is current (voxel_ensure_table)
 void voxel_enqueue_pairs(icpmi_ctx* c, int64_t n, int nb, float eps)
 {
+    if (c->vox_levels >= 2) { // (a schedule: the level is read on the device)
+        hipLaunchKernelGGL(voxel_pairs_sched_kernel, dim3(nb), dim3(256), 0, c->stream, (const float4*)c->d_reading, (const float4*)c->d_read_normals, (int)n,
+                           c->d_state.get(), (const unsigned*)c->d_vox_sched.get(), eps, c->d_selhist.get());
+        return;
+    }
     hipLaunchKernelGGL(voxel_pairs_kernel, dim3(nb), dim3(256), 0, c->stream, (const float4*)c->d_reading, (const float4*)c->d_read_normals, (int)n,
-                       c->d_state.get(), (const uint4*)c->d_vox_tab.get(), c->vox_mask, c->voxel_size, eps, c->d_selhist.get());
+                       c->d_state.get(), (const uint4*)c->vox[0].tab.get(), c->vox[0].mask, c->voxel_size, eps, c->d_selhist.get());
 }
 
-icpmi_status voxel_get_map(icpmi_ctx* c, int64_t cap, int32_t* ijk3, float* mean3, float* moments6, int32_t* count, int64_t* n_voxels)
+// level: of the schedule, 0 the coarsest; -1 the finest
+static icpmi_status voxel_level_arg(icpmi_ctx* c, const char* who, int* level)
+{
+    if (*level == -1) *level = c->vox_levels - 1;
+    if (*level < 0 || *level >= c->vox_levels) { c->last_error = std::string(who) + ": no such level in the voxel schedule"; return ICPMI_ERR_INVALID_ARG; }
+    return ICPMI_OK;
+}
+
+icpmi_status voxel_get_map(icpmi_ctx* c, int level, int64_t cap, int32_t* ijk3, float* mean3, float* moments6, int32_t* count, int64_t* n_voxels)
 {
     { const icpmi_status s = voxel_ensure_table(c, nullptr); if (s != ICPMI_OK) return s; }
-    const int64_t nv = c->vox_nv;
+    { const icpmi_status s = voxel_level_arg(c, "get_voxel_map", &level); if (s != ICPMI_OK) return s; }
+    const VoxLevel& lv = c->vox[level];
+    const int64_t nv = lv.nv;
     if (n_voxels) *n_voxels = nv;
     if (cap < nv) { c->last_error = "get_voxel_map: capacity below the voxel count (*n_voxels has it)"; return ICPMI_ERR_INVALID_ARG; }
     std::vector<unsigned long long> keys((size_t)nv);
     std::vector<float> rec((size_t)12 * nv);
-    HIP_TRY(c, hipMemcpyAsync(keys.data(), c->d_vox_keys.get(), (size_t)nv * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(rec.data(), c->d_vox_rec.get(), (size_t)nv * 12 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(keys.data(), lv.keys.get(), (size_t)nv * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(rec.data(), lv.rec.get(), (size_t)nv * 12 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     for (int64_t v = 0; v < nv; ++v) {
         const float* r = rec.data() + 12 * v;
@@ -355,16 +483,18 @@ icpmi_status voxel_get_map(icpmi_ctx* c, int64_t cap, int32_t* ijk3, float* mean
     return ICPMI_OK;
 }
 
-icpmi_status voxel_lookup(icpmi_ctx* c, const float* q4_centred, int64_t n, int32_t* voxel)
+icpmi_status voxel_lookup(icpmi_ctx* c, int level, const float* q4_centred, int64_t n, int32_t* voxel)
 {
     { const icpmi_status s = voxel_ensure_table(c, nullptr); if (s != ICPMI_OK) return s; }
+    { const icpmi_status s = voxel_level_arg(c, "voxel_lookup", &level); if (s != ICPMI_OK) return s; }
+    const VoxLevel& lv = c->vox[level];
     if (n == 0) return ICPMI_OK;
     DevBuf<float4> d_q; DevBuf<int> d_out;
     HIP_TRY(c, d_q.alloc((size_t)n));
     HIP_TRY(c, d_out.alloc((size_t)n));
     HIP_TRY(c, hipMemcpyAsync(d_q.get(), q4_centred, (size_t)n * sizeof(float4), hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(vox_lookup_kernel, dim3((int)((n + 255) / 256)), dim3(256), 0, c->stream, (const float4*)d_q.get(), n, c->voxel_size,
-                       (const uint4*)c->d_vox_tab.get(), c->vox_mask, d_out.get());
+    hipLaunchKernelGGL(vox_lookup_kernel, dim3((int)((n + 255) / 256)), dim3(256), 0, c->stream, (const float4*)d_q.get(), n, c->vox_sizes[level],
+                       (const uint4*)lv.tab.get(), lv.mask, d_out.get());
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipMemcpyAsync(voxel, d_out.get(), (size_t)n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -376,6 +506,7 @@ icpmi_status voxel_lookup(icpmi_ctx* c, const float* q4_centred, int64_t n, int3
 icpmi_status voxel_lookup_times(icpmi_ctx* c, const float* q4_centred, int64_t n, int reps, float ms[2], int64_t* mismatch)
 {
     { const icpmi_status s = voxel_ensure_table(c, nullptr); if (s != ICPMI_OK) return s; }
+    const VoxLevel& lv = c->vox[c->vox_levels - 1]; // (the finest level)
     DevBuf<float4> d_q; DevBuf<int> d_a, d_b;
     HIP_TRY(c, d_q.alloc((size_t)n));
     HIP_TRY(c, d_a.alloc((size_t)n));
@@ -388,12 +519,12 @@ icpmi_status voxel_lookup_times(icpmi_ctx* c, const float* q4_centred, int64_t n
     for (int pass = 0; pass < 2; ++pass) { // (pass 0 warms both)
         (void)hipEventRecord(ev[0], c->stream);
         for (int r = 0; r < reps; ++r)
-            hipLaunchKernelGGL(vox_lookup_kernel, grid, dim3(256), 0, c->stream, (const float4*)d_q.get(), n, c->voxel_size, (const uint4*)c->d_vox_tab.get(),
-                               c->vox_mask, d_a.get());
+            hipLaunchKernelGGL(vox_lookup_kernel, grid, dim3(256), 0, c->stream, (const float4*)d_q.get(), n, c->voxel_size, (const uint4*)lv.tab.get(),
+                               lv.mask, d_a.get());
         (void)hipEventRecord(ev[1], c->stream);
         for (int r = 0; r < reps; ++r)
             hipLaunchKernelGGL(vox_lookup_bsearch_kernel, grid, dim3(256), 0, c->stream, (const float4*)d_q.get(), n, c->voxel_size,
-                               (const unsigned long long*)c->d_vox_keys.get(), c->vox_nv, d_b.get());
+                               (const unsigned long long*)lv.keys.get(), lv.nv, d_b.get());
         (void)hipEventRecord(ev[2], c->stream);
     }
     const hipError_t se = hipStreamSynchronize(c->stream);

@@ -70,6 +70,25 @@ void GpuICPSequence::setVoxelMatcher(float size)
 {
     check(h, icpmi_set_voxel_matcher(h, size));
     voxelSize = size;
+    voxelSizes.clear();
+}
+
+// icpmi_set_voxel_schedule: 1 to 4 voxel sizes, strictly descending (an empty list: off); handle state like setVoxelMatcher
+void GpuICPSequence::setVoxelSchedule(const std::vector<float>& sizes)
+{
+    check(h, icpmi_set_voxel_schedule(h, sizes.data(), (int32_t)sizes.size()));
+    voxelSizes = sizes;
+    voxelSize = sizes.empty() ? 0.f : sizes.back();
+}
+
+// icpmi_get_voxel_schedule_report of the last registration: one entry per level entered
+std::vector<GpuICPSequence::VoxelLevelReport> GpuICPSequence::voxelScheduleReport() const
+{
+    int32_t levels = 0, it[4], pf[4], pl[4];
+    check(h, icpmi_get_voxel_schedule_report(h, &levels, it, pf, pl));
+    std::vector<VoxelLevelReport> out;
+    for (int l = 0; l < levels && l < 4; ++l) out.push_back({it[l], pf[l], pl[l]});
+    return out;
 }
 
 void GpuICPSequence::recreate()
@@ -98,7 +117,7 @@ void GpuICPSequence::setDefault()
     cfg.use_differential = 1;
     recreate();
     check(h, icpmi_set_intensity_weight(h, 0.f)); // (handle state, which icpmi_set_config leaves: a chain loaded before may have set it)
-    voxelSize = 0.f;
+    voxelSize = 0.f; voxelSizes.clear();
     check(h, icpmi_set_voxel_matcher(h, 0.f));    // (likewise)
     readingDataPointsFilters = std::make_shared<DataPointsFilters>();
     readingDataPointsFilters->ctx = h;
@@ -127,18 +146,36 @@ std::pair<std::string, yaml::Node> singleEntry(const yaml::Node& n, const std::s
 }
 
 // the `matcher:` entry of an ICP chain into the configuration; maxDistField = KDTreeVarDistMatcher's descriptor name, empty for KDTreeMatcher
-void parseMatcher(const yaml::Node& matcher, icpmi_config& cfg, std::string& maxDistField, float* voxelSize)
+void parseMatcher(const yaml::Node& matcher, icpmi_config& cfg, std::string& maxDistField, float* voxelSize, std::vector<float>* voxelSizes)
 {
     maxDistField.clear();
     cfg.var_dist = 0;
     if (voxelSize) *voxelSize = 0.f;
+    if (voxelSizes) voxelSizes->clear();
     auto e = singleEntry(matcher, "matcher");
     if (e.first == "VoxelMatcher") {
         // voxelised plane-to-plane ICP (not libpointmatcher's; include/icpmi.h: icpmi_set_voxel_matcher): a reading point is paired with the
         // map voxel it falls into -- no search, hence no knn / maxDist / epsilon
-        requireKnown(e.second, {"voxelSize"}, "VoxelMatcher");
-        const float size = e.second["voxelSize"] ? e.second["voxelSize"].as<float>() : 1.f;
-        if (!std::isfinite(size) || !(size > 0.f)) throw InvalidParameter("VoxelMatcher: voxelSize must be finite and > 0");
+        requireKnown(e.second, {"voxelSize", "voxelSizes"}, "VoxelMatcher");
+        if (e.second["voxelSize"] && e.second["voxelSizes"])
+            throw InvalidParameter("VoxelMatcher: voxelSize and voxelSizes are one parameter said two ways: give one of them");
+        float size = 1.f;
+        if (e.second["voxelSizes"]) {
+            // a schedule, coarsest first: the rules of icpmi_set_voxel_schedule (include/icpmi.h)
+            const yaml::Node& list = e.second["voxelSizes"];
+            if (!list.IsSequence() || list.seq.empty() || list.seq.size() > 4) throw InvalidParameter("VoxelMatcher: voxelSizes takes 1 to 4 voxel sizes");
+            if (!voxelSizes) throw InvalidParameter("VoxelMatcher: voxelSizes is not available here");
+            for (const yaml::Node& item : list.seq) {
+                const float v = item.as<float>();
+                if (!std::isfinite(v) || !(v > 0.f)) throw InvalidParameter("VoxelMatcher: every voxel size of voxelSizes must be finite and > 0");
+                if (!voxelSizes->empty() && !(v < voxelSizes->back())) throw InvalidParameter("VoxelMatcher: voxelSizes must be strictly descending (coarsest first)");
+                voxelSizes->push_back(v);
+            }
+            size = voxelSizes->back();
+        } else {
+            size = e.second["voxelSize"] ? e.second["voxelSize"].as<float>() : 1.f;
+            if (!std::isfinite(size) || !(size > 0.f)) throw InvalidParameter("VoxelMatcher: voxelSize must be finite and > 0");
+        }
         if (!voxelSize) throw InvalidParameter("VoxelMatcher: not available here");
         *voxelSize = size;
         // the loop reads none of KDTreeMatcher's parameters; getResidualError, which scores the pose through the nearest-neighbour matcher,
@@ -259,7 +296,8 @@ void GpuICPSequence::loadFromYamlNode(const yaml::Node& icp)
 
     maxDistFieldName.clear();
     voxelSize = 0.f;
-    if (icp["matcher"]) parseMatcher(icp["matcher"], cfg, maxDistFieldName, &voxelSize);
+    voxelSizes.clear();
+    if (icp["matcher"]) parseMatcher(icp["matcher"], cfg, maxDistFieldName, &voxelSize, &voxelSizes);
     cfg.n_outlier = 0;
     genericDescName.clear(); genericReadDescName.clear();
     if (icp["outlierFilters"].IsSequence())
@@ -359,7 +397,8 @@ void GpuICPSequence::loadFromYamlNode(const yaml::Node& icp)
     check(h, icpmi_set_plane_epsilon(h, planeEpsilon));
     check(h, icpmi_set_plane_pair_model(h, planeModel));
     check(h, icpmi_set_intensity_weight(h, intensity.weight));
-    check(h, icpmi_set_voxel_matcher(h, voxelSize));
+    if (voxelSizes.empty()) check(h, icpmi_set_voxel_matcher(h, voxelSize));
+    else check(h, icpmi_set_voxel_schedule(h, voxelSizes.data(), (int32_t)voxelSizes.size()));
     auto chain = [&](const char* key) -> std::shared_ptr<DataPointsFilters> {
         if (!icp[key] || !icp[key].IsSequence() || icp[key].seq.empty()) return nullptr;
         return std::make_shared<DataPointsFilters>(icp[key], h);

@@ -28,7 +28,8 @@ void requireKnown(const yaml::Node& params, std::initializer_list<const char*> k
 std::pair<std::string, yaml::Node> singleEntry(const yaml::Node& n, const std::string& what);
 // the `matcher:` entry of an ICP chain (KDTreeMatcher | KDTreeVarDistMatcher) into cfg; maxDistField = the descriptor name of a
 // KDTreeVarDistMatcher (default maxSearchDist), empty for KDTreeMatcher.  Needs no GPU.
-void parseMatcher(const yaml::Node& matcher, icpmi_config& cfg, std::string& maxDistField, float* voxelSize = nullptr); // voxelSize: VoxelMatcher.voxelSize, 0 for the others (null: VoxelMatcher is refused)
+void parseMatcher(const yaml::Node& matcher, icpmi_config& cfg, std::string& maxDistField, float* voxelSize = nullptr, // voxelSize: VoxelMatcher.voxelSize (the finest of voxelSizes), 0 for the others (null: VoxelMatcher is refused)
+                  std::vector<float>* voxelSizes = nullptr);                                                            // voxelSizes: VoxelMatcher.voxelSizes, empty when the entry has none (null: the key is refused)
 // the `errorMinimizer:` entry into cfg (minimizer, force2D / force4DOF, covariance, degeneracy options); planeEpsilon = the epsilon of a
 // PlaneToPlaneErrorMinimizer (default 0.001; the others leave it alone); planeModel = ICPMI_PLANE_MODEL_SYMMETRIC under
 // SymmetricPointToPlaneErrorMinimizer, which travels as ICPMI_MIN_PLANE_TO_PLANE (the others leave it alone).  Needs no GPU.
@@ -108,6 +109,10 @@ public:
     void setDefault();                                 // PM::ICPSequence::setDefault
     void setVoxelMatcher(float size);                  // icpmi_set_voxel_matcher (0: off): VoxelMatcher on a PlaneToPlaneErrorMinimizer chain
     float getVoxelMatcher() const { return voxelSize; }
+    void setVoxelSchedule(const std::vector<float>& sizes);   // icpmi_set_voxel_schedule: coarse-to-fine over 1 to 4 voxel sizes (empty: off)
+    const std::vector<float>& getVoxelSchedule() const { return voxelSizes; }
+    struct VoxelLevelReport { int iterations, pairsFirst, pairsLast; };
+    std::vector<VoxelLevelReport> voxelScheduleReport() const; // icpmi_get_voxel_schedule_report: the last registration, level by level
     void loadFromYamlNode(const yaml::Node& icpNode);  // the `icp:` sub-tree
     bool setMap(const DataPoints& map);                // false on an empty cloud, state unchanged
     bool hasMap() const;
@@ -188,6 +193,7 @@ private:
     icpmi_stats lastStats{};
     float planeEpsilon = 1e-3f;                        // PlaneToPlaneErrorMinimizer.epsilon (icpmi_set_plane_epsilon)
     float voxelSize = 0.f;                             // VoxelMatcher.voxelSize (icpmi_set_voxel_matcher; 0: a KDTree matcher)
+    std::vector<float> voxelSizes;                     // VoxelMatcher.voxelSizes (icpmi_set_voxel_schedule; empty: voxelSize alone)
     int planeModel = ICPMI_PLANE_MODEL_GICP;           // ... and its pair model (icpmi_set_plane_pair_model): SymmetricPointToPlaneErrorMinimizer
     size_t stagedPoints = 0;                           // size of the scan kept on the GPU by registerWithPrior
     std::string genericDescName;                       // GenericDescriptorOutlierFilter.descName (empty: no such filter)

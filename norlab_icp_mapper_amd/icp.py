@@ -104,6 +104,26 @@ def _check_voxel_size(size):
     return size
 
 
+VOXEL_MAX_LEVELS = 4
+
+
+def _check_voxel_sizes(sizes):
+    """The rules of icpmi_set_voxel_schedule: 1 to 4 sizes, each finite and > 0, strictly descending (coarsest first)."""
+    if isinstance(sizes, (str, bytes)) or not hasattr(sizes, "__iter__"):
+        raise InvalidParameter("VoxelMatcher: voxelSizes must be a list of 1 to 4 voxel sizes")
+    try:
+        sizes = [float(v) for v in sizes]
+    except (TypeError, ValueError):
+        raise InvalidParameter("VoxelMatcher: voxelSizes must be a list of numbers")
+    if not 1 <= len(sizes) <= VOXEL_MAX_LEVELS:
+        raise InvalidParameter("VoxelMatcher: voxelSizes takes 1 to 4 voxel sizes")
+    if not all(math.isfinite(v) and v > 0.0 for v in sizes):
+        raise InvalidParameter("VoxelMatcher: every voxel size of voxelSizes must be finite and > 0")
+    if any(not b < a for a, b in zip(sizes, sizes[1:])):
+        raise InvalidParameter("VoxelMatcher: voxelSizes must be strictly descending (coarsest first)")
+    return sizes
+
+
 def _check_plane_model(model):
     if model not in _PLANE_MODELS:
         raise InvalidParameter(f"plane_model must be one of {sorted(_PLANE_MODELS)}, not {model!r}")
@@ -176,15 +196,22 @@ def config_from_yaml_chain(chain, **engine):
     name, p = single(matcher, "matcher")
     max_dist_field = None
     voxel_size = None
+    voxel_sizes = None
     if name == "VoxelMatcher":
         # voxelised plane-to-plane ICP (not libpointmatcher's; include/icpmi.h: icpmi_set_voxel_matcher): a reading point is paired with the
         # map voxel it falls into -- no search, hence no knn / maxDist / epsilon
         for key in p:
-            if key != "voxelSize":
+            if key not in ("voxelSize", "voxelSizes"):
                 raise InvalidParameter(f"VoxelMatcher: unknown parameter {key}")
-        voxel_size = _check_voxel_size(p.get("voxelSize", VOXEL_SIZE_DEFAULT))
-        if not voxel_size > 0.0:
-            raise InvalidParameter("VoxelMatcher: voxelSize must be finite and > 0")
+        if "voxelSize" in p and "voxelSizes" in p:
+            raise InvalidParameter("VoxelMatcher: voxelSize and voxelSizes are one parameter said two ways: give one of them")
+        if "voxelSizes" in p:  # a schedule, coarsest first (include/icpmi.h: icpmi_set_voxel_schedule)
+            voxel_sizes = _check_voxel_sizes(p["voxelSizes"])
+            voxel_size = voxel_sizes[-1]
+        else:
+            voxel_size = _check_voxel_size(p.get("voxelSize", VOXEL_SIZE_DEFAULT))
+            if not voxel_size > 0.0:
+                raise InvalidParameter("VoxelMatcher: voxelSize must be finite and > 0")
     elif name == "KDTreeVarDistMatcher":
         # every reading point searches within its own radius: the reading's 1-row descriptor `maxDistField` (ICPSequence.__call__ hands it over)
         for key in p:
@@ -340,6 +367,8 @@ def config_from_yaml_chain(chain, **engine):
         cfg.max_dist_field = max_dist_field  # (a Python attribute next to the C fields: the descriptor name is the host's business)
     if voxel_size is not None:
         cfg.voxel_size = voxel_size  # (likewise: ICPSequence hands it to icpmi_set_voxel_matcher)
+    if voxel_sizes is not None:
+        cfg.voxel_sizes = voxel_sizes  # (... and the schedule to icpmi_set_voxel_schedule)
     if plane_epsilon is not None:
         cfg.plane_epsilon = plane_epsilon  # (likewise: icpmi_config has no word left; ICPSequence hands it to icpmi_set_plane_epsilon)
     if plane_model is not None:
@@ -533,18 +562,26 @@ class _ErrorMinimizerView:
 class ICPSequence:
     """``PM::ICPSequence`` backed by one icpmi handle (one GPU, one stream)."""
 
-    def __init__(self, cfg=None, plane_epsilon=None, plane_model=None, intensity_weight=None, intensity_knn=None, voxel_size=None, **kw):
+    def __init__(self, cfg=None, plane_epsilon=None, plane_model=None, intensity_weight=None, intensity_knn=None, voxel_size=None, voxel_sizes=None, **kw):
         """plane_epsilon: epsilon of PlaneToPlaneErrorMinimizer (icpmi_set_plane_epsilon; default: the chain's, else 1e-3)
         plane_model: "gicp" | "symmetric", the pair model of minimizer 3 (icpmi_set_plane_pair_model; default: the chain's, else "gicp")
         intensity_weight: 1 - lambdaGeometric of the photometric term on minimizer 2 (icpmi_set_intensity_weight; default: the chain's, else 0 = off)
-        intensity_knn: neighbours of a map-side intensity gradient, setMapIntensity's default (default: the chain's, else 10)"""
+        intensity_knn: neighbours of a map-side intensity gradient, setMapIntensity's default (default: the chain's, else 10)
+        voxel_size: VoxelMatcher's voxel size (icpmi_set_voxel_matcher; default: the chain's, else off)
+        voxel_sizes: a schedule of 1 to 4 voxel sizes, coarsest first (icpmi_set_voxel_schedule; default: the chain's); not with voxel_size"""
         self._lib = _capi.load()
         self.cfg = cfg if cfg is not None else default_config(**kw)
         if plane_epsilon is None:
             plane_epsilon = getattr(self.cfg, "plane_epsilon", None)
         if plane_epsilon is not None:
             plane_epsilon = _check_plane_epsilon(plane_epsilon)
-        if voxel_size is None:
+        if voxel_size is not None and voxel_sizes is not None:
+            raise InvalidParameter("VoxelMatcher: voxel_size and voxel_sizes are one parameter said two ways: give one of them")
+        if voxel_sizes is None and voxel_size is None:
+            voxel_sizes = getattr(self.cfg, "voxel_sizes", None)
+        if voxel_sizes is not None:
+            voxel_sizes = _check_voxel_sizes(voxel_sizes)
+        elif voxel_size is None:
             voxel_size = getattr(self.cfg, "voxel_size", None)
         if voxel_size is not None:
             voxel_size = _check_voxel_size(voxel_size)
@@ -573,7 +610,9 @@ class ICPSequence:
             self.setPlaneEpsilon(plane_epsilon)
         if plane_model is not None:
             self.setPlaneModel(plane_model)
-        if voxel_size is not None:
+        if voxel_sizes is not None:
+            self.setVoxelSchedule(voxel_sizes)
+        elif voxel_size is not None:
             self.setVoxelMatcher(voxel_size)
         if intensity_weight is not None:
             self.setIntensityWeight(intensity_weight)
@@ -602,26 +641,54 @@ class ICPSequence:
         self._check(self._lib.icpmi_get_voxel_matcher(self._h, C.byref(out)))
         return out.value
 
-    def voxelMap(self):
+    def setVoxelSchedule(self, sizes):
+        """icpmi_set_voxel_schedule: 1 to 4 voxel sizes, strictly descending -- the registration runs them coarse to fine, every level on the
+        chain's checkers, the level switch on the device; an empty list switches the matcher off.  Handle state like
+        setVoxelMatcher, which is a schedule of one."""
+        sizes = _check_voxel_sizes(sizes) if len(sizes) else []
+        arr = (C.c_float * max(1, len(sizes)))(*sizes)
+        self._check(self._lib.icpmi_set_voxel_schedule(self._h, arr, len(sizes)))
+
+    def getVoxelSchedule(self):
+        arr, n = (C.c_float * VOXEL_MAX_LEVELS)(), C.c_int32(0)
+        self._check(self._lib.icpmi_get_voxel_schedule(self._h, arr, C.byref(n)))
+        return [arr[i] for i in range(n.value)]
+
+    def voxelScheduleReport(self):
+        """icpmi_get_voxel_schedule_report of the last registration: a list with one (iterations, pairs_first, pairs_last) per level entered"""
+        lv = C.c_int32(0)
+        it, pf, pl = ((C.c_int32 * VOXEL_MAX_LEVELS)() for _ in range(3))
+        self._check(self._lib.icpmi_get_voxel_schedule_report(self._h, C.byref(lv), it, pf, pl))
+        return [(it[i], pf[i], pl[i]) for i in range(lv.value)]
+
+    def voxelMap(self, level=None):
         """icpmi_get_voxel_map: (ijk (V, 3) int32, mean (V, 3) in the centred frame, moments (V, 6): xx xy xz yy yz zz, count (V,)) in
-        ascending key order"""
+        ascending key order; level: of the schedule (0 = the coarsest; icpmi_get_voxel_map_level), None = the finest"""
+        def call(cap, *arrs):
+            if level is None:
+                return self._lib.icpmi_get_voxel_map(self._h, cap, *arrs, C.byref(nv))
+            return self._lib.icpmi_get_voxel_map_level(self._h, int(level), cap, *arrs, C.byref(nv))
         nv = C.c_int64(0)
-        st = self._lib.icpmi_get_voxel_map(self._h, 0, None, None, None, None, C.byref(nv))
+        st = call(0, None, None, None, None)
         if nv.value == 0:
             self._check(st)
         v = nv.value
         ijk, mean = np.zeros((v, 3), np.int32), np.zeros((v, 3), np.float32)
         mom, cnt = np.zeros((v, 6), np.float32), np.zeros(v, np.int32)
-        self._check(self._lib.icpmi_get_voxel_map(self._h, v, ijk.ctypes.data, mean.ctypes.data, mom.ctypes.data, cnt.ctypes.data, C.byref(nv)))
+        self._check(call(v, ijk.ctypes.data, mean.ctypes.data, mom.ctypes.data, cnt.ctypes.data))
         return ijk, mean, mom, cnt
 
-    def voxelLookup(self, q_centred):
-        """icpmi_voxel_lookup: for (N, 3) or (N, 4) centred-frame points the index into voxelMap()'s order, -1 for no voxel"""
+    def voxelLookup(self, q_centred, level=None):
+        """icpmi_voxel_lookup: for (N, 3) or (N, 4) centred-frame points the index into voxelMap()'s order, -1 for no voxel; level as for
+        voxelMap (icpmi_voxel_lookup_level)"""
         q = np.asarray(q_centred, np.float32)
         q4 = np.ones((q.shape[0], 4), np.float32)
         q4[:, :q.shape[1]] = q
         out = np.full(q.shape[0], -2, np.int32)
-        self._check(self._lib.icpmi_voxel_lookup(self._h, q4.ctypes.data, q4.shape[0], out.ctypes.data))
+        if level is None:
+            self._check(self._lib.icpmi_voxel_lookup(self._h, q4.ctypes.data, q4.shape[0], out.ctypes.data))
+        else:
+            self._check(self._lib.icpmi_voxel_lookup_level(self._h, int(level), q4.ctypes.data, q4.shape[0], out.ctypes.data))
         return out
 
     def setPlaneModel(self, model):
