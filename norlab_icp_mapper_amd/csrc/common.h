@@ -216,6 +216,60 @@ __device__ __forceinline__ void st_stream(int* p, int v) { __builtin_nontemporal
 template <class T> __device__ __forceinline__ T ld_stream(const T* p) { return *p; }
 template <class T> __device__ __forceinline__ void st_stream(T* p, T v) { *p = v; }
 #endif
+// Write-through stores (`sc1`) for what a loop kernel hands to the NEXT kernel: the bytes leave the XCD's L2 as the store is issued and leave
+// no dirty line behind, so the write-back of the eight L2s at the kernel boundary finds nothing of them (a plain or `nt` store keeps the
+// line, dirty, until that write-back).  Nothing is ordered by them: the kernel boundary orders producer and consumer as before.  4 bytes: a
+// relaxed agent-scope atomic store (global_store_dword ... sc1).  16 bytes: ONE global_store_dwordx4 ... sc1 -- no builtin gives that
+// instruction through a plain pointer, so it is one line of assembly; the s_nop keeps the compiler's next instruction off the data
+// registers until the store has read them.  Dword-wide write-through stores are one fabric write each (about six times the 16-byte cost
+// per byte): for wide streams and clears only, unless measured.
+__device__ __forceinline__ void st_wt(int* p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ void st_wt(float* p, float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ void st_wt(uint4* p, uint4 v)
+{
+    typedef unsigned icpmi_vu4 __attribute__((ext_vector_type(4)));
+    icpmi_vu4 w; w.x = v.x; w.y = v.y; w.z = v.z; w.w = v.w;
+    asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(p), "v"(w) : "memory");
+}
+__device__ __forceinline__ void st_wt(float4* p, float4 v)
+{
+    st_wt(reinterpret_cast<uint4*>(p), make_uint4(__float_as_uint(v.x), __float_as_uint(v.y), __float_as_uint(v.z), __float_as_uint(v.w)));
+}
+// The sites, one compile-time switch each (0 = the plain store the site had).  The defaults are what the alternating A/B of DESIGN 4.2
+// (profiles/store_policy_bench.json, 12 rounds of the headline) left on: the clears alone +1.5 %, the clears with all three result streams
+// of the k = 1 matcher +2.9 %; the result streams WITHOUT the clears stay inside the parent's run-to-run range, and so does everything the
+// head of a registration writes (qfirst_kernel, qpass_kernel: built, measured, taken out again).
+//   ICPMI_WT_MATCH     nn1_wg_kernel's matched points (match_pt, 16 bytes per query)
+//   ICPMI_WT_RESULT    nn1_wg_kernel's dword-wide result streams (out_sidx, out_d2)
+//   ICPMI_WT_RESULT_K  ... those of nnk_ml_kernel and nnk_wg_kernel (k dwords per query and stream)
+//   ICPMI_WT_CLEAR     the per-iteration histogram clears (nn1_wg_kernel, accumulate_kernel, sel2_hist0_kernel), as 16-byte zero stores
+//                      from a quarter of the threads
+#ifndef ICPMI_WT_MATCH
+#define ICPMI_WT_MATCH 1
+#endif
+#ifndef ICPMI_WT_RESULT
+#define ICPMI_WT_RESULT 1
+#endif
+#ifndef ICPMI_WT_RESULT_K
+#define ICPMI_WT_RESULT_K 0
+#endif
+#ifndef ICPMI_WT_CLEAR
+#define ICPMI_WT_CLEAR 1
+#endif
+template <int WT, bool STREAM = true, class T> __device__ __forceinline__ void st_policy(T* p, T v) // STREAM: a st_stream site when not written through
+{
+    if constexpr (WT != 0) st_wt(p, v);
+    else if constexpr (STREAM) st_stream(p, v);
+    else *p = v;
+}
+// ICPMI_WT_CLEAR: `words` zeroed words at p (16-byte aligned, words % 4 == 0) by the threads gtid, gtid + stride, ... of a launch, 16 bytes a
+// store (2: the same width with plain stores, for the A/B of width against policy)
+__device__ __forceinline__ void clear_words_wt(unsigned* p, int words, int64_t gtid, int64_t stride)
+{
+    for (int64_t i = gtid; i < words / 4; i += stride) st_policy<(ICPMI_WT_CLEAR == 1), false>(reinterpret_cast<uint4*>(p) + i, make_uint4(0u, 0u, 0u, 0u));
+}
+static_assert(ICPMI_S2_C0 % 4 == 0 && ICPMI_S2_C1 % 4 == 0 && ICPMI_S2_WIN % 4 == 0 && ICPMI_SELHIST_WORDS % 4 == 0 && (2 * ICPMI_WIN_U64) % 4 == 0,
+              "the cleared regions of d_selhist start and end on 16 bytes");
 
 // ---- runs of equal keys inside a wave become ONE atomic per run (counting sorts: map_build.hip, the DynamicPoints bucket grid) ----
 struct WaveRun { bool head; int rank; int len; int head_lane; };
@@ -432,6 +486,7 @@ struct alignas(128) LoopHdr {
 static_assert(sizeof(LoopHdr) == 256 && alignof(LoopHdr) == 128, "the loop header is two 128-byte lines: one dword per lane of a wave");
 #define ICPMI_HDR_W(field) ((int)(offsetof(LoopHdr, field) / 4))   // dword index of a header field = the lane that holds it after hdr_load
 
+#define ICPMI_TL_LAUNCHES 24   // -DICPMI_NN_TIMING: NN launches of a registration whose workgroup timeline is kept (nn.hip)
 struct IcpState : LoopHdr {
     int   stop_reason;
     double hq[(ICPMI_MAX_SMOOTH + 1) * 4];
@@ -462,6 +517,10 @@ struct IcpState : LoopHdr {
     // is NOT in profile mode, i.e. bench.py's roofline duration taken from the timed graph replay itself
     unsigned long long t_nn_sum;
     unsigned nn_count, pad_nn;
+#ifdef ICPMI_NN_TIMING
+    // timing builds only (scripts/nn_wg_timeline.py): the open and the close stamp of every NN launch of the registration, by launch number
+    unsigned long long tl_open[ICPMI_TL_LAUNCHES], tl_close[ICPMI_TL_LAUNCHES];
+#endif
 };
 
 #ifdef __HIPCC__
@@ -481,8 +540,15 @@ __device__ __forceinline__ void nn_stamp_open(IcpState* st) { st->t_nn_begin = (
 __device__ __forceinline__ void nn_stamp_close(IcpState* st, unsigned long long b)
 {
     if (b) {
+#ifdef ICPMI_NN_TIMING
+        const unsigned long long now = (unsigned long long)wall_clock64();
+        atomicAdd(&st->t_nn_sum, now - b);
+        const unsigned launch = atomicAdd(&st->nn_count, 1u);
+        if (launch < ICPMI_TL_LAUNCHES) { st->tl_open[launch] = b; st->tl_close[launch] = now; }
+#else
         atomicAdd(&st->t_nn_sum, (unsigned long long)wall_clock64() - b);
         atomicAdd(&st->nn_count, 1u);
+#endif
         st->t_nn_begin = 0;
     }
 }

@@ -179,9 +179,14 @@ __global__ __launch_bounds__(BT) void accumulate_kernel(const float4* __restrict
         fused_limit = is_median ? factor * q : q;
         if (blockIdx.x == 0 && threadIdx.x == 0) st->limits[fused_slot] = fused_limit;
         // level 0 is dead (its only reader ran in the previous kernel): clear it for the next iteration
+#if ICPMI_WT_CLEAR
+        clear_words_wt(hists + ICPMI_S2_C0, ICPMI_S2_COPIES * 256 + ICPMI_S2_FCOPIES * 65536, gtid, stride);
+        if (lc.k > 1) clear_words_wt(hists + ICPMI_S2_WIN, 2 * ICPMI_WIN_U64, gtid, stride);
+#else
         for (int64_t i = gtid; i < ICPMI_S2_COPIES * 256 + ICPMI_S2_FCOPIES * 65536; i += stride) hists[ICPMI_S2_C0 + i] = 0;
         // ... and so is the speculative window of the k > 1 loop (its readers ran in the two kernels before this one)
         if (lc.k > 1) for (int64_t i = gtid; i < 2 * ICPMI_WIN_U64; i += stride) hists[ICPMI_S2_WIN + i] = 0;
+#endif
     }
     constexpr int NVAL = USES_N ? 27 : (PM == PAIR_POINT_TO_POINT ? 16 : 0);
     double acc[NVAL > 0 ? NVAL : 1];

@@ -357,7 +357,23 @@ __device__ __forceinline__ void nn_timing_flush(IcpState* st, const long long (&
         atomicAdd(&st->dbg[16 + (st_iter > 1 ? 1 : 0)], (unsigned long long)tacc[7]);
     }
 }
+// The life of every nn1_wg_kernel workgroup of a single registration on the 100 MHz constant clock (scripts/nn_wg_timeline.py): thread 0's
+// entry, the moment its last store was issued, the moment the wave's stores had drained, and {XCC id, pieces, passes}.  One slot per
+// (launch, workgroup), written once with plain stores: no atomics, nothing shared between workgroups.
+#define NN_TL_WGS 2048
+struct NnWgStamp { unsigned long long t_in, t_issued, t_drained, info; };
+__device__ NnWgStamp g_nn_tl[ICPMI_TL_LAUNCHES][NN_TL_WGS];
+__device__ __forceinline__ unsigned nn_xcc_id()
+{
+    unsigned v;
+    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(v));
+    return v & 15u;
+}
 #else
+#define NN_TICK(i) do { } while (0)
+#endif
+#if defined(ICPMI_NN_TIMING) && defined(ICPMI_NN_TIMELINE_ONLY) // the timeline without the serialising phase clocks: the kernel's own schedule
+#undef NN_TICK
 #define NN_TICK(i) do { } while (0)
 #endif
 // ------------------------------------------------------------------------------------------------
@@ -528,6 +544,7 @@ __global__ __launch_bounds__(64 * NW) NN1_WAVES_ATTR void nn1_wg_kernel(const fl
     long long tacc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     long long tlast = clock64();
     const long long t_c0 = tlast, t_w0 = wall_clock64();
+    const unsigned xcc_id = nn_xcc_id();
 #endif
     __shared__ uint4 ltab[ICPMI_MAXLEV * 4];
     __shared__ unsigned lh[256];
@@ -581,7 +598,11 @@ __global__ __launch_bounds__(64 * NW) NN1_WAVES_ATTR void nn1_wg_kernel(const fl
     if (hist0) {
         for (int t = tid; t < 256; t += NT) lh[t] = 0;
         // the builder of level 0 clears level 1 of the previous iteration (loop.hip, fused selection)
+#if ICPMI_WT_CLEAR
+        clear_words_wt(hist0 + ICPMI_S2_C1, 256 + 65536, (int64_t)blockIdx.x * NT + tid, (int64_t)wgs * NT);
+#else
         for (int gt = blockIdx.x * NT + tid; gt < 256 + 65536; gt += wgs * NT) hist0[ICPMI_S2_C1 + gt] = 0; // (the workgroups of THIS reading: a batch launches the grid of its largest)
+#endif
     }
     const bool allow_self = SELF;
 
@@ -727,9 +748,9 @@ __global__ __launch_bounds__(64 * NW) NN1_WAVES_ATTR void nn1_wg_kernel(const fl
         int bs = -1;
         float4 mpt = make_float4(0.f, 0.f, 0.f, 0.f);
         if (found) { bs = resolve_level0(ltab, (unsigned)best.sidx); mpt = qpt[slot]; }
-        st_stream(out_sidx + orig, bs);
-        st_stream(out_d2 + orig, bd2);
-        if (match_pt) st_stream(match_pt + orig, make_float4(mpt.x, mpt.y, mpt.z, __uint_as_float((unsigned)(best.key & 0xffffffffull))));
+        st_policy<ICPMI_WT_RESULT>(out_sidx + orig, bs);
+        st_policy<ICPMI_WT_RESULT>(out_d2 + orig, bd2);
+        if (match_pt) st_policy<ICPMI_WT_MATCH>(match_pt + orig, make_float4(mpt.x, mpt.y, mpt.z, __uint_as_float((unsigned)(best.key & 0xffffffffull))));
         if (hist0 && decided && bd2 != INFINITY && bd2 > 0.f) {
             const unsigned bits = __float_as_uint(bd2);
             atomicAdd(&hist0[ICPMI_S2_F0 + (blockIdx.x % ICPMI_S2_FCOPIES) * 65536 + ICPMI_S2_FIDX(bits >> 16)], 1u);
@@ -740,8 +761,20 @@ __global__ __launch_bounds__(64 * NW) NN1_WAVES_ATTR void nn1_wg_kernel(const fl
         }
     }
 #ifdef ICPMI_NN_TIMING
+    // the workgroup's timeline slot first: nothing that other workgroups share (nn_timing_flush's atomics) stands between the stores and the stamps
+    if (threadIdx.x == 0 && blockIdx.y == 0 && st_iter >= 0 && st_iter < ICPMI_TL_LAUNCHES && blockIdx.x < NN_TL_WGS) {
+        const unsigned long long t_issued = (unsigned long long)wall_clock64();
+        __builtin_amdgcn_s_waitcnt(0);
+        const unsigned long long t_drained = (unsigned long long)wall_clock64();
+        NnWgStamp s;
+        s.t_in = (unsigned long long)t_w0; s.t_issued = t_issued; s.t_drained = t_drained;
+        s.info = (unsigned long long)xcc_id | ((unsigned long long)tacc[7] & 0xffffffffull) << 8 | ((unsigned long long)tacc[6] & 0xffffull) << 40;
+        g_nn_tl[st_iter][blockIdx.x] = s;
+    }
     NN_TICK(5);
+#ifndef ICPMI_NN_TIMELINE_ONLY
     nn_timing_flush(st, tacc, st_iter, t_c0);
+#endif
     if (threadIdx.x == 0 && (blockIdx.x % 61) == 0) {
         atomicAdd(&st->dbg[22], (unsigned long long)(clock64() - t_c0));       // shader clock ticks of this workgroup's life
         atomicAdd(&st->dbg[23], (unsigned long long)(wall_clock64() - t_w0));  // ... and 100 MHz constant-clock ticks of the same
@@ -990,8 +1023,8 @@ __global__ __launch_bounds__(NN_BLOCK) void nnk_ml_kernel(const float4* __restri
             int bs = -1;
             if (key != ~0ull && d2 <= r2q) bs = resolve_level0(ltab, (unsigned)sx);
             else d2 = INFINITY;
-            out_sidx[(size_t)k * orig + jj] = bs;
-            out_d2[(size_t)k * orig + jj] = d2;
+            st_policy<ICPMI_WT_RESULT_K, false>(out_sidx + ((size_t)k * orig + jj), bs);
+            st_policy<ICPMI_WT_RESULT_K, false>(out_d2 + ((size_t)k * orig + jj), d2);
         }
         }
         if (sub == 0 && !decided) {
@@ -1300,7 +1333,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KMAX <= 8 ?
         }
 #pragma unroll
         for (int j = 0; j < KMAX; ++j)
-            if (j < k) { out_sidx[(size_t)k * orig + j] = bs[j]; out_d2[(size_t)k * orig + j] = bd[j]; }
+            if (j < k) { st_policy<ICPMI_WT_RESULT_K, false>(out_sidx + ((size_t)k * orig + j), bs[j]); st_policy<ICPMI_WT_RESULT_K, false>(out_d2 + ((size_t)k * orig + j), bd[j]); }
         if (!decided) {
             const unsigned hslot = atomicAdd(&st->hard_count, 1u);
             hard[hslot] = (unsigned)(qindex ? qindex[qi] : qi);
@@ -1513,3 +1546,22 @@ icpmi_status nn_ids_to_original(icpmi_ctx* c, const int* d_sidx, int64_t count, 
     HIP_TRY(c, hipGetLastError());
     return ICPMI_OK;
 }
+
+#ifdef ICPMI_NN_TIMING
+// Timing builds only (not in icpmi.h; scripts/nn_wg_timeline.py binds it): the workgroup timeline of the handle's last single registration.
+// wg: ICPMI_TL_LAUNCHES x 2048 x {t_in, t_issued, t_drained, info}; open_close: the launches' open stamps, then their close stamps (the
+// stamp nn_stamp_close makes in the next kernel); *launches: NN launches the registration closed.
+extern "C" icpmi_status icpmi_debug_nn_timeline(icpmi_handle h, uint64_t* wg, uint64_t* open_close, uint32_t* launches)
+{
+    if (!h || !wg || !open_close || !launches) return ICPMI_ERR_INVALID_ARG;
+    static_assert(sizeof(NnWgStamp) == 4 * sizeof(uint64_t), "four words per workgroup");
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    HIP_TRY(h, hipMemcpyFromSymbol(wg, HIP_SYMBOL(g_nn_tl), sizeof(NnWgStamp) * ICPMI_TL_LAUNCHES * NN_TL_WGS));
+    IcpState s;
+    HIP_TRY(h, hipMemcpy(&s, h->d_state, sizeof(IcpState), hipMemcpyDeviceToHost));
+    memcpy(open_close, s.tl_open, sizeof s.tl_open);
+    memcpy(open_close + ICPMI_TL_LAUNCHES, s.tl_close, sizeof s.tl_close);
+    *launches = s.nn_count;
+    return ICPMI_OK;
+}
+#endif

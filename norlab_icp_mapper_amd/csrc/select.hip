@@ -262,7 +262,11 @@ __global__ __launch_bounds__(256) void sel2_hist0_kernel(const float* __restrict
     h[threadIdx.x] = 0;
     for (int i = threadIdx.x; i < WIN; i += 256) win[i] = 0;
     if (threadIdx.x == 0) s_top = 0u;
+#if ICPMI_WT_CLEAR
+    clear_words_wt(hists + ICPMI_S2_C1, 256 + 65536, i0, stride);
+#else
     for (int64_t i = i0; i < 256 + 65536; i += stride) hists[ICPMI_S2_C1 + i] = 0;
+#endif
     __syncthreads();
     {
         unsigned mx = 0;
