@@ -413,6 +413,42 @@ icpmi_status icpmi_voxel_lookup_level(icpmi_handle h, int32_t level, const float
 icpmi_status icpmi_get_voxel_schedule_report(icpmi_handle h, int32_t* levels, int32_t iterations[4], int32_t pairs_first[4], int32_t pairs_last[4]);
 icpmi_status icpmi_debug_voxel_step_level(icpmi_handle h, int32_t level);
 
+/* Many poses scored by table lookup, for relocalisation on the voxel path.  No matcher launch, no selection, no tile sort.
+ * Reading, T and the frame mean what they mean for icpmi_residual_error: the reading as given, T[p] (16 floats, column-major) a correction
+ * in the map frame; the centred pose Tc = [R | t + R mu - mu] is formed in double on the host.  Per reading point x (x, y, z, w), its
+ * normal n_x and pose, in float32 with no contraction, exactly voxel_pairs_kernel's arithmetic up to S:
+ *   p   = Tc x                 per row r: fmaf(Tc[12+r], w, fmaf(Tc[8+r], z, fmaf(Tc[4+r], y, Tc[r] * x)))
+ *   key = the float32 floor of p / size (above); no voxel: no pair, the point adds nothing
+ *   d   = p - mu;  u = unit_or_zero(R n_x), row r of R n_x = fmaf(Tc[8+r], n.z, fmaf(Tc[4+r], n.y, Tc[r] * n.x)); g = 1 - eps
+ *   S   = 2 I - g (N + u u^T):  sxx = 2 - g * (Nxx + u.x * u.x) (likewise syy, szz), sxy = -g * (Nxy + u.x * u.y) (likewise sxz, syz)
+ *   M   = adj(S) / det(S):  c00 = syy * szz - syz * syz, c01 = sxz * syz - sxy * szz, c02 = sxy * syz - sxz * syy, c11 = sxx * szz - sxz * sxz,
+ *         c12 = sxy * sxz - sxx * syz, c22 = sxx * syy - sxy * sxy, idet = 1 / ((sxx * c00 + sxy * c01) + sxz * c02), m_ij = c_ij * idet
+ *   Md  = ((m00 * d.x + m01 * d.y) + m02 * d.z,  (m01 * d.x + m11 * d.y) + m12 * d.z,  (m02 * d.x + m12 * d.y) + m22 * d.z)
+ *   r   = (d.x * Md.x + d.y * Md.y) + d.z * Md.z
+ *   l   = expf(-(hb * r)),  hb = 0.5f * beta rounded once on the host
+ * Per pose, in double, in a fixed order that depends on n alone (no float atomics): pairs, likelihood = sum l, sum_maha = sum r; max_maha =
+ * the largest r (float, exact; 0 without a pair); pairs_ratio = (float)(pairs / n); level = the level scored.  The reading is cut into
+ * slices of *slice points (icpmi_voxel_score_shape), a thread adds its points in ascending order, a wave folds by the xor butterfly
+ * (partners 1, 2, .. 32), the waves and then the slices add in ascending order.  A bounded likelihood ranks poses where the mean of r does
+ * not: it joins "how many points fall on the map" and "how well they fit".
+ * out[p] and status[p] are bit for bit what a call with pose p alone returns, whichever poses share the call and in whatever order.
+ * Errors of the whole call, found before anything is enqueued, with out and status zeroed (min(n_poses, 4096) entries): a handle that is not on the voxel path
+ * (ICPMI_ERR_UNSUPPORTED); no map, null arguments, n < 0, n_poses outside 1 .. 4096, a level the schedule does not have, beta not finite or
+ * <= 0 (ICPMI_ERR_INVALID_ARG); a map without normals or no reading normals (ICPMI_ERR_MISSING_NORMALS); n == 0
+ * (ICPMI_ERR_NO_POINT_TO_MINIMIZE).  Errors of one pose go to status[p] (status == NULL: the first of them is the return value): a T[p] that
+ * is not rigid (ICPMI_ERR_INVALID_ARG; not launched, out[p] zero), pairs == 0 (ICPMI_ERR_NO_POINT_TO_MINIMIZE).
+ * The one-shot reading rows are consumed.  Afterwards the handle is as after icpmi_voxel_lookup: no registration result, covariance,
+ * schedule report, staged scan or captured loop has changed.  icpmi_voxel_score_poses uploads the reading once. */
+typedef struct { int32_t level; float beta; int32_t reserved[6]; } icpmi_voxel_score_options;
+/* level -1: the last (finest) level, and the only one of a one-size handle; beta 1 */
+typedef struct { double likelihood; double sum_maha; int64_t pairs; float max_maha; float pairs_ratio; int32_t level; int32_t reserved[3]; } icpmi_voxel_score;
+void icpmi_voxel_score_options_default(icpmi_voxel_score_options* opts);
+void icpmi_voxel_score_shape(int32_t* slice, int32_t* tile); /* points per slice, poses a workgroup walks */
+icpmi_status icpmi_voxel_score_poses_dev(icpmi_handle h, const float* d_scan4, int64_t n, const float* d_scan_normals3, const float* T,
+                                         int32_t n_poses, const icpmi_voxel_score_options* opts, icpmi_voxel_score* out, icpmi_status* status);
+icpmi_status icpmi_voxel_score_poses(icpmi_handle h, const float* scan4, int64_t n, const float* scan_normals3, const float* T, int32_t n_poses,
+                                     const icpmi_voxel_score_options* opts, icpmi_voxel_score* out, icpmi_status* status);
+
 /* ---- IntensityPointToPlaneErrorMinimizer: a photometric term on ICPMI_MIN_POINT_TO_PLANE.  Not libpointmatcher's: the joint
  * geometric + photometric objective of Park, Zhou, Koltun, "Colored Point Cloud Registration Revisited" (ICCV 2017), one scalar channel.
  *

@@ -109,6 +109,24 @@ class Residual(C.Structure):
 RES_CHAIN, RES_POINT_TO_POINT, RES_POINT_TO_PLANE = 0, 1, 2
 
 
+class VoxelScoreOptions(C.Structure):
+    """icpmi_voxel_score_options: level (-1: the finest) and beta of icpmi_voxel_score_poses*."""
+    _fields_ = [("level", C.c_int32), ("beta", C.c_float), ("reserved", C.c_int32 * 6)]
+
+
+class VoxelScore(C.Structure):
+    """icpmi_voxel_score: what icpmi_voxel_score_poses* returns per pose."""
+    _fields_ = [
+        ("likelihood", C.c_double),
+        ("sum_maha", C.c_double),
+        ("pairs", C.c_int64),
+        ("max_maha", C.c_float),
+        ("pairs_ratio", C.c_float),
+        ("level", C.c_int32),
+        ("reserved", C.c_int32 * 3),
+    ]
+
+
 class Localizability(C.Structure):
     """icpmi_localizability: the report of icpmi_get_localizability (basis[6 e + i] = component i of eigenvector e)."""
     _fields_ = [
@@ -216,6 +234,10 @@ SYMBOLS = [
     ("icpmi_voxel_lookup_level", C.c_int, [_P, C.c_int32, _P, C.c_int64, _P]),
     ("icpmi_get_voxel_schedule_report", C.c_int, [_P, C.POINTER(C.c_int32), _P, _P, _P]),
     ("icpmi_debug_voxel_step_level", C.c_int, [_P, C.c_int32]),
+    ("icpmi_voxel_score_options_default", None, [C.POINTER(VoxelScoreOptions)]),
+    ("icpmi_voxel_score_shape", None, [C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    ("icpmi_voxel_score_poses", C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int32, C.POINTER(VoxelScoreOptions), _P, _P]),
+    ("icpmi_voxel_score_poses_dev", C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int32, C.POINTER(VoxelScoreOptions), _P, _P]),
     ("icpmi_debug_voxel_build_times", C.c_int, [_P, _P]),
     ("icpmi_debug_voxel_lookup_times", C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, C.POINTER(C.c_int64)]),
     ("icpmi_set_intensity_weight", C.c_int, [_P, C.c_float]),

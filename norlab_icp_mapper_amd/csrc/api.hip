@@ -1478,6 +1478,91 @@ icpmi_status icpmi_voxel_lookup_level(icpmi_handle h, int32_t level, const float
     return voxel_lookup(h, level, q4_centred, n, voxel);
 }
 
+void icpmi_voxel_score_options_default(icpmi_voxel_score_options* opts)
+{
+    if (!opts) return;
+    memset(opts, 0, sizeof *opts);
+    opts->level = -1; opts->beta = 1.f;
+}
+
+void icpmi_voxel_score_shape(int32_t* slice, int32_t* tile)
+{
+    int32_t s = 0, t = 0;
+    voxel_score_shape(&s, &t);
+    if (slice) *slice = s;
+    if (tile) *tile = t;
+}
+
+// icpmi_voxel_score_poses*: the whole call's checks, the table, then the rigid poses in the caller's order through voxel_score_poses
+// (voxel.hip).  stage: the host variant's upload, run behind the checks and the table build
+static icpmi_status voxel_score_impl(icpmi_handle h, const char* who, const float* scan4, bool on_host, int64_t n, const float* n3, const float* T,
+                                     int32_t n_poses, const icpmi_voxel_score_options* opts, icpmi_voxel_score* out, icpmi_status* status)
+{
+    h->read_scalar_n = 0; h->read_noise_n = 0; h->read_r2_n = 0; h->read_int_n = 0; // (the one-shot reading rows belong to this call)
+    // zeroed on every whole-call error; a count above the limit zeroes the limit's worth: a wild n_poses must not size a write
+    const size_t n_zero = n_poses < 1 ? 0 : (size_t)(n_poses > 4096 ? 4096 : n_poses);
+    if (out && n_zero) memset(out, 0, sizeof(icpmi_voxel_score) * n_zero);
+    if (status && n_zero) memset(status, 0, sizeof(icpmi_status) * n_zero);
+    if (!voxel_path(h)) {
+        h->last_error = std::string(who) + ": the handle is not on the voxel path (icpmi_set_voxel_matcher > 0 on PlaneToPlaneErrorMinimizer with the GICP pair model)";
+        return ICPMI_ERR_UNSUPPORTED;
+    }
+    icpmi_voxel_score_options o;
+    icpmi_voxel_score_options_default(&o);
+    if (opts) o = *opts;
+    if (!out || !T || n_poses < 1 || n_poses > 4096 || n < 0 || (n > 0 && !scan4)) {
+        h->last_error = std::string(who) + ": bad arguments (1 <= n_poses <= 4096)"; return ICPMI_ERR_INVALID_ARG;
+    }
+    if (!std::isfinite(o.beta) || !(o.beta > 0.f)) { h->last_error = std::string(who) + ": beta must be finite and > 0"; return ICPMI_ERR_INVALID_ARG; }
+    if (h->m <= 0) { h->last_error = std::string(who) + ": no map"; return ICPMI_ERR_INVALID_ARG; }
+    int level = o.level;
+    if (level == -1) level = h->vox_levels - 1;
+    if (level < 0 || level >= h->vox_levels) { h->last_error = std::string(who) + ": no such level in the voxel schedule"; return ICPMI_ERR_INVALID_ARG; }
+    if (n > 0x7fffffff / ICPMI_MAX_K) { h->last_error = std::string(who) + ": too many points"; return ICPMI_ERR_UNSUPPORTED; }
+    if (!h->has_normals) { h->last_error = "InvalidField: VoxelMatcher needs the descriptor 'normals' on the map"; return ICPMI_ERR_MISSING_NORMALS; }
+    if (!n3) { h->last_error = std::string(who) + ": the voxel score needs the reading's normals"; return ICPMI_ERR_MISSING_NORMALS; }
+    if (n == 0) { h->last_error = std::string(who) + ": the reading is empty"; return ICPMI_ERR_NO_POINT_TO_MINIMIZE; }
+    { const icpmi_status ts = voxel_ensure_table(h, nullptr); if (ts != ICPMI_OK) return ts; }
+    const float* d_scan = scan4;
+    const float* d_n3 = n3;
+    if (on_host) { const icpmi_status ss = stage_in_scratch(h, scan4, n, n3, &d_scan, &d_n3); if (ss != ICPMI_OK) return ss; }
+    const float hb = 0.5f * o.beta;
+    std::vector<icpmi_status> st((size_t)n_poses, ICPMI_OK);
+    std::vector<int> live;
+    std::vector<float> Tc;
+    for (int p = 0; p < n_poses; ++p) {
+        st[(size_t)p] = check_rigid(h, T + 16 * (size_t)p);
+        if (st[(size_t)p] != ICPMI_OK) continue;
+        live.push_back(p);
+        Tc.resize(Tc.size() + 16);
+        centred_pose(h, T + 16 * (size_t)p, Tc.data() + Tc.size() - 16);
+    }
+    if (!live.empty()) {
+        std::vector<icpmi_voxel_score> ro(live.size());
+        const icpmi_status vs = voxel_score_poses(h, (const float4*)d_scan, n, d_n3, Tc.data(), (int)live.size(), level, hb, ro.data());
+        if (vs != ICPMI_OK) { memset(out, 0, sizeof(icpmi_voxel_score) * (size_t)n_poses); return vs; }
+        for (size_t i = 0; i < live.size(); ++i) {
+            out[live[i]] = ro[i];
+            if (ro[i].pairs == 0) st[(size_t)live[i]] = ICPMI_ERR_NO_POINT_TO_MINIMIZE;
+        }
+    }
+    return fold_status(h, status, st.data(), n_poses, (std::string(who) + ": a pose ended with an error (see the per-pose status)").c_str());
+}
+
+icpmi_status icpmi_voxel_score_poses_dev(icpmi_handle h, const float* d_scan4, int64_t n, const float* d_scan_normals3, const float* T,
+                                         int32_t n_poses, const icpmi_voxel_score_options* opts, icpmi_voxel_score* out, icpmi_status* status)
+{
+    CHECK_H(h);
+    return voxel_score_impl(h, "voxel_score_poses_dev", d_scan4, false, n, d_scan_normals3, T, n_poses, opts, out, status);
+}
+
+icpmi_status icpmi_voxel_score_poses(icpmi_handle h, const float* scan4, int64_t n, const float* scan_normals3, const float* T, int32_t n_poses,
+                                     const icpmi_voxel_score_options* opts, icpmi_voxel_score* out, icpmi_status* status)
+{
+    CHECK_H(h);
+    return voxel_score_impl(h, "voxel_score_poses", scan4, true, n, scan_normals3, T, n_poses, opts, out, status);
+}
+
 // test seam of scripts/voxel_bench.py: rebuilds the table and reports what its three stages took (sort, reduce, fill; milliseconds by HIP events)
 icpmi_status icpmi_debug_voxel_build_times(icpmi_handle h, float times_ms3[3])
 {

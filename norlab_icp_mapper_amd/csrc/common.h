@@ -1560,6 +1560,12 @@ void voxel_enqueue_pairs(icpmi_ctx* c, int64_t n, int nb, float eps); // one lau
 icpmi_status voxel_get_map(icpmi_ctx* c, int level, int64_t cap, int32_t* ijk3, float* mean3, float* moments6, int32_t* count, int64_t* n_voxels);
 icpmi_status voxel_lookup(icpmi_ctx* c, int level, const float* q4_centred, int64_t n, int32_t* voxel);
 icpmi_status voxel_lookup_times(icpmi_ctx* c, const float* q4_centred, int64_t n, int reps, float ms[2], int64_t* mismatch); // table against binary search
+// icpmi_voxel_score_poses* (DESIGN.md 4.22): the raw reading d_scan / d_n3 under n_poses centred-frame poses (16 floats each), scored against
+// level `level`'s table (current: voxel_ensure_table); out[p] complete, hb = 0.5f * beta.  loop_centre_pad (loop.hip) prepares the reading
+icpmi_status voxel_score_poses(icpmi_ctx* c, const float4* d_scan, int64_t n, const float* d_n3, const float* Tc, int n_poses, int level, float hb,
+                               icpmi_voxel_score* out);
+void voxel_score_shape(int32_t* slice, int32_t* tile);
+icpmi_status loop_centre_pad(icpmi_ctx* c, const float4* d_scan, int64_t n, const float* d_normals3, float4* d_pts, float4* d_nrm);
 // the reading's normals (host, 3 per point) into c->d_read_normals, padded as a registration's head pads them
 icpmi_status loop_upload_read_normals(icpmi_ctx* c, const float* normals3, int64_t n);
 // getResidualError() of the centred reading in c->d_reading under the centred-frame pose T (host, column-major); kind 1 / 2

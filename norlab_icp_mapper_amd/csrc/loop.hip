@@ -988,6 +988,19 @@ icpmi_status loop_prepare_reading(icpmi_ctx* c, const float4* d_scan, int64_t n,
     return ICPMI_OK;
 }
 
+// The reading as a voxel registration's head prepares it, into buffers of the caller's (voxel.hip: voxel_score_poses): centred in the
+// caller's order, the normals padded.  Nothing of the handle's own reading, loop state or captured loop is touched.
+icpmi_status loop_centre_pad(icpmi_ctx* c, const float4* d_scan, int64_t n, const float* d_normals3, float4* d_pts, float4* d_nrm)
+{
+    const int blocks = (int)((n + 255) / 256);
+    if (!blocks) return ICPMI_OK;
+    BatchSrc src; memset(&src, 0, sizeof src); src.p[0] = d_scan;
+    hipLaunchKernelGGL(centre_kernel, dim3(blocks), dim3(256), 0, c->stream, src, batch_of_one(n), c->mean[0], c->mean[1], c->mean[2], d_pts);
+    hipLaunchKernelGGL(pad_normals_kernel, dim3(blocks), dim3(256), 0, c->stream, d_normals3, n, d_nrm);
+    HIP_TRY(c, hipGetLastError());
+    return ICPMI_OK;
+}
+
 static int acc_cap()
 {
     static int cap = -1;

@@ -297,6 +297,133 @@ __global__ __launch_bounds__(256) void voxel_pairs_sched_kernel(const float4* __
     pair_sums_fold<256, 27, false>(acc, cnt, cnt, nullptr, hists);
 }
 
+// ---- many poses scored by table lookup (icpmi_voxel_score_poses) ------------------
+// A slice is VS_SLICE consecutive reading points (thread t of the workgroup holds the points t, t + 256, ... of its slice): the partition
+// of a reading depends on n alone.  A workgroup walks VS_TILE poses over the points it keeps in registers.
+constexpr int VS_PPT = 4;                 // points a thread keeps (scripts/voxel_score_bench.py, profiles/voxel_score_sweep.json: 2 / 4 / 8 tried)
+constexpr int VS_SLICE = 256 * VS_PPT;
+constexpr int VS_TILE = 8;                // poses a workgroup walks (8 / 16 / 32 / 64 tried)
+struct VsPartial { double lik, sum; int pairs; float mx; }; // of one (pose, slice); mx = -inf without a pair
+
+__device__ __forceinline__ unsigned lane_xor_bit_u32(unsigned v, int m)
+{
+    switch (m) {
+    case 1: return lane_xor<1>(v);
+    case 2: return lane_xor<2>(v);
+    case 4: return lane_xor<4>(v);
+    case 8: return lane_xor<8>(v);
+    case 16: return lane_xor<16>(v);
+    default: return lane_xor<32>(v);
+    }
+}
+
+// One pair's r = d^T M d: voxel_pairs_kernel's arithmetic up to S, then M = adj(S) / det(S) as gicp_pair_sums forms it (a copy: that
+// function's sums are not wanted here, and its kernels stay as they are), M d row by row, and the dot product with d -- every product and
+// sum in float, left to right, no contraction (include/icpmi.h writes the order out).  false: no pair.
+__device__ __forceinline__ bool vs_pair(const float* __restrict__ T, float4 x, float3 rn, const uint4* __restrict__ tab, unsigned mask, float size, float g,
+                                        float* r_out)
+{
+    const float3 p = xf_point(T, x.x, x.y, x.z, x.w);
+    unsigned long long key = 0;
+    VoxHit h;
+    if (!vox_key(p.x, p.y, p.z, size, &key) || !vox_probe(tab, mask, key, &h)) return false;
+    const float3 up = unit_or_zero(fmaf(T[8], rn.z, fmaf(T[4], rn.y, T[0] * rn.x)), fmaf(T[9], rn.z, fmaf(T[5], rn.y, T[1] * rn.x)),
+                                   fmaf(T[10], rn.z, fmaf(T[6], rn.y, T[2] * rn.x)));
+    const float nxx = h.a.w, nxy = h.b.x, nxz = h.b.y, nyy = h.b.z, nyz = h.b.w, nzz = h.c.x;
+    const float sxx = 2.f - g * (nxx + up.x * up.x), syy = 2.f - g * (nyy + up.y * up.y), szz = 2.f - g * (nzz + up.z * up.z);
+    const float sxy = -g * (nxy + up.x * up.y), sxz = -g * (nxz + up.x * up.z), syz = -g * (nyz + up.y * up.z);
+    const float c00 = syy * szz - syz * syz, c01 = sxz * syz - sxy * szz, c02 = sxy * syz - sxz * syy;
+    const float c11 = sxx * szz - sxz * sxz, c12 = sxy * sxz - sxx * syz, c22 = sxx * syy - sxy * sxy;
+    const float idet = 1.f / (sxx * c00 + sxy * c01 + sxz * c02);
+    const float m00 = c00 * idet, m01 = c01 * idet, m02 = c02 * idet, m11 = c11 * idet, m12 = c12 * idet, m22 = c22 * idet;
+    const float dx = p.x - h.a.x, dy = p.y - h.a.y, dz = p.z - h.a.z;
+    const float mdx = m00 * dx + m01 * dy + m02 * dz, mdy = m01 * dx + m11 * dy + m12 * dz, mdz = m02 * dx + m12 * dy + m22 * dz;
+    *r_out = dx * mdx + dy * mdy + dz * mdz;
+    return true;
+}
+
+// grid = (slices, pose tiles).  poses: 16 floats each, centred frame, uniform over the workgroup (scalar loads).  One VsPartial per
+// (pose, slice) at part[pose * slices + slice].  Per pose: every thread adds its points in ascending order, the wave folds in the fixed
+// butterfly (lane_xor_bit, m = 1 .. 32), thread 0 adds the four waves in ascending order.  The LDS cells alternate with the pose's parity:
+// one barrier per pose.  No lane past the reading forms an address of it.
+__global__ __launch_bounds__(256) void voxel_score_kernel(const float4* __restrict__ reading, const float4* __restrict__ normals, int n,
+                                                          const float* __restrict__ poses, int n_poses, const uint4* __restrict__ tab, unsigned mask,
+                                                          float size, float eps, float hb, VsPartial* __restrict__ part)
+{
+    __shared__ double sh_d[2][4][2];
+    __shared__ int sh_p[2][4];
+    __shared__ float sh_m[2][4];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int64_t e0 = (int64_t)blockIdx.x * VS_SLICE + threadIdx.x;
+    float4 pt[VS_PPT]; float3 nr[VS_PPT];
+#pragma unroll
+    for (int u = 0; u < VS_PPT; ++u) {
+        const int64_t e = e0 + u * 256;
+        const bool in = e < n;
+        pt[u] = in ? reading[e] : make_float4(0.f, 0.f, 0.f, 0.f);
+        nr[u] = in ? *reinterpret_cast<const float3*>(normals + e) : make_float3(0.f, 0.f, 0.f);
+    }
+    const float g = 1.f - eps;
+    const int p0 = (int)blockIdx.y * VS_TILE;
+    const int p1 = p0 + VS_TILE < n_poses ? p0 + VS_TILE : n_poses;
+    for (int p = p0; p < p1; ++p) {
+        const float* __restrict__ T = poses + 16 * (size_t)p;
+        double lik = 0.0, sum = 0.0;
+        int pairs = 0;
+        float mx = -INFINITY;
+#pragma unroll
+        for (int u = 0; u < VS_PPT; ++u) {
+            float r;
+            if (e0 + u * 256 < n && vs_pair(T, pt[u], nr[u], tab, mask, size, g, &r)) {
+                lik += (double)expf(-(hb * r));
+                sum += (double)r;
+                ++pairs;
+                mx = fmaxf(mx, r);
+            }
+        }
+#pragma unroll
+        for (int mk = 1; mk < 64; mk <<= 1) { // (the wave is whole again behind the loop above)
+            lik += lane_xor_bit(lik, mk);
+            sum += lane_xor_bit(sum, mk);
+            pairs += (int)lane_xor_bit_u32((unsigned)pairs, mk);
+            mx = fmaxf(mx, __uint_as_float(lane_xor_bit_u32(__float_as_uint(mx), mk)));
+        }
+        const int b = p & 1;
+        if (lane == 0) { sh_d[b][wv][0] = lik; sh_d[b][wv][1] = sum; sh_p[b][wv] = pairs; sh_m[b][wv] = mx; }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            VsPartial o;
+            o.lik = ((sh_d[b][0][0] + sh_d[b][1][0]) + sh_d[b][2][0]) + sh_d[b][3][0];
+            o.sum = ((sh_d[b][0][1] + sh_d[b][1][1]) + sh_d[b][2][1]) + sh_d[b][3][1];
+            o.pairs = sh_p[b][0] + sh_p[b][1] + sh_p[b][2] + sh_p[b][3];
+            o.mx = fmaxf(fmaxf(sh_m[b][0], sh_m[b][1]), fmaxf(sh_m[b][2], sh_m[b][3]));
+            part[(size_t)p * gridDim.x + blockIdx.x] = o;
+        }
+    }
+}
+
+// per pose: the slices' partials in ascending slice order, in double; then the result as the caller reads it
+__global__ __launch_bounds__(256) void voxel_score_finish_kernel(const VsPartial* __restrict__ part, int n_poses, int slices, int n, int level,
+                                                                 icpmi_voxel_score* __restrict__ out)
+{
+    const int p = (int)blockIdx.x * 256 + (int)threadIdx.x;
+    if (p >= n_poses) return;
+    double lik = 0.0, sum = 0.0;
+    long long pairs = 0;
+    float mx = -INFINITY;
+    for (int s = 0; s < slices; ++s) {
+        const VsPartial v = part[(size_t)p * slices + s];
+        lik += v.lik; sum += v.sum; pairs += v.pairs; mx = fmaxf(mx, v.mx);
+    }
+    icpmi_voxel_score o;
+    o.likelihood = lik; o.sum_maha = sum; o.pairs = pairs;
+    o.max_maha = pairs > 0 ? mx : 0.f;
+    o.pairs_ratio = (float)((double)pairs / (double)n);
+    o.level = level;
+    o.reserved[0] = o.reserved[1] = o.reserved[2] = 0;
+    out[p] = o;
+}
+
 // the HIP events of a timed diagnostic: created together, destroyed on every way out of the call
 template <int N>
 struct EventSet {
@@ -498,6 +625,34 @@ icpmi_status voxel_lookup(icpmi_ctx* c, int level, const float* q4_centred, int6
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipMemcpyAsync(voxel, d_out.get(), (size_t)n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return ICPMI_OK;
+}
+
+void voxel_score_shape(int32_t* slice, int32_t* tile) { *slice = VS_SLICE; *tile = VS_TILE; }
+
+// icpmi_voxel_score_poses*: centre and pad the reading once, one scoring launch over (slices, pose tiles), the finish, one read-back.
+// Everything lives in the operator scratch (slots 10 .. 14): the handle's reading, loop state and captured loop stay what they were.
+icpmi_status voxel_score_poses(icpmi_ctx* c, const float4* d_scan, int64_t n, const float* d_n3, const float* Tc, int n_poses, int level, float hb,
+                               icpmi_voxel_score* out)
+{
+    const VoxLevel& lv = c->vox[level];
+    const int slices = (int)((n + VS_SLICE - 1) / VS_SLICE);
+    const int tiles = (n_poses + VS_TILE - 1) / VS_TILE;
+    float4* d_pts = scratch_get<float4>(c, 10, (size_t)n);
+    float4* d_nrm = scratch_get<float4>(c, 11, (size_t)n);
+    float* d_T = scratch_get<float>(c, 12, (size_t)16 * n_poses);
+    VsPartial* d_part = scratch_get<VsPartial>(c, 13, (size_t)n_poses * slices);
+    icpmi_voxel_score* d_out = scratch_get<icpmi_voxel_score>(c, 14, (size_t)n_poses);
+    if (!d_pts || !d_nrm || !d_T || !d_part || !d_out) return ICPMI_ERR_HIP;
+    { const icpmi_status s = loop_centre_pad(c, d_scan, n, d_n3, d_pts, d_nrm); if (s != ICPMI_OK) return s; }
+    HIP_TRY(c, hipMemcpyAsync(d_T, Tc, (size_t)16 * n_poses * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(voxel_score_kernel, dim3(slices, tiles), dim3(256), 0, c->stream, (const float4*)d_pts, (const float4*)d_nrm, (int)n,
+                       (const float*)d_T, n_poses, (const uint4*)lv.tab.get(), lv.mask, c->vox_sizes[level], c->plane_eps, hb, d_part);
+    hipLaunchKernelGGL(voxel_score_finish_kernel, dim3((n_poses + 255) / 256), dim3(256), 0, c->stream, (const VsPartial*)d_part, n_poses, slices, (int)n,
+                       level, d_out);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(out, d_out, (size_t)n_poses * sizeof(icpmi_voxel_score), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream)); // (Tc is the caller's until here)
     return ICPMI_OK;
 }
 

@@ -811,6 +811,88 @@ Relocalization GpuICPSequence::relocalize(const DataPoints& readingIn, const std
     return out;
 }
 
+// ---- relocalisation on the voxel path -----------------------------------------------------------
+std::vector<int> rankVoxelCandidates(const VoxelPoseScores& scores, size_t n, float minPairsRatio)
+{
+    const double need = (double)minPairsRatio * (double)n;
+    std::vector<std::pair<double, int>> keyed;
+    for (size_t i = 0; i < scores.size(); ++i) {
+        const icpmi_voxel_score& r = scores.score[i];
+        if (scores.status[i] != ICPMI_OK || r.pairs <= 0 || (double)r.pairs < need) continue;
+        keyed.emplace_back(-(r.likelihood / (double)n), (int)i);
+    }
+    std::sort(keyed.begin(), keyed.end()); // (the index breaks ties)
+    std::vector<int> order;
+    for (const auto& kv : keyed) order.push_back(kv.second);
+    return order;
+}
+
+VoxelPoseScores GpuICPSequence::voxelScoresFiltered(const DataPoints& reading, const std::vector<Mat4>& poses, int level, float beta) const
+{
+    const float* normals = nullptr;
+    if (reading.descriptorExists("normals") && reading.getDescriptorByName("normals").span == 3)
+        normals = reading.getDescriptorByName("normals").data.data();
+    VoxelPoseScores out;
+    out.score.assign(poses.size(), icpmi_voxel_score{});
+    out.status.assign(poses.size(), ICPMI_OK);
+    std::vector<float> T(16 * poses.size());
+    for (size_t p = 0; p < poses.size(); ++p) std::copy(poses[p].m.begin(), poses[p].m.end(), T.begin() + 16 * p);
+    icpmi_voxel_score_options opt;
+    icpmi_voxel_score_options_default(&opt);
+    opt.level = level; opt.beta = beta;
+    check(h, icpmi_voxel_score_poses(h, reading.features.data(), (int64_t)reading.getNbPoints(), normals, T.data(), (int32_t)poses.size(), &opt,
+                                     out.score.data(), out.status.data()));
+    return out;
+}
+
+VoxelPoseScores GpuICPSequence::voxelScores(const DataPoints& readingIn, const std::vector<Mat4>& poses, int level, float beta) const
+{
+    if (!hasReadingFilters()) return voxelScoresFiltered(readingIn, poses, level, beta);
+    return voxelScoresFiltered(filteredReading(readingIn), poses, level, beta);
+}
+
+VoxelRelocalization GpuICPSequence::relocalizeVoxel(const DataPoints& readingIn, const std::vector<Mat4>& candidates, const RelocalizeVoxelOptions& options)
+{
+    if (candidates.empty()) throw InvalidParameter("relocalizeVoxel: no candidates");
+    DataPoints owned;
+    if (hasReadingFilters()) owned = filteredReading(readingIn); // once for the three passes
+    const DataPoints& reading = hasReadingFilters() ? owned : readingIn;
+    const size_t n = reading.getNbPoints();
+    VoxelRelocalization out;
+    out.scores = voxelScoresFiltered(reading, candidates, options.level, options.beta);
+    const std::vector<int> order = rankVoxelCandidates(out.scores, n, options.minPairsRatio);
+    if (order.empty()) throw ConvergenceError("relocalizeVoxel: no candidate survived the scoring");
+    const size_t k = std::min<size_t>(order.size(), (size_t)std::max(1, options.refine));
+    std::vector<Mat4> refined(k);
+    std::vector<icpmi_status> status(k, ICPMI_OK);
+    const RigidTransformation move(h);
+    for (size_t i = 0; i < k; ++i) { // the chain as it is, the whole schedule, start after start (a voxel chain reads no row of the reading but its normals)
+        const Mat4& cand = candidates[(size_t)order[i]];
+        const DataPoints moved = move.compute(reading, cand);
+        const float* normals = nullptr;
+        if (moved.descriptorExists("normals") && moved.getDescriptorByName("normals").span == 3)
+            normals = moved.getDescriptorByName("normals").data.data();
+        Mat4 T = Mat4::identity();
+        haveCovariance = false; haveLocalizability = false;
+        const icpmi_status s = icpmi_register(h, moved.features.data(), (int64_t)moved.getNbPoints(), normals, T.data(), &lastStats);
+        if (s == ICPMI_ERR_NO_POINT_TO_MINIMIZE || s == ICPMI_ERR_NO_OUTLIER_TO_FILTER || s == ICPMI_ERR_BOUND || s == ICPMI_ERR_NAN) {
+            status[i] = s; refined[i] = cand; // a start that did not converge is out
+            continue;
+        }
+        check(h, s);
+        refined[i] = T * cand;
+    }
+    VoxelPoseScores again = voxelScoresFiltered(reading, refined, -1, options.beta);
+    for (size_t i = 0; i < k; ++i) if (status[i] != ICPMI_OK) again.status[i] = status[i];
+    const std::vector<int> fin = rankVoxelCandidates(again, n, options.minPairsRatio);
+    if (fin.empty()) throw ConvergenceError("relocalizeVoxel: no refined candidate survived the scoring");
+    const size_t w = (size_t)fin[0];
+    out.pose = refined[w];
+    out.score = again.score[w];
+    out.index = order[w];
+    return out;
+}
+
 float GpuICPSequence::ErrorMinimizerView::getResidualError(const DataPoints& reading, const Mat4& T) const
 {
     return (float)owner->residual(reading, T).sum_abs;

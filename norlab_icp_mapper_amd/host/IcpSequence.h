@@ -77,6 +77,29 @@ std::vector<int> rankCandidates(const PoseScores& scores, size_t n, float minPai
 // innermost, each ascending: (2 stepsX + 1)(2 stepsY + 1)(2 stepsYaw + 1) poses.  Needs no GPU.
 std::vector<Mat4> candidateGrid(const Mat4& centre, float halfX, float halfY, float halfYaw, int stepsX = 1, int stepsY = 1, int stepsYaw = 1);
 
+// ---- relocalisation on the voxel path: poses scored by table lookup (include/icpmi.h: icpmi_voxel_score_poses) ----
+// one icpmi_voxel_score and one status per pose (a pose that is not rigid keeps an empty score)
+struct VoxelPoseScores {
+    std::vector<icpmi_voxel_score> score;
+    std::vector<icpmi_status> status;
+    size_t size() const { return score.size(); }
+};
+struct RelocalizeVoxelOptions {
+    int refine = 4;                     // how many of the best candidates are registered
+    int level = 0;                      // the level the candidates are scored at (0: the coarsest of a schedule, the widest basin)
+    float beta = 1.f;                   // l = exp(-beta / 2 d^T M d)
+    float minPairsRatio = 0.f;          // a candidate needs pairs >= minPairsRatio * N
+};
+struct VoxelRelocalization {
+    Mat4 pose = Mat4::identity();       // the winner's corrected pose: correction * candidate
+    icpmi_voxel_score score{};          // ... scored under it at the finest level
+    int index = -1;                     // ... its index among the candidates
+    VoxelPoseScores scores;             // every candidate's first score
+};
+// The order in which a voxel relocalisation prefers its candidates: status not ICPMI_OK or pairs < minPairsRatio * n (in double) are
+// dropped, the rest come by likelihood / n descending (double), ties by the lower index.  Needs no GPU.
+std::vector<int> rankVoxelCandidates(const VoxelPoseScores& scores, size_t n, float minPairsRatio = 0.f);
+
 // What GpuICPSequence::registerSweep returns: the sensor's pose in the map at sweep begin and at sweep end, and the call's figures
 // (include/icpmi.h: icpmi_sweep_result; stats.pose7 holds the two poses in double, as icpmi_sweep_motion takes them)
 struct SweepRegistration {
@@ -137,6 +160,15 @@ public:
     // ConvergenceError when no candidate survives.
     Relocalization relocalize(const DataPoints& readingInSensorFrame, const std::vector<Mat4>& candidates, const RelocalizeOptions& options = RelocalizeOptions());
 
+    // On a VoxelMatcher chain: the bounded likelihood of `reading` (with its `normals`) under every T of `poses` against the voxel table of
+    // `level` (-1: the finest), one call (icpmi_voxel_score_poses).  The chain's reading filters are applied once.  Errors of one pose are in
+    // its status; errors of the whole call throw.  Leaves stats() alone.
+    VoxelPoseScores voxelScores(const DataPoints& reading, const std::vector<Mat4>& poses, int level = -1, float beta = 1.f) const;
+    // Where is the sensor, given candidate poses -- on a VoxelMatcher chain: every candidate scored at options.level and ranked
+    // (rankVoxelCandidates), the reading moved by each of the best options.refine registered by the chain as it is (the whole schedule, start
+    // after start), the refined poses scored at the finest level and ranked again.  ConvergenceError when nothing survives.
+    VoxelRelocalization relocalizeVoxel(const DataPoints& reading, const std::vector<Mat4>& candidates, const RelocalizeVoxelOptions& options = RelocalizeVoxelOptions());
+
     // Sweep registration (include/icpmi.h: icpmi_register_sweep; not libpointmatcher's): the skewed scan in the sensor frame with its point
     // times tRel (one per point, in units of opts.time_unit_s from the scan's stamp) registered as a motion -- the two poses estimated by
     // the chain's matcher and outlier filters.  Point-to-plane chains without reading filters; throws what operator() throws.  Leaves
@@ -187,6 +219,7 @@ private:
     DataPoints filteredReading(const DataPoints& reading) const;
     PoseScores residualsFiltered(const DataPoints& reading, const std::vector<Mat4>& poses, int kind) const; // (the reading as the chain's filters left it)
     MultiStartResult multiStartFiltered(const DataPoints& reading, const std::vector<Mat4>& priors);
+    VoxelPoseScores voxelScoresFiltered(const DataPoints& reading, const std::vector<Mat4>& poses, int level, float beta) const;
     void requireBareReadingChain(const char* who) const;    // InvalidParameter for a chain that reads the reading's normals or descriptors
     icpmi_handle h = nullptr;
     icpmi_config cfg;

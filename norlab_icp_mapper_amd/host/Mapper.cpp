@@ -395,6 +395,21 @@ Relocalization Mapper::relocalize(const DataPoints& inputInSensorFrame, const st
     return found;
 }
 
+VoxelRelocalization Mapper::relocalizeVoxel(const DataPoints& inputInSensorFrame, const std::vector<Mat4>& candidates, const TimePoint& timeStamp,
+                                            const RelocalizeVoxelOptions& options)
+{
+    DataPoints scan = inputInSensorFrame;
+    applyInputFilters(scan);
+    VoxelRelocalization found;
+    {
+        std::lock_guard<std::mutex> g(icpMapLock);
+        found = icp.relocalizeVoxel(scan, candidates, options);
+    }
+    { std::lock_guard<std::mutex> g(poseLock); pose = found.pose; }
+    { std::lock_guard<std::mutex> g(trajectoryLock); trajectory.addPose(found.pose, timeStamp); }
+    return found;
+}
+
 bool Mapper::mapUpdateIsDue(const TimePoint& now, const Mat4& poseNow, float overlap) const
 {
     if (!isMapping.load()) return false;

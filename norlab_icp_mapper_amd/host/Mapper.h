@@ -100,6 +100,9 @@ public:
     // cells are paged by the next processInput, not here.  Throws what GpuICPSequence::relocalize throws; the pose then stays.
     Relocalization relocalize(const DataPoints& inputInSensorFrame, const std::vector<Mat4>& candidates, const TimePoint& timeStamp,
                               const RelocalizeOptions& options = RelocalizeOptions());
+    // ... on a VoxelMatcher chain, by GpuICPSequence::relocalizeVoxel: the input filters, the current map, the pose set, no map update
+    VoxelRelocalization relocalizeVoxel(const DataPoints& inputInSensorFrame, const std::vector<Mat4>& candidates, const TimePoint& timeStamp,
+                                        const RelocalizeVoxelOptions& options = RelocalizeVoxelOptions());
     DataPoints getMap() { return map.getGlobalPointCloud(); }
     long residentMapUpdates() const { return map.residentUpdateCount(); }
     size_t localMapSize() { return map.localSize(); }

@@ -473,6 +473,56 @@ def rank_candidates(scores, n, min_pairs_ratio=0.5):
     return [i for _, i in keyed]
 
 
+class VoxelScore:
+    """icpmi_voxel_score as plain Python values (likelihood = sum over the pairs of exp(-beta / 2 d^T M d))."""
+    __slots__ = ("likelihood", "sum_maha", "pairs", "max_maha", "pairs_ratio", "level")
+
+    def __init__(self, c):
+        self.likelihood, self.sum_maha, self.pairs = float(c.likelihood), float(c.sum_maha), int(c.pairs)
+        self.max_maha, self.pairs_ratio, self.level = np.float32(c.max_maha), np.float32(c.pairs_ratio), int(c.level)
+
+    def bits(self):
+        """every field as raw bits (bit-for-bit comparisons)"""
+        return (np.float64([self.likelihood, self.sum_maha]).view(np.uint64).tolist(), self.pairs,
+                np.float32([self.max_maha, self.pairs_ratio]).view(np.uint32).tolist(), self.level)
+
+    def __repr__(self):
+        return "VoxelScore(" + ", ".join(f"{k}={getattr(self, k)!r}" for k in self.__slots__) + ")"
+
+
+class VoxelPoseScores:
+    """What icpmi_voxel_score_poses* returns: one VoxelScore and one status per pose (a pose that is not rigid keeps an empty score)."""
+
+    def __init__(self, scores, status):
+        self.scores, self.status = list(scores), [int(s) for s in status]
+
+    def __len__(self):
+        return len(self.scores)
+
+    def table(self):
+        """(status, pairs, likelihood) per pose: what rank_voxel_candidates reads"""
+        return [(st, r.pairs, r.likelihood) for st, r in zip(self.status, self.scores)]
+
+    def bits(self):
+        return [(st, r.bits()) for st, r in zip(self.status, self.scores)]
+
+
+def rank_voxel_candidates(scores, n, min_pairs_ratio=0.0):
+    """The order in which a relocalisation on the voxel path prefers its candidates.  scores: a VoxelPoseScores, or (status, pairs,
+    likelihood) per candidate; n: points of the reading.  A candidate whose status is not 0 or whose pairs < min_pairs_ratio * n (the ratio
+    as float32, the product in double) is dropped; the rest come by likelihood / n descending (double), ties by the lower index.  Returns
+    the list of indices."""
+    table = scores.table() if isinstance(scores, VoxelPoseScores) else list(scores)
+    need = float(np.float32(min_pairs_ratio)) * float(n)
+    keyed = []
+    for i, (st, pairs, lik) in enumerate(table):
+        if int(st) != 0 or int(pairs) <= 0 or float(int(pairs)) < need:
+            continue
+        keyed.append((-(float(lik) / float(n)), i))
+    keyed.sort()
+    return [i for _, i in keyed]
+
+
 def candidate_grid(pose, half_x, half_y, half_yaw, steps_x=1, steps_y=1, steps_yaw=1):
     """The start poses of a relocalisation around `pose` (4x4): translations pose.t + (dx, dy, 0) and rotations Rz(dyaw) pose.R with
     dx = half_x i / steps_x for i = -steps_x .. steps_x (likewise dy, dyaw; 0 steps: that axis stays), formed in double and rounded to
@@ -973,6 +1023,72 @@ class ICPSequence:
             raise ConvergenceError("relocalize: no refined candidate survived the scoring")
         w = final[0]
         return Relocalization(refined[w].copy(), again.residuals[w], best[w], scores)
+
+    # ---- the same on the voxel path: poses scored by table lookup (icpmi_voxel_score_poses*) ----
+    def _voxel_scores(self, fn, scan_ptr, n, nptr, poses, level, beta):
+        Tc = self._poses_to_c(poses)
+        P = Tc.shape[0] // 16
+        opts = _capi.VoxelScoreOptions()
+        self._lib.icpmi_voxel_score_options_default(C.byref(opts))
+        opts.level, opts.beta = (-1 if level is None else int(level)), float(beta)
+        res = (_capi.VoxelScore * max(P, 1))()
+        status = (C.c_int * max(P, 1))()
+        self._check(fn(self._h, scan_ptr, int(n), nptr, Tc.ctypes.data, P, C.byref(opts), res, status))
+        return VoxelPoseScores([VoxelScore(r) for r in res[:P]], status[:P])
+
+    def voxelScores(self, reading, normals, poses, level=None, beta=1.0):
+        """icpmi_voxel_score_poses: for every T of `poses` (P, 4, 4; P <= 4096) the bounded likelihood of `reading` (N, 4) with `normals`
+        (N, 3) against the voxel table of `level` (None: the finest; 0: the coarsest of a schedule) -- one upload, one scoring launch, no
+        matcher.  Returns a VoxelPoseScores; errors of one pose (not rigid, no pair) are in its status, errors of the whole call raise."""
+        scan = _f32c(reading, 4)
+        nptr = None
+        if normals is not None:
+            normals = _f32c(normals, 3)
+            if normals.shape[0] != scan.shape[0]:
+                raise InvalidParameter("normals / cloud size mismatch")
+            nptr = normals.ctypes.data
+        return self._voxel_scores(self._lib.icpmi_voxel_score_poses, scan.ctypes.data, scan.shape[0], nptr, poses, level, beta)
+
+    def voxelScoresDev(self, d_scan_ptr, n, d_normals_ptr, poses, level=None, beta=1.0):
+        """icpmi_voxel_score_poses_dev: voxelScores() for a reading and its normals already in HBM."""
+        return self._voxel_scores(self._lib.icpmi_voxel_score_poses_dev, d_scan_ptr, n, d_normals_ptr, poses, level, beta)
+
+    def relocalizeVoxel(self, reading, normals, candidates, refine=4, level=0, beta=1.0, min_pairs_ratio=0.0):
+        """Where is the sensor, given candidate poses -- on a VoxelMatcher handle.  Every candidate is scored at `level` (0: the coarsest
+        level of a schedule, the widest basin) and ranked (rank_voxel_candidates); the reading moved by each of the best `refine` is
+        registered by the handle's own chain, the whole schedule, start after start; the refined poses are scored at the finest level and
+        ranked again.  Returns a Relocalization whose `residual` is the winner's VoxelScore; ConvergenceError when nothing survives."""
+        scan, nrm = _f32c(reading, 4), _f32c(normals, 3)
+        cand = np.asarray(candidates, dtype=np.float32).reshape(-1, 4, 4)
+        if cand.shape[0] == 0:
+            raise InvalidParameter("relocalizeVoxel: no candidates")
+        n = scan.shape[0]
+        scores = self.voxelScores(scan, nrm, cand, level=level, beta=beta)
+        order = rank_voxel_candidates(scores, n, min_pairs_ratio)
+        if not order:
+            raise ConvergenceError("relocalizeVoxel: no candidate survived the scoring")
+        best = order[:max(1, int(refine))]
+        refined, status = [], []
+        for i in best:  # (a voxel chain reads no row of the reading but its normals: the registration call itself, so that a start's status stays what it was)
+            moved, movedn = self.transform(cand[i], scan, nrm)
+            T = (C.c_float * 16)()
+            self._last_n = n
+            st = self._lib.icpmi_register(self._h, moved.ctypes.data, n, movedn.ctypes.data, T, C.byref(self.stats))
+            if st in (_capi.ERR_NO_POINT_TO_MINIMIZE, _capi.ERR_NO_OUTLIER_TO_FILTER, _capi.ERR_BOUND, _capi.ERR_NAN):
+                refined.append(cand[i].copy())  # a start that did not converge is out, under the status it ended with
+                status.append(int(st))
+                continue
+            self._check(st)
+            refined.append(compose_pose(_T_from_c(T[:]), cand[i]))
+            status.append(0)
+        refined = np.stack(refined)
+        again = self.voxelScores(scan, nrm, refined, level=None, beta=beta)
+        again.status = [a if s == 0 else s for a, s in zip(again.status, status)]  # a start that did not converge is out
+        final = rank_voxel_candidates(again, n, min_pairs_ratio)
+        if not final:
+            raise ConvergenceError("relocalizeVoxel: no refined candidate survived the scoring")
+        w = final[0]
+        return Relocalization(refined[w].copy(), again.scores[w], best[w], scores)
 
     def setReadingMaxDist(self, radii):
         """icpmi_set_reading_max_dist: the search radius of every point of the NEXT reading (KDTreeVarDistMatcher's `maxDistField` row; one shot)."""
