@@ -449,6 +449,45 @@ icpmi_status icpmi_voxel_score_poses_dev(icpmi_handle h, const float* d_scan4, i
 icpmi_status icpmi_voxel_score_poses(icpmi_handle h, const float* scan4, int64_t n, const float* scan_normals3, const float* T, int32_t n_poses,
                                      const icpmi_voxel_score_options* opts, icpmi_voxel_score* out, icpmi_status* status);
 
+/* Many readings, or many starts of one reading, registered in one loop on the voxel path.  The handle is a VoxelMatcher
+ * handle, one-size or scheduled.  icpmi_register_batch_dev and icpmi_register_multistart* keep refusing such a handle: they cannot carry
+ * the readings' normals.
+ * icpmi_voxel_register_batch_dev: batch in 1 .. 16 readings d_scans4[b] (device, n[b] points of 4 floats) with their normals
+ *   d_scan_normals3[b] (device, 3 floats per point).  T_out + 16 b, status[b] and stats[b] are bit for bit what
+ *   icpmi_register_dev(h, d_scans4[b], n[b], d_scan_normals3[b], ...) -- fixed_iterations > 0: icpmi_register_fixed_dev -- returns for that
+ *   reading alone, whichever readings share the launch and in whatever order.  Outside that claim are the timing fields of icpmi_stats:
+ *   loop_ms (the whole batch's loop here), nn_ms_avg and nn_launches.  status == NULL: the first error of a member is the return value.
+ * icpmi_voxel_register_multistart_dev: one reading and n_starts in 1 .. 16 priors (16 floats each, column-major).  Reading and normals are
+ *   moved by every prior on the device into slices of their own, with icpmi_transform's arithmetic element for element, and the slices
+ *   go through the batch: start s is bit for bit icpmi_transform(priors + 16 s) followed by icpmi_register on the result.  T_out + 16 s is
+ *   the correction that registration returns (composing it with the prior stays the caller's).  A prior that is not rigid:
+ *   ICPMI_ERR_INVALID_ARG in status[s], an identity, the other starts untouched.  icpmi_voxel_register_multistart takes host pointers and
+ *   uploads the reading and its normals once.
+ * icpmi_get_voxel_batch_report: member b's (start s's) icpmi_get_voxel_schedule_report for the last of these calls;
+ *   ICPMI_ERR_INVALID_ARG on a handle with fewer than two levels or for a member that call did not have.
+ * Errors of the whole call, found before anything is enqueued, with T_out set to identities: batch / n_starts outside 1 .. 16, null
+ *   arguments, n < 0 (ICPMI_ERR_INVALID_ARG); a handle that is not on the voxel path (ICPMI_ERR_INVALID_ARG, the message names
+ *   icpmi_set_voxel_matcher); everything a single registration on the voxel path refuses, in its words; a member with points and no
+ *   normals pointer (ICPMI_ERR_MISSING_NORMALS).  An empty map: identities and ICPMI_OK.
+ * A batch of one, or one with an empty member (n[b] == 0), registers its members one after the other: the same answers, no sharing.
+ * Afterwards: no covariance, no staged scan, nothing for icpmi_debug_last_matches; the one-shot reading rows are consumed. */
+icpmi_status icpmi_voxel_register_batch_dev(icpmi_handle h, int32_t batch, const float* const* d_scans4, const int64_t* n,
+                                            const float* const* d_scan_normals3, int32_t fixed_iterations, float* T_out, icpmi_stats* stats,
+                                            icpmi_status* status);
+/* ... for readings and normals on the host (what the C++ host shell calls): one upload per reading, then the call above */
+icpmi_status icpmi_voxel_register_batch(icpmi_handle h, int32_t batch, const float* const* scans4, const int64_t* n,
+                                        const float* const* scan_normals3, int32_t fixed_iterations, float* T_out, icpmi_stats* stats,
+                                        icpmi_status* status);
+icpmi_status icpmi_voxel_register_multistart_dev(icpmi_handle h, const float* d_scan4, int64_t n, const float* d_scan_normals3, const float* priors,
+                                                 int32_t n_starts, int32_t fixed_iterations, float* T_out, icpmi_stats* stats, icpmi_status* status);
+icpmi_status icpmi_voxel_register_multistart(icpmi_handle h, const float* scan4, int64_t n, const float* scan_normals3, const float* priors,
+                                             int32_t n_starts, int32_t fixed_iterations, float* T_out, icpmi_stats* stats, icpmi_status* status);
+icpmi_status icpmi_get_voxel_batch_report(icpmi_handle h, int32_t member, int32_t* levels, int32_t iterations[4], int32_t pairs_first[4],
+                                          int32_t pairs_last[4]);
+/* test seam: out[0] = loops the voxel batch has run on this handle, out[1] = the members they carried, out[2] = single registrations on the
+ * voxel path (icpmi_register*, and the one-by-one route of the calls above) */
+icpmi_status icpmi_debug_voxel_batch_calls(icpmi_handle h, int64_t out[3]);
+
 /* ---- IntensityPointToPlaneErrorMinimizer: a photometric term on ICPMI_MIN_POINT_TO_PLANE.  Not libpointmatcher's: the joint
  * geometric + photometric objective of Park, Zhou, Koltun, "Colored Point Cloud Registration Revisited" (ICCV 2017), one scalar channel.
  *

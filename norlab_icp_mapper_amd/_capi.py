@@ -238,6 +238,12 @@ SYMBOLS = [
     ("icpmi_voxel_score_shape", None, [C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     ("icpmi_voxel_score_poses", C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int32, C.POINTER(VoxelScoreOptions), _P, _P]),
     ("icpmi_voxel_score_poses_dev", C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int32, C.POINTER(VoxelScoreOptions), _P, _P]),
+    ("icpmi_voxel_register_batch_dev", C.c_int, [_P, C.c_int32, _P, _P, _P, C.c_int32, _P, _P, _P]),
+    ("icpmi_voxel_register_batch", C.c_int, [_P, C.c_int32, _P, _P, _P, C.c_int32, _P, _P, _P]),
+    ("icpmi_voxel_register_multistart_dev", C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int32, C.c_int32, _P, _P, _P]),
+    ("icpmi_voxel_register_multistart", C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int32, C.c_int32, _P, _P, _P]),
+    ("icpmi_get_voxel_batch_report", C.c_int, [_P, C.c_int32, C.POINTER(C.c_int32), _P, _P, _P]),
+    ("icpmi_debug_voxel_batch_calls", C.c_int, [_P, _P]),
     ("icpmi_debug_voxel_build_times", C.c_int, [_P, _P]),
     ("icpmi_debug_voxel_lookup_times", C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, C.POINTER(C.c_int64)]),
     ("icpmi_set_intensity_weight", C.c_int, [_P, C.c_float]),

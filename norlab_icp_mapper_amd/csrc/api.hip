@@ -763,6 +763,7 @@ static icpmi_status register_impl(icpmi_handle h, const float* d_scan4, int64_t 
     // `normals` -- ADVICE r3)
     const bool voxel = voxel_path(h); // (voxel_check passed: the chain is one the voxel matcher serves)
     if (voxel) { const icpmi_status ts = voxel_ensure_table(h, nullptr); if (ts != ICPMI_OK) return ts; } // (before the loop: it allocates and waits)
+    if (voxel) ++h->vox_single_regs; // (icpmi_debug_voxel_batch_calls)
     // (a voxel loop leaves no matched pairs behind for the overlap pass: the row is consumed, the overlap stays "not computed")
     const bool sn = !voxel && have_noise_n == n && !lc.ext && !lc.is_2d &&
                     (lc.minimizer == ICPMI_MIN_POINT_TO_POINT || (lc.minimizer == ICPMI_MIN_POINT_TO_PLANE && d_n3));
@@ -1177,6 +1178,222 @@ icpmi_status icpmi_register_multistart(icpmi_handle h, const float* scan4, int64
         HIP_TRY(h, hipMemcpyAsync(h->d_stage_in, scan4, (size_t)n * sizeof(float4), hipMemcpyHostToDevice, h->stream));
     }
     return icpmi_register_multistart_dev(h, n > 0 ? (const float*)h->d_stage_in.get() : nullptr, n, priors, n_starts, fixed_iterations, T_out, stats, status);
+}
+
+// ---- many readings, or many starts, on the voxel path --------------------------
+// What the whole call is refused for, before anything is enqueued: a handle off the voxel path, then everything voxel_check refuses for
+// a single registration, in its words.
+static icpmi_status voxel_batch_check(icpmi_ctx* h, const char* who)
+{
+    if (!(h->voxel_size > 0.f)) {
+        h->last_error = std::string(who) + ": the handle is not on the voxel path (icpmi_set_voxel_matcher or icpmi_set_voxel_schedule with a size > 0)";
+        return ICPMI_ERR_INVALID_ARG;
+    }
+    return voxel_check(h, "register", true);
+}
+
+// the report of a registration that went through register_impl, as member b's
+static void voxel_batch_report_from_single(icpmi_ctx* h, int b)
+{
+    for (int i = 0; i < 1 + 3 * ICPMI_MAX_VOXEL_LEVELS; ++i) h->vox_batch_report[b][i] = h->vox_levels >= 2 ? h->vox_report[i] : 0;
+}
+
+// the members of a batch, checked: through the one loop, or -- a batch of one, an empty member -- one after the other
+static icpmi_status voxel_batch_impl(icpmi_handle h, const char* who, int batch, const float* const* d_scans4, const int64_t* n,
+                                     const float* const* d_n3, int fixed_iterations, float* T_out, icpmi_stats* stats, icpmi_status* status)
+{
+    h->read_scalar_n = 0; h->read_noise_n = 0; h->read_r2_n = 0; h->read_int_n = 0; // (the one-shot reading rows belong to this call)
+    h->cov_ready = false; h->degen_ready = false; h->last_match_n = 0; h->cov_kept = false;
+    h->scan_map_n = 0;
+    h->vox_batch_members = 0;
+    for (int b = 0; b < batch; ++b) {
+        identity16(T_out + 16 * b);
+        if (stats) { memset(stats + b, 0, sizeof(icpmi_stats)); stats[b].sensor_noise_overlap = -1.f; }
+        if (status) status[b] = ICPMI_OK;
+    }
+    { const icpmi_status vs = voxel_batch_check(h, who); if (vs != ICPMI_OK) return vs; }
+    for (int b = 0; b < batch; ++b)
+        if (n[b] > 0 && !d_n3[b]) {
+            h->last_error = std::string("InvalidField: ") + plane_minimizer_name(h) + " needs the descriptor 'normals' on both reading and map";
+            return ICPMI_ERR_MISSING_NORMALS;
+        }
+    memset(h->vox_batch_report, 0, sizeof h->vox_batch_report);
+    if (h->m <= 0) { h->vox_batch_members = batch; return ICPMI_OK; } // (an empty map: identities, as a single registration answers; empty reports)
+    bool together = batch > 1;
+    for (int b = 0; b < batch; ++b) if (n[b] == 0 || n[b] > 0x7fffffff / ICPMI_MAX_K) together = false;
+    if (!together) {
+        icpmi_status sb[ICPMI_MAX_BATCH];
+        for (int b = 0; b < batch; ++b) {
+            sb[b] = register_impl(h, d_scans4[b], n[b], d_n3[b], fixed_iterations, T_out + 16 * b, stats ? stats + b : nullptr);
+            if (sb[b] == ICPMI_ERR_HIP) return sb[b];
+            voxel_batch_report_from_single(h, b);
+        }
+        h->vox_batch_members = batch;
+        h->last_match_n = 0; h->cov_ready = false; h->degen_ready = false;
+        return fold_status(h, status, sb, batch, nullptr); // (last_error: what the last reading that failed said)
+    }
+    { const icpmi_status ts = voxel_ensure_table(h, nullptr); if (ts != ICPMI_OK) return ts; } // (before the loop: both allocate and wait)
+    { const icpmi_status ts = voxel_ensure_batch_block(h); if (ts != ICPMI_OK) return ts; }
+    LoopCfg lc = make_loop_cfg(h, fixed_iterations);
+    lc.has_read_normals = 1; // (as register_impl leaves the chain of a plane-to-plane handle)
+    ++h->vox_batch_loops; h->vox_batch_loop_members += batch;
+    const icpmi_status rs = loop_run_voxel_batch(h, batch, d_scans4, n, d_n3, lc, T_out, stats, status);
+    if (rs != ICPMI_ERR_HIP) h->vox_batch_members = batch;
+    return rs;
+}
+
+icpmi_status icpmi_voxel_register_batch_dev(icpmi_handle h, int32_t batch, const float* const* d_scans4, const int64_t* n,
+                                            const float* const* d_scan_normals3, int32_t fixed_iterations, float* T_out, icpmi_stats* stats,
+                                            icpmi_status* status)
+{
+    CHECK_H(h);
+    if (batch < 1 || batch > ICPMI_MAX_BATCH || !d_scans4 || !n || !d_scan_normals3 || !T_out || fixed_iterations < 0) {
+        h->last_error = "voxel_register_batch: bad arguments (1 <= batch <= 16)"; return ICPMI_ERR_INVALID_ARG;
+    }
+    for (int b = 0; b < batch; ++b)
+        if (n[b] < 0 || (n[b] > 0 && !d_scans4[b])) {
+            for (int i = 0; i < batch; ++i) identity16(T_out + 16 * i);
+            h->last_error = "voxel_register_batch: bad arguments"; return ICPMI_ERR_INVALID_ARG;
+        }
+    return voxel_batch_impl(h, "voxel_register_batch", batch, d_scans4, n, d_scan_normals3, fixed_iterations, T_out, stats, status);
+}
+
+// ... for readings on the host: every reading and its normals uploaded once into the operator scratch (slots 8 and 9), then the call above
+icpmi_status icpmi_voxel_register_batch(icpmi_handle h, int32_t batch, const float* const* scans4, const int64_t* n, const float* const* scan_normals3,
+                                        int32_t fixed_iterations, float* T_out, icpmi_stats* stats, icpmi_status* status)
+{
+    CHECK_H(h);
+    if (batch < 1 || batch > ICPMI_MAX_BATCH || !scans4 || !n || !scan_normals3 || !T_out || fixed_iterations < 0) {
+        h->last_error = "voxel_register_batch: bad arguments (1 <= batch <= 16)"; return ICPMI_ERR_INVALID_ARG;
+    }
+    const float* dp[ICPMI_MAX_BATCH]; const float* dn[ICPMI_MAX_BATCH];
+    size_t total = 0;
+    bool bad = false;
+    for (int b = 0; b < batch; ++b) { bad |= n[b] < 0 || (n[b] > 0 && !scans4[b]); if (!bad) total += (size_t)n[b]; }
+    const bool stage = !bad && h->m > 0 && h->voxel_size > 0.f && total > 0; // (otherwise the call below answers before it reads a reading)
+    float4* d_in = stage ? scratch_get<float4>(h, 8, total) : nullptr;
+    float* d_n = stage ? scratch_get<float>(h, 9, 3 * total) : nullptr;
+    if (stage && (!d_in || !d_n)) return ICPMI_ERR_HIP;
+    size_t off = 0;
+    for (int b = 0; b < batch; ++b) {
+        dp[b] = scans4[b]; dn[b] = scan_normals3[b];
+        if (!stage || n[b] <= 0) continue;
+        HIP_TRY(h, hipMemcpyAsync(d_in + off, scans4[b], (size_t)n[b] * sizeof(float4), hipMemcpyHostToDevice, h->stream));
+        dp[b] = (const float*)(d_in + off);
+        if (scan_normals3[b]) {
+            HIP_TRY(h, hipMemcpyAsync(d_n + 3 * off, scan_normals3[b], (size_t)n[b] * 3 * sizeof(float), hipMemcpyHostToDevice, h->stream));
+            dn[b] = d_n + 3 * off;
+        }
+        off += (size_t)n[b];
+    }
+    return icpmi_voxel_register_batch_dev(h, batch, dp, n, dn, fixed_iterations, T_out, stats, status);
+}
+
+icpmi_status icpmi_voxel_register_multistart_dev(icpmi_handle h, const float* d_scan4, int64_t n, const float* d_scan_normals3, const float* priors,
+                                                 int32_t n_starts, int32_t fixed_iterations, float* T_out, icpmi_stats* stats, icpmi_status* status)
+{
+    CHECK_H(h);
+    if (n_starts < 1 || n_starts > ICPMI_MAX_BATCH || n < 0 || (n > 0 && !d_scan4) || !priors || !T_out || fixed_iterations < 0) {
+        h->last_error = "voxel_register_multistart: bad arguments (1 <= n_starts <= 16)"; return ICPMI_ERR_INVALID_ARG;
+    }
+    h->vox_batch_members = 0;
+    for (int s = 0; s < n_starts; ++s) {
+        identity16(T_out + 16 * s);
+        if (stats) { memset(stats + s, 0, sizeof(icpmi_stats)); stats[s].sensor_noise_overlap = -1.f; }
+        if (status) status[s] = ICPMI_OK;
+    }
+    { const icpmi_status vs = voxel_batch_check(h, "voxel_register_multistart"); if (vs != ICPMI_OK) return vs; }
+    if (n > 0 && !d_scan_normals3) {
+        h->last_error = std::string("InvalidField: ") + plane_minimizer_name(h) + " needs the descriptor 'normals' on both reading and map";
+        return ICPMI_ERR_MISSING_NORMALS;
+    }
+    icpmi_status st[ICPMI_MAX_BATCH];
+    int idx[ICPMI_MAX_BATCH], nlive = 0;
+    for (int s = 0; s < n_starts; ++s) {
+        st[s] = check_rigid(h, priors + 16 * s);
+        if (st[s] == ICPMI_OK) idx[nlive++] = s;
+    }
+    if (h->m <= 0) nlive = 0; // (an empty map: identities, as a single registration answers; the reading is not touched)
+    // every live start into slices of its own, points and normals (the stage of icpmi_register_prior and an operator scratch: nothing is
+    // left staged), then the slices through the batch
+    h->scan_map_n = 0;
+    const int64_t NS = (n + 63) / 64 * 64;
+    float* d_nslices = nullptr;
+    if (n > 0 && nlive > 0) {
+        if (h->d_scan_map.ensure(h, (size_t)NS * nlive + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
+        d_nslices = scratch_get<float>(h, 19, (size_t)3 * NS * nlive + 3);
+        if (!d_nslices) return ICPMI_ERR_HIP;
+    }
+    const float* ptrs[ICPMI_MAX_BATCH]; const float* nptrs[ICPMI_MAX_BATCH];
+    int64_t ns[ICPMI_MAX_BATCH];
+    for (int i = 0; i < nlive; ++i) {
+        float4* slice = n > 0 ? h->d_scan_map.get() + (size_t)i * NS : nullptr;
+        float* nslice = n > 0 ? d_nslices + (size_t)3 * i * NS : nullptr;
+        const icpmi_status ts = ops_transform_normals_dev(h, priors + 16 * idx[i], (const float4*)d_scan4, d_scan_normals3, n, slice, nslice);
+        if (ts != ICPMI_OK) return ts;
+        ptrs[i] = (const float*)slice; nptrs[i] = nslice; ns[i] = n;
+    }
+    int32_t rep[ICPMI_MAX_BATCH][1 + 3 * ICPMI_MAX_VOXEL_LEVELS];
+    memset(rep, 0, sizeof rep);
+    if (nlive > 0) {
+        float Tl[16 * ICPMI_MAX_BATCH];
+        icpmi_stats sl[ICPMI_MAX_BATCH];
+        icpmi_status stl[ICPMI_MAX_BATCH];
+        const icpmi_status bs = voxel_batch_impl(h, "voxel_register_multistart", nlive, ptrs, ns, nptrs, fixed_iterations, Tl, sl, stl);
+        if (bs != ICPMI_OK) return bs;
+        for (int i = 0; i < nlive; ++i) {
+            memcpy(T_out + 16 * idx[i], Tl + 16 * i, 16 * sizeof(float));
+            if (stats) stats[idx[i]] = sl[i];
+            st[idx[i]] = stl[i];
+            memcpy(rep[idx[i]], h->vox_batch_report[i], sizeof rep[0]);
+        }
+    } else {
+        h->read_scalar_n = 0; h->read_noise_n = 0; h->read_r2_n = 0; h->read_int_n = 0;
+        h->cov_ready = false; h->degen_ready = false; h->last_match_n = 0; h->cov_kept = false;
+    }
+    memcpy(h->vox_batch_report, rep, sizeof rep); // (by start: a start that was not launched reports nothing)
+    h->vox_batch_members = n_starts;
+    return fold_status(h, status, st, n_starts, "voxel_register_multistart: a start ended with an error (see the per-start status)");
+}
+
+icpmi_status icpmi_voxel_register_multistart(icpmi_handle h, const float* scan4, int64_t n, const float* scan_normals3, const float* priors,
+                                             int32_t n_starts, int32_t fixed_iterations, float* T_out, icpmi_stats* stats, icpmi_status* status)
+{
+    CHECK_H(h);
+    if (n < 0 || (n > 0 && !scan4)) { h->last_error = "voxel_register_multistart: bad arguments"; return ICPMI_ERR_INVALID_ARG; }
+    const float* d_scan = scan4; // (n == 0, no map or a call that is refused: never dereferenced)
+    const float* d_n3 = scan_normals3;
+    if (n > 0 && h->m > 0 && h->voxel_size > 0.f && n_starts >= 1 && n_starts <= ICPMI_MAX_BATCH) { // one upload of the scan and its normals
+        d_n3 = nullptr;
+        const icpmi_status ss = stage_in_scratch(h, scan4, n, scan_normals3, &d_scan, &d_n3);
+        if (ss != ICPMI_OK) return ss;
+    }
+    return icpmi_voxel_register_multistart_dev(h, d_scan, n, d_n3, priors, n_starts, fixed_iterations, T_out, stats, status);
+}
+
+icpmi_status icpmi_get_voxel_batch_report(icpmi_handle h, int32_t member, int32_t* levels, int32_t iterations[4], int32_t pairs_first[4],
+                                          int32_t pairs_last[4])
+{
+    CHECK_H(h);
+    if (!levels || !iterations || !pairs_first || !pairs_last) { h->last_error = "get_voxel_batch_report: null argument"; return ICPMI_ERR_INVALID_ARG; }
+    if (h->vox_levels < 2) { h->last_error = "get_voxel_batch_report: the handle has no schedule of two or more voxel sizes (icpmi_set_voxel_schedule)"; return ICPMI_ERR_INVALID_ARG; }
+    if (member < 0 || member >= h->vox_batch_members) { h->last_error = "get_voxel_batch_report: the last batch or multistart had no such member"; return ICPMI_ERR_INVALID_ARG; }
+    const int32_t* r = h->vox_batch_report[member];
+    *levels = r[0];
+    for (int l = 0; l < ICPMI_MAX_VOXEL_LEVELS; ++l) {
+        iterations[l] = r[1 + l];
+        pairs_first[l] = r[1 + ICPMI_MAX_VOXEL_LEVELS + l];
+        pairs_last[l] = r[1 + 2 * ICPMI_MAX_VOXEL_LEVELS + l];
+    }
+    return ICPMI_OK;
+}
+
+// test seam: [0] loops run by the voxel batch, [1] members they carried, [2] single registrations on the voxel path
+icpmi_status icpmi_debug_voxel_batch_calls(icpmi_handle h, int64_t out[3])
+{
+    if (!h || !out) return ICPMI_ERR_INVALID_ARG;
+    out[0] = h->vox_batch_loops; out[1] = h->vox_batch_loop_members; out[2] = h->vox_single_regs;
+    return ICPMI_OK;
 }
 
 icpmi_status icpmi_transform(icpmi_handle h, const float T[16], const float* in4, int64_t n, float* out4, const float* in_normals3,

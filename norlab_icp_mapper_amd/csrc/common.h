@@ -972,7 +972,15 @@ struct icpmi_ctx {
     DevArr<unsigned> d_vox_sched; uint64_t vox_sched_sig = 0;
     int vox_step_level = -1;
     int32_t vox_report[1 + 3 * ICPMI_MAX_VOXEL_LEVELS] = {0};
-    DevArr<IcpState> d_state;          // ICPMI_MAX_BATCH states (a single registration uses the first)
+    // a batch on the voxel path: d_vox_batch = ICPMI_VS_WORDS dwords with the level descriptors every member reads (one
+    // level for a one-size handle), then ICPMI_VS_WORDS per member for its own report (voxel.hip: voxel_ensure_batch_block).
+    // vox_batch_report: per member of the last batch or multistart what vox_report is for a registration; vox_batch_members: how many
+    DevArr<unsigned> d_vox_batch; uint64_t vox_batch_sig = 0;
+    int32_t vox_batch_report[ICPMI_MAX_BATCH][1 + 3 * ICPMI_MAX_VOXEL_LEVELS] = {{0}};
+    int vox_batch_members = 0;
+    // test seam (icpmi_debug_voxel_batch_calls): loops of loop_run_voxel_batch, members they carried, single registrations on the voxel path
+    int64_t vox_batch_loops = 0, vox_batch_loop_members = 0, vox_single_regs = 0;
+    DevArr<IcpState> d_state;         // ICPMI_MAX_BATCH states (a single registration uses the first)
     IcpState* h_state = nullptr;                               // pinned mirror (ICPMI_MAX_BATCH)
     bool zero_pending = false;                                 // d_state / d_selhist still to be cleared: on the stream the handle really uses, at its first call (zero_state_if_pending)
     unsigned scan_tag = 0;                                     // call number of device_scan_flags_count: the tag its count comes back with (map_build.hip)
@@ -1557,6 +1565,13 @@ bool voxel_table_current(const icpmi_ctx* c);
 icpmi_status voxel_ensure_table(icpmi_ctx* c, float* times_ms); // every level; times_ms (3 floats: sort, reduce, fill) forces a rebuild of the finest
 void voxel_enqueue_pairs(icpmi_ctx* c, int64_t n, int nb, float eps); // one launch on c->stream: the sums of c->d_reading under d_state->T_iter
 // (scheduled handles: the level word is set and raised by loop.hip's voxel_sched_reset_kernel and voxel_advance_kernel)
+// A batch on the voxel path: the batch block (descriptors current, before anything is enqueued), the pair sums of one
+// iteration of all members (blockIdx.y = member; nb = acc_blocks of the largest, cap = the cap of acc_blocks), and the loop: B readings
+// with their normals (3 floats per point, device) registered in one loop, every member to the bits loop_run gives it alone
+icpmi_status voxel_ensure_batch_block(icpmi_ctx* c);
+void voxel_enqueue_pairs_batch(icpmi_ctx* c, const BatchArgs& ba, int nb, int cap, float eps);
+icpmi_status loop_run_voxel_batch(icpmi_ctx* c, int batch, const float* const* d_scans4, const int64_t* n, const float* const* d_normals3,
+                                  const LoopCfg& lc, float* T_out, icpmi_stats* stats, icpmi_status* status);
 icpmi_status voxel_get_map(icpmi_ctx* c, int level, int64_t cap, int32_t* ijk3, float* mean3, float* moments6, int32_t* count, int64_t* n_voxels);
 icpmi_status voxel_lookup(icpmi_ctx* c, int level, const float* q4_centred, int64_t n, int32_t* voxel);
 icpmi_status voxel_lookup_times(icpmi_ctx* c, const float* q4_centred, int64_t n, int reps, float ms[2], int64_t* mismatch); // table against binary search
@@ -1663,6 +1678,7 @@ icpmi_status ops_map_update_point_distance(icpmi_ctx* c, const float* scan4, int
 icpmi_status ops_map_update_dev(icpmi_ctx* c, const float4* d_scan, int64_t n, const float* d_scan_n3, float min_dist, int normals_knn,
                                 uint8_t* keep_out, int64_t* appended, int64_t* new_m);
 icpmi_status ops_transform_dev(icpmi_ctx* c, const float T[16], const float4* d_in, int64_t n, float4* d_out);
+icpmi_status ops_transform_normals_dev(icpmi_ctx* c, const float T[16], const float4* d_in, const float* d_in3, int64_t n, float4* d_out, float* d_out3);
 icpmi_status ops_get_map(icpmi_ctx* c, float* out4, float* normals3, int64_t capacity, int64_t* m);
 icpmi_status ops_voxel_keep_first(icpmi_ctx* c, const float* in4, int64_t n, float edge, int method, uint8_t* keep);
 icpmi_status ops_point_distance_keep(icpmi_ctx* c, const float* map4, int64_t m, const float* in4, int64_t n,

@@ -502,6 +502,47 @@ __global__ __launch_bounds__(64) void voxel_advance_kernel(IcpState* __restrict_
     if (threadIdx.x == 0) publish_progress(st, progress);
 }
 
+// ---- a batch on the voxel path --------------------------------------------------
+// blockIdx.x = member: its state, its report block (ICPMI_VS_WORDS dwords behind the descriptor block of the handle's batch block), its
+// progress word.  A one-size handle runs the reset too: the pair kernel of a batch reads the level word on every handle.
+__global__ __launch_bounds__(64) void voxel_sched_reset_batch_kernel(IcpState* __restrict__ st, unsigned* __restrict__ blocks)
+{
+    st += blockIdx.x;
+    unsigned* __restrict__ sched = blocks + (size_t)(1 + blockIdx.x) * ICPMI_VS_WORDS;
+    if (threadIdx.x == 0) st->vox_level = 0u;
+    if (threadIdx.x < ICPMI_VS_WORDS - ICPMI_VS_BASE) sched[ICPMI_VS_BASE + threadIdx.x] = 0u;
+}
+
+// voxel_advance_kernel for the members of a batch, one wave each: the same report and the same level switch, on the member's own state and
+// report block.  No mirror and no host report: a batch reads its states back at the end, and the report blocks with them.
+__global__ __launch_bounds__(64) void voxel_advance_batch_kernel(IcpState* __restrict__ st, unsigned* __restrict__ blocks, int nlevels,
+                                                                 unsigned* __restrict__ progress)
+{
+    st += blockIdx.x;
+    unsigned* __restrict__ sched = blocks + (size_t)(1 + blockIdx.x) * ICPMI_VS_WORDS;
+    if (progress) progress += blockIdx.x;
+    if (threadIdx.x == 0) {
+        const int L = (int)(st->vox_level & (ICPMI_MAX_VOXEL_LEVELS - 1));
+        const int it = st->iter - (int)sched[ICPMI_VS_BASE];
+        const unsigned pairs = (unsigned)st->pairs;
+        sched[ICPMI_VS_ITERS + L] = (unsigned)it;
+        if (it == 1 && pairs) sched[ICPMI_VS_FIRST + L] = pairs;
+        sched[ICPMI_VS_LAST + L] = pairs;
+        if (st->done && !st->error && L + 1 < nlevels) {
+            st->done = 0; st->stop_reason = 0; st->counter = 0; st->t_done = 0;
+            // (the history of the new level begins empty: voxel_advance_kernel says how that state is built)
+            constexpr int RING = ICPMI_MAX_SMOOTH + 1;
+            for (int i = 0; i < RING; ++i) { st->hrot[i] = INFINITY; st->htr[i] = INFINITY; }
+            quat_from_T(st->T_iter, st->hq + 4 * (RING - 1));
+            for (int r = 0; r < 3; ++r) st->ht[3 * (RING - 1) + r] = 1e30;
+            st->hist_n = RING;
+            sched[ICPMI_VS_BASE] = (unsigned)st->iter;
+            st->vox_level = (unsigned)(L + 1);
+        }
+        publish_progress(st, progress);
+    }
+}
+
 __global__ __launch_bounds__(256) void centre_kernel(BatchSrc src, BatchArgs ba, float mx, float my, float mz, float4* __restrict__ out)
 {
     // blockIdx.y = reading of a batch: its own source pointer, slice blockIdx.y of `out`
@@ -1647,6 +1688,105 @@ icpmi_status loop_run_batch(icpmi_ctx* c, int B, const float* const* d_scans4, c
         if (stats) stats[b].loop_ms = ms;
     }
     return fold_status(c, status, sb, B, "register_batch: a reading ended with a convergence error (see the per-reading status)");
+}
+
+// ---------------------------------------------------------------------------------------------
+// A batch on the voxel path: B readings, each with its own normals, through one loop.  Per iteration two launches (three
+// with a schedule) for all members: voxel_pairs_batch_kernel (blockIdx.y = member), the solve every chain ends in (blockIdx.x = member,
+// unchanged), voxel_advance_batch_kernel (one wave per member).  A member keeps its own state, accumulators, level and report, stops on its
+// own checkers and switches level on its own; its pair sums are added in the order it has alone: it ends on the bits loop_run gives it.
+// Tables and the batch block are current (api.hip: voxel_ensure_table, voxel_ensure_batch_block); no member is empty.  Enqueued eagerly,
+// `ahead` iterations in front of the slowest member still running; no captured graph (the results are the same bits either way).
+// ---------------------------------------------------------------------------------------------
+icpmi_status loop_run_voxel_batch(icpmi_ctx* c, int B, const float* const* d_scans4, const int64_t* nn, const float* const* d_normals3,
+                                  const LoopCfg& lc, float* T_out, icpmi_stats* stats, icpmi_status* status)
+{
+    c->last_match_n = 0; c->cov_ready = false; c->cov_kept = false; c->degen_ready = false;
+    int64_t nmax = 0;
+    for (int b = 0; b < B; ++b) nmax = nn[b] > nmax ? nn[b] : nmax;
+    const int64_t NS = (nmax + 63) / 64 * 64; // slice stride of the centred readings and of the padded normals
+    BatchArgs ba; memset(&ba, 0, sizeof ba);
+    BatchSrc src; memset(&src, 0, sizeof src);
+    ba.nscan = B; ba.qstride = (int)NS;
+    for (int b = 0; b < B; ++b) { ba.n[b] = (int)nn[b]; src.p[b] = (const float4*)d_scans4[b]; }
+    // all allocations up front
+    if (c->d_reading.ensure(c, (size_t)NS * B + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
+    if (c->d_read_normals.ensure(c, (size_t)NS * B + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
+    if (c->d_selhist.ensure(c, (size_t)ICPMI_SELHIST_WORDS * B) != ICPMI_OK) return ICPMI_ERR_HIP;
+    c->qsorted_n = -1; c->qsorted_src = nullptr; // (d_reading gets new contents and no sorted copy, as in a single voxel loop)
+    const bool sched = voxel_scheduled(c);
+    const int total_iter = sched ? (lc.max_iter < 0xfff ? lc.max_iter * c->vox_levels : lc.max_iter) : lc.max_iter; // (loop_run's bound)
+    unsigned* d_blocks = c->d_vox_batch.get();
+
+    c->reg_seq = (c->reg_seq + 1) & 0x7ffffu;
+    HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
+    // head: centred readings and padded normals into the members' slices, B fresh states and accumulators, level 0 and clean reports.
+    // No tile sort: nothing on this path reads it
+    hipLaunchKernelGGL(centre_kernel, dim3((int)((nmax + 255) / 256), B), dim3(256), 0, c->stream, src, ba, c->mean[0], c->mean[1], c->mean[2], c->d_reading);
+    for (int b = 0; b < B; ++b)
+        hipLaunchKernelGGL(pad_normals_kernel, dim3((int)((nn[b] + 255) / 256)), dim3(256), 0, c->stream, d_normals3[b], nn[b],
+                           c->d_read_normals.get() + (size_t)b * NS);
+    hipLaunchKernelGGL(init_state_kernel, dim3(B), dim3(64), 0, c->stream, c->d_state, (const float*)nullptr, c->reg_seq, c->d_progress,
+                       (const unsigned*)nullptr, 0);
+    HIP_TRY(c, hipMemsetAsync(c->d_selhist, 0, (size_t)ICPMI_SELHIST_WORDS * B * sizeof(unsigned), c->stream));
+    hipLaunchKernelGGL(voxel_sched_reset_batch_kernel, dim3(B), dim3(64), 0, c->stream, c->d_state.get(), d_blocks);
+    HIP_TRY(c, hipGetLastError());
+
+    const int nb = acc_blocks(nmax);
+    constexpr int ahead = 2;
+    const bool poll = (lc.use_diff || lc.use_bound) && total_iter < 0xfff;
+    bool stopped = false;
+    for (int it = 0; it < total_iter && !stopped; ++it) {
+        voxel_enqueue_pairs_batch(c, ba, nb, acc_cap(), lc.plane_eps);
+        // (with a schedule the solve tells the host nothing -- its stop may be a level switch: the advance behind it publishes)
+        hipLaunchKernelGGL(solve_kernel<false>, dim3(B), dim3(256), 0, c->stream, c->d_state, c->d_selhist, 1, lc, (float*)nullptr, (double*)nullptr,
+                           sched ? (unsigned*)nullptr : c->d_progress, (IcpState*)nullptr);
+        if (sched)
+            hipLaunchKernelGGL(voxel_advance_batch_kernel, dim3(B), dim3(64), 0, c->stream, c->d_state.get(), d_blocks, c->vox_levels, c->d_progress);
+        HIP_TRY(c, hipGetLastError());
+        if (it + 1 >= total_iter || !poll) continue;
+        // as loop_run_batch: stay `ahead` iterations in front of the slowest member still running; stop when all have stopped, or when the
+        // stream is idle and no member still iterates
+        unsigned v[ICPMI_MAX_BATCH]; bool idle = false, all_done = true;
+        HIP_TRY(c, spin_on_host(c->stream, 256, c->h_progress, B, v, [&](const unsigned* w) {
+            bool may_go = true;
+            all_done = true;
+            for (int b = 0; b < B; ++b) {
+                const ProgressWord p = decode_progress(w[b], c->reg_seq);
+                all_done &= p.mine && p.done;
+                may_go &= p.mine && (p.done || p.iter + ahead > it);
+            }
+            return all_done || may_go;
+        }, &idle));
+        stopped = all_done || idle;
+        for (int b = 0; b < B && idle; ++b) {
+            const ProgressWord p = decode_progress(v[b], c->reg_seq);
+            if (p.mine && !p.done && p.iter > it) stopped = false;
+        }
+    }
+    HIP_TRY(c, hipEventRecord(c->ev1, c->stream));
+    unsigned rep[ICPMI_VS_WORDS * ICPMI_MAX_BATCH];
+    HIP_TRY(c, hipMemcpyAsync(c->h_state, c->d_state, sizeof(IcpState) * B, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(rep, d_blocks + ICPMI_VS_WORDS, sizeof(unsigned) * ICPMI_VS_WORDS * B, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    float ms = 0.f;
+    (void)hipEventElapsedTime(&ms, c->ev0, c->ev1);
+    icpmi_status sb[ICPMI_MAX_BATCH];
+    for (int b = 0; b < B; ++b) {
+        const IcpState* hs = c->h_state + b;
+        fill_stats(hs, lc, nn[b], stats ? stats + b : nullptr); // (reserved[] as the single call fills it)
+        sb[b] = (icpmi_status)hs->error;
+        if (hs->error) for (int i = 0; i < 16; ++i) T_out[16 * b + i] = (i % 5 == 0) ? 1.f : 0.f;
+        else pose_out(c, hs->T_iter, T_out + 16 * b);
+        if (stats) { stats[b].loop_ms = ms; stats[b].nn_ms_avg = 0.f; stats[b].nn_launches = 0; }
+        int32_t* r = c->vox_batch_report[b];
+        for (int i = 0; i < 1 + 3 * ICPMI_MAX_VOXEL_LEVELS; ++i) r[i] = 0;
+        if (sched) { // (what loop_run leaves in vox_report: the levels entered, then iterations, first and last pair counts per level)
+            r[0] = (int32_t)(hs->vox_level & (ICPMI_MAX_VOXEL_LEVELS - 1)) + 1;
+            for (int i = 0; i < 3 * ICPMI_MAX_VOXEL_LEVELS; ++i) r[1 + i] = (int32_t)rep[(size_t)b * ICPMI_VS_WORDS + ICPMI_VS_ITERS + i];
+        }
+    }
+    return fold_status(c, status, sb, B, "voxel_register_batch: a reading ended with a convergence error (see the per-reading status)");
 }
 
 icpmi_status loop_single_step(icpmi_ctx* c, int64_t n, const LoopCfg& lc, const float* T_iter_host, float T_step[16],

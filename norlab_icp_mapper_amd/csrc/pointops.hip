@@ -51,6 +51,24 @@ __global__ __launch_bounds__(256) void move_kernel(float4* __restrict__ pts, flo
     }
 }
 
+// ... out of place, normals always: a start of icpmi_voxel_register_multistart* into its slices, one launch (the same arithmetic again,
+// element for element: the slices hold the bits icpmi_transform returns)
+__global__ __launch_bounds__(256) void move_to_kernel(const float4* __restrict__ in, const float* __restrict__ in3, int64_t n, Mat16 M,
+                                                      float4* __restrict__ out, float* __restrict__ out3)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const float* T = M.v;
+    const float4 p = in[i];
+    const float3 o = xf_point(T, p.x, p.y, p.z, p.w);
+    const float w = fmaf(T[15], p.w, fmaf(T[11], p.z, fmaf(T[7], p.y, T[3] * p.x)));
+    out[i] = make_float4(o.x, o.y, o.z, w);
+    const float x = in3[3 * i], y = in3[3 * i + 1], z = in3[3 * i + 2];
+    out3[3 * i] = fmaf(T[8], z, fmaf(T[4], y, T[0] * x));
+    out3[3 * i + 1] = fmaf(T[9], z, fmaf(T[5], y, T[1] * x));
+    out3[3 * i + 2] = fmaf(T[10], z, fmaf(T[6], y, T[2] * x));
+}
+
 __global__ __launch_bounds__(256) void bin_kernel(const float4* __restrict__ in, int64_t n, float cell, int* __restrict__ ijk)
 {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -526,6 +544,15 @@ icpmi_status ops_transform_dev(icpmi_ctx* c, const float T[16], const float4* d_
     icpmi_status s = check_rigid(c, T);
     if (s != ICPMI_OK || n == 0) return s;
     hipLaunchKernelGGL(transform_kernel, dim3((int)((n + 255) / 256)), dim3(256), 0, c->stream, d_in, n, mat16(T), d_out);
+    HIP_TRY(c, hipGetLastError());
+    return ICPMI_OK;
+}
+
+// ... points and normals (3 floats per point) by T into buffers of the caller's, one launch; T passed check_rigid
+icpmi_status ops_transform_normals_dev(icpmi_ctx* c, const float T[16], const float4* d_in, const float* d_in3, int64_t n, float4* d_out, float* d_out3)
+{
+    if (n == 0) return ICPMI_OK;
+    hipLaunchKernelGGL(move_to_kernel, dim3((int)((n + 255) / 256)), dim3(256), 0, c->stream, d_in, d_in3, n, mat16(T), d_out, d_out3);
     HIP_TRY(c, hipGetLastError());
     return ICPMI_OK;
 }

@@ -6,6 +6,8 @@
 //                                   M = (C_v + C(u_p))^-1, into the fixed-point accumulators the existing solve kernel reads
 //   a schedule of sizes (4.21):     one table per level by the same build; voxel_pairs_sched_kernel: the same pair sums with table, mask and
 //                                   size taken from the level descriptors by the level the loop header holds (loop.hip raises it)
+//   a batch of readings (4.23):     voxel_pairs_batch_kernel: the same pair sums with blockIdx.y = member, every member on the workgroups and
+//                                   in the order of additions it has alone (loop.hip: loop_run_voxel_batch drives it)
 // No float atomics anywhere: two builds of one map give the same bits, and so do two registrations.
 #include "common.h"
 #include <vector>
@@ -182,6 +184,24 @@ __global__ __launch_bounds__(256) void vox_lookup_bsearch_kernel(const float4* _
 // Per reading point: p = T_iter x, the voxel p falls into (none: no pair), q = mu, M = (C_v + C(u_p))^-1 with C_v = I - (1 - eps) N and
 // u_p = unit_or_zero(R n_x); then the sums of DESIGN.md 4.15 with weight 1 (common.h: gicp_pair_sums) and accumulate_kernel's workgroup fold
 // as a function (common.h: pair_sums_fold).
+// voxel_pair: one pair, the arithmetic the three pair kernels below share (g = 1 - eps; no voxel: nothing is added).
+__device__ __forceinline__ void voxel_pair(const float (&T)[16], float4 r, float3 rn, const uint4* __restrict__ tab, unsigned mask, float size, float g,
+                                           double (&acc)[27], double& cnt)
+{
+    const float3 p = xf_point(T, r.x, r.y, r.z, r.w);
+    unsigned long long key = 0;
+    VoxHit h;
+    if (!vox_key(p.x, p.y, p.z, size, &key) || !vox_probe(tab, mask, key, &h)) return;
+    cnt += 1.0;
+    const float3 up = unit_or_zero(fmaf(T[8], rn.z, fmaf(T[4], rn.y, T[0] * rn.x)), fmaf(T[9], rn.z, fmaf(T[5], rn.y, T[1] * rn.x)),
+                                   fmaf(T[10], rn.z, fmaf(T[6], rn.y, T[2] * rn.x)));
+    const float nxx = h.a.w, nxy = h.b.x, nxz = h.b.y, nyy = h.b.z, nyz = h.b.w, nzz = h.c.x;
+    // S = C_v + C(u_p) = 2 I - (1 - eps)(N + u_p u_p^T), symmetric: xx xy xz yy yz zz
+    const float sxx = 2.f - g * (nxx + up.x * up.x), syy = 2.f - g * (nyy + up.y * up.y), szz = 2.f - g * (nzz + up.z * up.z);
+    const float sxy = -g * (nxy + up.x * up.y), sxz = -g * (nxz + up.x * up.z), syz = -g * (nyz + up.y * up.z);
+    gicp_pair_sums<false>(acc, sxx, sxy, sxz, syy, syz, szz, p, make_float3(p.x - h.a.x, p.y - h.a.y, p.z - h.a.z), 1.0);
+}
+
 __global__ __launch_bounds__(256) void voxel_pairs_kernel(const float4* __restrict__ reading, const float4* __restrict__ read_normals, int n,
                                                           IcpState* __restrict__ st, const uint4* __restrict__ tab, unsigned mask, float size, float eps,
                                                           unsigned* __restrict__ hists)
@@ -213,20 +233,7 @@ __global__ __launch_bounds__(256) void voxel_pairs_kernel(const float4* __restri
 #pragma unroll
     for (int i = 0; i < 27; ++i) acc[i] = 0.0;
     double cnt = 0.0;
-    auto pair = [&](float4 r, float3 rn) {
-        const float3 p = xf_point(T, r.x, r.y, r.z, r.w);
-        unsigned long long key = 0;
-        VoxHit h;
-        if (!vox_key(p.x, p.y, p.z, size, &key) || !vox_probe(tab, mask, key, &h)) return;
-        cnt += 1.0;
-        const float3 up = unit_or_zero(fmaf(T[8], rn.z, fmaf(T[4], rn.y, T[0] * rn.x)), fmaf(T[9], rn.z, fmaf(T[5], rn.y, T[1] * rn.x)),
-                                       fmaf(T[10], rn.z, fmaf(T[6], rn.y, T[2] * rn.x)));
-        const float nxx = h.a.w, nxy = h.b.x, nxz = h.b.y, nyy = h.b.z, nyz = h.b.w, nzz = h.c.x;
-        // S = C_v + C(u_p) = 2 I - (1 - eps)(N + u_p u_p^T), symmetric: xx xy xz yy yz zz
-        const float sxx = 2.f - g * (nxx + up.x * up.x), syy = 2.f - g * (nyy + up.y * up.y), szz = 2.f - g * (nzz + up.z * up.z);
-        const float sxy = -g * (nxy + up.x * up.y), sxz = -g * (nxz + up.x * up.z), syz = -g * (nyz + up.y * up.z);
-        gicp_pair_sums<false>(acc, sxx, sxy, sxz, syy, syz, szz, p, make_float3(p.x - h.a.x, p.y - h.a.y, p.z - h.a.z), 1.0);
-    };
+    auto pair = [&](float4 r, float3 rn) { voxel_pair(T, r, rn, tab, mask, size, g, acc, cnt); };
 #pragma unroll
     for (int u = 0; u < PF; ++u)
         if (e0 + u * stride < n) pair(pr[u], pn[u]);
@@ -275,24 +282,82 @@ __global__ __launch_bounds__(256) void voxel_pairs_sched_kernel(const float4* __
 #pragma unroll
     for (int i = 0; i < 27; ++i) acc[i] = 0.0;
     double cnt = 0.0;
-    auto pair = [&](float4 r, float3 rn) {
-        const float3 p = xf_point(T, r.x, r.y, r.z, r.w);
-        unsigned long long key = 0;
-        VoxHit h;
-        if (!vox_key(p.x, p.y, p.z, size, &key) || !vox_probe(tab, mask, key, &h)) return;
-        cnt += 1.0;
-        const float3 up = unit_or_zero(fmaf(T[8], rn.z, fmaf(T[4], rn.y, T[0] * rn.x)), fmaf(T[9], rn.z, fmaf(T[5], rn.y, T[1] * rn.x)),
-                                       fmaf(T[10], rn.z, fmaf(T[6], rn.y, T[2] * rn.x)));
-        const float nxx = h.a.w, nxy = h.b.x, nxz = h.b.y, nyy = h.b.z, nyz = h.b.w, nzz = h.c.x;
-        const float sxx = 2.f - g * (nxx + up.x * up.x), syy = 2.f - g * (nyy + up.y * up.y), szz = 2.f - g * (nzz + up.z * up.z);
-        const float sxy = -g * (nxy + up.x * up.y), sxz = -g * (nxz + up.x * up.z), syz = -g * (nyz + up.y * up.z);
-        gicp_pair_sums<false>(acc, sxx, sxy, sxz, syy, syz, szz, p, make_float3(p.x - h.a.x, p.y - h.a.y, p.z - h.a.z), 1.0);
-    };
+    auto pair = [&](float4 r, float3 rn) { voxel_pair(T, r, rn, tab, mask, size, g, acc, cnt); };
 #pragma unroll
     for (int u = 0; u < PF; ++u)
         if (e0 + u * stride < n) pair(pr[u], pn[u]);
     for (int64_t e = e0 + PF * stride; e < n; e += stride)
         pair(reading[e], read_normals ? *reinterpret_cast<const float3*>(read_normals + e) : make_float3(0.f, 0.f, 0.f));
+
+    pair_sums_fold<256, 27, false>(acc, cnt, cnt, nullptr, hists);
+}
+
+// The pair sums of a batch of readings (icpmi_voxel_register_batch_dev, icpmi_voxel_register_multistart*), grid =
+// (workgroups of the largest member, members).  blockIdx.y = the member: its slice of the centred readings and of the padded normals
+// (ba.qstride), its state, its accumulators.  As in accumulate_kernel a member uses the workgroups -- and the stride -- it has alone
+// (acc_blocks of its own n; the grid's other workgroups return at once), so every thread adds the pairs it adds in a single
+// registration in the same order, and pair_sums_fold joins fixed-point integers: the member's sums are the bits it has alone.
+// The level is the member's own header word; table, mask and size come from `desc`, the 16 descriptor dwords of the handle's batch
+// block (a one-size handle uploads one level, repeated in the other slots: one body serves both).  The prologue is
+// voxel_pairs_sched_kernel's: header dword, descriptor dword and the first two points and normals of every lane in one trip.  Every
+// member has points and normals (api.hip sends a batch with an empty member through the one-by-one route); no lane past a member's
+// reading forms an address.
+__device__ __forceinline__ int vox_acc_blocks(int n, int cap)
+{
+    const int nb = (n + 255) / 256; // (loop.hip: acc_blocks_dev with 256 threads)
+    return nb < 1 ? 1 : (nb > cap ? cap : nb);
+}
+
+// (waves_per_eu: without the hint the allocator takes 98 VGPRs -- two over the 96 of voxel_pairs_sched_kernel and one wave per SIMD fewer;
+// with it 96 and no scratch: profiles/voxel_batch_isa_diff.txt)
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 8))) void voxel_pairs_batch_kernel(const float4* __restrict__ reading, const float4* __restrict__ read_normals, BatchArgs ba,
+                                                                int acc_cap, IcpState* __restrict__ st, const unsigned* __restrict__ desc, float eps,
+                                                                unsigned* __restrict__ hists)
+{
+    asm volatile("" ::"s"(ba.n[blockIdx.y]), "s"(ba.qstride), "s"(acc_cap), "s"(reading), "s"(read_normals), "s"(st), "s"(desc), "s"(eps), "s"(hists));
+    const int n = ba.n[blockIdx.y];
+    const int nbe = vox_acc_blocks(n, acc_cap);
+    if ((int)blockIdx.x >= nbe) return;
+    {
+        const size_t qo = (size_t)blockIdx.y * (size_t)ba.qstride;
+        reading += qo; read_normals += qo;
+        hists += (size_t)blockIdx.y * ICPMI_SELHIST_WORDS;
+        st += blockIdx.y;
+    }
+    unsigned hw = hdr_load(st);
+    unsigned dw = desc[ICPMI_VS_DESC + (threadIdx.x & 15)];
+    const int64_t stride = (int64_t)nbe * 256;
+    const int64_t e0 = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    constexpr int PF = 2;
+    float4 pr[PF]; float3 pn[PF];
+#pragma unroll
+    for (int u = 0; u < PF; ++u) {
+        const int64_t e = e0 + u * stride;
+        const bool in = e < n;
+        pr[u] = in ? ld_stream(reading + e) : make_float4(0.f, 0.f, 0.f, 0.f);
+        pn[u] = in ? *reinterpret_cast<const float3*>(read_normals + e) : make_float3(0.f, 0.f, 0.f);
+    }
+    asm volatile("" : "+v"(hw), "+v"(dw));
+    const HdrView hv{hw}, dv{dw};
+    const int done = hv.i(ICPMI_HDR_W(done));
+    const int lvl = hv.i(ICPMI_HDR_W(vox_level)) & (ICPMI_MAX_VOXEL_LEVELS - 1);
+    const uint4* __restrict__ tab = reinterpret_cast<const uint4*>((uintptr_t)dv.u64(4 * lvl));
+    const unsigned mask = dv.u(4 * lvl + 2);
+    const float size = dv.f(4 * lvl + 3);
+    float T[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) T[i] = hv.f(ICPMI_HDR_W(T_iter) + i);
+    if (done) return;
+    const float g = 1.f - eps;
+    double acc[27];
+#pragma unroll
+    for (int i = 0; i < 27; ++i) acc[i] = 0.0;
+    double cnt = 0.0;
+#pragma unroll
+    for (int u = 0; u < PF; ++u)
+        if (e0 + u * stride < n) voxel_pair(T, pr[u], pn[u], tab, mask, size, g, acc, cnt);
+    for (int64_t e = e0 + PF * stride; e < n; e += stride)
+        voxel_pair(T, reading[e], *reinterpret_cast<const float3*>(read_normals + e), tab, mask, size, g, acc, cnt);
 
     pair_sums_fold<256, 27, false>(acc, cnt, cnt, nullptr, hists);
 }
@@ -573,6 +638,38 @@ void voxel_enqueue_pairs(icpmi_ctx* c, int64_t n, int nb, float eps)
     }
     hipLaunchKernelGGL(voxel_pairs_kernel, dim3(nb), dim3(256), 0, c->stream, (const float4*)c->d_reading, (const float4*)c->d_read_normals, (int)n,
                        c->d_state.get(), (const uint4*)c->vox[0].tab.get(), c->vox[0].mask, c->voxel_size, eps, c->d_selhist.get());
+}
+
+// The device block of a batch (common.h: icpmi_ctx::d_vox_batch): ICPMI_VS_WORDS dwords whose descriptor part every member reads -- for a
+// one-size handle too: its one level in all four slots -- and behind them one block of ICPMI_VS_WORDS per member, whose report part
+// (ICPMI_VS_BASE ..) is that member's.  The tables are current (voxel_ensure_table); uploaded again when they, or the sizes, change.
+// Allocates and waits: before anything of the batch is enqueued.
+icpmi_status voxel_ensure_batch_block(icpmi_ctx* c)
+{
+    const int L = c->vox_levels;
+    unsigned desc[4 * ICPMI_MAX_VOXEL_LEVELS];
+    for (int l = 0; l < ICPMI_MAX_VOXEL_LEVELS; ++l) {
+        const int src = l < L ? l : L - 1;
+        const unsigned long long a = (unsigned long long)(uintptr_t)c->vox[src].tab.get();
+        desc[4 * l + 0] = (unsigned)a; desc[4 * l + 1] = (unsigned)(a >> 32); desc[4 * l + 2] = c->vox[src].mask;
+        memcpy(desc + 4 * l + 3, c->vox_sizes + src, sizeof(float));
+    }
+    const uint64_t sig = voxel_sched_sig(c, 0);
+    if (c->d_vox_batch.get() && c->vox_batch_sig == sig) return ICPMI_OK;
+    constexpr size_t words = (size_t)ICPMI_VS_WORDS * (1 + ICPMI_MAX_BATCH);
+    if (c->d_vox_batch.ensure(c, words) != ICPMI_OK) return ICPMI_ERR_HIP;
+    HIP_TRY(c, hipMemsetAsync(c->d_vox_batch.get(), 0, words * sizeof(unsigned), c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->d_vox_batch.get() + ICPMI_VS_DESC, desc, sizeof desc, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream)); // (desc is on this frame)
+    c->vox_batch_sig = sig;
+    return ICPMI_OK;
+}
+
+// the pair sums of a batch's iteration on the handle's stream (no allocation, no wait); nmax = the largest member, cap = loop.hip's acc_cap
+void voxel_enqueue_pairs_batch(icpmi_ctx* c, const BatchArgs& ba, int nb, int cap, float eps)
+{
+    hipLaunchKernelGGL(voxel_pairs_batch_kernel, dim3(nb, ba.nscan), dim3(256), 0, c->stream, (const float4*)c->d_reading, (const float4*)c->d_read_normals, ba,
+                       cap, c->d_state.get(), (const unsigned*)c->d_vox_batch.get(), eps, c->d_selhist.get());
 }
 
 // level: of the schedule, 0 the coarsest; -1 the finest

@@ -851,6 +851,69 @@ VoxelPoseScores GpuICPSequence::voxelScores(const DataPoints& readingIn, const s
     return voxelScoresFiltered(filteredReading(readingIn), poses, level, beta);
 }
 
+// ---- many readings, or many starts, in one loop on the voxel path (include/icpmi.h: icpmi_voxel_register_*) ----
+static const float* normalsOf(const DataPoints& cloud)
+{
+    if (cloud.descriptorExists("normals") && cloud.getDescriptorByName("normals").span == 3) return cloud.getDescriptorByName("normals").data.data();
+    return nullptr;
+}
+
+MultiStartResult GpuICPSequence::registerVoxelBatch(const std::vector<DataPoints>& readingsIn)
+{
+    const size_t B = readingsIn.size();
+    std::vector<DataPoints> owned;
+    if (hasReadingFilters()) for (const DataPoints& r : readingsIn) owned.push_back(filteredReading(r)); // once per reading
+    const std::vector<DataPoints>& readings = hasReadingFilters() ? owned : readingsIn;
+    MultiStartResult out;
+    out.correction.assign(B, Mat4::identity());
+    out.stats.assign(B, icpmi_stats{});
+    out.status.assign(B, ICPMI_OK);
+    std::vector<const float*> pts(B), nrm(B);
+    std::vector<int64_t> ns(B);
+    for (size_t b = 0; b < B; ++b) { pts[b] = readings[b].features.data(); nrm[b] = normalsOf(readings[b]); ns[b] = (int64_t)readings[b].getNbPoints(); }
+    std::vector<float> T(16 * std::max<size_t>(B, 1));
+    stagedPoints = 0;
+    haveCovariance = false; haveLocalizability = false;
+    check(h, icpmi_voxel_register_batch(h, (int32_t)B, pts.data(), ns.data(), nrm.data(), 0, T.data(), out.stats.data(), out.status.data()));
+    for (size_t b = 0; b < B; ++b) std::copy(T.begin() + 16 * b, T.begin() + 16 * b + 16, out.correction[b].m.begin());
+    if (B) lastStats = out.stats.back();
+    return out;
+}
+
+MultiStartResult GpuICPSequence::voxelMultiStartFiltered(const DataPoints& reading, const std::vector<Mat4>& priors)
+{
+    const size_t S = priors.size();
+    MultiStartResult out;
+    out.correction.assign(S, Mat4::identity());
+    out.stats.assign(S, icpmi_stats{});
+    out.status.assign(S, ICPMI_OK);
+    std::vector<float> P(16 * std::max<size_t>(S, 1)), T(16 * std::max<size_t>(S, 1));
+    for (size_t s = 0; s < S; ++s) std::copy(priors[s].m.begin(), priors[s].m.end(), P.begin() + 16 * s);
+    stagedPoints = 0;
+    haveCovariance = false; haveLocalizability = false;
+    check(h, icpmi_voxel_register_multistart(h, reading.features.data(), (int64_t)reading.getNbPoints(), normalsOf(reading), P.data(), (int32_t)S, 0,
+                                             T.data(), out.stats.data(), out.status.data()));
+    for (size_t s = 0; s < S; ++s) std::copy(T.begin() + 16 * s, T.begin() + 16 * s + 16, out.correction[s].m.begin());
+    if (S) lastStats = out.stats.back();
+    return out;
+}
+
+MultiStartResult GpuICPSequence::registerVoxelMultiStart(const DataPoints& readingIn, const std::vector<Mat4>& priors)
+{
+    if (!hasReadingFilters()) return voxelMultiStartFiltered(readingIn, priors);
+    return voxelMultiStartFiltered(filteredReading(readingIn), priors);
+}
+
+// icpmi_get_voxel_batch_report: one entry per level the member entered
+std::vector<GpuICPSequence::VoxelLevelReport> GpuICPSequence::voxelBatchReport(int member) const
+{
+    int32_t levels = 0, it[4], pf[4], pl[4];
+    check(h, icpmi_get_voxel_batch_report(h, member, &levels, it, pf, pl));
+    std::vector<VoxelLevelReport> out;
+    for (int l = 0; l < levels && l < 4; ++l) out.push_back({it[l], pf[l], pl[l]});
+    return out;
+}
+
 VoxelRelocalization GpuICPSequence::relocalizeVoxel(const DataPoints& readingIn, const std::vector<Mat4>& candidates, const RelocalizeVoxelOptions& options)
 {
     if (candidates.empty()) throw InvalidParameter("relocalizeVoxel: no candidates");
@@ -865,22 +928,22 @@ VoxelRelocalization GpuICPSequence::relocalizeVoxel(const DataPoints& readingIn,
     const size_t k = std::min<size_t>(order.size(), (size_t)std::max(1, options.refine));
     std::vector<Mat4> refined(k);
     std::vector<icpmi_status> status(k, ICPMI_OK);
-    const RigidTransformation move(h);
-    for (size_t i = 0; i < k; ++i) { // the chain as it is, the whole schedule, start after start (a voxel chain reads no row of the reading but its normals)
-        const Mat4& cand = candidates[(size_t)order[i]];
-        const DataPoints moved = move.compute(reading, cand);
-        const float* normals = nullptr;
-        if (moved.descriptorExists("normals") && moved.getDescriptorByName("normals").span == 3)
-            normals = moved.getDescriptorByName("normals").data.data();
-        Mat4 T = Mat4::identity();
-        haveCovariance = false; haveLocalizability = false;
-        const icpmi_status s = icpmi_register(h, moved.features.data(), (int64_t)moved.getNbPoints(), normals, T.data(), &lastStats);
-        if (s == ICPMI_ERR_NO_POINT_TO_MINIMIZE || s == ICPMI_ERR_NO_OUTLIER_TO_FILTER || s == ICPMI_ERR_BOUND || s == ICPMI_ERR_NAN) {
-            status[i] = s; refined[i] = cand; // a start that did not converge is out
-            continue;
+    // the chain as it is, the whole schedule, the starts of a chunk of 16 in one loop: every start is bit for bit the reading moved by its
+    // candidate and registered alone (a voxel chain reads no row of the reading but its normals)
+    for (size_t c0 = 0; c0 < k; c0 += 16) {
+        const size_t cn = std::min<size_t>(16, k - c0);
+        std::vector<Mat4> chunk(cn);
+        for (size_t j = 0; j < cn; ++j) chunk[j] = candidates[(size_t)order[c0 + j]];
+        const MultiStartResult ms = voxelMultiStartFiltered(reading, chunk);
+        for (size_t j = 0; j < cn; ++j) {
+            const icpmi_status s = ms.status[j];
+            if (s == ICPMI_ERR_NO_POINT_TO_MINIMIZE || s == ICPMI_ERR_NO_OUTLIER_TO_FILTER || s == ICPMI_ERR_BOUND || s == ICPMI_ERR_NAN) {
+                status[c0 + j] = s; refined[c0 + j] = chunk[j]; // a start that did not converge is out
+                continue;
+            }
+            check(h, s);
+            refined[c0 + j] = ms.correction[j] * chunk[j];
         }
-        check(h, s);
-        refined[i] = T * cand;
     }
     VoxelPoseScores again = voxelScoresFiltered(reading, refined, -1, options.beta);
     for (size_t i = 0; i < k; ++i) if (status[i] != ICPMI_OK) again.status[i] = status[i];

@@ -164,9 +164,19 @@ public:
     // `level` (-1: the finest), one call (icpmi_voxel_score_poses).  The chain's reading filters are applied once.  Errors of one pose are in
     // its status; errors of the whole call throw.  Leaves stats() alone.
     VoxelPoseScores voxelScores(const DataPoints& reading, const std::vector<Mat4>& poses, int level = -1, float beta = 1.f) const;
+    // On a VoxelMatcher chain: up to 16 readings, each with its `normals`, registered in one loop (icpmi_voxel_register_batch_dev after one
+    // upload per reading); every reading as operator() registers it alone, bit for bit.  The chain's reading filters are applied once per
+    // reading.  Errors of one reading are in its status; errors of the whole call throw in the C call's words.  stats() ends as the last
+    // reading's; no covariance and no staged scan are left.
+    MultiStartResult registerVoxelBatch(const std::vector<DataPoints>& readings);
+    // ... one reading moved by every prior (at most 16) on the device and the moved readings registered in one loop
+    // (icpmi_voxel_register_multistart): start s as RigidTransformation::compute(reading, priors[s]) followed by operator() alone.
+    MultiStartResult registerVoxelMultiStart(const DataPoints& reading, const std::vector<Mat4>& priors);
+    std::vector<VoxelLevelReport> voxelBatchReport(int member) const; // icpmi_get_voxel_batch_report: a member of the last of the two calls
     // Where is the sensor, given candidate poses -- on a VoxelMatcher chain: every candidate scored at options.level and ranked
-    // (rankVoxelCandidates), the reading moved by each of the best options.refine registered by the chain as it is (the whole schedule, start
-    // after start), the refined poses scored at the finest level and ranked again.  ConvergenceError when nothing survives.
+    // (rankVoxelCandidates), the reading moved by each of the best options.refine registered by the chain as it is (the whole schedule, all
+    // starts in one loop: registerVoxelMultiStart, chunks of 16), the refined poses scored at the finest level and ranked again.
+    // ConvergenceError when nothing survives.
     VoxelRelocalization relocalizeVoxel(const DataPoints& reading, const std::vector<Mat4>& candidates, const RelocalizeVoxelOptions& options = RelocalizeVoxelOptions());
 
     // Sweep registration (include/icpmi.h: icpmi_register_sweep; not libpointmatcher's): the skewed scan in the sensor frame with its point
@@ -220,6 +230,7 @@ private:
     PoseScores residualsFiltered(const DataPoints& reading, const std::vector<Mat4>& poses, int kind) const; // (the reading as the chain's filters left it)
     MultiStartResult multiStartFiltered(const DataPoints& reading, const std::vector<Mat4>& priors);
     VoxelPoseScores voxelScoresFiltered(const DataPoints& reading, const std::vector<Mat4>& poses, int level, float beta) const;
+    MultiStartResult voxelMultiStartFiltered(const DataPoints& reading, const std::vector<Mat4>& priors);
     void requireBareReadingChain(const char* who) const;    // InvalidParameter for a chain that reads the reading's normals or descriptors
     icpmi_handle h = nullptr;
     icpmi_config cfg;

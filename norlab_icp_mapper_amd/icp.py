@@ -1053,11 +1053,64 @@ class ICPSequence:
         """icpmi_voxel_score_poses_dev: voxelScores() for a reading and its normals already in HBM."""
         return self._voxel_scores(self._lib.icpmi_voxel_score_poses_dev, d_scan_ptr, n, d_normals_ptr, poses, level, beta)
 
+    # ---- many readings, or many starts, in one loop on the voxel path (icpmi_voxel_register_*; DESIGN.md 4.23) ----
+    def voxelRegisterBatchDev(self, d_scan_ptrs, ns, d_normals_ptrs, fixed_iterations=0):
+        """icpmi_voxel_register_batch_dev: B <= 16 readings in HBM (device pointers, sizes) with their normals (device pointers, 3 floats
+        per point) against the map of a VoxelMatcher handle in one loop; every reading to the bits registerDev gives it alone.
+        Returns (list of 4x4 corrections, list of Stats, list of status codes)."""
+        B = len(d_scan_ptrs)
+        if len(ns) != B or len(d_normals_ptrs) != B:
+            raise InvalidParameter("voxelRegisterBatchDev: one size and one normals pointer per reading")
+        ptrs = (C.c_void_p * max(B, 1))(*[None if p is None else int(p) for p in d_scan_ptrs])
+        nptrs = (C.c_void_p * max(B, 1))(*[None if p is None else int(p) for p in d_normals_ptrs])
+        nn = (C.c_int64 * max(B, 1))(*[int(n) for n in ns])
+        T = (C.c_float * (16 * max(B, 1)))()
+        stats = (_capi.Stats * max(B, 1))()
+        status = (C.c_int * max(B, 1))()
+        self._check(self._lib.icpmi_voxel_register_batch_dev(self._h, B, ptrs, nn, nptrs, int(fixed_iterations), T, stats, status))
+        self.batch_stats = stats
+        return [_T_from_c(T[16 * b:16 * b + 16]) for b in range(B)], [stats[b] for b in range(B)], [int(status[b]) for b in range(B)]
+
+    def _voxel_multistart(self, fn, scan_ptr, n, nptr, priors, fixed_iterations):
+        Tc = self._poses_to_c(priors)
+        S = Tc.shape[0] // 16
+        T = (C.c_float * (16 * max(S, 1)))()
+        stats = (_capi.Stats * max(S, 1))()
+        status = (C.c_int * max(S, 1))()
+        self._check(fn(self._h, scan_ptr, int(n), nptr, Tc.ctypes.data, S, int(fixed_iterations), T, stats, status))
+        return [_T_from_c(T[16 * s:16 * s + 16]) for s in range(S)], [stats[s] for s in range(S)], [int(status[s]) for s in range(S)]
+
+    def voxelRegisterMultiStartDev(self, d_scan_ptr, n, d_normals_ptr, priors, fixed_iterations=0):
+        """icpmi_voxel_register_multistart_dev: the reading and its normals in HBM registered from every prior of `priors` (S <= 16,
+        (S, 4, 4)) in one loop; start s is transform(priors[s]) followed by the registration of the result, bit for bit.
+        Returns (list of 4x4 corrections, list of Stats, list of status codes); composing with the prior stays the caller's."""
+        return self._voxel_multistart(self._lib.icpmi_voxel_register_multistart_dev, d_scan_ptr, n, d_normals_ptr, priors, fixed_iterations)
+
+    def voxelRegisterMultiStart(self, reading, normals, priors, fixed_iterations=0):
+        """icpmi_voxel_register_multistart: voxelRegisterMultiStartDev for a reading on the host (one upload of it and its normals)."""
+        scan = _f32c(reading, 4)
+        nptr = None
+        if normals is not None:
+            normals = _f32c(normals, 3)
+            if normals.shape[0] != scan.shape[0]:
+                raise InvalidParameter("normals / cloud size mismatch")
+            nptr = normals.ctypes.data
+        return self._voxel_multistart(self._lib.icpmi_voxel_register_multistart, scan.ctypes.data, scan.shape[0], nptr, priors, fixed_iterations)
+
+    def voxel_batch_report(self, member):
+        """icpmi_get_voxel_batch_report: what voxelScheduleReport() answers, for member `member` (start `member`) of the last voxel batch
+        or multistart: a list with one (iterations, pairs_first, pairs_last) per level entered"""
+        lv = C.c_int32(0)
+        it, pf, pl = ((C.c_int32 * VOXEL_MAX_LEVELS)() for _ in range(3))
+        self._check(self._lib.icpmi_get_voxel_batch_report(self._h, int(member), C.byref(lv), it, pf, pl))
+        return [(it[i], pf[i], pl[i]) for i in range(lv.value)]
+
     def relocalizeVoxel(self, reading, normals, candidates, refine=4, level=0, beta=1.0, min_pairs_ratio=0.0):
         """Where is the sensor, given candidate poses -- on a VoxelMatcher handle.  Every candidate is scored at `level` (0: the coarsest
         level of a schedule, the widest basin) and ranked (rank_voxel_candidates); the reading moved by each of the best `refine` is
-        registered by the handle's own chain, the whole schedule, start after start; the refined poses are scored at the finest level and
-        ranked again.  Returns a Relocalization whose `residual` is the winner's VoxelScore; ConvergenceError when nothing survives."""
+        registered by the handle's own chain, the whole schedule, all starts in one loop (voxelRegisterMultiStart, chunks of 16); the
+        refined poses are scored at the finest level and ranked again.  Returns a Relocalization whose `residual` is the winner's
+        VoxelScore; ConvergenceError when nothing survives."""
         scan, nrm = _f32c(reading, 4), _f32c(normals, 3)
         cand = np.asarray(candidates, dtype=np.float32).reshape(-1, 4, 4)
         if cand.shape[0] == 0:
@@ -1069,18 +1122,22 @@ class ICPSequence:
             raise ConvergenceError("relocalizeVoxel: no candidate survived the scoring")
         best = order[:max(1, int(refine))]
         refined, status = [], []
-        for i in best:  # (a voxel chain reads no row of the reading but its normals: the registration call itself, so that a start's status stays what it was)
-            moved, movedn = self.transform(cand[i], scan, nrm)
-            T = (C.c_float * 16)()
+        soft = (_capi.ERR_NO_POINT_TO_MINIMIZE, _capi.ERR_NO_OUTLIER_TO_FILTER, _capi.ERR_BOUND, _capi.ERR_NAN)
+        for c0 in range(0, len(best), 16):  # one multistart call per chunk of 16: every start is bit for bit transform + icpmi_register
+            chunk = best[c0:c0 + 16]
+            corr, sts, status_c = self.voxelRegisterMultiStart(scan, nrm, cand[chunk])
             self._last_n = n
-            st = self._lib.icpmi_register(self._h, moved.ctypes.data, n, movedn.ctypes.data, T, C.byref(self.stats))
-            if st in (_capi.ERR_NO_POINT_TO_MINIMIZE, _capi.ERR_NO_OUTLIER_TO_FILTER, _capi.ERR_BOUND, _capi.ERR_NAN):
-                refined.append(cand[i].copy())  # a start that did not converge is out, under the status it ended with
-                status.append(int(st))
-                continue
-            self._check(st)
-            refined.append(compose_pose(_T_from_c(T[:]), cand[i]))
-            status.append(0)
+            C.memmove(C.byref(self.stats), C.byref(sts[-1]), C.sizeof(_capi.Stats))  # (the last refined start's, as start after start left it)
+            for j, i in enumerate(chunk):
+                st = status_c[j]
+                if st in soft:
+                    refined.append(cand[i].copy())  # a start that did not converge is out, under the status it ended with
+                    status.append(int(st))
+                    continue
+                if st != _capi.ICPMI_OK:
+                    raise _STATUS_EXC.get(st, RuntimeError)(f"relocalizeVoxel: the refinement of candidate {i} ended with status {st}")
+                refined.append(compose_pose(corr[j], cand[i]))
+                status.append(0)
         refined = np.stack(refined)
         again = self.voxelScores(scan, nrm, refined, level=None, beta=beta)
         again.status = [a if s == 0 else s for a, s in zip(again.status, status)]  # a start that did not converge is out
