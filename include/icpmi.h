@@ -488,6 +488,78 @@ icpmi_status icpmi_get_voxel_batch_report(icpmi_handle h, int32_t member, int32_
  * voxel path (icpmi_register*, and the one-by-one route of the calls above) */
 icpmi_status icpmi_debug_voxel_batch_calls(icpmi_handle h, int64_t out[3]);
 
+/* ---- Global localisation: branch and bound over voxel occupancy levels (the 3D-BBS formulation of Aoki, Koide, Oishi,
+ * Yokozuka, Banno, ICRA 2024).  A search without candidates: exhaustive over a lattice of translations and a caller-supplied list of
+ * rotations, exact, all in integers.  It needs no normals on either cloud and no matcher, and works on any handle that holds a map.
+ *
+ * Frame and cells.  Points live in the handle's centred frame, mu = icpmi_get_map_mean.  s0 (finite, > 0, float32) is the finest cell size.
+ *   Cells are those of the voxel table above: per axis (int)floorf(x / s0) in float32, taking part iff finite and |i| < 2^19 -- half of the
+ *   table's range, so that cell plus offset always fits the 63-bit key.  A map point out of that range: ICPMI_ERR_INVALID_ARG.
+ *   occ0 = the set of cells of the resident map's points.
+ * Poses.  Rotation k of the list is R_k: R9 + 9 k, column-major 3 x 3 (R[r][c] = R9[9 k + 3 c + r]).  The translation is tau = mu + s0 * a
+ *   with integer a in a window [a_min, a_max] per axis; the pose [R_k | tau] is a correction in the map frame, as T is elsewhere.
+ *   For a reading point x (x, y, z, w; w not used) y = R_k x, per row r in float32 with no contraction:
+ *     fmaf(R[r][2], z, fmaf(R[r][1], y, R[r][0] * x)),  c = floorf(y / s0) per axis.
+ *   A point whose y is not finite, or with |c| >= 2^19 on an axis, adds nothing under that rotation.
+ * Score.  score(k, a) = the number of reading points with c + a in occ0 (int64).
+ * Levels l = 0 .. L-1, L in 1 .. 8.  A node (k, l, A) stands for the 2^l cube of translations a in [A * 2^l, A * 2^l + 2^l - 1] per axis.
+ *   bound(k, l, A) = the number of points with (c >> l) + A in occB_l (>> = the arithmetic shift, floor division), where
+ *   occC_l = { u >> l : u in occ0 }, occB_0 = occ0, and for l >= 1 occB_l = { w - e : w in occC_l, e in {0, 1}^3 }.
+ *   For a in the node's cube (c + a) >> l is (c >> l) + A or that plus one per axis, so occ0[c + a] <= occB_l[(c >> l) + A]: the bound is
+ *   at least the largest score in the cube, and bound(k, 0, a) = score(k, a).
+ * Tables.  Per level the keys of occB_l ascending (icpmi_get_occupancy_level hands them out as cells, with icpmi_get_voxel_map's capacity
+ *   rule; cap == 0 with ijk3 == NULL is a size query: *n_keys alone, ICPMI_OK) and an open-addressing table of key-only 8-byte slots: capacity the smallest power of two >= 2 x keys, first slot
+ *   (key * 0x9E3779B97F4A7C15 >> 32) & (capacity - 1), linear probing.  Built lazily on the device and kept on the handle for (map, s0): a level
+ *   depends on (map, s0, l) alone, so a pyramid of fewer levels is extended and one of more serves a call that asks for fewer.
+ * Window.  options.box_lo / box_hi (has_box != 0): a box in the map frame in metres; a_min = floor((lo - mu) / s0), a_max =
+ *   floor((hi - mu) / s0), formed in double.  lo <= hi, finite, |a| < 2^19, else ICPMI_ERR_INVALID_ARG.  Without a box the window is the
+ *   map's bounding box in cells: the smallest and the largest cell of occ0 per axis.  Top-level nodes are the blocks A in
+ *   [a_min >> (L-1), a_max >> (L-1)] of every rotation; a child whose cube does not meet the window is dropped unscored, a leaf outside
+ *   the window is no candidate.
+ * Search.  Best-first and batched.  A heap ordered by (bound descending, level ascending, k ascending, A lexicographic).  The top-level
+ *   nodes are scored in launches of at most *launch_nodes nodes (icpmi_global_localize_shape).  Then rounds: pop up to `batch` nodes whose
+ *   bound is > best; form their window-clipped children (at most 8 each); score all of them in one launch, read the counts back once; the
+ *   first leaf in the heap's order becomes the best if its score is > best (strictly: the first in that order wins a tie); push every
+ *   inner child with bound > best.  It stops when the heap's top is <= best.  The answer is the same for every batch; nodes_scored is
+ *   not, and is a function of (map, reading, rotations, options) alone.
+ *   levels 0 = automatic: the largest L <= 6 with 2^(L-1) at most the window's longest side in cells, at least 1.
+ *   min_score_ratio (default 0): need = ceil((double)(float)ratio * n); the search starts with best = need - 1 and answers found = 0
+ *   (ICPMI_OK) when nothing reaches need: what keeps a reading that is not in the map from costing more than the exhaustive search.
+ *   max_nodes (default 0: no cap): checked behind every launch; once more nodes than that have been scored the search stops with the best
+ *   so far and proven = 0.  batch: 1 .. 8192 (default 64): a round's children, at most 8 each, fit one launch.
+ *   A larger batch means fewer, fuller launches and more nodes scored (DESIGN.md 4.24 has both measured); the default is provisional.
+ * Result.  found; proven (the search ran to its end); rotation k, cell a, score; points = the points that took part under R_k; T =
+ *   [R_k | tau] column-major, tau = (double)mu + (double)s0 * a rounded once to float; levels = L; nodes_scored, leaves_scored, launches
+ *   (scoring launches).  found = 0: rotation -1, T the identity.
+ * icpmi_occupancy_score_nodes (test seam and inspection): bound(k, l, A) of n_nodes caller-given nodes, 5 ints each (k, l, A.x, A.y, A.z)
+ *   with k in [0, n_rot), l in [0, levels), |A| < 2^19, through the kernel the search uses; `levels` in 1 .. 8.
+ * Errors of the whole call, found before anything is enqueued, with the result zeroed: no map, null arguments, n < 0, n_rot outside
+ *   1 .. 4096, a rotation that is not orthonormal (the test of icpmi_transform), s0 not finite or <= 0, levels outside 0 .. 8, batch outside
+ *   1 .. 8192, a negative max_nodes, a min_score_ratio that is not finite or outside 0 .. 1, a bad box (ICPMI_ERR_INVALID_ARG); n == 0
+ *   (ICPMI_ERR_NO_POINT_TO_MINIMIZE); planar mode, force_2d or is_2d (ICPMI_ERR_UNSUPPORTED, the message names the call).
+ * Afterwards the handle is as after icpmi_voxel_lookup: no registration result, covariance, staged scan or captured loop has changed, and
+ *   the VoxelMatcher tables are neither read nor touched.  icpmi_global_localize uploads the reading once. */
+typedef struct {
+    float cell_size; int32_t levels; float min_score_ratio; int32_t batch; int64_t max_nodes; int32_t has_box; int32_t reserved0;
+    double box_lo[3]; double box_hi[3]; int32_t reserved[8];
+} icpmi_global_localize_options;
+typedef struct {
+    int32_t found; int32_t proven; int32_t rotation; int32_t cell[3]; int64_t score; int64_t points; float T[16]; int32_t levels;
+    int32_t launches; int64_t nodes_scored; int64_t leaves_scored; int32_t reserved[8];
+} icpmi_global_localize_result;
+void icpmi_global_localize_options_default(icpmi_global_localize_options* opts); /* cell_size 0.5, levels 0, ratio 0, batch 64, no cap, no box */
+void icpmi_global_localize_shape(int32_t* slice, int32_t* tile, int32_t* launch_nodes); /* points per slice, nodes a workgroup walks, nodes per launch */
+icpmi_status icpmi_global_localize(icpmi_handle h, const float* scan4, int64_t n, const float* R9, int32_t n_rot,
+                                   const icpmi_global_localize_options* opts, icpmi_global_localize_result* result);
+icpmi_status icpmi_global_localize_dev(icpmi_handle h, const float* d_scan4, int64_t n, const float* R9, int32_t n_rot,
+                                       const icpmi_global_localize_options* opts, icpmi_global_localize_result* result);
+icpmi_status icpmi_occupancy_score_nodes(icpmi_handle h, const float* scan4, int64_t n, const float* R9, int32_t n_rot, float s0, int32_t levels,
+                                         const int32_t* nodes5, int64_t n_nodes, int64_t* counts);
+icpmi_status icpmi_get_occupancy_level(icpmi_handle h, float s0, int32_t levels, int32_t level, int64_t cap, int32_t* ijk3, int64_t* n_keys);
+/* inspection (scripts/global_localize_bench.py): of the pyramid the handle holds, *levels, and per level the keys, the bytes of keys and
+ * table, and the host milliseconds its build took; *builds = pyramids built on this handle so far.  Every pointer may be NULL. */
+icpmi_status icpmi_get_occupancy_info(icpmi_handle h, int32_t* levels, int64_t keys[8], int64_t bytes[8], float build_ms[8], int64_t* builds);
+
 /* ---- IntensityPointToPlaneErrorMinimizer: a photometric term on ICPMI_MIN_POINT_TO_PLANE.  Not libpointmatcher's: the joint
  * geometric + photometric objective of Park, Zhou, Koltun, "Colored Point Cloud Registration Revisited" (ICCV 2017), one scalar channel.
  *

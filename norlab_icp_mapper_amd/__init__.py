@@ -8,7 +8,7 @@ workload of SURVEY.md 8d).  Importing the package does not load the library; con
 """
 from . import synth  # noqa: F401
 from .icp import (ICPSequence, ConvergenceError, InvalidField, InvalidParameter, TransformationError,  # noqa: F401
-                  default_config, config_from_yaml_chain, rank_candidates, rank_voxel_candidates, candidate_grid)
+                  default_config, config_from_yaml_chain, rank_candidates, rank_voxel_candidates, candidate_grid, yaw_rotations)
 
 __all__ = ["ICPSequence", "ConvergenceError", "InvalidField", "InvalidParameter", "TransformationError",
-           "default_config", "config_from_yaml_chain", "rank_candidates", "rank_voxel_candidates", "candidate_grid", "synth"]
+           "default_config", "config_from_yaml_chain", "rank_candidates", "rank_voxel_candidates", "candidate_grid", "yaw_rotations", "synth"]

@@ -127,6 +127,19 @@ class VoxelScore(C.Structure):
     ]
 
 
+class GlobalLocalizeOptions(C.Structure):
+    """icpmi_global_localize_options: cell size, levels (0: automatic), min_score_ratio, batch, max_nodes (0: no cap) and the box."""
+    _fields_ = [("cell_size", C.c_float), ("levels", C.c_int32), ("min_score_ratio", C.c_float), ("batch", C.c_int32), ("max_nodes", C.c_int64),
+                ("has_box", C.c_int32), ("reserved0", C.c_int32), ("box_lo", C.c_double * 3), ("box_hi", C.c_double * 3), ("reserved", C.c_int32 * 8)]
+
+
+class GlobalLocalizeResult(C.Structure):
+    """icpmi_global_localize_result: the leaf found (rotation, cell, score, points, T column-major) and what the search took."""
+    _fields_ = [("found", C.c_int32), ("proven", C.c_int32), ("rotation", C.c_int32), ("cell", C.c_int32 * 3), ("score", C.c_int64),
+                ("points", C.c_int64), ("T", C.c_float * 16), ("levels", C.c_int32), ("launches", C.c_int32), ("nodes_scored", C.c_int64),
+                ("leaves_scored", C.c_int64), ("reserved", C.c_int32 * 8)]
+
+
 class Localizability(C.Structure):
     """icpmi_localizability: the report of icpmi_get_localizability (basis[6 e + i] = component i of eigenvector e)."""
     _fields_ = [
@@ -244,6 +257,13 @@ SYMBOLS = [
     ("icpmi_voxel_register_multistart", C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int32, C.c_int32, _P, _P, _P]),
     ("icpmi_get_voxel_batch_report", C.c_int, [_P, C.c_int32, C.POINTER(C.c_int32), _P, _P, _P]),
     ("icpmi_debug_voxel_batch_calls", C.c_int, [_P, _P]),
+    ("icpmi_global_localize_options_default", None, [C.POINTER(GlobalLocalizeOptions)]),
+    ("icpmi_global_localize_shape", None, [C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    ("icpmi_global_localize", C.c_int, [_P, _P, C.c_int64, _P, C.c_int32, C.POINTER(GlobalLocalizeOptions), C.POINTER(GlobalLocalizeResult)]),
+    ("icpmi_global_localize_dev", C.c_int, [_P, _P, C.c_int64, _P, C.c_int32, C.POINTER(GlobalLocalizeOptions), C.POINTER(GlobalLocalizeResult)]),
+    ("icpmi_occupancy_score_nodes", C.c_int, [_P, _P, C.c_int64, _P, C.c_int32, C.c_float, C.c_int32, _P, C.c_int64, _P]),
+    ("icpmi_get_occupancy_level", C.c_int, [_P, C.c_float, C.c_int32, C.c_int32, C.c_int64, _P, C.POINTER(C.c_int64)]),
+    ("icpmi_get_occupancy_info", C.c_int, [_P, C.POINTER(C.c_int32), _P, _P, _P, C.POINTER(C.c_int64)]),
     ("icpmi_debug_voxel_build_times", C.c_int, [_P, _P]),
     ("icpmi_debug_voxel_lookup_times", C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, C.POINTER(C.c_int64)]),
     ("icpmi_set_intensity_weight", C.c_int, [_P, C.c_float]),

@@ -1780,6 +1780,158 @@ icpmi_status icpmi_voxel_score_poses(icpmi_handle h, const float* scan4, int64_t
     return voxel_score_impl(h, "voxel_score_poses", scan4, true, n, scan_normals3, T, n_poses, opts, out, status);
 }
 
+// ---- global localisation (occupancy.hip) ----
+void icpmi_global_localize_options_default(icpmi_global_localize_options* opts)
+{
+    if (!opts) return;
+    memset(opts, 0, sizeof *opts);
+    opts->cell_size = 0.5f; opts->batch = 64;
+}
+
+void icpmi_global_localize_shape(int32_t* slice, int32_t* tile, int32_t* launch_nodes)
+{
+    int32_t s = 0, t = 0, ln = 0;
+    occ_shape(&s, &t, &ln);
+    if (slice) *slice = s;
+    if (tile) *tile = t;
+    if (launch_nodes) *launch_nodes = ln;
+}
+
+// what the occupancy calls share: a map, no planar mode, a reading, rigid rotations, a cell size, a level count in [lmin, 8]
+static icpmi_status occupancy_checks(icpmi_handle h, const char* who, const float* scan4, int64_t n, const float* R9, int32_t n_rot, float s0, int32_t levels,
+                                     int32_t lmin)
+{
+    const std::string w(who);
+    if (h->cfg.force_2d || h->cfg.is_2d) { h->last_error = w + ": is not served in planar mode (force_2d / is_2d)"; return ICPMI_ERR_UNSUPPORTED; }
+    if (h->m <= 0) { h->last_error = w + ": no map"; return ICPMI_ERR_INVALID_ARG; }
+    if (n_rot < 1 || n_rot > 4096) { h->last_error = w + ": n_rot must be in 1 .. 4096"; return ICPMI_ERR_INVALID_ARG; }
+    if (!R9 || n < 0 || (n > 0 && !scan4)) { h->last_error = w + ": bad arguments"; return ICPMI_ERR_INVALID_ARG; }
+    if (!std::isfinite(s0) || !(s0 > 0.f)) { h->last_error = w + ": the cell size must be finite and > 0"; return ICPMI_ERR_INVALID_ARG; }
+    if (levels < lmin || levels > ICPMI_MAX_OCC_LEVELS) { h->last_error = w + ": levels must be in " + (lmin ? "1" : "0") + " .. 8"; return ICPMI_ERR_INVALID_ARG; }
+    if (n > 0x7fffffff) { h->last_error = w + ": too many points"; return ICPMI_ERR_UNSUPPORTED; }
+    for (int k = 0; k < n_rot; ++k) {
+        float T[16] = {0};
+        for (int cc = 0; cc < 3; ++cc) for (int r = 0; r < 3; ++r) T[4 * cc + r] = R9[9 * (size_t)k + 3 * cc + r];
+        T[15] = 1.f;
+        bool finite = true;
+        for (int i = 0; i < 9; ++i) finite = finite && std::isfinite(R9[9 * (size_t)k + i]);
+        if (!finite || check_rigid(h, T) != ICPMI_OK) {
+            h->last_error = w + ": rotation " + std::to_string(k) + ": TransformationError: RigidTransformation: rotation part is not orthonormal (|1 - det| > 1e-3)";
+            return ICPMI_ERR_INVALID_ARG;
+        }
+    }
+    if (n == 0) { h->last_error = w + ": the reading is empty"; return ICPMI_ERR_NO_POINT_TO_MINIMIZE; }
+    return ICPMI_OK;
+}
+
+static icpmi_status global_localize_impl(icpmi_handle h, const char* who, const float* scan4, bool on_host, int64_t n, const float* R9, int32_t n_rot,
+                                         const icpmi_global_localize_options* opts, icpmi_global_localize_result* res)
+{
+    const std::string w(who);
+    if (!res) { h->last_error = w + ": result is null"; return ICPMI_ERR_INVALID_ARG; }
+    memset(res, 0, sizeof *res);
+    res->rotation = -1;
+    res->T[0] = res->T[5] = res->T[10] = res->T[15] = 1.f;
+    icpmi_global_localize_options o;
+    icpmi_global_localize_options_default(&o);
+    if (opts) o = *opts;
+    { const icpmi_status s = occupancy_checks(h, who, scan4, n, R9, n_rot, o.cell_size, o.levels, 0); if (s != ICPMI_OK) return s; }
+    if (o.batch < 1 || o.batch > 8192) { h->last_error = w + ": batch must be in 1 .. 8192"; return ICPMI_ERR_INVALID_ARG; }
+    if (o.max_nodes < 0) { h->last_error = w + ": max_nodes must be >= 0"; return ICPMI_ERR_INVALID_ARG; }
+    if (!std::isfinite(o.min_score_ratio) || o.min_score_ratio < 0.f || o.min_score_ratio > 1.f) {
+        h->last_error = w + ": min_score_ratio must be in 0 .. 1"; return ICPMI_ERR_INVALID_ARG;
+    }
+    int64_t a_min[3] = {0, 0, 0}, a_max[3] = {0, 0, 0};
+    if (o.has_box) {
+        for (int j = 0; j < 3; ++j) {
+            const double lo = o.box_lo[j], hi = o.box_hi[j];
+            const double fl = floor((lo - (double)h->mean[j]) / (double)o.cell_size), fh = floor((hi - (double)h->mean[j]) / (double)o.cell_size);
+            if (!std::isfinite(lo) || !std::isfinite(hi) || !(lo <= hi) || !(fabs(fl) < 524288.0) || !(fabs(fh) < 524288.0)) {
+                h->last_error = w + ": bad box (finite, lo <= hi, within 2^19 cells of the map's centroid)"; return ICPMI_ERR_INVALID_ARG;
+            }
+            a_min[j] = (int64_t)fl; a_max[j] = (int64_t)fh;
+        }
+    }
+    // the window's extent decides an automatic level count; without a box the window is the extent of the pyramid's level 0
+    int levels = o.levels;
+    if (!o.has_box) {
+        { const icpmi_status s = occ_ensure(h, o.cell_size, levels ? levels : 1); if (s != ICPMI_OK) return s; }
+        for (int j = 0; j < 3; ++j) { a_min[j] = h->occ.cell_lo[j]; a_max[j] = h->occ.cell_hi[j]; }
+    }
+    if (levels == 0) {
+        int64_t side = 1;
+        for (int j = 0; j < 3; ++j) side = std::max<int64_t>(side, a_max[j] - a_min[j] + 1);
+        levels = 1;
+        while (levels < 6 && ((int64_t)1 << levels) <= side) ++levels;
+    }
+    const float* d_scan = scan4;
+    if (on_host) { const float* none = nullptr; const icpmi_status ss = stage_in_scratch(h, scan4, n, nullptr, &d_scan, &none); if (ss != ICPMI_OK) return ss; }
+    const int64_t need = (int64_t)ceil((double)o.min_score_ratio * (double)n);
+    const icpmi_status s = occ_global_localize(h, (const float4*)d_scan, n, R9, n_rot, o.cell_size, levels, a_min, a_max, o.batch, need, o.max_nodes, res);
+    if (s != ICPMI_OK) { memset(res, 0, sizeof *res); res->rotation = -1; res->T[0] = res->T[5] = res->T[10] = res->T[15] = 1.f; }
+    return s;
+}
+
+icpmi_status icpmi_global_localize(icpmi_handle h, const float* scan4, int64_t n, const float* R9, int32_t n_rot, const icpmi_global_localize_options* opts,
+                                   icpmi_global_localize_result* result)
+{
+    CHECK_H(h);
+    return global_localize_impl(h, "global_localize", scan4, true, n, R9, n_rot, opts, result);
+}
+
+icpmi_status icpmi_global_localize_dev(icpmi_handle h, const float* d_scan4, int64_t n, const float* R9, int32_t n_rot,
+                                       const icpmi_global_localize_options* opts, icpmi_global_localize_result* result)
+{
+    CHECK_H(h);
+    return global_localize_impl(h, "global_localize_dev", d_scan4, false, n, R9, n_rot, opts, result);
+}
+
+icpmi_status icpmi_occupancy_score_nodes(icpmi_handle h, const float* scan4, int64_t n, const float* R9, int32_t n_rot, float s0, int32_t levels,
+                                         const int32_t* nodes5, int64_t n_nodes, int64_t* counts)
+{
+    CHECK_H(h);
+    { const icpmi_status s = occupancy_checks(h, "occupancy_score_nodes", scan4, n, R9, n_rot, s0, levels, 1); if (s != ICPMI_OK) return s; }
+    if (n_nodes < 0 || (n_nodes > 0 && (!nodes5 || !counts))) { h->last_error = "occupancy_score_nodes: bad arguments"; return ICPMI_ERR_INVALID_ARG; }
+    for (int64_t q = 0; q < n_nodes; ++q) {
+        const int32_t* f = nodes5 + 5 * q;
+        bool ok = f[0] >= 0 && f[0] < n_rot && f[1] >= 0 && f[1] < levels;
+        for (int j = 0; j < 3; ++j) ok = ok && f[2 + j] > -524288 && f[2 + j] < 524288;
+        if (!ok) { h->last_error = "occupancy_score_nodes: node " + std::to_string(q) + " is not (k in [0, n_rot), l in [0, levels), |A| < 2^19)"; return ICPMI_ERR_INVALID_ARG; }
+    }
+    if (n_nodes == 0) return ICPMI_OK;
+    const float* d_scan = nullptr; const float* none = nullptr;
+    { const icpmi_status ss = stage_in_scratch(h, scan4, n, nullptr, &d_scan, &none); if (ss != ICPMI_OK) return ss; }
+    return occ_score_nodes(h, (const float4*)d_scan, n, R9, n_rot, s0, levels, nodes5, n_nodes, counts);
+}
+
+icpmi_status icpmi_get_occupancy_level(icpmi_handle h, float s0, int32_t levels, int32_t level, int64_t cap, int32_t* ijk3, int64_t* n_keys)
+{
+    CHECK_H(h);
+    if (n_keys) *n_keys = 0;
+    if (h->cfg.force_2d || h->cfg.is_2d) { h->last_error = "get_occupancy_level: is not served in planar mode (force_2d / is_2d)"; return ICPMI_ERR_UNSUPPORTED; }
+    if (h->m <= 0) { h->last_error = "get_occupancy_level: no map"; return ICPMI_ERR_INVALID_ARG; }
+    if (!std::isfinite(s0) || !(s0 > 0.f) || levels < 1 || levels > ICPMI_MAX_OCC_LEVELS || level < 0 || level >= levels || cap < 0) {
+        h->last_error = "get_occupancy_level: bad arguments (a finite cell size > 0, levels in 1 .. 8, level in [0, levels))"; return ICPMI_ERR_INVALID_ARG;
+    }
+    return occ_get_level(h, s0, levels, level, cap, ijk3, n_keys);
+}
+
+icpmi_status icpmi_get_occupancy_info(icpmi_handle h, int32_t* levels, int64_t keys[8], int64_t bytes[8], float build_ms[8], int64_t* builds)
+{
+    CHECK_H(h);
+    const OccPyramid& p = h->occ;
+    const int L = p.ready ? p.levels : 0;
+    if (levels) *levels = L;
+    if (builds) *builds = (int64_t)p.builds;
+    for (int l = 0; l < ICPMI_MAX_OCC_LEVELS; ++l) {
+        const bool on = l < L;
+        if (keys) keys[l] = on ? p.lv[l].nk : 0;
+        if (bytes) bytes[l] = on ? (int64_t)(sizeof(unsigned long long) * ((size_t)p.lv[l].nk + (size_t)p.lv[l].mask + 1)) : 0;
+        if (build_ms) build_ms[l] = on ? p.lv[l].build_ms : 0.f;
+    }
+    return ICPMI_OK;
+}
+
 // test seam of scripts/voxel_bench.py: rebuilds the table and reports what its three stages took (sort, reduce, fill; milliseconds by HIP events)
 icpmi_status icpmi_debug_voxel_build_times(icpmi_handle h, float times_ms3[3])
 {

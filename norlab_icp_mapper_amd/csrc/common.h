@@ -801,6 +801,17 @@ struct VoxLevel {
     int64_t nv = 0; unsigned mask = 0; bool ready = false;
     uint64_t map_version = 0, epoch = 0, gen = 0; float built_size = 0.f;
 };
+// The occupancy pyramid of the global localisation search (occupancy.hip): per level l the keys of occB_l in ascending order
+// and an open-addressing table of key-only 8-byte slots (mask + 1 of them, the smallest power of two >= 2 x keys).  Built lazily for
+// (map_version, map_epoch, s0, levels) and kept until one of them changes.  cell_lo / cell_hi: the extent of occ0, the default window.
+#define ICPMI_MAX_OCC_LEVELS 8
+struct OccLevel { DevArr<unsigned long long> keys, tab; int64_t nk = 0; unsigned mask = 0; float build_ms = 0.f; };
+struct OccPyramid {
+    OccLevel lv[ICPMI_MAX_OCC_LEVELS];
+    int levels = 0; float s0 = 0.f; bool ready = false;
+    uint64_t map_version = 0, epoch = 0, builds = 0;
+    int cell_lo[3] = {0, 0, 0}, cell_hi[3] = {0, 0, 0};
+};
 // The device block of a scheduled handle (two or more levels), in dwords: 16 of level descriptors (per level: table address lo, hi, mask,
 // size bits -- voxel_pairs_sched_kernel takes them in one load, lane l dword l), then what voxel_advance_kernel keeps between iterations:
 // the iteration count at which the current level began, and per level the iterations run and the pair counts of its first and last
@@ -811,6 +822,26 @@ struct VoxLevel {
 #define ICPMI_VS_FIRST 21
 #define ICPMI_VS_LAST 25
 #define ICPMI_VS_WORDS 32
+
+// The 63-bit key of a cell, shared by the VoxelMatcher tables (voxel.hip) and the occupancy pyramid (occupancy.hip)
+constexpr unsigned long long VOX_EMPTY = ~0ull;          // (a key has 63 bits: never all ones)
+constexpr float VOX_RANGE = 1048576.f;                   // |index| < 2^20 on every axis
+constexpr int VOX_BIAS = 1 << 20;
+
+// The key of a centred point: per axis i = (int)floorf(x / size) in float32 (the division correctly rounded), biased by 2^20 into 21 bits;
+// x in the top field, so ascending keys are ascending (ix, iy, iz).  false: a coordinate is not finite or an index is out of range.
+__host__ __device__ __forceinline__ bool vox_key(float x, float y, float z, float size, unsigned long long* key)
+{
+    const float fx = floorf(x / size), fy = floorf(y / size), fz = floorf(z / size);
+    if (!(fabsf(fx) < VOX_RANGE && fabsf(fy) < VOX_RANGE && fabsf(fz) < VOX_RANGE)) return false; // (NaN and +-inf fail here too)
+    *key = ((unsigned long long)((int)fx + VOX_BIAS) << 42) | ((unsigned long long)((int)fy + VOX_BIAS) << 21) | (unsigned long long)((int)fz + VOX_BIAS);
+    return true;
+}
+// where a key's probe sequence starts (include/icpmi.h states it: tests build colliding key sets from it)
+__host__ __device__ __forceinline__ unsigned vox_hash(unsigned long long key, unsigned mask)
+{
+    return (unsigned)((key * 0x9E3779B97F4A7C15ull) >> 32) & mask;
+}
 
 #define ICPMI_SCRATCH_SLOTS 24
 struct icpmi_ctx {
@@ -978,6 +1009,7 @@ struct icpmi_ctx {
     DevArr<unsigned> d_vox_batch; uint64_t vox_batch_sig = 0;
     int32_t vox_batch_report[ICPMI_MAX_BATCH][1 + 3 * ICPMI_MAX_VOXEL_LEVELS] = {{0}};
     int vox_batch_members = 0;
+    OccPyramid occ;                   // icpmi_global_localize* and the occupancy calls (occupancy.hip); nothing else reads it
     // test seam (icpmi_debug_voxel_batch_calls): loops of loop_run_voxel_batch, members they carried, single registrations on the voxel path
     int64_t vox_batch_loops = 0, vox_batch_loop_members = 0, vox_single_regs = 0;
     DevArr<IcpState> d_state;         // ICPMI_MAX_BATCH states (a single registration uses the first)
@@ -1580,6 +1612,17 @@ icpmi_status voxel_lookup_times(icpmi_ctx* c, const float* q4_centred, int64_t n
 icpmi_status voxel_score_poses(icpmi_ctx* c, const float4* d_scan, int64_t n, const float* d_n3, const float* Tc, int n_poses, int level, float hb,
                                icpmi_voxel_score* out);
 void voxel_score_shape(int32_t* slice, int32_t* tile);
+// Global localisation (occupancy.hip).  occ_ensure: the pyramid of the resident map for (s0, levels), built unless current.
+// occ_get_level: the keys of occB_level as cells, ascending.  occ_score_nodes: bound(k, l, A) of n_nodes caller-checked nodes (5 ints each)
+// for the raw reading d_scan under the n_rot rotations R9 (host, 9 floats each, column-major).  occ_global_localize: the search over the
+// window [a_min, a_max] with `levels` levels; every argument is checked by the caller (api.hip), the result arrives zeroed.
+icpmi_status occ_ensure(icpmi_ctx* c, float s0, int levels);
+icpmi_status occ_get_level(icpmi_ctx* c, float s0, int levels, int level, int64_t cap, int32_t* ijk3, int64_t* n_keys);
+icpmi_status occ_score_nodes(icpmi_ctx* c, const float4* d_scan, int64_t n, const float* R9, int n_rot, float s0, int levels, const int32_t* nodes5,
+                             int64_t n_nodes, int64_t* counts);
+icpmi_status occ_global_localize(icpmi_ctx* c, const float4* d_scan, int64_t n, const float* R9, int n_rot, float s0, int levels, const int64_t a_min[3],
+                                 const int64_t a_max[3], int batch, int64_t need, int64_t max_nodes, icpmi_global_localize_result* res);
+void occ_shape(int32_t* slice, int32_t* tile, int32_t* launch_nodes);
 icpmi_status loop_centre_pad(icpmi_ctx* c, const float4* d_scan, int64_t n, const float* d_normals3, float4* d_pts, float4* d_nrm);
 // the reading's normals (host, 3 per point) into c->d_read_normals, padded as a registration's head pads them
 icpmi_status loop_upload_read_normals(icpmi_ctx* c, const float* normals3, int64_t n);

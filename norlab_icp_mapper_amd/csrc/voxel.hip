@@ -14,25 +14,7 @@
 
 namespace {
 
-constexpr unsigned long long VOX_EMPTY = ~0ull;          // (a key has 63 bits: never all ones)
-constexpr float VOX_RANGE = 1048576.f;                   // |index| < 2^20 on every axis
-constexpr int VOX_BIAS = 1 << 20;
-
-// The key of a centred point: per axis i = (int)floorf(x / size) in float32 (the division correctly rounded), biased by 2^20 into 21 bits;
-// x in the top field, so ascending keys are ascending (ix, iy, iz).  false: a coordinate is not finite or an index is out of range.
-__host__ __device__ __forceinline__ bool vox_key(float x, float y, float z, float size, unsigned long long* key)
-{
-    const float fx = floorf(x / size), fy = floorf(y / size), fz = floorf(z / size);
-    if (!(fabsf(fx) < VOX_RANGE && fabsf(fy) < VOX_RANGE && fabsf(fz) < VOX_RANGE)) return false; // (NaN and +-inf fail here too)
-    *key = ((unsigned long long)((int)fx + VOX_BIAS) << 42) | ((unsigned long long)((int)fy + VOX_BIAS) << 21) | (unsigned long long)((int)fz + VOX_BIAS);
-    return true;
-}
-// where a key's probe sequence starts (include/icpmi.h states it: tests build colliding key sets from it)
-__host__ __device__ __forceinline__ unsigned vox_hash(unsigned long long key, unsigned mask)
-{
-    return (unsigned)((key * 0x9E3779B97F4A7C15ull) >> 32) & mask;
-}
-
+// (the key of a centred point and where its probe sequence starts: common.h, vox_key and vox_hash -- occupancy.hip packs the same key)
 // A slot of the table is one 64-byte line, read as four 16-byte words that one probe requests together:
 //   [0] key lo, key hi, ordinal in ascending key order, count     [1] mu.x mu.y mu.z Nxx     [2] Nxy Nxz Nyy Nyz     [3] Nzz 0 0 0
 // The sorted records (what icpmi_get_voxel_map hands out) are words [1..3] with the count in [3].y.

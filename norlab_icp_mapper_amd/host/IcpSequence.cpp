@@ -851,6 +851,58 @@ VoxelPoseScores GpuICPSequence::voxelScores(const DataPoints& readingIn, const s
     return voxelScoresFiltered(filteredReading(readingIn), poses, level, beta);
 }
 
+// ---- global localisation (include/icpmi.h: icpmi_global_localize) -----------------
+std::vector<Rot9> yawRotations(int steps, double roll, double pitch)
+{
+    if (steps < 1) throw InvalidParameter("yawRotations: steps must be >= 1");
+    const double cr = std::cos(roll), sr = std::sin(roll), cp = std::cos(pitch), sp = std::sin(pitch);
+    const double Rx[3][3] = {{1.0, 0.0, 0.0}, {0.0, cr, -sr}, {0.0, sr, cr}};
+    const double Ry[3][3] = {{cp, 0.0, sp}, {0.0, 1.0, 0.0}, {-sp, 0.0, cp}};
+    double Ryx[3][3];
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) Ryx[r][c] = (Ry[r][0] * Rx[0][c] + Ry[r][1] * Rx[1][c]) + Ry[r][2] * Rx[2][c];
+    std::vector<Rot9> out((size_t)steps);
+    for (int i = 0; i < steps; ++i) {
+        const double a = 2.0 * M_PI * (double)i / (double)steps;
+        const double ca = std::cos(a), sa = std::sin(a);
+        const double Rz[3][3] = {{ca, -sa, 0.0}, {sa, ca, 0.0}, {0.0, 0.0, 1.0}};
+        for (int r = 0; r < 3; ++r)
+            for (int c = 0; c < 3; ++c) out[(size_t)i][(size_t)(3 * c + r)] = (float)((Rz[r][0] * Ryx[0][c] + Rz[r][1] * Ryx[1][c]) + Rz[r][2] * Ryx[2][c]);
+    }
+    return out;
+}
+
+icpmi_global_localize_result GpuICPSequence::globalLocalize(const DataPoints& readingIn, const std::vector<Rot9>& rotations,
+                                                            const GlobalLocalizeOptions& options) const
+{
+    DataPoints owned;
+    if (hasReadingFilters()) owned = filteredReading(readingIn);
+    const DataPoints& reading = hasReadingFilters() ? owned : readingIn;
+    icpmi_global_localize_options opt;
+    icpmi_global_localize_options_default(&opt);
+    opt.cell_size = options.cellSize; opt.levels = options.levels; opt.min_score_ratio = options.minScoreRatio;
+    opt.max_nodes = options.maxNodes; opt.batch = options.batch; opt.has_box = options.hasBox ? 1 : 0;
+    for (int j = 0; j < 3; ++j) { opt.box_lo[j] = options.boxLo[(size_t)j]; opt.box_hi[j] = options.boxHi[(size_t)j]; }
+    icpmi_global_localize_result res{};
+    check(h, icpmi_global_localize(h, reading.features.data(), (int64_t)reading.getNbPoints(), rotations.empty() ? nullptr : rotations[0].data(),
+                                   (int32_t)rotations.size(), &opt, &res));
+    return res;
+}
+
+GlobalRelocalization GpuICPSequence::relocalizeGlobal(const DataPoints& reading, const std::vector<Rot9>& rotations, const GlobalLocalizeOptions& options,
+                                                      const RelocalizeOptions& refine, const RelocalizeVoxelOptions& refineVoxel)
+{
+    GlobalRelocalization out;
+    out.search = globalLocalize(reading, rotations, options);
+    if (!out.search.found) throw ConvergenceError("relocalizeGlobal: no pose reaches minScoreRatio");
+    Mat4 start;
+    std::copy(out.search.T, out.search.T + 16, start.m.begin());
+    out.voxel = voxelSize > 0.f;
+    if (out.voxel) { out.refinedVoxel = relocalizeVoxel(reading, {start}, refineVoxel); out.pose = out.refinedVoxel.pose; }
+    else { out.refined = relocalize(reading, {start}, refine); out.pose = out.refined.pose; }
+    return out;
+}
+
 // ---- many readings, or many starts, in one loop on the voxel path (include/icpmi.h: icpmi_voxel_register_*) ----
 static const float* normalsOf(const DataPoints& cloud)
 {

@@ -100,6 +100,30 @@ struct VoxelRelocalization {
 // dropped, the rest come by likelihood / n descending (double), ties by the lower index.  Needs no GPU.
 std::vector<int> rankVoxelCandidates(const VoxelPoseScores& scores, size_t n, float minPairsRatio = 0.f);
 
+// ---- global localisation: a search without candidates (include/icpmi.h: icpmi_global_localize) ----
+using Rot9 = std::array<float, 9>;      // a rotation as the C call takes it: column-major 3 x 3
+struct GlobalLocalizeOptions {
+    float cellSize = 0.5f;              // s0: the finest cell, and the lattice's step
+    int levels = 0;                     // occupancy levels, 1 .. 8 (0: automatic)
+    float minScoreRatio = 0.f;          // a pose needs ceil(ratio * N) points in occupied cells
+    int64_t maxNodes = 0;               // stop behind that many scored nodes with the best so far (0: no cap)
+    int batch = 64;                     // nodes expanded per round
+    bool hasBox = false;                // false: the map's bounding box
+    std::array<double, 3> boxLo{{0, 0, 0}}, boxHi{{0, 0, 0}}; // the window in the map frame, metres
+};
+// Rz(2 pi i / steps) Ry(pitch) Rx(roll) for i = 0 .. steps - 1, formed in double -- every entry of a product summed left to right, Ry Rx
+// first -- and rounded to float.  Needs no GPU.
+std::vector<Rot9> yawRotations(int steps, double roll = 0.0, double pitch = 0.0);
+// What GpuICPSequence::relocalizeGlobal returns: the search's result, and the refinement's with the found pose as its one candidate --
+// `refined` on a KDTree chain, `refinedVoxel` on a VoxelMatcher chain (the other stays empty); pose is the one that holds
+struct GlobalRelocalization {
+    icpmi_global_localize_result search{};
+    bool voxel = false;
+    Relocalization refined;
+    VoxelRelocalization refinedVoxel;
+    Mat4 pose = Mat4::identity();
+};
+
 // What GpuICPSequence::registerSweep returns: the sensor's pose in the map at sweep begin and at sweep end, and the call's figures
 // (include/icpmi.h: icpmi_sweep_result; stats.pose7 holds the two poses in double, as icpmi_sweep_motion takes them)
 struct SweepRegistration {
@@ -178,6 +202,18 @@ public:
     // starts in one loop: registerVoxelMultiStart, chunks of 16), the refined poses scored at the finest level and ranked again.
     // ConvergenceError when nothing survives.
     VoxelRelocalization relocalizeVoxel(const DataPoints& reading, const std::vector<Mat4>& candidates, const RelocalizeVoxelOptions& options = RelocalizeVoxelOptions());
+
+    // Where is the sensor, with no candidate at all?  The pose [R_k | mu + cellSize a] under which the most points of `reading` fall into
+    // occupied cells of the map, over the lattice inside the box and the `rotations`, by branch and bound (icpmi_global_localize): exact,
+    // no normals, no matcher.  The chain's reading filters are applied once.  found = 0 when nothing reaches minScoreRatio; errors throw.
+    // Leaves stats() alone.
+    icpmi_global_localize_result globalLocalize(const DataPoints& reading, const std::vector<Rot9>& rotations,
+                                                const GlobalLocalizeOptions& options = GlobalLocalizeOptions()) const;
+    // ... then the existing refinement with the found pose as its one candidate: relocalize, on a VoxelMatcher chain relocalizeVoxel.
+    // ConvergenceError when the search finds nothing.
+    GlobalRelocalization relocalizeGlobal(const DataPoints& reading, const std::vector<Rot9>& rotations,
+                                          const GlobalLocalizeOptions& options = GlobalLocalizeOptions(), const RelocalizeOptions& refine = RelocalizeOptions(),
+                                          const RelocalizeVoxelOptions& refineVoxel = RelocalizeVoxelOptions());
 
     // Sweep registration (include/icpmi.h: icpmi_register_sweep; not libpointmatcher's): the skewed scan in the sensor frame with its point
     // times tRel (one per point, in units of opts.time_unit_s from the scan's stamp) registered as a motion -- the two poses estimated by

@@ -410,6 +410,21 @@ VoxelRelocalization Mapper::relocalizeVoxel(const DataPoints& inputInSensorFrame
     return found;
 }
 
+GlobalRelocalization Mapper::relocalizeGlobal(const DataPoints& inputInSensorFrame, const std::vector<Rot9>& rotations, const TimePoint& timeStamp,
+                                              const GlobalLocalizeOptions& options, const RelocalizeOptions& refine, const RelocalizeVoxelOptions& refineVoxel)
+{
+    DataPoints scan = inputInSensorFrame;
+    applyInputFilters(scan);
+    GlobalRelocalization found;
+    {
+        std::lock_guard<std::mutex> g(icpMapLock);
+        found = icp.relocalizeGlobal(scan, rotations, options, refine, refineVoxel);
+    }
+    { std::lock_guard<std::mutex> g(poseLock); pose = found.pose; }
+    { std::lock_guard<std::mutex> g(trajectoryLock); trajectory.addPose(found.pose, timeStamp); }
+    return found;
+}
+
 bool Mapper::mapUpdateIsDue(const TimePoint& now, const Mat4& poseNow, float overlap) const
 {
     if (!isMapping.load()) return false;

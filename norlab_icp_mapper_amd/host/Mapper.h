@@ -103,6 +103,11 @@ public:
     // ... on a VoxelMatcher chain, by GpuICPSequence::relocalizeVoxel: the input filters, the current map, the pose set, no map update
     VoxelRelocalization relocalizeVoxel(const DataPoints& inputInSensorFrame, const std::vector<Mat4>& candidates, const TimePoint& timeStamp,
                                         const RelocalizeVoxelOptions& options = RelocalizeVoxelOptions());
+    // ... with no candidate at all, by GpuICPSequence::relocalizeGlobal (the search over `rotations` and the lattice, then the refinement the
+    // chain has): the input filters, the current map, the pose set, no map update
+    GlobalRelocalization relocalizeGlobal(const DataPoints& inputInSensorFrame, const std::vector<Rot9>& rotations, const TimePoint& timeStamp,
+                                          const GlobalLocalizeOptions& options = GlobalLocalizeOptions(), const RelocalizeOptions& refine = RelocalizeOptions(),
+                                          const RelocalizeVoxelOptions& refineVoxel = RelocalizeVoxelOptions());
     DataPoints getMap() { return map.getGlobalPointCloud(); }
     long residentMapUpdates() const { return map.residentUpdateCount(); }
     size_t localMapSize() { return map.localSize(); }

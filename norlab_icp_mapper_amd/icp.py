@@ -555,6 +555,43 @@ def candidate_grid(pose, half_x, half_y, half_yaw, steps_x=1, steps_y=1, steps_y
     return np.stack(out).astype(np.float32)
 
 
+def yaw_rotations(steps, roll=0.0, pitch=0.0):
+    """The rotations of a search over the heading (globalLocalize): Rz(2 pi i / steps) Ry(pitch) Rx(roll) for i = 0 .. steps - 1, formed in
+    double -- every entry of a product summed left to right -- and rounded to float32.  Returns (steps, 3, 3) float32."""
+    if int(steps) < 1:
+        raise InvalidParameter("yaw_rotations: steps must be >= 1")
+    cr, sr, cp, sp = math.cos(roll), math.sin(roll), math.cos(pitch), math.sin(pitch)
+    Rx = [[1.0, 0.0, 0.0], [0.0, cr, -sr], [0.0, sr, cr]]
+    Ry = [[cp, 0.0, sp], [0.0, 1.0, 0.0], [-sp, 0.0, cp]]
+    mul = lambda A, B: [[(A[r][0] * B[0][c] + A[r][1] * B[1][c]) + A[r][2] * B[2][c] for c in range(3)] for r in range(3)]
+    Ryx = mul(Ry, Rx)
+    out = np.empty((int(steps), 3, 3), dtype=np.float32)
+    for i in range(int(steps)):
+        a = 2.0 * math.pi * float(i) / float(int(steps))
+        ca, sa = math.cos(a), math.sin(a)
+        out[i] = np.array(mul([[ca, -sa, 0.0], [sa, ca, 0.0], [0.0, 0.0, 1.0]], Ryx), dtype=np.float64).astype(np.float32)
+    return out
+
+
+class GlobalLocalization:
+    """What ICPSequence.globalLocalize returns (icpmi_global_localize_result): found, proven, rotation (index into the list), cell (a),
+    score, points, pose (4x4 float32: [R_k | mu + s0 a]), levels, nodes_scored, leaves_scored, launches."""
+    __slots__ = ("found", "proven", "rotation", "cell", "score", "points", "pose", "levels", "nodes_scored", "leaves_scored", "launches", "_raw")
+
+    def __init__(self, c):
+        self.found, self.proven, self.rotation, self.cell = bool(c.found), bool(c.proven), int(c.rotation), tuple(int(v) for v in c.cell)
+        self.score, self.points, self.pose, self.levels = int(c.score), int(c.points), _T_from_c(c.T[:]), int(c.levels)
+        self.nodes_scored, self.leaves_scored, self.launches = int(c.nodes_scored), int(c.leaves_scored), int(c.launches)
+        self._raw = bytes(c)
+
+    def bits(self):
+        return self._raw
+
+    def __repr__(self):
+        return (f"GlobalLocalization(found={self.found}, proven={self.proven}, rotation={self.rotation}, cell={self.cell}, score={self.score}, "
+                f"points={self.points}, levels={self.levels}, nodes_scored={self.nodes_scored}, launches={self.launches})")
+
+
 def compose_pose(A, B):
     """A B for two 4x4 float32 matrices the way the host shell's Mat4 multiplies: every entry summed over k = 0 .. 3 in float32, one
     multiply and one add per term -- the same bits on both sides of the C ABI (host/Makefile compiles the shell with -ffp-contract=off
@@ -569,11 +606,12 @@ def compose_pose(A, B):
 
 class Relocalization:
     """What ICPSequence.relocalize returns: the winner's corrected pose (4x4), its Residual, its index among the candidates and the
-    PoseScores of all candidates."""
-    __slots__ = ("pose", "residual", "index", "scores")
+    PoseScores of all candidates.  `search`: the GlobalLocalization that supplied the candidate (relocalizeGlobal), else None."""
+    __slots__ = ("pose", "residual", "index", "scores", "search")
 
     def __init__(self, pose, residual, index, scores):
         self.pose, self.residual, self.index, self.scores = pose, residual, int(index), scores
+        self.search = None
 
 
 class _ErrorMinimizerView:
@@ -1146,6 +1184,88 @@ class ICPSequence:
             raise ConvergenceError("relocalizeVoxel: no refined candidate survived the scoring")
         w = final[0]
         return Relocalization(refined[w].copy(), again.scores[w], best[w], scores)
+
+    # ---- a search without candidates: branch and bound over occupancy levels (icpmi_global_localize*) ----
+    @staticmethod
+    def _rotations_to_c(rotations):
+        """(K, 3, 3) rotation matrices -> K column-major blocks of 9 floats"""
+        R = np.asarray(rotations, dtype=np.float32).reshape(-1, 3, 3)
+        return np.ascontiguousarray(np.transpose(R, (0, 2, 1))).reshape(-1)
+
+    def _global_localize_options(self, cell_size, box, levels, min_score_ratio, max_nodes, batch):
+        o = _capi.GlobalLocalizeOptions()
+        self._lib.icpmi_global_localize_options_default(C.byref(o))
+        o.cell_size, o.levels, o.min_score_ratio, o.max_nodes = float(cell_size), int(levels), float(min_score_ratio), int(max_nodes)
+        if batch is not None:
+            o.batch = int(batch)
+        if box is not None:
+            lo, hi = (np.asarray(b, dtype=np.float64).reshape(3) for b in box)
+            o.has_box = 1
+            o.box_lo[:], o.box_hi[:] = lo.tolist(), hi.tolist()
+        return o
+
+    def globalLocalize(self, reading, rotations, cell_size, box=None, levels=0, min_score_ratio=0.0, max_nodes=0, batch=None):
+        """icpmi_global_localize: where is the sensor, with no candidate at all?  Exhaustive over the translations mu + cell_size * a of a
+        lattice inside `box` ((lo, hi) in the map frame, metres; None: the map's bounding box) and the `rotations` ((K, 3, 3), K <= 4096;
+        see yaw_rotations), by branch and bound over `levels` occupancy levels (0: automatic): the pose under which the most reading points
+        fall into occupied cells of the map, exactly.  No normals, no matcher.  Returns a GlobalLocalization (found = False when nothing
+        reaches min_score_ratio * N; proven = False when max_nodes stopped the search)."""
+        scan = _f32c(reading, 4)
+        R9 = self._rotations_to_c(rotations)
+        o = self._global_localize_options(cell_size, box, levels, min_score_ratio, max_nodes, batch)
+        res = _capi.GlobalLocalizeResult()
+        self._check(self._lib.icpmi_global_localize(self._h, scan.ctypes.data, scan.shape[0], R9.ctypes.data, R9.shape[0] // 9, C.byref(o), C.byref(res)))
+        return GlobalLocalization(res)
+
+    def globalLocalizeDev(self, d_scan_ptr, n, rotations, cell_size, box=None, levels=0, min_score_ratio=0.0, max_nodes=0, batch=None):
+        """icpmi_global_localize_dev: globalLocalize() for a reading already in HBM."""
+        R9 = self._rotations_to_c(rotations)
+        o = self._global_localize_options(cell_size, box, levels, min_score_ratio, max_nodes, batch)
+        res = _capi.GlobalLocalizeResult()
+        self._check(self._lib.icpmi_global_localize_dev(self._h, d_scan_ptr, int(n), R9.ctypes.data, R9.shape[0] // 9, C.byref(o), C.byref(res)))
+        return GlobalLocalization(res)
+
+    def occupancyScoreNodes(self, reading, rotations, cell_size, levels, nodes):
+        """icpmi_occupancy_score_nodes (test seam and inspection): bound(k, l, A) of the (N, 5) `nodes` (k, l, A.x, A.y, A.z): (N,) int64"""
+        scan = _f32c(reading, 4)
+        R9 = self._rotations_to_c(rotations)
+        nd = np.ascontiguousarray(np.asarray(nodes, dtype=np.int32).reshape(-1, 5))
+        out = np.zeros(max(nd.shape[0], 1), dtype=np.int64)
+        self._check(self._lib.icpmi_occupancy_score_nodes(self._h, scan.ctypes.data, scan.shape[0], R9.ctypes.data, R9.shape[0] // 9, float(cell_size),
+                                                          int(levels), nd.ctypes.data, nd.shape[0], out.ctypes.data))
+        return out[:nd.shape[0]]
+
+    def occupancyLevel(self, cell_size, levels, level):
+        """icpmi_get_occupancy_level: the cells of occB_level in ascending key order, (K, 3) int32"""
+        nk = C.c_int64(0)
+        self._check(self._lib.icpmi_get_occupancy_level(self._h, float(cell_size), int(levels), int(level), 0, None, C.byref(nk)))  # (a size query)
+        ijk = np.zeros((max(nk.value, 1), 3), dtype=np.int32)
+        self._check(self._lib.icpmi_get_occupancy_level(self._h, float(cell_size), int(levels), int(level), nk.value, ijk.ctypes.data, C.byref(nk)))
+        return ijk[:nk.value]
+
+    def occupancyInfo(self):
+        """icpmi_get_occupancy_info: dict(levels, keys, bytes, build_ms (per level), builds) of the pyramid the handle holds"""
+        lv, builds = C.c_int32(0), C.c_int64(0)
+        keys, nbytes, ms = (C.c_int64 * 8)(), (C.c_int64 * 8)(), (C.c_float * 8)()
+        self._check(self._lib.icpmi_get_occupancy_info(self._h, C.byref(lv), keys, nbytes, ms, C.byref(builds)))
+        L = lv.value
+        return dict(levels=L, keys=list(keys[:L]), bytes=list(nbytes[:L]), build_ms=list(ms[:L]), builds=builds.value)
+
+    def relocalizeGlobal(self, reading, rotations, cell_size, normals=None, box=None, levels=0, min_score_ratio=0.0, max_nodes=0, **refine):
+        """The search, then the existing refinement with the found pose as its one candidate: relocalize(reading, [pose], **refine), on a
+        VoxelMatcher handle relocalizeVoxel(reading, normals, [pose], **refine).  Returns that call's Relocalization with the search's
+        GlobalLocalization as `.search`; ConvergenceError when the search finds nothing."""
+        found = self.globalLocalize(reading, rotations, cell_size, box=box, levels=levels, min_score_ratio=min_score_ratio, max_nodes=max_nodes)
+        if not found.found:
+            raise ConvergenceError("relocalizeGlobal: no pose reaches min_score_ratio")
+        if self.getVoxelMatcher() > 0:
+            if normals is None:
+                raise InvalidField("relocalizeGlobal: a VoxelMatcher handle refines with the reading's normals")
+            out = self.relocalizeVoxel(reading, normals, [found.pose], **refine)
+        else:
+            out = self.relocalize(reading, [found.pose], **refine)
+        out.search = found
+        return out
 
     def setReadingMaxDist(self, radii):
         """icpmi_set_reading_max_dist: the search radius of every point of the NEXT reading (KDTreeVarDistMatcher's `maxDistField` row; one shot)."""
