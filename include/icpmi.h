@@ -1141,8 +1141,17 @@ const char*  icpmi_build_info(void);
  * block goes back to the runtime now; live handles stay valid. */
 icpmi_status icpmi_trim_cache(void);
 /* Diagnostics of the last registration (engine internals, not part of the reference surface).  Slots 12 / 13 (r5): iterations of a k > 1 loop whose
-   quantile selection took its level 0 from the NN kernel's window / from the full histogram behind a window that missed. */
+   quantile selection took its level 0 from the NN kernel's window / from the full histogram behind a window that missed.
+   Slot 23: normals an append-only update recomputed whose copy in the registration index was not found, hence not rewritten, since the handle
+   was created -- 0 on a sound handle (read back from the device: the call waits for the handle's stream). */
 icpmi_status icpmi_debug_counters(icpmi_handle h, uint64_t out[24]);
+/* Test seam: the normals the registration index holds, by ORIGINAL index (the order of icpmi_get_map).  sorted3 (m x 3): the sorted copy the
+ * k = 1 pair sums, the covariance and the voxel tables read; pn3 (m x 3, may be NULL): the copy interleaved with the points that the k > 1
+ * pair sums read, written only where the handle keeps one -- *has_pn (may be NULL) says whether it does.  Both are gathered on the host
+ * through the original index each level-0 position carries.  m must be the indexed map's size.  Reads only: no launch, the handle and its
+ * cached loop graphs stay as they are.  ICPMI_ERR_UNSUPPORTED when the index holds no normals; ICPMI_ERR_HIP when the positions' original
+ * indices are not a permutation of 0 .. m - 1 or the two copies disagree on them.  No production path calls it. */
+icpmi_status icpmi_debug_index_normals(icpmi_handle h, int64_t m, float* sorted3, float* pn3, int32_t* has_pn);
 /* Test seam: the matches of the last COUNTED iteration of the last single registration (icpmi_register*) on this handle, in the caller's point
  * order: row i holds the k matches of reading point i as ORIGINAL map indices, ascending by (d2, index), unfilled slots -1 / +inf; d2 as the
  * matcher computed it, against the centred map.  T_used (column-major) is the centred-frame pose that iteration's NN launch moved the centred

@@ -326,6 +326,7 @@ SYMBOLS = [
     ("icpmi_debug_last_matches", C.c_int, [_P, C.c_int64, C.c_int32, _P, _P, _F]),
     ("icpmi_debug_self_knn", C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, _P, C.POINTER(C.c_uint64)]),
     ("icpmi_debug_resident_kth_d2", C.c_int, [_P, C.c_int64, _P, C.POINTER(C.c_int32)]),
+    ("icpmi_debug_index_normals", C.c_int, [_P, C.c_int64, _P, _P, C.POINTER(C.c_int32)]),
     ("icpmi_debug_merge_blocks", C.c_int, [_P, _P, _P, C.c_int32, C.c_int64, C.c_float, C.c_int32, _P, C.c_int64, C.POINTER(C.c_int64), _P,
                                            C.POINTER(C.c_int32)]),
     ("icpmi_debug_keep_sums", C.c_int, [_P, C.c_int32]),

@@ -300,7 +300,8 @@ icpmi_status icpmi_get_map_mean(icpmi_handle h, float mean3[3])
 
 icpmi_status icpmi_debug_counters(icpmi_handle h, uint64_t out[24])
 {
-    if (!h || !out) return ICPMI_ERR_INVALID_ARG;
+    CHECK_H(h); // (slot 23 is read back from the device)
+    if (!out) return ICPMI_ERR_INVALID_ARG;
     for (int i = 0; i < 24; ++i) out[i] = h->h_state->dbg[i];
     // [18] / [19]: index builds served by the incremental insert / from scratch (low word: this handle's registration index; high
     // word: its private raw-frame index, ops.hip: raw_index)
@@ -316,8 +317,19 @@ icpmi_status icpmi_debug_counters(icpmi_handle h, uint64_t out[24])
     out[20] = (uint64_t)h->normals_incremental;
     out[21] = (uint64_t)h->normals_full;
     out[22] = (uint64_t)h->normals_last_searched;
-#endif
+    // changed normals whose copy in the registration index map_patch_normals did not find, since the handle was created: 0, or the index
+    // holds stale normals (map_build.hip: patch_normals_kernel; one word read back from the device)
+    return map_patch_unplaced(h, &out[23]);
+#else
     return ICPMI_OK;
+#endif
+}
+
+icpmi_status icpmi_debug_index_normals(icpmi_handle h, int64_t m, float* sorted3, float* pn3, int32_t* has_pn)
+{
+    CHECK_H(h);
+    if (m < 1 || !sorted3) { h->last_error = "debug_index_normals: bad arguments"; return ICPMI_ERR_INVALID_ARG; }
+    return map_debug_index_normals(h, m, sorted3, pn3, has_pn);
 }
 
 icpmi_status icpmi_debug_last_matches(icpmi_handle h, int64_t n, int32_t k, int32_t* ids, float* d2, float T_used[16])

@@ -1056,6 +1056,7 @@ struct icpmi_ctx {
     // dk_epoch == raw_epoch (nobody rewrote the resident copy) and the filter's knn is dk_knn.
     DevArr<float> d_raw_dk; int64_t dk_m = 0; int dk_knn = 0; uint64_t dk_epoch = ~0ull;
     long normals_incremental = 0, normals_full = 0; int64_t normals_last_searched = 0;   // diagnostics (icpmi_debug_counters 20 / 21 / 22)
+    DevArr<unsigned> d_patch_unplaced; // one word: changed normals whose sorted copy patch_normals_kernel did not find, since the handle was created (icpmi_debug_counters 23)
     bool merged_binned = false;       // the merged set of the last epoch is in the log already
     int cell_bits_hint = 0;           // key bits the previous epoch's cell count needed (the sort is enqueued before the count is known)
     float cell_auto_size = 0.f;       // > 0 (icpmi_cell_log_configure): every epoch enqueues the binning of its merged set itself, behind the merge
@@ -1514,6 +1515,8 @@ struct SortHead {
 // keep_prefix: the first keep_prefix points of d_pts are the cloud of the previous build, unchanged and in the same order (an append)
 icpmi_status map_build(icpmi_ctx* c, const float4* d_pts, int64_t m, const float* d_normals3, int64_t keep_prefix = 0);
 icpmi_status map_patch_normals(icpmi_ctx* c, const unsigned* d_list, int64_t n_list, const float4* d_raw, const float* d_normals3);
+icpmi_status map_patch_unplaced(icpmi_ctx* c, uint64_t* out); // the word behind icpmi_debug_counters 23 (0 while no patch has run)
+icpmi_status map_debug_index_normals(icpmi_ctx* c, int64_t m, float* sorted3, float* pn3, int32_t* has_pn); // icpmi_debug_index_normals
 icpmi_status upload_level_table(icpmi_ctx* c); // c->levels -> c->d_lvl_tab (the table the NN kernels copy to LDS)
 icpmi_status device_exclusive_scan(icpmi_ctx* c, unsigned* data, int n, unsigned total);
 icpmi_status device_exclusive_scan_io(icpmi_ctx* c, const unsigned* in, unsigned* out, int n, unsigned total); // in == out allowed

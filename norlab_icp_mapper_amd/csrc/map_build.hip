@@ -1024,38 +1024,94 @@ static icpmi_status map_insert(icpmi_ctx* c, const float4* d_pts, int64_t m0, in
 }
 
 // r6: the normals of a FEW resident points changed (ops.hip: surface_normals_dev after an append) -- their sorted copies are found through the
-// point's level-0 cell (the key of key_kernel from the raw coordinates and the index's mean) and rewritten, instead of gathering the whole field again
+// point's level-0 cell and rewritten, instead of gathering the whole field again.
+// The cell is RECOMPUTED here (key_kernel's arithmetic on the raw coordinates, the index's current mean and grid), while the index holds the
+// key the point got under the centroid of its own build or insert (ins_move0_kernel carries it over unchanged): for a coordinate within a
+// few ulps of a cell wall the two differ, by one cell per axis at the most (every rounding of cell_of is far below a cell; clamped overhang
+// points clamp alike under any centroid -- tests/index_key_cases.py restates both, tests/test_gpu_index_normals.py builds such points).  So
+// a point missing from the recomputed cell is looked for in the 26 around it: i walks the 3 x 3 x 3 block starting at its centre.
 __global__ __launch_bounds__(256) void patch_normals_kernel(const unsigned* __restrict__ list, int64_t n_list, const float4* __restrict__ raw,
                                                             float mx, float my, float mz, GridParams g, const unsigned* __restrict__ cs,
                                                             const float4* __restrict__ pts0, const float* __restrict__ normals3,
-                                                            float4* __restrict__ nrm, float4* __restrict__ pn)
+                                                            float4* __restrict__ nrm, float4* __restrict__ pn, unsigned* __restrict__ unplaced)
 {
     const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (t >= n_list) return;
     const unsigned orig = list[t];
     const float4 p = raw[orig];
     const int cx = cell_of(p.x - mx, g.ox, g.inv_cell, g.nx), cy = cell_of(p.y - my, g.oy, g.inv_cell, g.ny), cz = cell_of(p.z - mz, g.oz, g.inv_cell, g.nz);
-    const unsigned key = (unsigned)((cz * g.ny + cy) * g.nx + cx);
-    const unsigned e = cs[key + 1];
-    for (unsigned np = cs[key]; np < e; ++np)
-        if (__float_as_uint(pts0[np].w) == orig) {
-            const float4 nn = make_float4(normals3[3 * (size_t)orig], normals3[3 * (size_t)orig + 1], normals3[3 * (size_t)orig + 2], 0.f);
-            nrm[np] = nn;
-            if (pn) pn[2 * (size_t)np + 1] = nn;
-            return;
-        }
-    // (not reached: the key is the build's own -- tests/test_gpu_incremental_normals.py registers against the patched index and against a fresh one)
+    for (int i = 0; i < 27; ++i) {
+        const int j = (i + 13) % 27; // (13 = the block's centre: the recomputed cell first -- all but a few points per update end there)
+        const int x = cx + j % 3 - 1, y = cy + (j / 3) % 3 - 1, z = cz + j / 9 - 1;
+        if (x < 0 || x >= g.nx || y < 0 || y >= g.ny || z < 0 || z >= g.nz) continue;
+        const unsigned key = (unsigned)((z * g.ny + y) * g.nx + x);
+        const unsigned e = cs[key + 1];
+        for (unsigned np = cs[key]; np < e; ++np)
+            if (__float_as_uint(pts0[np].w) == orig) {
+                const float4 nn = make_float4(normals3[3 * (size_t)orig], normals3[3 * (size_t)orig + 1], normals3[3 * (size_t)orig + 2], 0.f);
+                nrm[np] = nn;
+                if (pn) pn[2 * (size_t)np + 1] = nn;
+                return;
+            }
+    }
+    atomicAdd(unplaced, 1u); // (in none of the 27 cells: the index would keep a stale normal -- counted, icpmi_debug_counters 23, and held at 0 by the tests)
 }
 
 icpmi_status map_patch_normals(icpmi_ctx* c, const unsigned* d_list, int64_t n_list, const float4* d_raw, const float* d_normals3)
 {
     if (n_list <= 0 || !c->d_normals_sorted || c->m <= 0) return ICPMI_OK;
     for (VoxLevel& lv : c->vox) lv.ready = false; // (the voxel tables' second moments are sums over these normals: voxel.hip rebuilds them at their next use)
+    if (!c->d_patch_unplaced) {
+        HIP_TRY(c, c->d_patch_unplaced.alloc(1));
+        HIP_TRY(c, hipMemsetAsync(c->d_patch_unplaced, 0, sizeof(unsigned), c->stream));
+    }
     const bool with_pn = c->d_map_pn != nullptr && !c->single_level && c->keep_raw;
     hipLaunchKernelGGL(patch_normals_kernel, dim3((int)((n_list + 255) / 256)), dim3(256), 0, c->stream, d_list, n_list, d_raw, c->mean[0], c->mean[1], c->mean[2],
                        c->levels.g[0], (const unsigned*)c->d_cell_start, (const float4*)c->d_map_sorted, d_normals3, c->d_normals_sorted,
-                       with_pn ? c->d_map_pn : (float4*)nullptr);
+                       with_pn ? c->d_map_pn : (float4*)nullptr, c->d_patch_unplaced.get());
     HIP_TRY(c, hipGetLastError());
+    return ICPMI_OK;
+}
+
+icpmi_status map_patch_unplaced(icpmi_ctx* c, uint64_t* out)
+{
+    unsigned w = 0;
+    if (c->d_patch_unplaced && read_back(c, &w, c->d_patch_unplaced, sizeof w) != ICPMI_OK) return ICPMI_ERR_HIP;
+    *out = w;
+    return ICPMI_OK;
+}
+
+// Test seam (icpmi_debug_index_normals): the normals the registration index holds, by ORIGINAL index -- the sorted copy (d_normals_sorted) and
+// the interleaved twin (d_map_pn), each gathered through the .w of the level-0 position it sits at.  Copies and a host loop: no launch, nothing written.
+icpmi_status map_debug_index_normals(icpmi_ctx* c, int64_t m, float* sorted3, float* pn3, int32_t* has_pn)
+{
+    if (c->m <= 0 || !c->has_normals || !c->d_normals_sorted) { c->last_error = "debug_index_normals: the registration index holds no normals"; return ICPMI_ERR_UNSUPPORTED; }
+    if (m != c->m) { c->last_error = "debug_index_normals: m differs from the indexed map's size"; return ICPMI_ERR_INVALID_ARG; }
+    const bool with_pn = c->d_map_pn != nullptr && !c->single_level && c->keep_raw;
+    if (has_pn) *has_pn = with_pn ? 1 : 0;
+    std::vector<float4> pts((size_t)m), nrm((size_t)m), pn(with_pn && pn3 ? 2 * (size_t)m : 0);
+    HIP_TRY(c, hipMemcpyAsync(pts.data(), c->d_map_sorted, (size_t)m * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(nrm.data(), c->d_normals_sorted, (size_t)m * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+    if (!pn.empty()) HIP_TRY(c, hipMemcpyAsync(pn.data(), c->d_map_pn, 2 * (size_t)m * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    std::vector<uint8_t> seen((size_t)m, 0);
+    for (int64_t s = 0; s < m; ++s) {
+        unsigned o;
+        memcpy(&o, &pts[(size_t)s].w, sizeof o);
+        if (o >= (uint64_t)m || seen[o]) { c->last_error = "debug_index_normals: the sorted points' original indices are not a permutation"; return ICPMI_ERR_HIP; }
+        seen[o] = 1;
+        if (!pn.empty()) {
+            unsigned o2;
+            memcpy(&o2, &pn[2 * (size_t)s].w, sizeof o2);
+            if (o2 != o) { c->last_error = "debug_index_normals: the interleaved copy is in another order than the sorted points"; return ICPMI_ERR_HIP; }
+        }
+        const float4 a = nrm[(size_t)s];
+        sorted3[3 * (size_t)o] = a.x; sorted3[3 * (size_t)o + 1] = a.y; sorted3[3 * (size_t)o + 2] = a.z;
+        if (!pn.empty()) {
+            const float4 b = pn[2 * (size_t)s + 1];
+            pn3[3 * (size_t)o] = b.x; pn3[3 * (size_t)o + 1] = b.y; pn3[3 * (size_t)o + 2] = b.z;
+        }
+    }
     return ICPMI_OK;
 }
 

@@ -2055,6 +2055,17 @@ class ICPSequence:
         self._check(self._lib.icpmi_debug_resident_kth_d2(self._h, m.value, out.ctypes.data, C.byref(knn)))
         return out[:m.value], int(knn.value)
 
+    def debugIndexNormals(self):
+        """icpmi_debug_index_normals: (sorted (m, 3) float32, pn (m, 3) float32 or None) -- the normals the registration index holds, rows by
+        original index as getMap's: the sorted copy, and the copy interleaved with the points where the handle keeps one."""
+        m = C.c_int64(0)
+        self._check(self._lib.icpmi_get_map(self._h, None, None, 0, C.byref(m)))
+        srt = np.full((max(m.value, 1), 3), np.nan, dtype=np.float32)
+        pn = np.full((max(m.value, 1), 3), np.nan, dtype=np.float32)
+        has = C.c_int32(0)
+        self._check(self._lib.icpmi_debug_index_normals(self._h, m.value, srt.ctypes.data, pn.ctypes.data, C.byref(has)))
+        return srt[:m.value], (pn[:m.value] if has.value else None)
+
     def keepSums(self, on=1):
         """icpmi_debug_keep_sums: from now on (on) / no longer (off) keep the pair sums of this handle's single registrations for lastSums();
         off by default.  Drops the cached loop graphs."""
