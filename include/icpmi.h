@@ -1140,7 +1140,9 @@ const char*  icpmi_build_info(void);
  * finds its ~300 arrays again.  A host that shares the GPU with another allocator calls this when it is done with a mapper: every cached
  * block goes back to the runtime now; live handles stay valid. */
 icpmi_status icpmi_trim_cache(void);
-/* Diagnostics of the last registration (engine internals, not part of the reference surface).  Slots 12 / 13 (r5): iterations of a k > 1 loop whose
+/* Diagnostics of the last registration (engine internals, not part of the reference surface).  Slots 10 / 11: k = 1 loop of a single
+   reading -- queries the matcher's helper workgroups ran in place of their home workgroup, summed over the launches / far-seeded queries that
+   found their launch's defer list full and stayed at home (both 0 under ICPMI_NN_DEFER=0, in a batch and for k > 1).  Slots 12 / 13 (r5): iterations of a k > 1 loop whose
    quantile selection took its level 0 from the NN kernel's window / from the full histogram behind a window that missed.
    Slot 23: normals an append-only update recomputed whose copy in the registration index was not found, hence not rewritten, since the handle
    was created -- 0 on a sound handle (read back from the device: the call waits for the handle's stream). */

@@ -172,6 +172,16 @@ icpmi_status create_handle(const icpmi_config* cfg, icpmi_handle* out)
     if (!c) { g_create_error = "icpmi_create: out of host memory"; return ICPMI_ERR_HIP; }
     store_config(c, cfg);
     c->device = cfg->device;
+    { // the k = 1 matcher's helper workgroups (nn.hip: nn1_wg_kernel), as the environment stands now: ICPMI_NN_DEFER=0 keeps every query at
+      // home, ICPMI_NN_DEFER_WGS = how many helpers a launch gets (rounded up to a multiple of 8; eight list entries each)
+        const char* e = getenv("ICPMI_NN_DEFER");
+        c->nn_defer = !(e && *e && atoi(e) == 0);
+        const char* w = getenv("ICPMI_NN_DEFER_WGS");
+        int wgs = (w && *w) ? atoi(w) : ICPMI_NN_DEFER_WGS_DEFAULT;
+        wgs = (wgs + 7) / 8 * 8;
+        if (wgs <= 0) c->nn_defer = false;
+        c->nn_defer_wgs = wgs < 8 ? 8 : (wgs > ICPMI_NN_DEFER_WGS_MAX ? ICPMI_NN_DEFER_WGS_MAX : wgs);
+    }
 #define CR(expr)                                                                                      \
     do {                                                                                              \
         hipError_t _e = (expr);                                                                       \
@@ -307,6 +317,9 @@ icpmi_status icpmi_debug_counters(icpmi_handle h, uint64_t out[24])
     // word: its private raw-frame index, ops.hip: raw_index)
     // (a -DICPMI_NN_TIMING build keeps all 24 slots for the NN kernels' phase clocks -- ADVICE r4)
 #ifndef ICPMI_NN_TIMING
+    // [10] / [11]: k = 1 matcher, last registration: queries its helper workgroups ran / far-seeded queries that found their defer list full
+    out[10] = (uint64_t)h->h_state->defer_served;
+    out[11] = (uint64_t)h->h_state->defer_overflow;
     out[14] = (uint64_t)h->merge_fast_epochs; // map-growth epochs served with ONE collective / with the count + ready + points exchanges (ops.hip)
     out[15] = (uint64_t)h->merge_slow_epochs;
     out[16] = (uint64_t)h->oct_respeculated; // octree filter calls whose speculated depth was too shallow (sorted twice; octree.hip)

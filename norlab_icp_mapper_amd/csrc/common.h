@@ -486,6 +486,8 @@ struct alignas(128) LoopHdr {
 static_assert(sizeof(LoopHdr) == 256 && alignof(LoopHdr) == 128, "the loop header is two 128-byte lines: one dword per lane of a wave");
 #define ICPMI_HDR_W(field) ((int)(offsetof(LoopHdr, field) / 4))   // dword index of a header field = the lane that holds it after hdr_load
 
+#define ICPMI_NN_DEFER_WGS_DEFAULT 160 // helper workgroups of a k = 1 loop launch (a multiple of 8; with the 1 568 home workgroups of 100 k queries all 1 792 resident slots hold up to 224)
+#define ICPMI_NN_DEFER_WGS_MAX 224
 #define ICPMI_TL_LAUNCHES 24   // -DICPMI_NN_TIMING: NN launches of a registration whose workgroup timeline is kept (nn.hip)
 struct IcpState : LoopHdr {
     int   stop_reason;
@@ -517,6 +519,12 @@ struct IcpState : LoopHdr {
     // is NOT in profile mode, i.e. bench.py's roofline duration taken from the timed graph replay itself
     unsigned long long t_nn_sum;
     unsigned nn_count, pad_nn;
+    // k = 1 matcher, deferral of far-seeded queries (nn.hip: nn1_wg_kernel): the NN launch of iteration i serves list i % 3, appends to list
+    // (i + 1) % 3 and zeroes the count of list (i + 2) % 3, which nobody touches in that launch.  A count may exceed the lists' capacity
+    // (readers clamp it).  defer_served / defer_overflow: queries the helper workgroups ran / heavy queries that found their list full,
+    // summed over the registration (icpmi_debug_counters 10 / 11).  Behind everything else: no other field moves.
+    unsigned defer_count[3];
+    unsigned defer_served, defer_overflow, pad_defer;
 #ifdef ICPMI_NN_TIMING
     // timing builds only (scripts/nn_wg_timeline.py): the open and the close stamp of every NN launch of the registration, by launch number
     unsigned long long tl_open[ICPMI_TL_LAUNCHES], tl_close[ICPMI_TL_LAUNCHES];
@@ -967,6 +975,10 @@ struct icpmi_ctx {
     DevArr<unsigned> d_hard;            // hard query list
     DevArr<unsigned> d_selhist;         // ICPMI_SELHIST_WORDS per reading of a batch
     DevArr<float4> d_match_pt;          // k = 1 loop: matched map point (xyz, original index bits) per query slot
+    // k = 1 loop of a single reading: three defer lists of 8 * nn_defer_wgs query slots, then one flag word per query slot (nn.hip:
+    // nn1_wg_kernel).  nn_defer / nn_defer_wgs: ICPMI_NN_DEFER (0 = off) and ICPMI_NN_DEFER_WGS as the handle found them when it was created.
+    DevArr<unsigned> d_defer;
+    bool nn_defer = true; int nn_defer_wgs = ICPMI_NN_DEFER_WGS_DEFAULT;
     // what icpmi_debug_last_matches reads: n and k of the last single registration whose matches are still in d_sidx / d_d2 (0 = none), and
     // whether they are in the tile-sorted query order (d_qindex).  Cleared by everything else that writes those buffers or moves the map.
     int64_t last_match_n = 0; int last_match_k = 0; bool last_match_sorted = false;
@@ -1495,6 +1507,8 @@ __device__ inline void init_state_dev(IcpState* st, const float* T0, unsigned se
     st->pairs = 0; st->wsum = 0; st->hard_count = 0; st->hard_total = 0; st->ticket = 0;
     for (int i = 0; i < 24; ++i) st->dbg[i] = 0;
     st->t_nn_begin = 0; st->t_nn_sum = 0; st->nn_count = 0;
+    for (int i = 0; i < 3; ++i) st->defer_count[i] = 0;
+    st->defer_served = 0; st->defer_overflow = 0;
     st->t_done = 0; // (t_start belongs to the first kernel of the head, which runs BEFORE this when the head is folded into the query sort)
 }
 
@@ -1542,6 +1556,8 @@ struct NnRequest {
     bool         sorted_k = false;     // k > 1: keep a query's k matches at its slot of the tile-sorted order
     const float* r2row    = nullptr;   // KDTreeVarDistMatcher / icpmi_knn_var: squared accept radii per query, caller's order (nn.hip: RowR2)
     int          iter     = 0;         // iteration index of this launch (> 0: seeded by the previous match)
+    unsigned*    defer    = nullptr;   // k = 1, one reading, state in query order: far-seeded queries run in defer_wgs extra workgroups of eight
+    int          defer_wgs = 0;        // (icpmi_ctx::d_defer and its layout; null = every query stays in its home workgroup)
     BatchArgs    batch{};              // nscan > 1: the readings of a batch (loop_run_batch); otherwise the launch's one reading of n points
 };
 struct NnOutcome {

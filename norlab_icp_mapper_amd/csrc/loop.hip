@@ -1060,6 +1060,9 @@ static int acc_blocks(int64_t count, int bt = 256)
     return (int)(nb < 1 ? 1 : (nb > cap ? cap : nb));
 }
 
+// words of icpmi_ctx::d_defer for a reading of n points: three lists of eight entries per helper workgroup, one flag per query slot
+static size_t defer_words(const icpmi_ctx* c, int64_t n) { return (size_t)3 * 8 * (size_t)c->nn_defer_wgs + (size_t)n + 1; }
+
 // everything the loop's launches for chain lc write to: n = points per slice, nscan slices (a single registration: one slice of n points).
 // The VarTrimmedDist scratch is reserved here too, so that enqueue_selection cannot fail (such a chain never takes a batch).
 icpmi_status ensure_loop_buffers(icpmi_ctx* c, int64_t n, const LoopCfg& lc, int nscan)
@@ -1069,6 +1072,11 @@ icpmi_status ensure_loop_buffers(icpmi_ctx* c, int64_t n, const LoopCfg& lc, int
     if (c->d_d2.ensure(c, cnt) != ICPMI_OK) return ICPMI_ERR_HIP;
     if (c->d_hard.ensure(c, (size_t)n * nscan + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
     if (lc.k == 1 && c->d_match_pt.ensure(c, (size_t)n * nscan + 1) != ICPMI_OK) return ICPMI_ERR_HIP;
+    if (lc.k == 1 && nscan == 1 && c->nn_defer) { // the k = 1 matcher's defer lists and flags (nn.hip: nn1_wg_kernel); a new block starts zeroed
+        bool fresh = false;
+        if (c->d_defer.ensure(c, defer_words(c, n), &fresh) != ICPMI_OK) return ICPMI_ERR_HIP;
+        if (fresh) HIP_TRY(c, hipMemsetAsync(c->d_defer, 0, c->d_defer.capacity() * sizeof(unsigned), c->stream));
+    }
     if (c->d_selhist.ensure(c, (size_t)ICPMI_SELHIST_WORDS * nscan) != ICPMI_OK) return ICPMI_ERR_HIP;
     return selection_reserve(c, lc, n * lc.k);
 }
@@ -1156,6 +1164,11 @@ NnRequest loop_request(icpmi_ctx* c, const LoopCfg& lc, const BatchArgs& ba, con
     req.sorted_k = lc.k > 1;
     req.r2row = d_r2row;
     req.batch = ba;
+    // (one reading, and only behind an ensure_loop_buffers that reserved the lists for it: a batch keeps every query in its home workgroup)
+    if (lc.k == 1 && ba.nscan <= 1 && c->nn_defer && c->d_defer.get() && c->d_defer.capacity() >= defer_words(c, ba.n[0])) {
+        req.defer = c->d_defer.get();
+        req.defer_wgs = c->nn_defer_wgs;
+    }
     return req;
 }
 
@@ -1291,7 +1304,8 @@ static uint64_t loop_sig(const icpmi_ctx* c, const LoopCfg& lc, const NnRequest&
     uint64_t sig = fnv(&lc, sizeof lc, 1469598103934665603ull);
     const void* ptrs[] = {d_scan, d_normals3, c->d_qkeys, c->d_qtile, c->d_reading, c->d_read_normals, c->d_sidx, c->d_d2, c->d_hard, c->d_state, c->d_match_pt,
                           c->d_qsorted, c->d_qindex, c->d_map_sorted, c->d_normals_sorted, c->d_cell_start, c->d_selhist, req.r2row,
-                          c->scratch[0], c->scratch[1], c->scratch[2], c->scratch[3], c->scratch[4]}; // (VarTrimmedDist passes)
+                          c->scratch[0], c->scratch[1], c->scratch[2], c->scratch[3], c->scratch[4], // (VarTrimmedDist passes)
+                          req.defer};
     sig = fnv(ptrs, sizeof ptrs, sig);
     sig = fnv(&c->grid, sizeof c->grid, sig);
     sig = fnv(&c->map_epoch, sizeof c->map_epoch, sig);

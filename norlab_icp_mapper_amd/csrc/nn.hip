@@ -517,8 +517,20 @@ __global__ __launch_bounds__(64 * NW) NN1_WAVES_ATTR void nn1_wg_kernel(const fl
                                                      const float* __restrict__ Tptr, GridLevels L, R maxr, int* __restrict__ out_sidx,
                                                      float* __restrict__ out_d2, IcpState* __restrict__ st, unsigned* __restrict__ hard,
                                                      unsigned* __restrict__ hist0, float4* __restrict__ match_pt,
-                                                     const uint4* __restrict__ ltab_g, int unseeded_lev, int seed_pre, float inv1e, float err2)
+                                                     const uint4* __restrict__ ltab_g, int unseeded_lev, int seed_pre, float inv1e, float err2,
+                                                     unsigned* __restrict__ defer, int defer_wgs)
 {
+    // DEFERRAL (SELF launches of a single reading's loop, defer != nullptr).  A query whose seeded search ended above level 0 -- its previous
+    // match lies farther away than a level-0 block reaches: new ground, something that moved, a pose that stalled -- brings 100 ... 430
+    // candidates against a median of 20, and such queries are neighbours in tile order: a few home workgroups hold most of them and end
+    // long after the rest of the launch.  The tail below puts such a query on the NEXT launch's list; there its home workgroup skips it and
+    // one of the defer_wgs helper workgroups in FRONT of the grid (blockIdx.x < defer_wgs, eight list entries in its first eight slots, the
+    // body as it is) runs it.  A query's result depends on its own seed, level and radius alone, the winner is a minimum over unique keys
+    // and the histograms are integer atomics: every output keeps its bits.
+    //   defer[0 .. 3 cap): three lists of cap = 8 defer_wgs query slots; launch i (= st->iter) serves list i % 3, appends to list (i + 1) % 3
+    //   and zeroes the count of list (i + 2) % 3 (IcpState::defer_count), which the launch before served and the next one appends to;
+    //   defer[3 cap + q]: the flag of query slot q = (the launch it is deferred in).  Its home workgroup of launch i skips q when the flag is
+    //   i, or i + 1: only q's helper of THIS launch can have written that already.  Launch 0 serves no list and writes every flag.
     // inv1e = 1 / (1 + epsilon), err2 = (1 + epsilon)^2 (both exactly 1 for the exact search: a multiplication by 1.0f changes no bit): libnabo's
     // `new_rd * maxError2 < heap.headValue()` -- what lies farther than (best so far) / (1 + epsilon) is not visited (KDTreeMatcher's epsilon)
     static_assert(NW == 3 || NW == 4, "waves per workgroup");
@@ -571,20 +583,40 @@ __global__ __launch_bounds__(64 * NW) NN1_WAVES_ATTR void nn1_wg_kernel(const fl
     }
 #endif
     const int wgs = (int)((((long long)n + Q - 1) / Q + 7) / 8 * 8);
-    if ((int)blockIdx.x >= wgs) return;
-    const int lb = xcd_block(blockIdx.x, wgs); // the workgroup's queries
+    const int nhelp = (SELF && defer) ? defer_wgs : 0; // helper workgroups in front of the grid
+    const int hb = (int)blockIdx.x - nhelp;            // the home workgroup's number; < 0: a helper
+    if (hb >= wgs) return;
+    const bool helper = SELF && hb < 0;
+    const unsigned dcap = 8u * (unsigned)nhelp;        // entries per defer list
+    const int lb = xcd_block((unsigned)hb, wgs); // the workgroup's queries (a helper, hb < 0: unsigned arithmetic on a number it never uses -- it takes qi from its list below)
     const int slot = lane;
-    const int qi = lb * Q + slot;
-    const bool active = w0 && qi < n; // only wave 0 owns queries
+    int qi = lb * Q + slot;
+    bool mine = qi < n;
+    if (SELF && helper) { // list entries 8 h ... 8 h + 7 of this launch's list in the first eight slots; nothing to serve: leave at once
+        const int it = st->iter;
+        if (st->done) return;
+        if (blockIdx.x == 0 && threadIdx.x == 0) nn_stamp_open(st); // (device clock of this launch: common.h)
+        if (it == 0) return;
+        const unsigned li = (unsigned)it % 3u, e0 = 8u * blockIdx.x;
+        unsigned cnt = st->defer_count[li];
+        cnt = cnt < dcap ? cnt : dcap;
+        if (e0 >= cnt) return;
+        mine = lane < 8 && e0 + (unsigned)lane < cnt;
+        qi = (int)defer[li * dcap + (mine ? e0 + (unsigned)lane : e0)];
+    }
+    bool active = w0 && mine; // only wave 0 owns queries
     float4 r = make_float4(0.f, 0.f, 0.f, 1.f);
     int orig = 0, sp_kept = -1;
+    unsigned dflag = 0;
     float4 qs_kept = make_float4(0.f, 0.f, 0.f, 0.f);
     if (w0) { // (a wave-uniform branch: the other waves go straight to the barrier)
         r = ld_stream(queries + (active ? qi : 0));
         orig = match_pt ? qi : (qindex ? qindex[active ? qi : 0] : qi);
         if (match_pt) { sp_kept = ld_stream(out_sidx + (active ? qi : 0)); qs_kept = ld_stream(match_pt + (active ? qi : 0)); }
+        if (SELF && defer && !helper) dflag = defer[3u * dcap + (unsigned)(active ? qi : 0)];
     }
     const int st_done = st->done, st_iter = st->iter;
+    if (SELF && defer && !helper && st_iter > 0 && (dflag == (unsigned)st_iter || dflag == (unsigned)st_iter + 1u)) active = false; // its helper runs it
     uint4 ltab_mine = make_uint4(0u, 0u, 0u, 0u);
     if (tid < ICPMI_MAXLEV * 4) ltab_mine = ltab_g[tid];
     float3 p = make_float3(0.f, 0.f, 0.f);
@@ -593,16 +625,25 @@ __global__ __launch_bounds__(64 * NW) NN1_WAVES_ATTR void nn1_wg_kernel(const fl
         else p = make_float3(r.x, r.y, r.z);
     }
     if (st_done) return;
-    if (blockIdx.x == 0 && threadIdx.x == 0) nn_stamp_open(st); // (device clock of this launch: common.h)
+    if (blockIdx.x == 0 && threadIdx.x == 0 && !helper) nn_stamp_open(st); // (device clock of this launch: common.h)
+    if (SELF && defer && hb == 0 && threadIdx.x == 0) { // the list this launch serves is final: count it; the next launch appends to the one that is cleared
+        if (st_iter > 0) {
+            const unsigned cnt = st->defer_count[(unsigned)st_iter % 3u];
+            if (cnt) { st->defer_served += cnt < dcap ? cnt : dcap; st->defer_overflow += cnt < dcap ? 0u : cnt - dcap; }
+        }
+        st->defer_count[((unsigned)st_iter + 2u) % 3u] = 0u;
+    }
     if (tid < ICPMI_MAXLEV * 4) ltab[tid] = ltab_mine;
     if (hist0) {
         for (int t = tid; t < 256; t += NT) lh[t] = 0;
         // the builder of level 0 clears level 1 of the previous iteration (loop.hip, fused selection)
+        if (!helper) {
 #if ICPMI_WT_CLEAR
-        clear_words_wt(hist0 + ICPMI_S2_C1, 256 + 65536, (int64_t)blockIdx.x * NT + tid, (int64_t)wgs * NT);
+            clear_words_wt(hist0 + ICPMI_S2_C1, 256 + 65536, (int64_t)(unsigned)hb * NT + tid, (int64_t)wgs * NT); // (a home workgroup: hb >= 0)
 #else
-        for (int gt = blockIdx.x * NT + tid; gt < 256 + 65536; gt += wgs * NT) hist0[ICPMI_S2_C1 + gt] = 0; // (the workgroups of THIS reading: a batch launches the grid of its largest)
+            for (int gt = hb * NT + tid; gt < 256 + 65536; gt += wgs * NT) hist0[ICPMI_S2_C1 + gt] = 0; // (the workgroups of THIS reading: a batch launches the grid of its largest)
 #endif
+        }
     }
     const bool allow_self = SELF;
 
@@ -759,6 +800,21 @@ __global__ __launch_bounds__(64 * NW) NN1_WAVES_ATTR void nn1_wg_kernel(const fl
             const unsigned hslot = atomicAdd(&st->hard_count, 1u);
             hard[hslot] = (unsigned)(match_pt ? qi : (qindex ? qindex[qi] : qi)); // the brute pass works on the order the state is kept in
         }
+    }
+    if (SELF && defer && w0) { // mark: a search that ended above level 0 goes to a helper of the next launch, while its list has room
+        const bool heavy = writer && lev >= 1;
+        const unsigned long long hm = __ballot(heavy);
+        bool put = false;
+        if (hm) { // one aggregated atomic per workgroup that has any heavy query
+            const unsigned li = ((unsigned)st_iter + 1u) % 3u;
+            unsigned base = 0;
+            if (lane == 0) base = atomicAdd(&st->defer_count[li], (unsigned)__popcll(hm));
+            base = (unsigned)__builtin_amdgcn_readfirstlane((int)base);
+            const unsigned pos = base + (unsigned)__popcll(hm & ((1ull << lane) - 1ull));
+            put = heavy && pos < dcap;
+            if (put) { defer[li * dcap + pos] = (unsigned)qi; defer[3u * dcap + (unsigned)qi] = (unsigned)st_iter + 1u; }
+        }
+        if (st_iter == 0 && writer && !put) defer[3u * dcap + (unsigned)qi] = 0u; // (launch 0 leaves no flag of an earlier registration behind)
     }
 #ifdef ICPMI_NN_TIMING
     // the workgroup's timeline slot first: nothing that other workgroups share (nn_timing_flush's atomics) stands between the stores and the stamps
@@ -1433,9 +1489,14 @@ static icpmi_status nn_launch_k1(icpmi_ctx* c, const NnRequest& req, const float
     // fresh own-row scan: that launch starts with the own-row pass at level 0 (seed_pre), the later ones go straight to their seed
     const bool seeded = req.iter > 0 && allow_self;
     const int seed_pre = (seeded && req.iter > 1) ? 0 : 1;
+    // far-seeded queries run in helper workgroups in front of the grid (nn1_wg_kernel): the loop of ONE reading whose state is kept in query
+    // order.  A batch would need lists per reading: deferral stays off for it.
+    unsigned* df = (mp && allow_self && !batch && req.defer_wgs > 0) ? req.defer : nullptr;
+    const int helpers = df ? req.defer_wgs : 0;
 #define LAUNCH_WG(S_)                                                                                                           \
-    hipLaunchKernelGGL((nn1_wg_kernel<4, S_, decltype(maxr)>), dim3((int)(((n + 63) / 64 + 7) / 8 * 8), ba.nscan), dim3(256), 0, c->stream,    \
-                       q, qi, ba, d_T, c->levels, maxr, d_sidx, d_d2, d_state, c->d_hard, h0, mp, c->d_lvl_tab, unseeded_lev, seed_pre, lc.inv1e, lc.err2)
+    hipLaunchKernelGGL((nn1_wg_kernel<4, S_, decltype(maxr)>), dim3((int)(((n + 63) / 64 + 7) / 8 * 8) + helpers, ba.nscan), dim3(256), 0, c->stream,    \
+                       q, qi, ba, d_T, c->levels, maxr, d_sidx, d_d2, d_state, c->d_hard, h0, mp, c->d_lvl_tab, unseeded_lev, seed_pre, lc.inv1e, lc.err2, \
+                       df, helpers)
     with_accept_radius(req, lc, nullptr, [&](auto maxr) { if (allow_self) LAUNCH_WG(true); else LAUNCH_WG(false); });
 #undef LAUNCH_WG
     if (needs_hard) {

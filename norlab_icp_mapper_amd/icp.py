@@ -2081,6 +2081,8 @@ class ICPSequence:
         return np.array(sums[:], dtype=np.float64), np.array(lim[:], dtype=np.float32), np.float32(rs.value), np.float32(vt.value)
 
     def debugCounters(self):
+        """icpmi_debug_counters: 24 diagnostic words of the last registration (include/icpmi.h; 10 / 11: queries the k = 1 matcher's helper
+        workgroups ran / far-seeded queries that found the defer list full)."""
         out = (C.c_uint64 * 24)()
         self._check(self._lib.icpmi_debug_counters(self._h, out))
         return list(out)
